@@ -2,7 +2,7 @@
 """Headline benchmark: posterior samples/sec of the spatial SEIR Metropolis-within-Gibbs
 sampler on the 380-LAD x 365-day UK workload (BASELINE.json `metric`).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one sweep = one posterior draw of every chain on this GPU: an HMC
 update of the P=750 parameters (16 leapfrogs = 17 gradient evaluations) plus
@@ -16,6 +16,11 @@ no data-path collective (weak scaling: --chains-per-gpu chains on every GPU).
 The timed region starts with the chain state resident in HBM; the burst
 buffer's device->host copy and HDF5 write happen between bursts and are
 reported separately (`pcie_inclusive_samples_per_sec`), never as `value`.
+
+A plain run sets up, warms up, times the K steps and prints the headline.  Everything
+else the benchmark measures (the roofline and per-kernel timings, log-prob evaluation
+rates, PCIe-inclusive rates, more chains per GPU, BASELINE.json's other configurations,
+the CLI end to end, the CPU baseline) runs only with --full.
 
 Rank 0 prints ONE JSON line (see README "Benchmark").
 """
@@ -65,7 +70,45 @@ def parse():
                     help="untimed sweeps run back to back before the timed region so that a short --steps run is "
                          "measured at steady clocks (a fresh box ramps for a few hundred ms)")
     ap.add_argument("--seed", type=int, default=20210101)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else the line can carry (roofline, kernel timings, "
+                         "evaluation rates, egress, chains scaling, configs, CLI, CPU baseline; the --no-* options above "
+                         "leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's chains) to DIR/<name>.npy (see dump_outputs)")
     return ap.parse_args()
+
+
+DUMP_BUDGET = 64_000_000          # bytes: all files of --dump-outputs together
+
+
+def dump_outputs(out_dir, tr, seed):
+    """What the timed path hands its caller for its last sweep: that sweep's draws and kernel results for this rank's
+    chains (`ChainSampler.read_trace`), one .npy per array, float64 (float32 for event counts and accept flags).  The
+    inputs depend on the command line alone, so two builds can be compared file for file.  If the event counts would
+    take the files past DUMP_BUDGET, only a fixed, seeded sample of the regions is written: `events` holds those rows,
+    `events_regions` their indices."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {"theta": tr.theta[0],
+            "hmc_is_accepted": tr.hmc["is_accepted"][0].astype(np.float32),
+            "hmc_target_log_prob": tr.hmc["target_log_prob"][0],
+            "hmc_step_size": tr.hmc["step_size"][0]}
+    for key, mv in tr.moves.items():
+        name = key.replace("/", "_").replace("->", "")                     # "move/S->E" -> "move_SE"
+        arrs[name + "_is_accepted"] = mv["is_accepted"][0].astype(np.float32)
+        arrs[name + "_target_log_prob"] = mv["target_log_prob"][0]
+        arrs[name + "_proposed_delta"] = mv["proposed_delta"][0].astype(np.float64)
+    ev = tr.events[0].astype(np.float32)                                    # [B, M, T, 3]
+    room = DUMP_BUDGET - sum(x.nbytes for x in arrs.values()) - 128 * (len(arrs) + 2)   # (.npy headers)
+    if ev.nbytes > room:
+        M = ev.shape[1]
+        n_keep = (room - 8 * M) // (ev.nbytes // M)
+        rows = np.sort(np.random.default_rng(seed).choice(M, n_keep, replace=False))
+        ev = np.ascontiguousarray(ev[:, rows])
+        arrs["events_regions"] = rows.astype(np.float64)
+    arrs["events"] = ev
+    for name, x in arrs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(x))
 
 
 def cpu_baseline(cov, init, events, u0, n_sweeps, seed, cores=None):
@@ -281,12 +324,11 @@ def main():
     sampler.set_adaptation(adapt_step_size=False)
     sampler.set_kernel(step_size=pooled)
 
-    # warm-up steps, then the timed region
-    sampler.reset_trace()
-    sampler.run(W)
-    model.sync()
     # spin-up (untimed): keep the GPU busy until it holds its steady clock; with the default
-    # --steps the timed region is only ~0.1 s and would otherwise sit on the clock ramp
+    # --steps the timed region is only ~0.1 s and would otherwise sit on the clock ramp.  How many sweeps that takes
+    # depends on the box, so the chains go back to the snapshot taken before it: what the timed steps compute
+    # depends on the command line alone (--dump-outputs).
+    sampler.snapshot(0)
     spin_sweeps, t_spin = 0, time.perf_counter()
     while time.perf_counter() - t_spin < a.spinup_seconds:
         # bursts of 100 sweeps whatever K is (sweeps beyond the trace capacity are simply not recorded): with K-sweep
@@ -296,6 +338,11 @@ def main():
         sampler.run(100)
         model.sync()
         spin_sweeps += 100
+    sampler.restore(0)
+    # warm-up steps, then the timed region
+    sampler.reset_trace()
+    sampler.run(W)
+    model.sync()
     sampler.reset_trace()
     if world > 1:
         dist.barrier()
@@ -309,6 +356,37 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = D.max_over_ranks(time.perf_counter() - t0, device=local)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, sampler.read_trace(1, first=K - 1), a.seed)
+
+    M, T, P = cov.M, cov.T, model.P
+    out = {
+        "metric": {"uk380": "posterior samples/sec, 380-LAD UK SEIR", "ni11": "posterior samples/sec, 11-LAD NI SEIR",
+                   "syn2048": "posterior samples/sec, synthetic 2048-region x 730-day SEIR"}[a.workload],
+        "value": world * B * K / elapsed,
+        "unit": "posterior samples/sec",
+        "n_gpus": world, "steps": K, "warmup": W,
+        "ms_per_step": 1e3 * elapsed / K,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64 (mobility contraction: fp32 MFMA)" if f32 else "f64", "data": "synthetic",
+        "config": {"workload": f"{a.workload}: M={M} LADs x T={T} days, P={P} parameters",
+                   "chains_per_gpu": B, "chains_total": world * B,
+                   "sweep": "HMC(16 leapfrogs) + 5 x [S->E move, E->I move, S->E occult, E->I occult]",
+                   "mcmc": MCMC_CONFIG, "draws_recorded": "theta + events[M,T,3] (uint16 counts) + kernel results per sweep",
+                   "parallelism": f"chains sharded over {world} GPU(s), no data-path collective"},
+        "spinup_sweeps": spin_sweeps,
+        "hip_event_ms_per_step": ev_ms / K,
+        "step_size": pooled,
+    }
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        sampler.close()
+        model.close()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # draws leave the device between bursts: D2H of the whole burst buffer (PCIe-inclusive rate)
     t1 = time.perf_counter()
@@ -366,7 +444,6 @@ def main():
                 lm_, ll_, le_ = sx_.time_leapfrog(100)
                 if ll_ == 1 and le_ == leap_evals:
                     leap_noend_ms = lm_
-    M, T, P = cov.M, cov.T, model.P
     alg_bytes = alg_bytes_per_eval(M, T, P, B)
     achieved = leap_evals * alg_bytes / (leap_ms * 1e-3) / 1e9
     achieved_k_se = alg_bytes / (grad_ms * 1e-3) / 1e9
@@ -606,20 +683,7 @@ def main():
                                        "epidemic; 2 - 15 s observed)", "wall_s": time.perf_counter() - t_cfg})
 
     if rank == 0:
-        out = {
-            "metric": {"uk380": "posterior samples/sec, 380-LAD UK SEIR", "ni11": "posterior samples/sec, 11-LAD NI SEIR",
-                       "syn2048": "posterior samples/sec, synthetic 2048-region x 730-day SEIR"}[a.workload],
-            "value": world * B * K / elapsed,
-            "unit": "posterior samples/sec",
-            "n_gpus": world, "steps": K, "warmup": W,
-            "ms_per_step": 1e3 * elapsed / K,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64 (mobility contraction: fp32 MFMA)" if f32 else "f64", "data": "synthetic",
-            "config": {"workload": f"{a.workload}: M={M} LADs x T={T} days, P={P} parameters",
-                       "chains_per_gpu": B, "chains_total": world * B,
-                       "sweep": "HMC(16 leapfrogs) + 5 x [S->E move, E->I move, S->E occult, E->I occult]",
-                       "mcmc": MCMC_CONFIG, "draws_recorded": "theta + events[M,T,3] (uint16 counts) + kernel results per sweep",
-                       "parallelism": f"chains sharded over {world} GPU(s), no data-path collective"},
+        out.update({
             "roofline": {"kernel": (f"k_leap<TSM,NTC,NST,RW> (persistent: {leap_evals} of the sweep's 17 gradient evaluations in one launch -- the "
                                     "whole HMC trajectory: per evaluation the S->E term's gradient sums of all chains "
                                     "from register-resident cells (and its value at the two end points), then the chunk roles' leapfrog "
@@ -661,16 +725,14 @@ def main():
                                               "traffic": traffic_k_se},
                          "frac_time_weighted_17": (17 * alg_bytes / ((leap_ms + max(0, 17 - leap_evals) * grad_ms) * 1e-3) / 1e9) / HBM_PEAK_GBPS},
             "roofline_stateless": stateless,
-            "spinup_sweeps": spin_sweeps,
             "steady_state": steady,
             "log_prob_evals_per_sec": evals,
-            "hip_event_ms_per_step": ev_ms / K,
             "pcie_inclusive_samples_per_sec": (world * B * n_bursts * burst / overlapped) if overlapped else None,
             "pcie_inclusive_note": f"{n_bursts} bursts of {burst} sweeps, draws (theta, events uint16, kernel results) copied to "
                                    "page-locked host memory on a copy stream while the next burst runs",
             "pcie_serial_samples_per_sec": world * B * K / (elapsed + d2h),
-            "acceptance": acc, "step_size": pooled, "all_log_probs_finite": finite,
-        }
+            "acceptance": acc, "all_log_probs_finite": finite,
+        })
         if cli:
             out["cli_samples_per_sec"] = cli
         if scaling:

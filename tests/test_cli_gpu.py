@@ -123,7 +123,7 @@ def test_bench_starts_its_own_ranks(tmp_path):
     env.update(PYTHONPATH=H.ROOT, BENCH_SHARE_GPU="1", BENCH_DIST_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(H.ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
                         "--workload", "ni11", "--chains-per-gpu", "3", "--adapt-sweeps", "5", "--spinup-seconds", "0.05",
-                        "--no-cpu-baseline", "--no-cli", "--no-chains-scaling", "--no-egress"],
+                        "--no-cpu-baseline", "--no-cli", "--no-chains-scaling", "--no-egress", "--full"],
                        cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -136,3 +136,35 @@ def test_bench_starts_its_own_ranks(tmp_path):
     bad = subprocess.run([sys.executable, os.path.join(H.ROOT, "bench.py"), "--gpus", "2", "--steps", "2"],
                          cwd=str(tmp_path), env=dict(env, WORLD_SIZE="3", RANK="0"), capture_output=True, text=True, timeout=300)
     assert bad.returncode == 2
+
+
+def test_bench_plain_run_and_its_outputs(tmp_path):
+    """A plain `bench.py` run prints the headline alone (the extras wait for --full), and `--dump-outputs` writes what its
+    last timed step computed: the same files, bit for bit, from two runs with the same arguments -- however many untimed
+    spin-up sweeps each of them ran."""
+    import glob
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(PYTHONPATH=H.ROOT)
+    runs = []
+    for i, spin in enumerate(("0.05", "0.4")):
+        d = tmp_path / f"out{i}"
+        r = subprocess.run([sys.executable, os.path.join(H.ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                            "--workload", "ni11", "--adapt-sweeps", "5", "--spinup-seconds", spin, "--dump-outputs", str(d)],
+                           cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == 5 and out["warmup"] == 2 and out["ms_per_step"] > 0 and out["value"] > 0
+        assert out["higher_is_better"] is True and out["unit"] == "posterior samples/sec" and out["dtype"] == "f64"
+        assert "roofline" not in out and "cpu_baseline" not in out and "configs" not in out
+        files = sorted(glob.glob(str(d / "*.npy")))
+        assert sum(os.path.getsize(f) for f in files) <= 64e6
+        runs.append({os.path.basename(f): np.load(f) for f in files})
+    a, b = runs
+    assert sorted(a) == sorted(b) and "theta.npy" in a and a["events.npy"].shape == (8, 11, 32, 3)
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64), name
+        assert np.array_equal(a[name], b[name]), name
+    assert np.isfinite(a["hmc_target_log_prob.npy"]).all()

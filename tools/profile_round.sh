@@ -11,8 +11,8 @@ tag=${1:-r01}
 export TMPDIR=/tmp
 out=gpurun_out/${tag}
 rm -rf "$out"; mkdir -p "$out"
-python3 bench.py --steps 200 --warmup 20 > "$out/bench.json" 2> "$out/bench.err"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o k -- python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-chains-scaling --no-cli --no-egress \
+python3 bench.py --steps 200 --warmup 20 --full > "$out/bench.json" 2> "$out/bench.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o k -- python3 bench.py --steps 200 --warmup 20 --full --no-cpu-baseline --no-chains-scaling --no-cli --no-egress \
     > "$out/bench_under_rocprof.json" 2> "$out/stats.err"
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $c --output-format csv -d "$out/pmc_$c" -o k -- python3 tools/quick_sweep_bench.py --groups 1 --sweeps 20 \
@@ -28,7 +28,7 @@ if [ -x tools/probes/se_probe ]; then
 fi
 # 4. BASELINE config 5 (SYN-2048 x 730, 8 chains): the bench line, kernel stats of a short sampler run, and the matrix-core
 #    counters of the fp32 and fp64 contraction kernels (SQ counters only, in passes of their own)
-python3 bench.py --workload syn2048 --steps 20 --warmup 3 --adapt-sweeps 10 > "$out/bench_syn2048.json" 2> "$out/bench_syn2048.err" \
+python3 bench.py --workload syn2048 --steps 20 --warmup 3 --adapt-sweeps 10 --full > "$out/bench_syn2048.json" 2> "$out/bench_syn2048.err" \
   || echo "syn2048 bench failed (see $out/bench_syn2048.err)"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats_syn2048" -o k -- python3 tools/quick_sweep_bench.py --workload syn2048 --groups 1 --sweeps 10 \
     > "$out/stats_syn2048.log" 2>&1 || echo "syn2048 kernel stats failed"
