@@ -60,8 +60,9 @@ class SeirSimDesc(ctypes.Structure):
     ]
 
 
-ABI_VERSION = 3               # SEIR_ABI_VERSION
+ABI_VERSION = 4               # SEIR_ABI_VERSION
 OPT_DEBUG_SKEW, OPT_XCD_AFFINITY, OPT_GEMM_F32, OPT_EVAL_FORM = 0, 1, 2, 3
+ERR_HANDOFF = -4              # SEIR_ERR_HANDOFF
 MMAX = 4                      # SEIR_MMAX
 MOVE_TRACE = 2 + 4 * MMAX     # SEIR_MOVE_TRACE
 
@@ -73,7 +74,7 @@ class SeirError(RuntimeError):
 
 
 class HandoffTimeout(SeirError):
-    """A wait inside one of the persistent launches timed out (SEIR_ERR_STATE from a read of the trace): its
+    """A wait inside one of the persistent launches gave up (SEIR_ERR_HANDOFF from a read of the trace): its
     workgroups were not all resident -- something else holds part of the GPU.  `ChainSampler` recovers from it by
     itself (snapshot, restore, per-step launch forms)."""
 
@@ -183,5 +184,5 @@ def check(rc):
     if rc != 0:
         msg = load().seir_last_error()
         text = msg.decode() if msg else "?"
-        cls = HandoffTimeout if (rc == -3 and "hand-off(s) timed out" in text) else SeirError
+        cls = HandoffTimeout if rc == ERR_HANDOFF else SeirError
         raise cls(f"libseirhip call failed ({rc}): {text}", rc)

@@ -17,6 +17,7 @@
 //   sampler path int32 planes K[3] (events), St[3] (S,E,I at start of day), F fp64
 #pragma once
 #include "device_math.h"
+#include "handoff.h"
 
 namespace seir {
 
@@ -1454,16 +1455,10 @@ constexpr int EVC_STRIDE = 32;          // 64-bit words per chain: counters A an
 __device__ __forceinline__ void evc_arrive(unsigned long long *p_, int wave_s) {
     __syncthreads();                                   // vmcnt(0): this block's stores are in the XCD's L2
     const bool first = wave_s == 0 && __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u;
-    if (first) __hip_atomic_fetch_add(p_, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (first) add_l2(p_, 1ull);
 }
 __device__ __forceinline__ void evc_wait(const unsigned long long *p_, unsigned long long target, int *err) {
-    if (threadIdx.x == 0) {
-        int spins = 0;
-        while (__hip_atomic_load(p_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-            __builtin_amdgcn_s_sleep(1);
-            if (++spins > (1 << 22)) { atomicAdd(err, 1); break; }     // ~0.1 s: reported by the host, no hang
-        }
-    }
+    if (threadIdx.x == 0) hs_wait<1, 0, HS_LIMIT, HS_CALLER>([&] { return ld_l2(p_) >= target; }, err);   // counted in eval_err
     __syncthreads();
 }
 template <bool GRAD, int TN>

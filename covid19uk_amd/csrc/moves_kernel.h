@@ -16,6 +16,7 @@
 // (Round 3's k_move_pairs, at the end of this file, is the persistent form that works: 27 workgroups per chain --
 // three roles and the band -- resident for the sweep, a per-chain step barrier in place of the launch boundary.)
 #pragma once
+#include "handoff.h"
 #include "sampler_kernels.h"
 
 namespace seir {
@@ -845,71 +846,23 @@ static_assert(sizeof(PairNote) == (2 + MMAX) * sizeof(int), "k_move_pair writes 
 // agent-scope fence; the host launches band workgroups only where the XCC_ID probe allows it.  Band workgroups have
 // the highest block ids: they are placed after every role, so a waiting one never holds a slot a role needs.
 // ---------------------------------------------------------------------------------------------
-template <typename TT>
-__device__ __forceinline__ TT ld_l2(const TT *p_) { return __hip_atomic_load(p_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void move_copy_l2(Move *dst, const Move *src, int t0) {
     const int i = (int)threadIdx.x - t0;
     if (i >= 0 && i < MOVE_DW) reinterpret_cast<int *>(dst)[i] = ld_l2(reinterpret_cast<const int *>(src) + i);
 }
+// (a band workgroup's waits for the roles' tokens: thread 0)
 __device__ __forceinline__ void wait_token(const unsigned *p_, unsigned token, unsigned *late) {
-    int spins = 0;
-    while (ld_l2(p_) != token) {
-        __builtin_amdgcn_s_sleep(1);
-        ++spins;
-        // once ANY wait of the chain has timed out (its workgroups cannot all have been placed: something else holds part of
-        // the chip) every later wait of the chain gives up at its first look at the counter, every 256 polls, so that a burst
-        // that cannot complete drains in about a second instead of a second per wait (as leap_wait); the host finds the
-        // counter at the next read of the trace, fails loudly and can restore the last snapshot (seir_sampler_restore)
-        if ((spins & 255) == 0 && ld_l2(late) != 0u) break;
-        if (spins > (1 << 22)) { __hip_atomic_fetch_add(late, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }   // counted, no hang
-    }
+    hs_wait<1, HS_CHECK, HS_LIMIT, HS_CALLER>([&] { return ld_l2(p_) == token; }, late);
 }
-// Role 0's last token of a step also says which descriptor stands (Chains::mvsel): the top bit -- one round trip less for the
-// band workgroups than the token and then the word (a token is sweep * 64 + step + 1: 31 bits hold 33 million sweeps)
+// Role 0's last token of a step also says which descriptor stands (Chains::mvsel): the top bit (pair_token) -- one round
+// trip less for the band workgroups than the token and then the word
 __device__ __forceinline__ unsigned wait_token_flag(const unsigned *p_, unsigned token, unsigned *late) {
-    int spins = 0;
     unsigned v;
-    while (((v = ld_l2(p_)) & 0x7fffffffu) != token) {
-        __builtin_amdgcn_s_sleep(1);
-        ++spins;
-        if ((spins & 255) == 0 && ld_l2(late) != 0u) break;
-        if (spins > (1 << 22)) { __hip_atomic_fetch_add(late, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-    }
+    hs_wait<1, HS_CHECK, HS_LIMIT, HS_CALLER>([&] { return ((v = ld_l2(p_)) & 0x7fffffffu) == token; }, late);
     return v >> 31;
 }
-// A proposal descriptor as hand-off words (sampler_kernels.h): 60 dwords in 30 words {dword, token, dword, token}.  The band
-// workgroups used to wait for role 1's token (after its stores were acknowledged) and then copy the descriptor -- two round
-// trips behind each other; now lanes 0..29 of one wave look at their word until it shows the launch's token.
-constexpr int MOVE_LLW = (MOVE_DW + 1) / 2;
-static_assert(MOVE_LLW <= 32, "Chains::llmv holds 32 words per descriptor");
-__device__ __forceinline__ void move_store_ll(uint4 *dst, const Move *src_lds, int lane, unsigned token) {
-    if (lane < MOVE_LLW) {
-        const int *sd = reinterpret_cast<const int *>(src_lds);
-        uint4 x;
-        x.x = (unsigned)sd[2 * lane]; x.y = token;
-        x.z = 2 * lane + 1 < MOVE_DW ? (unsigned)sd[2 * lane + 1] : 0u; x.w = token;
-        dst[lane] = x;
-    }
-}
-__device__ __forceinline__ void move_wait_ll(Move *dst_lds, const uint4 *src, int lane, unsigned token, unsigned *late) {
-    // (one wave; every lane looks at a word -- the lanes beyond the descriptor at its last one)
-    const uint4 *pp[1] = {src + min(lane, MOVE_LLW - 1)};
-    u32x4 x[1];
-    int spins = 0;
-    for (;;) {
-        ll_load<1>(pp, x);
-        if (__builtin_amdgcn_ballot_w64(!ll_ok(x[0], token)) == 0ull) break;
-        __builtin_amdgcn_s_sleep(1);
-        ++spins;
-        if ((spins & 255) == 0 && ld_l2(late) != 0u) break;
-        if (spins > (1 << 22)) { if (lane == 0) __hip_atomic_fetch_add(late, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-    }
-    if (lane < MOVE_LLW) {
-        int *dd = reinterpret_cast<int *>(dst_lds);
-        dd[2 * lane] = (int)x[0].x;
-        if (2 * lane + 1 < MOVE_DW) dd[2 * lane + 1] = (int)x[0].z;
-    }
-}
+// A proposal descriptor as hand-off words (handoff.h, move_store_ll / move_wait_ll): 60 dwords in 30 words
+static_assert((MOVE_DW + 1) / 2 <= 32, "Chains::llmv holds 32 words per descriptor");
 // SOLO (k_move_pairs): the workgroup has its CU to itself and its L1 was emptied when the step began, so what it loads of
 // the planes AFTER the token that declares them final cannot be an older copy: plain loads, which a wave issues back to
 // back, where the launch-per-pair form (other workgroups of the chain may share the CU and its L1) reads past the L1
@@ -977,7 +930,7 @@ __device__ __forceinline__ void pair_band_block(const Dims &d, const Consts &c, 
     if (has_r1) {
         // the speculative role publishes its descriptor as hand-off words well before it is done (token 1): wave 1 looks for
         // them while thread 0 waits for the planes
-        if (wave == 1) move_wait_ll(&mvA, ch.llmv + ((size_t)buf * s.B + b) * 32, lane, token, ch.late + ch.late_fatal + b);
+        if (wave == 1) move_wait_ll<MOVE_DW>(reinterpret_cast<int *>(&mvA), ch.llmv + ((size_t)buf * s.B + b) * 32, lane, token, ch.late + ch.late_fatal + b);
         QSTAMP(st_slot, st_step, 2);
         __syncthreads();
     } else {
@@ -1206,10 +1159,10 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
     if (slot >= nroles) {                                  // band workgroups (the highest block ids)
         if (nband == 0) return;
         if (fin) {                                         // the closing step of k_move_pairs: they finish the sweep
-            pair_band_finish(d, c, w, s, ch, b, slot - nroles, nband, sweep0 * 64u + (unsigned)lidx + 1u, sweep0, fin & 2);
+            pair_band_finish(d, c, w, s, ch, b, slot - nroles, nband, pair_token(sweep0, lidx), sweep0, fin & 2);
             return;
         }
-        const unsigned tok = ch.sweep[b] * 64u + (unsigned)lidx + 1u;
+        const unsigned tok = pair_token(ch.sweep[b], lidx);
         const bool r1 = next.kind >= 0 && nroles >= 2, r2 = se_next.kind >= 0 && nroles == 3;
         if ((d.M + nband - 1) / nband > 2 * MVW)              // (uniform) more than 16 rows per band workgroup: four per wave
             pair_band_block<SOLO, 4>(d, c, w, s, ch, b, slot - nroles, nband, tok, r1, r2, pbuf ^ 1, slot, lidx);
@@ -1250,7 +1203,7 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
     int pre_se[PRE_RT], pre_nx[PRE_RT];
     mv_prefetch_rows(d, w, s, b, se, do_se && pre_ok, pre_se);
     mv_prefetch_rows(d, w, s, b, mine, (role == 2 || do_nx) && pre_ok, pre_nx);
-    const unsigned token = ch.sweep[b] * 64u + (unsigned)lidx + 1u;       // unique per (sweep, launch): lidx < 63
+    const unsigned token = pair_token(ch.sweep[b], lidx);
     // ... all of it issued before the first wait: the pending descriptors, k_move_delta's partial sums, the
     // own-rows parts, the pre-drawn proposal and its note -- one round trip for the whole entry, into registers (a thread
     // holds at most one word of the descriptors and one of the doubles): the uniforms of this step's proposals (Philox and
@@ -1320,7 +1273,7 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
         if (dbg & late_bit)
             for (int i = 0; i < 100; ++i) __builtin_amdgcn_s_sleep(127);   // ~0.35 ms: well inside role 0's bounded wait
         if (tid == 0 && !(dbg & absent_bit))
-            __hip_atomic_store((role == 1 ? ch.hand : ch.hand2) + b, token, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (loads done: above)
+            st_l2((role == 1 ? ch.hand : ch.hand2) + b, token);   // (loads done: above)
     }
     MvLds L{};
     int *rtl = dyn_i + M;
@@ -1364,7 +1317,8 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
         // band workgroups start from this descriptor while the log-ratio over the updated rows is still being evaluated: as
         // hand-off words, which need neither the acknowledgement of the stores nor a token
         if (nband > 0 && role == 1 && tid >= MVB - WAVE)
-            move_store_ll(ch.llmv + ((size_t)(pbuf ^ 1) * s.B + b) * 32, &sm_nx.mv, tid - (MVB - WAVE), token);
+            move_store_ll<MOVE_DW>(ch.llmv + ((size_t)(pbuf ^ 1) * s.B + b) * 32, reinterpret_cast<const int *>(&sm_nx.mv), tid - (MVB - WAVE),
+                                   token);
         // ... and its log-ratio over the rows it updates (for role 1, k_move_delta then does the band only); the F
         // band of an accepted pending update is not in F yet and is added on the fly
         const Move *fpp = (pend_acc && pendp->any_dI) ? pendp : nullptr;
@@ -1376,7 +1330,7 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
         if (nband > 0) {                                   // band workgroups: this role reads F no more, its output is in L2
             __syncthreads();
             if (tid == 0)
-                __hip_atomic_store(ch.done + (size_t)b * 2 * TAIL_STRIDE + role, token, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                st_l2(ch.done + (size_t)b * 2 * TAIL_STRIDE + role, token);
         }
         return;
     }
@@ -1384,7 +1338,7 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
         ch.fpend[b].valid = 0;
         if (nband > 0) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_store(ch.done + (size_t)b * 2 * TAIL_STRIDE + 4, token, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            st_l2(ch.done + (size_t)b * 2 * TAIL_STRIDE + 4, token);
         }
     }
     // before the first store a speculative role could mistake for the state at entry: has it fetched its totals?
@@ -1392,23 +1346,10 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
     bool late = false, late2 = false;
     auto wait_roles = [&]() {
         if (tid == 0) {
-            int spins = 0;
-            if (do_nx) {
-                while (__hip_atomic_load(ch.hand + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != token && spins < 4000) {
-                    __builtin_amdgcn_s_sleep(2);
-                    ++spins;
-                }
-            }
-            s_late = spins >= 4000 ? 1 : 0;
-            int spins2 = 0;
-            if (do_pre) {
-                while (__hip_atomic_load(ch.hand2 + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != token && spins2 < 4000) {
-                    __builtin_amdgcn_s_sleep(2);
-                    ++spins2;
-                }
-            }
-            s_late2 = spins2 >= 4000 ? 1 : 0;
-            if (spins >= 4000 || spins2 >= 4000) ch.late[b] += 1;   // visible through seir_sampler_pair_timeouts
+            const bool l1 = do_nx && hs_wait<2, 0, HS_LIMIT_ROLES, HS_NONE>([&] { return ld_l2(ch.hand + b) == token; });
+            const bool l2 = do_pre && hs_wait<2, 0, HS_LIMIT_ROLES, HS_NONE>([&] { return ld_l2(ch.hand2 + b) == token; });
+            s_late = l1; s_late2 = l2;
+            if (l1 || l2) ch.late[b] += 1;                 // visible through seir_sampler_pair_timeouts
             // relaxed polls, one acquire once the tokens are seen: this workgroup's stores below are ordered after it
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         }
@@ -1429,7 +1370,7 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
             // band workgroups prefetch what the F band needs (token 4) long before the proposal they evaluate is certified
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if (tid == MVB - WAVE)
-                __hip_atomic_store(ch.done + (size_t)b * 2 * TAIL_STRIDE + 4, token, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                st_l2(ch.done + (size_t)b * 2 * TAIL_STRIDE + 4, token);
         }
         if (pend_acc) mv_apply_rows(d, w, s, b, mv);
         if (tid == 0) {
@@ -1448,7 +1389,7 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
         // closing step of k_move_pairs: the band workgroups finish the sweep (pair_band_finish) once the planes are final
         __syncthreads();                                   // mv_apply_rows ends drained; the trace stores need not be
         if (tid == 0)
-            __hip_atomic_store(ch.done + (size_t)b * 2 * TAIL_STRIDE + 5, token, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            st_l2(ch.done + (size_t)b * 2 * TAIL_STRIDE + 5, token);
     }
     // ---- (2) the whole S->E-type update
     bool se_acc = false;
@@ -1512,7 +1453,7 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
         __syncthreads();             // a re-drawn proposal in (3) must see the state written above
         // band workgroups: the planes are final (token 5); which descriptor stands they learn from the last token
         if (nband > 0 && tid == 0)
-            __hip_atomic_store(ch.done + (size_t)b * 2 * TAIL_STRIDE + 5, token, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            st_l2(ch.done + (size_t)b * 2 * TAIL_STRIDE + 5, token);
         PSTAMP(5);
         QSTAMP(slot, lidx, 2);
     }
@@ -1578,8 +1519,7 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
     if (nband > 0) {                                       // band workgroups may go: descriptors, mvsel and fpend are in L2
         __syncthreads();
         if (tid == 0)                                      // (which descriptor stands -- Chains::mvsel -- in the token's top bit)
-            __hip_atomic_store(ch.done + (size_t)b * 2 * TAIL_STRIDE + 0, token | ((do_nx && s_conf) ? 0x80000000u : 0u), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
+            st_l2(ch.done + (size_t)b * 2 * TAIL_STRIDE + 0, token | ((do_nx && s_conf) ? 0x80000000u : 0u));
     }
 }
 
@@ -1626,7 +1566,7 @@ __device__ __forceinline__ void pair_chain_barrier(const Chains &ch, int b, unsi
     QSTAMP(st_slot, st_step, 10);
     if (threadIdx.x == 0) {
         unsigned *cnt = ch.pbar + (size_t)b * PBAR_STRIDE;
-        const unsigned old = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned old = add_l2(cnt, 1u);
         // Drop this CU's L1, so that plain loads of the next step see what other workgroups wrote in this one -- at once,
         // not when the count is complete: the launch holds ONE workgroup per CU (its LDS request, k_move_pairs_lds_bytes),
         // and from here to the end of the wait this one loads nothing but the counter, past the L1, so the cache stays empty.
@@ -1639,19 +1579,11 @@ __device__ __forceinline__ void pair_chain_barrier(const Chains &ch, int b, unsi
         // (Issued AHEAD of the arrival instead, so that the last workgroup in has the two round trips side by side: slower,
         // 0.3063 against 0.3029 ms per sweep -- the atomic queues behind the invalidate.)
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        if (old + 1u != target) {
-            int spins = 0;
-            unsigned *late = ch.late + ch.late_fatal + b;
 #ifndef PBAR_SLEEP
 #define PBAR_SLEEP 1
 #endif
-            while ((int)(ld_l2(cnt) - target) < 0) {
-                __builtin_amdgcn_s_sleep(PBAR_SLEEP);
-                ++spins;
-                if ((spins & 255) == 0 && ld_l2(late) != 0u) break;                          // (see wait_token)
-                if (spins > (1 << 22)) { __hip_atomic_fetch_add(late, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }   // counted, no hang
-            }
-        }
+        if (old + 1u != target)
+            hs_wait<PBAR_SLEEP, HS_CHECK, HS_LIMIT, HS_CALLER>([&] { return (int)(ld_l2(cnt) - target) >= 0; }, ch.late + ch.late_fatal + b);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     QSTAMP(st_slot, st_step, 11);

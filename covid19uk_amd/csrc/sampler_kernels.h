@@ -20,6 +20,7 @@
 // same definitions are implemented by the CPU oracle oracle/mcmc_oracle.py with
 // the same Philox stream, so traces are comparable draw by draw.
 #pragma once
+#include "handoff.h"
 #include "logprob_kernels.h"
 #include "philox.h"
 
@@ -136,95 +137,6 @@ struct Chains {
     double *tr_hmc;                                      // [cap][B][3]  is_accepted, target_log_prob, step_size
     double *tr_mv;                                       // [cap][B][4][NMVTR]
 };
-
-// ---------------------------------------------------------------------------------------------
-// Hand-off words (k_leap).  A value handed from one workgroup of a launch to another through the XCD's L2 used to cost the
-// producer its stores, the wait for their acknowledgement (s_waitcnt vmcnt(0), ~0.3 us), a returning atomic on the chain's
-// counter (~0.4 us) and -- for the last one in -- a flag store; the consumer a poll of the flag (a round trip, ~0.5 us) and only
-// then the loads of the values (another).  Here every value carries its own flag: a double travels as 16 bytes
-// {low word, seq, high word, seq} -- two aligned 8-byte halves, each written whole by the memory system, each with the step
-// number -- so the producer only issues its stores and the consumer's first look at the DATA is also its wait: it loads past
-// the L1 and looks again until both halves of everything it asked for show the step.  seq = the step's number over all
-// launches of the sampler with the top bit set: never the zero of a reset buffer, never the number of the step before.
-// No release / acquire anywhere: all of a chain's workgroups share one L2 (checked at creation, as for every hand-off here).
-// ---------------------------------------------------------------------------------------------
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ unsigned ll_seq(unsigned long long step) { return (unsigned)step | 0x80000000u; }
-__device__ __forceinline__ void ll_store(uint4 *p, double v, unsigned seq) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    uint4 x;
-    x.x = (unsigned)u; x.y = seq; x.z = (unsigned)(u >> 32); x.w = seq;
-    *p = x;                                                 // one global_store_dwordx4
-}
-__device__ __forceinline__ bool ll_ok(const u32x4 &x, unsigned seq) { return x.y == seq && x.w == seq; }
-__device__ __forceinline__ double ll_value(const u32x4 &x) {
-    return __longlong_as_double((long long)(((unsigned long long)x.z << 32) | (unsigned long long)x.x));
-}
-// N 16-byte loads past the L1 and the wait for them, as ONE asm block: the compiler does not count these loads, so nothing
-// may touch the destination registers between the issue and the wait
-template <int N> __device__ __forceinline__ void ll_load(const uint4 *const (&p)[N], u32x4 (&x)[N]) {
-    static_assert(N >= 1 && N <= 6, "groups of up to six");
-    if constexpr (N == 1)
-        asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(x[0]) : "v"(p[0]) : "memory");
-    else if constexpr (N == 2)
-        asm volatile("global_load_dwordx4 %0, %2, off sc1\n\tglobal_load_dwordx4 %1, %3, off sc1\n\ts_waitcnt vmcnt(0)"
-                     : "=&v"(x[0]), "=&v"(x[1]) : "v"(p[0]), "v"(p[1]) : "memory");
-    else if constexpr (N == 3)
-        asm volatile("global_load_dwordx4 %0, %3, off sc1\n\tglobal_load_dwordx4 %1, %4, off sc1\n\tglobal_load_dwordx4 %2, %5, off sc1\n\t"
-                     "s_waitcnt vmcnt(0)" : "=&v"(x[0]), "=&v"(x[1]), "=&v"(x[2]) : "v"(p[0]), "v"(p[1]), "v"(p[2]) : "memory");
-    else if constexpr (N == 4)
-        asm volatile("global_load_dwordx4 %0, %4, off sc1\n\tglobal_load_dwordx4 %1, %5, off sc1\n\tglobal_load_dwordx4 %2, %6, off sc1\n\t"
-                     "global_load_dwordx4 %3, %7, off sc1\n\ts_waitcnt vmcnt(0)"
-                     : "=&v"(x[0]), "=&v"(x[1]), "=&v"(x[2]), "=&v"(x[3]) : "v"(p[0]), "v"(p[1]), "v"(p[2]), "v"(p[3]) : "memory");
-    else if constexpr (N == 5)
-        asm volatile("global_load_dwordx4 %0, %5, off sc1\n\tglobal_load_dwordx4 %1, %6, off sc1\n\tglobal_load_dwordx4 %2, %7, off sc1\n\t"
-                     "global_load_dwordx4 %3, %8, off sc1\n\tglobal_load_dwordx4 %4, %9, off sc1\n\ts_waitcnt vmcnt(0)"
-                     : "=&v"(x[0]), "=&v"(x[1]), "=&v"(x[2]), "=&v"(x[3]), "=&v"(x[4])
-                     : "v"(p[0]), "v"(p[1]), "v"(p[2]), "v"(p[3]), "v"(p[4]) : "memory");
-    else
-        asm volatile("global_load_dwordx4 %0, %6, off sc1\n\tglobal_load_dwordx4 %1, %7, off sc1\n\tglobal_load_dwordx4 %2, %8, off sc1\n\t"
-                     "global_load_dwordx4 %3, %9, off sc1\n\tglobal_load_dwordx4 %4, %10, off sc1\n\tglobal_load_dwordx4 %5, %11, off sc1\n\t"
-                     "s_waitcnt vmcnt(0)"
-                     : "=&v"(x[0]), "=&v"(x[1]), "=&v"(x[2]), "=&v"(x[3]), "=&v"(x[4]), "=&v"(x[5])
-                     : "v"(p[0]), "v"(p[1]), "v"(p[2]), "v"(p[3]), "v"(p[4]), "v"(p[5]) : "memory");
-}
-// The consumer's wait: load, look, again -- until every lane of the wave has the step's words in all N places.  Bounded like
-// every wait of k_leap (leap_wait): a time-out is counted in the chain's fatal counter, and once that is non-zero every wait
-// of the chain gives up at its next look at it; the values are then whatever was there -- the host discards the burst.
-// (Looking again at only the places that were late, one load at a time, was slower -- 140.7 us per launch against 134.7: with
-// several tiles late, each place's round trip came behind the last one's.)
-#ifndef LEAP_ROLE_PRIO
-#define LEAP_ROLE_PRIO 3            // k_leap's role waves (see there)
-#endif
-#ifdef LL_POLL_DROP_PRIO
-#define LL_RPRIO LEAP_ROLE_PRIO
-#else
-#define LL_RPRIO -1
-#endif
-// RPRIO >= 0 (a role's waves): the wave's priority is dropped while it looks again and again, and put back to RPRIO when the
-// words are there
-template <int N, int RPRIO = -1> __device__ __forceinline__ void ll_poll(const uint4 *const (&p)[N], unsigned seq, unsigned *late, double (&v)[N]) {
-    u32x4 x[N];
-    int spins = 0;
-    for (;;) {
-        ll_load<N>(p, x);
-        bool ok = true;
-#pragma unroll
-        for (int j = 0; j < N; ++j) ok = ok && ll_ok(x[j], seq);
-        if (__builtin_amdgcn_ballot_w64(!ok) == 0ull) break;
-        if (RPRIO >= 0 && spins == 0) __builtin_amdgcn_s_setprio(0);
-#ifndef LL_POLL_SLEEP
-#define LL_POLL_SLEEP 2
-#endif
-        __builtin_amdgcn_s_sleep(LL_POLL_SLEEP);
-        ++spins;
-        if ((spins & 63) == 0 && __hip_atomic_load(late, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
-        if (spins > (1 << 19)) { if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(late, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-    }
-    if (RPRIO >= 0 && spins > 0) __builtin_amdgcn_s_setprio(RPRIO);
-#pragma unroll
-    for (int j = 0; j < N; ++j) v[j] = ll_value(x[j]);
-}
 
 __device__ inline RngKey rng_key(const SamplerCfg &s, const Chains &ch, int b) {
     return RngKey{s.k0, s.k1, (uint32_t)(s.chain0 + b), ch.sweep[b]};
@@ -949,7 +861,7 @@ __device__ __forceinline__ void role_pregather(const Dims &d, const Consts &c, c
         }
         double sv[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) sv[j] = __hip_atomic_load(spr + qc[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int j = 0; j < 8; ++j) sv[j] = ld_l2(spr + qc[j]);
         double Qs = 0.0;
 #pragma unroll
         for (int j = 0; j < 8; ++j) Qs += qv[j] * sv[j];
@@ -962,7 +874,7 @@ __device__ __forceinline__ void role_pregather(const Dims &d, const Consts &c, c
         if (role_gather_row_wave(kk) != wv || kk >= nrow) continue;
         const int mm = lane + kk * WAVE;
         const bool on = mm < d.M;
-        const double sv_ = __hip_atomic_load(spr + (on ? mm : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const double sv_ = ld_l2(spr + (on ? mm : 0));
         g[G::SX + kk * WAVE + lane] = on ? sv_ : 0.0;
     }
 }
@@ -1122,10 +1034,10 @@ __device__ __forceinline__ void hmc_chunk_role(const Dims &d, const Consts &c, c
 #endif
     __shared__ double2 ltab[LOGTAB_N];
     auto LDP = [](const double *p_) {
-        return COH ? __hip_atomic_load(p_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p_;
+        return COH ? ld_l2(p_) : *p_;
     };
     auto LDQ = [](const double *p_) {
-        return PERS ? __hip_atomic_load(p_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p_;
+        return PERS ? ld_l2(p_) : *p_;
     };
     constexpr int NC = NTC > 0 ? NTC : CT_MAXC;
     const int T = d.T, M = d.M, nmt = d.nmt;
@@ -1629,7 +1541,7 @@ __device__ __forceinline__ void hmc_chunk_role(const Dims &d, const Consts &c, c
 template <int NTC>
 __device__ __forceinline__ void hmc_final_apply(const Dims &d, const Consts &c, const Work &w, const SamplerCfg &s,
                                                 const Chains &ch, int par, int bx, int b, int lane) {
-    auto LDQ = [](const double *p_) { return __hip_atomic_load(p_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    auto LDQ = [](const double *p_) { return ld_l2(p_); };
     const int T = d.T, M = d.M, ntc = NTC > 0 ? NTC : d.ntc, nroles = ntc + d.Mp / WAVE, ntile = d.nmt * ntc;
     const int oT = 6 - 1, oM = 6 + T - 1;
     double *q = ch.q + (size_t)b * d.Pp, *q0 = ch.q0 + (size_t)b * d.Pp, *var = ch.var + (size_t)b * d.Pp;
@@ -1819,20 +1731,19 @@ void k_se_chunk(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, int par, unsi
         // 10 first role past its wait, 11 last role past its wait, 12 last role done, 13 first role start -- of the launches
         // with par = 1 since the last reset (the probe runs trajectories of three leapfrog steps: exactly one such launch)
         unsigned long long *stp = ch.tail + (size_t)(d.b0 + bz) * TAIL_STRIDE + 8;
-        if (threadIdx.x == 0 && par == 1) __hip_atomic_fetch_min(stp + 0, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (threadIdx.x == 0 && par == 1) min_l2(stp + 0, __builtin_amdgcn_s_memrealtime());
 #endif
         se_tile<true, 1, TSM>(d, c, w, tile % d.ntc, tile / d.ntc, bz);
         __syncthreads();                               // vmcnt(0): this tile's partial sums are in the XCD's L2
         if (threadIdx.x == 0) {
-            const unsigned long long old = __hip_atomic_fetch_add(ch.tail + (size_t)(d.b0 + bz) * TAIL_STRIDE, 1ull, __ATOMIC_RELAXED,
-                                                                  __HIP_MEMORY_SCOPE_AGENT);
+            const unsigned long long old = add_l2(ch.tail + (size_t)(d.b0 + bz) * TAIL_STRIDE, 1ull);
             // the last tile of the chain raises the chain's flag, in a line of its own: the roles poll that one -- polling
             // the counter's line, which 144 tiles are still adding to, cost 11 us per sweep
             if (old + 1 == target)
-                __hip_atomic_store(ch.tail + TAIL_FLAG_AT(s.B, d.b0 + bz), target, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                st_l2(ch.tail + TAIL_FLAG_AT(s.B, d.b0 + bz), target);
         }
 #ifdef TAIL_STAMPS
-        if (threadIdx.x == 0 && par == 1) __hip_atomic_fetch_max(stp + 1, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (threadIdx.x == 0 && par == 1) max_l2(stp + 1, __builtin_amdgcn_s_memrealtime());
 #endif
         return;
     }
@@ -1848,39 +1759,30 @@ void k_se_chunk(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, int par, unsi
     const unsigned long long *flag = ch.tail + TAIL_FLAG_AT(s.B, b);   // raised by the chain's last tile
 #ifdef TAIL_STAMPS
     unsigned long long *stp = ch.tail + (size_t)b * TAIL_STRIDE + 8;
-    if (threadIdx.x == 0 && par == 1) __hip_atomic_fetch_min(stp + 5, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x == 0 && par == 1) min_l2(stp + 5, __builtin_amdgcn_s_memrealtime());
 #endif
     // traj (hmc_mode 6: the whole trajectory as L + 1 of these launches): 1 = the trajectory's first step (the momentum is
     // drawn here, the start point read from Chains::q0: k_hmc_step<0>'s work in chunk form), 2 = the step after it, 3 = the last
     // half kick (the accept test follows in k_hmc_final); 0 = an inner step, the only kind the other forms launch
     hmc_chunk_role<NTC, true, false, true>(d, c, w, s, ch, par, role, b, [&] {
-        int spins = 0;
         // back off before the first look: since the roles fit beside all the tiles (96 VGPRs, five waves per SIMD) they
         // are resident from the start of the launch, and no tile phase of this size is shorter than the ~0.9 us slept
         // through.  (While the roles still polled the counters' own lines, 96 polling waves made the launch slower than
         // at four waves per SIMD, 12.7 us against 12.1, and a 1.8 us sleep was worth 0.9 us; with the flag lines the
         // launch takes 11.0 us and the sleep is worth little.)
         if (ntile >= 32) __builtin_amdgcn_s_sleep(TAIL_BACKOFF);
-        while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-            __builtin_amdgcn_s_sleep(1);
-            ++spins;
-            if ((spins & 255) == 0 && __hip_atomic_load(ch.late + ch.late_fatal + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;   // see leap_wait
-            if (spins > (1 << 22)) {                   // never seen; counted like k_move_pair's time-outs, no hang
-                if (threadIdx.x == 0) __hip_atomic_fetch_add(ch.late + ch.late_fatal + b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                break;
-            }
-        }
+        hs_wait<1, HS_CHECK, HS_LIMIT, HS_THREAD0>([&] { return ld_l2(flag) >= target; }, ch.late + ch.late_fatal + b);
 #ifdef TAIL_STAMPS
         if (threadIdx.x == 0 && par == 1) {
             const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-            __hip_atomic_fetch_min(stp + 2, now, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_max(stp + 3, now, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            min_l2(stp + 2, now);
+            max_l2(stp + 3, now);
         }
 #endif
     }, -1, nullptr, nullptr, traj);
 #ifdef TAIL_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (threadIdx.x == 0 && par == 1) __hip_atomic_fetch_max(stp + 4, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x == 0 && par == 1) max_l2(stp + 4, __builtin_amdgcn_s_memrealtime());
 #endif
 }
 
@@ -1931,8 +1833,8 @@ constexpr int LEAP_CH = 1024;        // 64-bit words of Chains::leap per chain
 // for the tables" (0, 1) and "counted in" (2, 3), min / max over the roles of "past the wait for the tiles" (4, 5) and "done" (6, 7)
 // (LEAP_STAMPS=2; they are atomics on one line per chain and stretch what they time: =1 keeps only the probes below)
 #if LEAP_STAMPS >= 2
-#define LSTAMP_MIN(k) __hip_atomic_fetch_min(ch.leap_st + ((size_t)b * 16 + (it & 15)) * 8 + (k), __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define LSTAMP_MAX(k) __hip_atomic_fetch_max(ch.leap_st + ((size_t)b * 16 + (it & 15)) * 8 + (k), __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define LSTAMP_MIN(k) min_l2(ch.leap_st + ((size_t)b * 16 + (it & 15)) * 8 + (k), __builtin_amdgcn_s_memrealtime())
+#define LSTAMP_MAX(k) max_l2(ch.leap_st + ((size_t)b * 16 + (it & 15)) * 8 + (k), __builtin_amdgcn_s_memrealtime())
 #else
 #define LSTAMP_MIN(k) do {} while (0)
 #define LSTAMP_MAX(k) do {} while (0)
@@ -1953,19 +1855,10 @@ constexpr int LEAP_CH = 1024;        // 64-bit words of Chains::leap per chain
 #define LALL(k) do {} while (0)
 #define RPROBE(k) do {} while (0)
 #endif
-// A wait of k_leap.  Every wait is bounded (~1 s), and once ANY wait of the chain has timed out -- its workgroups cannot
-// all have been resident: something else holds part of the chip, e.g. a second process with a launch of the same kind -- the
-// chain's fatal counter is non-zero and every later wait of the chain gives up at its first look at it (every 256 polls), so
-// that a launch that cannot complete drains in about a second instead of a second per step; the host finds the counter at
-// the next read of the trace and fails loudly (check_handoffs).
+// A wait of k_leap for a flag (handoff.h: a time-out means its workgroups cannot all have been resident -- something else
+// holds part of the chip, e.g. a second process with a launch of the same kind)
 __device__ __forceinline__ void leap_wait(const unsigned long long *flag, unsigned long long target, unsigned *late) {
-    int spins = 0;
-    while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-        __builtin_amdgcn_s_sleep(1);
-        ++spins;
-        if ((spins & 255) == 0 && __hip_atomic_load(late, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
-        if (spins > (1 << 21)) { if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(late, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-    }
+    hs_wait<1, HS_CHECK, HS_LIMIT_LEAP, HS_LANE0>([&] { return ld_l2(flag) >= target; }, late);
 }
 
 // NST: 16-row gradient tiles per workgroup (the same day chunk, consecutive row tiles) -- wave w owns rows 4w..4w+3 of each of
@@ -1997,7 +1890,7 @@ __device__ __forceinline__ void leap_tile(const Dims &d, const Consts &c, const 
     __shared__ double tabbuf[WAVE + 2 * NST * TM + 8];
     constexpr int TB_EB = WAVE, TB_SP = WAVE + NST * TM, TB_PSI = WAVE + 2 * NST * TM;
     static_assert(NST * TM <= WAVE, "one wave fetches the rows' table entries");
-    auto LDP = [](const double *p_) { return __hip_atomic_load(p_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    auto LDP = [](const double *p_) { return ld_l2(p_); };
     debug_skew(d);
     const int b = d.b0 + bz, wave0 = threadIdx.x >> 6, lane0 = threadIdx.x & 63;
     const int wave = wave0;                                      // (ahead of the step loop; inside it: an opaque copy)
@@ -2301,8 +2194,8 @@ __device__ __forceinline__ void leap_tile(const Dims &d, const Consts &c, const 
         LPROBE(5);
         if (threadIdx.x == 0) {
             const unsigned long long stepno = stepno_;
-            const unsigned long long old = __hip_atomic_fetch_add(cnt1, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (old + 1 == stepno * shard_size) __hip_atomic_store(flag1, stepno, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const unsigned long long old = add_l2(cnt1, 1ull);
+            if (old + 1 == stepno * shard_size) st_l2(flag1, stepno);
             LSTAMP_MIN(2); LSTAMP_MAX(3);
             LPROBE(6);                                           // counted in (the atomic has returned)
             LALL(2);
@@ -2387,15 +2280,10 @@ void k_leap(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, int par0, int nst
         LeapLL ll;
         ll.seq_in = ll_seq(stepno); ll.seq_out = ll_seq(rstep); ll.pb = (int)(stepno & 1ull); ll.late = late;
         auto wait_tiles = [&] {
-            int spins = 0;                                       // every shard's tiles are in: all of (up to) eight flags show the step
+            // every shard's tiles are in: all of (up to) eight flags show the step
             // (the first look at once: a role that reaches its wait after the tiles -- most do, their waves get few issue slots
             // while the tile waves of their SIMDs are at their cells -- must not sleep first; then the back-off, once)
-            while (__builtin_amdgcn_ballot_w64(__hip_atomic_load(flag1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < stepno) != 0ull) {
-                if (spins == 0 && nwg >= 32) __builtin_amdgcn_s_sleep(LEAP_BACKOFF_ROLE); else __builtin_amdgcn_s_sleep(1);
-                ++spins;
-                if ((spins & 255) == 0 && __hip_atomic_load(late, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;   // see leap_wait
-                if (spins > (1 << 21)) { if (lane_w == 0) __hip_atomic_fetch_add(late, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-            }
+            hs_wait<1, HS_CHECK, HS_LIMIT_LEAP, HS_LANE0, LEAP_BACKOFF_ROLE>([&] { return hs_all(ld_l2(flag1) >= stepno); }, late, nwg >= 32);
         };
         if (wv != 0) {
             // the helper waves: the rows' spatial effects of the current position once the previous step's roles are done
@@ -2445,10 +2333,10 @@ void k_leap(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, int par0, int nst
         RPROBE(3);
         {
             unsigned long long old = 0ull;
-            if (threadIdx.x == 0) old = __hip_atomic_fetch_add(cnt2, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (threadIdx.x == 0) old = add_l2(cnt2, 1ull);
             const bool last = __builtin_amdgcn_readfirstlane((int)(old + 1 == rstep * (unsigned long long)nroles)) != 0;
             if (last && threadIdx.x < LEAP_NSH)                  // the step's last role: eight copies of the flag, one store
-                __hip_atomic_store(LEAP_FLAG2(b, threadIdx.x), rstep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                st_l2(LEAP_FLAG2(b, threadIdx.x), rstep);
             if (threadIdx.x == 0) { LSTAMP_MIN(6); LSTAMP_MAX(7); }
             RPROBE(4);                                           // counted in
         }

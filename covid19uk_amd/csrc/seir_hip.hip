@@ -700,7 +700,7 @@ static int check_eval_handoffs(seir_ctx *ctx) {
     HIP_TRY(hipMemcpy(&n, ctx->eval_err, sizeof(int), hipMemcpyDeviceToHost));
     if (n) {
         (void)hipMemset(ctx->eval_err, 0, sizeof(int));
-        return fail(SEIR_ERR_STATE, "%d in-launch hand-off(s) of the one-launch evaluation timed out: results since the last "
+        return fail(SEIR_ERR_HANDOFF, "%d in-launch hand-off(s) of the one-launch evaluation timed out: results since the last "
                     "synchronisation are unreliable (SEIR_OPT_EVAL_FORM 2 selects the three-launch form)", n);
     }
     return 0;
@@ -1980,7 +1980,7 @@ static int check_handoffs(seir_sampler *s) {
         // sampler produces is to be trusted until its state is rebuilt -- seir_sampler_restore (back to the last snapshot:
         // the failed burst can be run again, e.g. in the per-step launch forms), seir_sampler_set_state or
         // seir_sampler_refresh (F and every table recomputed from the planes as they are; the failed burst's draws are lost)
-        return fail(SEIR_ERR_STATE, "chain %d: %u in-launch hand-off(s) timed out -- the persistent launches could not get all "
+        return fail(SEIR_ERR_HANDOFF, "chain %d: %u in-launch hand-off(s) timed out -- the persistent launches could not get all "
                     "their workgroups on the GPU at once (another sampler or process holds part of it?).  Draws since the last "
                     "check are unreliable and the sampler refuses to go on until seir_sampler_restore / _set_state / _refresh; "
                     "hmc_mode 3 + moves_mode 4 (seir_sampler_set_launch_form) are the launch forms for a shared GPU",

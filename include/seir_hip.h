@@ -33,13 +33,14 @@
 extern "C" {
 #endif
 
-#define SEIR_ABI_VERSION 3
+#define SEIR_ABI_VERSION 4
 
 typedef enum {
     SEIR_OK = 0,
     SEIR_ERR_INVALID = -1,   /* bad argument / shape */
     SEIR_ERR_DEVICE = -2,    /* HIP runtime failure (no device, OOM, launch error) */
-    SEIR_ERR_STATE = -3      /* call made in the wrong state */
+    SEIR_ERR_STATE = -3,     /* call made in the wrong state */
+    SEIR_ERR_HANDOFF = -4    /* a wait inside a persistent launch timed out (see seir_sampler_pair_timeouts) */
 } seir_status;
 
 typedef struct seir_ctx seir_ctx;
@@ -315,7 +316,7 @@ int seir_sampler_xcd_local(seir_sampler *s);
  * authoritative workgroup gave up waiting for a speculative one (it then draws the proposal itself:
  * results are unaffected, throughput is not) + (b) waits that cannot be recovered from (band tokens,
  * k_se_chunk's tile flag, k_leap's flags, k_move_pairs' step barrier).  (a) is benign and only counted
- * here.  (b) makes the next seir_sampler_read_trace / seir_sampler_trace_wait fail with SEIR_ERR_STATE
+ * here.  (b) makes the next seir_sampler_read_trace / seir_sampler_trace_wait fail with SEIR_ERR_HANDOFF
  * and the error is STICKY: a workgroup that gave up went on with stale data (the incrementally updated
  * F = Cstar . I/N can be out of step with the event planes afterwards), so seir_sampler_run and every read
  * of the trace keep failing until seir_sampler_restore, seir_sampler_set_state or seir_sampler_refresh has
@@ -345,11 +346,11 @@ int seir_sampler_time_leapfrog(seir_sampler *s, int32_t sweeps, float *mean_ms, 
  *
  * hmc_mode 0 and moves_mode 0 need every workgroup of their launch resident at once; a second sampler, another
  * process or a profiler's replay pass can leave part of a grid unplaced, the bounded waits then time out and the
- * sampler reports SEIR_ERR_STATE (see seir_sampler_pair_timeouts).  The burst loop of inference.py:453-468 is kept
+ * sampler reports SEIR_ERR_HANDOFF (see seir_sampler_pair_timeouts).  The burst loop of inference.py:453-468 is kept
  * alive like this:
  *     seir_sampler_snapshot(s, k & 1)            at the start of burst k (in stream order, a few device copies)
  *     seir_sampler_run(s, n); read the trace
- *     on SEIR_ERR_STATE:  seir_sampler_restore(s, k & 1);  seir_sampler_set_launch_form(s, 3, 4);  run burst k again
+ *     on SEIR_ERR_HANDOFF:  seir_sampler_restore(s, k & 1);  seir_sampler_set_launch_form(s, 3, 4);  run burst k again
  * A snapshot holds everything the next sweep's draws are a function of (event planes, state planes, F, the
  * tables, position, step size, adaptation state, sweep counter) -- not the trace.  After a restore the same
  * launch form reproduces the burst bit for bit, the per-step forms (hmc_mode 3, moves_mode 4) draw for draw with

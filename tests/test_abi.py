@@ -36,10 +36,18 @@ def test_header_symbols_are_exported(lib):
     assert sorted(declared) == _lib.exported_symbols()
 
 
-def test_abi_version(lib):
+def test_abi_version_4_and_the_handoff_status(lib):
     text = open(os.path.join(ROOT, "include", "seir_hip.h")).read()
     declared = int(re.search(r"#define\s+SEIR_ABI_VERSION\s+(\d+)", text).group(1))
-    assert lib.seir_abi_version() == declared == _lib.ABI_VERSION == 3
+    assert lib.seir_abi_version() == declared == _lib.ABI_VERSION == 4
+    # v4: hand-off time-outs have a status of their own, and the binding knows them by that status alone
+    code = int(re.search(r"SEIR_ERR_HANDOFF\s*=\s*(-\d+)", text).group(1))
+    assert code == _lib.ERR_HANDOFF == -4
+    with pytest.raises(_lib.HandoffTimeout):
+        _lib.check(code)
+    with pytest.raises(_lib.SeirError) as e:
+        _lib.check(-3)
+    assert not isinstance(e.value, _lib.HandoffTimeout)
 
 
 def test_sampler_desc_struct_layout_matches_header():

@@ -36,7 +36,7 @@ class FakeDevice(ChainSampler):
         self.log = []
 
     def _fail(self):
-        raise _lib.HandoffTimeout("libseirhip call failed (-3): chain 0: 1 in-launch hand-off(s) timed out", -3)
+        raise _lib.HandoffTimeout("libseirhip call failed (-4): chain 0: 1 in-launch hand-off(s) timed out", _lib.ERR_HANDOFF)
 
     def snapshot(self, slot=0):
         if self.poisoned:
