@@ -25,6 +25,10 @@ constexpr int SCAN_ROWS = 8;    // rows per k_scan workgroup
 constexpr int SCAN_WAVES = 8;   // one row per wave: 3 waves per SIMD at UK-380 x 8 chains, evenly
 constexpr int SCAN_CB = 6;      // k_scan: 64-day chunks fetched per batch (6 = one batch at T <= 384)
 constexpr int SCAN_LFT = 2048;  // k_scan: entries of the log-factorial table held in LDS (16 KB)
+// dynamic LDS of k_scan / k_scan_params: [SCAN_WAVES][Tp][2] fp64 columns | the log-factorial table
+constexpr size_t scan_lds_bytes(int Tp) { return ((size_t)SCAN_WAVES * Tp * 2 + SCAN_LFT) * sizeof(double); }
+// ... and their static LDS: scan_rows's log table, k_scan_params's parameter block (sh[4], seg[256])
+constexpr size_t SCAN_STATIC_LDS = sizeof(double2) * LDSTAB_N + sizeof(double) * (4 + 256);
 constexpr int SE_RW = 4;        // k_se: rows per wave; tile = (4*SE_RW) rows x 64 days per workgroup
 constexpr int SE_TM = 4 * SE_RW;
 constexpr int NSCAL = 16;       // per-chain scalar block

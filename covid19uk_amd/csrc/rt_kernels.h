@@ -12,12 +12,15 @@
 // VALU.  Workgroup = 64 destination columns (lane = j) x RT_TT days x all sources i: Cstar[i][j]
 // is loaded once per (i, lane) and reused for the RT_TT days held in registers; the per-(i,t)
 // factors sit in LDS.  S_it comes from the state scan of the log-prob path (KS = (k_se, S-k_se)).
+// E and S of a workgroup's days take 2 RT_TT Mp doubles of LDS: the day tile is a template
+// parameter, picked from Mp by rt_days_per_block.
 #pragma once
 #include "logprob_kernels.h"
 
 namespace seir {
 
-constexpr int RT_TT = 16;      // days per workgroup
+// days per workgroup of k_rt: 16 up to Mp = 512 (160 KiB of LDS), 4 up to Mp = 2048 (136 KiB)
+constexpr int rt_days_per_block(int Mp) { return Mp <= 512 ? 16 : 4; }
 
 // a_t table with the NGM's indexing, one workgroup per draw; writes w.ea[b][t] = exp(a_t)
 __global__ __launch_bounds__(256) void k_rt_tables(Dims d, Work w, const double *__restrict__ theta) {
@@ -48,6 +51,7 @@ __device__ __forceinline__ double prob_of_rate(double x) {
     return -expm1(-x);
 }
 
+template <int RT_TT>
 __global__ __launch_bounds__(256) void k_rt(Dims d, Consts c, Work w, const double *__restrict__ theta,
                                              double *__restrict__ Rit) {
     extern __shared__ double lds[];                      // E [RT_TT][Mp] | S [RT_TT][Mp] | red [4][RT_TT][64]
@@ -97,7 +101,12 @@ __global__ __launch_bounds__(256) void k_rt(Dims d, Consts c, Work w, const doub
     }
 }
 
-inline size_t k_rt_lds_bytes(const Dims &d) { return sizeof(double) * ((size_t)2 * RT_TT * d.Mp + 4 * RT_TT * WAVE); }
+template <int RT_TT>
+constexpr size_t k_rt_lds_bytes(int Mp) { return sizeof(double) * ((size_t)2 * RT_TT * Mp + 4 * RT_TT * WAVE); }
+// k_rt has no static LDS: the dynamic part is all of it
+static_assert(k_rt_lds_bytes<rt_days_per_block(512)>(512) <= 160 * 1024 &&
+              k_rt_lds_bytes<rt_days_per_block(2048)>(2048) <= 160 * 1024,
+              "k_rt's day tile must fit a workgroup's LDS at the largest Mp it is picked for");
 
 // Within-/between-location infection pressure of the last state of every draw
 // (covid19uk/posterior/within_between.py:13-57):

@@ -258,14 +258,21 @@ static int create_impl(const seir_desc *ds, seir_ctx *ctx) {
     return 0;
 }
 
+// SEIR_MAX_T is the largest T whose state scan (k_scan, k_scan_params: the tightest launch of a context) fits the 160 KiB
+// of a workgroup; k_state_params and k_eval_all hold the same columns without the log-factorial table
+static_assert(SEIR_MAX_T % 64 == 0 && scan_lds_bytes(SEIR_MAX_T) + SCAN_STATIC_LDS <= 160 * 1024 &&
+              scan_lds_bytes(SEIR_MAX_T + 64) + SCAN_STATIC_LDS > 160 * 1024,
+              "SEIR_MAX_T must be the longest series whose state scan fits the LDS of a workgroup");
+
 extern "C" int seir_create(const seir_desc *ds, seir_ctx **out) {
     if (!ds || !out) return fail(SEIR_ERR_INVALID, "null argument");
     *out = nullptr;
     if (ds->M < 1 || ds->T < 1 || ds->max_chains < 1)
         return fail(SEIR_ERR_INVALID, "M, T and max_chains must be >= 1 (got %d, %d, %d)", ds->M, ds->T,
                     ds->max_chains);
-    if (ds->T > 2048 || ds->M > 2048)
-        return fail(SEIR_ERR_INVALID, "M=%d, T=%d exceed the supported 2048 x 2048", ds->M, ds->T);
+    if (ds->M > SEIR_MAX_M || ds->T > SEIR_MAX_T)
+        return fail(SEIR_ERR_INVALID, "M=%d, T=%d exceed the supported M <= %d, T <= %d (the state scan's LDS)", ds->M, ds->T,
+                    SEIR_MAX_M, SEIR_MAX_T);
     if (!ds->Cstar || !ds->N || !ds->W || !ds->weekday_c || !ds->log_area_c || !ds->car_Q || !ds->init_state)
         return fail(SEIR_ERR_INVALID, "null covariate pointer");
     if (!(ds->time_delta > 0.0) || !(ds->nu > 0.0))
@@ -350,7 +357,7 @@ extern "C" int seir_set_option(seir_ctx *ctx, int32_t option, int32_t value) {
 template <int SRC>
 static void launch_scan(seir_ctx *ctx, const LaunchCfg &l, const double *events) {
     const Dims &d = l.d;
-    const size_t lds = ((size_t)SCAN_WAVES * d.Tp * 2 + SCAN_LFT) * sizeof(double);
+    const size_t lds = scan_lds_bytes(d.Tp);
     if (lds > 64 * 1024)
         (void)hipFuncSetAttribute((const void *)k_scan<SRC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(k_scan<SRC>, dim3(d.nrb_scan, l.nb), dim3(SCAN_WAVES * WAVE), lds,
@@ -638,7 +645,7 @@ extern "C" int seir_log_prob_dev(seir_ctx *ctx, int32_t B, const double *u_dev, 
             launch_eval_fused<64>(ctx, l, u_dev, events_dev, logp_dev, grad_dev);
         }
     } else {
-        const size_t lds = ((size_t)SCAN_WAVES * d.Tp * 2 + SCAN_LFT) * sizeof(double);
+        const size_t lds = scan_lds_bytes(d.Tp);
         if (lds > 64 * 1024)
             (void)hipFuncSetAttribute((const void *)k_scan_params, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(k_scan_params, dim3(d.nrb_scan + 1, B), dim3(SCAN_WAVES * WAVE), lds, l.st, d, ctx->c, ctx->w,
@@ -813,6 +820,17 @@ extern "C" int seir_selftest_math(seir_ctx *ctx, int32_t n, const double *x, dou
     return 0;
 }
 
+template <int RT_TT>
+static void launch_rt(seir_ctx *ctx, int nb, double *rit_dev) {
+    const Dims &d = ctx->d;
+    const size_t lds = k_rt_lds_bytes<RT_TT>(d.Mp);
+    static std::atomic<unsigned long long> attr_set{0ull};
+    if (lds > 64 * 1024 && first_on_device(attr_set, ctx->device))
+        (void)hipFuncSetAttribute((const void *)k_rt<RT_TT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(k_rt<RT_TT>, dim3((d.M + 63) / 64, (d.T + RT_TT - 1) / RT_TT, nb), dim3(256), lds, ctx->stream, d,
+                       ctx->c, ctx->w, ctx->u_stage, rit_dev);
+}
+
 extern "C" int seir_reproduction_number(seir_ctx *ctx, int32_t n, const double *theta, const double *events,
                                         double *R_it) {
     int rc = check_batch(ctx, 1);
@@ -830,8 +848,8 @@ extern "C" int seir_reproduction_number(seir_ctx *ctx, int32_t n, const double *
                                hipMemcpyHostToDevice, ctx->stream));
         launch_scan<0>(ctx, whole(ctx, nb), ctx->ev_stage);               // KS = (k_se, S - k_se): S_it
         hipLaunchKernelGGL(k_rt_tables, dim3(nb), dim3(256), 0, ctx->stream, d, ctx->w, ctx->u_stage);
-        hipLaunchKernelGGL(k_rt, dim3((d.M + 63) / 64, (d.T + RT_TT - 1) / RT_TT, nb), dim3(256), k_rt_lds_bytes(d),
-                           ctx->stream, d, ctx->c, ctx->w, ctx->u_stage, rit_dev);
+        if (rt_days_per_block(d.Mp) == 16) launch_rt<16>(ctx, nb, rit_dev);
+        else launch_rt<4>(ctx, nb, rit_dev);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(R_it + (size_t)s0 * d.T * d.M, rit_dev, sizeof(double) * nb * d.T * d.M,
                                hipMemcpyDeviceToHost, ctx->stream));

@@ -71,6 +71,18 @@ typedef struct {
 int seir_abi_version(void);
 const char *seir_last_error(void);
 
+/* Shape limits.  seir_create accepts 1 <= M <= SEIR_MAX_M and 1 <= T <= SEIR_MAX_T and refuses anything else with
+ * SEIR_ERR_INVALID before it allocates.  SEIR_MAX_T = 1088 = 17 x 64 is the longest series at which every launch a
+ * context can make keeps its LDS within the 160 KiB of a gfx950 workgroup: the state scans of the four-launch and
+ * prepared forms and of R_it hold [8 rows][ceil64(T)][2] fp64 next to a 2048-entry log-factorial table and 4.5 KiB of
+ * static LDS (at T = 1152 that is 164.5 KiB).  The other entry points add limits of their own:
+ *   seir_sampler_create       ceil64(T) <= 1024 and M <= 2048
+ *   seir_reproduction_number  the context's limits (day tile of 16 up to ceil64(M) = 512, of 4 beyond)
+ *   seir_within_between       the context's limits
+ *   seir_simulate             M <= 1280 (124 ceil64(M) bytes of LDS per workgroup), any num_steps with num_steps x M < 2^31 */
+#define SEIR_MAX_M 2048
+#define SEIR_MAX_T 1088
+
 /* CovidUK(covariates, initial_state, initial_step=0, num_steps=T)  (model_spec.py:139) */
 int seir_create(const seir_desc *desc, seir_ctx **out);
 void seir_destroy(seir_ctx *ctx);

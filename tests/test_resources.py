@@ -49,6 +49,35 @@ def test_hot_path_instances_have_no_scratch_and_keep_their_occupancy(resources, 
     assert r["vgpr"] <= vmax and r["occupancy_waves_per_simd"] >= occ, (kernel, r)
 
 
+def test_launches_fit_the_lds_at_the_shape_limits(resources):
+    """Static LDS (the compiler's figure) + the dynamic LDS the host asks for, at the largest shape each launch is made
+    for, within the 160 KiB of a gfx950 workgroup: the evaluation kernels at T = SEIR_MAX_T, k_rt's two day tiles at
+    the largest Mp each is picked for, the simulator at M = 1280."""
+    import re
+    hdr = open(os.path.join(entry.ROOT, "include", "seir_hip.h")).read()
+    t_max = int(re.search(r"#define SEIR_MAX_T (\d+)", hdr).group(1))
+    tp = (t_max + 63) // 64 * 64
+    assert tp == t_max
+    scan = (8 * tp * 2 + 2048) * 8                                   # [SCAN_WAVES][Tp][2] | SCAN_LFT table
+    cols = 8 * tp * 2 * 8
+
+    def tiles(tn):                                                   # eval_tiles_lds_bytes<TN>
+        panels = (2 * 16 * (80 + tn + 16) + 2) * 8
+        epi = (64 * (tn + 2) + 4 * tn + 2 * 64 + 16) * 8
+        return max(panels, epi, 2048 * 8)
+    dynamic = {"k_scan<0>": scan, "k_scan<1>": scan, "k_scan_params": scan, "k_state_params": cols,
+               "k_eval_all<true,64>": max(tiles(64), cols), "k_eval_all<false,64>": max(tiles(64), cols),
+               "k_eval_all<true,96>": max(tiles(96), cols // tp * 960), "k_eval_all<false,96>": max(tiles(96), cols // tp * 960),
+               "k_finish<true>": tp * 8, "k_finish<false>": tp * 8,
+               "k_rt<16>": (2 * 16 * 512 + 4 * 16 * 64) * 8, "k_rt<4>": (2 * 4 * 2048 + 4 * 4 * 64) * 8,
+               "k_simulate": 124 * 1280}
+    over = {k: resources[k]["lds_bytes_per_block"] + v for k, v in dynamic.items()
+            if resources[k]["lds_bytes_per_block"] + v > 160 * 1024}
+    assert not over, over
+    # ... and the limit is the largest such T: one more 64-day chunk does not fit the state scan
+    assert resources["k_scan_params"]["lds_bytes_per_block"] + scan + 2 * 8 * 64 * 8 > 160 * 1024
+
+
 def test_the_committed_copy_is_this_rounds(resources):
     """profiles/rNN_kernel_resources.json is the tracked copy the docs cite: it must list the same kernels, and agree with a
     fresh build on what the hot path is held to (scratch) -- register counts may move by a few with the compiler's mood."""
