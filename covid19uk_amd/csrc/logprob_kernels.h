@@ -702,7 +702,7 @@ constexpr int SE_RS = 72;       // LDS row stride (doubles) of the row-sum trans
 // other are then found in that XCD's L2 instead of at the cross-XCD rate.
 // Maps the linear block id L of a 1-D grid of per*nb blocks to (chain, tile); the host only sets
 // aff_nb when nb is 1, 2, 4 or a multiple of 8 (then several chains share an XCD, each still whole on one) and
-// per*nb is a multiple of 8 (otherwise the natural 2-D grid).
+// per*nb is a multiple of 8 (otherwise the natural 2-D grid: xcd_affinity_applies, sweep_plan.h).
 __device__ __forceinline__ void xcd_affine(int L, int per, int nb, int &chain, int &tile) {
     const int l = L & 7;
     if (nb == 8) {
@@ -715,9 +715,6 @@ __device__ __forceinline__ void xcd_affine(int L, int per, int nb, int &chain, i
         chain = l % nb;
         tile = (L >> 3) * (8 / nb) + l / nb;
     }
-}
-inline bool xcd_affinity_applies(int per, int nb) {
-    return (nb == 1 || nb == 2 || nb == 4 || (nb > 0 && nb % 8 == 0)) && ((long long)per * nb) % 8 == 0;
 }
 
 // The S->E cells of one lane (NR rows, one day): rate r = (exp(a_t) exp(b_m)/N_m (I + psi W_t F) + floor) dt, L = log(1 - e^-r),

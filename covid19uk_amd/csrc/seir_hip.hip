@@ -18,8 +18,12 @@
 #include "sim_kernels.h"
 #include "moves_kernel.h"
 #include "rt_kernels.h"
+#include "sweep_plan.h"
 
 using namespace seir;
+
+static_assert(plan::WAVE == WAVE && plan::CT_MAXC == CT_MAXC && plan::ROLE_SLOTS == ROLE_SLOTS,
+              "sweep_plan.h reads the kernels' constants");
 
 static thread_local char g_err[512] = "";
 
@@ -999,8 +1003,10 @@ struct seir_sampler {
     SamplerCfg cfg{};
     Chains ch{};
     int record_events = 1;
-    bool move_lds_attr = false;       // the event-update kernels were allowed more than 64 KB of dynamic LDS
-    int pairs_lds_attr = 0;           // k_move_pairs was allowed its LDS request (one workgroup per CU): 1 yes, -1 refused
+    // what the chip holds, asked once at creation (inputs of plan_sweep): compute units, workgroups per CU of the k_leap
+    // instances the planner can choose (24-row / this shape's 32-row tiles), k_move_pairs allowed its LDS request
+    int cus = 0, leap_occ[2] = {0, 0};
+    bool pairs_lds_attr = false;
     std::vector<void *> allocs;
     // chains are independent: they are split into groups that run on their own streams
     // so that one group's single-workgroup-per-chain kernels overlap another group's wide ones
@@ -1014,19 +1020,10 @@ struct seir_sampler {
     hipEvent_t ev_burst = nullptr, ev_copy = nullptr;
     bool copy_pending = false;
     bool use_graph = false;       // seir_sampler_desc::use_graph
-    bool hmc_chunked = true;      // hmc_mode 1: every leapfrog step by the single-workgroup kernel
-    bool hmc_tail = true;         // hmc_mode 0 / 3: chunk roles inside the gradient launch (k_se_chunk) where xcd_local holds
-    bool hmc_leap = true;         // hmc_mode 0: all inner steps in one persistent launch (k_leap) where every workgroup fits the chip
-    int leap_occ[2][3][2];        // workgroups of k_leap<TSM, NTC, NST> the chip holds at once (occupancy query, cached; -1: not asked yet)
     int leap_rows = 0;            // seir_sampler_desc::leap_rows: 0 auto, 24 / 32: only that tile shape (else the per-step form)
     // seir_sampler_time_leapfrog: HIP events around the inner leapfrog steps of each sweep while it is on
     std::vector<hipEvent_t> prof_ev;     // pairs (before, after)
-    int prof_i = -1, prof_launches = 0, prof_evals = 0;  // next pair to record (-1: off); launches / gradient evaluations of the section in the last sweep
-    bool hmc_fold = true;         // hmc_mode 0 / 5: the trajectory's first step and both end-point gradients inside k_leap as well
-    bool hmc_end = true;          // hmc_mode 0: ... and its last half kick, accept test, adaptation and trace (5: k_hmc_step<2> does those)
-    bool hmc_tailfold = true;     // hmc_mode 0 (where k_leap does not fit) / 6: the trajectory's first and last step by the chunk roles of
-                                  // the per-step launches as well (L + 1 k_se_chunk launches and k_hmc_final instead of k_se, k_hmc_step<0>,
-                                  // L - 1 k_se_chunk, k_se, k_hmc_step<2>)
+    int prof_i = -1;              // next pair to record (-1: off)
     bool vt_dirty = true;         // Work::Vt does not match Chains::var (set_kernel / set_adaptation / creation)
     unsigned long long leap_rsteps = 0;  // steps the ROLES of k_leap have done over all launches (the tiles do one more per folded launch)
     unsigned long long leap_steps = 0;   // leapfrog steps done by all k_leap launches so far (what Chains::leap's flags show)
@@ -1034,7 +1031,7 @@ struct seir_sampler {
     unsigned long long tail_count = 0;   // tiles per chain counted in by all k_se_chunk launches so far (Chains::tail)
     unsigned pbar_count = 0;      // workgroup arrivals every chain's step counter (Chains::pbar) has seen over all k_move_pairs launches
     int pair_debug = 0;           // debug_pair: test hooks of k_move_pair's handshake (1 late, 2 absent role 1)
-    int moves_mode = 0;           // 0 = paired updates (k_move_pair) with the S->E-type proposal pre-drawn one pair ahead -- every pair of a
+    int moves_mode = 0;           // (moves_form: the mode in force) 0 = paired updates (k_move_pair) with the S->E-type proposal pre-drawn one pair ahead -- every pair of a
                                   //     sweep in one launch (k_move_pairs) where band workgroups can be part of it, else one launch per
                                   //     pair (4: always one launch per pair; 3: the same, never with band workgroups in the pair launch);
                                   // 1 = one proposal kernel per update (k_move_pa2); 2 = paired launches without the pre-draw
@@ -1096,17 +1093,42 @@ extern "C" void seir_sampler_destroy(seir_sampler *s) {
     delete s;
 }
 
-// seir_sampler_desc::hmc_mode / moves_mode -> the switches enqueue_sweep reads
+// The kernel instances a sweep launches, for the numbers of its plan (sweep_plan.h).
+// The persistent leapfrog kernel for (tile-scalar mode, day chunks, gradient tiles per workgroup)
+// nst = 2: two 16-row gradient tiles per workgroup (32 rows); nst = 1: ONE 24-row tile per workgroup, six rows per wave -- the
+// shape whose 96 workgroups per chain divide UK-380's XCD evenly (instantiated for that size class: M <= 512, six day chunks)
+static const void *leap_fn(int ts_mode, int ntc, int nst) {
+    if (nst == 1) return (const void *)k_leap<1, 6, 1, 6>;
+#define LEAP_ROW(TSM_, NTC_) ((const void *)k_leap<TSM_, NTC_, 2>)
+    if (ts_mode == 1) return ntc == 1 ? LEAP_ROW(1, 1) : ntc == 6 ? LEAP_ROW(1, 6) : LEAP_ROW(1, 12);
+    return ntc == 1 ? LEAP_ROW(2, 1) : ntc == 6 ? LEAP_ROW(2, 6) : LEAP_ROW(2, 12);
+#undef LEAP_ROW
+}
+static decltype(&k_se_chunk<1, 1>) se_chunk_fn(int ts_mode, int ntc) {
+    if (ts_mode == 1) return ntc == 1 ? k_se_chunk<1, 1> : ntc == 6 ? k_se_chunk<1, 6> : k_se_chunk<1, 12>;
+    return ntc == 1 ? k_se_chunk<2, 1> : ntc == 6 ? k_se_chunk<2, 6> : k_se_chunk<2, 12>;
+}
+static decltype(&k_hmc_final<1>) hmc_final_fn(int ntc) { return ntc == 1 ? k_hmc_final<1> : ntc == 6 ? k_hmc_final<6> : k_hmc_final<12>; }
+// chunk count at compile time for the BASELINE sizes (NI, UK, SYN), rolled loops otherwise
+static decltype(&k_hmc_chunk<0>) hmc_chunk_fn(int ntc) {
+    return ntc == 1 ? k_hmc_chunk<1> : ntc == 6 ? k_hmc_chunk<6> : ntc == 12 ? k_hmc_chunk<12> : k_hmc_chunk<0>;
+}
+// HT / HM: 512-day / 512-row parts of the series and the rows (sampler_create caps T <= 1024, M <= 2048)
+static decltype(&k_hmc_step<0, 1, 1>) hmc_step_fn(int stage, const Dims &d) {
+    const int ht = (d.Tp + HB - 1) / HB, hm = (d.M + HB - 1) / HB;
+#define HMC_STEP(S_) (ht <= 1 ? (hm <= 1 ? k_hmc_step<S_, 1, 1> : hm <= 2 ? k_hmc_step<S_, 1, 2> : k_hmc_step<S_, 1, 4>) \
+                              : (hm <= 1 ? k_hmc_step<S_, 2, 1> : hm <= 2 ? k_hmc_step<S_, 2, 2> : k_hmc_step<S_, 2, 4>))
+    return stage == 0 ? HMC_STEP(0) : stage == 1 ? HMC_STEP(1) : HMC_STEP(2);
+#undef HMC_STEP
+}
+static decltype(&k_move_pair<6>) move_pair_fn(int nch) { return nch == 6 ? k_move_pair<6> : nch == 12 ? k_move_pair<12> : k_move_pair<16>; }
+static decltype(&k_move_pairs<6>) move_pairs_fn(int nch) { return nch == 6 ? k_move_pairs<6> : nch == 12 ? k_move_pairs<12> : k_move_pairs<16>; }
+static decltype(&k_move_pa2<6>) move_pa2_fn(int nch) { return nch == 6 ? k_move_pa2<6> : nch == 12 ? k_move_pa2<12> : k_move_pa2<16>; }
+
+// seir_sampler_desc::hmc_mode / moves_mode -> the form in force (plan_sweep reads it)
 static void apply_launch_form(seir_sampler *s, int hmc_mode, int moves_mode) {
     s->hmc_mode = hmc_mode;
-    s->hmc_chunked = hmc_mode != 1;
-    s->hmc_tail = hmc_mode == 0 || hmc_mode == 3 || hmc_mode == 4 || hmc_mode == 5;
-    s->hmc_leap = hmc_mode == 0 || hmc_mode == 4 || hmc_mode == 5;
-    s->hmc_fold = hmc_mode == 0 || hmc_mode == 5;
-    s->hmc_end = hmc_mode == 0;
-    s->hmc_tailfold = hmc_mode == 0 || hmc_mode == 6;
-    if (hmc_mode == 6) s->hmc_tail = true;
-    s->moves_mode = moves_mode;
+    s->moves_mode = moves_form(moves_mode, s->cfg.n_scans);
 }
 
 extern "C" int seir_sampler_create(seir_ctx *ctx, const seir_sampler_desc *ds, seir_sampler **out) {
@@ -1153,7 +1175,6 @@ extern "C" int seir_sampler_create(seir_ctx *ctx, const seir_sampler_desc *ds, s
     s->pair_debug = ds->debug_pair;
     s->leap_rows = ds->leap_rows;
     apply_launch_form(s, ds->hmc_mode, ds->moves_mode);
-    for (auto &a : s->leap_occ) for (auto &b2 : a) for (int &v : b2) v = -1;
     c.disable_mask = ds->disable_mask;
     {
         int g = ds->chain_groups;    // measured: concurrent chain groups on several streams do not overlap profitably
@@ -1259,11 +1280,27 @@ extern "C" int seir_sampler_create(seir_ctx *ctx, const seir_sampler_desc *ds, s
         }
         if (e != hipSuccess) rc = fail(SEIR_ERR_DEVICE, "sampler stream setup failed: %s", hipGetErrorString(e));
     }
-    if (!rc && (s->hmc_tail || s->moves_mode == 0 || s->moves_mode == 2 || s->moves_mode == 4)) {
+    if (!rc && (HMC_FORMS[ds->hmc_mode].roles || ds->moves_mode == 0 || ds->moves_mode == 2 || ds->moves_mode == 4)) {
         // Do blocks with the same id mod 8 share an XCD here?  (probe_xcd_local)
         if (ctx->xcd_local < 0) ctx->xcd_local = probe_xcd_local(ctx->stream) ? 1 : 0;
         const bool ok = ctx->xcd_local == 1;
         s->xcd_local = ok;
+    }
+    if (!rc) {
+        // What the chip holds, asked once here: a sweep makes no HIP query (it may be under graph capture).  Workgroups
+        // per CU of the k_leap instances plan_sweep can choose (a refused query: 0, the launch never fits)
+        (void)hipDeviceGetAttribute(&s->cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
+        for (int nst = 1; nst <= 2; ++nst)
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&s->leap_occ[nst - 1], leap_fn(chunk_ts_mode(d.Mp), d.ntc, nst), 256, 0) != hipSuccess)
+                s->leap_occ[nst - 1] = 0;
+        // k_move_pairs asks for more than half a CU's LDS (one workgroup per CU); the other event-update kernels only above
+        // the default 64 KB
+        const int nch = move_nch(d.Tp);
+        s->pairs_lds_attr = hipFuncSetAttribute((const void *)move_pairs_fn(nch), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                (int)k_move_pairs_lds_bytes(d)) == hipSuccess;
+        const size_t plds = k_move_pa2_lds_bytes(d);
+        for (const void *fn : {(const void *)move_pair_fn(nch), (const void *)move_pa2_fn(nch)})
+            if (plds > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds);
     }
     if (rc) { seir_sampler_destroy(s); return rc; }
     *out = s;
@@ -1297,7 +1334,7 @@ extern "C" int seir_sampler_set_launch_form(seir_sampler *s, int32_t hmc_mode, i
     if (rc) return rc;
     if (moves_mode < 0 || moves_mode > 4 || hmc_mode < 0 || hmc_mode > 6)
         return fail(SEIR_ERR_INVALID, "moves_mode is 0..4, hmc_mode 0..6");
-    if (hmc_mode != s->hmc_mode || moves_mode != s->moves_mode) {
+    if (hmc_mode != s->hmc_mode || moves_form(moves_mode, s->cfg.n_scans) != s->moves_mode) {
         HIP_TRY(hipStreamSynchronize(s->ctx->stream));
         drop_graph(s);                               // the captured sweep is one form's launches
         apply_launch_form(s, hmc_mode, moves_mode);
@@ -1555,30 +1592,9 @@ extern "C" int seir_sampler_reset_trace_at(seir_sampler *s, int32_t first_slot) 
     return 0;
 }
 
-template <int HT, int HM>
-static void launch_hmc_t(seir_ctx *ctx, const LaunchCfg &l, const SamplerCfg &c, const Chains &ch, int stage,
-                         int gather_qs) {
-    const size_t lds = (size_t)l.d.Mp * sizeof(double);
-    const dim3 g(l.nb), blk(HB);
-    if (stage == 0)
-        hipLaunchKernelGGL((k_hmc_step<0, HT, HM>), g, blk, lds, l.st, l.d, ctx->c, ctx->w, c, ch, gather_qs);
-    else if (stage == 1)
-        hipLaunchKernelGGL((k_hmc_step<1, HT, HM>), g, blk, lds, l.st, l.d, ctx->c, ctx->w, c, ch, gather_qs);
-    else
-        hipLaunchKernelGGL((k_hmc_step<2, HT, HM>), g, blk, lds, l.st, l.d, ctx->c, ctx->w, c, ch, gather_qs);
-}
 static void launch_hmc(seir_ctx *ctx, const LaunchCfg &l, const SamplerCfg &c, const Chains &ch, int stage,
                        int gather_qs = 0) {
-    const int ht = (l.d.Tp + HB - 1) / HB, hm = (l.d.M + HB - 1) / HB;    // sampler_create caps T<=1024, M<=2048
-    if (ht <= 1) {
-        if (hm <= 1) launch_hmc_t<1, 1>(ctx, l, c, ch, stage, gather_qs);
-        else if (hm <= 2) launch_hmc_t<1, 2>(ctx, l, c, ch, stage, gather_qs);
-        else launch_hmc_t<1, 4>(ctx, l, c, ch, stage, gather_qs);
-    } else {
-        if (hm <= 1) launch_hmc_t<2, 1>(ctx, l, c, ch, stage, gather_qs);
-        else if (hm <= 2) launch_hmc_t<2, 2>(ctx, l, c, ch, stage, gather_qs);
-        else launch_hmc_t<2, 4>(ctx, l, c, ch, stage, gather_qs);
-    }
+    hipLaunchKernelGGL(hmc_step_fn(stage, l.d), dim3(l.nb), dim3(HB), (size_t)l.d.Mp * sizeof(double), l.st, l.d, ctx->c, ctx->w, c, ch, gather_qs);
 }
 
 // chains [b0, b0+nb) of group g
@@ -1588,20 +1604,24 @@ static void group_range(const seir_sampler *s, int g, int &b0, int &nb) {
     nb = (int)((long long)B * (g + 1) / G) - b0;
 }
 
-// the instance of the persistent leapfrog kernel for (tile-scalar mode, day chunks, gradient tiles per workgroup)
-// nst = 2: two 16-row gradient tiles per workgroup (32 rows); nst = 1: ONE 24-row tile per workgroup, six rows per wave -- the
-// shape whose 96 workgroups per chain divide UK-380's XCD evenly (instantiated for that size class: M <= 512, six day chunks)
-static const void *leap_fn(int ts_mode, int ntc, int nst) {
-    if (nst == 1) return (const void *)k_leap<1, 6, 1, 6>;
-#define LEAP_ROW(TSM_, NTC_) ((const void *)k_leap<TSM_, NTC_, 2>)
-    if (ts_mode == 1) return ntc == 1 ? LEAP_ROW(1, 1) : ntc == 6 ? LEAP_ROW(1, 6) : LEAP_ROW(1, 12);
-    return ntc == 1 ? LEAP_ROW(2, 1) : ntc == 6 ? LEAP_ROW(2, 6) : LEAP_ROW(2, 12);
-#undef LEAP_ROW
+// what plan_sweep reads for group g's sweep
+static SweepInputs sweep_inputs(const seir_sampler *s, int g) {
+    const Dims &d = s->ctx->d;
+    const SamplerCfg &c = s->cfg;
+    int b0, nb;
+    group_range(s, g, b0, nb);
+    return {d.M, d.Mp, d.Tp, d.ntc, d.nmt, c.nrb_d,
+            nb, c.L, c.n_scans, s->record_events,
+            s->hmc_mode, s->moves_mode, s->leap_rows,
+            s->xcd_local, s->ngroups == 1, s->use_graph, s->ctx->opt_affinity,
+            s->cus, s->leap_occ[0], s->leap_occ[1], s->pairs_lds_attr};
 }
 
+// Group g's sweep: the launches of its plan, with the hand-off counters the host keeps for them
 static void enqueue_sweep(seir_sampler *s, int g) {
     seir_ctx *ctx = s->ctx;
     const SamplerCfg &c = s->cfg;
+    const SweepPlan p = plan_sweep(sweep_inputs(s, g));
     int b0, nb;
     group_range(s, g, b0, nb);
     LaunchCfg l{ctx->d, s->gstream[g], nb, ctx->opt_affinity};
@@ -1609,333 +1629,197 @@ static void enqueue_sweep(seir_sampler *s, int g) {
     l.d.skew = ctx->opt_skew;
     const Dims d0 = l.d;
     hipStream_t st = l.st;
-    // [part 0] HMC on u | events: L+1 gradient evaluations
-    const bool chunked = s->hmc_chunked && c.L >= 3 && d0.ntc <= CT_MAXC;
-    const int ts_mode = chunked ? (d0.Mp <= 512 ? 1 : 2) : 0;   // 1: the M-chunks sum the row partials themselves
-    l.d.sp_par = 0;
-    // Is the persistent leapfrog launch (k_leap) usable for this sweep?  (the conditions of k_se_chunk -- XCD placement checked,
-    // one stream, the XCD-affine grid -- and every workgroup of the launch resident at once: its tiles wait for the roles)
-    const int per_roles = d0.ntc + d0.Mp / WAVE, ntile_all = d0.ntc * d0.nmt, nbv_all = (nb + 7) / 8 * 8;
-    bool leap_ok = false;
-    // the tile shape: 24-row workgroups (k_leap<1, 6, 1, 6>: nmt24 row tiles, one per workgroup) where they exist for the size
-    // and the whole launch -- three of them per CU and the roles beside -- is resident; else 32-row workgroups (two 16-row tiles)
-    int leap_nst = 2, leap_nmt = d0.nmt, leap_wgs = ntile_all / 2;
-    auto leap_slots = [&](int ti, int ni, int nst) {
-        int &slot = s->leap_occ[ti][ni][nst - 1];
-        if (slot < 0) {
-            int occ = 0, cus = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, leap_fn(ti + 1, ni == 0 ? 1 : ni == 1 ? 6 : 12, nst), 256, 0) != hipSuccess) occ = 0;
-            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
-            slot = occ * cus;                                     // workgroups the chip holds at once
-        }
-        return (long long)slot;
+    const int ntile = d0.ntc * d0.nmt;
+    // seir_sampler_time_leapfrog: HIP events around the leapfrog section (end = 1 closes the pair)
+    const bool prof = s->prof_i >= 0 && (size_t)(2 * s->prof_i + 1) < s->prof_ev.size() && g == 0;
+    auto prof_mark = [&](int end) {
+        if (prof) (void)hipEventRecord(s->prof_ev[2 * s->prof_i + end], st);
+        if (prof) s->prof_i += end;
     };
-    // chains per launch of k_leap: all of them -- or, for 16 chains, which do not fit the chip at once, two launches of 8 one
-    // after the other (2 x 134 us at UK-380 against 335 us for the 18 launches of the per-step form; from 24 chains on the
-    // per-step form is the faster one)
-    int leap_nbv = nbv_all;
-    if (chunked && s->hmc_leap && s->hmc_tail && s->xcd_local && s->ngroups == 1 && (l.affinity & 1) && !s->use_graph &&
-        xcd_affinity_applies(ntile_all, nbv_all) && (d0.ntc == 1 || d0.ntc == 6 || d0.ntc == 12) && c.L >= 3 && d0.nmt <= WAVE &&
-        d0.nmt % 2 == 0) {
-        const int ti = ts_mode - 1, ni = d0.ntc == 1 ? 0 : d0.ntc == 6 ? 1 : 2;
-        const int nmt24 = d0.Mp / 24, wgs24 = d0.ntc * nmt24;
-        auto fit = [&](int nbv) {
-            if (s->leap_rows != 32 && ts_mode == 1 && d0.ntc == 6 && d0.Mp % 24 == 0 && xcd_affinity_applies(wgs24, nbv) &&
-                (long long)(wgs24 + per_roles) * nbv <= leap_slots(ti, ni, 1)) {
-                leap_nst = 1; leap_nmt = nmt24; leap_wgs = wgs24;
-                return true;
-            }
-            if (s->leap_rows != 24) return (long long)(ntile_all / 2 + per_roles) * nbv <= leap_slots(ti, ni, 2);
-            return false;
-        };
-        leap_ok = fit(nbv_all);
-        if (!leap_ok && nb == 16 && fit(8)) { leap_ok = true; leap_nbv = 8; }
-    }
+    auto vt = [&] {     // Work::Vt to Chains::var where it does not match (set_kernel / set_adaptation / creation, mass adaptation)
+        if (s->vt_dirty || c.adapt_mass) hipLaunchKernelGGL(k_vt, dim3(nb), dim3(WAVE), 0, st, l.d, ctx->w, s->ch);
+        s->vt_dirty = false;
+    };
     auto launch_leap = [&](int par0, int nsteps, int fold) {
         Dims df = l.d;
-        df.aff_nb = leap_nbv;
-        df.nlive = leap_nbv == nbv_all && nbv_all != nb ? nb : 0;
+        df.aff_nb = p.leap_nbv;
+        df.nlive = p.leap_nlive;
         df.sp_par = 0;
-        df.chunked = ts_mode;
-        df.nmt = leap_nmt;                                       // the partial sums of this launch: one set per row tile of ITS shape
-        const dim3 gf((unsigned)((leap_wgs + per_roles) * leap_nbv));
+        df.chunked = p.ts_mode;
+        df.nmt = p.leap_nmt;                                     // the partial sums of this launch: one set per row tile of ITS shape
+        const dim3 gf((unsigned)((p.leap_wgs + p.per) * p.leap_nbv));
         // (every chain's counters and hand-off words count its OWN launches: the sub-batches of a sweep share the step numbers)
         const unsigned long long step_base = s->leap_steps, role_base = s->leap_rsteps;
         s->leap_steps += (unsigned long long)nsteps;
         s->leap_rsteps += (unsigned long long)(nsteps - (((fold & 2) && !(fold & 4)) ? 1 : 0));
-        for (int sub = 0; sub < nbv_all / leap_nbv; ++sub) {
-            df.b0 = l.d.b0 + sub * leap_nbv;
+        for (int sub = 0; sub < p.leap_launches; ++sub) {
+            df.b0 = l.d.b0 + sub * p.leap_nbv;
             void *args[] = {(void *)&df, (void *)&ctx->c, (void *)&ctx->w, (void *)&c, (void *)&s->ch, (void *)&par0, (void *)&nsteps,
                             (void *)&step_base, (void *)&role_base, (void *)&fold};
-            (void)hipLaunchKernel(leap_fn(ts_mode, d0.ntc, leap_nst), gf, dim3(256), args, 0, st);
+            (void)hipLaunchKernel(leap_fn(p.ts_mode, d0.ntc, p.leap_nst), gf, dim3(256), args, 0, st);
         }
     };
-    const bool prof0 = s->prof_i >= 0 && (size_t)(2 * s->prof_i + 1) < s->prof_ev.size() && g == 0;
-    const bool fold = leap_ok && s->hmc_fold;
-    if (fold) {
+    // steps it0..it1 of the trajectory as k_se_chunk launches (tiles, then the chunk roles) from buffer par; with `ends`, the
+    // roles also do the trajectory's first step (momentum draw, half kick: traj 1), the step after it (2) and the last half
+    // kick (3).  Returns the buffer the last step wrote.
+    auto se_chunk_steps = [&](int it0, int it1, int par, bool ends) {
+        Dims df = l.d;
+        df.aff_nb = p.nbv;
+        df.nlive = p.nlive;
+        df.chunked = p.ts_mode;
+        for (int it = it0; it <= it1; ++it) {
+            const int traj = !ends ? 0 : it == 0 ? 1 : it == 1 ? 2 : it == c.L ? 3 : 0;
+            df.sp_par = par;
+            Work wf = ctx->w;
+            if (it == 0) wf.Lpart = wf.Lpart0;                    // the start point's value of the S->E term: kept for the accept test
+            s->tail_count += (unsigned long long)ntile;           // what a chain's counter shows once this launch's tiles are in
+            const unsigned long long target = s->tail_count;
+            hipLaunchKernelGGL(se_chunk_fn(p.ts_mode, d0.ntc), dim3((unsigned)((ntile + p.per) * p.nbv)), dim3(256), 0, st, df, ctx->c, wf,
+                               c, s->ch, par, target, traj);
+            if (it < c.L) par ^= 1;
+        }
+        return par;
+    };
+    // [part 0] HMC on u | events: L+1 gradient evaluations
+    l.d.sp_par = 0;
+    if (p.hmc == SweepPlan::FOLD) {
         // The whole trajectory in ONE launch: gradient at the start point, the first step (momentum draw, half kick, drift:
         // k_hmc_step<0>'s work, by the chunk roles), the L-1 inner steps, gradient at the end point, and the end itself (half
         // kick, accept test, adaptation, trace: by the roles as well, or -- hmc_mode 5 -- by k_hmc_step<2> as a launch of its
         // own).  L+1 gradient evaluations, L (+1) role steps.
-        if (s->vt_dirty || c.adapt_mass) {
-            Dims dv = l.d;
-            hipLaunchKernelGGL(k_vt, dim3(nb), dim3(WAVE), 0, st, dv, ctx->w, s->ch);
-            s->vt_dirty = false;
-        }
-        if (prof0) (void)hipEventRecord(s->prof_ev[2 * s->prof_i], st);
-        // hmc_end: the last half kick, the accept test, adaptation and trace by the chunk roles of the same launch as well;
-        // otherwise (hmc_mode 5) k_hmc_step<2> closes the trajectory as a launch of its own
-        launch_leap(1, c.L + 1, s->hmc_end ? 7 : 3);
-        if (prof0) {
-            (void)hipEventRecord(s->prof_ev[2 * s->prof_i + 1], st);
-            s->prof_i += 1;
-            s->prof_launches = nbv_all / leap_nbv;
-            s->prof_evals = c.L + 1;
-        }
-        if (!s->hmc_end) {
+        vt();
+        prof_mark(0);
+        launch_leap(1, c.L + 1, p.end_in_leap ? 7 : 3);
+        prof_mark(1);
+        if (!p.end_in_leap) {
             l.d.sp_par = c.L & 1 ? 0 : 1;       // the buffer the last role step wrote: steps alternate from buffer 1
             l.d.chunked = 0;
-            l.d.nmt = leap_nmt;                 // the end point's partial sums are k_leap's: its row tiles
+            l.d.nmt = p.leap_nmt;               // the end point's partial sums are k_leap's: its row tiles
             launch_hmc(ctx, l, c, s->ch, 2, /*gather_qs=*/3);
             l.d.nmt = d0.nmt;
         }
-    } else if (chunked && s->hmc_tailfold && s->hmc_tail && s->xcd_local && nbv_all > 0 && s->ngroups == 1 && (l.affinity & 1) &&
-               xcd_affinity_applies(ntile_all, nbv_all) && !s->use_graph && (d0.ntc == 1 || d0.ntc == 6 || d0.ntc == 12) && c.L >= 3 && per_roles <= ROLE_SLOTS) {
-        // The whole trajectory as L + 1 launches of k_se_chunk -- where the persistent launch does not fit the chip (16+ chains
-        // at UK-380, SYN-2048) -- with the trajectory's first step (momentum draw, half kick: traj 1), the step after it (2) and
-        // the last half kick (3) by the chunk roles of those launches, and the accept test, adaptation and trace by the roles'
-        // own launch (k_hmc_final): what k_se, k_hmc_step<0>, ..., k_se, k_hmc_step<2> do in the stage form (hmc_mode 3), and
-        // what k_leap's roles do inside the persistent launch.  Buffers alternate from 1, as there.
-        if (s->vt_dirty || c.adapt_mass) {
-            hipLaunchKernelGGL(k_vt, dim3(nb), dim3(WAVE), 0, st, l.d, ctx->w, s->ch);
-            s->vt_dirty = false;
-        }
+    } else if (p.hmc == SweepPlan::TAILFOLD) {
+        // The whole trajectory as L + 1 launches of k_se_chunk whose roles also do its first step and last half kick, then
+        // the accept test, adaptation and trace by the roles' own launch (k_hmc_final): what k_se, k_hmc_step<0>, ..., k_se,
+        // k_hmc_step<2> do in the stage form, and what k_leap's roles do inside the persistent launch.  Buffers alternate
+        // from 1, as there.
+        vt();
         int par = 1;
-        if (ts_mode == 2) hipLaunchKernelGGL(k_sp_prep, dim3(nb), dim3(256), 0, st, l.d, ctx->w, s->ch, par);
-        if (prof0) (void)hipEventRecord(s->prof_ev[2 * s->prof_i], st);
-        const int per = d0.ntc + d0.Mp / WAVE;
-        Dims df = l.d;
-        df.aff_nb = nbv_all;
-        df.nlive = nbv_all != nb ? nb : 0;
-        df.chunked = ts_mode;
-        const dim3 gf((unsigned)((ntile_all + per) * nbv_all));      // tiles, then the chunk roles
-        for (int it = 0; it <= c.L; ++it) {
-            const int traj = it == 0 ? 1 : it == 1 ? 2 : it == c.L ? 3 : 0;
-            df.sp_par = par;
-            Work wf = ctx->w;
-            if (it == 0) wf.Lpart = wf.Lpart0;                    // the start point's value of the S->E term: kept for the accept test
-            s->tail_count += (unsigned long long)ntile_all;
-            const unsigned long long target = s->tail_count;
-#define LAUNCH_TAILF(TSM_, NTC_) hipLaunchKernelGGL((k_se_chunk<TSM_, NTC_>), gf, dim3(256), 0, st, df, ctx->c, wf, c, s->ch, par, target, traj)
-            if (ts_mode == 1) {
-                if (d0.ntc == 1) LAUNCH_TAILF(1, 1); else if (d0.ntc == 6) LAUNCH_TAILF(1, 6); else LAUNCH_TAILF(1, 12);
+        if (p.ts_mode == 2) hipLaunchKernelGGL(k_sp_prep, dim3(nb), dim3(256), 0, st, l.d, ctx->w, s->ch, par);
+        prof_mark(0);
+        par = se_chunk_steps(0, c.L, par, true);
+        Dims dz = l.d;
+        dz.aff_nb = p.final_aff ? nb : 0;
+        hipLaunchKernelGGL(hmc_final_fn(d0.ntc), p.final_aff ? dim3(p.per * nb) : dim3(p.per, nb), dim3(WAVE), 0, st, dz, ctx->c, ctx->w, c, s->ch, par);
+        prof_mark(1);
+    } else {
+        l.d.chunked = 0;                       // k_se writes tile scalars only ahead of a chunked step
+        launch_se<1>(ctx, l, true);
+        l.d.chunked = p.ts_mode;               // stage 0 hands the trajectory over to the chunk kernel
+        launch_hmc(ctx, l, c, s->ch, 0);
+        s->vt_dirty = false;                   // (k_hmc_step<0> writes Work::Vt on its way)
+        if (p.inner == SweepPlan::SINGLE) {
+            for (int i = 1; i < c.L; ++i) {
+                launch_se<1>(ctx, l, true);
+                launch_hmc(ctx, l, c, s->ch, 1);
+            }
+        } else {
+            // the inner steps 1..L-1 by the chunk roles; stage 2 then gathers (Q s) and computes the priors and the
+            // Jacobian of the end point itself (gather_qs = 3)
+            int par = 0;
+            prof_mark(0);
+            if (p.inner == SweepPlan::LEAP) {
+                launch_leap(par, c.L - 1, 0);
+                par = (c.L - 1) & 1;
+            } else if (p.inner == SweepPlan::SE_CHUNK) {
+                par = se_chunk_steps(1, c.L - 1, par, false);
             } else {
-                if (d0.ntc == 1) LAUNCH_TAILF(2, 1); else if (d0.ntc == 6) LAUNCH_TAILF(2, 6); else LAUNCH_TAILF(2, 12);
-            }
-#undef LAUNCH_TAILF
-            if (it < c.L) par ^= 1;
-        }
-        {
-            Dims dz = l.d;
-            const bool aff = xcd_affinity_applies(per, nb);
-            dz.aff_nb = aff ? nb : 0;
-            const dim3 gz = aff ? dim3(per * nb) : dim3(per, nb);
-            switch (d0.ntc) {
-                case 1: hipLaunchKernelGGL(k_hmc_final<1>, gz, dim3(WAVE), 0, st, dz, ctx->c, ctx->w, c, s->ch, par); break;
-                case 6: hipLaunchKernelGGL(k_hmc_final<6>, gz, dim3(WAVE), 0, st, dz, ctx->c, ctx->w, c, s->ch, par); break;
-                default: hipLaunchKernelGGL(k_hmc_final<12>, gz, dim3(WAVE), 0, st, dz, ctx->c, ctx->w, c, s->ch, par); break;
-            }
-        }
-        if (prof0) {
-            (void)hipEventRecord(s->prof_ev[2 * s->prof_i + 1], st);
-            s->prof_i += 1;
-            s->prof_launches = c.L + 2;
-            s->prof_evals = c.L + 1;
-        }
-    } else {
-    l.d.chunked = 0;                       // k_se writes tile scalars only ahead of a chunked step
-    launch_se<1>(ctx, l, true);
-    l.d.chunked = ts_mode;                 // stage 0 hands the trajectory over to the chunk kernel
-    launch_hmc(ctx, l, c, s->ch, 0);
-    s->vt_dirty = false;                   // (k_hmc_step<0> writes Work::Vt on its way)
-    if (!chunked) {
-        for (int i = 1; i < c.L; ++i) {
-            launch_se<1>(ctx, l, true);
-            launch_hmc(ctx, l, c, s->ch, 1);
-        }
-    } else {
-        // all inner steps 1..L-1 by independent 64-lane chunks (k_hmc_chunk); stage 2 then gathers (Q s) and
-        // computes the priors and the Jacobian of the end point itself (gather_qs = 3)
-        const int per = d0.ntc + d0.Mp / WAVE;
-        const bool aff = (l.affinity & 1) && xcd_affinity_applies(per, nb);
-        int par = 0;
-        // chunk roles inside the gradient launch (k_se_chunk): 8 chains, one XCD each (checked at creation), the
-        // XCD-affine grid, no graph capture in progress (the ticket counter does not care, but keep the two apart)
-        const int ntile_se = d0.ntc * d0.nmt;
-        // not a multiple of 8 chains: the layout of the next multiple with the missing chains' blocks retiring at once,
-        // so that every chain is still whole on one XCD (nbv = chains of the layout)
-        const int nbv = (nb + 7) / 8 * 8;
-        const bool tail = s->hmc_tail && s->xcd_local && nbv > 0 && s->ngroups == 1 && (l.affinity & 1) && xcd_affinity_applies(ntile_se, nbv) &&
-                          !s->use_graph && (d0.ntc == 1 || d0.ntc == 6 || d0.ntc == 12) && ts_mode != 0;
-        // all of them in ONE persistent launch (k_leap: the tiles keep their cells in registers over the steps) when every
-        // workgroup of that launch can be resident at once -- its tiles wait for the roles.  (Reached only when the folded
-        // form above is switched off: the inner steps alone, between k_hmc_step<0> and k_se + k_hmc_step<2>.)
-        const bool prof = prof0;
-        if (prof) (void)hipEventRecord(s->prof_ev[2 * s->prof_i], st);
-        const bool leap = leap_ok;
-        if (leap) {
-            launch_leap(par, c.L - 1, 0);
-            par = (c.L - 1) & 1;
-        }
-        for (int i = 1; i < c.L && !leap; ++i) {
-            l.d.sp_par = par;
-            if (tail) {
-                Dims df = l.d;
-                df.aff_nb = nbv;
-                df.nlive = nbv != nb ? nb : 0;
-                const dim3 gf((unsigned)((ntile_se + per) * nbv));     // tiles, then the chunk roles
-                s->tail_count += (unsigned long long)ntile_se;         // what a chain's counter shows once this launch's tiles are in
-                const unsigned long long target = s->tail_count;
-#define LAUNCH_TAIL(TSM_, NTC_) hipLaunchKernelGGL((k_se_chunk<TSM_, NTC_>), gf, dim3(256), 0, st, df, ctx->c, ctx->w, c, s->ch, par, target, 0)
-                if (ts_mode == 1) {
-                    if (d0.ntc == 1) LAUNCH_TAIL(1, 1); else if (d0.ntc == 6) LAUNCH_TAIL(1, 6); else LAUNCH_TAIL(1, 12);
-                } else {
-                    if (d0.ntc == 1) LAUNCH_TAIL(2, 1); else if (d0.ntc == 6) LAUNCH_TAIL(2, 6); else LAUNCH_TAIL(2, 12);
+                for (int i = 1; i < c.L; ++i) {
+                    l.d.sp_par = par;
+                    launch_se<1>(ctx, l, true);
+                    Dims dc = l.d;
+                    dc.aff_nb = p.chunk_aff ? nb : 0;
+                    hipLaunchKernelGGL(hmc_chunk_fn(d0.ntc), p.chunk_aff ? dim3(p.per * nb) : dim3(p.per, nb), dim3(WAVE), 0, st, dc, ctx->c, ctx->w, c, s->ch, par);
+                    par ^= 1;
                 }
-#undef LAUNCH_TAIL
-                par ^= 1;
-                continue;
             }
-            launch_se<1>(ctx, l, true);
-            Dims dc = l.d;
-            dc.aff_nb = aff ? nb : 0;
-            const dim3 gc = aff ? dim3(per * nb) : dim3(per, nb);
-            switch (d0.ntc) {       // chunk count at compile time for the BASELINE sizes (NI, UK, SYN), rolled loops otherwise
-                case 1: hipLaunchKernelGGL(k_hmc_chunk<1>, gc, dim3(WAVE), 0, st, dc, ctx->c, ctx->w, c, s->ch, par); break;
-                case 6: hipLaunchKernelGGL(k_hmc_chunk<6>, gc, dim3(WAVE), 0, st, dc, ctx->c, ctx->w, c, s->ch, par); break;
-                case 12: hipLaunchKernelGGL(k_hmc_chunk<12>, gc, dim3(WAVE), 0, st, dc, ctx->c, ctx->w, c, s->ch, par); break;
-                default: hipLaunchKernelGGL(k_hmc_chunk<0>, gc, dim3(WAVE), 0, st, dc, ctx->c, ctx->w, c, s->ch, par); break;
-            }
-            par ^= 1;
+            l.d.sp_par = par;
+            prof_mark(1);
         }
-        l.d.sp_par = par;
-        if (prof) {
-            (void)hipEventRecord(s->prof_ev[2 * s->prof_i + 1], st);
-            s->prof_i += 1;
-            s->prof_launches = leap ? 1 : tail ? c.L - 1 : 2 * (c.L - 1);
-            s->prof_evals = c.L - 1;
-        }
+        l.d.chunked = 0;
+        launch_se<1>(ctx, l, true);
+        launch_hmc(ctx, l, c, s->ch, 2, /*gather_qs=*/p.inner == SweepPlan::SINGLE ? 0 : 3);
     }
-    l.d.chunked = 0;
-    launch_se<1>(ctx, l, true);
-    launch_hmc(ctx, l, c, s->ch, 2, /*gather_qs=*/chunked ? 3 : 0);
-    }   // !fold
     // [part 1] MultiScan(n_scans, Gibbs[move S->E, move E->I, occult S->E, occult E->I]):
     // per update [finalize previous | propose] then the log-ratio over the touched cells
     Dims d = l.d;
-    int advanced = 0, fpend_in_record = 0, recorded = 0;
-    {
-        const bool aff = (l.affinity & 2) && xcd_affinity_applies(c.nrb_d, nb);
-        d.aff_nb = aff ? nb : 0;
-        const dim3 gm = aff ? dim3(c.nrb_d * nb) : dim3(c.nrb_d, nb);
-        const size_t plds = k_move_pa2_lds_bytes(d);
-        // 64-day chunks a row of the series is held in by the proposing wave (moves_kernel.h; sampler_create caps T at 1024)
-        const int nch = d.Tp <= 6 * WAVE ? 6 : d.Tp <= 12 * WAVE ? 12 : 16;
-        auto pair_fn = nch == 6 ? k_move_pair<6> : nch == 12 ? k_move_pair<12> : k_move_pair<16>;
-        auto pa2_fn = nch == 6 ? k_move_pa2<6> : nch == 12 ? k_move_pa2<12> : k_move_pa2<16>;
-        auto pairs_fn = nch == 6 ? k_move_pairs<6> : nch == 12 ? k_move_pairs<12> : k_move_pairs<16>;
-        const size_t plds_pairs = k_move_pairs_lds_bytes(d);
-        if (s->pairs_lds_attr == 0)
-            s->pairs_lds_attr = hipFuncSetAttribute((const void *)pairs_fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                    (int)plds_pairs) == hipSuccess ? 1 : -1;
-        if (plds > 64 * 1024 && !s->move_lds_attr) {
-            (void)hipFuncSetAttribute((const void *)pair_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds);
-            (void)hipFuncSetAttribute((const void *)pa2_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds);
-            s->move_lds_attr = true;
-        }
-        int have_prev = 0, pbuf = 0;
-        if (s->moves_mode != 1 && c.n_scans > 30) s->moves_mode = 1;   // k_move_pair's launch tokens cover 62 launches per sweep
-        if (s->moves_mode != 1) {
-            // paired form: [finalize pending E->I-type | whole S->E-type update | propose E->I-type], then
-            // the log-ratio of the E->I-type proposal over its band: 4 launches per scan -- or 2, with the band
-            // evaluated by more workgroups of the pair launch itself (XCD-local hand-off, see pair_band_block): 8
-            // chains on one stream, one XCD each (checked at creation), every workgroup resident at once
-            const int npairs = 2 * c.n_scans;
-            int have_pre = 0;
-            int cus = 0;
-            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
-            const int nbv = (nb + 7) / 8 * 8;                            // as for k_se_chunk: the layout's chains
-            // 16 rows per band workgroup, two per wave; 32 (four per wave) where that is what lets every workgroup of the launch
-            // hold a CU: sixteen chains at UK-380 are (3 + 12) x 16 = 240 workgroups
-            int nband_fit = (d.M + 15) / 16;
-            if ((3 + nband_fit) * nbv > cus && (3 + (d.M + 31) / 32) * nbv <= cus) nband_fit = (d.M + 31) / 32;
-            const bool band_in_pair = s->moves_mode != 3 && s->xcd_local && nbv > 0 && s->ngroups == 1 && !s->use_graph &&
-                                      (3 + nband_fit) * nbv <= cus;
-            const int nbk = band_in_pair ? nbv : nb;
-            Dims dp = d;
-            dp.nlive = band_in_pair && nbv != nb ? nb : 0;
-            const int nband = band_in_pair ? nband_fit : 0;
-            SamplerCfg cp = c;
-            if (band_in_pair) cp.nrb_d = nband;                          // the band's partial sums: one pair per band workgroup
-            // every pair of the sweep and the closing step in ONE launch (k_move_pairs): the grid of a pair launch with band
-            // workgroups, resident for the whole sweep -- under the same conditions
-            const bool persistent = band_in_pair && s->moves_mode == 0 && npairs > 0 && s->pairs_lds_attr == 1;
-            if (persistent) {
-                // (its closing step also does what k_apply_fpend / k_record are launched for in the other forms)
-                hipLaunchKernelGGL(pairs_fn, dim3((3 + nband) * nbk), dim3(MVB), plds_pairs, st, dp, ctx->c, ctx->w, cp, s->ch, npairs, 1, nbk,
-                                   s->pair_debug, nband, s->pbar_count, s->record_events ? 3 : 1);
-                s->pbar_count += (unsigned)(npairs * (3 + nband));           // what every live chain's counter shows after this launch
-                advanced = 1;
-                recorded = 1;
+    d.aff_nb = p.move_aff ? nb : 0;
+    const dim3 gm = p.move_aff ? dim3(c.nrb_d * nb) : dim3(c.nrb_d, nb);
+    const size_t plds = k_move_pa2_lds_bytes(d);
+    int have_prev = 0, pbuf = 0;
+    if (p.moves == SweepPlan::SPLIT_MOVES) {
+        const auto pa2_fn = move_pa2_fn(p.nch);
+        for (int scan = 0; scan < c.n_scans; ++scan)
+            for (int slot = 0; slot < 4; ++slot) {
+                const MoveSpec spec{slot >= 2 ? 1 : 0, slot & 1, slot, scan};
+                hipLaunchKernelGGL(pa2_fn, gm, dim3(MVB), plds, st, d, ctx->c, ctx->w, c, s->ch, spec,
+                                   have_prev, pbuf);
+                pbuf ^= 1;
+                hipLaunchKernelGGL((k_move_delta<true>), gm, dim3(DELTA_THREADS), 0, st, d, ctx->c, ctx->w, c, s->ch, pbuf, 0);
+                have_prev = 1;
             }
-            for (int scan = 0; scan < (persistent ? 0 : c.n_scans); ++scan)
+        if (have_prev) {
+            // closing launch: finalize the last proposal and advance the sweep counter
+            const MoveSpec none{-2, 0, 0, 0};
+            hipLaunchKernelGGL(pa2_fn, gm, dim3(MVB), plds, st, d, ctx->c, ctx->w, c, s->ch, none, 1, pbuf);
+        }
+    } else {
+        // paired form: [finalize pending E->I-type | whole S->E-type update | propose E->I-type], then the log-ratio of the
+        // E->I-type proposal over its band -- by k_move_delta, or by the band workgroups of the pair launch itself
+        // (XCD-local hand-off, see pair_band_block)
+        const int npairs = 2 * c.n_scans;
+        const auto pair_fn = move_pair_fn(p.nch);
+        Dims dp = d;
+        dp.nlive = p.pair_nlive;
+        SamplerCfg cp = c;
+        if (p.nband) cp.nrb_d = p.nband;                             // the band's partial sums: one pair per band workgroup
+        if (p.moves == SweepPlan::PAIRS) {
+            // every pair of the sweep and the closing step in ONE launch, resident for the whole sweep (its closing step
+            // also does what k_apply_fpend / k_record are launched for in the other forms)
+            hipLaunchKernelGGL(move_pairs_fn(p.nch), dim3((3 + p.nband) * p.nbk), dim3(MVB), k_move_pairs_lds_bytes(d), st, dp, ctx->c, ctx->w, cp,
+                               s->ch, npairs, 1, p.nbk, s->pair_debug, p.nband, s->pbar_count, s->record_events ? 3 : 1);
+            s->pbar_count += (unsigned)(npairs * (3 + p.nband));     // what every live chain's counter shows after this launch
+        } else {
+            int have_pre = 0;
+            for (int scan = 0; scan < c.n_scans; ++scan)
                 for (int half = 0; half < 2; ++half) {
                     const int pair = 2 * scan + half;
                     const MoveSpec se{half, 0, 2 * half, scan}, nx{half, 1, 2 * half + 1, scan};
                     // a third role pre-draws the S->E-type proposal of the next pair (same sweep)
-                    const bool pre = (s->moves_mode == 0 || s->moves_mode == 3 || s->moves_mode == 4) && pair + 1 < npairs;
+                    const bool pre = p.pre && pair + 1 < npairs;
                     const int nh = (half + 1) & 1, nscan = scan + (half == 1 ? 1 : 0);
                     const MoveSpec se_next = pre ? MoveSpec{nh, 0, 2 * nh, nscan} : MoveSpec{-1, 0, 0, 0};
-                    hipLaunchKernelGGL(pair_fn, dim3(((pre ? 3 : 2) + nband) * nbk), dim3(MVB), plds, st, dp, ctx->c, ctx->w, cp, s->ch,
-                                       se, nx, se_next, have_prev, have_pre, pbuf, nbk, pair, s->pair_debug, nband);
+                    hipLaunchKernelGGL(pair_fn, dim3(((pre ? 3 : 2) + p.nband) * p.nbk), dim3(MVB), plds, st, dp, ctx->c, ctx->w, cp,
+                                       s->ch, se, nx, se_next, have_prev, have_pre, pbuf, p.nbk, pair, s->pair_debug, p.nband);
                     have_pre = pre ? 1 : 0;
                     pbuf ^= 1;
-                    if (!band_in_pair)
+                    if (!p.nband)
                         hipLaunchKernelGGL((k_move_delta<false>), gm, dim3(DELTA_THREADS), 0, st, d, ctx->c, ctx->w, c, s->ch, pbuf, 1);
                     have_prev = 1;
                 }
-            if (have_prev && !persistent) {
+            if (have_prev) {
                 const MoveSpec none{-1, 0, 0, 0}, close{-2, 0, 0, 0};
                 hipLaunchKernelGGL(pair_fn, dim3(nb), dim3(MVB), plds, st, d, ctx->c, ctx->w, cp, s->ch, none, close, none, 1,
                                    0, pbuf, nb, 62, 0, 0);
-                // the F band of the last accepted E->I update: by k_record's waves when it runs anyway
-                if (s->record_events) fpend_in_record = 1;
-                else hipLaunchKernelGGL(k_apply_fpend, gm, dim3(256), 0, st, d, ctx->c, ctx->w, c, s->ch);
-                advanced = 1;
-            }
-        } else {
-            for (int scan = 0; scan < c.n_scans; ++scan)
-                for (int slot = 0; slot < 4; ++slot) {
-                    const MoveSpec spec{slot >= 2 ? 1 : 0, slot & 1, slot, scan};
-                    hipLaunchKernelGGL(pa2_fn, gm, dim3(MVB), plds, st, d, ctx->c, ctx->w, c, s->ch, spec,
-                                       have_prev, pbuf);
-                    pbuf ^= 1;
-                    hipLaunchKernelGGL((k_move_delta<true>), gm, dim3(DELTA_THREADS), 0, st, d, ctx->c, ctx->w, c, s->ch, pbuf, 0);
-                    have_prev = 1;
-                }
-            if (have_prev) {
-                // closing launch: finalize the last proposal and advance the sweep counter
-                const MoveSpec none{-2, 0, 0, 0};
-                hipLaunchKernelGGL(pa2_fn, gm, dim3(MVB), plds, st, d, ctx->c, ctx->w, c, s->ch, none, 1, pbuf);
-                advanced = 1;
+                if (p.fpend == SweepPlan::F_APPLY) hipLaunchKernelGGL(k_apply_fpend, gm, dim3(256), 0, st, d, ctx->c, ctx->w, c, s->ch);
             }
         }
     }
     d.aff_nb = 0;
-    if (s->record_events && !recorded)
-        hipLaunchKernelGGL(k_record, dim3((d.M + 3) / 4, nb), dim3(256), 0, st, d, ctx->c, ctx->w, c, s->ch, advanced,
-                           fpend_in_record);
-    if (!advanced) hipLaunchKernelGGL(k_advance, dim3((nb + 63) / 64), dim3(64), 0, st, s->ch, b0, nb);
+    if (p.record)
+        hipLaunchKernelGGL(k_record, dim3((d.M + 3) / 4, nb), dim3(256), 0, st, d, ctx->c, ctx->w, c, s->ch, p.advance ? 0 : 1,
+                           p.fpend == SweepPlan::F_RECORD ? 1 : 0);
+    if (p.advance) hipLaunchKernelGGL(k_advance, dim3((nb + 63) / 64), dim3(64), 0, st, s->ch, b0, nb);
 }
 
 static int check_handoffs(seir_sampler *s);
@@ -2103,7 +1987,7 @@ extern "C" int seir_sampler_time_grad_kernel(seir_sampler *s, int32_t iters, flo
     if (!mean_ms || iters < 1) return fail(SEIR_ERR_INVALID, "bad iters/mean_ms");
     seir_ctx *ctx = s->ctx;
     LaunchCfg l = whole(ctx, s->cfg.B);
-    l.d.chunked = (s->hmc_chunked && s->cfg.L >= 3 && l.d.ntc <= CT_MAXC) ? (l.d.Mp <= 512 ? 1 : 2) : 0;   // as in the sweep
+    l.d.chunked = plan_sweep(sweep_inputs(s, 0)).ts_mode;   // as in the sweep
     launch_se<1>(ctx, l, true);
     HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
     for (int i = 0; i < iters; ++i) launch_se<1>(ctx, l, true);
@@ -2128,7 +2012,6 @@ extern "C" int seir_sampler_time_leapfrog(seir_sampler *s, int32_t sweeps, float
         s->prof_ev.push_back(e);
     }
     s->prof_i = 0;
-    s->prof_launches = 0;
     rc = seir_sampler_run(s, sweeps);
     const int recorded = s->prof_i;
     s->prof_i = -1;
@@ -2142,8 +2025,9 @@ extern "C" int seir_sampler_time_leapfrog(seir_sampler *s, int32_t sweeps, float
         sum += ms;
     }
     *mean_ms = (float)(sum / recorded);
-    if (launches) *launches = s->prof_launches;
-    if (evals) *evals = s->prof_evals;
+    const SweepPlan p = plan_sweep(sweep_inputs(s, 0));
+    if (launches) *launches = p.section_launches;
+    if (evals) *evals = p.section_evals;
     return 0;
 }
 
