@@ -13,6 +13,15 @@
 //     can restore the last snapshot (seir_sampler_restore).
 //   * A value that travels on its own carries its own flag (the hand-off words below); everything else is published
 //     after the producer's stores are acknowledged (s_waitcnt vmcnt(0)) with a counter, flag or token the consumer polls.
+//     Words may also vouch for plain stores, on the same terms: k_move_pairs' band workgroups write their rows of F, wait
+//     for the acknowledgement, and only then issue the words of their partial sums -- a role that has seen the words
+//     may load F.
+//   * Plain loads and the L1.  A consumer may read with plain loads what another workgroup wrote only if its CU's L1 cannot
+//     hold an older copy: the workgroup has the CU to itself (k_move_pairs' LDS request), one of its waves has emptied the
+//     L1 (agent-scope acquire fence: buffer_inv sc1 -- sc0 does not empty it on this part) after the workgroup's last load
+//     of the step before, and it loads nothing of that data again before the wait that declares it final.  Anything read
+//     earlier than that wait is read past the L1 (ld_l2, the word loads).  Each workgroup drops its own L1, once per step,
+//     by one wave: the roles where they meet (pair_chain_barrier), a band workgroup on its own (pair_band_next_step).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -169,6 +178,21 @@ template <int NDW> __device__ __forceinline__ void move_wait_ll(int *dst, const 
         dst[2 * lane] = (int)x[0].x;
         if (2 * lane + 1 < NDW) dst[2 * lane + 1] = (int)x[0].z;
     }
+}
+
+// k_move_pairs' form: what a band workgroup leaves for the roles of the next step -- its two partial sums {theta part,
+// constant part} -- as two words numbered by the token of the step that wrote them, one lane per band workgroup at the
+// reading end (the lanes beyond the last workgroup look at the last one's)
+__device__ __forceinline__ void pair_sums_store(uint4 *dst, double th, double cn, unsigned seq) {
+    ll_store(dst, th, seq);
+    ll_store(dst + 1, cn, seq);
+}
+__device__ __forceinline__ void pair_sums_wait(const uint4 *src, unsigned seq, unsigned *late, double &th, double &cn) {
+    const uint4 *pp[2] = {src, src + 1};
+    u32x4 x[2];
+    ll_wait<2, 1, HS_CHECK, HS_LIMIT>(pp, seq, late, x);
+    th = ll_value(x[0]);
+    cn = ll_value(x[1]);
 }
 
 // ---- k_move_pair's tokens: unique per (sweep, launch of the sweep) since lidx < 63, never 0.  31 bits: the top bit of the

@@ -1012,13 +1012,18 @@ __device__ __forceinline__ void pair_band_block(const Dims &d, const Consts &c, 
     dth = wave_sum(dth);
     if (lane == 0) sh_th[wave] = dth;
     __syncthreads();
+    // SOLO (k_move_pairs): the partial sums travel as hand-off words (Chains::llD), published at the very end of the step --
+    // after the F band: the roles of the NEXT step find in them both the sums and the word that F is final, and this
+    // workgroup takes no part in the roles' step barrier.  The launch-per-pair form leaves plain doubles for the next launch.
+    double dsum = 0.0;
     if (tid == 0) {
-        double *out = ch.Dpart + ((size_t)b * nband + bx) * 2;
-        double a = 0.0;
 #pragma unroll
-        for (int k = 0; k < MVW; ++k) a += sh_th[k];
-        out[0] = a;
-        out[1] = 0.0;
+        for (int k = 0; k < MVW; ++k) dsum += sh_th[k];
+        if (!SOLO) {
+            double *out = ch.Dpart + ((size_t)b * nband + bx) * 2;
+            out[0] = dsum;
+            out[1] = 0.0;
+        }
         QSTAMP(st_slot, st_step, 4);
         // the F band: once nobody reads F any more
         if (has_fp) {
@@ -1027,6 +1032,18 @@ __device__ __forceinline__ void pair_band_block(const Dims &d, const Consts &c, 
         }
         QSTAMP(st_slot, st_step, 5);
     }
+    auto publish = [&]() {
+        if (!SOLO) return;
+        // (the F rows are plain stores: acknowledged by the L2 before the words that vouch for them are issued)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (tid == 0) {
+            uint4 *out = ch.llD + (((size_t)buf * s.B + b) * nband + bx) * 2;
+            pair_sums_store(out, dsum, 0.0, token);
+            QSTAMP(st_slot, st_step, 10);
+        }
+    };
+    if (!has_fp) { publish(); return; }
     if (!has_fp) return;
     __syncthreads();
 #pragma unroll
@@ -1060,6 +1077,7 @@ __device__ __forceinline__ void pair_band_block(const Dims &d, const Consts &c, 
             }
         }
     }
+    publish();
     (void)sh_cn;
 }
 
@@ -1140,7 +1158,7 @@ template <int NCH, bool SOLO>
 __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const Work &w, const SamplerCfg &s, const Chains &ch,
                                           MoveSpec se, MoveSpec next, MoveSpec se_next, int have_prev, int have_pre, int pbuf,
                                           int lidx, int dbg, int nband, int nroles, int slot, int b, int fin = 0,
-                                          unsigned sweep0 = 0u) {
+                                          unsigned sweep0 = 0u, int lprev = 0) {
     extern __shared__ __attribute__((aligned(16))) int dyn_i[];                     // rg [M] | rt [M]
     __shared__ MvShared sm_se, sm_nx;
     __shared__ Move pendA, pendB;
@@ -1216,13 +1234,36 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
         if (tid >= 128 && tid < 128 + MOVE_DW) ld_i = reinterpret_cast<const int *>(ch.mvfix + (size_t)pbuf * s.B + b)[tid - 128];
         if (tid == 192) ld_i = ch.mvsel[(size_t)pbuf * s.B + b];
         if (tid >= 196 && tid < 200) ld_d = ch.Down[(((size_t)pbuf * 2 + ((tid - 196) >> 1)) * s.B + b) * 2 + ((tid - 196) & 1)];
-        if (tid < s.nrb_d) {
-            dth0 = ch.Dpart[((size_t)b * s.nrb_d + tid) * 2];
-            dcn0 = ch.Dpart[((size_t)b * s.nrb_d + tid) * 2 + 1];
+        if (!SOLO) {
+            if (tid < s.nrb_d) {
+                dth0 = ch.Dpart[((size_t)b * s.nrb_d + tid) * 2];
+                dcn0 = ch.Dpart[((size_t)b * s.nrb_d + tid) * 2 + 1];
+            }
+            for (int i = tid + MVB; i < s.nrb_d; i += MVB) {
+                dth0 += ch.Dpart[((size_t)b * s.nrb_d + i) * 2];
+                dcn0 += ch.Dpart[((size_t)b * s.nrb_d + i) * 2 + 1];
+            }
         }
-        for (int i = tid + MVB; i < s.nrb_d; i += MVB) {
-            dth0 += ch.Dpart[((size_t)b * s.nrb_d + i) * 2];
-            dcn0 += ch.Dpart[((size_t)b * s.nrb_d + i) * 2 + 1];
+    }
+    // k_move_pairs: the band workgroups are not part of the step barrier -- what they left in the step before comes as
+    // hand-off words (Chains::llD, numbered by THAT step's token), and this wait is the only thing that orders them before
+    // this step: the sums, and the F band they applied before they published (F is first read long after this wait, with
+    // plain loads: the L1 was emptied at the barrier and has seen no line of F since).  One lane per band workgroup; up to 64
+    // of them: the LAST wave, so that the waves that draw the uniforms below do not stand behind this wait (the sum over
+    // the lanes is the same in any wave); more: thread i at workgroup i, as the plain loads above
+    constexpr int DW0 = SOLO ? MVB - WAVE : 0;                 // first thread of the wave that holds the sums (nrb_d <= 64)
+    if (SOLO && have_prev) {
+        static_assert(MVB >= 253, "one thread per band workgroup (plan_sweep: 3 + nband <= 256)");
+        const bool few = s.nrb_d <= WAVE;
+        const int i0 = few ? tid - DW0 : tid;
+        if (few ? tid >= DW0 : (tid & ~(WAVE - 1)) < s.nrb_d) {   // (uniform in a wave)
+            const uint4 *src = ch.llD + (((size_t)pbuf * s.B + b) * s.nrb_d + min(i0, s.nrb_d - 1)) * 2;
+            double th, cn;
+            pair_sums_wait(src, pair_token(ch.sweep[b], lprev), ch.late + ch.late_fatal + b, th, cn);
+            if (i0 < s.nrb_d) { dth0 = th; dcn0 = cn; }
+#ifdef PAIR_STAMPS
+            if (tid == DW0 && b_stamp == 0 && lidx < 12) ch.leap_st[((size_t)slot * 12 + lidx) * 16 + 7] = __builtin_amdgcn_s_memrealtime();
+#endif
         }
     }
     const bool pre_avail = do_se && have_pre;
@@ -1258,9 +1299,9 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
         if (tid == 328 || tid == 329) pre_down[tid - 328] = ld_d;
     }
     if (tid < LDSTAB_N) ltab[tid] = ld_t;
-    if (have_prev && s.nrb_d <= WAVE && tid < WAVE) {
+    if (have_prev && s.nrb_d <= WAVE && tid >= DW0 && tid < DW0 + WAVE) {
         const double a = wave_sum(dth0), a2 = wave_sum(dcn0);
-        if (tid == 0) { s_dsum[0] = 0.0 + a; s_dsum[1] = 0.0 + a2; }
+        if (tid == DW0) { s_dsum[0] = 0.0 + a; s_dsum[1] = 0.0 + a2; }
     }
     if (role != 0) {
         // the totals are in registers: tell role 0 it may start writing
@@ -1544,10 +1585,13 @@ __global__ __launch_bounds__(MVB) void k_move_pair(Dims d, Consts c, Work w, Sam
 // k_move_pairs: EVERY pair of a sweep, and the closing step, in ONE launch -- the grid of k_move_pair with band
 // workgroups (3 roles + nband band workgroups per chain, every workgroup resident, a chain's workgroups on one XCD),
 // each workgroup walking through the steps k_move_pair is launched for.  What a launch boundary gave is restated per
-// chain: a workgroup that has finished step i drains its stores (they are acknowledged by the XCD's L2), counts in on
-// the chain's counter (Chains::pbar) and waits until it shows them all; then it drops its CU's L1 and scalar
-// cache, so that the plain loads of step i + 1 see what any workgroup of the chain wrote in step i, exactly as the
-// loads of a new launch would.  Inside a step nothing changes: the hand-offs of k_move_pair (tokens unique per sweep
+// chain, for the three ROLES: a role that has finished step i drains its stores (they are acknowledged by the XCD's L2),
+// counts in on the chain's counter (Chains::pbar) and waits until it shows all three; it drops its CU's L1, so that the
+// plain loads of step i + 1 see what any role wrote in step i, exactly as the loads of a new launch would.  The band
+// workgroups stay out of that barrier: what they leave for step i + 1 -- their partial sums, and F with the step's band
+// applied -- is vouched for by hand-off words (Chains::llD) that every role waits for at its entry to step i + 1, and
+// they themselves go on at once (pair_band_next_step): the roles meet when the last ROLE is done, not ~2 us after the
+// last of 27 workgroups.  Inside a step nothing changes: the hand-offs of k_move_pair (tokens unique per sweep
 // and step, reads past the L1 of everything written in the same step).  What it saves is what a launch costs a
 // latency chain like this one: the dispatch ramp, the kernel-argument and first-touch misses, a cold instruction
 // cache for a path of a few thousand instructions executed once, and the drain at the end.
@@ -1556,7 +1600,7 @@ __global__ __launch_bounds__(MVB) void k_move_pair(Dims d, Consts c, Work w, Sam
 constexpr int PBAR_STRIDE = 64;                               // 32-bit words per chain: the counter in a line of its own (and a spare line:
                                                               // a flag there, raised by the last arrival and polled instead of the
                                                               // counter, changed nothing -- 0.3344 against 0.3342 ms per sweep)
-// `target`: what the chain's counter shows once every workgroup of the chain has finished the step -- the counter runs on
+// `target`: what the chain's counter shows once every role of the chain has finished the step -- the counter runs on
 // over the launches (the host knows how many steps have been counted: seir_sampler::pbar_count), so the last one in
 // has nothing to reset or to raise, and the others poll the counter itself
 __device__ __forceinline__ void pair_chain_barrier(const Chains &ch, int b, unsigned target, int b_stamp = 0, int st_slot = 0,
@@ -1590,6 +1634,36 @@ __device__ __forceinline__ void pair_chain_barrier(const Chains &ch, int b, unsi
     __syncthreads();
 }
 
+// A band workgroup between two steps: no arrival, no wait -- its next step begins with the wait for role 0's first token.
+// It only drops its own L1 (one wave, as in pair_chain_barrier), so that the plain loads of the next step cannot return a
+// line of the planes cached in this one: every load of this step has come back (the barriers behind its last use), the
+// planes are not loaded again before role 0 declares them final (token 5), and F -- loaded earlier -- is written by this
+// workgroup alone, its stores acknowledged before the hand-off words of pair_band_block were issued.
+__device__ __forceinline__ void pair_band_next_step() {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __syncthreads();
+}
+
+// Test hooks that only DELAY (seir_sampler_desc::debug_pair, k_move_pairs): ~30 us of sleep at the entry of every step in
+// 16: the band workgroups, 32: role 0, 64: roles 1 and 2, 128: a third of all workgroups, drawn again for every step --
+// so that a step overtaking its neighbour shows in the bits (tests/test_pair_dataflow_gpu.py)
+constexpr int PAIR_DBG_DELAYS = 16 | 32 | 64 | 128;
+__device__ __forceinline__ void pair_debug_delay(int dbg, int slot, int nroles, int pair, int b) {
+    const bool band = slot >= nroles, role0 = slot == nroles - 1;
+    bool on = ((dbg & 16) && band) || ((dbg & 32) && role0) || ((dbg & 64) && !band && !role0);
+    if (dbg & 128) {
+        unsigned h = (unsigned)slot * 0x9e3779b1u ^ (unsigned)pair * 0x85ebca6bu ^ (unsigned)b * 0xc2b2ae35u;
+        h ^= h >> 15; h *= 0x2c1b3c6du; h ^= h >> 12;
+        on = on || h % 3u == 0u;
+    }
+    if (on)
+        for (int i = 0; i < 9; ++i) __builtin_amdgcn_s_sleep(127);
+}
+
 template <int NCH>
 __global__ __launch_bounds__(MVB) void k_move_pairs(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, int npairs, int pre_on,
                                                     int nbk, int dbg, int nband, unsigned pbase, int fin) {
@@ -1610,13 +1684,16 @@ __global__ __launch_bounds__(MVB) void k_move_pairs(Dims d, Consts c, Work w, Sa
         const MoveSpec se = closing ? none : MoveSpec{half, 0, 2 * half, scan};
         const MoveSpec nx = closing ? MoveSpec{-2, 0, 0, 0} : MoveSpec{half, 1, 2 * half + 1, scan};
         const MoveSpec se_next = pre ? MoveSpec{nh, 0, 2 * nh, nscan} : none;
+        if (dbg & PAIR_DBG_DELAYS) pair_debug_delay(dbg, slot, nroles, pair, b);
         pair_step<NCH, true>(d, c, w, s, ch, se, nx, se_next, pair > 0 ? 1 : 0, (pair > 0 && pre_on && !closing) ? 1 : 0, pair & 1,
-                       closing ? 62 : pair, closing ? 0 : dbg, (closing && !fin) ? 0 : nband, nroles, slot, b, closing ? fin : 0, sweep0);
+                       closing ? 62 : pair, closing ? 0 : dbg, (closing && !fin) ? 0 : nband, nroles, slot, b, closing ? fin : 0, sweep0,
+                       pair - 1);
         if (closing) break;
         const int b_stamp = b - d.b0;
         (void)b_stamp;
         QSTAMP(slot, pair, 8);
-        pair_chain_barrier(ch, b, pbase + (unsigned)((pair + 1) * (nroles + nband)), b_stamp, slot, pair);
+        if (slot < nroles) pair_chain_barrier(ch, b, pbase + (unsigned)((pair + 1) * nroles), b_stamp, slot, pair);
+        else pair_band_next_step();
         QSTAMP(slot, pair, 9);
     }
 }

@@ -120,6 +120,13 @@ struct Chains {
                                                          //     spatial effects | psi (Work::ea, eb, sp, scal[SC_PSI])
     uint4 *llmv;                                         // [2][B][32] k_move_pair(s) with band workgroups: role 1's proposal descriptor (Chains::mv)
                                                          //     as hand-off words, two dwords apiece, numbered by the launch's token
+    uint4 *llD;                                          // [2][B][nrb_d][2] k_move_pairs: the band workgroups' partial sums (Dpart) as hand-off
+                                                         //     words numbered by the step's token, by step parity.  A band workgroup publishes
+                                                         //     them after it has applied the step's F band: the words also say "F is final".
+                                                         //     Why the writer of step i + 2 cannot overtake a reader of step i: a band workgroup
+                                                         //     writes only after role 0's last token of its step, role 0 enters step i + 2 through
+                                                         //     the roles' barrier of step i + 1, and every role reads the words of step i at its
+                                                         //     entry to step i + 1
     unsigned *hand2;                                     // [B] the same token for role 2 (pre-drawn S->E-type proposal)
     Move *mvs;                                           // [2][B] S->E-type proposal pre-drawn for the next launch (k_move_pair, role 2)
     double *DownS;                                       // [2][B][2] its own-rows log-ratio {theta, const}

@@ -1029,8 +1029,8 @@ struct seir_sampler {
     unsigned long long leap_steps = 0;   // leapfrog steps done by all k_leap launches so far (what Chains::leap's flags show)
     bool xcd_local = false;       // blocks with the same id mod 8 share an XCD (k_xcc_probe at creation)
     unsigned long long tail_count = 0;   // tiles per chain counted in by all k_se_chunk launches so far (Chains::tail)
-    unsigned pbar_count = 0;      // workgroup arrivals every chain's step counter (Chains::pbar) has seen over all k_move_pairs launches
-    int pair_debug = 0;           // debug_pair: test hooks of k_move_pair's handshake (1 late, 2 absent role 1)
+    unsigned pbar_count = 0;      // role arrivals every chain's step counter (Chains::pbar) has seen over all k_move_pairs launches
+    int pair_debug = 0;           // debug_pair: test hooks of k_move_pair's handshake (1 late, 2 absent role 1; 16..128: delays per step, k_move_pairs)
     int moves_mode = 0;           // (moves_form: the mode in force) 0 = paired updates (k_move_pair) with the S->E-type proposal pre-drawn one pair ahead -- every pair of a
                                   //     sweep in one launch (k_move_pairs) where band workgroups can be part of it, else one launch per
                                   //     pair (4: always one launch per pair; 3: the same, never with band workgroups in the pair launch);
@@ -1235,6 +1235,7 @@ extern "C" int seir_sampler_create(seir_ctx *ctx, const seir_sampler_desc *ds, s
     S_HAND(ch.DownS, (size_t)2 * B * 2);
     S_HAND(ch.prev, (size_t)2 * B);
     S_HAND(ch.Dpart, (size_t)B * c.nrb_d * 2);
+    S_HAND(ch.llD, (size_t)2 * B * c.nrb_d * 2);           // (band workgroups per chain <= nrb_d: plan_sweep)
     S_HAND(ch.Down, (size_t)2 * 2 * B * 2);
     S_STATE(ch.sweep, (size_t)B); S_STATE(ch.slot0, 1);
     S_ALLOC(ch.tr_theta, (size_t)c.cap * B * d.P);
@@ -1788,7 +1789,7 @@ static void enqueue_sweep(seir_sampler *s, int g) {
             // also does what k_apply_fpend / k_record are launched for in the other forms)
             hipLaunchKernelGGL(move_pairs_fn(p.nch), dim3((3 + p.nband) * p.nbk), dim3(MVB), k_move_pairs_lds_bytes(d), st, dp, ctx->c, ctx->w, cp,
                                s->ch, npairs, 1, p.nbk, s->pair_debug, p.nband, s->pbar_count, s->record_events ? 3 : 1);
-            s->pbar_count += (unsigned)(npairs * (3 + p.nband));     // what every live chain's counter shows after this launch
+            s->pbar_count += (unsigned)(npairs * 3);                 // what every live chain's counter shows after this launch: the roles' arrivals
         } else {
             int have_pre = 0;
             for (int scan = 0; scan < c.n_scans; ++scan)
@@ -1865,7 +1866,7 @@ extern "C" int seir_sampler_run(seir_sampler *s, int32_t n) {
 // a workgroup went on without what it waited for: never seen outside the test hooks, and then the draws are not to be
 // trusted -- the next read of the trace fails loudly instead of delivering them.
 static int check_handoffs(seir_sampler *s) {
-    if (s->pair_debug != 0) return 0;                     // the hooks make roles late on purpose
+    if ((s->pair_debug & 15) != 0) return 0;              // the hooks make roles late on purpose (16..128 only delay: checked)
     // only the waits a workgroup cannot recover from (band tokens, k_se_chunk's tile flag, k_leap's flags, k_move_pairs'
     // step barrier); a late speculative role of k_move_pair is benign -- role 0 draws the proposal itself, the traces
     // are the same -- and only counted

@@ -246,7 +246,9 @@ typedef struct {
                                        occult.  A disabled sub-kernel still draws its proposal (the random
                                        streams do not shift) but is always rejected -- used by the
                                        invariant-distribution tests to run each MH kernel alone */
-    int32_t debug_pair;             /* test hooks of k_move_pair's handshake: 1 late, 2 absent speculative role */
+    int32_t debug_pair;             /* test hooks of k_move_pair's handshake: 1 late, 2 absent speculative role (4, 8: the
+                                       pre-drawing one); of k_move_pairs' steps, delays only: 16 band workgroups, 32 role 0,
+                                       64 roles 1 and 2, 128 a third of all workgroups drawn again per step */
     int32_t leap_rows;              /* tile shape of the persistent leapfrog launch (hmc_mode 0, 4, 5; speed only, same draws up
                                        to the order of summation): 0 = auto -- workgroups of 24 rows x 64 days (six rows per
                                        wave) where ceil64(M) is a multiple of 24 with M <= 512 and T in six 64-day chunks

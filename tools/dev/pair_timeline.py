@@ -41,7 +41,7 @@ with SeirModel(cov, init, max_chains=B) as model:
         names = {0: "role 1", 1: "role 2", R0: "role 0", NR: "band 0", NR + 11: "band 11", NR + 23: "band 23"}
         if NR == 4:
             names[2] = "role 3"
-        print(f"moves={moves}; ns after role 0 entered the step (median of 9 sweeps); stamps: 0 entry, roles: 6 entry loads issued, 12 back, 13 past the barrier, 14 uniforms drawn, 15 pending descriptors in LDS; 1..5 inside, 8 step done, 10 drained, 11 flag seen, 9 L1 dropped")
+        print(f"moves={moves}; ns after role 0 entered the step (median of 9 sweeps); stamps: 0 entry, roles: 6 entry loads issued, 12 back, 13 past the barrier, 14 uniforms drawn, 15 pending descriptors in LDS; 7 the band's words of the step before seen (their wait began at 6); 1..5 inside, 8 step done; roles: 10 drained, 11 the roles' barrier released, 9 L1 dropped; band: 10 partial sums published as words (F band applied), 9 own L1 dropped")
         for step in (0, 1, 4, 5, 8, 9):
             print(f"-- step {step}")
             for slot, name in names.items():
@@ -53,3 +53,9 @@ with SeirModel(cov, init, max_chains=B) as model:
         who = st[:, :, :10, 8].argmax(axis=1)
         print("last workgroup done (ns after role 0's entry):", med(last).round().tolist())
         print("which slot is last (last sweep):", who[-1].tolist())
+        roles = [0, 1, R0]
+        print("roles' barrier: last role done -> released (ns):", med(st[:, roles, :10, 11].max(axis=1) - st[:, roles, :10, 8].max(axis=1)).round().tolist())
+        if (st[:, R0, 1:10, 7] > 0).all():
+            print("role 0: entry -> band's words of the step before seen (ns):", med(st[:, R0, 1:10, 7] - st[:, R0, 1:10, 0]).round().tolist())
+            print("last band workgroup published -> role 0 entered the next step (ns; > 0: the words were waiting):",
+                  med(st[:, R0, 1:10, 0] - st[:, NR:, 0:9, 10].max(axis=1)).round().tolist())
