@@ -43,7 +43,7 @@ class SeirSamplerDesc(ctypes.Structure):
         # ABI v2: launch form and test hooks, all-zero = defaults
         ("moves_mode", ctypes.c_int32), ("hmc_mode", ctypes.c_int32), ("use_graph", ctypes.c_int32),
         ("chain_groups", ctypes.c_int32), ("disable_mask", ctypes.c_int32), ("debug_pair", ctypes.c_int32),
-        ("leap_rows", ctypes.c_int32), ("reserved", ctypes.c_int32 * 1),
+        ("leap_rows", ctypes.c_int32), ("thin", ctypes.c_int32),
     ]
 
 
@@ -124,6 +124,8 @@ _SIGNATURES = {
     "seir_sampler_refresh": (ctypes.c_int, [ctypes.c_void_p]),
     "seir_sampler_reset_trace": (ctypes.c_int, [ctypes.c_void_p]),
     "seir_sampler_reset_trace_at": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
+    "seir_sampler_set_thin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
+    "seir_sampler_thin": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     "seir_sampler_read_trace_async": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, c_double_p,
                                                      ctypes.c_void_p, c_double_p, c_double_p]),
     "seir_sampler_trace_wait": (ctypes.c_int, [ctypes.c_void_p]),

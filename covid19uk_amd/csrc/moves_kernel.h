@@ -527,7 +527,7 @@ __global__ __launch_bounds__(MVB) void k_move_pa2(Dims d, Consts c, Work w, Samp
     if (bx == 0 && have_prev && tid == 0) {
         const double *hs = ch.hs + (size_t)b * NHS;
         hs_th = hs[HS_LP_THETA]; hs_cn = hs[HS_LP_CONST];
-        tr_slot = ch.sweep[b] - ch.slot0[0];
+        tr_slot = chain_trace_slot(s, ch, ch.sweep[b]);
     }
     if (have_prev) {
         if (tid == 0) pend = ch.mv[(size_t)pbuf * s.B + b];
@@ -1086,9 +1086,10 @@ __device__ __forceinline__ void pair_band_block(const Dims &d, const Consts &c, 
 // (record != 0) those rows' events written to the trace in the reference's [M][T][3] order.  Role 0 raises token 4 when
 // the pending update is decided (Chains::fpend) and token 5 when its rows are in the planes; the workgroup's L1 was
 // emptied when the step began and it has loaded nothing of the planes since: plain loads.
-// sweep0: the chain's sweep counter as the launch found it (role 0 advances it in this very step).
+// slot: the sweep's trace slot, from the sweep counter as the launch found it (role 0 advances it in this very step); a
+// sweep that is not recorded (thinning, trace_slot.h) still applies the F band and only skips the copy.
 __device__ __forceinline__ void pair_band_finish(const Dims &d, const Consts &c, const Work &w, const SamplerCfg &s,
-                                                 const Chains &ch, int b, int bx, int nband, unsigned token, unsigned sweep0,
+                                                 const Chains &ch, int b, int bx, int nband, unsigned token, unsigned slot,
                                                  int record) {
     __shared__ Move fp;
     int tid = threadIdx.x;
@@ -1102,7 +1103,6 @@ __device__ __forceinline__ void pair_band_finish(const Dims &d, const Consts &c,
     move_copy_l2(&fp, ch.fpend + b, 128);
     if (tid == 0) wait_token(done + 5, token, ch.late + ch.late_fatal + b);
     __syncthreads();
-    const unsigned slot = sweep0 - ch.slot0[0];
     for (int m = r_lo + wave; m < r_hi; m += MVW) {
         if (fp.valid == 1) {
             double coef[MMAX];
@@ -1158,7 +1158,7 @@ template <int NCH, bool SOLO>
 __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const Work &w, const SamplerCfg &s, const Chains &ch,
                                           MoveSpec se, MoveSpec next, MoveSpec se_next, int have_prev, int have_pre, int pbuf,
                                           int lidx, int dbg, int nband, int nroles, int slot, int b, int fin = 0,
-                                          unsigned sweep0 = 0u, int lprev = 0) {
+                                          unsigned sweep0 = 0u, int lprev = 0, unsigned tslot = TRACE_NOT_RECORDED) {
     extern __shared__ __attribute__((aligned(16))) int dyn_i[];                     // rg [M] | rt [M]
     __shared__ MvShared sm_se, sm_nx;
     __shared__ Move pendA, pendB;
@@ -1177,7 +1177,7 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
     if (slot >= nroles) {                                  // band workgroups (the highest block ids)
         if (nband == 0) return;
         if (fin) {                                         // the closing step of k_move_pairs: they finish the sweep
-            pair_band_finish(d, c, w, s, ch, b, slot - nroles, nband, pair_token(sweep0, lidx), sweep0, fin & 2);
+            pair_band_finish(d, c, w, s, ch, b, slot - nroles, nband, pair_token(sweep0, lidx), tslot, fin & 2);
             return;
         }
         const unsigned tok = pair_token(ch.sweep[b], lidx);
@@ -1280,7 +1280,7 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
     if (role == 0 && tid == 0) {
         const double *hs = ch.hs + (size_t)b * NHS;
         hs_th = hs[HS_LP_THETA]; hs_cn = hs[HS_LP_CONST];
-        tr_slot = ch.sweep[b] - ch.slot0[0];
+        tr_slot = SOLO ? tslot : chain_trace_slot(s, ch, ch.sweep[b]);
     }
     psi = w.scal[(size_t)b * NSCAL + SC_PSI];
     QSTAMP(slot, lidx, 6);
@@ -1675,6 +1675,8 @@ __global__ __launch_bounds__(MVB) void k_move_pairs(Dims d, Consts c, Work w, Sa
     // fin: in the closing step the band workgroups apply the F band of the last accepted E->I-type update (1) and write
     // the sweep's events to the trace (3): k_apply_fpend's / k_record's work, without their launch
     const unsigned sweep0 = ch.sweep[b];
+    // the sweep's trace slot, once for all its steps (role 0's move results, the band workgroups' copy of the events)
+    const unsigned tslot = chain_trace_slot(s, ch, sweep0);
     for (int pair = 0; pair <= npairs; ++pair) {
         // as enqueue_sweep launches k_move_pair: scan = pair / 2, the first half of a scan is the event-time moves, the second
         // the occults; step npairs is the closing one: role 0 finalizes the last E->I-type proposal and advances the sweep counter
@@ -1687,7 +1689,7 @@ __global__ __launch_bounds__(MVB) void k_move_pairs(Dims d, Consts c, Work w, Sa
         if (dbg & PAIR_DBG_DELAYS) pair_debug_delay(dbg, slot, nroles, pair, b);
         pair_step<NCH, true>(d, c, w, s, ch, se, nx, se_next, pair > 0 ? 1 : 0, (pair > 0 && pre_on && !closing) ? 1 : 0, pair & 1,
                        closing ? 62 : pair, closing ? 0 : dbg, (closing && !fin) ? 0 : nband, nroles, slot, b, closing ? fin : 0, sweep0,
-                       pair - 1);
+                       pair - 1, tslot);
         if (closing) break;
         const int b_stamp = b - d.b0;
         (void)b_stamp;

@@ -23,6 +23,7 @@
 #include "handoff.h"
 #include "logprob_kernels.h"
 #include "philox.h"
+#include "trace_slot.h"
 
 namespace seir {
 
@@ -50,6 +51,7 @@ struct SamplerCfg {
     int nrb_d;        // row blocks of k_move_delta / k_move_pa2
     int ev16;         // 1: samples/seir recorded as uint16 (half the burst buffer and half the bytes over PCIe)
     int disable_mask; // bit 0 HMC, bits 1..4 the four event sub-kernels: proposal drawn, always rejected
+    int thin;         // thinning interval k >= 1: the last sweep of every group of k is recorded (trace_slot.h)
 };
 
 struct Move {
@@ -144,6 +146,12 @@ struct Chains {
     double *tr_hmc;                                      // [cap][B][3]  is_accepted, target_log_prob, step_size
     double *tr_mv;                                       // [cap][B][4][NMVTR]
 };
+
+// the trace slot of the sweep numbered `sweep` (a value >= s.cap: not recorded).  Uniform over the workgroup; once per
+// workgroup and sweep, outside the step loops
+__device__ __forceinline__ unsigned chain_trace_slot(const SamplerCfg &s, const Chains &ch, unsigned sweep) {
+    return trace_slot(sweep, ch.slot0[0], (unsigned)s.thin, (unsigned)s.cap);
+}
 
 __device__ inline RngKey rng_key(const SamplerCfg &s, const Chains &ch, int b) {
     return RngKey{s.k0, s.k1, (uint32_t)(s.chain0 + b), ch.sweep[b]};
@@ -582,7 +590,7 @@ __global__ __launch_bounds__(HB) void k_hmc_step(Dims d, Consts c, Work w, Sampl
             // trace_results_fn reads step_size from the kernel results AFTER DualAveragingStepSizeAdaptation
             // has written new_step_size back (inference.py:255-261): the traced value is the step size the
             // NEXT sweep will use, which is what run_mcmc averages over the last 25 draws (inference.py:439-441)
-            const unsigned slot = ch.sweep[b] - ch.slot0[0];
+            const unsigned slot = chain_trace_slot(s, ch, ch.sweep[b]);
             if (slot < (unsigned)s.cap) {
                 double *tr = ch.tr_hmc + ((size_t)slot * s.B + b) * 3;
                 tr[0] = (double)acc;
@@ -775,7 +783,7 @@ __global__ __launch_bounds__(HB) void k_hmc_step(Dims d, Consts c, Work w, Sampl
     STAMP(9);
     if (STAGE == 2) {
         // constrained draw -> trace (param_bijector.inverse(draws[0]), inference.py:375)
-        const unsigned slot = ch.sweep[b] - ch.slot0[0];
+        const unsigned slot = chain_trace_slot(s, ch, ch.sweep[b]);
         if (slot < (unsigned)s.cap) {
             double *tr = ch.tr_theta + ((size_t)slot * s.B + b) * d.P;
 #pragma unroll
@@ -1583,7 +1591,7 @@ __device__ __forceinline__ void hmc_final_apply(const Dims &d, const Consts &c, 
     double ua, ub;
     rng_uniform2(key, RS_HMC_ACCEPT, 0u, ua, ub);
     const bool acc = cold_log(ua) < log_ratio && !(s.disable_mask & 1);            // NaN compares false -> reject
-    const unsigned slot = ch.sweep[b] - ch.slot0[0];
+    const unsigned slot = chain_trace_slot(s, ch, ch.sweep[b]);
     double *tr = slot < (unsigned)s.cap ? ch.tr_theta + ((size_t)slot * s.B + b) * d.P : nullptr;
     const double n1 = n_old + 1.0;
     auto welford = [&](int i, double x) {                      // running variance with the new state (ddof 0)
@@ -2792,7 +2800,7 @@ __global__ __launch_bounds__(256) void k_record(Dims d, Consts c, Work w, Sample
     debug_skew(d);
     const int b = d.b0 + blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int m = blockIdx.x * 4 + wave;
-    const unsigned slot = ch.sweep[b] - (unsigned)advanced - ch.slot0[0];
+    const unsigned slot = chain_trace_slot(s, ch, ch.sweep[b] - (unsigned)advanced);
     if (apply_f) {                                           // uniform
         if (threadIdx.x == 0) fp = ch.fpend[b];
         __syncthreads();
@@ -2859,9 +2867,9 @@ __global__ __launch_bounds__(256) void k_range_totals(Dims d, Work w, SamplerCfg
     }
 }
 
-// slot0 = sweep counter of chain 0 minus `first`: the next sweep is recorded in trace slot `first`
-// (unsigned arithmetic: slot = sweep - slot0 stays right across the wrap)
-__global__ void k_set_slot0(Chains ch, unsigned first) { ch.slot0[0] = ch.sweep[0] - first; }
+// slot0 = sweep counter of chain 0 minus `first` * thin: the next sweep opens a group of `thin` sweeps whose last one is
+// recorded in trace slot `first` (trace_slot.h; unsigned arithmetic: exact across the wrap for thin a power of two)
+__global__ void k_set_slot0(Chains ch, unsigned first, unsigned thin) { ch.slot0[0] = trace_slot0(ch.sweep[0], first, thin); }
 
 __global__ void k_advance(Chains ch, int b0, int nb) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -1052,6 +1052,7 @@ struct seir_sampler {
     int poison_chain = 0;
     unsigned poison_count = 0;
     int hmc_mode = 0;                 // the launch forms in force (seir_sampler_set_launch_form)
+    int thin_pending = 1;             // seir_sampler_set_thin: becomes cfg.thin at the next trace reset (Chains::slot0 is encoded for cfg.thin)
 };
 
 template <typename T>
@@ -1152,6 +1153,7 @@ extern "C" int seir_sampler_create(seir_ctx *ctx, const seir_sampler_desc *ds, s
         return fail(SEIR_ERR_INVALID, "moves_mode is 0..4, hmc_mode 0..6");
     if (ds->disable_mask < 0 || ds->disable_mask > 31) return fail(SEIR_ERR_INVALID, "disable_mask is a 5-bit mask");
     if (ds->leap_rows != 0 && ds->leap_rows != 24 && ds->leap_rows != 32) return fail(SEIR_ERR_INVALID, "leap_rows is 0 (auto), 24 or 32");
+    if (ds->thin < 0) return fail(SEIR_ERR_INVALID, "thin must be >= 0 (0 or 1: every sweep is recorded)");
     HIP_TRY(hipSetDevice(ctx->device));
     seir_sampler *s = new (std::nothrow) seir_sampler();
     if (!s) return fail(SEIR_ERR_DEVICE, "out of host memory");
@@ -1176,6 +1178,7 @@ extern "C" int seir_sampler_create(seir_ctx *ctx, const seir_sampler_desc *ds, s
     s->leap_rows = ds->leap_rows;
     apply_launch_form(s, ds->hmc_mode, ds->moves_mode);
     c.disable_mask = ds->disable_mask;
+    c.thin = s->thin_pending = ds->thin < 1 ? 1 : ds->thin;
     {
         int g = ds->chain_groups;    // measured: concurrent chain groups on several streams do not overlap profitably
         if (g < 1) g = 1;
@@ -1575,10 +1578,43 @@ extern "C" int seir_sampler_set_adaptation(seir_sampler *s, int32_t adapt_step, 
     return 0;
 }
 
+// A thinning interval set since the last reset comes into force: the sweeps enqueued so far carry the old one in their
+// kernel arguments, the ones enqueued from here on the new one, and slot0 is written for it by the caller
+static int drop_graph_for_thin(seir_sampler *s) {
+    bool captured = false;
+    for (auto g : s->gexec) captured = captured || g != nullptr;
+    if (!captured) return 0;
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));   // its replays have finished (as seir_sampler_set_launch_form waits)
+    drop_graph(s);                                   // kernel arguments are baked into the graph
+    return 0;
+}
+static int apply_pending_thin(seir_sampler *s) {
+    if (s->cfg.thin == s->thin_pending) return 0;
+    int rc = drop_graph_for_thin(s);
+    if (rc) return rc;
+    s->cfg.thin = s->thin_pending;
+    return 0;
+}
+
+extern "C" int seir_sampler_set_thin(seir_sampler *s, int32_t thin) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if (thin < 0) return fail(SEIR_ERR_INVALID, "thin must be >= 0 (0 or 1: every sweep is recorded)");
+    s->thin_pending = thin < 1 ? 1 : thin;
+    return s->thin_pending != s->cfg.thin ? drop_graph_for_thin(s) : 0;
+}
+
+extern "C" int seir_sampler_thin(seir_sampler *s, int32_t *thin) {
+    if (!s) return fail(SEIR_ERR_INVALID, "null sampler");
+    if (thin) *thin = s->thin_pending;
+    return 0;
+}
+
 extern "C" int seir_sampler_reset_trace(seir_sampler *s) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    // slot0 = sweep counter of chain 0 (all chains advance together)
+    if ((rc = apply_pending_thin(s))) return rc;
+    // slot0 = sweep counter of chain 0 (all chains advance together): first slot 0, whatever the thinning interval
     HIP_TRY(hipMemcpyAsync(s->ch.slot0, s->ch.sweep, sizeof(unsigned), hipMemcpyDeviceToDevice, s->ctx->stream));
     return 0;
 }
@@ -1588,7 +1624,8 @@ extern "C" int seir_sampler_reset_trace_at(seir_sampler *s, int32_t first_slot) 
     if (rc) return rc;
     if (first_slot < 0 || first_slot >= s->cfg.cap)
         return fail(SEIR_ERR_INVALID, "first_slot %d outside [0, %d)", first_slot, s->cfg.cap);
-    hipLaunchKernelGGL(k_set_slot0, dim3(1), dim3(1), 0, s->ctx->stream, s->ch, (unsigned)first_slot);
+    if ((rc = apply_pending_thin(s))) return rc;
+    hipLaunchKernelGGL(k_set_slot0, dim3(1), dim3(1), 0, s->ctx->stream, s->ch, (unsigned)first_slot, (unsigned)s->cfg.thin);
     HIP_TRY(hipGetLastError());
     return 0;
 }

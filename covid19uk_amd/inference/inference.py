@@ -222,10 +222,23 @@ def trace_to_dict(tr, chain):
     return out
 
 
+def thin_interval(config, override=None):
+    """Mcmc.thin ("Thin MCMC samples every 'thin' iterations", example_config.yaml:33; absent: 1), or the command line's
+    `--thin`.  Anything below 1 is refused -- here, before a sampler exists."""
+    thin = int(config.get("thin", 1) if override is None else override)
+    if thin < 1:
+        raise ValueError(f"thin={thin}: the thinning interval is >= 1 (1 keeps every draw)")
+    return thin
+
+
 def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_step_size=False):
     """The windowed schedule of inference.py:303-470: fast 200, slow 25*2^k (k<6), fast 50,
-    then num_bursts x num_burst_samples with the kernel fixed.  Every draw -- warm-up
-    included -- is written, as in the reference."""
+    then num_bursts x num_burst_samples with the kernel fixed.  Every draw of the warm-up is
+    written, as in the reference (its running variance is formed from every draw of a window);
+    the sampling phase keeps every `thin`-th sweep: num_burst_samples kept draws per burst from
+    num_burst_samples * thin sweeps (inference.py:455), thinned on the device."""
+    thin = thin_interval(config)
+    sampler.set_thin(1)
     first_window_size, last_window_size, slow_window_size, num_slow_windows = 200, 50, 25, 6
     dual_averaging_kwargs = {"target_accept_prob": 0.75}
     offset = 0
@@ -266,6 +279,7 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     sampler.set_adaptation(adapt_step_size=False)
     sampler.set_kernel(step_size=step_size, variance=sampler.get_kernel()[1])
     nb, ns = int(config["num_bursts"]), int(config["num_burst_samples"])
+    sampler.set_thin(thin)                                  # in force from the first burst's trace reset
     t0 = time.perf_counter()
     if nb and ns and sampler.cap >= 2 * ns:
         # bursts overlap: while burst k+1 runs, burst k crosses PCIe into page-locked memory and is written
@@ -280,8 +294,8 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
             print(f"  burst {i + 1}/{nb}", file=log, flush=True)
     dt = time.perf_counter() - t0
     if nb * ns:
-        print(f"Sampling: {nb * ns * sampler.B / dt:.1f} posterior samples/s "
-              f"({sampler.B} chain(s), device->host->disk included)", file=log, flush=True)
+        print(f"Sampling: {nb * ns * thin * sampler.B / dt:.1f} sweeps/s, {nb * ns * sampler.B / dt:.1f} kept posterior samples/s "
+              f"(thin {thin}, {sampler.B} chain(s), device->host->disk included)", file=log, flush=True)
     return offset
 
 
@@ -346,14 +360,15 @@ def launch_forms(lay, device_arg, hmc="auto", moves="auto", env=os.environ):
 
 
 def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool_step_size=False, init_jitter=0.0,
-         events_dtype="auto", hmc="auto", moves="auto"):
+         events_dtype="auto", hmc="auto", moves="auto", thin=None):
     """Constructs and runs the MCMC (covid19uk/inference/inference.py:473-608).
 
     Multi-GPU: launched as one process per GPU, every rank runs `num_chains` chains with
     global ids rank*num_chains ... (the Philox streams are keyed by the global id, so the draws of chain c
     do not depend on how the job is sharded) and writes its own posterior_chain{c}.hd5; there is no
     data-path collective.  `pool_step_size` adds the one optional exchange: an all_gather of one float64
-    per chain after warm-up."""
+    per chain after warm-up.  `thin` overrides config["thin"] (every rank is given the same value)."""
+    config = dict(config, thin=thin_interval(config, thin))  # refused here if < 1: before any GPU call
     lay = job_layout(num_chains, device)                    # before any GPU call
     cov, cases, dates = read_inference_data(data_file)
     rng = np.random.default_rng(seed)                       # same imputation on every rank: one initial state per job
@@ -439,12 +454,17 @@ def main(argv=None):
     parser.add_argument("--moves", choices=["auto"] + sorted(MOVES_MODES), default="auto",
                         help="launch form of the event updates (auto: one persistent launch per sweep, or one launch per pair "
                              "of updates when ranks share a GPU)")
+    parser.add_argument("--thin", type=int, default=None, metavar="K",
+                        help="keep every K-th sweep of the sampling phase, thinned on the device (overrides Mcmc.thin of the "
+                             "configuration; the warm-up is never thinned, the shape of the output does not depend on it)")
     args = parser.parse_args(argv)
+    if args.thin is not None and args.thin < 1:
+        parser.error(f"--thin {args.thin}: the thinning interval is >= 1")
     with open(args.config, "r") as f:
         config = yaml.load(f, Loader=yaml.FullLoader)
     mcmc(args.data_file, args.output, config["Mcmc"], seed=args.seed, num_chains=args.chains, device=args.device,
          pool_step_size=args.pool_step_size, init_jitter=args.init_jitter, events_dtype=args.events_dtype,
-         hmc=args.hmc, moves=args.moves)
+         hmc=args.hmc, moves=args.moves, thin=args.thin)
 
 
 if __name__ == "__main__":

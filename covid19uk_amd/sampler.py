@@ -31,7 +31,7 @@ FALLBACK_FORMS = (("chunk-launch", "paired-launch"), ("chunk-split", "paired-del
 
 @dataclasses.dataclass
 class Trace:
-    """Draws and kernel results of `count` sweeps for B chains (leading axes [count, B])."""
+    """Draws and kernel results of `count` kept sweeps for B chains (leading axes [count, B])."""
     theta: np.ndarray        # [n,B,P] constrained parameter draws
     events: np.ndarray       # [n,B,M,T,3] int32 or uint16 (or None)
     hmc: dict                # is_accepted, target_log_prob, step_size  -> [n,B]
@@ -74,12 +74,15 @@ class PinnedTrace:
 
 
 class ChainSampler:
+    # thinning interval in force for the next burst (subclasses that never run __init__ sample every sweep)
+    _thin = 1
+
     def __init__(self, model: SeirModel, config: dict, num_chains: int, seed: int = 0,
                  t_range=None, num_leapfrog_steps: int = 16, trace_capacity: int = 100,
                  first_chain_id: int = 0, record_events: bool = True, moves: str = "paired",
                  hmc: str = "chunk", use_graph: bool = False, chain_groups: int = 1,
                  disable: tuple = (), debug_pair: int = 0, auto_recover: bool = True, log=sys.stderr,
-                 leap_rows: int = 0):
+                 leap_rows: int = 0, thin: int = 1):
         """`config` is the reference's config["Mcmc"] dict: dmax, nmax, m,
         occult_nmax, num_event_time_updates (mcmc_kernel_factory.py:79-81,106,123).
 
@@ -94,7 +97,14 @@ class ChainSampler:
         hand-off inside a persistent launch time out (`_lib.HandoffTimeout`: the launch could not get all its workgroups on
         the GPU -- another sampler or process holds part of it), restore it, switch to the per-step launch forms
         (`FALLBACK_FORMS`), run the burst again and carry on; after `retry_after` clean bursts the preferred forms are tried
-        again (twice as many after every further failure).  Every recovery is logged and kept in `self.recoveries`."""
+        again (twice as many after every further failure).  Every recovery is logged and kept in `self.recoveries`.
+
+        `thin`: thinning interval k >= 1, the reference's Mcmc.thin (example_config.yaml:33).  The device records the last
+        sweep of every group of k (`tfp.mcmc.sample_chain(num_steps_between_results=k - 1)`) and skips the trace writes of
+        the others; chain, random streams and adaptation see every sweep.  `sample(n)` / `sample_bursts(nb, n, ...)` keep
+        meaning n KEPT draws (n * k sweeps), `trace_capacity` counts kept draws, `run(num_sweeps)` counts sweeps."""
+        if int(thin) < 1:
+            raise ValueError(f"thin={thin}: the thinning interval is >= 1")
         names = ("hmc",) + MOVE_KEYS
         mask = 0
         for name in disable:
@@ -121,9 +131,10 @@ class ChainSampler:
             seed=int(seed) & (2 ** 64 - 1),
             moves_mode=MOVES_MODES[moves], hmc_mode=HMC_MODES[hmc],
             use_graph=int(bool(use_graph)), chain_groups=int(chain_groups), disable_mask=mask,
-            debug_pair=int(debug_pair), leap_rows=int(leap_rows))
+            debug_pair=int(debug_pair), leap_rows=int(leap_rows), thin=int(thin))
         self._s = ctypes.c_void_p()
         _lib.check(self._lib.seir_sampler_create(model._ctx, ctypes.byref(desc), ctypes.byref(self._s)))
+        self._thin = int(thin)
         self.auto_recover = bool(auto_recover) and debug_pair == 0
         self.preferred_form = (hmc, moves)
         self.recoveries = []              # one dict per recovery: burst form that failed, form it was re-run in, message
@@ -252,8 +263,24 @@ class ChainSampler:
             float(target_accept_prob), *args))
 
     # -- sampling ---------------------------------------------------------------
+    @property
+    def thin(self) -> int:
+        """Thinning interval: sweeps per kept draw."""
+        return self._thin
+
+    def set_thin(self, k: int):
+        """Thinning interval from the next `reset_trace` on -- i.e. from the next `sample` / `sample_bursts` burst (sweeps
+        already enqueued are recorded by the old rule).  `run_mcmc` keeps the warm-up windows at 1 and sets Mcmc.thin for
+        the sampling bursts."""
+        k = int(k)
+        if k < 1:
+            raise ValueError(f"thin={k}: the thinning interval is >= 1")
+        _lib.check(self._lib.seir_sampler_set_thin(self._s, k))
+        self._thin = k
+
     def reset_trace(self, at: int = 0):
-        """The next sweep is recorded in trace slot `at` (0: start of the burst buffer)."""
+        """The next sweep opens a group of `thin` sweeps whose last one is recorded in trace slot `at` (0: start of the
+        burst buffer)."""
         if at:
             _lib.check(self._lib.seir_sampler_reset_trace_at(self._s, int(at)))
         else:
@@ -303,8 +330,8 @@ class ChainSampler:
                               buf.moves[:n])
 
     def sample_bursts(self, num_bursts: int, burst: int, consume, events: bool = True):
-        """`num_bursts` x `burst` sweeps with the burst buffer used as two halves: while burst k+1 runs on
-        the device, burst k crosses PCIe into page-locked memory on a copy stream and `consume(trace, k)`
+        """`num_bursts` x `burst` kept draws (`burst * thin` sweeps each) with the burst buffer used as two halves:
+        while burst k+1 runs on the device, burst k crosses PCIe into page-locked memory on a copy stream and `consume(trace, k)`
         (e.g. the HDF5 writer) runs on a worker thread -- the sampler only waits when the consumer is
         the slower side.  Needs trace_capacity >= 2 * burst.  The trace handed to `consume` is a view of a
         pinned buffer that is re-used two bursts later: copy what must outlive the call."""
@@ -338,7 +365,7 @@ class ChainSampler:
                             if self.auto_recover:
                                 self.snapshot(h)                 # stream order: the state burst i starts from
                             self.reset_trace(at=h * burst)
-                            self.run(burst)                      # asynchronous
+                            self.run(burst * self._thin)         # asynchronous; a re-run after _recover passes here again
                         if prev >= 0:
                             self.trace_wait()                    # burst prev has landed (it crossed while burst i ran)
                             futs[prev & 1] = pool.submit(consume, self.trace_view(bufs[prev & 1], burst), prev)
@@ -367,14 +394,15 @@ class ChainSampler:
                 pass
 
     def sample(self, num_sweeps: int, events: bool = True) -> Trace:
-        """reset_trace + run + read: the analogue of one `sample_chain` call."""
+        """reset_trace + run + read: the analogue of one `sample_chain` call with `num_sweeps` results, each the last of
+        `thin` sweeps."""
         if num_sweeps > self.cap:
             raise ValueError(f"num_sweeps={num_sweeps} exceeds trace_capacity={self.cap}")
         while True:
             if self.auto_recover:
                 self.snapshot(0)
             self.reset_trace()
-            self.run(num_sweeps)
+            self.run(num_sweeps * self._thin)
             try:
                 tr = self.read_trace(num_sweeps, events=events)
             except _lib.HandoffTimeout as e:

@@ -196,10 +196,11 @@ typedef struct {
     int32_t num_event_time_updates; /* config["num_event_time_updates"]  (:123) */
     int32_t t_range_lo, t_range_hi; /* occult window [lo, hi)            (inference.py:336-339) */
     int32_t num_leapfrog_steps;     /* 16                                (inference.py:326) */
-    int32_t trace_capacity;         /* sweeps the burst buffer holds */
+    int32_t trace_capacity;         /* slots of the burst buffer: the kept draws it holds (= sweeps / thin) */
     int32_t first_chain_id;         /* global id of chain 0: selects the RNG stream (multi-GPU sharding) */
-    int32_t record_events;          /* 0: no samples/seir; 1: int32 counts for every draw; 2: uint16 counts (half the burst
-                                       buffer and half the bytes over PCIe; a count > 65535 makes the read fail) */
+    int32_t record_events;          /* 0: no samples/seir; 1: int32 counts for every kept draw; 2: uint16 counts (half the
+                                       burst buffer and half the bytes over PCIe; a count > 65535 in a kept draw makes
+                                       the read fail -- sweeps dropped by `thin` are not looked at) */
     uint64_t seed;
     /* ---- ABI v2: launch form and test hooks; all-zero = the defaults ---------------------------- */
     int32_t moves_mode;             /* 0: paired event updates (k_move_pair's steps) with the S->E-type proposal
@@ -255,7 +256,14 @@ typedef struct {
                                        (UK-380: 96 tile workgroups per chain, three on every CU of the chain's XCD) and the
                                        launch is resident, else 32 rows (two 16-row tiles per workgroup); 24 / 32: that shape
                                        only (the per-step form where it cannot be used) */
-    int32_t reserved[1];
+    int32_t thin;                   /* thinning interval k (0 or 1: every sweep is recorded; negative: SEIR_ERR_INVALID).
+                                       The reference's Mcmc.thin, "Thin MCMC samples every 'thin' iterations"
+                                       (example_config.yaml:33; inference.py:455 counts num_burst_samples * thin
+                                       iterations per burst, the thinning itself it never built).  After a trace reset
+                                       sweep i = 0, 1, ... is recorded iff (i + 1) % k == 0, in slot first_slot + i / k:
+                                       tfp.mcmc.sample_chain(num_steps_between_results = k - 1).  The chain, its random
+                                       streams and its adaptation see every sweep; only the trace writes of the others
+                                       are skipped.  Exact across the 2^32 wrap of the sweep counter for k a power of two */
 } seir_sampler_desc;
 
 int seir_sampler_create(seir_ctx *ctx, const seir_sampler_desc *desc, seir_sampler **out);
@@ -285,14 +293,25 @@ int seir_sampler_set_adaptation(seir_sampler *s, int32_t adapt_step_size, int32_
  * event planes and u; called implicitly by set_state. */
 int seir_sampler_refresh(seir_sampler *s);
 
-/* Start a new burst: trace slot 0 = the next sweep. */
+/* Start a new burst: the next sweep opens a group of `thin` sweeps whose last one is recorded in trace slot 0
+ * (thin 1: trace slot 0 = the next sweep). */
 int seir_sampler_reset_trace(seir_sampler *s);
-/* The same with the next sweep recorded in slot `first_slot`: a burst buffer of 2 n slots used as two
+/* The same with the first kept draw in slot `first_slot` (a slot, not a sweep): a burst buffer of 2 n slots used as two
  * halves lets burst k+1 run while burst k leaves the device (seir_sampler_read_trace_async). */
 int seir_sampler_reset_trace_at(seir_sampler *s, int32_t first_slot);
-/* Enqueue num_sweeps sweeps on the context stream (asynchronous). */
+/* Thinning interval of a live sampler (seir_sampler_desc::thin; 0 or 1: every sweep, negative: SEIR_ERR_INVALID), e.g.
+ * 1 for the warm-up windows, whose running variance is formed from every draw (inference.py:36-47), then Mcmc.thin
+ * (example_config.yaml:33) for the sampling bursts (inference.py:453-468).  It takes effect at the next
+ * seir_sampler_reset_trace[_at]: sweeps enqueued before that reset are recorded by the old rule.  A captured graph is
+ * dropped (the interval is a kernel argument).  A snapshot does not hold the interval: after seir_sampler_restore of a
+ * snapshot taken under another interval, reset the trace before running.  seir_sampler_thin reads the value set last. */
+int seir_sampler_set_thin(seir_sampler *s, int32_t thin);
+int seir_sampler_thin(seir_sampler *s, int32_t *thin);
+/* Enqueue num_sweeps sweeps on the context stream (asynchronous).  Sweeps, not kept draws: num_sweeps = n * thin fills
+ * n trace slots, and the last kept draw is the chain's current state. */
 int seir_sampler_run(seir_sampler *s, int32_t num_sweeps);
-/* Blocking read of trace slots [first, first+count):
+/* Blocking read of trace slots [first, first+count) -- slots are kept draws: with thinning interval k, slot j of a burst
+ * holds sweep (j + 1) k - 1 of it, exactly what an unthinned run records for that sweep:
  *   theta  [count][B][P]           constrained draws (param_bijector.inverse, inference.py:375)
  *   events [count][B][M][T][3]     int32 counts -- uint16 if record_events == 2 -- (NULL to skip)
  *   hmc    [count][B][3]           is_accepted, target_log_prob, step_size (inference.py:255-261)
