@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libseirhip.so")
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_void_pp = ctypes.POINTER(ctypes.c_void_p)
+c_int64_p = ctypes.POINTER(ctypes.c_int64)
 
 
 class SeirDesc(ctypes.Structure):
@@ -62,6 +63,7 @@ class SeirSimDesc(ctypes.Structure):
 
 ABI_VERSION = 4               # SEIR_ABI_VERSION
 OPT_DEBUG_SKEW, OPT_XCD_AFFINITY, OPT_GEMM_F32, OPT_EVAL_FORM = 0, 1, 2, 3
+ERR_INVALID, ERR_STATE = -1, -3   # SEIR_ERR_INVALID, SEIR_ERR_STATE
 ERR_HANDOFF = -4              # SEIR_ERR_HANDOFF
 MMAX = 4                      # SEIR_MMAX
 MOVE_TRACE = 2 + 4 * MMAX     # SEIR_MOVE_TRACE
@@ -146,6 +148,16 @@ _SIGNATURES = {
     "seir_sampler_set_launch_form": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]),
     "seir_sampler_launch_form": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32),
                                                 ctypes.POINTER(ctypes.c_int32)]),
+    # summaries of the recorded events on the device: moments and marginals
+    "seir_sampler_summary_reset": (ctypes.c_int, [ctypes.c_void_p]),
+    "seir_sampler_summarize": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "seir_sampler_read_marginals": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                                   c_int64_p, c_int64_p, c_int64_p]),
+    "seir_sampler_read_marginals_async": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                                         c_int64_p, c_int64_p, c_int64_p]),
+    "seir_sampler_read_summary": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
+                                                 ctypes.POINTER(ctypes.c_int32), c_int64_p,
+                                                 ctypes.POINTER(ctypes.c_uint64)]),
 }
 
 _lib = None

@@ -19,6 +19,7 @@
 #include "moves_kernel.h"
 #include "rt_kernels.h"
 #include "sweep_plan.h"
+#include "summary_kernels.h"
 
 using namespace seir;
 
@@ -1053,6 +1054,11 @@ struct seir_sampler {
     unsigned poison_count = 0;
     int hmc_mode = 0;                 // the launch forms in force (seir_sampler_set_launch_form)
     int thin_pending = 1;             // seir_sampler_set_thin: becomes cfg.thin at the next trace reset (Chains::slot0 is encoded for cfg.thin)
+    // --- summaries of the recorded events (seir_sampler_summary_reset ...; summary_kernels.h) ---
+    bool sum_on = false;              // enabled by the first seir_sampler_summary_reset: buffers exist
+    SummaryBufs sum{};
+    void *sum_snap[2] = {nullptr, nullptr};   // shadow copies of ref | sum | sumsq | count | flag for the two snapshot slots
+    bool sum_snap_valid[2] = {false, false};
 };
 
 template <typename T>
@@ -1087,6 +1093,7 @@ extern "C" void seir_sampler_destroy(seir_sampler *s) {
     if (s->ev_copy) (void)hipEventDestroy(s->ev_copy);
     for (void *p : s->allocs) (void)hipFree(p);
     for (void *p : s->snap) if (p) (void)hipFree(p);
+    for (void *p : s->sum_snap) if (p) (void)hipFree(p);
     Work &w = s->ctx->w;
     for (int x = 0; x < 3; ++x) { w.K[x] = nullptr; w.St[x] = nullptr; }
     w.rowtot = w.rngtot = nullptr;
@@ -1365,6 +1372,33 @@ extern "C" int seir_sampler_debug_fail_handoff(seir_sampler *s, int32_t chain) {
     return 0;
 }
 
+// While summaries are enabled a snapshot also holds the moment accumulators, count and the overflow flag (device copies in
+// stream order), so that a burst can be folded as soon as it is enqueued and a burst that is run again after a hand-off
+// time-out is not counted twice.  A snapshot taken before summaries were enabled holds none: restoring it leaves them alone.
+static size_t summary_cells(const seir_sampler *s) { return (size_t)s->cfg.B * s->ctx->d.M * s->ctx->d.T * seir::SUMMARY_Q; }
+static int summary_shadow(seir_sampler *s, int slot, bool save) {
+    if (!s->sum_on) return 0;
+    if (!save && !s->sum_snap_valid[slot]) return 0;
+    const size_t n = summary_cells(s), B = (size_t)s->cfg.B;
+    struct Part { void *p; size_t bytes; } parts[5] = {{s->sum.ref, n * sizeof(int32_t)}, {s->sum.sum, n * sizeof(int64_t)},
+                                                       {s->sum.sumsq, n * sizeof(uint64_t)}, {s->sum.count, B * sizeof(uint64_t)},
+                                                       {s->sum.overflow, sizeof(unsigned)}};
+    if (!s->sum_snap[slot]) {
+        size_t total = 0;
+        for (const Part &q : parts) total += (q.bytes + 255) / 256 * 256;
+        HIP_TRY(hipMalloc(&s->sum_snap[slot], total));
+    }
+    size_t off = 0;
+    for (const Part &q : parts) {
+        char *shadow = (char *)s->sum_snap[slot] + off;
+        HIP_TRY(hipMemcpyAsync(save ? (void *)shadow : q.p, save ? q.p : (void *)shadow, q.bytes, hipMemcpyDeviceToDevice,
+                               s->ctx->stream));
+        off += (q.bytes + 255) / 256 * 256;
+    }
+    if (save) s->sum_snap_valid[slot] = true;
+    return 0;
+}
+
 extern "C" int seir_sampler_snapshot(seir_sampler *s, int32_t slot) {
     int rc = sampler_check(s);
     if (rc) return rc;
@@ -1383,7 +1417,7 @@ extern "C" int seir_sampler_snapshot(seir_sampler *s, int32_t slot) {
             off += (r.bytes + 255) / 256 * 256;
         }
     s->snap_valid[slot] = true;
-    return 0;
+    return summary_shadow(s, slot, true);
 }
 
 extern "C" int seir_sampler_restore(seir_sampler *s, int32_t slot) {
@@ -1403,6 +1437,7 @@ extern "C" int seir_sampler_restore(seir_sampler *s, int32_t slot) {
             off += (r.bytes + 255) / 256 * 256;
         }
     if ((rc = reset_handoffs(s))) return rc;
+    if ((rc = summary_shadow(s, slot, false))) return rc;
     s->vt_dirty = true;                              // Work::Vt came back with the snapshot, the flag did not
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
@@ -2005,6 +2040,125 @@ extern "C" int seir_sampler_trace_wait(seir_sampler *s) {
         s->copy_pending = false;
         return check_ev_overflow(s);
     }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Summaries of the recorded events (include/seir_hip.h; kernels: summary_kernels.h)
+// ---------------------------------------------------------------------------
+extern "C" int seir_sampler_summary_reset(seir_sampler *s) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if (!s->record_events) return fail(SEIR_ERR_STATE, "sampler was created with record_events=0: there are no recorded events to summarise");
+    const Dims &d = s->ctx->d;
+    const size_t n = summary_cells(s), B = (size_t)s->cfg.B, cap = (size_t)s->cfg.cap;
+    SummaryBufs &sb = s->sum;
+    if (!s->sum_on) {
+#define S_ALLOC(ptr, n_) if (!rc) rc = s_alloc(s, &(ptr), (n_))
+        S_ALLOC(sb.ref, n); S_ALLOC(sb.sum, n); S_ALLOC(sb.sumsq, n);
+        S_ALLOC(sb.count, B); S_ALLOC(sb.overflow, 1);
+        S_ALLOC(sb.ebd, cap * B * d.T * 3); S_ALLOC(sb.ebl, cap * B * d.M * 3); S_ALLOC(sb.sbd, cap * B * d.T * 3);
+#undef S_ALLOC
+        if (rc) return rc;
+        s->sum_on = true;
+    }
+    hipStream_t st = s->ctx->stream;
+    HIP_TRY(hipMemsetAsync(sb.ref, 0, n * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(sb.sum, 0, n * sizeof(int64_t), st));
+    HIP_TRY(hipMemsetAsync(sb.sumsq, 0, n * sizeof(uint64_t), st));
+    HIP_TRY(hipMemsetAsync(sb.count, 0, B * sizeof(uint64_t), st));
+    HIP_TRY(hipMemsetAsync(sb.overflow, 0, sizeof(unsigned), st));
+    return 0;
+}
+
+static int summary_range_check(seir_sampler *s, int32_t first, int32_t count) {
+    if (!s->record_events) return fail(SEIR_ERR_STATE, "sampler was created with record_events=0: there are no recorded events to summarise");
+    if (!s->sum_on) return fail(SEIR_ERR_STATE, "summaries are not enabled: call seir_sampler_summary_reset first");
+    if (first < 0 || count < 0 || (long long)first + count > s->cfg.cap)
+        return fail(SEIR_ERR_INVALID, "trace range [%d,%lld) outside capacity %d", first, (long long)first + count, s->cfg.cap);
+    return 0;
+}
+
+extern "C" int seir_sampler_summarize(seir_sampler *s, int32_t first, int32_t count, int32_t accumulate) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = summary_range_check(s, first, count))) return rc;
+    if (count == 0) return 0;
+    seir_ctx *ctx = s->ctx;
+    const LaunchCfg l = whole(ctx, s->cfg.B);
+    const Dims &d = l.d;
+    const int B = s->cfg.B;
+    // events_by_day is summed with atomics: zero the call's slots first
+    HIP_TRY(hipMemsetAsync(s->sum.ebd + (size_t)first * B * d.T * 3, 0, sizeof(int64_t) * count * B * d.T * 3, l.st));
+    for (int j0 = 0; j0 < count; j0 += SUM_JMAX) {
+        const int nj = std::min(SUM_JMAX, count - j0);
+        const dim3 grid((d.M + SUM_ROWS - 1) / SUM_ROWS, B), block(64 * SUM_ROWS);
+        if (s->cfg.ev16)
+            hipLaunchKernelGGL(k_summarize<1>, grid, block, 0, l.st, d, ctx->c, s->sum, (const void *)s->ch.tr_events, B,
+                               first + j0, nj, accumulate != 0);
+        else
+            hipLaunchKernelGGL(k_summarize<0>, grid, block, 0, l.st, d, ctx->c, s->sum, (const void *)s->ch.tr_events, B,
+                               first + j0, nj, accumulate != 0);
+        hipLaunchKernelGGL(k_summary_finish, dim3(nj, B), dim3(64), 0, l.st, d, ctx->c, s->sum, B, first + j0, nj,
+                           accumulate != 0);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+static int summary_copy_marginals(seir_sampler *s, hipStream_t st, int32_t first, int32_t count, int64_t *events_by_day,
+                                  int64_t *events_by_location, int64_t *state_by_day) {
+    const Dims &d = s->ctx->d;
+    const size_t B = s->cfg.B, f = (size_t)first, n = (size_t)count;
+    if (events_by_day)
+        HIP_TRY(hipMemcpyAsync(events_by_day, s->sum.ebd + f * B * d.T * 3, sizeof(int64_t) * n * B * d.T * 3, hipMemcpyDeviceToHost, st));
+    if (events_by_location)
+        HIP_TRY(hipMemcpyAsync(events_by_location, s->sum.ebl + f * B * d.M * 3, sizeof(int64_t) * n * B * d.M * 3, hipMemcpyDeviceToHost, st));
+    if (state_by_day)
+        HIP_TRY(hipMemcpyAsync(state_by_day, s->sum.sbd + f * B * d.T * 3, sizeof(int64_t) * n * B * d.T * 3, hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+extern "C" int seir_sampler_read_marginals(seir_sampler *s, int32_t first, int32_t count, int64_t *events_by_day,
+                                           int64_t *events_by_location, int64_t *state_by_day) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = summary_range_check(s, first, count))) return rc;
+    if ((rc = summary_copy_marginals(s, s->ctx->stream, first, count, events_by_day, events_by_location, state_by_day))) return rc;
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    return check_ev_overflow(s);
+}
+
+extern "C" int seir_sampler_read_marginals_async(seir_sampler *s, int32_t first, int32_t count, int64_t *events_by_day,
+                                                 int64_t *events_by_location, int64_t *state_by_day) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = summary_range_check(s, first, count))) return rc;
+    // as seir_sampler_read_trace_async: behind everything queued on the context stream so far, on the copy stream
+    HIP_TRY(hipEventRecord(s->ev_burst, s->ctx->stream));
+    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_burst, 0));
+    if ((rc = summary_copy_marginals(s, s->copy_stream, first, count, events_by_day, events_by_location, state_by_day))) return rc;
+    HIP_TRY(hipEventRecord(s->ev_copy, s->copy_stream));
+    s->copy_pending = true;
+    return 0;
+}
+
+extern "C" int seir_sampler_read_summary(seir_sampler *s, uint64_t *count, int32_t *ref, int64_t *sum, uint64_t *sumsq) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = summary_range_check(s, 0, 0))) return rc;
+    hipStream_t st = s->ctx->stream;
+    const size_t n = summary_cells(s);
+    unsigned flag = 0;
+    HIP_TRY(hipMemcpyAsync(&flag, s->sum.overflow, sizeof(flag), hipMemcpyDeviceToHost, st));
+    if (count) HIP_TRY(hipMemcpyAsync(count, s->sum.count, sizeof(uint64_t) * s->cfg.B, hipMemcpyDeviceToHost, st));
+    if (ref) HIP_TRY(hipMemcpyAsync(ref, s->sum.ref, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    if (sum) HIP_TRY(hipMemcpyAsync(sum, s->sum.sum, sizeof(int64_t) * n, hipMemcpyDeviceToHost, st));
+    if (sumsq) HIP_TRY(hipMemcpyAsync(sumsq, s->sum.sumsq, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = check_ev_overflow(s))) return rc;
+    if (flag) return fail(SEIR_ERR_STATE, "a sum of squared deviations reached 2^63: the moment accumulators overflowed "
+                          "(seir_sampler_summary_reset starts them again)");
     return 0;
 }
 

@@ -1,0 +1,207 @@
+// Summaries of the recorded latent epidemic, formed where the burst buffer lies (include/seir_hip.h, "Summaries of
+// samples/seir on the device"): per-cell moments of the event counts and of the state over the kept draws, and per-draw
+// marginals (events by day, events by location, state by day).  The definitions are summary_update.h's.
+//
+// k_summarize<EV16> reads trace slots [first, first + count) of all chains once.  The shape of the work:
+//   - a WAVE owns a row m of a chain and walks its 64-day chunks, a lane per day; a workgroup is SUM_ROWS such waves on
+//     neighbouring rows.  The state is a prefix over days: inside a chunk a DPP wave scan per transition, from chunk to
+//     chunk a carry per draw (3 ints, LDS; only the owning wave touches it).  The carry after the last chunk is
+//     events_by_location;
+//   - the loop over the call's draws is the INNER one: a cell's six (ref, sum, sumsq) triples are loaded before it, held
+//     in registers across it and stored after it, so the accumulators (20 B per cell and quantity) cross memory once per
+//     launch whatever the number of draws.  The host cuts a call into launches of at most SUM_JMAX draws (the carries'
+//     LDS); integer sums do not care;
+//   - a lane reads its day's three counts as one 12-byte access (int32: global_load_dwordx3) or a 4-byte and a 2-byte one
+//     (uint16, whose rows are only 2-byte aligned), contiguous over the wave: nothing to de-interleave.  The loads of SUM_U
+//     draws are issued before the first of them is used;
+//   - events_by_day is a sum over rows, i.e. over waves and workgroups: the waves of a workgroup add their counts into an
+//     LDS tile [SUM_JB draws][64 days][3] (64-bit integer LDS adds), and after every SUM_JB draws the workgroup issues
+//     one global 64-bit atomicAdd per (draw, day, transition) that is not zero, 1536 contiguous bytes per draw, onto
+//     arrays the call has zeroed.  At UK-380 x 8 and 100 draws that is 4.2e7 atomics instead of 7e8, and integer adds
+//     are exact in any order;
+//   - state_by_day needs no pass over the cells at all: sum_m S[m][t] = sum_m S0[m] - sum_{s<t} events_by_day[s][0], and
+//     so on -- k_summary_finish scans the finished events_by_day (a wave per draw and chain) and also advances count[b].
+// No hand-off inside a launch, no persistence, nothing of the sweep's plan: ordinary launches on the context stream.
+#pragma once
+
+#include "summary_update.h"
+
+namespace seir {
+
+constexpr int SUM_ROWS = 8;        // waves (rows) per workgroup
+constexpr int SUM_JB = 16;         // draws per flush of the by-day tile (24 KiB of LDS)
+constexpr int SUM_JMAX = 128;      // draws per launch (12 KiB of carries)
+constexpr int SUM_U = 4;           // draws whose loads are in flight together
+
+struct SummaryBufs {
+    int32_t *ref;                  // [B][M][T][6]
+    int64_t *sum;                  // [B][M][T][6]
+    uint64_t *sumsq;               // [B][M][T][6]
+    uint64_t *count;               // [B] draws folded since the last reset
+    unsigned *overflow;            // [1] sticky: some sumsq reached 2^63
+    int64_t *ebd;                  // [cap][B][T][3] events_by_day
+    int64_t *ebl;                  // [cap][B][M][3] events_by_location
+    int64_t *sbd;                  // [cap][B][T][3] state_by_day
+};
+
+struct __attribute__((aligned(4))) SumEv32 { int32_t k[3]; };
+struct __attribute__((aligned(2))) SumEv16 { uint16_t k[3]; };
+
+template <int EV16>
+__device__ __forceinline__ void summary_load(const void *__restrict__ tr, size_t cell, bool live, int (&k)[3]) {
+    k[0] = k[1] = k[2] = 0;
+    if (!live) return;
+    if (EV16) {
+        const SumEv16 v = reinterpret_cast<const SumEv16 *>(tr)[cell];
+        k[0] = v.k[0]; k[1] = v.k[1]; k[2] = v.k[2];
+    } else {
+        const SumEv32 v = reinterpret_cast<const SumEv32 *>(tr)[cell];
+        k[0] = v.k[0]; k[1] = v.k[1]; k[2] = v.k[2];
+    }
+}
+
+// grid (ceil(M / SUM_ROWS), B), 64 SUM_ROWS threads.  1 <= count <= SUM_JMAX, first + count <= cap (the host checks).
+template <int EV16>
+__global__ __launch_bounds__(64 * SUM_ROWS) void k_summarize(Dims d, Consts c, SummaryBufs sb,
+                                                             const void *__restrict__ tr_events, int B, int first,
+                                                             int count, int accumulate) {
+    debug_skew(d);
+    __shared__ unsigned long long bd[SUM_JB][64][3];
+    __shared__ int carry[SUM_ROWS][SUM_JMAX][3];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int b = blockIdx.y, m = blockIdx.x * SUM_ROWS + wv;
+    const int M = d.M, T = d.T;
+    const bool row_ok = m < M;
+    const bool fold = accumulate != 0;
+    const bool fresh = fold && sb.count[b] == 0;      // count moves in k_summary_finish, a launch of its own: no race
+    int s0[3] = {0, 0, 0};
+    if (row_ok)
+#pragma unroll
+        for (int x = 0; x < 3; ++x) s0[x] = (int)c.init[(size_t)m * 4 + x];
+    for (int i = lane; i < count * 3; i += 64) (&carry[wv][0][0])[i] = 0;
+    for (int i = threadIdx.x; i < SUM_JB * 64 * 3; i += 64 * SUM_ROWS) (&bd[0][0][0])[i] = 0ull;
+    __syncthreads();
+
+    const size_t draw_cells = (size_t)B * M * T;      // cells of one trace slot
+    bool ovf = false;
+    for (int t0 = 0; t0 < T; t0 += 64) {
+        const int t = t0 + lane;
+        const bool live = row_ok && t < T;
+        const size_t cell = ((size_t)b * M + (row_ok ? m : 0)) * T + (t < T ? t : 0);
+        int32_t ref[seir::SUMMARY_Q];
+        int64_t sm[seir::SUMMARY_Q];
+        uint64_t sq[seir::SUMMARY_Q];
+#pragma unroll
+        for (int q = 0; q < seir::SUMMARY_Q; ++q) { ref[q] = 0; sm[q] = 0; sq[q] = 0; }
+        if (fold && live && !fresh) {
+#pragma unroll
+            for (int q = 0; q < seir::SUMMARY_Q; ++q) {
+                ref[q] = sb.ref[cell * seir::SUMMARY_Q + q];
+                sm[q] = sb.sum[cell * seir::SUMMARY_Q + q];
+                sq[q] = sb.sumsq[cell * seir::SUMMARY_Q + q];
+            }
+        }
+        for (int jb = 0; jb < count; jb += SUM_JB) {
+            const int nj = min(SUM_JB, count - jb);
+            for (int ju = 0; ju < nj; ju += SUM_U) {
+                int kk[SUM_U][3];
+#pragma unroll
+                for (int u = 0; u < SUM_U; ++u)
+                    summary_load<EV16>(tr_events, (size_t)(first + jb + ju + u) * draw_cells + cell,
+                                       live && ju + u < nj, kk[u]);
+#pragma unroll
+                for (int u = 0; u < SUM_U; ++u) {
+                    if (ju + u >= nj) break;                       // uniform
+                    const int jj = ju + u, j = jb + jj;
+                    int ex[3];
+#pragma unroll
+                    for (int x = 0; x < 3; ++x) {
+                        const int inc = wave_incl_scan(kk[u][x], lane);
+                        const int cr = carry[wv][j][x];
+                        ex[x] = cr + inc - kk[u][x];
+                        const int tot = cr + __builtin_amdgcn_readlane(inc, 63);
+                        if (lane == 0) carry[wv][j][x] = tot;
+                    }
+                    if (live) {
+#pragma unroll
+                        for (int x = 0; x < 3; ++x)
+                            if (kk[u][x] != 0) atomicAdd(&bd[jj][lane][x], (unsigned long long)kk[u][x]);
+                        if (fold) {
+                            const int val[seir::SUMMARY_Q] = {kk[u][0], kk[u][1], kk[u][2], s0[0] - ex[0],
+                                                              s0[1] + ex[0] - ex[1], s0[2] + ex[1] - ex[2]};
+                            const bool is_first = fresh && j == 0;
+#pragma unroll
+                            for (int q = 0; q < seir::SUMMARY_Q; ++q)
+                                ovf |= seir::summary_fold(ref[q], sm[q], sq[q], val[q], is_first);
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            // the workgroup's part of events_by_day for these draws and days: one atomic per entry that is not zero
+            for (int i = threadIdx.x; i < nj * 64 * 3; i += 64 * SUM_ROWS) {
+                const unsigned long long v = (&bd[0][0][0])[i];
+                const int jj = i / 192, r = i - jj * 192, tl = r / 3, x = r - tl * 3;
+                if (v != 0ull) {
+                    (&bd[0][0][0])[i] = 0ull;
+                    atomicAdd(reinterpret_cast<unsigned long long *>(sb.ebd) +
+                                  (((size_t)(first + jb + jj) * B + b) * T + (t0 + tl)) * 3 + x, v);
+                }
+            }
+            __syncthreads();
+        }
+        if (fold && live) {
+#pragma unroll
+            for (int q = 0; q < seir::SUMMARY_Q; ++q) {
+                if (fresh) sb.ref[cell * seir::SUMMARY_Q + q] = ref[q];
+                sb.sum[cell * seir::SUMMARY_Q + q] = sm[q];
+                sb.sumsq[cell * seir::SUMMARY_Q + q] = sq[q];
+            }
+        }
+    }
+    // the carries after the last chunk are the row totals
+    if (row_ok)
+        for (int i = lane; i < count * 3; i += 64) {
+            const int j = i / 3, x = i - j * 3;
+            sb.ebl[(((size_t)(first + j) * B + b) * M + m) * 3 + x] = (int64_t)carry[wv][j][x];
+        }
+    if (ovf) sb.overflow[0] = 1u;
+}
+
+// state_by_day from the finished events_by_day, and count[b] += count when the draws were folded.  grid (count, B), one wave.
+__global__ __launch_bounds__(64) void k_summary_finish(Dims d, Consts c, SummaryBufs sb, int B, int first, int count,
+                                                       int accumulate) {
+    const int lane = threadIdx.x, b = blockIdx.y, slot = first + blockIdx.x;
+    long long tot0[3] = {0, 0, 0};
+    for (int m = lane; m < d.M; m += 64)
+#pragma unroll
+        for (int x = 0; x < 3; ++x) tot0[x] += (long long)c.init[(size_t)m * 4 + x];
+#pragma unroll
+    for (int x = 0; x < 3; ++x)
+        for (int o = 32; o > 0; o >>= 1) tot0[x] += __shfl_xor(tot0[x], o, 64);
+    long long cr[3] = {0, 0, 0};
+    const size_t base = ((size_t)slot * B + b) * d.T;
+    for (int t0 = 0; t0 < d.T; t0 += 64) {
+        const int t = t0 + lane;
+        long long ex[3];
+#pragma unroll
+        for (int x = 0; x < 3; ++x) {
+            const long long v = t < d.T ? sb.ebd[(base + t) * 3 + x] : 0ll;
+            long long inc = v;
+            for (int o = 1; o < 64; o <<= 1) {
+                const long long up = __shfl_up(inc, o, 64);
+                if (lane >= o) inc += up;
+            }
+            ex[x] = cr[x] + inc - v;
+            cr[x] += __shfl(inc, 63, 64);
+        }
+        if (t < d.T) {
+            sb.sbd[(base + t) * 3 + 0] = tot0[0] - ex[0];
+            sb.sbd[(base + t) * 3 + 1] = tot0[1] + ex[0] - ex[1];
+            sb.sbd[(base + t) * 3 + 2] = tot0[2] + ex[1] - ex[2];
+        }
+    }
+    if (accumulate && blockIdx.x == 0 && lane == 0) sb.count[b] += (uint64_t)count;
+}
+
+}  // namespace seir

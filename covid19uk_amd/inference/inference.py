@@ -105,7 +105,11 @@ class Posterior:
     `is_accepted` is a bool dataset the way h5py stores one (gemlib's Posterior writes numpy bools through h5py):
     the int8 enum {FALSE = 0, TRUE = 1}."""
 
-    def __init__(self, filename, M, T, mmax, num_samples, burst=100):
+    def __init__(self, filename, M, T, mmax, num_samples, burst=100, summaries="off"):
+        """`summaries` ("off" | "on" | "only", Mcmc.summaries / --summaries): with "on" and "only" the per-draw marginals
+        samples/seir_by_day [n,T,3], samples/seir_by_location [n,M,3], samples/state_by_day [n,T,3] (int64) are written
+        with every burst and `write_summary` adds summaries/* at the end of the run; with "only" samples/seir is not
+        created.  "off" creates exactly the datasets of a run without the option."""
         self.filename = filename
         self.use_h5 = not str(filename).endswith(".npz") and hdf5io.available()
         self.shapes = {
@@ -115,6 +119,13 @@ class Posterior:
             "results/hmc/is_accepted": (), "results/hmc/target_log_prob": (), "results/hmc/step_size": (),
         }
         self.dtypes = {"results/hmc/is_accepted": np.bool_}
+        if summaries != "off":
+            self.shapes.update({"samples/seir_by_day": (T, 3), "samples/seir_by_location": (M, 3),
+                                "samples/state_by_day": (T, 3)})
+            self.dtypes.update({k: np.int64 for k in ("samples/seir_by_day", "samples/seir_by_location",
+                                                      "samples/state_by_day")})
+        if summaries == "only":
+            del self.shapes["samples/seir"]
         for key in MOVE_KEYS:
             self.shapes[f"results/{key}/is_accepted"] = ()
             self.shapes[f"results/{key}/target_log_prob"] = ()
@@ -141,7 +152,7 @@ class Posterior:
                 # the file's float64 and written at its file address by a few threads (hdf5io.write_rows_parallel)
                 self._file.write_rows_parallel("/" + name, v, offset=first_dim_offset)
                 return
-            if v.dtype != np.float64 and v.dtype.kind in "iu" and v.nbytes > (1 << 20):
+            if v.dtype != np.float64 and v.dtype.kind in "iu" and v.nbytes > (1 << 20) and name not in self.dtypes:
                 # the event tensor arrives as the device's integer counts (a strided view of the burst); it is
                 # converted to the file's float64 in ONE pass into a buffer kept between bursts -- a fresh
                 # 165 MB array per burst costs more in page faults than the conversion itself
@@ -171,6 +182,16 @@ class Posterior:
             self._file.write("/" + name, data)
         else:
             self._extra[name] = data
+
+    def write_summary(self, count, mean, var):
+        """The moments of one chain over the sampling phase (`Summary.mean` / `.var` rows, [M,T,6] float64):
+        summaries/count [1], summaries/seir_mean, seir_var (k_se, k_ei, k_ir) and state_mean, state_var (S, E, I),
+        each [M,T,3]."""
+        self.create_dataset("summaries/count", np.array([float(count)]))
+        self.create_dataset("summaries/seir_mean", np.ascontiguousarray(mean[..., :3]))
+        self.create_dataset("summaries/seir_var", np.ascontiguousarray(var[..., :3]))
+        self.create_dataset("summaries/state_mean", np.ascontiguousarray(mean[..., 3:]))
+        self.create_dataset("summaries/state_var", np.ascontiguousarray(var[..., 3:]))
 
     def __getitem__(self, name):
         if self.use_h5:
@@ -202,16 +223,27 @@ def unconstrain_theta(theta):
     return u
 
 
-def draws_to_dict(theta, events, chain):
-    """inference.py:285-300 for one chain: theta [n,B,P] constrained, events [n,B,M,T,3]."""
-    M, T = events.shape[2], events.shape[3]
+def draws_to_dict(theta, events, chain, marginals=None):
+    """inference.py:285-300 for one chain: theta [n,B,P] constrained, events [n,B,M,T,3] -- None when the event tensors
+    stay on the device (summaries "only"); then, and with summaries "on", `marginals` (Trace.marginals) gives the shapes
+    and the three per-draw marginal datasets."""
+    if events is not None:
+        M, T = events.shape[2], events.shape[3]
+    else:
+        M, T = marginals["events_by_location"].shape[2], marginals["events_by_day"].shape[2]
     th = theta[:, chain]
-    return {
+    out = {
         "psi": th[:, 0], "sigma_space": th[:, 1], "beta_area": th[:, 2], "gamma0": th[:, 3],
         "gamma1": th[:, 4], "alpha_0": th[:, 5], "alpha_t": th[:, 6:6 + T - 1],
         "spatial_effect": th[:, 6 + T - 1:6 + T - 1 + M],
-        "seir": events[:, chain] if events.dtype.kind in "iu" else events[:, chain].astype(DTYPE),   # Posterior.write converts
     }
+    if events is not None:
+        out["seir"] = events[:, chain] if events.dtype.kind in "iu" else events[:, chain].astype(DTYPE)   # Posterior.write converts
+    if marginals is not None:
+        out["seir_by_day"] = marginals["events_by_day"][:, chain]
+        out["seir_by_location"] = marginals["events_by_location"][:, chain]
+        out["state_by_day"] = marginals["state_by_day"][:, chain]
+    return out
 
 
 def trace_to_dict(tr, chain):
@@ -231,6 +263,21 @@ def thin_interval(config, override=None):
     return thin
 
 
+SUMMARIES = ("off", "on", "only")
+
+
+def summaries_mode(config, override=None):
+    """Mcmc.summaries (absent: "off"), or the command line's `--summaries`: "on" adds the device-side summaries of the
+    latent epidemic to the output, "only" also keeps the event tensors on the device.  Anything else is refused -- here,
+    before a sampler exists."""
+    mode = config.get("summaries", "off") if override is None else override
+    if mode is False or mode is True:                       # YAML reads a bare `on` / `off` as a boolean
+        mode = "on" if mode else "off"
+    if mode not in SUMMARIES:
+        raise ValueError(f"summaries={mode!r}: choose one of {', '.join(SUMMARIES)}")
+    return mode
+
+
 def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_step_size=False):
     """The windowed schedule of inference.py:303-470: fast 200, slow 25*2^k (k<6), fast 50,
     then num_bursts x num_burst_samples with the kernel fixed.  Every draw of the warm-up is
@@ -238,6 +285,11 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     the sampling phase keeps every `thin`-th sweep: num_burst_samples kept draws per burst from
     num_burst_samples * thin sweeps (inference.py:455), thinned on the device."""
     thin = thin_interval(config)
+    summaries = summaries_mode(config)
+    # "off": sample / sample_bursts are called exactly as before the option existed.  Otherwise every written draw gets its
+    # marginals (the warm-up without folding), the moments cover the sampling phase, and with "only" no event tensor is read
+    warm_kw = {} if summaries == "off" else dict(events=summaries != "only", summarize="marginals")
+    burst_kw = {} if summaries == "off" else dict(events=summaries != "only", summarize=True)
     sampler.set_thin(1)
     first_window_size, last_window_size, slow_window_size, num_slow_windows = 200, 50, 25, 6
     dual_averaging_kwargs = {"target_accept_prob": 0.75}
@@ -247,14 +299,15 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
         nonlocal offset
         n = tr.theta.shape[0]
         for c, post in enumerate(posteriors):
-            post.write_samples(draws_to_dict(tr.theta, tr.events, c), first_dim_offset=offset)
+            post.write_samples(draws_to_dict(tr.theta, tr.events, c, **({} if summaries == "off" else dict(marginals=tr.marginals))),
+                               first_dim_offset=offset)
             post.write_results(trace_to_dict(tr, c), first_dim_offset=offset)
         offset += n
 
     def window(n, adapt_mass, running_variance=None):
         sampler.set_adaptation(adapt_step_size=True, adapt_mass=adapt_mass, num_adaptation_steps=n,
                                running_variance=running_variance, **dual_averaging_kwargs)
-        tr = sampler.sample(n)
+        tr = sampler.sample(n, **warm_kw)
         flush(tr)
         return tr, get_weighted_running_variance(unconstrain_theta(tr.theta))
 
@@ -280,6 +333,11 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     sampler.set_kernel(step_size=step_size, variance=sampler.get_kernel()[1])
     nb, ns = int(config["num_bursts"]), int(config["num_burst_samples"])
     sampler.set_thin(thin)                                  # in force from the first burst's trace reset
+    if summaries != "off":
+        sampler.reset_summary()                             # the moments are over the sampling phase
+        if summaries == "only":
+            print("summaries only: the event tensors stay on the device and samples/seir is not created -- what reads it "
+                  "(thin_posterior, predict, reproduction_number) cannot run on this output", file=log, flush=True)
     t0 = time.perf_counter()
     if nb and ns and sampler.cap >= 2 * ns:
         # bursts overlap: while burst k+1 runs, burst k crosses PCIe into page-locked memory and is written
@@ -287,15 +345,20 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
         def on_burst(tr, i):
             flush(tr)
             print(f"  burst {i + 1}/{nb}", file=log, flush=True)
-        sampler.sample_bursts(nb, ns, on_burst)
+        sampler.sample_bursts(nb, ns, on_burst, **burst_kw)
     else:
         for i in range(nb):
-            flush(sampler.sample(ns))
+            flush(sampler.sample(ns, **burst_kw))
             print(f"  burst {i + 1}/{nb}", file=log, flush=True)
     dt = time.perf_counter() - t0
     if nb * ns:
         print(f"Sampling: {nb * ns * thin * sampler.B / dt:.1f} sweeps/s, {nb * ns * sampler.B / dt:.1f} kept posterior samples/s "
               f"(thin {thin}, {sampler.B} chain(s), device->host->disk included)", file=log, flush=True)
+    if summaries != "off":
+        sm = sampler.summary()
+        mean, var = sm.mean, sm.var
+        for c, post in enumerate(posteriors):
+            post.write_summary(sm.count[c], mean[c], var[c])
     return offset
 
 
@@ -360,15 +423,17 @@ def launch_forms(lay, device_arg, hmc="auto", moves="auto", env=os.environ):
 
 
 def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool_step_size=False, init_jitter=0.0,
-         events_dtype="auto", hmc="auto", moves="auto", thin=None):
+         events_dtype="auto", hmc="auto", moves="auto", thin=None, summaries=None):
     """Constructs and runs the MCMC (covid19uk/inference/inference.py:473-608).
 
     Multi-GPU: launched as one process per GPU, every rank runs `num_chains` chains with
     global ids rank*num_chains ... (the Philox streams are keyed by the global id, so the draws of chain c
     do not depend on how the job is sharded) and writes its own posterior_chain{c}.hd5; there is no
     data-path collective.  `pool_step_size` adds the one optional exchange: an all_gather of one float64
-    per chain after warm-up.  `thin` overrides config["thin"] (every rank is given the same value)."""
+    per chain after warm-up.  `thin` overrides config["thin"] (every rank is given the same value), `summaries`
+    config["summaries"] (`summaries_mode`)."""
     config = dict(config, thin=thin_interval(config, thin))  # refused here if < 1: before any GPU call
+    config = dict(config, summaries=summaries_mode(config, summaries))    # an unknown value likewise
     lay = job_layout(num_chains, device)                    # before any GPU call
     cov, cases, dates = read_inference_data(data_file)
     rng = np.random.default_rng(seed)                       # same imputation on every rank: one initial state per job
@@ -406,7 +471,8 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
 
     total = lay["world"] * B
     names = [chain_file_name(output_file, lay["first_chain_id"] + c, total) for c in range(B)]
-    posteriors = [Posterior(name, M, T, cfg["m"], num_samples, burst=int(config["num_burst_samples"]))
+    posteriors = [Posterior(name, M, T, cfg["m"], num_samples, burst=int(config["num_burst_samples"]),
+                            **({} if config["summaries"] == "off" else dict(summaries=config["summaries"])))
                   for name in names]
     run_mcmc(sampler, config, posteriors, pool_step_size=pool_step_size and total > 1)
     if sampler.recoveries:
@@ -457,6 +523,11 @@ def main(argv=None):
     parser.add_argument("--thin", type=int, default=None, metavar="K",
                         help="keep every K-th sweep of the sampling phase, thinned on the device (overrides Mcmc.thin of the "
                              "configuration; the warm-up is never thinned, the shape of the output does not depend on it)")
+    parser.add_argument("--summaries", choices=list(SUMMARIES), default=None,
+                        help="summaries of the latent epidemic formed on the device (overrides Mcmc.summaries; default off): "
+                             "on = per-draw marginals samples/seir_by_day, seir_by_location, state_by_day and per-cell "
+                             "summaries/* mean and variance of events and state over the sampling phase, next to samples/seir; "
+                             "only = the same without samples/seir, whose tensors then never leave the device")
     args = parser.parse_args(argv)
     if args.thin is not None and args.thin < 1:
         parser.error(f"--thin {args.thin}: the thinning interval is >= 1")
@@ -464,7 +535,7 @@ def main(argv=None):
         config = yaml.load(f, Loader=yaml.FullLoader)
     mcmc(args.data_file, args.output, config["Mcmc"], seed=args.seed, num_chains=args.chains, device=args.device,
          pool_step_size=args.pool_step_size, init_jitter=args.init_jitter, events_dtype=args.events_dtype,
-         hmc=args.hmc, moves=args.moves, thin=args.thin)
+         hmc=args.hmc, moves=args.moves, thin=args.thin, summaries=args.summaries)
 
 
 if __name__ == "__main__":

@@ -36,13 +36,60 @@ class Trace:
     events: np.ndarray       # [n,B,M,T,3] int32 or uint16 (or None)
     hmc: dict                # is_accepted, target_log_prob, step_size  -> [n,B]
     moves: dict              # MOVE_KEYS -> dict(is_accepted [n,B], target_log_prob [n,B], proposed_delta [n,B,4,m])
+    marginals: dict = None   # MARGINAL_KEYS -> int64 [n,B,T,3] / [n,B,M,3] / [n,B,T,3]; None unless asked for
+
+
+MARGINAL_KEYS = ("events_by_day", "events_by_location", "state_by_day")
+SUMMARY_QUANTITIES = ("k_se", "k_ei", "k_ir", "S", "E", "I")
+
+
+@dataclasses.dataclass
+class Summary:
+    """Moments of the recorded events and of the state over the kept draws folded since the last `reset_summary`
+    (include/seir_hip.h, "Summaries of samples/seir on the device"): exact integers, per chain.  The last axis is
+    `SUMMARY_QUANTITIES`; the state is the one at the start of the day (`model_spec.compute_state`)."""
+    count: np.ndarray        # [B] uint64 draws folded
+    ref: np.ndarray          # [B,M,T,6] int32: the value in the first draw folded
+    sum: np.ndarray          # [B,M,T,6] int64: sum_j (x_j - ref)
+    sumsq: np.ndarray        # [B,M,T,6] uint64: sum_j (x_j - ref)^2
+
+    @property
+    def mean(self) -> np.ndarray:
+        """ref + sum / n, float64 [B,M,T,6]; NaN for a chain with no draw."""
+        return summary_mean(self.count, self.ref, self.sum)
+
+    @property
+    def var(self) -> np.ndarray:
+        """Unbiased variance (sumsq - sum^2 / n) / (n - 1), float64 [B,M,T,6]; NaN where n < 2."""
+        return summary_var(self.count, self.sum, self.sumsq)
+
+
+def _per_chain(count, like):
+    n = np.asarray(count).astype(np.float64)
+    return n.reshape(n.shape + (1,) * (np.ndim(like) - n.ndim))
+
+
+def summary_mean(count, ref, sum_):
+    """mean = ref + sum / n from the integer accumulators (count broadcast over the leading axes); NaN where n = 0."""
+    n = _per_chain(count, ref)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(n > 0, np.asarray(ref, np.float64) + np.asarray(sum_, np.float64) / n, np.nan)
+
+
+def summary_var(count, sum_, sumsq):
+    """Unbiased variance (sumsq - sum^2 / n) / (n - 1) from the integer accumulators; NaN (no warning) where n < 2."""
+    n = _per_chain(count, sum_)
+    s1, s2 = np.asarray(sum_, np.float64), np.asarray(sumsq, np.float64)
+    ok = n > 1
+    nn = np.where(ok, n, 2.0)
+    return np.where(ok, (s2 - s1 * s1 / nn) / (nn - 1.0), np.nan)
 
 
 class PinnedTrace:
     """Page-locked host arrays for `count` sweeps of the burst buffer (seir_host_alloc): the target of
     `ChainSampler.read_trace_async`.  Views are valid until close()."""
 
-    def __init__(self, sampler: "ChainSampler", count: int, events: bool = True):
+    def __init__(self, sampler: "ChainSampler", count: int, events: bool = True, marginals: bool = False):
         self._lib = sampler._lib
         self.count = int(count)
         B, P, M, T = sampler.B, sampler.P, sampler.M, sampler.T
@@ -51,6 +98,11 @@ class PinnedTrace:
         self.events = self._alloc((count, B, M, T, 3), sampler.events_dtype) if (events and sampler.record_events) else None
         self.hmc = self._alloc((count, B, 3), np.float64)
         self.moves = self._alloc((count, B, 4, _lib.MOVE_TRACE), np.float64)
+        self.marginals = None
+        if marginals:
+            self.marginals = dict(events_by_day=self._alloc((count, B, T, 3), np.int64),
+                                  events_by_location=self._alloc((count, B, M, 3), np.int64),
+                                  state_by_day=self._alloc((count, B, T, 3), np.int64))
 
     def _alloc(self, shape, dtype):
         nbytes = int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize
@@ -61,7 +113,7 @@ class PinnedTrace:
         return np.frombuffer(buf, dtype=dtype, count=int(np.prod(shape, dtype=np.int64))).reshape(shape)
 
     def close(self):
-        self.theta = self.events = self.hmc = self.moves = None
+        self.theta = self.events = self.hmc = self.moves = self.marginals = None
         for p in self._ptrs:
             self._lib.seir_host_free(p)
         self._ptrs = []
@@ -76,6 +128,7 @@ class PinnedTrace:
 class ChainSampler:
     # thinning interval in force for the next burst (subclasses that never run __init__ sample every sweep)
     _thin = 1
+    _summary_on = False           # reset_summary has been called: the device holds accumulators and marginal arrays
 
     def __init__(self, model: SeirModel, config: dict, num_chains: int, seed: int = 0,
                  t_range=None, num_leapfrog_steps: int = 16, trace_capacity: int = 100,
@@ -326,25 +379,87 @@ class ChainSampler:
 
     def trace_view(self, buf: PinnedTrace, count: int) -> Trace:
         n = int(count)
-        return self._as_trace(n, buf.theta[:n], None if buf.events is None else buf.events[:n], buf.hmc[:n],
-                              buf.moves[:n])
+        tr = self._as_trace(n, buf.theta[:n], None if buf.events is None else buf.events[:n], buf.hmc[:n],
+                            buf.moves[:n])
+        if buf.marginals is not None:
+            tr.marginals = {k: v[:n] for k, v in buf.marginals.items()}
+        return tr
 
-    def sample_bursts(self, num_bursts: int, burst: int, consume, events: bool = True):
+    # -- summaries of the recorded events on the device (include/seir_hip.h) --------------------------
+    def reset_summary(self):
+        """Enable the summaries (first call) and zero the moment accumulators, `count` and the overflow flag, in stream
+        order: the next draw folded becomes `ref`."""
+        _lib.check(self._lib.seir_sampler_summary_reset(self._s))
+        self._summary_on = True
+
+    def summarize(self, first: int, count: int, accumulate: bool = True):
+        """Enqueue the summary of trace slots [first, first+count) behind the sweeps that fill them: their marginals are
+        written, and with `accumulate` the draws are folded into the moments."""
+        _lib.check(self._lib.seir_sampler_summarize(self._s, int(first), int(count), int(bool(accumulate))))
+
+    def _marg_ptrs(self, m):
+        return [m[k].ctypes.data_as(_lib.c_int64_p) for k in MARGINAL_KEYS]
+
+    def read_marginals(self, count: int, first: int = 0) -> dict:
+        """Blocking read of the marginals of trace slots [first, first+count): MARGINAL_KEYS -> int64 arrays with
+        leading axes [count, B]."""
+        n = int(count)
+        m = dict(events_by_day=np.empty((n, self.B, self.T, 3), np.int64),
+                 events_by_location=np.empty((n, self.B, self.M, 3), np.int64),
+                 state_by_day=np.empty((n, self.B, self.T, 3), np.int64))
+        _lib.check(self._lib.seir_sampler_read_marginals(self._s, int(first), n, *self._marg_ptrs(m)))
+        return m
+
+    def read_marginals_async(self, count: int, first: int, into: PinnedTrace):
+        """As `read_trace_async`, for the marginals; completed by `trace_wait()`."""
+        if int(count) > into.count or into.marginals is None:
+            raise ValueError("pinned buffer too small or without marginals")
+        _lib.check(self._lib.seir_sampler_read_marginals_async(self._s, int(first), int(count),
+                                                               *self._marg_ptrs(into.marginals)))
+
+    def summary(self) -> Summary:
+        """The moments folded since the last `reset_summary` (blocking).  Raises `SeirError` (SEIR_ERR_STATE) if an
+        accumulator overflowed."""
+        shape = (self.B, self.M, self.T, len(SUMMARY_QUANTITIES))
+        cnt = np.zeros(self.B, np.uint64)
+        ref, sm, sq = np.empty(shape, np.int32), np.empty(shape, np.int64), np.empty(shape, np.uint64)
+        _lib.check(self._lib.seir_sampler_read_summary(
+            self._s, cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ref.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+            sm.ctypes.data_as(_lib.c_int64_p), sq.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        return Summary(count=cnt, ref=ref, sum=sm, sumsq=sq)
+
+    def _summarize_mode(self, summarize):
+        """`summarize` of sample / sample_bursts: False, True (marginals + moments) or "marginals" (accumulate = 0)."""
+        if summarize not in (False, True, "marginals"):
+            raise ValueError(f"summarize={summarize!r}: False, True or 'marginals'")
+        if summarize and not self._summary_on:
+            self.reset_summary()
+        return bool(summarize), summarize is True
+
+    def sample_bursts(self, num_bursts: int, burst: int, consume, events: bool = True, summarize=False):
         """`num_bursts` x `burst` kept draws (`burst * thin` sweeps each) with the burst buffer used as two halves:
         while burst k+1 runs on the device, burst k crosses PCIe into page-locked memory on a copy stream and `consume(trace, k)`
         (e.g. the HDF5 writer) runs on a worker thread -- the sampler only waits when the consumer is
         the slower side.  Needs trace_capacity >= 2 * burst.  The trace handed to `consume` is a view of a
-        pinned buffer that is re-used two bursts later: copy what must outlive the call."""
+        pinned buffer that is re-used two bursts later: copy what must outlive the call.
+
+        `summarize` (True, or "marginals" for the marginals without folding the draws into the moments): every burst is
+        summarised on the device right behind its sweeps (snapshot -> reset_trace -> run -> summarize, in stream order) and
+        its marginals cross with the trace (`trace.marginals`); with `events=False` the event tensors never leave the
+        device.  A burst that is run again after a hand-off time-out is not counted twice: the snapshot taken at its start
+        holds the accumulators."""
         from concurrent.futures import ThreadPoolExecutor
+        do_sum, accumulate = self._summarize_mode(summarize)
         burst, num_bursts = int(burst), int(num_bursts)
         if 2 * burst > self.cap:
             raise ValueError(f"sample_bursts needs trace_capacity >= 2 * burst = {2 * burst}, have {self.cap}")
         # page-locking GBs of host memory takes tenths of a second: the two buffers are kept for the next call
-        key = (burst, bool(events))
+        key = (burst, bool(events), do_sum)
         if getattr(self, "_pinned_key", None) != key:
             for bf in getattr(self, "_pinned", []):
                 bf.close()
-            self._pinned = [PinnedTrace(self, burst, events), PinnedTrace(self, burst, events)]
+            mk = dict(marginals=True) if do_sum else {}
+            self._pinned = [PinnedTrace(self, burst, events, **mk), PinnedTrace(self, burst, events, **mk)]
             self._pinned_key = key
         bufs = self._pinned
         futs = [None, None]
@@ -366,6 +481,8 @@ class ChainSampler:
                                 self.snapshot(h)                 # stream order: the state burst i starts from
                             self.reset_trace(at=h * burst)
                             self.run(burst * self._thin)         # asynchronous; a re-run after _recover passes here again
+                            if do_sum:
+                                self.summarize(h * burst, burst, accumulate)
                         if prev >= 0:
                             self.trace_wait()                    # burst prev has landed (it crossed while burst i ran)
                             futs[prev & 1] = pool.submit(consume, self.trace_view(bufs[prev & 1], burst), prev)
@@ -373,6 +490,8 @@ class ChainSampler:
                             self._burst_ok()
                         if i < num_bursts:
                             self.read_trace_async(burst, h * burst, bufs[h])
+                            if do_sum:
+                                self.read_marginals_async(burst, h * burst, bufs[h])
                             prev = i
                             i += 1
                     except _lib.HandoffTimeout as e:
@@ -393,9 +512,11 @@ class ChainSampler:
             except _lib.HandoffTimeout:
                 pass
 
-    def sample(self, num_sweeps: int, events: bool = True) -> Trace:
+    def sample(self, num_sweeps: int, events: bool = True, summarize=False) -> Trace:
         """reset_trace + run + read: the analogue of one `sample_chain` call with `num_sweeps` results, each the last of
-        `thin` sweeps."""
+        `thin` sweeps.  `summarize` as in `sample_bursts`: the burst is summarised on the device and `trace.marginals`
+        filled."""
+        do_sum, accumulate = self._summarize_mode(summarize)
         if num_sweeps > self.cap:
             raise ValueError(f"num_sweeps={num_sweeps} exceeds trace_capacity={self.cap}")
         while True:
@@ -404,7 +525,11 @@ class ChainSampler:
             self.reset_trace()
             self.run(num_sweeps * self._thin)
             try:
+                if do_sum:
+                    self.summarize(0, num_sweeps, accumulate)
                 tr = self.read_trace(num_sweeps, events=events)
+                if do_sum:
+                    tr.marginals = self.read_marginals(num_sweeps)
             except _lib.HandoffTimeout as e:
                 if not self.auto_recover:
                     raise

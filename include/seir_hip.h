@@ -401,6 +401,58 @@ int seir_sampler_launch_form(seir_sampler *s, int32_t *hmc_mode, int32_t *moves_
 int seir_sampler_debug_fail_handoff(seir_sampler *s, int32_t chain);
 
 /* ------------------------------------------------------------------------
+ * Summaries of samples/seir on the device: moments and marginals.
+ *
+ * Stand in for the reductions a consumer of the event tensor samples/seir [n][M][T][3] (written per burst by
+ * inference.py:285-300 / :453-468) computes after reading it back: posterior mean and spread of incidence and of the
+ * state per location and day, national curves per draw, cumulative incidence per location per draw.  They are formed
+ * from the burst buffer where it lies, so that kilobytes per draw leave the device instead of megabytes.
+ *
+ * Definitions (csrc/summary_update.h).  Six integer quantities per cell (m, t), in this order: the event counts
+ * k_se, k_ei, k_ir of the draw and the state S, E, I at the start of day t, scanned from the draw's recorded events
+ * and the context's initial state (S[t] = S0 - sum_{s<t} k_se[s], ...: model_spec.compute_state; R follows from N).
+ *   Moments, per chain b over the draws j = 0 .. n-1 folded since the last reset, exact integers:
+ *     ref[b][m][t][q]   (int32)   the value in the first draw folded after the reset
+ *     sum               (int64)   sum_j (x_j - ref)
+ *     sumsq             (uint64)  sum_j (x_j - ref)^2
+ *     count[b]          (uint64)  n
+ *   mean = ref + sum / n and the unbiased variance (sumsq - sum^2 / n) / (n - 1) are formed by the host.  A sticky
+ *   flag is raised when any sumsq reaches 2^63 (until then |sum| <= sumsq fits int64); seir_sampler_read_summary then
+ *   fails with SEIR_ERR_STATE until the next reset.
+ *   Marginals per kept draw, int64, indexed by trace slot like the trace itself ([count][B] leading):
+ *     events_by_day      [count][B][T][3]  sum_m k
+ *     events_by_location [count][B][M][3]  sum_t k
+ *     state_by_day       [count][B][T][3]  sum_m (S, E, I)
+ * All of it is integer arithmetic: no result depends on the order of additions, on the launch geometry or on how a
+ * burst is cut into calls.  Sweeps dropped by thinning are not in the trace and not in the summaries.
+ *
+ * The feature is switched on by the first seir_sampler_summary_reset; a sampler that never calls it allocates and
+ * does nothing more than before.  While it is on, seir_sampler_snapshot / _restore also save and restore the
+ * accumulators, count and the flag (device copies in stream order): a burst can be folded as soon as it is enqueued,
+ * and a burst that is run again after a hand-off time-out is not counted twice.  A snapshot taken before the first
+ * reset holds no accumulators; restoring it leaves them as they are.
+ * ------------------------------------------------------------------------ */
+/* First call allocates; every call zeroes count, the accumulators and the overflow flag, in stream order: the next
+ * draw folded becomes ref.  SEIR_ERR_STATE if the sampler was created with record_events == 0. */
+int seir_sampler_summary_reset(seir_sampler *s);
+/* Summarise trace slots [first_slot, first_slot + count) of every chain: asynchronous on the context stream, behind the
+ * sweeps that fill those slots.  Writes the three marginals of those slots and, if accumulate != 0, folds the draws
+ * into the moments in slot order (accumulate == 0: marginals only; accumulators and count untouched).
+ * SEIR_ERR_INVALID for slots outside the burst buffer, SEIR_ERR_STATE before a reset or with record_events == 0. */
+int seir_sampler_summarize(seir_sampler *s, int32_t first_slot, int32_t count, int32_t accumulate);
+/* Blocking read of the marginals of slots [first, first + count) (written by the last seir_sampler_summarize that
+ * covered them); any pointer may be NULL to skip that array.  Host pointers. */
+int seir_sampler_read_marginals(seir_sampler *s, int32_t first, int32_t count,
+                                int64_t *events_by_day, int64_t *events_by_location, int64_t *state_by_day);
+/* The same on the copy stream of seir_sampler_read_trace_async, behind everything queued on the context stream so far;
+ * completed by seir_sampler_trace_wait.  The host buffers should be page-locked (seir_host_alloc). */
+int seir_sampler_read_marginals_async(seir_sampler *s, int32_t first, int32_t count,
+                                      int64_t *events_by_day, int64_t *events_by_location, int64_t *state_by_day);
+/* Blocking read of the moments: count [B]; ref, sum, sumsq each [B][M][T][6].  Any pointer may be NULL.
+ * SEIR_ERR_STATE (and a message) if the overflow flag is up, or before a reset. */
+int seir_sampler_read_summary(seir_sampler *s, uint64_t *count, int32_t *ref, int64_t *sum, uint64_t *sumsq);
+
+/* ------------------------------------------------------------------------
  * Reproduction number R_it.
  *
  * calc_posterior_rit (covid19uk/posterior/reproduction_number.py:13-44): for each
