@@ -158,6 +158,13 @@ _SIGNATURES = {
     "seir_sampler_read_summary": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
                                                  ctypes.POINTER(ctypes.c_int32), c_int64_p,
                                                  ctypes.POINTER(ctypes.c_uint64)]),
+    # convergence diagnostics: batch sums and marks next to the moments
+    "seir_sampler_diag_reset": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
+    "seir_sampler_diag_mark": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
+    "seir_sampler_read_diag": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), c_int64_p,
+                                              ctypes.POINTER(ctypes.c_uint64)]),
+    "seir_sampler_read_diag_mark": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64),
+                                                   c_int64_p, ctypes.POINTER(ctypes.c_uint64)]),
 }
 
 _lib = None

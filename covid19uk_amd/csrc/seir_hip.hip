@@ -1059,6 +1059,13 @@ struct seir_sampler {
     SummaryBufs sum{};
     void *sum_snap[2] = {nullptr, nullptr};   // shadow copies of ref | sum | sumsq | count | flag for the two snapshot slots
     bool sum_snap_valid[2] = {false, false};
+    // --- convergence diagnostics (seir_sampler_diag_reset ...): ONE allocation of 64-bit words,
+    //     bsum [n] | bsumsq [n] | nbatch [B] | mark 0: count [B] | sum [n] | sumsq [n] | mark 1: the same
+    bool diag_on = false;
+    SummaryDiag<1> diag{};
+    uint64_t *diag_buf = nullptr;
+    void *diag_snap[2] = {nullptr, nullptr};  // shadow copies of all of it for the two snapshot slots
+    bool diag_snap_valid[2] = {false, false};
 };
 
 template <typename T>
@@ -1094,6 +1101,7 @@ extern "C" void seir_sampler_destroy(seir_sampler *s) {
     for (void *p : s->allocs) (void)hipFree(p);
     for (void *p : s->snap) if (p) (void)hipFree(p);
     for (void *p : s->sum_snap) if (p) (void)hipFree(p);
+    for (void *p : s->diag_snap) if (p) (void)hipFree(p);
     Work &w = s->ctx->w;
     for (int x = 0; x < 3; ++x) { w.K[x] = nullptr; w.St[x] = nullptr; }
     w.rowtot = w.rngtot = nullptr;
@@ -1376,8 +1384,27 @@ extern "C" int seir_sampler_debug_fail_handoff(seir_sampler *s, int32_t chain) {
 // stream order), so that a burst can be folded as soon as it is enqueued and a burst that is run again after a hand-off
 // time-out is not counted twice.  A snapshot taken before summaries were enabled holds none: restoring it leaves them alone.
 static size_t summary_cells(const seir_sampler *s) { return (size_t)s->cfg.B * s->ctx->d.M * s->ctx->d.T * seir::SUMMARY_Q; }
+static size_t diag_words(const seir_sampler *s) { return 6 * summary_cells(s) + 3 * (size_t)s->cfg.B; }
+static uint64_t *diag_mark(const seir_sampler *s, int which) {       // count [B] | sum [n] | sumsq [n]
+    const size_t n = summary_cells(s), B = (size_t)s->cfg.B;
+    return s->diag_buf + 2 * n + B + (size_t)which * (B + 2 * n);
+}
+// The batch accumulators and the marks travel with a snapshot as the moments do: a burst that is run again is counted
+// once, and a mark taken in a burst that is thrown away goes with it.
+static int diag_shadow(seir_sampler *s, int slot, bool save) {
+    if (!s->diag_on) return 0;
+    if (!save && !s->diag_snap_valid[slot]) return 0;
+    const size_t bytes = diag_words(s) * sizeof(uint64_t);
+    if (!s->diag_snap[slot]) HIP_TRY(hipMalloc(&s->diag_snap[slot], bytes));
+    HIP_TRY(hipMemcpyAsync(save ? s->diag_snap[slot] : (void *)s->diag_buf, save ? (void *)s->diag_buf : s->diag_snap[slot], bytes,
+                           hipMemcpyDeviceToDevice, s->ctx->stream));
+    if (save) s->diag_snap_valid[slot] = true;
+    return 0;
+}
+
 static int summary_shadow(seir_sampler *s, int slot, bool save) {
     if (!s->sum_on) return 0;
+    if (int rc = diag_shadow(s, slot, save)) return rc;
     if (!save && !s->sum_snap_valid[slot]) return 0;
     const size_t n = summary_cells(s), B = (size_t)s->cfg.B;
     struct Part { void *p; size_t bytes; } parts[5] = {{s->sum.ref, n * sizeof(int32_t)}, {s->sum.sum, n * sizeof(int64_t)},
@@ -2068,6 +2095,8 @@ extern "C" int seir_sampler_summary_reset(seir_sampler *s) {
     HIP_TRY(hipMemsetAsync(sb.sumsq, 0, n * sizeof(uint64_t), st));
     HIP_TRY(hipMemsetAsync(sb.count, 0, B * sizeof(uint64_t), st));
     HIP_TRY(hipMemsetAsync(sb.overflow, 0, sizeof(unsigned), st));
+    // the batch sums are about the same ref and the marks are copies of these accumulators: they start again with them
+    if (s->diag_on) HIP_TRY(hipMemsetAsync(s->diag_buf, 0, diag_words(s) * sizeof(uint64_t), st));
     return 0;
 }
 
@@ -2093,12 +2122,20 @@ extern "C" int seir_sampler_summarize(seir_sampler *s, int32_t first, int32_t co
     for (int j0 = 0; j0 < count; j0 += SUM_JMAX) {
         const int nj = std::min(SUM_JMAX, count - j0);
         const dim3 grid((d.M + SUM_ROWS - 1) / SUM_ROWS, B), block(64 * SUM_ROWS);
-        if (s->cfg.ev16)
-            hipLaunchKernelGGL(k_summarize<1>, grid, block, 0, l.st, d, ctx->c, s->sum, (const void *)s->ch.tr_events, B,
-                               first + j0, nj, accumulate != 0);
+        // while the diagnostics are on, folding draws goes through the instance that carries the batch sums as well
+        const bool diag = s->diag_on && accumulate != 0;
+        if (s->cfg.ev16 && diag)
+            hipLaunchKernelGGL((k_summarize<1, 1>), grid, block, 0, l.st, d, ctx->c, s->sum, (const void *)s->ch.tr_events, B,
+                               first + j0, nj, 1, s->diag);
+        else if (diag)
+            hipLaunchKernelGGL((k_summarize<0, 1>), grid, block, 0, l.st, d, ctx->c, s->sum, (const void *)s->ch.tr_events, B,
+                               first + j0, nj, 1, s->diag);
+        else if (s->cfg.ev16)
+            hipLaunchKernelGGL((k_summarize<1, 0>), grid, block, 0, l.st, d, ctx->c, s->sum, (const void *)s->ch.tr_events, B,
+                               first + j0, nj, accumulate != 0, SummaryDiag<0>{});
         else
-            hipLaunchKernelGGL(k_summarize<0>, grid, block, 0, l.st, d, ctx->c, s->sum, (const void *)s->ch.tr_events, B,
-                               first + j0, nj, accumulate != 0);
+            hipLaunchKernelGGL((k_summarize<0, 0>), grid, block, 0, l.st, d, ctx->c, s->sum, (const void *)s->ch.tr_events, B,
+                               first + j0, nj, accumulate != 0, SummaryDiag<0>{});
         hipLaunchKernelGGL(k_summary_finish, dim3(nj, B), dim3(64), 0, l.st, d, ctx->c, s->sum, B, first + j0, nj,
                            accumulate != 0);
     }
@@ -2160,6 +2197,88 @@ extern "C" int seir_sampler_read_summary(seir_sampler *s, uint64_t *count, int32
     if (flag) return fail(SEIR_ERR_STATE, "a sum of squared deviations reached 2^63: the moment accumulators overflowed "
                           "(seir_sampler_summary_reset starts them again)");
     return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Convergence diagnostics (include/seir_hip.h; the DIAG instance of k_summarize)
+// ---------------------------------------------------------------------------
+extern "C" int seir_sampler_diag_reset(seir_sampler *s, int32_t batch_len) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if (batch_len < 1) return fail(SEIR_ERR_INVALID, "batch_len=%d: a batch has at least one draw", batch_len);
+    if (!s->record_events) return fail(SEIR_ERR_STATE, "sampler was created with record_events=0: there are no recorded events to diagnose");
+    if (!s->diag_on) {
+        if ((rc = s_alloc(s, &s->diag_buf, diag_words(s)))) return rc;
+        const size_t n = summary_cells(s);
+        s->diag.bsum = reinterpret_cast<int64_t *>(s->diag_buf);
+        s->diag.bsumsq = s->diag_buf + n;
+        s->diag.nbatch = s->diag_buf + 2 * n;
+        s->diag_on = true;
+    }
+    s->diag.L = (uint64_t)batch_len;
+    // a snapshot taken before this reset holds batch sums cut by another L (which is no part of it): restoring it from now
+    // on leaves the moments, the batch sums and the marks alone, as a snapshot from before the summaries were enabled does
+    for (int slot = 0; slot < 2; ++slot) s->sum_snap_valid[slot] = s->diag_snap_valid[slot] = false;
+    return seir_sampler_summary_reset(s);            // zeroes the batch sums and the marks with the moments
+}
+
+static int diag_check(seir_sampler *s, int32_t which) {
+    if (!s->record_events) return fail(SEIR_ERR_STATE, "sampler was created with record_events=0: there are no recorded events to diagnose");
+    if (!s->diag_on) return fail(SEIR_ERR_STATE, "diagnostics are not enabled: call seir_sampler_diag_reset first");
+    if (which < 0 || which > 1) return fail(SEIR_ERR_INVALID, "mark %d: marks are numbered 0 and 1", which);
+    return 0;
+}
+
+extern "C" int seir_sampler_diag_mark(seir_sampler *s, int32_t which) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = diag_check(s, which))) return rc;
+    const size_t n = summary_cells(s), B = (size_t)s->cfg.B;
+    uint64_t *mk = diag_mark(s, which);
+    hipStream_t st = s->ctx->stream;
+    HIP_TRY(hipMemcpyAsync(mk, s->sum.count, B * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(mk + B, s->sum.sum, n * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(mk + B + n, s->sum.sumsq, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+static int diag_read_end(seir_sampler *s, unsigned flag) {
+    int rc = check_ev_overflow(s);
+    if (rc) return rc;
+    if (flag) return fail(SEIR_ERR_STATE, "a sum of squares reached 2^63 or a batch sum 2^32: the accumulators overflowed "
+                          "(seir_sampler_diag_reset starts them again)");
+    return 0;
+}
+
+extern "C" int seir_sampler_read_diag(seir_sampler *s, uint64_t *nbatch, int64_t *bsum, uint64_t *bsumsq) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = diag_check(s, 0))) return rc;
+    hipStream_t st = s->ctx->stream;
+    const size_t n = summary_cells(s);
+    unsigned flag = 0;
+    HIP_TRY(hipMemcpyAsync(&flag, s->sum.overflow, sizeof(flag), hipMemcpyDeviceToHost, st));
+    if (nbatch) HIP_TRY(hipMemcpyAsync(nbatch, s->diag.nbatch, sizeof(uint64_t) * s->cfg.B, hipMemcpyDeviceToHost, st));
+    if (bsum) HIP_TRY(hipMemcpyAsync(bsum, s->diag.bsum, sizeof(int64_t) * n, hipMemcpyDeviceToHost, st));
+    if (bsumsq) HIP_TRY(hipMemcpyAsync(bsumsq, s->diag.bsumsq, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return diag_read_end(s, flag);
+}
+
+extern "C" int seir_sampler_read_diag_mark(seir_sampler *s, int32_t which, uint64_t *count, int64_t *sum, uint64_t *sumsq) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = diag_check(s, which))) return rc;
+    hipStream_t st = s->ctx->stream;
+    const size_t n = summary_cells(s), B = (size_t)s->cfg.B;
+    const uint64_t *mk = diag_mark(s, which);
+    unsigned flag = 0;
+    HIP_TRY(hipMemcpyAsync(&flag, s->sum.overflow, sizeof(flag), hipMemcpyDeviceToHost, st));
+    if (count) HIP_TRY(hipMemcpyAsync(count, mk, sizeof(uint64_t) * B, hipMemcpyDeviceToHost, st));
+    if (sum) HIP_TRY(hipMemcpyAsync(sum, mk + B, sizeof(int64_t) * n, hipMemcpyDeviceToHost, st));
+    if (sumsq) HIP_TRY(hipMemcpyAsync(sumsq, mk + B + n, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return diag_read_end(s, flag);
 }
 
 extern "C" int seir_host_alloc(void **p, uint64_t bytes) {

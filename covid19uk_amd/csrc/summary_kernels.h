@@ -22,6 +22,13 @@
 //   - state_by_day needs no pass over the cells at all: sum_m S[m][t] = sum_m S0[m] - sum_{s<t} events_by_day[s][0], and
 //     so on -- k_summary_finish scans the finished events_by_day (a wave per draw and chain) and also advances count[b].
 // No hand-off inside a launch, no persistence, nothing of the sweep's plan: ordinary launches on the context stream.
+//
+// k_summarize<EV16, 1> is the instance launched while the convergence diagnostics are on (seir_sampler_diag_reset): next
+// to the moments it carries a cell's batch sums (summary_update.h: bsum, bsumsq; 16 B per cell and quantity) the same
+// way -- loaded before the draw loop, in registers across it, stored after it.  Which draws close a batch is the same for
+// every cell of a chain: the position in the open batch, count[b] % L, is read once at the start of the launch and then
+// counted along with the draws (uniform: no 64-bit division per draw).  The DIAG = 0 instances take an empty argument in
+// its place and compile to what they were before the parameter existed.
 #pragma once
 
 #include "summary_update.h"
@@ -44,6 +51,15 @@ struct SummaryBufs {
     int64_t *sbd;                  // [cap][B][T][3] state_by_day
 };
 
+// the batch accumulators of the diagnostics; the DIAG = 0 instances of k_summarize get the empty one
+template <int DIAG> struct SummaryDiag {};
+template <> struct SummaryDiag<1> {
+    int64_t *bsum;                 // [B][M][T][6] sum of (x - ref) over the open batch
+    uint64_t *bsumsq;              // [B][M][T][6] sum of the closed batches' squared sums
+    uint64_t *nbatch;              // [B] closed batches (= count / L, kept for the reader)
+    uint64_t L;                    // batch length, >= 1
+};
+
 struct __attribute__((aligned(4))) SumEv32 { int32_t k[3]; };
 struct __attribute__((aligned(2))) SumEv16 { uint16_t k[3]; };
 
@@ -61,10 +77,10 @@ __device__ __forceinline__ void summary_load(const void *__restrict__ tr, size_t
 }
 
 // grid (ceil(M / SUM_ROWS), B), 64 SUM_ROWS threads.  1 <= count <= SUM_JMAX, first + count <= cap (the host checks).
-template <int EV16>
+template <int EV16, int DIAG = 0>
 __global__ __launch_bounds__(64 * SUM_ROWS) void k_summarize(Dims d, Consts c, SummaryBufs sb,
                                                              const void *__restrict__ tr_events, int B, int first,
-                                                             int count, int accumulate) {
+                                                             int count, int accumulate, SummaryDiag<DIAG> dg) {
     debug_skew(d);
     __shared__ unsigned long long bd[SUM_JB][64][3];
     __shared__ int carry[SUM_ROWS][SUM_JMAX][3];
@@ -74,6 +90,11 @@ __global__ __launch_bounds__(64 * SUM_ROWS) void k_summarize(Dims d, Consts c, S
     const bool row_ok = m < M;
     const bool fold = accumulate != 0;
     const bool fresh = fold && sb.count[b] == 0;      // count moves in k_summary_finish, a launch of its own: no race
+    unsigned long long phase = 0ull, blen = 1ull;     // draws already in the open batch at the start of the launch; L
+    if constexpr (DIAG) {
+        blen = dg.L;
+        phase = fold ? sb.count[b] % blen : 0ull;
+    }
     int s0[3] = {0, 0, 0};
     if (row_ok)
 #pragma unroll
@@ -93,6 +114,12 @@ __global__ __launch_bounds__(64 * SUM_ROWS) void k_summarize(Dims d, Consts c, S
         uint64_t sq[seir::SUMMARY_Q];
 #pragma unroll
         for (int q = 0; q < seir::SUMMARY_Q; ++q) { ref[q] = 0; sm[q] = 0; sq[q] = 0; }
+        int64_t bs[DIAG ? seir::SUMMARY_Q : 1];
+        uint64_t bq[DIAG ? seir::SUMMARY_Q : 1];
+        if constexpr (DIAG) {
+#pragma unroll
+            for (int q = 0; q < seir::SUMMARY_Q; ++q) { bs[q] = 0; bq[q] = 0; }
+        }
         if (fold && live && !fresh) {
 #pragma unroll
             for (int q = 0; q < seir::SUMMARY_Q; ++q) {
@@ -100,7 +127,15 @@ __global__ __launch_bounds__(64 * SUM_ROWS) void k_summarize(Dims d, Consts c, S
                 sm[q] = sb.sum[cell * seir::SUMMARY_Q + q];
                 sq[q] = sb.sumsq[cell * seir::SUMMARY_Q + q];
             }
+            if constexpr (DIAG) {
+#pragma unroll
+                for (int q = 0; q < seir::SUMMARY_Q; ++q) {
+                    bs[q] = dg.bsum[cell * seir::SUMMARY_Q + q];
+                    bq[q] = dg.bsumsq[cell * seir::SUMMARY_Q + q];
+                }
+            }
         }
+        unsigned long long pos = phase;                // uniform: the same draws close a batch in every cell
         for (int jb = 0; jb < count; jb += SUM_JB) {
             const int nj = min(SUM_JB, count - jb);
             for (int ju = 0; ju < nj; ju += SUM_U) {
@@ -133,8 +168,17 @@ __global__ __launch_bounds__(64 * SUM_ROWS) void k_summarize(Dims d, Consts c, S
 #pragma unroll
                             for (int q = 0; q < seir::SUMMARY_Q; ++q)
                                 ovf |= seir::summary_fold(ref[q], sm[q], sq[q], val[q], is_first);
+                            if constexpr (DIAG) {
+#pragma unroll
+                                for (int q = 0; q < seir::SUMMARY_Q; ++q) seir::summary_batch_add(bs[q], ref[q], val[q]);
+                                if (pos + 1 == blen) {             // uniform
+#pragma unroll
+                                    for (int q = 0; q < seir::SUMMARY_Q; ++q) ovf |= seir::summary_batch_close(bs[q], bq[q]);
+                                }
+                            }
                         }
                     }
+                    if constexpr (DIAG) pos = pos + 1 == blen ? 0ull : pos + 1;
                 }
             }
             __syncthreads();
@@ -157,8 +201,17 @@ __global__ __launch_bounds__(64 * SUM_ROWS) void k_summarize(Dims d, Consts c, S
                 sb.sum[cell * seir::SUMMARY_Q + q] = sm[q];
                 sb.sumsq[cell * seir::SUMMARY_Q + q] = sq[q];
             }
+            if constexpr (DIAG) {
+#pragma unroll
+                for (int q = 0; q < seir::SUMMARY_Q; ++q) {
+                    dg.bsum[cell * seir::SUMMARY_Q + q] = bs[q];
+                    dg.bsumsq[cell * seir::SUMMARY_Q + q] = bq[q];
+                }
+            }
         }
     }
+    if constexpr (DIAG)
+        if (fold && blockIdx.x == 0 && threadIdx.x == 0) dg.nbatch[b] = (sb.count[b] + (unsigned long long)count) / blen;
     // the carries after the last chunk are the row totals
     if (row_ok)
         for (int i = lane; i < count * 3; i += 64) {

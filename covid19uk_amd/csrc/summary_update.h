@@ -40,4 +40,31 @@ SEIR_SU_HD bool summary_fold(int32_t &ref, int64_t &sum, uint64_t &sumsq, int32_
     return sumsq >= (1ull << 63) || sumsq < before;
 }
 
+// Batch sums for the convergence diagnostics (include/seir_hip.h, "Convergence diagnostics"): the draws folded since the
+// reset are cut into batches of L, batch k being draws [kL, (k+1)L).  Per chain, cell and quantity, next to the moments:
+//     bsum   = sum of (x_j - ref) over the draws of the batch that is open            (int64)
+//     bsumsq = sum over the closed batches of B_k^2, B_k that batch's bsum at its end   (uint64)
+// The variance of the B_k is what the batch-means estimate of the autocorrelation time is made of
+// (covid19uk_amd/posterior/diagnostics.py); like the moments it is exact integer arithmetic.
+//
+// summary_batch_add takes the draw AFTER summary_fold has seen it (so that ref is the first draw's value for that draw too).
+SEIR_SU_HD void summary_batch_add(int64_t &bsum, int32_t ref, int32_t x) {
+    bsum = (int64_t)((uint64_t)bsum + (uint64_t)((int64_t)x - (int64_t)ref));    // wraps only once the moments' flag is up
+}
+
+// The draw just added was the last of its batch: bsumsq += bsum^2, bsum = 0.  Returns the overflow test: |bsum| >= 2^32
+// (its square does not fit 64 bits: bsumsq is then left as it is), or bsumsq has reached 2^63 or wrapped.  The caller raises
+// the same sticky flag as for the moments.
+SEIR_SU_HD bool summary_batch_close(int64_t &bsum, uint64_t &bsumsq) {
+    const uint64_t a = bsum < 0 ? (uint64_t)0 - (uint64_t)bsum : (uint64_t)bsum;
+    bsum = 0;
+    if (a >> 32) return true;
+    const uint64_t before = bsumsq;
+    bsumsq = before + a * a;
+    return bsumsq >= (1ull << 63) || bsumsq < before;
+}
+
+// Is draw j of a launch (0-based) the last of a batch?  `count` is the number of draws folded before the launch.
+SEIR_SU_HD bool summary_batch_closes(uint64_t count, uint64_t j, uint64_t L) { return (count + j + 1) % L == 0; }
+
 }  // namespace seir

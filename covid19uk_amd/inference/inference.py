@@ -19,7 +19,8 @@ import numpy as np
 
 from .. import hdf5io
 from .. import model_spec
-from ..sampler import MOVE_KEYS, ChainSampler
+from ..posterior import diagnostics as diag_mod
+from ..sampler import MOVE_KEYS, ChainSampler, Summary
 from ..seir import SeirModel
 from .mcmc_kernel_factory import event_kernel_config, hmc_kernel_kwargs_default
 
@@ -193,6 +194,11 @@ class Posterior:
         self.create_dataset("summaries/state_mean", np.ascontiguousarray(mean[..., 3:]))
         self.create_dataset("summaries/state_var", np.ascontiguousarray(var[..., 3:]))
 
+    def write_diagnostics(self, datasets: dict):
+        """The group diagnostics/ of one chain (`posterior.diagnostics.chain_datasets`), float64."""
+        for k, v in datasets.items():
+            self.create_dataset(f"diagnostics/{k}", np.asarray(v, np.float64))
+
     def __getitem__(self, name):
         if self.use_h5:
             self._file.flush()
@@ -278,6 +284,43 @@ def summaries_mode(config, override=None):
     return mode
 
 
+DIAGNOSTICS = ("off", "on")
+
+
+def diagnostics_mode(config, override=None, batch=None):
+    """Mcmc.diagnostics (absent: "off") and Mcmc.diagnostics_batch, or the command line's `--diagnostics` /
+    `--diagnostics-batch`: (mode, batch length).  With "on" the batch length defaults to num_burst_samples (one burst is
+    one batch) and must divide it or be a multiple of it, and the run needs two bursts for its two halves.  Everything
+    else is refused, a batch length given with "off" included -- here, before a sampler exists."""
+    mode = config.get("diagnostics", "off") if override is None else override
+    if mode is False or mode is True:                       # YAML reads a bare `on` / `off` as a boolean
+        mode = "on" if mode else "off"
+    if mode not in DIAGNOSTICS:
+        raise ValueError(f"diagnostics={mode!r}: choose one of {', '.join(DIAGNOSTICS)}")
+    if batch is None:
+        batch = config.get("diagnostics_batch")
+    if mode == "off":
+        if batch is not None:
+            raise ValueError(f"diagnostics batch length {batch} given with diagnostics=off: it would have no effect")
+        return mode, 0
+    nb, ns = int(config["num_bursts"]), int(config["num_burst_samples"])
+    if nb < 2:
+        raise ValueError(f"diagnostics=on needs num_bursts >= 2 (the two halves of split R-hat are whole bursts), have {nb}")
+    L = ns if batch is None else int(batch)
+    if L < 1 or ns < 1 or (L % ns != 0 and ns % L != 0):
+        raise ValueError(f"diagnostics batch length {L}: it must divide num_burst_samples = {ns} or be a multiple of it")
+    return mode, L
+
+
+def diagnostics_marks(nb):
+    """{burst index: mark}: mark 0 behind burst nb // 2 - 1 and, with nb odd, mark 1 behind burst nb - nb // 2 - 1, so that
+    the middle burst belongs to neither half."""
+    marks = {nb // 2 - 1: 0}
+    if nb % 2:
+        marks[nb - nb // 2 - 1] = 1
+    return marks
+
+
 def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_step_size=False):
     """The windowed schedule of inference.py:303-470: fast 200, slow 25*2^k (k<6), fast 50,
     then num_bursts x num_burst_samples with the kernel fixed.  Every draw of the warm-up is
@@ -290,6 +333,13 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     # marginals (the warm-up without folding), the moments cover the sampling phase, and with "only" no event tensor is read
     warm_kw = {} if summaries == "off" else dict(events=summaries != "only", summarize="marginals")
     burst_kw = {} if summaries == "off" else dict(events=summaries != "only", summarize=True)
+    # diagnostics "on" folds the sampling phase's draws whatever `summaries` says (which then only decides what is written)
+    diagnostics, batch_len = diagnostics_mode(config)
+    marks, theta_acc = {}, None
+    if diagnostics == "on":
+        burst_kw = dict(events=summaries != "only", summarize=True)
+        marks = diagnostics_marks(int(config["num_bursts"]))
+        theta_acc = diag_mod.DrawAccumulator(batch_len)
     sampler.set_thin(1)
     first_window_size, last_window_size, slow_window_size, num_slow_windows = 200, 50, 25, 6
     dual_averaging_kwargs = {"target_accept_prob": 0.75}
@@ -333,29 +383,50 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     sampler.set_kernel(step_size=step_size, variance=sampler.get_kernel()[1])
     nb, ns = int(config["num_bursts"]), int(config["num_burst_samples"])
     sampler.set_thin(thin)                                  # in force from the first burst's trace reset
-    if summaries != "off":
+    if diagnostics == "on":
+        sampler.reset_diagnostics(batch_len)                # the moments too: all of it is over the sampling phase
+    elif summaries != "off":
         sampler.reset_summary()                             # the moments are over the sampling phase
-        if summaries == "only":
-            print("summaries only: the event tensors stay on the device and samples/seir is not created -- what reads it "
-                  "(thin_posterior, predict, reproduction_number) cannot run on this output", file=log, flush=True)
+    if summaries == "only":
+        print("summaries only: the event tensors stay on the device and samples/seir is not created -- what reads it "
+              "(thin_posterior, predict, reproduction_number) cannot run on this output", file=log, flush=True)
     t0 = time.perf_counter()
     if nb and ns and sampler.cap >= 2 * ns:
         # bursts overlap: while burst k+1 runs, burst k crosses PCIe into page-locked memory and is written
         # to the HDF5 file on a worker thread (ChainSampler.sample_bursts)
         def on_burst(tr, i):
             flush(tr)
+            if theta_acc is not None:                       # the parameters' accumulators, marked where the device's are
+                theta_acc.fold(tr.theta)
+                if i in marks:
+                    theta_acc.mark(marks[i])
             print(f"  burst {i + 1}/{nb}", file=log, flush=True)
-        sampler.sample_bursts(nb, ns, on_burst, **burst_kw)
+        sampler.sample_bursts(nb, ns, on_burst, **burst_kw, **(dict(marks=marks) if marks else {}))
     else:
         for i in range(nb):
-            flush(sampler.sample(ns, **burst_kw))
+            tr = sampler.sample(ns, **burst_kw)
+            if i in marks:
+                sampler.mark(marks[i])
+            flush(tr)
+            if theta_acc is not None:
+                theta_acc.fold(tr.theta)
+                if i in marks:
+                    theta_acc.mark(marks[i])
             print(f"  burst {i + 1}/{nb}", file=log, flush=True)
     dt = time.perf_counter() - t0
     if nb * ns:
         print(f"Sampling: {nb * ns * thin * sampler.B / dt:.1f} sweeps/s, {nb * ns * sampler.B / dt:.1f} kept posterior samples/s "
               f"(thin {thin}, {sampler.B} chain(s), device->host->disk included)", file=log, flush=True)
+    dg = None
+    if diagnostics == "on":
+        dg = sampler.diagnostics()
+        ev = diag_mod.evaluate(dg, theta_acc.result())
+        for c, post in enumerate(posteriors):
+            post.write_diagnostics(diag_mod.chain_datasets(ev, c))
+        print(diag_mod.run_line(ev, diag_mod.theta_names(sampler.P, sampler.M, sampler.T))
+              + f" ({sampler.B} chain(s) of this process, batches of {batch_len})", file=log, flush=True)
     if summaries != "off":
-        sm = sampler.summary()
+        sm = sampler.summary() if dg is None else Summary(count=dg.count, ref=dg.ref, sum=dg.sum, sumsq=dg.sumsq)
         mean, var = sm.mean, sm.var
         for c, post in enumerate(posteriors):
             post.write_summary(sm.count[c], mean[c], var[c])
@@ -423,7 +494,7 @@ def launch_forms(lay, device_arg, hmc="auto", moves="auto", env=os.environ):
 
 
 def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool_step_size=False, init_jitter=0.0,
-         events_dtype="auto", hmc="auto", moves="auto", thin=None, summaries=None):
+         events_dtype="auto", hmc="auto", moves="auto", thin=None, summaries=None, diagnostics=None, diagnostics_batch=None):
     """Constructs and runs the MCMC (covid19uk/inference/inference.py:473-608).
 
     Multi-GPU: launched as one process per GPU, every rank runs `num_chains` chains with
@@ -431,9 +502,13 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     do not depend on how the job is sharded) and writes its own posterior_chain{c}.hd5; there is no
     data-path collective.  `pool_step_size` adds the one optional exchange: an all_gather of one float64
     per chain after warm-up.  `thin` overrides config["thin"] (every rank is given the same value), `summaries`
-    config["summaries"] (`summaries_mode`)."""
+    config["summaries"] (`summaries_mode`), `diagnostics` / `diagnostics_batch` config["diagnostics"] /
+    config["diagnostics_batch"] (`diagnostics_mode`)."""
     config = dict(config, thin=thin_interval(config, thin))  # refused here if < 1: before any GPU call
     config = dict(config, summaries=summaries_mode(config, summaries))    # an unknown value likewise
+    if diagnostics is not None or diagnostics_batch is not None or "diagnostics" in config or "diagnostics_batch" in config:
+        mode, batch_len = diagnostics_mode(config, diagnostics, diagnostics_batch)   # and too few bursts, or a batch length that does not fit
+        config = dict(config, diagnostics=mode, **(dict(diagnostics_batch=batch_len) if mode == "on" else {}))
     lay = job_layout(num_chains, device)                    # before any GPU call
     cov, cases, dates = read_inference_data(data_file)
     rng = np.random.default_rng(seed)                       # same imputation on every rank: one initial state per job
@@ -528,6 +603,15 @@ def main(argv=None):
                              "on = per-draw marginals samples/seir_by_day, seir_by_location, state_by_day and per-cell "
                              "summaries/* mean and variance of events and state over the sampling phase, next to samples/seir; "
                              "only = the same without samples/seir, whose tensors then never leave the device")
+    parser.add_argument("--diagnostics", choices=list(DIAGNOSTICS), default=None,
+                        help="convergence diagnostics formed on the device and the host as the run goes (overrides "
+                             "Mcmc.diagnostics; default off): on = a group diagnostics/ in every chain's file with split R-hat "
+                             "over this process's chains, batch-means ESS and the half-chain moments that "
+                             "`python -m covid19uk_amd.posterior.diagnostics` pools over files; needs num_bursts >= 2 and "
+                             "folds the sampling phase's draws on the device whatever --summaries says")
+    parser.add_argument("--diagnostics-batch", type=int, default=None, metavar="L",
+                        help="batch length of the batch-means ESS in kept draws (overrides Mcmc.diagnostics_batch; default "
+                             "num_burst_samples, which it must divide or be a multiple of)")
     args = parser.parse_args(argv)
     if args.thin is not None and args.thin < 1:
         parser.error(f"--thin {args.thin}: the thinning interval is >= 1")
@@ -535,7 +619,8 @@ def main(argv=None):
         config = yaml.load(f, Loader=yaml.FullLoader)
     mcmc(args.data_file, args.output, config["Mcmc"], seed=args.seed, num_chains=args.chains, device=args.device,
          pool_step_size=args.pool_step_size, init_jitter=args.init_jitter, events_dtype=args.events_dtype,
-         hmc=args.hmc, moves=args.moves, thin=args.thin, summaries=args.summaries)
+         hmc=args.hmc, moves=args.moves, thin=args.thin, summaries=args.summaries, diagnostics=args.diagnostics,
+         diagnostics_batch=args.diagnostics_batch)
 
 
 if __name__ == "__main__":

@@ -17,6 +17,7 @@ import sys
 import numpy as np
 
 from . import _lib
+from .posterior.diagnostics import Diagnostics
 from .seir import SeirModel, _dptr
 
 MOVE_KEYS = ("move/S->E", "move/E->I", "occult/S->E", "occult/E->I")   # inference.py:277-280
@@ -129,6 +130,7 @@ class ChainSampler:
     # thinning interval in force for the next burst (subclasses that never run __init__ sample every sweep)
     _thin = 1
     _summary_on = False           # reset_summary has been called: the device holds accumulators and marginal arrays
+    _diag_L = 0                   # batch length of the diagnostics in force (0: reset_diagnostics was never called)
 
     def __init__(self, model: SeirModel, config: dict, num_chains: int, seed: int = 0,
                  t_range=None, num_leapfrog_steps: int = 16, trace_capacity: int = 100,
@@ -428,6 +430,40 @@ class ChainSampler:
             sm.ctypes.data_as(_lib.c_int64_p), sq.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
         return Summary(count=cnt, ref=ref, sum=sm, sumsq=sq)
 
+    # -- convergence diagnostics: batch sums and marks next to the moments (include/seir_hip.h) -----------
+    def reset_diagnostics(self, batch_len: int):
+        """Enable the diagnostics (first call), set the batch length and do what `reset_summary` does, zeroing the batch
+        sums and the marks with the moments.  From now on every draw folded into the moments is folded into the batch
+        sums too."""
+        if int(batch_len) < 1:
+            raise ValueError(f"batch_len={batch_len}: a batch has at least one draw")
+        _lib.check(self._lib.seir_sampler_diag_reset(self._s, int(batch_len)))
+        self._summary_on = True
+        self._diag_L = int(batch_len)
+
+    def mark(self, which: int):
+        """Copy (count, sum, sumsq) into mark 0 / 1 on the device, in stream order behind everything queued so far."""
+        _lib.check(self._lib.seir_sampler_diag_mark(self._s, int(which)))
+
+    def diagnostics(self) -> Diagnostics:
+        """The moments, the batch sums and both marks (blocking): `covid19uk_amd.posterior.diagnostics.Diagnostics`, whose
+        `.ess`, `.half_mean`, `.half_var` and `.rhat` apply that module's formulas.  Raises `SeirError` (SEIR_ERR_STATE)
+        if an accumulator overflowed or before `reset_diagnostics`."""
+        shape = (self.B, self.M, self.T, len(SUMMARY_QUANTITIES))
+        u64p, i64p = ctypes.POINTER(ctypes.c_uint64), _lib.c_int64_p
+        nbatch = np.zeros(self.B, np.uint64)
+        bsum, bsumsq = np.empty(shape, np.int64), np.empty(shape, np.uint64)
+        _lib.check(self._lib.seir_sampler_read_diag(self._s, nbatch.ctypes.data_as(u64p), bsum.ctypes.data_as(i64p),
+                                                    bsumsq.ctypes.data_as(u64p)))
+        mc = np.zeros((2, self.B), np.uint64)
+        ms, mq = np.empty((2,) + shape, np.int64), np.empty((2,) + shape, np.uint64)
+        for w in (0, 1):
+            _lib.check(self._lib.seir_sampler_read_diag_mark(self._s, w, mc[w].ctypes.data_as(u64p), ms[w].ctypes.data_as(i64p),
+                                                             mq[w].ctypes.data_as(u64p)))
+        sm = self.summary()
+        return Diagnostics(batch_length=self._diag_L, count=sm.count, ref=sm.ref, sum=sm.sum, sumsq=sm.sumsq, bsum=bsum,
+                           bsumsq=bsumsq, nbatch=nbatch, mark_count=mc, mark_sum=ms, mark_sumsq=mq)
+
     def _summarize_mode(self, summarize):
         """`summarize` of sample / sample_bursts: False, True (marginals + moments) or "marginals" (accumulate = 0)."""
         if summarize not in (False, True, "marginals"):
@@ -436,7 +472,7 @@ class ChainSampler:
             self.reset_summary()
         return bool(summarize), summarize is True
 
-    def sample_bursts(self, num_bursts: int, burst: int, consume, events: bool = True, summarize=False):
+    def sample_bursts(self, num_bursts: int, burst: int, consume, events: bool = True, summarize=False, marks=None):
         """`num_bursts` x `burst` kept draws (`burst * thin` sweeps each) with the burst buffer used as two halves:
         while burst k+1 runs on the device, burst k crosses PCIe into page-locked memory on a copy stream and `consume(trace, k)`
         (e.g. the HDF5 writer) runs on a worker thread -- the sampler only waits when the consumer is
@@ -447,7 +483,11 @@ class ChainSampler:
         summarised on the device right behind its sweeps (snapshot -> reset_trace -> run -> summarize, in stream order) and
         its marginals cross with the trace (`trace.marginals`); with `events=False` the event tensors never leave the
         device.  A burst that is run again after a hand-off time-out is not counted twice: the snapshot taken at its start
-        holds the accumulators."""
+        holds the accumulators.
+
+        `marks` ({burst index: 0 | 1}, with the diagnostics on): `mark(which)` is enqueued right behind the summary of that
+        burst, so the mark holds the accumulators over bursts 0 .. index.  A burst that is run again is marked again: the
+        restored snapshot holds the marks as they were before it."""
         from concurrent.futures import ThreadPoolExecutor
         do_sum, accumulate = self._summarize_mode(summarize)
         burst, num_bursts = int(burst), int(num_bursts)
@@ -483,6 +523,8 @@ class ChainSampler:
                             self.run(burst * self._thin)         # asynchronous; a re-run after _recover passes here again
                             if do_sum:
                                 self.summarize(h * burst, burst, accumulate)
+                            if marks and i in marks:
+                                self.mark(marks[i])
                         if prev >= 0:
                             self.trace_wait()                    # burst prev has landed (it crossed while burst i ran)
                             futs[prev & 1] = pool.submit(consume, self.trace_view(bufs[prev & 1], burst), prev)

@@ -453,6 +453,49 @@ int seir_sampler_read_marginals_async(seir_sampler *s, int32_t first, int32_t co
 int seir_sampler_read_summary(seir_sampler *s, uint64_t *count, int32_t *ref, int64_t *sum, uint64_t *sumsq);
 
 /* ------------------------------------------------------------------------
+ * Convergence diagnostics of the latent epidemic: batch sums and marks.
+ *
+ * Answer, without the event tensors leaving the device, the two questions a run of several chains is asked first: do
+ * the chains agree (split R-hat), and how many independent draws is a chain worth (effective sample size).  Both follow
+ * from integer accumulators kept next to the moments above; the formulas are the host's
+ * (covid19uk_amd/posterior/diagnostics.py).
+ *
+ * Definitions (csrc/summary_update.h), per chain, cell (m, t) and quantity q as above.  The draws x_0 .. x_{n-1} folded
+ * since the reset are cut into batches of L = batch_len draws, batch k being draws [kL, (k+1)L):
+ *     bsum[b][m][t][q]    (int64)   sum of (x_j - ref) over the draws of the batch that is open
+ *     bsumsq              (uint64)  sum over the closed batches of B_k^2, B_k being that batch's bsum when it closed
+ *     nbatch[b]           (uint64)  closed batches, count[b] / L
+ *   The sticky overflow flag of the moments is also raised when a batch closes with |bsum| >= 2^32 or bsumsq reaches
+ *   2^63.  Whether a draw closes a batch depends on its number since the reset alone, (j + 1) % L == 0: as for the
+ *   moments, no result depends on how a burst is cut into calls, launches or buffer halves.
+ *   Marks: two device-side copies, numbered 0 and 1, of (count, sum, sumsq) as they stand when the mark is reached in
+ *   stream order.  A mark carries the accumulators' ref, so the moments of the draws between two marks, or between a mark
+ *   and the end, are exact integer differences -- the halves of split R-hat without a second set of accumulators.
+ *
+ * The feature is switched on by the first seir_sampler_diag_reset; a sampler that never calls it allocates, launches and
+ * copies nothing more than before.  While it is on, seir_sampler_summarize(..., accumulate != 0) launches the instance
+ * of k_summarize that carries the batch sums (16 B more per cell and quantity, read and written once per launch),
+ * seir_sampler_summary_reset zeroes batch sums and marks as well (the batch length stays), and seir_sampler_snapshot /
+ * _restore carry them: a burst that is run again after a hand-off time-out is counted once, and a mark taken in a burst
+ * that is thrown away does not survive it.
+ * ------------------------------------------------------------------------ */
+/* First call allocates; every call sets the batch length and does what seir_sampler_summary_reset does (enabling the
+ * summaries if need be), zeroing batch sums and marks with the moments.  A snapshot does not hold the batch length, so
+ * what the snapshots taken before this call hold of moments, batch sums and marks is dropped: restoring one of them
+ * afterwards restores the chain and leaves the accumulators as they are.  SEIR_ERR_INVALID for batch_len < 1,
+ * SEIR_ERR_STATE if the sampler was created with record_events == 0. */
+int seir_sampler_diag_reset(seir_sampler *s, int32_t batch_len);
+/* Copy (count, sum, sumsq) into mark `which` (0 or 1), device to device, asynchronous on the context stream behind
+ * everything queued so far.  SEIR_ERR_INVALID for another `which`, SEIR_ERR_STATE before a seir_sampler_diag_reset. */
+int seir_sampler_diag_mark(seir_sampler *s, int32_t which);
+/* Blocking read of the batch accumulators: nbatch [B]; bsum, bsumsq each [B][M][T][6].  Any pointer may be NULL.
+ * SEIR_ERR_STATE (and a message) if the overflow flag is up, or before a seir_sampler_diag_reset. */
+int seir_sampler_read_diag(seir_sampler *s, uint64_t *nbatch, int64_t *bsum, uint64_t *bsumsq);
+/* Blocking read of mark `which`: count [B]; sum, sumsq each [B][M][T][6] (all zero for a mark not taken since the
+ * reset).  Any pointer may be NULL.  Refused as seir_sampler_read_diag is. */
+int seir_sampler_read_diag_mark(seir_sampler *s, int32_t which, uint64_t *count, int64_t *sum, uint64_t *sumsq);
+
+/* ------------------------------------------------------------------------
  * Reproduction number R_it.
  *
  * calc_posterior_rit (covid19uk/posterior/reproduction_number.py:13-44): for each
