@@ -67,6 +67,8 @@ ERR_INVALID, ERR_STATE = -1, -3   # SEIR_ERR_INVALID, SEIR_ERR_STATE
 ERR_HANDOFF = -4              # SEIR_ERR_HANDOFF
 MMAX = 4                      # SEIR_MMAX
 MOVE_TRACE = 2 + 4 * MMAX     # SEIR_MOVE_TRACE
+FORECAST_MAX_H = 128          # SEIR_FORECAST_MAX_H
+FORECAST_ID_SHIFT, FORECAST_MAX_CHAIN = 20, 2048   # draw id = (global chain id << 20) + j
 
 
 class SeirError(RuntimeError):
@@ -165,6 +167,16 @@ _SIGNATURES = {
                                               ctypes.POINTER(ctypes.c_uint64)]),
     "seir_sampler_read_diag_mark": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64),
                                                    c_int64_p, ctypes.POINTER(ctypes.c_uint64)]),
+    # forecast of the next H days from the burst buffer: moments and marginals of the simulated counts
+    "seir_sampler_forecast_reset": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_double_p, c_double_p, ctypes.c_uint64]),
+    "seir_sampler_forecast": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, c_double_p]),
+    "seir_sampler_read_forecast_marginals": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                                            c_int64_p, c_int64_p, c_int64_p]),
+    "seir_sampler_read_forecast_marginals_async": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                                                  c_int64_p, c_int64_p, c_int64_p]),
+    "seir_sampler_read_forecast": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
+                                                  ctypes.POINTER(ctypes.c_int32), c_int64_p,
+                                                  ctypes.POINTER(ctypes.c_uint64)]),
 }
 
 _lib = None

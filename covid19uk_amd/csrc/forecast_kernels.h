@@ -1,0 +1,291 @@
+// Posterior predictive of the next H days, formed where the burst buffer lies (include/seir_hip.h, "Forecast on the
+// device"): for every kept draw of a burst the chain-binomial model of sim_kernels.h is run H days forward from the state
+// the draw's recorded events leave at the end of the series, and the simulated counts are folded into moments and
+// per-draw marginals with the definitions of summary_update.h.  No event tensor leaves the device.
+//
+// The parallel axis is the draws of the call, ND = slots x chains of them, nd = slot_in_batch * B + chain; the days are
+// sequential for all of them together.  Every plane has the draw index contiguous (row stride ndp = ceil64(ND)):
+//   k_forecast_prepare<EV16>  once per batch.  A wave per (row, draw) sums the draw's recorded events over T (loads as
+//       summary_load does) and writes the state at day T (St0 for the fold, St the running copy), X = I / N and
+//       eb = exp(beta l_m + sigma s_m) / N_m.  One lane per draw forms a_last = alpha_0 + cumsum(alpha_t)[T-2] by the
+//       sequential sum (NumPy's order: the host can restate it to the bit) and the H baselines a_last + c_s.
+//   k_gemm<64>                per day: F[Mp][ndp] = Cstar . X on v_mfma_f64_16x16x4_f64 -- logprob_kernels.h's tile
+//       code through a Dims / Work that put the draw index in the place of the day index (one "chain", Tp := ndp).  An
+//       output element's sum runs over K ascending whatever its column: F does not depend on where a draw sits.
+//   k_forecast_day            per day: a lane per (row, draw), the draw contiguous over the wave, so F, St, eb and the
+//       draw's scalars are coalesced loads.  Rates through the simulator's functions (sim_eb, sim_p_se, sim_p_ir),
+//       three sim_binomial variates, state update, X of the next day, and the day's counts as int32 into the staging
+//       tensor fev[ND][M][H][3].
+//   k_forecast_fold           once per batch, the shape of k_summarize: a wave per (row, chain), a lane per forecast
+//       day, the draw loop inside, so the accumulators cross memory once per launch; by-day sums through an LDS tile and
+//       one global atomic per entry that is not zero; the state is scanned from the PER-DRAW initial state St0.
+//   k_forecast_finish         state_by_day from the finished by-day sums; advances count[b].
+// Random numbers are k_simulate's protocol: Philox4x32-10, key = forecast seed, counter = (attempt, 64 + transition,
+// s M + m, draw id) with draw id = (global chain id << 20) + j, j the number of that chain's draws forecast since the last
+// reset: nothing depends on how bursts are cut into calls or batches, on the launch geometry or on the sharding of chains.
+// Ordinary launches on the context stream: no hand-off inside a launch, no persistence.
+#pragma once
+
+#include "sim_kernels.h"
+#include "summary_kernels.h"
+
+namespace seir {
+
+constexpr int FC_MAX_H = 128;      // SEIR_FORECAST_MAX_H
+constexpr int FC_JMAX = 128;       // trace slots per batch (the staging tensor and ndp are bounded by it)
+constexpr int FC_ROWS = 8;         // waves (rows) per workgroup of prepare and fold
+constexpr int FC_JB = 16;          // draws per flush of the fold's by-day tile
+constexpr int FC_DAY_ROWS = 4;     // rows per workgroup of k_forecast_day (x 64 draws)
+constexpr int FC_ID_SHIFT = 20;    // draw id = (global chain id << 20) + j
+constexpr int FC_MAX_CHAIN = 2048; // global chain ids below this keep the draw id in 31 bits
+
+struct ForecastBufs {
+    int H;
+    uint32_t k0, k1;
+    const double *W, *wd;          // [H] calendar of the forecast days
+    // planes of a batch, draw index contiguous with row stride ndp
+    int *St0;                      // [3][Mp][ndp] state at day T (the fold's initial state)
+    int *St;                       // [3][Mp][ndp] running state
+    double *X, *F;                 // [Mp][ndp] I / N and Cstar . X
+    double *eb;                    // [Mp][ndp]
+    double *sc;                    // [3][ndp] psi, gamma0, gamma1
+    double *base;                  // [H][ndp] log baseline of forecast day s
+    const double *steps;           // [ND][H] random-walk steps of the batch (or null: the baseline is held)
+    int *fev;                      // [ND][M][H][3] the simulated counts
+    // accumulators and marginals
+    int32_t *ref;                  // [B][M][H][6]
+    int64_t *sum;
+    uint64_t *sumsq;
+    uint64_t *count;               // [B]
+    unsigned *overflow;            // [1]
+    int64_t *fbd;                  // [cap][B][H][3] forecast_by_day
+    int64_t *fbl;                  // [cap][B][M][3] forecast_by_location
+    int64_t *fsbd;                 // [cap][B][H][3] forecast_state_by_day
+};
+
+// grid (Mp / FC_ROWS, ndp), 64 FC_ROWS threads.  Draws [ND, ndp) and rows [M, Mp) get zeros (the contraction reads them).
+template <int EV16>
+__global__ __launch_bounds__(64 * FC_ROWS) void k_forecast_prepare(Dims d, Consts c, ForecastBufs fb,
+                                                                   const double *__restrict__ tr_theta,
+                                                                   const void *__restrict__ tr_events, int B, int first,
+                                                                   int ND, int ndp) {
+    debug_skew(d);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int nd = blockIdx.y, m = blockIdx.x * FC_ROWS + wv;
+    const int M = d.M, T = d.T;
+    const size_t plane = (size_t)d.Mp * ndp, idx = (size_t)m * ndp + nd;
+    if (nd >= ND || m >= M) {
+        if (lane == 0) {
+#pragma unroll
+            for (int x = 0; x < 3; ++x) { fb.St0[x * plane + idx] = 0; fb.St[x * plane + idx] = 0; }
+            fb.X[idx] = 0.0;
+            fb.eb[idx] = 0.0;
+        }
+        return;
+    }
+    const int jj = nd / B, b = nd - jj * B, slot = first + jj;
+    const double *th = tr_theta + ((size_t)slot * B + b) * d.P;
+    const size_t row = (((size_t)slot * B + b) * M + m) * T;
+    int tot[3] = {0, 0, 0};
+    for (int t = lane; t < T; t += 64) {
+        int k[3];
+        summary_load<EV16>(tr_events, row + t, true, k);
+        tot[0] += k[0]; tot[1] += k[1]; tot[2] += k[2];
+    }
+#pragma unroll
+    for (int x = 0; x < 3; ++x)
+        for (int o = 32; o > 0; o >>= 1) tot[x] += __shfl_xor(tot[x], o, 64);
+    if (lane == 0) {
+        const int S = (int)c.init[(size_t)m * 4 + 0] - tot[0];
+        const int E = (int)c.init[(size_t)m * 4 + 1] + tot[0] - tot[1];
+        const int I = (int)c.init[(size_t)m * 4 + 2] + tot[1] - tot[2];
+        fb.St0[idx] = S; fb.St0[plane + idx] = E; fb.St0[2 * plane + idx] = I;
+        fb.St[idx] = S; fb.St[plane + idx] = E; fb.St[2 * plane + idx] = I;
+        fb.X[idx] = (double)I * c.invN[m];
+        fb.eb[idx] = sim_eb(th[2], c.la[m], th[1], th[6 + T - 1 + m], c.invN[m]);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        fb.sc[nd] = th[0]; fb.sc[ndp + nd] = th[3]; fb.sc[2 * ndp + nd] = th[4];
+        // alpha_0 + cumsum(alpha_t)[T-2]: the running sum in index order, then added to alpha_0 (np.cumsum's order)
+        double a_last = th[5];
+        if (T > 1) {
+            double cs = th[6];
+            for (int i = 1; i < T - 1; ++i) cs += th[6 + i];
+            a_last = th[5] + cs;
+        }
+        double walk = 0.0;
+        for (int s = 0; s < fb.H; ++s) {
+            double a = a_last;
+            if (fb.steps) {
+                walk = s == 0 ? fb.steps[(size_t)nd * fb.H] : walk + fb.steps[(size_t)nd * fb.H + s];
+                a = a_last + walk;
+            }
+            fb.base[(size_t)s * ndp + nd] = a;
+        }
+    }
+}
+
+// Forecast day s for every (row, draw): grid (ndp / 64, ceil(M / FC_DAY_ROWS)), 64 FC_DAY_ROWS threads.
+// j0: the chain's draws forecast before this batch (the draw of slot_in_batch jj has j = j0 + jj).
+__global__ __launch_bounds__(64 * FC_DAY_ROWS) void k_forecast_day(Dims d, Consts c, ForecastBufs fb, int B, int chain0,
+                                                                   int j0, int ND, int ndp, int s) {
+    debug_skew(d);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int nd = blockIdx.x * 64 + lane, m = blockIdx.y * FC_DAY_ROWS + wv;
+    if (nd >= ND || m >= d.M) return;
+    const int M = d.M, H = fb.H;
+    const size_t plane = (size_t)d.Mp * ndp, idx = (size_t)m * ndp + nd;
+    const int jj = nd / B, b = nd - jj * B;
+    int S = fb.St[idx], E = fb.St[plane + idx], I = fb.St[2 * plane + idx];
+    const double F = fb.F[idx], eb = fb.eb[idx];
+    const double psi = fb.sc[nd], g0 = fb.sc[ndp + nd], g1 = fb.sc[2 * ndp + nd];
+    const double ea = exp(fb.base[(size_t)s * ndp + nd]);
+    const double psiW = psi * fb.W[s];
+    const double p_ir = sim_p_ir(g0, g1, fb.wd[s], d.dt);
+    const double p_ei = sim_p_ei(d.nu, d.dt);
+    const double p_se = sim_p_se(ea, eb, (double)I, psiW, F, d.rate_floor, d.dt);
+    RngKey key{fb.k0, fb.k1, ((uint32_t)(chain0 + b) << FC_ID_SHIFT) + (uint32_t)(j0 + jj), (uint32_t)(s * M + m)};
+    const int y0 = sim_binomial(S, p_se, key, RS_SIM_BASE + 0);
+    const int y1 = sim_binomial(E, p_ei, key, RS_SIM_BASE + 1);
+    const int y2 = sim_binomial(I, p_ir, key, RS_SIM_BASE + 2);
+    SumEv32 out;
+    out.k[0] = y0; out.k[1] = y1; out.k[2] = y2;
+    reinterpret_cast<SumEv32 *>(fb.fev)[((size_t)nd * M + m) * H + s] = out;
+    S -= y0; E += y0 - y1; I += y1 - y2;
+    fb.St[idx] = S; fb.St[plane + idx] = E; fb.St[2 * plane + idx] = I;
+    fb.X[idx] = (double)I * c.invN[m];
+}
+
+// grid (ceil(M / FC_ROWS), B), 64 FC_ROWS threads.  1 <= count <= FC_JMAX slots starting at trace slot `first`.
+__global__ __launch_bounds__(64 * FC_ROWS) void k_forecast_fold(Dims d, ForecastBufs fb, int B, int first, int count,
+                                                                int ndp) {
+    debug_skew(d);
+    __shared__ unsigned long long bd[FC_JB][64][3];
+    __shared__ int carry[FC_ROWS][FC_JMAX][3];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int b = blockIdx.y, m = blockIdx.x * FC_ROWS + wv;
+    const int M = d.M, H = fb.H;
+    const bool row_ok = m < M;
+    const bool fresh = fb.count[b] == 0;               // count moves in k_forecast_finish, a launch of its own: no race
+    const size_t plane = (size_t)d.Mp * ndp;
+    for (int i = lane; i < count * 3; i += 64) (&carry[wv][0][0])[i] = 0;
+    for (int i = threadIdx.x; i < FC_JB * 64 * 3; i += 64 * FC_ROWS) (&bd[0][0][0])[i] = 0ull;
+    __syncthreads();
+
+    bool ovf = false;
+    for (int h0 = 0; h0 < H; h0 += 64) {
+        const int s = h0 + lane;
+        const bool live = row_ok && s < H;
+        const size_t cell = ((size_t)b * M + (row_ok ? m : 0)) * H + (s < H ? s : 0);
+        int32_t ref[SUMMARY_Q];
+        int64_t sm[SUMMARY_Q];
+        uint64_t sq[SUMMARY_Q];
+#pragma unroll
+        for (int q = 0; q < SUMMARY_Q; ++q) { ref[q] = 0; sm[q] = 0; sq[q] = 0; }
+        if (live && !fresh) {
+#pragma unroll
+            for (int q = 0; q < SUMMARY_Q; ++q) {
+                ref[q] = fb.ref[cell * SUMMARY_Q + q];
+                sm[q] = fb.sum[cell * SUMMARY_Q + q];
+                sq[q] = fb.sumsq[cell * SUMMARY_Q + q];
+            }
+        }
+        for (int jb = 0; jb < count; jb += FC_JB) {
+            const int nj = min(FC_JB, count - jb);
+            for (int jj = 0; jj < nj; ++jj) {
+                const int j = jb + jj, nd = j * B + b;
+                int kk[3];
+                summary_load<0>(fb.fev, ((size_t)nd * M + (row_ok ? m : 0)) * H + (s < H ? s : 0), live, kk);
+                int s0[3] = {0, 0, 0}, ex[3];
+                if (row_ok)
+#pragma unroll
+                    for (int x = 0; x < 3; ++x) s0[x] = fb.St0[x * plane + (size_t)m * ndp + nd];
+#pragma unroll
+                for (int x = 0; x < 3; ++x) {
+                    const int inc = wave_incl_scan(kk[x], lane);
+                    const int cr = carry[wv][j][x];
+                    ex[x] = cr + inc - kk[x];
+                    const int tot = cr + __builtin_amdgcn_readlane(inc, 63);
+                    if (lane == 0) carry[wv][j][x] = tot;
+                }
+                if (live) {
+#pragma unroll
+                    for (int x = 0; x < 3; ++x)
+                        if (kk[x] != 0) atomicAdd(&bd[jj][lane][x], (unsigned long long)kk[x]);
+                    const int val[SUMMARY_Q] = {kk[0], kk[1], kk[2], s0[0] - ex[0], s0[1] + ex[0] - ex[1],
+                                                s0[2] + ex[1] - ex[2]};
+                    const bool is_first = fresh && j == 0;
+#pragma unroll
+                    for (int q = 0; q < SUMMARY_Q; ++q) ovf |= summary_fold(ref[q], sm[q], sq[q], val[q], is_first);
+                }
+            }
+            __syncthreads();
+            // the workgroup's part of forecast_by_day for these draws and days: one atomic per entry that is not zero
+            for (int i = threadIdx.x; i < nj * 64 * 3; i += 64 * FC_ROWS) {
+                const unsigned long long v = (&bd[0][0][0])[i];
+                const int jj = i / 192, r = i - jj * 192, sl = r / 3, x = r - sl * 3;
+                if (v != 0ull) {
+                    (&bd[0][0][0])[i] = 0ull;
+                    atomicAdd(reinterpret_cast<unsigned long long *>(fb.fbd) +
+                                  (((size_t)(first + jb + jj) * B + b) * H + (h0 + sl)) * 3 + x, v);
+                }
+            }
+            __syncthreads();
+        }
+        if (live) {
+#pragma unroll
+            for (int q = 0; q < SUMMARY_Q; ++q) {
+                if (fresh) fb.ref[cell * SUMMARY_Q + q] = ref[q];
+                fb.sum[cell * SUMMARY_Q + q] = sm[q];
+                fb.sumsq[cell * SUMMARY_Q + q] = sq[q];
+            }
+        }
+    }
+    // the carries after the last chunk are the row totals over the horizon
+    if (row_ok)
+        for (int i = lane; i < count * 3; i += 64) {
+            const int j = i / 3, x = i - j * 3;
+            fb.fbl[(((size_t)(first + j) * B + b) * M + m) * 3 + x] = (int64_t)carry[wv][j][x];
+        }
+    if (ovf) fb.overflow[0] = 1u;
+}
+
+// forecast_state_by_day from the finished forecast_by_day and the draw's own initial state; count[b] += count.
+// grid (count, B), one wave.
+__global__ __launch_bounds__(64) void k_forecast_finish(Dims d, ForecastBufs fb, int B, int first, int count, int ndp) {
+    const int lane = threadIdx.x, b = blockIdx.y, j = blockIdx.x, nd = j * B + b;
+    const int H = fb.H;
+    const size_t plane = (size_t)d.Mp * ndp;
+    long long tot0[3] = {0, 0, 0};
+    for (int m = lane; m < d.M; m += 64)
+#pragma unroll
+        for (int x = 0; x < 3; ++x) tot0[x] += (long long)fb.St0[x * plane + (size_t)m * ndp + nd];
+#pragma unroll
+    for (int x = 0; x < 3; ++x)
+        for (int o = 32; o > 0; o >>= 1) tot0[x] += __shfl_xor(tot0[x], o, 64);
+    long long cr[3] = {0, 0, 0};
+    const size_t base = ((size_t)(first + j) * B + b) * H;
+    for (int h0 = 0; h0 < H; h0 += 64) {
+        const int s = h0 + lane;
+        long long ex[3];
+#pragma unroll
+        for (int x = 0; x < 3; ++x) {
+            const long long v = s < H ? fb.fbd[(base + s) * 3 + x] : 0ll;
+            long long inc = v;
+            for (int o = 1; o < 64; o <<= 1) {
+                const long long up = __shfl_up(inc, o, 64);
+                if (lane >= o) inc += up;
+            }
+            ex[x] = cr[x] + inc - v;
+            cr[x] += __shfl(inc, 63, 64);
+        }
+        if (s < H) {
+            fb.fsbd[(base + s) * 3 + 0] = tot0[0] - ex[0];
+            fb.fsbd[(base + s) * 3 + 1] = tot0[1] + ex[0] - ex[1];
+            fb.fsbd[(base + s) * 3 + 2] = tot0[2] + ex[1] - ex[2];
+        }
+    }
+    if (blockIdx.x == 0 && lane == 0) fb.count[b] += (uint64_t)count;
+}
+
+}  // namespace seir

@@ -20,6 +20,7 @@
 #include "rt_kernels.h"
 #include "sweep_plan.h"
 #include "summary_kernels.h"
+#include "forecast_kernels.h"
 
 using namespace seir;
 
@@ -1066,6 +1067,22 @@ struct seir_sampler {
     uint64_t *diag_buf = nullptr;
     void *diag_snap[2] = {nullptr, nullptr};  // shadow copies of all of it for the two snapshot slots
     bool diag_snap_valid[2] = {false, false};
+    // --- forecast of the next H days (seir_sampler_forecast_reset ...; forecast_kernels.h) ---
+    bool fc_on = false;
+    ForecastBufs fc{};
+    int fc_slots = 0;                 // trace slots per batch: min(cap, FC_JMAX)
+    int fc_ndmax = 0;                 // row stride the planes are allocated for: ceil64(fc_slots * B)
+    std::vector<void *> fc_allocs;    // device buffers whose size depends on the horizon (allocated again when it changes)
+    void *fc_acc = nullptr;           // ONE allocation: sum [n] | sumsq [n] | count [B] | ref [n] | flag
+    size_t fc_acc_bytes = 0;
+    long long fc_j = 0;               // draws per chain forecast since the last reset (the j of the draw id)
+    void *fc_snap[2] = {nullptr, nullptr};    // shadow copies of fc_acc for the two snapshot slots ...
+    long long fc_snap_j[2] = {0, 0};          // ... and of fc_j
+    bool fc_snap_valid[2] = {false, false};
+    double *fc_steps_host = nullptr;  // page-locked [cap][B][H]: the caller's random-walk steps on their way to the device
+    double *fc_steps_dev = nullptr;   // [fc_slots * B][H]
+    hipEvent_t fc_ev_steps = nullptr; // behind the last upload from fc_steps_host
+    bool fc_steps_pending = false;
 };
 
 template <typename T>
@@ -1102,6 +1119,11 @@ extern "C" void seir_sampler_destroy(seir_sampler *s) {
     for (void *p : s->snap) if (p) (void)hipFree(p);
     for (void *p : s->sum_snap) if (p) (void)hipFree(p);
     for (void *p : s->diag_snap) if (p) (void)hipFree(p);
+    for (void *p : s->fc_allocs) (void)hipFree(p);
+    for (void *p : s->fc_snap) if (p) (void)hipFree(p);
+    if (s->fc_acc) (void)hipFree(s->fc_acc);
+    if (s->fc_steps_host) (void)hipHostFree(s->fc_steps_host);
+    if (s->fc_ev_steps) (void)hipEventDestroy(s->fc_ev_steps);
     Work &w = s->ctx->w;
     for (int x = 0; x < 3; ++x) { w.K[x] = nullptr; w.St[x] = nullptr; }
     w.rowtot = w.rngtot = nullptr;
@@ -1426,6 +1448,18 @@ static int summary_shadow(seir_sampler *s, int slot, bool save) {
     return 0;
 }
 
+// The forecast accumulators, count, flag and the draw counter travel with a snapshot in the same way.
+static int forecast_shadow(seir_sampler *s, int slot, bool save) {
+    if (!s->fc_on) return 0;
+    if (!save && !s->fc_snap_valid[slot]) return 0;
+    if (!s->fc_snap[slot]) HIP_TRY(hipMalloc(&s->fc_snap[slot], s->fc_acc_bytes));
+    HIP_TRY(hipMemcpyAsync(save ? s->fc_snap[slot] : s->fc_acc, save ? s->fc_acc : s->fc_snap[slot], s->fc_acc_bytes,
+                           hipMemcpyDeviceToDevice, s->ctx->stream));
+    if (save) { s->fc_snap_j[slot] = s->fc_j; s->fc_snap_valid[slot] = true; }
+    else s->fc_j = s->fc_snap_j[slot];
+    return 0;
+}
+
 extern "C" int seir_sampler_snapshot(seir_sampler *s, int32_t slot) {
     int rc = sampler_check(s);
     if (rc) return rc;
@@ -1444,6 +1478,7 @@ extern "C" int seir_sampler_snapshot(seir_sampler *s, int32_t slot) {
             off += (r.bytes + 255) / 256 * 256;
         }
     s->snap_valid[slot] = true;
+    if ((rc = forecast_shadow(s, slot, true))) return rc;
     return summary_shadow(s, slot, true);
 }
 
@@ -1465,6 +1500,7 @@ extern "C" int seir_sampler_restore(seir_sampler *s, int32_t slot) {
         }
     if ((rc = reset_handoffs(s))) return rc;
     if ((rc = summary_shadow(s, slot, false))) return rc;
+    if ((rc = forecast_shadow(s, slot, false))) return rc;
     s->vt_dirty = true;                              // Work::Vt came back with the snapshot, the flag did not
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
@@ -2279,6 +2315,216 @@ extern "C" int seir_sampler_read_diag_mark(seir_sampler *s, int32_t which, uint6
     if (sumsq) HIP_TRY(hipMemcpyAsync(sumsq, mk + B + n, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return diag_read_end(s, flag);
+}
+
+// ---------------------------------------------------------------------------
+// Forecast on the device (include/seir_hip.h; kernels: forecast_kernels.h)
+// ---------------------------------------------------------------------------
+static size_t forecast_cells(const seir_sampler *s, int H) { return (size_t)s->cfg.B * s->ctx->d.M * H * seir::SUMMARY_Q; }
+
+template <typename T>
+static int fc_alloc(seir_sampler *s, T **p, size_t count) {
+    void *q = nullptr;
+    const size_t bytes = (count ? count : 1) * sizeof(T);
+    HIP_TRY(hipMalloc(&q, bytes));
+    s->fc_allocs.push_back(q);
+    HIP_TRY(hipMemset(q, 0, bytes));
+    *p = (T *)q;
+    return 0;
+}
+
+extern "C" int seir_sampler_forecast_reset(seir_sampler *s, int32_t horizon, const double *W, const double *weekday_c,
+                                           uint64_t seed) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if (!s->record_events) return fail(SEIR_ERR_STATE, "sampler was created with record_events=0: there are no recorded events to forecast from");
+    if (horizon < 1 || horizon > SEIR_FORECAST_MAX_H)
+        return fail(SEIR_ERR_INVALID, "horizon=%d outside [1, %d]", horizon, SEIR_FORECAST_MAX_H);
+    if (!W || !weekday_c) return fail(SEIR_ERR_INVALID, "null calendar pointer");
+    const Dims &d = s->ctx->d;
+    const size_t lds = k_simulate_lds_bytes(d);
+    if (lds > 160 * 1024) return fail(SEIR_ERR_INVALID, "M=%d needs %zu B of LDS for the simulator", d.M, lds);
+    const int B = s->cfg.B, H = horizon;
+    if ((long long)s->cfg.chain0 + B > FC_MAX_CHAIN)
+        return fail(SEIR_ERR_INVALID, "global chain id %d: the forecast's draw ids need chain ids below %d", s->cfg.chain0 + B - 1,
+                    FC_MAX_CHAIN);
+    hipStream_t st = s->ctx->stream;
+    ForecastBufs &fb = s->fc;
+    const size_t n = forecast_cells(s, H), cap = (size_t)s->cfg.cap;
+    if (!s->fc_on || fb.H != H) {
+        // first reset, or another horizon: everything is sized by H
+        HIP_TRY(hipStreamSynchronize(st));
+        if (s->copy_pending) { (void)hipEventSynchronize(s->ev_copy); s->copy_pending = false; }
+        for (void *p : s->fc_allocs) (void)hipFree(p);
+        s->fc_allocs.clear();
+        if (s->fc_acc) { (void)hipFree(s->fc_acc); s->fc_acc = nullptr; }
+        if (s->fc_steps_host) { (void)hipHostFree(s->fc_steps_host); s->fc_steps_host = nullptr; }
+        for (int k = 0; k < 2; ++k) {
+            if (s->fc_snap[k]) { (void)hipFree(s->fc_snap[k]); s->fc_snap[k] = nullptr; }
+            s->fc_snap_valid[k] = false;
+        }
+        s->fc_on = false;
+        fb = ForecastBufs{};
+        s->fc_slots = std::min(s->cfg.cap, FC_JMAX);
+        s->fc_ndmax = ceil_to(s->fc_slots * B, 64);
+        const size_t plane = (size_t)d.Mp * s->fc_ndmax, ndm = (size_t)s->fc_slots * B;
+        double *Wd = nullptr, *wdd = nullptr;
+#define F_ALLOC(ptr, n_) if (!rc) rc = fc_alloc(s, &(ptr), (n_))
+        F_ALLOC(Wd, H); F_ALLOC(wdd, H);
+        F_ALLOC(fb.St0, 3 * plane); F_ALLOC(fb.St, 3 * plane); F_ALLOC(fb.X, plane); F_ALLOC(fb.F, plane); F_ALLOC(fb.eb, plane);
+        F_ALLOC(fb.sc, 3 * (size_t)s->fc_ndmax); F_ALLOC(fb.base, (size_t)H * s->fc_ndmax);
+        F_ALLOC(fb.fev, ndm * d.M * H * 3); F_ALLOC(s->fc_steps_dev, ndm * H);
+        F_ALLOC(fb.fbd, cap * B * H * 3); F_ALLOC(fb.fbl, cap * B * d.M * 3); F_ALLOC(fb.fsbd, cap * B * H * 3);
+#undef F_ALLOC
+        if (rc) return rc;
+        fb.W = Wd; fb.wd = wdd;
+        s->fc_acc_bytes = n * (sizeof(int64_t) + sizeof(uint64_t) + sizeof(int32_t)) + (size_t)B * sizeof(uint64_t) + 8;
+        HIP_TRY(hipMalloc(&s->fc_acc, s->fc_acc_bytes));
+        fb.sum = (int64_t *)s->fc_acc;
+        fb.sumsq = (uint64_t *)(fb.sum + n);
+        fb.count = fb.sumsq + n;
+        fb.ref = (int32_t *)(fb.count + B);
+        fb.overflow = (unsigned *)(fb.ref + n);
+        fb.H = H;
+        if (!s->fc_ev_steps) HIP_TRY(hipEventCreate(&s->fc_ev_steps));
+        (void)hipFuncSetAttribute((const void *)k_gemm<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_lds_bytes<64>());
+        s->fc_on = true;
+    }
+    fb.k0 = (uint32_t)(seed & 0xffffffffu); fb.k1 = (uint32_t)(seed >> 32);
+    // the caller's arrays are not retained: blocking copies behind what is queued (a reset is not on the hot path)
+    HIP_TRY(hipMemcpyAsync(const_cast<double *>(fb.W), W, sizeof(double) * H, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(const_cast<double *>(fb.wd), weekday_c, sizeof(double) * H, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(s->fc_acc, 0, s->fc_acc_bytes, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    s->fc_j = 0;
+    // what the snapshots taken before this reset hold of the forecast is dropped with it: restoring one of them restores
+    // the chain and leaves the forecast accumulators and j as they are
+    s->fc_snap_valid[0] = s->fc_snap_valid[1] = false;
+    return 0;
+}
+
+static int forecast_range_check(seir_sampler *s, int32_t first, int32_t count) {
+    if (!s->record_events) return fail(SEIR_ERR_STATE, "sampler was created with record_events=0: there are no recorded events to forecast from");
+    if (!s->fc_on) return fail(SEIR_ERR_STATE, "the forecast is not enabled: call seir_sampler_forecast_reset first");
+    if (first < 0 || count < 0 || (long long)first + count > s->cfg.cap)
+        return fail(SEIR_ERR_INVALID, "trace range [%d,%lld) outside capacity %d", first, (long long)first + count, s->cfg.cap);
+    return 0;
+}
+
+extern "C" int seir_sampler_forecast(seir_sampler *s, int32_t first, int32_t count, const double *log_baseline_steps) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = forecast_range_check(s, first, count))) return rc;
+    if (count == 0) return 0;
+    if (s->fc_j + count > (1ll << FC_ID_SHIFT))
+        return fail(SEIR_ERR_INVALID, "%lld draws per chain forecast since the reset and %d more: the draw id holds 2^%d", s->fc_j,
+                    count, FC_ID_SHIFT);
+    seir_ctx *ctx = s->ctx;
+    const LaunchCfg l = whole(ctx, s->cfg.B);
+    const Dims &d = l.d;
+    const int B = s->cfg.B, H = s->fc.H;
+    if (log_baseline_steps) {
+        // through page-locked memory indexed by trace slot, so that the call stays asynchronous; a slot's steps are
+        // overwritten only once the upload that read them last has been done
+        if (!s->fc_steps_host) HIP_TRY(hipHostMalloc((void **)&s->fc_steps_host, sizeof(double) * s->cfg.cap * B * H, hipHostMallocDefault));
+        if (s->fc_steps_pending) { HIP_TRY(hipEventSynchronize(s->fc_ev_steps)); s->fc_steps_pending = false; }
+        std::memcpy(s->fc_steps_host + (size_t)first * B * H, log_baseline_steps, sizeof(double) * count * B * H);
+    }
+    // forecast_by_day is summed with atomics: zero the call's slots first
+    HIP_TRY(hipMemsetAsync(s->fc.fbd + (size_t)first * B * H * 3, 0, sizeof(int64_t) * count * B * H * 3, l.st));
+    Dims gd = d;                                     // the contraction's view: one "chain", the draw index as the day index
+    gd.b0 = 0;
+    Work gw{};
+    gw.Xn = s->fc.X; gw.F = s->fc.F;
+    for (int j0 = 0; j0 < count; j0 += s->fc_slots) {
+        const int nj = std::min(s->fc_slots, count - j0), ND = nj * B, ndp = ceil_to(ND, 64);
+        ForecastBufs fb = s->fc;
+        fb.steps = nullptr;
+        if (log_baseline_steps) {
+            HIP_TRY(hipMemcpyAsync(s->fc_steps_dev, s->fc_steps_host + (size_t)(first + j0) * B * H, sizeof(double) * ND * H,
+                                   hipMemcpyHostToDevice, l.st));
+            fb.steps = s->fc_steps_dev;
+        }
+        const dim3 pgrid(d.Mp / FC_ROWS, ndp), pblock(64 * FC_ROWS);
+        if (s->cfg.ev16)
+            hipLaunchKernelGGL(k_forecast_prepare<1>, pgrid, pblock, 0, l.st, d, ctx->c, fb, (const double *)s->ch.tr_theta,
+                               (const void *)s->ch.tr_events, B, first + j0, ND, ndp);
+        else
+            hipLaunchKernelGGL(k_forecast_prepare<0>, pgrid, pblock, 0, l.st, d, ctx->c, fb, (const double *)s->ch.tr_theta,
+                               (const void *)s->ch.tr_events, B, first + j0, ND, ndp);
+        gd.Tp = ndp;
+        for (int h = 0; h < H; ++h) {
+            hipLaunchKernelGGL((k_gemm<64>), dim3(ndp / 64, d.Mp / GEMM_TM, 1), dim3(gemm_threads<64>()), gemm_lds_bytes<64>(),
+                               l.st, gd, ctx->c, gw);
+            hipLaunchKernelGGL(k_forecast_day, dim3(ndp / 64, (d.M + FC_DAY_ROWS - 1) / FC_DAY_ROWS), dim3(64 * FC_DAY_ROWS), 0,
+                               l.st, d, ctx->c, fb, B, s->cfg.chain0, (int)(s->fc_j + j0), ND, ndp, h);
+        }
+        hipLaunchKernelGGL(k_forecast_fold, dim3((d.M + FC_ROWS - 1) / FC_ROWS, B), dim3(64 * FC_ROWS), 0, l.st, d, fb, B,
+                           first + j0, nj, ndp);
+        hipLaunchKernelGGL(k_forecast_finish, dim3(nj, B), dim3(64), 0, l.st, d, fb, B, first + j0, nj, ndp);
+    }
+    if (log_baseline_steps) { HIP_TRY(hipEventRecord(s->fc_ev_steps, l.st)); s->fc_steps_pending = true; }
+    HIP_TRY(hipGetLastError());
+    s->fc_j += count;
+    return 0;
+}
+
+static int forecast_copy_marginals(seir_sampler *s, hipStream_t st, int32_t first, int32_t count, int64_t *by_day,
+                                   int64_t *by_location, int64_t *state_by_day) {
+    const Dims &d = s->ctx->d;
+    const size_t B = s->cfg.B, f = (size_t)first, n = (size_t)count, H = (size_t)s->fc.H;
+    if (by_day)
+        HIP_TRY(hipMemcpyAsync(by_day, s->fc.fbd + f * B * H * 3, sizeof(int64_t) * n * B * H * 3, hipMemcpyDeviceToHost, st));
+    if (by_location)
+        HIP_TRY(hipMemcpyAsync(by_location, s->fc.fbl + f * B * d.M * 3, sizeof(int64_t) * n * B * d.M * 3, hipMemcpyDeviceToHost, st));
+    if (state_by_day)
+        HIP_TRY(hipMemcpyAsync(state_by_day, s->fc.fsbd + f * B * H * 3, sizeof(int64_t) * n * B * H * 3, hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+extern "C" int seir_sampler_read_forecast_marginals(seir_sampler *s, int32_t first, int32_t count, int64_t *forecast_by_day,
+                                                    int64_t *forecast_by_location, int64_t *forecast_state_by_day) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = forecast_range_check(s, first, count))) return rc;
+    if ((rc = forecast_copy_marginals(s, s->ctx->stream, first, count, forecast_by_day, forecast_by_location, forecast_state_by_day)))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    return check_ev_overflow(s);
+}
+
+extern "C" int seir_sampler_read_forecast_marginals_async(seir_sampler *s, int32_t first, int32_t count,
+                                                          int64_t *forecast_by_day, int64_t *forecast_by_location,
+                                                          int64_t *forecast_state_by_day) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = forecast_range_check(s, first, count))) return rc;
+    HIP_TRY(hipEventRecord(s->ev_burst, s->ctx->stream));
+    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_burst, 0));
+    if ((rc = forecast_copy_marginals(s, s->copy_stream, first, count, forecast_by_day, forecast_by_location, forecast_state_by_day)))
+        return rc;
+    HIP_TRY(hipEventRecord(s->ev_copy, s->copy_stream));
+    s->copy_pending = true;
+    return 0;
+}
+
+extern "C" int seir_sampler_read_forecast(seir_sampler *s, uint64_t *count, int32_t *ref, int64_t *sum, uint64_t *sumsq) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = forecast_range_check(s, 0, 0))) return rc;
+    hipStream_t st = s->ctx->stream;
+    const size_t n = forecast_cells(s, s->fc.H);
+    unsigned flag = 0;
+    HIP_TRY(hipMemcpyAsync(&flag, s->fc.overflow, sizeof(flag), hipMemcpyDeviceToHost, st));
+    if (count) HIP_TRY(hipMemcpyAsync(count, s->fc.count, sizeof(uint64_t) * s->cfg.B, hipMemcpyDeviceToHost, st));
+    if (ref) HIP_TRY(hipMemcpyAsync(ref, s->fc.ref, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    if (sum) HIP_TRY(hipMemcpyAsync(sum, s->fc.sum, sizeof(int64_t) * n, hipMemcpyDeviceToHost, st));
+    if (sumsq) HIP_TRY(hipMemcpyAsync(sumsq, s->fc.sumsq, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = check_ev_overflow(s))) return rc;
+    if (flag) return fail(SEIR_ERR_STATE, "a sum of squared deviations reached 2^63: the forecast's moment accumulators overflowed "
+                          "(seir_sampler_forecast_reset starts them again)");
+    return 0;
 }
 
 extern "C" int seir_host_alloc(void **p, uint64_t bytes) {

@@ -89,6 +89,23 @@ __device__ __attribute__((noinline)) int sim_binomial(int n, double p, const Rng
     return flip ? n - x : x;
 }
 
+// The per-cell expressions of a simulated day, shared by k_simulate and the forecast kernels (forecast_kernels.h): both
+// evaluate them through this one code, out of line, so that a cell's probabilities do not depend on the kernel around it.
+// exp(beta l_m + sigma s_m) / N_m: constant over the simulated days
+__device__ __attribute__((noinline)) double sim_eb(double beta, double la, double sig, double sp, double invN) {
+    return exp(beta * la + sig * sp) * invN;
+}
+// S->E: lam = ea eb_m (I + psi W_s F) + floor with ea = exp(a_s), p = 1 - exp(-lam dt)
+__device__ __attribute__((noinline)) double sim_p_se(double ea, double eb, double I, double psiW, double F, double rate_floor,
+                                                     double dt) {
+    const double lam = ea * eb * (I + psiW * F) + rate_floor;
+    return -expm1(-lam * dt);
+}
+__device__ __forceinline__ double sim_p_ei(double nu, double dt) { return -expm1(-nu * dt); }
+__device__ __attribute__((noinline)) double sim_p_ir(double g0, double g1, double wd, double dt) {
+    return -expm1(-exp(g0 + g1 * wd) * dt);
+}
+
 // dynamic LDS: x [Mp] fp64 | eb [Mp] fp64 | St [3][Mp] int | stage [SIM_DAYS_STAGED][3][Mp] int
 __host__ __device__ inline size_t k_simulate_lds_bytes(const Dims &d) {
     return sizeof(double) * 2 * d.Mp + sizeof(int) * 3 * d.Mp + sizeof(int) * SIM_DAYS_STAGED * 3 * d.Mp;
@@ -108,12 +125,11 @@ __global__ __launch_bounds__(SIM_THREADS) void k_simulate(Dims d, Consts c, SimA
         St[m] = m < M ? (int)in[0] : 0;
         St[d.Mp + m] = m < M ? (int)in[1] : 0;
         St[2 * d.Mp + m] = m < M ? (int)in[2] : 0;
-        // exp(beta l_m + sigma s_m) / N_m: constant over the simulated days
-        ebs[m] = m < M ? exp(beta * c.la[m] + sig * a.spatial[(size_t)b * M + m]) * c.invN[m] : 0.0;
+        ebs[m] = m < M ? sim_eb(beta, c.la[m], sig, a.spatial[(size_t)b * M + m], c.invN[m]) : 0.0;
     }
     __syncthreads();
     RngKey key{a.k0, a.k1, (uint32_t)(a.first_draw + b), 0u};
-    const double p_ei = -expm1(-d.nu * d.dt);
+    const double p_ei = sim_p_ei(d.nu, d.dt);
     for (int s0 = 0; s0 < S; s0 += SIM_DAYS_STAGED) {
         const int ns = min(SIM_DAYS_STAGED, S - s0);
         for (int ds = 0; ds < ns; ++ds) {
@@ -122,7 +138,7 @@ __global__ __launch_bounds__(SIM_THREADS) void k_simulate(Dims d, Consts c, SimA
             __syncthreads();
             const double ea = exp(a.a_path[(size_t)b * S + s]);
             const double psiW = psi * a.W[s];
-            const double p_ir = -expm1(-exp(g0 + g1 * a.wd[s]) * d.dt);
+            const double p_ir = sim_p_ir(g0, g1, a.wd[s], d.dt);
             for (int m = tid; m < M; m += SIM_THREADS) {
                 // four independent partial sums: a dependent fp64 FMA chain costs ~32 cycles a link
                 double F0 = 0.0, F1 = 0.0, F2 = 0.0, F3 = 0.0;
@@ -139,8 +155,7 @@ __global__ __launch_bounds__(SIM_THREADS) void k_simulate(Dims d, Consts c, SimA
                 }
                 const double F = (F0 + F1) + (F2 + F3);
                 const double I = (double)St[2 * d.Mp + m];
-                const double lam = ea * ebs[m] * (I + psiW * F) + d.rate_floor;
-                const double p_se = -expm1(-lam * d.dt);
+                const double p_se = sim_p_se(ea, ebs[m], I, psiW, F, d.rate_floor, d.dt);
                 key.sweep = (uint32_t)(s * M + m);
                 const int y0 = sim_binomial(St[m], p_se, key, RS_SIM_BASE + 0);
                 const int y1 = sim_binomial(St[d.Mp + m], p_ei, key, RS_SIM_BASE + 1);

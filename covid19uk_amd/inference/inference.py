@@ -106,11 +106,15 @@ class Posterior:
     `is_accepted` is a bool dataset the way h5py stores one (gemlib's Posterior writes numpy bools through h5py):
     the int8 enum {FALSE = 0, TRUE = 1}."""
 
-    def __init__(self, filename, M, T, mmax, num_samples, burst=100, summaries="off"):
+    def __init__(self, filename, M, T, mmax, num_samples, burst=100, summaries="off", forecast=None):
         """`summaries` ("off" | "on" | "only", Mcmc.summaries / --summaries): with "on" and "only" the per-draw marginals
         samples/seir_by_day [n,T,3], samples/seir_by_location [n,M,3], samples/state_by_day [n,T,3] (int64) are written
         with every burst and `write_summary` adds summaries/* at the end of the run; with "only" samples/seir is not
-        created.  "off" creates exactly the datasets of a run without the option."""
+        created.  "off" creates exactly the datasets of a run without the option.
+
+        `forecast` ((H, n) or None, Mcmc.forecast / --forecast): samples/forecast_by_day [n,H,3], forecast_by_location
+        [n,M,3], forecast_state_by_day [n,H,3] (int64), one row per kept draw of the sampling phase -- n of them, not
+        num_samples: the warm-up is not forecast -- and `write_forecast` adds the group forecast/ at the end of the run."""
         self.filename = filename
         self.use_h5 = not str(filename).endswith(".npz") and hdf5io.available()
         self.shapes = {
@@ -133,15 +137,21 @@ class Posterior:
             self.shapes[f"results/{key}/proposed_delta"] = (4, mmax)
             self.dtypes[f"results/{key}/is_accepted"] = np.bool_
         self.num_samples = int(num_samples)
+        self.rows = {}                                     # datasets with another number of rows than num_samples
+        if forecast is not None:
+            H, n_fc = int(forecast[0]), int(forecast[1])
+            for k, shp in (("samples/forecast_by_day", (H, 3)), ("samples/forecast_by_location", (M, 3)),
+                           ("samples/forecast_state_by_day", (H, 3))):
+                self.shapes[k], self.dtypes[k], self.rows[k] = shp, np.int64, n_fc
         self._scratch = {}
         if self.use_h5:
             self._file = hdf5io.File(filename, "w")
             for name, shp in self.shapes.items():
-                self._file.create_dataset("/" + name, (self.num_samples,) + shp, self.dtypes.get(name, np.float64),
+                self._file.create_dataset("/" + name, (self.rows.get(name, self.num_samples),) + shp, self.dtypes.get(name, np.float64),
                                           raw=name == "samples/seir")
         else:
             self._file = None
-            self._mem = {name: np.zeros((self.num_samples,) + shp, self.dtypes.get(name, np.float64))
+            self._mem = {name: np.zeros((self.rows.get(name, self.num_samples),) + shp, self.dtypes.get(name, np.float64))
                          for name, shp in self.shapes.items()}
             self._extra = {}
 
@@ -193,6 +203,18 @@ class Posterior:
         self.create_dataset("summaries/seir_var", np.ascontiguousarray(var[..., :3]))
         self.create_dataset("summaries/state_mean", np.ascontiguousarray(mean[..., 3:]))
         self.create_dataset("summaries/state_var", np.ascontiguousarray(var[..., 3:]))
+
+    def write_forecast(self, horizon, first_day, count, mean, var):
+        """The group forecast/ of one chain: horizon [1], first_day [1] (= T, the absolute day of forecast day 0),
+        count [1] and the moments of the simulated events and of the state at the start of each forecast day over the
+        draws forecast (`Summary.mean` / `.var` rows, [M,H,6]): seir_mean, seir_var, state_mean, state_var, each [M,H,3]."""
+        self.create_dataset("forecast/horizon", np.array([float(horizon)]))
+        self.create_dataset("forecast/first_day", np.array([float(first_day)]))
+        self.create_dataset("forecast/count", np.array([float(count)]))
+        self.create_dataset("forecast/seir_mean", np.ascontiguousarray(mean[..., :3]))
+        self.create_dataset("forecast/seir_var", np.ascontiguousarray(var[..., :3]))
+        self.create_dataset("forecast/state_mean", np.ascontiguousarray(mean[..., 3:]))
+        self.create_dataset("forecast/state_var", np.ascontiguousarray(var[..., 3:]))
 
     def write_diagnostics(self, datasets: dict):
         """The group diagnostics/ of one chain (`posterior.diagnostics.chain_datasets`), float64."""
@@ -312,6 +334,47 @@ def diagnostics_mode(config, override=None, batch=None):
     return mode, L
 
 
+def forecast_mode(config, override=None, walk=None):
+    """Mcmc.forecast (absent: off) and Mcmc.forecast_walk, or the command line's `--forecast H` / `--forecast-walk`:
+    (H, walk) with H = 0 for off.  H is the number of days simulated forward from the end of the series for every kept
+    draw of the sampling phase, 1 <= H <= 128 (SEIR_FORECAST_MAX_H); `walk` lets the log baseline go on as the prior's
+    random walk instead of holding its last value.  The one place that validates -- before a sampler exists."""
+    from .. import _lib
+    H = config.get("forecast") if override is None else override
+    w = config.get("forecast_walk", False) if walk is None else walk
+    if isinstance(w, str):
+        if w.lower() not in ("on", "off", "true", "false"):
+            raise ValueError(f"forecast_walk={w!r}: on or off")
+        w = w.lower() in ("on", "true")
+    w = bool(w)
+    if H is None or H is False or (isinstance(H, str) and H.lower() == "off"):
+        if w:
+            raise ValueError("forecast_walk given without forecast: it would have no effect")
+        return 0, False
+    if isinstance(H, bool) or (not isinstance(H, (int, np.integer)) and not (isinstance(H, str) and H.strip().lstrip("+-").isdigit())):
+        raise ValueError(f"forecast={H!r}: the horizon is a number of days, 1 .. {_lib.FORECAST_MAX_H}")
+    H = int(H)
+    if not 1 <= H <= _lib.FORECAST_MAX_H:
+        raise ValueError(f"forecast={H}: the horizon is 1 .. {_lib.FORECAST_MAX_H} days")
+    return H, w
+
+
+def forecast_steps_fn(seed, chain_ids, horizon):
+    """The random-walk steps of the forecast baseline (`forecast_walk`): for the j-th forecast draw of global chain c,
+    H normals N(0, ALPHA_T_SCALE = 0.005) from np.random.default_rng([seed, c, j]) -- keyed like the device's draw id, so
+    they do not depend on how the run is cut into bursts or sharded.  Returns the callable `ChainSampler.sample(...,
+    forecast=)` takes: (j0, count) -> [count, B, H]."""
+    from ..posterior.predict import ALPHA_T_SCALE
+
+    def steps(j0, count):
+        out = np.empty((int(count), len(chain_ids), int(horizon)))
+        for jj in range(int(count)):
+            for b, c in enumerate(chain_ids):
+                out[jj, b] = np.random.default_rng([int(seed), int(c), int(j0) + jj]).normal(0.0, ALPHA_T_SCALE, int(horizon))
+        return out
+    return steps
+
+
 def diagnostics_marks(nb):
     """{burst index: mark}: mark 0 behind burst nb // 2 - 1 and, with nb odd, mark 1 behind burst nb - nb // 2 - 1, so that
     the middle burst belongs to neither half."""
@@ -321,13 +384,21 @@ def diagnostics_marks(nb):
     return marks
 
 
-def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_step_size=False):
+def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_step_size=False, forecast_calendar=None,
+             seed=0):
     """The windowed schedule of inference.py:303-470: fast 200, slow 25*2^k (k<6), fast 50,
     then num_bursts x num_burst_samples with the kernel fixed.  Every draw of the warm-up is
     written, as in the reference (its running variance is formed from every draw of a window);
     the sampling phase keeps every `thin`-th sweep: num_burst_samples kept draws per burst from
-    num_burst_samples * thin sweeps (inference.py:455), thinned on the device."""
+    num_burst_samples * thin sweeps (inference.py:455), thinned on the device.
+
+    With Mcmc.forecast = H (`forecast_mode`) every kept draw of the sampling phase is forecast H days on the device
+    behind its burst; `forecast_calendar` = (W [H], weekday_c [H]) (`posterior.predict.forecast_calendar`) and `seed`
+    (the forecast's Philox stream and, with forecast_walk, the steps) are then needed.  The warm-up is not forecast."""
     thin = thin_interval(config)
+    horizon, walk = forecast_mode(config)
+    if horizon and forecast_calendar is None:
+        raise ValueError("forecast: run_mcmc needs forecast_calendar = (W, weekday_c) of the forecast days")
     summaries = summaries_mode(config)
     # "off": sample / sample_bursts are called exactly as before the option existed.  Otherwise every written draw gets its
     # marginals (the warm-up without folding), the moments cover the sampling phase, and with "only" no event tensor is read
@@ -344,10 +415,15 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     first_window_size, last_window_size, slow_window_size, num_slow_windows = 200, 50, 25, 6
     dual_averaging_kwargs = {"target_accept_prob": 0.75}
     offset = 0
+    fc_offset = 0
 
     def flush(tr):
-        nonlocal offset
+        nonlocal offset, fc_offset
         n = tr.theta.shape[0]
+        if horizon and tr.forecast is not None:
+            for c, post in enumerate(posteriors):
+                post.write_samples({k: v[:, c] for k, v in tr.forecast.items()}, first_dim_offset=fc_offset)
+            fc_offset += n
         for c, post in enumerate(posteriors):
             post.write_samples(draws_to_dict(tr.theta, tr.events, c, **({} if summaries == "off" else dict(marginals=tr.marginals))),
                                first_dim_offset=offset)
@@ -387,6 +463,11 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
         sampler.reset_diagnostics(batch_len)                # the moments too: all of it is over the sampling phase
     elif summaries != "off":
         sampler.reset_summary()                             # the moments are over the sampling phase
+    if horizon:
+        sampler.reset_forecast(horizon, forecast_calendar[0], forecast_calendar[1], seed)   # once: the sampling phase
+        first_id = getattr(sampler, "first_chain_id", 0)
+        burst_kw = dict(burst_kw, forecast=forecast_steps_fn(seed, [first_id + c for c in range(sampler.B)], horizon)
+                        if walk else True)
     if summaries == "only":
         print("summaries only: the event tensors stay on the device and samples/seir is not created -- what reads it "
               "(thin_posterior, predict, reproduction_number) cannot run on this output", file=log, flush=True)
@@ -430,6 +511,14 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
         mean, var = sm.mean, sm.var
         for c, post in enumerate(posteriors):
             post.write_summary(sm.count[c], mean[c], var[c])
+    if horizon:
+        fs = sampler.forecast_summary()
+        mean, var = fs.mean, fs.var
+        for c, post in enumerate(posteriors):
+            post.write_forecast(horizon, sampler.T, fs.count[c], mean[c], var[c])
+        print(f"Forecast: {horizon} day(s) from day {sampler.T} for {int(fs.count.min()) if len(fs.count) else 0} kept draw(s) per "
+              f"chain, formed on the device ({'random-walk' if walk else 'held'} baseline); forecast/* and "
+              "samples/forecast_* written", file=log, flush=True)
     return offset
 
 
@@ -494,7 +583,8 @@ def launch_forms(lay, device_arg, hmc="auto", moves="auto", env=os.environ):
 
 
 def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool_step_size=False, init_jitter=0.0,
-         events_dtype="auto", hmc="auto", moves="auto", thin=None, summaries=None, diagnostics=None, diagnostics_batch=None):
+         events_dtype="auto", hmc="auto", moves="auto", thin=None, summaries=None, diagnostics=None, diagnostics_batch=None,
+         forecast=None, forecast_walk=None):
     """Constructs and runs the MCMC (covid19uk/inference/inference.py:473-608).
 
     Multi-GPU: launched as one process per GPU, every rank runs `num_chains` chains with
@@ -503,7 +593,14 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     data-path collective.  `pool_step_size` adds the one optional exchange: an all_gather of one float64
     per chain after warm-up.  `thin` overrides config["thin"] (every rank is given the same value), `summaries`
     config["summaries"] (`summaries_mode`), `diagnostics` / `diagnostics_batch` config["diagnostics"] /
-    config["diagnostics_batch"] (`diagnostics_mode`)."""
+    config["diagnostics_batch"] (`diagnostics_mode`), `forecast` / `forecast_walk` config["forecast"] /
+    config["forecast_walk"] (`forecast_mode`)."""
+    horizon = 0
+    if forecast is not None or forecast_walk is not None or "forecast" in config or "forecast_walk" in config:
+        horizon, walk = forecast_mode(config, forecast, forecast_walk)    # refused here: before any GPU call
+        config = {k: v for k, v in config.items() if k not in ("forecast", "forecast_walk")}
+        if horizon:
+            config = dict(config, forecast=horizon, forecast_walk=walk)
     config = dict(config, thin=thin_interval(config, thin))  # refused here if < 1: before any GPU call
     config = dict(config, summaries=summaries_mode(config, summaries))    # an unknown value likewise
     if diagnostics is not None or diagnostics_batch is not None or "diagnostics" in config or "diagnostics_batch" in config:
@@ -547,9 +644,14 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     total = lay["world"] * B
     names = [chain_file_name(output_file, lay["first_chain_id"] + c, total) for c in range(B)]
     posteriors = [Posterior(name, M, T, cfg["m"], num_samples, burst=int(config["num_burst_samples"]),
-                            **({} if config["summaries"] == "off" else dict(summaries=config["summaries"])))
+                            **({} if config["summaries"] == "off" else dict(summaries=config["summaries"])),
+                            **(dict(forecast=(horizon, int(config["num_burst_samples"]) * int(config["num_bursts"]))) if horizon else {}))
                   for name in names]
-    run_mcmc(sampler, config, posteriors, pool_step_size=pool_step_size and total > 1)
+    fc_kw = {}
+    if horizon:
+        from ..posterior.predict import forecast_calendar
+        fc_kw = dict(forecast_calendar=forecast_calendar(cov, dates, T, horizon), seed=seed)
+    run_mcmc(sampler, config, posteriors, pool_step_size=pool_step_size and total > 1, **fc_kw)
     if sampler.recoveries:
         print(f"{len(sampler.recoveries)} burst(s) were run again after a hand-off time-out (shared GPU?)", flush=True)
     for post in posteriors:
@@ -612,6 +714,15 @@ def main(argv=None):
     parser.add_argument("--diagnostics-batch", type=int, default=None, metavar="L",
                         help="batch length of the batch-means ESS in kept draws (overrides Mcmc.diagnostics_batch; default "
                              "num_burst_samples, which it must divide or be a multiple of)")
+    parser.add_argument("--forecast", type=int, default=None, metavar="H",
+                        help="simulate H days (1..128) forward from the end of the series for every kept draw of the "
+                             "sampling phase, on the device (overrides Mcmc.forecast; default off): a group forecast/ with "
+                             "the mean and variance of events and state per location and forecast day, and per-draw "
+                             "samples/forecast_by_day, forecast_by_location, forecast_state_by_day; works with "
+                             "--summaries only")
+    parser.add_argument("--forecast-walk", action="store_true", default=None,
+                        help="let the forecast's log baseline continue as the prior's random walk (N(0, 0.005) steps) "
+                             "instead of holding its last value (overrides Mcmc.forecast_walk; needs --forecast)")
     args = parser.parse_args(argv)
     if args.thin is not None and args.thin < 1:
         parser.error(f"--thin {args.thin}: the thinning interval is >= 1")
@@ -620,7 +731,7 @@ def main(argv=None):
     mcmc(args.data_file, args.output, config["Mcmc"], seed=args.seed, num_chains=args.chains, device=args.device,
          pool_step_size=args.pool_step_size, init_jitter=args.init_jitter, events_dtype=args.events_dtype,
          hmc=args.hmc, moves=args.moves, thin=args.thin, summaries=args.summaries, diagnostics=args.diagnostics,
-         diagnostics_batch=args.diagnostics_batch)
+         diagnostics_batch=args.diagnostics_batch, forecast=args.forecast, forecast_walk=args.forecast_walk)
 
 
 if __name__ == "__main__":

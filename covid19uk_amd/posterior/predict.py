@@ -41,6 +41,21 @@ def clipped(values, initial_step, num_steps):
     return values[np.clip(initial_step + np.arange(num_steps), 0, values.shape[0] - 1)]
 
 
+def prediction_calendar(W, weekday, initial_step, num_steps):
+    """(W, centred weekday) of the days initial_step .. initial_step + num_steps - 1 by the model's clipped indexing:
+    `weekday` covers the whole prediction range and is centred over it (model_spec.py:224-225, 239-241)."""
+    weekday = np.asarray(weekday, dtype=np.float64).reshape(-1)
+    return clipped(W, initial_step, num_steps), clipped(weekday - weekday.mean(), initial_step, num_steps)
+
+
+def forecast_calendar(covar_data: model_spec.Covariates, dates, T, horizon):
+    """(W [H], weekday_c [H]) of the H days after the T observed ones, formed as `predict` forms them for
+    initial_step = T, num_steps = H: `prediction_weekday` over T + H days (the covariate's weekday without calendar
+    dates), centred over that range, and the clipped W.  What `run_mcmc` hands to `ChainSampler.reset_forecast`."""
+    weekday, _ = prediction_weekday(dates, int(T) + int(horizon), covar_data.weekday)
+    return prediction_calendar(covar_data.W, weekday, int(T), int(horizon))
+
+
 def predicted_incidence(posterior_samples, init_state, covar_data: model_spec.Covariates, init_step, num_steps,
                         out_of_sample=False, seed=0, device=0):
     """Simulate forward from the posterior state at `init_step` for `num_steps` days.
@@ -61,9 +76,7 @@ def predicted_incidence(posterior_samples, init_state, covar_data: model_spec.Co
         rng = np.random.default_rng(seed)
         alpha_t = rng.normal(0.0, ALPHA_T_SCALE, size=(n, max(num_steps - 1, 0)))
     a_path = log_baseline_path(alpha_0, alpha_t, init_step, num_steps)
-    weekday = np.asarray(covar_data.weekday, dtype=np.float64).reshape(-1)
-    wd = clipped(weekday - weekday.mean(), init_step, num_steps)         # model_spec.py:224-225,239-241
-    W = clipped(covar_data.W, init_step, num_steps)
+    W, wd = prediction_calendar(covar_data.W, covar_data.weekday, init_step, num_steps)
     par = np.stack([np.asarray(samples[k], dtype=np.float64).reshape(n)
                     for k in ("psi", "sigma_space", "beta_area", "gamma0", "gamma1")], axis=1)
     spatial = np.asarray(samples["spatial_effect"], dtype=np.float64).reshape(n, -1)

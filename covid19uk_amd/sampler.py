@@ -38,9 +38,11 @@ class Trace:
     hmc: dict                # is_accepted, target_log_prob, step_size  -> [n,B]
     moves: dict              # MOVE_KEYS -> dict(is_accepted [n,B], target_log_prob [n,B], proposed_delta [n,B,4,m])
     marginals: dict = None   # MARGINAL_KEYS -> int64 [n,B,T,3] / [n,B,M,3] / [n,B,T,3]; None unless asked for
+    forecast: dict = None    # FORECAST_KEYS -> int64 [n,B,H,3] / [n,B,M,3] / [n,B,H,3]; None unless the draws were forecast
 
 
 MARGINAL_KEYS = ("events_by_day", "events_by_location", "state_by_day")
+FORECAST_KEYS = ("forecast_by_day", "forecast_by_location", "forecast_state_by_day")
 SUMMARY_QUANTITIES = ("k_se", "k_ei", "k_ir", "S", "E", "I")
 
 
@@ -63,6 +65,17 @@ class Summary:
     def var(self) -> np.ndarray:
         """Unbiased variance (sumsq - sum^2 / n) / (n - 1), float64 [B,M,T,6]; NaN where n < 2."""
         return summary_var(self.count, self.sum, self.sumsq)
+
+
+def forecast_draw_id(global_chain_id: int, j: int) -> int:
+    """The Philox draw id of the forecast of a chain's j-th draw since the last `reset_forecast`
+    (include/seir_hip.h, "Forecast on the device"): (global chain id << 20) + j, with both limits."""
+    c, j = int(global_chain_id), int(j)
+    if not 0 <= c < _lib.FORECAST_MAX_CHAIN:
+        raise ValueError(f"global chain id {c}: the forecast's draw ids need chain ids in [0, {_lib.FORECAST_MAX_CHAIN})")
+    if not 0 <= j < (1 << _lib.FORECAST_ID_SHIFT):
+        raise ValueError(f"draw number {j}: fewer than 2^{_lib.FORECAST_ID_SHIFT} draws per chain between two forecast resets")
+    return (c << _lib.FORECAST_ID_SHIFT) + j
 
 
 def _per_chain(count, like):
@@ -90,7 +103,8 @@ class PinnedTrace:
     """Page-locked host arrays for `count` sweeps of the burst buffer (seir_host_alloc): the target of
     `ChainSampler.read_trace_async`.  Views are valid until close()."""
 
-    def __init__(self, sampler: "ChainSampler", count: int, events: bool = True, marginals: bool = False):
+    def __init__(self, sampler: "ChainSampler", count: int, events: bool = True, marginals: bool = False,
+                 forecast: int = 0):
         self._lib = sampler._lib
         self.count = int(count)
         B, P, M, T = sampler.B, sampler.P, sampler.M, sampler.T
@@ -104,6 +118,12 @@ class PinnedTrace:
             self.marginals = dict(events_by_day=self._alloc((count, B, T, 3), np.int64),
                                   events_by_location=self._alloc((count, B, M, 3), np.int64),
                                   state_by_day=self._alloc((count, B, T, 3), np.int64))
+        self.forecast = None
+        if forecast:
+            H = int(forecast)
+            self.forecast = dict(forecast_by_day=self._alloc((count, B, H, 3), np.int64),
+                                 forecast_by_location=self._alloc((count, B, M, 3), np.int64),
+                                 forecast_state_by_day=self._alloc((count, B, H, 3), np.int64))
 
     def _alloc(self, shape, dtype):
         nbytes = int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize
@@ -114,7 +134,7 @@ class PinnedTrace:
         return np.frombuffer(buf, dtype=dtype, count=int(np.prod(shape, dtype=np.int64))).reshape(shape)
 
     def close(self):
-        self.theta = self.events = self.hmc = self.moves = self.marginals = None
+        self.theta = self.events = self.hmc = self.moves = self.marginals = self.forecast = None
         for p in self._ptrs:
             self._lib.seir_host_free(p)
         self._ptrs = []
@@ -131,6 +151,9 @@ class ChainSampler:
     _thin = 1
     _summary_on = False           # reset_summary has been called: the device holds accumulators and marginal arrays
     _diag_L = 0                   # batch length of the diagnostics in force (0: reset_diagnostics was never called)
+    _forecast_H = 0               # horizon of the forecast in force (0: reset_forecast was never called)
+    _fc_j = 0                     # draws per chain forecast since the last reset_forecast (the library's counter, mirrored)
+    first_chain_id = 0
 
     def __init__(self, model: SeirModel, config: dict, num_chains: int, seed: int = 0,
                  t_range=None, num_leapfrog_steps: int = 16, trace_capacity: int = 100,
@@ -190,6 +213,8 @@ class ChainSampler:
         self._s = ctypes.c_void_p()
         _lib.check(self._lib.seir_sampler_create(model._ctx, ctypes.byref(desc), ctypes.byref(self._s)))
         self._thin = int(thin)
+        self.first_chain_id = int(first_chain_id)
+        self._fc_j_snap = {}
         self.auto_recover = bool(auto_recover) and debug_pair == 0
         self.preferred_form = (hmc, moves)
         self.recoveries = []              # one dict per recovery: burst form that failed, form it was re-run in, message
@@ -246,10 +271,14 @@ class ChainSampler:
         """Copy the chain state (everything the next sweep's draws are a function of; not the trace) to shadow slot 0 / 1,
         in stream order."""
         _lib.check(self._lib.seir_sampler_snapshot(self._s, int(slot)))
+        if self._forecast_H:
+            self._fc_j_snap[int(slot)] = self._fc_j
 
     def restore(self, slot: int = 0):
         """Back to the snapshot in `slot`; clears a hand-off time-out."""
         _lib.check(self._lib.seir_sampler_restore(self._s, int(slot)))
+        if self._forecast_H and int(slot) in self._fc_j_snap:
+            self._fc_j = self._fc_j_snap[int(slot)]
 
     def set_launch_form(self, hmc: str, moves: str):
         _lib.check(self._lib.seir_sampler_set_launch_form(self._s, HMC_MODES[hmc], MOVES_MODES[moves]))
@@ -385,6 +414,8 @@ class ChainSampler:
                             buf.moves[:n])
         if buf.marginals is not None:
             tr.marginals = {k: v[:n] for k, v in buf.marginals.items()}
+        if buf.forecast is not None:
+            tr.forecast = {k: v[:n] for k, v in buf.forecast.items()}
         return tr
 
     # -- summaries of the recorded events on the device (include/seir_hip.h) --------------------------
@@ -464,6 +495,70 @@ class ChainSampler:
         return Diagnostics(batch_length=self._diag_L, count=sm.count, ref=sm.ref, sum=sm.sum, sumsq=sm.sumsq, bsum=bsum,
                            bsumsq=bsumsq, nbatch=nbatch, mark_count=mc, mark_sum=ms, mark_sumsq=mq)
 
+    # -- forecast of the next H days from the burst buffer (include/seir_hip.h, "Forecast on the device") ----------
+    def reset_forecast(self, horizon: int, W, weekday_c, seed: int = 0):
+        """Enable the forecast (first call), zero its moments, count and flag, set the horizon, the calendar of the H
+        forecast days (`W`, `weekday_c`: [H], `posterior.predict.forecast_calendar`) and the seed of its Philox stream, and
+        start the draw counter j at 0."""
+        H = int(horizon)
+        if not 1 <= H <= _lib.FORECAST_MAX_H:
+            raise ValueError(f"forecast horizon {H}: 1 <= H <= {_lib.FORECAST_MAX_H}")
+        W = np.ascontiguousarray(W, dtype=np.float64).reshape(-1)
+        wd = np.ascontiguousarray(weekday_c, dtype=np.float64).reshape(-1)
+        if W.shape != (H,) or wd.shape != (H,):
+            raise ValueError(f"need W [{H}] and weekday_c [{H}]")
+        _lib.check(self._lib.seir_sampler_forecast_reset(self._s, H, _dptr(W), _dptr(wd), int(seed) & (2 ** 64 - 1)))
+        self._forecast_H, self._fc_j, self._fc_j_snap = H, 0, {}
+
+    def forecast(self, first: int, count: int, steps=None):
+        """Enqueue the forecast of trace slots [first, first+count) behind the sweeps that fill them and fold it.  `steps`
+        [count,B,H] (optional): random-walk steps of the log baseline; None holds the baseline at its last value."""
+        n = int(count)
+        if steps is not None:
+            steps = np.ascontiguousarray(steps, dtype=np.float64)
+            if steps.shape != (n, self.B, self._forecast_H):
+                raise ValueError(f"need steps [{n},{self.B},{self._forecast_H}]")
+        _lib.check(self._lib.seir_sampler_forecast(self._s, int(first), n, None if steps is None else _dptr(steps)))
+        self._fc_j += n
+
+    def _fc_ptrs(self, m):
+        return [m[k].ctypes.data_as(_lib.c_int64_p) for k in FORECAST_KEYS]
+
+    def read_forecast_marginals(self, count: int, first: int = 0) -> dict:
+        """Blocking read of the forecast marginals of trace slots [first, first+count): FORECAST_KEYS -> int64 arrays with
+        leading axes [count, B]."""
+        n, H = int(count), self._forecast_H
+        m = dict(forecast_by_day=np.empty((n, self.B, H, 3), np.int64),
+                 forecast_by_location=np.empty((n, self.B, self.M, 3), np.int64),
+                 forecast_state_by_day=np.empty((n, self.B, H, 3), np.int64))
+        _lib.check(self._lib.seir_sampler_read_forecast_marginals(self._s, int(first), n, *self._fc_ptrs(m)))
+        return m
+
+    def read_forecast_marginals_async(self, count: int, first: int, into: PinnedTrace):
+        """As `read_marginals_async`, for the forecast marginals; completed by `trace_wait()`."""
+        if int(count) > into.count or into.forecast is None:
+            raise ValueError("pinned buffer too small or without forecast arrays")
+        _lib.check(self._lib.seir_sampler_read_forecast_marginals_async(self._s, int(first), int(count),
+                                                                        *self._fc_ptrs(into.forecast)))
+
+    def forecast_summary(self) -> Summary:
+        """The forecast moments folded since the last `reset_forecast` (blocking): a `Summary` whose day axis is the H
+        forecast days, [B,M,H,6].  Raises `SeirError` (SEIR_ERR_STATE) if an accumulator overflowed or before a reset."""
+        shape = (self.B, self.M, self._forecast_H, len(SUMMARY_QUANTITIES))
+        cnt = np.zeros(self.B, np.uint64)
+        ref, sm, sq = np.empty(shape, np.int32), np.empty(shape, np.int64), np.empty(shape, np.uint64)
+        _lib.check(self._lib.seir_sampler_read_forecast(
+            self._s, cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ref.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+            sm.ctypes.data_as(_lib.c_int64_p), sq.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        return Summary(count=cnt, ref=ref, sum=sm, sumsq=sq)
+
+    def _forecast_burst(self, first, count, forecast):
+        """`forecast` of sample / sample_bursts: True (held baseline) or a callable (j0, count) -> steps [count,B,H], j0
+        being the number of draws per chain forecast since the reset -- after a re-run of a burst it is the same again."""
+        if not self._forecast_H:
+            raise ValueError("forecast asked for before reset_forecast")
+        self.forecast(first, count, forecast(self._fc_j, count) if callable(forecast) else None)
+
     def _summarize_mode(self, summarize):
         """`summarize` of sample / sample_bursts: False, True (marginals + moments) or "marginals" (accumulate = 0)."""
         if summarize not in (False, True, "marginals"):
@@ -472,7 +567,8 @@ class ChainSampler:
             self.reset_summary()
         return bool(summarize), summarize is True
 
-    def sample_bursts(self, num_bursts: int, burst: int, consume, events: bool = True, summarize=False, marks=None):
+    def sample_bursts(self, num_bursts: int, burst: int, consume, events: bool = True, summarize=False, marks=None,
+                      forecast=False):
         """`num_bursts` x `burst` kept draws (`burst * thin` sweeps each) with the burst buffer used as two halves:
         while burst k+1 runs on the device, burst k crosses PCIe into page-locked memory on a copy stream and `consume(trace, k)`
         (e.g. the HDF5 writer) runs on a worker thread -- the sampler only waits when the consumer is
@@ -487,18 +583,25 @@ class ChainSampler:
 
         `marks` ({burst index: 0 | 1}, with the diagnostics on): `mark(which)` is enqueued right behind the summary of that
         burst, so the mark holds the accumulators over bursts 0 .. index.  A burst that is run again is marked again: the
-        restored snapshot holds the marks as they were before it."""
+        restored snapshot holds the marks as they were before it.
+
+        `forecast` (True, or a callable giving random-walk steps, see `_forecast_burst`; needs `reset_forecast`): every
+        burst's draws are forecast on the device right behind its summary and the forecast marginals cross with the trace
+        (`trace.forecast`)."""
         from concurrent.futures import ThreadPoolExecutor
         do_sum, accumulate = self._summarize_mode(summarize)
         burst, num_bursts = int(burst), int(num_bursts)
         if 2 * burst > self.cap:
             raise ValueError(f"sample_bursts needs trace_capacity >= 2 * burst = {2 * burst}, have {self.cap}")
         # page-locking GBs of host memory takes tenths of a second: the two buffers are kept for the next call
-        key = (burst, bool(events), do_sum)
+        do_fc = bool(forecast)
+        key = (burst, bool(events), do_sum, self._forecast_H if do_fc else 0)
         if getattr(self, "_pinned_key", None) != key:
             for bf in getattr(self, "_pinned", []):
                 bf.close()
             mk = dict(marginals=True) if do_sum else {}
+            if do_fc:
+                mk["forecast"] = self._forecast_H
             self._pinned = [PinnedTrace(self, burst, events, **mk), PinnedTrace(self, burst, events, **mk)]
             self._pinned_key = key
         bufs = self._pinned
@@ -525,6 +628,8 @@ class ChainSampler:
                                 self.summarize(h * burst, burst, accumulate)
                             if marks and i in marks:
                                 self.mark(marks[i])
+                            if do_fc:
+                                self._forecast_burst(h * burst, burst, forecast)
                         if prev >= 0:
                             self.trace_wait()                    # burst prev has landed (it crossed while burst i ran)
                             futs[prev & 1] = pool.submit(consume, self.trace_view(bufs[prev & 1], burst), prev)
@@ -534,6 +639,8 @@ class ChainSampler:
                             self.read_trace_async(burst, h * burst, bufs[h])
                             if do_sum:
                                 self.read_marginals_async(burst, h * burst, bufs[h])
+                            if do_fc:
+                                self.read_forecast_marginals_async(burst, h * burst, bufs[h])
                             prev = i
                             i += 1
                     except _lib.HandoffTimeout as e:
@@ -554,10 +661,10 @@ class ChainSampler:
             except _lib.HandoffTimeout:
                 pass
 
-    def sample(self, num_sweeps: int, events: bool = True, summarize=False) -> Trace:
+    def sample(self, num_sweeps: int, events: bool = True, summarize=False, forecast=False) -> Trace:
         """reset_trace + run + read: the analogue of one `sample_chain` call with `num_sweeps` results, each the last of
         `thin` sweeps.  `summarize` as in `sample_bursts`: the burst is summarised on the device and `trace.marginals`
-        filled."""
+        filled; `forecast` likewise (`trace.forecast`)."""
         do_sum, accumulate = self._summarize_mode(summarize)
         if num_sweeps > self.cap:
             raise ValueError(f"num_sweeps={num_sweeps} exceeds trace_capacity={self.cap}")
@@ -569,9 +676,13 @@ class ChainSampler:
             try:
                 if do_sum:
                     self.summarize(0, num_sweeps, accumulate)
+                if forecast:
+                    self._forecast_burst(0, num_sweeps, forecast)
                 tr = self.read_trace(num_sweeps, events=events)
                 if do_sum:
                     tr.marginals = self.read_marginals(num_sweeps)
+                if forecast:
+                    tr.forecast = self.read_forecast_marginals(num_sweeps)
             except _lib.HandoffTimeout as e:
                 if not self.auto_recover:
                     raise

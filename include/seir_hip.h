@@ -496,6 +496,67 @@ int seir_sampler_read_diag(seir_sampler *s, uint64_t *nbatch, int64_t *bsum, uin
 int seir_sampler_read_diag_mark(seir_sampler *s, int32_t which, uint64_t *count, int64_t *sum, uint64_t *sumsq);
 
 /* ------------------------------------------------------------------------
+ * Forecast on the device: posterior predictive of the next H days.
+ *
+ * Stands in for covid19uk/posterior/predict.py run on every kept draw: for each draw of trace slots
+ * [first_slot, first_slot + count) the chain-binomial model of seir_simulate (below) is simulated `horizon` days forward
+ * and the simulated counts are folded into moments and per-draw marginals, the way the summaries above fold the
+ * recorded ones.  Neither the recorded nor the simulated event tensor crosses PCIe.
+ *
+ * Semantics (the one definition; kernels: csrc/forecast_kernels.h).
+ *   Start.  Forecast day s = 0 is absolute day T, the day after the last recorded day.  The initial state of a draw is
+ *     S0 + stoichiometry . sum_t events of that draw, integers formed on the device from the trace slot.  (The host path
+ *     `posterior.predict` cannot start there: compute_state ends at the START of day T - 1.)
+ *   Time indexing for t >= T is the reference's clip (model_spec.py:234-256).  The log baseline of every forecast day is
+ *     a_last = alpha_0 + cumsum(alpha_t)[T-2] (alpha_0 when T = 1), the cumulative sum taken sequentially in index order in
+ *     fp64 and then added to alpha_0, which is what np.cumsum does.  W[s] and the centred weekday weekday_c[s] of the H
+ *     days are host arrays handed over at the reset (covid19uk_amd.posterior.predict.forecast_calendar).
+ *   Optional random walk.  With log_baseline_steps [count][B][H] the baseline of forecast day s is a_last + c_s, c the
+ *     sequential running sum of that draw's steps from zero (c_0 = step_0).  NULL holds the baseline.
+ *   Random stream: seir_simulate's protocol unchanged -- Philox4x32-10, key = the forecast seed, counter = (attempt,
+ *     64 + transition, s M + m, draw id) -- with draw id = (global chain id << 20) + j, j being the number of that chain's
+ *     draws forecast since the last reset.  A forecast therefore does not depend on how bursts are cut into calls, on the
+ *     launch geometry or on how chains are sharded over samplers, and one seir_simulate call per chain reproduces it
+ *     (first_draw_id = chain << 20, num_draws = n).
+ *   Rates, binomial sampler, rate floor, nu, dt: seir_simulate's, through the same device functions.
+ *   Quantities and accumulators: those of the summaries (csrc/summary_update.h) with forecast day s in the place of t and
+ *     the draw's own initial state in the place of the context's: k_se, k_ei, k_ir and S, E, I at the start of forecast
+ *     day s; ref / sum / sumsq [B][M][H][6], count [B], and the sticky overflow flag.
+ *   Marginals per kept draw, int64, indexed by trace slot:
+ *     forecast_by_day       [count][B][H][3]  sum_m k
+ *     forecast_by_location  [count][B][M][3]  sum_s k over the horizon
+ *     forecast_state_by_day [count][B][H][3]  sum_m (S, E, I)
+ * Limits: 1 <= horizon <= SEIR_FORECAST_MAX_H; M <= 1280 (the simulator's); global chain ids below 2048; fewer than 2^20
+ * draws per chain between two resets; record_events != 0.
+ *
+ * Switched on by the first seir_sampler_forecast_reset; a sampler that never calls it allocates and launches nothing
+ * more than before.  While it is on, seir_sampler_snapshot / _restore carry the forecast accumulators, count, flag and
+ * the draw counter j, so that a burst run again after a hand-off time-out is forecast and counted once.  A snapshot taken
+ * before the last reset holds none of it; restoring it leaves them as they are.
+ * ------------------------------------------------------------------------ */
+#define SEIR_FORECAST_MAX_H 128
+/* First call (and a call with another horizon) allocates; every call zeroes count, moments and flag in stream order,
+ * sets horizon, calendar (W, weekday_c: [horizon], copied) and seed and starts j at 0 again.  SEIR_ERR_INVALID for a
+ * horizon outside [1, SEIR_FORECAST_MAX_H], M > 1280 or a global chain id >= 2048; SEIR_ERR_STATE with
+ * record_events == 0. */
+int seir_sampler_forecast_reset(seir_sampler *s, int32_t horizon, const double *W, const double *weekday_c, uint64_t seed);
+/* Forecast the draws of trace slots [first_slot, first_slot + count) of every chain and fold them: asynchronous on the
+ * context stream, behind the sweeps that fill those slots.  log_baseline_steps: host [count][B][H] or NULL (copied
+ * before the call returns).  SEIR_ERR_INVALID for slots outside the burst buffer or when j would reach 2^20,
+ * SEIR_ERR_STATE before a reset. */
+int seir_sampler_forecast(seir_sampler *s, int32_t first_slot, int32_t count, const double *log_baseline_steps);
+/* Blocking read of the forecast marginals of slots [first, first + count); any pointer may be NULL.  Host pointers. */
+int seir_sampler_read_forecast_marginals(seir_sampler *s, int32_t first, int32_t count, int64_t *forecast_by_day,
+                                         int64_t *forecast_by_location, int64_t *forecast_state_by_day);
+/* The same on the copy stream, with the stream and the wait of seir_sampler_read_marginals_async
+ * (seir_sampler_trace_wait completes it). */
+int seir_sampler_read_forecast_marginals_async(seir_sampler *s, int32_t first, int32_t count, int64_t *forecast_by_day,
+                                               int64_t *forecast_by_location, int64_t *forecast_state_by_day);
+/* Blocking read of the forecast moments: count [B]; ref, sum, sumsq each [B][M][H][6].  Any pointer may be NULL.
+ * SEIR_ERR_STATE (and a message) if the overflow flag is up, or before a reset. */
+int seir_sampler_read_forecast(seir_sampler *s, uint64_t *count, int32_t *ref, int64_t *sum, uint64_t *sumsq);
+
+/* ------------------------------------------------------------------------
  * Reproduction number R_it.
  *
  * calc_posterior_rit (covid19uk/posterior/reproduction_number.py:13-44): for each

@@ -1,0 +1,506 @@
+"""Forecast on the device (include/seir_hip.h, "Forecast on the device"; covid19uk_amd/csrc/forecast_kernels.h): for every
+kept draw the chain-binomial model is simulated H days forward from the state the draw's recorded events leave at the end
+of the series, and the simulated counts are folded into moments and per-draw marginals.
+
+The oracle uses the same run's recorded draws: `tr.theta` and `tr.events` are read back, the state at day T is formed by
+integer sums, the log baseline by `predict.log_baseline_path` (plus the running sum of the steps where given), and
+`SeirModel.simulate` is called per chain with `first_draw_id = chain << 20` -- the stated equivalence.  The six quantities
+and the int64 sums are NumPy's, with the per-draw initial state.  Two micro cases also go through
+`oracle/sim_oracle.simulate`, which does not share the device's binomial code.  Every comparison of device results is
+`np.array_equal` on integers.
+
+(The contraction associates F differently from k_simulate, at the 1e-16 level; a variate changes only if its uniform lies
+within that distance of a CDF step.  Seeds are fixed; should a seeded case ever trip this, show the variate and its
+threshold and take another seed -- no tolerance.)"""
+import os
+
+import numpy as np
+import pytest
+
+from covid19uk_amd import _lib, synth
+from covid19uk_amd.inference import inference as inf
+from covid19uk_amd.posterior import predict
+from covid19uk_amd.sampler import forecast_draw_id
+from oracle import sim_oracle
+from tests import helpers as H
+from tests.test_recovery_gpu import _case, _same_bits
+from tests.test_sampler_gpu import CFG_REF, CFG_SMALL, api  # noqa: F401  (fixture)
+from tests.test_summary_gpu import _cli, _datasets, _sampler
+
+pytestmark = pytest.mark.gpu
+
+FC = ("forecast_by_day", "forecast_by_location", "forecast_state_by_day")
+SEED = 77
+
+
+def _calendar(case, Hn):
+    return predict.forecast_calendar(case["cov"], None, case["k"].T, Hn)
+
+
+def _state_at_T(init, events):
+    """init [M,4], events [n,M,T,3] integer -> [n,M,4] int64: S0 + stoichiometry . sum_t events."""
+    tot = events.astype(np.int64).sum(axis=2)
+    i0 = np.asarray(init).astype(np.int64)
+    assert np.array_equal(i0, init)
+    return np.stack([i0[:, 0] - tot[..., 0], i0[:, 1] + tot[..., 0] - tot[..., 1], i0[:, 2] + tot[..., 1] - tot[..., 2],
+                     i0[:, 3] + tot[..., 2]], axis=-1)
+
+
+def _inputs(theta, events, init, T, Hn, steps=None):
+    """One chain's draws -> what `simulate` takes: par, a_path, spatial, the state at T."""
+    a_path = predict.log_baseline_path(theta[:, 5], theta[:, 6:6 + T - 1], T, Hn)
+    if steps is not None:
+        a_path = a_path + np.cumsum(steps, axis=1)
+    return theta[:, :5], a_path, theta[:, 6 + T - 1:], _state_at_T(init, events)
+
+
+def _quantities(sim, st0):
+    """sim [n,M,H,3] int64, st0 [n,M,4] -> the six quantities [n,M,H,6] with the state at the START of forecast day s."""
+    ex = np.cumsum(sim, axis=2) - sim
+    S = st0[:, :, None, 0] - ex[..., 0]
+    E = st0[:, :, None, 1] + ex[..., 0] - ex[..., 1]
+    I = st0[:, :, None, 2] + ex[..., 1] - ex[..., 2]
+    return np.concatenate([sim, np.stack([S, E, I], axis=-1)], axis=-1)
+
+
+def _fold(x, out):
+    d = x - x[0]
+    assert int(np.abs(d).max()) ** 2 * len(x) < 2 ** 62
+    out["ref"].append(x[0].astype(np.int32))
+    out["sum"].append(d.sum(axis=0))
+    out["sumsq"].append((d * d).sum(axis=0).astype(np.uint64))
+
+
+def _oracle(model, case, theta, events, Hn, seed=SEED, chain0=0, j0=0, steps=None, folds=None, simulate=None):
+    """theta [n,B,P], events [n,B,M,T,3] of one run -> forecast moments (over the draws `folds`) and marginals."""
+    n, B = theta.shape[:2]
+    T = case["k"].T
+    W, wd = _calendar(case, Hn)
+    out = dict(count=np.zeros(B, np.uint64), ref=[], sum=[], sumsq=[], sim=[], **{k: [] for k in FC})
+    for b in range(B):
+        par, a_path, spatial, st0 = _inputs(theta[:, b], events[:, b], case["init"], T, Hn, None if steps is None else steps[:, b])
+        first = forecast_draw_id(chain0 + b, j0)
+        if simulate is None:
+            sim = model.simulate(par, a_path, spatial, W, wd, st0.astype(np.float64), seed=seed, first_draw_id=first)
+        else:
+            sim = simulate(par, a_path, spatial, W, wd, st0.astype(np.float64), seed=seed, first_draw_id=first)
+        assert np.array_equal(sim, np.rint(sim))
+        sim = sim.astype(np.int64)
+        x = _quantities(sim, st0)
+        out["sim"].append(sim)
+        out["forecast_by_day"].append(x[..., :3].sum(axis=1))
+        out["forecast_by_location"].append(x[..., :3].sum(axis=2))
+        out["forecast_state_by_day"].append(x[..., 3:].sum(axis=1))
+        f = x if folds is None else x[folds]
+        out["count"][b] = len(f)
+        _fold(f, out)
+    for k in ("ref", "sum", "sumsq"):
+        out[k] = np.stack(out[k])
+    for k in FC + ("sim",):
+        out[k] = np.stack(out[k], axis=1)
+    return out
+
+
+def _same_moments(sm, want):
+    assert sm.count.dtype == np.uint64 and sm.ref.dtype == np.int32 and sm.sum.dtype == np.int64 and sm.sumsq.dtype == np.uint64
+    assert np.array_equal(sm.count, want["count"])
+    assert np.array_equal(sm.ref, want["ref"])
+    assert np.array_equal(sm.sum, want["sum"])
+    assert np.array_equal(sm.sumsq, want["sumsq"])
+
+
+def _same_marginals(m, want, rows=slice(None)):
+    for k in FC:
+        assert m[k].dtype == np.int64
+        assert np.array_equal(m[k], want[k][rows]), k
+
+
+def _same_forecast(a, b):
+    _same_moments(a[0], dict(count=b[0].count, ref=b[0].ref, sum=b[0].sum, sumsq=b[0].sumsq))
+    for k in FC:
+        assert np.array_equal(a[1][k], b[1][k]), k
+
+
+def _moved(want, sm):
+    assert want["sim"].any(), "the forecast simulated no event at all"
+    assert sm.sumsq.any(), "every draw's forecast is the same"
+
+
+def _reset(s, case, Hn, seed=SEED):
+    W, wd = _calendar(case, Hn)
+    s.reset_forecast(Hn, W, wd, seed)
+
+
+# the case ids name the branch they turn: shape of the model, horizon (the fold's day chunks and its carry), and the
+# number of draws ND = n x B against the 64-draw column tile
+CASES = {
+    # name, cfg, eps, B, record, n, H
+    "M=1": ("micro_1x70", CFG_SMALL, 0.002, 3, "u16", 6, 7),
+    "T=1,no_alpha_t": ("micro_3x1", CFG_SMALL, 0.002, 2, True, 4, 7),
+    "T=64,M=rowblock+1,H=1": ("micro_9x64", CFG_SMALL, 0.0004, 3, "u16", 5, 1),            # ND = 15
+    "T=65,M=rowblock-1,H=64,ND=64": ("micro_7x65", CFG_SMALL, 0.0004, 8, True, 8, 64),      # exactly one column tile
+    "M=65,H=65,ND=65": ("micro_65x70", CFG_SMALL, 0.0001, 1, "u16", 65, 65),                # one row / column / day past a tile
+    "M=520,H=7": ("slow_520x70", CFG_SMALL, 3e-5, 2, True, 6, 7),                           # several row tiles and K chunks
+    "T=800,H=128,ND=72": ("slower_4x800", CFG_REF, 3e-5, 8, True, 9, 128),
+    "T=800,u16,H=7": ("slower_4x800", CFG_REF, 3e-5, 1, "u16", 8, 7),
+    "uk380x8,12,H=56": ("uk380", CFG_REF, 1.2e-5, 8, "u16", 12, 56),
+}
+
+
+@pytest.mark.parametrize("case_id", list(CASES))
+def test_forecast_equals_simulate_on_the_recorded_draws(api, case_id):
+    name, cfg, eps, B, record, n, Hn = CASES[case_id]
+    case = H.build_case(name, 43, alpha_t_sd=0.005)
+    u = synth.jitter_params(case["u"], B, scale=0.002 if name == "uk380" else 0.01, seed=3, T=case["k"].T)
+    ev = np.stack([case["events"]] * B)
+    model, s = _sampler(api, case, cfg, u, ev, eps, n, record_events=record)
+    with model, s:
+        _reset(s, case, Hn)
+        tr = s.sample(n, forecast=True)
+        sm = s.forecast_summary()
+        assert tr.events.dtype == (np.uint16 if record == "u16" else np.int32)
+        assert sm.ref.shape == (B, case["k"].M, Hn, 6) and tr.forecast["forecast_by_day"].shape == (n, B, Hn, 3)
+        want = _oracle(model, case, tr.theta, tr.events, Hn)
+        if case["k"].T > 1 and case["k"].M > 1:
+            _moved(want, sm)
+        _same_marginals(tr.forecast, want)
+        _same_moments(sm, want)
+        # a second reset starts j at 0 again: the last slot alone becomes ref and is draw 0 of every chain
+        _reset(s, case, Hn)
+        s.forecast(n - 1, 1)
+        one = _oracle(model, case, tr.theta[n - 1:], tr.events[n - 1:], Hn)
+        _same_moments(s.forecast_summary(), one)
+        _same_marginals(s.read_forecast_marginals(1, first=n - 1), one)
+        assert not s.pair_timeouts().any()
+
+
+@pytest.mark.parametrize("name,Hn", [("micro_9x64", 3), ("micro_3x1", 4)])
+def test_forecast_equals_the_independent_cpu_simulator(api, name, Hn):
+    """oracle/sim_oracle.simulate shares the Philox protocol and nothing of the device's binomial code."""
+    case, u, ev, cfg, eps = _case(name, 2)
+    n = 3
+    model, s = _sampler(api, case, cfg, u, ev, eps, n)
+    with model, s:
+        _reset(s, case, Hn)
+        tr = s.sample(n, forecast=True)
+        want = _oracle(model, case, tr.theta, tr.events, Hn,
+                       simulate=lambda *a, **kw: sim_oracle.simulate(H.oracle_constants(case["cov"], case["init"]), *a, **kw))
+        assert want["sim"].any()
+        _same_marginals(tr.forecast, want)
+        _same_moments(s.forecast_summary(), want)
+
+
+def test_cutting_a_burst_into_calls_halves_or_batches_does_not_matter(api):
+    case, u, ev, cfg, eps = _case("micro_20x60", 5)
+    n, Hn = 11, 9
+    model, s = _sampler(api, case, cfg, u, ev, eps, 2 * n)
+    with model, s:
+        _reset(s, case, Hn)
+        for first in (0, n):                                   # two bursts in the two halves of the buffer
+            s.reset_trace(at=first)
+            s.run(n)
+            s.forecast(first, n)
+        tr = s.read_trace(2 * n)
+        halves = (s.forecast_summary(), s.read_forecast_marginals(2 * n))
+        want = _oracle(model, case, tr.theta, tr.events, Hn)
+        _moved(want, halves[0])
+        _same_moments(halves[0], want)
+        _same_marginals(halves[1], want)
+        _reset(s, case, Hn)
+        s.forecast(0, 2 * n)                                   # one call over everything
+        _same_forecast((s.forecast_summary(), s.read_forecast_marginals(2 * n)), halves)
+        _reset(s, case, Hn)
+        for first, count in ((0, 3), (3, 1), (4, 9), (13, 2 * n - 13)):
+            s.forecast(first, count)
+        _same_forecast((s.forecast_summary(), s.read_forecast_marginals(2 * n)), halves)
+
+
+def test_a_call_longer_than_one_host_batch_holds(api):
+    """More slots than one batch of the host's cut (128): ND above the batch size, the same integers as slot by slot."""
+    case, u, ev, cfg, eps = _case("micro_5x24", 2)
+    n, Hn = 150, 3
+    model, s = _sampler(api, case, cfg, u, ev, 0.002, n)
+    with model, s:
+        _reset(s, case, Hn)
+        tr = s.sample(n, forecast=True)
+        whole = (s.forecast_summary(), tr.forecast)
+        want = _oracle(model, case, tr.theta, tr.events, Hn)
+        _moved(want, whole[0])
+        _same_moments(whole[0], want)
+        _same_marginals(whole[1], want)
+        _reset(s, case, Hn)
+        for first in range(0, n, 50):
+            s.forecast(first, 50)
+        _same_forecast((s.forecast_summary(), s.read_forecast_marginals(n)), whole)
+
+
+@pytest.mark.parametrize("skew", [1, 2, 3])
+def test_forecasts_do_not_depend_on_workgroup_timing_and_repeat(api, skew):
+    case, u, ev, cfg, eps = _case("micro_20x60", 5)
+    n, Hn = 6, 10
+    res = {}
+    for tag, sk in (("a", 0), ("b", 0), ("skew", skew)):
+        if tag == "b" and skew != 1:
+            continue                                           # the repeat of the plain run is checked once
+        model, s = _sampler(api, case, cfg, u, ev, eps, n, skew=sk, record_events="u16")
+        with model, s:
+            _reset(s, case, Hn)
+            tr = s.sample(n, forecast=True)
+            res[tag] = (s.forecast_summary(), tr.forecast, tr)
+    assert res["a"][0].sumsq.any()
+    for tag in res:
+        assert np.array_equal(res["a"][2].events, res[tag][2].events)
+        _same_forecast(res[tag], res["a"])
+
+
+def test_chains_keep_their_forecasts_however_they_are_sharded(api):
+    """Chains 2 and 3 of a 4-chain sampler against a 2-chain sampler created with first_chain_id = 2."""
+    case, u, ev, cfg, eps = _case("micro_20x60", 4)
+    n, Hn = 5, 8
+    model, s = _sampler(api, case, cfg, u, ev, eps, n)
+    with model, s:
+        _reset(s, case, Hn)
+        tr4 = s.sample(n, forecast=True)
+        sm4 = s.forecast_summary()
+    model, s = _sampler(api, case, cfg, u[2:], ev[2:], eps, n, first_chain_id=2)
+    with model, s:
+        _reset(s, case, Hn)
+        tr2 = s.sample(n, forecast=True)
+        sm2 = s.forecast_summary()
+        want = _oracle(model, case, tr2.theta, tr2.events, Hn, chain0=2)
+        _same_moments(sm2, want)
+    assert np.array_equal(tr4.events[:, 2:], tr2.events)
+    assert sm2.sumsq.any()
+    for k in FC:
+        assert np.array_equal(tr4.forecast[k][:, 2:], tr2.forecast[k]), k
+    for a, b in ((sm4.count[2:], sm2.count), (sm4.ref[2:], sm2.ref), (sm4.sum[2:], sm2.sum), (sm4.sumsq[2:], sm2.sumsq)):
+        assert np.array_equal(a, b)
+
+
+def test_the_chain_does_not_notice_being_forecast(api):
+    """A sampler that forecasts (and summarises) every burst against one that never does: traces, summaries, final state
+    and kernel bit for bit."""
+    case, u, ev, cfg, eps = _case("micro_20x60", 5)
+    nb, burst, Hn = 4, 5, 6
+    runs = {}
+    for fc in (False, True):
+        model, s = _sampler(api, case, cfg, u, ev, eps, 2 * burst, log=None)
+        with model, s:
+            got = {}
+            if fc:
+                _reset(s, case, Hn)
+
+            def consume(tr, i, got=got):
+                got[i] = (tr.theta.copy(), tr.events.copy(), {k: v.copy() for k, v in tr.hmc.items()},
+                          {mk: {kk: v.copy() for kk, v in mv.items()} for mk, mv in tr.moves.items()},
+                          {k: v.copy() for k, v in tr.marginals.items()},
+                          None if tr.forecast is None else {k: v.copy() for k, v in tr.forecast.items()})
+            s.sample_bursts(nb, burst, consume, summarize=True, **(dict(forecast=True) if fc else {}))
+            runs[fc] = (got, s.get_state() + s.get_kernel(), s.summary(), s.forecast_summary() if fc else None)
+            if fc:
+                theta = np.concatenate([got[i][0] for i in range(nb)])
+                events = np.concatenate([got[i][1] for i in range(nb)])
+                want = _oracle(model, case, theta, events, Hn)
+                _moved(want, runs[fc][3])
+                _same_moments(runs[fc][3], want)
+                _same_marginals({k: np.concatenate([got[i][5][k] for i in range(nb)]) for k in FC}, want)
+    from types import SimpleNamespace
+    for i in range(nb):
+        a, b = (SimpleNamespace(theta=x[0], events=x[1], hmc=x[2], moves=x[3]) for x in (runs[False][0][i], runs[True][0][i]))
+        _same_bits(a, b)
+        assert runs[False][0][i][5] is None
+        for k in runs[False][0][i][4]:
+            assert np.array_equal(runs[False][0][i][4][k], runs[True][0][i][4][k]), k
+    for x, y in zip(runs[False][1], runs[True][1]):
+        assert np.array_equal(x, y)
+    for k in ("count", "ref", "sum", "sumsq"):
+        assert np.array_equal(getattr(runs[False][2], k), getattr(runs[True][2], k)), k
+
+
+@pytest.mark.parametrize("k", [3])
+def test_with_thinning_the_forecasts_are_those_of_the_kept_draws(api, k):
+    case, u, ev, cfg, eps = _case("micro_20x60", 4)
+    n, Hn = 6, 5
+    model, s = _sampler(api, case, cfg, u, ev, eps, n, thin=k)
+    with model, s:
+        _reset(s, case, Hn)
+        kept = s.sample(n, forecast=True)
+        sm = s.forecast_summary()
+    model, s = _sampler(api, case, cfg, u, ev, eps, n * k)
+    with model, s:
+        every = s.sample(n * k)
+        assert np.array_equal(every.events[k - 1::k], kept.events)
+        want = _oracle(model, case, every.theta[k - 1::k], every.events[k - 1::k], Hn)
+    _moved(want, sm)
+    _same_moments(sm, want)
+    _same_marginals(kept.forecast, want)
+
+
+def test_supplied_steps_walk_the_baseline_and_another_seed_gives_other_forecasts(api):
+    case, u, ev, cfg, eps = _case("micro_20x60", 3)
+    n, Hn = 7, 12
+    steps = np.random.default_rng(5).normal(0.0, 0.05, size=(n, 3, Hn))
+    model, s = _sampler(api, case, cfg, u, ev, eps, n)
+    with model, s:
+        _reset(s, case, Hn)
+        tr = s.sample(n, forecast=True)
+        held = (s.forecast_summary(), tr.forecast)
+        _same_moments(held[0], _oracle(model, case, tr.theta, tr.events, Hn))
+        _reset(s, case, Hn)
+        s.forecast(0, 4, steps[:4])                            # two calls: j goes on, and so do the steps' rows
+        s.forecast(4, n - 4, steps[4:])
+        walked = (s.forecast_summary(), s.read_forecast_marginals(n))
+        want = _oracle(model, case, tr.theta, tr.events, Hn, steps=steps)
+        _moved(want, walked[0])
+        _same_moments(walked[0], want)
+        _same_marginals(walked[1], want)
+        assert any((walked[1][k] != held[1][k]).any() for k in FC)
+        _reset(s, case, Hn, seed=SEED + 1)
+        s.forecast(0, n)
+        other = (s.forecast_summary(), s.read_forecast_marginals(n))
+        _same_moments(other[0], _oracle(model, case, tr.theta, tr.events, Hn, seed=SEED + 1))
+        assert any((other[1][k] != held[1][k]).any() for k in FC)
+
+
+def test_a_burst_run_again_after_a_time_out_is_forecast_and_counted_once(api):
+    """seir_sampler_debug_fail_handoff (the existing test hook, once) in the middle of overlapped bursts that are forecast:
+    the burst is restored -- forecast accumulators and the draw counter included -- and run again one launch form down."""
+    case, u, ev, cfg, eps = _case("micro_20x60", 8)
+    B, nb, burst, Hn = 8, 6, 4, 5
+    runs = {}
+    for disturb in (False, True):
+        model, s = _sampler(api, case, cfg, u, ev, eps, 2 * burst, log=None)
+        with model, s:
+            got = {}
+            _reset(s, case, Hn)
+
+            def consume(tr, i, got=got, s=s, disturb=disturb):
+                got[i] = (tr.events.copy(), {k: v.copy() for k, v in tr.forecast.items()}, tr.theta.copy())
+                if disturb and i == 1 and not s.recoveries:    # while burst 2 or 3 is in flight
+                    _lib.check(s._lib.seir_sampler_debug_fail_handoff(s._s, B - 1))
+            s.sample_bursts(nb, burst, consume, forecast=True)
+            runs[disturb] = (got, s.forecast_summary(), list(s.recoveries))
+            if not disturb:
+                want = _oracle(model, case, np.concatenate([got[i][2] for i in range(nb)]),
+                               np.concatenate([got[i][0] for i in range(nb)]), Hn)
+    ref, got = runs[False], runs[True]
+    assert not ref[2] and len(got[2]) == 1, got[2]
+    assert sorted(got[0]) == list(range(nb))
+    for i in range(nb):
+        assert np.array_equal(ref[0][i][0], got[0][i][0]), i
+    _moved(want, ref[1])
+    _same_moments(ref[1], want)
+    # theta of the re-run bursts agrees to the order of summation only (another launch form), so the disturbed run is
+    # held to its own draws: counted once, and forecast with the draw numbers it would have had undisturbed
+    with api[0](case["cov"], case["init"], max_chains=B) as model:
+        want2 = _oracle(model, case, np.concatenate([got[0][i][2] for i in range(nb)]),
+                        np.concatenate([got[0][i][0] for i in range(nb)]), Hn)
+    _same_moments(got[1], want2)
+    _same_marginals({k: np.concatenate([got[0][i][1][k] for i in range(nb)]) for k in FC}, want2)
+
+
+def test_refusals(api):
+    case, u, ev, cfg, eps = _case("micro_20x60", 2)
+    W, wd = _calendar(case, 5)
+    model, s = _sampler(api, case, cfg, u, ev, eps, 4, record_events=False)
+    with model, s:
+        for call in (lambda: s.reset_forecast(5, W, wd), lambda: s.forecast(0, 1), lambda: s.read_forecast_marginals(1),
+                     lambda: s.forecast_summary()):
+            with pytest.raises(_lib.SeirError) as e:
+                call()
+            assert e.value.code == _lib.ERR_STATE
+    model, s = _sampler(api, case, cfg, u, ev, eps, 4)
+    with model, s:
+        for call in (lambda: s.forecast(0, 1), lambda: s.read_forecast_marginals(1), lambda: s.forecast_summary()):
+            with pytest.raises(_lib.SeirError, match="seir_sampler_forecast_reset") as e:    # before a reset
+                call()
+            assert e.value.code == _lib.ERR_STATE
+        one = np.zeros(129)
+        for Hn in (0, 129):                                    # past the Python check too: the library refuses
+            with pytest.raises(ValueError):
+                s.reset_forecast(Hn, one[:Hn], one[:Hn])
+            rc = s._lib.seir_sampler_forecast_reset(s._s, Hn, one.ctypes.data_as(_lib.c_double_p),
+                                                    one.ctypes.data_as(_lib.c_double_p), 0)
+            assert rc == _lib.ERR_INVALID
+        s.reset_forecast(5, W, wd)
+        for first, count in ((-1, 1), (0, 5), (4, 1), (3, 2), (0, -1)):
+            calls = [lambda: s.forecast(first, count)]
+            if count >= 0:
+                calls.append(lambda: s.read_forecast_marginals(count, first=first))
+            for call in calls:
+                with pytest.raises(_lib.SeirError) as e:
+                    call()
+                assert e.value.code == _lib.ERR_INVALID, (first, count)
+        s.sample(4, forecast=True)                             # and the sampler is as usable as before
+        assert np.array_equal(s.forecast_summary().count, [4, 4])
+    model, s = _sampler(api, case, cfg, u, ev, eps, 4, first_chain_id=2047)     # chain ids 2047 and 2048
+    with model, s:
+        with pytest.raises(_lib.SeirError, match="chain id 2048") as e:
+            s.reset_forecast(5, W, wd)
+        assert e.value.code == _lib.ERR_INVALID
+
+
+def test_m_above_the_simulators_limit_is_refused_with_its_message(api):
+    case = H.build_case("micro_1281x2", 43)
+    u = case["u"][None]
+    model, s = _sampler(api, case, CFG_SMALL, u, case["events"][None], 1e-4, 2)
+    with model, s:
+        with pytest.raises(_lib.SeirError, match="M=1281 needs .* B of LDS for the simulator") as e:
+            s.reset_forecast(3, np.ones(3), np.zeros(3))
+        assert e.value.code == _lib.ERR_INVALID
+
+
+# ---- CLI end to end -------------------------------------------------------------------------------------------------------
+def test_cli_forecast(api, tmp_path):
+    """`--forecast 14` on an NI-11 data set: the group and datasets with the right shapes, equal to the oracle from the
+    file's own samples/seir and parameters; `--summaries only --forecast 14` works without samples/seir and gives the same
+    forecast; without the flag the file has exactly today's datasets."""
+    tmp_path = str(tmp_path)
+    cov = synth.make_covariates("ni11")
+    events, init, _ = synth.simulate_epidemic(cov)
+    data = os.path.join(tmp_path, "data.npz")
+    inf.write_inference_data(data, cov, events[..., 2])
+    fc_path, fc_log = _cli(tmp_path, "fc", data, ["--forecast", "14"])
+    fc = _datasets(fc_path)
+    only = _datasets(_cli(tmp_path, "only", data, ["--summaries", "only", "--forecast", "14"])[0])
+    plain = _datasets(_cli(tmp_path, "plain", data, [])[0])
+    new = {"forecast/horizon", "forecast/first_day", "forecast/count", "forecast/seir_mean", "forecast/seir_var",
+           "forecast/state_mean", "forecast/state_var", "samples/forecast_by_day", "samples/forecast_by_location",
+           "samples/forecast_state_by_day"}
+    assert set(fc) - set(plain) == new and set(plain) <= set(fc)
+    for k in plain:
+        if plain[k].dtype.kind in "fiub":
+            assert np.array_equal(plain[k], fc[k], equal_nan=plain[k].dtype.kind == "f"), k
+    assert "samples/seir" not in only and new <= set(only)
+    for k in new:
+        assert np.array_equal(only[k], fc[k], equal_nan=fc[k].dtype.kind == "f"), k
+    assert "Forecast: 14 day(s)" in fc_log
+    M, T, Hn, ns = cov.M, cov.T, 14, 2 * 6
+    assert fc["samples/forecast_by_day"].shape == (ns, Hn, 3) and fc["samples/forecast_by_day"].dtype == np.int64
+    assert fc["samples/forecast_by_location"].shape == (ns, M, 3) and fc["samples/forecast_state_by_day"].shape == (ns, Hn, 3)
+    assert fc["forecast/seir_mean"].shape == (M, Hn, 3) and fc["forecast/state_var"].shape == (M, Hn, 3)
+    assert fc["forecast/horizon"].reshape(-1)[0] == Hn and fc["forecast/first_day"].reshape(-1)[0] == T
+    assert fc["forecast/count"].reshape(-1)[0] == ns
+    # the oracle from the file's own draws: the sampling phase is the last ns rows
+    from covid19uk_amd.sampler import summary_mean, summary_var
+    cov2, _, dates = inf.read_inference_data(data)
+    W, wd = predict.forecast_calendar(cov2, dates, T, Hn)
+    seir = fc["samples/seir"][-ns:]
+    assert np.array_equal(seir, np.rint(seir))
+    theta = np.concatenate([fc[f"samples/{k}"][-ns:].reshape(ns, -1) for k in
+                            ("psi", "sigma_space", "beta_area", "gamma0", "gamma1", "alpha_0", "alpha_t", "spatial_effect")], axis=1)
+    init_f = fc["initial_state"]
+    par, a_path, spatial, st0 = _inputs(theta, seir.astype(np.int64), init_f, T, Hn)
+    with api[0](cov2, init_f, max_chains=1) as model:
+        sim = model.simulate(par, a_path, spatial, W, wd, st0.astype(np.float64), seed=0, first_draw_id=0).astype(np.int64)
+    assert sim.any()
+    x = _quantities(sim, st0)
+    assert np.array_equal(fc["samples/forecast_by_day"], x[..., :3].sum(axis=1))
+    assert np.array_equal(fc["samples/forecast_by_location"], x[..., :3].sum(axis=2))
+    assert np.array_equal(fc["samples/forecast_state_by_day"], x[..., 3:].sum(axis=1))
+    d = x - x[:1]
+    cnt = np.array(ns, np.uint64)
+    mean = summary_mean(cnt, x[0], d.sum(axis=0))
+    var = summary_var(cnt, d.sum(axis=0), (d * d).sum(axis=0))
+    assert np.array_equal(fc["forecast/seir_mean"], mean[..., :3]) and np.array_equal(fc["forecast/state_mean"], mean[..., 3:])
+    assert np.array_equal(fc["forecast/seir_var"], var[..., :3]) and np.array_equal(fc["forecast/state_var"], var[..., 3:])
