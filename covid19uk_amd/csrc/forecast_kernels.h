@@ -16,10 +16,10 @@
 //       draw's scalars are coalesced loads.  Rates through the simulator's functions (sim_eb, sim_p_se, sim_p_ir),
 //       three sim_binomial variates, state update, X of the next day, and the day's counts as int32 into the staging
 //       tensor fev[ND][M][H][3].
-//   k_forecast_fold           once per batch, the shape of k_summarize: a wave per (row, chain), a lane per forecast
-//       day, the draw loop inside, so the accumulators cross memory once per launch; by-day sums through an LDS tile and
-//       one global atomic per entry that is not zero; the state is scanned from the PER-DRAW initial state St0.
-//   k_forecast_finish         state_by_day from the finished by-day sums; advances count[b].
+//   k_forecast_fold           once per batch: k_summarize<0, 0> over the H forecast days of the staging tensor, with its
+//       pieces (summary_kernels.h) and the state scanned from the PER-DRAW initial state St0.
+//   k_forecast_finish         k_summary_finish's body with St0: state_by_day from the finished by-day sums; advances count[b].
+// The accumulators and marginals are a MomentBufs (ForecastBufs::mom), as the summaries' are.
 // Random numbers are k_simulate's protocol: Philox4x32-10, key = forecast seed, counter = (attempt, 64 + transition,
 // s M + m, draw id) with draw id = (global chain id << 20) + j, j the number of that chain's draws forecast since the last
 // reset: nothing depends on how bursts are cut into calls or batches, on the launch geometry or on the sharding of chains.
@@ -52,15 +52,7 @@ struct ForecastBufs {
     double *base;                  // [H][ndp] log baseline of forecast day s
     const double *steps;           // [ND][H] random-walk steps of the batch (or null: the baseline is held)
     int *fev;                      // [ND][M][H][3] the simulated counts
-    // accumulators and marginals
-    int32_t *ref;                  // [B][M][H][6]
-    int64_t *sum;
-    uint64_t *sumsq;
-    uint64_t *count;               // [B]
-    unsigned *overflow;            // [1]
-    int64_t *fbd;                  // [cap][B][H][3] forecast_by_day
-    int64_t *fbl;                  // [cap][B][M][3] forecast_by_location
-    int64_t *fsbd;                 // [cap][B][H][3] forecast_state_by_day
+    MomentBufs mom;                // accumulators and marginals over [H]: forecast_by_day, _by_location, _state_by_day
 };
 
 // grid (Mp / FC_ROWS, ndp), 64 FC_ROWS threads.  Draws [ND, ndp) and rows [M, Mp) get zeros (the contraction reads them).
@@ -156,6 +148,10 @@ __global__ __launch_bounds__(64 * FC_DAY_ROWS) void k_forecast_day(Dims d, Const
     fb.X[idx] = (double)I * c.invN[m];
 }
 
+static_assert(FC_ROWS == SUM_ROWS && FC_JB == SUM_JB && FC_JMAX == SUM_JMAX, "k_forecast_fold uses k_summarize's pieces");
+
+// k_summarize<0, 0> over the H forecast days of the staging tensor, with its pieces (summary_kernels.h), but for: each
+// draw's state is scanned from ITS OWN initial state St0; one draw's load is in flight, not SUM_U; the draws are always folded.
 // grid (ceil(M / FC_ROWS), B), 64 FC_ROWS threads.  1 <= count <= FC_JMAX slots starting at trace slot `first`.
 __global__ __launch_bounds__(64 * FC_ROWS) void k_forecast_fold(Dims d, ForecastBufs fb, int B, int first, int count,
                                                                 int ndp) {
@@ -165,11 +161,11 @@ __global__ __launch_bounds__(64 * FC_ROWS) void k_forecast_fold(Dims d, Forecast
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int b = blockIdx.y, m = blockIdx.x * FC_ROWS + wv;
     const int M = d.M, H = fb.H;
+    const MomentBufs &sb = fb.mom;
     const bool row_ok = m < M;
-    const bool fresh = fb.count[b] == 0;               // count moves in k_forecast_finish, a launch of its own: no race
+    const bool fresh = sb.count[b] == 0;               // count moves in k_forecast_finish, a launch of its own: no race
     const size_t plane = (size_t)d.Mp * ndp;
-    for (int i = lane; i < count * 3; i += 64) (&carry[wv][0][0])[i] = 0;
-    for (int i = threadIdx.x; i < FC_JB * 64 * 3; i += 64 * FC_ROWS) (&bd[0][0][0])[i] = 0ull;
+    fold_lds_zero(bd, carry[wv], count, lane);
     __syncthreads();
 
     bool ovf = false;
@@ -182,14 +178,7 @@ __global__ __launch_bounds__(64 * FC_ROWS) void k_forecast_fold(Dims d, Forecast
         uint64_t sq[SUMMARY_Q];
 #pragma unroll
         for (int q = 0; q < SUMMARY_Q; ++q) { ref[q] = 0; sm[q] = 0; sq[q] = 0; }
-        if (live && !fresh) {
-#pragma unroll
-            for (int q = 0; q < SUMMARY_Q; ++q) {
-                ref[q] = fb.ref[cell * SUMMARY_Q + q];
-                sm[q] = fb.sum[cell * SUMMARY_Q + q];
-                sq[q] = fb.sumsq[cell * SUMMARY_Q + q];
-            }
-        }
+        if (live && !fresh) fold_load(sb, cell, ref, sm, sq);
         for (int jb = 0; jb < count; jb += FC_JB) {
             const int nj = min(FC_JB, count - jb);
             for (int jj = 0; jj < nj; ++jj) {
@@ -212,32 +201,23 @@ __global__ __launch_bounds__(64 * FC_ROWS) void k_forecast_fold(Dims d, Forecast
 #pragma unroll
                     for (int x = 0; x < 3; ++x)
                         if (kk[x] != 0) atomicAdd(&bd[jj][lane][x], (unsigned long long)kk[x]);
-                    const int val[SUMMARY_Q] = {kk[0], kk[1], kk[2], s0[0] - ex[0], s0[1] + ex[0] - ex[1],
-                                                s0[2] + ex[1] - ex[2]};
+                    int val[SUMMARY_Q];
+                    fold_values(kk, s0, ex, val);
                     const bool is_first = fresh && j == 0;
 #pragma unroll
                     for (int q = 0; q < SUMMARY_Q; ++q) ovf |= summary_fold(ref[q], sm[q], sq[q], val[q], is_first);
                 }
             }
             __syncthreads();
-            // the workgroup's part of forecast_by_day for these draws and days: one atomic per entry that is not zero
-            for (int i = threadIdx.x; i < nj * 64 * 3; i += 64 * FC_ROWS) {
-                const unsigned long long v = (&bd[0][0][0])[i];
-                const int jj = i / 192, r = i - jj * 192, sl = r / 3, x = r - sl * 3;
-                if (v != 0ull) {
-                    (&bd[0][0][0])[i] = 0ull;
-                    atomicAdd(reinterpret_cast<unsigned long long *>(fb.fbd) +
-                                  (((size_t)(first + jb + jj) * B + b) * H + (h0 + sl)) * 3 + x, v);
-                }
-            }
+            fold_tile_flush(bd, nj, sb.by_day, first + jb, B, b, H, h0);
             __syncthreads();
         }
         if (live) {
 #pragma unroll
             for (int q = 0; q < SUMMARY_Q; ++q) {
-                if (fresh) fb.ref[cell * SUMMARY_Q + q] = ref[q];
-                fb.sum[cell * SUMMARY_Q + q] = sm[q];
-                fb.sumsq[cell * SUMMARY_Q + q] = sq[q];
+                if (fresh) sb.ref[cell * SUMMARY_Q + q] = ref[q];
+                sb.sum[cell * SUMMARY_Q + q] = sm[q];
+                sb.sumsq[cell * SUMMARY_Q + q] = sq[q];
             }
         }
     }
@@ -245,47 +225,17 @@ __global__ __launch_bounds__(64 * FC_ROWS) void k_forecast_fold(Dims d, Forecast
     if (row_ok)
         for (int i = lane; i < count * 3; i += 64) {
             const int j = i / 3, x = i - j * 3;
-            fb.fbl[(((size_t)(first + j) * B + b) * M + m) * 3 + x] = (int64_t)carry[wv][j][x];
+            sb.by_loc[(((size_t)(first + j) * B + b) * M + m) * 3 + x] = (int64_t)carry[wv][j][x];
         }
-    if (ovf) fb.overflow[0] = 1u;
+    if (ovf) sb.overflow[0] = 1u;
 }
 
-// forecast_state_by_day from the finished forecast_by_day and the draw's own initial state; count[b] += count.
-// grid (count, B), one wave.
+// k_summary_finish over the H forecast days, with the draw's own initial state St0.  grid (count, B), one wave.
 __global__ __launch_bounds__(64) void k_forecast_finish(Dims d, ForecastBufs fb, int B, int first, int count, int ndp) {
-    const int lane = threadIdx.x, b = blockIdx.y, j = blockIdx.x, nd = j * B + b;
-    const int H = fb.H;
     const size_t plane = (size_t)d.Mp * ndp;
-    long long tot0[3] = {0, 0, 0};
-    for (int m = lane; m < d.M; m += 64)
-#pragma unroll
-        for (int x = 0; x < 3; ++x) tot0[x] += (long long)fb.St0[x * plane + (size_t)m * ndp + nd];
-#pragma unroll
-    for (int x = 0; x < 3; ++x)
-        for (int o = 32; o > 0; o >>= 1) tot0[x] += __shfl_xor(tot0[x], o, 64);
-    long long cr[3] = {0, 0, 0};
-    const size_t base = ((size_t)(first + j) * B + b) * H;
-    for (int h0 = 0; h0 < H; h0 += 64) {
-        const int s = h0 + lane;
-        long long ex[3];
-#pragma unroll
-        for (int x = 0; x < 3; ++x) {
-            const long long v = s < H ? fb.fbd[(base + s) * 3 + x] : 0ll;
-            long long inc = v;
-            for (int o = 1; o < 64; o <<= 1) {
-                const long long up = __shfl_up(inc, o, 64);
-                if (lane >= o) inc += up;
-            }
-            ex[x] = cr[x] + inc - v;
-            cr[x] += __shfl(inc, 63, 64);
-        }
-        if (s < H) {
-            fb.fsbd[(base + s) * 3 + 0] = tot0[0] - ex[0];
-            fb.fsbd[(base + s) * 3 + 1] = tot0[1] + ex[0] - ex[1];
-            fb.fsbd[(base + s) * 3 + 2] = tot0[2] + ex[1] - ex[2];
-        }
-    }
-    if (blockIdx.x == 0 && lane == 0) fb.count[b] += (uint64_t)count;
+    const int nd = blockIdx.x * B + blockIdx.y;
+    moment_finish(fb.mom, d.M, fb.H, B, first + blockIdx.x, count, true,
+                  [&](int m, int x) { return fb.St0[x * plane + (size_t)m * ndp + nd]; });
 }
 
 }  // namespace seir

@@ -1000,6 +1000,73 @@ extern "C" int seir_selftest_binomial(seir_ctx *ctx, int32_t count, const int32_
 // ===========================================================================
 // Sampler (see include/seir_hip.h, "Device-resident Metropolis-within-Gibbs")
 // ===========================================================================
+// A device allocation that travels with the snapshots (seir_sampler_snapshot / _restore): its shadow copy for each of the two
+// slots and whether that holds anything.  A shadow taken before the feature that owns the buffer was enabled or last reset
+// holds nothing of it (valid = false): restoring that slot leaves the buffer alone.
+struct Shadowed {
+    void *p = nullptr;
+    size_t bytes = 0;
+    void *snap[2] = {nullptr, nullptr};
+    bool valid[2] = {false, false};
+};
+// One set of moment accumulators (MomentBufs' ref .. overflow) as ONE allocation, every part naturally aligned:
+//     sum [cells] | sumsq [cells] | count [B, padded to 256 B] | ref [cells] | flag
+// (the padding keeps count's length from moving ref off the cache lines that the 16 B x cells before it leave it on)
+struct MomentAcc : Shadowed {
+    size_t cells = 0, B = 0;
+    size_t count_words() const { return (B + 31) / 32 * 32; }
+};
+
+static void acc_layout(const MomentAcc &a, MomentBufs &mb) {
+    mb.sum = (int64_t *)a.p;
+    mb.sumsq = (uint64_t *)(mb.sum + a.cells);
+    mb.count = mb.sumsq + a.cells;
+    mb.ref = (int32_t *)(mb.count + a.count_words());
+    mb.overflow = (unsigned *)(mb.ref + a.cells);
+}
+static int acc_alloc(Shadowed &a, size_t bytes) {
+    a.bytes = bytes;
+    HIP_TRY(hipMalloc(&a.p, bytes));
+    HIP_TRY(hipMemset(a.p, 0, bytes));
+    return 0;
+}
+static int acc_alloc(MomentAcc &a, size_t cells, size_t B, MomentBufs &mb) {
+    a.cells = cells; a.B = B;
+    if (int rc = acc_alloc(a, cells * (sizeof(int64_t) + sizeof(uint64_t) + sizeof(int32_t)) + a.count_words() * sizeof(uint64_t) + 8))
+        return rc;
+    acc_layout(a, mb);
+    return 0;
+}
+static int acc_zero(Shadowed &a, hipStream_t st) {
+    HIP_TRY(hipMemsetAsync(a.p, 0, a.bytes, st));
+    return 0;
+}
+// save: the buffer into the slot's shadow; else the shadow back, if it holds anything.  In stream order.
+static int acc_shadow(Shadowed &a, int slot, bool save, hipStream_t st) {
+    if (!save && !a.valid[slot]) return 0;
+    if (!a.snap[slot]) HIP_TRY(hipMalloc(&a.snap[slot], a.bytes));
+    HIP_TRY(hipMemcpyAsync(save ? a.snap[slot] : a.p, save ? a.p : a.snap[slot], a.bytes, hipMemcpyDeviceToDevice, st));
+    if (save) a.valid[slot] = true;
+    return 0;
+}
+static void acc_invalidate(Shadowed &a) { a.valid[0] = a.valid[1] = false; }
+static void acc_free(Shadowed &a) {
+    for (void *q : {a.p, a.snap[0], a.snap[1]}) if (q) (void)hipFree(q);
+    a = Shadowed{};
+}
+// Blocking read of whichever parts are asked for, and of the sticky overflow flag.
+static int acc_read(const MomentAcc &a, hipStream_t st, uint64_t *count, int32_t *ref, int64_t *sum, uint64_t *sumsq, unsigned *flag) {
+    MomentBufs mb{};
+    acc_layout(a, mb);
+    HIP_TRY(hipMemcpyAsync(flag, mb.overflow, sizeof(*flag), hipMemcpyDeviceToHost, st));
+    if (count) HIP_TRY(hipMemcpyAsync(count, mb.count, sizeof(uint64_t) * a.B, hipMemcpyDeviceToHost, st));
+    if (ref) HIP_TRY(hipMemcpyAsync(ref, mb.ref, sizeof(int32_t) * a.cells, hipMemcpyDeviceToHost, st));
+    if (sum) HIP_TRY(hipMemcpyAsync(sum, mb.sum, sizeof(int64_t) * a.cells, hipMemcpyDeviceToHost, st));
+    if (sumsq) HIP_TRY(hipMemcpyAsync(sumsq, mb.sumsq, sizeof(uint64_t) * a.cells, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
 struct seir_sampler {
     seir_ctx *ctx = nullptr;
     SamplerCfg cfg{};
@@ -1057,45 +1124,42 @@ struct seir_sampler {
     int thin_pending = 1;             // seir_sampler_set_thin: becomes cfg.thin at the next trace reset (Chains::slot0 is encoded for cfg.thin)
     // --- summaries of the recorded events (seir_sampler_summary_reset ...; summary_kernels.h) ---
     bool sum_on = false;              // enabled by the first seir_sampler_summary_reset: buffers exist
-    SummaryBufs sum{};
-    void *sum_snap[2] = {nullptr, nullptr};   // shadow copies of ref | sum | sumsq | count | flag for the two snapshot slots
-    bool sum_snap_valid[2] = {false, false};
+    MomentBufs sum{};
+    MomentAcc sum_acc;                // sum's ref .. overflow
     // --- convergence diagnostics (seir_sampler_diag_reset ...): ONE allocation of 64-bit words,
     //     bsum [n] | bsumsq [n] | nbatch [B] | mark 0: count [B] | sum [n] | sumsq [n] | mark 1: the same
     bool diag_on = false;
     SummaryDiag<1> diag{};
-    uint64_t *diag_buf = nullptr;
-    void *diag_snap[2] = {nullptr, nullptr};  // shadow copies of all of it for the two snapshot slots
-    bool diag_snap_valid[2] = {false, false};
+    Shadowed diag_buf;
     // --- forecast of the next H days (seir_sampler_forecast_reset ...; forecast_kernels.h) ---
     bool fc_on = false;
     ForecastBufs fc{};
     int fc_slots = 0;                 // trace slots per batch: min(cap, FC_JMAX)
     int fc_ndmax = 0;                 // row stride the planes are allocated for: ceil64(fc_slots * B)
     std::vector<void *> fc_allocs;    // device buffers whose size depends on the horizon (allocated again when it changes)
-    void *fc_acc = nullptr;           // ONE allocation: sum [n] | sumsq [n] | count [B] | ref [n] | flag
-    size_t fc_acc_bytes = 0;
+    MomentAcc fc_acc;                 // fc.mom's ref .. overflow
     long long fc_j = 0;               // draws per chain forecast since the last reset (the j of the draw id)
-    void *fc_snap[2] = {nullptr, nullptr};    // shadow copies of fc_acc for the two snapshot slots ...
-    long long fc_snap_j[2] = {0, 0};          // ... and of fc_j
-    bool fc_snap_valid[2] = {false, false};
+    long long fc_snap_j[2] = {0, 0};  // fc_j as it was when fc_acc's shadows were taken
     double *fc_steps_host = nullptr;  // page-locked [cap][B][H]: the caller's random-walk steps on their way to the device
     double *fc_steps_dev = nullptr;   // [fc_slots * B][H]
     hipEvent_t fc_ev_steps = nullptr; // behind the last upload from fc_steps_host
     bool fc_steps_pending = false;
 };
 
+// Zeroed device memory, registered in `list` (seir_sampler::allocs: freed with the sampler; fc_allocs: also when the horizon
+// changes) and, when it is chain state or hand-off scratch, in the regions a snapshot / restore goes through.
 template <typename T>
-static int s_alloc(seir_sampler *s, T **p, size_t count, int kind = seir_sampler::R_OTHER) {
+static int s_alloc(seir_sampler *s, std::vector<void *> &list, T **p, size_t count, int kind = seir_sampler::R_OTHER) {
     void *q = nullptr;
     const size_t bytes = (count ? count : 1) * sizeof(T);
     HIP_TRY(hipMalloc(&q, bytes));
-    s->allocs.push_back(q);
-    s->regions.push_back({q, bytes, kind});
+    list.push_back(q);
+    if (kind != seir_sampler::R_OTHER) s->regions.push_back({q, bytes, kind});
     HIP_TRY(hipMemset(q, 0, bytes));
     *p = (T *)q;
     return 0;
 }
+#define S_ALLOC(list, ptr, ...) if (!rc) rc = s_alloc(s, s->list, &(ptr), __VA_ARGS__)
 
 static void drop_graph(seir_sampler *s) {
     for (auto &g : s->gexec) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
@@ -1117,11 +1181,8 @@ extern "C" void seir_sampler_destroy(seir_sampler *s) {
     if (s->ev_copy) (void)hipEventDestroy(s->ev_copy);
     for (void *p : s->allocs) (void)hipFree(p);
     for (void *p : s->snap) if (p) (void)hipFree(p);
-    for (void *p : s->sum_snap) if (p) (void)hipFree(p);
-    for (void *p : s->diag_snap) if (p) (void)hipFree(p);
     for (void *p : s->fc_allocs) (void)hipFree(p);
-    for (void *p : s->fc_snap) if (p) (void)hipFree(p);
-    if (s->fc_acc) (void)hipFree(s->fc_acc);
+    acc_free(s->sum_acc); acc_free(s->diag_buf); acc_free(s->fc_acc);
     if (s->fc_steps_host) (void)hipHostFree(s->fc_steps_host);
     if (s->fc_ev_steps) (void)hipEventDestroy(s->fc_ev_steps);
     Work &w = s->ctx->w;
@@ -1229,19 +1290,18 @@ extern "C" int seir_sampler_create(seir_ctx *ctx, const seir_sampler_desc *ds, s
     Work &w = ctx->w;
     const size_t cells = (size_t)ctx->Bmax * d.Mp * d.Tp;
     Chains &ch = s->ch;
-#define S_ALLOC(ptr, n) if (!rc) rc = s_alloc(s, &(ptr), (n))
-#define S_STATE(ptr, n) if (!rc) rc = s_alloc(s, &(ptr), (n), seir_sampler::R_STATE)
-#define S_HAND(ptr, n) if (!rc) rc = s_alloc(s, &(ptr), (n), seir_sampler::R_HANDOFF)
+#define S_STATE(ptr, n) S_ALLOC(allocs, ptr, (n), seir_sampler::R_STATE)
+#define S_HAND(ptr, n) S_ALLOC(allocs, ptr, (n), seir_sampler::R_HANDOFF)
     for (int x = 0; x < 3; ++x) { S_STATE(w.K[x], cells); S_STATE(w.St[x], cells); }
     S_STATE(w.rowtot, (size_t)ctx->Bmax * 2 * d.Mp);
     S_STATE(w.rngtot, (size_t)ctx->Bmax * 2 * d.Mp);
-    S_ALLOC(w.TS, (size_t)ctx->Bmax * d.nmt * d.ntc * 4);
-    S_ALLOC(w.Lpart0, (size_t)ctx->Bmax * d.nmt * d.ntc);
+    S_ALLOC(allocs, w.TS, (size_t)ctx->Bmax * d.nmt * d.ntc * 4);
+    S_ALLOC(allocs, w.Lpart0, (size_t)ctx->Bmax * d.nmt * d.ntc);
     S_STATE(w.sp, (size_t)ctx->Bmax * 2 * d.Mp);
     S_STATE(w.gst, (size_t)ctx->Bmax * 2 * GST_N);
     S_STATE(w.Vt, (size_t)ctx->Bmax * d.Tp);
     S_STATE(w.acur, (size_t)ctx->Bmax * d.Tp);
-    S_ALLOC(w.rirc, (size_t)ctx->Bmax * 2 * d.Tp);
+    S_ALLOC(allocs, w.rirc, (size_t)ctx->Bmax * 2 * d.Tp);
     S_STATE(w.CT, (size_t)ctx->Bmax * 2 * CT_MAXC * 4);
     S_STATE(w.CG, (size_t)ctx->Bmax * 2 * CT_MAXC * 2);
     S_STATE(ch.q, (size_t)B * d.Pp); S_STATE(ch.p, (size_t)B * d.Pp); S_STATE(ch.q0, (size_t)B * d.Pp);
@@ -1266,7 +1326,7 @@ extern "C" int seir_sampler_create(seir_ctx *ctx, const seir_sampler_desc *ds, s
     S_HAND(ch.llmv, (size_t)2 * B * 32);
     S_HAND(ch.k0part, (size_t)B * ROLE_SLOTS);
     S_HAND(ch.irl0, (size_t)B);
-    S_ALLOC(ch.leap_st, (size_t)(B + 2) * 16 * 8 + 4096);
+    S_ALLOC(allocs, ch.leap_st, (size_t)(B + 2) * 16 * 8 + 4096);
     S_HAND(ch.done, (size_t)B * 2 * TAIL_STRIDE);
     S_HAND(ch.pbar, (size_t)B * PBAR_STRIDE);
     S_HAND(ch.finpart, (size_t)B * ROLE_SLOTS * 4);
@@ -1278,16 +1338,16 @@ extern "C" int seir_sampler_create(seir_ctx *ctx, const seir_sampler_desc *ds, s
     S_HAND(ch.llD, (size_t)2 * B * c.nrb_d * 2);           // (band workgroups per chain <= nrb_d: plan_sweep)
     S_HAND(ch.Down, (size_t)2 * 2 * B * 2);
     S_STATE(ch.sweep, (size_t)B); S_STATE(ch.slot0, 1);
-    S_ALLOC(ch.tr_theta, (size_t)c.cap * B * d.P);
+    S_ALLOC(allocs, ch.tr_theta, (size_t)c.cap * B * d.P);
     {
         char *tre = nullptr;                               // bytes: int32 or uint16 per count
-        S_ALLOC(tre, s->record_events ? (size_t)c.cap * B * d.M * d.T * 3 * (c.ev16 ? 2 : 4) : 4);
+        S_ALLOC(allocs, tre, s->record_events ? (size_t)c.cap * B * d.M * d.T * 3 * (c.ev16 ? 2 : 4) : 4);
         ch.tr_events = tre;
     }
-    S_ALLOC(ch.ev_overflow, 1);
-    S_ALLOC(ch.tr_hmc, (size_t)c.cap * B * 3);
-    S_ALLOC(ch.tr_mv, (size_t)c.cap * B * 4 * NMVTR);
-    S_ALLOC(s->ev_stage, (size_t)B * d.M * d.T * 3);
+    S_ALLOC(allocs, ch.ev_overflow, 1);
+    S_ALLOC(allocs, ch.tr_hmc, (size_t)c.cap * B * 3);
+    S_ALLOC(allocs, ch.tr_mv, (size_t)c.cap * B * 4 * NMVTR);
+    S_ALLOC(allocs, s->ev_stage, (size_t)B * d.M * d.T * 3);
 #undef S_STATE
 #undef S_HAND
     if (!rc) {
@@ -1302,7 +1362,6 @@ extern "C" int seir_sampler_create(seir_ctx *ctx, const seir_sampler_desc *ds, s
         st_(w.Kir, Bm * d.Tp * sizeof(double)); st_(w.Dir, Bm * d.Tp * sizeof(double));
         st_(w.constsum, Bm * sizeof(double));
     }
-#undef S_ALLOC
     if (!rc) {
         std::vector<double> ones((size_t)B * d.Pp, 1.0), hs((size_t)B * NHS, 0.0);
         for (int b = 0; b < B; ++b) hs[(size_t)b * NHS + HS_EPS] = 0.1;     // inference.py:325
@@ -1402,62 +1461,29 @@ extern "C" int seir_sampler_debug_fail_handoff(seir_sampler *s, int32_t chain) {
     return 0;
 }
 
-// While summaries are enabled a snapshot also holds the moment accumulators, count and the overflow flag (device copies in
-// stream order), so that a burst can be folded as soon as it is enqueued and a burst that is run again after a hand-off
-// time-out is not counted twice.  A snapshot taken before summaries were enabled holds none: restoring it leaves them alone.
+// While a feature is enabled a snapshot also holds its accumulators (device copies in stream order), so that a burst can
+// be folded as soon as it is enqueued and a burst that is run again after a hand-off time-out is not counted twice: the
+// moments, count and flag of the summaries; with them the diagnostics' batch sums and marks (a mark taken in a burst that is
+// thrown away goes with it); the forecast's moments and its draw counter.
 static size_t summary_cells(const seir_sampler *s) { return (size_t)s->cfg.B * s->ctx->d.M * s->ctx->d.T * seir::SUMMARY_Q; }
 static size_t diag_words(const seir_sampler *s) { return 6 * summary_cells(s) + 3 * (size_t)s->cfg.B; }
 static uint64_t *diag_mark(const seir_sampler *s, int which) {       // count [B] | sum [n] | sumsq [n]
     const size_t n = summary_cells(s), B = (size_t)s->cfg.B;
-    return s->diag_buf + 2 * n + B + (size_t)which * (B + 2 * n);
+    return (uint64_t *)s->diag_buf.p + 2 * n + B + (size_t)which * (B + 2 * n);
 }
-// The batch accumulators and the marks travel with a snapshot as the moments do: a burst that is run again is counted
-// once, and a mark taken in a burst that is thrown away goes with it.
-static int diag_shadow(seir_sampler *s, int slot, bool save) {
-    if (!s->diag_on) return 0;
-    if (!save && !s->diag_snap_valid[slot]) return 0;
-    const size_t bytes = diag_words(s) * sizeof(uint64_t);
-    if (!s->diag_snap[slot]) HIP_TRY(hipMalloc(&s->diag_snap[slot], bytes));
-    HIP_TRY(hipMemcpyAsync(save ? s->diag_snap[slot] : (void *)s->diag_buf, save ? (void *)s->diag_buf : s->diag_snap[slot], bytes,
-                           hipMemcpyDeviceToDevice, s->ctx->stream));
-    if (save) s->diag_snap_valid[slot] = true;
-    return 0;
-}
-
-static int summary_shadow(seir_sampler *s, int slot, bool save) {
-    if (!s->sum_on) return 0;
-    if (int rc = diag_shadow(s, slot, save)) return rc;
-    if (!save && !s->sum_snap_valid[slot]) return 0;
-    const size_t n = summary_cells(s), B = (size_t)s->cfg.B;
-    struct Part { void *p; size_t bytes; } parts[5] = {{s->sum.ref, n * sizeof(int32_t)}, {s->sum.sum, n * sizeof(int64_t)},
-                                                       {s->sum.sumsq, n * sizeof(uint64_t)}, {s->sum.count, B * sizeof(uint64_t)},
-                                                       {s->sum.overflow, sizeof(unsigned)}};
-    if (!s->sum_snap[slot]) {
-        size_t total = 0;
-        for (const Part &q : parts) total += (q.bytes + 255) / 256 * 256;
-        HIP_TRY(hipMalloc(&s->sum_snap[slot], total));
+static int moments_shadow(seir_sampler *s, int slot, bool save) {
+    hipStream_t st = s->ctx->stream;
+    int rc = 0;
+    if (s->sum_on) {
+        if (s->diag_on) rc = acc_shadow(s->diag_buf, slot, save, st);
+        if (!rc) rc = acc_shadow(s->sum_acc, slot, save, st);
     }
-    size_t off = 0;
-    for (const Part &q : parts) {
-        char *shadow = (char *)s->sum_snap[slot] + off;
-        HIP_TRY(hipMemcpyAsync(save ? (void *)shadow : q.p, save ? q.p : (void *)shadow, q.bytes, hipMemcpyDeviceToDevice,
-                               s->ctx->stream));
-        off += (q.bytes + 255) / 256 * 256;
+    if (!rc && s->fc_on) {
+        if (save) s->fc_snap_j[slot] = s->fc_j;
+        else if (s->fc_acc.valid[slot]) s->fc_j = s->fc_snap_j[slot];
+        rc = acc_shadow(s->fc_acc, slot, save, st);
     }
-    if (save) s->sum_snap_valid[slot] = true;
-    return 0;
-}
-
-// The forecast accumulators, count, flag and the draw counter travel with a snapshot in the same way.
-static int forecast_shadow(seir_sampler *s, int slot, bool save) {
-    if (!s->fc_on) return 0;
-    if (!save && !s->fc_snap_valid[slot]) return 0;
-    if (!s->fc_snap[slot]) HIP_TRY(hipMalloc(&s->fc_snap[slot], s->fc_acc_bytes));
-    HIP_TRY(hipMemcpyAsync(save ? s->fc_snap[slot] : s->fc_acc, save ? s->fc_acc : s->fc_snap[slot], s->fc_acc_bytes,
-                           hipMemcpyDeviceToDevice, s->ctx->stream));
-    if (save) { s->fc_snap_j[slot] = s->fc_j; s->fc_snap_valid[slot] = true; }
-    else s->fc_j = s->fc_snap_j[slot];
-    return 0;
+    return rc;
 }
 
 extern "C" int seir_sampler_snapshot(seir_sampler *s, int32_t slot) {
@@ -1478,8 +1504,7 @@ extern "C" int seir_sampler_snapshot(seir_sampler *s, int32_t slot) {
             off += (r.bytes + 255) / 256 * 256;
         }
     s->snap_valid[slot] = true;
-    if ((rc = forecast_shadow(s, slot, true))) return rc;
-    return summary_shadow(s, slot, true);
+    return moments_shadow(s, slot, true);
 }
 
 extern "C" int seir_sampler_restore(seir_sampler *s, int32_t slot) {
@@ -1499,8 +1524,7 @@ extern "C" int seir_sampler_restore(seir_sampler *s, int32_t slot) {
             off += (r.bytes + 255) / 256 * 256;
         }
     if ((rc = reset_handoffs(s))) return rc;
-    if ((rc = summary_shadow(s, slot, false))) return rc;
-    if ((rc = forecast_shadow(s, slot, false))) return rc;
+    if ((rc = moments_shadow(s, slot, false))) return rc;
     s->vt_dirty = true;                              // Work::Vt came back with the snapshot, the flag did not
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
@@ -2036,16 +2060,35 @@ static int check_ev_overflow(seir_sampler *s) {
     return 0;
 }
 
-extern "C" int seir_sampler_read_trace(seir_sampler *s, int32_t first, int32_t count, double *theta,
-                                       void *events, double *hmc, double *moves) {
-    int rc = sampler_check(s);
-    if (rc) return rc;
+// What every reader of recorded events refuses first.  verb: what the caller wanted the events for (null: just to read them).
+static int need_events(const seir_sampler *s, const char *verb) {
+    if (s->record_events) return 0;
+    if (!verb) return fail(SEIR_ERR_STATE, "sampler was created with record_events=0");
+    return fail(SEIR_ERR_STATE, "sampler was created with record_events=0: there are no recorded events to %s", verb);
+}
+
+// Enqueue fn(copy stream) behind everything queued on the context stream so far (the burst); what is queued there afterwards
+// overlaps it.  seir_sampler_trace_wait completes it.
+template <typename F>
+static int on_copy_stream(seir_sampler *s, F fn) {
+    HIP_TRY(hipEventRecord(s->ev_burst, s->ctx->stream));
+    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_burst, 0));
+    if (int rc = fn(s->copy_stream)) return rc;
+    HIP_TRY(hipEventRecord(s->ev_copy, s->copy_stream));
+    s->copy_pending = true;
+    return 0;
+}
+
+static int read_trace_check(seir_sampler *s, int32_t first, int32_t count, const void *events) {
+    if (first < 0 || count < 0 || first + count > s->cfg.cap)
+        return fail(SEIR_ERR_INVALID, "trace range [%d,%d) outside capacity %d", first, first + count, s->cfg.cap);
+    return events ? need_events(s, nullptr) : 0;
+}
+
+static int copy_trace(seir_sampler *s, hipStream_t st, int32_t first, int32_t count, double *theta, void *events, double *hmc,
+                      double *moves) {
     const Dims &d = s->ctx->d;
     const SamplerCfg &c = s->cfg;
-    if (first < 0 || count < 0 || first + count > c.cap)
-        return fail(SEIR_ERR_INVALID, "trace range [%d,%d) outside capacity %d", first, first + count, c.cap);
-    if (events && !s->record_events) return fail(SEIR_ERR_STATE, "sampler was created with record_events=0");
-    hipStream_t st = s->ctx->stream;
     const size_t B = c.B;
     if (theta)
         HIP_TRY(hipMemcpyAsync(theta, s->ch.tr_theta + (size_t)first * B * d.P, sizeof(double) * count * B * d.P,
@@ -2059,7 +2102,16 @@ extern "C" int seir_sampler_read_trace(seir_sampler *s, int32_t first, int32_t c
     if (moves)
         HIP_TRY(hipMemcpyAsync(moves, s->ch.tr_mv + (size_t)first * B * 4 * NMVTR,
                                sizeof(double) * count * B * 4 * NMVTR, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int seir_sampler_read_trace(seir_sampler *s, int32_t first, int32_t count, double *theta,
+                                       void *events, double *hmc, double *moves) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = read_trace_check(s, first, count, events))) return rc;
+    if ((rc = copy_trace(s, s->ctx->stream, first, count, theta, events, hmc, moves))) return rc;
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
     return check_ev_overflow(s);
 }
 
@@ -2067,32 +2119,8 @@ extern "C" int seir_sampler_read_trace_async(seir_sampler *s, int32_t first, int
                                              void *events, double *hmc, double *moves) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    const Dims &d = s->ctx->d;
-    const SamplerCfg &c = s->cfg;
-    if (first < 0 || count < 0 || first + count > c.cap)
-        return fail(SEIR_ERR_INVALID, "trace range [%d,%d) outside capacity %d", first, first + count, c.cap);
-    if (events && !s->record_events) return fail(SEIR_ERR_STATE, "sampler was created with record_events=0");
-    // the copies start when everything queued on the context stream so far (the burst) is done; what is
-    // queued there afterwards overlaps them
-    HIP_TRY(hipEventRecord(s->ev_burst, s->ctx->stream));
-    hipStream_t st = s->copy_stream;
-    HIP_TRY(hipStreamWaitEvent(st, s->ev_burst, 0));
-    const size_t B = c.B;
-    if (theta)
-        HIP_TRY(hipMemcpyAsync(theta, s->ch.tr_theta + (size_t)first * B * d.P, sizeof(double) * count * B * d.P,
-                               hipMemcpyDeviceToHost, st));
-    if (events)
-        HIP_TRY(hipMemcpyAsync(events, (const char *)s->ch.tr_events + (size_t)first * B * d.M * d.T * 3 * (c.ev16 ? 2 : 4),
-                               (size_t)(c.ev16 ? 2 : 4) * count * B * d.M * d.T * 3, hipMemcpyDeviceToHost, st));
-    if (hmc)
-        HIP_TRY(hipMemcpyAsync(hmc, s->ch.tr_hmc + (size_t)first * B * 3, sizeof(double) * count * B * 3,
-                               hipMemcpyDeviceToHost, st));
-    if (moves)
-        HIP_TRY(hipMemcpyAsync(moves, s->ch.tr_mv + (size_t)first * B * 4 * NMVTR,
-                               sizeof(double) * count * B * 4 * NMVTR, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(s->ev_copy, st));
-    s->copy_pending = true;
-    return 0;
+    if ((rc = read_trace_check(s, first, count, events))) return rc;
+    return on_copy_stream(s, [&](hipStream_t st) { return copy_trace(s, st, first, count, theta, events, hmc, moves); });
 }
 
 extern "C" int seir_sampler_trace_wait(seir_sampler *s) {
@@ -2109,52 +2137,75 @@ extern "C" int seir_sampler_trace_wait(seir_sampler *s) {
 // ---------------------------------------------------------------------------
 // Summaries of the recorded events (include/seir_hip.h; kernels: summary_kernels.h)
 // ---------------------------------------------------------------------------
-extern "C" int seir_sampler_summary_reset(seir_sampler *s) {
-    int rc = sampler_check(s);
-    if (rc) return rc;
-    if (!s->record_events) return fail(SEIR_ERR_STATE, "sampler was created with record_events=0: there are no recorded events to summarise");
-    const Dims &d = s->ctx->d;
-    const size_t n = summary_cells(s), B = (size_t)s->cfg.B, cap = (size_t)s->cfg.cap;
-    SummaryBufs &sb = s->sum;
-    if (!s->sum_on) {
-#define S_ALLOC(ptr, n_) if (!rc) rc = s_alloc(s, &(ptr), (n_))
-        S_ALLOC(sb.ref, n); S_ALLOC(sb.sum, n); S_ALLOC(sb.sumsq, n);
-        S_ALLOC(sb.count, B); S_ALLOC(sb.overflow, 1);
-        S_ALLOC(sb.ebd, cap * B * d.T * 3); S_ALLOC(sb.ebl, cap * B * d.M * 3); S_ALLOC(sb.sbd, cap * B * d.T * 3);
-#undef S_ALLOC
-        if (rc) return rc;
-        s->sum_on = true;
-    }
-    hipStream_t st = s->ctx->stream;
-    HIP_TRY(hipMemsetAsync(sb.ref, 0, n * sizeof(int32_t), st));
-    HIP_TRY(hipMemsetAsync(sb.sum, 0, n * sizeof(int64_t), st));
-    HIP_TRY(hipMemsetAsync(sb.sumsq, 0, n * sizeof(uint64_t), st));
-    HIP_TRY(hipMemsetAsync(sb.count, 0, B * sizeof(uint64_t), st));
-    HIP_TRY(hipMemsetAsync(sb.overflow, 0, sizeof(unsigned), st));
-    // the batch sums are about the same ref and the marks are copies of these accumulators: they start again with them
-    if (s->diag_on) HIP_TRY(hipMemsetAsync(s->diag_buf, 0, diag_words(s) * sizeof(uint64_t), st));
-    return 0;
-}
+// The two users of a trace range that have to be enabled first: what they do with the recorded events, and their refusal.
+struct TraceUser { const char *verb, *not_enabled; };
+static const TraceUser SUMMARY_USER = {"summarise", "summaries are not enabled: call seir_sampler_summary_reset first"};
+static const TraceUser FORECAST_USER = {"forecast from", "the forecast is not enabled: call seir_sampler_forecast_reset first"};
 
-static int summary_range_check(seir_sampler *s, int32_t first, int32_t count) {
-    if (!s->record_events) return fail(SEIR_ERR_STATE, "sampler was created with record_events=0: there are no recorded events to summarise");
-    if (!s->sum_on) return fail(SEIR_ERR_STATE, "summaries are not enabled: call seir_sampler_summary_reset first");
+static int trace_range_check(seir_sampler *s, bool enabled, const TraceUser &what, int32_t first = 0, int32_t count = 0) {
+    if (int rc = need_events(s, what.verb)) return rc;
+    if (!enabled) return fail(SEIR_ERR_STATE, "%s", what.not_enabled);
     if (first < 0 || count < 0 || (long long)first + count > s->cfg.cap)
         return fail(SEIR_ERR_INVALID, "trace range [%d,%lld) outside capacity %d", first, (long long)first + count, s->cfg.cap);
     return 0;
 }
 
+// The per-draw marginals of a MomentBufs as the readers see them: day_extent is T (summaries) or H (forecast).
+struct Marginals { const int64_t *by_day, *by_loc, *state_by_day; size_t day_extent; };
+static Marginals marginals(const MomentBufs &mb, int day_extent) { return {mb.by_day, mb.by_loc, mb.state_by_day, (size_t)day_extent}; }
+
+static int copy_marginals(seir_sampler *s, hipStream_t st, int32_t first, int32_t count, const Marginals &m, int64_t *by_day,
+                          int64_t *by_loc, int64_t *state_by_day) {
+    const size_t B = s->cfg.B, f = (size_t)first, n = (size_t)count, M = (size_t)s->ctx->d.M, E = m.day_extent;
+    if (by_day) HIP_TRY(hipMemcpyAsync(by_day, m.by_day + f * B * E * 3, sizeof(int64_t) * n * B * E * 3, hipMemcpyDeviceToHost, st));
+    if (by_loc) HIP_TRY(hipMemcpyAsync(by_loc, m.by_loc + f * B * M * 3, sizeof(int64_t) * n * B * M * 3, hipMemcpyDeviceToHost, st));
+    if (state_by_day)
+        HIP_TRY(hipMemcpyAsync(state_by_day, m.state_by_day + f * B * E * 3, sizeof(int64_t) * n * B * E * 3, hipMemcpyDeviceToHost, st));
+    return 0;
+}
+static int read_marginals(seir_sampler *s, bool async, int32_t first, int32_t count, const Marginals &m, int64_t *by_day,
+                          int64_t *by_loc, int64_t *state_by_day) {
+    if (async)   // as seir_sampler_read_trace_async
+        return on_copy_stream(s, [&](hipStream_t st) { return copy_marginals(s, st, first, count, m, by_day, by_loc, state_by_day); });
+    if (int rc = copy_marginals(s, s->ctx->stream, first, count, m, by_day, by_loc, state_by_day)) return rc;
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    return check_ev_overflow(s);
+}
+
+// ---------------------------------------------------------------------------
+// Summaries of the recorded events (include/seir_hip.h; kernels: summary_kernels.h)
+// ---------------------------------------------------------------------------
+extern "C" int seir_sampler_summary_reset(seir_sampler *s) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = need_events(s, SUMMARY_USER.verb))) return rc;
+    const Dims &d = s->ctx->d;
+    const size_t B = (size_t)s->cfg.B, cap = (size_t)s->cfg.cap;
+    MomentBufs &sb = s->sum;
+    if (!s->sum_on) {
+        S_ALLOC(allocs, sb.by_day, cap * B * d.T * 3); S_ALLOC(allocs, sb.by_loc, cap * B * d.M * 3);
+        S_ALLOC(allocs, sb.state_by_day, cap * B * d.T * 3);
+        if (!rc) rc = acc_alloc(s->sum_acc, summary_cells(s), B, sb);
+        if (rc) return rc;
+        s->sum_on = true;
+    }
+    hipStream_t st = s->ctx->stream;
+    if ((rc = acc_zero(s->sum_acc, st))) return rc;
+    // the batch sums are about the same ref and the marks are copies of these accumulators: they start again with them
+    return s->diag_on ? acc_zero(s->diag_buf, st) : 0;
+}
+
 extern "C" int seir_sampler_summarize(seir_sampler *s, int32_t first, int32_t count, int32_t accumulate) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    if ((rc = summary_range_check(s, first, count))) return rc;
+    if ((rc = trace_range_check(s, s->sum_on, SUMMARY_USER, first, count))) return rc;
     if (count == 0) return 0;
     seir_ctx *ctx = s->ctx;
     const LaunchCfg l = whole(ctx, s->cfg.B);
     const Dims &d = l.d;
     const int B = s->cfg.B;
     // events_by_day is summed with atomics: zero the call's slots first
-    HIP_TRY(hipMemsetAsync(s->sum.ebd + (size_t)first * B * d.T * 3, 0, sizeof(int64_t) * count * B * d.T * 3, l.st));
+    HIP_TRY(hipMemsetAsync(s->sum.by_day + (size_t)first * B * d.T * 3, 0, sizeof(int64_t) * count * B * d.T * 3, l.st));
     for (int j0 = 0; j0 < count; j0 += SUM_JMAX) {
         const int nj = std::min(SUM_JMAX, count - j0);
         const dim3 grid((d.M + SUM_ROWS - 1) / SUM_ROWS, B), block(64 * SUM_ROWS);
@@ -2179,60 +2230,39 @@ extern "C" int seir_sampler_summarize(seir_sampler *s, int32_t first, int32_t co
     return 0;
 }
 
-static int summary_copy_marginals(seir_sampler *s, hipStream_t st, int32_t first, int32_t count, int64_t *events_by_day,
-                                  int64_t *events_by_location, int64_t *state_by_day) {
-    const Dims &d = s->ctx->d;
-    const size_t B = s->cfg.B, f = (size_t)first, n = (size_t)count;
-    if (events_by_day)
-        HIP_TRY(hipMemcpyAsync(events_by_day, s->sum.ebd + f * B * d.T * 3, sizeof(int64_t) * n * B * d.T * 3, hipMemcpyDeviceToHost, st));
-    if (events_by_location)
-        HIP_TRY(hipMemcpyAsync(events_by_location, s->sum.ebl + f * B * d.M * 3, sizeof(int64_t) * n * B * d.M * 3, hipMemcpyDeviceToHost, st));
-    if (state_by_day)
-        HIP_TRY(hipMemcpyAsync(state_by_day, s->sum.sbd + f * B * d.T * 3, sizeof(int64_t) * n * B * d.T * 3, hipMemcpyDeviceToHost, st));
-    return 0;
-}
-
 extern "C" int seir_sampler_read_marginals(seir_sampler *s, int32_t first, int32_t count, int64_t *events_by_day,
                                            int64_t *events_by_location, int64_t *state_by_day) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    if ((rc = summary_range_check(s, first, count))) return rc;
-    if ((rc = summary_copy_marginals(s, s->ctx->stream, first, count, events_by_day, events_by_location, state_by_day))) return rc;
-    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
-    return check_ev_overflow(s);
+    if ((rc = trace_range_check(s, s->sum_on, SUMMARY_USER, first, count))) return rc;
+    return read_marginals(s, false, first, count, marginals(s->sum, s->ctx->d.T), events_by_day, events_by_location, state_by_day);
 }
 
 extern "C" int seir_sampler_read_marginals_async(seir_sampler *s, int32_t first, int32_t count, int64_t *events_by_day,
                                                  int64_t *events_by_location, int64_t *state_by_day) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    if ((rc = summary_range_check(s, first, count))) return rc;
-    // as seir_sampler_read_trace_async: behind everything queued on the context stream so far, on the copy stream
-    HIP_TRY(hipEventRecord(s->ev_burst, s->ctx->stream));
-    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_burst, 0));
-    if ((rc = summary_copy_marginals(s, s->copy_stream, first, count, events_by_day, events_by_location, state_by_day))) return rc;
-    HIP_TRY(hipEventRecord(s->ev_copy, s->copy_stream));
-    s->copy_pending = true;
+    if ((rc = trace_range_check(s, s->sum_on, SUMMARY_USER, first, count))) return rc;
+    return read_marginals(s, true, first, count, marginals(s->sum, s->ctx->d.T), events_by_day, events_by_location, state_by_day);
+}
+
+// Blocking read of a set of moments; `whose` and `reset` word the refusal when an accumulator has overflowed.
+static int read_moments(seir_sampler *s, const MomentAcc &a, const char *whose, const char *reset, uint64_t *count, int32_t *ref,
+                        int64_t *sum, uint64_t *sumsq) {
+    unsigned flag = 0;
+    int rc = acc_read(a, s->ctx->stream, count, ref, sum, sumsq, &flag);
+    if (!rc) rc = check_ev_overflow(s);
+    if (rc) return rc;
+    if (flag) return fail(SEIR_ERR_STATE, "a sum of squared deviations reached 2^63: the %smoment accumulators overflowed "
+                          "(%s starts them again)", whose, reset);
     return 0;
 }
 
 extern "C" int seir_sampler_read_summary(seir_sampler *s, uint64_t *count, int32_t *ref, int64_t *sum, uint64_t *sumsq) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    if ((rc = summary_range_check(s, 0, 0))) return rc;
-    hipStream_t st = s->ctx->stream;
-    const size_t n = summary_cells(s);
-    unsigned flag = 0;
-    HIP_TRY(hipMemcpyAsync(&flag, s->sum.overflow, sizeof(flag), hipMemcpyDeviceToHost, st));
-    if (count) HIP_TRY(hipMemcpyAsync(count, s->sum.count, sizeof(uint64_t) * s->cfg.B, hipMemcpyDeviceToHost, st));
-    if (ref) HIP_TRY(hipMemcpyAsync(ref, s->sum.ref, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-    if (sum) HIP_TRY(hipMemcpyAsync(sum, s->sum.sum, sizeof(int64_t) * n, hipMemcpyDeviceToHost, st));
-    if (sumsq) HIP_TRY(hipMemcpyAsync(sumsq, s->sum.sumsq, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if ((rc = check_ev_overflow(s))) return rc;
-    if (flag) return fail(SEIR_ERR_STATE, "a sum of squared deviations reached 2^63: the moment accumulators overflowed "
-                          "(seir_sampler_summary_reset starts them again)");
-    return 0;
+    if ((rc = trace_range_check(s, s->sum_on, SUMMARY_USER))) return rc;
+    return read_moments(s, s->sum_acc, "", "seir_sampler_summary_reset", count, ref, sum, sumsq);
 }
 
 // ---------------------------------------------------------------------------
@@ -2242,24 +2272,25 @@ extern "C" int seir_sampler_diag_reset(seir_sampler *s, int32_t batch_len) {
     int rc = sampler_check(s);
     if (rc) return rc;
     if (batch_len < 1) return fail(SEIR_ERR_INVALID, "batch_len=%d: a batch has at least one draw", batch_len);
-    if (!s->record_events) return fail(SEIR_ERR_STATE, "sampler was created with record_events=0: there are no recorded events to diagnose");
+    if ((rc = need_events(s, "diagnose"))) return rc;
     if (!s->diag_on) {
-        if ((rc = s_alloc(s, &s->diag_buf, diag_words(s)))) return rc;
+        if ((rc = acc_alloc(s->diag_buf, diag_words(s) * sizeof(uint64_t)))) return rc;
         const size_t n = summary_cells(s);
-        s->diag.bsum = reinterpret_cast<int64_t *>(s->diag_buf);
-        s->diag.bsumsq = s->diag_buf + n;
-        s->diag.nbatch = s->diag_buf + 2 * n;
+        s->diag.bsum = (int64_t *)s->diag_buf.p;
+        s->diag.bsumsq = (uint64_t *)s->diag_buf.p + n;
+        s->diag.nbatch = s->diag.bsumsq + n;
         s->diag_on = true;
     }
     s->diag.L = (uint64_t)batch_len;
     // a snapshot taken before this reset holds batch sums cut by another L (which is no part of it): restoring it from now
     // on leaves the moments, the batch sums and the marks alone, as a snapshot from before the summaries were enabled does
-    for (int slot = 0; slot < 2; ++slot) s->sum_snap_valid[slot] = s->diag_snap_valid[slot] = false;
+    acc_invalidate(s->sum_acc);
+    acc_invalidate(s->diag_buf);
     return seir_sampler_summary_reset(s);            // zeroes the batch sums and the marks with the moments
 }
 
 static int diag_check(seir_sampler *s, int32_t which) {
-    if (!s->record_events) return fail(SEIR_ERR_STATE, "sampler was created with record_events=0: there are no recorded events to diagnose");
+    if (int rc = need_events(s, "diagnose")) return rc;
     if (!s->diag_on) return fail(SEIR_ERR_STATE, "diagnostics are not enabled: call seir_sampler_diag_reset first");
     if (which < 0 || which > 1) return fail(SEIR_ERR_INVALID, "mark %d: marks are numbered 0 and 1", which);
     return 0;
@@ -2320,24 +2351,11 @@ extern "C" int seir_sampler_read_diag_mark(seir_sampler *s, int32_t which, uint6
 // ---------------------------------------------------------------------------
 // Forecast on the device (include/seir_hip.h; kernels: forecast_kernels.h)
 // ---------------------------------------------------------------------------
-static size_t forecast_cells(const seir_sampler *s, int H) { return (size_t)s->cfg.B * s->ctx->d.M * H * seir::SUMMARY_Q; }
-
-template <typename T>
-static int fc_alloc(seir_sampler *s, T **p, size_t count) {
-    void *q = nullptr;
-    const size_t bytes = (count ? count : 1) * sizeof(T);
-    HIP_TRY(hipMalloc(&q, bytes));
-    s->fc_allocs.push_back(q);
-    HIP_TRY(hipMemset(q, 0, bytes));
-    *p = (T *)q;
-    return 0;
-}
-
 extern "C" int seir_sampler_forecast_reset(seir_sampler *s, int32_t horizon, const double *W, const double *weekday_c,
                                            uint64_t seed) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    if (!s->record_events) return fail(SEIR_ERR_STATE, "sampler was created with record_events=0: there are no recorded events to forecast from");
+    if ((rc = need_events(s, FORECAST_USER.verb))) return rc;
     if (horizon < 1 || horizon > SEIR_FORECAST_MAX_H)
         return fail(SEIR_ERR_INVALID, "horizon=%d outside [1, %d]", horizon, SEIR_FORECAST_MAX_H);
     if (!W || !weekday_c) return fail(SEIR_ERR_INVALID, "null calendar pointer");
@@ -2350,41 +2368,31 @@ extern "C" int seir_sampler_forecast_reset(seir_sampler *s, int32_t horizon, con
                     FC_MAX_CHAIN);
     hipStream_t st = s->ctx->stream;
     ForecastBufs &fb = s->fc;
-    const size_t n = forecast_cells(s, H), cap = (size_t)s->cfg.cap;
+    const size_t cap = (size_t)s->cfg.cap;
     if (!s->fc_on || fb.H != H) {
         // first reset, or another horizon: everything is sized by H
         HIP_TRY(hipStreamSynchronize(st));
         if (s->copy_pending) { (void)hipEventSynchronize(s->ev_copy); s->copy_pending = false; }
         for (void *p : s->fc_allocs) (void)hipFree(p);
         s->fc_allocs.clear();
-        if (s->fc_acc) { (void)hipFree(s->fc_acc); s->fc_acc = nullptr; }
+        acc_free(s->fc_acc);
         if (s->fc_steps_host) { (void)hipHostFree(s->fc_steps_host); s->fc_steps_host = nullptr; }
-        for (int k = 0; k < 2; ++k) {
-            if (s->fc_snap[k]) { (void)hipFree(s->fc_snap[k]); s->fc_snap[k] = nullptr; }
-            s->fc_snap_valid[k] = false;
-        }
         s->fc_on = false;
         fb = ForecastBufs{};
         s->fc_slots = std::min(s->cfg.cap, FC_JMAX);
         s->fc_ndmax = ceil_to(s->fc_slots * B, 64);
         const size_t plane = (size_t)d.Mp * s->fc_ndmax, ndm = (size_t)s->fc_slots * B;
         double *Wd = nullptr, *wdd = nullptr;
-#define F_ALLOC(ptr, n_) if (!rc) rc = fc_alloc(s, &(ptr), (n_))
-        F_ALLOC(Wd, H); F_ALLOC(wdd, H);
-        F_ALLOC(fb.St0, 3 * plane); F_ALLOC(fb.St, 3 * plane); F_ALLOC(fb.X, plane); F_ALLOC(fb.F, plane); F_ALLOC(fb.eb, plane);
-        F_ALLOC(fb.sc, 3 * (size_t)s->fc_ndmax); F_ALLOC(fb.base, (size_t)H * s->fc_ndmax);
-        F_ALLOC(fb.fev, ndm * d.M * H * 3); F_ALLOC(s->fc_steps_dev, ndm * H);
-        F_ALLOC(fb.fbd, cap * B * H * 3); F_ALLOC(fb.fbl, cap * B * d.M * 3); F_ALLOC(fb.fsbd, cap * B * H * 3);
-#undef F_ALLOC
+        S_ALLOC(fc_allocs, Wd, H); S_ALLOC(fc_allocs, wdd, H);
+        S_ALLOC(fc_allocs, fb.St0, 3 * plane); S_ALLOC(fc_allocs, fb.St, 3 * plane);
+        S_ALLOC(fc_allocs, fb.X, plane); S_ALLOC(fc_allocs, fb.F, plane); S_ALLOC(fc_allocs, fb.eb, plane);
+        S_ALLOC(fc_allocs, fb.sc, 3 * (size_t)s->fc_ndmax); S_ALLOC(fc_allocs, fb.base, (size_t)H * s->fc_ndmax);
+        S_ALLOC(fc_allocs, fb.fev, ndm * d.M * H * 3); S_ALLOC(fc_allocs, s->fc_steps_dev, ndm * H);
+        S_ALLOC(fc_allocs, fb.mom.by_day, cap * B * H * 3); S_ALLOC(fc_allocs, fb.mom.by_loc, cap * B * d.M * 3);
+        S_ALLOC(fc_allocs, fb.mom.state_by_day, cap * B * H * 3);
+        if (!rc) rc = acc_alloc(s->fc_acc, (size_t)B * d.M * H * seir::SUMMARY_Q, (size_t)B, fb.mom);
         if (rc) return rc;
         fb.W = Wd; fb.wd = wdd;
-        s->fc_acc_bytes = n * (sizeof(int64_t) + sizeof(uint64_t) + sizeof(int32_t)) + (size_t)B * sizeof(uint64_t) + 8;
-        HIP_TRY(hipMalloc(&s->fc_acc, s->fc_acc_bytes));
-        fb.sum = (int64_t *)s->fc_acc;
-        fb.sumsq = (uint64_t *)(fb.sum + n);
-        fb.count = fb.sumsq + n;
-        fb.ref = (int32_t *)(fb.count + B);
-        fb.overflow = (unsigned *)(fb.ref + n);
         fb.H = H;
         if (!s->fc_ev_steps) HIP_TRY(hipEventCreate(&s->fc_ev_steps));
         (void)hipFuncSetAttribute((const void *)k_gemm<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_lds_bytes<64>());
@@ -2394,27 +2402,19 @@ extern "C" int seir_sampler_forecast_reset(seir_sampler *s, int32_t horizon, con
     // the caller's arrays are not retained: blocking copies behind what is queued (a reset is not on the hot path)
     HIP_TRY(hipMemcpyAsync(const_cast<double *>(fb.W), W, sizeof(double) * H, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(const_cast<double *>(fb.wd), weekday_c, sizeof(double) * H, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(s->fc_acc, 0, s->fc_acc_bytes, st));
+    if ((rc = acc_zero(s->fc_acc, st))) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     s->fc_j = 0;
     // what the snapshots taken before this reset hold of the forecast is dropped with it: restoring one of them restores
     // the chain and leaves the forecast accumulators and j as they are
-    s->fc_snap_valid[0] = s->fc_snap_valid[1] = false;
-    return 0;
-}
-
-static int forecast_range_check(seir_sampler *s, int32_t first, int32_t count) {
-    if (!s->record_events) return fail(SEIR_ERR_STATE, "sampler was created with record_events=0: there are no recorded events to forecast from");
-    if (!s->fc_on) return fail(SEIR_ERR_STATE, "the forecast is not enabled: call seir_sampler_forecast_reset first");
-    if (first < 0 || count < 0 || (long long)first + count > s->cfg.cap)
-        return fail(SEIR_ERR_INVALID, "trace range [%d,%lld) outside capacity %d", first, (long long)first + count, s->cfg.cap);
+    acc_invalidate(s->fc_acc);
     return 0;
 }
 
 extern "C" int seir_sampler_forecast(seir_sampler *s, int32_t first, int32_t count, const double *log_baseline_steps) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    if ((rc = forecast_range_check(s, first, count))) return rc;
+    if ((rc = trace_range_check(s, s->fc_on, FORECAST_USER, first, count))) return rc;
     if (count == 0) return 0;
     if (s->fc_j + count > (1ll << FC_ID_SHIFT))
         return fail(SEIR_ERR_INVALID, "%lld draws per chain forecast since the reset and %d more: the draw id holds 2^%d", s->fc_j,
@@ -2431,7 +2431,7 @@ extern "C" int seir_sampler_forecast(seir_sampler *s, int32_t first, int32_t cou
         std::memcpy(s->fc_steps_host + (size_t)first * B * H, log_baseline_steps, sizeof(double) * count * B * H);
     }
     // forecast_by_day is summed with atomics: zero the call's slots first
-    HIP_TRY(hipMemsetAsync(s->fc.fbd + (size_t)first * B * H * 3, 0, sizeof(int64_t) * count * B * H * 3, l.st));
+    HIP_TRY(hipMemsetAsync(s->fc.mom.by_day + (size_t)first * B * H * 3, 0, sizeof(int64_t) * count * B * H * 3, l.st));
     Dims gd = d;                                     // the contraction's view: one "chain", the draw index as the day index
     gd.b0 = 0;
     Work gw{};
@@ -2469,28 +2469,13 @@ extern "C" int seir_sampler_forecast(seir_sampler *s, int32_t first, int32_t cou
     return 0;
 }
 
-static int forecast_copy_marginals(seir_sampler *s, hipStream_t st, int32_t first, int32_t count, int64_t *by_day,
-                                   int64_t *by_location, int64_t *state_by_day) {
-    const Dims &d = s->ctx->d;
-    const size_t B = s->cfg.B, f = (size_t)first, n = (size_t)count, H = (size_t)s->fc.H;
-    if (by_day)
-        HIP_TRY(hipMemcpyAsync(by_day, s->fc.fbd + f * B * H * 3, sizeof(int64_t) * n * B * H * 3, hipMemcpyDeviceToHost, st));
-    if (by_location)
-        HIP_TRY(hipMemcpyAsync(by_location, s->fc.fbl + f * B * d.M * 3, sizeof(int64_t) * n * B * d.M * 3, hipMemcpyDeviceToHost, st));
-    if (state_by_day)
-        HIP_TRY(hipMemcpyAsync(state_by_day, s->fc.fsbd + f * B * H * 3, sizeof(int64_t) * n * B * H * 3, hipMemcpyDeviceToHost, st));
-    return 0;
-}
-
 extern "C" int seir_sampler_read_forecast_marginals(seir_sampler *s, int32_t first, int32_t count, int64_t *forecast_by_day,
                                                     int64_t *forecast_by_location, int64_t *forecast_state_by_day) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    if ((rc = forecast_range_check(s, first, count))) return rc;
-    if ((rc = forecast_copy_marginals(s, s->ctx->stream, first, count, forecast_by_day, forecast_by_location, forecast_state_by_day)))
-        return rc;
-    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
-    return check_ev_overflow(s);
+    if ((rc = trace_range_check(s, s->fc_on, FORECAST_USER, first, count))) return rc;
+    return read_marginals(s, false, first, count, marginals(s->fc.mom, s->fc.H), forecast_by_day, forecast_by_location,
+                          forecast_state_by_day);
 }
 
 extern "C" int seir_sampler_read_forecast_marginals_async(seir_sampler *s, int32_t first, int32_t count,
@@ -2498,33 +2483,16 @@ extern "C" int seir_sampler_read_forecast_marginals_async(seir_sampler *s, int32
                                                           int64_t *forecast_state_by_day) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    if ((rc = forecast_range_check(s, first, count))) return rc;
-    HIP_TRY(hipEventRecord(s->ev_burst, s->ctx->stream));
-    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_burst, 0));
-    if ((rc = forecast_copy_marginals(s, s->copy_stream, first, count, forecast_by_day, forecast_by_location, forecast_state_by_day)))
-        return rc;
-    HIP_TRY(hipEventRecord(s->ev_copy, s->copy_stream));
-    s->copy_pending = true;
-    return 0;
+    if ((rc = trace_range_check(s, s->fc_on, FORECAST_USER, first, count))) return rc;
+    return read_marginals(s, true, first, count, marginals(s->fc.mom, s->fc.H), forecast_by_day, forecast_by_location,
+                          forecast_state_by_day);
 }
 
 extern "C" int seir_sampler_read_forecast(seir_sampler *s, uint64_t *count, int32_t *ref, int64_t *sum, uint64_t *sumsq) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    if ((rc = forecast_range_check(s, 0, 0))) return rc;
-    hipStream_t st = s->ctx->stream;
-    const size_t n = forecast_cells(s, s->fc.H);
-    unsigned flag = 0;
-    HIP_TRY(hipMemcpyAsync(&flag, s->fc.overflow, sizeof(flag), hipMemcpyDeviceToHost, st));
-    if (count) HIP_TRY(hipMemcpyAsync(count, s->fc.count, sizeof(uint64_t) * s->cfg.B, hipMemcpyDeviceToHost, st));
-    if (ref) HIP_TRY(hipMemcpyAsync(ref, s->fc.ref, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-    if (sum) HIP_TRY(hipMemcpyAsync(sum, s->fc.sum, sizeof(int64_t) * n, hipMemcpyDeviceToHost, st));
-    if (sumsq) HIP_TRY(hipMemcpyAsync(sumsq, s->fc.sumsq, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if ((rc = check_ev_overflow(s))) return rc;
-    if (flag) return fail(SEIR_ERR_STATE, "a sum of squared deviations reached 2^63: the forecast's moment accumulators overflowed "
-                          "(seir_sampler_forecast_reset starts them again)");
-    return 0;
+    if ((rc = trace_range_check(s, s->fc_on, FORECAST_USER))) return rc;
+    return read_moments(s, s->fc_acc, "forecast's ", "seir_sampler_forecast_reset", count, ref, sum, sumsq);
 }
 
 extern "C" int seir_host_alloc(void **p, uint64_t bytes) {

@@ -2,6 +2,9 @@
 // samples/seir on the device"): per-cell moments of the event counts and of the state over the kept draws, and per-draw
 // marginals (events by day, events by location, state by day).  The definitions are summary_update.h's.
 //
+// The accumulators are a MomentBufs, the one type the summaries, the diagnostics and the forecast (forecast_kernels.h)
+// accumulate into; the forecast's fold and finish are built from the pieces and the finish body below.
+//
 // k_summarize<EV16> reads trace slots [first, first + count) of all chains once.  The shape of the work:
 //   - a WAVE owns a row m of a chain and walks its 64-day chunks, a lane per day; a workgroup is SUM_ROWS such waves on
 //     neighbouring rows.  The state is a prefix over days: inside a chunk a DPP wave scan per transition, from chunk to
@@ -40,15 +43,17 @@ constexpr int SUM_JB = 16;         // draws per flush of the by-day tile (24 KiB
 constexpr int SUM_JMAX = 128;      // draws per launch (12 KiB of carries)
 constexpr int SUM_U = 4;           // draws whose loads are in flight together
 
-struct SummaryBufs {
-    int32_t *ref;                  // [B][M][T][6]
-    int64_t *sum;                  // [B][M][T][6]
-    uint64_t *sumsq;               // [B][M][T][6]
+// One set of moment accumulators and per-draw marginals over a day axis of extent E: E = T for the recorded events
+// (summaries, diagnostics), E = H for the forecast.  The host's MomentAcc owns ref .. overflow as one allocation.
+struct MomentBufs {
+    int32_t *ref;                  // [B][M][E][6]
+    int64_t *sum;                  // [B][M][E][6]
+    uint64_t *sumsq;               // [B][M][E][6]
     uint64_t *count;               // [B] draws folded since the last reset
     unsigned *overflow;            // [1] sticky: some sumsq reached 2^63
-    int64_t *ebd;                  // [cap][B][T][3] events_by_day
-    int64_t *ebl;                  // [cap][B][M][3] events_by_location
-    int64_t *sbd;                  // [cap][B][T][3] state_by_day
+    int64_t *by_day;               // [cap][B][E][3] events by day
+    int64_t *by_loc;               // [cap][B][M][3] events by location
+    int64_t *state_by_day;         // [cap][B][E][3]
 };
 
 // the batch accumulators of the diagnostics; the DIAG = 0 instances of k_summarize get the empty one
@@ -76,9 +81,53 @@ __device__ __forceinline__ void summary_load(const void *__restrict__ tr, size_t
     }
 }
 
+// The pieces of the fold that k_summarize and k_forecast_fold (forecast_kernels.h) share.  Pieces, and not one body templated
+// on where the draws come from: as ONE inlined function the loop nest takes 81 VGPRs in k_summarize<0,0> and k_forecast_fold
+// where it takes 73 and 69 in the kernels, a wave or two of occupancy.  These four leave the machine code of all five kernels
+// what it was; the carry scan, the store of the accumulators and the row totals as functions do not (the same registers, other
+// code, and one-chain calls 0.2 to 1 % slower), so those stay written out in both kernels, with the loop nest (DESIGN.md,
+// "One accumulator, three users").
+
+// The six quantities of a cell: the day's counts, and the state before them from the initial state s0 and the prefix.
+__device__ __forceinline__ void fold_values(const int (&k)[3], const int (&s0)[3], const int (&ex)[3], int (&val)[SUMMARY_Q]) {
+    val[0] = k[0]; val[1] = k[1]; val[2] = k[2];
+    val[3] = s0[0] - ex[0]; val[4] = s0[1] + ex[0] - ex[1]; val[5] = s0[2] + ex[1] - ex[2];
+}
+
+// The workgroup's by-day tile, into which the lanes have added their counts with 64-bit LDS atomics: its nj draws onto
+// by_day [cap][B][E][3] from slot0, days from t0 -- one global atomic per entry that is not zero, which is zero again
+// afterwards.  Between two __syncthreads of the caller.
+__device__ __forceinline__ void fold_tile_flush(unsigned long long (&bd)[SUM_JB][64][3], int nj, int64_t *by_day, int slot0, int B,
+                                                int b, int E, int t0) {
+    for (int i = threadIdx.x; i < nj * 64 * 3; i += 64 * SUM_ROWS) {
+        const unsigned long long v = (&bd[0][0][0])[i];
+        const int jj = i / 192, r = i - jj * 192, tl = r / 3, x = r - tl * 3;
+        if (v != 0ull) {
+            (&bd[0][0][0])[i] = 0ull;
+            atomicAdd(reinterpret_cast<unsigned long long *>(by_day) + (((size_t)(slot0 + jj) * B + b) * E + (t0 + tl)) * 3 + x, v);
+        }
+    }
+}
+
+// Zero the workgroup's by-day tile and the wave's carries of `count` draws.  Before a __syncthreads of the caller.
+__device__ __forceinline__ void fold_lds_zero(unsigned long long (&bd)[SUM_JB][64][3], int (&carry)[SUM_JMAX][3], int count, int lane) {
+    for (int i = lane; i < count * 3; i += 64) (&carry[0][0])[i] = 0;
+    for (int i = threadIdx.x; i < SUM_JB * 64 * 3; i += 64 * SUM_ROWS) (&bd[0][0][0])[i] = 0ull;
+}
+
+// A cell's six (ref, sum, sumsq) triples into registers.
+__device__ __forceinline__ void fold_load(const MomentBufs &sb, size_t cell, int32_t (&ref)[SUMMARY_Q], int64_t (&sm)[SUMMARY_Q],
+                                          uint64_t (&sq)[SUMMARY_Q]) {
+#pragma unroll
+    for (int q = 0; q < SUMMARY_Q; ++q) {
+        ref[q] = sb.ref[cell * SUMMARY_Q + q];
+        sm[q] = sb.sum[cell * SUMMARY_Q + q];
+        sq[q] = sb.sumsq[cell * SUMMARY_Q + q];
+    }
+}
 // grid (ceil(M / SUM_ROWS), B), 64 SUM_ROWS threads.  1 <= count <= SUM_JMAX, first + count <= cap (the host checks).
 template <int EV16, int DIAG = 0>
-__global__ __launch_bounds__(64 * SUM_ROWS) void k_summarize(Dims d, Consts c, SummaryBufs sb,
+__global__ __launch_bounds__(64 * SUM_ROWS) void k_summarize(Dims d, Consts c, MomentBufs sb,
                                                              const void *__restrict__ tr_events, int B, int first,
                                                              int count, int accumulate, SummaryDiag<DIAG> dg) {
     debug_skew(d);
@@ -99,8 +148,7 @@ __global__ __launch_bounds__(64 * SUM_ROWS) void k_summarize(Dims d, Consts c, S
     if (row_ok)
 #pragma unroll
         for (int x = 0; x < 3; ++x) s0[x] = (int)c.init[(size_t)m * 4 + x];
-    for (int i = lane; i < count * 3; i += 64) (&carry[wv][0][0])[i] = 0;
-    for (int i = threadIdx.x; i < SUM_JB * 64 * 3; i += 64 * SUM_ROWS) (&bd[0][0][0])[i] = 0ull;
+    fold_lds_zero(bd, carry[wv], count, lane);
     __syncthreads();
 
     const size_t draw_cells = (size_t)B * M * T;      // cells of one trace slot
@@ -121,12 +169,7 @@ __global__ __launch_bounds__(64 * SUM_ROWS) void k_summarize(Dims d, Consts c, S
             for (int q = 0; q < seir::SUMMARY_Q; ++q) { bs[q] = 0; bq[q] = 0; }
         }
         if (fold && live && !fresh) {
-#pragma unroll
-            for (int q = 0; q < seir::SUMMARY_Q; ++q) {
-                ref[q] = sb.ref[cell * seir::SUMMARY_Q + q];
-                sm[q] = sb.sum[cell * seir::SUMMARY_Q + q];
-                sq[q] = sb.sumsq[cell * seir::SUMMARY_Q + q];
-            }
+            fold_load(sb, cell, ref, sm, sq);
             if constexpr (DIAG) {
 #pragma unroll
                 for (int q = 0; q < seir::SUMMARY_Q; ++q) {
@@ -162,8 +205,8 @@ __global__ __launch_bounds__(64 * SUM_ROWS) void k_summarize(Dims d, Consts c, S
                         for (int x = 0; x < 3; ++x)
                             if (kk[u][x] != 0) atomicAdd(&bd[jj][lane][x], (unsigned long long)kk[u][x]);
                         if (fold) {
-                            const int val[seir::SUMMARY_Q] = {kk[u][0], kk[u][1], kk[u][2], s0[0] - ex[0],
-                                                              s0[1] + ex[0] - ex[1], s0[2] + ex[1] - ex[2]};
+                            int val[seir::SUMMARY_Q];
+                            fold_values(kk[u], s0, ex, val);
                             const bool is_first = fresh && j == 0;
 #pragma unroll
                             for (int q = 0; q < seir::SUMMARY_Q; ++q)
@@ -182,16 +225,7 @@ __global__ __launch_bounds__(64 * SUM_ROWS) void k_summarize(Dims d, Consts c, S
                 }
             }
             __syncthreads();
-            // the workgroup's part of events_by_day for these draws and days: one atomic per entry that is not zero
-            for (int i = threadIdx.x; i < nj * 64 * 3; i += 64 * SUM_ROWS) {
-                const unsigned long long v = (&bd[0][0][0])[i];
-                const int jj = i / 192, r = i - jj * 192, tl = r / 3, x = r - tl * 3;
-                if (v != 0ull) {
-                    (&bd[0][0][0])[i] = 0ull;
-                    atomicAdd(reinterpret_cast<unsigned long long *>(sb.ebd) +
-                                  (((size_t)(first + jb + jj) * B + b) * T + (t0 + tl)) * 3 + x, v);
-                }
-            }
+            fold_tile_flush(bd, nj, sb.by_day, first + jb, B, b, T, t0);
             __syncthreads();
         }
         if (fold && live) {
@@ -216,30 +250,32 @@ __global__ __launch_bounds__(64 * SUM_ROWS) void k_summarize(Dims d, Consts c, S
     if (row_ok)
         for (int i = lane; i < count * 3; i += 64) {
             const int j = i / 3, x = i - j * 3;
-            sb.ebl[(((size_t)(first + j) * B + b) * M + m) * 3 + x] = (int64_t)carry[wv][j][x];
+            sb.by_loc[(((size_t)(first + j) * B + b) * M + m) * 3 + x] = (int64_t)carry[wv][j][x];
         }
     if (ovf) sb.overflow[0] = 1u;
 }
 
-// state_by_day from the finished events_by_day, and count[b] += count when the draws were folded.  grid (count, B), one wave.
-__global__ __launch_bounds__(64) void k_summary_finish(Dims d, Consts c, SummaryBufs sb, int B, int first, int count,
-                                                       int accumulate) {
-    const int lane = threadIdx.x, b = blockIdx.y, slot = first + blockIdx.x;
+// state_by_day from the finished by_day of trace slot `slot` and count[b] += count when the draws were folded: the body of
+// k_summary_finish and k_forecast_finish (one wave per draw and chain).  init0(m, x): the draw's initial state in row m.
+template <class Init0>
+__device__ __forceinline__ void moment_finish(const MomentBufs sb, int M, int T, int B, int slot, int count,
+                                              bool accumulate, Init0 init0) {
+    const int lane = threadIdx.x, b = blockIdx.y;
     long long tot0[3] = {0, 0, 0};
-    for (int m = lane; m < d.M; m += 64)
+    for (int m = lane; m < M; m += 64)
 #pragma unroll
-        for (int x = 0; x < 3; ++x) tot0[x] += (long long)c.init[(size_t)m * 4 + x];
+        for (int x = 0; x < 3; ++x) tot0[x] += (long long)init0(m, x);
 #pragma unroll
     for (int x = 0; x < 3; ++x)
         for (int o = 32; o > 0; o >>= 1) tot0[x] += __shfl_xor(tot0[x], o, 64);
     long long cr[3] = {0, 0, 0};
-    const size_t base = ((size_t)slot * B + b) * d.T;
-    for (int t0 = 0; t0 < d.T; t0 += 64) {
+    const size_t base = ((size_t)slot * B + b) * T;
+    for (int t0 = 0; t0 < T; t0 += 64) {
         const int t = t0 + lane;
         long long ex[3];
 #pragma unroll
         for (int x = 0; x < 3; ++x) {
-            const long long v = t < d.T ? sb.ebd[(base + t) * 3 + x] : 0ll;
+            const long long v = t < T ? sb.by_day[(base + t) * 3 + x] : 0ll;
             long long inc = v;
             for (int o = 1; o < 64; o <<= 1) {
                 const long long up = __shfl_up(inc, o, 64);
@@ -248,13 +284,20 @@ __global__ __launch_bounds__(64) void k_summary_finish(Dims d, Consts c, Summary
             ex[x] = cr[x] + inc - v;
             cr[x] += __shfl(inc, 63, 64);
         }
-        if (t < d.T) {
-            sb.sbd[(base + t) * 3 + 0] = tot0[0] - ex[0];
-            sb.sbd[(base + t) * 3 + 1] = tot0[1] + ex[0] - ex[1];
-            sb.sbd[(base + t) * 3 + 2] = tot0[2] + ex[1] - ex[2];
+        if (t < T) {
+            sb.state_by_day[(base + t) * 3 + 0] = tot0[0] - ex[0];
+            sb.state_by_day[(base + t) * 3 + 1] = tot0[1] + ex[0] - ex[1];
+            sb.state_by_day[(base + t) * 3 + 2] = tot0[2] + ex[1] - ex[2];
         }
     }
     if (accumulate && blockIdx.x == 0 && lane == 0) sb.count[b] += (uint64_t)count;
+}
+
+// grid (count, B), one wave.
+__global__ __launch_bounds__(64) void k_summary_finish(Dims d, Consts c, MomentBufs sb, int B, int first, int count,
+                                                       int accumulate) {
+    moment_finish(sb, d.M, d.T, B, first + blockIdx.x, count, accumulate != 0,
+                  [&](int m, int x) { return c.init[(size_t)m * 4 + x]; });
 }
 
 }  // namespace seir

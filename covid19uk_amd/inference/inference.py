@@ -194,15 +194,19 @@ class Posterior:
         else:
             self._extra[name] = data
 
+    def _write_moments(self, group, mean, var):
+        """<group>/seir_mean, seir_var (k_se, k_ei, k_ir) and state_mean, state_var (S, E, I) from [M,days,6] rows."""
+        self.create_dataset(f"{group}/seir_mean", np.ascontiguousarray(mean[..., :3]))
+        self.create_dataset(f"{group}/seir_var", np.ascontiguousarray(var[..., :3]))
+        self.create_dataset(f"{group}/state_mean", np.ascontiguousarray(mean[..., 3:]))
+        self.create_dataset(f"{group}/state_var", np.ascontiguousarray(var[..., 3:]))
+
     def write_summary(self, count, mean, var):
         """The moments of one chain over the sampling phase (`Summary.mean` / `.var` rows, [M,T,6] float64):
         summaries/count [1], summaries/seir_mean, seir_var (k_se, k_ei, k_ir) and state_mean, state_var (S, E, I),
         each [M,T,3]."""
         self.create_dataset("summaries/count", np.array([float(count)]))
-        self.create_dataset("summaries/seir_mean", np.ascontiguousarray(mean[..., :3]))
-        self.create_dataset("summaries/seir_var", np.ascontiguousarray(var[..., :3]))
-        self.create_dataset("summaries/state_mean", np.ascontiguousarray(mean[..., 3:]))
-        self.create_dataset("summaries/state_var", np.ascontiguousarray(var[..., 3:]))
+        self._write_moments("summaries", mean, var)
 
     def write_forecast(self, horizon, first_day, count, mean, var):
         """The group forecast/ of one chain: horizon [1], first_day [1] (= T, the absolute day of forecast day 0),
@@ -211,10 +215,7 @@ class Posterior:
         self.create_dataset("forecast/horizon", np.array([float(horizon)]))
         self.create_dataset("forecast/first_day", np.array([float(first_day)]))
         self.create_dataset("forecast/count", np.array([float(count)]))
-        self.create_dataset("forecast/seir_mean", np.ascontiguousarray(mean[..., :3]))
-        self.create_dataset("forecast/seir_var", np.ascontiguousarray(var[..., :3]))
-        self.create_dataset("forecast/state_mean", np.ascontiguousarray(mean[..., 3:]))
-        self.create_dataset("forecast/state_var", np.ascontiguousarray(var[..., 3:]))
+        self._write_moments("forecast", mean, var)
 
     def write_diagnostics(self, datasets: dict):
         """The group diagnostics/ of one chain (`posterior.diagnostics.chain_datasets`), float64."""

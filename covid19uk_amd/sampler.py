@@ -430,36 +430,40 @@ class ChainSampler:
         written, and with `accumulate` the draws are folded into the moments."""
         _lib.check(self._lib.seir_sampler_summarize(self._s, int(first), int(count), int(bool(accumulate))))
 
-    def _marg_ptrs(self, m):
-        return [m[k].ctypes.data_as(_lib.c_int64_p) for k in MARGINAL_KEYS]
+    def _read_marginal_set(self, fn, keys, days, count, first, into=None):
+        """The three per-draw marginals `keys` (by day, by location, state by day; `days` = T or H) of trace slots
+        [first, first+count) through the reader `fn`: into fresh arrays (blocking `fn`), or into the pinned arrays `into`
+        (asynchronous `fn`, completed by `trace_wait()`)."""
+        n = int(count)
+        if into is None:
+            into = {k: np.empty((n, self.B, e, 3), np.int64) for k, e in zip(keys, (days, self.M, days))}
+        _lib.check(fn(self._s, int(first), n, *(into[k].ctypes.data_as(_lib.c_int64_p) for k in keys)))
+        return into
+
+    def _read_moments(self, fn, days) -> Summary:
+        """(count, ref, sum, sumsq) over [B,M,days,6] through the blocking reader `fn`."""
+        shape = (self.B, self.M, days, len(SUMMARY_QUANTITIES))
+        cnt = np.zeros(self.B, np.uint64)
+        ref, sm, sq = np.empty(shape, np.int32), np.empty(shape, np.int64), np.empty(shape, np.uint64)
+        _lib.check(fn(self._s, cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ref.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                      sm.ctypes.data_as(_lib.c_int64_p), sq.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        return Summary(count=cnt, ref=ref, sum=sm, sumsq=sq)
 
     def read_marginals(self, count: int, first: int = 0) -> dict:
         """Blocking read of the marginals of trace slots [first, first+count): MARGINAL_KEYS -> int64 arrays with
         leading axes [count, B]."""
-        n = int(count)
-        m = dict(events_by_day=np.empty((n, self.B, self.T, 3), np.int64),
-                 events_by_location=np.empty((n, self.B, self.M, 3), np.int64),
-                 state_by_day=np.empty((n, self.B, self.T, 3), np.int64))
-        _lib.check(self._lib.seir_sampler_read_marginals(self._s, int(first), n, *self._marg_ptrs(m)))
-        return m
+        return self._read_marginal_set(self._lib.seir_sampler_read_marginals, MARGINAL_KEYS, self.T, count, first)
 
     def read_marginals_async(self, count: int, first: int, into: PinnedTrace):
         """As `read_trace_async`, for the marginals; completed by `trace_wait()`."""
         if int(count) > into.count or into.marginals is None:
             raise ValueError("pinned buffer too small or without marginals")
-        _lib.check(self._lib.seir_sampler_read_marginals_async(self._s, int(first), int(count),
-                                                               *self._marg_ptrs(into.marginals)))
+        self._read_marginal_set(self._lib.seir_sampler_read_marginals_async, MARGINAL_KEYS, self.T, count, first, into.marginals)
 
     def summary(self) -> Summary:
         """The moments folded since the last `reset_summary` (blocking).  Raises `SeirError` (SEIR_ERR_STATE) if an
         accumulator overflowed."""
-        shape = (self.B, self.M, self.T, len(SUMMARY_QUANTITIES))
-        cnt = np.zeros(self.B, np.uint64)
-        ref, sm, sq = np.empty(shape, np.int32), np.empty(shape, np.int64), np.empty(shape, np.uint64)
-        _lib.check(self._lib.seir_sampler_read_summary(
-            self._s, cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ref.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-            sm.ctypes.data_as(_lib.c_int64_p), sq.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
-        return Summary(count=cnt, ref=ref, sum=sm, sumsq=sq)
+        return self._read_moments(self._lib.seir_sampler_read_summary, self.T)
 
     # -- convergence diagnostics: batch sums and marks next to the moments (include/seir_hip.h) -----------
     def reset_diagnostics(self, batch_len: int):
@@ -521,36 +525,22 @@ class ChainSampler:
         _lib.check(self._lib.seir_sampler_forecast(self._s, int(first), n, None if steps is None else _dptr(steps)))
         self._fc_j += n
 
-    def _fc_ptrs(self, m):
-        return [m[k].ctypes.data_as(_lib.c_int64_p) for k in FORECAST_KEYS]
-
     def read_forecast_marginals(self, count: int, first: int = 0) -> dict:
         """Blocking read of the forecast marginals of trace slots [first, first+count): FORECAST_KEYS -> int64 arrays with
         leading axes [count, B]."""
-        n, H = int(count), self._forecast_H
-        m = dict(forecast_by_day=np.empty((n, self.B, H, 3), np.int64),
-                 forecast_by_location=np.empty((n, self.B, self.M, 3), np.int64),
-                 forecast_state_by_day=np.empty((n, self.B, H, 3), np.int64))
-        _lib.check(self._lib.seir_sampler_read_forecast_marginals(self._s, int(first), n, *self._fc_ptrs(m)))
-        return m
+        return self._read_marginal_set(self._lib.seir_sampler_read_forecast_marginals, FORECAST_KEYS, self._forecast_H, count, first)
 
     def read_forecast_marginals_async(self, count: int, first: int, into: PinnedTrace):
         """As `read_marginals_async`, for the forecast marginals; completed by `trace_wait()`."""
         if int(count) > into.count or into.forecast is None:
             raise ValueError("pinned buffer too small or without forecast arrays")
-        _lib.check(self._lib.seir_sampler_read_forecast_marginals_async(self._s, int(first), int(count),
-                                                                        *self._fc_ptrs(into.forecast)))
+        self._read_marginal_set(self._lib.seir_sampler_read_forecast_marginals_async, FORECAST_KEYS, self._forecast_H, count,
+                                first, into.forecast)
 
     def forecast_summary(self) -> Summary:
         """The forecast moments folded since the last `reset_forecast` (blocking): a `Summary` whose day axis is the H
         forecast days, [B,M,H,6].  Raises `SeirError` (SEIR_ERR_STATE) if an accumulator overflowed or before a reset."""
-        shape = (self.B, self.M, self._forecast_H, len(SUMMARY_QUANTITIES))
-        cnt = np.zeros(self.B, np.uint64)
-        ref, sm, sq = np.empty(shape, np.int32), np.empty(shape, np.int64), np.empty(shape, np.uint64)
-        _lib.check(self._lib.seir_sampler_read_forecast(
-            self._s, cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ref.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-            sm.ctypes.data_as(_lib.c_int64_p), sq.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
-        return Summary(count=cnt, ref=ref, sum=sm, sumsq=sq)
+        return self._read_moments(self._lib.seir_sampler_read_forecast, self._forecast_H)
 
     def _forecast_burst(self, first, count, forecast):
         """`forecast` of sample / sample_bursts: True (held baseline) or a callable (j0, count) -> steps [count,B,H], j0

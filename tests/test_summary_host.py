@@ -351,3 +351,22 @@ def test_off_creates_todays_datasets_only_leaves_out_the_tensor_and_on_adds_the_
         for k in ("seir_var", "state_var"):
             np.testing.assert_allclose(f[f"summaries/{k}"], np.var(sweeps[w:], ddof=1), rtol=1e-14)
     assert set(MARGINAL_KEYS) == {"events_by_day", "events_by_location", "state_by_day"}
+
+
+# ---- the compiler's account of the kernels that share the fold's pieces and the finish body --------------------------------
+MOMENT_KERNELS = [f"k_summarize<{ev16},{diag}>" for ev16 in (0, 1) for diag in (0, 1)] + \
+    ["k_summary_finish", "k_forecast_fold", "k_forecast_finish"]
+
+
+@pytest.mark.parametrize("kernel", MOMENT_KERNELS)
+def test_the_kernels_built_from_shared_pieces_keep_the_resources_they_had_on_their_own(kernel):
+    """Against the build before the pieces were shared (profiles/r09_kernel_resources.json): scratch, spills and LDS equal,
+    occupancy not lower, and the register count within the few that move with the compiler's mood."""
+    import json
+    entry.build()
+    r = json.load(open(entry.RESOURCES))[kernel]
+    was = json.load(open(os.path.join(ROOT, "profiles", "r09_kernel_resources.json")))[kernel]
+    for k in ("scratch_bytes_per_lane", "vgpr_spill", "sgpr_spill", "lds_bytes_per_block"):
+        assert r[k] == was[k], (kernel, k, r, was)
+    assert r["occupancy_waves_per_simd"] >= was["occupancy_waves_per_simd"], (kernel, r, was)
+    assert r["vgpr"] <= was["vgpr"] + 4, (kernel, r, was)

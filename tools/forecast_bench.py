@@ -38,8 +38,13 @@ def main():
     ap.add_argument("--device-sweeps", type=int, default=300)
     ap.add_argument("--kernels-only", action="store_true", help="one burst and --reps forecast calls, nothing else (for rocprofv3)")
     ap.add_argument("--kernel-stats", default=None, help="a rocprofv3 kernel_stats.csv of a --kernels-only run")
+    ap.add_argument("--lib", default=None, help="load this libseirhip.so in place of the tree's: another build of the same ABI, "
+                    "for an A/B in one call (profiles/r10_ab.txt)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r09_forecast.json"))
     a = ap.parse_args()
+    if a.lib:
+        from covid19uk_amd import _lib
+        _lib.LIB_PATH = os.path.abspath(a.lib)
     import __graft_entry__ as entry
     entry.build()
     import torch
@@ -82,6 +87,7 @@ def main():
             print(f"forecast of {n} x {B} draws, H = {Hn}: {ms:.2f} ms; the burst's sweeps {burst_ms:.1f} ms "
                   f"({ms / burst_ms:.3f})", file=sys.stderr, flush=True)
             if a.kernels_only:
+                print(json.dumps(res))
                 return
             if a.kernel_stats:
                 rows = list(csv.DictReader(open(a.kernel_stats)))

@@ -56,8 +56,14 @@ def main():
     ap.add_argument("--kept-per-burst", default="20,50", help="kept draws per burst end to end, per entry of --chains")
     ap.add_argument("--device-sweeps", type=int, default=400)
     ap.add_argument("--diagnostics", action="store_true", help="add the diagnostics rows (see above)")
+    ap.add_argument("--kernels-only", action="store_true", help="the kernel table alone, not the sampling phase through the file")
+    ap.add_argument("--lib", default=None, help="load this libseirhip.so in place of the tree's: another build of the same ABI, "
+                    "for an A/B in one call (profiles/r10_ab.txt)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r07_summary.json"))
     a = ap.parse_args()
+    if a.lib:
+        from covid19uk_amd import _lib
+        _lib.LIB_PATH = os.path.abspath(a.lib)
     import __graft_entry__ as entry
     entry.build()
     import torch
@@ -143,7 +149,7 @@ def main():
                 row["bytes_of_the_same_call_without"] = row["bytes"] / without["bytes"]
 
     # ---- end to end: the sampling phase through the file --------------------------------------------------------------------
-    for B, ns in zip(chains, kept):
+    for B, ns in [] if a.kernels_only else zip(chains, kept):
         u = synth.jitter_params(u0, B, scale=0.002, seed=7, T=T)
         ev = np.stack([events] * B)
         with SeirModel(cov, init, max_chains=B) as model:
