@@ -14,8 +14,8 @@ def lib():
     global _LIB
     if _LIB is None:
         path = os.path.join(_HERE, "libseir_oracle.so")
-        src = os.path.join(_HERE, "seir_oracle.c")
-        if not os.path.exists(path) or os.path.getmtime(path) < os.path.getmtime(src):
+        srcs = [os.path.join(_HERE, f) for f in ("seir_oracle.c", "mcmc_oracle.c", "sim_oracle.c", "seir_oracle.h")]
+        if not os.path.exists(path) or os.path.getmtime(path) < max(os.path.getmtime(s) for s in srcs):
             subprocess.check_call(["make", "-s", "-C", _HERE])
         h = ctypes.CDLL(path)
         dp = ctypes.POINTER(ctypes.c_double)
@@ -190,3 +190,32 @@ class COracleChain:
         out["theta"] = so.constrain(self.u)
         out["events"] = self.events
         return out
+
+
+# ---------------------------------------------------------------------------------------------
+# The simulator's binomial sampler in C (oracle/sim_oracle.c): oracle/sim_oracle.py's `binomial` with a report
+# ---------------------------------------------------------------------------------------------
+SIM_BRANCHES = ("trivial", "binv", "btrs_squeeze", "btrs_full", "fallback")
+SIM_TRIVIAL, SIM_BINV, SIM_BTRS_SQUEEZE, SIM_BTRS_FULL, SIM_FALLBACK = range(5)
+
+
+def sim_binomial(n, p, draw, cell, stream, seed=0):
+    """Binomial(n_i, p_i) on the substream (draw_i, cell_i, stream_i) of `seed` (arguments broadcast; `stream` is the
+    counter word, 64 + x for the simulator's transition x).
+
+    Returns (variate int32, branch uint8 indexing SIM_BRANCHES, near_tie bool, attempts int32): see oracle/sim_oracle.c."""
+    h = lib()
+    if not getattr(h, "_sim_ready", False):
+        vp = ctypes.c_void_p
+        h.sim_oracle_binomial.restype = None
+        h.sim_oracle_binomial.argtypes = [ctypes.c_int64] + [vp] * 5 + [ctypes.c_uint64] + [vp] * 4
+        h._sim_ready = True
+    n, p, draw, cell, stream = np.broadcast_arrays(n, p, draw, cell, stream)
+    n = np.ascontiguousarray(n, dtype=np.int32).reshape(-1)
+    p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1)
+    draw, cell, stream = (np.ascontiguousarray(a, dtype=np.uint32).reshape(-1) for a in (draw, cell, stream))
+    out, att = np.empty(n.size, np.int32), np.empty(n.size, np.int32)
+    branch, tie = np.empty(n.size, np.uint8), np.empty(n.size, np.uint8)
+    h.sim_oracle_binomial(n.size, n.ctypes.data, p.ctypes.data, draw.ctypes.data, cell.ctypes.data, stream.ctypes.data,
+                          int(seed) & (2 ** 64 - 1), out.ctypes.data, branch.ctypes.data, tie.ctypes.data, att.ctypes.data)
+    return out, branch, tie.astype(bool), att
