@@ -62,7 +62,7 @@ class SeirSimDesc(ctypes.Structure):
 
 
 ABI_VERSION = 4               # SEIR_ABI_VERSION
-OPT_DEBUG_SKEW, OPT_XCD_AFFINITY, OPT_GEMM_F32, OPT_EVAL_FORM = 0, 1, 2, 3
+OPT_DEBUG_SKEW, OPT_XCD_AFFINITY, OPT_GEMM_F32, OPT_EVAL_FORM, OPT_RT_STAGING_KIB = 0, 1, 2, 3, 4
 ERR_INVALID, ERR_STATE = -1, -3   # SEIR_ERR_INVALID, SEIR_ERR_STATE
 ERR_HANDOFF = -4              # SEIR_ERR_HANDOFF
 MMAX = 4                      # SEIR_MMAX
@@ -177,6 +177,13 @@ _SIGNATURES = {
     "seir_sampler_read_forecast": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
                                                   ctypes.POINTER(ctypes.c_int32), c_int64_p,
                                                   ctypes.POINTER(ctypes.c_uint64)]),
+    # reproduction number of the kept draws from the burst buffer: R_it moments and the national curve per draw
+    "seir_sampler_rt_reset": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_double_p]),
+    "seir_sampler_rt": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]),
+    "seir_sampler_read_rt_draws": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, c_double_p]),
+    "seir_sampler_read_rt_draws_async": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, c_double_p]),
+    "seir_sampler_read_rt": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), c_double_p, c_double_p,
+                                            c_double_p, ctypes.POINTER(ctypes.c_uint32)]),
 }
 
 _lib = None

@@ -21,6 +21,7 @@
 #include "sweep_plan.h"
 #include "summary_kernels.h"
 #include "forecast_kernels.h"
+#include "rt_trace_kernels.h"
 
 using namespace seir;
 
@@ -61,6 +62,7 @@ struct seir_ctx {
     bool prepared = false;
     int opt_skew = 0, opt_affinity = 3;     // seir_set_option
     int opt_gemm_f32 = 0;
+    int opt_rt_staging_kib = 0;       // bound on the S plane of a seir_sampler_rt batch in KiB (0: RT_STAGING_BYTES)
     int opt_eval_form = 0;            // 0 auto (one launch where a chain's blocks share an XCD, else three), 1 four launches, 2 three
     int xcd_local = -1;               // -1 not probed yet; 1: blocks with the same id mod 8 share an XCD, eight different ones
     unsigned long long *eval_cnt = nullptr;   // [8][EVC_STRIDE] k_eval_all's counters
@@ -339,6 +341,10 @@ extern "C" int seir_set_option(seir_ctx *ctx, int32_t option, int32_t value) {
         case SEIR_OPT_EVAL_FORM:
             if (value < 0 || value > 2) return fail(SEIR_ERR_INVALID, "eval form is 0 (auto), 1 (four launches) or 2 (three launches)");
             ctx->opt_eval_form = value;
+            return 0;
+        case SEIR_OPT_RT_STAGING_KIB:
+            if (value < 0) return fail(SEIR_ERR_INVALID, "the staging bound is a number of KiB (0: the default)");
+            ctx->opt_rt_staging_kib = value;
             return 0;
         case SEIR_OPT_GEMM_F32: {
             if (value < 0 || value > 1) return fail(SEIR_ERR_INVALID, "gemm_f32 is 0 or 1");
@@ -1144,6 +1150,12 @@ struct seir_sampler {
     double *fc_steps_dev = nullptr;   // [fc_slots * B][H]
     hipEvent_t fc_ev_steps = nullptr; // behind the last upload from fc_steps_host
     bool fc_steps_pending = false;
+    // --- reproduction number of the kept draws (seir_sampler_rt_reset ...; rt_trace_kernels.h) ---
+    bool rt_on = false;
+    RtBufs rt{};
+    int rt_slots = 0;                 // trace slots the batch planes (ea, S, part) are allocated for
+    std::vector<void *> rt_allocs;    // device buffers sized by the window (allocated again when it changes)
+    Shadowed rt_acc;                  // sum [cells] | sumsq [cells] | ref [cells] | count [B, padded] | gt1 [cells]
 };
 
 // Zeroed device memory, registered in `list` (seir_sampler::allocs: freed with the sampler; fc_allocs: also when the horizon
@@ -1182,7 +1194,8 @@ extern "C" void seir_sampler_destroy(seir_sampler *s) {
     for (void *p : s->allocs) (void)hipFree(p);
     for (void *p : s->snap) if (p) (void)hipFree(p);
     for (void *p : s->fc_allocs) (void)hipFree(p);
-    acc_free(s->sum_acc); acc_free(s->diag_buf); acc_free(s->fc_acc);
+    for (void *p : s->rt_allocs) (void)hipFree(p);
+    acc_free(s->sum_acc); acc_free(s->diag_buf); acc_free(s->fc_acc); acc_free(s->rt_acc);
     if (s->fc_steps_host) (void)hipHostFree(s->fc_steps_host);
     if (s->fc_ev_steps) (void)hipEventDestroy(s->fc_ev_steps);
     Work &w = s->ctx->w;
@@ -1464,7 +1477,7 @@ extern "C" int seir_sampler_debug_fail_handoff(seir_sampler *s, int32_t chain) {
 // While a feature is enabled a snapshot also holds its accumulators (device copies in stream order), so that a burst can
 // be folded as soon as it is enqueued and a burst that is run again after a hand-off time-out is not counted twice: the
 // moments, count and flag of the summaries; with them the diagnostics' batch sums and marks (a mark taken in a burst that is
-// thrown away goes with it); the forecast's moments and its draw counter.
+// thrown away goes with it); the forecast's moments and its draw counter; the reproduction number's moments and count.
 static size_t summary_cells(const seir_sampler *s) { return (size_t)s->cfg.B * s->ctx->d.M * s->ctx->d.T * seir::SUMMARY_Q; }
 static size_t diag_words(const seir_sampler *s) { return 6 * summary_cells(s) + 3 * (size_t)s->cfg.B; }
 static uint64_t *diag_mark(const seir_sampler *s, int which) {       // count [B] | sum [n] | sumsq [n]
@@ -1483,6 +1496,7 @@ static int moments_shadow(seir_sampler *s, int slot, bool save) {
         else if (s->fc_acc.valid[slot]) s->fc_j = s->fc_snap_j[slot];
         rc = acc_shadow(s->fc_acc, slot, save, st);
     }
+    if (!rc && s->rt_on) rc = acc_shadow(s->rt_acc, slot, save, st);
     return rc;
 }
 
@@ -2140,6 +2154,8 @@ extern "C" int seir_sampler_trace_wait(seir_sampler *s) {
 // The two users of a trace range that have to be enabled first: what they do with the recorded events, and their refusal.
 struct TraceUser { const char *verb, *not_enabled; };
 static const TraceUser SUMMARY_USER = {"summarise", "summaries are not enabled: call seir_sampler_summary_reset first"};
+static const TraceUser RT_USER = {"form the reproduction number from",
+                                   "the reproduction number is not enabled: call seir_sampler_rt_reset first"};
 static const TraceUser FORECAST_USER = {"forecast from", "the forecast is not enabled: call seir_sampler_forecast_reset first"};
 
 static int trace_range_check(seir_sampler *s, bool enabled, const TraceUser &what, int32_t first = 0, int32_t count = 0) {
@@ -2493,6 +2509,140 @@ extern "C" int seir_sampler_read_forecast(seir_sampler *s, uint64_t *count, int3
     if (rc) return rc;
     if ((rc = trace_range_check(s, s->fc_on, FORECAST_USER))) return rc;
     return read_moments(s, s->fc_acc, "forecast's ", "seir_sampler_forecast_reset", count, ref, sum, sumsq);
+}
+
+// ---------------------------------------------------------------------------
+// Reproduction number on the device (include/seir_hip.h; kernels: rt_trace_kernels.h)
+// ---------------------------------------------------------------------------
+// need_events' refusal as SEIR_ERR_INVALID (a sampler without recorded events is a bad argument to this feature), then
+// trace_range_check's
+static int rt_check(seir_sampler *s, int32_t first = 0, int32_t count = 0) {
+    if (need_events(s, RT_USER.verb)) return SEIR_ERR_INVALID;
+    return trace_range_check(s, s->rt_on, RT_USER, first, count);
+}
+static size_t rt_cells(const seir_sampler *s) { return (size_t)s->cfg.B * s->rt.D * s->ctx->d.M; }
+static size_t rt_count_words(const seir_sampler *s) { return ((size_t)s->cfg.B + 31) / 32 * 32; }
+
+extern "C" int seir_sampler_rt_reset(seir_sampler *s, int32_t days, const double *weight) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if (need_events(s, RT_USER.verb)) return SEIR_ERR_INVALID;
+    const Dims &d = s->ctx->d;
+    if (days < 1 || days > d.T) return fail(SEIR_ERR_INVALID, "days=%d outside [1, T = %d]", days, d.T);
+    if (!weight) return fail(SEIR_ERR_INVALID, "null weight pointer");
+    const int B = s->cfg.B, D = days;
+    hipStream_t st = s->ctx->stream;
+    RtBufs &rb = s->rt;
+    if (!s->rt_on || rb.D != D) {
+        // first reset, or another window: everything is sized by D
+        HIP_TRY(hipStreamSynchronize(st));
+        if (s->copy_pending) { (void)hipEventSynchronize(s->ev_copy); s->copy_pending = false; }
+        for (void *p : s->rt_allocs) (void)hipFree(p);
+        s->rt_allocs.clear();
+        acc_free(s->rt_acc);
+        s->rt_on = false;
+        rb = RtBufs{};
+        rb.D = D; rb.t0 = d.T - D; rb.ncb = (d.M + 63) / 64;
+        // the S plane of a batch is bounded: a call is cut into batches of at most rt_slots trace slots
+        const size_t bound = s->ctx->opt_rt_staging_kib ? (size_t)s->ctx->opt_rt_staging_kib << 10 : RT_STAGING_BYTES;
+        const size_t per_slot = (size_t)B * d.Mp * D * sizeof(int);
+        s->rt_slots = (int)std::max<size_t>(1, std::min<size_t>((size_t)s->cfg.cap, bound / per_slot));
+        const size_t nd = (size_t)s->rt_slots * B;
+        double *wd = nullptr;
+        S_ALLOC(rt_allocs, wd, (size_t)rb.ncb * 64);
+        S_ALLOC(rt_allocs, rb.ea, nd * d.Tp); S_ALLOC(rt_allocs, rb.S, nd * d.Mp * D);
+        S_ALLOC(rt_allocs, rb.part, nd * D * rb.ncb); S_ALLOC(rt_allocs, rb.Rt, (size_t)s->cfg.cap * B * D);
+        rb.weight = wd;
+        const size_t cells = (size_t)B * D * d.M;
+        if (!rc) rc = acc_alloc(s->rt_acc, cells * (3 * sizeof(double) + sizeof(uint32_t)) + rt_count_words(s) * sizeof(uint64_t));
+        if (rc) return rc;
+        rb.sum = (double *)s->rt_acc.p;
+        rb.sumsq = rb.sum + cells;
+        rb.ref = rb.sumsq + cells;
+        rb.count = (uint64_t *)(rb.ref + cells);
+        rb.gt1 = (uint32_t *)(rb.count + rt_count_words(s));
+        const size_t lds = k_rt_trace_lds_bytes<RT_DT>(d.Mp);
+        if (lds > 64 * 1024)
+            (void)hipFuncSetAttribute((const void *)k_rt_trace<RT_DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        s->rt_on = true;
+    }
+    // the caller's array is not retained: a blocking copy behind what is queued (a reset is not on the hot path)
+    HIP_TRY(hipMemcpyAsync(const_cast<double *>(rb.weight), weight, sizeof(double) * d.M, hipMemcpyHostToDevice, st));
+    if ((rc = acc_zero(s->rt_acc, st))) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    // what the snapshots taken before this reset hold of it is dropped: restoring one of them leaves the accumulators alone
+    acc_invalidate(s->rt_acc);
+    return 0;
+}
+
+extern "C" int seir_sampler_rt(seir_sampler *s, int32_t first, int32_t count) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = rt_check(s, first, count))) return rc;
+    if (count == 0) return 0;
+    seir_ctx *ctx = s->ctx;
+    const LaunchCfg l = whole(ctx, s->cfg.B);
+    const Dims &d = l.d;
+    const int B = s->cfg.B, D = s->rt.D;
+    const RtBufs &rb = s->rt;
+    Work tw = ctx->w;                                 // k_rt_tables writes Work::ea: the feature's own buffer, not the sampler's
+    tw.ea = rb.ea;
+    const size_t lds = k_rt_trace_lds_bytes<RT_DT>(d.Mp);
+    for (int j0 = 0; j0 < count; j0 += s->rt_slots) {
+        const int nj = std::min(s->rt_slots, count - j0), ND = nj * B;
+        hipLaunchKernelGGL(k_rt_tables, dim3(ND), dim3(256), 0, l.st, d, tw,
+                           (const double *)s->ch.tr_theta + (size_t)(first + j0) * B * d.P);
+        const dim3 pgrid((d.M + RT_PREP_ROWS - 1) / RT_PREP_ROWS, ND), pblock(64 * RT_PREP_ROWS);
+        if (s->cfg.ev16)
+            hipLaunchKernelGGL(k_rt_prepare<1>, pgrid, pblock, 0, l.st, d, ctx->c, rb, (const void *)s->ch.tr_events, B, first + j0);
+        else
+            hipLaunchKernelGGL(k_rt_prepare<0>, pgrid, pblock, 0, l.st, d, ctx->c, rb, (const void *)s->ch.tr_events, B, first + j0);
+        hipLaunchKernelGGL(k_rt_trace<RT_DT>, dim3(rb.ncb, (D + RT_DT - 1) / RT_DT, B), dim3(256), lds, l.st, d, ctx->c, rb,
+                           (const double *)s->ch.tr_theta, B, first + j0, nj);
+        hipLaunchKernelGGL(k_rt_finish, dim3((unsigned)(((size_t)ND * D + 255) / 256)), dim3(256), 0, l.st, rb, B, first + j0, nj);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+static int copy_rt_draws(seir_sampler *s, hipStream_t st, int32_t first, int32_t count, double *R_t) {
+    const size_t row = (size_t)s->cfg.B * s->rt.D;
+    HIP_TRY(hipMemcpyAsync(R_t, s->rt.Rt + (size_t)first * row, sizeof(double) * count * row, hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+extern "C" int seir_sampler_read_rt_draws(seir_sampler *s, int32_t first, int32_t count, double *R_t) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = rt_check(s, first, count))) return rc;
+    if (!R_t) return fail(SEIR_ERR_INVALID, "null pointer");
+    if ((rc = copy_rt_draws(s, s->ctx->stream, first, count, R_t))) return rc;
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    return check_ev_overflow(s);
+}
+
+extern "C" int seir_sampler_read_rt_draws_async(seir_sampler *s, int32_t first, int32_t count, double *R_t) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = rt_check(s, first, count))) return rc;
+    if (!R_t) return fail(SEIR_ERR_INVALID, "null pointer");
+    return on_copy_stream(s, [&](hipStream_t st) { return copy_rt_draws(s, st, first, count, R_t); });
+}
+
+extern "C" int seir_sampler_read_rt(seir_sampler *s, uint64_t *count, double *ref, double *sum, double *sumsq, uint32_t *gt1) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = rt_check(s))) return rc;
+    hipStream_t st = s->ctx->stream;
+    const size_t n = rt_cells(s);
+    const RtBufs &rb = s->rt;
+    if (count) HIP_TRY(hipMemcpyAsync(count, rb.count, sizeof(uint64_t) * s->cfg.B, hipMemcpyDeviceToHost, st));
+    if (ref) HIP_TRY(hipMemcpyAsync(ref, rb.ref, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    if (sum) HIP_TRY(hipMemcpyAsync(sum, rb.sum, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    if (sumsq) HIP_TRY(hipMemcpyAsync(sumsq, rb.sumsq, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    if (gt1) HIP_TRY(hipMemcpyAsync(gt1, rb.gt1, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return check_ev_overflow(s);
 }
 
 extern "C" int seir_host_alloc(void **p, uint64_t bytes) {

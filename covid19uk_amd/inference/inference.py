@@ -106,7 +106,7 @@ class Posterior:
     `is_accepted` is a bool dataset the way h5py stores one (gemlib's Posterior writes numpy bools through h5py):
     the int8 enum {FALSE = 0, TRUE = 1}."""
 
-    def __init__(self, filename, M, T, mmax, num_samples, burst=100, summaries="off", forecast=None):
+    def __init__(self, filename, M, T, mmax, num_samples, burst=100, summaries="off", forecast=None, rt=None):
         """`summaries` ("off" | "on" | "only", Mcmc.summaries / --summaries): with "on" and "only" the per-draw marginals
         samples/seir_by_day [n,T,3], samples/seir_by_location [n,M,3], samples/state_by_day [n,T,3] (int64) are written
         with every burst and `write_summary` adds summaries/* at the end of the run; with "only" samples/seir is not
@@ -114,7 +114,10 @@ class Posterior:
 
         `forecast` ((H, n) or None, Mcmc.forecast / --forecast): samples/forecast_by_day [n,H,3], forecast_by_location
         [n,M,3], forecast_state_by_day [n,H,3] (int64), one row per kept draw of the sampling phase -- n of them, not
-        num_samples: the warm-up is not forecast -- and `write_forecast` adds the group forecast/ at the end of the run."""
+        num_samples: the warm-up is not forecast -- and `write_forecast` adds the group forecast/ at the end of the run.
+
+        `rt` ((D, n) or None, Mcmc.rt / --rt): samples/R_t [n,D] (float64), the national reproduction number of the last
+        D days, one row per kept draw of the sampling phase, and `write_rt` adds the group rt/ at the end of the run."""
         self.filename = filename
         self.use_h5 = not str(filename).endswith(".npz") and hdf5io.available()
         self.shapes = {
@@ -143,6 +146,8 @@ class Posterior:
             for k, shp in (("samples/forecast_by_day", (H, 3)), ("samples/forecast_by_location", (M, 3)),
                            ("samples/forecast_state_by_day", (H, 3))):
                 self.shapes[k], self.dtypes[k], self.rows[k] = shp, np.int64, n_fc
+        if rt is not None:
+            self.shapes["samples/R_t"], self.rows["samples/R_t"] = (int(rt[0]),), int(rt[1])
         self._scratch = {}
         if self.use_h5:
             self._file = hdf5io.File(filename, "w")
@@ -216,6 +221,16 @@ class Posterior:
         self.create_dataset("forecast/first_day", np.array([float(first_day)]))
         self.create_dataset("forecast/count", np.array([float(count)]))
         self._write_moments("forecast", mean, var)
+
+    def write_rt(self, days, first_day, count, mean, var, prob_gt1):
+        """The group rt/ of one chain: days [1], first_day [1] (= T - D, the absolute day of the window's first day),
+        count [1] and R_it_mean, R_it_var, R_it_prob_gt1 over the draws folded (`RtSummary` rows), each [D,M]."""
+        self.create_dataset("rt/days", np.array([float(days)]))
+        self.create_dataset("rt/first_day", np.array([float(first_day)]))
+        self.create_dataset("rt/count", np.array([float(count)]))
+        self.create_dataset("rt/R_it_mean", np.ascontiguousarray(mean, dtype=np.float64))
+        self.create_dataset("rt/R_it_var", np.ascontiguousarray(var, dtype=np.float64))
+        self.create_dataset("rt/R_it_prob_gt1", np.ascontiguousarray(prob_gt1, dtype=np.float64))
 
     def write_diagnostics(self, datasets: dict):
         """The group diagnostics/ of one chain (`posterior.diagnostics.chain_datasets`), float64."""
@@ -360,6 +375,35 @@ def forecast_mode(config, override=None, walk=None):
     return H, w
 
 
+def rt_mode(config, override=None, T=None):
+    """Mcmc.rt (absent: off), or the command line's `--rt D`: the number of days D of the window [T - D, T) over which the
+    reproduction number of every kept draw of the sampling phase is formed on the device; 0 for off.  1 <= D, and D <= T
+    when the length of the series is given.  The one place that validates -- before a sampler exists."""
+    D = config.get("rt") if override is None else override
+    if D is None or D is False or (isinstance(D, str) and D.lower() == "off"):
+        return 0
+    if isinstance(D, bool) or (not isinstance(D, (int, np.integer)) and not (isinstance(D, str) and D.strip().lstrip("+-").isdigit())):
+        raise ValueError(f"rt={D!r}: the window is a number of days, 1 .. T")
+    D = int(D)
+    if D < 1 or (T is not None and D > int(T)):
+        raise ValueError(f"rt={D}: the window is 1 .. T{'' if T is None else f' = {int(T)}'} days")
+    return D
+
+
+def rt_run_line(days, T, r_t, prob_gt1):
+    """The run's one line about R_t: the national value on the last day (mean and 0.05 / 0.95 quantiles over the per-draw
+    curves `r_t` [n, chains, D]) and the share of locations whose P(R_it > 1) on that day exceeds 0.5 (`prob_gt1`
+    [chains, D, M])."""
+    last = np.asarray(r_t, np.float64)[..., -1].reshape(-1)
+    if last.size == 0:
+        return f"R_t: window of {days} day(s) from day {T - days}, no kept draw"
+    lo, hi = np.quantile(last, [0.05, 0.95])
+    share = float(np.mean(np.asarray(prob_gt1)[:, -1, :] > 0.5))
+    return (f"R_t: day {T - 1} national mean {last.mean():.3f} (0.05 / 0.95 quantiles {lo:.3f} / {hi:.3f}) over {last.size} "
+            f"kept draw(s); P(R_it > 1) > 0.5 in {100.0 * share:.1f} % of locations; window of {days} day(s) from day "
+            f"{T - days}, formed on the device; rt/* and samples/R_t written")
+
+
 def forecast_steps_fn(seed, chain_ids, horizon):
     """The random-walk steps of the forecast baseline (`forecast_walk`): for the j-th forecast draw of global chain c,
     H normals N(0, ALPHA_T_SCALE = 0.005) from np.random.default_rng([seed, c, j]) -- keyed like the device's draw id, so
@@ -386,7 +430,7 @@ def diagnostics_marks(nb):
 
 
 def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_step_size=False, forecast_calendar=None,
-             seed=0):
+             seed=0, rt_weight=None):
     """The windowed schedule of inference.py:303-470: fast 200, slow 25*2^k (k<6), fast 50,
     then num_bursts x num_burst_samples with the kernel fixed.  Every draw of the warm-up is
     written, as in the reference (its running variance is formed from every draw of a window);
@@ -395,8 +439,15 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
 
     With Mcmc.forecast = H (`forecast_mode`) every kept draw of the sampling phase is forecast H days on the device
     behind its burst; `forecast_calendar` = (W [H], weekday_c [H]) (`posterior.predict.forecast_calendar`) and `seed`
-    (the forecast's Philox stream and, with forecast_walk, the steps) are then needed.  The warm-up is not forecast."""
+    (the forecast's Philox stream and, with forecast_walk, the steps) are then needed.  The warm-up is not forecast.
+
+    With Mcmc.rt = D (`rt_mode`) R_it of every kept draw of the sampling phase over the last D days is formed and folded
+    on the device behind its burst (and behind the burst's summary and forecast); `rt_weight` [M] = N / N.sum() is then
+    needed.  The warm-up is not folded; without the key nothing of it is called."""
     thin = thin_interval(config)
+    rt_days = rt_mode(config, T=getattr(sampler, "T", None))
+    if rt_days and rt_weight is None:
+        raise ValueError("rt: run_mcmc needs rt_weight = N / N.sum()")
     horizon, walk = forecast_mode(config)
     if horizon and forecast_calendar is None:
         raise ValueError("forecast: run_mcmc needs forecast_calendar = (W, weekday_c) of the forecast days")
@@ -417,10 +468,18 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     dual_averaging_kwargs = {"target_accept_prob": 0.75}
     offset = 0
     fc_offset = 0
+    rt_offset = 0
+    rt_draws = []
 
     def flush(tr):
-        nonlocal offset, fc_offset
+        nonlocal offset, fc_offset, rt_offset
         n = tr.theta.shape[0]
+        if rt_days and getattr(tr, "rt", None) is not None:
+            r = np.array(tr.rt)                            # the pinned buffer is used again two bursts later
+            rt_draws.append(r)
+            for c, post in enumerate(posteriors):
+                post.write_samples({"R_t": r[:, c]}, first_dim_offset=rt_offset)
+            rt_offset += n
         if horizon and tr.forecast is not None:
             for c, post in enumerate(posteriors):
                 post.write_samples({k: v[:, c] for k, v in tr.forecast.items()}, first_dim_offset=fc_offset)
@@ -469,6 +528,9 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
         first_id = getattr(sampler, "first_chain_id", 0)
         burst_kw = dict(burst_kw, forecast=forecast_steps_fn(seed, [first_id + c for c in range(sampler.B)], horizon)
                         if walk else True)
+    if rt_days:
+        sampler.reset_rt(rt_days, rt_weight)                # once: the sampling phase
+        burst_kw = dict(burst_kw, rt=True)
     if summaries == "only":
         print("summaries only: the event tensors stay on the device and samples/seir is not created -- what reads it "
               "(thin_posterior, predict, reproduction_number) cannot run on this output", file=log, flush=True)
@@ -520,6 +582,13 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
         print(f"Forecast: {horizon} day(s) from day {sampler.T} for {int(fs.count.min()) if len(fs.count) else 0} kept draw(s) per "
               f"chain, formed on the device ({'random-walk' if walk else 'held'} baseline); forecast/* and "
               "samples/forecast_* written", file=log, flush=True)
+    if rt_days:
+        rs = sampler.rt_summary()
+        mean, var, prob = rs.mean, rs.var, rs.prob_gt1
+        for c, post in enumerate(posteriors):
+            post.write_rt(rt_days, sampler.T - rt_days, rs.count[c], mean[c], var[c], prob[c])
+        r_t = np.concatenate(rt_draws) if rt_draws else np.empty((0, sampler.B, rt_days))
+        print(rt_run_line(rt_days, sampler.T, r_t, prob), file=log, flush=True)
     return offset
 
 
@@ -585,7 +654,7 @@ def launch_forms(lay, device_arg, hmc="auto", moves="auto", env=os.environ):
 
 def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool_step_size=False, init_jitter=0.0,
          events_dtype="auto", hmc="auto", moves="auto", thin=None, summaries=None, diagnostics=None, diagnostics_batch=None,
-         forecast=None, forecast_walk=None):
+         forecast=None, forecast_walk=None, rt=None):
     """Constructs and runs the MCMC (covid19uk/inference/inference.py:473-608).
 
     Multi-GPU: launched as one process per GPU, every rank runs `num_chains` chains with
@@ -595,7 +664,13 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     per chain after warm-up.  `thin` overrides config["thin"] (every rank is given the same value), `summaries`
     config["summaries"] (`summaries_mode`), `diagnostics` / `diagnostics_batch` config["diagnostics"] /
     config["diagnostics_batch"] (`diagnostics_mode`), `forecast` / `forecast_walk` config["forecast"] /
-    config["forecast_walk"] (`forecast_mode`)."""
+    config["forecast_walk"] (`forecast_mode`), `rt` config["rt"] (`rt_mode`)."""
+    rt_days = 0
+    if rt is not None or "rt" in config:
+        rt_days = rt_mode(config, rt)                       # refused here: before any GPU call
+        config = {k: v for k, v in config.items() if k != "rt"}
+        if rt_days:
+            config = dict(config, rt=rt_days)
     horizon = 0
     if forecast is not None or forecast_walk is not None or "forecast" in config or "forecast_walk" in config:
         horizon, walk = forecast_mode(config, forecast, forecast_walk)    # refused here: before any GPU call
@@ -614,6 +689,8 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     initial_state, events = model_spec.initial_conditions(cases, cov.N, rng)
     M, T = events.shape[0], events.shape[1]
     P = model_spec.num_params(M, T)
+    if rt_days:
+        rt_mode(config, T=T)                                # the window against the series: still before any GPU call
     cfg = event_kernel_config(config)
     num_samples = warmup_size() + int(config["num_burst_samples"]) * int(config["num_bursts"])
     cap = max(800, 2 * int(config["num_burst_samples"]))      # two halves: a burst runs while the previous one is written
@@ -646,12 +723,16 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     names = [chain_file_name(output_file, lay["first_chain_id"] + c, total) for c in range(B)]
     posteriors = [Posterior(name, M, T, cfg["m"], num_samples, burst=int(config["num_burst_samples"]),
                             **({} if config["summaries"] == "off" else dict(summaries=config["summaries"])),
-                            **(dict(forecast=(horizon, int(config["num_burst_samples"]) * int(config["num_bursts"]))) if horizon else {}))
+                            **(dict(forecast=(horizon, int(config["num_burst_samples"]) * int(config["num_bursts"]))) if horizon else {}),
+                            **(dict(rt=(rt_days, int(config["num_burst_samples"]) * int(config["num_bursts"]))) if rt_days else {}))
                   for name in names]
     fc_kw = {}
     if horizon:
         from ..posterior.predict import forecast_calendar
         fc_kw = dict(forecast_calendar=forecast_calendar(cov, dates, T, horizon), seed=seed)
+    if rt_days:
+        N = np.asarray(cov.N, dtype=np.float64).reshape(-1)
+        fc_kw["rt_weight"] = N / N.sum()                    # reproduction_number.py:82-83
     run_mcmc(sampler, config, posteriors, pool_step_size=pool_step_size and total > 1, **fc_kw)
     if sampler.recoveries:
         print(f"{len(sampler.recoveries)} burst(s) were run again after a hand-off time-out (shared GPU?)", flush=True)
@@ -724,6 +805,11 @@ def main(argv=None):
     parser.add_argument("--forecast-walk", action="store_true", default=None,
                         help="let the forecast's log baseline continue as the prior's random walk (N(0, 0.005) steps) "
                              "instead of holding its last value (overrides Mcmc.forecast_walk; needs --forecast)")
+    parser.add_argument("--rt", type=int, default=None, metavar="D",
+                        help="form the reproduction number R_it of every kept draw of the sampling phase over the last D "
+                             "days (1..T) on the device (overrides Mcmc.rt; default off): a group rt/ with the mean, "
+                             "variance and P(R > 1) per day and location, and the national curve per draw samples/R_t; "
+                             "works with --summaries only, --thin and --forecast")
     args = parser.parse_args(argv)
     if args.thin is not None and args.thin < 1:
         parser.error(f"--thin {args.thin}: the thinning interval is >= 1")
@@ -732,7 +818,7 @@ def main(argv=None):
     mcmc(args.data_file, args.output, config["Mcmc"], seed=args.seed, num_chains=args.chains, device=args.device,
          pool_step_size=args.pool_step_size, init_jitter=args.init_jitter, events_dtype=args.events_dtype,
          hmc=args.hmc, moves=args.moves, thin=args.thin, summaries=args.summaries, diagnostics=args.diagnostics,
-         diagnostics_batch=args.diagnostics_batch, forecast=args.forecast, forecast_walk=args.forecast_walk)
+         diagnostics_batch=args.diagnostics_batch, forecast=args.forecast, forecast_walk=args.forecast_walk, rt=args.rt)
 
 
 if __name__ == "__main__":

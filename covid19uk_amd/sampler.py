@@ -39,6 +39,7 @@ class Trace:
     moves: dict              # MOVE_KEYS -> dict(is_accepted [n,B], target_log_prob [n,B], proposed_delta [n,B,4,m])
     marginals: dict = None   # MARGINAL_KEYS -> int64 [n,B,T,3] / [n,B,M,3] / [n,B,T,3]; None unless asked for
     forecast: dict = None    # FORECAST_KEYS -> int64 [n,B,H,3] / [n,B,M,3] / [n,B,H,3]; None unless the draws were forecast
+    rt: np.ndarray = None    # [n,B,D] national R_t of every kept draw over the window; None unless asked for
 
 
 MARGINAL_KEYS = ("events_by_day", "events_by_location", "state_by_day")
@@ -65,6 +66,40 @@ class Summary:
     def var(self) -> np.ndarray:
         """Unbiased variance (sumsq - sum^2 / n) / (n - 1), float64 [B,M,T,6]; NaN where n < 2."""
         return summary_var(self.count, self.sum, self.sumsq)
+
+
+@dataclasses.dataclass
+class RtSummary:
+    """Moments of R_it over the kept draws folded since the last `reset_rt` (include/seir_hip.h, "Reproduction number on
+    the device"), per chain, day of the window [T - D, T) and location: the device's accumulators as they are, and what
+    the host forms from them."""
+    count: np.ndarray        # [B] uint64 draws folded
+    ref: np.ndarray          # [B,D,M] float64: R_it of the first draw folded
+    sum: np.ndarray          # [B,D,M] float64: sum_j (r_j - ref)
+    sumsq: np.ndarray        # [B,D,M] float64: sum_j (r_j - ref)^2
+    gt1: np.ndarray          # [B,D,M] uint32: draws with r_j > 1
+
+    @property
+    def mean(self) -> np.ndarray:
+        """ref + sum / n, [B,D,M]; NaN for a chain with no draw."""
+        return summary_mean(self.count, self.ref, self.sum)
+
+    @property
+    def var(self) -> np.ndarray:
+        """Unbiased variance (sumsq - sum^2 / n) / (n - 1), [B,D,M]; NaN (no warning) where n < 2."""
+        return summary_var(self.count, self.sum, self.sumsq)
+
+    @property
+    def prob_gt1(self) -> np.ndarray:
+        """gt1 / n, the posterior probability of R_it > 1, [B,D,M]; NaN for a chain with no draw."""
+        return rt_prob_gt1(self.count, self.gt1)
+
+
+def rt_prob_gt1(count, gt1):
+    """gt1 / n (count broadcast over the leading axes); NaN where n = 0."""
+    n = _per_chain(count, gt1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(n > 0, np.asarray(gt1, np.float64) / n, np.nan)
 
 
 def forecast_draw_id(global_chain_id: int, j: int) -> int:
@@ -104,7 +139,7 @@ class PinnedTrace:
     `ChainSampler.read_trace_async`.  Views are valid until close()."""
 
     def __init__(self, sampler: "ChainSampler", count: int, events: bool = True, marginals: bool = False,
-                 forecast: int = 0):
+                 forecast: int = 0, rt: int = 0):
         self._lib = sampler._lib
         self.count = int(count)
         B, P, M, T = sampler.B, sampler.P, sampler.M, sampler.T
@@ -124,6 +159,7 @@ class PinnedTrace:
             self.forecast = dict(forecast_by_day=self._alloc((count, B, H, 3), np.int64),
                                  forecast_by_location=self._alloc((count, B, M, 3), np.int64),
                                  forecast_state_by_day=self._alloc((count, B, H, 3), np.int64))
+        self.rt = self._alloc((count, B, int(rt)), np.float64) if rt else None
 
     def _alloc(self, shape, dtype):
         nbytes = int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize
@@ -134,7 +170,7 @@ class PinnedTrace:
         return np.frombuffer(buf, dtype=dtype, count=int(np.prod(shape, dtype=np.int64))).reshape(shape)
 
     def close(self):
-        self.theta = self.events = self.hmc = self.moves = self.marginals = self.forecast = None
+        self.theta = self.events = self.hmc = self.moves = self.marginals = self.forecast = self.rt = None
         for p in self._ptrs:
             self._lib.seir_host_free(p)
         self._ptrs = []
@@ -153,6 +189,7 @@ class ChainSampler:
     _diag_L = 0                   # batch length of the diagnostics in force (0: reset_diagnostics was never called)
     _forecast_H = 0               # horizon of the forecast in force (0: reset_forecast was never called)
     _fc_j = 0                     # draws per chain forecast since the last reset_forecast (the library's counter, mirrored)
+    _rt_D = 0                     # window of the reproduction number in force (0: reset_rt was never called)
     first_chain_id = 0
 
     def __init__(self, model: SeirModel, config: dict, num_chains: int, seed: int = 0,
@@ -416,6 +453,8 @@ class ChainSampler:
             tr.marginals = {k: v[:n] for k, v in buf.marginals.items()}
         if buf.forecast is not None:
             tr.forecast = {k: v[:n] for k, v in buf.forecast.items()}
+        if buf.rt is not None:
+            tr.rt = buf.rt[:n]
         return tr
 
     # -- summaries of the recorded events on the device (include/seir_hip.h) --------------------------
@@ -549,6 +588,51 @@ class ChainSampler:
             raise ValueError("forecast asked for before reset_forecast")
         self.forecast(first, count, forecast(self._fc_j, count) if callable(forecast) else None)
 
+    # -- reproduction number of the kept draws (include/seir_hip.h, "Reproduction number on the device") ----------
+    def reset_rt(self, days: int, weight):
+        """Enable the reproduction number (first call), zero its accumulators and count, set the window to the last `days`
+        days of the series (1 <= days <= T) and the national weights `weight` [M] (N / N.sum(), as the reference)."""
+        D = int(days)
+        if not 1 <= D <= self.T:
+            raise ValueError(f"rt days {D}: 1 <= D <= T = {self.T}")
+        w = np.ascontiguousarray(weight, dtype=np.float64).reshape(-1)
+        if w.shape != (self.M,):
+            raise ValueError(f"need weight [{self.M}]")
+        _lib.check(self._lib.seir_sampler_rt_reset(self._s, D, _dptr(w)))
+        self._rt_D = D
+
+    def rt(self, first: int, count: int):
+        """Enqueue R_it of trace slots [first, first+count) behind the sweeps that fill them: folded into the moments,
+        and the national curve of every draw written."""
+        _lib.check(self._lib.seir_sampler_rt(self._s, int(first), int(count)))
+
+    def read_rt_draws(self, count: int, first: int = 0) -> np.ndarray:
+        """Blocking read of R_t [count,B,D] of trace slots [first, first+count)."""
+        out = np.empty((int(count), self.B, self._rt_D))
+        _lib.check(self._lib.seir_sampler_read_rt_draws(self._s, int(first), int(count), _dptr(out)))
+        return out
+
+    def read_rt_draws_async(self, count: int, first: int, into: PinnedTrace):
+        """As `read_marginals_async`, for the national curves; completed by `trace_wait()`."""
+        if int(count) > into.count or into.rt is None:
+            raise ValueError("pinned buffer too small or without R_t")
+        _lib.check(self._lib.seir_sampler_read_rt_draws_async(self._s, int(first), int(count), _dptr(into.rt)))
+
+    def rt_summary(self) -> RtSummary:
+        """The R_it accumulators folded since the last `reset_rt` (blocking): `RtSummary`, whose `.mean`, `.var` and
+        `.prob_gt1` are formed here.  Raises `SeirError` (SEIR_ERR_STATE) before a reset."""
+        shape = (self.B, self._rt_D, self.M)
+        cnt = np.zeros(self.B, np.uint64)
+        ref, sm, sq, g1 = np.empty(shape), np.empty(shape), np.empty(shape), np.empty(shape, np.uint32)
+        _lib.check(self._lib.seir_sampler_read_rt(self._s, cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), _dptr(ref),
+                                                  _dptr(sm), _dptr(sq), g1.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
+        return RtSummary(count=cnt, ref=ref, sum=sm, sumsq=sq, gt1=g1)
+
+    def _rt_burst(self, first, count):
+        if not self._rt_D:
+            raise ValueError("rt asked for before reset_rt")
+        self.rt(first, count)
+
     def _summarize_mode(self, summarize):
         """`summarize` of sample / sample_bursts: False, True (marginals + moments) or "marginals" (accumulate = 0)."""
         if summarize not in (False, True, "marginals"):
@@ -558,7 +642,7 @@ class ChainSampler:
         return bool(summarize), summarize is True
 
     def sample_bursts(self, num_bursts: int, burst: int, consume, events: bool = True, summarize=False, marks=None,
-                      forecast=False):
+                      forecast=False, rt=False):
         """`num_bursts` x `burst` kept draws (`burst * thin` sweeps each) with the burst buffer used as two halves:
         while burst k+1 runs on the device, burst k crosses PCIe into page-locked memory on a copy stream and `consume(trace, k)`
         (e.g. the HDF5 writer) runs on a worker thread -- the sampler only waits when the consumer is
@@ -577,7 +661,10 @@ class ChainSampler:
 
         `forecast` (True, or a callable giving random-walk steps, see `_forecast_burst`; needs `reset_forecast`): every
         burst's draws are forecast on the device right behind its summary and the forecast marginals cross with the trace
-        (`trace.forecast`)."""
+        (`trace.forecast`).
+
+        `rt` (needs `reset_rt`): R_it of every burst's draws is formed and folded on the device right behind its summary
+        and forecast, and the national curves cross with the trace (`trace.rt`)."""
         from concurrent.futures import ThreadPoolExecutor
         do_sum, accumulate = self._summarize_mode(summarize)
         burst, num_bursts = int(burst), int(num_bursts)
@@ -585,13 +672,16 @@ class ChainSampler:
             raise ValueError(f"sample_bursts needs trace_capacity >= 2 * burst = {2 * burst}, have {self.cap}")
         # page-locking GBs of host memory takes tenths of a second: the two buffers are kept for the next call
         do_fc = bool(forecast)
-        key = (burst, bool(events), do_sum, self._forecast_H if do_fc else 0)
+        do_rt = bool(rt)
+        key = (burst, bool(events), do_sum, self._forecast_H if do_fc else 0) + ((self._rt_D,) if do_rt else ())
         if getattr(self, "_pinned_key", None) != key:
             for bf in getattr(self, "_pinned", []):
                 bf.close()
             mk = dict(marginals=True) if do_sum else {}
             if do_fc:
                 mk["forecast"] = self._forecast_H
+            if do_rt:
+                mk["rt"] = self._rt_D
             self._pinned = [PinnedTrace(self, burst, events, **mk), PinnedTrace(self, burst, events, **mk)]
             self._pinned_key = key
         bufs = self._pinned
@@ -620,6 +710,8 @@ class ChainSampler:
                                 self.mark(marks[i])
                             if do_fc:
                                 self._forecast_burst(h * burst, burst, forecast)
+                            if do_rt:
+                                self._rt_burst(h * burst, burst)
                         if prev >= 0:
                             self.trace_wait()                    # burst prev has landed (it crossed while burst i ran)
                             futs[prev & 1] = pool.submit(consume, self.trace_view(bufs[prev & 1], burst), prev)
@@ -631,6 +723,8 @@ class ChainSampler:
                                 self.read_marginals_async(burst, h * burst, bufs[h])
                             if do_fc:
                                 self.read_forecast_marginals_async(burst, h * burst, bufs[h])
+                            if do_rt:
+                                self.read_rt_draws_async(burst, h * burst, bufs[h])
                             prev = i
                             i += 1
                     except _lib.HandoffTimeout as e:
@@ -651,10 +745,10 @@ class ChainSampler:
             except _lib.HandoffTimeout:
                 pass
 
-    def sample(self, num_sweeps: int, events: bool = True, summarize=False, forecast=False) -> Trace:
+    def sample(self, num_sweeps: int, events: bool = True, summarize=False, forecast=False, rt=False) -> Trace:
         """reset_trace + run + read: the analogue of one `sample_chain` call with `num_sweeps` results, each the last of
         `thin` sweeps.  `summarize` as in `sample_bursts`: the burst is summarised on the device and `trace.marginals`
-        filled; `forecast` likewise (`trace.forecast`)."""
+        filled; `forecast` likewise (`trace.forecast`), and `rt` (`trace.rt`)."""
         do_sum, accumulate = self._summarize_mode(summarize)
         if num_sweeps > self.cap:
             raise ValueError(f"num_sweeps={num_sweeps} exceeds trace_capacity={self.cap}")
@@ -668,11 +762,15 @@ class ChainSampler:
                     self.summarize(0, num_sweeps, accumulate)
                 if forecast:
                     self._forecast_burst(0, num_sweeps, forecast)
+                if rt:
+                    self._rt_burst(0, num_sweeps)
                 tr = self.read_trace(num_sweeps, events=events)
                 if do_sum:
                     tr.marginals = self.read_marginals(num_sweeps)
                 if forecast:
                     tr.forecast = self.read_forecast_marginals(num_sweeps)
+                if rt:
+                    tr.rt = self.read_rt_draws(num_sweeps)
             except _lib.HandoffTimeout as e:
                 if not self.auto_recover:
                     raise

@@ -136,8 +136,12 @@ void *seir_stream(seir_ctx *ctx);                  /* hipStream_t of the context
  *                            GPU that places block ids congruent mod 8 on one XCD each (state, tiles and reduction hand
  *                            over through that XCD's L2), as three launches otherwise; 1 = the four-launch form (scan, contraction, S->E tiles, reduction); 2 = always
  *                            three launches.  0 and 2 give the same bits
+ *   SEIR_OPT_RT_STAGING_KIB  test hook: bound in KiB on the staging plane of a seir_sampler_rt batch (0, the default:
+ *                            64 MiB), read by seir_sampler_rt_reset.  A smaller bound cuts a call into more batches of
+ *                            trace slots; no result depends on it
  * Options are read when a launch is enqueued (for a sampler using graph replay: at capture). */
-enum { SEIR_OPT_DEBUG_SKEW = 0, SEIR_OPT_XCD_AFFINITY = 1, SEIR_OPT_GEMM_F32 = 2, SEIR_OPT_EVAL_FORM = 3 };
+enum { SEIR_OPT_DEBUG_SKEW = 0, SEIR_OPT_XCD_AFFINITY = 1, SEIR_OPT_GEMM_F32 = 2, SEIR_OPT_EVAL_FORM = 3,
+       SEIR_OPT_RT_STAGING_KIB = 4 };
 int seir_set_option(seir_ctx *ctx, int32_t option, int32_t value);
 
 /* Device memory helpers so that a ctypes host can keep inputs resident
@@ -555,6 +559,57 @@ int seir_sampler_read_forecast_marginals_async(seir_sampler *s, int32_t first, i
 /* Blocking read of the forecast moments: count [B]; ref, sum, sumsq each [B][M][H][6].  Any pointer may be NULL.
  * SEIR_ERR_STATE (and a message) if the overflow flag is up, or before a reset. */
 int seir_sampler_read_forecast(seir_sampler *s, uint64_t *count, int32_t *ref, int64_t *sum, uint64_t *sumsq);
+
+/* ------------------------------------------------------------------------
+ * Reproduction number on the device: R_it moments and R_t per draw.
+ *
+ * Stands in for covid19uk/posterior/reproduction_number.py run on every kept draw, without samples/seir: for each draw
+ * of trace slots [first_slot, first_slot + count), each day t of the window [T - days, T) and each location j the device
+ * forms R_it[t][j] and folds it; neither the event tensor nor an [n][days][M] tensor crosses PCIe.
+ *
+ * Semantics (the one definition; kernels: csrc/rt_trace_kernels.h).
+ *   Per-cell value.  R_it of a draw is bit-identical to what seir_reproduction_number (below) returns for that draw's
+ *     theta and events: the same expressions, the sum over the source rows i as four partial sums (partial p takes
+ *     i = p mod 4, ascending) combined as (p0 + p1) + (p2 + p3) and multiplied by the infectious period.  The reference's
+ *     indexing is kept: a_t indexed with t, alpha_0 at t = 0, the clip at T - 1.  theta comes from the trace slot; S_it is
+ *     formed as integers, S0 - sum_{u<t} k_se[u], from the recorded events of that slot.  The sampler's live workspace is
+ *     not touched.
+ *   Accumulators per chain, [B][days][M] (day-major, location-minor, as the reference's R_it [iteration, time, location]):
+ *     ref   (double)    R_it of the chain's first draw folded since the reset
+ *     sum   (double)    sum of (r - ref)
+ *     sumsq (double)    sum of (r - ref)^2
+ *     gt1   (uint32)    draws with r > 1.0
+ *     count [B] (uint64)
+ *     The fold is sequential in draw order per chain and cell, every operation rounded on its own (no FMA):
+ *     d = r - ref; sum = sum + d; sumsq = sumsq + d * d.  A loop on the host restates every bit, and nothing depends on
+ *     how a burst is cut into calls, buffer halves or batches.  mean = ref + sum / n, the unbiased variance
+ *     (sumsq - sum^2 / n) / (n - 1) and P(R > 1) = gt1 / n are formed by the host.
+ *   National curve per kept draw, indexed by trace slot: R_t [count][B][days] = sum_j R_it[t][j] weight[j], weight [M]
+ *     handed over at the reset (N / sum N, reproduction_number.py:82-83).  No floating-point atomics: blocks of 64
+ *     columns are summed in a fixed order each and then in ascending block order, so the value is the same bits in every
+ *     run, for every cut and launch geometry.
+ * Switched on by the first seir_sampler_rt_reset; a sampler that never calls it allocates and launches nothing more than
+ * before.  While it is on, seir_sampler_snapshot / _restore carry the accumulators and count, so that a burst run again
+ * after a hand-off time-out is folded once.  A snapshot taken before the last reset holds none of it; restoring it leaves
+ * them as they are.
+ * ------------------------------------------------------------------------ */
+/* First call (and a call with another `days`) allocates; every call zeroes the accumulators and count in stream order and
+ * takes weight [M] (copied).  SEIR_ERR_INVALID for days outside [1, T], a null weight pointer, or a sampler created with
+ * record_events == 0. */
+int seir_sampler_rt_reset(seir_sampler *s, int32_t days, const double *weight);
+/* Form and fold R_it of trace slots [first_slot, first_slot + count) of every chain and write their R_t: asynchronous on
+ * the context stream, behind the sweeps that fill those slots.  SEIR_ERR_INVALID for slots outside the burst buffer or
+ * with record_events == 0, SEIR_ERR_STATE before a reset. */
+int seir_sampler_rt(seir_sampler *s, int32_t first_slot, int32_t count);
+/* Blocking read of R_t [count][B][days] of slots [first, first + count) (written by the last seir_sampler_rt that covered
+ * them).  Host pointer. */
+int seir_sampler_read_rt_draws(seir_sampler *s, int32_t first, int32_t count, double *R_t);
+/* The same on the copy stream of seir_sampler_read_trace_async, behind everything queued on the context stream so far;
+ * completed by seir_sampler_trace_wait.  The host buffer should be page-locked (seir_host_alloc). */
+int seir_sampler_read_rt_draws_async(seir_sampler *s, int32_t first, int32_t count, double *R_t);
+/* Blocking read of the accumulators: count [B]; ref, sum, sumsq, gt1 each [B][days][M].  Any pointer may be NULL.
+ * SEIR_ERR_STATE before a reset. */
+int seir_sampler_read_rt(seir_sampler *s, uint64_t *count, double *ref, double *sum, double *sumsq, uint32_t *gt1);
 
 /* ------------------------------------------------------------------------
  * Reproduction number R_it.
