@@ -69,6 +69,7 @@ MMAX = 4                      # SEIR_MMAX
 MOVE_TRACE = 2 + 4 * MMAX     # SEIR_MOVE_TRACE
 FORECAST_MAX_H = 128          # SEIR_FORECAST_MAX_H
 FORECAST_ID_SHIFT, FORECAST_MAX_CHAIN = 20, 2048   # draw id = (global chain id << 20) + j
+CHECK_MAX_DAYS = 128          # SEIR_CHECK_MAX_DAYS
 
 
 class SeirError(RuntimeError):
@@ -177,6 +178,17 @@ _SIGNATURES = {
     "seir_sampler_read_forecast": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
                                                   ctypes.POINTER(ctypes.c_int32), c_int64_p,
                                                   ctypes.POINTER(ctypes.c_uint64)]),
+    # in-sample check of the last K days from the burst buffer: moments, marginals and the comparison with the data
+    "seir_sampler_check_reset": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_double_p, c_double_p, ctypes.c_uint64]),
+    "seir_sampler_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]),
+    "seir_sampler_read_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
+                                               ctypes.POINTER(ctypes.c_int32), c_int64_p, ctypes.POINTER(ctypes.c_uint64)]),
+    "seir_sampler_read_check_marginals": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                                         c_int64_p, c_int64_p, c_int64_p]),
+    "seir_sampler_read_check_marginals_async": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                                               c_int64_p, c_int64_p, c_int64_p]),
+    "seir_sampler_read_check_counts": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)] +
+                                       [ctypes.POINTER(ctypes.c_uint32)] * 8),
     # reproduction number of the kept draws from the burst buffer: R_it moments and the national curve per draw
     "seir_sampler_rt_reset": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_double_p]),
     "seir_sampler_rt": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]),

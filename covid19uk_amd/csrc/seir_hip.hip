@@ -21,6 +21,7 @@
 #include "sweep_plan.h"
 #include "summary_kernels.h"
 #include "forecast_kernels.h"
+#include "check_kernels.h"
 #include "rt_trace_kernels.h"
 
 using namespace seir;
@@ -1150,6 +1151,18 @@ struct seir_sampler {
     double *fc_steps_dev = nullptr;   // [fc_slots * B][H]
     hipEvent_t fc_ev_steps = nullptr; // behind the last upload from fc_steps_host
     bool fc_steps_pending = false;
+    // --- in-sample check of the last K days (seir_sampler_check_reset ...; check_kernels.h): a ForecastBufs with H := K ---
+    bool ck_on = false;
+    ForecastBufs ck{};
+    CheckCmp ck_cmp{};
+    int ck_slots = 0;                 // trace slots per batch: min(cap, FC_JMAX)
+    int ck_ndmax = 0;                 // row stride the planes are allocated for: ceil64(ck_slots * B)
+    std::vector<void *> ck_allocs;    // device buffers sized by K (allocated again when it changes)
+    MomentAcc ck_acc;                 // ck.mom's ref .. overflow
+    Shadowed ck_cnt;                  // ck_cmp's arrays, 32-bit words: lt | eq | obs [B M K] | loc_lt | loc_eq [B M] |
+                                      //     day_lt | day_eq [B K] | all_lt | all_eq | moved [B]
+    long long ck_j = 0;               // draws per chain checked since the last reset (the j of the draw id; not the forecast's)
+    long long ck_snap_j[2] = {0, 0};  // ck_j as it was when the shadows were taken
     // --- reproduction number of the kept draws (seir_sampler_rt_reset ...; rt_trace_kernels.h) ---
     bool rt_on = false;
     RtBufs rt{};
@@ -1195,7 +1208,9 @@ extern "C" void seir_sampler_destroy(seir_sampler *s) {
     for (void *p : s->snap) if (p) (void)hipFree(p);
     for (void *p : s->fc_allocs) (void)hipFree(p);
     for (void *p : s->rt_allocs) (void)hipFree(p);
+    for (void *p : s->ck_allocs) (void)hipFree(p);
     acc_free(s->sum_acc); acc_free(s->diag_buf); acc_free(s->fc_acc); acc_free(s->rt_acc);
+    acc_free(s->ck_acc); acc_free(s->ck_cnt);
     if (s->fc_steps_host) (void)hipHostFree(s->fc_steps_host);
     if (s->fc_ev_steps) (void)hipEventDestroy(s->fc_ev_steps);
     Work &w = s->ctx->w;
@@ -1477,7 +1492,8 @@ extern "C" int seir_sampler_debug_fail_handoff(seir_sampler *s, int32_t chain) {
 // While a feature is enabled a snapshot also holds its accumulators (device copies in stream order), so that a burst can
 // be folded as soon as it is enqueued and a burst that is run again after a hand-off time-out is not counted twice: the
 // moments, count and flag of the summaries; with them the diagnostics' batch sums and marks (a mark taken in a burst that is
-// thrown away goes with it); the forecast's moments and its draw counter; the reproduction number's moments and count.
+// thrown away goes with it); the forecast's moments and its draw counter; the reproduction number's moments and count; the
+// check's moments, comparison counts, obs, flags and its draw counter.
 static size_t summary_cells(const seir_sampler *s) { return (size_t)s->cfg.B * s->ctx->d.M * s->ctx->d.T * seir::SUMMARY_Q; }
 static size_t diag_words(const seir_sampler *s) { return 6 * summary_cells(s) + 3 * (size_t)s->cfg.B; }
 static uint64_t *diag_mark(const seir_sampler *s, int which) {       // count [B] | sum [n] | sumsq [n]
@@ -1497,6 +1513,12 @@ static int moments_shadow(seir_sampler *s, int slot, bool save) {
         rc = acc_shadow(s->fc_acc, slot, save, st);
     }
     if (!rc && s->rt_on) rc = acc_shadow(s->rt_acc, slot, save, st);
+    if (!rc && s->ck_on) {
+        if (save) s->ck_snap_j[slot] = s->ck_j;
+        else if (s->ck_acc.valid[slot]) s->ck_j = s->ck_snap_j[slot];
+        rc = acc_shadow(s->ck_acc, slot, save, st);
+        if (!rc) rc = acc_shadow(s->ck_cnt, slot, save, st);
+    }
     return rc;
 }
 
@@ -2157,6 +2179,7 @@ static const TraceUser SUMMARY_USER = {"summarise", "summaries are not enabled: 
 static const TraceUser RT_USER = {"form the reproduction number from",
                                    "the reproduction number is not enabled: call seir_sampler_rt_reset first"};
 static const TraceUser FORECAST_USER = {"forecast from", "the forecast is not enabled: call seir_sampler_forecast_reset first"};
+static const TraceUser CHECK_USER = {"check", "the in-sample check is not enabled: call seir_sampler_check_reset first"};
 
 static int trace_range_check(seir_sampler *s, bool enabled, const TraceUser &what, int32_t first = 0, int32_t count = 0) {
     if (int rc = need_events(s, what.verb)) return rc;
@@ -2509,6 +2532,188 @@ extern "C" int seir_sampler_read_forecast(seir_sampler *s, uint64_t *count, int3
     if (rc) return rc;
     if ((rc = trace_range_check(s, s->fc_on, FORECAST_USER))) return rc;
     return read_moments(s, s->fc_acc, "forecast's ", "seir_sampler_forecast_reset", count, ref, sum, sumsq);
+}
+
+// ---------------------------------------------------------------------------
+// In-sample predictive check on the device (include/seir_hip.h; kernels: check_kernels.h)
+// ---------------------------------------------------------------------------
+static void check_layout(seir_sampler *s, int K) {
+    const size_t B = (size_t)s->cfg.B, M = (size_t)s->ctx->d.M, cells = B * M * K;
+    CheckCmp &cc = s->ck_cmp;
+    uint32_t *w = (uint32_t *)s->ck_cnt.p;
+    cc.lt = w; cc.eq = w + cells; cc.obs = (int32_t *)(w + 2 * cells);
+    w += 3 * cells;
+    cc.loc_lt = w; cc.loc_eq = w + B * M;
+    w += 2 * B * M;
+    cc.day_lt = w; cc.day_eq = w + B * K;
+    w += 2 * B * K;
+    cc.all_lt = w; cc.all_eq = w + B; cc.moved = w + 2 * B;
+}
+static size_t check_words(const seir_sampler *s, int K) {
+    const size_t B = (size_t)s->cfg.B, M = (size_t)s->ctx->d.M;
+    return 3 * B * M * K + 2 * B * M + 2 * B * K + 3 * B;
+}
+
+extern "C" int seir_sampler_check_reset(seir_sampler *s, int32_t days, const double *W, const double *weekday_c, uint64_t seed) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = need_events(s, CHECK_USER.verb))) return rc;
+    const Dims &d = s->ctx->d;
+    const int kmax = std::min(d.T, SEIR_CHECK_MAX_DAYS);
+    if (days < 1 || days > kmax) return fail(SEIR_ERR_INVALID, "days=%d outside [1, min(T = %d, %d)]", days, d.T, SEIR_CHECK_MAX_DAYS);
+    if (!W || !weekday_c) return fail(SEIR_ERR_INVALID, "null calendar pointer");
+    const size_t lds = k_simulate_lds_bytes(d);
+    if (lds > 160 * 1024) return fail(SEIR_ERR_INVALID, "M=%d needs %zu B of LDS for the simulator", d.M, lds);
+    const int B = s->cfg.B, K = days;
+    if ((long long)s->cfg.chain0 + B > FC_MAX_CHAIN)
+        return fail(SEIR_ERR_INVALID, "global chain id %d: the check's draw ids need chain ids below %d", s->cfg.chain0 + B - 1,
+                    FC_MAX_CHAIN);
+    hipStream_t st = s->ctx->stream;
+    ForecastBufs &fb = s->ck;
+    const size_t cap = (size_t)s->cfg.cap;
+    if (!s->ck_on || fb.H != K) {
+        // first reset, or another window: everything is sized by K
+        HIP_TRY(hipStreamSynchronize(st));
+        if (s->copy_pending) { (void)hipEventSynchronize(s->ev_copy); s->copy_pending = false; }
+        for (void *p : s->ck_allocs) (void)hipFree(p);
+        s->ck_allocs.clear();
+        acc_free(s->ck_acc);
+        acc_free(s->ck_cnt);
+        s->ck_on = false;
+        fb = ForecastBufs{};
+        s->ck_slots = std::min(s->cfg.cap, FC_JMAX);
+        s->ck_ndmax = ceil_to(s->ck_slots * B, 64);
+        const size_t plane = (size_t)d.Mp * s->ck_ndmax, ndm = (size_t)s->ck_slots * B;
+        double *Wd = nullptr, *wdd = nullptr;
+        S_ALLOC(ck_allocs, Wd, K); S_ALLOC(ck_allocs, wdd, K);
+        S_ALLOC(ck_allocs, fb.St0, 3 * plane); S_ALLOC(ck_allocs, fb.St, 3 * plane);
+        S_ALLOC(ck_allocs, fb.X, plane); S_ALLOC(ck_allocs, fb.F, plane); S_ALLOC(ck_allocs, fb.eb, plane);
+        S_ALLOC(ck_allocs, fb.sc, 3 * (size_t)s->ck_ndmax); S_ALLOC(ck_allocs, fb.base, (size_t)K * s->ck_ndmax);
+        S_ALLOC(ck_allocs, fb.fev, ndm * d.M * K * 3);       // the check's own staging tensor
+        S_ALLOC(ck_allocs, fb.mom.by_day, cap * B * K * 3); S_ALLOC(ck_allocs, fb.mom.by_loc, cap * B * d.M * 3);
+        S_ALLOC(ck_allocs, fb.mom.state_by_day, cap * B * K * 3);
+        if (!rc) rc = acc_alloc(s->ck_acc, (size_t)B * d.M * K * seir::SUMMARY_Q, (size_t)B, fb.mom);
+        if (!rc) rc = acc_alloc(s->ck_cnt, check_words(s, K) * sizeof(uint32_t));
+        if (rc) return rc;
+        check_layout(s, K);
+        fb.W = Wd; fb.wd = wdd;
+        fb.H = K;
+        fb.steps = nullptr;
+        (void)hipFuncSetAttribute((const void *)k_gemm<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_lds_bytes<64>());
+        s->ck_on = true;
+    }
+    fb.k0 = (uint32_t)(seed & 0xffffffffu); fb.k1 = (uint32_t)(seed >> 32);
+    // the caller's arrays are not retained: blocking copies behind what is queued (a reset is not on the hot path)
+    HIP_TRY(hipMemcpyAsync(const_cast<double *>(fb.W), W, sizeof(double) * K, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(const_cast<double *>(fb.wd), weekday_c, sizeof(double) * K, hipMemcpyHostToDevice, st));
+    if ((rc = acc_zero(s->ck_acc, st))) return rc;
+    if ((rc = acc_zero(s->ck_cnt, st))) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    s->ck_j = 0;
+    // what the snapshots taken before this reset hold of the check is dropped with it
+    acc_invalidate(s->ck_acc);
+    acc_invalidate(s->ck_cnt);
+    return 0;
+}
+
+extern "C" int seir_sampler_check(seir_sampler *s, int32_t first, int32_t count) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = trace_range_check(s, s->ck_on, CHECK_USER, first, count))) return rc;
+    if (count == 0) return 0;
+    if (s->ck_j + count > (1ll << FC_ID_SHIFT))
+        return fail(SEIR_ERR_INVALID, "%lld draws per chain checked since the reset and %d more: the draw id holds 2^%d", s->ck_j,
+                    count, FC_ID_SHIFT);
+    seir_ctx *ctx = s->ctx;
+    const LaunchCfg l = whole(ctx, s->cfg.B);
+    const Dims &d = l.d;
+    const int B = s->cfg.B, K = s->ck.H;
+    // check_by_day is summed with atomics: zero the call's slots first
+    HIP_TRY(hipMemsetAsync(s->ck.mom.by_day + (size_t)first * B * K * 3, 0, sizeof(int64_t) * count * B * K * 3, l.st));
+    Dims gd = d;                                     // the contraction's view: one "chain", the draw index as the day index
+    gd.b0 = 0;
+    Work gw{};
+    gw.Xn = s->ck.X; gw.F = s->ck.F;
+    const ForecastBufs &fb = s->ck;
+    for (int j0 = 0; j0 < count; j0 += s->ck_slots) {
+        const int nj = std::min(s->ck_slots, count - j0), ND = nj * B, ndp = ceil_to(ND, 64);
+        const int fresh = s->ck_j + j0 == 0;
+        const dim3 pgrid(d.Mp / FC_ROWS, ndp), rgrid((d.M + FC_ROWS - 1) / FC_ROWS, B), rblock(64 * FC_ROWS);
+        if (s->cfg.ev16)
+            hipLaunchKernelGGL(k_check_prepare<1>, pgrid, rblock, 0, l.st, d, ctx->c, fb, (const double *)s->ch.tr_theta,
+                               (const void *)s->ch.tr_events, B, first + j0, ND, ndp);
+        else
+            hipLaunchKernelGGL(k_check_prepare<0>, pgrid, rblock, 0, l.st, d, ctx->c, fb, (const double *)s->ch.tr_theta,
+                               (const void *)s->ch.tr_events, B, first + j0, ND, ndp);
+        gd.Tp = ndp;
+        for (int h = 0; h < K; ++h) {
+            hipLaunchKernelGGL((k_gemm<64>), dim3(ndp / 64, d.Mp / GEMM_TM, 1), dim3(gemm_threads<64>()), gemm_lds_bytes<64>(),
+                               l.st, gd, ctx->c, gw);
+            hipLaunchKernelGGL(k_forecast_day, dim3(ndp / 64, (d.M + FC_DAY_ROWS - 1) / FC_DAY_ROWS), dim3(64 * FC_DAY_ROWS), 0,
+                               l.st, d, ctx->c, fb, B, s->cfg.chain0, (int)(s->ck_j + j0), ND, ndp, h);
+        }
+        hipLaunchKernelGGL(k_forecast_fold, rgrid, rblock, 0, l.st, d, fb, B, first + j0, nj, ndp);
+        hipLaunchKernelGGL(k_forecast_finish, dim3(nj, B), dim3(64), 0, l.st, d, fb, B, first + j0, nj, ndp);
+        if (s->cfg.ev16)
+            hipLaunchKernelGGL(k_check_compare<1>, rgrid, rblock, 0, l.st, d, fb, s->ck_cmp, (const void *)s->ch.tr_events, B,
+                               first + j0, nj, fresh);
+        else
+            hipLaunchKernelGGL(k_check_compare<0>, rgrid, rblock, 0, l.st, d, fb, s->ck_cmp, (const void *)s->ch.tr_events, B,
+                               first + j0, nj, fresh);
+        hipLaunchKernelGGL(k_check_totals, dim3(B), dim3(CK_TOT_THREADS), 0, l.st, d, fb, s->ck_cmp, B, first + j0, nj);
+    }
+    HIP_TRY(hipGetLastError());
+    s->ck_j += count;
+    return 0;
+}
+
+extern "C" int seir_sampler_read_check_marginals(seir_sampler *s, int32_t first, int32_t count, int64_t *check_by_day,
+                                                 int64_t *check_by_location, int64_t *check_state_by_day) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = trace_range_check(s, s->ck_on, CHECK_USER, first, count))) return rc;
+    return read_marginals(s, false, first, count, marginals(s->ck.mom, s->ck.H), check_by_day, check_by_location, check_state_by_day);
+}
+
+extern "C" int seir_sampler_read_check_marginals_async(seir_sampler *s, int32_t first, int32_t count, int64_t *check_by_day,
+                                                       int64_t *check_by_location, int64_t *check_state_by_day) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = trace_range_check(s, s->ck_on, CHECK_USER, first, count))) return rc;
+    return read_marginals(s, true, first, count, marginals(s->ck.mom, s->ck.H), check_by_day, check_by_location, check_state_by_day);
+}
+
+extern "C" int seir_sampler_read_check(seir_sampler *s, uint64_t *count, int32_t *ref, int64_t *sum, uint64_t *sumsq) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = trace_range_check(s, s->ck_on, CHECK_USER))) return rc;
+    return read_moments(s, s->ck_acc, "check's ", "seir_sampler_check_reset", count, ref, sum, sumsq);
+}
+
+extern "C" int seir_sampler_read_check_counts(seir_sampler *s, int32_t *obs, uint32_t *lt, uint32_t *eq, uint32_t *loc_lt,
+                                              uint32_t *loc_eq, uint32_t *day_lt, uint32_t *day_eq, uint32_t *all_lt,
+                                              uint32_t *all_eq) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = trace_range_check(s, s->ck_on, CHECK_USER))) return rc;
+    hipStream_t st = s->ctx->stream;
+    const size_t B = (size_t)s->cfg.B, M = (size_t)s->ctx->d.M, K = (size_t)s->ck.H;
+    const CheckCmp &cc = s->ck_cmp;
+    std::vector<unsigned> moved(B, 0u);
+    HIP_TRY(hipMemcpyAsync(moved.data(), cc.moved, sizeof(unsigned) * B, hipMemcpyDeviceToHost, st));
+    const struct { void *dst; const void *src; size_t n; } parts[] = {
+        {obs, cc.obs, B * M * K}, {lt, cc.lt, B * M * K}, {eq, cc.eq, B * M * K}, {loc_lt, cc.loc_lt, B * M},
+        {loc_eq, cc.loc_eq, B * M}, {day_lt, cc.day_lt, B * K}, {day_eq, cc.day_eq, B * K}, {all_lt, cc.all_lt, B},
+        {all_eq, cc.all_eq, B}};
+    for (const auto &p : parts)
+        if (p.dst) HIP_TRY(hipMemcpyAsync(p.dst, p.src, sizeof(uint32_t) * p.n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = check_ev_overflow(s))) return rc;
+    for (size_t b = 0; b < B; ++b)
+        if (moved[b])
+            return fail(SEIR_ERR_STATE, "chain %zu: a draw's recorded I->R counts in the check window differ from those of the first "
+                        "draw checked: the observed removals moved (seir_sampler_check_reset starts the check again)", b);
+    return 0;
 }
 
 // ---------------------------------------------------------------------------

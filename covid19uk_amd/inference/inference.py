@@ -20,7 +20,7 @@ import numpy as np
 from .. import hdf5io
 from .. import model_spec
 from ..posterior import diagnostics as diag_mod
-from ..sampler import MOVE_KEYS, ChainSampler, Summary
+from ..sampler import MOVE_KEYS, ChainSampler, Summary, mid_p
 from ..seir import SeirModel
 from .mcmc_kernel_factory import event_kernel_config, hmc_kernel_kwargs_default
 
@@ -106,7 +106,7 @@ class Posterior:
     `is_accepted` is a bool dataset the way h5py stores one (gemlib's Posterior writes numpy bools through h5py):
     the int8 enum {FALSE = 0, TRUE = 1}."""
 
-    def __init__(self, filename, M, T, mmax, num_samples, burst=100, summaries="off", forecast=None, rt=None):
+    def __init__(self, filename, M, T, mmax, num_samples, burst=100, summaries="off", forecast=None, rt=None, check=None):
         """`summaries` ("off" | "on" | "only", Mcmc.summaries / --summaries): with "on" and "only" the per-draw marginals
         samples/seir_by_day [n,T,3], samples/seir_by_location [n,M,3], samples/state_by_day [n,T,3] (int64) are written
         with every burst and `write_summary` adds summaries/* at the end of the run; with "only" samples/seir is not
@@ -117,7 +117,11 @@ class Posterior:
         num_samples: the warm-up is not forecast -- and `write_forecast` adds the group forecast/ at the end of the run.
 
         `rt` ((D, n) or None, Mcmc.rt / --rt): samples/R_t [n,D] (float64), the national reproduction number of the last
-        D days, one row per kept draw of the sampling phase, and `write_rt` adds the group rt/ at the end of the run."""
+        D days, one row per kept draw of the sampling phase, and `write_rt` adds the group rt/ at the end of the run.
+
+        `check` ((K, n) or None, Mcmc.check / --check): samples/check_by_day [n,K,3], check_by_location [n,M,3],
+        check_state_by_day [n,K,3] (int64), one row per kept draw of the sampling phase, and `write_check` adds the group
+        check/ at the end of the run."""
         self.filename = filename
         self.use_h5 = not str(filename).endswith(".npz") and hdf5io.available()
         self.shapes = {
@@ -148,6 +152,11 @@ class Posterior:
                 self.shapes[k], self.dtypes[k], self.rows[k] = shp, np.int64, n_fc
         if rt is not None:
             self.shapes["samples/R_t"], self.rows["samples/R_t"] = (int(rt[0]),), int(rt[1])
+        if check is not None:
+            K, n_ck = int(check[0]), int(check[1])
+            for k, shp in (("samples/check_by_day", (K, 3)), ("samples/check_by_location", (M, 3)),
+                           ("samples/check_state_by_day", (K, 3))):
+                self.shapes[k], self.dtypes[k], self.rows[k] = shp, np.int64, n_ck
         self._scratch = {}
         if self.use_h5:
             self._file = hdf5io.File(filename, "w")
@@ -231,6 +240,19 @@ class Posterior:
         self.create_dataset("rt/R_it_mean", np.ascontiguousarray(mean, dtype=np.float64))
         self.create_dataset("rt/R_it_var", np.ascontiguousarray(var, dtype=np.float64))
         self.create_dataset("rt/R_it_prob_gt1", np.ascontiguousarray(prob_gt1, dtype=np.float64))
+
+    def write_check(self, days, first_day, count, mean, var, counts: dict):
+        """The group check/ of one chain: days [1], first_day [1] (= T - K, the absolute day of check day 0), count [1],
+        the moments of the re-simulated events and state ([M,K,6] rows: seir_mean, seir_var, state_mean, state_var, each
+        [M,K,3]) and `counts` (`check_chain_datasets`): observed, lt, eq [M,K], location_lt, location_eq [M], day_lt,
+        day_eq [K], total_lt, total_eq [1] -- the raw counts, so that pooling over chains and ranks is a sum -- and the
+        mid-p values pit, location_pit, day_pit, total_pit."""
+        self.create_dataset("check/days", np.array([float(days)]))
+        self.create_dataset("check/first_day", np.array([float(first_day)]))
+        self.create_dataset("check/count", np.array([float(count)]))
+        self._write_moments("check", mean, var)
+        for k, v in counts.items():
+            self.create_dataset(f"check/{k}", np.atleast_1d(np.asarray(v, np.float64)))
 
     def write_diagnostics(self, datasets: dict):
         """The group diagnostics/ of one chain (`posterior.diagnostics.chain_datasets`), float64."""
@@ -390,6 +412,55 @@ def rt_mode(config, override=None, T=None):
     return D
 
 
+# The check's Philox key is the run's seed with this constant folded in: the check and the forecast (keyed by the run's seed
+# itself) share a protocol and a draw-id space, and so must never share a key
+CHECK_SEED_SALT = 0x636865636B5F6B31                        # "check_k1"
+
+
+def check_seed(seed):
+    return (int(seed) ^ CHECK_SEED_SALT) & (2 ** 64 - 1)
+
+
+def check_mode(config, override=None, T=None):
+    """Mcmc.check (absent: off), or the command line's `--check K`: the number of days K of the window [T - K, T) that is
+    simulated again from every kept draw of the sampling phase and set against the observed removals; 0 for off.
+    1 <= K <= 128 (SEIR_CHECK_MAX_DAYS), and K <= T when the length of the series is given.  The one place that validates
+    -- before a sampler exists."""
+    from .. import _lib
+    K = config.get("check") if override is None else override
+    if K is None or K is False or (isinstance(K, str) and K.lower() == "off"):
+        return 0
+    if isinstance(K, bool) or (not isinstance(K, (int, np.integer)) and not (isinstance(K, str) and K.strip().lstrip("+-").isdigit())):
+        raise ValueError(f"check={K!r}: the window is a number of days, 1 .. min(T, {_lib.CHECK_MAX_DAYS})")
+    K = int(K)
+    if K < 1 or K > _lib.CHECK_MAX_DAYS or (T is not None and K > int(T)):
+        raise ValueError(f"check={K}: the window is 1 .. min(T{'' if T is None else f' = {int(T)}'}, {_lib.CHECK_MAX_DAYS}) days")
+    return K
+
+
+def check_chain_datasets(cs, c):
+    """check/* of chain c beyond the moments, from a `CheckSummary`: the raw counts and the mid-p values."""
+    return {"observed": cs.observed[c], "lt": cs.lt[c], "eq": cs.eq[c],
+            "location_lt": cs.location_lt[c], "location_eq": cs.location_eq[c],
+            "day_lt": cs.day_lt[c], "day_eq": cs.day_eq[c], "total_lt": cs.total_lt[c], "total_eq": cs.total_eq[c],
+            "pit": cs.pit[c], "location_pit": cs.location_pit[c], "day_pit": cs.day_pit[c], "total_pit": cs.total_pit[c]}
+
+
+def check_run_line(days, T, cs):
+    """The run's one line about the check: the mid-p value of the national total over the window, pooled over the
+    process's chains (the counts add), and the share of locations whose `location_pit`, pooled likewise, lies in
+    [0.05, 0.95]."""
+    n = np.asarray(cs.count, np.uint64).sum()
+    if n == 0:
+        return f"Check: window of {days} day(s) from day {T - days}, no kept draw"
+    total = float(mid_p(n, cs.total_lt.astype(np.uint64).sum(), cs.total_eq.astype(np.uint64).sum()))
+    loc = mid_p(n, cs.location_lt.astype(np.uint64).sum(axis=0), cs.location_eq.astype(np.uint64).sum(axis=0))
+    share = float(np.mean((loc >= 0.05) & (loc <= 0.95)))
+    return (f"Check: last {days} day(s) from day {T - days} simulated again from {int(n)} kept draw(s): national total mid-p "
+            f"{total:.3f}; location totals with mid-p in [0.05, 0.95]: {100.0 * share:.1f} %; formed on the device; check/* "
+            "and samples/check_* written")
+
+
 def rt_run_line(days, T, r_t, prob_gt1):
     """The run's one line about R_t: the national value on the last day (mean and 0.05 / 0.95 quantiles over the per-draw
     curves `r_t` [n, chains, D]) and the share of locations whose P(R_it > 1) on that day exceeds 0.5 (`prob_gt1`
@@ -430,7 +501,7 @@ def diagnostics_marks(nb):
 
 
 def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_step_size=False, forecast_calendar=None,
-             seed=0, rt_weight=None):
+             seed=0, rt_weight=None, check_calendar=None):
     """The windowed schedule of inference.py:303-470: fast 200, slow 25*2^k (k<6), fast 50,
     then num_bursts x num_burst_samples with the kernel fixed.  Every draw of the warm-up is
     written, as in the reference (its running variance is formed from every draw of a window);
@@ -443,8 +514,16 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
 
     With Mcmc.rt = D (`rt_mode`) R_it of every kept draw of the sampling phase over the last D days is formed and folded
     on the device behind its burst (and behind the burst's summary and forecast); `rt_weight` [M] = N / N.sum() is then
-    needed.  The warm-up is not folded; without the key nothing of it is called."""
+    needed.  The warm-up is not folded; without the key nothing of it is called.
+
+    With Mcmc.check = K (`check_mode`) the last K days are simulated again from every kept draw of the sampling phase and
+    set against the observed removals on the device, behind the burst's summary, forecast and R_t; `check_calendar` =
+    (W [K], weekday_c [K]) (`posterior.predict.check_calendar`) is then needed, and the check's stream is keyed by
+    `check_seed(seed)`.  The warm-up is not checked; without the key nothing of it is called."""
     thin = thin_interval(config)
+    check_days = check_mode(config, T=getattr(sampler, "T", None))
+    if check_days and check_calendar is None:
+        raise ValueError("check: run_mcmc needs check_calendar = (W, weekday_c) of the window")
     rt_days = rt_mode(config, T=getattr(sampler, "T", None))
     if rt_days and rt_weight is None:
         raise ValueError("rt: run_mcmc needs rt_weight = N / N.sum()")
@@ -470,10 +549,15 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     fc_offset = 0
     rt_offset = 0
     rt_draws = []
+    ck_offset = 0
 
     def flush(tr):
-        nonlocal offset, fc_offset, rt_offset
+        nonlocal offset, fc_offset, rt_offset, ck_offset
         n = tr.theta.shape[0]
+        if check_days and getattr(tr, "check", None) is not None:
+            for c, post in enumerate(posteriors):
+                post.write_samples({k: v[:, c] for k, v in tr.check.items()}, first_dim_offset=ck_offset)
+            ck_offset += n
         if rt_days and getattr(tr, "rt", None) is not None:
             r = np.array(tr.rt)                            # the pinned buffer is used again two bursts later
             rt_draws.append(r)
@@ -531,6 +615,9 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     if rt_days:
         sampler.reset_rt(rt_days, rt_weight)                # once: the sampling phase
         burst_kw = dict(burst_kw, rt=True)
+    if check_days:
+        sampler.reset_check(check_days, check_calendar[0], check_calendar[1], check_seed(seed))   # once: the sampling phase
+        burst_kw = dict(burst_kw, check=True)
     if summaries == "only":
         print("summaries only: the event tensors stay on the device and samples/seir is not created -- what reads it "
               "(thin_posterior, predict, reproduction_number) cannot run on this output", file=log, flush=True)
@@ -589,6 +676,12 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
             post.write_rt(rt_days, sampler.T - rt_days, rs.count[c], mean[c], var[c], prob[c])
         r_t = np.concatenate(rt_draws) if rt_draws else np.empty((0, sampler.B, rt_days))
         print(rt_run_line(rt_days, sampler.T, r_t, prob), file=log, flush=True)
+    if check_days:
+        cs = sampler.check_summary()
+        mean, var = cs.moments.mean, cs.moments.var
+        for c, post in enumerate(posteriors):
+            post.write_check(check_days, sampler.T - check_days, cs.count[c], mean[c], var[c], check_chain_datasets(cs, c))
+        print(check_run_line(check_days, sampler.T, cs), file=log, flush=True)
     return offset
 
 
@@ -654,7 +747,7 @@ def launch_forms(lay, device_arg, hmc="auto", moves="auto", env=os.environ):
 
 def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool_step_size=False, init_jitter=0.0,
          events_dtype="auto", hmc="auto", moves="auto", thin=None, summaries=None, diagnostics=None, diagnostics_batch=None,
-         forecast=None, forecast_walk=None, rt=None):
+         forecast=None, forecast_walk=None, rt=None, check=None):
     """Constructs and runs the MCMC (covid19uk/inference/inference.py:473-608).
 
     Multi-GPU: launched as one process per GPU, every rank runs `num_chains` chains with
@@ -664,7 +757,13 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     per chain after warm-up.  `thin` overrides config["thin"] (every rank is given the same value), `summaries`
     config["summaries"] (`summaries_mode`), `diagnostics` / `diagnostics_batch` config["diagnostics"] /
     config["diagnostics_batch"] (`diagnostics_mode`), `forecast` / `forecast_walk` config["forecast"] /
-    config["forecast_walk"] (`forecast_mode`), `rt` config["rt"] (`rt_mode`)."""
+    config["forecast_walk"] (`forecast_mode`), `rt` config["rt"] (`rt_mode`), `check` config["check"] (`check_mode`)."""
+    check_days = 0
+    if check is not None or "check" in config:
+        check_days = check_mode(config, check)              # refused here: before any GPU call
+        config = {k: v for k, v in config.items() if k != "check"}
+        if check_days:
+            config = dict(config, check=check_days)
     rt_days = 0
     if rt is not None or "rt" in config:
         rt_days = rt_mode(config, rt)                       # refused here: before any GPU call
@@ -691,6 +790,8 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     P = model_spec.num_params(M, T)
     if rt_days:
         rt_mode(config, T=T)                                # the window against the series: still before any GPU call
+    if check_days:
+        check_mode(config, T=T)                             # likewise
     cfg = event_kernel_config(config)
     num_samples = warmup_size() + int(config["num_burst_samples"]) * int(config["num_bursts"])
     cap = max(800, 2 * int(config["num_burst_samples"]))      # two halves: a burst runs while the previous one is written
@@ -724,7 +825,8 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     posteriors = [Posterior(name, M, T, cfg["m"], num_samples, burst=int(config["num_burst_samples"]),
                             **({} if config["summaries"] == "off" else dict(summaries=config["summaries"])),
                             **(dict(forecast=(horizon, int(config["num_burst_samples"]) * int(config["num_bursts"]))) if horizon else {}),
-                            **(dict(rt=(rt_days, int(config["num_burst_samples"]) * int(config["num_bursts"]))) if rt_days else {}))
+                            **(dict(rt=(rt_days, int(config["num_burst_samples"]) * int(config["num_bursts"]))) if rt_days else {}),
+                            **(dict(check=(check_days, int(config["num_burst_samples"]) * int(config["num_bursts"]))) if check_days else {}))
                   for name in names]
     fc_kw = {}
     if horizon:
@@ -733,6 +835,10 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     if rt_days:
         N = np.asarray(cov.N, dtype=np.float64).reshape(-1)
         fc_kw["rt_weight"] = N / N.sum()                    # reproduction_number.py:82-83
+    if check_days:
+        from ..posterior.predict import check_calendar
+        fc_kw["check_calendar"] = check_calendar(cov, dates, T, check_days)
+        fc_kw["seed"] = seed
     run_mcmc(sampler, config, posteriors, pool_step_size=pool_step_size and total > 1, **fc_kw)
     if sampler.recoveries:
         print(f"{len(sampler.recoveries)} burst(s) were run again after a hand-off time-out (shared GPU?)", flush=True)
@@ -810,6 +916,13 @@ def main(argv=None):
                              "days (1..T) on the device (overrides Mcmc.rt; default off): a group rt/ with the mean, "
                              "variance and P(R > 1) per day and location, and the national curve per draw samples/R_t; "
                              "works with --summaries only, --thin and --forecast")
+    parser.add_argument("--check", type=int, default=None, metavar="K",
+                        help="simulate the last K observed days (1..min(T, 128)) again from every kept draw of the sampling "
+                             "phase and set them against the observed removals, on the device (overrides Mcmc.check; default "
+                             "off): a group check/ with the moments of the re-simulated window, the counts of draws below / "
+                             "at the data per cell, location, day and in total with their mid-p values, and per-draw "
+                             "samples/check_by_day, check_by_location, check_state_by_day; works with --summaries only, "
+                             "--thin, --forecast and --rt")
     args = parser.parse_args(argv)
     if args.thin is not None and args.thin < 1:
         parser.error(f"--thin {args.thin}: the thinning interval is >= 1")
@@ -818,7 +931,8 @@ def main(argv=None):
     mcmc(args.data_file, args.output, config["Mcmc"], seed=args.seed, num_chains=args.chains, device=args.device,
          pool_step_size=args.pool_step_size, init_jitter=args.init_jitter, events_dtype=args.events_dtype,
          hmc=args.hmc, moves=args.moves, thin=args.thin, summaries=args.summaries, diagnostics=args.diagnostics,
-         diagnostics_batch=args.diagnostics_batch, forecast=args.forecast, forecast_walk=args.forecast_walk, rt=args.rt)
+         diagnostics_batch=args.diagnostics_batch, forecast=args.forecast, forecast_walk=args.forecast_walk, rt=args.rt,
+         **({} if args.check is None else dict(check=args.check)))
 
 
 if __name__ == "__main__":

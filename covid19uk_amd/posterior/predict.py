@@ -56,6 +56,14 @@ def forecast_calendar(covar_data: model_spec.Covariates, dates, T, horizon):
     return prediction_calendar(covar_data.W, weekday, int(T), int(horizon))
 
 
+def check_calendar(covar_data: model_spec.Covariates, dates, T, days):
+    """(W [K], weekday_c [K]) of the last K of the T observed days, formed as `predict` forms them for
+    initial_step = T - K, num_steps = K: `prediction_weekday` over T days, centred over them, and the clipped W.  What
+    `run_mcmc` hands to `ChainSampler.reset_check`."""
+    weekday, _ = prediction_weekday(dates, int(T), covar_data.weekday)
+    return prediction_calendar(covar_data.W, weekday, int(T) - int(days), int(days))
+
+
 def predicted_incidence(posterior_samples, init_state, covar_data: model_spec.Covariates, init_step, num_steps,
                         out_of_sample=False, seed=0, device=0):
     """Simulate forward from the posterior state at `init_step` for `num_steps` days.

@@ -40,10 +40,12 @@ class Trace:
     marginals: dict = None   # MARGINAL_KEYS -> int64 [n,B,T,3] / [n,B,M,3] / [n,B,T,3]; None unless asked for
     forecast: dict = None    # FORECAST_KEYS -> int64 [n,B,H,3] / [n,B,M,3] / [n,B,H,3]; None unless the draws were forecast
     rt: np.ndarray = None    # [n,B,D] national R_t of every kept draw over the window; None unless asked for
+    check: dict = None       # CHECK_KEYS -> int64 [n,B,K,3] / [n,B,M,3] / [n,B,K,3]; None unless the draws were checked
 
 
 MARGINAL_KEYS = ("events_by_day", "events_by_location", "state_by_day")
 FORECAST_KEYS = ("forecast_by_day", "forecast_by_location", "forecast_state_by_day")
+CHECK_KEYS = ("check_by_day", "check_by_location", "check_state_by_day")
 SUMMARY_QUANTITIES = ("k_se", "k_ei", "k_ir", "S", "E", "I")
 
 
@@ -95,6 +97,53 @@ class RtSummary:
         return rt_prob_gt1(self.count, self.gt1)
 
 
+@dataclasses.dataclass
+class CheckSummary:
+    """The in-sample check folded since the last `reset_check` (include/seir_hip.h, "In-sample predictive check on the
+    device"), per chain: the moments of the re-simulated last K days (a `Summary` over [B,M,K,6]) and the integer counts
+    of the comparison with the observed removals.  gt is count - lt - eq; the mid-p values are formed by `mid_p`."""
+    moments: Summary
+    observed: np.ndarray     # [B,M,K] int32: the recorded I->R counts of the window
+    lt: np.ndarray           # [B,M,K] uint32: draws whose simulated I->R count is < observed
+    eq: np.ndarray           # [B,M,K] uint32: ... == observed
+    location_lt: np.ndarray  # [B,M]: the location's total over the window
+    location_eq: np.ndarray
+    day_lt: np.ndarray       # [B,K]: the day's total over the locations
+    day_eq: np.ndarray
+    total_lt: np.ndarray     # [B]: the whole window, all locations
+    total_eq: np.ndarray
+
+    @property
+    def count(self) -> np.ndarray:
+        return self.moments.count
+
+    @property
+    def pit(self) -> np.ndarray:
+        return mid_p(self.count, self.lt, self.eq)
+
+    @property
+    def location_pit(self) -> np.ndarray:
+        return mid_p(self.count, self.location_lt, self.location_eq)
+
+    @property
+    def day_pit(self) -> np.ndarray:
+        return mid_p(self.count, self.day_lt, self.day_eq)
+
+    @property
+    def total_pit(self) -> np.ndarray:
+        return mid_p(self.count, self.total_lt, self.total_eq)
+
+
+def mid_p(count, lt, eq):
+    """The mid-p value (lt + eq / 2) / count of an observed value among `count` simulated ones (count broadcast over the
+    leading axes); NaN, without a warning, where count = 0.  2 lt + eq < 2^22 is exact in float64 and so is the halving:
+    the result is the correctly rounded quotient (2 lt + eq) / (2 count)."""
+    n = _per_chain(count, lt)
+    num = 2.0 * np.asarray(lt, np.float64) + np.asarray(eq, np.float64)
+    ok = n > 0
+    return np.where(ok, num / np.where(ok, 2.0 * n, 1.0), np.nan)
+
+
 def rt_prob_gt1(count, gt1):
     """gt1 / n (count broadcast over the leading axes); NaN where n = 0."""
     n = _per_chain(count, gt1)
@@ -139,7 +188,7 @@ class PinnedTrace:
     `ChainSampler.read_trace_async`.  Views are valid until close()."""
 
     def __init__(self, sampler: "ChainSampler", count: int, events: bool = True, marginals: bool = False,
-                 forecast: int = 0, rt: int = 0):
+                 forecast: int = 0, rt: int = 0, check: int = 0):
         self._lib = sampler._lib
         self.count = int(count)
         B, P, M, T = sampler.B, sampler.P, sampler.M, sampler.T
@@ -160,6 +209,12 @@ class PinnedTrace:
                                  forecast_by_location=self._alloc((count, B, M, 3), np.int64),
                                  forecast_state_by_day=self._alloc((count, B, H, 3), np.int64))
         self.rt = self._alloc((count, B, int(rt)), np.float64) if rt else None
+        self.check = None
+        if check:
+            K = int(check)
+            self.check = dict(check_by_day=self._alloc((count, B, K, 3), np.int64),
+                              check_by_location=self._alloc((count, B, M, 3), np.int64),
+                              check_state_by_day=self._alloc((count, B, K, 3), np.int64))
 
     def _alloc(self, shape, dtype):
         nbytes = int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize
@@ -170,7 +225,7 @@ class PinnedTrace:
         return np.frombuffer(buf, dtype=dtype, count=int(np.prod(shape, dtype=np.int64))).reshape(shape)
 
     def close(self):
-        self.theta = self.events = self.hmc = self.moves = self.marginals = self.forecast = self.rt = None
+        self.theta = self.events = self.hmc = self.moves = self.marginals = self.forecast = self.rt = self.check = None
         for p in self._ptrs:
             self._lib.seir_host_free(p)
         self._ptrs = []
@@ -190,6 +245,7 @@ class ChainSampler:
     _forecast_H = 0               # horizon of the forecast in force (0: reset_forecast was never called)
     _fc_j = 0                     # draws per chain forecast since the last reset_forecast (the library's counter, mirrored)
     _rt_D = 0                     # window of the reproduction number in force (0: reset_rt was never called)
+    _check_K = 0                  # window of the in-sample check in force (0: reset_check was never called)
     first_chain_id = 0
 
     def __init__(self, model: SeirModel, config: dict, num_chains: int, seed: int = 0,
@@ -455,6 +511,8 @@ class ChainSampler:
             tr.forecast = {k: v[:n] for k, v in buf.forecast.items()}
         if buf.rt is not None:
             tr.rt = buf.rt[:n]
+        if getattr(buf, "check", None) is not None:
+            tr.check = {k: v[:n] for k, v in buf.check.items()}
         return tr
 
     # -- summaries of the recorded events on the device (include/seir_hip.h) --------------------------
@@ -633,6 +691,56 @@ class ChainSampler:
             raise ValueError("rt asked for before reset_rt")
         self.rt(first, count)
 
+    # -- in-sample check of the last K days (include/seir_hip.h, "In-sample predictive check on the device") ----------
+    def reset_check(self, days: int, W, weekday_c, seed: int = 0):
+        """Enable the check (first call), zero its moments, comparison counts, observed counts and flags, set the window
+        to the last `days` days (1 <= days <= min(T, 128)), its calendar (`W`, `weekday_c`: [days],
+        `posterior.predict.check_calendar`) and the seed of its Philox stream, and start its draw counter at 0."""
+        K = int(days)
+        if not 1 <= K <= min(self.T, _lib.CHECK_MAX_DAYS):
+            raise ValueError(f"check days {K}: 1 <= K <= min(T = {self.T}, {_lib.CHECK_MAX_DAYS})")
+        W = np.ascontiguousarray(W, dtype=np.float64).reshape(-1)
+        wd = np.ascontiguousarray(weekday_c, dtype=np.float64).reshape(-1)
+        if W.shape != (K,) or wd.shape != (K,):
+            raise ValueError(f"need W [{K}] and weekday_c [{K}]")
+        _lib.check(self._lib.seir_sampler_check_reset(self._s, K, _dptr(W), _dptr(wd), int(seed) & (2 ** 64 - 1)))
+        self._check_K = K
+
+    def check(self, first: int, count: int):
+        """Enqueue the check of trace slots [first, first+count) behind the sweeps that fill them: the window is simulated
+        again from every draw, folded, and counted against the draw's recorded removals."""
+        _lib.check(self._lib.seir_sampler_check(self._s, int(first), int(count)))
+
+    def read_check_marginals(self, count: int, first: int = 0) -> dict:
+        """Blocking read of the check's marginals of trace slots [first, first+count): CHECK_KEYS -> int64 arrays with
+        leading axes [count, B]."""
+        return self._read_marginal_set(self._lib.seir_sampler_read_check_marginals, CHECK_KEYS, self._check_K, count, first)
+
+    def read_check_marginals_async(self, count: int, first: int, into: PinnedTrace):
+        """As `read_marginals_async`, for the check's marginals; completed by `trace_wait()`."""
+        if int(count) > into.count or into.check is None:
+            raise ValueError("pinned buffer too small or without check arrays")
+        self._read_marginal_set(self._lib.seir_sampler_read_check_marginals_async, CHECK_KEYS, self._check_K, count, first,
+                                into.check)
+
+    def check_summary(self) -> CheckSummary:
+        """Moments and comparison counts folded since the last `reset_check` (blocking).  Raises `SeirError`
+        (SEIR_ERR_STATE) if an accumulator overflowed, if the observed removals differed between draws, or before a reset."""
+        B, M, K = self.B, self.M, self._check_K
+        u32 = ctypes.POINTER(ctypes.c_uint32)
+        obs = np.empty((B, M, K), np.int32)
+        shapes = ((B, M, K), (B, M, K), (B, M), (B, M), (B, K), (B, K), (B,), (B,))
+        arrs = [np.empty(sh, np.uint32) for sh in shapes]
+        _lib.check(self._lib.seir_sampler_read_check_counts(self._s, obs.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                            *(a.ctypes.data_as(u32) for a in arrs)))
+        mom = self._read_moments(self._lib.seir_sampler_read_check, K)
+        return CheckSummary(mom, obs, *arrs)
+
+    def _check_burst(self, first, count):
+        if not self._check_K:
+            raise ValueError("check asked for before reset_check")
+        self.check(first, count)
+
     def _summarize_mode(self, summarize):
         """`summarize` of sample / sample_bursts: False, True (marginals + moments) or "marginals" (accumulate = 0)."""
         if summarize not in (False, True, "marginals"):
@@ -642,7 +750,7 @@ class ChainSampler:
         return bool(summarize), summarize is True
 
     def sample_bursts(self, num_bursts: int, burst: int, consume, events: bool = True, summarize=False, marks=None,
-                      forecast=False, rt=False):
+                      forecast=False, rt=False, check=False):
         """`num_bursts` x `burst` kept draws (`burst * thin` sweeps each) with the burst buffer used as two halves:
         while burst k+1 runs on the device, burst k crosses PCIe into page-locked memory on a copy stream and `consume(trace, k)`
         (e.g. the HDF5 writer) runs on a worker thread -- the sampler only waits when the consumer is
@@ -664,7 +772,11 @@ class ChainSampler:
         (`trace.forecast`).
 
         `rt` (needs `reset_rt`): R_it of every burst's draws is formed and folded on the device right behind its summary
-        and forecast, and the national curves cross with the trace (`trace.rt`)."""
+        and forecast, and the national curves cross with the trace (`trace.rt`).
+
+        `check` (needs `reset_check`): the last K days of every burst's draws are simulated again and set against the data
+        on the device, behind the summary, the forecast and R_t; the check's marginals cross with the trace
+        (`trace.check`)."""
         from concurrent.futures import ThreadPoolExecutor
         do_sum, accumulate = self._summarize_mode(summarize)
         burst, num_bursts = int(burst), int(num_bursts)
@@ -673,7 +785,9 @@ class ChainSampler:
         # page-locking GBs of host memory takes tenths of a second: the two buffers are kept for the next call
         do_fc = bool(forecast)
         do_rt = bool(rt)
-        key = (burst, bool(events), do_sum, self._forecast_H if do_fc else 0) + ((self._rt_D,) if do_rt else ())
+        do_ck = bool(check)
+        key = (burst, bool(events), do_sum, self._forecast_H if do_fc else 0) + ((self._rt_D,) if do_rt else ()) + \
+            ((("check", self._check_K),) if do_ck else ())
         if getattr(self, "_pinned_key", None) != key:
             for bf in getattr(self, "_pinned", []):
                 bf.close()
@@ -682,6 +796,8 @@ class ChainSampler:
                 mk["forecast"] = self._forecast_H
             if do_rt:
                 mk["rt"] = self._rt_D
+            if do_ck:
+                mk["check"] = self._check_K
             self._pinned = [PinnedTrace(self, burst, events, **mk), PinnedTrace(self, burst, events, **mk)]
             self._pinned_key = key
         bufs = self._pinned
@@ -712,6 +828,8 @@ class ChainSampler:
                                 self._forecast_burst(h * burst, burst, forecast)
                             if do_rt:
                                 self._rt_burst(h * burst, burst)
+                            if do_ck:
+                                self._check_burst(h * burst, burst)
                         if prev >= 0:
                             self.trace_wait()                    # burst prev has landed (it crossed while burst i ran)
                             futs[prev & 1] = pool.submit(consume, self.trace_view(bufs[prev & 1], burst), prev)
@@ -725,6 +843,8 @@ class ChainSampler:
                                 self.read_forecast_marginals_async(burst, h * burst, bufs[h])
                             if do_rt:
                                 self.read_rt_draws_async(burst, h * burst, bufs[h])
+                            if do_ck:
+                                self.read_check_marginals_async(burst, h * burst, bufs[h])
                             prev = i
                             i += 1
                     except _lib.HandoffTimeout as e:
@@ -745,10 +865,10 @@ class ChainSampler:
             except _lib.HandoffTimeout:
                 pass
 
-    def sample(self, num_sweeps: int, events: bool = True, summarize=False, forecast=False, rt=False) -> Trace:
+    def sample(self, num_sweeps: int, events: bool = True, summarize=False, forecast=False, rt=False, check=False) -> Trace:
         """reset_trace + run + read: the analogue of one `sample_chain` call with `num_sweeps` results, each the last of
         `thin` sweeps.  `summarize` as in `sample_bursts`: the burst is summarised on the device and `trace.marginals`
-        filled; `forecast` likewise (`trace.forecast`), and `rt` (`trace.rt`)."""
+        filled; `forecast` likewise (`trace.forecast`), `rt` (`trace.rt`) and `check` (`trace.check`)."""
         do_sum, accumulate = self._summarize_mode(summarize)
         if num_sweeps > self.cap:
             raise ValueError(f"num_sweeps={num_sweeps} exceeds trace_capacity={self.cap}")
@@ -764,6 +884,8 @@ class ChainSampler:
                     self._forecast_burst(0, num_sweeps, forecast)
                 if rt:
                     self._rt_burst(0, num_sweeps)
+                if check:
+                    self._check_burst(0, num_sweeps)
                 tr = self.read_trace(num_sweeps, events=events)
                 if do_sum:
                     tr.marginals = self.read_marginals(num_sweeps)
@@ -771,6 +893,8 @@ class ChainSampler:
                     tr.forecast = self.read_forecast_marginals(num_sweeps)
                 if rt:
                     tr.rt = self.read_rt_draws(num_sweeps)
+                if check:
+                    tr.check = self.read_check_marginals(num_sweeps)
             except _lib.HandoffTimeout as e:
                 if not self.auto_recover:
                     raise

@@ -612,6 +612,81 @@ int seir_sampler_read_rt_draws_async(seir_sampler *s, int32_t first, int32_t cou
 int seir_sampler_read_rt(seir_sampler *s, uint64_t *count, double *ref, double *sum, double *sumsq, uint32_t *gt1);
 
 /* ------------------------------------------------------------------------
+ * In-sample predictive check on the device: the last K days against the data.
+ *
+ * Stands in for covid19uk/posterior/predict.py run in sample on every kept draw (`predict -i -K -n K`, predict.py:96-120)
+ * and for the comparison of its output with the observed removals: for each draw of trace slots
+ * [first_slot, first_slot + count) the last `days` observed days are simulated again from the draw's state at day T - days,
+ * folded into moments and per-draw marginals as the forecast's are, and counted against the data.  Neither the recorded
+ * nor the simulated event tensor crosses PCIe.
+ *
+ * Semantics (the one definition; kernels: csrc/check_kernels.h, the per-day machinery is the forecast's).
+ *   Window.  Check day s = 0 .. K - 1 is absolute day t = T - K + s.  The initial state of a draw is
+ *     S0 + stoichiometry . sum_{t' < T - K} events of that draw, integers formed on the device from the trace slot; K = T
+ *     starts from the context's initial state.
+ *   Log baseline of day t, the reference's indexing (model_spec.py:242-256; covid19uk_amd.posterior.predict
+ *     .log_baseline_path): alpha_0 if t = 0, otherwise alpha_0 + cumsum(alpha_t)[min(t - 1, T - 2)], the cumulative sum
+ *     taken sequentially in index order in fp64 and then added to alpha_0, which is what np.cumsum does.  No random walk:
+ *     the draw's own alpha_t.
+ *   Calendar.  W[t] and the centred weekday of the window, centred over the T observed days: host arrays handed over at the
+ *     reset (covid19uk_amd.posterior.predict.check_calendar, what `predict` builds for initial_step = T - K, num_steps = K).
+ *   Rates, binomial sampler, rate floor, nu, dt: seir_simulate's, through the same device functions as the forecast.
+ *   Random stream: seir_simulate's protocol -- Philox4x32-10, key = the seed given at the reset, counter = (attempt,
+ *     64 + transition, s M + m, draw id) -- with draw id = (global chain id << 20) + j, j being the number of that chain's
+ *     draws checked since the last check reset: a counter of its own, not the forecast's.  One seir_simulate call per chain
+ *     reproduces a check (first_draw_id = chain << 20, num_draws = n); nothing depends on how bursts are cut into calls or
+ *     batches, on the launch geometry or on how chains are sharded over samplers.
+ *   Moments and marginals: exactly the forecast's with K in the place of H: ref / sum / sumsq [B][M][K][6], count [B], the
+ *     sticky overflow flag, and per kept draw, int64, indexed by trace slot
+ *       check_by_day       [count][B][K][3]  sum_m k
+ *       check_by_location  [count][B][M][3]  sum_s k over the window
+ *       check_state_by_day [count][B][K][3]  sum_m (S, E, I)
+ *   Comparison with the data (csrc/check_update.h).  The I->R plane of every recorded draw is the data: no MH kernel
+ *     targets it (mcmc_kernel_factory.py:127-162 move S->E and E->I only).  Integers, one set per chain, uint32 (a chain
+ *     has fewer than 2^20 draws between two resets):
+ *       obs [B][M][K]  (int32)  the recorded I->R count at day T - K + s of the first draw folded after a reset
+ *       obs_moved [B]           sticky: a later draw's I->R counts in the window differ from obs (cannot happen with this
+ *                               sampler; it guards the assumption).  While it is up the reads below fail with SEIR_ERR_STATE
+ *       lt, eq [B][M][K]        draws whose simulated I->R count is < / == obs[m][s]
+ *       loc_lt, loc_eq [B][M]   the same for sum_s simulated against sum_s obs
+ *       day_lt, day_eq [B][K]   for sum_m simulated against sum_m obs
+ *       all_lt, all_eq [B]      for the whole window over all locations
+ *     gt is count - lt - eq and is not stored.  No floating-point value is accumulated anywhere in the comparison.
+ * Limits: 1 <= days <= min(T, SEIR_CHECK_MAX_DAYS); M <= 1280 (the simulator's); global chain ids below 2048; fewer than
+ * 2^20 draws per chain between two resets; record_events != 0.
+ *
+ * Switched on by the first seir_sampler_check_reset; a sampler that never calls it allocates and launches nothing more
+ * than before.  While it is on, seir_sampler_snapshot / _restore carry the accumulators, the comparison counts, obs, the
+ * flags and j, so that a burst run again after a hand-off time-out is checked and counted once.  A snapshot taken before
+ * the last reset holds none of it; restoring it leaves them as they are.
+ * ------------------------------------------------------------------------ */
+#define SEIR_CHECK_MAX_DAYS 128
+/* First call (and a call with another `days`) allocates; every call zeroes count, moments, comparison counts, obs and the
+ * flags in stream order, sets the window, calendar (W, weekday_c: [days], copied) and seed and starts j at 0 again.
+ * SEIR_ERR_INVALID for days outside [1, min(T, SEIR_CHECK_MAX_DAYS)], M > 1280 or a global chain id >= 2048;
+ * SEIR_ERR_STATE with record_events == 0. */
+int seir_sampler_check_reset(seir_sampler *s, int32_t days, const double *W, const double *weekday_c, uint64_t seed);
+/* Check the draws of trace slots [first_slot, first_slot + count) of every chain: asynchronous on the context stream,
+ * behind the sweeps that fill those slots.  SEIR_ERR_INVALID for slots outside the burst buffer or when j would reach
+ * 2^20, SEIR_ERR_STATE before a reset. */
+int seir_sampler_check(seir_sampler *s, int32_t first_slot, int32_t count);
+/* Blocking read of the check's moments: count [B]; ref, sum, sumsq each [B][M][days][6].  Any pointer may be NULL.
+ * SEIR_ERR_STATE (and a message) if the overflow flag is up, or before a reset. */
+int seir_sampler_read_check(seir_sampler *s, uint64_t *count, int32_t *ref, int64_t *sum, uint64_t *sumsq);
+/* Blocking read of the check's marginals of slots [first, first + count); any pointer may be NULL.  Host pointers. */
+int seir_sampler_read_check_marginals(seir_sampler *s, int32_t first, int32_t count, int64_t *check_by_day,
+                                      int64_t *check_by_location, int64_t *check_state_by_day);
+/* The same on the copy stream, with the stream and the wait of seir_sampler_read_marginals_async
+ * (seir_sampler_trace_wait completes it). */
+int seir_sampler_read_check_marginals_async(seir_sampler *s, int32_t first, int32_t count, int64_t *check_by_day,
+                                            int64_t *check_by_location, int64_t *check_state_by_day);
+/* Blocking read of the comparison with the data: obs, lt, eq [B][M][days]; loc_lt, loc_eq [B][M]; day_lt, day_eq [B][days];
+ * all_lt, all_eq [B].  Any pointer may be NULL.  SEIR_ERR_STATE (and a message) if a chain's obs_moved flag is up, or
+ * before a reset. */
+int seir_sampler_read_check_counts(seir_sampler *s, int32_t *obs, uint32_t *lt, uint32_t *eq, uint32_t *loc_lt,
+                                   uint32_t *loc_eq, uint32_t *day_lt, uint32_t *day_eq, uint32_t *all_lt, uint32_t *all_eq);
+
+/* ------------------------------------------------------------------------
  * Reproduction number R_it.
  *
  * calc_posterior_rit (covid19uk/posterior/reproduction_number.py:13-44): for each
