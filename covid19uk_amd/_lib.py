@@ -70,6 +70,7 @@ MOVE_TRACE = 2 + 4 * MMAX     # SEIR_MOVE_TRACE
 FORECAST_MAX_H = 128          # SEIR_FORECAST_MAX_H
 FORECAST_ID_SHIFT, FORECAST_MAX_CHAIN = 20, 2048   # draw id = (global chain id << 20) + j
 CHECK_MAX_DAYS = 128          # SEIR_CHECK_MAX_DAYS
+ORDER_STATS_MAX_RANKS = 16    # SEIR_ORDER_STATS_MAX_RANKS
 
 
 class SeirError(RuntimeError):
@@ -178,6 +179,13 @@ _SIGNATURES = {
     "seir_sampler_read_forecast": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
                                                   ctypes.POINTER(ctypes.c_int32), c_int64_p,
                                                   ctypes.POINTER(ctypes.c_uint64)]),
+    # forecast intervals: the draw store and exact order statistics of its cells; the selection alone on host arrays
+    "seir_sampler_forecast_keep": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
+    "seir_sampler_forecast_order_stats": (ctypes.c_int, [ctypes.c_void_p, c_int64_p, ctypes.c_int32, ctypes.c_int32,
+                                                         ctypes.POINTER(ctypes.c_int32)]),
+    "seir_order_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, ctypes.c_int32,
+                                        ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_int64_p, ctypes.c_int32,
+                                        ctypes.POINTER(ctypes.c_int32)]),
     # in-sample check of the last K days from the burst buffer: moments, marginals and the comparison with the data
     "seir_sampler_check_reset": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_double_p, c_double_p, ctypes.c_uint64]),
     "seir_sampler_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]),

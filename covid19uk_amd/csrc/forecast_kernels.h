@@ -18,6 +18,8 @@
 //       tensor fev[ND][M][H][3].
 //   k_forecast_fold           once per batch: k_summarize<0, 0> over the H forecast days of the staging tensor, with its
 //       pieces (summary_kernels.h) and the state scanned from the PER-DRAW initial state St0.
+//   k_forecast_keep           once per batch, behind the fold and only while the draw store is on: cases, cumulative cases
+//       and prevalence of every (row, day, draw) into keep[B][3][M][H][cap], for the exact quantiles of k_order_stats.
 //   k_forecast_finish         k_summary_finish's body with St0: state_by_day from the finished by-day sums; advances count[b].
 // The accumulators and marginals are a MomentBufs (ForecastBufs::mom), as the summaries' are.
 // Random numbers are k_simulate's protocol: Philox4x32-10, key = forecast seed, counter = (attempt, 64 + transition,
@@ -228,6 +230,80 @@ __global__ __launch_bounds__(64 * FC_ROWS) void k_forecast_fold(Dims d, Forecast
             sb.by_loc[(((size_t)(first + j) * B + b) * M + m) * 3 + x] = (int64_t)carry[wv][j][x];
         }
     if (ovf) sb.overflow[0] = 1u;
+}
+
+// The draw store of the forecast intervals (include/seir_hip.h, "Forecast intervals on the device"): three int32 per
+// (chain, location, day, draw) kept in keep[B][3][M][H][cap], the draw index innermost, so that a cell's draws are one
+// contiguous run for k_order_stats (order_stats_kernels.h).  The planes, for day s of the window:
+//     0 cases       k_ir[m][s]
+//     1 cum_cases   sum_{s' <= s} k_ir[m][s']
+//     2 prevalence  I at the START of day s: I0 + exclusive scan of k_ei - exclusive scan of k_ir (quantity 5 of the fold)
+// ev is a batch's staging tensor [ND][M][H][3] (nd = slot_in_batch * B + chain) and I0 [Mp][ndp] the I plane of the
+// per-draw state at the window's start; the draw of slot_in_batch jj goes to position j0 + jj of its chain's cells (the
+// host checks j0 + count <= cap).  Nothing here is the forecast's alone: the in-sample check has the same two tensors.
+// A wave per (row, chain), a lane per day, the draws in flushes of KEEP_JB: the three values go through an LDS tile
+// [plane][day][draw of the flush] (rows padded by one word: the lanes of a store are a row apart) and leave it with the
+// lanes along the DRAW axis -- every cell receives one run of up to KEEP_JB int32, not a 4-byte store at a stride of cap.
+// grid (ceil(M / KEEP_ROWS), B), 64 KEEP_ROWS threads.  1 <= count <= FC_JMAX.
+constexpr int KEEP_ROWS = 2;       // waves (rows) per workgroup
+constexpr int KEEP_JB = 32;        // draws per flush: a cell's run is up to 128 B
+constexpr int KEEP_U = 4;          // draws whose loads are in flight together
+static_assert(KEEP_JB <= 64 && KEEP_JB % KEEP_U == 0, "a lane per carry; whole groups of loads");
+
+__global__ __launch_bounds__(64 * KEEP_ROWS) void k_forecast_keep(Dims d, const int *__restrict__ ev,
+                                                                  const int *__restrict__ I0, int *__restrict__ keep,
+                                                                  long long cap, long long j0, int H, int B, int count,
+                                                                  int ndp) {
+    debug_skew(d);
+    __shared__ int tile[KEEP_ROWS][3][64][KEEP_JB + 1];
+    __shared__ int carry[KEEP_ROWS][KEEP_JB][2];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int b = blockIdx.y, m = blockIdx.x * KEEP_ROWS + wv;
+    const int M = d.M;
+    const bool row_ok = m < M;
+    const int mr = row_ok ? m : 0;
+    for (int jb = 0; jb < count; jb += KEEP_JB) {
+        const int nj = min(KEEP_JB, count - jb);
+        if (lane < KEEP_JB) { carry[wv][lane][0] = 0; carry[wv][lane][1] = 0; }
+        __syncthreads();
+        for (int h0 = 0; h0 < H; h0 += 64) {
+            const int s = h0 + lane;
+            const bool live = row_ok && s < H;
+            for (int ju = 0; ju < nj; ju += KEEP_U) {
+                int kk[KEEP_U][3], i0[KEEP_U];
+#pragma unroll
+                for (int u = 0; u < KEEP_U; ++u) {
+                    const bool on = ju + u < nj;
+                    const int nd = (jb + (on ? ju + u : 0)) * B + b;
+                    summary_load<0>(ev, ((size_t)nd * M + mr) * H + (s < H ? s : 0), live && on, kk[u]);
+                    i0[u] = I0[(size_t)mr * ndp + nd];
+                }
+#pragma unroll
+                for (int u = 0; u < KEEP_U; ++u) {
+                    const int jj = ju + u;
+                    if (jj < nj) {                                     // uniform over the wave: the scans see every lane
+                        const int inc_ei = wave_incl_scan(kk[u][1], lane), inc_ir = wave_incl_scan(kk[u][2], lane);
+                        const int c_ei = carry[wv][jj][0], c_ir = carry[wv][jj][1];
+                        tile[wv][0][lane][jj] = kk[u][2];
+                        tile[wv][1][lane][jj] = c_ir + inc_ir;
+                        tile[wv][2][lane][jj] = i0[u] + (c_ei + inc_ei - kk[u][1]) - (c_ir + inc_ir - kk[u][2]);
+                        if (lane == 63) { carry[wv][jj][0] = c_ei + inc_ei; carry[wv][jj][1] = c_ir + inc_ir; }
+                    }
+                }
+            }
+            __syncthreads();
+            const int cnt = min(64, H - h0) * nj;
+            if (row_ok)
+                for (int i = lane; i < cnt; i += 64) {
+                    const int tl = i / nj, jj = i - tl * nj;
+#pragma unroll
+                    for (int x = 0; x < 3; ++x)
+                        keep[((((size_t)b * 3 + x) * M + m) * H + (h0 + tl)) * (size_t)cap + (size_t)(j0 + jb + jj)] =
+                            tile[wv][x][tl][jj];
+                }
+            __syncthreads();
+        }
+    }
 }
 
 // k_summary_finish over the H forecast days, with the draw's own initial state St0.  grid (count, B), one wave.

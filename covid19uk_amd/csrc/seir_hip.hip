@@ -23,6 +23,7 @@
 #include "forecast_kernels.h"
 #include "check_kernels.h"
 #include "rt_trace_kernels.h"
+#include "order_stats_kernels.h"
 
 using namespace seir;
 
@@ -1151,6 +1152,8 @@ struct seir_sampler {
     double *fc_steps_dev = nullptr;   // [fc_slots * B][H]
     hipEvent_t fc_ev_steps = nullptr; // behind the last upload from fc_steps_host
     bool fc_steps_pending = false;
+    int *fc_keep = nullptr;           // the draw store keep[B][3][M][H][fc_keep_cap] (seir_sampler_forecast_keep), or null: off
+    long long fc_keep_cap = 0;        // draws per chain it holds; position j of a cell is the draw with the forecast's j
     // --- in-sample check of the last K days (seir_sampler_check_reset ...; check_kernels.h): a ForecastBufs with H := K ---
     bool ck_on = false;
     ForecastBufs ck{};
@@ -1212,6 +1215,7 @@ extern "C" void seir_sampler_destroy(seir_sampler *s) {
     acc_free(s->sum_acc); acc_free(s->diag_buf); acc_free(s->fc_acc); acc_free(s->rt_acc);
     acc_free(s->ck_acc); acc_free(s->ck_cnt);
     if (s->fc_steps_host) (void)hipHostFree(s->fc_steps_host);
+    if (s->fc_keep) (void)hipFree(s->fc_keep);
     if (s->fc_ev_steps) (void)hipEventDestroy(s->fc_ev_steps);
     Work &w = s->ctx->w;
     for (int x = 0; x < 3; ++x) { w.K[x] = nullptr; w.St[x] = nullptr; }
@@ -2416,6 +2420,7 @@ extern "C" int seir_sampler_forecast_reset(seir_sampler *s, int32_t horizon, con
         s->fc_allocs.clear();
         acc_free(s->fc_acc);
         if (s->fc_steps_host) { (void)hipHostFree(s->fc_steps_host); s->fc_steps_host = nullptr; }
+        if (s->fc_keep) { (void)hipFree(s->fc_keep); s->fc_keep = nullptr; s->fc_keep_cap = 0; }   // sized by H as well
         s->fc_on = false;
         fb = ForecastBufs{};
         s->fc_slots = std::min(s->cfg.cap, FC_JMAX);
@@ -2443,7 +2448,7 @@ extern "C" int seir_sampler_forecast_reset(seir_sampler *s, int32_t horizon, con
     HIP_TRY(hipMemcpyAsync(const_cast<double *>(fb.wd), weekday_c, sizeof(double) * H, hipMemcpyHostToDevice, st));
     if ((rc = acc_zero(s->fc_acc, st))) return rc;
     HIP_TRY(hipStreamSynchronize(st));
-    s->fc_j = 0;
+    s->fc_j = 0;                                     // ... which empties the draw store too: it holds draws [0, fc_j)
     // what the snapshots taken before this reset hold of the forecast is dropped with it: restoring one of them restores
     // the chain and leaves the forecast accumulators and j as they are
     acc_invalidate(s->fc_acc);
@@ -2458,6 +2463,9 @@ extern "C" int seir_sampler_forecast(seir_sampler *s, int32_t first, int32_t cou
     if (s->fc_j + count > (1ll << FC_ID_SHIFT))
         return fail(SEIR_ERR_INVALID, "%lld draws per chain forecast since the reset and %d more: the draw id holds 2^%d", s->fc_j,
                     count, FC_ID_SHIFT);
+    if (s->fc_keep && s->fc_j + count > s->fc_keep_cap)
+        return fail(SEIR_ERR_INVALID, "%lld draws per chain forecast since the reset and %d more: the draw store holds %lld "
+                    "(seir_sampler_forecast_keep)", s->fc_j, count, s->fc_keep_cap);
     seir_ctx *ctx = s->ctx;
     const LaunchCfg l = whole(ctx, s->cfg.B);
     const Dims &d = l.d;
@@ -2500,6 +2508,10 @@ extern "C" int seir_sampler_forecast(seir_sampler *s, int32_t first, int32_t cou
         }
         hipLaunchKernelGGL(k_forecast_fold, dim3((d.M + FC_ROWS - 1) / FC_ROWS, B), dim3(64 * FC_ROWS), 0, l.st, d, fb, B,
                            first + j0, nj, ndp);
+        if (s->fc_keep)
+            hipLaunchKernelGGL(k_forecast_keep, dim3((d.M + KEEP_ROWS - 1) / KEEP_ROWS, B), dim3(64 * KEEP_ROWS), 0, l.st, d,
+                               (const int *)fb.fev, (const int *)(fb.St0 + 2 * (size_t)d.Mp * ndp), s->fc_keep, s->fc_keep_cap,
+                               s->fc_j + j0, H, B, nj, ndp);
         hipLaunchKernelGGL(k_forecast_finish, dim3(nj, B), dim3(64), 0, l.st, d, fb, B, first + j0, nj, ndp);
     }
     if (log_baseline_steps) { HIP_TRY(hipEventRecord(s->fc_ev_steps, l.st)); s->fc_steps_pending = true; }
@@ -2532,6 +2544,132 @@ extern "C" int seir_sampler_read_forecast(seir_sampler *s, uint64_t *count, int3
     if (rc) return rc;
     if ((rc = trace_range_check(s, s->fc_on, FORECAST_USER))) return rc;
     return read_moments(s, s->fc_acc, "forecast's ", "seir_sampler_forecast_reset", count, ref, sum, sumsq);
+}
+
+// ---------------------------------------------------------------------------
+// Forecast intervals on the device (include/seir_hip.h; kernels: k_forecast_keep, order_stats_kernels.h)
+// ---------------------------------------------------------------------------
+extern "C" int seir_sampler_forecast_keep(seir_sampler *s, int64_t cap) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = trace_range_check(s, s->fc_on, FORECAST_USER))) return rc;
+    if (cap < 0 || cap > (1ll << FC_ID_SHIFT))
+        return fail(SEIR_ERR_INVALID, "cap=%lld outside [0, 2^%d]: the draws per chain between two resets", (long long)cap, FC_ID_SHIFT);
+    hipStream_t st = s->ctx->stream;
+    if (cap == 0) {
+        if (s->fc_keep) {
+            HIP_TRY(hipStreamSynchronize(st));
+            (void)hipFree(s->fc_keep);
+            s->fc_keep = nullptr; s->fc_keep_cap = 0;
+        }
+        return 0;
+    }
+    if (s->fc_j != 0)
+        return fail(SEIR_ERR_STATE, "%lld draws per chain have been forecast since the reset: the draw store is sized between "
+                    "seir_sampler_forecast_reset and the first seir_sampler_forecast", s->fc_j);
+    if (s->fc_keep && s->fc_keep_cap == cap) return 0;       // the reset has emptied it
+    if (s->fc_keep) {
+        HIP_TRY(hipStreamSynchronize(st));
+        (void)hipFree(s->fc_keep);
+        s->fc_keep = nullptr; s->fc_keep_cap = 0;
+    }
+    const unsigned long long cells = 3ull * s->cfg.B * s->ctx->d.M * s->fc.H, bytes = cells * (unsigned long long)cap * 4ull;
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    // half of what is free: the policy of a device that is shared, not a measurement
+    if (bytes > (unsigned long long)free_b / 2)
+        return fail(SEIR_ERR_INVALID, "the draw store needs %llu bytes (%d chains x 3 x %d locations x %d days x %lld draws x 4), "
+                    "more than half of the %llu bytes free on the device", bytes, s->cfg.B, s->ctx->d.M, s->fc.H, (long long)cap,
+                    (unsigned long long)free_b);
+    void *q = nullptr;
+    HIP_TRY(hipMalloc(&q, (size_t)bytes));
+    if (hipMemsetAsync(q, 0, (size_t)bytes, st) != hipSuccess) { (void)hipFree(q); return fail(SEIR_ERR_DEVICE, "hipMemsetAsync failed"); }
+    s->fc_keep = (int *)q;
+    s->fc_keep_cap = cap;
+    return 0;
+}
+
+// ranks [R] strictly increasing in [0, n): into OrderArgs, or the refusal.
+static int order_ranks(const int64_t *ranks, int32_t R, long long n, OrderArgs &a) {
+    if (R < 1 || R > ORDER_MAX_RANKS) return fail(SEIR_ERR_INVALID, "R=%d outside [1, %d]", R, ORDER_MAX_RANKS);
+    if (!ranks) return fail(SEIR_ERR_INVALID, "null ranks pointer");
+    for (int r = 0; r < R; ++r) {
+        if (ranks[r] < 0 || ranks[r] >= n)
+            return fail(SEIR_ERR_INVALID, "rank %lld outside [0, n=%lld)", (long long)ranks[r], n);
+        if (r && ranks[r] <= ranks[r - 1])
+            return fail(SEIR_ERR_INVALID, "ranks must be strictly increasing: %lld after %lld", (long long)ranks[r], (long long)ranks[r - 1]);
+        a.ranks[r] = (uint32_t)ranks[r];
+    }
+    a.R = R;
+    return 0;
+}
+
+static void order_launch(const OrderArgs &a, hipStream_t st) {
+    if ((long long)a.segs * a.seg_len <= ORDER_WAVE_N) hipLaunchKernelGGL(k_order_stats<1>, dim3((unsigned)a.cells), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(k_order_stats<4>, dim3((unsigned)a.cells), dim3(256), 0, st, a);
+}
+
+extern "C" int seir_sampler_forecast_order_stats(seir_sampler *s, const int64_t *ranks, int32_t R, int32_t pooled, int32_t *out) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = trace_range_check(s, s->fc_on, FORECAST_USER))) return rc;
+    if (!s->fc_keep) return fail(SEIR_ERR_STATE, "the draw store is not enabled: call seir_sampler_forecast_keep first");
+    if (!out) return fail(SEIR_ERR_INVALID, "null output pointer");
+    if (s->fc_j < 1) return fail(SEIR_ERR_STATE, "no draws kept since the forecast reset");
+    const int B = s->cfg.B;
+    hipStream_t st = s->ctx->stream;
+    std::vector<uint64_t> cnt((size_t)B);
+    HIP_TRY(hipMemcpyAsync(cnt.data(), s->fc.mom.count, sizeof(uint64_t) * B, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int b = 0; b < B; ++b)
+        if ((long long)cnt[b] != s->fc_j)
+            return fail(SEIR_ERR_STATE, "chain %d has %llu draws forecast, the store %lld: the chains' counts differ", b,
+                        (unsigned long long)cnt[b], s->fc_j);
+    const long long plane = 3ll * s->ctx->d.M * s->fc.H;
+    OrderArgs a{};
+    if ((rc = order_ranks(ranks, R, pooled ? s->fc_j * B : s->fc_j, a))) return rc;
+    a.values = s->fc_keep;
+    a.cells = pooled ? plane : plane * B;
+    a.segs = pooled ? B : 1;
+    a.seg_len = s->fc_j;
+    a.seg_stride = plane * s->fc_keep_cap;
+    a.cell_stride = s->fc_keep_cap;
+    DevBuf dout;
+    const size_t nout = (size_t)R * (size_t)a.cells;
+    if ((rc = dout.alloc(sizeof(int32_t) * nout))) return rc;
+    a.out = dout.as<int32_t>();
+    order_launch(a, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, dout.p, sizeof(int32_t) * nout, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int seir_order_stats(seir_ctx *ctx, const int32_t *values, int64_t cells, int32_t segs, int64_t seg_len,
+                                int64_t seg_stride, int64_t cell_stride, const int64_t *ranks, int32_t R, int32_t *out) {
+    int rc = check_batch(ctx, 1);
+    if (rc) return rc;
+    if (!values || !out) return fail(SEIR_ERR_INVALID, "null pointer");
+    if (cells < 1 || cells > 0x7fffffffll || segs < 1 || seg_len < 1 || (long long)segs * seg_len > 0x7fffffffll)
+        return fail(SEIR_ERR_INVALID, "cells=%lld, segs=%d, seg_len=%lld: at least one of each, n = segs x seg_len and cells below 2^31",
+                    (long long)cells, segs, (long long)seg_len);
+    if (cell_stride < 0 || seg_stride < 0 || (segs > 1 && seg_stride < seg_len))
+        return fail(SEIR_ERR_INVALID, "seg_stride=%lld, cell_stride=%lld: no negative stride, and segments do not overlap",
+                    (long long)seg_stride, (long long)cell_stride);
+    OrderArgs a{};
+    if ((rc = order_ranks(ranks, R, (long long)segs * seg_len, a))) return rc;
+    const size_t extent = (size_t)(cells - 1) * cell_stride + (size_t)(segs - 1) * seg_stride + (size_t)seg_len;
+    const size_t nout = (size_t)R * (size_t)cells;
+    DevBuf dv, dout;
+    if ((rc = dv.alloc(sizeof(int32_t) * extent)) || (rc = dout.alloc(sizeof(int32_t) * nout))) return rc;
+    HIP_TRY(hipMemcpyAsync(dv.p, values, sizeof(int32_t) * extent, hipMemcpyHostToDevice, ctx->stream));
+    a.values = dv.as<int32_t>(); a.out = dout.as<int32_t>();
+    a.cells = cells; a.segs = segs; a.seg_len = seg_len; a.seg_stride = seg_stride; a.cell_stride = cell_stride;
+    order_launch(a, ctx->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, dout.p, sizeof(int32_t) * nout, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
 }
 
 // ---------------------------------------------------------------------------

@@ -231,6 +231,17 @@ class Posterior:
         self.create_dataset("forecast/count", np.array([float(count)]))
         self._write_moments("forecast", mean, var)
 
+    def write_forecast_quantiles(self, probs, chain, pooled, pooled_chains):
+        """forecast/quantile_probs [K]; forecast/cases_quantiles, cum_cases_quantiles, prevalence_quantiles, each [K,M,H]
+        float64 over this chain's draws (`chain` [K,3,M,H]); forecast/pooled_* likewise over the draws of all chains of the
+        process (`pooled` [K,3,M,H], the same in every chain's file) with forecast/pooled_chains, their global ids."""
+        from ..sampler import FORECAST_QUANTILE_PLANES
+        self.create_dataset("forecast/quantile_probs", np.asarray(probs, np.float64))
+        self.create_dataset("forecast/pooled_chains", np.asarray(pooled_chains, np.float64))
+        for x, name in enumerate(FORECAST_QUANTILE_PLANES):
+            self.create_dataset(f"forecast/{name}_quantiles", np.ascontiguousarray(chain[:, x], dtype=np.float64))
+            self.create_dataset(f"forecast/pooled_{name}_quantiles", np.ascontiguousarray(pooled[:, x], dtype=np.float64))
+
     def write_rt(self, days, first_day, count, mean, var, prob_gt1):
         """The group rt/ of one chain: days [1], first_day [1] (= T - D, the absolute day of the window's first day),
         count [1] and R_it_mean, R_it_var, R_it_prob_gt1 over the draws folded (`RtSummary` rows), each [D,M]."""
@@ -397,6 +408,18 @@ def forecast_mode(config, override=None, walk=None):
     return H, w
 
 
+def forecast_quantiles_mode(config, override=None, horizon=None):
+    """Mcmc.forecast_quantiles (absent: off), or the command line's `--forecast-quantiles 0.05,0.5,0.95`: the tuple of
+    probabilities whose exact per-location quantiles of the forecast draws are formed on the device; () for off.  1 to 8
+    probabilities in [0, 1], strictly increasing (`posterior.quantiles.parse_probs`).  With `horizon` given (0: the
+    forecast is off) quantiles without a forecast are refused.  The one place that validates -- before a sampler exists."""
+    from ..posterior.quantiles import parse_probs
+    probs = parse_probs(config.get("forecast_quantiles") if override is None else override)
+    if probs and horizon is not None and not horizon:
+        raise ValueError("forecast_quantiles given without forecast: it would have no effect")
+    return probs
+
+
 def rt_mode(config, override=None, T=None):
     """Mcmc.rt (absent: off), or the command line's `--rt D`: the number of days D of the window [T - D, T) over which the
     reproduction number of every kept draw of the sampling phase is formed on the device; 0 for off.  1 <= D, and D <= T
@@ -512,6 +535,11 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     behind its burst; `forecast_calendar` = (W [H], weekday_c [H]) (`posterior.predict.forecast_calendar`) and `seed`
     (the forecast's Philox stream and, with forecast_walk, the steps) are then needed.  The warm-up is not forecast.
 
+    With Mcmc.forecast_quantiles (`forecast_quantiles_mode`; needs Mcmc.forecast) the device keeps cases, cumulative cases
+    and prevalence of every forecast draw: the store is sized once, right behind the forecast's reset, for num_bursts x
+    num_burst_samples draws per chain, and at the end of the run exact quantiles per location and forecast day are selected
+    on the device, per chain and pooled over the chains of this process.  Without the key nothing of it is called.
+
     With Mcmc.rt = D (`rt_mode`) R_it of every kept draw of the sampling phase over the last D days is formed and folded
     on the device behind its burst (and behind the burst's summary and forecast); `rt_weight` [M] = N / N.sum() is then
     needed.  The warm-up is not folded; without the key nothing of it is called.
@@ -530,6 +558,7 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     horizon, walk = forecast_mode(config)
     if horizon and forecast_calendar is None:
         raise ValueError("forecast: run_mcmc needs forecast_calendar = (W, weekday_c) of the forecast days")
+    fq_probs = forecast_quantiles_mode(config, horizon=horizon)
     summaries = summaries_mode(config)
     # "off": sample / sample_bursts are called exactly as before the option existed.  Otherwise every written draw gets its
     # marginals (the warm-up without folding), the moments cover the sampling phase, and with "only" no event tensor is read
@@ -609,6 +638,8 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
         sampler.reset_summary()                             # the moments are over the sampling phase
     if horizon:
         sampler.reset_forecast(horizon, forecast_calendar[0], forecast_calendar[1], seed)   # once: the sampling phase
+        if fq_probs:
+            sampler.keep_forecast_draws(nb * ns)            # the draw store of the quantiles: every kept draw of the phase
         first_id = getattr(sampler, "first_chain_id", 0)
         burst_kw = dict(burst_kw, forecast=forecast_steps_fn(seed, [first_id + c for c in range(sampler.B)], horizon)
                         if walk else True)
@@ -669,6 +700,15 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
         print(f"Forecast: {horizon} day(s) from day {sampler.T} for {int(fs.count.min()) if len(fs.count) else 0} kept draw(s) per "
               f"chain, formed on the device ({'random-walk' if walk else 'held'} baseline); forecast/* and "
               "samples/forecast_* written", file=log, flush=True)
+        if fq_probs and nb * ns:
+            first_id = getattr(sampler, "first_chain_id", 0)
+            own = sampler.forecast_quantiles(fq_probs)                  # [K,B,3,M,H]
+            pooled = sampler.forecast_quantiles(fq_probs, pooled=True)  # [K,3,M,H]
+            for c, post in enumerate(posteriors):
+                post.write_forecast_quantiles(fq_probs, own[:, c], pooled, [first_id + b for b in range(sampler.B)])
+            print(f"Forecast quantiles: {', '.join(f'{p:g}' for p in fq_probs)} of cases, cumulative cases and prevalence per "
+                  f"location and forecast day, exact over {nb * ns} kept draw(s) per chain and pooled over the {sampler.B} "
+                  "chain(s) of this process, selected on the device; forecast/*_quantiles written", file=log, flush=True)
     if rt_days:
         rs = sampler.rt_summary()
         mean, var, prob = rs.mean, rs.var, rs.prob_gt1
@@ -747,7 +787,7 @@ def launch_forms(lay, device_arg, hmc="auto", moves="auto", env=os.environ):
 
 def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool_step_size=False, init_jitter=0.0,
          events_dtype="auto", hmc="auto", moves="auto", thin=None, summaries=None, diagnostics=None, diagnostics_batch=None,
-         forecast=None, forecast_walk=None, rt=None, check=None):
+         forecast=None, forecast_walk=None, rt=None, check=None, forecast_quantiles=None):
     """Constructs and runs the MCMC (covid19uk/inference/inference.py:473-608).
 
     Multi-GPU: launched as one process per GPU, every rank runs `num_chains` chains with
@@ -757,7 +797,8 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     per chain after warm-up.  `thin` overrides config["thin"] (every rank is given the same value), `summaries`
     config["summaries"] (`summaries_mode`), `diagnostics` / `diagnostics_batch` config["diagnostics"] /
     config["diagnostics_batch"] (`diagnostics_mode`), `forecast` / `forecast_walk` config["forecast"] /
-    config["forecast_walk"] (`forecast_mode`), `rt` config["rt"] (`rt_mode`), `check` config["check"] (`check_mode`)."""
+    config["forecast_walk"] (`forecast_mode`), `forecast_quantiles` config["forecast_quantiles"]
+    (`forecast_quantiles_mode`), `rt` config["rt"] (`rt_mode`), `check` config["check"] (`check_mode`)."""
     check_days = 0
     if check is not None or "check" in config:
         check_days = check_mode(config, check)              # refused here: before any GPU call
@@ -776,6 +817,11 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
         config = {k: v for k, v in config.items() if k not in ("forecast", "forecast_walk")}
         if horizon:
             config = dict(config, forecast=horizon, forecast_walk=walk)
+    if forecast_quantiles is not None or "forecast_quantiles" in config:
+        fq_probs = forecast_quantiles_mode(config, forecast_quantiles, horizon=horizon)   # refused here: before any GPU call
+        config = {k: v for k, v in config.items() if k != "forecast_quantiles"}
+        if fq_probs:
+            config = dict(config, forecast_quantiles=list(fq_probs))
     config = dict(config, thin=thin_interval(config, thin))  # refused here if < 1: before any GPU call
     config = dict(config, summaries=summaries_mode(config, summaries))    # an unknown value likewise
     if diagnostics is not None or diagnostics_batch is not None or "diagnostics" in config or "diagnostics_batch" in config:
@@ -911,6 +957,11 @@ def main(argv=None):
     parser.add_argument("--forecast-walk", action="store_true", default=None,
                         help="let the forecast's log baseline continue as the prior's random walk (N(0, 0.005) steps) "
                              "instead of holding its last value (overrides Mcmc.forecast_walk; needs --forecast)")
+    parser.add_argument("--forecast-quantiles", type=str, default=None, metavar="P,P,...",
+                        help="exact quantiles of the forecast draws per location and forecast day, selected on the device "
+                             "(overrides Mcmc.forecast_quantiles; needs --forecast): 1 to 8 increasing probabilities in [0, 1], "
+                             "e.g. 0.05,0.5,0.95; forecast/cases_quantiles, cum_cases_quantiles, prevalence_quantiles per "
+                             "chain and forecast/pooled_* over the chains of the process; works with --summaries only and --thin")
     parser.add_argument("--rt", type=int, default=None, metavar="D",
                         help="form the reproduction number R_it of every kept draw of the sampling phase over the last D "
                              "days (1..T) on the device (overrides Mcmc.rt; default off): a group rt/ with the mean, "
@@ -932,7 +983,8 @@ def main(argv=None):
          pool_step_size=args.pool_step_size, init_jitter=args.init_jitter, events_dtype=args.events_dtype,
          hmc=args.hmc, moves=args.moves, thin=args.thin, summaries=args.summaries, diagnostics=args.diagnostics,
          diagnostics_batch=args.diagnostics_batch, forecast=args.forecast, forecast_walk=args.forecast_walk, rt=args.rt,
-         **({} if args.check is None else dict(check=args.check)))
+         **({} if args.check is None else dict(check=args.check)),
+         **({} if args.forecast_quantiles is None else dict(forecast_quantiles=args.forecast_quantiles)))
 
 
 if __name__ == "__main__":

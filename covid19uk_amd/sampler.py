@@ -45,6 +45,7 @@ class Trace:
 
 MARGINAL_KEYS = ("events_by_day", "events_by_location", "state_by_day")
 FORECAST_KEYS = ("forecast_by_day", "forecast_by_location", "forecast_state_by_day")
+FORECAST_QUANTILE_PLANES = ("cases", "cum_cases", "prevalence")   # the planes of the draw store (keep_forecast_draws)
 CHECK_KEYS = ("check_by_day", "check_by_location", "check_state_by_day")
 SUMMARY_QUANTITIES = ("k_se", "k_ei", "k_ir", "S", "E", "I")
 
@@ -638,6 +639,36 @@ class ChainSampler:
         """The forecast moments folded since the last `reset_forecast` (blocking): a `Summary` whose day axis is the H
         forecast days, [B,M,H,6].  Raises `SeirError` (SEIR_ERR_STATE) if an accumulator overflowed or before a reset."""
         return self._read_moments(self._lib.seir_sampler_read_forecast, self._forecast_H)
+
+    # -- forecast intervals: the draw store and exact order statistics (include/seir_hip.h, "Forecast intervals") ----
+    def keep_forecast_draws(self, cap: int):
+        """Keep cases, cumulative cases and prevalence of every forecast draw on the device, for up to `cap` draws per
+        chain: between `reset_forecast` and the first `forecast`.  0 frees the store.  B x 3 x M x H x cap x 4 bytes; the
+        library refuses a store above half of the device's free memory."""
+        cap = int(cap)
+        if cap < 0:
+            raise ValueError(f"cap={cap}: the number of draws per chain to keep")
+        _lib.check(self._lib.seir_sampler_forecast_keep(self._s, cap))
+
+    def forecast_order_stats(self, ranks, pooled: bool = False) -> np.ndarray:
+        """Exact order statistics `ranks` (strictly increasing, at most 16) of every cell over the draws kept since the
+        reset (blocking): int32 [R, B, 3, M, H] -- planes `FORECAST_QUANTILE_PLANES` -- or, `pooled`, [R, 3, M, H] over the
+        B x count values of all chains of this sampler.  Equal to np.sort(draws, axis=0)[ranks]."""
+        ranks = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
+        shape = (len(ranks),) + (() if pooled else (self.B,)) + (3, self.M, self._forecast_H)
+        out = np.empty(shape, np.int32)
+        _lib.check(self._lib.seir_sampler_forecast_order_stats(self._s, ranks.ctypes.data_as(_lib.c_int64_p), len(ranks),
+                                                               1 if pooled else 0,
+                                                               out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+        return out
+
+    def forecast_quantiles(self, probs, pooled: bool = False) -> np.ndarray:
+        """Quantiles `probs` (NumPy's default rule, `posterior.quantiles`) of every cell over the draws kept since the
+        reset (blocking): float64 [K, B, 3, M, H], or [K, 3, M, H] when `pooled`."""
+        from .posterior import quantiles as Q
+        n = self._fc_j * (self.B if pooled else 1)
+        ranks = Q.quantile_ranks(n, probs)
+        return Q.interpolate(self.forecast_order_stats(ranks, pooled=pooled), ranks, n, probs)
 
     def _forecast_burst(self, first, count, forecast):
         """`forecast` of sample / sample_bursts: True (held baseline) or a callable (j0, count) -> steps [count,B,H], j0

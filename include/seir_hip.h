@@ -561,6 +561,51 @@ int seir_sampler_read_forecast_marginals_async(seir_sampler *s, int32_t first, i
 int seir_sampler_read_forecast(seir_sampler *s, uint64_t *count, int32_t *ref, int64_t *sum, uint64_t *sumsq);
 
 /* ------------------------------------------------------------------------
+ * Forecast intervals on the device: exact per-cell order statistics of the forecast draws.
+ *
+ * The moments above cannot give the interval of a small, zero-heavy, skewed count.  While the draw store is on, every
+ * forecast draw leaves three int32 per (chain, location, forecast day) on the device, and at the end of the run exact
+ * order statistics are selected from them there; only the selected values cross PCIe.
+ *
+ * Semantics (the one definition; kernels: k_forecast_keep of csrc/forecast_kernels.h, csrc/order_stats_kernels.h, the
+ * narrowing step csrc/order_select.h).
+ *   Store.  keep[B][3][M][H][cap] int32, the draw index innermost.  Draw j of chain b -- the j of the forecast's draw id --
+ *     fills position j of every cell of that chain: nothing depends on how bursts are cut into calls, host batches or
+ *     buffer halves, or on how chains are sharded over samplers; a burst run again after a hand-off time-out overwrites its
+ *     own positions (seir_sampler_restore brings j back), so the store has no shadow copy.
+ *   Planes, with the definitions of the forecast's quantities, for forecast day s:
+ *     0 cases       the day's simulated I->R count k_ir[m][s]
+ *     1 cum_cases   sum_{s' <= s} k_ir[m][s']  (day 6: the cases of the next 7 days)
+ *     2 prevalence  I at the START of forecast day s (quantity 5 of the moments)
+ *     All are non-negative and bounded by the location's population.
+ *   Order statistic r of a cell of n values: np.sort(values)[r], exactly, in the order of signed int32.
+ *   Size: B x 3 x M x H x cap x 4 bytes (UK-380 x 8 chains, H = 56, 5000 draws: 10.2 GB).
+ * A sampler that never calls seir_sampler_forecast_keep allocates and launches nothing more than before.
+ * ------------------------------------------------------------------------ */
+#define SEIR_ORDER_STATS_MAX_RANKS 16
+/* Size the draw store for `cap` draws per chain: after seir_sampler_forecast_reset and before the first
+ * seir_sampler_forecast (SEIR_ERR_STATE otherwise).  Allocates on first use (and when cap changes); cap = 0 frees the
+ * store, at any time.  A later seir_sampler_forecast_reset with the same horizon empties the store, one with another
+ * horizon frees it.  While the store is on, seir_sampler_forecast refuses (SEIR_ERR_INVALID, naming both numbers) a call
+ * that would take a chain past cap.  SEIR_ERR_INVALID, before anything is allocated, for cap outside [0, 2^20] and for a
+ * store larger than half of what hipMemGetInfo reports free (the message carries both figures): the policy of a device
+ * that is shared, not a measurement. */
+int seir_sampler_forecast_keep(seir_sampler *s, int64_t cap);
+/* Blocking.  Order statistics `ranks` [R] (strictly increasing, 1 <= R <= SEIR_ORDER_STATS_MAX_RANKS) of every cell over
+ * the `count` draws per chain kept since the reset.  out is a host pointer: [R][B][3][M][H] with ranks in [0, count), or,
+ * pooled != 0, [R][3][M][H] over the B x count values of the process's chains with ranks in [0, B x count).
+ * SEIR_ERR_STATE before a reset, without a store, when no draw is kept yet or when the chains' counts differ;
+ * SEIR_ERR_INVALID for R outside its range and for ranks out of range, unsorted or repeated. */
+int seir_sampler_forecast_order_stats(seir_sampler *s, const int64_t *ranks, int32_t R, int32_t pooled, int32_t *out);
+/* The selection alone, stateless, host pointers, blocking.  `cells` cells, cell c starting at values[c x cell_stride]; a
+ * cell is n = segs x seg_len values in `segs` runs of seg_len contiguous values, seg_stride apart (values therefore spans
+ * (cells - 1) cell_stride + (segs - 1) seg_stride + seg_len elements).  out [R][cells]: np.sort(cell)[ranks[r]].
+ * SEIR_ERR_INVALID for counts below 1, n or cells of 2^31 or more, a negative stride, seg_stride < seg_len with segs > 1, and
+ * for R and ranks as above. */
+int seir_order_stats(seir_ctx *ctx, const int32_t *values, int64_t cells, int32_t segs, int64_t seg_len, int64_t seg_stride,
+                     int64_t cell_stride, const int64_t *ranks, int32_t R, int32_t *out);
+
+/* ------------------------------------------------------------------------
  * Reproduction number on the device: R_it moments and R_t per draw.
  *
  * Stands in for covid19uk/posterior/reproduction_number.py run on every kept draw, without samples/seir: for each draw
