@@ -71,6 +71,18 @@ FORECAST_MAX_H = 128          # SEIR_FORECAST_MAX_H
 FORECAST_ID_SHIFT, FORECAST_MAX_CHAIN = 20, 2048   # draw id = (global chain id << 20) + j
 CHECK_MAX_DAYS = 128          # SEIR_CHECK_MAX_DAYS
 ORDER_STATS_MAX_RANKS = 16    # SEIR_ORDER_STATS_MAX_RANKS
+# SEIR_FN_*: the functions of seir_selftest_fn, name -> (op, takes y, has out1)
+SELFTEST_FN = {"fast_log": (0, False, False), "fast_rcp": (1, False, False), "mv_log": (2, False, False),
+               "softplus_tab": (3, False, False), "softplus_sigmoid_tab": (4, False, True), "softplus": (5, False, False),
+               "lfact_bf": (6, False, False), "lbinom_tab": (7, True, False), "lbinom_const": (8, True, False),
+               "lbinom_bf": (9, True, False), "log1mexp_tab": (10, False, False), "log1mexp": (11, False, False),
+               "log1mexp_series": (12, False, True), "l1me_inv_series": (13, False, True), "l1me_inv_k": (14, False, True),
+               "l1me_inv_series_k": (15, False, True), "log1mexp_diff_slow": (16, True, False), "fast_log_k": (17, False, False)}
+SELFTEST_DELTA = {"band": 0, "own_ei": 1, "own_se": 2}                        # SEIR_DELTA_*
+# SEIR_WAVE_* / SEIR_BLOCK_*: name -> (op, has an int32 form)
+SELFTEST_WAVE = {"wave_sum": (0, True), "wave_min": (1, False), "wave_incl_scan": (2, True),
+                 "wave_incl_suffix_scan": (3, False), "block_excl_scan_256": (4, True),
+                 "block_incl_suffix_scan_256": (5, False), "block_sum_256": (6, False)}
 
 
 class SeirError(RuntimeError):
@@ -112,6 +124,12 @@ _SIGNATURES = {
                                         ctypes.POINTER(ctypes.c_float)]),
     "seir_selftest_math": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32] + [c_double_p] * 4),
     "seir_selftest_math_wide": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32] + [c_double_p] * 3),
+    # the device math by function, the delta log-ratios and the wave primitives (csrc/selftest_kernels.h)
+    "seir_selftest_fn": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32] + [c_double_p] * 4),
+    "seir_selftest_band_delta": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32] + [c_double_p] * 7 +
+                                 [ctypes.c_double, ctypes.c_double, c_double_p]),
+    "seir_selftest_wave": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32] +
+                           [ctypes.c_void_p] * 3),
     "seir_reproduction_number": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_double_p, c_double_p, c_double_p]),
     "seir_within_between": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_double_p, c_double_p, ctypes.c_double,
                                            c_double_p, c_double_p]),

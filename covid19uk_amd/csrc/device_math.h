@@ -63,9 +63,13 @@ __device__ __forceinline__ double fast_log(double x, const double2 *tab) {
 __device__ __forceinline__ double fast_rcp(double x);
 // softplus(x) = max(x, 0) + log1p(e^-|x|) in ONE path for every lane (libm's two-sided form runs both sides when the
 // lanes' signs differ) with the table logarithm: log1p(e) = log(w) + (e - (w - 1)) / w, w = fl(1 + e) -- the rounding of
-// 1 + e given back, so the result is good to the last bit or two for any e in (0, 1].  For the chunk roles of a leapfrog
-// step, where psi and sigma_space of the new point sit on the step's critical path (the stage kernels and the
-// parameter tables, once per launch, keep libm's: the two agree to ~1e-16 relative).
+// 1 + e given back.  Error: |err| <= 2 ulp(value) + 2^-59 (tests/devmath_lib.py) -- the last bit or two of the value down
+// to x of about -8, an ABSOLUTE floor of ~4e-19 below: fast_log(w) for w in [1, 1 + 2^-7) cancels two table-sized addends of
+// up to 2^-8, each rounded at 2^-61, so the relative error grows as the value shrinks (2e-11 at x = -20, 5e-6 at x = -30).
+// psi, sigma_space and the log-sigmoids take it as an absolute error, for which the floor is far below fp64.  For the chunk
+// roles of a leapfrog step, where psi and sigma_space of the new point sit on the step's critical path (the stage kernels
+// and the parameter tables, once per launch, keep libm's: the two agree to ~1e-16 relative above x of about -8 and to the
+// absolute floor below it).
 __device__ __forceinline__ double softplus_tab(double x, const double2 *tab) {
     const double e = exp(-fabs(x));
     const double wv = 1.0 + e;
@@ -111,7 +115,8 @@ __device__ __forceinline__ void log_table_to_lds(double2 *lds_tab, const double2
 }
 
 // L = log(1 - exp(-r)) and inv = 1/expm1(r) for a rate*dt r.  r < 0 gives NaN
-// (the reference's log(1 - exp(-r)) does too).  Daily hazards are small, so the
+// (the reference's log(1 - exp(-r)) does too; -inf where |r| < 2^-54, whose e^-r
+// rounds to 1: never a finite value).  Daily hazards are small, so the
 // common path is a series around 0 (|rel err| < 3e-16 for r <= 1/8, checked
 // against mpmath in tests/test_abi.py::test_series_constants):
 //   log((1-e^-r)/r) = -r/2 + r^2/24 - r^4/2880 + r^6/181440 - r^8/9676800

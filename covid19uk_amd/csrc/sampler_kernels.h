@@ -2655,8 +2655,11 @@ __device__ __attribute__((noinline)) double log1mexp_diff_slow(double r1, double
 // Change of the S->E term of a cell whose F moves by dF while its own state is unchanged:
 //   k [L(r1) - L(r0)] - (S-k)(r1 - r0),  L(r) = log(1-exp(-r)),  r1 = r0 + a.
 // In the small-rate regime L(r1)-L(r0) = log(r1/r0) + g(r1) - g(r0) with log(r1/r0) = 2 atanh(z),
-// z = a/(2 r0 + a): one reciprocal and two short polynomials instead of two table logs, and more
-// accurate than differencing them.
+// z = a/(2 r0 + a): one reciprocal and two short polynomials instead of two table logs.  Against
+// L(r0 + a) - L(r0) with exact r0 + a: |err| <= 4 eps (|dL| + (r0 + r1)/2) (measured on the exact-fma restatement: 1.9
+// eps; tests/devmath_lib.py), where differencing two table logs errs by eps (|L0| + |L1|) -- the smaller ABSOLUTE error
+// whenever |dL| << |L|; the RELATIVE error of dL is no better than the rounding of r1 = r0 + a allows (eps r0 / a: 3e-6 at
+// a = 1e-10 r0).
 __device__ __forceinline__ double band_delta(double S, double I, double K0, double F, double dF, double ee,
                                              double psiW, double floor_dt, double dt, const double2 *ltab) {
     const double r0 = ee * (I + psiW * F) * dt + floor_dt;

@@ -17,6 +17,7 @@
 #include "sampler_kernels.h"
 #include "sim_kernels.h"
 #include "moves_kernel.h"
+#include "selftest_kernels.h"
 #include "rt_kernels.h"
 #include "sweep_plan.h"
 #include "summary_kernels.h"
@@ -909,6 +910,112 @@ extern "C" int seir_selftest_math_wide(seir_ctx *ctx, int32_t n, const double *x
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(L, dL.p, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(inv, di.p, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// ---- self-tests of the device math by function (selftest_kernels.h; tests/test_devmath_gpu.py) ----
+namespace {
+bool st_finite(const double *v, int n) {
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+bool st_count(const double *v, int n, double lo, double hi) {      // integer-valued, lo <= v <= hi
+    for (int i = 0; i < n; ++i)
+        if (!(v[i] >= lo && v[i] <= hi) || v[i] != std::floor(v[i])) return false;
+    return true;
+}
+}  // namespace
+
+extern "C" int seir_selftest_fn(seir_ctx *ctx, int32_t op, int32_t n, const double *x, const double *y, double *out0,
+                                double *out1) {
+    int rc = check_batch(ctx, 1);
+    if (rc) return rc;
+    if (op < 0 || op >= SEIR_FN_COUNT) return fail(SEIR_ERR_INVALID, "unknown function %d", op);
+    if (n < 1 || !x || !out0) return fail(SEIR_ERR_INVALID, "bad arguments");
+    const bool two_in = op == SEIR_FN_LBINOM_TAB || op == SEIR_FN_LBINOM_CONST || op == SEIR_FN_LBINOM_BF ||
+                        op == SEIR_FN_LOG1MEXP_DIFF_SLOW;
+    const bool two_out = op == SEIR_FN_SOFTPLUS_SIGMOID_TAB || op == SEIR_FN_LOG1MEXP_SERIES ||
+                         op == SEIR_FN_L1ME_INV_SERIES || op == SEIR_FN_L1ME_INV_K || op == SEIR_FN_L1ME_INV_SERIES_K;
+    if (two_in && !y) return fail(SEIR_ERR_INVALID, "function %d takes two arguments", op);
+    if (two_out && !out1) return fail(SEIR_ERR_INVALID, "function %d has two results", op);
+    // the domains (include/seir_hip.h): a table is never indexed out of range, whatever the caller passes
+    if (!st_finite(x, n) || (two_in && !st_finite(y, n))) return fail(SEIR_ERR_INVALID, "argument not finite");
+    switch (op) {
+        case SEIR_FN_FAST_LOG: case SEIR_FN_FAST_LOG_K: case SEIR_FN_MV_LOG: case SEIR_FN_FAST_RCP:
+            for (int i = 0; i < n; ++i)
+                if (!(x[i] > 0.0) || !std::isnormal(x[i])) return fail(SEIR_ERR_INVALID, "x[%d] is not a positive normal number", i);
+            break;
+        case SEIR_FN_LFACT_BF: case SEIR_FN_LBINOM_TAB: case SEIR_FN_LBINOM_CONST: case SEIR_FN_LBINOM_BF:
+            if (!st_count(x, n, 0.0, 2147483647.0)) return fail(SEIR_ERR_INVALID, "n must be an integer in 0 .. 2^31 - 1");
+            if (two_in && !st_count(y, n, -2147483648.0, 2147483648.0)) return fail(SEIR_ERR_INVALID, "k must be an integer of |k| <= 2^31");
+            break;
+        default: break;
+    }
+    DevBuf dx, dy, d0, d1;
+    const size_t bytes = sizeof(double) * (size_t)n;
+    if ((rc = dx.alloc(bytes)) || (rc = dy.alloc(two_in ? bytes : 8)) || (rc = d0.alloc(bytes)) ||
+        (rc = d1.alloc(out1 ? bytes : 8)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(dx.p, x, bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (two_in) HIP_TRY(hipMemcpyAsync(dy.p, y, bytes, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_selftest_fn, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->c.logtab, (int)op, (int)n,
+                       dx.as<double>(), two_in ? dy.as<double>() : (const double *)nullptr, d0.as<double>(),
+                       out1 ? d1.as<double>() : (double *)nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out0, d0.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (out1) HIP_TRY(hipMemcpyAsync(out1, d1.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+extern "C" int seir_selftest_band_delta(seir_ctx *ctx, int32_t op, int32_t n, const double *S, const double *I,
+                                        const double *K0, const double *F, const double *dF, const double *ee,
+                                        const double *psiW, double rate_floor, double dt, double *out) {
+    int rc = check_batch(ctx, 1);
+    if (rc) return rc;
+    if (op < SEIR_DELTA_BAND || op > SEIR_DELTA_OWN_SE) return fail(SEIR_ERR_INVALID, "unknown delta %d", op);
+    if (n < 1 || !S || !I || !K0 || !F || !dF || !ee || !psiW || !out) return fail(SEIR_ERR_INVALID, "bad arguments");
+    const double *in[7] = {S, I, K0, F, dF, ee, psiW};
+    for (const double *v : in)
+        if (!st_finite(v, n)) return fail(SEIR_ERR_INVALID, "argument not finite");
+    if (!std::isfinite(rate_floor) || !std::isfinite(dt)) return fail(SEIR_ERR_INVALID, "argument not finite");
+    DevBuf din, dout;
+    const size_t bytes = sizeof(double) * (size_t)n;
+    if ((rc = din.alloc(7 * bytes)) || (rc = dout.alloc(bytes))) return rc;
+    double *p = din.as<double>();
+    for (int a = 0; a < 7; ++a) HIP_TRY(hipMemcpyAsync(p + (size_t)a * n, in[a], bytes, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_selftest_delta, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->c.logtab, (int)op, (int)n, p,
+                       p + (size_t)n, p + (size_t)2 * n, p + (size_t)3 * n, p + (size_t)4 * n, p + (size_t)5 * n,
+                       p + (size_t)6 * n, rate_floor, dt, dout.as<double>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, dout.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+extern "C" int seir_selftest_wave(seir_ctx *ctx, int32_t op, int32_t is_int, int32_t nblocks, const void *in, void *out,
+                                  void *total) {
+    int rc = check_batch(ctx, 1);
+    if (rc) return rc;
+    if (op < SEIR_WAVE_SUM || op > SEIR_BLOCK_SUM) return fail(SEIR_ERR_INVALID, "unknown primitive %d", op);
+    if (is_int && op != SEIR_WAVE_SUM && op != SEIR_WAVE_INCL_SCAN && op != SEIR_BLOCK_EXCL_SCAN)
+        return fail(SEIR_ERR_INVALID, "primitive %d has no int32 form", op);
+    if (nblocks < 1 || nblocks > 1024 || !in || !out) return fail(SEIR_ERR_INVALID, "bad arguments");
+    DevBuf din, dout, dtot;
+    const size_t bytes = (is_int ? sizeof(int32_t) : sizeof(double)) * (size_t)nblocks * 256;
+    if ((rc = din.alloc(bytes)) || (rc = dout.alloc(bytes)) || (rc = dtot.alloc(bytes))) return rc;
+    HIP_TRY(hipMemcpyAsync(din.p, in, bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (is_int)
+        hipLaunchKernelGGL(k_selftest_wave<1>, dim3(nblocks), dim3(256), 0, ctx->stream, (int)op, din.as<int>(),
+                           dout.as<int>(), total ? dtot.as<int>() : (int *)nullptr);
+    else
+        hipLaunchKernelGGL(k_selftest_wave<0>, dim3(nblocks), dim3(256), 0, ctx->stream, (int)op, din.as<double>(),
+                           dout.as<double>(), total ? dtot.as<double>() : (double *)nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, dout.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (total) HIP_TRY(hipMemcpyAsync(total, dtot.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
 }

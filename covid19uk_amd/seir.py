@@ -192,6 +192,50 @@ class SeirModel:
         _lib.check(self._lib.seir_selftest_math_wide(self._ctx, x.size, _dptr(x), _dptr(L), _dptr(inv)))
         return L, inv
 
+    def selftest_fn(self, name, x, y=None):
+        """One scalar function of csrc/device_math.h (a key of `_lib.SELFTEST_FN`) on each x[i] (and y[i]) as the kernels
+        evaluate it: the values, or (values, second result) for a function that has two (include/seir_hip.h)."""
+        op, two_in, two_out = _lib.SELFTEST_FN[name]
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        if two_in:
+            y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+            if y.shape != x.shape:
+                raise ValueError("x and y differ in length")
+        out0 = np.empty_like(x)
+        out1 = np.empty_like(x) if two_out else None
+        _lib.check(self._lib.seir_selftest_fn(self._ctx, op, x.size, _dptr(x), _dptr(y) if two_in else None, _dptr(out0),
+                                              _dptr(out1) if two_out else None))
+        return (out0, out1) if two_out else out0
+
+    def selftest_delta(self, which, S, I, K0, F, dF, ee, psiW, rate_floor, dt):
+        """`band_delta` ("band") or the S->E piece of `own_rows_delta` ("own_ei", "own_se") per element
+        (csrc/sampler_kernels.h; the arguments: include/seir_hip.h, seir_selftest_band_delta)."""
+        arrs = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (S, I, K0, F, dF, ee, psiW)]
+        n = arrs[0].size
+        if any(a.size != n for a in arrs):
+            raise ValueError("arguments differ in length")
+        out = np.empty(n)
+        _lib.check(self._lib.seir_selftest_band_delta(self._ctx, _lib.SELFTEST_DELTA[which], n, *[_dptr(a) for a in arrs],
+                                                      float(rate_floor), float(dt), _dptr(out)))
+        return out
+
+    def selftest_wave(self, name, v):
+        """A wave or block primitive of csrc/device_math.h (a key of `_lib.SELFTEST_WAVE`) fed v[block * 256 + tid] by
+        256-thread blocks; v int32 or float64, a multiple of 256 long.  Returns (what each thread got back, the block total
+        each thread was handed: zeros for the wave forms and block_sum_256)."""
+        op, has_int = _lib.SELFTEST_WAVE[name]
+        v = np.asarray(v)
+        is_int = v.dtype == np.int32
+        if not is_int:
+            v = np.ascontiguousarray(v, dtype=np.float64)
+        v = np.ascontiguousarray(v).reshape(-1)
+        if v.size % 256 or (is_int and not has_int):
+            raise ValueError("need whole 256-thread blocks, and int32 only where the primitive has that form")
+        out, tot = np.empty_like(v), np.empty_like(v)
+        _lib.check(self._lib.seir_selftest_wave(self._ctx, op, int(is_int), v.size // 256, v.ctypes.data, out.ctypes.data,
+                                                tot.ctypes.data))
+        return out, tot
+
     def within_between(self, psi, I_last, W):
         """(within, between) fractions [n,M] of the infection pressure of the last state
         (covid19uk/posterior/within_between.py:13-57).  psi [n], I_last [n,M], W scalar."""

@@ -173,6 +173,46 @@ int seir_selftest_math(seir_ctx *ctx, int32_t n, const double *x, double *L, dou
 /* the 8-term variant used where rates are not small (the I->R terms of the HMC kernels): L, inv as above */
 int seir_selftest_math_wide(seir_ctx *ctx, int32_t n, const double *x, double *L, double *inv);
 
+/* Every scalar function of csrc/device_math.h by itself (csrc/selftest_kernels.h): out0[i] = fn(x[i] [, y[i]]) as the
+ * kernels evaluate it, one element per thread of 256-thread blocks, so the lanes of a wave take different branches.
+ * Host pointers; y and out1 may be null for an op that has no second argument / second result.
+ *   FAST_LOG, FAST_LOG_K, MV_LOG, FAST_RCP     x positive, normal and finite
+ *   SOFTPLUS_TAB, SOFTPLUS                     x finite
+ *   SOFTPLUS_SIGMOID_TAB                       x finite; out1 = sigmoid(x)
+ *   LFACT_BF                                   x = n, an integer 0 .. 2^31 - 1
+ *   LBINOM_TAB / _CONST / _BF                  x = n as above, y = k, any integer of |k| <= 2^31 (k < 0, k > n: -inf);
+ *                                              _CONST is the form with the table in constant memory
+ *   LOG1MEXP_TAB, LOG1MEXP                     x = r finite (r < 0: NaN)
+ *   LOG1MEXP_SERIES                            x = r finite; out1 = 1 where `odd` was raised, else 0
+ *   L1ME_INV_SERIES, L1ME_INV_K, L1ME_INV_SERIES_K   x = r finite; out0 = L, out1 = inv (the _K forms with SeK::load())
+ *   LOG1MEXP_DIFF_SLOW                         x = r1, y = r0 finite: L(r1) - L(r0)
+ * Arguments outside these domains, n < 1 and an unknown op are refused with SEIR_ERR_INVALID before any launch. */
+enum { SEIR_FN_FAST_LOG = 0, SEIR_FN_FAST_RCP = 1, SEIR_FN_MV_LOG = 2, SEIR_FN_SOFTPLUS_TAB = 3,
+       SEIR_FN_SOFTPLUS_SIGMOID_TAB = 4, SEIR_FN_SOFTPLUS = 5, SEIR_FN_LFACT_BF = 6, SEIR_FN_LBINOM_TAB = 7,
+       SEIR_FN_LBINOM_CONST = 8, SEIR_FN_LBINOM_BF = 9, SEIR_FN_LOG1MEXP_TAB = 10, SEIR_FN_LOG1MEXP = 11,
+       SEIR_FN_LOG1MEXP_SERIES = 12, SEIR_FN_L1ME_INV_SERIES = 13, SEIR_FN_L1ME_INV_K = 14,
+       SEIR_FN_L1ME_INV_SERIES_K = 15, SEIR_FN_LOG1MEXP_DIFF_SLOW = 16, SEIR_FN_FAST_LOG_K = 17, SEIR_FN_COUNT = 18 };
+int seir_selftest_fn(seir_ctx *ctx, int32_t op, int32_t n, const double *x, const double *y, double *out0, double *out1);
+
+/* The delta log-ratios of the event updates, per element (arrays of n, host pointers; all values finite):
+ *   SEIR_DELTA_BAND    band_delta(S, I, K0, F, dF, ee, psiW, rate_floor * dt, dt): a cell whose F moves by dF
+ *   SEIR_DELTA_OWN_EI  the S->E piece of own_rows_delta for an E->I-type update, K0 (L(rr1) - L(rr0)) - (S - K0)(rr1 - rr0)
+ *                      with rr0 = (ee (I + psiW F) + rate_floor) dt and rr1 the same with F + dF
+ *   SEIR_DELTA_OWN_SE  the same piece for an S->E-type update: k_se goes from K0 to K0 + dk0 and S by dS at the rate rr0;
+ *                      `dF` holds dk0 and `S` holds dS */
+enum { SEIR_DELTA_BAND = 0, SEIR_DELTA_OWN_EI = 1, SEIR_DELTA_OWN_SE = 2 };
+int seir_selftest_band_delta(seir_ctx *ctx, int32_t op, int32_t n, const double *S, const double *I, const double *K0,
+                             const double *F, const double *dF, const double *ee, const double *psiW, double rate_floor,
+                             double dt, double *out);
+
+/* The wave and block primitives of csrc/device_math.h: thread tid of each of `nblocks` (1 .. 1024) 256-thread blocks
+ * feeds in[block * 256 + tid] and stores what the primitive hands back in out[...]; `total` (block forms; may be null)
+ * receives the block total every thread was handed.  is_int != 0: int32 arrays (SUM, INCL_SCAN, BLOCK_EXCL_SCAN only),
+ * else double.  Host pointers. */
+enum { SEIR_WAVE_SUM = 0, SEIR_WAVE_MIN = 1, SEIR_WAVE_INCL_SCAN = 2, SEIR_WAVE_INCL_SUFFIX_SCAN = 3,
+       SEIR_BLOCK_EXCL_SCAN = 4, SEIR_BLOCK_INCL_SUFFIX_SCAN = 5, SEIR_BLOCK_SUM = 6 };
+int seir_selftest_wave(seir_ctx *ctx, int32_t op, int32_t is_int, int32_t nblocks, const void *in, void *out, void *total);
+
 
 /* ------------------------------------------------------------------------
  * Device-resident Metropolis-within-Gibbs sampler.

@@ -409,3 +409,88 @@ def joint_log_prob_mp(u, events, k: ModelConstants, dps=50):
     for i in range(2):
         lp += -mp.log1p(mp.e ** (-u[i]))
     return tot + lp
+
+
+def changed_cells(events_a, events_b, k: ModelConstants):
+    """The cells (m, t) whose likelihood term can differ between two event tensors: their own state or events differ, or
+    the infectious count of a row that their force of infection sees (Cstar[m, j] != 0) does."""
+    ea, eb = np.asarray(events_a, dtype=np.float64), np.asarray(events_b, dtype=np.float64)
+    sa, sb = compute_state(k.initial_state, ea), compute_state(k.initial_state, eb)
+    own = (sa != sb).any(axis=2) | (ea != eb).any(axis=2)                       # [M, T]
+    seen = (np.asarray(k.Cstar) != 0).astype(np.float64) @ (sa[..., 2] != sb[..., 2]).astype(np.float64) > 0
+    return [(int(m), int(t)) for m, t in zip(*np.nonzero(own | seen))]
+
+
+def likelihood_cells_mp(u, events, k: ModelConstants, cells, dps=50, cache=None):
+    """The per-cell terms of joint_log_prob_mp's likelihood sum, for the cells [(m, t), ...] alone, so that the difference
+    of two log-densities at the same u needs only the cells that changed (`changed_cells`).  Returns {(m, t): (term, mag)}:
+    term = the cell's three binomial log-probabilities, mag = the sum of the absolute values of each log-factorial, each
+    k log(1 - e^-r) and each (n - k) r in it (the scale of the rounding of a double evaluation).  `cache`: a dict that a
+    caller evaluating several event tensors at the SAME u hands to each call (the parameters, log-factorials and unchanged
+    terms are then computed once)."""
+    import mpmath as mp
+    out = {}
+    cache = {} if cache is None else cache
+    with mp.workdps(dps):
+        mpf = mp.mpf
+        M, T = k.M, k.T
+        if "par" not in cache:
+            uu = [mpf(float(x)) for x in u]
+            theta = list(uu)
+            for i in range(2):
+                theta[i] = mp.log1p(mp.e ** uu[i]) + mpf(EPS64)
+            a = [theta[5]]
+            for j in range(T - 1):
+                a.append(a[-1] + theta[6 + j])
+            cache["par"] = (theta, a, np.array(u, dtype=np.float64))
+        theta, a, u_of = cache["par"]
+        assert np.array_equal(u_of, np.asarray(u, dtype=np.float64)), "one cache per u"
+        psi, sig, beta, g0, g1 = theta[:5]
+        sp = theta[6 + T - 1:]
+        ev = np.asarray(events, dtype=np.float64)
+        st = compute_state(k.initial_state, ev)
+
+        def lgam(n):
+            key = ("lgam", n)
+            if key not in cache:
+                cache[key] = mp.loggamma(mpf(n + 1))
+            return cache[key]
+
+        def ll(n, kk, r):
+            n, kk = int(n), int(kk)
+            key = ("ll", n, kk, r)
+            if key in cache:
+                return cache[key]
+            if kk < 0 or kk > n:
+                return mpf("-inf"), mpf(0)
+            lg = [lgam(n), lgam(kk), lgam(n - kk)]
+            val, mag = lg[0] - lg[1] - lg[2], sum(abs(x) for x in lg)
+            if n - kk:
+                val += (n - kk) * (-r)
+                mag += (n - kk) * abs(r)
+            if kk:
+                L = mp.log(1 - mp.e ** (-r))
+                val += kk * L
+                mag += kk * abs(L)
+            cache[key] = (val, mag)
+            return val, mag
+
+        def once(key, fn):
+            if key not in cache:
+                cache[key] = fn()
+            return cache[key]
+
+        # Cstar[m, j] / N[j] once per u; the infectious counts enter as exact integers
+        cn = once("cn", lambda: [[mpf(float(k.Cstar[m, j])) / mpf(float(k.N[j])) if k.Cstar[m, j] != 0 else None
+                                  for j in range(M)] for m in range(M)])
+        I = st[..., 2].astype(np.int64)
+        assert np.array_equal(I, st[..., 2])
+        for (m, t) in cells:
+            r_ir = once(("r_ir", t), lambda: mp.e ** (g0 + g1 * mpf(float(k.weekday_c[t]))))
+            Fm = sum((cn[m][j] * int(I[j, t]) for j in range(M) if cn[m][j] is not None and I[j, t]), mpf(0))
+            ee = once(("ee", m, t), lambda: mp.e ** (a[t] + beta * mpf(float(k.log_area_c[m])) + sig * sp[m]))
+            lam = ee * (mpf(float(st[m, t, 2])) + psi * mpf(float(k.W[t])) * Fm) / mpf(float(k.N[m])) + mpf("1e-9")
+            parts = [ll(st[m, t, 0], ev[m, t, 0], lam), ll(st[m, t, 1], ev[m, t, 1], mpf(NU)),
+                     ll(st[m, t, 2], ev[m, t, 2], r_ir)]
+            out[(m, t)] = (sum(p[0] for p in parts), sum(p[1] for p in parts))
+    return out

@@ -367,8 +367,9 @@ def test_on_keeps_once_behind_the_reset_asks_twice_at_the_end_and_writes_the_dat
 # ---- 6. the compiler's account of the new kernels --------------------------------------------------------------------------
 def test_the_new_kernels_have_no_scratch_and_the_others_are_what_they_were():
     """build() keeps the account of the kernels this product adds in a file of its own (`entry.RESOURCES_ADDED`), because
-    kernel_resources.json is held to the set of kernels of the round before (tests/test_check_host.py); the two files
-    together are the compiler's account of the library."""
+    kernel_resources.json is held to the set of kernels of the round before (tests/test_check_host.py); the three files
+    (the third: `entry.RESOURCES_SELFTEST`, the self-test kernels of the device math) together are the compiler's account
+    of the library."""
     entry.build()
     res = json.load(open(entry.RESOURCES))
     added = json.load(open(entry.RESOURCES_ADDED))
