@@ -36,49 +36,15 @@ struct CheckCmp {
     unsigned *moved;               // [B] sticky: a later draw's I->R counts in the window differ from obs
 };
 
-// grid (Mp / FC_ROWS, ndp), 64 FC_ROWS threads.  Draws [ND, ndp) and rows [M, Mp) get zeros (the contraction reads them).
+// forecast_prepare_draws up to day T - K (its geometry); one lane per draw forms the K baselines of the draw's own days.
 template <int EV16>
 __global__ __launch_bounds__(64 * FC_ROWS) void k_check_prepare(Dims d, Consts c, ForecastBufs fb,
                                                                 const double *__restrict__ tr_theta,
                                                                 const void *__restrict__ tr_events, int B, int first,
                                                                 int ND, int ndp) {
     debug_skew(d);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int nd = blockIdx.y, m = blockIdx.x * FC_ROWS + wv;
-    const int M = d.M, T = d.T, t0 = d.T - fb.H;
-    const size_t plane = (size_t)d.Mp * ndp, idx = (size_t)m * ndp + nd;
-    if (nd >= ND || m >= M) {
-        if (lane == 0) {
-#pragma unroll
-            for (int x = 0; x < 3; ++x) { fb.St0[x * plane + idx] = 0; fb.St[x * plane + idx] = 0; }
-            fb.X[idx] = 0.0;
-            fb.eb[idx] = 0.0;
-        }
-        return;
-    }
-    const int jj = nd / B, b = nd - jj * B, slot = first + jj;
-    const double *th = tr_theta + ((size_t)slot * B + b) * d.P;
-    const size_t row = (((size_t)slot * B + b) * M + m) * T;
-    int tot[3] = {0, 0, 0};
-    for (int t = lane; t < t0; t += 64) {
-        int k[3];
-        summary_load<EV16>(tr_events, row + t, true, k);
-        tot[0] += k[0]; tot[1] += k[1]; tot[2] += k[2];
-    }
-#pragma unroll
-    for (int x = 0; x < 3; ++x)
-        for (int o = 32; o > 0; o >>= 1) tot[x] += __shfl_xor(tot[x], o, 64);
-    if (lane == 0) {
-        const int S = (int)c.init[(size_t)m * 4 + 0] - tot[0];
-        const int E = (int)c.init[(size_t)m * 4 + 1] + tot[0] - tot[1];
-        const int I = (int)c.init[(size_t)m * 4 + 2] + tot[1] - tot[2];
-        fb.St0[idx] = S; fb.St0[plane + idx] = E; fb.St0[2 * plane + idx] = I;
-        fb.St[idx] = S; fb.St[plane + idx] = E; fb.St[2 * plane + idx] = I;
-        fb.X[idx] = (double)I * c.invN[m];
-        fb.eb[idx] = sim_eb(th[2], c.la[m], th[1], th[6 + T - 1 + m], c.invN[m]);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        fb.sc[nd] = th[0]; fb.sc[ndp + nd] = th[3]; fb.sc[2 * ndp + nd] = th[4];
+    const int T = d.T, t0 = d.T - fb.H;
+    forecast_prepare_draws<EV16>(d, c, fb, tr_theta, tr_events, B, first, ND, ndp, t0, [&](const double *th, int nd) {
         // day t of the window: alpha_0 at t = 0, else alpha_0 + cumsum(alpha_t)[t - 1] -- the running sum in index order,
         // then added to alpha_0 (np.cumsum's order).  t <= T - 1, so the reference's clip at T - 2 never binds in sample.
         if (t0 == 0) fb.base[nd] = th[5];
@@ -88,7 +54,7 @@ __global__ __launch_bounds__(64 * FC_ROWS) void k_check_prepare(Dims d, Consts c
             const int s = i + 1 - t0;
             if (s >= 0) fb.base[(size_t)s * ndp + nd] = th[5] + cs;
         }
-    }
+    });
 }
 
 // grid (ceil(M / FC_ROWS), B), 64 FC_ROWS threads.  1 <= count <= FC_JMAX slots from trace slot `first`, whose simulated

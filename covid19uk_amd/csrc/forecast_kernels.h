@@ -57,13 +57,14 @@ struct ForecastBufs {
     MomentBufs mom;                // accumulators and marginals over [H]: forecast_by_day, _by_location, _state_by_day
 };
 
-// grid (Mp / FC_ROWS, ndp), 64 FC_ROWS threads.  Draws [ND, ndp) and rows [M, Mp) get zeros (the contraction reads them).
-template <int EV16>
-__global__ __launch_bounds__(64 * FC_ROWS) void k_forecast_prepare(Dims d, Consts c, ForecastBufs fb,
-                                                                   const double *__restrict__ tr_theta,
-                                                                   const void *__restrict__ tr_events, int B, int first,
-                                                                   int ND, int ndp) {
-    debug_skew(d);
+// What a prepare kernel does whatever the rollout starts from (grid (Mp / FC_ROWS, ndp), 64 FC_ROWS threads): draws
+// [ND, ndp) and rows [M, Mp) get zeros (the contraction reads them); a wave per (row, draw) sums the draw's recorded events
+// over the days before t_end and writes the state at t_end, X and eb; one thread per draw writes the three scalars and
+// calls baselines(theta of the draw, nd), which forms the draw's log baselines.
+template <int EV16, typename Baselines>
+__device__ __forceinline__ void forecast_prepare_draws(const Dims &d, const Consts &c, const ForecastBufs &fb,
+                                                       const double *__restrict__ tr_theta, const void *__restrict__ tr_events,
+                                                       int B, int first, int ND, int ndp, int t_end, Baselines baselines) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int nd = blockIdx.y, m = blockIdx.x * FC_ROWS + wv;
     const int M = d.M, T = d.T;
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(64 * FC_ROWS) void k_forecast_prepare(Dims d, Const
     const double *th = tr_theta + ((size_t)slot * B + b) * d.P;
     const size_t row = (((size_t)slot * B + b) * M + m) * T;
     int tot[3] = {0, 0, 0};
-    for (int t = lane; t < T; t += 64) {
+    for (int t = lane; t < t_end; t += 64) {
         int k[3];
         summary_load<EV16>(tr_events, row + t, true, k);
         tot[0] += k[0]; tot[1] += k[1]; tot[2] += k[2];
@@ -100,6 +101,19 @@ __global__ __launch_bounds__(64 * FC_ROWS) void k_forecast_prepare(Dims d, Const
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         fb.sc[nd] = th[0]; fb.sc[ndp + nd] = th[3]; fb.sc[2 * ndp + nd] = th[4];
+        baselines(th, nd);
+    }
+}
+
+// The state at day T; one lane per draw forms the H baselines from a_last (forecast_prepare_draws' geometry).
+template <int EV16>
+__global__ __launch_bounds__(64 * FC_ROWS) void k_forecast_prepare(Dims d, Consts c, ForecastBufs fb,
+                                                                   const double *__restrict__ tr_theta,
+                                                                   const void *__restrict__ tr_events, int B, int first,
+                                                                   int ND, int ndp) {
+    debug_skew(d);
+    const int T = d.T;
+    forecast_prepare_draws<EV16>(d, c, fb, tr_theta, tr_events, B, first, ND, ndp, T, [&](const double *th, int nd) {
         // alpha_0 + cumsum(alpha_t)[T-2]: the running sum in index order, then added to alpha_0 (np.cumsum's order)
         double a_last = th[5];
         if (T > 1) {
@@ -116,7 +130,7 @@ __global__ __launch_bounds__(64 * FC_ROWS) void k_forecast_prepare(Dims d, Const
             }
             fb.base[(size_t)s * ndp + nd] = a;
         }
-    }
+    });
 }
 
 // Forecast day s for every (row, draw): grid (ndp / 64, ceil(M / FC_DAY_ROWS)), 64 FC_DAY_ROWS threads.

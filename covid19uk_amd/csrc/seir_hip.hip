@@ -1182,6 +1182,19 @@ static int acc_read(const MomentAcc &a, hipStream_t st, uint64_t *count, int32_t
     return 0;
 }
 
+// The host's half of a ForecastBufs that is rolled forward day by day from the kept draws (forecast_kernels.h): the forecast
+// and the in-sample check each own one (rollout_*, below).
+struct Rollout {
+    bool on = false;                  // enabled by the user's first reset: buffers exist
+    ForecastBufs fb{};
+    int slots = 0;                    // trace slots per batch: min(cap, FC_JMAX)
+    int ndmax = 0;                    // row stride the planes are allocated for: ceil64(slots * B)
+    std::vector<void *> allocs;       // device buffers sized by fb.H (allocated again when it changes)
+    MomentAcc acc;                    // fb.mom's ref .. overflow
+    long long j = 0;                  // draws per chain rolled forward since the last reset (the j of the draw id)
+    long long snap_j[2] = {0, 0};     // j as it was when acc's shadows were taken
+};
+
 struct seir_sampler {
     seir_ctx *ctx = nullptr;
     SamplerCfg cfg{};
@@ -1247,32 +1260,18 @@ struct seir_sampler {
     SummaryDiag<1> diag{};
     Shadowed diag_buf;
     // --- forecast of the next H days (seir_sampler_forecast_reset ...; forecast_kernels.h) ---
-    bool fc_on = false;
-    ForecastBufs fc{};
-    int fc_slots = 0;                 // trace slots per batch: min(cap, FC_JMAX)
-    int fc_ndmax = 0;                 // row stride the planes are allocated for: ceil64(fc_slots * B)
-    std::vector<void *> fc_allocs;    // device buffers whose size depends on the horizon (allocated again when it changes)
-    MomentAcc fc_acc;                 // fc.mom's ref .. overflow
-    long long fc_j = 0;               // draws per chain forecast since the last reset (the j of the draw id)
-    long long fc_snap_j[2] = {0, 0};  // fc_j as it was when fc_acc's shadows were taken
+    Rollout fc;
     double *fc_steps_host = nullptr;  // page-locked [cap][B][H]: the caller's random-walk steps on their way to the device
-    double *fc_steps_dev = nullptr;   // [fc_slots * B][H]
+    double *fc_steps_dev = nullptr;   // [fc.slots * B][H] (one of fc.allocs)
     hipEvent_t fc_ev_steps = nullptr; // behind the last upload from fc_steps_host
     bool fc_steps_pending = false;
     int *fc_keep = nullptr;           // the draw store keep[B][3][M][H][fc_keep_cap] (seir_sampler_forecast_keep), or null: off
     long long fc_keep_cap = 0;        // draws per chain it holds; position j of a cell is the draw with the forecast's j
-    // --- in-sample check of the last K days (seir_sampler_check_reset ...; check_kernels.h): a ForecastBufs with H := K ---
-    bool ck_on = false;
-    ForecastBufs ck{};
+    // --- in-sample check of the last K days (seir_sampler_check_reset ...; check_kernels.h): a Rollout with H := K ---
+    Rollout ck;                       // its j is not the forecast's
     CheckCmp ck_cmp{};
-    int ck_slots = 0;                 // trace slots per batch: min(cap, FC_JMAX)
-    int ck_ndmax = 0;                 // row stride the planes are allocated for: ceil64(ck_slots * B)
-    std::vector<void *> ck_allocs;    // device buffers sized by K (allocated again when it changes)
-    MomentAcc ck_acc;                 // ck.mom's ref .. overflow
     Shadowed ck_cnt;                  // ck_cmp's arrays, 32-bit words: lt | eq | obs [B M K] | loc_lt | loc_eq [B M] |
                                       //     day_lt | day_eq [B K] | all_lt | all_eq | moved [B]
-    long long ck_j = 0;               // draws per chain checked since the last reset (the j of the draw id; not the forecast's)
-    long long ck_snap_j[2] = {0, 0};  // ck_j as it was when the shadows were taken
     // --- reproduction number of the kept draws (seir_sampler_rt_reset ...; rt_trace_kernels.h) ---
     bool rt_on = false;
     RtBufs rt{};
@@ -1281,7 +1280,7 @@ struct seir_sampler {
     Shadowed rt_acc;                  // sum [cells] | sumsq [cells] | ref [cells] | count [B, padded] | gt1 [cells]
 };
 
-// Zeroed device memory, registered in `list` (seir_sampler::allocs: freed with the sampler; fc_allocs: also when the horizon
+// Zeroed device memory, registered in `list` (seir_sampler::allocs: freed with the sampler; Rollout::allocs: also when the length
 // changes) and, when it is chain state or hand-off scratch, in the regions a snapshot / restore goes through.
 template <typename T>
 static int s_alloc(seir_sampler *s, std::vector<void *> &list, T **p, size_t count, int kind = seir_sampler::R_OTHER) {
@@ -1295,6 +1294,20 @@ static int s_alloc(seir_sampler *s, std::vector<void *> &list, T **p, size_t cou
     return 0;
 }
 #define S_ALLOC(list, ptr, ...) if (!rc) rc = s_alloc(s, s->list, &(ptr), __VA_ARGS__)
+
+static void rollout_free(Rollout &r) {
+    for (void *p : r.allocs) (void)hipFree(p);
+    r.allocs.clear();
+    acc_free(r.acc);
+    r.on = false;
+    r.fb = ForecastBufs{};
+}
+// The moments with the draw counter: a restore from a slot that holds nothing of them leaves both alone.
+static int rollout_shadow(Rollout &r, int slot, bool save, hipStream_t st) {
+    if (save) r.snap_j[slot] = r.j;
+    else if (r.acc.valid[slot]) r.j = r.snap_j[slot];
+    return acc_shadow(r.acc, slot, save, st);
+}
 
 static void drop_graph(seir_sampler *s) {
     for (auto &g : s->gexec) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
@@ -1316,11 +1329,9 @@ extern "C" void seir_sampler_destroy(seir_sampler *s) {
     if (s->ev_copy) (void)hipEventDestroy(s->ev_copy);
     for (void *p : s->allocs) (void)hipFree(p);
     for (void *p : s->snap) if (p) (void)hipFree(p);
-    for (void *p : s->fc_allocs) (void)hipFree(p);
     for (void *p : s->rt_allocs) (void)hipFree(p);
-    for (void *p : s->ck_allocs) (void)hipFree(p);
-    acc_free(s->sum_acc); acc_free(s->diag_buf); acc_free(s->fc_acc); acc_free(s->rt_acc);
-    acc_free(s->ck_acc); acc_free(s->ck_cnt);
+    rollout_free(s->fc); rollout_free(s->ck);
+    acc_free(s->sum_acc); acc_free(s->diag_buf); acc_free(s->rt_acc); acc_free(s->ck_cnt);
     if (s->fc_steps_host) (void)hipHostFree(s->fc_steps_host);
     if (s->fc_keep) (void)hipFree(s->fc_keep);
     if (s->fc_ev_steps) (void)hipEventDestroy(s->fc_ev_steps);
@@ -1554,6 +1565,13 @@ static int sampler_check(seir_sampler *s) {
     return 0;
 }
 
+// Whatever is still queued on the context stream, and a pending copy of a burst.
+static int drain(seir_sampler *s) {
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    if (s->copy_pending) { (void)hipEventSynchronize(s->ev_copy); s->copy_pending = false; }
+    return 0;
+}
+
 // Hand-off scratch back to its initial state, in stream order: every token / counter / in-flight descriptor zero (0 is no
 // launch's token) and the host's running totals of the counters with them.  Between two sweeps nothing of it is live
 // (a sweep's first launch starts with have_prev = have_pre = 0), so this is always allowed there.
@@ -1618,16 +1636,10 @@ static int moments_shadow(seir_sampler *s, int slot, bool save) {
         if (s->diag_on) rc = acc_shadow(s->diag_buf, slot, save, st);
         if (!rc) rc = acc_shadow(s->sum_acc, slot, save, st);
     }
-    if (!rc && s->fc_on) {
-        if (save) s->fc_snap_j[slot] = s->fc_j;
-        else if (s->fc_acc.valid[slot]) s->fc_j = s->fc_snap_j[slot];
-        rc = acc_shadow(s->fc_acc, slot, save, st);
-    }
+    if (!rc && s->fc.on) rc = rollout_shadow(s->fc, slot, save, st);
     if (!rc && s->rt_on) rc = acc_shadow(s->rt_acc, slot, save, st);
-    if (!rc && s->ck_on) {
-        if (save) s->ck_snap_j[slot] = s->ck_j;
-        else if (s->ck_acc.valid[slot]) s->ck_j = s->ck_snap_j[slot];
-        rc = acc_shadow(s->ck_acc, slot, save, st);
+    if (!rc && s->ck.on) {
+        rc = rollout_shadow(s->ck, slot, save, st);
         if (!rc) rc = acc_shadow(s->ck_cnt, slot, save, st);
     }
     return rc;
@@ -1662,8 +1674,7 @@ extern "C" int seir_sampler_restore(seir_sampler *s, int32_t slot) {
     hipStream_t st = s->ctx->stream;
     // whatever is still queued (the rest of a failed burst: its waits give up at their first look at the chain's time-out
     // counter, so it drains quickly) and the copy of a burst that nobody wants any more
-    HIP_TRY(hipStreamSynchronize(st));
-    if (s->copy_pending) { (void)hipEventSynchronize(s->ev_copy); s->copy_pending = false; }
+    if ((rc = drain(s))) return rc;
     size_t off = 0;
     for (const auto &r : s->regions)
         if (r.kind == seir_sampler::R_STATE) {
@@ -2284,13 +2295,16 @@ extern "C" int seir_sampler_trace_wait(seir_sampler *s) {
 // ---------------------------------------------------------------------------
 // Summaries of the recorded events (include/seir_hip.h; kernels: summary_kernels.h)
 // ---------------------------------------------------------------------------
-// The two users of a trace range that have to be enabled first: what they do with the recorded events, and their refusal.
-struct TraceUser { const char *verb, *not_enabled; };
+// The users of a trace range that have to be enabled first: what they do with the recorded events, and their refusal.
+// The two that roll the model forward (Rollout) also word the refusals they share: their name, and what they have done to a draw.
+struct TraceUser { const char *verb, *not_enabled, *name, *done; };
 static const TraceUser SUMMARY_USER = {"summarise", "summaries are not enabled: call seir_sampler_summary_reset first"};
 static const TraceUser RT_USER = {"form the reproduction number from",
                                    "the reproduction number is not enabled: call seir_sampler_rt_reset first"};
-static const TraceUser FORECAST_USER = {"forecast from", "the forecast is not enabled: call seir_sampler_forecast_reset first"};
-static const TraceUser CHECK_USER = {"check", "the in-sample check is not enabled: call seir_sampler_check_reset first"};
+static const TraceUser FORECAST_USER = {"forecast from", "the forecast is not enabled: call seir_sampler_forecast_reset first",
+                                         "forecast", "forecast"};
+static const TraceUser CHECK_USER = {"check", "the in-sample check is not enabled: call seir_sampler_check_reset first", "check",
+                                      "checked"};
 
 static int trace_range_check(seir_sampler *s, bool enabled, const TraceUser &what, int32_t first = 0, int32_t count = 0) {
     if (int rc = need_events(s, what.verb)) return rc;
@@ -2300,24 +2314,25 @@ static int trace_range_check(seir_sampler *s, bool enabled, const TraceUser &wha
     return 0;
 }
 
-// The per-draw marginals of a MomentBufs as the readers see them: day_extent is T (summaries) or H (forecast).
-struct Marginals { const int64_t *by_day, *by_loc, *state_by_day; size_t day_extent; };
-static Marginals marginals(const MomentBufs &mb, int day_extent) { return {mb.by_day, mb.by_loc, mb.state_by_day, (size_t)day_extent}; }
-
-static int copy_marginals(seir_sampler *s, hipStream_t st, int32_t first, int32_t count, const Marginals &m, int64_t *by_day,
-                          int64_t *by_loc, int64_t *state_by_day) {
-    const size_t B = s->cfg.B, f = (size_t)first, n = (size_t)count, M = (size_t)s->ctx->d.M, E = m.day_extent;
+// The per-draw marginals of a MomentBufs: E, the day extent, is T (summaries), H (forecast) or K (check).
+static int copy_marginals(seir_sampler *s, hipStream_t st, int32_t first, int32_t count, const MomentBufs &m, size_t E,
+                          int64_t *by_day, int64_t *by_loc, int64_t *state_by_day) {
+    const size_t B = s->cfg.B, f = (size_t)first, n = (size_t)count, M = (size_t)s->ctx->d.M;
     if (by_day) HIP_TRY(hipMemcpyAsync(by_day, m.by_day + f * B * E * 3, sizeof(int64_t) * n * B * E * 3, hipMemcpyDeviceToHost, st));
     if (by_loc) HIP_TRY(hipMemcpyAsync(by_loc, m.by_loc + f * B * M * 3, sizeof(int64_t) * n * B * M * 3, hipMemcpyDeviceToHost, st));
     if (state_by_day)
         HIP_TRY(hipMemcpyAsync(state_by_day, m.state_by_day + f * B * E * 3, sizeof(int64_t) * n * B * E * 3, hipMemcpyDeviceToHost, st));
     return 0;
 }
-static int read_marginals(seir_sampler *s, bool async, int32_t first, int32_t count, const Marginals &m, int64_t *by_day,
-                          int64_t *by_loc, int64_t *state_by_day) {
+// What is behind every seir_sampler_read_*_marginals(_async), after the null-sampler refusal.
+static int read_marginals(seir_sampler *s, bool enabled, const TraceUser &what, const MomentBufs &m, int day_extent, bool async,
+                          int32_t first, int32_t count, int64_t *by_day, int64_t *by_loc, int64_t *state_by_day) {
+    if (int rc = trace_range_check(s, enabled, what, first, count)) return rc;
     if (async)   // as seir_sampler_read_trace_async
-        return on_copy_stream(s, [&](hipStream_t st) { return copy_marginals(s, st, first, count, m, by_day, by_loc, state_by_day); });
-    if (int rc = copy_marginals(s, s->ctx->stream, first, count, m, by_day, by_loc, state_by_day)) return rc;
+        return on_copy_stream(s, [&](hipStream_t st) {
+            return copy_marginals(s, st, first, count, m, (size_t)day_extent, by_day, by_loc, state_by_day);
+        });
+    if (int rc = copy_marginals(s, s->ctx->stream, first, count, m, (size_t)day_extent, by_day, by_loc, state_by_day)) return rc;
     HIP_TRY(hipStreamSynchronize(s->ctx->stream));
     return check_ev_overflow(s);
 }
@@ -2382,25 +2397,26 @@ extern "C" int seir_sampler_summarize(seir_sampler *s, int32_t first, int32_t co
 
 extern "C" int seir_sampler_read_marginals(seir_sampler *s, int32_t first, int32_t count, int64_t *events_by_day,
                                            int64_t *events_by_location, int64_t *state_by_day) {
-    int rc = sampler_check(s);
-    if (rc) return rc;
-    if ((rc = trace_range_check(s, s->sum_on, SUMMARY_USER, first, count))) return rc;
-    return read_marginals(s, false, first, count, marginals(s->sum, s->ctx->d.T), events_by_day, events_by_location, state_by_day);
+    if (int rc = sampler_check(s)) return rc;
+    return read_marginals(s, s->sum_on, SUMMARY_USER, s->sum, s->ctx->d.T, false, first, count, events_by_day, events_by_location,
+                          state_by_day);
 }
 
 extern "C" int seir_sampler_read_marginals_async(seir_sampler *s, int32_t first, int32_t count, int64_t *events_by_day,
                                                  int64_t *events_by_location, int64_t *state_by_day) {
-    int rc = sampler_check(s);
-    if (rc) return rc;
-    if ((rc = trace_range_check(s, s->sum_on, SUMMARY_USER, first, count))) return rc;
-    return read_marginals(s, true, first, count, marginals(s->sum, s->ctx->d.T), events_by_day, events_by_location, state_by_day);
+    if (int rc = sampler_check(s)) return rc;
+    return read_marginals(s, s->sum_on, SUMMARY_USER, s->sum, s->ctx->d.T, true, first, count, events_by_day, events_by_location,
+                          state_by_day);
 }
 
-// Blocking read of a set of moments; `whose` and `reset` word the refusal when an accumulator has overflowed.
-static int read_moments(seir_sampler *s, const MomentAcc &a, const char *whose, const char *reset, uint64_t *count, int32_t *ref,
-                        int64_t *sum, uint64_t *sumsq) {
+// What is behind every seir_sampler_read_<moments>, after the null-sampler refusal: a blocking read of a set of moments;
+// `whose` and `reset` word the refusal when an accumulator has overflowed.
+static int read_moments(seir_sampler *s, bool enabled, const TraceUser &what, const MomentAcc &a, const char *whose,
+                        const char *reset, uint64_t *count, int32_t *ref, int64_t *sum, uint64_t *sumsq) {
+    int rc = trace_range_check(s, enabled, what);
+    if (rc) return rc;
     unsigned flag = 0;
-    int rc = acc_read(a, s->ctx->stream, count, ref, sum, sumsq, &flag);
+    rc = acc_read(a, s->ctx->stream, count, ref, sum, sumsq, &flag);
     if (!rc) rc = check_ev_overflow(s);
     if (rc) return rc;
     if (flag) return fail(SEIR_ERR_STATE, "a sum of squared deviations reached 2^63: the %smoment accumulators overflowed "
@@ -2409,10 +2425,8 @@ static int read_moments(seir_sampler *s, const MomentAcc &a, const char *whose, 
 }
 
 extern "C" int seir_sampler_read_summary(seir_sampler *s, uint64_t *count, int32_t *ref, int64_t *sum, uint64_t *sumsq) {
-    int rc = sampler_check(s);
-    if (rc) return rc;
-    if ((rc = trace_range_check(s, s->sum_on, SUMMARY_USER))) return rc;
-    return read_moments(s, s->sum_acc, "", "seir_sampler_summary_reset", count, ref, sum, sumsq);
+    if (int rc = sampler_check(s)) return rc;
+    return read_moments(s, s->sum_on, SUMMARY_USER, s->sum_acc, "", "seir_sampler_summary_reset", count, ref, sum, sumsq);
 }
 
 // ---------------------------------------------------------------------------
@@ -2501,6 +2515,110 @@ extern "C" int seir_sampler_read_diag_mark(seir_sampler *s, int32_t which, uint6
 // ---------------------------------------------------------------------------
 // Forecast on the device (include/seir_hip.h; kernels: forecast_kernels.h)
 // ---------------------------------------------------------------------------
+// One Rollout behind the forecast and the in-sample check: what the two resets and the two calls have in common.  Where the
+// users differ (the range of the length, the prepare kernel, what follows the fold, their own buffers) the callers do it.
+static int rollout_refuse(const seir_sampler *s, const TraceUser &who, const double *W, const double *weekday_c) {
+    if (!W || !weekday_c) return fail(SEIR_ERR_INVALID, "null calendar pointer");
+    const Dims &d = s->ctx->d;
+    const size_t lds = k_simulate_lds_bytes(d);
+    if (lds > 160 * 1024) return fail(SEIR_ERR_INVALID, "M=%d needs %zu B of LDS for the simulator", d.M, lds);
+    if ((long long)s->cfg.chain0 + s->cfg.B > FC_MAX_CHAIN)
+        return fail(SEIR_ERR_INVALID, "global chain id %d: the %s's draw ids need chain ids below %d", s->cfg.chain0 + s->cfg.B - 1,
+                    who.name, FC_MAX_CHAIN);
+    return 0;
+}
+
+// First reset, or another length: everything is sized by H.  The caller sets r.on once its own buffers exist as well.
+static int rollout_resize(seir_sampler *s, Rollout &r, int H) {
+    int rc = drain(s);
+    if (rc) return rc;
+    rollout_free(r);
+    const Dims &d = s->ctx->d;
+    const size_t B = (size_t)s->cfg.B, cap = (size_t)s->cfg.cap;
+    ForecastBufs &fb = r.fb;
+    r.slots = std::min(s->cfg.cap, FC_JMAX);
+    r.ndmax = ceil_to(r.slots * s->cfg.B, 64);
+    const size_t plane = (size_t)d.Mp * r.ndmax, ndm = (size_t)r.slots * B;
+#define R_ALLOC(ptr, ...) if (!rc) rc = s_alloc(s, r.allocs, &(ptr), __VA_ARGS__)
+    double *Wd = nullptr, *wdd = nullptr;
+    R_ALLOC(Wd, H); R_ALLOC(wdd, H);
+    R_ALLOC(fb.St0, 3 * plane); R_ALLOC(fb.St, 3 * plane);
+    R_ALLOC(fb.X, plane); R_ALLOC(fb.F, plane); R_ALLOC(fb.eb, plane);
+    R_ALLOC(fb.sc, 3 * (size_t)r.ndmax); R_ALLOC(fb.base, (size_t)H * r.ndmax);
+    R_ALLOC(fb.fev, ndm * d.M * H * 3);              // the user's own staging tensor
+    R_ALLOC(fb.mom.by_day, cap * B * H * 3); R_ALLOC(fb.mom.by_loc, cap * B * d.M * 3);
+    R_ALLOC(fb.mom.state_by_day, cap * B * H * 3);
+#undef R_ALLOC
+    if (!rc) rc = acc_alloc(r.acc, B * d.M * H * seir::SUMMARY_Q, B, fb.mom);
+    if (rc) return rc;
+    fb.W = Wd; fb.wd = wdd;
+    fb.H = H;
+    (void)hipFuncSetAttribute((const void *)k_gemm<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_lds_bytes<64>());
+    return 0;
+}
+
+// Begin again: seed, calendar, moments and j.  Synchronises the stream, so what the caller has queued before is done as well.
+static int rollout_begin(seir_sampler *s, Rollout &r, const double *W, const double *weekday_c, uint64_t seed) {
+    hipStream_t st = s->ctx->stream;
+    ForecastBufs &fb = r.fb;
+    fb.k0 = (uint32_t)(seed & 0xffffffffu); fb.k1 = (uint32_t)(seed >> 32);
+    // the caller's arrays are not retained: blocking copies behind what is queued (a reset is not on the hot path)
+    HIP_TRY(hipMemcpyAsync(const_cast<double *>(fb.W), W, sizeof(double) * fb.H, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(const_cast<double *>(fb.wd), weekday_c, sizeof(double) * fb.H, hipMemcpyHostToDevice, st));
+    if (int rc = acc_zero(r.acc, st)) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    r.j = 0;
+    // what the snapshots taken before this reset hold of the moments is dropped with them: restoring one of them restores
+    // the chain and leaves the accumulators and j as they are
+    acc_invalidate(r.acc);
+    return 0;
+}
+
+static int rollout_ids_left(const Rollout &r, const TraceUser &who, int32_t count) {
+    if (r.j + count > (1ll << FC_ID_SHIFT))
+        return fail(SEIR_ERR_INVALID, "%lld draws per chain %s since the reset and %d more: the draw id holds 2^%d", r.j, who.done,
+                    count, FC_ID_SHIFT);
+    return 0;
+}
+
+// Trace slots [first + j0, first + j0 + nj) of a call: ND = nj * B draws, the planes' row stride ndp = ceil64(ND).
+struct RolloutBatch { int j0, nj, ND, ndp; };
+
+// The draws of trace slots [first, first + count) rolled forward fb.H days, in batches of at most r.slots slots.  Per batch:
+// prepare(fb, batch) -- the user's prepare kernel on the batch's copy of r.fb, which it may amend first -- then per day the
+// contraction and k_forecast_day, then k_forecast_fold, then after_fold(fb, batch).  The draw of slot first + jj has
+// j = r.j + jj; adding count to r.j is left to the caller, behind whatever else it enqueues.
+template <typename Prepare, typename AfterFold>
+static int rollout_days(seir_sampler *s, const Rollout &r, int32_t first, int32_t count, Prepare prepare, AfterFold after_fold) {
+    seir_ctx *ctx = s->ctx;
+    const LaunchCfg l = whole(ctx, s->cfg.B);
+    const Dims &d = l.d;
+    const int B = s->cfg.B, H = r.fb.H;
+    // by_day is summed with atomics: zero the call's slots first
+    HIP_TRY(hipMemsetAsync(r.fb.mom.by_day + (size_t)first * B * H * 3, 0, sizeof(int64_t) * count * B * H * 3, l.st));
+    Dims gd = d;                                     // the contraction's view: one "chain", the draw index as the day index
+    gd.b0 = 0;
+    Work gw{};
+    gw.Xn = r.fb.X; gw.F = r.fb.F;
+    for (int j0 = 0; j0 < count; j0 += r.slots) {
+        const int nj = std::min(r.slots, count - j0), ND = nj * B, ndp = ceil_to(ND, 64);
+        const RolloutBatch bt{j0, nj, ND, ndp};
+        ForecastBufs fb = r.fb;
+        if (int rc = prepare(fb, bt)) return rc;
+        gd.Tp = ndp;
+        for (int h = 0; h < H; ++h) {
+            hipLaunchKernelGGL((k_gemm<64>), dim3(ndp / 64, d.Mp / GEMM_TM, 1), dim3(gemm_threads<64>()), gemm_lds_bytes<64>(),
+                               l.st, gd, ctx->c, gw);
+            hipLaunchKernelGGL(k_forecast_day, dim3(ndp / 64, (d.M + FC_DAY_ROWS - 1) / FC_DAY_ROWS), dim3(64 * FC_DAY_ROWS), 0,
+                               l.st, d, ctx->c, fb, B, s->cfg.chain0, (int)(r.j + j0), ND, ndp, h);
+        }
+        hipLaunchKernelGGL(k_forecast_fold, dim3((d.M + FC_ROWS - 1) / FC_ROWS, B), dim3(64 * FC_ROWS), 0, l.st, d, fb, B,
+                           first + j0, nj, ndp);
+        after_fold(fb, bt);
+    }
+    return 0;
+}
+
 extern "C" int seir_sampler_forecast_reset(seir_sampler *s, int32_t horizon, const double *W, const double *weekday_c,
                                            uint64_t seed) {
     int rc = sampler_check(s);
@@ -2508,75 +2626,35 @@ extern "C" int seir_sampler_forecast_reset(seir_sampler *s, int32_t horizon, con
     if ((rc = need_events(s, FORECAST_USER.verb))) return rc;
     if (horizon < 1 || horizon > SEIR_FORECAST_MAX_H)
         return fail(SEIR_ERR_INVALID, "horizon=%d outside [1, %d]", horizon, SEIR_FORECAST_MAX_H);
-    if (!W || !weekday_c) return fail(SEIR_ERR_INVALID, "null calendar pointer");
-    const Dims &d = s->ctx->d;
-    const size_t lds = k_simulate_lds_bytes(d);
-    if (lds > 160 * 1024) return fail(SEIR_ERR_INVALID, "M=%d needs %zu B of LDS for the simulator", d.M, lds);
-    const int B = s->cfg.B, H = horizon;
-    if ((long long)s->cfg.chain0 + B > FC_MAX_CHAIN)
-        return fail(SEIR_ERR_INVALID, "global chain id %d: the forecast's draw ids need chain ids below %d", s->cfg.chain0 + B - 1,
-                    FC_MAX_CHAIN);
-    hipStream_t st = s->ctx->stream;
-    ForecastBufs &fb = s->fc;
-    const size_t cap = (size_t)s->cfg.cap;
-    if (!s->fc_on || fb.H != H) {
-        // first reset, or another horizon: everything is sized by H
-        HIP_TRY(hipStreamSynchronize(st));
-        if (s->copy_pending) { (void)hipEventSynchronize(s->ev_copy); s->copy_pending = false; }
-        for (void *p : s->fc_allocs) (void)hipFree(p);
-        s->fc_allocs.clear();
-        acc_free(s->fc_acc);
+    if ((rc = rollout_refuse(s, FORECAST_USER, W, weekday_c))) return rc;
+    Rollout &r = s->fc;
+    if (!r.on || r.fb.H != horizon) {
+        if ((rc = rollout_resize(s, r, horizon))) return rc;
+        // the steps' buffers and the draw store are sized by H as well; the stream is idle
         if (s->fc_steps_host) { (void)hipHostFree(s->fc_steps_host); s->fc_steps_host = nullptr; }
-        if (s->fc_keep) { (void)hipFree(s->fc_keep); s->fc_keep = nullptr; s->fc_keep_cap = 0; }   // sized by H as well
-        s->fc_on = false;
-        fb = ForecastBufs{};
-        s->fc_slots = std::min(s->cfg.cap, FC_JMAX);
-        s->fc_ndmax = ceil_to(s->fc_slots * B, 64);
-        const size_t plane = (size_t)d.Mp * s->fc_ndmax, ndm = (size_t)s->fc_slots * B;
-        double *Wd = nullptr, *wdd = nullptr;
-        S_ALLOC(fc_allocs, Wd, H); S_ALLOC(fc_allocs, wdd, H);
-        S_ALLOC(fc_allocs, fb.St0, 3 * plane); S_ALLOC(fc_allocs, fb.St, 3 * plane);
-        S_ALLOC(fc_allocs, fb.X, plane); S_ALLOC(fc_allocs, fb.F, plane); S_ALLOC(fc_allocs, fb.eb, plane);
-        S_ALLOC(fc_allocs, fb.sc, 3 * (size_t)s->fc_ndmax); S_ALLOC(fc_allocs, fb.base, (size_t)H * s->fc_ndmax);
-        S_ALLOC(fc_allocs, fb.fev, ndm * d.M * H * 3); S_ALLOC(fc_allocs, s->fc_steps_dev, ndm * H);
-        S_ALLOC(fc_allocs, fb.mom.by_day, cap * B * H * 3); S_ALLOC(fc_allocs, fb.mom.by_loc, cap * B * d.M * 3);
-        S_ALLOC(fc_allocs, fb.mom.state_by_day, cap * B * H * 3);
-        if (!rc) rc = acc_alloc(s->fc_acc, (size_t)B * d.M * H * seir::SUMMARY_Q, (size_t)B, fb.mom);
+        if (s->fc_keep) { (void)hipFree(s->fc_keep); s->fc_keep = nullptr; s->fc_keep_cap = 0; }
+        S_ALLOC(fc.allocs, s->fc_steps_dev, (size_t)r.slots * s->cfg.B * horizon);
         if (rc) return rc;
-        fb.W = Wd; fb.wd = wdd;
-        fb.H = H;
         if (!s->fc_ev_steps) HIP_TRY(hipEventCreate(&s->fc_ev_steps));
-        (void)hipFuncSetAttribute((const void *)k_gemm<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_lds_bytes<64>());
-        s->fc_on = true;
+        r.on = true;
     }
-    fb.k0 = (uint32_t)(seed & 0xffffffffu); fb.k1 = (uint32_t)(seed >> 32);
-    // the caller's arrays are not retained: blocking copies behind what is queued (a reset is not on the hot path)
-    HIP_TRY(hipMemcpyAsync(const_cast<double *>(fb.W), W, sizeof(double) * H, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(const_cast<double *>(fb.wd), weekday_c, sizeof(double) * H, hipMemcpyHostToDevice, st));
-    if ((rc = acc_zero(s->fc_acc, st))) return rc;
-    HIP_TRY(hipStreamSynchronize(st));
-    s->fc_j = 0;                                     // ... which empties the draw store too: it holds draws [0, fc_j)
-    // what the snapshots taken before this reset hold of the forecast is dropped with it: restoring one of them restores
-    // the chain and leaves the forecast accumulators and j as they are
-    acc_invalidate(s->fc_acc);
-    return 0;
+    return rollout_begin(s, r, W, weekday_c, seed);  // j = 0 empties the draw store too: it holds draws [0, j)
 }
 
 extern "C" int seir_sampler_forecast(seir_sampler *s, int32_t first, int32_t count, const double *log_baseline_steps) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    if ((rc = trace_range_check(s, s->fc_on, FORECAST_USER, first, count))) return rc;
+    Rollout &r = s->fc;
+    if ((rc = trace_range_check(s, r.on, FORECAST_USER, first, count))) return rc;
     if (count == 0) return 0;
-    if (s->fc_j + count > (1ll << FC_ID_SHIFT))
-        return fail(SEIR_ERR_INVALID, "%lld draws per chain forecast since the reset and %d more: the draw id holds 2^%d", s->fc_j,
-                    count, FC_ID_SHIFT);
-    if (s->fc_keep && s->fc_j + count > s->fc_keep_cap)
+    if ((rc = rollout_ids_left(r, FORECAST_USER, count))) return rc;
+    if (s->fc_keep && r.j + count > s->fc_keep_cap)
         return fail(SEIR_ERR_INVALID, "%lld draws per chain forecast since the reset and %d more: the draw store holds %lld "
-                    "(seir_sampler_forecast_keep)", s->fc_j, count, s->fc_keep_cap);
+                    "(seir_sampler_forecast_keep)", r.j, count, s->fc_keep_cap);
     seir_ctx *ctx = s->ctx;
     const LaunchCfg l = whole(ctx, s->cfg.B);
     const Dims &d = l.d;
-    const int B = s->cfg.B, H = s->fc.H;
+    const int B = s->cfg.B, H = r.fb.H;
     if (log_baseline_steps) {
         // through page-locked memory indexed by trace slot, so that the call stays asynchronous; a slot's steps are
         // overwritten only once the upload that read them last has been done
@@ -2584,73 +2662,50 @@ extern "C" int seir_sampler_forecast(seir_sampler *s, int32_t first, int32_t cou
         if (s->fc_steps_pending) { HIP_TRY(hipEventSynchronize(s->fc_ev_steps)); s->fc_steps_pending = false; }
         std::memcpy(s->fc_steps_host + (size_t)first * B * H, log_baseline_steps, sizeof(double) * count * B * H);
     }
-    // forecast_by_day is summed with atomics: zero the call's slots first
-    HIP_TRY(hipMemsetAsync(s->fc.mom.by_day + (size_t)first * B * H * 3, 0, sizeof(int64_t) * count * B * H * 3, l.st));
-    Dims gd = d;                                     // the contraction's view: one "chain", the draw index as the day index
-    gd.b0 = 0;
-    Work gw{};
-    gw.Xn = s->fc.X; gw.F = s->fc.F;
-    for (int j0 = 0; j0 < count; j0 += s->fc_slots) {
-        const int nj = std::min(s->fc_slots, count - j0), ND = nj * B, ndp = ceil_to(ND, 64);
-        ForecastBufs fb = s->fc;
-        fb.steps = nullptr;
-        if (log_baseline_steps) {
-            HIP_TRY(hipMemcpyAsync(s->fc_steps_dev, s->fc_steps_host + (size_t)(first + j0) * B * H, sizeof(double) * ND * H,
-                                   hipMemcpyHostToDevice, l.st));
-            fb.steps = s->fc_steps_dev;
-        }
-        const dim3 pgrid(d.Mp / FC_ROWS, ndp), pblock(64 * FC_ROWS);
-        if (s->cfg.ev16)
-            hipLaunchKernelGGL(k_forecast_prepare<1>, pgrid, pblock, 0, l.st, d, ctx->c, fb, (const double *)s->ch.tr_theta,
-                               (const void *)s->ch.tr_events, B, first + j0, ND, ndp);
-        else
-            hipLaunchKernelGGL(k_forecast_prepare<0>, pgrid, pblock, 0, l.st, d, ctx->c, fb, (const double *)s->ch.tr_theta,
-                               (const void *)s->ch.tr_events, B, first + j0, ND, ndp);
-        gd.Tp = ndp;
-        for (int h = 0; h < H; ++h) {
-            hipLaunchKernelGGL((k_gemm<64>), dim3(ndp / 64, d.Mp / GEMM_TM, 1), dim3(gemm_threads<64>()), gemm_lds_bytes<64>(),
-                               l.st, gd, ctx->c, gw);
-            hipLaunchKernelGGL(k_forecast_day, dim3(ndp / 64, (d.M + FC_DAY_ROWS - 1) / FC_DAY_ROWS), dim3(64 * FC_DAY_ROWS), 0,
-                               l.st, d, ctx->c, fb, B, s->cfg.chain0, (int)(s->fc_j + j0), ND, ndp, h);
-        }
-        hipLaunchKernelGGL(k_forecast_fold, dim3((d.M + FC_ROWS - 1) / FC_ROWS, B), dim3(64 * FC_ROWS), 0, l.st, d, fb, B,
-                           first + j0, nj, ndp);
-        if (s->fc_keep)
-            hipLaunchKernelGGL(k_forecast_keep, dim3((d.M + KEEP_ROWS - 1) / KEEP_ROWS, B), dim3(64 * KEEP_ROWS), 0, l.st, d,
-                               (const int *)fb.fev, (const int *)(fb.St0 + 2 * (size_t)d.Mp * ndp), s->fc_keep, s->fc_keep_cap,
-                               s->fc_j + j0, H, B, nj, ndp);
-        hipLaunchKernelGGL(k_forecast_finish, dim3(nj, B), dim3(64), 0, l.st, d, fb, B, first + j0, nj, ndp);
-    }
+    rc = rollout_days(s, r, first, count,
+        [&](ForecastBufs &fb, const RolloutBatch &bt) {
+            if (log_baseline_steps) {
+                HIP_TRY(hipMemcpyAsync(s->fc_steps_dev, s->fc_steps_host + (size_t)(first + bt.j0) * B * H,
+                                       sizeof(double) * bt.ND * H, hipMemcpyHostToDevice, l.st));
+                fb.steps = s->fc_steps_dev;
+            }
+            hipLaunchKernelGGL(s->cfg.ev16 ? k_forecast_prepare<1> : k_forecast_prepare<0>, dim3(d.Mp / FC_ROWS, bt.ndp),
+                               dim3(64 * FC_ROWS), 0, l.st, d, ctx->c, fb, (const double *)s->ch.tr_theta,
+                               (const void *)s->ch.tr_events, B, first + bt.j0, bt.ND, bt.ndp);
+            return 0;
+        },
+        [&](const ForecastBufs &fb, const RolloutBatch &bt) {
+            if (s->fc_keep)
+                hipLaunchKernelGGL(k_forecast_keep, dim3((d.M + KEEP_ROWS - 1) / KEEP_ROWS, B), dim3(64 * KEEP_ROWS), 0, l.st, d,
+                                   (const int *)fb.fev, (const int *)(fb.St0 + 2 * (size_t)d.Mp * bt.ndp), s->fc_keep,
+                                   s->fc_keep_cap, r.j + bt.j0, H, B, bt.nj, bt.ndp);
+            hipLaunchKernelGGL(k_forecast_finish, dim3(bt.nj, B), dim3(64), 0, l.st, d, fb, B, first + bt.j0, bt.nj, bt.ndp);
+        });
+    if (rc) return rc;
     if (log_baseline_steps) { HIP_TRY(hipEventRecord(s->fc_ev_steps, l.st)); s->fc_steps_pending = true; }
     HIP_TRY(hipGetLastError());
-    s->fc_j += count;
+    r.j += count;
     return 0;
 }
 
 extern "C" int seir_sampler_read_forecast_marginals(seir_sampler *s, int32_t first, int32_t count, int64_t *forecast_by_day,
                                                     int64_t *forecast_by_location, int64_t *forecast_state_by_day) {
-    int rc = sampler_check(s);
-    if (rc) return rc;
-    if ((rc = trace_range_check(s, s->fc_on, FORECAST_USER, first, count))) return rc;
-    return read_marginals(s, false, first, count, marginals(s->fc.mom, s->fc.H), forecast_by_day, forecast_by_location,
-                          forecast_state_by_day);
+    if (int rc = sampler_check(s)) return rc;
+    return read_marginals(s, s->fc.on, FORECAST_USER, s->fc.fb.mom, s->fc.fb.H, false, first, count, forecast_by_day,
+                          forecast_by_location, forecast_state_by_day);
 }
 
 extern "C" int seir_sampler_read_forecast_marginals_async(seir_sampler *s, int32_t first, int32_t count,
                                                           int64_t *forecast_by_day, int64_t *forecast_by_location,
                                                           int64_t *forecast_state_by_day) {
-    int rc = sampler_check(s);
-    if (rc) return rc;
-    if ((rc = trace_range_check(s, s->fc_on, FORECAST_USER, first, count))) return rc;
-    return read_marginals(s, true, first, count, marginals(s->fc.mom, s->fc.H), forecast_by_day, forecast_by_location,
-                          forecast_state_by_day);
+    if (int rc = sampler_check(s)) return rc;
+    return read_marginals(s, s->fc.on, FORECAST_USER, s->fc.fb.mom, s->fc.fb.H, true, first, count, forecast_by_day,
+                          forecast_by_location, forecast_state_by_day);
 }
 
 extern "C" int seir_sampler_read_forecast(seir_sampler *s, uint64_t *count, int32_t *ref, int64_t *sum, uint64_t *sumsq) {
-    int rc = sampler_check(s);
-    if (rc) return rc;
-    if ((rc = trace_range_check(s, s->fc_on, FORECAST_USER))) return rc;
-    return read_moments(s, s->fc_acc, "forecast's ", "seir_sampler_forecast_reset", count, ref, sum, sumsq);
+    if (int rc = sampler_check(s)) return rc;
+    return read_moments(s, s->fc.on, FORECAST_USER, s->fc.acc, "forecast's ", "seir_sampler_forecast_reset", count, ref, sum, sumsq);
 }
 
 // ---------------------------------------------------------------------------
@@ -2659,7 +2714,7 @@ extern "C" int seir_sampler_read_forecast(seir_sampler *s, uint64_t *count, int3
 extern "C" int seir_sampler_forecast_keep(seir_sampler *s, int64_t cap) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    if ((rc = trace_range_check(s, s->fc_on, FORECAST_USER))) return rc;
+    if ((rc = trace_range_check(s, s->fc.on, FORECAST_USER))) return rc;
     if (cap < 0 || cap > (1ll << FC_ID_SHIFT))
         return fail(SEIR_ERR_INVALID, "cap=%lld outside [0, 2^%d]: the draws per chain between two resets", (long long)cap, FC_ID_SHIFT);
     hipStream_t st = s->ctx->stream;
@@ -2671,22 +2726,22 @@ extern "C" int seir_sampler_forecast_keep(seir_sampler *s, int64_t cap) {
         }
         return 0;
     }
-    if (s->fc_j != 0)
+    if (s->fc.j != 0)
         return fail(SEIR_ERR_STATE, "%lld draws per chain have been forecast since the reset: the draw store is sized between "
-                    "seir_sampler_forecast_reset and the first seir_sampler_forecast", s->fc_j);
+                    "seir_sampler_forecast_reset and the first seir_sampler_forecast", s->fc.j);
     if (s->fc_keep && s->fc_keep_cap == cap) return 0;       // the reset has emptied it
     if (s->fc_keep) {
         HIP_TRY(hipStreamSynchronize(st));
         (void)hipFree(s->fc_keep);
         s->fc_keep = nullptr; s->fc_keep_cap = 0;
     }
-    const unsigned long long cells = 3ull * s->cfg.B * s->ctx->d.M * s->fc.H, bytes = cells * (unsigned long long)cap * 4ull;
+    const unsigned long long cells = 3ull * s->cfg.B * s->ctx->d.M * s->fc.fb.H, bytes = cells * (unsigned long long)cap * 4ull;
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     // half of what is free: the policy of a device that is shared, not a measurement
     if (bytes > (unsigned long long)free_b / 2)
         return fail(SEIR_ERR_INVALID, "the draw store needs %llu bytes (%d chains x 3 x %d locations x %d days x %lld draws x 4), "
-                    "more than half of the %llu bytes free on the device", bytes, s->cfg.B, s->ctx->d.M, s->fc.H, (long long)cap,
+                    "more than half of the %llu bytes free on the device", bytes, s->cfg.B, s->ctx->d.M, s->fc.fb.H, (long long)cap,
                     (unsigned long long)free_b);
     void *q = nullptr;
     HIP_TRY(hipMalloc(&q, (size_t)bytes));
@@ -2719,26 +2774,26 @@ static void order_launch(const OrderArgs &a, hipStream_t st) {
 extern "C" int seir_sampler_forecast_order_stats(seir_sampler *s, const int64_t *ranks, int32_t R, int32_t pooled, int32_t *out) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    if ((rc = trace_range_check(s, s->fc_on, FORECAST_USER))) return rc;
+    if ((rc = trace_range_check(s, s->fc.on, FORECAST_USER))) return rc;
     if (!s->fc_keep) return fail(SEIR_ERR_STATE, "the draw store is not enabled: call seir_sampler_forecast_keep first");
     if (!out) return fail(SEIR_ERR_INVALID, "null output pointer");
-    if (s->fc_j < 1) return fail(SEIR_ERR_STATE, "no draws kept since the forecast reset");
+    if (s->fc.j < 1) return fail(SEIR_ERR_STATE, "no draws kept since the forecast reset");
     const int B = s->cfg.B;
     hipStream_t st = s->ctx->stream;
     std::vector<uint64_t> cnt((size_t)B);
-    HIP_TRY(hipMemcpyAsync(cnt.data(), s->fc.mom.count, sizeof(uint64_t) * B, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(cnt.data(), s->fc.fb.mom.count, sizeof(uint64_t) * B, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     for (int b = 0; b < B; ++b)
-        if ((long long)cnt[b] != s->fc_j)
+        if ((long long)cnt[b] != s->fc.j)
             return fail(SEIR_ERR_STATE, "chain %d has %llu draws forecast, the store %lld: the chains' counts differ", b,
-                        (unsigned long long)cnt[b], s->fc_j);
-    const long long plane = 3ll * s->ctx->d.M * s->fc.H;
+                        (unsigned long long)cnt[b], s->fc.j);
+    const long long plane = 3ll * s->ctx->d.M * s->fc.fb.H;
     OrderArgs a{};
-    if ((rc = order_ranks(ranks, R, pooled ? s->fc_j * B : s->fc_j, a))) return rc;
+    if ((rc = order_ranks(ranks, R, pooled ? s->fc.j * B : s->fc.j, a))) return rc;
     a.values = s->fc_keep;
     a.cells = pooled ? plane : plane * B;
     a.segs = pooled ? B : 1;
-    a.seg_len = s->fc_j;
+    a.seg_len = s->fc.j;
     a.seg_stride = plane * s->fc_keep_cap;
     a.cell_stride = s->fc_keep_cap;
     DevBuf dout;
@@ -2806,133 +2861,70 @@ extern "C" int seir_sampler_check_reset(seir_sampler *s, int32_t days, const dou
     const Dims &d = s->ctx->d;
     const int kmax = std::min(d.T, SEIR_CHECK_MAX_DAYS);
     if (days < 1 || days > kmax) return fail(SEIR_ERR_INVALID, "days=%d outside [1, min(T = %d, %d)]", days, d.T, SEIR_CHECK_MAX_DAYS);
-    if (!W || !weekday_c) return fail(SEIR_ERR_INVALID, "null calendar pointer");
-    const size_t lds = k_simulate_lds_bytes(d);
-    if (lds > 160 * 1024) return fail(SEIR_ERR_INVALID, "M=%d needs %zu B of LDS for the simulator", d.M, lds);
-    const int B = s->cfg.B, K = days;
-    if ((long long)s->cfg.chain0 + B > FC_MAX_CHAIN)
-        return fail(SEIR_ERR_INVALID, "global chain id %d: the check's draw ids need chain ids below %d", s->cfg.chain0 + B - 1,
-                    FC_MAX_CHAIN);
-    hipStream_t st = s->ctx->stream;
-    ForecastBufs &fb = s->ck;
-    const size_t cap = (size_t)s->cfg.cap;
-    if (!s->ck_on || fb.H != K) {
-        // first reset, or another window: everything is sized by K
-        HIP_TRY(hipStreamSynchronize(st));
-        if (s->copy_pending) { (void)hipEventSynchronize(s->ev_copy); s->copy_pending = false; }
-        for (void *p : s->ck_allocs) (void)hipFree(p);
-        s->ck_allocs.clear();
-        acc_free(s->ck_acc);
-        acc_free(s->ck_cnt);
-        s->ck_on = false;
-        fb = ForecastBufs{};
-        s->ck_slots = std::min(s->cfg.cap, FC_JMAX);
-        s->ck_ndmax = ceil_to(s->ck_slots * B, 64);
-        const size_t plane = (size_t)d.Mp * s->ck_ndmax, ndm = (size_t)s->ck_slots * B;
-        double *Wd = nullptr, *wdd = nullptr;
-        S_ALLOC(ck_allocs, Wd, K); S_ALLOC(ck_allocs, wdd, K);
-        S_ALLOC(ck_allocs, fb.St0, 3 * plane); S_ALLOC(ck_allocs, fb.St, 3 * plane);
-        S_ALLOC(ck_allocs, fb.X, plane); S_ALLOC(ck_allocs, fb.F, plane); S_ALLOC(ck_allocs, fb.eb, plane);
-        S_ALLOC(ck_allocs, fb.sc, 3 * (size_t)s->ck_ndmax); S_ALLOC(ck_allocs, fb.base, (size_t)K * s->ck_ndmax);
-        S_ALLOC(ck_allocs, fb.fev, ndm * d.M * K * 3);       // the check's own staging tensor
-        S_ALLOC(ck_allocs, fb.mom.by_day, cap * B * K * 3); S_ALLOC(ck_allocs, fb.mom.by_loc, cap * B * d.M * 3);
-        S_ALLOC(ck_allocs, fb.mom.state_by_day, cap * B * K * 3);
-        if (!rc) rc = acc_alloc(s->ck_acc, (size_t)B * d.M * K * seir::SUMMARY_Q, (size_t)B, fb.mom);
-        if (!rc) rc = acc_alloc(s->ck_cnt, check_words(s, K) * sizeof(uint32_t));
-        if (rc) return rc;
-        check_layout(s, K);
-        fb.W = Wd; fb.wd = wdd;
-        fb.H = K;
-        fb.steps = nullptr;
-        (void)hipFuncSetAttribute((const void *)k_gemm<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_lds_bytes<64>());
-        s->ck_on = true;
+    if ((rc = rollout_refuse(s, CHECK_USER, W, weekday_c))) return rc;
+    Rollout &r = s->ck;
+    if (!r.on || r.fb.H != days) {
+        if ((rc = rollout_resize(s, r, days))) return rc;
+        acc_free(s->ck_cnt);                         // sized by K as well; the stream is idle
+        if ((rc = acc_alloc(s->ck_cnt, check_words(s, days) * sizeof(uint32_t)))) return rc;
+        check_layout(s, days);
+        r.on = true;
     }
-    fb.k0 = (uint32_t)(seed & 0xffffffffu); fb.k1 = (uint32_t)(seed >> 32);
-    // the caller's arrays are not retained: blocking copies behind what is queued (a reset is not on the hot path)
-    HIP_TRY(hipMemcpyAsync(const_cast<double *>(fb.W), W, sizeof(double) * K, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(const_cast<double *>(fb.wd), weekday_c, sizeof(double) * K, hipMemcpyHostToDevice, st));
-    if ((rc = acc_zero(s->ck_acc, st))) return rc;
-    if ((rc = acc_zero(s->ck_cnt, st))) return rc;
-    HIP_TRY(hipStreamSynchronize(st));
-    s->ck_j = 0;
-    // what the snapshots taken before this reset hold of the check is dropped with it
-    acc_invalidate(s->ck_acc);
-    acc_invalidate(s->ck_cnt);
+    if ((rc = acc_zero(s->ck_cnt, s->ctx->stream))) return rc;
+    if ((rc = rollout_begin(s, r, W, weekday_c, seed))) return rc;
+    acc_invalidate(s->ck_cnt);                       // dropped from the snapshots with the moments
     return 0;
 }
 
 extern "C" int seir_sampler_check(seir_sampler *s, int32_t first, int32_t count) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    if ((rc = trace_range_check(s, s->ck_on, CHECK_USER, first, count))) return rc;
+    Rollout &r = s->ck;
+    if ((rc = trace_range_check(s, r.on, CHECK_USER, first, count))) return rc;
     if (count == 0) return 0;
-    if (s->ck_j + count > (1ll << FC_ID_SHIFT))
-        return fail(SEIR_ERR_INVALID, "%lld draws per chain checked since the reset and %d more: the draw id holds 2^%d", s->ck_j,
-                    count, FC_ID_SHIFT);
+    if ((rc = rollout_ids_left(r, CHECK_USER, count))) return rc;
     seir_ctx *ctx = s->ctx;
     const LaunchCfg l = whole(ctx, s->cfg.B);
     const Dims &d = l.d;
-    const int B = s->cfg.B, K = s->ck.H;
-    // check_by_day is summed with atomics: zero the call's slots first
-    HIP_TRY(hipMemsetAsync(s->ck.mom.by_day + (size_t)first * B * K * 3, 0, sizeof(int64_t) * count * B * K * 3, l.st));
-    Dims gd = d;                                     // the contraction's view: one "chain", the draw index as the day index
-    gd.b0 = 0;
-    Work gw{};
-    gw.Xn = s->ck.X; gw.F = s->ck.F;
-    const ForecastBufs &fb = s->ck;
-    for (int j0 = 0; j0 < count; j0 += s->ck_slots) {
-        const int nj = std::min(s->ck_slots, count - j0), ND = nj * B, ndp = ceil_to(ND, 64);
-        const int fresh = s->ck_j + j0 == 0;
-        const dim3 pgrid(d.Mp / FC_ROWS, ndp), rgrid((d.M + FC_ROWS - 1) / FC_ROWS, B), rblock(64 * FC_ROWS);
-        if (s->cfg.ev16)
-            hipLaunchKernelGGL(k_check_prepare<1>, pgrid, rblock, 0, l.st, d, ctx->c, fb, (const double *)s->ch.tr_theta,
-                               (const void *)s->ch.tr_events, B, first + j0, ND, ndp);
-        else
-            hipLaunchKernelGGL(k_check_prepare<0>, pgrid, rblock, 0, l.st, d, ctx->c, fb, (const double *)s->ch.tr_theta,
-                               (const void *)s->ch.tr_events, B, first + j0, ND, ndp);
-        gd.Tp = ndp;
-        for (int h = 0; h < K; ++h) {
-            hipLaunchKernelGGL((k_gemm<64>), dim3(ndp / 64, d.Mp / GEMM_TM, 1), dim3(gemm_threads<64>()), gemm_lds_bytes<64>(),
-                               l.st, gd, ctx->c, gw);
-            hipLaunchKernelGGL(k_forecast_day, dim3(ndp / 64, (d.M + FC_DAY_ROWS - 1) / FC_DAY_ROWS), dim3(64 * FC_DAY_ROWS), 0,
-                               l.st, d, ctx->c, fb, B, s->cfg.chain0, (int)(s->ck_j + j0), ND, ndp, h);
-        }
-        hipLaunchKernelGGL(k_forecast_fold, rgrid, rblock, 0, l.st, d, fb, B, first + j0, nj, ndp);
-        hipLaunchKernelGGL(k_forecast_finish, dim3(nj, B), dim3(64), 0, l.st, d, fb, B, first + j0, nj, ndp);
-        if (s->cfg.ev16)
-            hipLaunchKernelGGL(k_check_compare<1>, rgrid, rblock, 0, l.st, d, fb, s->ck_cmp, (const void *)s->ch.tr_events, B,
-                               first + j0, nj, fresh);
-        else
-            hipLaunchKernelGGL(k_check_compare<0>, rgrid, rblock, 0, l.st, d, fb, s->ck_cmp, (const void *)s->ch.tr_events, B,
-                               first + j0, nj, fresh);
-        hipLaunchKernelGGL(k_check_totals, dim3(B), dim3(CK_TOT_THREADS), 0, l.st, d, fb, s->ck_cmp, B, first + j0, nj);
-    }
+    const int B = s->cfg.B;
+    const dim3 rgrid((d.M + FC_ROWS - 1) / FC_ROWS, B), rblock(64 * FC_ROWS);
+    rc = rollout_days(s, r, first, count,
+        [&](ForecastBufs &fb, const RolloutBatch &bt) {
+            hipLaunchKernelGGL(s->cfg.ev16 ? k_check_prepare<1> : k_check_prepare<0>, dim3(d.Mp / FC_ROWS, bt.ndp), rblock, 0,
+                               l.st, d, ctx->c, fb, (const double *)s->ch.tr_theta, (const void *)s->ch.tr_events, B,
+                               first + bt.j0, bt.ND, bt.ndp);
+            return 0;
+        },
+        [&](const ForecastBufs &fb, const RolloutBatch &bt) {
+            const int fresh = r.j + bt.j0 == 0;
+            hipLaunchKernelGGL(k_forecast_finish, dim3(bt.nj, B), dim3(64), 0, l.st, d, fb, B, first + bt.j0, bt.nj, bt.ndp);
+            hipLaunchKernelGGL(s->cfg.ev16 ? k_check_compare<1> : k_check_compare<0>, rgrid, rblock, 0, l.st, d, fb, s->ck_cmp,
+                               (const void *)s->ch.tr_events, B, first + bt.j0, bt.nj, fresh);
+            hipLaunchKernelGGL(k_check_totals, dim3(B), dim3(CK_TOT_THREADS), 0, l.st, d, fb, s->ck_cmp, B, first + bt.j0, bt.nj);
+        });
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
-    s->ck_j += count;
+    r.j += count;
     return 0;
 }
 
 extern "C" int seir_sampler_read_check_marginals(seir_sampler *s, int32_t first, int32_t count, int64_t *check_by_day,
                                                  int64_t *check_by_location, int64_t *check_state_by_day) {
-    int rc = sampler_check(s);
-    if (rc) return rc;
-    if ((rc = trace_range_check(s, s->ck_on, CHECK_USER, first, count))) return rc;
-    return read_marginals(s, false, first, count, marginals(s->ck.mom, s->ck.H), check_by_day, check_by_location, check_state_by_day);
+    if (int rc = sampler_check(s)) return rc;
+    return read_marginals(s, s->ck.on, CHECK_USER, s->ck.fb.mom, s->ck.fb.H, false, first, count, check_by_day, check_by_location,
+                          check_state_by_day);
 }
 
 extern "C" int seir_sampler_read_check_marginals_async(seir_sampler *s, int32_t first, int32_t count, int64_t *check_by_day,
                                                        int64_t *check_by_location, int64_t *check_state_by_day) {
-    int rc = sampler_check(s);
-    if (rc) return rc;
-    if ((rc = trace_range_check(s, s->ck_on, CHECK_USER, first, count))) return rc;
-    return read_marginals(s, true, first, count, marginals(s->ck.mom, s->ck.H), check_by_day, check_by_location, check_state_by_day);
+    if (int rc = sampler_check(s)) return rc;
+    return read_marginals(s, s->ck.on, CHECK_USER, s->ck.fb.mom, s->ck.fb.H, true, first, count, check_by_day, check_by_location,
+                          check_state_by_day);
 }
 
 extern "C" int seir_sampler_read_check(seir_sampler *s, uint64_t *count, int32_t *ref, int64_t *sum, uint64_t *sumsq) {
-    int rc = sampler_check(s);
-    if (rc) return rc;
-    if ((rc = trace_range_check(s, s->ck_on, CHECK_USER))) return rc;
-    return read_moments(s, s->ck_acc, "check's ", "seir_sampler_check_reset", count, ref, sum, sumsq);
+    if (int rc = sampler_check(s)) return rc;
+    return read_moments(s, s->ck.on, CHECK_USER, s->ck.acc, "check's ", "seir_sampler_check_reset", count, ref, sum, sumsq);
 }
 
 extern "C" int seir_sampler_read_check_counts(seir_sampler *s, int32_t *obs, uint32_t *lt, uint32_t *eq, uint32_t *loc_lt,
@@ -2940,9 +2932,9 @@ extern "C" int seir_sampler_read_check_counts(seir_sampler *s, int32_t *obs, uin
                                               uint32_t *all_eq) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    if ((rc = trace_range_check(s, s->ck_on, CHECK_USER))) return rc;
+    if ((rc = trace_range_check(s, s->ck.on, CHECK_USER))) return rc;
     hipStream_t st = s->ctx->stream;
-    const size_t B = (size_t)s->cfg.B, M = (size_t)s->ctx->d.M, K = (size_t)s->ck.H;
+    const size_t B = (size_t)s->cfg.B, M = (size_t)s->ctx->d.M, K = (size_t)s->ck.fb.H;
     const CheckCmp &cc = s->ck_cmp;
     std::vector<unsigned> moved(B, 0u);
     HIP_TRY(hipMemcpyAsync(moved.data(), cc.moved, sizeof(unsigned) * B, hipMemcpyDeviceToHost, st));
@@ -2985,8 +2977,7 @@ extern "C" int seir_sampler_rt_reset(seir_sampler *s, int32_t days, const double
     RtBufs &rb = s->rt;
     if (!s->rt_on || rb.D != D) {
         // first reset, or another window: everything is sized by D
-        HIP_TRY(hipStreamSynchronize(st));
-        if (s->copy_pending) { (void)hipEventSynchronize(s->ev_copy); s->copy_pending = false; }
+        if ((rc = drain(s))) return rc;
         for (void *p : s->rt_allocs) (void)hipFree(p);
         s->rt_allocs.clear();
         acc_free(s->rt_acc);

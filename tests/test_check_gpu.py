@@ -460,6 +460,49 @@ def test_data_that_move_between_draws_raise_the_flag_and_the_read_fails_with_its
         _same_summary(cs, _oracle(model, case, tr.theta, tr.events, K))
 
 
+def test_a_reset_with_another_window_on_a_checking_sampler_starts_everything_again(api):
+    """A reset with another K while the check is on: every buffer is sized again (K = 1, then K = T: window start 0), and a
+    snapshot from before the reset no longer holds anything of the check -- restoring it leaves moments, comparison counts
+    and the library's j alone."""
+    case, u, ev, cfg, eps = _case("micro_20x60", 3)
+    n, T = 5, case["k"].T
+    assert T == 60
+    model, s = _sampler(api, case, cfg, u, ev, eps, n)
+    with model, s:
+        _reset(s, case, 12)
+        tr = s.sample(n, check=True)
+        cs = s.check_summary()
+        want = _oracle(model, case, tr.theta, tr.events, 12)
+        assert want["sim"].any() and cs.moments.sumsq.any()
+        _same_summary(cs, want)
+        _same_marginals(tr.check, want)
+        s.snapshot(0)
+        _reset(s, case, 1)
+        s.check(0, n)
+        want = _oracle(model, case, tr.theta, tr.events, 1)
+        _same_summary(s.check_summary(), want)
+        _same_marginals(s.read_check_marginals(n), want)
+        s.restore(0)                                           # the snapshot predates the reset: the check is left alone
+        cs = s.check_summary()
+        assert np.array_equal(cs.count, [n] * 3)
+        assert np.all(cs.lt.astype(np.int64) + cs.eq <= cs.count[:, None, None].astype(np.int64))
+        _same_summary(cs, want)
+        s.check(0, 1)                                          # the library's j is still n (the call passes none)
+        one = _oracle(model, case, tr.theta[:1], tr.events[:1], 1, j0=n)
+        _same_marginals(s.read_check_marginals(1), one)
+        cs = s.check_summary()
+        assert np.array_equal(cs.count, [n + 1] * 3)
+        assert np.array_equal(cs.observed, want["observed"])
+        for k in COUNTS[1:]:
+            assert np.array_equal(getattr(cs, k), want[k] + one[k]), k
+        _reset(s, case, T)                                     # larger: the whole series, window start 0
+        s.check(0, n)
+        want = _oracle(model, case, tr.theta, tr.events, T)
+        _same_summary(s.check_summary(), want)
+        _same_marginals(s.read_check_marginals(n), want)
+        assert not s.pair_timeouts().any()
+
+
 def test_refusals(api):
     case, u, ev, cfg, eps = _case("micro_20x60", 2)
     T = case["k"].T

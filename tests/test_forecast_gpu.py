@@ -399,6 +399,50 @@ def test_a_burst_run_again_after_a_time_out_is_forecast_and_counted_once(api):
     _same_marginals({k: np.concatenate([got[0][i][1][k] for i in range(nb)]) for k in FC}, want2)
 
 
+def test_a_reset_with_another_horizon_on_a_forecasting_sampler_starts_everything_again(api):
+    """A reset with another H while the forecast is on: every buffer is sized again (a smaller H, then one past the fold's
+    64-day chunk), the steps' buffers and the draw store go, and a snapshot from before the reset no longer holds anything
+    of the forecast -- restoring it leaves moments, count and the library's j alone."""
+    case, u, ev, cfg, eps = _case("micro_20x60", 3)
+    n = 5
+    rng = np.random.default_rng(11)
+    steps9, steps3 = rng.normal(0.0, 0.05, size=(n, 3, 9)), rng.normal(0.0, 0.05, size=(n, 3, 3))
+    model, s = _sampler(api, case, cfg, u, ev, eps, n)
+    with model, s:
+        _reset(s, case, 9)
+        s.keep_forecast_draws(n)
+        tr = s.sample(n, forecast=lambda j0, count: steps9[j0:j0 + count])
+        sm = s.forecast_summary()
+        want = _oracle(model, case, tr.theta, tr.events, 9, steps=steps9)
+        _moved(want, sm)
+        _same_moments(sm, want)
+        _same_marginals(tr.forecast, want)
+        assert s.forecast_order_stats([0, n - 1]).shape == (2, 3, 3, case["k"].M, 9)
+        s.snapshot(0)
+        _reset(s, case, 3)                                     # smaller: the store was sized by the old H and is gone
+        with pytest.raises(_lib.SeirError, match="the draw store is not enabled") as e:
+            s.forecast_order_stats([0])
+        assert e.value.code == _lib.ERR_STATE
+        s.forecast(0, n, steps3)
+        want = _oracle(model, case, tr.theta, tr.events, 3, steps=steps3)
+        _same_moments(s.forecast_summary(), want)
+        _same_marginals(s.read_forecast_marginals(n), want)
+        s.restore(0)                                           # the snapshot predates the reset: the forecast is left alone
+        sm = s.forecast_summary()
+        assert np.array_equal(sm.count, [n] * 3)
+        _same_moments(sm, want)
+        s.forecast(0, 1)                                       # the library's j is still n (the call passes none)
+        one = _oracle(model, case, tr.theta[:1], tr.events[:1], 3, j0=n)
+        _same_marginals(s.read_forecast_marginals(1), one)
+        assert np.array_equal(s.forecast_summary().count, [n + 1] * 3)
+        _reset(s, case, 70)                                    # larger, and past the fold's 64-day chunk
+        s.forecast(0, n)
+        want = _oracle(model, case, tr.theta, tr.events, 70)
+        _same_moments(s.forecast_summary(), want)
+        _same_marginals(s.read_forecast_marginals(n), want)
+        assert not s.pair_timeouts().any()
+
+
 def test_refusals(api):
     case, u, ev, cfg, eps = _case("micro_20x60", 2)
     W, wd = _calendar(case, 5)
