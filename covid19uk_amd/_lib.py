@@ -222,6 +222,15 @@ _SIGNATURES = {
     "seir_sampler_read_rt_draws_async": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, c_double_p]),
     "seir_sampler_read_rt": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), c_double_p, c_double_p,
                                             c_double_p, ctypes.POINTER(ctypes.c_uint32)]),
+    # within/between pressure shares of the kept draws from the burst buffer: moments per cell, national pressures per draw
+    "seir_sampler_wb_reset": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
+    "seir_sampler_wb": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]),
+    "seir_sampler_read_wb": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32),
+                                            c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                            ctypes.POINTER(ctypes.c_uint32)]),
+    "seir_sampler_read_wb_draws": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, c_double_p, c_double_p]),
+    "seir_sampler_read_wb_draws_async": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, c_double_p,
+                                                        c_double_p]),
 }
 
 _lib = None

@@ -24,6 +24,7 @@
 #include "forecast_kernels.h"
 #include "check_kernels.h"
 #include "rt_trace_kernels.h"
+#include "wb_kernels.h"
 #include "order_stats_kernels.h"
 
 using namespace seir;
@@ -1278,6 +1279,12 @@ struct seir_sampler {
     int rt_slots = 0;                 // trace slots the batch planes (ea, S, part) are allocated for
     std::vector<void *> rt_allocs;    // device buffers sized by the window (allocated again when it changes)
     Shadowed rt_acc;                  // sum [cells] | sumsq [cells] | ref [cells] | count [B, padded] | gt1 [cells]
+    // --- within/between pressure shares of the kept draws (seir_sampler_wb_reset ...; wb_kernels.h) ---
+    bool wb_on = false;
+    WbBufs wb{};
+    int wb_slots = 0;                 // trace slots the batch planes (I, part) are allocated for
+    std::vector<void *> wb_allocs;    // device buffers sized by the window (allocated again when it changes)
+    Shadowed wb_acc;                  // sum_w | sumsq_w | ref_w | ref_b | sum_b [cells] | count [B, padded] | n [cells] | gt [cells]
 };
 
 // Zeroed device memory, registered in `list` (seir_sampler::allocs: freed with the sampler; Rollout::allocs: also when the length
@@ -1330,8 +1337,9 @@ extern "C" void seir_sampler_destroy(seir_sampler *s) {
     for (void *p : s->allocs) (void)hipFree(p);
     for (void *p : s->snap) if (p) (void)hipFree(p);
     for (void *p : s->rt_allocs) (void)hipFree(p);
+    for (void *p : s->wb_allocs) (void)hipFree(p);
     rollout_free(s->fc); rollout_free(s->ck);
-    acc_free(s->sum_acc); acc_free(s->diag_buf); acc_free(s->rt_acc); acc_free(s->ck_cnt);
+    acc_free(s->sum_acc); acc_free(s->diag_buf); acc_free(s->rt_acc); acc_free(s->ck_cnt); acc_free(s->wb_acc);
     if (s->fc_steps_host) (void)hipHostFree(s->fc_steps_host);
     if (s->fc_keep) (void)hipFree(s->fc_keep);
     if (s->fc_ev_steps) (void)hipEventDestroy(s->fc_ev_steps);
@@ -1622,7 +1630,7 @@ extern "C" int seir_sampler_debug_fail_handoff(seir_sampler *s, int32_t chain) {
 // be folded as soon as it is enqueued and a burst that is run again after a hand-off time-out is not counted twice: the
 // moments, count and flag of the summaries; with them the diagnostics' batch sums and marks (a mark taken in a burst that is
 // thrown away goes with it); the forecast's moments and its draw counter; the reproduction number's moments and count; the
-// check's moments, comparison counts, obs, flags and its draw counter.
+// check's moments, comparison counts, obs, flags and its draw counter; the within/between shares' accumulators and count.
 static size_t summary_cells(const seir_sampler *s) { return (size_t)s->cfg.B * s->ctx->d.M * s->ctx->d.T * seir::SUMMARY_Q; }
 static size_t diag_words(const seir_sampler *s) { return 6 * summary_cells(s) + 3 * (size_t)s->cfg.B; }
 static uint64_t *diag_mark(const seir_sampler *s, int which) {       // count [B] | sum [n] | sumsq [n]
@@ -1642,6 +1650,7 @@ static int moments_shadow(seir_sampler *s, int slot, bool save) {
         rc = rollout_shadow(s->ck, slot, save, st);
         if (!rc) rc = acc_shadow(s->ck_cnt, slot, save, st);
     }
+    if (!rc && s->wb_on) rc = acc_shadow(s->wb_acc, slot, save, st);
     return rc;
 }
 
@@ -2301,6 +2310,8 @@ struct TraceUser { const char *verb, *not_enabled, *name, *done; };
 static const TraceUser SUMMARY_USER = {"summarise", "summaries are not enabled: call seir_sampler_summary_reset first"};
 static const TraceUser RT_USER = {"form the reproduction number from",
                                    "the reproduction number is not enabled: call seir_sampler_rt_reset first"};
+static const TraceUser WB_USER = {"form the within/between pressure shares from",
+                                   "the within/between pressure shares are not enabled: call seir_sampler_wb_reset first"};
 static const TraceUser FORECAST_USER = {"forecast from", "the forecast is not enabled: call seir_sampler_forecast_reset first",
                                          "forecast", "forecast"};
 static const TraceUser CHECK_USER = {"check", "the in-sample check is not enabled: call seir_sampler_check_reset first", "check",
@@ -3082,6 +3093,134 @@ extern "C" int seir_sampler_read_rt(seir_sampler *s, uint64_t *count, double *re
     if (sum) HIP_TRY(hipMemcpyAsync(sum, rb.sum, sizeof(double) * n, hipMemcpyDeviceToHost, st));
     if (sumsq) HIP_TRY(hipMemcpyAsync(sumsq, rb.sumsq, sizeof(double) * n, hipMemcpyDeviceToHost, st));
     if (gt1) HIP_TRY(hipMemcpyAsync(gt1, rb.gt1, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return check_ev_overflow(s);
+}
+
+// ---------------------------------------------------------------------------
+// Within/between pressure shares on the device (include/seir_hip.h; kernels: wb_kernels.h)
+// ---------------------------------------------------------------------------
+// as rt_check
+static int wb_check(seir_sampler *s, int32_t first = 0, int32_t count = 0) {
+    if (need_events(s, WB_USER.verb)) return SEIR_ERR_INVALID;
+    return trace_range_check(s, s->wb_on, WB_USER, first, count);
+}
+static size_t wb_cells(const seir_sampler *s) { return (size_t)s->cfg.B * s->wb.D * s->ctx->d.M; }
+
+extern "C" int seir_sampler_wb_reset(seir_sampler *s, int32_t days) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if (need_events(s, WB_USER.verb)) return SEIR_ERR_INVALID;
+    const Dims &d = s->ctx->d;
+    if (days < 1 || days > d.T) return fail(SEIR_ERR_INVALID, "days=%d outside [1, T = %d]", days, d.T);
+    const int B = s->cfg.B, D = days;
+    hipStream_t st = s->ctx->stream;
+    WbBufs &wb = s->wb;
+    if (!s->wb_on || wb.D != D) {
+        // first reset, or another window: everything is sized by D
+        if ((rc = drain(s))) return rc;
+        for (void *p : s->wb_allocs) (void)hipFree(p);
+        s->wb_allocs.clear();
+        acc_free(s->wb_acc);
+        s->wb_on = false;
+        wb = WbBufs{};
+        wb.D = D; wb.t0 = d.T - D; wb.ncb = (d.M + 63) / 64;
+        // the I plane of a batch is bounded as the reproduction number's S plane: a call is cut into batches of at most wb_slots slots
+        const size_t bound = s->ctx->opt_rt_staging_kib ? (size_t)s->ctx->opt_rt_staging_kib << 10 : RT_STAGING_BYTES;
+        const size_t per_slot = (size_t)B * d.Mp * D * sizeof(int);
+        s->wb_slots = (int)std::max<size_t>(1, std::min<size_t>((size_t)s->cfg.cap, bound / per_slot));
+        const size_t nd = (size_t)s->wb_slots * B;
+        S_ALLOC(wb_allocs, wb.I, nd * D * d.Mp); S_ALLOC(wb_allocs, wb.part, nd * D * wb.ncb * 2);
+        S_ALLOC(wb_allocs, wb.Wn, (size_t)s->cfg.cap * B * D); S_ALLOC(wb_allocs, wb.Bn, (size_t)s->cfg.cap * B * D);
+        const size_t cells = (size_t)B * D * d.M, cw = rt_count_words(s);
+        if (!rc) rc = acc_alloc(s->wb_acc, cells * (5 * sizeof(double) + 2 * sizeof(uint32_t)) + cw * sizeof(uint64_t));
+        if (rc) return rc;
+        wb.sum_w = (double *)s->wb_acc.p;
+        wb.sumsq_w = wb.sum_w + cells;
+        wb.ref_w = wb.sumsq_w + cells;
+        wb.ref_b = wb.ref_w + cells;
+        wb.sum_b = wb.ref_b + cells;
+        wb.count = (uint64_t *)(wb.sum_b + cells);
+        wb.n = (uint32_t *)(wb.count + cw);
+        wb.gt = wb.n + cells;
+        const size_t lds = k_wb_trace_lds_bytes<WB_DT>(d.Mp);
+        if (lds > 64 * 1024)
+            (void)hipFuncSetAttribute((const void *)k_wb_trace<WB_DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        s->wb_on = true;
+    }
+    if ((rc = acc_zero(s->wb_acc, st))) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    // what the snapshots taken before this reset hold of it is dropped: restoring one of them leaves the accumulators alone
+    acc_invalidate(s->wb_acc);
+    return 0;
+}
+
+extern "C" int seir_sampler_wb(seir_sampler *s, int32_t first, int32_t count) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = wb_check(s, first, count))) return rc;
+    if (count == 0) return 0;
+    seir_ctx *ctx = s->ctx;
+    const LaunchCfg l = whole(ctx, s->cfg.B);
+    const Dims &d = l.d;
+    const int B = s->cfg.B, D = s->wb.D;
+    const WbBufs &wb = s->wb;
+    const size_t lds = k_wb_trace_lds_bytes<WB_DT>(d.Mp);
+    for (int j0 = 0; j0 < count; j0 += s->wb_slots) {
+        const int nj = std::min(s->wb_slots, count - j0), ND = nj * B;
+        const dim3 pgrid((d.M + WB_PREP_ROWS - 1) / WB_PREP_ROWS, ND), pblock(64 * WB_PREP_ROWS);
+        if (s->cfg.ev16)
+            hipLaunchKernelGGL(k_wb_prepare<1>, pgrid, pblock, 0, l.st, d, ctx->c, wb, (const void *)s->ch.tr_events, B, first + j0);
+        else
+            hipLaunchKernelGGL(k_wb_prepare<0>, pgrid, pblock, 0, l.st, d, ctx->c, wb, (const void *)s->ch.tr_events, B, first + j0);
+        hipLaunchKernelGGL(k_wb_trace<WB_DT>, dim3(wb.ncb, (D + WB_DT - 1) / WB_DT, B), dim3(256), lds, l.st, d, ctx->c, wb,
+                           (const double *)s->ch.tr_theta, B, first + j0, nj);
+        hipLaunchKernelGGL(k_wb_finish, dim3((unsigned)(((size_t)ND * D + 255) / 256)), dim3(256), 0, l.st, wb, B, first + j0, nj);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+static int copy_wb_draws(seir_sampler *s, hipStream_t st, int32_t first, int32_t count, double *Wn, double *Bn) {
+    const size_t row = (size_t)s->cfg.B * s->wb.D;
+    if (Wn) HIP_TRY(hipMemcpyAsync(Wn, s->wb.Wn + (size_t)first * row, sizeof(double) * count * row, hipMemcpyDeviceToHost, st));
+    if (Bn) HIP_TRY(hipMemcpyAsync(Bn, s->wb.Bn + (size_t)first * row, sizeof(double) * count * row, hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+extern "C" int seir_sampler_read_wb_draws(seir_sampler *s, int32_t first, int32_t count, double *within_pressure,
+                                          double *between_pressure) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = wb_check(s, first, count))) return rc;
+    if ((rc = copy_wb_draws(s, s->ctx->stream, first, count, within_pressure, between_pressure))) return rc;
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    return check_ev_overflow(s);
+}
+
+extern "C" int seir_sampler_read_wb_draws_async(seir_sampler *s, int32_t first, int32_t count, double *within_pressure,
+                                                double *between_pressure) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = wb_check(s, first, count))) return rc;
+    return on_copy_stream(s, [&](hipStream_t st) { return copy_wb_draws(s, st, first, count, within_pressure, between_pressure); });
+}
+
+extern "C" int seir_sampler_read_wb(seir_sampler *s, uint64_t *count, uint32_t *n, double *ref_w, double *sum_w, double *sumsq_w,
+                                    double *ref_b, double *sum_b, uint32_t *gt) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = wb_check(s))) return rc;
+    hipStream_t st = s->ctx->stream;
+    const size_t cells = wb_cells(s);
+    const WbBufs &wb = s->wb;
+    if (count) HIP_TRY(hipMemcpyAsync(count, wb.count, sizeof(uint64_t) * s->cfg.B, hipMemcpyDeviceToHost, st));
+    const struct { double *dst; const double *src; } dbl[] = {{ref_w, wb.ref_w}, {sum_w, wb.sum_w}, {sumsq_w, wb.sumsq_w},
+                                                              {ref_b, wb.ref_b}, {sum_b, wb.sum_b}};
+    for (const auto &p : dbl)
+        if (p.dst) HIP_TRY(hipMemcpyAsync(p.dst, p.src, sizeof(double) * cells, hipMemcpyDeviceToHost, st));
+    if (n) HIP_TRY(hipMemcpyAsync(n, wb.n, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost, st));
+    if (gt) HIP_TRY(hipMemcpyAsync(gt, wb.gt, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return check_ev_overflow(s);
 }

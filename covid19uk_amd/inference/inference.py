@@ -106,7 +106,8 @@ class Posterior:
     `is_accepted` is a bool dataset the way h5py stores one (gemlib's Posterior writes numpy bools through h5py):
     the int8 enum {FALSE = 0, TRUE = 1}."""
 
-    def __init__(self, filename, M, T, mmax, num_samples, burst=100, summaries="off", forecast=None, rt=None, check=None):
+    def __init__(self, filename, M, T, mmax, num_samples, burst=100, summaries="off", forecast=None, rt=None, check=None,
+                 within_between=None):
         """`summaries` ("off" | "on" | "only", Mcmc.summaries / --summaries): with "on" and "only" the per-draw marginals
         samples/seir_by_day [n,T,3], samples/seir_by_location [n,M,3], samples/state_by_day [n,T,3] (int64) are written
         with every burst and `write_summary` adds summaries/* at the end of the run; with "only" samples/seir is not
@@ -121,7 +122,12 @@ class Posterior:
 
         `check` ((K, n) or None, Mcmc.check / --check): samples/check_by_day [n,K,3], check_by_location [n,M,3],
         check_state_by_day [n,K,3] (int64), one row per kept draw of the sampling phase, and `write_check` adds the group
-        check/ at the end of the run."""
+        check/ at the end of the run.
+
+        `within_between` ((D, n) or None, Mcmc.within_between / --within-between): samples/within_pressure and
+        samples/between_pressure [n,D] (float64), the national within- and between-location infection pressure of the last
+        D days, one row per kept draw of the sampling phase, and `write_within_between` adds the group within_between/ at the
+        end of the run."""
         self.filename = filename
         self.use_h5 = not str(filename).endswith(".npz") and hdf5io.available()
         self.shapes = {
@@ -157,6 +163,9 @@ class Posterior:
             for k, shp in (("samples/check_by_day", (K, 3)), ("samples/check_by_location", (M, 3)),
                            ("samples/check_state_by_day", (K, 3))):
                 self.shapes[k], self.dtypes[k], self.rows[k] = shp, np.int64, n_ck
+        if within_between is not None:
+            for k in ("samples/within_pressure", "samples/between_pressure"):
+                self.shapes[k], self.rows[k] = (int(within_between[0]),), int(within_between[1])
         self._scratch = {}
         if self.use_h5:
             self._file = hdf5io.File(filename, "w")
@@ -264,6 +273,17 @@ class Posterior:
         self._write_moments("check", mean, var)
         for k, v in counts.items():
             self.create_dataset(f"check/{k}", np.atleast_1d(np.asarray(v, np.float64)))
+
+    def write_within_between(self, days, first_day, count, defined, within_mean, within_var, between_mean, p_within_gt_between):
+        """The group within_between/ of one chain: days [1], first_day [1] (= T - D, the absolute day of the window's first
+        day), count [1] (draws folded) and defined (draws with finite shares; the weight when files are pooled),
+        within_mean, within_var, between_mean, p_within_gt_between over them (`WbSummary` rows), each [D,M]."""
+        self.create_dataset("within_between/days", np.array([float(days)]))
+        self.create_dataset("within_between/first_day", np.array([float(first_day)]))
+        self.create_dataset("within_between/count", np.array([float(count)]))
+        for k, v in (("defined", defined), ("within_mean", within_mean), ("within_var", within_var),
+                     ("between_mean", between_mean), ("p_within_gt_between", p_within_gt_between)):
+            self.create_dataset(f"within_between/{k}", np.ascontiguousarray(v, dtype=np.float64))
 
     def write_diagnostics(self, datasets: dict):
         """The group diagnostics/ of one chain (`posterior.diagnostics.chain_datasets`), float64."""
@@ -435,6 +455,22 @@ def rt_mode(config, override=None, T=None):
     return D
 
 
+def within_between_mode(config, override=None, T=None):
+    """Mcmc.within_between (absent: off), or the command line's `--within-between D`: the number of days D of the window
+    [T - D, T) over which the within/between pressure shares of every kept draw of the sampling phase are formed on the
+    device; 0 for off.  1 <= D, and D <= T when the length of the series is given.  The one place that validates -- before
+    a sampler exists."""
+    D = config.get("within_between") if override is None else override
+    if D is None or D is False or (isinstance(D, str) and D.lower() == "off"):
+        return 0
+    if isinstance(D, bool) or (not isinstance(D, (int, np.integer)) and not (isinstance(D, str) and D.strip().lstrip("+-").isdigit())):
+        raise ValueError(f"within_between={D!r}: the window is a number of days, 1 .. T")
+    D = int(D)
+    if D < 1 or (T is not None and D > int(T)):
+        raise ValueError(f"within_between={D}: the window is 1 .. T{'' if T is None else f' = {int(T)}'} days")
+    return D
+
+
 # The check's Philox key is the run's seed with this constant folded in: the check and the forecast (keyed by the run's seed
 # itself) share a protocol and a draw-id space, and so must never share a key
 CHECK_SEED_SALT = 0x636865636B5F6B31                        # "check_k1"
@@ -498,6 +534,29 @@ def rt_run_line(days, T, r_t, prob_gt1):
             f"{T - days}, formed on the device; rt/* and samples/R_t written")
 
 
+def within_between_run_line(days, T, within_pressure, between_pressure, p_gt):
+    """The run's one line about the within/between shares: the national within share Wn / (Wn + Bn) on the last day (mean
+    and 0.05 / 0.95 quantiles over the per-draw pressures [n, chains, D]; draws without any pressure left out) and the share
+    of locations whose P(within > between) on that day (`p_gt` [chains, D, M], pooled by the mean over the chains that
+    define it) exceeds 0.5."""
+    wn = np.asarray(within_pressure, np.float64)[..., -1].reshape(-1)
+    bn = np.asarray(between_pressure, np.float64)[..., -1].reshape(-1)
+    tot = wn + bn
+    ok = np.isfinite(tot) & (tot != 0.0)
+    if not ok.any():
+        return f"Within/between: window of {days} day(s) from day {T - days}, no kept draw with infection pressure"
+    share = wn[ok] / tot[ok]
+    lo, hi = np.quantile(share, [0.05, 0.95])
+    p = np.asarray(p_gt, np.float64)[:, -1, :]
+    seen = np.isfinite(p)
+    pm = np.where(seen, p, 0.0).sum(axis=0) / np.maximum(seen.sum(axis=0), 1)
+    locs = float(np.mean(pm[seen.any(axis=0)] > 0.5)) if seen.any() else float("nan")
+    return (f"Within/between: day {T - 1} national within share mean {share.mean():.3f} (0.05 / 0.95 quantiles {lo:.3f} / "
+            f"{hi:.3f}) over {share.size} kept draw(s); P(within > between) > 0.5 in {100.0 * locs:.1f} % of locations; window "
+            f"of {days} day(s) from day {T - days}, formed on the device; within_between/* and samples/within_pressure, "
+            "between_pressure written")
+
+
 def forecast_steps_fn(seed, chain_ids, horizon):
     """The random-walk steps of the forecast baseline (`forecast_walk`): for the j-th forecast draw of global chain c,
     H normals N(0, ALPHA_T_SCALE = 0.005) from np.random.default_rng([seed, c, j]) -- keyed like the device's draw id, so
@@ -547,8 +606,13 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     With Mcmc.check = K (`check_mode`) the last K days are simulated again from every kept draw of the sampling phase and
     set against the observed removals on the device, behind the burst's summary, forecast and R_t; `check_calendar` =
     (W [K], weekday_c [K]) (`posterior.predict.check_calendar`) is then needed, and the check's stream is keyed by
-    `check_seed(seed)`.  The warm-up is not checked; without the key nothing of it is called."""
+    `check_seed(seed)`.  The warm-up is not checked; without the key nothing of it is called.
+
+    With Mcmc.within_between = D (`within_between_mode`) the within/between pressure shares of every kept draw of the
+    sampling phase over the last D days are formed and folded on the device, behind the burst's summary, forecast, R_t and
+    check.  The warm-up is not folded; without the key nothing of it is called."""
     thin = thin_interval(config)
+    wb_days = within_between_mode(config, T=getattr(sampler, "T", None))
     check_days = check_mode(config, T=getattr(sampler, "T", None))
     if check_days and check_calendar is None:
         raise ValueError("check: run_mcmc needs check_calendar = (W, weekday_c) of the window")
@@ -579,10 +643,18 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     rt_offset = 0
     rt_draws = []
     ck_offset = 0
+    wb_offset = 0
+    wb_draws = []
 
     def flush(tr):
-        nonlocal offset, fc_offset, rt_offset, ck_offset
+        nonlocal offset, fc_offset, rt_offset, ck_offset, wb_offset
         n = tr.theta.shape[0]
+        if wb_days and getattr(tr, "wb", None) is not None:
+            w = {k: np.array(v) for k, v in tr.wb.items()}  # the pinned buffer is used again two bursts later
+            wb_draws.append(w)
+            for c, post in enumerate(posteriors):
+                post.write_samples({k: v[:, c] for k, v in w.items()}, first_dim_offset=wb_offset)
+            wb_offset += n
         if check_days and getattr(tr, "check", None) is not None:
             for c, post in enumerate(posteriors):
                 post.write_samples({k: v[:, c] for k, v in tr.check.items()}, first_dim_offset=ck_offset)
@@ -649,6 +721,9 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     if check_days:
         sampler.reset_check(check_days, check_calendar[0], check_calendar[1], check_seed(seed))   # once: the sampling phase
         burst_kw = dict(burst_kw, check=True)
+    if wb_days:
+        sampler.reset_within_between(wb_days)               # once: the sampling phase
+        burst_kw = dict(burst_kw, within_between=True)
     if summaries == "only":
         print("summaries only: the event tensors stay on the device and samples/seir is not created -- what reads it "
               "(thin_posterior, predict, reproduction_number) cannot run on this output", file=log, flush=True)
@@ -722,6 +797,15 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
         for c, post in enumerate(posteriors):
             post.write_check(check_days, sampler.T - check_days, cs.count[c], mean[c], var[c], check_chain_datasets(cs, c))
         print(check_run_line(check_days, sampler.T, cs), file=log, flush=True)
+    if wb_days:
+        ws = sampler.within_between_summary()
+        wm, wv, bm, pg = ws.within_mean, ws.within_var, ws.between_mean, ws.p_within_gt_between
+        for c, post in enumerate(posteriors):
+            post.write_within_between(wb_days, sampler.T - wb_days, ws.count[c], ws.defined[c], wm[c], wv[c], bm[c], pg[c])
+        empty = np.empty((0, sampler.B, wb_days))
+        wn = np.concatenate([w["within_pressure"] for w in wb_draws]) if wb_draws else empty
+        bn = np.concatenate([w["between_pressure"] for w in wb_draws]) if wb_draws else empty
+        print(within_between_run_line(wb_days, sampler.T, wn, bn, pg), file=log, flush=True)
     return offset
 
 
@@ -787,7 +871,7 @@ def launch_forms(lay, device_arg, hmc="auto", moves="auto", env=os.environ):
 
 def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool_step_size=False, init_jitter=0.0,
          events_dtype="auto", hmc="auto", moves="auto", thin=None, summaries=None, diagnostics=None, diagnostics_batch=None,
-         forecast=None, forecast_walk=None, rt=None, check=None, forecast_quantiles=None):
+         forecast=None, forecast_walk=None, rt=None, check=None, forecast_quantiles=None, within_between=None):
     """Constructs and runs the MCMC (covid19uk/inference/inference.py:473-608).
 
     Multi-GPU: launched as one process per GPU, every rank runs `num_chains` chains with
@@ -798,7 +882,14 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     config["summaries"] (`summaries_mode`), `diagnostics` / `diagnostics_batch` config["diagnostics"] /
     config["diagnostics_batch"] (`diagnostics_mode`), `forecast` / `forecast_walk` config["forecast"] /
     config["forecast_walk"] (`forecast_mode`), `forecast_quantiles` config["forecast_quantiles"]
-    (`forecast_quantiles_mode`), `rt` config["rt"] (`rt_mode`), `check` config["check"] (`check_mode`)."""
+    (`forecast_quantiles_mode`), `rt` config["rt"] (`rt_mode`), `check` config["check"] (`check_mode`), `within_between`
+    config["within_between"] (`within_between_mode`)."""
+    wb_days = 0
+    if within_between is not None or "within_between" in config:
+        wb_days = within_between_mode(config, within_between)   # refused here: before any GPU call
+        config = {k: v for k, v in config.items() if k != "within_between"}
+        if wb_days:
+            config = dict(config, within_between=wb_days)
     check_days = 0
     if check is not None or "check" in config:
         check_days = check_mode(config, check)              # refused here: before any GPU call
@@ -838,6 +929,8 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
         rt_mode(config, T=T)                                # the window against the series: still before any GPU call
     if check_days:
         check_mode(config, T=T)                             # likewise
+    if wb_days:
+        within_between_mode(config, T=T)                    # likewise
     cfg = event_kernel_config(config)
     num_samples = warmup_size() + int(config["num_burst_samples"]) * int(config["num_bursts"])
     cap = max(800, 2 * int(config["num_burst_samples"]))      # two halves: a burst runs while the previous one is written
@@ -872,7 +965,9 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
                             **({} if config["summaries"] == "off" else dict(summaries=config["summaries"])),
                             **(dict(forecast=(horizon, int(config["num_burst_samples"]) * int(config["num_bursts"]))) if horizon else {}),
                             **(dict(rt=(rt_days, int(config["num_burst_samples"]) * int(config["num_bursts"]))) if rt_days else {}),
-                            **(dict(check=(check_days, int(config["num_burst_samples"]) * int(config["num_bursts"]))) if check_days else {}))
+                            **(dict(check=(check_days, int(config["num_burst_samples"]) * int(config["num_bursts"]))) if check_days else {}),
+                            **(dict(within_between=(wb_days, int(config["num_burst_samples"]) * int(config["num_bursts"])))
+                               if wb_days else {}))
                   for name in names]
     fc_kw = {}
     if horizon:
@@ -974,6 +1069,13 @@ def main(argv=None):
                              "at the data per cell, location, day and in total with their mid-p values, and per-draw "
                              "samples/check_by_day, check_by_location, check_state_by_day; works with --summaries only, "
                              "--thin, --forecast and --rt")
+    parser.add_argument("--within-between", type=int, default=None, metavar="D", dest="within_between",
+                        help="form the within- and between-location shares of the infection pressure of every kept draw of "
+                             "the sampling phase over the last D days (1..T) on the device (overrides Mcmc.within_between; "
+                             "default off): a group within_between/ with the mean and variance of the within share, the "
+                             "mean of the between share and P(within > between) per day and location, and the national "
+                             "pressures per draw samples/within_pressure, between_pressure; works with --summaries only, "
+                             "--thin, --forecast, --rt and --check")
     args = parser.parse_args(argv)
     if args.thin is not None and args.thin < 1:
         parser.error(f"--thin {args.thin}: the thinning interval is >= 1")
@@ -984,6 +1086,7 @@ def main(argv=None):
          hmc=args.hmc, moves=args.moves, thin=args.thin, summaries=args.summaries, diagnostics=args.diagnostics,
          diagnostics_batch=args.diagnostics_batch, forecast=args.forecast, forecast_walk=args.forecast_walk, rt=args.rt,
          **({} if args.check is None else dict(check=args.check)),
+         **({} if args.within_between is None else dict(within_between=args.within_between)),
          **({} if args.forecast_quantiles is None else dict(forecast_quantiles=args.forecast_quantiles)))
 
 

@@ -1,7 +1,8 @@
 """The compiler's account of the library's kernels: parser of `hipcc -Rpass-analysis=kernel-resource-usage` remarks
 (registers, scratch, spills, LDS, occupancy per kernel).  `__graft_entry__.build()` keeps the result next to the library as
 kernel_resources.json (and, for the kernels added since that file's set was pinned, added_kernel_resources.json; for the
-self-test kernels of the device math, selftest_kernel_resources.json);
+self-test kernels of the device math, selftest_kernel_resources.json; for the kernels of the within/between shares,
+wb_kernel_resources.json);
 tests/test_resources.py holds the hot-path instances to it; tools/dev/resources.py prints it."""
 import re
 

@@ -41,12 +41,14 @@ class Trace:
     forecast: dict = None    # FORECAST_KEYS -> int64 [n,B,H,3] / [n,B,M,3] / [n,B,H,3]; None unless the draws were forecast
     rt: np.ndarray = None    # [n,B,D] national R_t of every kept draw over the window; None unless asked for
     check: dict = None       # CHECK_KEYS -> int64 [n,B,K,3] / [n,B,M,3] / [n,B,K,3]; None unless the draws were checked
+    wb: dict = None          # WB_KEYS -> float64 [n,B,D] national within / between pressure; None unless asked for
 
 
 MARGINAL_KEYS = ("events_by_day", "events_by_location", "state_by_day")
 FORECAST_KEYS = ("forecast_by_day", "forecast_by_location", "forecast_state_by_day")
 FORECAST_QUANTILE_PLANES = ("cases", "cum_cases", "prevalence")   # the planes of the draw store (keep_forecast_draws)
 CHECK_KEYS = ("check_by_day", "check_by_location", "check_state_by_day")
+WB_KEYS = ("within_pressure", "between_pressure")
 SUMMARY_QUANTITIES = ("k_se", "k_ei", "k_ir", "S", "E", "I")
 
 
@@ -96,6 +98,49 @@ class RtSummary:
     def prob_gt1(self) -> np.ndarray:
         """gt1 / n, the posterior probability of R_it > 1, [B,D,M]; NaN for a chain with no draw."""
         return rt_prob_gt1(self.count, self.gt1)
+
+
+@dataclasses.dataclass
+class WbSummary:
+    """The within/between pressure shares folded since the last `reset_within_between` (include/seir_hip.h, "Within/between
+    pressure shares on the device"), per chain, day of the window [T - D, T) and location: the device's accumulators as they
+    are, and what the host forms from them.  A draw whose shares are not finite for a cell (no infective anywhere) is counted
+    in `count` and in no cell."""
+    count: np.ndarray        # [B] uint64 draws folded, defined or not
+    defined: np.ndarray      # [B,D,M] uint32: draws with finite shares in the cell
+    ref_w: np.ndarray        # [B,D,M] float64: the within share of the cell's first defined draw
+    sum_w: np.ndarray        # [B,D,M] float64: sum_j (within_j - ref_w)
+    sumsq_w: np.ndarray      # [B,D,M] float64: sum_j (within_j - ref_w)^2
+    ref_b: np.ndarray        # [B,D,M] float64: the between share of the cell's first defined draw
+    sum_b: np.ndarray        # [B,D,M] float64: sum_j (between_j - ref_b)
+    gt: np.ndarray           # [B,D,M] uint32: draws with within_j > between_j
+
+    @property
+    def within_mean(self) -> np.ndarray:
+        """ref_w + sum_w / defined, [B,D,M]; NaN (no warning) where defined = 0."""
+        return wb_mean(self.defined, self.ref_w, self.sum_w)
+
+    @property
+    def within_var(self) -> np.ndarray:
+        """Unbiased variance (sumsq_w - sum_w^2 / defined) / (defined - 1), [B,D,M]; NaN (no warning) where defined < 2."""
+        return summary_var(self.defined, self.sum_w, self.sumsq_w)
+
+    @property
+    def between_mean(self) -> np.ndarray:
+        """ref_b + sum_b / defined, [B,D,M]; NaN (no warning) where defined = 0."""
+        return wb_mean(self.defined, self.ref_b, self.sum_b)
+
+    @property
+    def p_within_gt_between(self) -> np.ndarray:
+        """gt / defined, [B,D,M]; NaN (no warning) where defined = 0."""
+        return wb_mean(self.defined, 0.0, self.gt)
+
+
+def wb_mean(defined, ref, sum_):
+    """ref + sum / n per cell; NaN, without a warning, where n = 0."""
+    n = np.asarray(defined, np.float64)
+    ok = n > 0
+    return np.where(ok, np.asarray(ref, np.float64) + np.asarray(sum_, np.float64) / np.where(ok, n, 1.0), np.nan)
 
 
 @dataclasses.dataclass
@@ -189,7 +234,7 @@ class PinnedTrace:
     `ChainSampler.read_trace_async`.  Views are valid until close()."""
 
     def __init__(self, sampler: "ChainSampler", count: int, events: bool = True, marginals: bool = False,
-                 forecast: int = 0, rt: int = 0, check: int = 0):
+                 forecast: int = 0, rt: int = 0, check: int = 0, wb: int = 0):
         self._lib = sampler._lib
         self.count = int(count)
         B, P, M, T = sampler.B, sampler.P, sampler.M, sampler.T
@@ -216,6 +261,7 @@ class PinnedTrace:
             self.check = dict(check_by_day=self._alloc((count, B, K, 3), np.int64),
                               check_by_location=self._alloc((count, B, M, 3), np.int64),
                               check_state_by_day=self._alloc((count, B, K, 3), np.int64))
+        self.wb = {k: self._alloc((count, B, int(wb)), np.float64) for k in WB_KEYS} if wb else None
 
     def _alloc(self, shape, dtype):
         nbytes = int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize
@@ -226,7 +272,7 @@ class PinnedTrace:
         return np.frombuffer(buf, dtype=dtype, count=int(np.prod(shape, dtype=np.int64))).reshape(shape)
 
     def close(self):
-        self.theta = self.events = self.hmc = self.moves = self.marginals = self.forecast = self.rt = self.check = None
+        self.theta = self.events = self.hmc = self.moves = self.marginals = self.forecast = self.rt = self.check = self.wb = None
         for p in self._ptrs:
             self._lib.seir_host_free(p)
         self._ptrs = []
@@ -247,6 +293,7 @@ class ChainSampler:
     _fc_j = 0                     # draws per chain forecast since the last reset_forecast (the library's counter, mirrored)
     _rt_D = 0                     # window of the reproduction number in force (0: reset_rt was never called)
     _check_K = 0                  # window of the in-sample check in force (0: reset_check was never called)
+    _wb_D = 0                     # window of the within/between shares in force (0: reset_within_between was never called)
     first_chain_id = 0
 
     def __init__(self, model: SeirModel, config: dict, num_chains: int, seed: int = 0,
@@ -514,6 +561,8 @@ class ChainSampler:
             tr.rt = buf.rt[:n]
         if getattr(buf, "check", None) is not None:
             tr.check = {k: v[:n] for k, v in buf.check.items()}
+        if getattr(buf, "wb", None) is not None:
+            tr.wb = {k: v[:n] for k, v in buf.wb.items()}
         return tr
 
     # -- summaries of the recorded events on the device (include/seir_hip.h) --------------------------
@@ -772,6 +821,53 @@ class ChainSampler:
             raise ValueError("check asked for before reset_check")
         self.check(first, count)
 
+    # -- within/between pressure shares (include/seir_hip.h, "Within/between pressure shares on the device") ----------
+    def reset_within_between(self, days: int):
+        """Enable the within/between shares (first call), zero their accumulators and count and set the window to the last
+        `days` days of the series (1 <= days <= T)."""
+        D = int(days)
+        if not 1 <= D <= self.T:
+            raise ValueError(f"within_between days {D}: 1 <= D <= T = {self.T}")
+        _lib.check(self._lib.seir_sampler_wb_reset(self._s, D))
+        self._wb_D = D
+
+    def within_between(self, first: int, count: int):
+        """Enqueue the shares of trace slots [first, first+count) behind the sweeps that fill them: folded into the
+        accumulators, and the national pressures of every draw written."""
+        _lib.check(self._lib.seir_sampler_wb(self._s, int(first), int(count)))
+
+    def read_wb_draws(self, count: int, first: int = 0) -> dict:
+        """Blocking read of the national pressures of trace slots [first, first+count): WB_KEYS -> [count,B,D]."""
+        out = {k: np.empty((int(count), self.B, self._wb_D)) for k in WB_KEYS}
+        _lib.check(self._lib.seir_sampler_read_wb_draws(self._s, int(first), int(count), *(_dptr(out[k]) for k in WB_KEYS)))
+        return out
+
+    def read_wb_draws_async(self, count: int, first: int, into: PinnedTrace):
+        """As `read_marginals_async`, for the national pressures; completed by `trace_wait()`."""
+        if int(count) > into.count or getattr(into, "wb", None) is None:
+            raise ValueError("pinned buffer too small or without within/between arrays")
+        _lib.check(self._lib.seir_sampler_read_wb_draws_async(self._s, int(first), int(count),
+                                                              *(_dptr(into.wb[k]) for k in WB_KEYS)))
+
+    def within_between_summary(self) -> WbSummary:
+        """The accumulators folded since the last `reset_within_between` (blocking): `WbSummary`, whose `.within_mean`,
+        `.within_var`, `.between_mean` and `.p_within_gt_between` are formed here.  Raises `SeirError` (SEIR_ERR_STATE)
+        before a reset."""
+        shape = (self.B, self._wb_D, self.M)
+        u32 = ctypes.POINTER(ctypes.c_uint32)
+        cnt = np.zeros(self.B, np.uint64)
+        n, gt = np.empty(shape, np.uint32), np.empty(shape, np.uint32)
+        ref_w, sum_w, sumsq_w, ref_b, sum_b = (np.empty(shape) for _ in range(5))
+        _lib.check(self._lib.seir_sampler_read_wb(self._s, cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                                  n.ctypes.data_as(u32), _dptr(ref_w), _dptr(sum_w), _dptr(sumsq_w),
+                                                  _dptr(ref_b), _dptr(sum_b), gt.ctypes.data_as(u32)))
+        return WbSummary(count=cnt, defined=n, ref_w=ref_w, sum_w=sum_w, sumsq_w=sumsq_w, ref_b=ref_b, sum_b=sum_b, gt=gt)
+
+    def _wb_burst(self, first, count):
+        if not self._wb_D:
+            raise ValueError("within_between asked for before reset_within_between")
+        self.within_between(first, count)
+
     def _summarize_mode(self, summarize):
         """`summarize` of sample / sample_bursts: False, True (marginals + moments) or "marginals" (accumulate = 0)."""
         if summarize not in (False, True, "marginals"):
@@ -781,7 +877,7 @@ class ChainSampler:
         return bool(summarize), summarize is True
 
     def sample_bursts(self, num_bursts: int, burst: int, consume, events: bool = True, summarize=False, marks=None,
-                      forecast=False, rt=False, check=False):
+                      forecast=False, rt=False, check=False, within_between=False):
         """`num_bursts` x `burst` kept draws (`burst * thin` sweeps each) with the burst buffer used as two halves:
         while burst k+1 runs on the device, burst k crosses PCIe into page-locked memory on a copy stream and `consume(trace, k)`
         (e.g. the HDF5 writer) runs on a worker thread -- the sampler only waits when the consumer is
@@ -807,7 +903,11 @@ class ChainSampler:
 
         `check` (needs `reset_check`): the last K days of every burst's draws are simulated again and set against the data
         on the device, behind the summary, the forecast and R_t; the check's marginals cross with the trace
-        (`trace.check`)."""
+        (`trace.check`).
+
+        `within_between` (needs `reset_within_between`): the within/between pressure shares of every burst's draws are
+        formed and folded on the device, behind the summary, the forecast, R_t and the check; the national pressures cross
+        with the trace (`trace.wb`)."""
         from concurrent.futures import ThreadPoolExecutor
         do_sum, accumulate = self._summarize_mode(summarize)
         burst, num_bursts = int(burst), int(num_bursts)
@@ -817,8 +917,9 @@ class ChainSampler:
         do_fc = bool(forecast)
         do_rt = bool(rt)
         do_ck = bool(check)
+        do_wb = bool(within_between)
         key = (burst, bool(events), do_sum, self._forecast_H if do_fc else 0) + ((self._rt_D,) if do_rt else ()) + \
-            ((("check", self._check_K),) if do_ck else ())
+            ((("check", self._check_K),) if do_ck else ()) + ((("wb", self._wb_D),) if do_wb else ())
         if getattr(self, "_pinned_key", None) != key:
             for bf in getattr(self, "_pinned", []):
                 bf.close()
@@ -829,6 +930,8 @@ class ChainSampler:
                 mk["rt"] = self._rt_D
             if do_ck:
                 mk["check"] = self._check_K
+            if do_wb:
+                mk["wb"] = self._wb_D
             self._pinned = [PinnedTrace(self, burst, events, **mk), PinnedTrace(self, burst, events, **mk)]
             self._pinned_key = key
         bufs = self._pinned
@@ -861,6 +964,8 @@ class ChainSampler:
                                 self._rt_burst(h * burst, burst)
                             if do_ck:
                                 self._check_burst(h * burst, burst)
+                            if do_wb:
+                                self._wb_burst(h * burst, burst)
                         if prev >= 0:
                             self.trace_wait()                    # burst prev has landed (it crossed while burst i ran)
                             futs[prev & 1] = pool.submit(consume, self.trace_view(bufs[prev & 1], burst), prev)
@@ -876,6 +981,8 @@ class ChainSampler:
                                 self.read_rt_draws_async(burst, h * burst, bufs[h])
                             if do_ck:
                                 self.read_check_marginals_async(burst, h * burst, bufs[h])
+                            if do_wb:
+                                self.read_wb_draws_async(burst, h * burst, bufs[h])
                             prev = i
                             i += 1
                     except _lib.HandoffTimeout as e:
@@ -896,10 +1003,11 @@ class ChainSampler:
             except _lib.HandoffTimeout:
                 pass
 
-    def sample(self, num_sweeps: int, events: bool = True, summarize=False, forecast=False, rt=False, check=False) -> Trace:
+    def sample(self, num_sweeps: int, events: bool = True, summarize=False, forecast=False, rt=False, check=False,
+               within_between=False) -> Trace:
         """reset_trace + run + read: the analogue of one `sample_chain` call with `num_sweeps` results, each the last of
         `thin` sweeps.  `summarize` as in `sample_bursts`: the burst is summarised on the device and `trace.marginals`
-        filled; `forecast` likewise (`trace.forecast`), `rt` (`trace.rt`) and `check` (`trace.check`)."""
+        filled; `forecast` likewise (`trace.forecast`), `rt` (`trace.rt`), `check` (`trace.check`) and `within_between` (`trace.wb`)."""
         do_sum, accumulate = self._summarize_mode(summarize)
         if num_sweeps > self.cap:
             raise ValueError(f"num_sweeps={num_sweeps} exceeds trace_capacity={self.cap}")
@@ -917,6 +1025,8 @@ class ChainSampler:
                     self._rt_burst(0, num_sweeps)
                 if check:
                     self._check_burst(0, num_sweeps)
+                if within_between:
+                    self._wb_burst(0, num_sweeps)
                 tr = self.read_trace(num_sweeps, events=events)
                 if do_sum:
                     tr.marginals = self.read_marginals(num_sweeps)
@@ -926,6 +1036,8 @@ class ChainSampler:
                     tr.rt = self.read_rt_draws(num_sweeps)
                 if check:
                     tr.check = self.read_check_marginals(num_sweeps)
+                if within_between:
+                    tr.wb = self.read_wb_draws(num_sweeps)
             except _lib.HandoffTimeout as e:
                 if not self.auto_recover:
                     raise

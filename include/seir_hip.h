@@ -697,6 +697,54 @@ int seir_sampler_read_rt_draws_async(seir_sampler *s, int32_t first, int32_t cou
 int seir_sampler_read_rt(seir_sampler *s, uint64_t *count, double *ref, double *sum, double *sumsq, uint32_t *gt1);
 
 /* ------------------------------------------------------------------------
+ * Within/between pressure shares on the device: moments per cell and the national pressures per draw.
+ *
+ * Stands in for covid19uk/posterior/within_between.py run on every kept draw, without samples/seir: for each draw of
+ * trace slots [first_slot, first_slot + count), each day t of the window [T - days, T) and each location m the device
+ * forms the within- and between-location infection pressure and folds their shares; neither the event tensor nor an
+ * [n][days][M] tensor crosses PCIe.
+ *
+ * Semantics: the header comment of csrc/wb_kernels.h is the one definition.  In short: I_t is scanned as integers from the
+ * slot's recorded events, psi is the slot's theta[0], W_t the context's W[t]; within = wi / tot and
+ * between = be / tot are bit-identical to what seir_within_between returns for (psi, I_t, W_t), day T - 1 being the
+ * reference's product.  A draw is defined for a cell iff both shares are finite; an undefined draw is counted in count[b]
+ * and folded into nothing.
+ *   Accumulators per chain, [B][days][M]:
+ *     n       (uint32)  defined draws of the cell
+ *     ref_w, ref_b (double)  the shares of the cell's first defined draw since the reset
+ *     sum_w   (double)  sum of (within - ref_w);  sumsq_w  sum of (within - ref_w)^2;  sum_b  sum of (between - ref_b)
+ *     gt      (uint32)  draws with within > between
+ *     count [B] (uint64) draws folded, defined or not
+ *     The fold is sequential in draw order per chain and cell, every operation rounded on its own (no FMA): a loop on the
+ *     host restates every bit, and nothing depends on how a burst is cut into calls, buffer halves or batches.
+ *   National pressures per kept draw, indexed by trace slot: within_pressure, between_pressure [count][B][days] =
+ *     sum_m wi, sum_m be over all locations, defined or not.  No floating-point atomics: blocks of 64 columns are summed in
+ *     a fixed order each and then in ascending block order.
+ * Switched on by the first seir_sampler_wb_reset; a sampler that never calls it allocates and launches nothing more than
+ * before.  While it is on, seir_sampler_snapshot / _restore carry the accumulators and count, so that a burst run again
+ * after a hand-off time-out is folded once.  A snapshot taken before the last reset holds none of it; restoring it leaves
+ * them as they are.  The staging plane of a call is bounded as seir_sampler_rt's (SEIR_OPT_RT_STAGING_KIB).
+ * ------------------------------------------------------------------------ */
+/* First call (and a call with another `days`) allocates; every call zeroes the accumulators and count in stream order.
+ * SEIR_ERR_INVALID for days outside [1, T] or a sampler created with record_events == 0. */
+int seir_sampler_wb_reset(seir_sampler *s, int32_t days);
+/* Form and fold the shares of trace slots [first_slot, first_slot + count) of every chain and write their national
+ * pressures: asynchronous on the context stream, behind the sweeps that fill those slots.  SEIR_ERR_INVALID for slots
+ * outside the burst buffer or with record_events == 0, SEIR_ERR_STATE before a reset. */
+int seir_sampler_wb(seir_sampler *s, int32_t first_slot, int32_t count);
+/* Blocking read of the accumulators: count [B]; n, ref_w, sum_w, sumsq_w, ref_b, sum_b, gt each [B][days][M].  Any pointer
+ * may be NULL.  SEIR_ERR_STATE before a reset. */
+int seir_sampler_read_wb(seir_sampler *s, uint64_t *count, uint32_t *n, double *ref_w, double *sum_w, double *sumsq_w,
+                         double *ref_b, double *sum_b, uint32_t *gt);
+/* Blocking read of the national pressures [count][B][days] of slots [first, first + count) (written by the last
+ * seir_sampler_wb that covered them).  Host pointers; either may be NULL. */
+int seir_sampler_read_wb_draws(seir_sampler *s, int32_t first, int32_t count, double *within_pressure, double *between_pressure);
+/* The same on the copy stream of seir_sampler_read_trace_async, behind everything queued on the context stream so far;
+ * completed by seir_sampler_trace_wait.  The host buffers should be page-locked (seir_host_alloc). */
+int seir_sampler_read_wb_draws_async(seir_sampler *s, int32_t first, int32_t count, double *within_pressure,
+                                     double *between_pressure);
+
+/* ------------------------------------------------------------------------
  * In-sample predictive check on the device: the last K days against the data.
  *
  * Stands in for covid19uk/posterior/predict.py run in sample on every kept draw (`predict -i -K -n K`, predict.py:96-120)
