@@ -222,6 +222,11 @@ _SIGNATURES = {
     "seir_sampler_read_rt_draws_async": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, c_double_p]),
     "seir_sampler_read_rt": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), c_double_p, c_double_p,
                                             c_double_p, ctypes.POINTER(ctypes.c_uint32)]),
+    # R_t intervals: the R_it draw store and exact order statistics of its cells; the fp64 selection alone on host arrays
+    "seir_sampler_rt_keep": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
+    "seir_sampler_rt_order_stats": (ctypes.c_int, [ctypes.c_void_p, c_int64_p, ctypes.c_int32, ctypes.c_int32, c_double_p]),
+    "seir_order_stats_f64": (ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
+                                            ctypes.c_int64, ctypes.c_int64, c_int64_p, ctypes.c_int32, c_double_p]),
     # within/between pressure shares of the kept draws from the burst buffer: moments per cell, national pressures per draw
     "seir_sampler_wb_reset": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "seir_sampler_wb": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]),

@@ -26,6 +26,8 @@
 #include "rt_trace_kernels.h"
 #include "wb_kernels.h"
 #include "order_stats_kernels.h"
+#include "order_stats64_kernels.h"
+#include "rt_keep_kernels.h"
 
 using namespace seir;
 
@@ -1279,6 +1281,11 @@ struct seir_sampler {
     int rt_slots = 0;                 // trace slots the batch planes (ea, S, part) are allocated for
     std::vector<void *> rt_allocs;    // device buffers sized by the window (allocated again when it changes)
     Shadowed rt_acc;                  // sum [cells] | sumsq [cells] | ref [cells] | count [B, padded] | gt1 [cells]
+    double *rt_keep = nullptr;        // the draw store keepR[B][D][M][rt_keep_stride] (seir_sampler_rt_keep), or null: off
+    long long rt_keep_cap = 0;        // draws per chain it holds; position j of a cell is the chain's j-th draw since the reset
+    long long rt_keep_stride = 0;     // cap rounded up to RT_KEEP_RUN: every run of a cell is aligned
+    long long rt_j = 0;               // the host's copy of RtBufs::count (the same for every chain: calls take all of them)
+    long long rt_snap_j[2] = {0, 0};  // rt_j as it was when rt_acc's shadows were taken
     // --- within/between pressure shares of the kept draws (seir_sampler_wb_reset ...; wb_kernels.h) ---
     bool wb_on = false;
     WbBufs wb{};
@@ -1342,6 +1349,7 @@ extern "C" void seir_sampler_destroy(seir_sampler *s) {
     acc_free(s->sum_acc); acc_free(s->diag_buf); acc_free(s->rt_acc); acc_free(s->ck_cnt); acc_free(s->wb_acc);
     if (s->fc_steps_host) (void)hipHostFree(s->fc_steps_host);
     if (s->fc_keep) (void)hipFree(s->fc_keep);
+    if (s->rt_keep) (void)hipFree(s->rt_keep);
     if (s->fc_ev_steps) (void)hipEventDestroy(s->fc_ev_steps);
     Work &w = s->ctx->w;
     for (int x = 0; x < 3; ++x) { w.K[x] = nullptr; w.St[x] = nullptr; }
@@ -1645,7 +1653,13 @@ static int moments_shadow(seir_sampler *s, int slot, bool save) {
         if (!rc) rc = acc_shadow(s->sum_acc, slot, save, st);
     }
     if (!rc && s->fc.on) rc = rollout_shadow(s->fc, slot, save, st);
-    if (!rc && s->rt_on) rc = acc_shadow(s->rt_acc, slot, save, st);
+    if (!rc && s->rt_on) {
+        // count comes back with the accumulators, and the host's copy of it with them: a burst run again overwrites its own
+        // positions of the R_it draw store, which therefore has no shadow
+        if (save) s->rt_snap_j[slot] = s->rt_j;
+        else if (s->rt_acc.valid[slot]) s->rt_j = s->rt_snap_j[slot];
+        rc = acc_shadow(s->rt_acc, slot, save, st);
+    }
     if (!rc && s->ck.on) {
         rc = rollout_shadow(s->ck, slot, save, st);
         if (!rc) rc = acc_shadow(s->ck_cnt, slot, save, st);
@@ -2992,6 +3006,7 @@ extern "C" int seir_sampler_rt_reset(seir_sampler *s, int32_t days, const double
         for (void *p : s->rt_allocs) (void)hipFree(p);
         s->rt_allocs.clear();
         acc_free(s->rt_acc);
+        if (s->rt_keep) { (void)hipFree(s->rt_keep); s->rt_keep = nullptr; s->rt_keep_cap = s->rt_keep_stride = 0; }   // sized by D
         s->rt_on = false;
         rb = RtBufs{};
         rb.D = D; rb.t0 = d.T - D; rb.ncb = (d.M + 63) / 64;
@@ -3021,7 +3036,9 @@ extern "C" int seir_sampler_rt_reset(seir_sampler *s, int32_t days, const double
     // the caller's array is not retained: a blocking copy behind what is queued (a reset is not on the hot path)
     HIP_TRY(hipMemcpyAsync(const_cast<double *>(rb.weight), weight, sizeof(double) * d.M, hipMemcpyHostToDevice, st));
     if ((rc = acc_zero(s->rt_acc, st))) return rc;
+    if (s->rt_keep) HIP_TRY(hipMemsetAsync(s->rt_keep, 0, sizeof(double) * rt_cells(s) * (size_t)s->rt_keep_stride, st));
     HIP_TRY(hipStreamSynchronize(st));
+    s->rt_j = 0;                                     // empties the draw store too: it holds draws [0, count)
     // what the snapshots taken before this reset hold of it is dropped: restoring one of them leaves the accumulators alone
     acc_invalidate(s->rt_acc);
     return 0;
@@ -3032,6 +3049,9 @@ extern "C" int seir_sampler_rt(seir_sampler *s, int32_t first, int32_t count) {
     if (rc) return rc;
     if ((rc = rt_check(s, first, count))) return rc;
     if (count == 0) return 0;
+    if (s->rt_keep && s->rt_j + count > s->rt_keep_cap)
+        return fail(SEIR_ERR_INVALID, "%lld draws per chain folded since the reset and %d more: the draw store holds %lld "
+                    "(seir_sampler_rt_keep)", s->rt_j, count, s->rt_keep_cap);
     seir_ctx *ctx = s->ctx;
     const LaunchCfg l = whole(ctx, s->cfg.B);
     const Dims &d = l.d;
@@ -3049,11 +3069,144 @@ extern "C" int seir_sampler_rt(seir_sampler *s, int32_t first, int32_t count) {
             hipLaunchKernelGGL(k_rt_prepare<1>, pgrid, pblock, 0, l.st, d, ctx->c, rb, (const void *)s->ch.tr_events, B, first + j0);
         else
             hipLaunchKernelGGL(k_rt_prepare<0>, pgrid, pblock, 0, l.st, d, ctx->c, rb, (const void *)s->ch.tr_events, B, first + j0);
-        hipLaunchKernelGGL(k_rt_trace<RT_DT>, dim3(rb.ncb, (D + RT_DT - 1) / RT_DT, B), dim3(256), lds, l.st, d, ctx->c, rb,
-                           (const double *)s->ch.tr_theta, B, first + j0, nj);
+        if (s->rt_keep)                               // in place of k_rt_trace: R_it is formed once
+            hipLaunchKernelGGL(k_rt_trace_keep<RT_DT>, dim3(rb.ncb, (D + RT_DT - 1) / RT_DT, B), dim3(256), lds, l.st, d, ctx->c, rb,
+                               (const double *)s->ch.tr_theta, B, first + j0, nj, s->rt_keep, s->rt_keep_stride);
+        else
+            hipLaunchKernelGGL(k_rt_trace<RT_DT>, dim3(rb.ncb, (D + RT_DT - 1) / RT_DT, B), dim3(256), lds, l.st, d, ctx->c, rb,
+                               (const double *)s->ch.tr_theta, B, first + j0, nj);
         hipLaunchKernelGGL(k_rt_finish, dim3((unsigned)(((size_t)ND * D + 255) / 256)), dim3(256), 0, l.st, rb, B, first + j0, nj);
     }
     HIP_TRY(hipGetLastError());
+    s->rt_j += count;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// R_t intervals on the device (include/seir_hip.h; kernels: rt_keep_kernels.h, order_stats64_kernels.h)
+// ---------------------------------------------------------------------------
+static void rt_keep_free(seir_sampler *s) {
+    (void)hipFree(s->rt_keep);
+    s->rt_keep = nullptr; s->rt_keep_cap = s->rt_keep_stride = 0;
+}
+
+extern "C" int seir_sampler_rt_keep(seir_sampler *s, int64_t cap) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = rt_check(s))) return rc;
+    if (cap < 0 || cap > (1ll << 20))
+        return fail(SEIR_ERR_INVALID, "cap=%lld outside [0, 2^20]: the draws per chain between two resets", (long long)cap);
+    hipStream_t st = s->ctx->stream;
+    if (cap == 0) {
+        if (s->rt_keep) {
+            HIP_TRY(hipStreamSynchronize(st));
+            rt_keep_free(s);
+        }
+        return 0;
+    }
+    if (s->rt_j != 0)
+        return fail(SEIR_ERR_STATE, "%lld draws per chain have been folded since the reset: the draw store is sized between "
+                    "seir_sampler_rt_reset and the first seir_sampler_rt", s->rt_j);
+    if (s->rt_keep && s->rt_keep_cap == cap) return 0;       // the reset has emptied it
+    if (s->rt_keep) {
+        HIP_TRY(hipStreamSynchronize(st));
+        rt_keep_free(s);
+    }
+    const long long stride = (cap + RT_KEEP_RUN - 1) / RT_KEEP_RUN * RT_KEEP_RUN;
+    const unsigned long long bytes = (unsigned long long)rt_cells(s) * (unsigned long long)stride * 8ull;
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    // half of what is free: the policy of a device that is shared, not a measurement
+    if (bytes > (unsigned long long)free_b / 2)
+        return fail(SEIR_ERR_INVALID, "the draw store needs %llu bytes (%d chains x %d days x %d locations x %lld draws x 8), "
+                    "more than half of the %llu bytes free on the device", bytes, s->cfg.B, s->rt.D, s->ctx->d.M, stride,
+                    (unsigned long long)free_b);
+    void *q = nullptr;
+    HIP_TRY(hipMalloc(&q, (size_t)bytes));
+    if (hipMemsetAsync(q, 0, (size_t)bytes, st) != hipSuccess) { (void)hipFree(q); return fail(SEIR_ERR_DEVICE, "hipMemsetAsync failed"); }
+    const size_t lds = k_rt_trace_lds_bytes<RT_DT>(s->ctx->d.Mp);
+    if (lds > 64 * 1024)
+        (void)hipFuncSetAttribute((const void *)k_rt_trace_keep<RT_DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    s->rt_keep = (double *)q;
+    s->rt_keep_cap = cap;
+    s->rt_keep_stride = stride;
+    return 0;
+}
+
+// ranks [R] strictly increasing in [0, n): into Order64Args, or order_ranks' refusal.
+static int order_ranks(const int64_t *ranks, int32_t R, long long n, Order64Args &a) {
+    OrderArgs t{};
+    if (int rc = order_ranks(ranks, R, n, t)) return rc;
+    for (int r = 0; r < R; ++r) a.ranks[r] = t.ranks[r];
+    a.R = R;
+    return 0;
+}
+
+static void order_launch(const Order64Args &a, hipStream_t st) {
+    if ((long long)a.segs * a.seg_len <= ORDER_WAVE_N) hipLaunchKernelGGL(k_order_stats_f64<1>, dim3((unsigned)a.cells), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(k_order_stats_f64<4>, dim3((unsigned)a.cells), dim3(256), 0, st, a);
+}
+
+extern "C" int seir_sampler_rt_order_stats(seir_sampler *s, const int64_t *ranks, int32_t R, int32_t pooled, double *out) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = rt_check(s))) return rc;
+    if (!s->rt_keep) return fail(SEIR_ERR_STATE, "the draw store is not enabled: call seir_sampler_rt_keep first");
+    if (!out) return fail(SEIR_ERR_INVALID, "null output pointer");
+    if (s->rt_j < 1) return fail(SEIR_ERR_STATE, "no draws kept since the rt reset");
+    const int B = s->cfg.B;
+    hipStream_t st = s->ctx->stream;
+    std::vector<uint64_t> cnt((size_t)B);
+    HIP_TRY(hipMemcpyAsync(cnt.data(), s->rt.count, sizeof(uint64_t) * B, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int b = 0; b < B; ++b)
+        if ((long long)cnt[b] != s->rt_j)
+            return fail(SEIR_ERR_STATE, "chain %d has %llu draws folded, the store %lld: the chains' counts differ", b,
+                        (unsigned long long)cnt[b], s->rt_j);
+    const long long plane = (long long)s->rt.D * s->ctx->d.M;
+    Order64Args a{};
+    if ((rc = order_ranks(ranks, R, pooled ? s->rt_j * B : s->rt_j, a))) return rc;
+    a.values = (const unsigned long long *)s->rt_keep;
+    a.cells = pooled ? plane : plane * B;
+    a.segs = pooled ? B : 1;
+    a.seg_len = s->rt_j;
+    a.seg_stride = plane * s->rt_keep_stride;
+    a.cell_stride = s->rt_keep_stride;
+    DevBuf dout;
+    const size_t nout = (size_t)R * (size_t)a.cells;
+    if ((rc = dout.alloc(sizeof(double) * nout))) return rc;
+    a.out = dout.as<unsigned long long>();
+    order_launch(a, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, dout.p, sizeof(double) * nout, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return check_ev_overflow(s);
+}
+
+extern "C" int seir_order_stats_f64(seir_ctx *ctx, const double *values, int64_t cells, int32_t segs, int64_t seg_len,
+                                    int64_t seg_stride, int64_t cell_stride, const int64_t *ranks, int32_t R, double *out) {
+    int rc = check_batch(ctx, 1);
+    if (rc) return rc;
+    if (!values || !out) return fail(SEIR_ERR_INVALID, "null pointer");
+    if (cells < 1 || cells > 0x7fffffffll || segs < 1 || seg_len < 1 || (long long)segs * seg_len > 0x7fffffffll)
+        return fail(SEIR_ERR_INVALID, "cells=%lld, segs=%d, seg_len=%lld: at least one of each, n = segs x seg_len and cells below 2^31",
+                    (long long)cells, segs, (long long)seg_len);
+    if (cell_stride < 0 || seg_stride < 0 || (segs > 1 && seg_stride < seg_len))
+        return fail(SEIR_ERR_INVALID, "seg_stride=%lld, cell_stride=%lld: no negative stride, and segments do not overlap",
+                    (long long)seg_stride, (long long)cell_stride);
+    Order64Args a{};
+    if ((rc = order_ranks(ranks, R, (long long)segs * seg_len, a))) return rc;
+    const size_t extent = (size_t)(cells - 1) * cell_stride + (size_t)(segs - 1) * seg_stride + (size_t)seg_len;
+    const size_t nout = (size_t)R * (size_t)cells;
+    DevBuf dv, dout;
+    if ((rc = dv.alloc(sizeof(double) * extent)) || (rc = dout.alloc(sizeof(double) * nout))) return rc;
+    HIP_TRY(hipMemcpyAsync(dv.p, values, sizeof(double) * extent, hipMemcpyHostToDevice, ctx->stream));
+    a.values = dv.as<unsigned long long>(); a.out = dout.as<unsigned long long>();
+    a.cells = cells; a.segs = segs; a.seg_len = seg_len; a.seg_stride = seg_stride; a.cell_stride = cell_stride;
+    order_launch(a, ctx->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, dout.p, sizeof(double) * nout, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
 }
 

@@ -261,6 +261,17 @@ class Posterior:
         self.create_dataset("rt/R_it_var", np.ascontiguousarray(var, dtype=np.float64))
         self.create_dataset("rt/R_it_prob_gt1", np.ascontiguousarray(prob_gt1, dtype=np.float64))
 
+    def write_rt_quantiles(self, probs, chain, pooled, pooled_chains, national, pooled_national):
+        """rt/quantile_probs [K]; rt/R_it_quantiles [K,D,M] float64 over this chain's draws; rt/pooled_R_it_quantiles
+        likewise over the draws of all chains of the process (the same in every chain's file) with rt/pooled_chains, their
+        global ids; rt/R_t_quantiles and rt/pooled_R_t_quantiles [K,D], the national curve's."""
+        self.create_dataset("rt/quantile_probs", np.asarray(probs, np.float64))
+        self.create_dataset("rt/pooled_chains", np.asarray(pooled_chains, np.float64))
+        self.create_dataset("rt/R_it_quantiles", np.ascontiguousarray(chain, dtype=np.float64))
+        self.create_dataset("rt/pooled_R_it_quantiles", np.ascontiguousarray(pooled, dtype=np.float64))
+        self.create_dataset("rt/R_t_quantiles", np.ascontiguousarray(national, dtype=np.float64))
+        self.create_dataset("rt/pooled_R_t_quantiles", np.ascontiguousarray(pooled_national, dtype=np.float64))
+
     def write_check(self, days, first_day, count, mean, var, counts: dict):
         """The group check/ of one chain: days [1], first_day [1] (= T - K, the absolute day of check day 0), count [1],
         the moments of the re-simulated events and state ([M,K,6] rows: seir_mean, seir_var, state_mean, state_var, each
@@ -455,6 +466,38 @@ def rt_mode(config, override=None, T=None):
     return D
 
 
+def rt_quantiles_mode(config, override=None, rt_days=None):
+    """Mcmc.rt_quantiles (absent: off), or the command line's `--rt-quantiles 0.05,0.5,0.95`: the tuple of probabilities
+    whose exact per-day, per-location quantiles of the R_it draws are formed on the device; () for off.  1 to 8
+    probabilities in [0, 1], strictly increasing (`posterior.quantiles.parse_probs`).  With `rt_days` given (0: rt is off)
+    quantiles without rt are refused.  The one place that validates -- before a sampler exists."""
+    from ..posterior.quantiles import parse_probs
+    probs = parse_probs(config.get("rt_quantiles") if override is None else override, name="rt_quantiles")
+    if probs and rt_days is not None and not rt_days:
+        raise ValueError("rt_quantiles given without rt: it would have no effect")
+    return probs
+
+
+def draw_quantiles(x, probs):
+    """Quantiles `probs` over the first axis of x [n, ...] by the one rank rule (`posterior.quantiles`): float64 [K, ...]."""
+    from ..posterior import quantiles as Q
+    x = np.asarray(x, np.float64)
+    ranks = Q.quantile_ranks(x.shape[0], probs)
+    return Q.interpolate(np.sort(x, axis=0)[ranks], ranks, x.shape[0], probs)
+
+
+def rt_quantiles_run_line(probs, days, T, n, B, own):
+    """One log line for rt_quantiles: of the last day, the widest and narrowest band between the outermost probabilities
+    over chains and locations, and the share of (chain, location) cells whose band excludes 1.  own [K,B,D,M]."""
+    lo, hi = own[0, :, -1], own[-1, :, -1]
+    width = hi - lo
+    out = float(np.mean((lo > 1.0) | (hi < 1.0))) if width.size else float("nan")
+    return (f"R_t quantiles: {', '.join(f'{p:g}' for p in probs)} of R_it per day and location over days [{T - days}, {T}), exact "
+            f"over {n} kept draw(s) per chain and pooled over the {B} chain(s) of this process, selected on the device; on day "
+            f"{T - 1} the {probs[0]:g}-{probs[-1]:g} band is {float(width.min()):.3g} to {float(width.max()):.3g} wide and excludes 1 "
+            f"in {100.0 * out:.1f} % of the locations; rt/*_quantiles written")
+
+
 def within_between_mode(config, override=None, T=None):
     """Mcmc.within_between (absent: off), or the command line's `--within-between D`: the number of days D of the window
     [T - D, T) over which the within/between pressure shares of every kept draw of the sampling phase are formed on the
@@ -603,6 +646,11 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     on the device behind its burst (and behind the burst's summary and forecast); `rt_weight` [M] = N / N.sum() is then
     needed.  The warm-up is not folded; without the key nothing of it is called.
 
+    With Mcmc.rt_quantiles (`rt_quantiles_mode`; needs Mcmc.rt) the device keeps R_it of every folded draw: the store is
+    sized once, right behind the rt reset, for num_bursts x num_burst_samples draws per chain, and at the end of the run
+    exact quantiles per day and location are selected on the device, per chain and pooled over the chains of this process;
+    the national curve's quantiles are formed here from the draws of R_t.  Without the key nothing of it is called.
+
     With Mcmc.check = K (`check_mode`) the last K days are simulated again from every kept draw of the sampling phase and
     set against the observed removals on the device, behind the burst's summary, forecast and R_t; `check_calendar` =
     (W [K], weekday_c [K]) (`posterior.predict.check_calendar`) is then needed, and the check's stream is keyed by
@@ -623,6 +671,7 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     if horizon and forecast_calendar is None:
         raise ValueError("forecast: run_mcmc needs forecast_calendar = (W, weekday_c) of the forecast days")
     fq_probs = forecast_quantiles_mode(config, horizon=horizon)
+    rq_probs = rt_quantiles_mode(config, rt_days=rt_days)
     summaries = summaries_mode(config)
     # "off": sample / sample_bursts are called exactly as before the option existed.  Otherwise every written draw gets its
     # marginals (the warm-up without folding), the moments cover the sampling phase, and with "only" no event tensor is read
@@ -717,6 +766,8 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
                         if walk else True)
     if rt_days:
         sampler.reset_rt(rt_days, rt_weight)                # once: the sampling phase
+        if rq_probs:
+            sampler.keep_rt_draws(nb * ns)                  # the draw store of the quantiles: every kept draw of the phase
         burst_kw = dict(burst_kw, rt=True)
     if check_days:
         sampler.reset_check(check_days, check_calendar[0], check_calendar[1], check_seed(seed))   # once: the sampling phase
@@ -791,6 +842,15 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
             post.write_rt(rt_days, sampler.T - rt_days, rs.count[c], mean[c], var[c], prob[c])
         r_t = np.concatenate(rt_draws) if rt_draws else np.empty((0, sampler.B, rt_days))
         print(rt_run_line(rt_days, sampler.T, r_t, prob), file=log, flush=True)
+        if rq_probs and nb * ns:
+            first_id = getattr(sampler, "first_chain_id", 0)
+            own = sampler.rt_quantiles(rq_probs)                        # [K,B,D,M]
+            pooled = sampler.rt_quantiles(rq_probs, pooled=True)        # [K,D,M]
+            nat = draw_quantiles(r_t, rq_probs)                         # [K,B,D]: costs nothing here
+            pnat = draw_quantiles(r_t.reshape(-1, rt_days), rq_probs)   # [K,D]
+            for c, post in enumerate(posteriors):
+                post.write_rt_quantiles(rq_probs, own[:, c], pooled, [first_id + b for b in range(sampler.B)], nat[:, c], pnat)
+            print(rt_quantiles_run_line(rq_probs, rt_days, sampler.T, nb * ns, sampler.B, own), file=log, flush=True)
     if check_days:
         cs = sampler.check_summary()
         mean, var = cs.moments.mean, cs.moments.var
@@ -871,7 +931,8 @@ def launch_forms(lay, device_arg, hmc="auto", moves="auto", env=os.environ):
 
 def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool_step_size=False, init_jitter=0.0,
          events_dtype="auto", hmc="auto", moves="auto", thin=None, summaries=None, diagnostics=None, diagnostics_batch=None,
-         forecast=None, forecast_walk=None, rt=None, check=None, forecast_quantiles=None, within_between=None):
+         forecast=None, forecast_walk=None, rt=None, check=None, forecast_quantiles=None, within_between=None,
+         rt_quantiles=None):
     """Constructs and runs the MCMC (covid19uk/inference/inference.py:473-608).
 
     Multi-GPU: launched as one process per GPU, every rank runs `num_chains` chains with
@@ -883,7 +944,7 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     config["diagnostics_batch"] (`diagnostics_mode`), `forecast` / `forecast_walk` config["forecast"] /
     config["forecast_walk"] (`forecast_mode`), `forecast_quantiles` config["forecast_quantiles"]
     (`forecast_quantiles_mode`), `rt` config["rt"] (`rt_mode`), `check` config["check"] (`check_mode`), `within_between`
-    config["within_between"] (`within_between_mode`)."""
+    config["within_between"] (`within_between_mode`), `rt_quantiles` config["rt_quantiles"] (`rt_quantiles_mode`)."""
     wb_days = 0
     if within_between is not None or "within_between" in config:
         wb_days = within_between_mode(config, within_between)   # refused here: before any GPU call
@@ -902,6 +963,11 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
         config = {k: v for k, v in config.items() if k != "rt"}
         if rt_days:
             config = dict(config, rt=rt_days)
+    if rt_quantiles is not None or "rt_quantiles" in config:
+        rq_probs = rt_quantiles_mode(config, rt_quantiles, rt_days=rt_days)   # refused here: before any GPU call
+        config = {k: v for k, v in config.items() if k != "rt_quantiles"}
+        if rq_probs:
+            config = dict(config, rt_quantiles=list(rq_probs))
     horizon = 0
     if forecast is not None or forecast_walk is not None or "forecast" in config or "forecast_walk" in config:
         horizon, walk = forecast_mode(config, forecast, forecast_walk)    # refused here: before any GPU call
@@ -1062,6 +1128,11 @@ def main(argv=None):
                              "days (1..T) on the device (overrides Mcmc.rt; default off): a group rt/ with the mean, "
                              "variance and P(R > 1) per day and location, and the national curve per draw samples/R_t; "
                              "works with --summaries only, --thin and --forecast")
+    parser.add_argument("--rt-quantiles", type=str, default=None, metavar="P,P,...", dest="rt_quantiles",
+                        help="exact quantiles of the R_it draws per day of the window and location, selected on the device "
+                             "(overrides Mcmc.rt_quantiles; needs --rt): 1 to 8 increasing probabilities in [0, 1], e.g. "
+                             "0.05,0.5,0.95; rt/R_it_quantiles per chain, rt/pooled_R_it_quantiles over the chains of the "
+                             "process and rt/R_t_quantiles of the national curve; works with --summaries only and --thin")
     parser.add_argument("--check", type=int, default=None, metavar="K",
                         help="simulate the last K observed days (1..min(T, 128)) again from every kept draw of the sampling "
                              "phase and set them against the observed removals, on the device (overrides Mcmc.check; default "
@@ -1087,7 +1158,8 @@ def main(argv=None):
          diagnostics_batch=args.diagnostics_batch, forecast=args.forecast, forecast_walk=args.forecast_walk, rt=args.rt,
          **({} if args.check is None else dict(check=args.check)),
          **({} if args.within_between is None else dict(within_between=args.within_between)),
-         **({} if args.forecast_quantiles is None else dict(forecast_quantiles=args.forecast_quantiles)))
+         **({} if args.forecast_quantiles is None else dict(forecast_quantiles=args.forecast_quantiles)),
+         **({} if args.rt_quantiles is None else dict(rt_quantiles=args.rt_quantiles)))
 
 
 if __name__ == "__main__":

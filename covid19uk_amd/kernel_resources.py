@@ -2,7 +2,7 @@
 (registers, scratch, spills, LDS, occupancy per kernel).  `__graft_entry__.build()` keeps the result next to the library as
 kernel_resources.json (and, for the kernels added since that file's set was pinned, added_kernel_resources.json; for the
 self-test kernels of the device math, selftest_kernel_resources.json; for the kernels of the within/between shares,
-wb_kernel_resources.json);
+wb_kernel_resources.json; for the kernels of the R_t intervals, rtq_kernel_resources.json);
 tests/test_resources.py holds the hot-path instances to it; tools/dev/resources.py prints it."""
 import re
 

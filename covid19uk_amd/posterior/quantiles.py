@@ -1,4 +1,5 @@
-"""Quantiles from exact order statistics: the one definition of the rank rule behind `Mcmc: forecast_quantiles`.
+"""Quantiles from exact order statistics: the one definition of the rank rule behind `Mcmc: forecast_quantiles` and
+`Mcmc: rt_quantiles`.
 
 The device selects order statistics (include/seir_hip.h, "Forecast intervals on the device"); which ones to ask for, and how
 two of them become a quantile, is decided here and nowhere else.  For a probability p and n draws
@@ -14,12 +15,13 @@ import numpy as np
 MAX_PROBS = 8                     # two ranks each: SEIR_ORDER_STATS_MAX_RANKS = 16
 
 
-def parse_probs(value):
-    """`Mcmc.forecast_quantiles` / `--forecast-quantiles`: a list of numbers or a comma-separated string -> a tuple of 1 to
-    MAX_PROBS probabilities in [0, 1], strictly increasing.  None, False and "off" -> ().  ValueError otherwise."""
+def parse_probs(value, name="forecast_quantiles"):
+    """`Mcmc.forecast_quantiles` / `--forecast-quantiles` (or the key `name`): a list of numbers or a comma-separated string
+    -> a tuple of 1 to MAX_PROBS probabilities in [0, 1], strictly increasing.  None, False and "off" -> ().  ValueError
+    otherwise."""
     if value is None or value is False or (isinstance(value, str) and value.strip().lower() == "off"):
         return ()
-    what = f"forecast_quantiles={value!r}"
+    what = f"{name}={value!r}"
     if isinstance(value, str):
         value = [v for v in value.split(",")]
     elif isinstance(value, (int, float, np.integer, np.floating)) and not isinstance(value, bool):

@@ -766,6 +766,37 @@ class ChainSampler:
                                                   _dptr(sm), _dptr(sq), g1.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
         return RtSummary(count=cnt, ref=ref, sum=sm, sumsq=sq, gt1=g1)
 
+    # -- R_t intervals: the R_it draw store and exact order statistics (include/seir_hip.h, "R_t intervals") ----------
+    def keep_rt_draws(self, cap: int):
+        """Keep R_it of every draw that `rt` folds on the device, for up to `cap` draws per chain: between `reset_rt` and
+        the first `rt`.  0 frees the store.  B x D x M x cap x 8 bytes; the library refuses a store above half of the
+        device's free memory."""
+        cap = int(cap)
+        if cap < 0:
+            raise ValueError(f"cap={cap}: the number of draws per chain to keep")
+        _lib.check(self._lib.seir_sampler_rt_keep(self._s, cap))
+
+    def rt_order_stats(self, ranks, pooled: bool = False) -> np.ndarray:
+        """Exact order statistics `ranks` (strictly increasing, at most 16) of every cell's R_it over the draws kept since
+        the reset (blocking): float64 [R, B, D, M] or, `pooled`, [R, D, M] over the B x count values of all chains of this
+        sampler.  Equal to np.sort(draws, axis=0)[ranks], bit for bit."""
+        ranks = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
+        out = np.empty((len(ranks),) + (() if pooled else (self.B,)) + (self._rt_D, self.M))
+        _lib.check(self._lib.seir_sampler_rt_order_stats(self._s, ranks.ctypes.data_as(_lib.c_int64_p), len(ranks),
+                                                         1 if pooled else 0, _dptr(out)))
+        return out
+
+    def rt_quantiles(self, probs, pooled: bool = False) -> np.ndarray:
+        """Quantiles `probs` (NumPy's default rule, `posterior.quantiles`) of every cell's R_it over the draws kept since
+        the reset (blocking): float64 [K, B, D, M], or [K, D, M] when `pooled`."""
+        from .posterior import quantiles as Q
+        cnt = np.zeros(self.B, np.uint64)
+        _lib.check(self._lib.seir_sampler_read_rt(self._s, cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), None, None,
+                                                  None, None))
+        n = int(cnt[0]) * (self.B if pooled else 1)         # the library refuses chains whose counts differ
+        ranks = Q.quantile_ranks(n, probs)
+        return Q.interpolate(self.rt_order_stats(ranks, pooled=pooled), ranks, n, probs)
+
     def _rt_burst(self, first, count):
         if not self._rt_D:
             raise ValueError("rt asked for before reset_rt")

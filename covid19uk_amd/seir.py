@@ -306,6 +306,26 @@ class SeirModel:
                                               out.ctypes.data_as(ip)))
         return out
 
+    def order_stats_f64(self, values, ranks, cells=1, segs=1, seg_len=None, seg_stride=None, cell_stride=None):
+        """`order_stats` for float64 (csrc/order_stats64_kernels.h; include/seir_hip.h, seir_order_stats_f64): the same
+        cell geometry, the order of IEEE-754 totalOrder on the bit patterns (np.sort's on values without NaN, except that
+        -0.0 comes before +0.0).  Returns float64 [R, cells]."""
+        v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+        ranks = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
+        cells, segs = int(cells), int(segs)
+        if seg_len is None:
+            seg_len = v.size // max(cells * segs, 1)
+        seg_stride = int(seg_len) if seg_stride is None else int(seg_stride)
+        cell_stride = segs * seg_stride if cell_stride is None else int(cell_stride)
+        extent = (cells - 1) * cell_stride + (segs - 1) * seg_stride + int(seg_len)
+        if cells < 1 or segs < 1 or int(seg_len) < 1 or min(seg_stride, cell_stride) < 0 or extent > v.size:
+            raise ValueError(f"{cells} cell(s) of {segs} x {seg_len} values at strides {seg_stride}, {cell_stride} do not "
+                             f"lie within the {v.size} values given")
+        out = np.empty((len(ranks), cells), dtype=np.float64)
+        _lib.check(self._lib.seir_order_stats_f64(self._ctx, _dptr(v), cells, segs, int(seg_len), seg_stride, cell_stride,
+                                                  ranks.ctypes.data_as(_lib.c_int64_p), len(ranks), _dptr(out)))
+        return out
+
     def reproduction_number(self, theta, events):
         """R_it [n,T,M] for n posterior draws: column sums of the next-generation matrix
         (covid19uk/posterior/reproduction_number.py:13-44, model_spec.py:302-368).

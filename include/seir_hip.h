@@ -697,6 +697,47 @@ int seir_sampler_read_rt_draws_async(seir_sampler *s, int32_t first, int32_t cou
 int seir_sampler_read_rt(seir_sampler *s, uint64_t *count, double *ref, double *sum, double *sumsq, uint32_t *gt1);
 
 /* ------------------------------------------------------------------------
+ * R_t intervals on the device: exact per-cell order statistics of the R_it draws.
+ *
+ * R_it is a sum of S (1 - exp(-x)) terms times a period that depends on the draw: its posterior per cell is skewed, and a
+ * normal band from the moments above is wrong near 1.  While the draw store is on, every draw folded by seir_sampler_rt
+ * leaves its R_it, one fp64 per (chain, window day, location), on the device, and at the end of the run exact order
+ * statistics are selected from them there; only the selected values cross PCIe.
+ *
+ * Semantics (the one definition; kernels: k_rt_trace_keep of csrc/rt_keep_kernels.h, csrc/order_stats64_kernels.h, the
+ * narrowing step csrc/order_select64.h).
+ *   Store.  keepR[B][D][M][cap] fp64, the draw index innermost (the rows are padded to a multiple of 4 draws).  Draw j of
+ *     chain b -- count[b] of seir_sampler_read_rt at the kernel's entry plus the draw's index in the call -- fills position j
+ *     of every cell of that chain, with the bits of the R_it that is folded: k_rt_trace_keep runs in place of k_rt_trace
+ *     and forms R_it once.  Nothing depends on how bursts are cut into calls, host batches or buffer halves, or on how
+ *     chains are sharded over samplers; a burst run again after a hand-off time-out overwrites its own positions
+ *     (seir_sampler_restore brings count back), so the store has no shadow copy.
+ *   Order.  That of IEEE-754 totalOrder on the bit pattern: key = bits ^ (bits >> 63 ? ~0 : 1 << 63), compared as unsigned
+ *     64-bit.  On values without NaN order statistic r is np.sort(values)[r], bit for bit, except that -0.0 sorts before
+ *     +0.0; NaNs sort by sign and payload, negative ones first and positive ones last.
+ *   Size: B x D x M x cap x 8 bytes (UK-380 x 8 chains, D = 14, 5000 draws: 1.70 GB; D = 365: 44 GB).
+ * A sampler that never calls seir_sampler_rt_keep allocates and launches exactly what it did before.
+ * ------------------------------------------------------------------------ */
+/* Size the draw store for `cap` draws per chain: after seir_sampler_rt_reset and before the first seir_sampler_rt
+ * (SEIR_ERR_STATE otherwise).  Allocates on first use (and when cap changes); cap = 0 frees the store, at any time.  A
+ * later seir_sampler_rt_reset with the same days empties the store, one with another window frees it.  While the store is
+ * on, seir_sampler_rt refuses (SEIR_ERR_INVALID, naming both numbers) a call that would take a chain past cap.
+ * SEIR_ERR_INVALID, before anything is allocated, for cap outside [0, 2^20] and for a store larger than half of what
+ * hipMemGetInfo reports free (the message carries both figures): the policy of a device that is shared, not a
+ * measurement. */
+int seir_sampler_rt_keep(seir_sampler *s, int64_t cap);
+/* Blocking.  Order statistics `ranks` [R] (strictly increasing, 1 <= R <= SEIR_ORDER_STATS_MAX_RANKS) of every cell over
+ * the `count` draws per chain kept since the reset.  out is a host pointer: [R][B][D][M] with ranks in [0, count), or,
+ * pooled != 0, [R][D][M] over the B x count values of the process's chains with ranks in [0, B x count).
+ * SEIR_ERR_STATE before a reset, without a store, when no draw is kept yet or when the chains' counts differ;
+ * SEIR_ERR_INVALID for R outside its range and for ranks out of range, unsorted or repeated. */
+int seir_sampler_rt_order_stats(seir_sampler *s, const int64_t *ranks, int32_t R, int32_t pooled, double *out);
+/* The fp64 selection alone, stateless, host pointers, blocking: seir_order_stats for doubles in the order above, with the
+ * same cell geometry and the same refusals.  out [R][cells]. */
+int seir_order_stats_f64(seir_ctx *ctx, const double *values, int64_t cells, int32_t segs, int64_t seg_len, int64_t seg_stride,
+                         int64_t cell_stride, const int64_t *ranks, int32_t R, double *out);
+
+/* ------------------------------------------------------------------------
  * Within/between pressure shares on the device: moments per cell and the national pressures per draw.
  *
  * Stands in for covid19uk/posterior/within_between.py run on every kept draw, without samples/seir: for each draw of

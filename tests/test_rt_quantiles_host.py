@@ -1,0 +1,433 @@
+"""Host side of the R_t intervals (include/seir_hip.h, "R_t intervals on the device"), no GPU: the symbols, the 64-bit
+narrowing step of the radix select (covid19uk_amd/csrc/order_select64.h, the one definition k_order_stats_f64 calls) compiled
+as plain C++ and driven through its eight passes against Python's sorted() under an independently written total-order key,
+the key map itself, the configuration and the command line, run_mcmc's call sequence with a stub sampler, the datasets
+written, and the compiler's account of the two new kernels."""
+import ctypes
+import json
+import os
+import re
+import shutil
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import __graft_entry__ as entry
+from covid19uk_amd import _lib, hdf5io
+from covid19uk_amd.inference import inference as inf
+from covid19uk_amd.posterior import quantiles as Q
+from covid19uk_amd.sampler import ChainSampler
+from covid19uk_amd.seir import SeirModel
+from tests.test_rt_device_host import RtStub
+from tests.test_summary_host import CFG, _read
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = {
+    "seir_sampler_rt_keep": "seir_sampler *s, int64_t cap",
+    "seir_sampler_rt_order_stats": "seir_sampler *s, const int64_t *ranks, int32_t R, int32_t pooled, double *out",
+    "seir_order_stats_f64": "seir_ctx *ctx, const double *values, int64_t cells, int32_t segs, int64_t seg_len, "
+                            "int64_t seg_stride, int64_t cell_stride, const int64_t *ranks, int32_t R, double *out",
+}
+CTYPES = {"seir_sampler *": ctypes.c_void_p, "seir_ctx *": ctypes.c_void_p, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
+          "const int64_t *": ctypes.POINTER(ctypes.c_int64), "double *": ctypes.POINTER(ctypes.c_double),
+          "const double *": ctypes.POINTER(ctypes.c_double)}
+MASK = (1 << 64) - 1
+
+
+# ---- 1. the symbols ------------------------------------------------------------------------------------------------------
+def test_new_symbols_are_declared_exported_and_bound_with_the_headers_types():
+    entry.build()
+    lib = _lib.load()
+    raw = open(os.path.join(ROOT, "include", "seir_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
+    for name, params in NEW.items():
+        m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
+        assert m, f"{name} is not declared in include/seir_hip.h"
+        declared = " ".join(m.group(1).split())
+        assert declared == params, (name, declared)
+        assert name in _lib.exported_symbols()
+        fn = getattr(lib, name)                              # exported by the library
+        want = []
+        for p in declared.split(","):
+            ty = p.strip().rsplit(" ", 1)[0] + (" *" if "*" in p else "")
+            want.append(CTYPES[ty.replace("* *", "*").strip()])
+        assert fn.restype is ctypes.c_int and list(fn.argtypes) == want, (name, fn.argtypes)
+    # new symbols only: the ABI version and the descriptors are the parent's
+    assert lib.seir_abi_version() == 4 and _lib.ABI_VERSION == 4
+    assert re.search(r"#define SEIR_ABI_VERSION 4\b", raw)
+    assert ctypes.sizeof(_lib.SeirSamplerDesc) == 12 * 4 + 8 + 8 * 4
+    assert ctypes.sizeof(_lib.SeirDesc) == 4 * 4 + 6 * 8 + 8 + 8 + 3 * 8
+    assert ctypes.sizeof(_lib.SeirSimDesc) == 4 * 4 + 8 + 7 * 8
+    # a null sampler / context is refused before anything touches a device
+    one = (ctypes.c_int64 * 1)(0)
+    out = (ctypes.c_double * 1)(0.0)
+    assert lib.seir_sampler_rt_keep(None, 5) == _lib.ERR_INVALID
+    assert lib.seir_sampler_rt_order_stats(None, one, 1, 0, out) == _lib.ERR_INVALID
+    assert lib.seir_order_stats_f64(None, out, 1, 1, 1, 1, 1, one, 1, out) == _lib.ERR_INVALID
+    for name in ("keep_rt_draws", "rt_order_stats", "rt_quantiles"):
+        assert callable(getattr(ChainSampler, name))
+    assert callable(SeirModel.order_stats_f64)
+
+
+# ---- 2. the key map and the narrowing step, as plain C++ -------------------------------------------------------------------
+def bits_of(x):
+    """The bit patterns of float64 values as Python ints."""
+    return [int(v) for v in np.ascontiguousarray(x, np.float64).view(np.uint64)]
+
+
+def total_order_key(bits):
+    """IEEE-754 totalOrder on a double's bit pattern, as an unsigned 64-bit key (written here, not read from the header)."""
+    return bits ^ (MASK if bits >> 63 else 1 << 63)
+
+
+def total_order_sorted(x):
+    """x (float64) in the total order, as float64 with the same bit patterns."""
+    return np.array(sorted(bits_of(x), key=total_order_key), np.uint64).view(np.float64)
+
+
+def _nan(sign, payload):
+    return struct.unpack("<d", struct.pack("<Q", (sign << 63) | (0x7FF << 52) | payload))[0]
+
+
+def value_families(n, seed=0):
+    """The arrays both test files hold the fp64 select to: name -> (float64 [n], same order as np.sort?)."""
+    rng = np.random.default_rng([seed, n])
+    near = np.array([np.nextafter(1.0, 0.0), 1.0, np.nextafter(1.0, 2.0)])
+    tiny = np.float64(5e-324)
+    big = np.finfo(np.float64).max
+    ext = np.array([np.inf, -np.inf, tiny, -tiny, big, -big, 1e-300, -1e-300, 3.0, -3.0])
+    low = (np.uint64(0x3FF0000000000000) + rng.integers(0, 256, size=n).astype(np.uint64)).view(np.float64)
+    high = ((rng.integers(0, 256, size=n).astype(np.uint64) << np.uint64(56)) | np.uint64(0x000ABCDEF0123456)).view(np.float64)
+    high = np.where(np.isnan(high) | np.isinf(high), 1.5, high)               # exponent 7ff / fff: kept for the NaN family
+    nans = rng.gamma(2.0, 0.6, size=n)
+    nans[::3] = _nan(0, 1 << 51)
+    nans[1::5] = _nan(1, 1 << 51)
+    nans[2::7] = _nan(0, 12345)
+    nans[3::11] = _nan(1, (1 << 51) | 77)
+    fam = {
+        "all_equal": (np.full(n, 1.2345), True),
+        "two_valued": (rng.choice([0.75, -70000.5], size=n), True),
+        "neighbours_of_one": (near[rng.integers(0, 3, size=n)], True),
+        "lowest_digit": (low, True),
+        "highest_digit": (high, True),
+        "signed_zeros": (np.where(rng.integers(0, 2, size=n) == 1, 0.0, -0.0) * 1.0, False),
+        "extremes": (ext[rng.integers(0, len(ext), size=n)], True),
+        "gamma": (rng.gamma(2.0, 0.6, size=n), True),
+        "small_integers": (rng.poisson(1.5, size=n).astype(np.float64), True),
+        "nans_of_both_signs": (nans, False),
+    }
+    return {k: (np.ascontiguousarray(v, np.float64), same) for k, (v, same) in fam.items()}
+
+
+DRIVER = r"""
+#include <cinttypes>
+#include <cstdio>
+#include <unordered_map>
+#include <vector>
+#include "order_select64.h"
+// stdin: n, then n bit patterns (unsigned decimal).  stdout: for every rank 0 .. n-1 the bit pattern the eight-pass select
+// arrives at, one per line.  As in k_order_stats_f64, ranks whose prefixes agree share a histogram, and a value is counted
+// under the prefix it matches.
+int main() {
+    long long n;
+    if (std::scanf("%lld", &n) != 1 || n < 1) return 2;
+    std::vector<uint64_t> v((size_t)n);
+    for (auto &x : v) if (std::scanf("%" SCNu64, &x) != 1) return 2;
+    std::vector<uint64_t> prefix((size_t)n, 0ull);
+    std::vector<uint32_t> rem((size_t)n);
+    for (long long r = 0; r < n; ++r) rem[(size_t)r] = (uint32_t)r;
+    static_assert(seir::ORDER64_PASSES == 8 && seir::ORDER_BINS == 256 && seir::ORDER_MAX_RANKS == 16, "8-bit digits, eight passes");
+    for (int pass = 0; pass < seir::ORDER64_PASSES; ++pass) {
+        std::unordered_map<uint64_t, std::vector<uint32_t>> hist;
+        for (uint64_t p : prefix) if (!hist.count(p)) hist[p] = std::vector<uint32_t>(seir::ORDER_BINS, 0u);
+        const int sh = seir::order64_shift(pass);
+        if (sh != 56 - 8 * pass) return 9;
+        for (uint64_t x : v) {
+            const uint64_t key = seir::order64_key(x);
+            if (seir::order64_value(key) != x) return 3;
+            const uint64_t high = pass == 0 ? 0ull : key & ~((1ull << (sh + seir::ORDER_DIGIT_BITS)) - 1ull);
+            auto it = hist.find(high);
+            if (it == hist.end()) continue;
+            if (!seir::order64_matches(key, it->first, pass)) return 4;
+            it->second[seir::order64_digit(key, pass)] += 1u;
+        }
+        for (long long r = 0; r < n; ++r)
+            if (!seir::order64_select_narrow(hist[prefix[(size_t)r]].data(), pass, prefix[(size_t)r], rem[(size_t)r])) return 5;
+    }
+    for (long long r = 0; r < n; ++r) {
+        if (rem[(size_t)r] >= (uint32_t)n) return 6;
+        std::printf("%" PRIu64 "\n", seir::order64_value(prefix[(size_t)r]));
+    }
+    // a rank past the count is refused, and the state is left alone
+    std::vector<uint32_t> h(seir::ORDER_BINS, 0u);
+    h[7] = 3;
+    uint64_t p = 0x1200000000000000ull;
+    uint32_t k = 3;
+    if (seir::order64_select_narrow(h.data(), 1, p, k) || p != 0x1200000000000000ull || k != 3) return 7;
+    k = 2;
+    if (!seir::order64_select_narrow(h.data(), 1, p, k) || p != 0x1207000000000000ull || k != 2) return 8;
+    p = 0xFFFFFFFFFFFFFF00ull; k = 2;
+    if (!seir::order64_select_narrow(h.data(), 7, p, k) || p != 0xFFFFFFFFFFFFFF07ull || k != 2) return 10;
+    return 0;
+}
+"""
+SIZES = (1, 2, 3, 255, 256, 257, 5000)
+
+
+@pytest.fixture(scope="module")
+def select(tmp_path_factory):
+    cxx = None
+    try:
+        cxx = [entry._hipcc(), "-x", "c++"]
+    except RuntimeError:
+        for cand in ("g++", "c++", "clang++"):
+            if shutil.which(cand):
+                cxx = [cand]
+                break
+    assert cxx, "no C++ compiler"
+    d = tmp_path_factory.mktemp("order_select64")
+    src, exe = d / "driver.cpp", d / "driver"
+    src.write_text(DRIVER)
+    subprocess.run(cxx + ["-std=c++17", "-O1", "-Wall", "-Werror", "-I", entry.CSRC, "-o", str(exe), str(src)],
+                   check=True, capture_output=True, text=True)
+
+    def run(bits):
+        text = f"{len(bits)}\n" + " ".join(str(int(v)) for v in bits) + "\n"
+        r = subprocess.run([str(exe)], input=text, capture_output=True, text=True)
+        assert r.returncode == 0, (r.returncode, r.stderr)
+        return [int(v) for v in r.stdout.split()]
+    return run
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_the_eight_pass_select_equals_the_total_order_for_every_rank(select, n):
+    for name, (x, as_numpy) in value_families(n).items():
+        assert x.shape == (n,) and x.dtype == np.float64
+        bits = bits_of(x)
+        got = select(bits)
+        assert got == sorted(bits, key=total_order_key), name
+        if as_numpy:                                         # no NaN, no mixed-sign zeros: np.sort's bits exactly
+            assert not np.isnan(x).any()
+            assert got == bits_of(np.sort(x)), name
+    fam = value_families(max(n, 64))
+    assert np.isnan(fam["nans_of_both_signs"][0]).any() and np.signbit(fam["nans_of_both_signs"][0][np.isnan(fam["nans_of_both_signs"][0])]).any()
+    assert {b >> 8 for b in bits_of(fam["lowest_digit"][0])} == {0x3FF0000000000000 >> 8}
+    assert len({b & ((1 << 56) - 1) for b in bits_of(fam["highest_digit"][0])} - {bits_of([1.5])[0] & ((1 << 56) - 1)}) == 1
+    z = fam["signed_zeros"][0]
+    assert np.all(z == 0.0) and np.signbit(z).any() and not np.signbit(z).all()
+    # the definition where it differs from np.sort: -0.0 before +0.0, negative NaNs first, positive NaNs last
+    srt = total_order_sorted(z)
+    k = int(np.signbit(z).sum())
+    assert np.signbit(srt[:k]).all() and not np.signbit(srt[k:]).any()
+    srt = total_order_sorted(fam["nans_of_both_signs"][0])
+    nn = np.isnan(srt)
+    neg, pos = int((nn & np.signbit(srt)).sum()), int((nn & ~np.signbit(srt)).sum())
+    assert neg and pos and nn[:neg].all() and nn[len(srt) - pos:].all() and not nn[neg:len(srt) - pos].any()
+
+
+def test_the_key_map_is_an_involution_and_strictly_monotone_on_finite_doubles():
+    rng = np.random.default_rng(5)
+    grid = np.unique(np.concatenate([
+        rng.standard_normal(2000) * 10.0 ** rng.integers(-300, 300, size=2000), [-np.finfo(np.float64).max, -1.0, -5e-324, 5e-324, 1.0,
+                                                                                np.nextafter(1.0, 2.0), np.finfo(np.float64).max]]))
+    assert np.all(np.isfinite(grid)) and np.all(np.diff(grid) > 0)
+    keys = [total_order_key(b) for b in bits_of(grid)]
+    assert all(a < b for a, b in zip(keys, keys[1:]))
+    # the inverse of the header (key's top bit set: the value was positive), on every pattern class
+    def value_of(key):
+        return key ^ ((1 << 63) if key >> 63 else MASK)
+    pats = bits_of(grid) + bits_of([0.0, -0.0, np.inf, -np.inf, _nan(0, 1), _nan(1, 1 << 51)]) + [0, MASK, 1 << 63, (1 << 63) - 1]
+    for b in pats:
+        k = total_order_key(b)
+        assert 0 <= k <= MASK and value_of(k) == b
+    assert total_order_key(bits_of([-0.0])[0]) + 1 == total_order_key(bits_of([0.0])[0])
+    # and the header says the same thing in its own words
+    text = open(os.path.join(entry.CSRC, "order_select64.h")).read()
+    assert "bits ^ ((bits >> 63) ? ~0ull : 1ull << 63)" in text and "key ^ ((key >> 63) ? 1ull << 63 : ~0ull)" in text
+
+
+# ---- 3. configuration and command line -------------------------------------------------------------------------------------
+def test_probabilities_are_parsed_and_bad_ones_refused_before_any_gpu_call(tmp_path):
+    mode = inf.rt_quantiles_mode
+    assert mode({}) == () and mode(dict(CFG, rt=14)) == ()
+    assert mode(dict(CFG, rt=14, rt_quantiles=[0.05, 0.5, 0.95]), rt_days=14) == (0.05, 0.5, 0.95)
+    assert mode(dict(CFG, rt_quantiles=[0.5]), "0.05,0.5,0.95", rt_days=7) == (0.05, 0.5, 0.95)       # the command line overrides
+    assert mode(CFG, "0, 1") == (0.0, 1.0) and mode(CFG, [0.25]) == (0.25,) and mode(CFG, 0.5) == (0.5,)
+    assert mode(dict(CFG, rt_quantiles="off")) == ()
+    assert len(mode(CFG, [i / 8 for i in range(8)])) == 8
+    for bad in ([], "", [0.5, 0.5], [0.9, 0.1], [-0.01], [1.01], ["soon"], "0.1,,0.2", [float("nan")], [True],
+                [i / 9 for i in range(9)], {"a": 1}, True):
+        with pytest.raises(ValueError, match="rt_quantiles"):
+            mode(dict(CFG, rt=14, rt_quantiles=bad), rt_days=14)
+    with pytest.raises(ValueError, match="no effect"):       # quantiles of nothing are not dropped in silence
+        mode(dict(CFG, rt_quantiles=[0.5]), rt_days=0)
+    # the forecast's key keeps its own name in its refusals
+    with pytest.raises(ValueError, match="forecast_quantiles"):
+        inf.forecast_quantiles_mode(dict(CFG, forecast=3, forecast_quantiles=[2.0]), horizon=3)
+    # mcmc() refuses all of it before it reads the data file or opens a device: the file named here does not exist
+    nofile, out = str(tmp_path / "no_such_file.nc"), str(tmp_path / "out.hd5")
+    with pytest.raises(ValueError, match="no effect"):
+        inf.mcmc(nofile, out, dict(CFG, rt_quantiles=[0.5]))
+    with pytest.raises(ValueError, match="no effect"):
+        inf.mcmc(nofile, out, CFG, rt_quantiles="0.5")
+    with pytest.raises(ValueError, match="no effect"):
+        inf.mcmc(nofile, out, dict(CFG, rt="off"), rt_quantiles="0.5")
+    for bad in ("", "0.5,0.5", "0.9,0.1", "2", "soon", "nan", ",".join(str(i / 9) for i in range(9))):
+        with pytest.raises(ValueError, match="rt_quantiles"):
+            inf.mcmc(nofile, out, dict(CFG, rt=14), rt_quantiles=bad)
+    with pytest.raises(ValueError, match="rt_quantiles"):
+        inf.mcmc(nofile, out, dict(CFG, rt=14, rt_quantiles=[]))
+    assert not os.path.exists(out)
+
+
+def test_the_cli_flag_parses(tmp_path, monkeypatch):
+    import yaml
+    cpath = str(tmp_path / "c.yaml")
+    with open(cpath, "w") as f:
+        yaml.safe_dump(dict(Mcmc=CFG), f)
+    seen = {}
+    monkeypatch.setattr(inf, "mcmc", lambda *a, **kw: (seen.clear(), seen.update(kw)))
+    inf.main(["-c", cpath, "-o", "x", "--rt", "7", "--rt-quantiles", "0.05,0.5,0.95", "data.nc"])
+    assert seen["rt"] == 7 and seen["rt_quantiles"] == "0.05,0.5,0.95"
+    inf.main(["-c", cpath, "-o", "x", "--rt", "7", "data.nc"])
+    assert "rt_quantiles" not in seen                        # absent: mcmc is called as before the option existed
+
+
+# ---- 4. run_mcmc with a stub sampler ---------------------------------------------------------------------------------------
+class RtqStub(RtStub):
+    """RtStub with the draw store: what is kept and asked for is recorded; a cell's draws are the sweep numbers."""
+
+    def keep_rt_draws(self, cap):
+        self.calls.append(("keep_rt_draws", cap))
+
+    def rt_quantiles(self, probs, pooled=False):
+        self.calls.append(("rt_quantiles", tuple(probs), pooled))
+        q = np.quantile(np.asarray(self.rt_rows, np.float64), probs)          # pooling B identical chains leaves them alone
+        cell = q[:, None, None] + np.arange(self.D)[None, :, None] / 4.0 + np.zeros((1, 1, self.M))
+        return cell + 100.0 if pooled else np.repeat(cell[:, None], self.B, axis=1)
+
+
+def _run(tmp_path, tag, config, ext=".npz", cap=800, stub=RtqStub):
+    s = stub()
+    s.cap = cap
+    nb, ns = config["num_bursts"], config["num_burst_samples"]
+    D = inf.rt_mode(config)
+    names = [str(tmp_path / f"{tag}_{c}{ext}") for c in range(s.B)]
+    kw = {} if config.get("summaries", "off") == "off" else dict(summaries=config["summaries"])
+    if D:
+        kw["rt"] = (D, nb * ns)
+    posts = [inf.Posterior(name, s.M, s.T, 2, inf.warmup_size() + nb * ns, **kw) for name in names]
+    logname = str(tmp_path / f"{tag}.log")
+    fkw = dict(rt_weight=np.arange(1, s.M + 1) / (s.M * (s.M + 1) / 2)) if D else {}
+    with open(logname, "w") as log:
+        inf.run_mcmc(s, config, posts, log=log, **fkw)
+    for p in posts:
+        p.close()
+    return s, [_read(n) for n in names], open(logname).read()
+
+
+def _untimed(log):
+    return [ln for ln in log.splitlines() if not ln.startswith("Sampling: ")]      # that line carries a wall-clock rate
+
+
+NEW_SETS = {"rt/quantile_probs", "rt/pooled_chains", "rt/R_it_quantiles", "rt/pooled_R_it_quantiles", "rt/R_t_quantiles",
+            "rt/pooled_R_t_quantiles"}
+
+
+def test_absent_calls_nothing_new_and_writes_todays_datasets(tmp_path):
+    cfg = dict(CFG, rt=3)
+    s0, f0, log0 = _run(tmp_path, "parent", cfg, stub=RtStub)             # a sampler that has never heard of the store
+    s1, f1, log1 = _run(tmp_path, "absent", cfg)
+    assert len(s1.calls) == len(s0.calls) and [c[0] for c in s1.calls] == [c[0] for c in s0.calls]
+    assert not any(c[0] in ("keep_rt_draws", "rt_quantiles") for c in s1.calls)
+    assert "uantiles:" not in log1 and _untimed(log1) == _untimed(log0)
+    for c in range(2):
+        assert set(f1[c]) == set(f0[c]) and not (NEW_SETS & set(f1[c]))
+        for k in f0[c]:
+            assert np.array_equal(f1[c][k], f0[c][k], equal_nan=True), k
+    with pytest.raises(ValueError, match="no effect"):
+        _run(tmp_path, "nort", dict(CFG, rt_quantiles=[0.5]))
+
+
+@pytest.mark.parametrize("summaries,overlap,ext", [("off", True, ".npz"), ("only", True, ".hd5"), ("on", False, ".npz")])
+def test_on_keeps_once_behind_the_reset_asks_twice_at_the_end_and_writes_the_datasets(tmp_path, summaries, overlap, ext):
+    if ext == ".hd5" and not hdf5io.available():
+        ext = ".npz"
+    nb, ns, D, probs = 3, 4, 3, (0.05, 0.5, 0.95)
+    cfg = dict(CFG, num_bursts=nb, num_burst_samples=ns, summaries=summaries, rt=D, rt_quantiles=list(probs))
+    s, files, log = _run(tmp_path, "on", cfg, ext=ext, cap=800 if overlap else ns)
+    names = [c[0] for c in s.calls]
+    # once, right behind the reset, with the number of draws the sampling phase keeps; nothing during the warm-up
+    assert names.count("keep_rt_draws") == 1 and names.count("reset_rt") == 1
+    r = names.index("reset_rt")
+    assert s.calls[r + 1] == ("keep_rt_draws", nb * ns)
+    assert not any(n in ("keep_rt_draws", "rt_quantiles", "rt") for n in names[:r])
+    # one per-chain and one pooled call, behind the last burst and the moments
+    asked = [c for c in s.calls if c[0] == "rt_quantiles"]
+    assert asked == [("rt_quantiles", probs, False), ("rt_quantiles", probs, True)]
+    last_burst = max(i for i, n in enumerate(names) if n in ("burst", "sample", "rt"))
+    assert names.index("rt_quantiles") > max(last_burst, names.index("rt_summary"))
+    # the files: the datasets of the same run without the key, plus the new ones
+    base, bf, blog = _run(tmp_path, "base", {k: v for k, v in cfg.items() if k != "rt_quantiles"}, ext=ext,
+                          cap=800 if overlap else ns)
+    assert [c[0] for c in s.calls if c[0] not in ("keep_rt_draws", "rt_quantiles")] == [c[0] for c in base.calls]
+    sweeps = (inf.warmup_size() + np.arange(nb * ns)).astype(np.float64)
+    want = np.quantile(sweeps, probs)
+    for c, f in enumerate(files):
+        assert set(f) == set(bf[c]) | NEW_SETS
+        for k in bf[c]:
+            assert np.array_equal(f[k], bf[c][k], equal_nan=True), k
+        assert np.array_equal(f["rt/quantile_probs"], probs) and f["rt/quantile_probs"].shape == (3,)
+        assert np.array_equal(f["rt/pooled_chains"], [6, 7])                  # the stub's first_chain_id = 6, global ids
+        own, pooled = f["rt/R_it_quantiles"], f["rt/pooled_R_it_quantiles"]
+        assert own.shape == pooled.shape == (3, D, s.M) and own.dtype == pooled.dtype == np.float64
+        assert np.array_equal(own, np.broadcast_to(want[:, None, None] + np.arange(D)[None, :, None] / 4.0, own.shape))
+        assert np.array_equal(pooled, own + 100.0)
+        # the national curve, on the host from samples/R_t by the same rank rule: np.quantile's values
+        r_t = f["samples/R_t"]                                                # [n, D]
+        assert f["rt/R_t_quantiles"].shape == f["rt/pooled_R_t_quantiles"].shape == (3, D)
+        np.testing.assert_allclose(f["rt/R_t_quantiles"], np.quantile(r_t, probs, axis=0), rtol=1e-12, atol=0)
+        np.testing.assert_allclose(f["rt/pooled_R_t_quantiles"], np.quantile(np.concatenate([r_t] * s.B), probs, axis=0),
+                                   rtol=1e-12, atol=0)
+    assert log.count("R_t quantiles:") == 1 and "0.05, 0.5, 0.95" in log and "excludes 1 in 100.0 % of the locations" in log
+    assert [ln for ln in _untimed(log) if not ln.startswith("R_t quantiles:")] == _untimed(blog)      # one line more
+
+
+def test_draw_quantiles_equal_numpy_quantile():
+    rng = np.random.default_rng(3)
+    for n in (1, 2, 7, 100):
+        x = rng.gamma(2.0, 0.6, size=(n, 2, 5))
+        probs = (0.0, 0.05, 1.0 / 3.0, 0.5, 0.95, 1.0)
+        np.testing.assert_allclose(inf.draw_quantiles(x, probs), np.quantile(x, probs, axis=0), rtol=1e-12, atol=0)
+    assert Q.MAX_PROBS == 8
+
+
+# ---- 5. the compiler's account of the new kernels --------------------------------------------------------------------------
+def test_the_new_kernels_have_an_account_of_their_own_and_the_other_four_are_the_parents():
+    entry.build()
+    res = json.load(open(entry.RESOURCES_RTQ))
+    new = ["k_order_stats_f64<1>", "k_order_stats_f64<4>", "k_rt_trace_keep<4>"]
+    assert sorted(res) == new, sorted(res)
+    assert res == json.load(open(os.path.join(ROOT, "profiles", "r16_rtq_kernels.json")))
+    for k in new:
+        assert res[k]["scratch_bytes_per_lane"] == 0 and res[k]["vgpr_spill"] == 0 and res[k]["sgpr_spill"] == 0, (k, res[k])
+    # k_order_stats_f64: 16 histograms of 256 bins and the ranks' state (two 64-bit prefixes, rank, group: 16 each)
+    for k in new[:2]:
+        assert 16 * 256 * 4 <= res[k]["lds_bytes_per_block"] <= 16 * 256 * 4 + 16 * (8 + 8 + 4 + 4) + 16, (k, res[k])
+    # k_rt_trace_keep stages in registers: no static LDS, k_rt_trace's dynamic part.  The four staged draws cost it one
+    # workgroup per CU against k_rt_trace (four waves per SIMD, not five); at UK-380 x 8 chains x 14 days the grid is 192
+    # workgroups on 256 CUs, so four to a CU bounds nothing there -- fewer than four would mean that something else grew
+    assert res["k_rt_trace_keep<4>"]["lds_bytes_per_block"] == 0
+    assert res["k_rt_trace_keep<4>"]["occupancy_waves_per_simd"] >= 4
+    # the other four accounts hold none of the new kernels and are the parent's, instance for instance
+    for path, committed in ((entry.RESOURCES, "r13_kernel_resources.json"), (entry.RESOURCES_ADDED, "r13_added_kernels.json"),
+                            (entry.RESOURCES_SELFTEST, "r14_selftest_kernels.json"), (entry.RESOURCES_WB, "r15_wb_kernels.json")):
+        got = json.load(open(path))
+        assert not any(k.split("<")[0] in entry.RTQ_KERNELS for k in got)
+        assert got == json.load(open(os.path.join(ROOT, "profiles", committed))), committed
+    whole = dict(json.load(open(entry.RESOURCES)), **json.load(open(entry.RESOURCES_ADDED)), **res,
+                 **json.load(open(entry.RESOURCES_SELFTEST)), **json.load(open(entry.RESOURCES_WB)))
+    assert entry.split_resources(whole) == (json.load(open(entry.RESOURCES)), json.load(open(entry.RESOURCES_ADDED)))
+    assert entry.rtq_resources(whole) == res and entry.wb_resources(whole) == json.load(open(entry.RESOURCES_WB))
