@@ -71,6 +71,7 @@ FORECAST_MAX_H = 128          # SEIR_FORECAST_MAX_H
 FORECAST_ID_SHIFT, FORECAST_MAX_CHAIN = 20, 2048   # draw id = (global chain id << 20) + j
 CHECK_MAX_DAYS = 128          # SEIR_CHECK_MAX_DAYS
 ORDER_STATS_MAX_RANKS = 16    # SEIR_ORDER_STATS_MAX_RANKS
+GROUPS_MAX = 256              # SEIR_GROUPS_MAX
 # SEIR_FN_*: the functions of seir_selftest_fn, name -> (op, takes y, has out1)
 SELFTEST_FN = {"fast_log": (0, False, False), "fast_rcp": (1, False, False), "mv_log": (2, False, False),
                "softplus_tab": (3, False, False), "softplus_sigmoid_tab": (4, False, True), "softplus": (5, False, False),
@@ -236,6 +237,16 @@ _SIGNATURES = {
     "seir_sampler_read_wb_draws": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, c_double_p, c_double_p]),
     "seir_sampler_read_wb_draws_async": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, c_double_p,
                                                         c_double_p]),
+    # region totals: per-draw sums over groups of locations (trace, forecast, check); the kernel alone on host arrays
+    "seir_sampler_groups_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                               ctypes.POINTER(ctypes.c_int32)]),
+    "seir_sampler_read_group_marginals": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                         c_int64_p, c_int64_p]),
+    "seir_sampler_read_group_marginals_async": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                               c_int64_p, c_int64_p]),
+    "seir_group_sums": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, ctypes.c_int32,
+                                       ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                       ctypes.POINTER(ctypes.c_int32), c_int64_p]),
 }
 
 _lib = None

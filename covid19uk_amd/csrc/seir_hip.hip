@@ -28,6 +28,7 @@
 #include "order_stats_kernels.h"
 #include "order_stats64_kernels.h"
 #include "rt_keep_kernels.h"
+#include "group_kernels.h"
 
 using namespace seir;
 
@@ -1185,6 +1186,12 @@ static int acc_read(const MomentAcc &a, hipStream_t st, uint64_t *count, int32_t
     return 0;
 }
 
+// The per-slot group sums of one source (seir_sampler_groups_set): ev [cap][B][G][L][3], st0 [cap][B][G][3] (null for the trace).
+struct GroupOut {
+    int64_t *ev = nullptr, *st0 = nullptr;
+    int L = 0;                        // day extent the arrays are sized for; 0: none (no table, or the source is off)
+};
+
 // The host's half of a ForecastBufs that is rolled forward day by day from the kept draws (forecast_kernels.h): the forecast
 // and the in-sample check each own one (rollout_*, below).
 struct Rollout {
@@ -1292,6 +1299,10 @@ struct seir_sampler {
     int wb_slots = 0;                 // trace slots the batch planes (I, part) are allocated for
     std::vector<void *> wb_allocs;    // device buffers sized by the window (allocated again when it changes)
     Shadowed wb_acc;                  // sum_w | sumsq_w | ref_w | ref_b | sum_b [cells] | count [B, padded] | n [cells] | gt [cells]
+    // --- region totals of the kept draws (seir_sampler_groups_set ...; group_kernels.h) ---
+    bool grp_on = false;              // a table is set
+    GroupTable grp{};                 // its device copy: segments and members
+    GroupOut grp_out[3];              // per-slot outputs of the trace, the forecast and the check (L = 0: that source is off)
 };
 
 // Zeroed device memory, registered in `list` (seir_sampler::allocs: freed with the sampler; Rollout::allocs: also when the length
@@ -1323,6 +1334,18 @@ static int rollout_shadow(Rollout &r, int slot, bool save, hipStream_t st) {
     return acc_shadow(r.acc, slot, save, st);
 }
 
+static void groups_free(seir_sampler *s) {
+    for (GroupOut &o : s->grp_out) {
+        if (o.ev) (void)hipFree(o.ev);
+        if (o.st0) (void)hipFree(o.st0);
+        o = GroupOut{};
+    }
+    if (s->grp.seg) (void)hipFree(const_cast<int *>(s->grp.seg));
+    if (s->grp.members) (void)hipFree(const_cast<int *>(s->grp.members));
+    s->grp = GroupTable{};
+    s->grp_on = false;
+}
+
 static void drop_graph(seir_sampler *s) {
     for (auto &g : s->gexec) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     for (auto &g : s->graph) if (g) { (void)hipGraphDestroy(g); g = nullptr; }
@@ -1350,6 +1373,7 @@ extern "C" void seir_sampler_destroy(seir_sampler *s) {
     if (s->fc_steps_host) (void)hipHostFree(s->fc_steps_host);
     if (s->fc_keep) (void)hipFree(s->fc_keep);
     if (s->rt_keep) (void)hipFree(s->rt_keep);
+    groups_free(s);
     if (s->fc_ev_steps) (void)hipEventDestroy(s->fc_ev_steps);
     Work &w = s->ctx->w;
     for (int x = 0; x < 3; ++x) { w.K[x] = nullptr; w.St[x] = nullptr; }
@@ -2363,6 +2387,200 @@ static int read_marginals(seir_sampler *s, bool enabled, const TraceUser &what, 
 }
 
 // ---------------------------------------------------------------------------
+// Region totals on the device (include/seir_hip.h; kernel: group_kernels.h)
+// ---------------------------------------------------------------------------
+// The refusals of a table against M rows, and its cut into segments of at most GRP_SEG members (GroupTable::seg).
+static int groups_parse(int32_t G, const int32_t *offsets, const int32_t *members, int M, std::vector<int> &seg) {
+    if (G < 1 || G > GRP_MAX_G) return fail(SEIR_ERR_INVALID, "G=%d outside [1, %d]", G, GRP_MAX_G);
+    if (!offsets || !members) return fail(SEIR_ERR_INVALID, "null group table pointer");
+    if (offsets[0] != 0) return fail(SEIR_ERR_INVALID, "offsets[0]=%d: the table starts at 0", offsets[0]);
+    for (int g = 0; g < G; ++g) {
+        const int beg = offsets[g], end = offsets[g + 1];
+        if (end < beg) return fail(SEIR_ERR_INVALID, "offsets[%d]=%d below offsets[%d]=%d: offsets must not decrease", g + 1, end, g, beg);
+        if (end == beg) return fail(SEIR_ERR_INVALID, "group %d is empty", g);
+        if (end - beg > M) return fail(SEIR_ERR_INVALID, "group %d has %d members of M=%d locations: a member is repeated", g, end - beg, M);
+        for (int i = beg; i < end; ++i) {
+            if (members[i] < 0 || members[i] >= M)
+                return fail(SEIR_ERR_INVALID, "member %d of group %d outside [0, M=%d)", members[i], g, M);
+            if (i > beg && members[i] <= members[i - 1])
+                return fail(SEIR_ERR_INVALID, "group %d: member %d after %d: members must be ascending and unique", g, members[i],
+                            members[i - 1]);
+        }
+        for (int b = beg; b < end; b += GRP_SEG) {
+            seg.push_back(g); seg.push_back(b); seg.push_back(std::min(end, b + GRP_SEG));
+        }
+    }
+    return 0;
+}
+
+// nd draws of ev [.][M][L][3] from draw ev_d0 onto out / state0 from draw out_d0, which the caller has zeroed (the kernel adds).
+// Defined at the end of this file: it is the one place that names k_group_sums, and a kernel template is emitted where it is
+// first named -- behind every kernel the parent had, whose places in the code object then stay what they were.
+static void groups_launch(const Dims &d, hipStream_t st, const GroupTable &gt, bool ev16, const void *ev, int M, int L,
+                          long long ev_d0, long long out_d0, long long nd, int64_t *out, const int *St0, long long plane, int ndp,
+                          int64_t *state0);
+
+// The day extent of source `which` (0 trace, 1 forecast, 2 check) while it is on, else 0.
+static int groups_source_len(const seir_sampler *s, int which) {
+    if (which == 0) return s->sum_on ? s->ctx->d.T : 0;
+    const Rollout &r = which == 1 ? s->fc : s->ck;
+    return r.on ? r.fb.H : 0;
+}
+
+// Bytes of the outputs of source `which` at G groups and L days, and the refusal above half of the device's free memory.
+static unsigned long long groups_bytes(const seir_sampler *s, int G, int which, int L) {
+    const unsigned long long rows = (unsigned long long)s->cfg.cap * s->cfg.B * G;
+    return rows * L * 3ull * 8ull + (which ? rows * 3ull * 8ull : 0ull);
+}
+static int groups_refuse_bytes(const seir_sampler *s, unsigned long long bytes, int G) {
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    // half of what is free: the policy of a device that is shared, not a measurement
+    if (bytes > (unsigned long long)free_b / 2)
+        return fail(SEIR_ERR_INVALID, "the group sums need %llu bytes (%d slots x %d chains x %d groups x 24 per day and per state), "
+                    "more than half of the %llu bytes free on the device", bytes, s->cfg.cap, s->cfg.B, G, (unsigned long long)free_b);
+    return 0;
+}
+
+// Size the outputs of source `which` for the table and the source's present length (none when either is off).
+static int groups_fit(seir_sampler *s, int which) {
+    GroupOut &o = s->grp_out[which];
+    const int L = s->grp_on ? groups_source_len(s, which) : 0;
+    if (L == o.L) return 0;
+    if (int rc = drain(s)) return rc;
+    if (o.ev) (void)hipFree(o.ev);
+    if (o.st0) (void)hipFree(o.st0);
+    o = GroupOut{};
+    if (L == 0) return 0;
+    const unsigned long long rows = (unsigned long long)s->cfg.cap * s->cfg.B * s->grp.G;
+    const unsigned long long bytes = groups_bytes(s, s->grp.G, which, L);
+    if (int rc = groups_refuse_bytes(s, bytes, s->grp.G)) return rc;
+    // both arrays or neither: a source whose outputs could not be made has none (L = 0) and is not launched for
+    void *ev = nullptr, *st0 = nullptr;
+    const size_t ev_bytes = (size_t)(rows * L * 3ull * 8ull), st_bytes = (size_t)(rows * 3ull * 8ull);
+    hipError_t e = hipMalloc(&ev, ev_bytes);
+    if (e == hipSuccess) e = hipMemset(ev, 0, ev_bytes);
+    if (e == hipSuccess && which) e = hipMalloc(&st0, st_bytes);
+    if (e == hipSuccess && which) e = hipMemset(st0, 0, st_bytes);
+    if (e != hipSuccess) {
+        if (ev) (void)hipFree(ev);
+        if (st0) (void)hipFree(st0);
+        return fail(SEIR_ERR_DEVICE, "allocating %llu bytes of group sums failed: %s", bytes, hipGetErrorString(e));
+    }
+    o.ev = (int64_t *)ev; o.st0 = (int64_t *)st0; o.L = L;
+    return 0;
+}
+
+// Source `which` forms group sums: a table is set and the source's outputs exist (a refused or failed groups_fit leaves none).
+static bool groups_live(const seir_sampler *s, int which) { return s->grp_on && s->grp_out[which].L != 0; }
+
+// The kernel adds: the outputs of slots [first, first + count) of source `which` start from zero.  In stream order.
+static int groups_zero(seir_sampler *s, int which, int32_t first, int32_t count) {
+    const GroupOut &o = s->grp_out[which];
+    const size_t row = (size_t)s->cfg.B * s->grp.G;
+    HIP_TRY(hipMemsetAsync(o.ev + (size_t)first * row * o.L * 3, 0, sizeof(int64_t) * count * row * o.L * 3, s->ctx->stream));
+    if (o.st0) HIP_TRY(hipMemsetAsync(o.st0 + (size_t)first * row * 3, 0, sizeof(int64_t) * count * row * 3, s->ctx->stream));
+    return 0;
+}
+
+extern "C" int seir_sampler_groups_set(seir_sampler *s, int32_t G, const int32_t *offsets, const int32_t *members) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if (G == 0) {
+        if ((rc = drain(s))) return rc;
+        groups_free(s);
+        return 0;
+    }
+    if ((rc = need_events(s, "sum over groups of locations"))) return rc;
+    std::vector<int> seg;
+    if ((rc = groups_parse(G, offsets, members, s->ctx->d.M, seg))) return rc;
+    // what the sources that are on need, against the free memory as it is with the old table's outputs still there
+    // (conservative), and the new table's device copy: a refusal or failure here leaves the table in force alone
+    unsigned long long need = 0;
+    for (int which = 0; which < 3; ++which)
+        if (const int L = groups_source_len(s, which)) need += groups_bytes(s, G, which, L);
+    if ((rc = groups_refuse_bytes(s, need, G))) return rc;
+    DevBuf dseg, dmem;
+    const size_t nnz = (size_t)offsets[G];
+    if ((rc = dseg.alloc(seg.size() * sizeof(int))) || (rc = dmem.alloc(nnz * sizeof(int)))) return rc;
+    HIP_TRY(hipMemcpy(dseg.p, seg.data(), seg.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dmem.p, members, nnz * sizeof(int), hipMemcpyHostToDevice));
+    if ((rc = drain(s))) return rc;
+    groups_free(s);
+    s->grp.seg = dseg.as<int>(); s->grp.members = dmem.as<int>();
+    dseg.p = dmem.p = nullptr;                       // the sampler owns them now
+    s->grp.nseg = (int)(seg.size() / 3);
+    s->grp.G = G;
+    s->grp_on = true;
+    for (int which = 0; which < 3; ++which)
+        if ((rc = groups_fit(s, which))) { groups_free(s); return rc; }
+    return 0;
+}
+
+static int copy_group_marginals(seir_sampler *s, hipStream_t st, int which, int32_t first, int32_t count, int64_t *ev, int64_t *st0) {
+    const GroupOut &o = s->grp_out[which];
+    const size_t row = (size_t)s->cfg.B * s->grp.G, f = (size_t)first, n = (size_t)count;
+    if (ev) HIP_TRY(hipMemcpyAsync(ev, o.ev + f * row * o.L * 3, sizeof(int64_t) * n * row * o.L * 3, hipMemcpyDeviceToHost, st));
+    if (st0) HIP_TRY(hipMemcpyAsync(st0, o.st0 + f * row * 3, sizeof(int64_t) * n * row * 3, hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+static int read_group_marginals(seir_sampler *s, bool async, int32_t which, int32_t first, int32_t count, int64_t *ev, int64_t *st0) {
+    if (int rc = sampler_check(s)) return rc;
+    if (which < 0 || which > 2) return fail(SEIR_ERR_INVALID, "which=%d: 0 trace, 1 forecast, 2 check", which);
+    if (int rc = need_events(s, "sum over groups of locations")) return rc;
+    if (!s->grp_on) return fail(SEIR_ERR_STATE, "no group table is set: call seir_sampler_groups_set first");
+    if (s->grp_out[which].L == 0)
+        return fail(SEIR_ERR_STATE, "%s", which == 0 ? SUMMARY_USER.not_enabled : which == 1 ? FORECAST_USER.not_enabled
+                                                                                             : CHECK_USER.not_enabled);
+    if (first < 0 || count < 0 || (long long)first + count > s->cfg.cap)
+        return fail(SEIR_ERR_INVALID, "trace range [%d,%lld) outside capacity %d", first, (long long)first + count, s->cfg.cap);
+    if (which == 0 && st0)
+        return fail(SEIR_ERR_INVALID, "the trace has no per-draw state0: it is the context's initial state summed over the members");
+    if (async) return on_copy_stream(s, [&](hipStream_t st) { return copy_group_marginals(s, st, which, first, count, ev, st0); });
+    if (int rc = copy_group_marginals(s, s->ctx->stream, which, first, count, ev, st0)) return rc;
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    return check_ev_overflow(s);
+}
+
+extern "C" int seir_sampler_read_group_marginals(seir_sampler *s, int32_t which, int32_t first, int32_t count,
+                                                 int64_t *events_by_group, int64_t *state0_by_group) {
+    return read_group_marginals(s, false, which, first, count, events_by_group, state0_by_group);
+}
+
+extern "C" int seir_sampler_read_group_marginals_async(seir_sampler *s, int32_t which, int32_t first, int32_t count,
+                                                       int64_t *events_by_group, int64_t *state0_by_group) {
+    return read_group_marginals(s, true, which, first, count, events_by_group, state0_by_group);
+}
+
+extern "C" int seir_group_sums(seir_ctx *ctx, const int32_t *events, int64_t n, int32_t M, int32_t L, int32_t G,
+                               const int32_t *offsets, const int32_t *members, int64_t *out) {
+    int rc = check_batch(ctx, 1);
+    if (rc) return rc;
+    if (!events || !out) return fail(SEIR_ERR_INVALID, "null pointer");
+    if (n < 1 || M < 1 || L < 1 || n > 0x7fffffffll)
+        return fail(SEIR_ERR_INVALID, "n=%lld, M=%d, L=%d: at least one of each, n below 2^31", (long long)n, M, L);
+    std::vector<int> seg;
+    if ((rc = groups_parse(G, offsets, members, M, seg))) return rc;
+    const size_t nin = (size_t)n * M * L * 3, nout = (size_t)n * G * L * 3, nnz = (size_t)offsets[G];
+    DevBuf dev, dout, dseg, dmem;
+    if ((rc = dev.alloc(sizeof(int32_t) * nin)) || (rc = dout.alloc(sizeof(int64_t) * nout)) ||
+        (rc = dseg.alloc(sizeof(int) * seg.size())) || (rc = dmem.alloc(sizeof(int) * nnz)))
+        return rc;
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(dev.p, events, sizeof(int32_t) * nin, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dseg.p, seg.data(), sizeof(int) * seg.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dmem.p, members, sizeof(int) * nnz, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(dout.p, 0, sizeof(int64_t) * nout, st));
+    const GroupTable gt{dseg.as<int>(), dmem.as<int>(), (int)(seg.size() / 3), G};
+    groups_launch(whole(ctx, 1).d, st, gt, false, dev.p, M, L, 0, 0, n, dout.as<int64_t>(), nullptr, 0, 0, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, dout.p, sizeof(int64_t) * nout, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
 // Summaries of the recorded events (include/seir_hip.h; kernels: summary_kernels.h)
 // ---------------------------------------------------------------------------
 extern "C" int seir_sampler_summary_reset(seir_sampler *s) {
@@ -2382,7 +2600,8 @@ extern "C" int seir_sampler_summary_reset(seir_sampler *s) {
     hipStream_t st = s->ctx->stream;
     if ((rc = acc_zero(s->sum_acc, st))) return rc;
     // the batch sums are about the same ref and the marks are copies of these accumulators: they start again with them
-    return s->diag_on ? acc_zero(s->diag_buf, st) : 0;
+    if (s->diag_on && (rc = acc_zero(s->diag_buf, st))) return rc;
+    return s->grp_on ? groups_fit(s, 0) : 0;
 }
 
 extern "C" int seir_sampler_summarize(seir_sampler *s, int32_t first, int32_t count, int32_t accumulate) {
@@ -2415,6 +2634,11 @@ extern "C" int seir_sampler_summarize(seir_sampler *s, int32_t first, int32_t co
                                first + j0, nj, accumulate != 0, SummaryDiag<0>{});
         hipLaunchKernelGGL(k_summary_finish, dim3(nj, B), dim3(64), 0, l.st, d, ctx->c, s->sum, B, first + j0, nj,
                            accumulate != 0);
+    }
+    if (groups_live(s, 0)) {                         // the region totals of the same slots
+        if ((rc = groups_zero(s, 0, first, count))) return rc;
+        groups_launch(d, l.st, s->grp, s->cfg.ev16 != 0, s->ch.tr_events, d.M, d.T, (long long)first * B, (long long)first * B,
+                      (long long)count * B, s->grp_out[0].ev, nullptr, 0, 0, nullptr);
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -2609,6 +2833,14 @@ static int rollout_ids_left(const Rollout &r, const TraceUser &who, int32_t coun
 // Trace slots [first + j0, first + j0 + nj) of a call: ND = nj * B draws, the planes' row stride ndp = ceil64(ND).
 struct RolloutBatch { int j0, nj, ND, ndp; };
 
+// A batch of a Rollout (forecast: which = 1, check: 2) behind its fold: the staging tensor and the per-draw initial state.
+static void groups_rollout_batch(seir_sampler *s, int which, const Dims &d, hipStream_t st, const ForecastBufs &fb, int32_t first,
+                                 const RolloutBatch &bt) {
+    const GroupOut &o = s->grp_out[which];
+    groups_launch(d, st, s->grp, false, fb.fev, d.M, fb.H, 0, (long long)(first + bt.j0) * s->cfg.B, bt.ND, o.ev, fb.St0,
+                  (long long)d.Mp * bt.ndp, bt.ndp, o.st0);
+}
+
 // The draws of trace slots [first, first + count) rolled forward fb.H days, in batches of at most r.slots slots.  Per batch:
 // prepare(fb, batch) -- the user's prepare kernel on the batch's copy of r.fb, which it may amend first -- then per day the
 // contraction and k_forecast_day, then k_forecast_fold, then after_fold(fb, batch).  The draw of slot first + jj has
@@ -2663,7 +2895,8 @@ extern "C" int seir_sampler_forecast_reset(seir_sampler *s, int32_t horizon, con
         if (!s->fc_ev_steps) HIP_TRY(hipEventCreate(&s->fc_ev_steps));
         r.on = true;
     }
-    return rollout_begin(s, r, W, weekday_c, seed);  // j = 0 empties the draw store too: it holds draws [0, j)
+    if ((rc = rollout_begin(s, r, W, weekday_c, seed))) return rc;   // j = 0 empties the draw store too: it holds draws [0, j)
+    return s->grp_on ? groups_fit(s, 1) : 0;
 }
 
 extern "C" int seir_sampler_forecast(seir_sampler *s, int32_t first, int32_t count, const double *log_baseline_steps) {
@@ -2680,6 +2913,7 @@ extern "C" int seir_sampler_forecast(seir_sampler *s, int32_t first, int32_t cou
     const LaunchCfg l = whole(ctx, s->cfg.B);
     const Dims &d = l.d;
     const int B = s->cfg.B, H = r.fb.H;
+    if (groups_live(s, 1) && (rc = groups_zero(s, 1, first, count))) return rc;
     if (log_baseline_steps) {
         // through page-locked memory indexed by trace slot, so that the call stays asynchronous; a slot's steps are
         // overwritten only once the upload that read them last has been done
@@ -2705,6 +2939,7 @@ extern "C" int seir_sampler_forecast(seir_sampler *s, int32_t first, int32_t cou
                                    (const int *)fb.fev, (const int *)(fb.St0 + 2 * (size_t)d.Mp * bt.ndp), s->fc_keep,
                                    s->fc_keep_cap, r.j + bt.j0, H, B, bt.nj, bt.ndp);
             hipLaunchKernelGGL(k_forecast_finish, dim3(bt.nj, B), dim3(64), 0, l.st, d, fb, B, first + bt.j0, bt.nj, bt.ndp);
+            if (groups_live(s, 1)) groups_rollout_batch(s, 1, d, l.st, fb, first, bt);
         });
     if (rc) return rc;
     if (log_baseline_steps) { HIP_TRY(hipEventRecord(s->fc_ev_steps, l.st)); s->fc_steps_pending = true; }
@@ -2898,7 +3133,7 @@ extern "C" int seir_sampler_check_reset(seir_sampler *s, int32_t days, const dou
     if ((rc = acc_zero(s->ck_cnt, s->ctx->stream))) return rc;
     if ((rc = rollout_begin(s, r, W, weekday_c, seed))) return rc;
     acc_invalidate(s->ck_cnt);                       // dropped from the snapshots with the moments
-    return 0;
+    return s->grp_on ? groups_fit(s, 2) : 0;
 }
 
 extern "C" int seir_sampler_check(seir_sampler *s, int32_t first, int32_t count) {
@@ -2913,6 +3148,7 @@ extern "C" int seir_sampler_check(seir_sampler *s, int32_t first, int32_t count)
     const Dims &d = l.d;
     const int B = s->cfg.B;
     const dim3 rgrid((d.M + FC_ROWS - 1) / FC_ROWS, B), rblock(64 * FC_ROWS);
+    if (groups_live(s, 2) && (rc = groups_zero(s, 2, first, count))) return rc;
     rc = rollout_days(s, r, first, count,
         [&](ForecastBufs &fb, const RolloutBatch &bt) {
             hipLaunchKernelGGL(s->cfg.ev16 ? k_check_prepare<1> : k_check_prepare<0>, dim3(d.Mp / FC_ROWS, bt.ndp), rblock, 0,
@@ -2926,6 +3162,7 @@ extern "C" int seir_sampler_check(seir_sampler *s, int32_t first, int32_t count)
             hipLaunchKernelGGL(s->cfg.ev16 ? k_check_compare<1> : k_check_compare<0>, rgrid, rblock, 0, l.st, d, fb, s->ck_cmp,
                                (const void *)s->ch.tr_events, B, first + bt.j0, bt.nj, fresh);
             hipLaunchKernelGGL(k_check_totals, dim3(B), dim3(CK_TOT_THREADS), 0, l.st, d, fb, s->ck_cmp, B, first + bt.j0, bt.nj);
+            if (groups_live(s, 2)) groups_rollout_batch(s, 2, d, l.st, fb, first, bt);
         });
     if (rc) return rc;
     HIP_TRY(hipGetLastError());
@@ -3500,3 +3737,17 @@ extern "C" int seir_sampler_debug_hs(seir_sampler *s, double *out) {
     return 0;
 }
 #endif
+
+// ===========================================================================
+// Region totals: the launch (declared above, with the rest of seir_sampler_groups_*)
+// ===========================================================================
+static void groups_launch(const Dims &d, hipStream_t st, const GroupTable &gt, bool ev16, const void *ev, int M, int L,
+                          long long ev_d0, long long out_d0, long long nd, int64_t *out, const int *St0, long long plane, int ndp,
+                          int64_t *state0) {
+    const int nchunk = (L + 63) / 64;
+    for (long long off = 0; off < nd; off += GRP_NDMAX) {
+        const dim3 grid((unsigned)(gt.nseg * nchunk), (unsigned)std::min<long long>(GRP_NDMAX, nd - off)), block(64 * GRP_WAVES);
+        hipLaunchKernelGGL(ev16 ? k_group_sums<1> : k_group_sums<0>, grid, block, 0, st, d, gt, ev, M, L, nchunk, ev_d0 + off,
+                           out_d0 + off, (unsigned long long *)out, St0, plane, ndp, (unsigned long long *)state0);
+    }
+}

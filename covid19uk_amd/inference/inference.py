@@ -20,6 +20,7 @@ import numpy as np
 from .. import hdf5io
 from .. import model_spec
 from ..posterior import diagnostics as diag_mod
+from ..posterior import groups as G_mod
 from ..sampler import MOVE_KEYS, ChainSampler, Summary, mid_p
 from ..seir import SeirModel
 from .mcmc_kernel_factory import event_kernel_config, hmc_kernel_kwargs_default
@@ -63,8 +64,9 @@ def read_inference_data(path):
     return cov, cases, dates
 
 
-def write_inference_data(path, cov: model_spec.Covariates, cases, dates=None):
-    """Write an input file with the layout `read_inference_data` expects (tests, synthetic runs)."""
+def write_inference_data(path, cov: model_spec.Covariates, cases, dates=None, locations=None):
+    """Write an input file with the layout `read_inference_data` expects (tests, synthetic runs).  `locations` [M] of str
+    (an .hd5 file only): the `location` coordinate that `read_location_names` returns."""
     cases = np.asarray(cases, DTYPE)
     dates = [str(i) for i in range(cases.shape[1])] if dates is None else list(dates)
     if str(path).endswith(".npz"):
@@ -81,6 +83,10 @@ def write_inference_data(path, cov: model_spec.Covariates, cases, dates=None):
         n = max(len(s) for s in dates)
         f.create_dataset("/observations/time", (len(dates),), f"S{n}")
         f.write("/observations/time", np.array(dates, dtype=f"S{n}"))
+        if locations is not None:
+            n = max(len(str(x)) for x in locations)
+            f.create_dataset("/constant_data/location", (len(locations),), f"S{n}")
+            f.write("/constant_data/location", np.array([str(x) for x in locations], dtype=f"S{n}"))
 
 
 def read_location_names(path):
@@ -107,7 +113,7 @@ class Posterior:
     the int8 enum {FALSE = 0, TRUE = 1}."""
 
     def __init__(self, filename, M, T, mmax, num_samples, burst=100, summaries="off", forecast=None, rt=None, check=None,
-                 within_between=None):
+                 within_between=None, groups=None):
         """`summaries` ("off" | "on" | "only", Mcmc.summaries / --summaries): with "on" and "only" the per-draw marginals
         samples/seir_by_day [n,T,3], samples/seir_by_location [n,M,3], samples/state_by_day [n,T,3] (int64) are written
         with every burst and `write_summary` adds summaries/* at the end of the run; with "only" samples/seir is not
@@ -127,7 +133,13 @@ class Posterior:
         `within_between` ((D, n) or None, Mcmc.within_between / --within-between): samples/within_pressure and
         samples/between_pressure [n,D] (float64), the national within- and between-location infection pressure of the last
         D days, one row per kept draw of the sampling phase, and `write_within_between` adds the group within_between/ at the
-        end of the run."""
+        end of the run.
+
+        `groups` (G or None, Mcmc.groups / --groups): the per-draw sums over G groups of locations (int64) of whichever
+        sources are on -- samples/seir_by_group [n,G,T,3] with `summaries` on / only (warm-up rows included, like
+        seir_by_day); samples/forecast_by_group [nf,G,H,3] and forecast_group_state0 [nf,G,3] with `forecast`;
+        samples/check_by_group [nf,G,K,3] and check_group_state0 [nf,G,3] with `check` -- and `write_groups`,
+        `write_group_forecast`, `write_group_check` add groups/* and the group_* datasets of forecast/ and check/."""
         self.filename = filename
         self.use_h5 = not str(filename).endswith(".npz") and hdf5io.available()
         self.shapes = {
@@ -166,6 +178,14 @@ class Posterior:
         if within_between is not None:
             for k in ("samples/within_pressure", "samples/between_pressure"):
                 self.shapes[k], self.rows[k] = (int(within_between[0]),), int(within_between[1])
+        if groups:
+            G = int(groups)
+            if summaries != "off":
+                self.shapes["samples/seir_by_group"], self.dtypes["samples/seir_by_group"] = (G, T, 3), np.int64
+            for src, spec in (("forecast", forecast), ("check", check)):
+                if spec is not None:
+                    for k, shp in ((f"samples/{src}_by_group", (G, int(spec[0]), 3)), (f"samples/{src}_group_state0", (G, 3))):
+                        self.shapes[k], self.dtypes[k], self.rows[k] = shp, np.int64, int(spec[1])
         self._scratch = {}
         if self.use_h5:
             self._file = hdf5io.File(filename, "w")
@@ -295,6 +315,30 @@ class Posterior:
         for k, v in (("defined", defined), ("within_mean", within_mean), ("within_var", within_var),
                      ("between_mean", between_mean), ("p_within_gt_between", p_within_gt_between)):
             self.create_dataset(f"within_between/{k}", np.ascontiguousarray(v, dtype=np.float64))
+
+    def write_groups(self, table, population, initial_state):
+        """The group groups/: names [G] (bytes), offsets [G+1] and members [nnz] (the CSR pair of `posterior.groups`),
+        population [G] and initial_state [G,4], the members' sums of N and of the run's initial state."""
+        n = max(len(x) for x in table.names)
+        self.create_dataset("groups/names", np.array([x.encode() for x in table.names], dtype=f"S{max(n, 1)}"))
+        self.create_dataset("groups/offsets", np.asarray(table.offsets, np.float64))
+        self.create_dataset("groups/members", np.asarray(table.members, np.float64))
+        self.create_dataset("groups/population", table.sum_rows(np.asarray(population, np.float64).reshape(-1)))
+        self.create_dataset("groups/initial_state", table.sum_rows(np.asarray(initial_state, np.float64)))
+
+    def write_group_forecast(self, seir_mean, state_mean, quantiles=None):
+        """forecast/group_seir_mean, group_state_mean [G,H,3] over this chain's draws; `quantiles` (or None): {plane:
+        (chain [K,G,H], pooled [K,G,H])} -> forecast/group_<plane>_quantiles and forecast/pooled_group_<plane>_quantiles."""
+        self.create_dataset("forecast/group_seir_mean", np.ascontiguousarray(seir_mean, dtype=np.float64))
+        self.create_dataset("forecast/group_state_mean", np.ascontiguousarray(state_mean, dtype=np.float64))
+        for name, (own, pooled) in (quantiles or {}).items():
+            self.create_dataset(f"forecast/group_{name}_quantiles", np.ascontiguousarray(own, dtype=np.float64))
+            self.create_dataset(f"forecast/pooled_group_{name}_quantiles", np.ascontiguousarray(pooled, dtype=np.float64))
+
+    def write_group_check(self, counts: dict):
+        """check/group_* of one chain (`posterior.groups.check_counts`): the raw counts and the mid-p values."""
+        for k, v in counts.items():
+            self.create_dataset(f"check/{k}", np.atleast_1d(np.asarray(v, np.float64)))
 
     def write_diagnostics(self, datasets: dict):
         """The group diagnostics/ of one chain (`posterior.diagnostics.chain_datasets`), float64."""
@@ -626,7 +670,7 @@ def diagnostics_marks(nb):
 
 
 def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_step_size=False, forecast_calendar=None,
-             seed=0, rt_weight=None, check_calendar=None):
+             seed=0, rt_weight=None, check_calendar=None, groups=None):
     """The windowed schedule of inference.py:303-470: fast 200, slow 25*2^k (k<6), fast 50,
     then num_bursts x num_burst_samples with the kernel fixed.  Every draw of the warm-up is
     written, as in the reference (its running variance is formed from every draw of a window);
@@ -658,7 +702,13 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
 
     With Mcmc.within_between = D (`within_between_mode`) the within/between pressure shares of every kept draw of the
     sampling phase over the last D days are formed and folded on the device, behind the burst's summary, forecast, R_t and
-    check.  The warm-up is not folded; without the key nothing of it is called."""
+    check.  The warm-up is not folded; without the key nothing of it is called.
+
+    With `groups` (a `posterior.groups.GroupTable`, Mcmc.groups resolved by `mcmc`; needs one of summaries on / only,
+    forecast, check) the table is set on the sampler once, before the first draw: from then on the summary, the forecast
+    and the check of every burst also form the draw's sums over each group's members on the device, and these cross with
+    the trace.  In the warm-up that rides on the summary which `summaries` already asks for there, and on nothing else.
+    The statistics are formed here (`posterior.groups`).  Without it nothing of it is called."""
     thin = thin_interval(config)
     wb_days = within_between_mode(config, T=getattr(sampler, "T", None))
     check_days = check_mode(config, T=getattr(sampler, "T", None))
@@ -684,6 +734,16 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
         burst_kw = dict(events=summaries != "only", summarize=True)
         marks = diagnostics_marks(int(config["num_bursts"]))
         theta_acc = diag_mod.DrawAccumulator(batch_len)
+    grp_fc, grp_ck = [], []                                 # the sampling phase's group sums, kept for the statistics
+    if groups is not None:
+        G_mod.require_source(groups, summaries, horizon, check_days)
+        sampler.set_groups(groups.offsets, groups.members)  # once; the sources size their outputs at their resets
+        # the sources whose sums are written: the trace's only with summaries on / only (diagnostics alone also summarises
+        # every burst, but nothing of it goes to the file)
+        grp_src = tuple(k for k, on in (("trace", summaries != "off"), ("forecast", horizon), ("check", check_days)) if on)
+        if summaries != "off":
+            warm_kw = dict(warm_kw, groups=("trace",))
+        burst_kw = dict(burst_kw, groups=grp_src)
     sampler.set_thin(1)
     first_window_size, last_window_size, slow_window_size, num_slow_windows = 200, 50, 25, 6
     dual_averaging_kwargs = {"target_accept_prob": 0.75}
@@ -698,6 +758,17 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     def flush(tr):
         nonlocal offset, fc_offset, rt_offset, ck_offset, wb_offset
         n = tr.theta.shape[0]
+        if groups is not None and getattr(tr, "groups", None) is not None:
+            g = {k: np.array(v) for k, v in tr.groups.items()}   # the pinned buffer is used again two bursts later
+            if "forecast_by_group" in g:
+                grp_fc.append((g["forecast_by_group"], g["forecast_group_state0"]))
+            if "check_by_group" in g:
+                grp_ck.append(g["check_by_group"])
+            for c, post in enumerate(posteriors):
+                if "seir_by_group" in g:
+                    post.write_samples({"seir_by_group": g["seir_by_group"][:, c]}, first_dim_offset=offset)
+                post.write_samples({k: v[:, c] for k, v in g.items() if k.startswith("forecast_")}, first_dim_offset=fc_offset)
+                post.write_samples({k: v[:, c] for k, v in g.items() if k.startswith("check_")}, first_dim_offset=ck_offset)
         if wb_days and getattr(tr, "wb", None) is not None:
             w = {k: np.array(v) for k, v in tr.wb.items()}  # the pinned buffer is used again two bursts later
             wb_draws.append(w)
@@ -857,6 +928,27 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
         for c, post in enumerate(posteriors):
             post.write_check(check_days, sampler.T - check_days, cs.count[c], mean[c], var[c], check_chain_datasets(cs, c))
         print(check_run_line(check_days, sampler.T, cs), file=log, flush=True)
+    if groups is not None:
+        if horizon and grp_fc:
+            ev = np.concatenate([x[0] for x in grp_fc])     # [nf,B,G,H,3]
+            st0 = np.concatenate([x[1] for x in grp_fc])    # [nf,B,G,3]
+            state = G_mod.group_state(ev, st0)
+            q = None
+            if fq_probs:
+                planes = G_mod.forecast_planes(ev, st0)     # [3,nf,B,G,H]
+                q = {name: (G_mod.quantiles(planes[x], fq_probs),                                    # [K,B,G,H]
+                            G_mod.quantiles(planes[x].reshape((-1,) + planes.shape[3:]), fq_probs))   # [K,G,H]
+                     for x, name in enumerate(G_mod.PLANES)}
+            for c, post in enumerate(posteriors):
+                post.write_group_forecast(ev[:, c].mean(axis=0), state[:, c].mean(axis=0),
+                                          None if q is None else {k: (v[0][:, c], v[1]) for k, v in q.items()})
+        if check_days and grp_ck:
+            sim = np.concatenate(grp_ck)                    # [nf,B,G,K,3]
+            for c, post in enumerate(posteriors):
+                post.write_group_check(G_mod.check_counts(sim[:, c], groups.sum_rows(cs.observed[c])))
+        sources = [k for k, on in (("the recorded epidemic", summaries != "off"), ("the forecast", horizon), ("the check", check_days))
+                   if on]
+        print(G_mod.run_line(groups, sources), file=log, flush=True)
     if wb_days:
         ws = sampler.within_between_summary()
         wm, wv, bm, pg = ws.within_mean, ws.within_var, ws.between_mean, ws.p_within_gt_between
@@ -932,7 +1024,7 @@ def launch_forms(lay, device_arg, hmc="auto", moves="auto", env=os.environ):
 def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool_step_size=False, init_jitter=0.0,
          events_dtype="auto", hmc="auto", moves="auto", thin=None, summaries=None, diagnostics=None, diagnostics_batch=None,
          forecast=None, forecast_walk=None, rt=None, check=None, forecast_quantiles=None, within_between=None,
-         rt_quantiles=None):
+         rt_quantiles=None, groups=None):
     """Constructs and runs the MCMC (covid19uk/inference/inference.py:473-608).
 
     Multi-GPU: launched as one process per GPU, every rank runs `num_chains` chains with
@@ -944,7 +1036,8 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     config["diagnostics_batch"] (`diagnostics_mode`), `forecast` / `forecast_walk` config["forecast"] /
     config["forecast_walk"] (`forecast_mode`), `forecast_quantiles` config["forecast_quantiles"]
     (`forecast_quantiles_mode`), `rt` config["rt"] (`rt_mode`), `check` config["check"] (`check_mode`), `within_between`
-    config["within_between"] (`within_between_mode`), `rt_quantiles` config["rt_quantiles"] (`rt_quantiles_mode`)."""
+    config["within_between"] (`within_between_mode`), `rt_quantiles` config["rt_quantiles"] (`rt_quantiles_mode`), `groups`
+    config["groups"] (`posterior.groups.parse_groups`: "nations" or a mapping name -> members)."""
     wb_days = 0
     if within_between is not None or "within_between" in config:
         wb_days = within_between_mode(config, within_between)   # refused here: before any GPU call
@@ -984,8 +1077,15 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     if diagnostics is not None or diagnostics_batch is not None or "diagnostics" in config or "diagnostics_batch" in config:
         mode, batch_len = diagnostics_mode(config, diagnostics, diagnostics_batch)   # and too few bursts, or a batch length that does not fit
         config = dict(config, diagnostics=mode, **(dict(diagnostics_batch=batch_len) if mode == "on" else {}))
+    group_spec = config.get("groups") if groups is None else groups
+    config = {k: v for k, v in config.items() if k != "groups"}
     lay = job_layout(num_chains, device)                    # before any GPU call
     cov, cases, dates = read_inference_data(data_file)
+    # the table against the input's locations, and groups without a source: refused here, before any GPU call
+    group_table = None
+    if not G_mod.is_off(group_spec):                        # absent: the input's location coordinate is not even opened
+        group_table = G_mod.parse_groups(group_spec, cases.shape[0], read_location_names(data_file))
+    G_mod.require_source(group_table, config["summaries"], horizon, check_days)
     rng = np.random.default_rng(seed)                       # same imputation on every rank: one initial state per job
     B = int(num_chains)
     initial_state, events = model_spec.initial_conditions(cases, cov.N, rng)
@@ -1033,7 +1133,8 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
                             **(dict(rt=(rt_days, int(config["num_burst_samples"]) * int(config["num_bursts"]))) if rt_days else {}),
                             **(dict(check=(check_days, int(config["num_burst_samples"]) * int(config["num_bursts"]))) if check_days else {}),
                             **(dict(within_between=(wb_days, int(config["num_burst_samples"]) * int(config["num_bursts"])))
-                               if wb_days else {}))
+                               if wb_days else {}),
+                            **(dict(groups=group_table.G) if group_table is not None else {}))
                   for name in names]
     fc_kw = {}
     if horizon:
@@ -1046,6 +1147,10 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
         from ..posterior.predict import check_calendar
         fc_kw["check_calendar"] = check_calendar(cov, dates, T, check_days)
         fc_kw["seed"] = seed
+    if group_table is not None:
+        fc_kw["groups"] = group_table
+        for post in posteriors:
+            post.write_groups(group_table, cov.N, initial_state)
     run_mcmc(sampler, config, posteriors, pool_step_size=pool_step_size and total > 1, **fc_kw)
     if sampler.recoveries:
         print(f"{len(sampler.recoveries)} burst(s) were run again after a hand-off time-out (shared GPU?)", flush=True)
@@ -1147,6 +1252,13 @@ def main(argv=None):
                              "mean of the between share and P(within > between) per day and location, and the national "
                              "pressures per draw samples/within_pressure, between_pressure; works with --summaries only, "
                              "--thin, --forecast, --rt and --check")
+    parser.add_argument("--groups", type=str, default=None, metavar="SPEC",
+                        help="per-draw totals over groups of locations, formed on the device for the recorded epidemic "
+                             "(--summaries on/only), the forecast and the check (overrides Mcmc.groups; default off): "
+                             "'nations' groups by the first letter of the location code (needs an input file with a location "
+                             "coordinate), or a path to a YAML mapping name: [members], a member being a location code, a "
+                             "prefix pattern E0* or an integer index; groups/*, samples/*_by_group and the group_* datasets "
+                             "of forecast/ and check/; needs one of --summaries on/only, --forecast, --check")
     args = parser.parse_args(argv)
     if args.thin is not None and args.thin < 1:
         parser.error(f"--thin {args.thin}: the thinning interval is >= 1")
@@ -1159,7 +1271,8 @@ def main(argv=None):
          **({} if args.check is None else dict(check=args.check)),
          **({} if args.within_between is None else dict(within_between=args.within_between)),
          **({} if args.forecast_quantiles is None else dict(forecast_quantiles=args.forecast_quantiles)),
-         **({} if args.rt_quantiles is None else dict(rt_quantiles=args.rt_quantiles)))
+         **({} if args.rt_quantiles is None else dict(rt_quantiles=args.rt_quantiles)),
+         **({} if args.groups is None else dict(groups=G_mod.load_spec(args.groups))))
 
 
 if __name__ == "__main__":

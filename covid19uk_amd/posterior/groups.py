@@ -1,0 +1,201 @@
+"""Region totals: the one definition of what `Mcmc: groups` / `--groups` means on the host.
+
+The device forms, for every kept draw, exact integer sums of the event counts over each group's members
+(include/seir_hip.h, "Region totals on the device"): of the recorded epidemic, of the forecast and of the in-sample check.
+Everything that is made of those sums is defined here and nowhere else:
+
+  - `parse_groups`: a group specification -> names and a CSR pair (offsets [G+1], members [nnz]);
+  - `group_state`: the state at the start of every day from the summed events and the summed initial state,
+    state0 + exclusive cumsum of stoichiometry . events, in exact integers -- `model_spec.compute_state`'s rule;
+  - `forecast_planes`: cases, cumulative cases and prevalence per group, with the definitions of forecast/*_quantiles;
+  - `check_counts`: the counts of draws below / at the observed removals per group and day and over the window, and
+    their mid-p values.
+
+The locations of a draw are correlated through the commuting matrix: none of this can be had from per-location moments
+or quantiles, which is why the sums are formed per draw."""
+from dataclasses import dataclass
+
+import numpy as np
+
+MAX_GROUPS = 256                  # SEIR_GROUPS_MAX
+PLANES = ("cases", "cum_cases", "prevalence")
+NATIONS = ("E", "S", "W", "N")    # England, Scotland, Wales, Northern Ireland: the first letter of a GSS code
+
+
+@dataclass
+class GroupTable:
+    names: list                   # [G] str
+    offsets: np.ndarray           # [G+1] int32, offsets[0] = 0, strictly increasing
+    members: np.ndarray           # [nnz] int32 rows, ascending and unique within a group
+
+    @property
+    def G(self) -> int:
+        return len(self.names)
+
+    def rows(self, g: int) -> np.ndarray:
+        return self.members[self.offsets[g]:self.offsets[g + 1]]
+
+    def sum_rows(self, x, axis=0):
+        """x with `axis` indexed by location -> the same with that axis indexed by group (sums over the members)."""
+        x = np.moveaxis(np.asarray(x), axis, 0)
+        return np.moveaxis(np.stack([x[self.rows(g)].sum(axis=0) for g in range(self.G)]), 0, axis)
+
+
+def _table(named_rows, what):
+    if not named_rows:
+        raise ValueError(f"{what}: no group at all")
+    if len(named_rows) > MAX_GROUPS:
+        raise ValueError(f"{what}: {len(named_rows)} groups, at most {MAX_GROUPS}")
+    names, offsets, members = [], [0], []
+    for name, rows in named_rows:
+        if not rows:
+            raise ValueError(f"{what}: group {name!r} is empty")
+        if len(set(rows)) != len(rows):
+            dup = sorted(r for r in set(rows) if rows.count(r) > 1)
+            raise ValueError(f"{what}: group {name!r} names location index {dup[0]} more than once")
+        names.append(str(name))
+        members.extend(sorted(rows))
+        offsets.append(len(members))
+    return GroupTable(names, np.asarray(offsets, np.int32), np.asarray(members, np.int32))
+
+
+def is_off(spec):
+    """None, False and "off": no groups."""
+    return spec is None or spec is False or (isinstance(spec, str) and spec.strip().lower() == "off")
+
+
+def parse_groups(spec, M, location_names=None):
+    """`Mcmc.groups`: "nations" (group by the first letter of the location code: `NATIONS` in that order, then any other
+    letter in order of first appearance; needs `location_names`) or a mapping name -> list of members, a member being a
+    location code, a prefix pattern "E0*" or an integer index.  None, False and "off" -> None.  ValueError for everything else: an unknown code, a pattern that
+    matches nothing, an index outside [0, M), an empty group, a member named twice within a group, more than MAX_GROUPS."""
+    if is_off(spec):
+        return None
+    M = int(M)
+    names = None if location_names is None else [str(x) for x in location_names]
+    if names is not None and len(names) != M:
+        raise ValueError(f"groups: {len(names)} location names for M={M} locations")
+    if isinstance(spec, str):
+        if spec.strip().lower() != "nations":
+            raise ValueError(f"groups={spec!r}: 'nations' or a mapping name -> members")
+        if names is None:
+            raise ValueError("groups='nations' needs the input file's location codes: the input has no `location` coordinate "
+                             "(an .npz input carries none)")
+        by_letter = {}
+        for m, code in enumerate(names):
+            if not code:
+                raise ValueError(f"groups='nations': location {m} has an empty code")
+            by_letter.setdefault(code[0], []).append(m)
+        order = [c for c in NATIONS if c in by_letter] + [c for c in by_letter if c not in NATIONS]
+        return _table([(c, by_letter[c]) for c in order], "groups='nations'")
+    if not isinstance(spec, dict):
+        raise ValueError(f"groups={spec!r}: 'nations' or a mapping name -> members")
+    index = {} if names is None else {c: m for m, c in enumerate(names)}
+    named_rows = []
+    for gname, mem in spec.items():
+        if isinstance(mem, (str, int, np.integer)) and not isinstance(mem, bool):
+            mem = [mem]
+        if not isinstance(mem, (list, tuple)):
+            raise ValueError(f"groups: group {gname!r}: a list of location codes, prefix patterns or indices, not {mem!r}")
+        rows = []
+        for x in mem:
+            if isinstance(x, bool):
+                raise ValueError(f"groups: group {gname!r}: {x!r} is no member")
+            if isinstance(x, (int, np.integer)):
+                if not 0 <= int(x) < M:
+                    raise ValueError(f"groups: group {gname!r}: index {int(x)} outside [0, M={M})")
+                rows.append(int(x))
+            elif isinstance(x, str) and x.endswith("*"):
+                if names is None:
+                    raise ValueError(f"groups: group {gname!r}: the pattern {x!r} needs the input file's location codes")
+                hit = [m for m, c in enumerate(names) if c.startswith(x[:-1])]
+                if not hit:
+                    raise ValueError(f"groups: group {gname!r}: the pattern {x!r} matches no location code")
+                rows.extend(hit)
+            elif isinstance(x, str):
+                if x not in index:
+                    raise ValueError(f"groups: group {gname!r}: unknown location code {x!r}")
+                rows.append(index[x])
+            else:
+                raise ValueError(f"groups: group {gname!r}: {x!r} is no member")
+        named_rows.append((gname, rows))
+    return _table(named_rows, "groups")
+
+
+def load_spec(value):
+    """The command line's `--groups SPEC`: "nations", or a path to a YAML mapping name -> members."""
+    if isinstance(value, str) and value.strip().lower() in ("nations", "off"):
+        return value.strip().lower()
+    import yaml
+    with open(value, "r") as f:
+        spec = yaml.safe_load(f)
+    if not isinstance(spec, dict):
+        raise ValueError(f"--groups {value}: the file does not hold a mapping name -> members")
+    return spec
+
+
+def require_source(table, summaries, horizon, check_days):
+    """`groups` without any of summaries on / only, forecast, check would launch and write nothing: refused."""
+    if table is not None and summaries == "off" and not horizon and not check_days:
+        raise ValueError("groups given without any of summaries on/only, forecast, check: it would have no effect")
+
+
+def group_state(events_by_group, state0):
+    """events_by_group [..., L, 3] and state0 [..., 3] (S, E, I at the window's start), integers -> int64 [..., L, 3]: the
+    state at the START of every day, state0 + exclusive cumsum over days of stoichiometry . events."""
+    ev = np.asarray(events_by_group)
+    s0 = np.asarray(state0)
+    if ev.dtype.kind not in "iu" or s0.dtype.kind not in "iu":
+        raise TypeError("group_state is exact: integer arrays only")
+    ev = ev.astype(np.int64)
+    ex = np.cumsum(ev, axis=-2) - ev
+    s0 = s0.astype(np.int64)[..., None, :]
+    return np.stack([s0[..., 0] - ex[..., 0], s0[..., 1] + ex[..., 0] - ex[..., 1], s0[..., 2] + ex[..., 1] - ex[..., 2]], axis=-1)
+
+
+def forecast_planes(events_by_group, state0):
+    """The three planes of forecast/*_quantiles per group: [..., L, 3] and [..., 3] -> int64 [3, ..., L] in the order
+    `PLANES`: cases k_ir, cumulative cases (inclusive), prevalence = I at the start of the day."""
+    ev = np.asarray(events_by_group)
+    st = group_state(ev, state0)
+    cases = ev[..., 2].astype(np.int64)
+    return np.stack([cases, np.cumsum(cases, axis=-1), st[..., 2]])
+
+
+def mid_p(count, lt, eq):
+    """(lt + eq / 2) / count, the rule of check/pit (`sampler.mid_p`); NaN where count = 0."""
+    n = np.asarray(count, np.float64)
+    num = 2.0 * np.asarray(lt, np.float64) + np.asarray(eq, np.float64)
+    ok = n > 0
+    return np.where(ok, num / np.where(ok, 2.0 * n, 1.0), np.nan)
+
+
+def check_counts(check_by_group, observed_by_group):
+    """check_by_group [n, G, K, 3] (one chain's draws) against observed_by_group [G, K] (the observed removals summed over
+    the members): the raw counts, which pool over chains by a sum, and their mid-p values.  Keys: group_observed, group_lt,
+    group_eq [G, K]; group_window_lt, group_window_eq [G] (the window's total); group_pit [G, K], group_window_pit [G]."""
+    sim = np.asarray(check_by_group)[..., 2].astype(np.int64)
+    obs = np.asarray(observed_by_group).astype(np.int64)
+    n = sim.shape[0]
+    out = {"group_observed": obs,
+           "group_lt": (sim < obs).sum(axis=0), "group_eq": (sim == obs).sum(axis=0),
+           "group_window_lt": (sim.sum(axis=-1) < obs.sum(axis=-1)).sum(axis=0),
+           "group_window_eq": (sim.sum(axis=-1) == obs.sum(axis=-1)).sum(axis=0)}
+    out["group_pit"] = mid_p(n, out["group_lt"], out["group_eq"])
+    out["group_window_pit"] = mid_p(n, out["group_window_lt"], out["group_window_eq"])
+    return out
+
+
+def quantiles(x, probs):
+    """Quantiles `probs` over the first axis of x [n, ...] by the one rank rule (`posterior.quantiles`): float64 [K, ...]."""
+    from . import quantiles as Q
+    x = np.asarray(x, np.float64)
+    ranks = Q.quantile_ranks(x.shape[0], probs)
+    return Q.interpolate(np.sort(x, axis=0)[ranks], ranks, x.shape[0], probs)
+
+
+def run_line(table, sources):
+    sizes = [int(table.offsets[g + 1] - table.offsets[g]) for g in range(table.G)]
+    shown = ", ".join(f"{n} ({s})" for n, s in list(zip(table.names, sizes))[:6]) + (", ..." if table.G > 6 else "")
+    return (f"Groups: {table.G} group(s) of locations -- {shown}; per-draw sums of {', '.join(sources)} formed on the device; "
+            "groups/* and samples/*_by_group written")

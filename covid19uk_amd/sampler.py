@@ -42,6 +42,7 @@ class Trace:
     rt: np.ndarray = None    # [n,B,D] national R_t of every kept draw over the window; None unless asked for
     check: dict = None       # CHECK_KEYS -> int64 [n,B,K,3] / [n,B,M,3] / [n,B,K,3]; None unless the draws were checked
     wb: dict = None          # WB_KEYS -> float64 [n,B,D] national within / between pressure; None unless asked for
+    groups: dict = None      # GROUP_KEYS of the sources that ran -> int64 [n,B,G,L,3] / [n,B,G,3]; None unless asked for
 
 
 MARGINAL_KEYS = ("events_by_day", "events_by_location", "state_by_day")
@@ -49,6 +50,10 @@ FORECAST_KEYS = ("forecast_by_day", "forecast_by_location", "forecast_state_by_d
 FORECAST_QUANTILE_PLANES = ("cases", "cum_cases", "prevalence")   # the planes of the draw store (keep_forecast_draws)
 CHECK_KEYS = ("check_by_day", "check_by_location", "check_state_by_day")
 WB_KEYS = ("within_pressure", "between_pressure")
+# region totals (set_groups): source -> (which of the C-ABI, events_by_group key, state0_by_group key or None)
+GROUP_SOURCES = {"trace": (0, "seir_by_group", None), "forecast": (1, "forecast_by_group", "forecast_group_state0"),
+                 "check": (2, "check_by_group", "check_group_state0")}
+GROUP_KEYS = tuple(k for _, ev, st in GROUP_SOURCES.values() for k in (ev, st) if k)
 SUMMARY_QUANTITIES = ("k_se", "k_ei", "k_ir", "S", "E", "I")
 
 
@@ -234,7 +239,7 @@ class PinnedTrace:
     `ChainSampler.read_trace_async`.  Views are valid until close()."""
 
     def __init__(self, sampler: "ChainSampler", count: int, events: bool = True, marginals: bool = False,
-                 forecast: int = 0, rt: int = 0, check: int = 0, wb: int = 0):
+                 forecast: int = 0, rt: int = 0, check: int = 0, wb: int = 0, groups=None):
         self._lib = sampler._lib
         self.count = int(count)
         B, P, M, T = sampler.B, sampler.P, sampler.M, sampler.T
@@ -262,6 +267,16 @@ class PinnedTrace:
                               check_by_location=self._alloc((count, B, M, 3), np.int64),
                               check_state_by_day=self._alloc((count, B, K, 3), np.int64))
         self.wb = {k: self._alloc((count, B, int(wb)), np.float64) for k in WB_KEYS} if wb else None
+        # groups: (G, {source: day extent}) -- the group sums of the sources that run with the burst
+        self.groups = None
+        if groups:
+            G, lens = groups
+            self.groups = {}
+            for src, L in lens.items():
+                _, ev_key, st_key = GROUP_SOURCES[src]
+                self.groups[ev_key] = self._alloc((count, B, G, int(L), 3), np.int64)
+                if st_key:
+                    self.groups[st_key] = self._alloc((count, B, G, 3), np.int64)
 
     def _alloc(self, shape, dtype):
         nbytes = int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize
@@ -273,6 +288,7 @@ class PinnedTrace:
 
     def close(self):
         self.theta = self.events = self.hmc = self.moves = self.marginals = self.forecast = self.rt = self.check = self.wb = None
+        self.groups = None
         for p in self._ptrs:
             self._lib.seir_host_free(p)
         self._ptrs = []
@@ -294,6 +310,7 @@ class ChainSampler:
     _rt_D = 0                     # window of the reproduction number in force (0: reset_rt was never called)
     _check_K = 0                  # window of the in-sample check in force (0: reset_check was never called)
     _wb_D = 0                     # window of the within/between shares in force (0: reset_within_between was never called)
+    _groups_G = 0                 # groups of the table in force (0: none set)
     first_chain_id = 0
 
     def __init__(self, model: SeirModel, config: dict, num_chains: int, seed: int = 0,
@@ -563,6 +580,8 @@ class ChainSampler:
             tr.check = {k: v[:n] for k, v in buf.check.items()}
         if getattr(buf, "wb", None) is not None:
             tr.wb = {k: v[:n] for k, v in buf.wb.items()}
+        if getattr(buf, "groups", None) is not None:
+            tr.groups = {k: v[:n] for k, v in buf.groups.items()}
         return tr
 
     # -- summaries of the recorded events on the device (include/seir_hip.h) --------------------------
@@ -899,6 +918,72 @@ class ChainSampler:
             raise ValueError("within_between asked for before reset_within_between")
         self.within_between(first, count)
 
+    # -- region totals: per-draw sums over groups of locations (include/seir_hip.h, "Region totals on the device") ------
+    def set_groups(self, offsets, members):
+        """Set the table of groups (CSR: `offsets` [G+1], `members` [nnz], ascending and unique within a group;
+        `posterior.groups.parse_groups`), or free it with `set_groups(None, None)`.  While a table is set, `summarize`,
+        `forecast` and `check` also form every kept draw's sums over each group's members (`read_group_marginals`)."""
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        if offsets is None:
+            _lib.check(self._lib.seir_sampler_groups_set(self._s, 0, None, None))
+            self._groups_G = 0
+            return
+        off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
+        mem = np.ascontiguousarray(members, dtype=np.int32).reshape(-1)
+        G = off.size - 1
+        if G < 1 or mem.size < int(off.max()):              # what the library cannot check: it reads members up to the offsets
+            raise ValueError(f"offsets [{off.size}] reach {int(off.max()) if off.size else 0}, members holds {mem.size}: not a "
+                             "CSR pair of at least one group")
+        if G > _lib.GROUPS_MAX:
+            raise ValueError(f"G={G}: at most {_lib.GROUPS_MAX} groups")
+        _lib.check(self._lib.seir_sampler_groups_set(self._s, G, off.ctypes.data_as(i32p), mem.ctypes.data_as(i32p)))
+        self._groups_G = G
+
+    def _group_len(self, source):
+        return {"trace": self.T if self._summary_on else 0, "forecast": self._forecast_H, "check": self._check_K}[source]
+
+    def _read_groups(self, fn, source, count, first, into=None):
+        which, ev_key, st_key = GROUP_SOURCES[source]
+        n, G = int(count), self._groups_G
+        if into is None:
+            into = {ev_key: np.empty((n, self.B, G, self._group_len(source), 3), np.int64)}
+            if st_key:
+                into[st_key] = np.empty((n, self.B, G, 3), np.int64)
+        _lib.check(fn(self._s, which, int(first), n, into[ev_key].ctypes.data_as(_lib.c_int64_p),
+                      into[st_key].ctypes.data_as(_lib.c_int64_p) if st_key else None))
+        return into
+
+    def read_group_marginals(self, source: str, count: int, first: int = 0) -> dict:
+        """Blocking read of the group sums of trace slots [first, first+count) of `source` ("trace", "forecast", "check"):
+        its keys of `GROUP_SOURCES` -> int64 [count,B,G,L,3] (L = T, H, K) and, for the forecast and the check, the
+        members' sum of S, E, I at the window's start [count,B,G,3]."""
+        return self._read_groups(self._lib.seir_sampler_read_group_marginals, source, count, first)
+
+    def read_group_marginals_async(self, source: str, count: int, first: int, into: PinnedTrace):
+        """As `read_marginals_async`, for the group sums of `source`; completed by `trace_wait()`."""
+        if int(count) > into.count or getattr(into, "groups", None) is None or GROUP_SOURCES[source][1] not in into.groups:
+            raise ValueError("pinned buffer too small or without group arrays")
+        self._read_groups(self._lib.seir_sampler_read_group_marginals_async, source, count, first, into.groups)
+
+    def _group_sources(self, groups, do_sum, do_fc, do_ck):
+        """`groups` of sample / sample_bursts: the sources whose group sums cross with the trace -- True: every one of
+        "trace", "forecast", "check" that runs with the burst; or a tuple of those names, each of which must run."""
+        if not groups:
+            return ()
+        if not self._groups_G:
+            raise ValueError("groups asked for before set_groups")
+        on = dict(trace=do_sum, forecast=do_fc, check=do_ck)
+        if groups is True:
+            src = tuple(k for k in GROUP_SOURCES if on[k])
+        else:
+            src = tuple(groups)
+            bad = [k for k in src if not on.get(k)]
+            if bad:
+                raise ValueError(f"groups={groups!r}: {bad[0]!r} is not one of summarize, forecast, check run with this burst")
+        if not src:
+            raise ValueError("groups needs one of summarize, forecast, check")
+        return src
+
     def _summarize_mode(self, summarize):
         """`summarize` of sample / sample_bursts: False, True (marginals + moments) or "marginals" (accumulate = 0)."""
         if summarize not in (False, True, "marginals"):
@@ -908,7 +993,7 @@ class ChainSampler:
         return bool(summarize), summarize is True
 
     def sample_bursts(self, num_bursts: int, burst: int, consume, events: bool = True, summarize=False, marks=None,
-                      forecast=False, rt=False, check=False, within_between=False):
+                      forecast=False, rt=False, check=False, within_between=False, groups=False):
         """`num_bursts` x `burst` kept draws (`burst * thin` sweeps each) with the burst buffer used as two halves:
         while burst k+1 runs on the device, burst k crosses PCIe into page-locked memory on a copy stream and `consume(trace, k)`
         (e.g. the HDF5 writer) runs on a worker thread -- the sampler only waits when the consumer is
@@ -938,7 +1023,11 @@ class ChainSampler:
 
         `within_between` (needs `reset_within_between`): the within/between pressure shares of every burst's draws are
         formed and folded on the device, behind the summary, the forecast, R_t and the check; the national pressures cross
-        with the trace (`trace.wb`)."""
+        with the trace (`trace.wb`).
+
+        `groups` (True, or a tuple of "trace", "forecast", "check"; needs `set_groups` and the matching `summarize`,
+        `forecast`, `check`): the group sums that the summary, the forecast and the check of every burst form while a table
+        is set cross with the trace (`trace.groups`), all of them or the named ones."""
         from concurrent.futures import ThreadPoolExecutor
         do_sum, accumulate = self._summarize_mode(summarize)
         burst, num_bursts = int(burst), int(num_bursts)
@@ -949,8 +1038,11 @@ class ChainSampler:
         do_rt = bool(rt)
         do_ck = bool(check)
         do_wb = bool(within_between)
+        grp_src = self._group_sources(groups, do_sum, do_fc, do_ck)
+        grp_lens = {k: self._group_len(k) for k in grp_src}
         key = (burst, bool(events), do_sum, self._forecast_H if do_fc else 0) + ((self._rt_D,) if do_rt else ()) + \
-            ((("check", self._check_K),) if do_ck else ()) + ((("wb", self._wb_D),) if do_wb else ())
+            ((("check", self._check_K),) if do_ck else ()) + ((("wb", self._wb_D),) if do_wb else ()) + \
+            ((("groups", self._groups_G, tuple(grp_lens.items())),) if grp_src else ())
         if getattr(self, "_pinned_key", None) != key:
             for bf in getattr(self, "_pinned", []):
                 bf.close()
@@ -963,6 +1055,8 @@ class ChainSampler:
                 mk["check"] = self._check_K
             if do_wb:
                 mk["wb"] = self._wb_D
+            if grp_src:
+                mk["groups"] = (self._groups_G, grp_lens)
             self._pinned = [PinnedTrace(self, burst, events, **mk), PinnedTrace(self, burst, events, **mk)]
             self._pinned_key = key
         bufs = self._pinned
@@ -1014,6 +1108,8 @@ class ChainSampler:
                                 self.read_check_marginals_async(burst, h * burst, bufs[h])
                             if do_wb:
                                 self.read_wb_draws_async(burst, h * burst, bufs[h])
+                            for src in grp_src:
+                                self.read_group_marginals_async(src, burst, h * burst, bufs[h])
                             prev = i
                             i += 1
                     except _lib.HandoffTimeout as e:
@@ -1035,11 +1131,13 @@ class ChainSampler:
                 pass
 
     def sample(self, num_sweeps: int, events: bool = True, summarize=False, forecast=False, rt=False, check=False,
-               within_between=False) -> Trace:
+               within_between=False, groups=False) -> Trace:
         """reset_trace + run + read: the analogue of one `sample_chain` call with `num_sweeps` results, each the last of
         `thin` sweeps.  `summarize` as in `sample_bursts`: the burst is summarised on the device and `trace.marginals`
-        filled; `forecast` likewise (`trace.forecast`), `rt` (`trace.rt`), `check` (`trace.check`) and `within_between` (`trace.wb`)."""
+        filled; `forecast` likewise (`trace.forecast`), `rt` (`trace.rt`), `check` (`trace.check`), `within_between` (`trace.wb`)
+        and `groups` (`trace.groups`)."""
         do_sum, accumulate = self._summarize_mode(summarize)
+        grp_src = self._group_sources(groups, do_sum, bool(forecast), bool(check))
         if num_sweeps > self.cap:
             raise ValueError(f"num_sweeps={num_sweeps} exceeds trace_capacity={self.cap}")
         while True:
@@ -1069,6 +1167,10 @@ class ChainSampler:
                     tr.check = self.read_check_marginals(num_sweeps)
                 if within_between:
                     tr.wb = self.read_wb_draws(num_sweeps)
+                if grp_src:
+                    tr.groups = {}
+                    for src in grp_src:
+                        tr.groups.update(self.read_group_marginals(src, num_sweeps))
             except _lib.HandoffTimeout as e:
                 if not self.auto_recover:
                     raise

@@ -306,6 +306,26 @@ class SeirModel:
                                               out.ctypes.data_as(ip)))
         return out
 
+    def group_sums(self, events, offsets, members):
+        """Sums over groups of locations on the device (csrc/group_kernels.h; include/seir_hip.h, seir_group_sums): `events`
+        int32 [n, M, L, 3] (M and L the array's own), the groups a CSR pair (`offsets` [G+1], `members` [nnz], ascending and
+        unique within a group).  Returns int64 [n, G, L, 3]: events[:, members(g)].sum(1)."""
+        ev = np.ascontiguousarray(events, dtype=np.int32)
+        if ev.ndim != 4 or ev.shape[3] != 3:
+            raise ValueError(f"events {ev.shape}: need [n, M, L, 3]")
+        off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
+        mem = np.ascontiguousarray(members, dtype=np.int32).reshape(-1)
+        G = off.size - 1
+        if G >= 1 and mem.size < int(off.max()):            # what the library cannot check: it reads members up to the offsets
+            raise ValueError(f"offsets reach {int(off.max())}, members holds {mem.size}")
+        n, M, L, _ = ev.shape
+        out = np.empty((n, max(G, 0), L, 3), dtype=np.int64)
+        ip = ctypes.POINTER(ctypes.c_int32)
+        mem_arg = mem if mem.size else np.zeros(1, np.int32)
+        _lib.check(self._lib.seir_group_sums(self._ctx, ev.ctypes.data_as(ip), n, M, L, G, off.ctypes.data_as(ip),
+                                             mem_arg.ctypes.data_as(ip), out.ctypes.data_as(_lib.c_int64_p)))
+        return out
+
     def order_stats_f64(self, values, ranks, cells=1, segs=1, seg_len=None, seg_stride=None, cell_stride=None):
         """`order_stats` for float64 (csrc/order_stats64_kernels.h; include/seir_hip.h, seir_order_stats_f64): the same
         cell geometry, the order of IEEE-754 totalOrder on the bit patterns (np.sort's on values without NaN, except that

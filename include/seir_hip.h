@@ -861,6 +861,52 @@ int seir_sampler_read_check_counts(seir_sampler *s, int32_t *obs, uint32_t *lt, 
                                    uint32_t *loc_eq, uint32_t *day_lt, uint32_t *day_eq, uint32_t *all_lt, uint32_t *all_eq);
 
 /* ------------------------------------------------------------------------
+ * Region totals on the device: per-draw sums over groups of locations.
+ *
+ * What leaves the device per kept draw is per location or national; the locations of a draw are correlated, so a region's
+ * curve with its band cannot be rebuilt from either.  While a table of groups is set, every kept draw also leaves exact
+ * integer sums of its event counts over each group's members -- for the recorded epidemic, the forecast and the in-sample
+ * check -- and the host does the statistics (covid19uk_amd/posterior/groups.py).
+ *
+ * Semantics (the one definition; kernel: csrc/group_kernels.h).
+ *   Table.  G groups as a CSR pair: offsets [G + 1] (offsets[0] = 0, strictly increasing: no empty group) and
+ *     members [offsets[G]], rows in [0, M), ascending and unique within a group.  Groups may overlap and need not cover
+ *     every location.  1 <= G <= SEIR_GROUPS_MAX.
+ *   Sums, int64, indexed by trace slot, rewritten when a slot is summarised / forecast / checked again (no accumulators:
+ *     snapshot and restore carry nothing of them):
+ *       events_by_group [count][B][G][L][3]   sum over m in members(g) of k[m][t][x]; L = T (which = 0, the recorded events
+ *                                             of the slot), H (1, the forecast's simulated counts), K (2, the check's)
+ *       state0_by_group [count][B][G][3]      which = 1, 2: the members' sum of the draw's S, E, I at the window's start
+ *                                             (day T, day T - K).  Not produced for which = 0: it is the context's initial
+ *                                             state summed over the members, the same for every draw.
+ *   No floating-point value is formed: the sums do not depend on the order of the adds, on the launch geometry or on how a
+ *   burst is cut into calls.
+ * A sampler that never sets a table allocates and launches nothing more than before.
+ * ------------------------------------------------------------------------ */
+#define SEIR_GROUPS_MAX 256
+/* Copies the table and sizes the outputs of every source that is on (summaries, forecast, check); a later
+ * seir_sampler_summary_reset / _forecast_reset / _check_reset sizes its source's again.  G = 0 frees everything (offsets and
+ * members are not read).  SEIR_ERR_INVALID for G outside [0, SEIR_GROUPS_MAX], an empty group, non-monotone offsets, a
+ * member outside [0, M), a non-ascending or repeated member, or outputs above half of the device's free memory;
+ * SEIR_ERR_STATE with record_events == 0.  A refused table leaves the one in force alone.  When a source's reset cannot
+ * size its outputs (the same refusal, returned by that reset) the source is on without group outputs: nothing is launched
+ * for them and seir_sampler_read_group_marginals of it fails with SEIR_ERR_STATE until a later reset or groups_set fits. */
+int seir_sampler_groups_set(seir_sampler *s, int32_t G, const int32_t *offsets, const int32_t *members);
+/* Blocking read of the group sums of slots [first, first + count) of source `which` (0 trace, 1 forecast, 2 check).
+ * Either pointer may be NULL; state0_by_group must be NULL for which = 0.  Host pointers.  SEIR_ERR_STATE before a table is
+ * set or when the source is off. */
+int seir_sampler_read_group_marginals(seir_sampler *s, int32_t which, int32_t first, int32_t count, int64_t *events_by_group,
+                                      int64_t *state0_by_group);
+/* The same on the copy stream, with the stream and the wait of seir_sampler_read_marginals_async
+ * (seir_sampler_trace_wait completes it). */
+int seir_sampler_read_group_marginals_async(seir_sampler *s, int32_t which, int32_t first, int32_t count,
+                                            int64_t *events_by_group, int64_t *state0_by_group);
+/* The kernel alone, on host arrays: events [n][M][L][3] (int32), the table as above; out [n][G][L][3] (int64).
+ * M and L are the call's own, not the context's. */
+int seir_group_sums(seir_ctx *ctx, const int32_t *events, int64_t n, int32_t M, int32_t L, int32_t G, const int32_t *offsets,
+                    const int32_t *members, int64_t *out);
+
+/* ------------------------------------------------------------------------
  * Reproduction number R_it.
  *
  * calc_posterior_rit (covid19uk/posterior/reproduction_number.py:13-44): for each
