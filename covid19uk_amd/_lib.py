@@ -247,6 +247,16 @@ _SIGNATURES = {
     "seir_group_sums": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, ctypes.c_int32,
                                        ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
                                        ctypes.POINTER(ctypes.c_int32), c_int64_p]),
+    # group curves: R_t and within / between per group of every kept draw; the kernel alone on host arrays
+    "seir_sampler_group_rt": (ctypes.c_int, [ctypes.c_void_p, c_double_p]),
+    "seir_sampler_group_wb": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
+    "seir_sampler_read_group_rt": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, c_double_p]),
+    "seir_sampler_read_group_rt_async": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, c_double_p]),
+    "seir_sampler_read_group_wb": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, c_double_p, c_double_p]),
+    "seir_sampler_read_group_wb_async": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, c_double_p, c_double_p]),
+    "seir_group_wsums": (ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                        ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                        c_double_p, c_double_p]),
 }
 
 _lib = None

@@ -1192,6 +1192,18 @@ struct GroupOut {
     int L = 0;                        // day extent the arrays are sized for; 0: none (no table, or the source is off)
 };
 
+// One family of group curves (seir_sampler_group_rt: 1 plane, weighted; seir_sampler_group_wb: 2 planes): the switch, the
+// per-slot outputs out [cap][B][G][D] and the cell planes [slots * B][D][Mp] of a batch.  D = 0: no outputs (the switch is
+// off, there is no table, the product is off, or the outputs were refused) -- nothing is launched then.
+struct GroupCurve {
+    bool on = false;
+    int planes = 1;
+    int D = 0, slots = 0;             // window days the buffers are sized for; trace slots per batch
+    int *offsets = nullptr;           // device copy of the table's offsets [G + 1]
+    double *weights = nullptr;        // [nnz] aligned with the members (group R_t), or null
+    double *cells[2] = {nullptr, nullptr}, *out[2] = {nullptr, nullptr};
+};
+
 // The host's half of a ForecastBufs that is rolled forward day by day from the kept draws (forecast_kernels.h): the forecast
 // and the in-sample check each own one (rollout_*, below).
 struct Rollout {
@@ -1303,6 +1315,9 @@ struct seir_sampler {
     bool grp_on = false;              // a table is set
     GroupTable grp{};                 // its device copy: segments and members
     GroupOut grp_out[3];              // per-slot outputs of the trace, the forecast and the check (L = 0: that source is off)
+    // --- group curves: R_t and within / between per group (seir_sampler_group_rt / _group_wb; group_curve_kernels.h) ---
+    std::vector<int> grp_offsets;     // the table's offsets [G + 1] on the host (the device copy exists only with a curve on)
+    GroupCurve grt, gwb;              // group R_t (one plane, weighted); group within / between (two planes)
 };
 
 // Zeroed device memory, registered in `list` (seir_sampler::allocs: freed with the sampler; Rollout::allocs: also when the length
@@ -1334,7 +1349,30 @@ static int rollout_shadow(Rollout &r, int slot, bool save, hipStream_t st) {
     return acc_shadow(r.acc, slot, save, st);
 }
 
+// Frees the buffers of a family of group curves; its switch and weights stay.
+static void gcurve_release(GroupCurve &c) {
+    for (int x = 0; x < 2; ++x) {
+        if (c.cells[x]) (void)hipFree(c.cells[x]);
+        if (c.out[x]) (void)hipFree(c.out[x]);
+        c.cells[x] = c.out[x] = nullptr;
+    }
+    if (c.offsets) (void)hipFree(c.offsets);
+    c.offsets = nullptr;
+    c.D = c.slots = 0;
+}
+// Switches group R_t off: its weights belonged to the table that was in force.
+static void gcurve_rt_off(seir_sampler *s) {
+    gcurve_release(s->grt);
+    if (s->grt.weights) (void)hipFree(s->grt.weights);
+    s->grt.weights = nullptr;
+    s->grt.on = false;
+}
+static int gcurve_fit(seir_sampler *s, bool rt);     // with the rest of the group curves, behind the within/between shares
+
 static void groups_free(seir_sampler *s) {
+    gcurve_rt_off(s);
+    gcurve_release(s->gwb);
+    s->grp_offsets.clear();
     for (GroupOut &o : s->grp_out) {
         if (o.ev) (void)hipFree(o.ev);
         if (o.st0) (void)hipFree(o.st0);
@@ -2489,6 +2527,7 @@ extern "C" int seir_sampler_groups_set(seir_sampler *s, int32_t G, const int32_t
     if (G == 0) {
         if ((rc = drain(s))) return rc;
         groups_free(s);
+        s->gwb.on = false;
         return 0;
     }
     if ((rc = need_events(s, "sum over groups of locations"))) return rc;
@@ -2514,7 +2553,9 @@ extern "C" int seir_sampler_groups_set(seir_sampler *s, int32_t G, const int32_t
     s->grp_on = true;
     for (int which = 0; which < 3; ++which)
         if ((rc = groups_fit(s, which))) { groups_free(s); return rc; }
-    return 0;
+    s->grp_offsets.assign(offsets, offsets + G + 1);
+    // group R_t went off with the old table's weights (groups_free); group within / between has none and is sized again
+    return s->gwb.on ? gcurve_fit(s, false) : 0;
 }
 
 static int copy_group_marginals(seir_sampler *s, hipStream_t st, int which, int32_t first, int32_t count, int64_t *ev, int64_t *st0) {
@@ -3218,6 +3259,14 @@ extern "C" int seir_sampler_read_check_counts(seir_sampler *s, int32_t *obs, uin
 // ---------------------------------------------------------------------------
 // Reproduction number on the device (include/seir_hip.h; kernels: rt_trace_kernels.h)
 // ---------------------------------------------------------------------------
+// The launches of the group curves (defined at the end of this file, where group_curve_kernels.h is included: the one place
+// that names its kernels, behind every kernel the parent had).  Slots [slot0, slot0 + nj) are one batch.
+static void gcurve_rt_trace_cells(seir_sampler *s, const LaunchCfg &l, int slot0, int nj);
+static void gcurve_rt_gather(seir_sampler *s, const LaunchCfg &l, long long pos0, int nj);
+static void gcurve_wb_trace_cells(seir_sampler *s, const LaunchCfg &l, int slot0, int nj);
+static void gcurve_sums(seir_sampler *s, const LaunchCfg &l, const GroupCurve &c, int D, int slot0, int nj);
+static void gcurve_lds_attributes(int Mp);
+
 // need_events' refusal as SEIR_ERR_INVALID (a sampler without recorded events is a bad argument to this feature), then
 // trace_range_check's
 static int rt_check(seir_sampler *s, int32_t first = 0, int32_t count = 0) {
@@ -3278,7 +3327,7 @@ extern "C" int seir_sampler_rt_reset(seir_sampler *s, int32_t days, const double
     s->rt_j = 0;                                     // empties the draw store too: it holds draws [0, count)
     // what the snapshots taken before this reset hold of it is dropped: restoring one of them leaves the accumulators alone
     acc_invalidate(s->rt_acc);
-    return 0;
+    return s->grt.on ? gcurve_fit(s, true) : 0;
 }
 
 extern "C" int seir_sampler_rt(seir_sampler *s, int32_t first, int32_t count) {
@@ -3297,8 +3346,10 @@ extern "C" int seir_sampler_rt(seir_sampler *s, int32_t first, int32_t count) {
     Work tw = ctx->w;                                 // k_rt_tables writes Work::ea: the feature's own buffer, not the sampler's
     tw.ea = rb.ea;
     const size_t lds = k_rt_trace_lds_bytes<RT_DT>(d.Mp);
-    for (int j0 = 0; j0 < count; j0 += s->rt_slots) {
-        const int nj = std::min(s->rt_slots, count - j0), ND = nj * B;
+    const bool curves = s->grt.D != 0;                // group R_t: the batch also fits the cell plane
+    const int slots = curves ? s->grt.slots : s->rt_slots;
+    for (int j0 = 0; j0 < count; j0 += slots) {
+        const int nj = std::min(slots, count - j0), ND = nj * B;
         hipLaunchKernelGGL(k_rt_tables, dim3(ND), dim3(256), 0, l.st, d, tw,
                            (const double *)s->ch.tr_theta + (size_t)(first + j0) * B * d.P);
         const dim3 pgrid((d.M + RT_PREP_ROWS - 1) / RT_PREP_ROWS, ND), pblock(64 * RT_PREP_ROWS);
@@ -3309,10 +3360,16 @@ extern "C" int seir_sampler_rt(seir_sampler *s, int32_t first, int32_t count) {
         if (s->rt_keep)                               // in place of k_rt_trace: R_it is formed once
             hipLaunchKernelGGL(k_rt_trace_keep<RT_DT>, dim3(rb.ncb, (D + RT_DT - 1) / RT_DT, B), dim3(256), lds, l.st, d, ctx->c, rb,
                                (const double *)s->ch.tr_theta, B, first + j0, nj, s->rt_keep, s->rt_keep_stride);
+        else if (curves)                              // in place of k_rt_trace: it also leaves every cell's r in the plane
+            gcurve_rt_trace_cells(s, l, first + j0, nj);
         else
             hipLaunchKernelGGL(k_rt_trace<RT_DT>, dim3(rb.ncb, (D + RT_DT - 1) / RT_DT, B), dim3(256), lds, l.st, d, ctx->c, rb,
                                (const double *)s->ch.tr_theta, B, first + j0, nj);
         hipLaunchKernelGGL(k_rt_finish, dim3((unsigned)(((size_t)ND * D + 255) / 256)), dim3(256), 0, l.st, rb, B, first + j0, nj);
+        if (curves) {
+            if (s->rt_keep) gcurve_rt_gather(s, l, s->rt_j + j0, nj);
+            gcurve_sums(s, l, s->grt, D, first + j0, nj);
+        }
     }
     HIP_TRY(hipGetLastError());
     s->rt_j += count;
@@ -3542,7 +3599,7 @@ extern "C" int seir_sampler_wb_reset(seir_sampler *s, int32_t days) {
     HIP_TRY(hipStreamSynchronize(st));
     // what the snapshots taken before this reset hold of it is dropped: restoring one of them leaves the accumulators alone
     acc_invalidate(s->wb_acc);
-    return 0;
+    return s->gwb.on ? gcurve_fit(s, false) : 0;
 }
 
 extern "C" int seir_sampler_wb(seir_sampler *s, int32_t first, int32_t count) {
@@ -3556,16 +3613,22 @@ extern "C" int seir_sampler_wb(seir_sampler *s, int32_t first, int32_t count) {
     const int B = s->cfg.B, D = s->wb.D;
     const WbBufs &wb = s->wb;
     const size_t lds = k_wb_trace_lds_bytes<WB_DT>(d.Mp);
-    for (int j0 = 0; j0 < count; j0 += s->wb_slots) {
-        const int nj = std::min(s->wb_slots, count - j0), ND = nj * B;
+    const bool curves = s->gwb.D != 0;                // group within / between: the batch also fits the two cell planes
+    const int slots = curves ? s->gwb.slots : s->wb_slots;
+    for (int j0 = 0; j0 < count; j0 += slots) {
+        const int nj = std::min(slots, count - j0), ND = nj * B;
         const dim3 pgrid((d.M + WB_PREP_ROWS - 1) / WB_PREP_ROWS, ND), pblock(64 * WB_PREP_ROWS);
         if (s->cfg.ev16)
             hipLaunchKernelGGL(k_wb_prepare<1>, pgrid, pblock, 0, l.st, d, ctx->c, wb, (const void *)s->ch.tr_events, B, first + j0);
         else
             hipLaunchKernelGGL(k_wb_prepare<0>, pgrid, pblock, 0, l.st, d, ctx->c, wb, (const void *)s->ch.tr_events, B, first + j0);
-        hipLaunchKernelGGL(k_wb_trace<WB_DT>, dim3(wb.ncb, (D + WB_DT - 1) / WB_DT, B), dim3(256), lds, l.st, d, ctx->c, wb,
-                           (const double *)s->ch.tr_theta, B, first + j0, nj);
+        if (curves)                                   // in place of k_wb_trace: it also leaves every cell's wi and be
+            gcurve_wb_trace_cells(s, l, first + j0, nj);
+        else
+            hipLaunchKernelGGL(k_wb_trace<WB_DT>, dim3(wb.ncb, (D + WB_DT - 1) / WB_DT, B), dim3(256), lds, l.st, d, ctx->c, wb,
+                               (const double *)s->ch.tr_theta, B, first + j0, nj);
         hipLaunchKernelGGL(k_wb_finish, dim3((unsigned)(((size_t)ND * D + 255) / 256)), dim3(256), 0, l.st, wb, B, first + j0, nj);
+        if (curves) gcurve_sums(s, l, s->gwb, D, first + j0, nj);
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -3613,6 +3676,160 @@ extern "C" int seir_sampler_read_wb(seir_sampler *s, uint64_t *count, uint32_t *
     if (gt) HIP_TRY(hipMemcpyAsync(gt, wb.gt, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return check_ev_overflow(s);
+}
+
+// ---------------------------------------------------------------------------
+// Group curves on the device: R_t and within / between per group (include/seir_hip.h; kernels: group_curve_kernels.h)
+// ---------------------------------------------------------------------------
+// Size the buffers of a family for the table, the switch and the product's window as they are now (none when any is off).
+// The batch shrinks so that the product's integer plane and the cell plane(s) stay within the staging bound together.
+static int gcurve_fit(seir_sampler *s, bool rt) {
+    GroupCurve &c = rt ? s->grt : s->gwb;
+    c.planes = rt ? 1 : 2;
+    const bool product = rt ? s->rt_on : s->wb_on;
+    const int D = (c.on && s->grp_on && product) ? (rt ? s->rt.D : s->wb.D) : 0;
+    if (D == c.D) return 0;
+    if (int rc = drain(s)) return rc;
+    gcurve_release(c);
+    if (D == 0) return 0;
+    const Dims &d = s->ctx->d;
+    const int B = s->cfg.B, G = s->grp.G;
+    const size_t bound = s->ctx->opt_rt_staging_kib ? (size_t)s->ctx->opt_rt_staging_kib << 10 : RT_STAGING_BYTES;
+    const size_t per_slot = (size_t)B * d.Mp * D * (sizeof(int) + c.planes * sizeof(double));
+    const int base = rt ? s->rt_slots : s->wb_slots;
+    const int slots = (int)std::max<size_t>(1, std::min<size_t>((size_t)base, bound / per_slot));
+    const unsigned long long out_bytes = (unsigned long long)s->cfg.cap * B * G * D * 8ull;
+    const unsigned long long cell_bytes = (unsigned long long)slots * B * D * d.Mp * 8ull;
+    const unsigned long long bytes = (unsigned long long)c.planes * (out_bytes + cell_bytes);
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    // half of what is free: the policy of a device that is shared, not a measurement (groups_refuse_bytes)
+    if (bytes > (unsigned long long)free_b / 2)
+        return fail(SEIR_ERR_INVALID, "the group curves need %llu bytes (%d planes x (%d slots x %d chains x %d groups x %d days "
+                    "x 8 + %llu of a batch's cells)), more than half of the %llu bytes free on the device", bytes, c.planes,
+                    s->cfg.cap, B, G, D, cell_bytes, (unsigned long long)free_b);
+    hipError_t e = hipMalloc((void **)&c.offsets, sizeof(int) * (size_t)(G + 1));
+    if (e == hipSuccess) e = hipMemcpy(c.offsets, s->grp_offsets.data(), sizeof(int) * (size_t)(G + 1), hipMemcpyHostToDevice);
+    for (int x = 0; x < c.planes && e == hipSuccess; ++x) {
+        e = hipMalloc((void **)&c.out[x], (size_t)out_bytes);
+        if (e == hipSuccess) e = hipMemset(c.out[x], 0, (size_t)out_bytes);
+        if (e == hipSuccess) e = hipMalloc((void **)&c.cells[x], (size_t)cell_bytes);
+        if (e == hipSuccess) e = hipMemset(c.cells[x], 0, (size_t)cell_bytes);
+    }
+    if (e != hipSuccess) {
+        gcurve_release(c);
+        return fail(SEIR_ERR_DEVICE, "allocating %llu bytes of group curves failed: %s", bytes, hipGetErrorString(e));
+    }
+    gcurve_lds_attributes(d.Mp);
+    c.D = D; c.slots = slots;
+    return 0;
+}
+
+extern "C" int seir_sampler_group_rt(seir_sampler *s, const double *weights) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if (!weights) {
+        if (s->grt.on && (rc = drain(s))) return rc;
+        gcurve_rt_off(s);
+        return 0;
+    }
+    if ((rc = need_events(s, RT_USER.verb))) return rc;
+    if (!s->grp_on) return fail(SEIR_ERR_STATE, "no group table is set: call seir_sampler_groups_set first");
+    const size_t nnz = (size_t)s->grp_offsets[s->grp.G];
+    for (size_t k = 0; k < nnz; ++k)
+        if (!(fabs(weights[k]) < __builtin_inf())) return fail(SEIR_ERR_INVALID, "weights[%zu] is not finite", k);
+    if ((rc = drain(s))) return rc;
+    if (!s->grt.weights) HIP_TRY(hipMalloc((void **)&s->grt.weights, sizeof(double) * nnz));
+    HIP_TRY(hipMemcpy(s->grt.weights, weights, sizeof(double) * nnz, hipMemcpyHostToDevice));
+    s->grt.on = true;
+    if ((rc = gcurve_fit(s, true))) { gcurve_rt_off(s); return rc; }
+    return 0;
+}
+
+extern "C" int seir_sampler_group_wb(seir_sampler *s, int32_t on) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if (!on) {
+        if (s->gwb.on && (rc = drain(s))) return rc;
+        gcurve_release(s->gwb);
+        s->gwb.on = false;
+        return 0;
+    }
+    if ((rc = need_events(s, WB_USER.verb))) return rc;
+    if (!s->grp_on) return fail(SEIR_ERR_STATE, "no group table is set: call seir_sampler_groups_set first");
+    s->gwb.on = true;
+    if ((rc = gcurve_fit(s, false))) { s->gwb.on = false; return rc; }
+    return 0;
+}
+
+static int copy_group_curves(seir_sampler *s, hipStream_t st, const GroupCurve &c, int32_t first, int32_t count, double *const *dst) {
+    const size_t row = (size_t)s->cfg.B * s->grp.G * c.D;
+    for (int x = 0; x < c.planes; ++x)
+        if (dst[x])
+            HIP_TRY(hipMemcpyAsync(dst[x], c.out[x] + (size_t)first * row, sizeof(double) * count * row, hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+static int read_group_curves(seir_sampler *s, bool rt, bool async, int32_t first, int32_t count, double *a, double *b) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = rt ? rt_check(s, first, count) : wb_check(s, first, count))) return rc;
+    const GroupCurve &c = rt ? s->grt : s->gwb;
+    if (c.D == 0)
+        return fail(SEIR_ERR_STATE, "%s", !c.on ? (rt ? "group R_t is not enabled: call seir_sampler_group_rt first"
+                                                     : "group within/between is not enabled: call seir_sampler_group_wb first")
+                                              : "the group curves have no outputs: no table is set, or they were refused");
+    if (rt && !a) return fail(SEIR_ERR_INVALID, "null pointer");
+    double *const dst[2] = {a, b};
+    if (async) return on_copy_stream(s, [&](hipStream_t st) { return copy_group_curves(s, st, c, first, count, dst); });
+    if ((rc = copy_group_curves(s, s->ctx->stream, c, first, count, dst))) return rc;
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    return check_ev_overflow(s);
+}
+
+extern "C" int seir_sampler_read_group_rt(seir_sampler *s, int32_t first, int32_t count, double *Rg) {
+    return read_group_curves(s, true, false, first, count, Rg, nullptr);
+}
+extern "C" int seir_sampler_read_group_rt_async(seir_sampler *s, int32_t first, int32_t count, double *Rg) {
+    return read_group_curves(s, true, true, first, count, Rg, nullptr);
+}
+extern "C" int seir_sampler_read_group_wb(seir_sampler *s, int32_t first, int32_t count, double *Wg, double *Bg) {
+    return read_group_curves(s, false, false, first, count, Wg, Bg);
+}
+extern "C" int seir_sampler_read_group_wb_async(seir_sampler *s, int32_t first, int32_t count, double *Wg, double *Bg) {
+    return read_group_curves(s, false, true, first, count, Wg, Bg);
+}
+
+static void gcurve_wsums_launch(const Dims &d, hipStream_t st, const int *offsets, const int *members, const double *weights,
+                                const double *v, int G, int L, long long ld, long long v_d0, long long out_d0, long long nd,
+                                double *out);
+
+extern "C" int seir_group_wsums(seir_ctx *ctx, const double *v, int64_t nd, int32_t L, int32_t M, int32_t G, const int32_t *offsets,
+                                const int32_t *members, const double *weights, double *out) {
+    int rc = check_batch(ctx, 1);
+    if (rc) return rc;
+    if (!v || !out) return fail(SEIR_ERR_INVALID, "null pointer");
+    if (nd < 1 || M < 1 || L < 1 || nd > 0x7fffffffll)
+        return fail(SEIR_ERR_INVALID, "nd=%lld, M=%d, L=%d: at least one of each, nd below 2^31", (long long)nd, M, L);
+    std::vector<int> seg;
+    if ((rc = groups_parse(G, offsets, members, M, seg))) return rc;
+    const size_t nin = (size_t)nd * L * M, nout = (size_t)nd * G * L, nnz = (size_t)offsets[G];
+    DevBuf dv, dout, doff, dmem, dw;
+    if ((rc = dv.alloc(sizeof(double) * nin)) || (rc = dout.alloc(sizeof(double) * nout)) ||
+        (rc = doff.alloc(sizeof(int) * (size_t)(G + 1))) || (rc = dmem.alloc(sizeof(int) * nnz)) ||
+        (weights && (rc = dw.alloc(sizeof(double) * nnz))))
+        return rc;
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(dv.p, v, sizeof(double) * nin, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(doff.p, offsets, sizeof(int) * (size_t)(G + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dmem.p, members, sizeof(int) * nnz, hipMemcpyHostToDevice, st));
+    if (weights) HIP_TRY(hipMemcpyAsync(dw.p, weights, sizeof(double) * nnz, hipMemcpyHostToDevice, st));
+    gcurve_wsums_launch(whole(ctx, 1).d, st, doff.as<int>(), dmem.as<int>(), dw.as<double>(), dv.as<double>(), G, L, M, 0, 0, nd,
+                        dout.as<double>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, dout.p, sizeof(double) * nout, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
 }
 
 extern "C" int seir_host_alloc(void **p, uint64_t bytes) {
@@ -3750,4 +3967,60 @@ static void groups_launch(const Dims &d, hipStream_t st, const GroupTable &gt, b
         hipLaunchKernelGGL(ev16 ? k_group_sums<1> : k_group_sums<0>, grid, block, 0, st, d, gt, ev, M, L, nchunk, ev_d0 + off,
                            out_d0 + off, (unsigned long long *)out, St0, plane, ndp, (unsigned long long *)state0);
     }
+}
+
+// ===========================================================================
+// Group curves: the launches (declared above, with seir_sampler_rt / _wb and the rest of seir_sampler_group_*).  The header
+// is included here, so that its kernels lie behind every kernel the parent had.
+// ===========================================================================
+#include "group_curve_kernels.h"
+
+static void gcurve_wsums_launch(const Dims &d, hipStream_t st, const int *offsets, const int *members, const double *weights,
+                                const double *v, int G, int L, long long ld, long long v_d0, long long out_d0, long long nd,
+                                double *out) {
+    const int nchunk = (L + GC_WAVES - 1) / GC_WAVES;
+    for (long long off = 0; off < nd; off += GRP_NDMAX) {
+        const dim3 grid((unsigned)(G * nchunk), (unsigned)std::min<long long>(GRP_NDMAX, nd - off)), block(64 * GC_WAVES);
+        hipLaunchKernelGGL(weights ? k_group_wsums<1> : k_group_wsums<0>, grid, block, 0, st, d, offsets, members, weights, v, G, L,
+                           ld, nchunk, v_d0 + off, out_d0 + off, out);
+    }
+}
+
+// The batch's cell planes [nj * B][D][Mp] onto out [.][B][G][D] from slot slot0.
+static void gcurve_sums(seir_sampler *s, const LaunchCfg &l, const GroupCurve &c, int D, int slot0, int nj) {
+    const int B = s->cfg.B;
+    for (int x = 0; x < c.planes; ++x)
+        gcurve_wsums_launch(l.d, l.st, c.offsets, s->grp.members, c.weights, c.cells[x], s->grp.G, D, l.d.Mp, 0,
+                            (long long)slot0 * B, (long long)nj * B, c.out[x]);
+}
+
+static void gcurve_rt_trace_cells(seir_sampler *s, const LaunchCfg &l, int slot0, int nj) {
+    const RtBufs &rb = s->rt;
+    const int B = s->cfg.B;
+    hipLaunchKernelGGL(k_rt_trace_cells<RT_DT>, dim3(rb.ncb, (rb.D + RT_DT - 1) / RT_DT, B), dim3(256),
+                       k_rt_trace_lds_bytes<RT_DT>(l.d.Mp), l.st, l.d, s->ctx->c, rb, (const double *)s->ch.tr_theta, B, slot0, nj,
+                       s->grt.cells[0], (long long)l.d.Mp);
+}
+
+static void gcurve_rt_gather(seir_sampler *s, const LaunchCfg &l, long long pos0, int nj) {
+    const int B = s->cfg.B, D = s->rt.D;
+    hipLaunchKernelGGL(k_rt_cells_from_keep, dim3((l.d.M + 255) / 256, D, B), dim3(256), 0, l.st, l.d, (const double *)s->rt_keep,
+                       s->rt_keep_stride, pos0, B, D, nj, s->grt.cells[0], (long long)l.d.Mp);
+}
+
+static void gcurve_wb_trace_cells(seir_sampler *s, const LaunchCfg &l, int slot0, int nj) {
+    const WbBufs &wb = s->wb;
+    const int B = s->cfg.B;
+    hipLaunchKernelGGL(k_wb_trace_cells<WB_DT>, dim3(wb.ncb, (wb.D + WB_DT - 1) / WB_DT, B), dim3(256),
+                       k_wb_trace_lds_bytes<WB_DT>(l.d.Mp), l.st, l.d, s->ctx->c, wb, (const double *)s->ch.tr_theta, B, slot0, nj,
+                       s->gwb.cells[0], s->gwb.cells[1], (long long)l.d.Mp);
+}
+
+// Above 64 KiB of dynamic LDS a kernel needs the attribute (as k_rt_trace and k_wb_trace get theirs at their resets).
+static void gcurve_lds_attributes(int Mp) {
+    const size_t rl = k_rt_trace_lds_bytes<RT_DT>(Mp), wl = k_wb_trace_lds_bytes<WB_DT>(Mp);
+    if (rl > 64 * 1024)
+        (void)hipFuncSetAttribute((const void *)k_rt_trace_cells<RT_DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rl);
+    if (wl > 64 * 1024)
+        (void)hipFuncSetAttribute((const void *)k_wb_trace_cells<WB_DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl);
 }

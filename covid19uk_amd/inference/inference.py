@@ -113,7 +113,7 @@ class Posterior:
     the int8 enum {FALSE = 0, TRUE = 1}."""
 
     def __init__(self, filename, M, T, mmax, num_samples, burst=100, summaries="off", forecast=None, rt=None, check=None,
-                 within_between=None, groups=None):
+                 within_between=None, groups=None, group_curves=None):
         """`summaries` ("off" | "on" | "only", Mcmc.summaries / --summaries): with "on" and "only" the per-draw marginals
         samples/seir_by_day [n,T,3], samples/seir_by_location [n,M,3], samples/state_by_day [n,T,3] (int64) are written
         with every burst and `write_summary` adds summaries/* at the end of the run; with "only" samples/seir is not
@@ -139,7 +139,12 @@ class Posterior:
         sources are on -- samples/seir_by_group [n,G,T,3] with `summaries` on / only (warm-up rows included, like
         seir_by_day); samples/forecast_by_group [nf,G,H,3] and forecast_group_state0 [nf,G,3] with `forecast`;
         samples/check_by_group [nf,G,K,3] and check_group_state0 [nf,G,3] with `check` -- and `write_groups`,
-        `write_group_forecast`, `write_group_check` add groups/* and the group_* datasets of forecast/ and check/."""
+        `write_group_forecast`, `write_group_check` add groups/* and the group_* datasets of forecast/ and check/.
+
+        `group_curves` ({"rt": (D, n)} and / or {"within_between": (D, n)} or None; Mcmc.groups_rt,
+        Mcmc.groups_within_between; needs `groups`): samples/R_t_by_group [n,G,D], samples/within_pressure_by_group and
+        samples/between_pressure_by_group [n,G,D] (float64), one row per kept draw of the sampling phase, and
+        `write_group_rt`, `write_group_within_between` add the group_* datasets of rt/ and within_between/."""
         self.filename = filename
         self.use_h5 = not str(filename).endswith(".npz") and hdf5io.available()
         self.shapes = {
@@ -186,6 +191,11 @@ class Posterior:
                 if spec is not None:
                     for k, shp in ((f"samples/{src}_by_group", (G, int(spec[0]), 3)), (f"samples/{src}_group_state0", (G, 3))):
                         self.shapes[k], self.dtypes[k], self.rows[k] = shp, np.int64, int(spec[1])
+        for key, names in (("rt", ("R_t_by_group",)), ("within_between", ("within_pressure_by_group", "between_pressure_by_group"))):
+            if group_curves and groups and key in group_curves:
+                for k in names:
+                    self.shapes[f"samples/{k}"] = (int(groups), int(group_curves[key][0]))
+                    self.rows[f"samples/{k}"] = int(group_curves[key][1])
         self._scratch = {}
         if self.use_h5:
             self._file = hdf5io.File(filename, "w")
@@ -334,6 +344,23 @@ class Posterior:
         for name, (own, pooled) in (quantiles or {}).items():
             self.create_dataset(f"forecast/group_{name}_quantiles", np.ascontiguousarray(own, dtype=np.float64))
             self.create_dataset(f"forecast/pooled_group_{name}_quantiles", np.ascontiguousarray(pooled, dtype=np.float64))
+
+    def write_group_rt(self, mean, var, prob_gt1, quantiles=None):
+        """rt/group_R_t_mean, group_R_t_var, group_prob_gt1 [G,D] over this chain's per-draw group curves; `quantiles` (or
+        None): (chain [K,G,D], pooled [K,G,D]) -> rt/group_R_t_quantiles and rt/pooled_group_R_t_quantiles."""
+        for k, v in (("group_R_t_mean", mean), ("group_R_t_var", var), ("group_prob_gt1", prob_gt1)):
+            self.create_dataset(f"rt/{k}", np.ascontiguousarray(v, dtype=np.float64))
+        if quantiles is not None:
+            self.create_dataset("rt/group_R_t_quantiles", np.ascontiguousarray(quantiles[0], dtype=np.float64))
+            self.create_dataset("rt/pooled_group_R_t_quantiles", np.ascontiguousarray(quantiles[1], dtype=np.float64))
+
+    def write_group_within_between(self, defined, within_share_mean, p_within_gt_between):
+        """within_between/group_defined, group_within_share_mean, group_p_within_gt_between [G,D] over this chain's draws:
+        the share is Wg / (Wg + Bg) of the members' summed pressures ("between": from outside each member location, as in
+        the national figure, not from outside the group); a draw with Wg + Bg == 0 is undefined and left out."""
+        for k, v in (("group_defined", defined), ("group_within_share_mean", within_share_mean),
+                     ("group_p_within_gt_between", p_within_gt_between)):
+            self.create_dataset(f"within_between/{k}", np.ascontiguousarray(v, dtype=np.float64))
 
     def write_group_check(self, counts: dict):
         """check/group_* of one chain (`posterior.groups.check_counts`): the raw counts and the mid-p values."""
@@ -670,7 +697,7 @@ def diagnostics_marks(nb):
 
 
 def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_step_size=False, forecast_calendar=None,
-             seed=0, rt_weight=None, check_calendar=None, groups=None):
+             seed=0, rt_weight=None, check_calendar=None, groups=None, population=None):
     """The windowed schedule of inference.py:303-470: fast 200, slow 25*2^k (k<6), fast 50,
     then num_bursts x num_burst_samples with the kernel fixed.  Every draw of the warm-up is
     written, as in the reference (its running variance is formed from every draw of a window);
@@ -708,7 +735,12 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     forecast, check) the table is set on the sampler once, before the first draw: from then on the summary, the forecast
     and the check of every burst also form the draw's sums over each group's members on the device, and these cross with
     the trace.  In the warm-up that rides on the summary which `summaries` already asks for there, and on nothing else.
-    The statistics are formed here (`posterior.groups`).  Without it nothing of it is called."""
+    The statistics are formed here (`posterior.groups`).  Without it nothing of it is called.
+
+    With Mcmc.groups_rt (needs `groups`, Mcmc.rt and `population` = N [M]) and Mcmc.groups_within_between (needs `groups`
+    and Mcmc.within_between) the switches are set on the sampler once, behind the table: R_t, population-weighted, and the
+    within / between pressures of every kept draw of the sampling phase are then also formed per group on the device and
+    cross with the trace (`trace.group_curves`).  Without the keys nothing of it is called."""
     thin = thin_interval(config)
     wb_days = within_between_mode(config, T=getattr(sampler, "T", None))
     check_days = check_mode(config, T=getattr(sampler, "T", None))
@@ -735,15 +767,29 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
         marks = diagnostics_marks(int(config["num_bursts"]))
         theta_acc = diag_mod.DrawAccumulator(batch_len)
     grp_fc, grp_ck = [], []                                 # the sampling phase's group sums, kept for the statistics
+    grp_rt, grp_wb = [], []                                 # and its group curves
+    groups_rt = G_mod.switch(config.get("groups_rt"), "groups_rt")
+    groups_wb = G_mod.switch(config.get("groups_within_between"), "groups_within_between")
+    G_mod.require_curves(groups, groups_rt, rt_days, groups_wb, wb_days)
+    if groups_rt and population is None:
+        raise ValueError("groups_rt: run_mcmc needs population = N")
     if groups is not None:
-        G_mod.require_source(groups, summaries, horizon, check_days)
+        G_mod.require_source(groups, summaries, horizon, check_days, groups_rt, groups_wb)
         sampler.set_groups(groups.offsets, groups.members)  # once; the sources size their outputs at their resets
+        if groups_rt:
+            rt_w = G_mod.rt_weights(groups, population)
+            sampler.set_group_rt(rt_w)                      # once, behind the table; sized at the rt reset
+            for post in posteriors:
+                post.create_dataset("groups/rt_weights", rt_w)
+        if groups_wb:
+            sampler.set_group_within_between(True)
         # the sources whose sums are written: the trace's only with summaries on / only (diagnostics alone also summarises
         # every burst, but nothing of it goes to the file)
         grp_src = tuple(k for k, on in (("trace", summaries != "off"), ("forecast", horizon), ("check", check_days)) if on)
         if summaries != "off":
             warm_kw = dict(warm_kw, groups=("trace",))
-        burst_kw = dict(burst_kw, groups=grp_src)
+        if grp_src:                                         # with the group curves alone there is nothing to ask for
+            burst_kw = dict(burst_kw, groups=grp_src)
     sampler.set_thin(1)
     first_window_size, last_window_size, slow_window_size, num_slow_windows = 200, 50, 25, 6
     dual_averaging_kwargs = {"target_accept_prob": 0.75}
@@ -769,6 +815,17 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
                     post.write_samples({"seir_by_group": g["seir_by_group"][:, c]}, first_dim_offset=offset)
                 post.write_samples({k: v[:, c] for k, v in g.items() if k.startswith("forecast_")}, first_dim_offset=fc_offset)
                 post.write_samples({k: v[:, c] for k, v in g.items() if k.startswith("check_")}, first_dim_offset=ck_offset)
+        if (groups_rt or groups_wb) and getattr(tr, "group_curves", None) is not None:
+            gc = {k: np.array(v) for k, v in tr.group_curves.items()}   # the pinned buffer is used again two bursts later
+            if "rt_by_group" in gc:
+                grp_rt.append(gc["rt_by_group"])
+                for c, post in enumerate(posteriors):
+                    post.write_samples({"R_t_by_group": gc["rt_by_group"][:, c]}, first_dim_offset=rt_offset)
+            if "within_by_group" in gc:
+                grp_wb.append((gc["within_by_group"], gc["between_by_group"]))
+                for c, post in enumerate(posteriors):
+                    post.write_samples({"within_pressure_by_group": gc["within_by_group"][:, c],
+                                        "between_pressure_by_group": gc["between_by_group"][:, c]}, first_dim_offset=wb_offset)
         if wb_days and getattr(tr, "wb", None) is not None:
             w = {k: np.array(v) for k, v in tr.wb.items()}  # the pinned buffer is used again two bursts later
             wb_draws.append(w)
@@ -948,7 +1005,27 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
                 post.write_group_check(G_mod.check_counts(sim[:, c], groups.sum_rows(cs.observed[c])))
         sources = [k for k, on in (("the recorded epidemic", summaries != "off"), ("the forecast", horizon), ("the check", check_days))
                    if on]
-        print(G_mod.run_line(groups, sources), file=log, flush=True)
+        if sources:
+            print(G_mod.run_line(groups, sources), file=log, flush=True)
+        if groups_rt:
+            rg = np.concatenate(grp_rt) if grp_rt else np.empty((0, sampler.B, groups.G, rt_days))   # [n,B,G,D]
+            q = None
+            if rq_probs and rg.shape[0]:
+                q = (draw_quantiles(rg, rq_probs), draw_quantiles(rg.reshape((-1,) + rg.shape[2:]), rq_probs))   # [K,B,G,D], [K,G,D]
+            for c, post in enumerate(posteriors):
+                post.write_group_rt(*G_mod.curve_moments(rg[:, c]), None if q is None else (q[0][:, c], q[1]))
+            print(G_mod.curve_run_line("R_t", groups, rg, "samples/R_t_by_group and rt/group_*"), file=log, flush=True)
+        if groups_wb:
+            empty = np.empty((0, sampler.B, groups.G, wb_days))
+            wg = np.concatenate([x[0] for x in grp_wb]) if grp_wb else empty
+            bg = np.concatenate([x[1] for x in grp_wb]) if grp_wb else empty
+            for c, post in enumerate(posteriors):
+                post.write_group_within_between(*G_mod.share_stats(wg[:, c], bg[:, c]))
+            with np.errstate(divide="ignore", invalid="ignore"):
+                share = wg / (wg + bg)
+            print(G_mod.curve_run_line("Within share of the infection pressure (between: from outside each member location)",
+                                       groups, share, "samples/*_pressure_by_group and within_between/group_*"),
+                  file=log, flush=True)
     if wb_days:
         ws = sampler.within_between_summary()
         wm, wv, bm, pg = ws.within_mean, ws.within_var, ws.between_mean, ws.p_within_gt_between
@@ -1024,7 +1101,7 @@ def launch_forms(lay, device_arg, hmc="auto", moves="auto", env=os.environ):
 def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool_step_size=False, init_jitter=0.0,
          events_dtype="auto", hmc="auto", moves="auto", thin=None, summaries=None, diagnostics=None, diagnostics_batch=None,
          forecast=None, forecast_walk=None, rt=None, check=None, forecast_quantiles=None, within_between=None,
-         rt_quantiles=None, groups=None):
+         rt_quantiles=None, groups=None, groups_rt=None, groups_within_between=None):
     """Constructs and runs the MCMC (covid19uk/inference/inference.py:473-608).
 
     Multi-GPU: launched as one process per GPU, every rank runs `num_chains` chains with
@@ -1037,7 +1114,8 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     config["forecast_walk"] (`forecast_mode`), `forecast_quantiles` config["forecast_quantiles"]
     (`forecast_quantiles_mode`), `rt` config["rt"] (`rt_mode`), `check` config["check"] (`check_mode`), `within_between`
     config["within_between"] (`within_between_mode`), `rt_quantiles` config["rt_quantiles"] (`rt_quantiles_mode`), `groups`
-    config["groups"] (`posterior.groups.parse_groups`: "nations" or a mapping name -> members)."""
+    config["groups"] (`posterior.groups.parse_groups`: "nations" or a mapping name -> members), `groups_rt` config["groups_rt"]
+    and `groups_within_between` config["groups_within_between"] (on / off; `posterior.groups.require_curves`)."""
     wb_days = 0
     if within_between is not None or "within_between" in config:
         wb_days = within_between_mode(config, within_between)   # refused here: before any GPU call
@@ -1078,14 +1156,22 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
         mode, batch_len = diagnostics_mode(config, diagnostics, diagnostics_batch)   # and too few bursts, or a batch length that does not fit
         config = dict(config, diagnostics=mode, **(dict(diagnostics_batch=batch_len) if mode == "on" else {}))
     group_spec = config.get("groups") if groups is None else groups
-    config = {k: v for k, v in config.items() if k != "groups"}
+    grp_rt_on = G_mod.switch(config.get("groups_rt") if groups_rt is None else groups_rt, "groups_rt")
+    grp_wb_on = G_mod.switch(config.get("groups_within_between") if groups_within_between is None else groups_within_between,
+                             "groups_within_between")
+    config = {k: v for k, v in config.items() if k not in ("groups", "groups_rt", "groups_within_between")}
+    if grp_rt_on:
+        config = dict(config, groups_rt=True)
+    if grp_wb_on:
+        config = dict(config, groups_within_between=True)
     lay = job_layout(num_chains, device)                    # before any GPU call
     cov, cases, dates = read_inference_data(data_file)
     # the table against the input's locations, and groups without a source: refused here, before any GPU call
     group_table = None
     if not G_mod.is_off(group_spec):                        # absent: the input's location coordinate is not even opened
         group_table = G_mod.parse_groups(group_spec, cases.shape[0], read_location_names(data_file))
-    G_mod.require_source(group_table, config["summaries"], horizon, check_days)
+    G_mod.require_curves(group_table, grp_rt_on, rt_days, grp_wb_on, wb_days)   # likewise before any GPU call
+    G_mod.require_source(group_table, config["summaries"], horizon, check_days, grp_rt_on, grp_wb_on)
     rng = np.random.default_rng(seed)                       # same imputation on every rank: one initial state per job
     B = int(num_chains)
     initial_state, events = model_spec.initial_conditions(cases, cov.N, rng)
@@ -1134,7 +1220,10 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
                             **(dict(check=(check_days, int(config["num_burst_samples"]) * int(config["num_bursts"]))) if check_days else {}),
                             **(dict(within_between=(wb_days, int(config["num_burst_samples"]) * int(config["num_bursts"])))
                                if wb_days else {}),
-                            **(dict(groups=group_table.G) if group_table is not None else {}))
+                            **(dict(groups=group_table.G) if group_table is not None else {}),
+                            **(dict(group_curves={k: (d, int(config["num_burst_samples"]) * int(config["num_bursts"]))
+                                                  for k, on, d in (("rt", grp_rt_on, rt_days), ("within_between", grp_wb_on, wb_days))
+                                                  if on}) if grp_rt_on or grp_wb_on else {}))
                   for name in names]
     fc_kw = {}
     if horizon:
@@ -1149,6 +1238,8 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
         fc_kw["seed"] = seed
     if group_table is not None:
         fc_kw["groups"] = group_table
+        if grp_rt_on:
+            fc_kw["population"] = np.asarray(cov.N, dtype=np.float64).reshape(-1)
         for post in posteriors:
             post.write_groups(group_table, cov.N, initial_state)
     run_mcmc(sampler, config, posteriors, pool_step_size=pool_step_size and total > 1, **fc_kw)
@@ -1259,6 +1350,15 @@ def main(argv=None):
                              "coordinate), or a path to a YAML mapping name: [members], a member being a location code, a "
                              "prefix pattern E0* or an integer index; groups/*, samples/*_by_group and the group_* datasets "
                              "of forecast/ and check/; needs one of --summaries on/only, --forecast, --check")
+    parser.add_argument("--groups-rt", action="store_true", default=None, dest="groups_rt",
+                        help="R_t of every kept draw per group, population-weighted over the group's members, formed on the "
+                             "device (overrides Mcmc.groups_rt; needs --groups and --rt): samples/R_t_by_group, rt/group_R_t_mean, "
+                             "group_R_t_var, group_prob_gt1 and, with --rt-quantiles, rt/group_R_t_quantiles")
+    parser.add_argument("--groups-within-between", action="store_true", default=None, dest="groups_within_between",
+                        help="within / between infection pressure of every kept draw per group, formed on the device (overrides "
+                             "Mcmc.groups_within_between; needs --groups and --within-between): samples/within_pressure_by_group, "
+                             "between_pressure_by_group and within_between/group_*; 'between' is from outside each member "
+                             "location, as in the national figure, not from outside the group")
     args = parser.parse_args(argv)
     if args.thin is not None and args.thin < 1:
         parser.error(f"--thin {args.thin}: the thinning interval is >= 1")
@@ -1272,7 +1372,9 @@ def main(argv=None):
          **({} if args.within_between is None else dict(within_between=args.within_between)),
          **({} if args.forecast_quantiles is None else dict(forecast_quantiles=args.forecast_quantiles)),
          **({} if args.rt_quantiles is None else dict(rt_quantiles=args.rt_quantiles)),
-         **({} if args.groups is None else dict(groups=G_mod.load_spec(args.groups))))
+         **({} if args.groups is None else dict(groups=G_mod.load_spec(args.groups))),
+         **({} if args.groups_rt is None else dict(groups_rt=True)),
+         **({} if args.groups_within_between is None else dict(groups_within_between=True)))
 
 
 if __name__ == "__main__":

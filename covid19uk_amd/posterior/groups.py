@@ -12,7 +12,12 @@ Everything that is made of those sums is defined here and nowhere else:
     their mid-p values.
 
 The locations of a draw are correlated through the commuting matrix: none of this can be had from per-location moments
-or quantiles, which is why the sums are formed per draw."""
+or quantiles, which is why the sums are formed per draw.
+
+The group curves (`Mcmc: groups_rt`, `groups_within_between`; include/seir_hip.h, "Group curves on the device") are sums of
+fp64 values, whose bits depend on the order of the adds.  `weighted_sum_rows` is the one host definition of that order --
+the device's (csrc/group_curve_kernels.h), restated in NumPy -- and `rt_weights`, `curve_moments`, `share_stats` are what
+the run makes of the curves."""
 from dataclasses import dataclass
 
 import numpy as np
@@ -39,6 +44,84 @@ class GroupTable:
         """x with `axis` indexed by location -> the same with that axis indexed by group (sums over the members)."""
         x = np.moveaxis(np.asarray(x), axis, 0)
         return np.moveaxis(np.stack([x[self.rows(g)].sum(axis=0) for g in range(self.G)]), 0, axis)
+
+
+WAVE = 64                         # lanes of the fixed order of `weighted_sum_rows`
+
+
+def weighted_sum_rows(table, v, weights=None, axis=-1):
+    """The group sums of fp64 values in the device's fixed order: `v` float64 with `axis` indexed by location -> the same
+    with that axis indexed by group; `weights` [nnz] aligned with `table.members`, or None.
+
+    For one group with members m_0 < ... < m_{n-1} in CSR order: lane l in [0, 64) starts from +0.0 and adds, for
+    k = l, l + 64, ... < n ascending, p = w_k * v[m_k] (one rounding; unweighted p = v[m_k]), one rounding per add; then for
+    o = 32, 16, 8, 4, 2, 1, all lanes at once, a_l = a_l + a_{l xor o}; the result is a_0.  No fused multiply-add."""
+    x = np.moveaxis(np.asarray(v, np.float64), axis, -1)
+    w = None if weights is None else np.asarray(weights, np.float64).reshape(-1)
+    if w is not None and w.shape != np.shape(table.members):
+        raise ValueError(f"weights {w.shape}: aligned with the table's members {np.shape(table.members)}")
+    lanes = np.arange(WAVE)
+    out = np.empty(x.shape[:-1] + (table.G,))
+    for g in range(table.G):
+        beg, end = int(table.offsets[g]), int(table.offsets[g + 1])
+        p = x[..., table.members[beg:end]]
+        if w is not None:
+            p = w[beg:end] * p
+        a = np.zeros(x.shape[:-1] + (WAVE,))
+        for k0 in range(0, end - beg, WAVE):
+            c = p[..., k0:k0 + WAVE]
+            a[..., :c.shape[-1]] = a[..., :c.shape[-1]] + c
+        for o in (32, 16, 8, 4, 2, 1):
+            a = a + a[..., lanes ^ o]
+        out[..., g] = a[..., 0]
+    return np.moveaxis(out, -1, axis)
+
+
+def rt_weights(table, N):
+    """The weights of the population-weighted group R_t: N[members] / the group's population, float64 [nnz].  The array
+    handed to the device is the definition (groups/rt_weights)."""
+    N = np.asarray(N, np.float64).reshape(-1)
+    pop = table.sum_rows(N)
+    return np.concatenate([N[table.rows(g)] / pop[g] for g in range(table.G)])
+
+
+def curve_moments(curves):
+    """Per-draw curves [n, ...] -> (mean, var (ddof 0), P(curve > 1)) over the draws, each [...]; NaN without draws."""
+    c = np.asarray(curves, np.float64)
+    if c.shape[0] == 0:
+        nan = np.full(c.shape[1:], np.nan)
+        return nan, nan.copy(), nan.copy()
+    return c.mean(axis=0), c.var(axis=0), (c > 1.0).mean(axis=0)
+
+
+def share_stats(within, between):
+    """Per-draw group pressures [n, ...] -> (defined, within_share_mean, p_within_gt_between), each [...]: the share is
+    Wg / (Wg + Bg); a draw with Wg + Bg == 0 (or a share that is not finite) is undefined and left out; NaN where no draw is
+    defined."""
+    wg, bg = np.asarray(within, np.float64), np.asarray(between, np.float64)
+    tot = wg + bg
+    with np.errstate(divide="ignore", invalid="ignore"):
+        share = wg / tot
+    ok = (tot != 0.0) & np.isfinite(share)
+    n = ok.sum(axis=0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = np.where(ok, share, 0.0).sum(axis=0) / n
+        gt = (ok & (wg > bg)).sum(axis=0) / n
+    return n.astype(np.float64), np.where(n > 0, mean, np.nan), np.where(n > 0, gt, np.nan)
+
+
+def curve_run_line(what, table, curves, dataset):
+    """One log line for a per-draw group curve [n, B, G, D]: every group's last-day mean with its 0.05 / 0.95 quantiles
+    over all draws and chains of this process."""
+    c = np.asarray(curves, np.float64)
+    if c.shape[0] == 0:
+        return f"{what} by group: no draws; {dataset} written"
+    last = c[..., -1].reshape(-1, c.shape[2])              # [n * B, G]
+    q = quantiles(last, (0.05, 0.95))
+    shown = ", ".join(f"{name} {last[:, g].mean():.3g} [{q[0, g]:.3g}, {q[1, g]:.3g}]"
+                      for g, name in list(enumerate(table.names))[:6]) + (", ..." if table.G > 6 else "")
+    return (f"{what} by group, last day, mean [0.05, 0.95] over {last.shape[0]} draw(s): {shown}; formed per draw on the "
+            f"device; {dataset} written")
 
 
 def _table(named_rows, what):
@@ -134,10 +217,32 @@ def load_spec(value):
     return spec
 
 
-def require_source(table, summaries, horizon, check_days):
-    """`groups` without any of summaries on / only, forecast, check would launch and write nothing: refused."""
-    if table is not None and summaries == "off" and not horizon and not check_days:
+def require_source(table, summaries, horizon, check_days, groups_rt=False, groups_within_between=False):
+    """`groups` without any of summaries on / only, forecast, check -- or one of the group curves `groups_rt`,
+    `groups_within_between` -- would launch and write nothing: refused."""
+    if table is not None and summaries == "off" and not horizon and not check_days and not groups_rt and not groups_within_between:
         raise ValueError("groups given without any of summaries on/only, forecast, check: it would have no effect")
+
+
+def require_curves(table, groups_rt, rt_days, groups_within_between, wb_days):
+    """`groups_rt` needs `groups` and `rt`, `groups_within_between` needs `groups` and `within_between`: refused otherwise."""
+    for on, key, need, days in ((groups_rt, "groups_rt", "rt", rt_days),
+                                (groups_within_between, "groups_within_between", "within_between", wb_days)):
+        if on and table is None:
+            raise ValueError(f"{key} given without groups: there is no table of groups to form the curves over")
+        if on and not days:
+            raise ValueError(f"{key} given without {need}: it would have no effect")
+
+
+def switch(value, name):
+    """An on / off key of the configuration (absent: off): True, False, "on", "off"."""
+    if value is None or value is False:
+        return False
+    if value is True:
+        return True
+    if isinstance(value, str) and value.strip().lower() in ("on", "off"):
+        return value.strip().lower() == "on"
+    raise ValueError(f"{name}={value!r}: on or off")
 
 
 def group_state(events_by_group, state0):

@@ -43,6 +43,7 @@ class Trace:
     check: dict = None       # CHECK_KEYS -> int64 [n,B,K,3] / [n,B,M,3] / [n,B,K,3]; None unless the draws were checked
     wb: dict = None          # WB_KEYS -> float64 [n,B,D] national within / between pressure; None unless asked for
     groups: dict = None      # GROUP_KEYS of the sources that ran -> int64 [n,B,G,L,3] / [n,B,G,3]; None unless asked for
+    group_curves: dict = None  # GROUP_CURVE_KEYS of the curves that are on -> float64 [n,B,G,D]; None unless one is on
 
 
 MARGINAL_KEYS = ("events_by_day", "events_by_location", "state_by_day")
@@ -54,6 +55,8 @@ WB_KEYS = ("within_pressure", "between_pressure")
 GROUP_SOURCES = {"trace": (0, "seir_by_group", None), "forecast": (1, "forecast_by_group", "forecast_group_state0"),
                  "check": (2, "check_by_group", "check_group_state0")}
 GROUP_KEYS = tuple(k for _, ev, st in GROUP_SOURCES.values() for k in (ev, st) if k)
+# group curves (set_group_rt / set_group_within_between): R_t and the within / between pressures of a draw per group
+GROUP_CURVE_KEYS = ("rt_by_group", "within_by_group", "between_by_group")
 SUMMARY_QUANTITIES = ("k_se", "k_ei", "k_ir", "S", "E", "I")
 
 
@@ -239,7 +242,7 @@ class PinnedTrace:
     `ChainSampler.read_trace_async`.  Views are valid until close()."""
 
     def __init__(self, sampler: "ChainSampler", count: int, events: bool = True, marginals: bool = False,
-                 forecast: int = 0, rt: int = 0, check: int = 0, wb: int = 0, groups=None):
+                 forecast: int = 0, rt: int = 0, check: int = 0, wb: int = 0, groups=None, group_curves=None):
         self._lib = sampler._lib
         self.count = int(count)
         B, P, M, T = sampler.B, sampler.P, sampler.M, sampler.T
@@ -277,6 +280,11 @@ class PinnedTrace:
                 self.groups[ev_key] = self._alloc((count, B, G, int(L), 3), np.int64)
                 if st_key:
                     self.groups[st_key] = self._alloc((count, B, G, 3), np.int64)
+        # group_curves: (G, {key of GROUP_CURVE_KEYS: window days}) -- the curves that run with the burst
+        self.group_curves = None
+        if group_curves:
+            G, days = group_curves
+            self.group_curves = {k: self._alloc((count, B, G, int(D)), np.float64) for k, D in days.items()}
 
     def _alloc(self, shape, dtype):
         nbytes = int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize
@@ -288,7 +296,7 @@ class PinnedTrace:
 
     def close(self):
         self.theta = self.events = self.hmc = self.moves = self.marginals = self.forecast = self.rt = self.check = self.wb = None
-        self.groups = None
+        self.groups = self.group_curves = None
         for p in self._ptrs:
             self._lib.seir_host_free(p)
         self._ptrs = []
@@ -311,6 +319,11 @@ class ChainSampler:
     _check_K = 0                  # window of the in-sample check in force (0: reset_check was never called)
     _wb_D = 0                     # window of the within/between shares in force (0: reset_within_between was never called)
     _groups_G = 0                 # groups of the table in force (0: none set)
+    _groups_nnz = 0               # members of the table in force
+    _group_rt_on = False          # set_group_rt: group R_t rides on rt
+    _group_wb_on = False          # set_group_within_between: group within / between rides on within_between
+    _group_rt_refused = False     # the last reset_rt could not size the group outputs: rt is on without them
+    _group_wb_refused = False
     first_chain_id = 0
 
     def __init__(self, model: SeirModel, config: dict, num_chains: int, seed: int = 0,
@@ -582,6 +595,8 @@ class ChainSampler:
             tr.wb = {k: v[:n] for k, v in buf.wb.items()}
         if getattr(buf, "groups", None) is not None:
             tr.groups = {k: v[:n] for k, v in buf.groups.items()}
+        if getattr(buf, "group_curves", None) is not None:
+            tr.group_curves = {k: v[:n] for k, v in buf.group_curves.items()}
         return tr
 
     # -- summaries of the recorded events on the device (include/seir_hip.h) --------------------------
@@ -755,8 +770,13 @@ class ChainSampler:
         w = np.ascontiguousarray(weight, dtype=np.float64).reshape(-1)
         if w.shape != (self.M,):
             raise ValueError(f"need weight [{self.M}]")
-        _lib.check(self._lib.seir_sampler_rt_reset(self._s, D, _dptr(w)))
-        self._rt_D = D
+        try:
+            _lib.check(self._lib.seir_sampler_rt_reset(self._s, D, _dptr(w)))
+        except _lib.SeirError as e:
+            if self._group_rt_on and "group curves" in str(e):   # the reset is done; the group outputs were refused
+                self._rt_D, self._group_rt_refused = D, True
+            raise
+        self._rt_D, self._group_rt_refused = D, False
 
     def rt(self, first: int, count: int):
         """Enqueue R_it of trace slots [first, first+count) behind the sweeps that fill them: folded into the moments,
@@ -878,8 +898,13 @@ class ChainSampler:
         D = int(days)
         if not 1 <= D <= self.T:
             raise ValueError(f"within_between days {D}: 1 <= D <= T = {self.T}")
-        _lib.check(self._lib.seir_sampler_wb_reset(self._s, D))
-        self._wb_D = D
+        try:
+            _lib.check(self._lib.seir_sampler_wb_reset(self._s, D))
+        except _lib.SeirError as e:
+            if self._group_wb_on and "group curves" in str(e):   # the reset is done; the group outputs were refused
+                self._wb_D, self._group_wb_refused = D, True
+            raise
+        self._wb_D, self._group_wb_refused = D, False
 
     def within_between(self, first: int, count: int):
         """Enqueue the shares of trace slots [first, first+count) behind the sweeps that fill them: folded into the
@@ -926,7 +951,8 @@ class ChainSampler:
         i32p = ctypes.POINTER(ctypes.c_int32)
         if offsets is None:
             _lib.check(self._lib.seir_sampler_groups_set(self._s, 0, None, None))
-            self._groups_G = 0
+            self._groups_G = self._groups_nnz = 0
+            self._group_rt_on = self._group_wb_on = False
             return
         off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
         mem = np.ascontiguousarray(members, dtype=np.int32).reshape(-1)
@@ -936,8 +962,92 @@ class ChainSampler:
                              "CSR pair of at least one group")
         if G > _lib.GROUPS_MAX:
             raise ValueError(f"G={G}: at most {_lib.GROUPS_MAX} groups")
-        _lib.check(self._lib.seir_sampler_groups_set(self._s, G, off.ctypes.data_as(i32p), mem.ctypes.data_as(i32p)))
-        self._groups_G = G
+        try:
+            _lib.check(self._lib.seir_sampler_groups_set(self._s, G, off.ctypes.data_as(i32p), mem.ctypes.data_as(i32p)))
+        except _lib.SeirError as e:
+            if "group curves" not in str(e):
+                raise
+            # the table is in force; group within / between could not be sized for it
+            self._groups_G, self._groups_nnz, self._group_rt_on, self._group_wb_refused = G, int(off[G]), False, True
+            raise
+        self._groups_G, self._groups_nnz = G, int(off[G])
+        self._group_rt_on = False                           # its weights belonged to the old table
+        self._group_wb_refused = False
+
+    # -- group curves: R_t and within / between per group (include/seir_hip.h, "Group curves on the device") ------------
+    def set_group_rt(self, weights):
+        """Group R_t on: while a table is set and `rt` runs, every draw it folds also leaves, per group and window day, the
+        sum over the members of weights[k] * R_it (`weights` [nnz] float64 aligned with the table's `members`; for a
+        population-weighted curve N[members] / the group's population) in the fixed order of
+        `posterior.groups.weighted_sum_rows`.  None switches it off.  A later `set_groups` switches it off too."""
+        if weights is None:
+            _lib.check(self._lib.seir_sampler_group_rt(self._s, None))
+            self._group_rt_on = False
+            return
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if self._groups_G and w.size != self._groups_nnz:
+            raise ValueError(f"need weights [{self._groups_nnz}], aligned with the table's members")
+        try:
+            _lib.check(self._lib.seir_sampler_group_rt(self._s, _dptr(w)))   # SEIR_ERR_STATE without a table
+        except _lib.SeirError as e:
+            if "group curves" in str(e):                    # outputs refused: the switch is off; any other refusal left it alone
+                self._group_rt_on = False
+            raise
+        self._group_rt_on, self._group_rt_refused = True, False
+
+    def set_group_within_between(self, on: bool):
+        """Group within / between on or off: while a table is set and `within_between` runs, every draw it folds also
+        leaves the members' sums of the within and the between pressure per group and window day ("between": from outside
+        each member location, as in the national figure)."""
+        try:
+            _lib.check(self._lib.seir_sampler_group_wb(self._s, 1 if on else 0))
+        except _lib.SeirError as e:
+            if "group curves" in str(e):                    # outputs refused: the switch is off; any other refusal left it alone
+                self._group_wb_on = False
+            raise
+        self._group_wb_on, self._group_wb_refused = bool(on), False
+
+    def _group_curve_days(self, do_rt, do_wb):
+        """{key of GROUP_CURVE_KEYS: window days} of the curves that leave outputs with a burst that runs rt / within_between."""
+        days = {}
+        if do_rt and self._group_rt_on and self._groups_G and not self._group_rt_refused:
+            days["rt_by_group"] = self._rt_D
+        if do_wb and self._group_wb_on and self._groups_G and not self._group_wb_refused:
+            days["within_by_group"] = days["between_by_group"] = self._wb_D
+        return days
+
+    def read_group_rt(self, count: int, first: int = 0) -> np.ndarray:
+        """Blocking read of the group R_t of trace slots [first, first+count): float64 [count,B,G,D]."""
+        out = np.empty((int(count), self.B, self._groups_G, self._rt_D))
+        _lib.check(self._lib.seir_sampler_read_group_rt(self._s, int(first), int(count), _dptr(out)))
+        return out
+
+    def read_group_wb(self, count: int, first: int = 0) -> dict:
+        """Blocking read of the group pressures of trace slots [first, first+count): within_by_group, between_by_group
+        -> float64 [count,B,G,D]."""
+        out = {k: np.empty((int(count), self.B, self._groups_G, self._wb_D)) for k in GROUP_CURVE_KEYS[1:]}
+        _lib.check(self._lib.seir_sampler_read_group_wb(self._s, int(first), int(count), *(_dptr(out[k]) for k in GROUP_CURVE_KEYS[1:])))
+        return out
+
+    def _read_group_curves(self, days, count, first=0, into=None):
+        """The curves of `_group_curve_days` of slots [first, first+count): blocking into new arrays, or on the copy stream
+        `into` the arrays of a PinnedTrace (completed by `trace_wait()`)."""
+        if into is None:
+            out = {}
+            if "rt_by_group" in days:
+                out["rt_by_group"] = self.read_group_rt(count, first)
+            if "within_by_group" in days:
+                out.update(self.read_group_wb(count, first))
+            return out
+        if int(count) > into.count or getattr(into, "group_curves", None) is None or any(k not in into.group_curves for k in days):
+            raise ValueError("pinned buffer too small or without group curves")
+        g = into.group_curves
+        if "rt_by_group" in days:
+            _lib.check(self._lib.seir_sampler_read_group_rt_async(self._s, int(first), int(count), _dptr(g["rt_by_group"])))
+        if "within_by_group" in days:
+            _lib.check(self._lib.seir_sampler_read_group_wb_async(self._s, int(first), int(count), _dptr(g["within_by_group"]),
+                                                                  _dptr(g["between_by_group"])))
+        return g
 
     def _group_len(self, source):
         return {"trace": self.T if self._summary_on else 0, "forecast": self._forecast_H, "check": self._check_K}[source]
@@ -1027,7 +1137,10 @@ class ChainSampler:
 
         `groups` (True, or a tuple of "trace", "forecast", "check"; needs `set_groups` and the matching `summarize`,
         `forecast`, `check`): the group sums that the summary, the forecast and the check of every burst form while a table
-        is set cross with the trace (`trace.groups`), all of them or the named ones."""
+        is set cross with the trace (`trace.groups`), all of them or the named ones.
+
+        The group curves have no keyword: while `set_group_rt` / `set_group_within_between` is on, the curves that `rt` /
+        `within_between` leave per group cross with the trace (`trace.group_curves`)."""
         from concurrent.futures import ThreadPoolExecutor
         do_sum, accumulate = self._summarize_mode(summarize)
         burst, num_bursts = int(burst), int(num_bursts)
@@ -1040,9 +1153,11 @@ class ChainSampler:
         do_wb = bool(within_between)
         grp_src = self._group_sources(groups, do_sum, do_fc, do_ck)
         grp_lens = {k: self._group_len(k) for k in grp_src}
+        gc_days = self._group_curve_days(do_rt, do_wb)
         key = (burst, bool(events), do_sum, self._forecast_H if do_fc else 0) + ((self._rt_D,) if do_rt else ()) + \
             ((("check", self._check_K),) if do_ck else ()) + ((("wb", self._wb_D),) if do_wb else ()) + \
-            ((("groups", self._groups_G, tuple(grp_lens.items())),) if grp_src else ())
+            ((("groups", self._groups_G, tuple(grp_lens.items())),) if grp_src else ()) + \
+            ((("group_curves", self._groups_G, tuple(gc_days.items())),) if gc_days else ())
         if getattr(self, "_pinned_key", None) != key:
             for bf in getattr(self, "_pinned", []):
                 bf.close()
@@ -1057,6 +1172,8 @@ class ChainSampler:
                 mk["wb"] = self._wb_D
             if grp_src:
                 mk["groups"] = (self._groups_G, grp_lens)
+            if gc_days:
+                mk["group_curves"] = (self._groups_G, gc_days)
             self._pinned = [PinnedTrace(self, burst, events, **mk), PinnedTrace(self, burst, events, **mk)]
             self._pinned_key = key
         bufs = self._pinned
@@ -1110,6 +1227,8 @@ class ChainSampler:
                                 self.read_wb_draws_async(burst, h * burst, bufs[h])
                             for src in grp_src:
                                 self.read_group_marginals_async(src, burst, h * burst, bufs[h])
+                            if gc_days:
+                                self._read_group_curves(gc_days, burst, h * burst, bufs[h])
                             prev = i
                             i += 1
                     except _lib.HandoffTimeout as e:
@@ -1135,9 +1254,11 @@ class ChainSampler:
         """reset_trace + run + read: the analogue of one `sample_chain` call with `num_sweeps` results, each the last of
         `thin` sweeps.  `summarize` as in `sample_bursts`: the burst is summarised on the device and `trace.marginals`
         filled; `forecast` likewise (`trace.forecast`), `rt` (`trace.rt`), `check` (`trace.check`), `within_between` (`trace.wb`)
-        and `groups` (`trace.groups`)."""
+        and `groups` (`trace.groups`); the group curves that are on (`set_group_rt`, `set_group_within_between`) ride on
+        `rt` / `within_between` (`trace.group_curves`)."""
         do_sum, accumulate = self._summarize_mode(summarize)
         grp_src = self._group_sources(groups, do_sum, bool(forecast), bool(check))
+        gc_days = self._group_curve_days(bool(rt), bool(within_between))
         if num_sweeps > self.cap:
             raise ValueError(f"num_sweeps={num_sweeps} exceeds trace_capacity={self.cap}")
         while True:
@@ -1171,6 +1292,8 @@ class ChainSampler:
                     tr.groups = {}
                     for src in grp_src:
                         tr.groups.update(self.read_group_marginals(src, num_sweeps))
+                if gc_days:
+                    tr.group_curves = self._read_group_curves(gc_days, num_sweeps)
             except _lib.HandoffTimeout as e:
                 if not self.auto_recover:
                     raise

@@ -326,6 +326,33 @@ class SeirModel:
                                              mem_arg.ctypes.data_as(ip), out.ctypes.data_as(_lib.c_int64_p)))
         return out
 
+    def group_wsums(self, v, offsets, members, weights=None):
+        """Group sums of fp64 values on the device (csrc/group_curve_kernels.h; include/seir_hip.h, seir_group_wsums): `v`
+        float64 [nd, L, M] (L and M the array's own), the groups a CSR pair as for `group_sums`, `weights` [nnz] aligned with
+        `members` or None.  Returns float64 [nd, G, L]: the bits of `posterior.groups.weighted_sum_rows`."""
+        x = np.ascontiguousarray(v, dtype=np.float64)
+        if x.ndim != 3:
+            raise ValueError(f"v {x.shape}: need [nd, L, M]")
+        off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
+        mem = np.ascontiguousarray(members, dtype=np.int32).reshape(-1)
+        G = off.size - 1
+        if G >= 1 and mem.size < int(off.max()):            # what the library cannot check: it reads members up to the offsets
+            raise ValueError(f"offsets reach {int(off.max())}, members holds {mem.size}")
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+            if w.size != mem.size:
+                raise ValueError(f"weights [{w.size}] are not aligned with members [{mem.size}]")
+        nd, L, M = x.shape
+        out = np.empty((nd, max(G, 0), L), dtype=np.float64)
+        ip = ctypes.POINTER(ctypes.c_int32)
+        mem_arg = mem if mem.size else np.zeros(1, np.int32)
+        _lib.check(self._lib.seir_group_wsums(self._ctx, x.ctypes.data_as(_lib.c_double_p), nd, L, M, G, off.ctypes.data_as(ip),
+                                              mem_arg.ctypes.data_as(ip),
+                                              None if w is None or not w.size else w.ctypes.data_as(_lib.c_double_p),
+                                              out.ctypes.data_as(_lib.c_double_p)))
+        return out
+
     def order_stats_f64(self, values, ranks, cells=1, segs=1, seg_len=None, seg_stride=None, cell_stride=None):
         """`order_stats` for float64 (csrc/order_stats64_kernels.h; include/seir_hip.h, seir_order_stats_f64): the same
         cell geometry, the order of IEEE-754 totalOrder on the bit patterns (np.sort's on values without NaN, except that

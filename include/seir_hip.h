@@ -907,6 +907,52 @@ int seir_group_sums(seir_ctx *ctx, const int32_t *events, int64_t n, int32_t M, 
                     const int32_t *members, int64_t *out);
 
 /* ------------------------------------------------------------------------
+ * Group curves on the device: R_t and the within / between pressures of every kept draw per group of locations.
+ *
+ * seir_sampler_rt leaves the national curve R_t of every draw and seir_sampler_wb the national pressures; R_it, wi and be
+ * of a draw exist only inside their kernels.  The locations of a draw are correlated through the commuting matrix, so the
+ * per-location moments and quantiles do not combine into a region's band.  While a table of groups is set
+ * (seir_sampler_groups_set) and a switch below is on, every draw that seir_sampler_rt / seir_sampler_wb folds also leaves
+ *     Rg [slot][B][G][D]   sum over the members of weights[k] * R_it[t][m_k]      (seir_sampler_group_rt)
+ *     Wg, Bg [slot][B][G][D]   sum over the members of wi[t][m], be[t][m]         (seir_sampler_group_wb)
+ * wi and be are the cell values whose national sums are within_pressure and between_pressure: "between" is the pressure
+ * from outside each member LOCATION, as in the national figure, not from outside the group.  Defined or not, a draw's cells
+ * enter Wg and Bg as they enter the national sums; the host forms the share Wg / (Wg + Bg) and leaves out Wg + Bg == 0.
+ *
+ * THE definition of a group sum (kernel and its header comment: csrc/group_curve_kernels.h; NumPy:
+ * covid19uk_amd/posterior/groups.py, weighted_sum_rows).  Members m_0 < ... < m_{n-1} in CSR order, weights w_k aligned with
+ * `members`; lane l in [0, 64) starts from +0.0 and adds p = w_k * v[m_k] (one rounding; unweighted p = v[m_k]) for
+ * k = l, l + 64, ... < n ascending, each add one rounding; then for o = 32, 16, 8, 4, 2, 1 all lanes at once
+ * a_l = a_l + a_{l xor o}; the result is a_0.  No FMA, no floating-point atomics: the bits depend on the table alone, not on
+ * the launch geometry, the debug skew or how a burst is cut into calls, buffer halves or batches.
+ *
+ * The outputs are indexed by trace slot and rewritten when a slot is folded again: snapshot and restore carry nothing of
+ * them.  They are sized at whichever of table, switch and window reset comes last, and refused (SEIR_ERR_INVALID) above half
+ * of the device's free memory.  A refusal at a reset leaves rt / within-between on without group outputs: nothing is launched
+ * for them and the reads fail with SEIR_ERR_STATE.  While a switch is on the batches of seir_sampler_rt / _wb may shrink so
+ * that the integer plane and the cell plane(s) stay within the staging bound (SEIR_OPT_RT_STAGING_KIB); no result depends on
+ * the cut.  A sampler that never calls these entry points allocates and launches exactly what it did before.
+ * ------------------------------------------------------------------------ */
+/* weights [offsets[G]] aligned with the members of the table in force, finite (for a population-weighted curve
+ * N[m_k] / the group's population).  NULL switches group R_t off and frees its buffers.  SEIR_ERR_STATE without a table or
+ * with record_events == 0.  A later seir_sampler_groups_set switches it off: the weights belonged to the old table. */
+int seir_sampler_group_rt(seir_sampler *s, const double *weights);
+/* on != 0: group within / between on (SEIR_ERR_STATE without a table); 0: off, its buffers freed.  It stays on across a new
+ * table (sized again for it) and goes off with seir_sampler_groups_set(G = 0). */
+int seir_sampler_group_wb(seir_sampler *s, int32_t on);
+/* Blocking reads of slots [first, first + count): Rg, Wg, Bg [count][B][G][D], host pointers; Wg or Bg may be NULL.
+ * SEIR_ERR_STATE while the product or its switch is off or there are no group outputs. */
+int seir_sampler_read_group_rt(seir_sampler *s, int32_t first, int32_t count, double *Rg);
+int seir_sampler_read_group_wb(seir_sampler *s, int32_t first, int32_t count, double *Wg, double *Bg);
+/* The same on the copy stream, with the stream and the wait of seir_sampler_read_marginals_async. */
+int seir_sampler_read_group_rt_async(seir_sampler *s, int32_t first, int32_t count, double *Rg);
+int seir_sampler_read_group_wb_async(seir_sampler *s, int32_t first, int32_t count, double *Wg, double *Bg);
+/* The kernel alone, on host arrays: v [nd][L][M] (fp64), the table as for seir_group_sums, weights [offsets[G]] or NULL;
+ * out [nd][G][L].  M and L are the call's own, not the context's. */
+int seir_group_wsums(seir_ctx *ctx, const double *v, int64_t nd, int32_t L, int32_t M, int32_t G, const int32_t *offsets,
+                     const int32_t *members, const double *weights, double *out);
+
+/* ------------------------------------------------------------------------
  * Reproduction number R_it.
  *
  * calc_posterior_rit (covid19uk/posterior/reproduction_number.py:13-44): for each
