@@ -125,11 +125,23 @@ constexpr size_t k_rt_trace_lds_bytes(int Mp) { return sizeof(double) * ((size_t
 // k_rt_trace has no static LDS: the dynamic part is all of it
 static_assert(k_rt_trace_lds_bytes<RT_DT>(2048) <= 160 * 1024, "k_rt_trace's day tile must fit a workgroup's LDS at Mp = 2048");
 
-// grid (ncb, ceil(D / DT), B), 256 threads.  Slots [first, first + count) of the trace; nd0 = 0 .. of the batch's planes.
-template <int DT>
-__global__ __launch_bounds__(256) void k_rt_trace(Dims d, Consts c, RtBufs rb, const double *__restrict__ tr_theta, int B,
-                                                  int first, int count) {
+// Where a live cell's r goes besides the fold and the national partials (rt_trace_body's SINK):
+//   RT_SINK_NONE    nowhere (k_rt_trace);
+//   RT_SINK_KEEP    the draw store out [B][D][M][ld], the draw index innermost, at position count[b] (at the kernel's entry)
+//                   + the draw's index in the launch (k_rt_trace_keep, rt_keep_kernels.h, which describes the write);
+//   RT_SINK_CELLS   the plane out [count * B][D][ld], ld >= M (k_rt_trace_cells, group_curve_kernels.h).
+constexpr int RT_SINK_NONE = 0, RT_SINK_KEEP = 1, RT_SINK_CELLS = 2;
+constexpr int RT_KEEP_RUN = 4;                   // draws staged per cell of the draw store: a 32-byte run along the draw axis
+
+// The one statement of the R_it contraction of a batch: the loop over the draws, the fold, the national partials and the
+// sink.  Its three kernels are __global__ wrappers with nothing else in them, so fold, partials and the r a sink receives
+// are the same bits whichever runs.  Dims, Consts and RtBufs come BY VALUE, as a kernel's own parameters: taken by
+// reference the keep instance spills scalar registers.
+template <int DT, int SINK>
+__device__ __forceinline__ void rt_trace_body(Dims d, Consts c, RtBufs rb, const double *__restrict__ tr_theta, int B, int first,
+                                              int count, double *__restrict__ out, long long ld) {
     static_assert(DT % 4 == 0 && (DT & (DT - 1)) == 0, "a wave owns the days tt = wave mod 4 of the tile");
+    static_assert(RT_KEEP_RUN == 4, "a run is two double2 stores");
     debug_skew(d);
     extern __shared__ double lds[];                      // E [DT][Mp] | S [DT][Mp] | red [4][DT][64]
     constexpr int NC = DT / 4;                           // cells per thread: days tt = cc * 4 + wave, column j
@@ -140,8 +152,9 @@ __global__ __launch_bounds__(256) void k_rt_trace(Dims d, Consts c, RtBufs rb, c
     const bool jin = j < M;
     const double inj = jin ? c.invN[j] : 0.0;
     const double wj = rb.weight[j];
-    const bool fresh = rb.count[b] == 0;                 // count moves in k_rt_finish, a launch of its own: no race
-    double ref[NC], sm[NC], sq[NC];
+    const unsigned long long pos0 = rb.count[b];         // count moves in k_rt_finish, a launch of its own: no race
+    const bool fresh = pos0 == 0;
+    double ref[NC], sm[NC], sq[NC], st[NC][RT_KEEP_RUN];
     uint32_t g1[NC];
     bool live[NC];
     size_t cell[NC];
@@ -152,10 +165,15 @@ __global__ __launch_bounds__(256) void k_rt_trace(Dims d, Consts c, RtBufs rb, c
         cell[cc] = ((size_t)b * D + (tw < D ? tw : 0)) * M + (jin ? j : 0);
         ref[cc] = sm[cc] = sq[cc] = 0.0;
         g1[cc] = 0u;
+        if constexpr (SINK == RT_SINK_KEEP) {
+#pragma unroll
+            for (int k = 0; k < RT_KEEP_RUN; ++k) st[cc][k] = 0.0;
+        }
         if (live[cc] && !fresh) {
             ref[cc] = rb.ref[cell[cc]]; sm[cc] = rb.sum[cell[cc]]; sq[cc] = rb.sumsq[cell[cc]]; g1[cc] = rb.gt1[cell[cc]];
         }
     }
+    int lo = (int)(pos0 & (RT_KEEP_RUN - 1));            // KEEP: first position of the current run that this launch owns
     for (int jd = 0; jd < count; ++jd) {
         const int nd = jd * B + b;
         const double *th = tr_theta + ((size_t)(first + jd) * B + b) * d.P;
@@ -186,6 +204,10 @@ __global__ __launch_bounds__(256) void k_rt_trace(Dims d, Consts c, RtBufs rb, c
         __syncthreads();
         const double period = rt_period(g0);
         const bool is_first = fresh && jd == 0;
+        // KEEP: this draw's place in the store: position pos, slot `at` of the run that starts at pos - at (uniform in the grid)
+        const unsigned long long pos = pos0 + (unsigned long long)jd;
+        const int at = (int)(pos & (RT_KEEP_RUN - 1));
+        const bool flush = at == RT_KEEP_RUN - 1 || jd == count - 1;
 #pragma unroll
         for (int cc = 0; cc < NC; ++cc) {
             const int tt = cc * 4 + wave, tw = w0 + tt;
@@ -195,10 +217,31 @@ __global__ __launch_bounds__(256) void k_rt_trace(Dims d, Consts c, RtBufs rb, c
                 if (is_first) ref[cc] = r;
                 rt_fold(r, ref[cc], sm[cc], sq[cc]);
                 g1[cc] += r > 1.0 ? 1u : 0u;
+                if constexpr (SINK == RT_SINK_CELLS)
+                    out[((size_t)nd * D + tw) * (size_t)ld + j] = r;         // the wave's 64 columns: 512 contiguous bytes
             }
             const double nat = rt_wave_sum(live[cc] ? rt_weighted(r, wj) : 0.0);
             if (lane == 0 && tw < D) rb.part[((size_t)nd * D + tw) * rb.ncb + blockIdx.x] = nat;
+            if constexpr (SINK == RT_SINK_KEEP) {
+#pragma unroll
+                for (int k = 0; k < RT_KEEP_RUN; ++k) st[cc][k] = (k == at) ? r : st[cc][k];
+                if (flush && live[cc] && pos < (unsigned long long)ld) {     // the host has refused a call past the cap
+                    double *run = out + cell[cc] * (size_t)ld + (size_t)(pos - (unsigned long long)at);
+                    if (lo == 0 && at == RT_KEEP_RUN - 1) {
+                        // a whole run: 32 bytes, aligned to 32
+                        reinterpret_cast<double2 *>(run)[0] = make_double2(st[cc][0], st[cc][1]);
+                        reinterpret_cast<double2 *>(run)[1] = make_double2(st[cc][2], st[cc][3]);
+                    } else {
+                        // ragged: the positions [lo, at] of the run are this launch's, the others are not touched
+#pragma unroll
+                        for (int k = 0; k < RT_KEEP_RUN; ++k)
+                            if (k >= lo && k <= at) run[k] = st[cc][k];
+                    }
+                }
+            }
         }
+        if constexpr (SINK == RT_SINK_KEEP)
+            if (flush) lo = 0;
         // the next draw's E and S are written behind the barrier above, its partials behind the one that follows them:
         // red is read here before this wave reaches that barrier
     }
@@ -208,6 +251,13 @@ __global__ __launch_bounds__(256) void k_rt_trace(Dims d, Consts c, RtBufs rb, c
             if (fresh) rb.ref[cell[cc]] = ref[cc];
             rb.sum[cell[cc]] = sm[cc]; rb.sumsq[cell[cc]] = sq[cc]; rb.gt1[cell[cc]] = g1[cc];
         }
+}
+
+// grid (ncb, ceil(D / DT), B), 256 threads.  Slots [first, first + count) of the trace; nd0 = 0 .. of the batch's planes.
+template <int DT>
+__global__ __launch_bounds__(256) void k_rt_trace(Dims d, Consts c, RtBufs rb, const double *__restrict__ tr_theta, int B,
+                                                  int first, int count) {
+    rt_trace_body<DT, RT_SINK_NONE>(d, c, rb, tr_theta, B, first, count, nullptr, 0);
 }
 
 // grid (ceil(count * B * D / 256)), 256 threads: the national curve of the batch's draws from their column-block partials,

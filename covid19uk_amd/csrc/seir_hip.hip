@@ -26,7 +26,6 @@
 #include "rt_trace_kernels.h"
 #include "wb_kernels.h"
 #include "order_stats_kernels.h"
-#include "order_stats64_kernels.h"
 #include "rt_keep_kernels.h"
 #include "group_kernels.h"
 
@@ -3012,48 +3011,58 @@ extern "C" int seir_sampler_read_forecast(seir_sampler *s, uint64_t *count, int3
 // ---------------------------------------------------------------------------
 // Forecast intervals on the device (include/seir_hip.h; kernels: k_forecast_keep, order_stats_kernels.h)
 // ---------------------------------------------------------------------------
+// A draw store (the forecast's keep, the R_it store keepR) is sized between its product's reset and the first draws: the
+// one resize behind seir_sampler_forecast_keep / seir_sampler_rt_keep.  cap == 0 frees it.  Otherwise a resize is refused
+// once j draws per chain have been taken since the reset (`verb`; `reset` and `call` name the two entry points), a store
+// that already has the capacity stays (the reset has emptied it), and a new one of `bytes` (`shape` spells the product
+// out for the refusal) may take half of what is free on the device; it is zeroed.
+template <typename T>
+static int keep_resize(seir_sampler *s, T *&store, long long &store_cap, int64_t cap, long long j, unsigned long long bytes,
+                       const char *verb, const char *reset, const char *call, const char *shape) {
+    hipStream_t st = s->ctx->stream;
+    if (cap != 0) {
+        if (j != 0)
+            return fail(SEIR_ERR_STATE, "%lld draws per chain have been %s since the reset: the draw store is sized between "
+                        "%s and the first %s", j, verb, reset, call);
+        if (store && store_cap == cap) return 0;
+    }
+    if (store) {
+        HIP_TRY(hipStreamSynchronize(st));
+        (void)hipFree(store);
+        store = nullptr; store_cap = 0;
+    }
+    if (cap == 0) return 0;
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    // half of what is free: the policy of a device that is shared, not a measurement
+    if (bytes > (unsigned long long)free_b / 2)
+        return fail(SEIR_ERR_INVALID, "the draw store needs %llu bytes (%s), more than half of the %llu bytes free on the device",
+                    bytes, shape, (unsigned long long)free_b);
+    void *q = nullptr;
+    HIP_TRY(hipMalloc(&q, (size_t)bytes));
+    if (hipMemsetAsync(q, 0, (size_t)bytes, st) != hipSuccess) { (void)hipFree(q); return fail(SEIR_ERR_DEVICE, "hipMemsetAsync failed"); }
+    store = (T *)q;
+    store_cap = cap;
+    return 0;
+}
+
 extern "C" int seir_sampler_forecast_keep(seir_sampler *s, int64_t cap) {
     int rc = sampler_check(s);
     if (rc) return rc;
     if ((rc = trace_range_check(s, s->fc.on, FORECAST_USER))) return rc;
     if (cap < 0 || cap > (1ll << FC_ID_SHIFT))
         return fail(SEIR_ERR_INVALID, "cap=%lld outside [0, 2^%d]: the draws per chain between two resets", (long long)cap, FC_ID_SHIFT);
-    hipStream_t st = s->ctx->stream;
-    if (cap == 0) {
-        if (s->fc_keep) {
-            HIP_TRY(hipStreamSynchronize(st));
-            (void)hipFree(s->fc_keep);
-            s->fc_keep = nullptr; s->fc_keep_cap = 0;
-        }
-        return 0;
-    }
-    if (s->fc.j != 0)
-        return fail(SEIR_ERR_STATE, "%lld draws per chain have been forecast since the reset: the draw store is sized between "
-                    "seir_sampler_forecast_reset and the first seir_sampler_forecast", s->fc.j);
-    if (s->fc_keep && s->fc_keep_cap == cap) return 0;       // the reset has emptied it
-    if (s->fc_keep) {
-        HIP_TRY(hipStreamSynchronize(st));
-        (void)hipFree(s->fc_keep);
-        s->fc_keep = nullptr; s->fc_keep_cap = 0;
-    }
-    const unsigned long long cells = 3ull * s->cfg.B * s->ctx->d.M * s->fc.fb.H, bytes = cells * (unsigned long long)cap * 4ull;
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    // half of what is free: the policy of a device that is shared, not a measurement
-    if (bytes > (unsigned long long)free_b / 2)
-        return fail(SEIR_ERR_INVALID, "the draw store needs %llu bytes (%d chains x 3 x %d locations x %d days x %lld draws x 4), "
-                    "more than half of the %llu bytes free on the device", bytes, s->cfg.B, s->ctx->d.M, s->fc.fb.H, (long long)cap,
-                    (unsigned long long)free_b);
-    void *q = nullptr;
-    HIP_TRY(hipMalloc(&q, (size_t)bytes));
-    if (hipMemsetAsync(q, 0, (size_t)bytes, st) != hipSuccess) { (void)hipFree(q); return fail(SEIR_ERR_DEVICE, "hipMemsetAsync failed"); }
-    s->fc_keep = (int *)q;
-    s->fc_keep_cap = cap;
-    return 0;
+    const unsigned long long cells = 3ull * s->cfg.B * s->ctx->d.M * s->fc.fb.H;
+    char shape[160];
+    snprintf(shape, sizeof shape, "%d chains x 3 x %d locations x %d days x %lld draws x 4", s->cfg.B, s->ctx->d.M, s->fc.fb.H,
+             (long long)cap);
+    return keep_resize(s, s->fc_keep, s->fc_keep_cap, cap, s->fc.j, cells * (unsigned long long)cap * 4ull, "forecast",
+                       "seir_sampler_forecast_reset", "seir_sampler_forecast", shape);
 }
 
-// ranks [R] strictly increasing in [0, n): into OrderArgs, or the refusal.
-static int order_ranks(const int64_t *ranks, int32_t R, long long n, OrderArgs &a) {
+// ranks [R] strictly increasing in [0, n): into the launch's arguments, or the refusal.
+template <typename V>
+static int order_ranks(const int64_t *ranks, int32_t R, long long n, OrderStatsArgs<V> &a) {
     if (R < 1 || R > ORDER_MAX_RANKS) return fail(SEIR_ERR_INVALID, "R=%d outside [1, %d]", R, ORDER_MAX_RANKS);
     if (!ranks) return fail(SEIR_ERR_INVALID, "null ranks pointer");
     for (int r = 0; r < R; ++r) {
@@ -3067,49 +3076,72 @@ static int order_ranks(const int64_t *ranks, int32_t R, long long n, OrderArgs &
     return 0;
 }
 
-static void order_launch(const OrderArgs &a, hipStream_t st) {
-    if ((long long)a.segs * a.seg_len <= ORDER_WAVE_N) hipLaunchKernelGGL(k_order_stats<1>, dim3((unsigned)a.cells), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(k_order_stats<4>, dim3((unsigned)a.cells), dim3(256), 0, st, a);
+// V = int32_t: k_order_stats; V = uint64_t, the doubles' bit patterns: k_order_stats_f64.  One wave per cell up to
+// ORDER_WAVE_N values, four above.
+template <typename V>
+static void order_launch(const OrderStatsArgs<V> &a, hipStream_t st) {
+    const bool one = (long long)a.segs * a.seg_len <= ORDER_WAVE_N;
+    const dim3 grid((unsigned)a.cells), block(one ? 64 : 256);
+    if constexpr (sizeof(V) == 4) {
+        if (one) hipLaunchKernelGGL(k_order_stats<1>, grid, block, 0, st, a);
+        else hipLaunchKernelGGL(k_order_stats<4>, grid, block, 0, st, a);
+    } else {
+        if (one) hipLaunchKernelGGL(k_order_stats_f64<1>, grid, block, 0, st, a);
+        else hipLaunchKernelGGL(k_order_stats_f64<4>, grid, block, 0, st, a);
+    }
+}
+
+// Order statistics of a draw store [B][plane][stride] holding j draws per chain, behind seir_sampler_forecast_order_stats
+// and seir_sampler_rt_order_stats: every chain's count (count_dev [B], the product's own) must be j; out [R][cells].
+// `keep_call`, `what` and `verb` are the product's words in the refusals.
+template <typename V>
+static int keep_order_stats(seir_sampler *s, const V *store, long long j, const uint64_t *count_dev, long long plane,
+                            long long stride, const int64_t *ranks, int32_t R, int32_t pooled, V *out, const char *keep_call,
+                            const char *what, const char *verb) {
+    if (!store) return fail(SEIR_ERR_STATE, "the draw store is not enabled: call %s first", keep_call);
+    if (!out) return fail(SEIR_ERR_INVALID, "null output pointer");
+    if (j < 1) return fail(SEIR_ERR_STATE, "no draws kept since the %s reset", what);
+    const int B = s->cfg.B;
+    hipStream_t st = s->ctx->stream;
+    std::vector<uint64_t> cnt((size_t)B);
+    HIP_TRY(hipMemcpyAsync(cnt.data(), count_dev, sizeof(uint64_t) * B, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int b = 0; b < B; ++b)
+        if ((long long)cnt[b] != j)
+            return fail(SEIR_ERR_STATE, "chain %d has %llu draws %s, the store %lld: the chains' counts differ", b,
+                        (unsigned long long)cnt[b], verb, j);
+    int rc;
+    OrderStatsArgs<V> a{};
+    if ((rc = order_ranks(ranks, R, pooled ? j * B : j, a))) return rc;
+    a.values = store;
+    a.cells = pooled ? plane : plane * B;
+    a.segs = pooled ? B : 1;
+    a.seg_len = j;
+    a.seg_stride = plane * stride;
+    a.cell_stride = stride;
+    DevBuf dout;
+    const size_t nout = (size_t)R * (size_t)a.cells;
+    if ((rc = dout.alloc(sizeof(V) * nout))) return rc;
+    a.out = dout.as<V>();
+    order_launch(a, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, dout.p, sizeof(V) * nout, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
 }
 
 extern "C" int seir_sampler_forecast_order_stats(seir_sampler *s, const int64_t *ranks, int32_t R, int32_t pooled, int32_t *out) {
     int rc = sampler_check(s);
     if (rc) return rc;
     if ((rc = trace_range_check(s, s->fc.on, FORECAST_USER))) return rc;
-    if (!s->fc_keep) return fail(SEIR_ERR_STATE, "the draw store is not enabled: call seir_sampler_forecast_keep first");
-    if (!out) return fail(SEIR_ERR_INVALID, "null output pointer");
-    if (s->fc.j < 1) return fail(SEIR_ERR_STATE, "no draws kept since the forecast reset");
-    const int B = s->cfg.B;
-    hipStream_t st = s->ctx->stream;
-    std::vector<uint64_t> cnt((size_t)B);
-    HIP_TRY(hipMemcpyAsync(cnt.data(), s->fc.fb.mom.count, sizeof(uint64_t) * B, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int b = 0; b < B; ++b)
-        if ((long long)cnt[b] != s->fc.j)
-            return fail(SEIR_ERR_STATE, "chain %d has %llu draws forecast, the store %lld: the chains' counts differ", b,
-                        (unsigned long long)cnt[b], s->fc.j);
-    const long long plane = 3ll * s->ctx->d.M * s->fc.fb.H;
-    OrderArgs a{};
-    if ((rc = order_ranks(ranks, R, pooled ? s->fc.j * B : s->fc.j, a))) return rc;
-    a.values = s->fc_keep;
-    a.cells = pooled ? plane : plane * B;
-    a.segs = pooled ? B : 1;
-    a.seg_len = s->fc.j;
-    a.seg_stride = plane * s->fc_keep_cap;
-    a.cell_stride = s->fc_keep_cap;
-    DevBuf dout;
-    const size_t nout = (size_t)R * (size_t)a.cells;
-    if ((rc = dout.alloc(sizeof(int32_t) * nout))) return rc;
-    a.out = dout.as<int32_t>();
-    order_launch(a, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, dout.p, sizeof(int32_t) * nout, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return 0;
+    return keep_order_stats<int32_t>(s, s->fc_keep, s->fc.j, s->fc.fb.mom.count, 3ll * s->ctx->d.M * s->fc.fb.H, s->fc_keep_cap, ranks,
+                                     R, pooled, out, "seir_sampler_forecast_keep", "forecast", "forecast");
 }
 
-extern "C" int seir_order_stats(seir_ctx *ctx, const int32_t *values, int64_t cells, int32_t segs, int64_t seg_len,
-                                int64_t seg_stride, int64_t cell_stride, const int64_t *ranks, int32_t R, int32_t *out) {
+// The stateless select behind seir_order_stats / seir_order_stats_f64: values up, out [R][cells] back.
+template <typename V>
+static int order_stats_host(seir_ctx *ctx, const V *values, int64_t cells, int32_t segs, int64_t seg_len, int64_t seg_stride,
+                            int64_t cell_stride, const int64_t *ranks, int32_t R, V *out) {
     int rc = check_batch(ctx, 1);
     if (rc) return rc;
     if (!values || !out) return fail(SEIR_ERR_INVALID, "null pointer");
@@ -3119,20 +3151,31 @@ extern "C" int seir_order_stats(seir_ctx *ctx, const int32_t *values, int64_t ce
     if (cell_stride < 0 || seg_stride < 0 || (segs > 1 && seg_stride < seg_len))
         return fail(SEIR_ERR_INVALID, "seg_stride=%lld, cell_stride=%lld: no negative stride, and segments do not overlap",
                     (long long)seg_stride, (long long)cell_stride);
-    OrderArgs a{};
+    OrderStatsArgs<V> a{};
     if ((rc = order_ranks(ranks, R, (long long)segs * seg_len, a))) return rc;
     const size_t extent = (size_t)(cells - 1) * cell_stride + (size_t)(segs - 1) * seg_stride + (size_t)seg_len;
     const size_t nout = (size_t)R * (size_t)cells;
     DevBuf dv, dout;
-    if ((rc = dv.alloc(sizeof(int32_t) * extent)) || (rc = dout.alloc(sizeof(int32_t) * nout))) return rc;
-    HIP_TRY(hipMemcpyAsync(dv.p, values, sizeof(int32_t) * extent, hipMemcpyHostToDevice, ctx->stream));
-    a.values = dv.as<int32_t>(); a.out = dout.as<int32_t>();
+    if ((rc = dv.alloc(sizeof(V) * extent)) || (rc = dout.alloc(sizeof(V) * nout))) return rc;
+    HIP_TRY(hipMemcpyAsync(dv.p, values, sizeof(V) * extent, hipMemcpyHostToDevice, ctx->stream));
+    a.values = dv.as<V>(); a.out = dout.as<V>();
     a.cells = cells; a.segs = segs; a.seg_len = seg_len; a.seg_stride = seg_stride; a.cell_stride = cell_stride;
     order_launch(a, ctx->stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, dout.p, sizeof(int32_t) * nout, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out, dout.p, sizeof(V) * nout, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
+}
+
+extern "C" int seir_order_stats(seir_ctx *ctx, const int32_t *values, int64_t cells, int32_t segs, int64_t seg_len,
+                                int64_t seg_stride, int64_t cell_stride, const int64_t *ranks, int32_t R, int32_t *out) {
+    return order_stats_host<int32_t>(ctx, values, cells, segs, seg_len, seg_stride, cell_stride, ranks, R, out);
+}
+
+extern "C" int seir_order_stats_f64(seir_ctx *ctx, const double *values, int64_t cells, int32_t segs, int64_t seg_len,
+                                    int64_t seg_stride, int64_t cell_stride, const int64_t *ranks, int32_t R, double *out) {
+    return order_stats_host<uint64_t>(ctx, (const uint64_t *)values, cells, segs, seg_len, seg_stride, cell_stride, ranks, R,
+                                      (uint64_t *)out);
 }
 
 // ---------------------------------------------------------------------------
@@ -3377,131 +3420,35 @@ extern "C" int seir_sampler_rt(seir_sampler *s, int32_t first, int32_t count) {
 }
 
 // ---------------------------------------------------------------------------
-// R_t intervals on the device (include/seir_hip.h; kernels: rt_keep_kernels.h, order_stats64_kernels.h)
+// R_t intervals on the device (include/seir_hip.h; kernels: rt_keep_kernels.h, order_stats_kernels.h)
 // ---------------------------------------------------------------------------
-static void rt_keep_free(seir_sampler *s) {
-    (void)hipFree(s->rt_keep);
-    s->rt_keep = nullptr; s->rt_keep_cap = s->rt_keep_stride = 0;
-}
-
 extern "C" int seir_sampler_rt_keep(seir_sampler *s, int64_t cap) {
     int rc = sampler_check(s);
     if (rc) return rc;
     if ((rc = rt_check(s))) return rc;
     if (cap < 0 || cap > (1ll << 20))
         return fail(SEIR_ERR_INVALID, "cap=%lld outside [0, 2^20]: the draws per chain between two resets", (long long)cap);
-    hipStream_t st = s->ctx->stream;
-    if (cap == 0) {
-        if (s->rt_keep) {
-            HIP_TRY(hipStreamSynchronize(st));
-            rt_keep_free(s);
-        }
-        return 0;
-    }
-    if (s->rt_j != 0)
-        return fail(SEIR_ERR_STATE, "%lld draws per chain have been folded since the reset: the draw store is sized between "
-                    "seir_sampler_rt_reset and the first seir_sampler_rt", s->rt_j);
-    if (s->rt_keep && s->rt_keep_cap == cap) return 0;       // the reset has emptied it
-    if (s->rt_keep) {
-        HIP_TRY(hipStreamSynchronize(st));
-        rt_keep_free(s);
-    }
     const long long stride = (cap + RT_KEEP_RUN - 1) / RT_KEEP_RUN * RT_KEEP_RUN;
-    const unsigned long long bytes = (unsigned long long)rt_cells(s) * (unsigned long long)stride * 8ull;
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    // half of what is free: the policy of a device that is shared, not a measurement
-    if (bytes > (unsigned long long)free_b / 2)
-        return fail(SEIR_ERR_INVALID, "the draw store needs %llu bytes (%d chains x %d days x %d locations x %lld draws x 8), "
-                    "more than half of the %llu bytes free on the device", bytes, s->cfg.B, s->rt.D, s->ctx->d.M, stride,
-                    (unsigned long long)free_b);
-    void *q = nullptr;
-    HIP_TRY(hipMalloc(&q, (size_t)bytes));
-    if (hipMemsetAsync(q, 0, (size_t)bytes, st) != hipSuccess) { (void)hipFree(q); return fail(SEIR_ERR_DEVICE, "hipMemsetAsync failed"); }
+    char shape[160];
+    snprintf(shape, sizeof shape, "%d chains x %d days x %d locations x %lld draws x 8", s->cfg.B, s->rt.D, s->ctx->d.M, stride);
+    rc = keep_resize(s, s->rt_keep, s->rt_keep_cap, cap, s->rt_j, (unsigned long long)rt_cells(s) * (unsigned long long)stride * 8ull,
+                     "folded", "seir_sampler_rt_reset", "seir_sampler_rt", shape);
+    if (!s->rt_keep) s->rt_keep_stride = 0;
+    else if (!rc) s->rt_keep_stride = stride;        // a refused resize leaves the store and its stride as they were
     const size_t lds = k_rt_trace_lds_bytes<RT_DT>(s->ctx->d.Mp);
-    if (lds > 64 * 1024)
+    if (s->rt_keep && lds > 64 * 1024)
         (void)hipFuncSetAttribute((const void *)k_rt_trace_keep<RT_DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    s->rt_keep = (double *)q;
-    s->rt_keep_cap = cap;
-    s->rt_keep_stride = stride;
-    return 0;
-}
-
-// ranks [R] strictly increasing in [0, n): into Order64Args, or order_ranks' refusal.
-static int order_ranks(const int64_t *ranks, int32_t R, long long n, Order64Args &a) {
-    OrderArgs t{};
-    if (int rc = order_ranks(ranks, R, n, t)) return rc;
-    for (int r = 0; r < R; ++r) a.ranks[r] = t.ranks[r];
-    a.R = R;
-    return 0;
-}
-
-static void order_launch(const Order64Args &a, hipStream_t st) {
-    if ((long long)a.segs * a.seg_len <= ORDER_WAVE_N) hipLaunchKernelGGL(k_order_stats_f64<1>, dim3((unsigned)a.cells), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(k_order_stats_f64<4>, dim3((unsigned)a.cells), dim3(256), 0, st, a);
+    return rc;
 }
 
 extern "C" int seir_sampler_rt_order_stats(seir_sampler *s, const int64_t *ranks, int32_t R, int32_t pooled, double *out) {
     int rc = sampler_check(s);
     if (rc) return rc;
     if ((rc = rt_check(s))) return rc;
-    if (!s->rt_keep) return fail(SEIR_ERR_STATE, "the draw store is not enabled: call seir_sampler_rt_keep first");
-    if (!out) return fail(SEIR_ERR_INVALID, "null output pointer");
-    if (s->rt_j < 1) return fail(SEIR_ERR_STATE, "no draws kept since the rt reset");
-    const int B = s->cfg.B;
-    hipStream_t st = s->ctx->stream;
-    std::vector<uint64_t> cnt((size_t)B);
-    HIP_TRY(hipMemcpyAsync(cnt.data(), s->rt.count, sizeof(uint64_t) * B, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int b = 0; b < B; ++b)
-        if ((long long)cnt[b] != s->rt_j)
-            return fail(SEIR_ERR_STATE, "chain %d has %llu draws folded, the store %lld: the chains' counts differ", b,
-                        (unsigned long long)cnt[b], s->rt_j);
-    const long long plane = (long long)s->rt.D * s->ctx->d.M;
-    Order64Args a{};
-    if ((rc = order_ranks(ranks, R, pooled ? s->rt_j * B : s->rt_j, a))) return rc;
-    a.values = (const unsigned long long *)s->rt_keep;
-    a.cells = pooled ? plane : plane * B;
-    a.segs = pooled ? B : 1;
-    a.seg_len = s->rt_j;
-    a.seg_stride = plane * s->rt_keep_stride;
-    a.cell_stride = s->rt_keep_stride;
-    DevBuf dout;
-    const size_t nout = (size_t)R * (size_t)a.cells;
-    if ((rc = dout.alloc(sizeof(double) * nout))) return rc;
-    a.out = dout.as<unsigned long long>();
-    order_launch(a, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, dout.p, sizeof(double) * nout, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = keep_order_stats<uint64_t>(s, (const uint64_t *)s->rt_keep, s->rt_j, s->rt.count, (long long)s->rt.D * s->ctx->d.M,
+                                         s->rt_keep_stride, ranks, R, pooled, (uint64_t *)out, "seir_sampler_rt_keep", "rt", "folded")))
+        return rc;
     return check_ev_overflow(s);
-}
-
-extern "C" int seir_order_stats_f64(seir_ctx *ctx, const double *values, int64_t cells, int32_t segs, int64_t seg_len,
-                                    int64_t seg_stride, int64_t cell_stride, const int64_t *ranks, int32_t R, double *out) {
-    int rc = check_batch(ctx, 1);
-    if (rc) return rc;
-    if (!values || !out) return fail(SEIR_ERR_INVALID, "null pointer");
-    if (cells < 1 || cells > 0x7fffffffll || segs < 1 || seg_len < 1 || (long long)segs * seg_len > 0x7fffffffll)
-        return fail(SEIR_ERR_INVALID, "cells=%lld, segs=%d, seg_len=%lld: at least one of each, n = segs x seg_len and cells below 2^31",
-                    (long long)cells, segs, (long long)seg_len);
-    if (cell_stride < 0 || seg_stride < 0 || (segs > 1 && seg_stride < seg_len))
-        return fail(SEIR_ERR_INVALID, "seg_stride=%lld, cell_stride=%lld: no negative stride, and segments do not overlap",
-                    (long long)seg_stride, (long long)cell_stride);
-    Order64Args a{};
-    if ((rc = order_ranks(ranks, R, (long long)segs * seg_len, a))) return rc;
-    const size_t extent = (size_t)(cells - 1) * cell_stride + (size_t)(segs - 1) * seg_stride + (size_t)seg_len;
-    const size_t nout = (size_t)R * (size_t)cells;
-    DevBuf dv, dout;
-    if ((rc = dv.alloc(sizeof(double) * extent)) || (rc = dout.alloc(sizeof(double) * nout))) return rc;
-    HIP_TRY(hipMemcpyAsync(dv.p, values, sizeof(double) * extent, hipMemcpyHostToDevice, ctx->stream));
-    a.values = dv.as<unsigned long long>(); a.out = dout.as<unsigned long long>();
-    a.cells = cells; a.segs = segs; a.seg_len = seg_len; a.seg_stride = seg_stride; a.cell_stride = cell_stride;
-    order_launch(a, ctx->stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, dout.p, sizeof(double) * nout, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
 }
 
 static int copy_rt_draws(seir_sampler *s, hipStream_t st, int32_t first, int32_t count, double *R_t) {

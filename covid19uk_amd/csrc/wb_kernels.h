@@ -138,10 +138,12 @@ constexpr size_t k_wb_trace_lds_bytes(int Mp) { return sizeof(double) * ((size_t
 // k_wb_trace has no static LDS: the dynamic part is all of it
 static_assert(k_wb_trace_lds_bytes<WB_DT>(2048) <= 160 * 1024, "k_wb_trace's day tile must fit a workgroup's LDS at Mp = 2048");
 
-// grid (ncb, ceil(D / DT), B), 256 threads.  Slots [first, first + count) of the trace; nd = 0 .. of the batch's planes.
-template <int DT>
-__global__ __launch_bounds__(256) void k_wb_trace(Dims d, Consts c, WbBufs wb, const double *__restrict__ tr_theta, int B,
-                                                  int first, int count) {
+// The one statement of the within/between contraction of a batch; k_wb_trace and k_wb_trace_cells (group_curve_kernels.h)
+// are __global__ wrappers with nothing else in them.  CELLS: wi and be of every live cell also go into the planes
+// Wc, Bc [count * B][D][ld], ld >= M.  Dims, Consts and WbBufs by value, as rt_trace_body takes its own.
+template <int DT, bool CELLS>
+__device__ __forceinline__ void wb_trace_body(Dims d, Consts c, WbBufs wb, const double *__restrict__ tr_theta, int B, int first,
+                                              int count, double *__restrict__ Wc, double *__restrict__ Bc, long long ld) {
     static_assert(DT % 4 == 0 && (DT & (DT - 1)) == 0, "a wave owns the days tt = wave mod 4 of the tile");
     debug_skew(d);
     extern __shared__ double lds[];                      // x [DT][Mp] | red [4][DT][64]
@@ -210,6 +212,11 @@ __global__ __launch_bounds__(256) void k_wb_trace(Dims d, Consts c, WbBufs wb, c
                     red[(2 * DT + tt) * WAVE + lane], red[(3 * DT + tt) * WAVE + lane], wi, be, fw, fb);
             if (live[cc] && wb_finite(fw) && wb_finite(fb))
                 wb_fold(fw, fb, n[cc], ref_w[cc], sum_w[cc], sumsq_w[cc], ref_b[cc], sum_b[cc], gt[cc]);
+            if constexpr (CELLS)
+                if (live[cc]) {                                              // defined or not, as the national sums
+                    const size_t at = ((size_t)nd * D + tw) * (size_t)ld + m;
+                    Wc[at] = wi; Bc[at] = be;
+                }
             const double nw = wb_wave_sum(live[cc] ? wi : 0.0), nb = wb_wave_sum(live[cc] ? be : 0.0);
             if (lane == 0 && tw < D) {
                 double *p = wb.part + (((size_t)nd * D + tw) * wb.ncb + blockIdx.x) * 2;
@@ -226,6 +233,13 @@ __global__ __launch_bounds__(256) void k_wb_trace(Dims d, Consts c, WbBufs wb, c
             wb.ref_w[cell[cc]] = ref_w[cc]; wb.sum_w[cell[cc]] = sum_w[cc]; wb.sumsq_w[cell[cc]] = sumsq_w[cc];
             wb.ref_b[cell[cc]] = ref_b[cc]; wb.sum_b[cell[cc]] = sum_b[cc];
         }
+}
+
+// grid (ncb, ceil(D / DT), B), 256 threads.  Slots [first, first + count) of the trace; nd = 0 .. of the batch's planes.
+template <int DT>
+__global__ __launch_bounds__(256) void k_wb_trace(Dims d, Consts c, WbBufs wb, const double *__restrict__ tr_theta, int B,
+                                                  int first, int count) {
+    wb_trace_body<DT, false>(d, c, wb, tr_theta, B, first, count, nullptr, nullptr, 0);
 }
 
 // grid (ceil(count * B * D / 256)), 256 threads: the national pressures of the batch's draws from their column-block

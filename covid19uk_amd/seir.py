@@ -354,7 +354,7 @@ class SeirModel:
         return out
 
     def order_stats_f64(self, values, ranks, cells=1, segs=1, seg_len=None, seg_stride=None, cell_stride=None):
-        """`order_stats` for float64 (csrc/order_stats64_kernels.h; include/seir_hip.h, seir_order_stats_f64): the same
+        """`order_stats` for float64 (csrc/order_stats_kernels.h; include/seir_hip.h, seir_order_stats_f64): the same
         cell geometry, the order of IEEE-754 totalOrder on the bit patterns (np.sort's on values without NaN, except that
         -0.0 comes before +0.0).  Returns float64 [R, cells]."""
         v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)

@@ -704,8 +704,8 @@ int seir_sampler_read_rt(seir_sampler *s, uint64_t *count, double *ref, double *
  * leaves its R_it, one fp64 per (chain, window day, location), on the device, and at the end of the run exact order
  * statistics are selected from them there; only the selected values cross PCIe.
  *
- * Semantics (the one definition; kernels: k_rt_trace_keep of csrc/rt_keep_kernels.h, csrc/order_stats64_kernels.h, the
- * narrowing step csrc/order_select64.h).
+ * Semantics (the one definition; kernels: k_rt_trace_keep of csrc/rt_keep_kernels.h, csrc/order_stats_kernels.h, the
+ * narrowing step csrc/order_select.h).
  *   Store.  keepR[B][D][M][cap] fp64, the draw index innermost (the rows are padded to a multiple of 4 draws).  Draw j of
  *     chain b -- count[b] of seir_sampler_read_rt at the kernel's entry plus the draw's index in the call -- fills position j
  *     of every cell of that chain, with the bits of the R_it that is folded: k_rt_trace_keep runs in place of k_rt_trace

@@ -93,7 +93,7 @@ int main() {
     for (int pass = 0; pass < seir::ORDER_PASSES; ++pass) {
         std::unordered_map<uint32_t, std::vector<uint32_t>> hist;
         for (uint32_t p : prefix) if (!hist.count(p)) hist[p] = std::vector<uint32_t>(seir::ORDER_BINS, 0u);
-        const int sh = seir::order_shift(pass);
+        const int sh = seir::order_shift<uint32_t>(pass);
         for (int32_t x : v) {
             const uint32_t key = seir::order_key(x);
             if (seir::order_value(key) != x) return 3;

@@ -1,6 +1,6 @@
 """R_t intervals on the device (include/seir_hip.h, "R_t intervals on the device"): k_rt_trace_keep
 (covid19uk_amd/csrc/rt_keep_kernels.h) runs in place of k_rt_trace and leaves every draw's R_it in the store
-keepR[B][D][M][cap]; k_order_stats_f64 (order_stats64_kernels.h) selects exact order statistics from it.
+keepR[B][D][M][cap]; k_order_stats_f64 (order_stats_kernels.h) selects exact order statistics from it.
 
 The selection alone is held, bit for bit (`.view(np.uint64)`), to Python's sorted() under the total-order key of
 tests/test_rt_quantiles_host.py through `SeirModel.order_stats_f64`, on values no model produces.  The store plus the

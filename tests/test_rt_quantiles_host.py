@@ -1,5 +1,5 @@
 """Host side of the R_t intervals (include/seir_hip.h, "R_t intervals on the device"), no GPU: the symbols, the 64-bit
-narrowing step of the radix select (covid19uk_amd/csrc/order_select64.h, the one definition k_order_stats_f64 calls) compiled
+narrowing step of the radix select (covid19uk_amd/csrc/order_select.h, the one definition k_order_stats_f64 calls) compiled
 as plain C++ and driven through its eight passes against Python's sorted() under an independently written total-order key,
 the key map itself, the configuration and the command line, run_mcmc's call sequence with a stub sampler, the datasets
 written, and the compiler's account of the two new kernels."""
@@ -126,7 +126,7 @@ DRIVER = r"""
 #include <cstdio>
 #include <unordered_map>
 #include <vector>
-#include "order_select64.h"
+#include "order_select.h"
 // stdin: n, then n bit patterns (unsigned decimal).  stdout: for every rank 0 .. n-1 the bit pattern the eight-pass select
 // arrives at, one per line.  As in k_order_stats_f64, ranks whose prefixes agree share a histogram, and a value is counted
 // under the prefix it matches.
@@ -142,34 +142,34 @@ int main() {
     for (int pass = 0; pass < seir::ORDER64_PASSES; ++pass) {
         std::unordered_map<uint64_t, std::vector<uint32_t>> hist;
         for (uint64_t p : prefix) if (!hist.count(p)) hist[p] = std::vector<uint32_t>(seir::ORDER_BINS, 0u);
-        const int sh = seir::order64_shift(pass);
+        const int sh = seir::order_shift<uint64_t>(pass);
         if (sh != 56 - 8 * pass) return 9;
         for (uint64_t x : v) {
-            const uint64_t key = seir::order64_key(x);
-            if (seir::order64_value(key) != x) return 3;
+            const uint64_t key = seir::order_key(x);
+            if (seir::order_value(key) != x) return 3;
             const uint64_t high = pass == 0 ? 0ull : key & ~((1ull << (sh + seir::ORDER_DIGIT_BITS)) - 1ull);
             auto it = hist.find(high);
             if (it == hist.end()) continue;
-            if (!seir::order64_matches(key, it->first, pass)) return 4;
-            it->second[seir::order64_digit(key, pass)] += 1u;
+            if (!seir::order_matches(key, it->first, pass)) return 4;
+            it->second[seir::order_digit(key, pass)] += 1u;
         }
         for (long long r = 0; r < n; ++r)
-            if (!seir::order64_select_narrow(hist[prefix[(size_t)r]].data(), pass, prefix[(size_t)r], rem[(size_t)r])) return 5;
+            if (!seir::order_select_narrow(hist[prefix[(size_t)r]].data(), pass, prefix[(size_t)r], rem[(size_t)r])) return 5;
     }
     for (long long r = 0; r < n; ++r) {
         if (rem[(size_t)r] >= (uint32_t)n) return 6;
-        std::printf("%" PRIu64 "\n", seir::order64_value(prefix[(size_t)r]));
+        std::printf("%" PRIu64 "\n", seir::order_value(prefix[(size_t)r]));
     }
     // a rank past the count is refused, and the state is left alone
     std::vector<uint32_t> h(seir::ORDER_BINS, 0u);
     h[7] = 3;
     uint64_t p = 0x1200000000000000ull;
     uint32_t k = 3;
-    if (seir::order64_select_narrow(h.data(), 1, p, k) || p != 0x1200000000000000ull || k != 3) return 7;
+    if (seir::order_select_narrow(h.data(), 1, p, k) || p != 0x1200000000000000ull || k != 3) return 7;
     k = 2;
-    if (!seir::order64_select_narrow(h.data(), 1, p, k) || p != 0x1207000000000000ull || k != 2) return 8;
+    if (!seir::order_select_narrow(h.data(), 1, p, k) || p != 0x1207000000000000ull || k != 2) return 8;
     p = 0xFFFFFFFFFFFFFF00ull; k = 2;
-    if (!seir::order64_select_narrow(h.data(), 7, p, k) || p != 0xFFFFFFFFFFFFFF07ull || k != 2) return 10;
+    if (!seir::order_select_narrow(h.data(), 7, p, k) || p != 0xFFFFFFFFFFFFFF07ull || k != 2) return 10;
     return 0;
 }
 """
@@ -244,7 +244,7 @@ def test_the_key_map_is_an_involution_and_strictly_monotone_on_finite_doubles():
         assert 0 <= k <= MASK and value_of(k) == b
     assert total_order_key(bits_of([-0.0])[0]) + 1 == total_order_key(bits_of([0.0])[0])
     # and the header says the same thing in its own words
-    text = open(os.path.join(entry.CSRC, "order_select64.h")).read()
+    text = open(os.path.join(entry.CSRC, "order_select.h")).read()
     assert "bits ^ ((bits >> 63) ? ~0ull : 1ull << 63)" in text and "key ^ ((key >> 63) ? 1ull << 63 : ~0ull)" in text
 
 
