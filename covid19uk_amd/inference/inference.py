@@ -696,6 +696,11 @@ def diagnostics_marks(nb):
     return marks
 
 
+def _stack(bursts, *shape):
+    """The bursts' kept arrays as one [n, ...]; [0, *shape] when there was no burst."""
+    return np.concatenate(bursts) if bursts else np.empty((0,) + shape)
+
+
 def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_step_size=False, forecast_calendar=None,
              seed=0, rt_weight=None, check_calendar=None, groups=None, population=None):
     """The windowed schedule of inference.py:303-470: fast 200, slow 25*2^k (k<6), fast 50,
@@ -704,49 +709,18 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     the sampling phase keeps every `thin`-th sweep: num_burst_samples kept draws per burst from
     num_burst_samples * thin sweeps (inference.py:455), thinned on the device.
 
-    With Mcmc.forecast = H (`forecast_mode`) every kept draw of the sampling phase is forecast H days on the device
-    behind its burst; `forecast_calendar` = (W [H], weekday_c [H]) (`posterior.predict.forecast_calendar`) and `seed`
-    (the forecast's Philox stream and, with forecast_walk, the steps) are then needed.  The warm-up is not forecast.
-
-    With Mcmc.forecast_quantiles (`forecast_quantiles_mode`; needs Mcmc.forecast) the device keeps cases, cumulative cases
-    and prevalence of every forecast draw: the store is sized once, right behind the forecast's reset, for num_bursts x
-    num_burst_samples draws per chain, and at the end of the run exact quantiles per location and forecast day are selected
-    on the device, per chain and pooled over the chains of this process.  Without the key nothing of it is called.
-
-    With Mcmc.rt = D (`rt_mode`) R_it of every kept draw of the sampling phase over the last D days is formed and folded
-    on the device behind its burst (and behind the burst's summary and forecast); `rt_weight` [M] = N / N.sum() is then
-    needed.  The warm-up is not folded; without the key nothing of it is called.
-
-    With Mcmc.rt_quantiles (`rt_quantiles_mode`; needs Mcmc.rt) the device keeps R_it of every folded draw: the store is
-    sized once, right behind the rt reset, for num_bursts x num_burst_samples draws per chain, and at the end of the run
-    exact quantiles per day and location are selected on the device, per chain and pooled over the chains of this process;
-    the national curve's quantiles are formed here from the draws of R_t.  Without the key nothing of it is called.
-
-    With Mcmc.check = K (`check_mode`) the last K days are simulated again from every kept draw of the sampling phase and
-    set against the observed removals on the device, behind the burst's summary, forecast and R_t; `check_calendar` =
-    (W [K], weekday_c [K]) (`posterior.predict.check_calendar`) is then needed, and the check's stream is keyed by
-    `check_seed(seed)`.  The warm-up is not checked; without the key nothing of it is called.
-
-    With Mcmc.within_between = D (`within_between_mode`) the within/between pressure shares of every kept draw of the
-    sampling phase over the last D days are formed and folded on the device, behind the burst's summary, forecast, R_t and
-    check.  The warm-up is not folded; without the key nothing of it is called.
-
-    With `groups` (a `posterior.groups.GroupTable`, Mcmc.groups resolved by `mcmc`; needs one of summaries on / only,
-    forecast, check) the table is set on the sampler once, before the first draw: from then on the summary, the forecast
-    and the check of every burst also form the draw's sums over each group's members on the device, and these cross with
-    the trace.  In the warm-up that rides on the summary which `summaries` already asks for there, and on nothing else.
-    The statistics are formed here (`posterior.groups`).  Without it nothing of it is called.
-
-    With Mcmc.groups_rt (needs `groups`, Mcmc.rt and `population` = N [M]) and Mcmc.groups_within_between (needs `groups`
-    and Mcmc.within_between) the switches are set on the sampler once, behind the table: R_t, population-weighted, and the
-    within / between pressures of every kept draw of the sampling phase are then also formed per group on the device and
-    cross with the trace (`trace.group_curves`).  Without the keys nothing of it is called."""
+    What each option adds is said at its record below, a product's three parts side by side: begin() -- the reset behind
+    the warm-up, the draw store where quantiles are on; flush(tr, burst) -- what must outlive the pinned view copied, its
+    datasets written at its row offset, what the end needs kept (burst is None in the warm-up); finish() -- the blocking
+    summary read, the write_* calls and the log line.  A product that is off has no record: nothing of it is called."""
+    # 1. resolve the modes and refuse what cannot run -- before the first call on the sampler
+    s, T = sampler, getattr(sampler, "T", None)
     thin = thin_interval(config)
-    wb_days = within_between_mode(config, T=getattr(sampler, "T", None))
-    check_days = check_mode(config, T=getattr(sampler, "T", None))
+    wb_days = within_between_mode(config, T=T)
+    check_days = check_mode(config, T=T)
     if check_days and check_calendar is None:
         raise ValueError("check: run_mcmc needs check_calendar = (W, weekday_c) of the window")
-    rt_days = rt_mode(config, T=getattr(sampler, "T", None))
+    rt_days = rt_mode(config, T=T)
     if rt_days and rt_weight is None:
         raise ValueError("rt: run_mcmc needs rt_weight = N / N.sum()")
     horizon, walk = forecast_mode(config)
@@ -755,108 +729,293 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     fq_probs = forecast_quantiles_mode(config, horizon=horizon)
     rq_probs = rt_quantiles_mode(config, rt_days=rt_days)
     summaries = summaries_mode(config)
-    # "off": sample / sample_bursts are called exactly as before the option existed.  Otherwise every written draw gets its
-    # marginals (the warm-up without folding), the moments cover the sampling phase, and with "only" no event tensor is read
-    warm_kw = {} if summaries == "off" else dict(events=summaries != "only", summarize="marginals")
-    burst_kw = {} if summaries == "off" else dict(events=summaries != "only", summarize=True)
-    # diagnostics "on" folds the sampling phase's draws whatever `summaries` says (which then only decides what is written)
     diagnostics, batch_len = diagnostics_mode(config)
-    marks, theta_acc = {}, None
-    if diagnostics == "on":
-        burst_kw = dict(events=summaries != "only", summarize=True)
-        marks = diagnostics_marks(int(config["num_bursts"]))
-        theta_acc = diag_mod.DrawAccumulator(batch_len)
-    grp_fc, grp_ck = [], []                                 # the sampling phase's group sums, kept for the statistics
-    grp_rt, grp_wb = [], []                                 # and its group curves
     groups_rt = G_mod.switch(config.get("groups_rt"), "groups_rt")
     groups_wb = G_mod.switch(config.get("groups_within_between"), "groups_within_between")
     G_mod.require_curves(groups, groups_rt, rt_days, groups_wb, wb_days)
     if groups_rt and population is None:
         raise ValueError("groups_rt: run_mcmc needs population = N")
-    if groups is not None:
+    nb, ns = int(config["num_bursts"]), int(config["num_burst_samples"])
+    chain_ids = [getattr(sampler, "first_chain_id", 0) + c for c in range(sampler.B)]
+    warm_kw, burst_kw = {}, {}                              # the keywords of the warm-up's and the sampling phase's draws
+    # `offset` counts every written draw, `kept` the sampling phase's: the row of every product's per-draw datasets (a field is
+    # in a trace exactly when its keyword was passed: all together, on the sampling phase's bursts); `check`: its summary
+    rows = dict(offset=0, kept=0, check=None)
+    records, grp = [], None                                 # (begin, flush, finish) in the order of the resets and the write-up
+
+    def write_rows(arrays, row):
+        for c, post in enumerate(posteriors):               # every chain's slice of per-draw arrays [n,B,...] into its file
+            post.write_samples({k: v[:, c] for k, v in arrays.items()}, first_dim_offset=row)
+
+    def writes(field):                                      # the flush of a product whose arrays go to the files as they are
+        def flush(tr, burst):
+            if getattr(tr, field, None) is not None:
+                write_rows(getattr(tr, field), rows["kept"])
+        return flush
+
+    # Mcmc.summaries and Mcmc.diagnostics.  Summaries "off": sample / sample_bursts are called exactly as before the option
+    # existed.  Otherwise every written draw gets its marginals (the warm-up without folding), the moments cover the sampling
+    # phase, and with "only" no event tensor is read.  Diagnostics "on" folds the sampling phase's draws whatever `summaries`
+    # says (which then only decides what is written)
+    marks = diagnostics_marks(nb) if diagnostics == "on" else {}
+    theta_acc = diag_mod.DrawAccumulator(batch_len) if diagnostics == "on" else None
+    if summaries != "off":
+        warm_kw.update(events=summaries != "only", summarize="marginals")
+    if summaries != "off" or diagnostics == "on":
+        burst_kw.update(events=summaries != "only", summarize=True)
+
+        def sm_begin():
+            if theta_acc is not None:
+                s.reset_diagnostics(batch_len)              # the moments too: all of it is over the sampling phase
+            else:
+                s.reset_summary()                           # the moments are over the sampling phase
+            if summaries == "only":
+                print("summaries only: the event tensors stay on the device and samples/seir is not created -- what reads it "
+                      "(thin_posterior, predict, reproduction_number) cannot run on this output", file=log, flush=True)
+
+        def sm_flush(tr, burst):
+            if theta_acc is not None and burst is not None:     # the parameters' accumulators, marked where the device's are
+                theta_acc.fold(tr.theta)
+                if burst in marks:
+                    theta_acc.mark(marks[burst])
+
+        def sm_finish():
+            dg = None
+            if theta_acc is not None:
+                dg = s.diagnostics()
+                ev = diag_mod.evaluate(dg, theta_acc.result())
+                for c, post in enumerate(posteriors):
+                    post.write_diagnostics(diag_mod.chain_datasets(ev, c))
+                print(diag_mod.run_line(ev, diag_mod.theta_names(s.P, s.M, s.T))
+                      + f" ({s.B} chain(s) of this process, batches of {batch_len})", file=log, flush=True)
+            if summaries != "off":
+                sm = s.summary() if dg is None else Summary(count=dg.count, ref=dg.ref, sum=dg.sum, sumsq=dg.sumsq)
+                mean, var = sm.mean, sm.var
+                for c, post in enumerate(posteriors):
+                    post.write_summary(sm.count[c], mean[c], var[c])
+        records.append((sm_begin, sm_flush, sm_finish))
+
+    # With Mcmc.forecast = H (`forecast_mode`) every kept draw of the sampling phase is forecast H days on the device
+    # behind its burst; `forecast_calendar` = (W [H], weekday_c [H]) (`posterior.predict.forecast_calendar`) and `seed`
+    # (the forecast's Philox stream and, with forecast_walk, the steps) are then needed.  The warm-up is not forecast.
+    # With Mcmc.forecast_quantiles (`forecast_quantiles_mode`; needs Mcmc.forecast) the device keeps cases, cumulative cases
+    # and prevalence of every forecast draw: the store is sized once, right behind the forecast's reset, for num_bursts x
+    # num_burst_samples draws per chain, and at the end of the run exact quantiles per location and forecast day are selected
+    # on the device, per chain and pooled over the chains of this process.  Without the key nothing of it is called.
+    if horizon:
+        burst_kw["forecast"] = forecast_steps_fn(seed, chain_ids, horizon) if walk else True
+
+        def fc_begin():
+            s.reset_forecast(horizon, forecast_calendar[0], forecast_calendar[1], seed)   # once: the sampling phase
+            if fq_probs:
+                s.keep_forecast_draws(nb * ns)              # the draw store of the quantiles: every kept draw of the phase
+
+        def fc_finish():
+            fs = s.forecast_summary()
+            mean, var = fs.mean, fs.var
+            for c, post in enumerate(posteriors):
+                post.write_forecast(horizon, s.T, fs.count[c], mean[c], var[c])
+            print(f"Forecast: {horizon} day(s) from day {s.T} for {int(fs.count.min()) if len(fs.count) else 0} kept draw(s) per "
+                  f"chain, formed on the device ({'random-walk' if walk else 'held'} baseline); forecast/* and "
+                  "samples/forecast_* written", file=log, flush=True)
+            if fq_probs and nb * ns:
+                own = s.forecast_quantiles(fq_probs)                        # [K,B,3,M,H]
+                pooled = s.forecast_quantiles(fq_probs, pooled=True)        # [K,3,M,H]
+                for c, post in enumerate(posteriors):
+                    post.write_forecast_quantiles(fq_probs, own[:, c], pooled, chain_ids)
+                print(f"Forecast quantiles: {', '.join(f'{p:g}' for p in fq_probs)} of cases, cumulative cases and prevalence per "
+                      f"location and forecast day, exact over {nb * ns} kept draw(s) per chain and pooled over the {s.B} "
+                      "chain(s) of this process, selected on the device; forecast/*_quantiles written", file=log, flush=True)
+        records.append((fc_begin, writes("forecast"), fc_finish))
+
+    # With Mcmc.rt = D (`rt_mode`) R_it of every kept draw of the sampling phase over the last D days is formed and folded
+    # on the device behind its burst (and behind the burst's summary and forecast); `rt_weight` [M] = N / N.sum() is then
+    # needed.  The warm-up is not folded; without the key nothing of it is called.
+    # With Mcmc.rt_quantiles (`rt_quantiles_mode`; needs Mcmc.rt) the device keeps R_it of every folded draw: the store is
+    # sized once, right behind the rt reset, for num_bursts x num_burst_samples draws per chain, and at the end of the run
+    # exact quantiles per day and location are selected on the device, per chain and pooled over the chains of this process;
+    # the national curve's quantiles are formed here from the draws of R_t.  Without the key nothing of it is called.
+    if rt_days:
+        burst_kw["rt"], rt_draws = True, []
+
+        def rt_begin():
+            s.reset_rt(rt_days, rt_weight)                  # once: the sampling phase
+            if rq_probs:
+                s.keep_rt_draws(nb * ns)                    # the draw store of the quantiles: every kept draw of the phase
+
+        def rt_flush(tr, burst):
+            if getattr(tr, "rt", None) is not None:
+                rt_draws.append(np.array(tr.rt))            # the pinned buffer is used again two bursts later
+                write_rows({"R_t": rt_draws[-1]}, rows["kept"])
+
+        def rt_finish():
+            rs = s.rt_summary()
+            mean, var, prob = rs.mean, rs.var, rs.prob_gt1
+            for c, post in enumerate(posteriors):
+                post.write_rt(rt_days, s.T - rt_days, rs.count[c], mean[c], var[c], prob[c])
+            r_t = _stack(rt_draws, s.B, rt_days)
+            print(rt_run_line(rt_days, s.T, r_t, prob), file=log, flush=True)
+            if rq_probs and nb * ns:
+                own = s.rt_quantiles(rq_probs)                              # [K,B,D,M]
+                pooled = s.rt_quantiles(rq_probs, pooled=True)              # [K,D,M]
+                nat = draw_quantiles(r_t, rq_probs)                         # [K,B,D]: costs nothing here
+                pnat = draw_quantiles(r_t.reshape(-1, rt_days), rq_probs)   # [K,D]
+                for c, post in enumerate(posteriors):
+                    post.write_rt_quantiles(rq_probs, own[:, c], pooled, chain_ids, nat[:, c], pnat)
+                print(rt_quantiles_run_line(rq_probs, rt_days, s.T, nb * ns, s.B, own), file=log, flush=True)
+        records.append((rt_begin, rt_flush, rt_finish))
+
+    # With Mcmc.check = K (`check_mode`) the last K days are simulated again from every kept draw of the sampling phase and
+    # set against the observed removals on the device, behind the burst's summary, forecast and R_t; `check_calendar` =
+    # (W [K], weekday_c [K]) (`posterior.predict.check_calendar`) is then needed, and the check's stream is keyed by
+    # `check_seed(seed)`.  The warm-up is not checked; without the key nothing of it is called.
+    if check_days:
+        burst_kw["check"] = True
+
+        def ck_finish():
+            rows["check"] = cs = s.check_summary()
+            mean, var = cs.moments.mean, cs.moments.var
+            for c, post in enumerate(posteriors):
+                post.write_check(check_days, s.T - check_days, cs.count[c], mean[c], var[c], check_chain_datasets(cs, c))
+            print(check_run_line(check_days, s.T, cs), file=log, flush=True)
+        records.append((lambda: s.reset_check(check_days, check_calendar[0], check_calendar[1], check_seed(seed)),   # once
+                        writes("check"), ck_finish))
+
+    # With `groups` (a `posterior.groups.GroupTable`, Mcmc.groups resolved by `mcmc`; needs one of summaries on / only,
+    # forecast, check) the table is set on the sampler once, before the first draw: from then on the summary, the forecast
+    # and the check of every burst also form the draw's sums over each group's members on the device, and these cross with
+    # the trace.  In the warm-up that rides on the summary which `summaries` already asks for there, and on nothing else.
+    # The statistics are formed here (`posterior.groups`).  Without it nothing of it is called.
+    # With Mcmc.groups_rt (needs `groups`, Mcmc.rt and `population` = N [M]) and Mcmc.groups_within_between (needs `groups`
+    # and Mcmc.within_between) the switches are set on the sampler once, behind the table: R_t, population-weighted, and the
+    # within / between pressures of every kept draw of the sampling phase are then also formed per group on the device and
+    # cross with the trace (`trace.group_curves`).  Without the keys nothing of it is called.
+    if groups is not None:                                  # the one record that calls the sampler here, ahead of the warm-up
         G_mod.require_source(groups, summaries, horizon, check_days, groups_rt, groups_wb)
-        sampler.set_groups(groups.offsets, groups.members)  # once; the sources size their outputs at their resets
+        s.set_groups(groups.offsets, groups.members)        # once; the sources size their outputs at their resets
         if groups_rt:
             rt_w = G_mod.rt_weights(groups, population)
-            sampler.set_group_rt(rt_w)                      # once, behind the table; sized at the rt reset
+            s.set_group_rt(rt_w)                            # once, behind the table; sized at the rt reset
             for post in posteriors:
                 post.create_dataset("groups/rt_weights", rt_w)
         if groups_wb:
-            sampler.set_group_within_between(True)
+            s.set_group_within_between(True)
         # the sources whose sums are written: the trace's only with summaries on / only (diagnostics alone also summarises
         # every burst, but nothing of it goes to the file)
         grp_src = tuple(k for k, on in (("trace", summaries != "off"), ("forecast", horizon), ("check", check_days)) if on)
         if summaries != "off":
-            warm_kw = dict(warm_kw, groups=("trace",))
+            warm_kw["groups"] = ("trace",)
         if grp_src:                                         # with the group curves alone there is nothing to ask for
-            burst_kw = dict(burst_kw, groups=grp_src)
+            burst_kw["groups"] = grp_src
+        grp_fc, grp_ck, grp_rt, grp_wb = [], [], [], []     # the sampling phase's group sums and curves, kept for the statistics
+
+        def grp_flush(tr, burst):
+            if getattr(tr, "groups", None) is not None:
+                g = {k: np.array(v) for k, v in tr.groups.items()}   # the pinned buffer is used again two bursts later
+                if "forecast_by_group" in g:
+                    grp_fc.append((g["forecast_by_group"], g["forecast_group_state0"]))
+                if "check_by_group" in g:
+                    grp_ck.append(g["check_by_group"])
+                for c, post in enumerate(posteriors):
+                    if "seir_by_group" in g:
+                        post.write_samples({"seir_by_group": g["seir_by_group"][:, c]}, first_dim_offset=rows["offset"])
+                    post.write_samples({k: v[:, c] for k, v in g.items() if k.startswith("forecast_")}, first_dim_offset=rows["kept"])
+                    post.write_samples({k: v[:, c] for k, v in g.items() if k.startswith("check_")}, first_dim_offset=rows["kept"])
+            if (groups_rt or groups_wb) and getattr(tr, "group_curves", None) is not None:
+                gc = {k: np.array(v) for k, v in tr.group_curves.items()}   # the pinned buffer is used again two bursts later
+                if "rt_by_group" in gc:
+                    grp_rt.append(gc["rt_by_group"])
+                    write_rows({"R_t_by_group": gc["rt_by_group"]}, rows["kept"])
+                if "within_by_group" in gc:
+                    grp_wb.append((gc["within_by_group"], gc["between_by_group"]))
+                    write_rows({"within_pressure_by_group": gc["within_by_group"],
+                                "between_pressure_by_group": gc["between_by_group"]}, rows["kept"])
+
+        def grp_finish():
+            if horizon and grp_fc:
+                ev = np.concatenate([x[0] for x in grp_fc])     # [nf,B,G,H,3]
+                st0 = np.concatenate([x[1] for x in grp_fc])    # [nf,B,G,3]
+                state = G_mod.group_state(ev, st0)
+                q = None
+                if fq_probs:
+                    planes = G_mod.forecast_planes(ev, st0)     # [3,nf,B,G,H]
+                    q = {name: (G_mod.quantiles(planes[x], fq_probs),                                    # [K,B,G,H]
+                                G_mod.quantiles(planes[x].reshape((-1,) + planes.shape[3:]), fq_probs))   # [K,G,H]
+                         for x, name in enumerate(G_mod.PLANES)}
+                for c, post in enumerate(posteriors):
+                    post.write_group_forecast(ev[:, c].mean(axis=0), state[:, c].mean(axis=0),
+                                              None if q is None else {k: (v[0][:, c], v[1]) for k, v in q.items()})
+            if check_days and grp_ck:
+                sim = np.concatenate(grp_ck)                    # [nf,B,G,K,3]
+                for c, post in enumerate(posteriors):
+                    post.write_group_check(G_mod.check_counts(sim[:, c], groups.sum_rows(rows["check"].observed[c])))
+            sources = [k for k, on in (("the recorded epidemic", summaries != "off"), ("the forecast", horizon),
+                                       ("the check", check_days)) if on]
+            if sources:
+                print(G_mod.run_line(groups, sources), file=log, flush=True)
+            if groups_rt:
+                rg = _stack(grp_rt, s.B, groups.G, rt_days)     # [n,B,G,D]
+                q = None
+                if rq_probs and rg.shape[0]:
+                    q = (draw_quantiles(rg, rq_probs), draw_quantiles(rg.reshape((-1,) + rg.shape[2:]), rq_probs))   # [K,B,G,D], [K,G,D]
+                for c, post in enumerate(posteriors):
+                    post.write_group_rt(*G_mod.curve_moments(rg[:, c]), None if q is None else (q[0][:, c], q[1]))
+                print(G_mod.curve_run_line("R_t", groups, rg, "samples/R_t_by_group and rt/group_*"), file=log, flush=True)
+            if groups_wb:
+                wg, bg = (_stack([x[i] for x in grp_wb], s.B, groups.G, wb_days) for i in (0, 1))
+                for c, post in enumerate(posteriors):
+                    post.write_group_within_between(*G_mod.share_stats(wg[:, c], bg[:, c]))
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    share = wg / (wg + bg)
+                print(G_mod.curve_run_line("Within share of the infection pressure (between: from outside each member location)",
+                                           groups, share, "samples/*_pressure_by_group and within_between/group_*"),
+                      file=log, flush=True)
+        grp = (lambda: None, grp_flush, grp_finish)
+        records.append(grp)
+
+    # With Mcmc.within_between = D (`within_between_mode`) the within/between pressure shares of every kept draw of the
+    # sampling phase over the last D days are formed and folded on the device, behind the burst's summary, forecast, R_t and
+    # check.  The warm-up is not folded; without the key nothing of it is called.
+    if wb_days:
+        burst_kw["within_between"], wb_draws = True, []
+
+        def wb_flush(tr, burst):
+            if getattr(tr, "wb", None) is not None:
+                wb_draws.append({k: np.array(v) for k, v in tr.wb.items()})   # the pinned buffer is used again two bursts later
+                write_rows(wb_draws[-1], rows["kept"])
+
+        def wb_finish():
+            ws = s.within_between_summary()
+            wm, wv, bm, pg = ws.within_mean, ws.within_var, ws.between_mean, ws.p_within_gt_between
+            for c, post in enumerate(posteriors):
+                post.write_within_between(wb_days, s.T - wb_days, ws.count[c], ws.defined[c], wm[c], wv[c], bm[c], pg[c])
+            wn, bn = (_stack([w[k] for w in wb_draws], s.B, wb_days) for k in ("within_pressure", "between_pressure"))
+            print(within_between_run_line(wb_days, s.T, wn, bn, pg), file=log, flush=True)
+        records.append((lambda: s.reset_within_between(wb_days), wb_flush, wb_finish))   # the reset: once, the sampling phase
+    # a burst is written out groups first, then last record to first: the order the files have always been written in
+    flush_order = ([grp] if grp else []) + [r for r in reversed(records) if r is not grp]
+
+    def flush(tr, burst=None):
+        for _, product_flush, _ in flush_order:
+            product_flush(tr, burst)
+        for c, post in enumerate(posteriors):
+            post.write_samples(draws_to_dict(tr.theta, tr.events, c, **({} if summaries == "off" else dict(marginals=tr.marginals))),
+                               first_dim_offset=rows["offset"])
+            post.write_results(trace_to_dict(tr, c), first_dim_offset=rows["offset"])
+        rows["offset"] += tr.theta.shape[0]
+        if burst is not None:
+            rows["kept"] += tr.theta.shape[0]
+        return tr
+
+    # 2. warm up
     sampler.set_thin(1)
     first_window_size, last_window_size, slow_window_size, num_slow_windows = 200, 50, 25, 6
     dual_averaging_kwargs = {"target_accept_prob": 0.75}
-    offset = 0
-    fc_offset = 0
-    rt_offset = 0
-    rt_draws = []
-    ck_offset = 0
-    wb_offset = 0
-    wb_draws = []
-
-    def flush(tr):
-        nonlocal offset, fc_offset, rt_offset, ck_offset, wb_offset
-        n = tr.theta.shape[0]
-        if groups is not None and getattr(tr, "groups", None) is not None:
-            g = {k: np.array(v) for k, v in tr.groups.items()}   # the pinned buffer is used again two bursts later
-            if "forecast_by_group" in g:
-                grp_fc.append((g["forecast_by_group"], g["forecast_group_state0"]))
-            if "check_by_group" in g:
-                grp_ck.append(g["check_by_group"])
-            for c, post in enumerate(posteriors):
-                if "seir_by_group" in g:
-                    post.write_samples({"seir_by_group": g["seir_by_group"][:, c]}, first_dim_offset=offset)
-                post.write_samples({k: v[:, c] for k, v in g.items() if k.startswith("forecast_")}, first_dim_offset=fc_offset)
-                post.write_samples({k: v[:, c] for k, v in g.items() if k.startswith("check_")}, first_dim_offset=ck_offset)
-        if (groups_rt or groups_wb) and getattr(tr, "group_curves", None) is not None:
-            gc = {k: np.array(v) for k, v in tr.group_curves.items()}   # the pinned buffer is used again two bursts later
-            if "rt_by_group" in gc:
-                grp_rt.append(gc["rt_by_group"])
-                for c, post in enumerate(posteriors):
-                    post.write_samples({"R_t_by_group": gc["rt_by_group"][:, c]}, first_dim_offset=rt_offset)
-            if "within_by_group" in gc:
-                grp_wb.append((gc["within_by_group"], gc["between_by_group"]))
-                for c, post in enumerate(posteriors):
-                    post.write_samples({"within_pressure_by_group": gc["within_by_group"][:, c],
-                                        "between_pressure_by_group": gc["between_by_group"][:, c]}, first_dim_offset=wb_offset)
-        if wb_days and getattr(tr, "wb", None) is not None:
-            w = {k: np.array(v) for k, v in tr.wb.items()}  # the pinned buffer is used again two bursts later
-            wb_draws.append(w)
-            for c, post in enumerate(posteriors):
-                post.write_samples({k: v[:, c] for k, v in w.items()}, first_dim_offset=wb_offset)
-            wb_offset += n
-        if check_days and getattr(tr, "check", None) is not None:
-            for c, post in enumerate(posteriors):
-                post.write_samples({k: v[:, c] for k, v in tr.check.items()}, first_dim_offset=ck_offset)
-            ck_offset += n
-        if rt_days and getattr(tr, "rt", None) is not None:
-            r = np.array(tr.rt)                            # the pinned buffer is used again two bursts later
-            rt_draws.append(r)
-            for c, post in enumerate(posteriors):
-                post.write_samples({"R_t": r[:, c]}, first_dim_offset=rt_offset)
-            rt_offset += n
-        if horizon and tr.forecast is not None:
-            for c, post in enumerate(posteriors):
-                post.write_samples({k: v[:, c] for k, v in tr.forecast.items()}, first_dim_offset=fc_offset)
-            fc_offset += n
-        for c, post in enumerate(posteriors):
-            post.write_samples(draws_to_dict(tr.theta, tr.events, c, **({} if summaries == "off" else dict(marginals=tr.marginals))),
-                               first_dim_offset=offset)
-            post.write_results(trace_to_dict(tr, c), first_dim_offset=offset)
-        offset += n
 
     def window(n, adapt_mass, running_variance=None):
         sampler.set_adaptation(adapt_step_size=True, adapt_mass=adapt_mass, num_adaptation_steps=n,
                                running_variance=running_variance, **dual_averaging_kwargs)
-        tr = sampler.sample(n, **warm_kw)
-        flush(tr)
+        tr = flush(sampler.sample(n, **warm_kw))
         return tr, get_weighted_running_variance(unconstrain_theta(tr.theta))
 
     print(f"Fast window {first_window_size}", file=log, flush=True)
@@ -869,6 +1028,7 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     print(f"Fast window {last_window_size}", file=log, flush=True)
     tr, _ = window(last_window_size, False)
 
+    # 3. sample
     print("Sampling...", file=log, flush=True)
     step_size = tr.hmc["step_size"][(-last_window_size) // 2:].mean(axis=0)      # inference.py:439-441
     if pool_step_size:
@@ -879,163 +1039,33 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
         print(f"Pooled step size over all chains: {step_size[0]:.4g}", file=log, flush=True)
     sampler.set_adaptation(adapt_step_size=False)
     sampler.set_kernel(step_size=step_size, variance=sampler.get_kernel()[1])
-    nb, ns = int(config["num_bursts"]), int(config["num_burst_samples"])
     sampler.set_thin(thin)                                  # in force from the first burst's trace reset
-    if diagnostics == "on":
-        sampler.reset_diagnostics(batch_len)                # the moments too: all of it is over the sampling phase
-    elif summaries != "off":
-        sampler.reset_summary()                             # the moments are over the sampling phase
-    if horizon:
-        sampler.reset_forecast(horizon, forecast_calendar[0], forecast_calendar[1], seed)   # once: the sampling phase
-        if fq_probs:
-            sampler.keep_forecast_draws(nb * ns)            # the draw store of the quantiles: every kept draw of the phase
-        first_id = getattr(sampler, "first_chain_id", 0)
-        burst_kw = dict(burst_kw, forecast=forecast_steps_fn(seed, [first_id + c for c in range(sampler.B)], horizon)
-                        if walk else True)
-    if rt_days:
-        sampler.reset_rt(rt_days, rt_weight)                # once: the sampling phase
-        if rq_probs:
-            sampler.keep_rt_draws(nb * ns)                  # the draw store of the quantiles: every kept draw of the phase
-        burst_kw = dict(burst_kw, rt=True)
-    if check_days:
-        sampler.reset_check(check_days, check_calendar[0], check_calendar[1], check_seed(seed))   # once: the sampling phase
-        burst_kw = dict(burst_kw, check=True)
-    if wb_days:
-        sampler.reset_within_between(wb_days)               # once: the sampling phase
-        burst_kw = dict(burst_kw, within_between=True)
-    if summaries == "only":
-        print("summaries only: the event tensors stay on the device and samples/seir is not created -- what reads it "
-              "(thin_posterior, predict, reproduction_number) cannot run on this output", file=log, flush=True)
+    for begin, _, _ in records:
+        begin()
+
+    def on_burst(tr, i):
+        flush(tr, i)
+        print(f"  burst {i + 1}/{nb}", file=log, flush=True)
     t0 = time.perf_counter()
     if nb and ns and sampler.cap >= 2 * ns:
         # bursts overlap: while burst k+1 runs, burst k crosses PCIe into page-locked memory and is written
         # to the HDF5 file on a worker thread (ChainSampler.sample_bursts)
-        def on_burst(tr, i):
-            flush(tr)
-            if theta_acc is not None:                       # the parameters' accumulators, marked where the device's are
-                theta_acc.fold(tr.theta)
-                if i in marks:
-                    theta_acc.mark(marks[i])
-            print(f"  burst {i + 1}/{nb}", file=log, flush=True)
         sampler.sample_bursts(nb, ns, on_burst, **burst_kw, **(dict(marks=marks) if marks else {}))
     else:
         for i in range(nb):
             tr = sampler.sample(ns, **burst_kw)
             if i in marks:
                 sampler.mark(marks[i])
-            flush(tr)
-            if theta_acc is not None:
-                theta_acc.fold(tr.theta)
-                if i in marks:
-                    theta_acc.mark(marks[i])
-            print(f"  burst {i + 1}/{nb}", file=log, flush=True)
+            on_burst(tr, i)
     dt = time.perf_counter() - t0
     if nb * ns:
         print(f"Sampling: {nb * ns * thin * sampler.B / dt:.1f} sweeps/s, {nb * ns * sampler.B / dt:.1f} kept posterior samples/s "
               f"(thin {thin}, {sampler.B} chain(s), device->host->disk included)", file=log, flush=True)
-    dg = None
-    if diagnostics == "on":
-        dg = sampler.diagnostics()
-        ev = diag_mod.evaluate(dg, theta_acc.result())
-        for c, post in enumerate(posteriors):
-            post.write_diagnostics(diag_mod.chain_datasets(ev, c))
-        print(diag_mod.run_line(ev, diag_mod.theta_names(sampler.P, sampler.M, sampler.T))
-              + f" ({sampler.B} chain(s) of this process, batches of {batch_len})", file=log, flush=True)
-    if summaries != "off":
-        sm = sampler.summary() if dg is None else Summary(count=dg.count, ref=dg.ref, sum=dg.sum, sumsq=dg.sumsq)
-        mean, var = sm.mean, sm.var
-        for c, post in enumerate(posteriors):
-            post.write_summary(sm.count[c], mean[c], var[c])
-    if horizon:
-        fs = sampler.forecast_summary()
-        mean, var = fs.mean, fs.var
-        for c, post in enumerate(posteriors):
-            post.write_forecast(horizon, sampler.T, fs.count[c], mean[c], var[c])
-        print(f"Forecast: {horizon} day(s) from day {sampler.T} for {int(fs.count.min()) if len(fs.count) else 0} kept draw(s) per "
-              f"chain, formed on the device ({'random-walk' if walk else 'held'} baseline); forecast/* and "
-              "samples/forecast_* written", file=log, flush=True)
-        if fq_probs and nb * ns:
-            first_id = getattr(sampler, "first_chain_id", 0)
-            own = sampler.forecast_quantiles(fq_probs)                  # [K,B,3,M,H]
-            pooled = sampler.forecast_quantiles(fq_probs, pooled=True)  # [K,3,M,H]
-            for c, post in enumerate(posteriors):
-                post.write_forecast_quantiles(fq_probs, own[:, c], pooled, [first_id + b for b in range(sampler.B)])
-            print(f"Forecast quantiles: {', '.join(f'{p:g}' for p in fq_probs)} of cases, cumulative cases and prevalence per "
-                  f"location and forecast day, exact over {nb * ns} kept draw(s) per chain and pooled over the {sampler.B} "
-                  "chain(s) of this process, selected on the device; forecast/*_quantiles written", file=log, flush=True)
-    if rt_days:
-        rs = sampler.rt_summary()
-        mean, var, prob = rs.mean, rs.var, rs.prob_gt1
-        for c, post in enumerate(posteriors):
-            post.write_rt(rt_days, sampler.T - rt_days, rs.count[c], mean[c], var[c], prob[c])
-        r_t = np.concatenate(rt_draws) if rt_draws else np.empty((0, sampler.B, rt_days))
-        print(rt_run_line(rt_days, sampler.T, r_t, prob), file=log, flush=True)
-        if rq_probs and nb * ns:
-            first_id = getattr(sampler, "first_chain_id", 0)
-            own = sampler.rt_quantiles(rq_probs)                        # [K,B,D,M]
-            pooled = sampler.rt_quantiles(rq_probs, pooled=True)        # [K,D,M]
-            nat = draw_quantiles(r_t, rq_probs)                         # [K,B,D]: costs nothing here
-            pnat = draw_quantiles(r_t.reshape(-1, rt_days), rq_probs)   # [K,D]
-            for c, post in enumerate(posteriors):
-                post.write_rt_quantiles(rq_probs, own[:, c], pooled, [first_id + b for b in range(sampler.B)], nat[:, c], pnat)
-            print(rt_quantiles_run_line(rq_probs, rt_days, sampler.T, nb * ns, sampler.B, own), file=log, flush=True)
-    if check_days:
-        cs = sampler.check_summary()
-        mean, var = cs.moments.mean, cs.moments.var
-        for c, post in enumerate(posteriors):
-            post.write_check(check_days, sampler.T - check_days, cs.count[c], mean[c], var[c], check_chain_datasets(cs, c))
-        print(check_run_line(check_days, sampler.T, cs), file=log, flush=True)
-    if groups is not None:
-        if horizon and grp_fc:
-            ev = np.concatenate([x[0] for x in grp_fc])     # [nf,B,G,H,3]
-            st0 = np.concatenate([x[1] for x in grp_fc])    # [nf,B,G,3]
-            state = G_mod.group_state(ev, st0)
-            q = None
-            if fq_probs:
-                planes = G_mod.forecast_planes(ev, st0)     # [3,nf,B,G,H]
-                q = {name: (G_mod.quantiles(planes[x], fq_probs),                                    # [K,B,G,H]
-                            G_mod.quantiles(planes[x].reshape((-1,) + planes.shape[3:]), fq_probs))   # [K,G,H]
-                     for x, name in enumerate(G_mod.PLANES)}
-            for c, post in enumerate(posteriors):
-                post.write_group_forecast(ev[:, c].mean(axis=0), state[:, c].mean(axis=0),
-                                          None if q is None else {k: (v[0][:, c], v[1]) for k, v in q.items()})
-        if check_days and grp_ck:
-            sim = np.concatenate(grp_ck)                    # [nf,B,G,K,3]
-            for c, post in enumerate(posteriors):
-                post.write_group_check(G_mod.check_counts(sim[:, c], groups.sum_rows(cs.observed[c])))
-        sources = [k for k, on in (("the recorded epidemic", summaries != "off"), ("the forecast", horizon), ("the check", check_days))
-                   if on]
-        if sources:
-            print(G_mod.run_line(groups, sources), file=log, flush=True)
-        if groups_rt:
-            rg = np.concatenate(grp_rt) if grp_rt else np.empty((0, sampler.B, groups.G, rt_days))   # [n,B,G,D]
-            q = None
-            if rq_probs and rg.shape[0]:
-                q = (draw_quantiles(rg, rq_probs), draw_quantiles(rg.reshape((-1,) + rg.shape[2:]), rq_probs))   # [K,B,G,D], [K,G,D]
-            for c, post in enumerate(posteriors):
-                post.write_group_rt(*G_mod.curve_moments(rg[:, c]), None if q is None else (q[0][:, c], q[1]))
-            print(G_mod.curve_run_line("R_t", groups, rg, "samples/R_t_by_group and rt/group_*"), file=log, flush=True)
-        if groups_wb:
-            empty = np.empty((0, sampler.B, groups.G, wb_days))
-            wg = np.concatenate([x[0] for x in grp_wb]) if grp_wb else empty
-            bg = np.concatenate([x[1] for x in grp_wb]) if grp_wb else empty
-            for c, post in enumerate(posteriors):
-                post.write_group_within_between(*G_mod.share_stats(wg[:, c], bg[:, c]))
-            with np.errstate(divide="ignore", invalid="ignore"):
-                share = wg / (wg + bg)
-            print(G_mod.curve_run_line("Within share of the infection pressure (between: from outside each member location)",
-                                       groups, share, "samples/*_pressure_by_group and within_between/group_*"),
-                  file=log, flush=True)
-    if wb_days:
-        ws = sampler.within_between_summary()
-        wm, wv, bm, pg = ws.within_mean, ws.within_var, ws.between_mean, ws.p_within_gt_between
-        for c, post in enumerate(posteriors):
-            post.write_within_between(wb_days, sampler.T - wb_days, ws.count[c], ws.defined[c], wm[c], wv[c], bm[c], pg[c])
-        empty = np.empty((0, sampler.B, wb_days))
-        wn = np.concatenate([w["within_pressure"] for w in wb_draws]) if wb_draws else empty
-        bn = np.concatenate([w["between_pressure"] for w in wb_draws]) if wb_draws else empty
-        print(within_between_run_line(wb_days, sampler.T, wn, bn, pg), file=log, flush=True)
-    return offset
+
+    # 4. write up
+    for _, _, finish in records:
+        finish()
+    return rows["offset"]
 
 
 def warmup_size():

@@ -13,6 +13,7 @@ from __future__ import annotations
 import ctypes
 import dataclasses
 import sys
+import typing
 
 import numpy as np
 
@@ -58,6 +59,80 @@ GROUP_KEYS = tuple(k for _, ev, st in GROUP_SOURCES.values() for k in (ev, st) i
 # group curves (set_group_rt / set_group_within_between): R_t and the within / between pressures of a draw per group
 GROUP_CURVE_KEYS = ("rt_by_group", "within_by_group", "between_by_group")
 SUMMARY_QUANTITIES = ("k_se", "k_ei", "k_ir", "S", "E", "I")
+
+
+class BurstProduct(typing.NamedTuple):
+    """A device product that rides on a burst of kept draws: one row of `BURST_PRODUCTS`."""
+    field: str          # the Trace / PinnedTrace field it fills; PinnedTrace's keyword has the same name
+    request: str        # the keyword of sample / sample_bursts that asks for it; None: the sampler's own switches decide
+    size: object        # (sampler, request, {field: size} of the rows above) -> the value that sizes its arrays, falsy when
+    #                     it is off; ValueError when it is asked for before its reset
+    arrays: object      # (sampler, size) -> {key: (trailing shape, dtype)} behind the leading [count, B]; one pair for rt
+    enqueue: str        # the method (first, count, *args) that enqueues it behind the sweeps; None: it rides on rows above
+    read: str           # the blocking reader (count) -> arrays; for a row without `enqueue`: (size, count)
+    read_async: str     # the reader on the copy stream (count, first, into); for a row without `enqueue`: (size, count, first, into)
+    args: object = lambda sampler, request, count: ()   # what `enqueue` takes beyond (first, count)
+    marks_behind: bool = False                          # the diagnostics' marks are enqueued right behind this row
+
+
+def _after_reset(attr, name):
+    """The size of a product whose reset leaves its extent in `sampler.<attr>` (0: never reset)."""
+    def size(sampler, request, sizes):
+        if request and not getattr(sampler, attr):
+            raise ValueError(f"{name} asked for before reset_{name}")
+        return getattr(sampler, attr) if request else 0
+    return size
+
+
+def _marginal_arrays(keys, whole=False):
+    """By day, by location, state by day: int64 [days,3], [M,3], [days,3]; `whole`: the size is a switch, the days are T."""
+    def arrays(sampler, days):
+        d = sampler.T if whole else int(days)
+        return {k: ((e, 3), np.int64) for k, e in zip(keys, (d, sampler.M, d))}
+    return arrays
+
+
+def _group_arrays(sampler, size):
+    out = {}
+    for src, L in size[1].items():
+        _, ev_key, st_key = GROUP_SOURCES[src]
+        out.update({ev_key: ((size[0], int(L), 3), np.int64)}, **({st_key: ((size[0], 3), np.int64)} if st_key else {}))
+    return out
+
+
+# The burst protocol, stated once (DESIGN.md, "The burst protocol"): per burst the products that are on are enqueued in this
+# order behind the sweeps, then read in this order behind the trace.  PinnedTrace, trace_view, sample and sample_bursts loop
+# over it and reach the sampler's methods by name, at call time.
+BURST_PRODUCTS = (
+    BurstProduct("marginals", "summarize", lambda s, req, sizes: s._summarize_mode(req),
+                 _marginal_arrays(MARGINAL_KEYS, whole=True), "summarize", "read_marginals", "read_marginals_async",
+                 args=lambda s, req, n: (req is True,), marks_behind=True),   # "marginals": written, not folded
+    # forecast=True holds the baseline; a callable (j0, count) -> steps [count,B,H] is asked with j0 = the draws per chain
+    # forecast since the reset, as they stand at enqueue time -- after a re-run of a burst it is the same again
+    BurstProduct("forecast", "forecast", _after_reset("_forecast_H", "forecast"), _marginal_arrays(FORECAST_KEYS),
+                 "forecast", "read_forecast_marginals", "read_forecast_marginals_async",
+                 args=lambda s, req, n: (req(s._fc_j, n) if callable(req) else None,)),
+    BurstProduct("rt", "rt", _after_reset("_rt_D", "rt"), lambda s, D: ((int(D),), np.float64),
+                 "rt", "read_rt_draws", "read_rt_draws_async"),
+    BurstProduct("check", "check", _after_reset("_check_K", "check"), _marginal_arrays(CHECK_KEYS),
+                 "check", "read_check_marginals", "read_check_marginals_async"),
+    BurstProduct("wb", "within_between", _after_reset("_wb_D", "within_between"),
+                 lambda s, D: {k: ((int(D),), np.float64) for k in WB_KEYS},
+                 "within_between", "read_wb_draws", "read_wb_draws_async"),
+    # (G, {source: day extent}): the group sums of the sources that run with the burst
+    BurstProduct("groups", "groups", lambda s, req, sizes: s._group_sources(req, sizes), _group_arrays,
+                 None, "_read_group_sums", "_read_group_sums"),
+    # (G, {key of GROUP_CURVE_KEYS: window days}): the curves that run with the burst
+    BurstProduct("group_curves", None, lambda s, req, sizes: s._group_curve_days(sizes),
+                 lambda s, size: {k: ((size[0], int(D)), np.float64) for k, D in size[1].items()},
+                 None, "_read_group_curves", "_read_group_curves"),
+)
+PRODUCTS = {p.field: p for p in BURST_PRODUCTS}
+
+
+def _allocate(spec, alloc):
+    """`alloc(trailing shape, dtype)` for the one pair or for every entry of a row's `arrays`."""
+    return alloc(*spec) if isinstance(spec, tuple) else {k: alloc(*v) for k, v in spec.items()}
 
 
 @dataclasses.dataclass
@@ -243,6 +318,7 @@ class PinnedTrace:
 
     def __init__(self, sampler: "ChainSampler", count: int, events: bool = True, marginals: bool = False,
                  forecast: int = 0, rt: int = 0, check: int = 0, wb: int = 0, groups=None, group_curves=None):
+        sizes = locals()                                    # first statement: the keywords, read by the rows' field names
         self._lib = sampler._lib
         self.count = int(count)
         B, P, M, T = sampler.B, sampler.P, sampler.M, sampler.T
@@ -251,40 +327,9 @@ class PinnedTrace:
         self.events = self._alloc((count, B, M, T, 3), sampler.events_dtype) if (events and sampler.record_events) else None
         self.hmc = self._alloc((count, B, 3), np.float64)
         self.moves = self._alloc((count, B, 4, _lib.MOVE_TRACE), np.float64)
-        self.marginals = None
-        if marginals:
-            self.marginals = dict(events_by_day=self._alloc((count, B, T, 3), np.int64),
-                                  events_by_location=self._alloc((count, B, M, 3), np.int64),
-                                  state_by_day=self._alloc((count, B, T, 3), np.int64))
-        self.forecast = None
-        if forecast:
-            H = int(forecast)
-            self.forecast = dict(forecast_by_day=self._alloc((count, B, H, 3), np.int64),
-                                 forecast_by_location=self._alloc((count, B, M, 3), np.int64),
-                                 forecast_state_by_day=self._alloc((count, B, H, 3), np.int64))
-        self.rt = self._alloc((count, B, int(rt)), np.float64) if rt else None
-        self.check = None
-        if check:
-            K = int(check)
-            self.check = dict(check_by_day=self._alloc((count, B, K, 3), np.int64),
-                              check_by_location=self._alloc((count, B, M, 3), np.int64),
-                              check_state_by_day=self._alloc((count, B, K, 3), np.int64))
-        self.wb = {k: self._alloc((count, B, int(wb)), np.float64) for k in WB_KEYS} if wb else None
-        # groups: (G, {source: day extent}) -- the group sums of the sources that run with the burst
-        self.groups = None
-        if groups:
-            G, lens = groups
-            self.groups = {}
-            for src, L in lens.items():
-                _, ev_key, st_key = GROUP_SOURCES[src]
-                self.groups[ev_key] = self._alloc((count, B, G, int(L), 3), np.int64)
-                if st_key:
-                    self.groups[st_key] = self._alloc((count, B, G, 3), np.int64)
-        # group_curves: (G, {key of GROUP_CURVE_KEYS: window days}) -- the curves that run with the burst
-        self.group_curves = None
-        if group_curves:
-            G, days = group_curves
-            self.group_curves = {k: self._alloc((count, B, G, int(D)), np.float64) for k, D in days.items()}
+        for p in BURST_PRODUCTS:                            # a row that is off leaves None
+            setattr(self, p.field, _allocate(p.arrays(sampler, sizes[p.field]), lambda sh, dt: self._alloc((count, B) + sh, dt))
+                    if sizes[p.field] else None)
 
     def _alloc(self, shape, dtype):
         nbytes = int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize
@@ -295,8 +340,8 @@ class PinnedTrace:
         return np.frombuffer(buf, dtype=dtype, count=int(np.prod(shape, dtype=np.int64))).reshape(shape)
 
     def close(self):
-        self.theta = self.events = self.hmc = self.moves = self.marginals = self.forecast = self.rt = self.check = self.wb = None
-        self.groups = self.group_curves = None
+        for field in ("theta", "events", "hmc", "moves") + tuple(PRODUCTS):
+            setattr(self, field, None)
         for p in self._ptrs:
             self._lib.seir_host_free(p)
         self._ptrs = []
@@ -583,21 +628,22 @@ class ChainSampler:
         n = int(count)
         tr = self._as_trace(n, buf.theta[:n], None if buf.events is None else buf.events[:n], buf.hmc[:n],
                             buf.moves[:n])
-        if buf.marginals is not None:
-            tr.marginals = {k: v[:n] for k, v in buf.marginals.items()}
-        if buf.forecast is not None:
-            tr.forecast = {k: v[:n] for k, v in buf.forecast.items()}
-        if buf.rt is not None:
-            tr.rt = buf.rt[:n]
-        if getattr(buf, "check", None) is not None:
-            tr.check = {k: v[:n] for k, v in buf.check.items()}
-        if getattr(buf, "wb", None) is not None:
-            tr.wb = {k: v[:n] for k, v in buf.wb.items()}
-        if getattr(buf, "groups", None) is not None:
-            tr.groups = {k: v[:n] for k, v in buf.groups.items()}
-        if getattr(buf, "group_curves", None) is not None:
-            tr.group_curves = {k: v[:n] for k, v in buf.group_curves.items()}
+        for field in PRODUCTS:                              # a stand-in buffer may lack the newer fields
+            v = getattr(buf, field, None)
+            if v is not None:
+                setattr(tr, field, {k: a[:n] for k, a in v.items()} if isinstance(v, dict) else v[:n])
         return tr
+
+    def _fresh(self, field, size, count):
+        """Unpinned arrays for `count` draws of the product `field`, shaped by its row of `BURST_PRODUCTS`."""
+        return _allocate(PRODUCTS[field].arrays(self, size), lambda sh, dt: np.empty((int(count), self.B) + sh, dt))
+
+    def _pinned_arrays(self, into, field, count, what):
+        """The arrays of `field` in the pinned buffer `into`, which must hold `count` draws of them."""
+        arrays = getattr(into, field, None)
+        if int(count) > into.count or arrays is None:
+            raise ValueError(f"pinned buffer too small or without {what}")
+        return arrays
 
     # -- summaries of the recorded events on the device (include/seir_hip.h) --------------------------
     def reset_summary(self):
@@ -611,15 +657,15 @@ class ChainSampler:
         written, and with `accumulate` the draws are folded into the moments."""
         _lib.check(self._lib.seir_sampler_summarize(self._s, int(first), int(count), int(bool(accumulate))))
 
-    def _read_marginal_set(self, fn, keys, days, count, first, into=None):
-        """The three per-draw marginals `keys` (by day, by location, state by day; `days` = T or H) of trace slots
-        [first, first+count) through the reader `fn`: into fresh arrays (blocking `fn`), or into the pinned arrays `into`
-        (asynchronous `fn`, completed by `trace_wait()`)."""
-        n = int(count)
-        if into is None:
-            into = {k: np.empty((n, self.B, e, 3), np.int64) for k, e in zip(keys, (days, self.M, days))}
-        _lib.check(fn(self._s, int(first), n, *(into[k].ctypes.data_as(_lib.c_int64_p) for k in keys)))
-        return into
+    def _read_product(self, fn, field, size, count, first, into=None, what=None):
+        """The arrays of the product `field` (the three per-draw marginals by day, by location, state by day; the national
+        curves) of trace slots [first, first+count) through its C reader `fn`, in the order of its row: into fresh arrays
+        (blocking `fn`), or into those of the PinnedTrace `into` (asynchronous `fn`, completed by `trace_wait()`)."""
+        out = self._fresh(field, size, count) if into is None else self._pinned_arrays(into, field, count, what)
+        arrays = [out[k] for k in PRODUCTS[field].arrays(self, size)] if isinstance(out, dict) else [out]
+        _lib.check(fn(self._s, int(first), int(count),
+                      *(a.ctypes.data_as(_lib.c_int64_p) if a.dtype == np.int64 else _dptr(a) for a in arrays)))
+        return out
 
     def _read_moments(self, fn, days) -> Summary:
         """(count, ref, sum, sumsq) over [B,M,days,6] through the blocking reader `fn`."""
@@ -633,13 +679,11 @@ class ChainSampler:
     def read_marginals(self, count: int, first: int = 0) -> dict:
         """Blocking read of the marginals of trace slots [first, first+count): MARGINAL_KEYS -> int64 arrays with
         leading axes [count, B]."""
-        return self._read_marginal_set(self._lib.seir_sampler_read_marginals, MARGINAL_KEYS, self.T, count, first)
+        return self._read_product(self._lib.seir_sampler_read_marginals, "marginals", True, count, first)
 
     def read_marginals_async(self, count: int, first: int, into: PinnedTrace):
         """As `read_trace_async`, for the marginals; completed by `trace_wait()`."""
-        if int(count) > into.count or into.marginals is None:
-            raise ValueError("pinned buffer too small or without marginals")
-        self._read_marginal_set(self._lib.seir_sampler_read_marginals_async, MARGINAL_KEYS, self.T, count, first, into.marginals)
+        self._read_product(self._lib.seir_sampler_read_marginals_async, "marginals", True, count, first, into, "marginals")
 
     def summary(self) -> Summary:
         """The moments folded since the last `reset_summary` (blocking).  Raises `SeirError` (SEIR_ERR_STATE) if an
@@ -709,14 +753,12 @@ class ChainSampler:
     def read_forecast_marginals(self, count: int, first: int = 0) -> dict:
         """Blocking read of the forecast marginals of trace slots [first, first+count): FORECAST_KEYS -> int64 arrays with
         leading axes [count, B]."""
-        return self._read_marginal_set(self._lib.seir_sampler_read_forecast_marginals, FORECAST_KEYS, self._forecast_H, count, first)
+        return self._read_product(self._lib.seir_sampler_read_forecast_marginals, "forecast", self._forecast_H, count, first)
 
     def read_forecast_marginals_async(self, count: int, first: int, into: PinnedTrace):
         """As `read_marginals_async`, for the forecast marginals; completed by `trace_wait()`."""
-        if int(count) > into.count or into.forecast is None:
-            raise ValueError("pinned buffer too small or without forecast arrays")
-        self._read_marginal_set(self._lib.seir_sampler_read_forecast_marginals_async, FORECAST_KEYS, self._forecast_H, count,
-                                first, into.forecast)
+        self._read_product(self._lib.seir_sampler_read_forecast_marginals_async, "forecast", self._forecast_H, count, first, into,
+                           "forecast arrays")
 
     def forecast_summary(self) -> Summary:
         """The forecast moments folded since the last `reset_forecast` (blocking): a `Summary` whose day axis is the H
@@ -753,13 +795,6 @@ class ChainSampler:
         ranks = Q.quantile_ranks(n, probs)
         return Q.interpolate(self.forecast_order_stats(ranks, pooled=pooled), ranks, n, probs)
 
-    def _forecast_burst(self, first, count, forecast):
-        """`forecast` of sample / sample_bursts: True (held baseline) or a callable (j0, count) -> steps [count,B,H], j0
-        being the number of draws per chain forecast since the reset -- after a re-run of a burst it is the same again."""
-        if not self._forecast_H:
-            raise ValueError("forecast asked for before reset_forecast")
-        self.forecast(first, count, forecast(self._fc_j, count) if callable(forecast) else None)
-
     # -- reproduction number of the kept draws (include/seir_hip.h, "Reproduction number on the device") ----------
     def reset_rt(self, days: int, weight):
         """Enable the reproduction number (first call), zero its accumulators and count, set the window to the last `days`
@@ -785,15 +820,11 @@ class ChainSampler:
 
     def read_rt_draws(self, count: int, first: int = 0) -> np.ndarray:
         """Blocking read of R_t [count,B,D] of trace slots [first, first+count)."""
-        out = np.empty((int(count), self.B, self._rt_D))
-        _lib.check(self._lib.seir_sampler_read_rt_draws(self._s, int(first), int(count), _dptr(out)))
-        return out
+        return self._read_product(self._lib.seir_sampler_read_rt_draws, "rt", self._rt_D, count, first)
 
     def read_rt_draws_async(self, count: int, first: int, into: PinnedTrace):
         """As `read_marginals_async`, for the national curves; completed by `trace_wait()`."""
-        if int(count) > into.count or into.rt is None:
-            raise ValueError("pinned buffer too small or without R_t")
-        _lib.check(self._lib.seir_sampler_read_rt_draws_async(self._s, int(first), int(count), _dptr(into.rt)))
+        self._read_product(self._lib.seir_sampler_read_rt_draws_async, "rt", self._rt_D, count, first, into, "R_t")
 
     def rt_summary(self) -> RtSummary:
         """The R_it accumulators folded since the last `reset_rt` (blocking): `RtSummary`, whose `.mean`, `.var` and
@@ -836,11 +867,6 @@ class ChainSampler:
         ranks = Q.quantile_ranks(n, probs)
         return Q.interpolate(self.rt_order_stats(ranks, pooled=pooled), ranks, n, probs)
 
-    def _rt_burst(self, first, count):
-        if not self._rt_D:
-            raise ValueError("rt asked for before reset_rt")
-        self.rt(first, count)
-
     # -- in-sample check of the last K days (include/seir_hip.h, "In-sample predictive check on the device") ----------
     def reset_check(self, days: int, W, weekday_c, seed: int = 0):
         """Enable the check (first call), zero its moments, comparison counts, observed counts and flags, set the window
@@ -864,14 +890,12 @@ class ChainSampler:
     def read_check_marginals(self, count: int, first: int = 0) -> dict:
         """Blocking read of the check's marginals of trace slots [first, first+count): CHECK_KEYS -> int64 arrays with
         leading axes [count, B]."""
-        return self._read_marginal_set(self._lib.seir_sampler_read_check_marginals, CHECK_KEYS, self._check_K, count, first)
+        return self._read_product(self._lib.seir_sampler_read_check_marginals, "check", self._check_K, count, first)
 
     def read_check_marginals_async(self, count: int, first: int, into: PinnedTrace):
         """As `read_marginals_async`, for the check's marginals; completed by `trace_wait()`."""
-        if int(count) > into.count or into.check is None:
-            raise ValueError("pinned buffer too small or without check arrays")
-        self._read_marginal_set(self._lib.seir_sampler_read_check_marginals_async, CHECK_KEYS, self._check_K, count, first,
-                                into.check)
+        self._read_product(self._lib.seir_sampler_read_check_marginals_async, "check", self._check_K, count, first, into,
+                           "check arrays")
 
     def check_summary(self) -> CheckSummary:
         """Moments and comparison counts folded since the last `reset_check` (blocking).  Raises `SeirError`
@@ -885,11 +909,6 @@ class ChainSampler:
                                                             *(a.ctypes.data_as(u32) for a in arrs)))
         mom = self._read_moments(self._lib.seir_sampler_read_check, K)
         return CheckSummary(mom, obs, *arrs)
-
-    def _check_burst(self, first, count):
-        if not self._check_K:
-            raise ValueError("check asked for before reset_check")
-        self.check(first, count)
 
     # -- within/between pressure shares (include/seir_hip.h, "Within/between pressure shares on the device") ----------
     def reset_within_between(self, days: int):
@@ -913,16 +932,11 @@ class ChainSampler:
 
     def read_wb_draws(self, count: int, first: int = 0) -> dict:
         """Blocking read of the national pressures of trace slots [first, first+count): WB_KEYS -> [count,B,D]."""
-        out = {k: np.empty((int(count), self.B, self._wb_D)) for k in WB_KEYS}
-        _lib.check(self._lib.seir_sampler_read_wb_draws(self._s, int(first), int(count), *(_dptr(out[k]) for k in WB_KEYS)))
-        return out
+        return self._read_product(self._lib.seir_sampler_read_wb_draws, "wb", self._wb_D, count, first)
 
     def read_wb_draws_async(self, count: int, first: int, into: PinnedTrace):
         """As `read_marginals_async`, for the national pressures; completed by `trace_wait()`."""
-        if int(count) > into.count or getattr(into, "wb", None) is None:
-            raise ValueError("pinned buffer too small or without within/between arrays")
-        _lib.check(self._lib.seir_sampler_read_wb_draws_async(self._s, int(first), int(count),
-                                                              *(_dptr(into.wb[k]) for k in WB_KEYS)))
+        self._read_product(self._lib.seir_sampler_read_wb_draws_async, "wb", self._wb_D, count, first, into, "within/between arrays")
 
     def within_between_summary(self) -> WbSummary:
         """The accumulators folded since the last `reset_within_between` (blocking): `WbSummary`, whose `.within_mean`,
@@ -937,11 +951,6 @@ class ChainSampler:
                                                   n.ctypes.data_as(u32), _dptr(ref_w), _dptr(sum_w), _dptr(sumsq_w),
                                                   _dptr(ref_b), _dptr(sum_b), gt.ctypes.data_as(u32)))
         return WbSummary(count=cnt, defined=n, ref_w=ref_w, sum_w=sum_w, sumsq_w=sumsq_w, ref_b=ref_b, sum_b=sum_b, gt=gt)
-
-    def _wb_burst(self, first, count):
-        if not self._wb_D:
-            raise ValueError("within_between asked for before reset_within_between")
-        self.within_between(first, count)
 
     # -- region totals: per-draw sums over groups of locations (include/seir_hip.h, "Region totals on the device") ------
     def set_groups(self, offsets, members):
@@ -1007,31 +1016,33 @@ class ChainSampler:
             raise
         self._group_wb_on, self._group_wb_refused = bool(on), False
 
-    def _group_curve_days(self, do_rt, do_wb):
-        """{key of GROUP_CURVE_KEYS: window days} of the curves that leave outputs with a burst that runs rt / within_between."""
+    def _group_curve_days(self, sizes):
+        """(G, {key of GROUP_CURVE_KEYS: window days}) of the curves that leave outputs with a burst that runs the rt /
+        within_between of `sizes` ({field: size} of the burst's products); () when there is none."""
         days = {}
-        if do_rt and self._group_rt_on and self._groups_G and not self._group_rt_refused:
+        if sizes["rt"] and self._group_rt_on and self._groups_G and not self._group_rt_refused:
             days["rt_by_group"] = self._rt_D
-        if do_wb and self._group_wb_on and self._groups_G and not self._group_wb_refused:
+        if sizes["wb"] and self._group_wb_on and self._groups_G and not self._group_wb_refused:
             days["within_by_group"] = days["between_by_group"] = self._wb_D
-        return days
+        return (self._groups_G, days) if days else ()
 
     def read_group_rt(self, count: int, first: int = 0) -> np.ndarray:
         """Blocking read of the group R_t of trace slots [first, first+count): float64 [count,B,G,D]."""
-        out = np.empty((int(count), self.B, self._groups_G, self._rt_D))
+        out = self._fresh("group_curves", (self._groups_G, {"rt_by_group": self._rt_D}), count)["rt_by_group"]
         _lib.check(self._lib.seir_sampler_read_group_rt(self._s, int(first), int(count), _dptr(out)))
         return out
 
     def read_group_wb(self, count: int, first: int = 0) -> dict:
         """Blocking read of the group pressures of trace slots [first, first+count): within_by_group, between_by_group
         -> float64 [count,B,G,D]."""
-        out = {k: np.empty((int(count), self.B, self._groups_G, self._wb_D)) for k in GROUP_CURVE_KEYS[1:]}
+        out = self._fresh("group_curves", (self._groups_G, dict.fromkeys(GROUP_CURVE_KEYS[1:], self._wb_D)), count)
         _lib.check(self._lib.seir_sampler_read_group_wb(self._s, int(first), int(count), *(_dptr(out[k]) for k in GROUP_CURVE_KEYS[1:])))
         return out
 
-    def _read_group_curves(self, days, count, first=0, into=None):
-        """The curves of `_group_curve_days` of slots [first, first+count): blocking into new arrays, or on the copy stream
-        `into` the arrays of a PinnedTrace (completed by `trace_wait()`)."""
+    def _read_group_curves(self, size, count, first=0, into=None):
+        """The curves of `size` (`_group_curve_days`) of slots [first, first+count): blocking into new arrays, or on the copy
+        stream `into` the arrays of a PinnedTrace (completed by `trace_wait()`)."""
+        days = size[1]
         if into is None:
             out = {}
             if "rt_by_group" in days:
@@ -1039,9 +1050,9 @@ class ChainSampler:
             if "within_by_group" in days:
                 out.update(self.read_group_wb(count, first))
             return out
-        if int(count) > into.count or getattr(into, "group_curves", None) is None or any(k not in into.group_curves for k in days):
+        g = self._pinned_arrays(into, "group_curves", count, "group curves")
+        if any(k not in g for k in days):
             raise ValueError("pinned buffer too small or without group curves")
-        g = into.group_curves
         if "rt_by_group" in days:
             _lib.check(self._lib.seir_sampler_read_group_rt_async(self._s, int(first), int(count), _dptr(g["rt_by_group"])))
         if "within_by_group" in days:
@@ -1054,12 +1065,9 @@ class ChainSampler:
 
     def _read_groups(self, fn, source, count, first, into=None):
         which, ev_key, st_key = GROUP_SOURCES[source]
-        n, G = int(count), self._groups_G
         if into is None:
-            into = {ev_key: np.empty((n, self.B, G, self._group_len(source), 3), np.int64)}
-            if st_key:
-                into[st_key] = np.empty((n, self.B, G, 3), np.int64)
-        _lib.check(fn(self._s, which, int(first), n, into[ev_key].ctypes.data_as(_lib.c_int64_p),
+            into = self._fresh("groups", (self._groups_G, {source: self._group_len(source)}), count)
+        _lib.check(fn(self._s, which, int(first), int(count), into[ev_key].ctypes.data_as(_lib.c_int64_p),
                       into[st_key].ctypes.data_as(_lib.c_int64_p) if st_key else None))
         return into
 
@@ -1071,18 +1079,28 @@ class ChainSampler:
 
     def read_group_marginals_async(self, source: str, count: int, first: int, into: PinnedTrace):
         """As `read_marginals_async`, for the group sums of `source`; completed by `trace_wait()`."""
-        if int(count) > into.count or getattr(into, "groups", None) is None or GROUP_SOURCES[source][1] not in into.groups:
+        g = self._pinned_arrays(into, "groups", count, "group arrays")
+        if GROUP_SOURCES[source][1] not in g:
             raise ValueError("pinned buffer too small or without group arrays")
-        self._read_groups(self._lib.seir_sampler_read_group_marginals_async, source, count, first, into.groups)
+        self._read_groups(self._lib.seir_sampler_read_group_marginals_async, source, count, first, g)
 
-    def _group_sources(self, groups, do_sum, do_fc, do_ck):
-        """`groups` of sample / sample_bursts: the sources whose group sums cross with the trace -- True: every one of
-        "trace", "forecast", "check" that runs with the burst; or a tuple of those names, each of which must run."""
+    def _read_group_sums(self, size, count, first=0, into=None):
+        """The group sums of every source of `size` (`_group_sources`) of slots [first, first+count): blocking into one new
+        dict, or on the copy stream into the arrays of the PinnedTrace `into` (completed by `trace_wait()`)."""
+        if into is None:
+            return {k: v for src in size[1] for k, v in self.read_group_marginals(src, count, first).items()}
+        for src in size[1]:
+            self.read_group_marginals_async(src, count, first, into)
+
+    def _group_sources(self, groups, sizes):
+        """`groups` of sample / sample_bursts: (G, {source: day extent}) of the sources whose group sums cross with the trace
+        -- True: every one of "trace", "forecast", "check" that runs with the burst (`sizes`: {field: size} of the burst's
+        products); or a tuple of those names, each of which must run.  () when `groups` is off."""
         if not groups:
             return ()
         if not self._groups_G:
             raise ValueError("groups asked for before set_groups")
-        on = dict(trace=do_sum, forecast=do_fc, check=do_ck)
+        on = dict(trace=self._group_len("trace") if sizes["marginals"] else 0, forecast=sizes["forecast"], check=sizes["check"])
         if groups is True:
             src = tuple(k for k in GROUP_SOURCES if on[k])
         else:
@@ -1092,7 +1110,7 @@ class ChainSampler:
                 raise ValueError(f"groups={groups!r}: {bad[0]!r} is not one of summarize, forecast, check run with this burst")
         if not src:
             raise ValueError("groups needs one of summarize, forecast, check")
-        return src
+        return self._groups_G, {k: on[k] for k in src}
 
     def _summarize_mode(self, summarize):
         """`summarize` of sample / sample_bursts: False, True (marginals + moments) or "marginals" (accumulate = 0)."""
@@ -1100,7 +1118,26 @@ class ChainSampler:
             raise ValueError(f"summarize={summarize!r}: False, True or 'marginals'")
         if summarize and not self._summary_on:
             self.reset_summary()
-        return bool(summarize), summarize is True
+        return bool(summarize)
+
+    def _burst_products(self, keywords):
+        """{field: (row, size, request)} of the rows of `BURST_PRODUCTS` that the requests -- those of `keywords`, the locals
+        of sample / sample_bursts, that a row names -- and the sampler's switches turn on, in table order.  Refuses what is
+        asked for too early."""
+        requests = {p.request: keywords[p.request] for p in BURST_PRODUCTS if p.request}
+        sizes = {}
+        for p in BURST_PRODUCTS:
+            sizes[p.field] = p.size(self, requests.get(p.request), sizes)
+        return {p.field: (p, sizes[p.field], requests.get(p.request)) for p in BURST_PRODUCTS if sizes[p.field]}
+
+    def _enqueue_products(self, on, first, count, mark=None):
+        """Enqueue the products `on` for trace slots [first, first+count) behind the sweeps that fill them, in table order;
+        `mark` (0 | 1): the diagnostics' mark, right behind the summary's place."""
+        for p in BURST_PRODUCTS:
+            if p.enqueue and p.field in on:
+                getattr(self, p.enqueue)(first, count, *p.args(self, on[p.field][2], count))
+            if p.marks_behind and mark is not None:
+                self.mark(mark)
 
     def sample_bursts(self, num_bursts: int, burst: int, consume, events: bool = True, summarize=False, marks=None,
                       forecast=False, rt=False, check=False, within_between=False, groups=False):
@@ -1120,9 +1157,9 @@ class ChainSampler:
         burst, so the mark holds the accumulators over bursts 0 .. index.  A burst that is run again is marked again: the
         restored snapshot holds the marks as they were before it.
 
-        `forecast` (True, or a callable giving random-walk steps, see `_forecast_burst`; needs `reset_forecast`): every
-        burst's draws are forecast on the device right behind its summary and the forecast marginals cross with the trace
-        (`trace.forecast`).
+        `forecast` (True, or a callable giving random-walk steps, see the forecast's row of `BURST_PRODUCTS`; needs
+        `reset_forecast`): every burst's draws are forecast on the device right behind its summary and the forecast
+        marginals cross with the trace (`trace.forecast`).
 
         `rt` (needs `reset_rt`): R_it of every burst's draws is formed and folded on the device right behind its summary
         and forecast, and the national curves cross with the trace (`trace.rt`).
@@ -1141,40 +1178,19 @@ class ChainSampler:
 
         The group curves have no keyword: while `set_group_rt` / `set_group_within_between` is on, the curves that `rt` /
         `within_between` leave per group cross with the trace (`trace.group_curves`)."""
+        on = self._burst_products(locals())                 # first statement: the locals are this call's keywords
         from concurrent.futures import ThreadPoolExecutor
-        do_sum, accumulate = self._summarize_mode(summarize)
         burst, num_bursts = int(burst), int(num_bursts)
         if 2 * burst > self.cap:
             raise ValueError(f"sample_bursts needs trace_capacity >= 2 * burst = {2 * burst}, have {self.cap}")
-        # page-locking GBs of host memory takes tenths of a second: the two buffers are kept for the next call
-        do_fc = bool(forecast)
-        do_rt = bool(rt)
-        do_ck = bool(check)
-        do_wb = bool(within_between)
-        grp_src = self._group_sources(groups, do_sum, do_fc, do_ck)
-        grp_lens = {k: self._group_len(k) for k in grp_src}
-        gc_days = self._group_curve_days(do_rt, do_wb)
-        key = (burst, bool(events), do_sum, self._forecast_H if do_fc else 0) + ((self._rt_D,) if do_rt else ()) + \
-            ((("check", self._check_K),) if do_ck else ()) + ((("wb", self._wb_D),) if do_wb else ()) + \
-            ((("groups", self._groups_G, tuple(grp_lens.items())),) if grp_src else ()) + \
-            ((("group_curves", self._groups_G, tuple(gc_days.items())),) if gc_days else ())
+        # page-locking GBs of host memory takes tenths of a second: the two buffers are kept for the next call, until the
+        # burst, `events` or the size of a product changes
+        sizes = {field: size for field, (_, size, _) in on.items()}
+        key = (burst, bool(events)) + tuple(sizes.items())
         if getattr(self, "_pinned_key", None) != key:
             for bf in getattr(self, "_pinned", []):
                 bf.close()
-            mk = dict(marginals=True) if do_sum else {}
-            if do_fc:
-                mk["forecast"] = self._forecast_H
-            if do_rt:
-                mk["rt"] = self._rt_D
-            if do_ck:
-                mk["check"] = self._check_K
-            if do_wb:
-                mk["wb"] = self._wb_D
-            if grp_src:
-                mk["groups"] = (self._groups_G, grp_lens)
-            if gc_days:
-                mk["group_curves"] = (self._groups_G, gc_days)
-            self._pinned = [PinnedTrace(self, burst, events, **mk), PinnedTrace(self, burst, events, **mk)]
+            self._pinned = [PinnedTrace(self, burst, events, **sizes), PinnedTrace(self, burst, events, **sizes)]
             self._pinned_key = key
         bufs = self._pinned
         futs = [None, None]
@@ -1196,18 +1212,7 @@ class ChainSampler:
                                 self.snapshot(h)                 # stream order: the state burst i starts from
                             self.reset_trace(at=h * burst)
                             self.run(burst * self._thin)         # asynchronous; a re-run after _recover passes here again
-                            if do_sum:
-                                self.summarize(h * burst, burst, accumulate)
-                            if marks and i in marks:
-                                self.mark(marks[i])
-                            if do_fc:
-                                self._forecast_burst(h * burst, burst, forecast)
-                            if do_rt:
-                                self._rt_burst(h * burst, burst)
-                            if do_ck:
-                                self._check_burst(h * burst, burst)
-                            if do_wb:
-                                self._wb_burst(h * burst, burst)
+                            self._enqueue_products(on, h * burst, burst, marks[i] if marks and i in marks else None)
                         if prev >= 0:
                             self.trace_wait()                    # burst prev has landed (it crossed while burst i ran)
                             futs[prev & 1] = pool.submit(consume, self.trace_view(bufs[prev & 1], burst), prev)
@@ -1215,20 +1220,8 @@ class ChainSampler:
                             self._burst_ok()
                         if i < num_bursts:
                             self.read_trace_async(burst, h * burst, bufs[h])
-                            if do_sum:
-                                self.read_marginals_async(burst, h * burst, bufs[h])
-                            if do_fc:
-                                self.read_forecast_marginals_async(burst, h * burst, bufs[h])
-                            if do_rt:
-                                self.read_rt_draws_async(burst, h * burst, bufs[h])
-                            if do_ck:
-                                self.read_check_marginals_async(burst, h * burst, bufs[h])
-                            if do_wb:
-                                self.read_wb_draws_async(burst, h * burst, bufs[h])
-                            for src in grp_src:
-                                self.read_group_marginals_async(src, burst, h * burst, bufs[h])
-                            if gc_days:
-                                self._read_group_curves(gc_days, burst, h * burst, bufs[h])
+                            for p, size, _ in on.values():
+                                getattr(self, p.read_async)(*(() if p.enqueue else (size,)), burst, h * burst, bufs[h])
                             prev = i
                             i += 1
                     except _lib.HandoffTimeout as e:
@@ -1256,9 +1249,7 @@ class ChainSampler:
         filled; `forecast` likewise (`trace.forecast`), `rt` (`trace.rt`), `check` (`trace.check`), `within_between` (`trace.wb`)
         and `groups` (`trace.groups`); the group curves that are on (`set_group_rt`, `set_group_within_between`) ride on
         `rt` / `within_between` (`trace.group_curves`)."""
-        do_sum, accumulate = self._summarize_mode(summarize)
-        grp_src = self._group_sources(groups, do_sum, bool(forecast), bool(check))
-        gc_days = self._group_curve_days(bool(rt), bool(within_between))
+        on = self._burst_products(locals())                 # first statement: the locals are this call's keywords
         if num_sweeps > self.cap:
             raise ValueError(f"num_sweeps={num_sweeps} exceeds trace_capacity={self.cap}")
         while True:
@@ -1267,33 +1258,10 @@ class ChainSampler:
             self.reset_trace()
             self.run(num_sweeps * self._thin)
             try:
-                if do_sum:
-                    self.summarize(0, num_sweeps, accumulate)
-                if forecast:
-                    self._forecast_burst(0, num_sweeps, forecast)
-                if rt:
-                    self._rt_burst(0, num_sweeps)
-                if check:
-                    self._check_burst(0, num_sweeps)
-                if within_between:
-                    self._wb_burst(0, num_sweeps)
+                self._enqueue_products(on, 0, num_sweeps)
                 tr = self.read_trace(num_sweeps, events=events)
-                if do_sum:
-                    tr.marginals = self.read_marginals(num_sweeps)
-                if forecast:
-                    tr.forecast = self.read_forecast_marginals(num_sweeps)
-                if rt:
-                    tr.rt = self.read_rt_draws(num_sweeps)
-                if check:
-                    tr.check = self.read_check_marginals(num_sweeps)
-                if within_between:
-                    tr.wb = self.read_wb_draws(num_sweeps)
-                if grp_src:
-                    tr.groups = {}
-                    for src in grp_src:
-                        tr.groups.update(self.read_group_marginals(src, num_sweeps))
-                if gc_days:
-                    tr.group_curves = self._read_group_curves(gc_days, num_sweeps)
+                for p, size, _ in on.values():
+                    setattr(tr, p.field, getattr(self, p.read)(*(() if p.enqueue else (size,)), num_sweeps))
             except _lib.HandoffTimeout as e:
                 if not self.auto_recover:
                     raise
