@@ -257,6 +257,12 @@ _SIGNATURES = {
     "seir_group_wsums": (ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                         ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
                                         c_double_p, c_double_p]),
+    # group next-generation matrix of every kept draw (rides on seir_sampler_rt); the rows kernel alone on host arrays
+    "seir_sampler_group_ngm": (ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.c_int64]),
+    "seir_sampler_read_group_ngm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_double_p]),
+    "seir_group_ngm_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_double_p, ctypes.POINTER(ctypes.c_int32),
+                                           ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                           ctypes.POINTER(ctypes.c_int32), c_double_p]),
 }
 
 _lib = None

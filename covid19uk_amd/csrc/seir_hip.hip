@@ -1203,6 +1203,17 @@ struct GroupCurve {
     double *cells[2] = {nullptr, nullptr}, *out[2] = {nullptr, nullptr};
 };
 
+// The group next-generation matrix of the kept draws (seir_sampler_group_ngm; ngm_kernels.h): the draw store
+// out [cap][B][G][G][D], indexed by draw position since the rt reset, and the rows plane P [slots * B][G][D][Mp] of a batch.
+// cap = 0: off, nothing is allocated and nothing is launched.
+struct GroupNgm {
+    long long cap = 0;                // draws per chain the store holds
+    int D = 0, slots = 0;             // window days the buffers are sized for; trace slots per batch
+    int *offsets = nullptr;           // device copy of the table's offsets [G + 1]
+    double *weights = nullptr;        // [nnz] aligned with the members
+    double *P = nullptr, *out = nullptr;
+};
+
 // The host's half of a ForecastBufs that is rolled forward day by day from the kept draws (forecast_kernels.h): the forecast
 // and the in-sample check each own one (rollout_*, below).
 struct Rollout {
@@ -1317,6 +1328,8 @@ struct seir_sampler {
     // --- group curves: R_t and within / between per group (seir_sampler_group_rt / _group_wb; group_curve_kernels.h) ---
     std::vector<int> grp_offsets;     // the table's offsets [G + 1] on the host (the device copy exists only with a curve on)
     GroupCurve grt, gwb;              // group R_t (one plane, weighted); group within / between (two planes)
+    // --- group next-generation matrix (seir_sampler_group_ngm; ngm_kernels.h) ---
+    GroupNgm ngm;
 };
 
 // Zeroed device memory, registered in `list` (seir_sampler::allocs: freed with the sampler; Rollout::allocs: also when the length
@@ -1367,8 +1380,16 @@ static void gcurve_rt_off(seir_sampler *s) {
     s->grt.on = false;
 }
 static int gcurve_fit(seir_sampler *s, bool rt);     // with the rest of the group curves, behind the within/between shares
+// Switches the group next-generation matrix off and frees its store: its weights belonged to the table, its sizes to D.
+static void ngm_off(seir_sampler *s) {
+    GroupNgm &n = s->ngm;
+    for (void *p : {(void *)n.offsets, (void *)n.weights, (void *)n.P, (void *)n.out})
+        if (p) (void)hipFree(p);
+    n = GroupNgm{};
+}
 
 static void groups_free(seir_sampler *s) {
+    ngm_off(s);
     gcurve_rt_off(s);
     gcurve_release(s->gwb);
     s->grp_offsets.clear();
@@ -3309,6 +3330,9 @@ static void gcurve_rt_gather(seir_sampler *s, const LaunchCfg &l, long long pos0
 static void gcurve_wb_trace_cells(seir_sampler *s, const LaunchCfg &l, int slot0, int nj);
 static void gcurve_sums(seir_sampler *s, const LaunchCfg &l, const GroupCurve &c, int D, int slot0, int nj);
 static void gcurve_lds_attributes(int Mp);
+// The launches of the group next-generation matrix (likewise at the end of this file, where ngm_kernels.h is included): the
+// batch's slots [slot0, slot0 + nj) into the store's positions [pos0, pos0 + nj).
+static void ngm_launch(seir_sampler *s, const LaunchCfg &l, int slot0, long long pos0, int nj);
 
 // need_events' refusal as SEIR_ERR_INVALID (a sampler without recorded events is a bad argument to this feature), then
 // trace_range_check's
@@ -3336,6 +3360,7 @@ extern "C" int seir_sampler_rt_reset(seir_sampler *s, int32_t days, const double
         s->rt_allocs.clear();
         acc_free(s->rt_acc);
         if (s->rt_keep) { (void)hipFree(s->rt_keep); s->rt_keep = nullptr; s->rt_keep_cap = s->rt_keep_stride = 0; }   // sized by D
+        ngm_off(s);                                  // sized by D too
         s->rt_on = false;
         rb = RtBufs{};
         rb.D = D; rb.t0 = d.T - D; rb.ncb = (d.M + 63) / 64;
@@ -3366,6 +3391,8 @@ extern "C" int seir_sampler_rt_reset(seir_sampler *s, int32_t days, const double
     HIP_TRY(hipMemcpyAsync(const_cast<double *>(rb.weight), weight, sizeof(double) * d.M, hipMemcpyHostToDevice, st));
     if ((rc = acc_zero(s->rt_acc, st))) return rc;
     if (s->rt_keep) HIP_TRY(hipMemsetAsync(s->rt_keep, 0, sizeof(double) * rt_cells(s) * (size_t)s->rt_keep_stride, st));
+    if (s->ngm.cap)                                  // the group next-generation matrix holds draws [0, count) too
+        HIP_TRY(hipMemsetAsync(s->ngm.out, 0, sizeof(double) * (size_t)s->ngm.cap * B * s->grp.G * s->grp.G * D, st));
     HIP_TRY(hipStreamSynchronize(st));
     s->rt_j = 0;                                     // empties the draw store too: it holds draws [0, count)
     // what the snapshots taken before this reset hold of it is dropped: restoring one of them leaves the accumulators alone
@@ -3381,6 +3408,9 @@ extern "C" int seir_sampler_rt(seir_sampler *s, int32_t first, int32_t count) {
     if (s->rt_keep && s->rt_j + count > s->rt_keep_cap)
         return fail(SEIR_ERR_INVALID, "%lld draws per chain folded since the reset and %d more: the draw store holds %lld "
                     "(seir_sampler_rt_keep)", s->rt_j, count, s->rt_keep_cap);
+    if (s->ngm.cap && s->rt_j + count > s->ngm.cap)
+        return fail(SEIR_ERR_INVALID, "%lld draws per chain folded since the reset and %d more: the draw store holds %lld "
+                    "(seir_sampler_group_ngm)", s->rt_j, count, s->ngm.cap);
     seir_ctx *ctx = s->ctx;
     const LaunchCfg l = whole(ctx, s->cfg.B);
     const Dims &d = l.d;
@@ -3390,7 +3420,7 @@ extern "C" int seir_sampler_rt(seir_sampler *s, int32_t first, int32_t count) {
     tw.ea = rb.ea;
     const size_t lds = k_rt_trace_lds_bytes<RT_DT>(d.Mp);
     const bool curves = s->grt.D != 0;                // group R_t: the batch also fits the cell plane
-    const int slots = curves ? s->grt.slots : s->rt_slots;
+    const int slots = std::min(curves ? s->grt.slots : s->rt_slots, s->ngm.cap ? s->ngm.slots : s->rt_slots);
     for (int j0 = 0; j0 < count; j0 += slots) {
         const int nj = std::min(slots, count - j0), ND = nj * B;
         hipLaunchKernelGGL(k_rt_tables, dim3(ND), dim3(256), 0, l.st, d, tw,
@@ -3400,6 +3430,7 @@ extern "C" int seir_sampler_rt(seir_sampler *s, int32_t first, int32_t count) {
             hipLaunchKernelGGL(k_rt_prepare<1>, pgrid, pblock, 0, l.st, d, ctx->c, rb, (const void *)s->ch.tr_events, B, first + j0);
         else
             hipLaunchKernelGGL(k_rt_prepare<0>, pgrid, pblock, 0, l.st, d, ctx->c, rb, (const void *)s->ch.tr_events, B, first + j0);
+        if (s->ngm.cap) ngm_launch(s, l, first + j0, s->rt_j + j0, nj);      // behind k_rt_prepare: ea and S of the batch lie there
         if (s->rt_keep)                               // in place of k_rt_trace: R_it is formed once
             hipLaunchKernelGGL(k_rt_trace_keep<RT_DT>, dim3(rb.ncb, (D + RT_DT - 1) / RT_DT, B), dim3(256), lds, l.st, d, ctx->c, rb,
                                (const double *)s->ch.tr_theta, B, first + j0, nj, s->rt_keep, s->rt_keep_stride);
@@ -3970,4 +4001,159 @@ static void gcurve_lds_attributes(int Mp) {
         (void)hipFuncSetAttribute((const void *)k_rt_trace_cells<RT_DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rl);
     if (wl > 64 * 1024)
         (void)hipFuncSetAttribute((const void *)k_wb_trace_cells<WB_DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl);
+}
+
+// ===========================================================================
+// Group next-generation matrix on the device (include/seir_hip.h; kernel: ngm_kernels.h).  The header is included here,
+// behind the group curves' launches, so that its kernel lies behind every kernel the parent had.
+// ===========================================================================
+#include "ngm_kernels.h"
+
+// nd draws of the planes rb.ea / rb.S (theta: trace slot first + nd / B, chain nd % B) into P [nd][G][D][ld].
+static void ngm_rows_launch(const Dims &d, const Consts &c, hipStream_t st, const RtBufs &rb, const double *theta, int B, int first,
+                            long long nd, const int *offsets, const int *members, int G, double *P, long long ld) {
+    const size_t lds = k_rt_trace_lds_bytes<RT_DT>(d.Mp);
+    for (long long off = 0; off < nd; off += NGM_NDMAX) {
+        const dim3 grid((unsigned)rb.ncb, (unsigned)((rb.D + RT_DT - 1) / RT_DT), (unsigned)std::min<long long>(NGM_NDMAX, nd - off));
+        hipLaunchKernelGGL(k_ngm_rows<RT_DT>, grid, dim3(256), lds, st, d, c, rb, theta, B, first, (int)off, offsets, members, G, P, ld);
+    }
+}
+
+// Above 64 KiB of dynamic LDS the kernel needs the attribute (as k_rt_trace gets its own at the rt reset).
+static void ngm_lds_attribute(int Mp) {
+    const size_t lds = k_rt_trace_lds_bytes<RT_DT>(Mp);
+    if (lds > 64 * 1024)
+        (void)hipFuncSetAttribute((const void *)k_ngm_rows<RT_DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
+static void ngm_launch(seir_sampler *s, const LaunchCfg &l, int slot0, long long pos0, int nj) {
+    const GroupNgm &n = s->ngm;
+    const int B = s->cfg.B, G = s->grp.G;
+    ngm_rows_launch(l.d, s->ctx->c, l.st, s->rt, (const double *)s->ch.tr_theta, B, slot0, (long long)nj * B, n.offsets,
+                    s->grp.members, G, n.P, (long long)l.d.Mp);
+    // K [pos][b][g][h][t]: the group sums of P [nd][g][t][.] over the members of h, (draw, g) as the "draw" axis
+    gcurve_wsums_launch(l.d, l.st, n.offsets, s->grp.members, n.weights, n.P, G, n.D, l.d.Mp, 0, pos0 * B * G, (long long)nj * B * G,
+                        n.out);
+}
+
+extern "C" int seir_sampler_group_ngm(seir_sampler *s, const double *weights, int64_t cap) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if (!weights || cap == 0) {
+        if (s->ngm.cap && (rc = drain(s))) return rc;
+        ngm_off(s);
+        return 0;
+    }
+    if ((rc = need_events(s, RT_USER.verb))) return rc;
+    if (cap < 0 || cap > (1ll << 20))
+        return fail(SEIR_ERR_INVALID, "cap=%lld outside [0, 2^20]: the draws per chain between two resets", (long long)cap);
+    if (!s->grp_on) return fail(SEIR_ERR_STATE, "no group table is set: call seir_sampler_groups_set first");
+    if (!s->rt_on) return fail(SEIR_ERR_STATE, "%s", RT_USER.not_enabled);
+    if (s->rt_j != 0)
+        return fail(SEIR_ERR_STATE, "%lld draws per chain have been folded since the reset: the draw store is sized between "
+                    "seir_sampler_rt_reset and the first seir_sampler_rt", s->rt_j);
+    const Dims &d = s->ctx->d;
+    const int B = s->cfg.B, G = s->grp.G, D = s->rt.D;
+    const size_t nnz = (size_t)s->grp_offsets[G];
+    for (size_t k = 0; k < nnz; ++k)
+        if (!(fabs(weights[k]) < __builtin_inf())) return fail(SEIR_ERR_INVALID, "weights[%zu] is not finite", k);
+    if ((rc = drain(s))) return rc;
+    ngm_off(s);
+    // the staging bound covers the S plane, the cell plane of group R_t and P together: the batch shrinks accordingly
+    const size_t bound = s->ctx->opt_rt_staging_kib ? (size_t)s->ctx->opt_rt_staging_kib << 10 : RT_STAGING_BYTES;
+    const size_t per_slot = (size_t)B * d.Mp * D * (sizeof(int) + sizeof(double) + (size_t)G * sizeof(double));
+    const int slots = (int)std::max<size_t>(1, std::min<size_t>((size_t)s->rt_slots, bound / per_slot));
+    const unsigned long long out_bytes = (unsigned long long)cap * B * G * G * D * 8ull;
+    const unsigned long long p_bytes = (unsigned long long)slots * B * G * D * d.Mp * 8ull;
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    // half of what is free: the policy of a device that is shared, not a measurement (groups_refuse_bytes)
+    if (out_bytes + p_bytes > (unsigned long long)free_b / 2)
+        return fail(SEIR_ERR_INVALID, "the group next-generation matrix needs %llu bytes (%lld draws x %d chains x %d x %d groups x "
+                    "%d days x 8 + %llu of a batch's rows), more than half of the %llu bytes free on the device",
+                    out_bytes + p_bytes, (long long)cap, B, G, G, D, p_bytes, (unsigned long long)free_b);
+    GroupNgm &n = s->ngm;
+    hipError_t e = hipMalloc((void **)&n.offsets, sizeof(int) * (size_t)(G + 1));
+    if (e == hipSuccess) e = hipMemcpy(n.offsets, s->grp_offsets.data(), sizeof(int) * (size_t)(G + 1), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void **)&n.weights, sizeof(double) * nnz);
+    if (e == hipSuccess) e = hipMemcpy(n.weights, weights, sizeof(double) * nnz, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void **)&n.out, (size_t)out_bytes);
+    if (e == hipSuccess) e = hipMemset(n.out, 0, (size_t)out_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&n.P, (size_t)p_bytes);
+    if (e == hipSuccess) e = hipMemset(n.P, 0, (size_t)p_bytes);
+    if (e != hipSuccess) {
+        ngm_off(s);
+        return fail(SEIR_ERR_DEVICE, "allocating %llu bytes of the group next-generation matrix failed: %s", out_bytes + p_bytes,
+                    hipGetErrorString(e));
+    }
+    ngm_lds_attribute(d.Mp);
+    n.cap = cap; n.D = D; n.slots = slots;
+    return 0;
+}
+
+extern "C" int seir_sampler_read_group_ngm(seir_sampler *s, int64_t first_draw, int64_t count, double *out) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = rt_check(s))) return rc;
+    if (!s->ngm.cap)
+        return fail(SEIR_ERR_STATE, "the group next-generation matrix is not enabled: call seir_sampler_group_ngm behind "
+                    "seir_sampler_rt_reset (a new table, another window or a refusal switches it off)");
+    if (first_draw < 0 || count < 0 || first_draw + count > s->rt_j)
+        return fail(SEIR_ERR_INVALID, "draws [%lld,%lld) outside the %lld folded since the reset", (long long)first_draw,
+                    (long long)(first_draw + count), s->rt_j);
+    if (!out) return fail(SEIR_ERR_INVALID, "null pointer");
+    const size_t row = (size_t)s->cfg.B * s->grp.G * s->grp.G * s->ngm.D;
+    if (count)
+        HIP_TRY(hipMemcpyAsync(out, s->ngm.out + (size_t)first_draw * row, sizeof(double) * (size_t)count * row, hipMemcpyDeviceToHost,
+                               s->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    return check_ev_overflow(s);
+}
+
+extern "C" int seir_group_ngm_rows(seir_ctx *ctx, int32_t n, const double *theta, const int32_t *events, int32_t days, int32_t G,
+                                   const int32_t *offsets, const int32_t *members, double *out) {
+    int rc = check_batch(ctx, 1);
+    if (rc) return rc;
+    if (!theta || !events || !out) return fail(SEIR_ERR_INVALID, "null pointer");
+    const Dims d = whole(ctx, 1).d;
+    if (n < 1) return fail(SEIR_ERR_INVALID, "n=%d: at least one draw", n);
+    if (days < 1 || days > d.T) return fail(SEIR_ERR_INVALID, "days=%d outside [1, T = %d]", days, d.T);
+    std::vector<int> seg;
+    if ((rc = groups_parse(G, offsets, members, d.M, seg))) return rc;
+    const int D = days;
+    const size_t nnz = (size_t)offsets[G];
+    // a batch's planes (events, S, P) stay within the staging bound; at least one draw is always taken
+    const size_t bound = ctx->opt_rt_staging_kib ? (size_t)ctx->opt_rt_staging_kib << 10 : RT_STAGING_BYTES;
+    const size_t ev_draw = (size_t)d.M * d.T * 3, p_draw = (size_t)G * D * d.M;
+    const size_t per_draw = ev_draw * sizeof(int) + (size_t)d.Mp * D * sizeof(int) + p_draw * sizeof(double);
+    const int nb = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)n, NGM_NDMAX), bound / per_draw));
+    RtBufs rb{};
+    rb.D = D; rb.t0 = d.T - D; rb.ncb = (d.M + 63) / 64;
+    DevBuf dth, dev, dea, dS, dP, doff, dmem;
+    if ((rc = dth.alloc(sizeof(double) * nb * d.P)) || (rc = dev.alloc(sizeof(int) * nb * ev_draw)) ||
+        (rc = dea.alloc(sizeof(double) * nb * d.Tp)) || (rc = dS.alloc(sizeof(int) * (size_t)nb * d.Mp * D)) ||
+        (rc = dP.alloc(sizeof(double) * nb * p_draw)) || (rc = doff.alloc(sizeof(int) * (size_t)(G + 1))) ||
+        (rc = dmem.alloc(sizeof(int) * nnz)))
+        return rc;
+    rb.ea = dea.as<double>(); rb.S = dS.as<int>();
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(doff.p, offsets, sizeof(int) * (size_t)(G + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dmem.p, members, sizeof(int) * nnz, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(dS.p, 0, sizeof(int) * (size_t)nb * d.Mp * D, st));
+    ngm_lds_attribute(d.Mp);
+    Work tw = ctx->w;                                 // k_rt_tables writes Work::ea: a buffer of this call's own
+    tw.ea = rb.ea;
+    for (int s0 = 0; s0 < n; s0 += nb) {
+        const int nj = std::min(nb, n - s0);
+        HIP_TRY(hipMemcpyAsync(dth.p, theta + (size_t)s0 * d.P, sizeof(double) * nj * d.P, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(dev.p, events + (size_t)s0 * ev_draw, sizeof(int) * nj * ev_draw, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_rt_tables, dim3(nj), dim3(256), 0, st, d, tw, dth.as<double>());
+        hipLaunchKernelGGL(k_rt_prepare<0>, dim3((d.M + RT_PREP_ROWS - 1) / RT_PREP_ROWS, nj), dim3(64 * RT_PREP_ROWS), 0, st, d,
+                           ctx->c, rb, (const void *)dev.p, 1, 0);
+        ngm_rows_launch(d, ctx->c, st, rb, dth.as<double>(), 1, 0, nj, doff.as<int>(), dmem.as<int>(), G, dP.as<double>(), d.M);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out + (size_t)s0 * p_draw, dP.p, sizeof(double) * nj * p_draw, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return 0;
 }

@@ -354,6 +354,28 @@ class Posterior:
             self.create_dataset("rt/group_R_t_quantiles", np.ascontiguousarray(quantiles[0], dtype=np.float64))
             self.create_dataset("rt/pooled_group_R_t_quantiles", np.ascontiguousarray(quantiles[1], dtype=np.float64))
 
+    def write_group_ngm(self, days, first_day, K, stats, pooled=None, radius=None):
+        """samples/ngm_by_group [n,G,G,D] (destination, source, day: this chain's draws of the group next-generation matrix)
+        and the group ngm/: days [1], first_day [1] (= T - D), count [1], K_mean, K_var [G,G,D], local_share_mean [G,D]
+        (`posterior.groups.ngm_stats`) and, where `stats` has them, K_quantiles [k,G,G,D] and local_share_quantiles [k,G,D];
+        `pooled` (or None): (K_quantiles, local_share_quantiles, chain ids) over the draws of all chains of the process ->
+        ngm/pooled_K_quantiles, pooled_local_share_quantiles, pooled_chains; `radius` (or None: the table is no partition):
+        samples/ngm_spectral_radius [n,D] (`posterior.groups.spectral_radius`)."""
+        K = np.ascontiguousarray(K, dtype=np.float64)
+        self.create_dataset("samples/ngm_by_group", K)
+        self.create_dataset("ngm/days", np.array([float(days)]))
+        self.create_dataset("ngm/first_day", np.array([float(first_day)]))
+        self.create_dataset("ngm/count", np.array([float(K.shape[0])]))
+        for k in ("K_mean", "K_var", "local_share_mean", "K_quantiles", "local_share_quantiles"):
+            if k in stats:
+                self.create_dataset(f"ngm/{k}", np.ascontiguousarray(stats[k], dtype=np.float64))
+        if pooled is not None:
+            self.create_dataset("ngm/pooled_K_quantiles", np.ascontiguousarray(pooled[0], dtype=np.float64))
+            self.create_dataset("ngm/pooled_local_share_quantiles", np.ascontiguousarray(pooled[1], dtype=np.float64))
+            self.create_dataset("ngm/pooled_chains", np.asarray(pooled[2], np.float64))
+        if radius is not None:
+            self.create_dataset("samples/ngm_spectral_radius", np.ascontiguousarray(radius, dtype=np.float64))
+
     def write_group_within_between(self, defined, within_share_mean, p_within_gt_between):
         """within_between/group_defined, group_within_share_mean, group_p_within_gt_between [G,D] over this chain's draws:
         the share is Wg / (Wg + Bg) of the members' summed pressures ("between": from outside each member location, as in
@@ -735,6 +757,8 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     G_mod.require_curves(groups, groups_rt, rt_days, groups_wb, wb_days)
     if groups_rt and population is None:
         raise ValueError("groups_rt: run_mcmc needs population = N")
+    groups_ngm = G_mod.switch(config.get("groups_ngm"), "groups_ngm")
+    G_mod.require_ngm(groups, groups_ngm, rt_days, groups_rt)
     nb, ns = int(config["num_bursts"]), int(config["num_burst_samples"])
     chain_ids = [getattr(sampler, "first_chain_id", 0) + c for c in range(sampler.B)]
     warm_kw, burst_kw = {}, {}                              # the keywords of the warm-up's and the sampling phase's draws
@@ -890,6 +914,10 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     # and Mcmc.within_between) the switches are set on the sampler once, behind the table: R_t, population-weighted, and the
     # within / between pressures of every kept draw of the sampling phase are then also formed per group on the device and
     # cross with the trace (`trace.group_curves`).  Without the keys nothing of it is called.
+    # With Mcmc.groups_ngm (needs `groups`, Mcmc.rt and Mcmc.groups_rt) the group next-generation matrix of every kept draw
+    # of the sampling phase is kept on the device: the switch is set once, behind set_group_rt and the rt reset, with a store
+    # of num_bursts x num_burst_samples draws per chain, and read once at the end of sampling.  It is no burst product: the
+    # draws' keywords are what they were.  Without the key nothing of it is called.
     if groups is not None:                                  # the one record that calls the sampler here, ahead of the warm-up
         G_mod.require_source(groups, summaries, horizon, check_days, groups_rt, groups_wb)
         s.set_groups(groups.offsets, groups.members)        # once; the sources size their outputs at their resets
@@ -961,6 +989,19 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
                 for c, post in enumerate(posteriors):
                     post.write_group_rt(*G_mod.curve_moments(rg[:, c]), None if q is None else (q[0][:, c], q[1]))
                 print(G_mod.curve_run_line("R_t", groups, rg, "samples/R_t_by_group and rt/group_*"), file=log, flush=True)
+            if groups_ngm:
+                K = s.read_group_ngm(nb * ns) if nb * ns else np.empty((0, s.B, groups.G, groups.G, rt_days))   # [n,B,G,G,D]
+                rg = _stack(grp_rt, s.B, groups.G, rt_days)     # [n,B,G,D]: the denominator of the local share
+                part = G_mod.is_partition(groups, s.M)
+                pooled = None
+                if rq_probs and K.shape[0]:
+                    ps = G_mod.ngm_stats(K.reshape((-1,) + K.shape[2:]), rg.reshape((-1,) + rg.shape[2:]), rq_probs)
+                    pooled = (ps["K_quantiles"], ps["local_share_quantiles"], chain_ids)
+                for c, post in enumerate(posteriors):
+                    post.write_group_ngm(rt_days, s.T - rt_days, K[:, c],
+                                         G_mod.ngm_stats(K[:, c], rg[:, c], rq_probs if rq_probs and K.shape[0] else None),
+                                         pooled, G_mod.spectral_radius(K[:, c]) if part else None)
+                print(G_mod.ngm_run_line(groups, K, rg), file=log, flush=True)
             if groups_wb:
                 wg, bg = (_stack([x[i] for x in grp_wb], s.B, groups.G, wb_days) for i in (0, 1))
                 for c, post in enumerate(posteriors):
@@ -970,7 +1011,8 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
                 print(G_mod.curve_run_line("Within share of the infection pressure (between: from outside each member location)",
                                            groups, share, "samples/*_pressure_by_group and within_between/group_*"),
                       file=log, flush=True)
-        grp = (lambda: None, grp_flush, grp_finish)
+        # the store is sized behind the rt reset (the rt record's begin, which runs first) and the switch of group R_t
+        grp = ((lambda: s.set_group_ngm(rt_w, nb * ns)) if groups_ngm else (lambda: None), grp_flush, grp_finish)
         records.append(grp)
 
     # With Mcmc.within_between = D (`within_between_mode`) the within/between pressure shares of every kept draw of the
@@ -1131,7 +1173,7 @@ def launch_forms(lay, device_arg, hmc="auto", moves="auto", env=os.environ):
 def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool_step_size=False, init_jitter=0.0,
          events_dtype="auto", hmc="auto", moves="auto", thin=None, summaries=None, diagnostics=None, diagnostics_batch=None,
          forecast=None, forecast_walk=None, rt=None, check=None, forecast_quantiles=None, within_between=None,
-         rt_quantiles=None, groups=None, groups_rt=None, groups_within_between=None):
+         rt_quantiles=None, groups=None, groups_rt=None, groups_within_between=None, groups_ngm=None):
     """Constructs and runs the MCMC (covid19uk/inference/inference.py:473-608).
 
     Multi-GPU: launched as one process per GPU, every rank runs `num_chains` chains with
@@ -1145,7 +1187,8 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     (`forecast_quantiles_mode`), `rt` config["rt"] (`rt_mode`), `check` config["check"] (`check_mode`), `within_between`
     config["within_between"] (`within_between_mode`), `rt_quantiles` config["rt_quantiles"] (`rt_quantiles_mode`), `groups`
     config["groups"] (`posterior.groups.parse_groups`: "nations" or a mapping name -> members), `groups_rt` config["groups_rt"]
-    and `groups_within_between` config["groups_within_between"] (on / off; `posterior.groups.require_curves`)."""
+    and `groups_within_between` config["groups_within_between"] (on / off; `posterior.groups.require_curves`), `groups_ngm`
+    config["groups_ngm"] (on / off; `posterior.groups.require_ngm`)."""
     wb_days = 0
     if within_between is not None or "within_between" in config:
         wb_days = within_between_mode(config, within_between)   # refused here: before any GPU call
@@ -1189,7 +1232,10 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     grp_rt_on = G_mod.switch(config.get("groups_rt") if groups_rt is None else groups_rt, "groups_rt")
     grp_wb_on = G_mod.switch(config.get("groups_within_between") if groups_within_between is None else groups_within_between,
                              "groups_within_between")
-    config = {k: v for k, v in config.items() if k not in ("groups", "groups_rt", "groups_within_between")}
+    grp_ngm_on = G_mod.switch(config.get("groups_ngm") if groups_ngm is None else groups_ngm, "groups_ngm")
+    config = {k: v for k, v in config.items() if k not in ("groups", "groups_rt", "groups_within_between", "groups_ngm")}
+    if grp_ngm_on:
+        config = dict(config, groups_ngm=True)
     if grp_rt_on:
         config = dict(config, groups_rt=True)
     if grp_wb_on:
@@ -1201,6 +1247,7 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     if not G_mod.is_off(group_spec):                        # absent: the input's location coordinate is not even opened
         group_table = G_mod.parse_groups(group_spec, cases.shape[0], read_location_names(data_file))
     G_mod.require_curves(group_table, grp_rt_on, rt_days, grp_wb_on, wb_days)   # likewise before any GPU call
+    G_mod.require_ngm(group_table, grp_ngm_on, rt_days, grp_rt_on)
     G_mod.require_source(group_table, config["summaries"], horizon, check_days, grp_rt_on, grp_wb_on)
     rng = np.random.default_rng(seed)                       # same imputation on every rank: one initial state per job
     B = int(num_chains)
@@ -1389,6 +1436,12 @@ def main(argv=None):
                              "Mcmc.groups_within_between; needs --groups and --within-between): samples/within_pressure_by_group, "
                              "between_pressure_by_group and within_between/group_*; 'between' is from outside each member "
                              "location, as in the national figure, not from outside the group")
+    parser.add_argument("--groups-ngm", action="store_true", default=None, dest="groups_ngm",
+                        help="group next-generation matrix of every kept draw, formed on the device (overrides Mcmc.groups_ngm; "
+                             "needs --groups, --rt and --groups-rt): K[g][h][t], the expected infections in group g caused by one "
+                             "typical infective of group h -- samples/ngm_by_group, ngm/K_mean, K_var, local_share_mean (the "
+                             "part of a group's R_t that stays inside it), with --rt-quantiles their quantiles, and for a "
+                             "partition samples/ngm_spectral_radius")
     args = parser.parse_args(argv)
     if args.thin is not None and args.thin < 1:
         parser.error(f"--thin {args.thin}: the thinning interval is >= 1")
@@ -1404,7 +1457,8 @@ def main(argv=None):
          **({} if args.rt_quantiles is None else dict(rt_quantiles=args.rt_quantiles)),
          **({} if args.groups is None else dict(groups=G_mod.load_spec(args.groups))),
          **({} if args.groups_rt is None else dict(groups_rt=True)),
-         **({} if args.groups_within_between is None else dict(groups_within_between=True)))
+         **({} if args.groups_within_between is None else dict(groups_within_between=True)),
+         **({} if args.groups_ngm is None else dict(groups_ngm=True)))
 
 
 if __name__ == "__main__":

@@ -17,7 +17,12 @@ or quantiles, which is why the sums are formed per draw.
 The group curves (`Mcmc: groups_rt`, `groups_within_between`; include/seir_hip.h, "Group curves on the device") are sums of
 fp64 values, whose bits depend on the order of the adds.  `weighted_sum_rows` is the one host definition of that order --
 the device's (csrc/group_curve_kernels.h), restated in NumPy -- and `rt_weights`, `curve_moments`, `share_stats` are what
-the run makes of the curves."""
+the run makes of the curves.
+
+The group next-generation matrix (`Mcmc: groups_ngm`; include/seir_hip.h, "Group next-generation matrix on the device") is
+K[g][h][t], the expected infections in group g caused by one typical infective of group h on day t: `ngm_rows` and
+`group_ngm` restate the device's definition (csrc/ngm_kernels.h), `ngm_stats` and `spectral_radius` are what the run makes
+of the draws, `require_ngm` its refusals."""
 from dataclasses import dataclass
 
 import numpy as np
@@ -108,6 +113,117 @@ def share_stats(within, between):
         mean = np.where(ok, share, 0.0).sum(axis=0) / n
         gt = (ok & (wg > bg)).sum(axis=0) / n
     return n.astype(np.float64), np.where(n > 0, mean, np.nan), np.where(n > 0, gt, np.nan)
+
+
+NGM_PARTIALS = 4                  # partial sums of a rows-plane cell: member positions p, p + 4, ...
+
+
+def ngm_rows(terms, table, period=1.0):
+    """The rows plane of the group next-generation matrix in the device's fixed order (csrc/ngm_kernels.h): `terms` float64
+    [..., M, D, M], terms[i][t][j] = S_it (1 - exp(-rate_ij)) of destination row i, day t and source column j (what the
+    device returns for a table of singletons when the infectious period is exactly 1) -> P [..., G, D, M].
+
+    For a group with members m_0 < ... < m_{n-1}: partial sum p in {0, 1, 2, 3} starts from +0.0 and adds the member
+    POSITIONS k = p, p + 4, ... ascending, one rounding per add; P = ((p0 + p1) + (p2 + p3)) * period.  The device adds a
+    term by the fused multiply-add of rt_cell, acc + S * prob with one rounding: this restatement has its bits wherever
+    S * prob is exact (S a power of two, or 0), and is within one rounding per add of it everywhere else."""
+    x = np.asarray(terms, np.float64)
+    out = np.empty(x.shape[:-3] + (table.G,) + x.shape[-2:])
+    for g in range(table.G):
+        rows = table.rows(g)
+        part = []
+        for p in range(NGM_PARTIALS):
+            acc = np.zeros(x.shape[:-3] + x.shape[-2:])
+            for k in range(p, len(rows), NGM_PARTIALS):
+                acc = acc + x[..., rows[k], :, :]
+            part.append(acc)
+        out[..., g, :, :] = ((part[0] + part[1]) + (part[2] + part[3])) * period
+    return out
+
+
+def group_ngm(rows, table, weights):
+    """K from a rows plane: `rows` float64 [..., G, D, M] (P[g][t][j]; `SeirModel.group_ngm_rows`, or `ngm_rows`) ->
+    K [..., G, G, D] (destination g, source h, day): the group sum of P[g][t][.] over the members of h with `weights` [nnz],
+    in the one order of `weighted_sum_rows`."""
+    k = weighted_sum_rows(table, np.asarray(rows, np.float64), weights, axis=-1)      # [..., g, D, h]
+    return np.ascontiguousarray(np.moveaxis(k, -1, -2))
+
+
+def is_partition(table, M):
+    """Every location of [0, M) is a member of exactly one group."""
+    return np.array_equal(np.sort(np.asarray(table.members)), np.arange(int(M)))
+
+
+def ngm_stats(K, R_by_group, probs=None):
+    """One chain's draws K [n, G, G, D] and the per-draw group curve R_by_group [n, G, D] (samples/R_t_by_group: the column
+    sums of K's fine-grained matrix over ALL destinations) -> dict:
+      K_mean, K_var [G, G, D]    over the draws (ddof 0); NaN without draws;
+      local_share [n, G, D]      K[h][h][t] / R_by_group[h][t] per draw: the part of a region's R that stays inside it; NaN
+                                 (without a warning) where R_by_group == 0;
+      local_share_mean [G, D]    over the draws, NaN where any draw is undefined;
+      K_quantiles [k, G, G, D], local_share_quantiles [k, G, D]    at `probs`, by the one rank rule
+                                 (`posterior.quantiles`), when `probs` is given."""
+    K = np.asarray(K, np.float64)
+    R = np.asarray(R_by_group, np.float64)
+    n, G = K.shape[0], K.shape[1]
+    if K.ndim != 4 or K.shape[2] != G or R.shape != (n, G, K.shape[3]):
+        raise ValueError(f"K {K.shape} and R_by_group {R.shape}: need [n, G, G, D] and [n, G, D]")
+    diag = K[:, np.arange(G), np.arange(G), :]                     # [n, G, D]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        share = np.where(R != 0.0, diag / np.where(R != 0.0, R, 1.0), np.nan)
+    out = {"local_share": share}
+    if n == 0:
+        out["K_mean"], out["K_var"] = np.full(K.shape[1:], np.nan), np.full(K.shape[1:], np.nan)
+        out["local_share_mean"] = np.full(R.shape[1:], np.nan)
+    else:
+        out["K_mean"], out["K_var"], out["local_share_mean"] = K.mean(axis=0), K.var(axis=0), share.mean(axis=0)
+    if probs is not None:
+        if n == 0:
+            out["K_quantiles"] = np.full((len(probs),) + K.shape[1:], np.nan)
+            out["local_share_quantiles"] = np.full((len(probs),) + R.shape[1:], np.nan)
+        else:
+            out["K_quantiles"] = quantiles(K, probs)
+            undefined = np.isnan(share).any(axis=0)
+            q = quantiles(np.where(undefined, 0.0, share), probs)
+            out["local_share_quantiles"] = np.where(undefined, np.nan, q)
+    return out
+
+
+def spectral_radius(K):
+    """K [..., G, G, D] -> max |eigenvalue| of K[..., :, :, t] per (draw, day), float64 [..., D].  For a table that
+    partitions the locations this is the dominant eigenvalue of the next-generation matrix aggregated under
+    population-distributed infectives (the weights of `rt_weights` spread a group's typical infective over its members by
+    population), and of the next-generation matrix itself for a table of singletons.  It is formed only for a partition
+    (`is_partition`): with overlapping groups or locations left out, K is not a next-generation matrix of anything."""
+    K = np.asarray(K, np.float64)
+    if K.ndim < 3 or K.shape[-3] != K.shape[-2]:
+        raise ValueError(f"K {K.shape}: need [..., G, G, D]")
+    if K.size == 0:
+        return np.empty(K.shape[:-3] + K.shape[-1:])
+    return np.abs(np.linalg.eigvals(np.moveaxis(K, -1, -3))).max(axis=-1)
+
+
+def ngm_run_line(table, K, R_by_group):
+    """One log line for K [n, B, G, G, D] with R_by_group [n, B, G, D]: every group's last-day local share with its 0.05 /
+    0.95 quantiles over all draws and chains of this process, and the largest off-diagonal entry of the last day's mean with
+    its (source -> destination) names."""
+    K, R = np.asarray(K, np.float64), np.asarray(R_by_group, np.float64)
+    if K.shape[0] == 0:
+        return "Group next-generation matrix: no draws; ngm/* and samples/ngm_by_group written"
+    G = K.shape[2]
+    last = K[..., -1].reshape(-1, G, G)
+    st = ngm_stats(last[..., None], R[..., -1].reshape(-1, G)[..., None], (0.05, 0.95))
+    mean, q = st["local_share_mean"][:, 0], st["local_share_quantiles"][:, :, 0]
+    shown = ", ".join(f"{name} {mean[g]:.3g} [{q[0, g]:.3g}, {q[1, g]:.3g}]"
+                      for g, name in list(enumerate(table.names))[:6]) + (", ..." if G > 6 else "")
+    line = (f"Local share of R_t by group (infections that stay inside the group), last day, mean [0.05, 0.95] over "
+            f"{last.shape[0]} draw(s): {shown}")
+    if G > 1:
+        off = st["K_mean"][:, :, 0].copy()
+        off[np.arange(G), np.arange(G)] = -np.inf
+        g, h = np.unravel_index(int(np.argmax(off)), off.shape)
+        line += f"; largest export {table.names[h]} -> {table.names[g]}: {off[g, h]:.3g}"
+    return line + "; formed per draw on the device; ngm/* and samples/ngm_by_group written"
 
 
 def curve_run_line(what, table, curves, dataset):
@@ -232,6 +348,19 @@ def require_curves(table, groups_rt, rt_days, groups_within_between, wb_days):
             raise ValueError(f"{key} given without groups: there is no table of groups to form the curves over")
         if on and not days:
             raise ValueError(f"{key} given without {need}: it would have no effect")
+
+
+def require_ngm(table, groups_ngm, rt_days, groups_rt):
+    """`groups_ngm` needs `groups`, `rt` and `groups_rt` (whose per-draw curve is the denominator of the local share):
+    refused otherwise."""
+    if not groups_ngm:
+        return
+    if table is None:
+        raise ValueError("groups_ngm given without groups: there is no table of groups to form the matrix over")
+    if not rt_days:
+        raise ValueError("groups_ngm given without rt: it would have no effect")
+    if not groups_rt:
+        raise ValueError("groups_ngm given without groups_rt: the group curve R_t_by_group is the denominator of the local share")
 
 
 def switch(value, name):

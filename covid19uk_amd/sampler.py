@@ -369,6 +369,7 @@ class ChainSampler:
     _group_wb_on = False          # set_group_within_between: group within / between rides on within_between
     _group_rt_refused = False     # the last reset_rt could not size the group outputs: rt is on without them
     _group_wb_refused = False
+    _group_ngm_cap = 0            # set_group_ngm: draws per chain of the group next-generation matrix's store (0: off)
     first_chain_id = 0
 
     def __init__(self, model: SeirModel, config: dict, num_chains: int, seed: int = 0,
@@ -809,8 +810,12 @@ class ChainSampler:
             _lib.check(self._lib.seir_sampler_rt_reset(self._s, D, _dptr(w)))
         except _lib.SeirError as e:
             if self._group_rt_on and "group curves" in str(e):   # the reset is done; the group outputs were refused
+                if D != self._rt_D:
+                    self._group_ngm_cap = 0
                 self._rt_D, self._group_rt_refused = D, True
             raise
+        if D != self._rt_D:
+            self._group_ngm_cap = 0                         # another window frees the store of the group NGM
         self._rt_D, self._group_rt_refused = D, False
 
     def rt(self, first: int, count: int):
@@ -962,6 +967,7 @@ class ChainSampler:
             _lib.check(self._lib.seir_sampler_groups_set(self._s, 0, None, None))
             self._groups_G = self._groups_nnz = 0
             self._group_rt_on = self._group_wb_on = False
+            self._group_ngm_cap = 0
             return
         off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
         mem = np.ascontiguousarray(members, dtype=np.int32).reshape(-1)
@@ -978,8 +984,10 @@ class ChainSampler:
                 raise
             # the table is in force; group within / between could not be sized for it
             self._groups_G, self._groups_nnz, self._group_rt_on, self._group_wb_refused = G, int(off[G]), False, True
+            self._group_ngm_cap = 0
             raise
         self._groups_G, self._groups_nnz = G, int(off[G])
+        self._group_ngm_cap = 0                             # its weights belonged to the old table, too
         self._group_rt_on = False                           # its weights belonged to the old table
         self._group_wb_refused = False
 
@@ -1015,6 +1023,40 @@ class ChainSampler:
                 self._group_wb_on = False
             raise
         self._group_wb_on, self._group_wb_refused = bool(on), False
+
+    # -- group next-generation matrix (include/seir_hip.h, "Group next-generation matrix on the device") ----------------
+    def set_group_ngm(self, weights, cap: int):
+        """Group next-generation matrix on: while a table is set, every draw that `rt` folds also leaves K[g][h][t], the
+        expected infections in group g caused by one typical infective of group h on window day t, in a store of `cap`
+        draws per chain (`read_group_ngm`).  `weights` [nnz] float64 aligned with the table's `members`
+        (`posterior.groups.rt_weights`: the array group R_t uses).  Between `reset_rt` and the first `rt`, as
+        `keep_rt_draws`.  None or cap = 0 switches it off and frees the store; so do a later `set_groups` and a `reset_rt`
+        with another window.  Not a burst product: `sample` / `sample_bursts` carry nothing of it."""
+        cap = int(cap)
+        if cap < 0:
+            raise ValueError(f"cap={cap}: the number of draws per chain to keep")
+        if weights is None or cap == 0:
+            _lib.check(self._lib.seir_sampler_group_ngm(self._s, None, 0))
+            self._group_ngm_cap = 0
+            return
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if self._groups_G and w.size != self._groups_nnz:
+            raise ValueError(f"need weights [{self._groups_nnz}], aligned with the table's members")
+        try:
+            _lib.check(self._lib.seir_sampler_group_ngm(self._s, _dptr(w), cap))   # SEIR_ERR_STATE without a table or an rt reset
+        except _lib.SeirError as e:
+            if "group next-generation matrix needs" in str(e):  # store refused: the switch is off; any other refusal left it alone
+                self._group_ngm_cap = 0
+            raise
+        self._group_ngm_cap = cap
+
+    def read_group_ngm(self, count: int, first: int = 0) -> np.ndarray:
+        """Blocking read of K of draws [first, first+count) since the last `reset_rt`: float64 [count,B,G,G,D]
+        (destination group, source group, window day)."""
+        count = int(count)
+        out = np.empty((max(count, 0), self.B, self._groups_G, self._groups_G, self._rt_D), dtype=np.float64)
+        _lib.check(self._lib.seir_sampler_read_group_ngm(self._s, int(first), count, _dptr(out)))
+        return out
 
     def _group_curve_days(self, sizes):
         """(G, {key of GROUP_CURVE_KEYS: window days}) of the curves that leave outputs with a burst that runs the rt /

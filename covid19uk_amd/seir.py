@@ -353,6 +353,33 @@ class SeirModel:
                                               out.ctypes.data_as(_lib.c_double_p)))
         return out
 
+    def group_ngm_rows(self, theta, events, offsets, members, days=None):
+        """The rows plane of the group next-generation matrix on the device (csrc/ngm_kernels.h; include/seir_hip.h,
+        seir_group_ngm_rows): `theta` [n, P] constrained draws, `events` integer [n, M, T, 3] (the trace layout with one chain),
+        the groups a CSR pair as for `group_sums`, `days` the window [T - days, T) (None: all T days).  Returns float64
+        [n, G, days, M]: P[g][t][j], the expected infections in group g caused by one infective of location j on day t -- the
+        bits of `posterior.groups.ngm_rows`; `posterior.groups.group_ngm` makes K of it."""
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        ev = np.ascontiguousarray(events)
+        n = th.shape[0]
+        if th.shape != (n, self.P) or ev.shape != (n, self.M, self.T, 3):
+            raise ValueError(f"need theta [n,{self.P}] and events [n,{self.M},{self.T},3]")
+        if ev.dtype.kind not in "iu":
+            raise TypeError("events: integer counts (the trace layout), not " + str(ev.dtype))
+        ev = np.ascontiguousarray(ev, dtype=np.int32)
+        off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
+        mem = np.ascontiguousarray(members, dtype=np.int32).reshape(-1)
+        G = off.size - 1
+        if G >= 1 and mem.size < int(off.max()):            # what the library cannot check: it reads members up to the offsets
+            raise ValueError(f"offsets reach {int(off.max())}, members holds {mem.size}")
+        D = self.T if days is None else int(days)
+        out = np.empty((n, max(G, 0), max(D, 0), self.M), dtype=np.float64)
+        ip = ctypes.POINTER(ctypes.c_int32)
+        mem_arg = mem if mem.size else np.zeros(1, np.int32)
+        _lib.check(self._lib.seir_group_ngm_rows(self._ctx, n, _dptr(th), ev.ctypes.data_as(ip), D, G, off.ctypes.data_as(ip),
+                                                 mem_arg.ctypes.data_as(ip), _dptr(out)))
+        return out
+
     def order_stats_f64(self, values, ranks, cells=1, segs=1, seg_len=None, seg_stride=None, cell_stride=None):
         """`order_stats` for float64 (csrc/order_stats_kernels.h; include/seir_hip.h, seir_order_stats_f64): the same
         cell geometry, the order of IEEE-754 totalOrder on the bit patterns (np.sort's on values without NaN, except that

@@ -953,6 +953,45 @@ int seir_group_wsums(seir_ctx *ctx, const double *v, int64_t nd, int32_t L, int3
                      const int32_t *members, const double *weights, double *out);
 
 /* ------------------------------------------------------------------------
+ * Group next-generation matrix on the device: who infects whom by region.
+ *
+ * Rg[h] of seir_sampler_group_rt is the column sum of the next-generation matrix (covid19uk/model_spec.py:302-368) over ALL
+ * destinations.  Its split by destination group cannot be rebuilt from anything else the device emits.  While the switch
+ * below is on, every draw that seir_sampler_rt folds also leaves
+ *     K [draw][B][G][G][D]   K[g][h][t]: the expected infections in group g caused by one typical infective of group h on
+ *                            window day t (destination, source, day),
+ * indexed by the draw's position since the rt reset.  THE definition (kernel and its header comment: csrc/ngm_kernels.h;
+ * NumPy: covid19uk_amd/posterior/groups.py, ngm_rows and group_ngm):
+ *   rows plane   P[g][t][j] = rt_combine(p0, p1, p2, p3, period), partial p adding the member POSITIONS k = p, p + 4, ... of
+ *                g ascending by rt_cell (the cell arithmetic of R_it, model_spec.py:302-368, as csrc/rt_trace_kernels.h has
+ *                it); for the group of all locations P is R_it bit for bit;
+ *   matrix       K[g][h][t] = the group sum of P[g][t][.] over the members of h with `weights`, by the one definition of a
+ *                group sum above.
+ * No FMA beyond rt_cell's, no floating-point atomics: the bits depend on the table and the draw alone, not on the launch
+ * geometry, the debug skew or the cut into calls, batches, buffer halves or shards.  A burst folded again after an rt reset
+ * overwrites its own positions; snapshot and restore carry nothing of the store.  A sampler that never calls these entry
+ * points allocates and launches exactly what it did before.
+ * ------------------------------------------------------------------------ */
+/* weights [offsets[G]] aligned with the members of the table in force, finite (N[m_k] / the group's population: the array
+ * group R_t uses), cap >= 1 draws per chain: on, the store ngm [cap][B][G][G][D] and a batch's rows plane allocated.  NULL or
+ * cap == 0: off, both freed.  Sized between seir_sampler_rt_reset and the first seir_sampler_rt, as seir_sampler_rt_keep is:
+ * SEIR_ERR_STATE without a table, before an rt reset or once draws have been folded.  Refused (SEIR_ERR_INVALID) above half
+ * of the device's free memory: the product is then off, seir_sampler_rt runs as before and the read fails with
+ * SEIR_ERR_STATE.  While it is on, the batches of seir_sampler_rt may shrink so that the S plane, the cell plane and the rows
+ * plane stay within the staging bound together (SEIR_OPT_RT_STAGING_KIB), and seir_sampler_rt refuses a call past cap
+ * before any launch.  An rt reset with the same window empties the store; another window frees it (off), and so does
+ * seir_sampler_groups_set: the weights belonged to the old table. */
+int seir_sampler_group_ngm(seir_sampler *s, const double *weights, int64_t cap);
+/* Blocking read of draws [first_draw, first_draw + count) since the rt reset: out [count][B][G][G][D] (destination, source,
+ * day), a host pointer.  SEIR_ERR_STATE while rt or the switch is off; SEIR_ERR_INVALID past the draws folded. */
+int seir_sampler_read_group_ngm(seir_sampler *s, int64_t first_draw, int64_t count, double *out);
+/* The rows plane alone, on host arrays: theta [n][P] constrained draws, events [n][M][T][3] (int32: the trace layout with
+ * one chain), days in [1, T] the window, the table as for seir_group_sums; out [n][G][days][M].  Runs in batches within the
+ * staging bound. */
+int seir_group_ngm_rows(seir_ctx *ctx, int32_t n, const double *theta, const int32_t *events, int32_t days, int32_t G,
+                        const int32_t *offsets, const int32_t *members, double *out);
+
+/* ------------------------------------------------------------------------
  * Reproduction number R_it.
  *
  * calc_posterior_rit (covid19uk/posterior/reproduction_number.py:13-44): for each

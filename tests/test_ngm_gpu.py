@@ -1,0 +1,589 @@
+"""Group next-generation matrix on the device (include/seir_hip.h, "Group next-generation matrix on the device";
+covid19uk_amd/csrc/ngm_kernels.h): K[g][h][t], the expected infections in group g caused by one typical infective of group h.
+
+The rows plane has ONE order (the kernel file's header; `posterior.groups.ngm_rows` restates it in NumPy), and K is a group
+sum of it in the one order of `posterior.groups.weighted_sum_rows`, so the comparisons are equalities of bits:
+
+  - the kernel alone (`SeirModel.group_ngm_rows`) with gamma0 = 4.0, where the device forms the infectious period
+    1 / (1 - exp(-exp 4)) as exactly 1.0: a table of singletons then returns every term S * prob itself, and the NumPy
+    definition on those terms must give the rows of any other table.  rt_cell adds a term by a fused multiply-add,
+    acc + S * prob rounded once; the restatement adds the rounded product.  The two are the same bits where S * prob is
+    exact, so these cases start from susceptibles that are powers of two and record no S->E events;
+  - the all-locations group against the stateless `SeirModel.reproduction_number` (k_rt) at any gamma0 and any S;
+  - through the sampler against `group_ngm(group_ngm_rows(recorded theta, recorded events))` on the same run's draws.
+
+One bound is taken from the project, not measured: against the independent oracle (`oracle.rt_oracle`, -expm1 form) the
+error form and the 1e-11 of tests/test_rt.py:62-63, the project's number for this cell arithmetic, on draws whose oracle
+matrix is entrywise >= 0 (asserted): a subset of a column then cancels no more than the column."""
+import os
+
+import numpy as np
+import pytest
+
+from covid19uk_amd import _lib, synth
+from covid19uk_amd.inference import inference as inf
+from covid19uk_amd.posterior import groups as G
+from oracle import rt_oracle as ro
+from oracle import seir_oracle as so
+from tests import helpers as H
+from tests.test_groups_gpu import _csr, _groups_for, _set
+from tests.test_recovery_gpu import _case, _same_bits
+from tests.test_rt_device_gpu import _same_run as _same_rt_run, _weight
+from tests.test_sampler_gpu import CFG_REF, api  # noqa: F401  (fixture)
+from tests.test_summary_gpu import _cli, _datasets, _sampler
+
+pytestmark = pytest.mark.gpu
+
+
+def _table(groups):
+    off, mem = _csr(groups)
+    return G.GroupTable([str(i) for i in range(len(groups))], off, mem)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def _theta(case, n, seed, gamma0=None, psi=None):
+    k = case["k"]
+    theta = so.constrain(synth.jitter_params(case["u"], n, scale=0.1, seed=seed, T=k.T))
+    if gamma0 is not None:
+        theta[:, 3] = gamma0
+    if psi is not None:
+        theta[:, 0] = psi
+    return theta
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the kernel alone
+# ---------------------------------------------------------------------------------------------------------------------
+def _sizes_table(M, rng):
+    """Groups of 1, 3, 4, 5, 64 and 65 members where M has them, two that overlap, one of all locations, the last row alone;
+    location 1 is left out of every group but `all` when M > 5."""
+    pool = np.array([m for m in range(M) if m != 1]) if M > 5 else np.arange(M)
+    groups = [list(range(M))]
+    for n in (1, 3, 4, 5, 64, 65):
+        if n <= len(pool):
+            groups.append(sorted(int(x) for x in rng.choice(pool, size=n, replace=False)))
+    groups += [list(range(0, M, 2)), list(range(M // 3, M)), [M - 1]]
+    return groups
+
+
+EXACT = {
+    # M (column blocks of 64), T, D (short of / equal to / one past the day tile of 4; D = T)
+    "M=3,T=2,D=1": (3, 2, 1),
+    "M=9,T=5,D=3": (9, 5, 3),
+    "M=65,T=5,D=4": (65, 5, 4),
+    "M=130,T=70,D=5": (130, 70, 5),
+    "M=256,T=5,D=T,256_singletons": (256, 5, 5),
+    "M=9,T=70,D=T": (9, 70, 70),
+}
+
+
+@pytest.mark.parametrize("case_id", list(EXACT))
+def test_rows_equal_the_definition_bit_for_bit_where_the_period_is_exactly_one(api, case_id):
+    M, T, D = EXACT[case_id]
+    case = H.build_case(f"micro_{M}x{T}", 7, alpha_t_sd=0.01)
+    rng = np.random.default_rng([M, T, D])
+    n = 2
+    theta = _theta(case, n, 5, gamma0=4.0)
+    # susceptibles that are powers of two and no S->E events: S_it = S0, and S * prob is exact
+    init = np.asarray(case["init"], np.float64).copy()
+    init[:, 0] = 2.0 ** rng.integers(6, 15, size=M)
+    ev = np.zeros((n, M, T, 3), np.int32)
+    ev[..., 1:] = rng.integers(0, 3, size=(n, M, T, 2))            # E->I and I->R do not enter R_it
+    single = _table([[m] for m in range(M)])
+    groups = _sizes_table(M, rng)
+    tab = _table(groups)
+    with api[0](case["cov"], init, max_chains=1) as model:
+        terms = model.group_ngm_rows(theta, ev, single.offsets, single.members, D)          # [n, M, D, M]
+        rows = model.group_ngm_rows(theta, ev, tab.offsets, tab.members, D)
+        R = model.reproduction_number(theta, ev.astype(np.float64))[:, T - D:]
+        w = rng.standard_normal(tab.members.shape) * 10.0 ** rng.integers(-3, 4, size=tab.members.shape)
+        K_dev = model.group_wsums(rows.reshape(n * tab.G, D, M), tab.offsets, tab.members, w).reshape(n, tab.G, tab.G, D)
+    assert terms.shape == (n, M, D, M) and rows.shape == (n, tab.G, D, M) and rows.dtype == np.float64
+    assert np.all(np.isfinite(terms)) and terms.max() > 0.0    # (a random dense C: psi W Cstar_ii / N_i may be below -1)
+    # the period is exactly 1.0: the all-locations rows are the definition on the terms with period 1.0, and they are R_it
+    assert np.array_equal(_bits(rows[:, 0]), _bits(G.ngm_rows(terms, _table([list(range(M))]))[:, 0]))
+    assert np.array_equal(_bits(rows[:, 0]), _bits(R))
+    assert np.array_equal(_bits(rows), _bits(G.ngm_rows(terms, tab)))
+    assert np.array_equal(_bits(rows[:, -1]), _bits(terms[:, M - 1]))                       # the last row alone
+    assert np.array_equal(_bits(G.group_ngm(rows, tab, w)), _bits(K_dev))
+    if M >= 9:
+        # the data does tell orders apart: a plain ascending sum over the rows differs somewhere
+        assert not np.array_equal(terms.sum(axis=1), rows[:, 0])
+
+
+ANY = {
+    "M=1,T=70,D=5": ("micro_1x70", 5),
+    "M=9,T=64,D=T": ("micro_9x64", 64),
+    "M=65,T=65,D=3": ("micro_65x65", 3),
+    "M=520,T=2,D=T": ("slow_520x2", 2),
+    "M=3,T=1,D=1": ("micro_3x1", 1),
+}
+
+
+@pytest.mark.parametrize("case_id", list(ANY))
+def test_the_all_locations_group_is_the_stateless_kernels_r_it_at_any_gamma0(api, case_id):
+    name, D = ANY[case_id]
+    case = H.build_case(name, 11, alpha_t_sd=0.01)
+    k = case["k"]
+    n = 3
+    theta = _theta(case, n, 3)
+    ev = np.stack([case["events"]] * n).astype(np.int32)
+    tab = _table([list(range(k.M)), [k.M - 1]])
+    with api[0](case["cov"], case["init"], max_chains=2) as model:
+        rows = model.group_ngm_rows(theta, ev, tab.offsets, tab.members, D)
+        full = model.group_ngm_rows(theta[:1], ev[:1], tab.offsets, tab.members)           # days=None: all T
+        R = model.reproduction_number(theta, ev.astype(np.float64))
+    assert rows.shape == (n, 2, D, k.M) and full.shape == (1, 2, k.T, k.M)
+    assert np.array_equal(_bits(rows[:, 0]), _bits(R[:, k.T - D:])) and np.array_equal(_bits(full[:, 0]), _bits(R[:1]))
+    assert np.all(np.isfinite(rows)) and rows[:, 0].max() > 0.0
+
+
+@pytest.mark.parametrize("name,n,D", [("ni11", 3, 5), ("uk380", 1, 2)])
+def test_rows_against_the_independent_oracle(api, name, n, D):
+    """sum_{i in g} NGM[i][j] of oracle.rt_oracle.next_generation_matrix(stable=True); psi in (0, 2] keeps the matrix
+    entrywise >= 0 on the bundled covariates (min diag(Cstar) / N = -0.307 at W = 1: negative entries need psi > 3.26)."""
+    case = H.build_case(name, 2, alpha_t_sd=0.01)
+    k = case["k"]
+    rng = np.random.default_rng(17)
+    theta = _theta(case, n, 2, psi=rng.uniform(0.05, 2.0, size=n))
+    ev = np.stack([case["events"]] * n).astype(np.int32)
+    M, T = k.M, k.T
+    groups = [list(range(M)), list(range(0, M, 3)), list(range(M // 2, M)), [0], [M - 1], sorted(rng.choice(M, size=5, replace=False))]
+    tab = _table(groups)
+    want = np.empty((n, tab.G, D, M))
+    for s in range(n):
+        par = so.unpack(theta[s], M, T)
+        state = so.compute_state(k.initial_state, ev[s].astype(np.float64))
+        for tw in range(D):
+            t = T - D + tw
+            ngm = ro.next_generation_matrix(t, state[:, t, :], par, k, stable=True)
+            assert ngm.min() >= 0.0                            # the condition of the bound: no cancellation within a column
+            for g in range(tab.G):
+                want[s, g, tw] = ngm[tab.rows(g)].sum(axis=0)
+    with api[0](case["cov"], case["init"], max_chains=1) as model:
+        got = model.group_ngm_rows(theta, ev, tab.offsets, tab.members, D)
+    err = np.max(np.abs(got - want) / np.maximum(np.abs(want), 1e-12 * np.abs(want).max()))
+    print(f"{name}: rows against the oracle, error {err:.3e}")
+    assert err < 1e-11, err
+
+
+def test_one_draw_one_past_a_batch_and_workgroup_timing(api):
+    case = H.build_case("micro_9x5", 7, alpha_t_sd=0.01)
+    k = case["k"]
+    D = 3
+    tab = _table(_sizes_table(9, np.random.default_rng(1)))
+    theta = _theta(case, 6, 9)
+    ev = np.stack([case["events"]] * 6).astype(np.int32)
+    res = {}
+    # 1 KiB of staging: one draw per batch; 4 KiB: the events (540 B), S (384 B) and P of a draw are 2.7 KiB, still one
+    for tag, kib, skew in (("plain", 0, 0), ("batches_of_1", 1, 0), ("skew1", 0, 1), ("skew3", 0, 3)):
+        with api[0](case["cov"], case["init"], max_chains=1) as model:
+            if kib:
+                model.set_option(rt_staging_kib=kib)
+            if skew:
+                model.set_option(debug_skew=skew)
+            res[tag] = model.group_ngm_rows(theta, ev, tab.offsets, tab.members, D)
+            if tag == "plain":
+                one = model.group_ngm_rows(theta[4:5], ev[4:5], tab.offsets, tab.members, D)
+                assert np.array_equal(_bits(one[0]), _bits(res[tag][4]))                    # n = 1
+    for tag in res:
+        assert np.array_equal(_bits(res[tag]), _bits(res["plain"])), tag
+    assert res["plain"].any()
+
+
+def test_group_ngm_rows_refusals(api):
+    case = H.build_case("micro_3x5", 7)
+    theta = _theta(case, 1, 1)
+    ev = np.zeros((1, 3, 5, 3), np.int32)
+    with api[0](case["cov"], case["init"], max_chains=1) as model:
+        def refused(off, mem, word, days=2):
+            with pytest.raises(_lib.SeirError) as e:
+                model.group_ngm_rows(theta, ev, np.asarray(off, np.int32), np.asarray(mem, np.int32), days)
+            assert e.value.code == _lib.ERR_INVALID and word in str(e.value), str(e.value)
+
+        refused([0, 1], [0], "days=0", days=0)
+        refused([0, 1], [0], "days=6", days=6)
+        refused([0, 0], [0], "empty")
+        refused([0, 2, 1], [0, 1], "decrease")
+        refused([0, 1], [4], "outside")
+        refused([0, 2], [1, 0], "ascending")
+        refused([1, 2], [0, 1], "starts at 0")
+        refused(list(range(_lib.GROUPS_MAX + 2)), [0] * (_lib.GROUPS_MAX + 1), "G=")
+        refused([0], [0], "G=")
+        with pytest.raises(ValueError, match="need theta"):
+            model.group_ngm_rows(theta, ev[:, :2], [0, 1], [0])
+        with pytest.raises(TypeError, match="integer"):
+            model.group_ngm_rows(theta, ev.astype(np.float64), [0, 1], [0])
+        with pytest.raises(ValueError, match="members holds"):
+            model.group_ngm_rows(theta, ev, [0, 2], [0])
+        assert model._lib.seir_group_ngm_rows(model._ctx, 1, None, None, 1, 1, None, None, None) == _lib.ERR_INVALID
+        assert model.group_ngm_rows(theta, ev, [0, 1], [2], 5).shape == (1, 1, 5, 3)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# through the sampler
+# ---------------------------------------------------------------------------------------------------------------------
+def _weights(case, tab):
+    return G.rt_weights(tab, np.asarray(case["cov"].N, np.float64).reshape(-1))
+
+
+def _want_K(api, case, tab, w, theta, events, D):
+    """theta [n,B,P], events [n,B,M,T,3] of one run -> K [n,B,G,G,D] by the stateless kernel and the NumPy definition."""
+    n, B = theta.shape[:2]
+    with api[0](case["cov"], case["init"], max_chains=1) as model:
+        rows = model.group_ngm_rows(theta.reshape(n * B, -1), events.reshape((n * B,) + events.shape[2:]), tab.offsets, tab.members, D)
+    return G.group_ngm(rows, tab, w).reshape(n, B, tab.G, tab.G, D)
+
+
+def _on(s, case, groups, D, cap, ngm=True):
+    tab = _table(groups)
+    w = _weights(case, tab)
+    _set(s, groups)
+    s.set_group_rt(w)
+    s.reset_rt(D, _weight(case))
+    if ngm:
+        s.set_group_ngm(w, cap)
+    return tab, w
+
+
+def _code(fn, *a):
+    with pytest.raises(_lib.SeirError) as e:
+        fn(*a)
+    return e.value.code
+
+
+SAMPLER = {
+    # name, B, record, n, D
+    "M=3,T=1,int32,B=3,full_burst": ("micro_3x1", 3, True, 5, 1),
+    "M=9,u16,B=8": ("micro_9x64", 8, "u16", 4, 4),
+    "M=65,u16,B=1": ("micro_65x70", 1, "u16", 5, 3),
+    "M=130,int32,B=1,one_draw": ("micro_130x8", 1, True, 1, 8),
+}
+
+
+@pytest.mark.parametrize("case_id", list(SAMPLER))
+def test_the_store_equals_the_definition_on_the_runs_own_draws_and_nothing_else_notices(api, case_id):
+    name, B, record, n, D = SAMPLER[case_id]
+    case, u, ev, cfg, eps = _case(name, B)
+    if name == "micro_65x70":
+        eps = 0.0001
+    groups = _groups_for(case["k"].M)                          # the all-locations group first
+    runs = {}
+    for on in (False, True):
+        model, s = _sampler(api, case, cfg, u, ev, eps, n, record_events=record)
+        with model, s:
+            tab, w = _on(s, case, groups, D, n, ngm=on)
+            tr = s.sample(n, rt=True)
+            runs[on] = (tr, s.rt_summary())
+            if not on:
+                assert _code(s.read_group_ngm, 1) == _lib.ERR_STATE
+                continue
+            K = s.read_group_ngm(n)
+            assert K.dtype == np.float64 and K.shape == (n, B, tab.G, tab.G, D)
+            assert tr.events.dtype == (np.uint16 if record == "u16" else np.int32)
+            assert np.array_equal(_bits(K), _bits(_want_K(api, case, tab, w, tr.theta, tr.events.astype(np.int32), D)))
+            # K[all][h] is the column sum over every destination: group R_t's bits
+            assert np.array_equal(_bits(K[:, :, 0]), _bits(tr.group_curves["rt_by_group"]))
+            assert np.all(np.isfinite(K)) and K.max() > 0.0
+            last = max(n - 2, 0)
+            assert np.array_equal(s.read_group_ngm(n - last, first=last), K[last:])
+            assert s.read_group_ngm(0).shape == (0, B, tab.G, tab.G, D)
+            assert _code(s.read_group_ngm, n + 1) == _lib.ERR_INVALID
+            assert not s.pair_timeouts().any()
+    _same_bits(runs[True][0], runs[False][0])
+    _same_rt_run((runs[True][1], runs[True][0].rt), (runs[False][1], runs[False][0].rt))
+    assert np.array_equal(runs[True][0].group_curves["rt_by_group"], runs[False][0].group_curves["rt_by_group"])
+
+
+def test_cuts_into_calls_batches_halves_skew_and_repeats_do_not_matter(api):
+    """Two bursts in the two halves of the buffer; the same slots in ragged calls; a staging bound of 1 KiB (one slot per
+    batch) and of 40 KiB (a few); under debug_skew; with the R_it draw store on; and once more: the same bits."""
+    case, u, ev, cfg, eps = _case("micro_20x60", 3)
+    n, D = 7, 6
+    groups = _groups_for(20)
+    res = {}
+    for tag, kib, skew in (("plain", 0, 0), ("again", 0, 0), ("1KiB", 1, 0), ("40KiB", 40, 0), ("skew", 0, 2)):
+        model, s = _sampler(api, case, cfg, u, ev, eps, 2 * n, skew=skew)
+        with model, s:
+            if kib:
+                model.set_option(rt_staging_kib=kib)
+            tab, w = _on(s, case, groups, D, 2 * n)
+            for first in (0, n):
+                s.reset_trace(at=first)
+                s.run(n)
+                s.rt(first, n)
+            tr = s.read_trace(2 * n)
+            res[tag] = (s.read_group_ngm(2 * n), s.read_group_rt(2 * n), s.rt_summary(), s.read_rt_draws(2 * n), tr)
+            if tag == "plain":
+                assert np.array_equal(_bits(res[tag][0]), _bits(_want_K(api, case, tab, w, tr.theta, tr.events.astype(np.int32), D)))
+                # a second rt reset empties the store; ragged calls fill the same positions
+                s.reset_rt(D, _weight(case))
+                assert _code(s.read_group_ngm, 1) == _lib.ERR_INVALID
+                for first, count in ((0, 3), (3, 1), (4, 2 * n - 4)):
+                    s.rt(first, count)
+                assert np.array_equal(_bits(s.read_group_ngm(2 * n)), _bits(res[tag][0]))
+                # with the R_it draw store: k_rt_trace_keep and the gather run next to it
+                s.reset_rt(D, _weight(case))
+                s.keep_rt_draws(2 * n)
+                s.rt(0, 2 * n)
+                assert np.array_equal(_bits(s.read_group_ngm(2 * n)), _bits(res[tag][0]))
+                assert np.array_equal(s.read_group_rt(2 * n), res[tag][1])
+    for tag in res:
+        _same_bits(res[tag][4], res["plain"][4])
+        assert np.array_equal(_bits(res[tag][0]), _bits(res["plain"][0])), tag
+        assert np.array_equal(res[tag][1], res["plain"][1]), tag
+        _same_rt_run(res[tag][2:4], res["plain"][2:4])
+
+
+def test_chains_keep_their_matrices_however_they_are_sharded_and_thinning_keeps_the_kept_draws(api):
+    case, u, ev, cfg, eps = _case("micro_20x60", 4)
+    n, D, k = 5, 4, 3
+    groups = _groups_for(20)
+    got = []
+    for sl, kw in ((slice(None), {}), (slice(2, None), dict(first_chain_id=2))):
+        model, s = _sampler(api, case, cfg, u[sl], ev[sl], eps, n, **kw)
+        with model, s:
+            _on(s, case, groups, D, n)
+            s.sample(n, rt=True)
+            got.append(s.read_group_ngm(n))
+    assert np.array_equal(_bits(got[0][:, 2:]), _bits(got[1]))
+    model, s = _sampler(api, case, cfg, u, ev, eps, n, thin=k)
+    with model, s:
+        tab, w = _on(s, case, groups, D, n)
+        kept = s.sample(n, rt=True)
+        K = s.read_group_ngm(n)
+    model, s = _sampler(api, case, cfg, u, ev, eps, n * k)
+    with model, s:
+        every = s.sample(n * k)
+    assert np.array_equal(every.events[k - 1::k], kept.events)
+    want = _want_K(api, case, tab, w, every.theta[k - 1::k], every.events[k - 1::k].astype(np.int32), D)
+    assert np.array_equal(_bits(K), _bits(want))
+
+
+def test_a_burst_run_again_after_a_time_out_overwrites_its_own_positions(api):
+    """seir_sampler_debug_fail_handoff (the existing test hook, once) in the middle of overlapped bursts in host batches."""
+    case, u, ev, cfg, eps = _case("micro_20x60", 8)
+    B, nb, burst, D = 8, 5, 4, 5
+    groups = _groups_for(20)
+    model, s = _sampler(api, case, cfg, u, ev, eps, 2 * burst, log=None)
+    with model, s:
+        got = {}
+        tab, w = _on(s, case, groups, D, nb * burst)
+
+        def consume(tr, i):
+            got[i] = (tr.events.copy(), tr.theta.copy(), tr.group_curves["rt_by_group"].copy())
+            if i == 1 and not s.recoveries:                    # while burst 2 or 3 is in flight
+                _lib.check(s._lib.seir_sampler_debug_fail_handoff(s._s, B - 1))
+        s.sample_bursts(nb, burst, consume, rt=True)
+        assert len(s.recoveries) == 1 and sorted(got) == list(range(nb))
+        events = np.concatenate([got[i][0] for i in range(nb)])
+        theta = np.concatenate([got[i][1] for i in range(nb)])
+        K = s.read_group_ngm(nb * burst)
+        assert np.array_equal(_bits(K), _bits(_want_K(api, case, tab, w, theta, events.astype(np.int32), D)))
+        assert np.array_equal(_bits(K[:, :, 0]), _bits(np.concatenate([got[i][2] for i in range(nb)])))
+
+
+def test_state_handling_and_refusals(api):
+    import torch
+    case, u, ev, cfg, eps = _case("micro_65x70", 1)
+    n, D = 3, 3
+    wn = _weight(case)
+    model, s = _sampler(api, case, cfg, u, ev, 0.0001, 1 << 10, record_events="u16")
+    with model, s:
+        a = [list(range(65)), [0, 1, 2], [64]]
+        tab = _table(a)
+        w = _weights(case, tab)
+        assert _code(s.set_group_ngm, np.ones(3), 4) == _lib.ERR_STATE                      # no table
+        _set(s, a)
+        with pytest.raises(ValueError, match="aligned"):
+            s.set_group_ngm(np.ones(3), 4)
+        with pytest.raises(ValueError, match="cap=-1"):
+            s.set_group_ngm(w, -1)
+        assert _code(s.set_group_ngm, w, 4) == _lib.ERR_STATE                               # no rt reset
+        s.set_group_rt(w)
+        s.reset_rt(D, wn)
+        assert _code(s.set_group_ngm, np.full(w.shape, np.nan), 4) == _lib.ERR_INVALID
+        assert _code(s.set_group_ngm, w, (1 << 20) + 1) == _lib.ERR_INVALID
+        s.set_group_ngm(w, n)
+        tr = s.sample(n, rt=True)
+        K = s.read_group_ngm(n)
+        assert np.array_equal(_bits(K), _bits(_want_K(api, case, tab, w, tr.theta, tr.events.astype(np.int32), D)))
+        # the call past cap is refused before any launch, with the draw store's wording; rt is what it was
+        with pytest.raises(_lib.SeirError, match=r"the draw store holds 3 \(seir_sampler_group_ngm\)") as e:
+            s.rt(0, 1)
+        assert e.value.code == _lib.ERR_INVALID
+        assert np.array_equal(_bits(s.read_group_ngm(n)), _bits(K)) and int(s.rt_summary().count[0]) == n
+        assert _code(s.set_group_ngm, w, n + 1) == _lib.ERR_STATE                           # draws have been folded
+        # a second rt reset empties the store
+        s.reset_rt(D, wn)
+        assert _code(s.read_group_ngm, 1) == _lib.ERR_INVALID
+        s.rt(0, n)
+        assert np.array_equal(_bits(s.read_group_ngm(n)), _bits(K))
+        # another D frees it: the product is off, rt runs on
+        s.reset_rt(D + 1, wn)
+        s.rt(0, n)
+        assert _code(s.read_group_ngm, 1) == _lib.ERR_STATE and s._group_ngm_cap == 0
+        # on again for the new window; a new table switches it off
+        s.reset_rt(D + 1, wn)
+        s.set_group_ngm(w, n)
+        s.rt(0, n)
+        assert s.read_group_ngm(n).shape == (n, 1, 3, 3, D + 1)
+        _set(s, [[0], [1]])
+        assert _code(s.read_group_ngm, 1) == _lib.ERR_STATE and s._group_ngm_cap == 0
+        # above half of the free memory: refused, the product is off, rt runs on
+        big = [[m] for m in range(65)]
+        _set(s, big)
+        s.reset_rt(70, wn)
+        cap = 1 << 20
+        assert cap * 65 * 65 * 70 * 8 > torch.cuda.mem_get_info()[0] / 2
+        with pytest.raises(_lib.SeirError, match=r"next-generation matrix needs \d+ bytes .* more than half of the \d+ bytes free") as e:
+            s.set_group_ngm(np.ones(65), cap)
+        assert e.value.code == _lib.ERR_INVALID and s._group_ngm_cap == 0
+        s.rt(0, n)
+        assert s.read_rt_draws(n).shape == (n, 1, 70) and _code(s.read_group_ngm, 1) == _lib.ERR_STATE
+        # off by hand
+        s.reset_rt(D, wn)
+        s.set_group_ngm(np.ones(65), n)
+        s.set_group_ngm(None, 0)
+        s.rt(0, n)
+        assert _code(s.read_group_ngm, 1) == _lib.ERR_STATE
+        assert not s.pair_timeouts().any()
+
+
+def test_nothing_else_notices_the_matrix(api):
+    """A sampler with the matrix on against one that never heard of it, the R_it draw store on and off: chain, summaries,
+    forecast, check, R_t with its order statistics, within / between, the group sums and the group curves, bit for bit."""
+    from tests import test_check_gpu as CG
+    from tests import test_forecast_gpu as FG
+    case, u, ev, cfg, eps = _case("micro_20x60", 3)
+    nb, burst, Hn, Kc, D = 3, 4, 6, 5, 7
+    groups = _groups_for(20)
+    tab = _table(groups)
+    w = _weights(case, tab)
+    for keep in (False, True):
+        runs = {}
+        for on in (False, True):
+            model, s = _sampler(api, case, cfg, u, ev, eps, 2 * burst, log=None)
+            with model, s:
+                got = {}
+                _set(s, groups)
+                s.set_group_rt(w)
+                s.set_group_within_between(True)
+                FG._reset(s, case, Hn)
+                CG._reset(s, case, Kc)
+                s.reset_rt(D, _weight(case))
+                if keep:
+                    s.keep_rt_draws(nb * burst)
+                if on:
+                    s.set_group_ngm(w, nb * burst)
+                s.reset_within_between(D)
+
+                def consume(tr, i, got=got):
+                    got[i] = dict(theta=tr.theta.copy(), events=tr.events.copy(), hmc={k: v.copy() for k, v in tr.hmc.items()},
+                                  moves={mk: {kk: v.copy() for kk, v in mv.items()} for mk, mv in tr.moves.items()},
+                                  rt=tr.rt.copy(),
+                                  **{k: v.copy() for d in (tr.marginals, tr.forecast, tr.check, tr.wb, tr.groups, tr.group_curves)
+                                     for k, v in d.items()})
+                s.sample_bursts(nb, burst, consume, summarize=True, forecast=True, rt=True, check=True, within_between=True,
+                                groups=True)
+                cs, rs, ws = s.check_summary(), s.rt_summary(), s.within_between_summary()
+                runs[on] = (got, s.get_state() + s.get_kernel(), [s.summary(), s.forecast_summary(), cs.moments],
+                            [getattr(cs, k) for k in CG.COUNTS], [rs.count, rs.ref, rs.sum, rs.sumsq, rs.gt1],
+                            [ws.count, ws.defined, ws.ref_w, ws.sum_w, ws.sumsq_w, ws.ref_b, ws.sum_b, ws.gt],
+                            [s.rt_order_stats([0, 5, nb * burst - 1])] if keep else [])
+                if on:
+                    K = s.read_group_ngm(nb * burst)
+                    rg = np.concatenate([got[i]["rt_by_group"] for i in range(nb)])
+                    assert np.array_equal(_bits(K[:, :, 0]), _bits(rg))
+        from types import SimpleNamespace
+        for i in range(nb):
+            a, b = runs[False][0][i], runs[True][0][i]
+            _same_bits(SimpleNamespace(**{k: a[k] for k in ("theta", "events", "hmc", "moves")}),
+                       SimpleNamespace(**{k: b[k] for k in ("theta", "events", "hmc", "moves")}))
+            assert set(a) == set(b)
+            for k in a:
+                if k not in ("theta", "events", "hmc", "moves"):
+                    assert np.array_equal(a[k], b[k], equal_nan=a[k].dtype.kind == "f"), k
+        for x, y in zip(runs[False][1], runs[True][1]):
+            assert np.array_equal(x, y)
+        for ma, mb in zip(runs[False][2], runs[True][2]):
+            for k in ("count", "ref", "sum", "sumsq"):
+                assert np.array_equal(getattr(ma, k), getattr(mb, k)), k
+        for j in (3, 4, 5, 6):
+            for x, y in zip(runs[False][j], runs[True][j]):
+                assert np.array_equal(x, y, equal_nan=np.asarray(x).dtype.kind == "f")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the size users run, and the command line
+# ---------------------------------------------------------------------------------------------------------------------
+def test_uk380_nations(api):
+    """UK-380 x 8 chains x 12 draws, `nations` (315, 32, 22 and 11 members), D = 14, uint16 trace."""
+    case = H.build_case("uk380", 43, alpha_t_sd=0.005)
+    B, n, D = 8, 12, 14
+    u = synth.jitter_params(case["u"], B, scale=0.002, seed=3, T=case["k"].T)
+    ev = np.stack([case["events"]] * B)
+    codes = [str(x) for x in np.load(synth._DATA)["lad19cd"]]
+    tab = G.parse_groups("nations", len(codes), codes)
+    w = _weights(case, tab)
+    model, s = _sampler(api, case, CFG_REF, u, ev, 1.2e-5, n, record_events="u16")
+    with model, s:
+        s.set_groups(tab.offsets, tab.members)
+        s.set_group_rt(w)
+        s.reset_rt(D, _weight(case))
+        s.set_group_ngm(w, n)
+        tr = s.sample(n, rt=True)
+        K = s.read_group_ngm(n)
+        assert K.shape == (n, B, 4, 4, D)
+        assert np.array_equal(_bits(K), _bits(_want_K(api, case, tab, w, tr.theta, tr.events.astype(np.int32), D)))
+        # the nations are a partition: the destinations of a source group add up to its R_t (another order: a bound, from
+        # four non-negative terms each within a few ulp of the exact value)
+        rg = tr.group_curves["rt_by_group"]
+        np.testing.assert_allclose(K.sum(axis=2), rg, rtol=1e-12)
+        share = G.ngm_stats(K[:, 0], rg[:, 0])["local_share"]
+        assert np.all((share > 0.0) & (share <= 1.0))
+        rho = G.spectral_radius(K)
+        assert rho.shape == (n, B, D) and np.all(rho <= K.sum(axis=2).max(axis=2) * (1 + 1e-12))   # at most the largest column sum
+
+
+def test_cli_group_ngm(api, tmp_path):
+    """`--rt 7 --groups nations --groups-rt --summaries only` with `--groups-ngm`, with `--rt-quantiles` too, and without the
+    new flag, on an NI-11 data set whose locations carry codes of three nations."""
+    tmp_path = str(tmp_path)
+    cov = synth.make_covariates("ni11")
+    events, init, _ = synth.simulate_epidemic(cov)
+    M = events.shape[0]
+    codes = ["E0%d" % m for m in range(5)] + ["S1%d" % m for m in range(4)] + ["W06", "W07"]
+    data = os.path.join(tmp_path, "data.h5")
+    inf.write_inference_data(data, cov, events[..., 2], locations=codes)
+    base = ["--rt", "7", "--groups", "nations", "--groups-rt", "--summaries", "only"]
+    plain_path, plain_log = _cli(tmp_path, "plain", data, base)
+    plain = _datasets(plain_path)
+    path, log = _cli(tmp_path, "ngm", data, base + ["--groups-ngm"])
+    got = _datasets(path)
+    qpath, qlog = _cli(tmp_path, "ngmq", data, base + ["--groups-ngm", "--rt-quantiles", "0.05,0.5,0.95"])
+    gotq = _datasets(qpath)
+    assert not any("ngm" in k for k in plain) and "Local share" not in plain_log
+    assert not set(plain) - set(got)
+    for k in plain:                                            # the same seed: the same run
+        assert np.array_equal(plain[k], got[k], equal_nan=plain[k].dtype.kind == "f"), k
+    stats = ["ngm/days", "ngm/first_day", "ngm/count", "ngm/K_mean", "ngm/K_var", "ngm/local_share_mean"]
+    assert sorted(set(got) - set(plain)) == sorted(["samples/ngm_by_group", "samples/ngm_spectral_radius"] + stats)
+    assert {k for k in set(gotq) - set(got) if "ngm" in k} == {"ngm/K_quantiles", "ngm/local_share_quantiles", "ngm/pooled_K_quantiles",
+                                                                 "ngm/pooled_local_share_quantiles", "ngm/pooled_chains"}
+    tab = G.parse_groups("nations", M, codes)
+    K, rg = got["samples/ngm_by_group"], got["samples/R_t_by_group"]
+    assert K.shape == (12, 3, 3, 7) and K.dtype == np.float64 and np.array_equal(K, gotq["samples/ngm_by_group"])
+    np.testing.assert_allclose(K.sum(axis=1), rg, rtol=1e-12)  # a partition: the destinations add up to the group's R_t
+    st = G.ngm_stats(K, rg, (0.05, 0.5, 0.95))
+    for k in ("K_mean", "K_var", "local_share_mean"):
+        assert np.array_equal(got[f"ngm/{k}"], st[k]), k
+    assert got["ngm/days"][0] == 7 and got["ngm/count"][0] == 12
+    assert np.array_equal(got["samples/ngm_spectral_radius"], G.spectral_radius(K))
+    np.testing.assert_allclose(gotq["ngm/K_quantiles"], np.quantile(K, [0.05, 0.5, 0.95], axis=0), rtol=1e-12)
+    np.testing.assert_allclose(gotq["ngm/pooled_K_quantiles"], gotq["ngm/K_quantiles"], rtol=1e-12)       # one chain
+    assert np.array_equal(gotq["ngm/local_share_quantiles"], st["local_share_quantiles"])
+    assert log.count("Local share of R_t by group") == 1 and "largest export" in log and qlog.count("Local share of R_t by group") == 1
