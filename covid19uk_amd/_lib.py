@@ -72,6 +72,8 @@ FORECAST_ID_SHIFT, FORECAST_MAX_CHAIN = 20, 2048   # draw id = (global chain id 
 CHECK_MAX_DAYS = 128          # SEIR_CHECK_MAX_DAYS
 ORDER_STATS_MAX_RANKS = 16    # SEIR_ORDER_STATS_MAX_RANKS
 GROUPS_MAX = 256              # SEIR_GROUPS_MAX
+# csrc/trace_load.h: the codes of a loaded item (LOAD_OK = 0 ...; out[code - 1] of seir_sampler_load_status counts them)
+LOAD_CODES = ("ok", "not an integer", "negative", "over the trace's width", "state below zero", "theta not finite")
 # SEIR_FN_*: the functions of seir_selftest_fn, name -> (op, takes y, has out1)
 SELFTEST_FN = {"fast_log": (0, False, False), "fast_rcp": (1, False, False), "mv_log": (2, False, False),
                "softplus_tab": (3, False, False), "softplus_sigmoid_tab": (4, False, True), "softplus": (5, False, False),
@@ -263,6 +265,10 @@ _SIGNATURES = {
     "seir_group_ngm_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_double_p, ctypes.POINTER(ctypes.c_int32),
                                            ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
                                            ctypes.POINTER(ctypes.c_int32), c_double_p]),
+    # stored draws into trace slots: the rows of a posterior file behind every product; the counters of what was wrong in them
+    "seir_sampler_load_trace": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_double_p,
+                                               c_double_p]),
+    "seir_sampler_load_status": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32]),
 }
 
 _lib = None

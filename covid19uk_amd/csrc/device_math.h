@@ -347,7 +347,19 @@ template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ double dpp_get0(double v) {
     return dpp_mov0<CTRL, ROW_MASK, 0xf>(v);
 }
+// 64-bit integers move as their two halves under the same control word, so the add behind the move carries
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ long long dpp_get0(long long v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned long long)v, CTRL, ROW_MASK, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)((unsigned long long)v >> 32), CTRL, ROW_MASK, 0xf, false);
+    return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
+}
 __device__ __forceinline__ int lane_value(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
+__device__ __forceinline__ long long lane_value(long long v, int l) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned long long)v, l);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)((unsigned long long)v >> 32), l);
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
 __device__ __forceinline__ double lane_value(double v, int l) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l),
                             __builtin_amdgcn_readlane(__double2loint(v), l));

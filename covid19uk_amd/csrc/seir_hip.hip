@@ -1330,6 +1330,12 @@ struct seir_sampler {
     GroupCurve grt, gwb;              // group R_t (one plane, weighted); group within / between (two planes)
     // --- group next-generation matrix (seir_sampler_group_ngm; ngm_kernels.h) ---
     GroupNgm ngm;
+    // --- stored draws into trace slots (seir_sampler_load_trace; trace_load_kernels.h): nothing of it exists before the first load ---
+    double *load_stage = nullptr;     // [load_slots][M T 3 + P] fp64 rows as the file has them: events, then theta (one of allocs)
+    unsigned long long *load_words = nullptr;   // the status words of trace_load.h (one of allocs)
+    int load_slots = 0;               // draws per chunk: min(LOAD_JMAX, LOAD_STAGING_BYTES / a draw's bytes), at least 1
+    hipEvent_t ev_load = nullptr;     // behind the last host-to-device copy of a call
+    std::vector<std::pair<int, int>> load_calls;   // (chain, first) of the calls since the last clear, by tag
 };
 
 // Zeroed device memory, registered in `list` (seir_sampler::allocs: freed with the sampler; Rollout::allocs: also when the length
@@ -1433,6 +1439,7 @@ extern "C" void seir_sampler_destroy(seir_sampler *s) {
     if (s->rt_keep) (void)hipFree(s->rt_keep);
     groups_free(s);
     if (s->fc_ev_steps) (void)hipEventDestroy(s->fc_ev_steps);
+    if (s->ev_load) (void)hipEventDestroy(s->ev_load);
     Work &w = s->ctx->w;
     for (int x = 0; x < 3; ++x) { w.K[x] = nullptr; w.St[x] = nullptr; }
     w.rowtot = w.rngtot = nullptr;
@@ -4156,4 +4163,96 @@ extern "C" int seir_group_ngm_rows(seir_ctx *ctx, int32_t n, const double *theta
         HIP_TRY(hipStreamSynchronize(st));
     }
     return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Stored draws into trace slots (include/seir_hip.h; kernels: trace_load_kernels.h)
+// ---------------------------------------------------------------------------
+#include "trace_load_kernels.h"
+
+static int load_words_clear(seir_sampler *s, hipStream_t st) {
+    HIP_TRY(hipMemsetAsync(s->load_words, 0, sizeof(unsigned long long) * LOAD_ST_FIRST_KEY, st));
+    HIP_TRY(hipMemsetAsync(s->load_words + LOAD_ST_FIRST_KEY, 0xff, sizeof(unsigned long long), st));
+    s->load_calls.clear();
+    return 0;
+}
+
+extern "C" int seir_sampler_load_trace(seir_sampler *s, int32_t chain, int32_t first, int32_t count, const double *theta,
+                                       const double *events) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if (!s->record_events)
+        return fail(SEIR_ERR_STATE, "sampler was created with record_events=0: there is no event trace to load stored draws into");
+    const int B = s->cfg.B;
+    if (chain < 0 || chain >= B) return fail(SEIR_ERR_INVALID, "chain=%d outside [0, %d)", chain, B);
+    if (first < 0 || count < 0 || (long long)first + count > s->cfg.cap)
+        return fail(SEIR_ERR_INVALID, "trace range [%d,%lld) outside capacity %d", first, (long long)first + count, s->cfg.cap);
+    if (count == 0) return 0;
+    if (!theta || !events) return fail(SEIR_ERR_INVALID, "null pointer");
+    seir_ctx *ctx = s->ctx;
+    const LaunchCfg l = whole(ctx, B);
+    const Dims &d = l.d;
+    const size_t ev_draw = (size_t)d.M * d.T * 3, draw = ev_draw + (size_t)d.P;
+    if ((unsigned long long)count * std::max(ev_draw, (size_t)d.P) >= (1ull << (LOAD_KEY_BITS - 3)))
+        return fail(SEIR_ERR_INVALID, "count=%d: the call's %zu items per draw do not fit the key of the first bad item", count,
+                    std::max(ev_draw, (size_t)d.P));
+    if (!s->load_stage) {                              // the first load of this sampler
+        const int slots = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(LOAD_JMAX, s->cfg.cap),
+                                                                    LOAD_STAGING_BYTES / (draw * sizeof(double))));
+        if (!s->ev_load) HIP_TRY(hipEventCreateWithFlags(&s->ev_load, hipEventDisableTiming));
+        double *stage = nullptr;
+        S_ALLOC(allocs, stage, (size_t)slots * draw);
+        const bool words = !s->load_words;
+        if (words) S_ALLOC(allocs, s->load_words, (size_t)LOAD_ST_FIRST_KEY + 1);
+        if (rc) return rc;
+        HIP_TRY(hipStreamSynchronize(nullptr));        // the allocations are zeroed on the null stream, which this one does not wait for
+        if (words && (rc = load_words_clear(s, l.st))) return rc;
+        s->load_stage = stage;
+        s->load_slots = slots;
+    }
+    // the call's tag: the number of calls since the last clear; past 2^20 - 1 they share the last one
+    const size_t tag = std::min<size_t>(s->load_calls.size(), ((size_t)1 << 20) - 1);
+    if (tag == s->load_calls.size()) s->load_calls.emplace_back(chain, first);
+    LoadArgs a{};
+    a.status = s->load_words;
+    a.tag = (unsigned long long)tag << LOAD_KEY_BITS;
+    a.chain = chain;
+    for (int j0 = 0; j0 < count; j0 += s->load_slots) {
+        const int nj = std::min(s->load_slots, count - j0);
+        double *st_ev = s->load_stage, *st_th = s->load_stage + (size_t)s->load_slots * ev_draw;
+        HIP_TRY(hipMemcpyAsync(st_ev, events + (size_t)j0 * ev_draw, sizeof(double) * nj * ev_draw, hipMemcpyHostToDevice, l.st));
+        HIP_TRY(hipMemcpyAsync(st_th, theta + (size_t)j0 * d.P, sizeof(double) * nj * d.P, hipMemcpyHostToDevice, l.st));
+        HIP_TRY(hipEventRecord(s->ev_load, l.st));
+        a.ev = st_ev; a.theta = st_th; a.first = first + j0; a.j0 = j0;
+        const dim3 grid((d.M + LOAD_ROWS - 1) / LOAD_ROWS, nj), block(64 * LOAD_ROWS);
+        if (s->cfg.ev16) hipLaunchKernelGGL(k_trace_load<1>, grid, block, 0, l.st, d, ctx->c, a, (void *)s->ch.tr_events, B);
+        else hipLaunchKernelGGL(k_trace_load<0>, grid, block, 0, l.st, d, ctx->c, a, (void *)s->ch.tr_events, B);
+        hipLaunchKernelGGL(k_trace_load_theta<LOAD_THETA_THREADS>, dim3(nj), dim3(LOAD_THETA_THREADS), 0, l.st, d, a, s->ch.tr_theta, s->ch.tr_hmc, s->ch.tr_mv, B);
+        HIP_TRY(hipGetLastError());
+    }
+    // the host buffers may be reused once the last copy is done; the kernels behind it are not waited for
+    HIP_TRY(hipEventSynchronize(s->ev_load));
+    return 0;
+}
+
+extern "C" int seir_sampler_load_status(seir_sampler *s, uint64_t out[8], int32_t clear) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if (!out) return fail(SEIR_ERR_INVALID, "null pointer");
+    for (int i = 0; i < LOAD_ST_WORDS; ++i) out[i] = 0;
+    if (!s->load_words) return 0;                      // nothing was ever loaded
+    hipStream_t st = s->ctx->stream;
+    unsigned long long w[LOAD_ST_FIRST_KEY + 1];
+    HIP_TRY(hipMemcpyAsync(w, s->load_words, sizeof(w), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int i = 0; i < LOAD_ST_FIRST_KEY; ++i) out[i] = w[i];
+    if (w[LOAD_ST_FIRST_KEY] != ~0ull) {
+        const size_t tag = (size_t)(w[LOAD_ST_FIRST_KEY] >> LOAD_KEY_BITS);
+        out[LOAD_ST_FIRST_KEY] = w[LOAD_ST_FIRST_KEY] & ((1ull << LOAD_KEY_BITS) - 1);
+        if (tag < s->load_calls.size()) {
+            out[LOAD_ST_CHAIN] = (uint64_t)s->load_calls[tag].first;
+            out[LOAD_ST_FIRST] = (uint64_t)s->load_calls[tag].second;
+        }
+    }
+    return clear ? load_words_clear(s, st) : 0;
 }

@@ -14,6 +14,7 @@ from __future__ import annotations
 import os
 import sys
 import time
+import types
 
 import numpy as np
 
@@ -113,7 +114,7 @@ class Posterior:
     the int8 enum {FALSE = 0, TRUE = 1}."""
 
     def __init__(self, filename, M, T, mmax, num_samples, burst=100, summaries="off", forecast=None, rt=None, check=None,
-                 within_between=None, groups=None, group_curves=None):
+                 within_between=None, groups=None, group_curves=None, results=True):
         """`summaries` ("off" | "on" | "only", Mcmc.summaries / --summaries): with "on" and "only" the per-draw marginals
         samples/seir_by_day [n,T,3], samples/seir_by_location [n,M,3], samples/state_by_day [n,T,3] (int64) are written
         with every burst and `write_summary` adds summaries/* at the end of the run; with "only" samples/seir is not
@@ -144,7 +145,10 @@ class Posterior:
         `group_curves` ({"rt": (D, n)} and / or {"within_between": (D, n)} or None; Mcmc.groups_rt,
         Mcmc.groups_within_between; needs `groups`): samples/R_t_by_group [n,G,D], samples/within_pressure_by_group and
         samples/between_pressure_by_group [n,G,D] (float64), one row per kept draw of the sampling phase, and
-        `write_group_rt`, `write_group_within_between` add the group_* datasets of rt/ and within_between/."""
+        `write_group_rt`, `write_group_within_between` add the group_* datasets of rt/ and within_between/.
+
+        `results` (False: the output of `posterior.replay`): no results/* and no samples/seir -- a replay has no kernel
+        results and its event tensors are the input's."""
         self.filename = filename
         self.use_h5 = not str(filename).endswith(".npz") and hdf5io.available()
         self.shapes = {
@@ -166,6 +170,10 @@ class Posterior:
             self.shapes[f"results/{key}/target_log_prob"] = ()
             self.shapes[f"results/{key}/proposed_delta"] = (4, mmax)
             self.dtypes[f"results/{key}/is_accepted"] = np.bool_
+        if not results:
+            for key in [k for k in self.shapes if k.startswith("results/") or k == "samples/seir"]:
+                del self.shapes[key]
+            self.dtypes = {k: v for k, v in self.dtypes.items() if k in self.shapes}
         self.num_samples = int(num_samples)
         self.rows = {}                                     # datasets with another number of rows than num_samples
         if forecast is not None:
@@ -239,10 +247,11 @@ class Posterior:
             for kk, vv in v.items():
                 self.write(f"results/{k}/{kk}", vv, first_dim_offset)
 
-    def create_dataset(self, name, data):
-        data = np.asarray(data)
+    def create_dataset(self, name, data, dtype=None):
+        """A dataset of its own, float64 unless `dtype` says otherwise (fixed-length strings keep their type)."""
+        data = np.asarray(data) if dtype is None else np.asarray(data, dtype)
         if self.use_h5:
-            self._file.create_dataset("/" + name, data.shape, data.dtype if data.dtype.kind == "S" else np.float64)
+            self._file.create_dataset("/" + name, data.shape, data.dtype if data.dtype.kind == "S" or dtype is not None else np.float64)
             self._file.write("/" + name, data)
         else:
             self._extra[name] = data
@@ -440,6 +449,21 @@ def draws_to_dict(theta, events, chain, marginals=None):
     }
     if events is not None:
         out["seir"] = events[:, chain] if events.dtype.kind in "iu" else events[:, chain].astype(DTYPE)   # Posterior.write converts
+    if marginals is not None:
+        out["seir_by_day"] = marginals["events_by_day"][:, chain]
+        out["seir_by_location"] = marginals["events_by_location"][:, chain]
+        out["state_by_day"] = marginals["state_by_day"][:, chain]
+    return out
+
+
+def theta_to_dict(th, M, T, marginals=None, chain=0):
+    """The parameters' datasets of `draws_to_dict` from one chain's theta [n,P], and the three marginal datasets of `chain`
+    when `marginals` (Trace.marginals) is given: what a replay writes per burst."""
+    out = {
+        "psi": th[:, 0], "sigma_space": th[:, 1], "beta_area": th[:, 2], "gamma0": th[:, 3],
+        "gamma1": th[:, 4], "alpha_0": th[:, 5], "alpha_t": th[:, 6:6 + T - 1],
+        "spatial_effect": th[:, 6 + T - 1:6 + T - 1 + M],
+    }
     if marginals is not None:
         out["seir_by_day"] = marginals["events_by_day"][:, chain]
         out["seir_by_location"] = marginals["events_by_location"][:, chain]
@@ -723,18 +747,13 @@ def _stack(bursts, *shape):
     return np.concatenate(bursts) if bursts else np.empty((0,) + shape)
 
 
-def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_step_size=False, forecast_calendar=None,
-             seed=0, rt_weight=None, check_calendar=None, groups=None, population=None):
-    """The windowed schedule of inference.py:303-470: fast 200, slow 25*2^k (k<6), fast 50,
-    then num_bursts x num_burst_samples with the kernel fixed.  Every draw of the warm-up is
-    written, as in the reference (its running variance is formed from every draw of a window);
-    the sampling phase keeps every `thin`-th sweep: num_burst_samples kept draws per burst from
-    num_burst_samples * thin sweeps (inference.py:455), thinned on the device.
-
-    What each option adds is said at its record below, a product's three parts side by side: begin() -- the reset behind
-    the warm-up, the draw store where quantiles are on; flush(tr, burst) -- what must outlive the pinned view copied, its
-    datasets written at its row offset, what the end needs kept (burst is None in the warm-up); finish() -- the blocking
-    summary read, the write_* calls and the log line.  A product that is off has no record: nothing of it is called."""
+def product_records(sampler, config, posteriors, log=sys.stderr, forecast_calendar=None, seed=0, rt_weight=None,
+                    check_calendar=None, groups=None, population=None, total=None, results=True):
+    """What `run_mcmc` and `posterior.replay.replay_files` share: the modes resolved and refused before the first call on the
+    sampler, the products' records (begin, flush, finish) in the order of the resets and the write-up, the keywords of the
+    warm-up's and the sampling phase's draws, the diagnostics' marks and the row bookkeeping.  `total`: the kept draws per
+    chain the products will see (default num_bursts x num_burst_samples: what sizes the draw stores); `results=False`: a
+    burst's flush writes the parameters' rows and the marginals only (a replay has no kernel results and no event tensor)."""
     # 1. resolve the modes and refuse what cannot run -- before the first call on the sampler
     s, T = sampler, getattr(sampler, "T", None)
     thin = thin_interval(config)
@@ -760,6 +779,7 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     groups_ngm = G_mod.switch(config.get("groups_ngm"), "groups_ngm")
     G_mod.require_ngm(groups, groups_ngm, rt_days, groups_rt)
     nb, ns = int(config["num_bursts"]), int(config["num_burst_samples"])
+    total = nb * ns if total is None else int(total)        # kept draws per chain that the products will see
     chain_ids = [getattr(sampler, "first_chain_id", 0) + c for c in range(sampler.B)]
     warm_kw, burst_kw = {}, {}                              # the keywords of the warm-up's and the sampling phase's draws
     # `offset` counts every written draw, `kept` the sampling phase's: the row of every product's per-draw datasets (a field is
@@ -832,7 +852,7 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
         def fc_begin():
             s.reset_forecast(horizon, forecast_calendar[0], forecast_calendar[1], seed)   # once: the sampling phase
             if fq_probs:
-                s.keep_forecast_draws(nb * ns)              # the draw store of the quantiles: every kept draw of the phase
+                s.keep_forecast_draws(total)              # the draw store of the quantiles: every kept draw of the phase
 
         def fc_finish():
             fs = s.forecast_summary()
@@ -842,13 +862,13 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
             print(f"Forecast: {horizon} day(s) from day {s.T} for {int(fs.count.min()) if len(fs.count) else 0} kept draw(s) per "
                   f"chain, formed on the device ({'random-walk' if walk else 'held'} baseline); forecast/* and "
                   "samples/forecast_* written", file=log, flush=True)
-            if fq_probs and nb * ns:
+            if fq_probs and total:
                 own = s.forecast_quantiles(fq_probs)                        # [K,B,3,M,H]
                 pooled = s.forecast_quantiles(fq_probs, pooled=True)        # [K,3,M,H]
                 for c, post in enumerate(posteriors):
                     post.write_forecast_quantiles(fq_probs, own[:, c], pooled, chain_ids)
                 print(f"Forecast quantiles: {', '.join(f'{p:g}' for p in fq_probs)} of cases, cumulative cases and prevalence per "
-                      f"location and forecast day, exact over {nb * ns} kept draw(s) per chain and pooled over the {s.B} "
+                      f"location and forecast day, exact over {total} kept draw(s) per chain and pooled over the {s.B} "
                       "chain(s) of this process, selected on the device; forecast/*_quantiles written", file=log, flush=True)
         records.append((fc_begin, writes("forecast"), fc_finish))
 
@@ -865,7 +885,7 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
         def rt_begin():
             s.reset_rt(rt_days, rt_weight)                  # once: the sampling phase
             if rq_probs:
-                s.keep_rt_draws(nb * ns)                    # the draw store of the quantiles: every kept draw of the phase
+                s.keep_rt_draws(total)                    # the draw store of the quantiles: every kept draw of the phase
 
         def rt_flush(tr, burst):
             if getattr(tr, "rt", None) is not None:
@@ -879,14 +899,14 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
                 post.write_rt(rt_days, s.T - rt_days, rs.count[c], mean[c], var[c], prob[c])
             r_t = _stack(rt_draws, s.B, rt_days)
             print(rt_run_line(rt_days, s.T, r_t, prob), file=log, flush=True)
-            if rq_probs and nb * ns:
+            if rq_probs and total:
                 own = s.rt_quantiles(rq_probs)                              # [K,B,D,M]
                 pooled = s.rt_quantiles(rq_probs, pooled=True)              # [K,D,M]
                 nat = draw_quantiles(r_t, rq_probs)                         # [K,B,D]: costs nothing here
                 pnat = draw_quantiles(r_t.reshape(-1, rt_days), rq_probs)   # [K,D]
                 for c, post in enumerate(posteriors):
                     post.write_rt_quantiles(rq_probs, own[:, c], pooled, chain_ids, nat[:, c], pnat)
-                print(rt_quantiles_run_line(rq_probs, rt_days, s.T, nb * ns, s.B, own), file=log, flush=True)
+                print(rt_quantiles_run_line(rq_probs, rt_days, s.T, total, s.B, own), file=log, flush=True)
         records.append((rt_begin, rt_flush, rt_finish))
 
     # With Mcmc.check = K (`check_mode`) the last K days are simulated again from every kept draw of the sampling phase and
@@ -990,7 +1010,7 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
                     post.write_group_rt(*G_mod.curve_moments(rg[:, c]), None if q is None else (q[0][:, c], q[1]))
                 print(G_mod.curve_run_line("R_t", groups, rg, "samples/R_t_by_group and rt/group_*"), file=log, flush=True)
             if groups_ngm:
-                K = s.read_group_ngm(nb * ns) if nb * ns else np.empty((0, s.B, groups.G, groups.G, rt_days))   # [n,B,G,G,D]
+                K = s.read_group_ngm(total) if total else np.empty((0, s.B, groups.G, groups.G, rt_days))   # [n,B,G,G,D]
                 rg = _stack(grp_rt, s.B, groups.G, rt_days)     # [n,B,G,D]: the denominator of the local share
                 part = G_mod.is_partition(groups, s.M)
                 pooled = None
@@ -1012,7 +1032,7 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
                                            groups, share, "samples/*_pressure_by_group and within_between/group_*"),
                       file=log, flush=True)
         # the store is sized behind the rt reset (the rt record's begin, which runs first) and the switch of group R_t
-        grp = ((lambda: s.set_group_ngm(rt_w, nb * ns)) if groups_ngm else (lambda: None), grp_flush, grp_finish)
+        grp = ((lambda: s.set_group_ngm(rt_w, total)) if groups_ngm else (lambda: None), grp_flush, grp_finish)
         records.append(grp)
 
     # With Mcmc.within_between = D (`within_between_mode`) the within/between pressure shares of every kept draw of the
@@ -1041,6 +1061,10 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
         for _, product_flush, _ in flush_order:
             product_flush(tr, burst)
         for c, post in enumerate(posteriors):
+            if not results:                                 # a replay: the parameters' rows and the marginals, nothing else
+                post.write_samples(theta_to_dict(tr.theta[:, c], s.M, s.T, None if summaries == "off" else tr.marginals, c),
+                                   first_dim_offset=rows["offset"])
+                continue
             post.write_samples(draws_to_dict(tr.theta, tr.events, c, **({} if summaries == "off" else dict(marginals=tr.marginals))),
                                first_dim_offset=rows["offset"])
             post.write_results(trace_to_dict(tr, c), first_dim_offset=rows["offset"])
@@ -1048,6 +1072,28 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
         if burst is not None:
             rows["kept"] += tr.theta.shape[0]
         return tr
+
+    return types.SimpleNamespace(records=records, flush=flush, warm_kw=warm_kw, burst_kw=burst_kw, marks=marks, thin=thin,
+                                 nb=nb, ns=ns, rows=rows)
+
+
+def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_step_size=False, forecast_calendar=None,
+             seed=0, rt_weight=None, check_calendar=None, groups=None, population=None):
+    """The windowed schedule of inference.py:303-470: fast 200, slow 25*2^k (k<6), fast 50,
+    then num_bursts x num_burst_samples with the kernel fixed.  Every draw of the warm-up is
+    written, as in the reference (its running variance is formed from every draw of a window);
+    the sampling phase keeps every `thin`-th sweep: num_burst_samples kept draws per burst from
+    num_burst_samples * thin sweeps (inference.py:455), thinned on the device.
+
+    What each option adds is said at its record below, a product's three parts side by side: begin() -- the reset behind
+    the warm-up, the draw store where quantiles are on; flush(tr, burst) -- what must outlive the pinned view copied, its
+    datasets written at its row offset, what the end needs kept (burst is None in the warm-up); finish() -- the blocking
+    summary read, the write_* calls and the log line.  A product that is off has no record: nothing of it is called."""
+    # 1. resolve the modes and refuse what cannot run -- before the first call on the sampler (product_records)
+    pr = product_records(sampler, config, posteriors, log=log, forecast_calendar=forecast_calendar, seed=seed, rt_weight=rt_weight,
+                         check_calendar=check_calendar, groups=groups, population=population)
+    records, flush, warm_kw, burst_kw, marks, thin, nb, ns, rows = (pr.records, pr.flush, pr.warm_kw, pr.burst_kw, pr.marks,
+                                                                    pr.thin, pr.nb, pr.ns, pr.rows)
 
     # 2. warm up
     sampler.set_thin(1)
@@ -1170,25 +1216,12 @@ def launch_forms(lay, device_arg, hmc="auto", moves="auto", env=os.environ):
            ("paired-launch" if shared else "paired") if moves == "auto" else moves
 
 
-def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool_step_size=False, init_jitter=0.0,
-         events_dtype="auto", hmc="auto", moves="auto", thin=None, summaries=None, diagnostics=None, diagnostics_batch=None,
-         forecast=None, forecast_walk=None, rt=None, check=None, forecast_quantiles=None, within_between=None,
-         rt_quantiles=None, groups=None, groups_rt=None, groups_within_between=None, groups_ngm=None):
-    """Constructs and runs the MCMC (covid19uk/inference/inference.py:473-608).
-
-    Multi-GPU (SURVEY.md 8e): launched as one process per GPU, every rank runs `num_chains` chains with
-    global ids rank*num_chains ... (the Philox streams are keyed by the global id, so the draws of chain c
-    do not depend on how the job is sharded) and writes its own posterior_chain{c}.hd5; there is no
-    data-path collective.  `pool_step_size` adds the one optional exchange: an all_gather of one float64
-    per chain after warm-up.  `thin` overrides config["thin"] (every rank is given the same value), `summaries`
-    config["summaries"] (`summaries_mode`), `diagnostics` / `diagnostics_batch` config["diagnostics"] /
-    config["diagnostics_batch"] (`diagnostics_mode`), `forecast` / `forecast_walk` config["forecast"] /
-    config["forecast_walk"] (`forecast_mode`), `forecast_quantiles` config["forecast_quantiles"]
-    (`forecast_quantiles_mode`), `rt` config["rt"] (`rt_mode`), `check` config["check"] (`check_mode`), `within_between`
-    config["within_between"] (`within_between_mode`), `rt_quantiles` config["rt_quantiles"] (`rt_quantiles_mode`), `groups`
-    config["groups"] (`posterior.groups.parse_groups`: "nations" or a mapping name -> members), `groups_rt` config["groups_rt"]
-    and `groups_within_between` config["groups_within_between"] (on / off; `posterior.groups.require_curves`), `groups_ngm`
-    config["groups_ngm"] (on / off; `posterior.groups.require_ngm`)."""
+def resolve_products(config, thin=None, summaries=None, diagnostics=None, diagnostics_batch=None, forecast=None, forecast_walk=None,
+                     rt=None, check=None, forecast_quantiles=None, within_between=None, rt_quantiles=None, groups=None, groups_rt=None,
+                     groups_within_between=None, groups_ngm=None):
+    """The Mcmc section with the command line's overrides applied, every product option resolved by its `*_mode` function
+    and refused here where it cannot run -- before any GPU call -- and what `mcmc` and `posterior.replay` need of it next to
+    the section: the windows, the horizon, the group specification and the group switches."""
     wb_days = 0
     if within_between is not None or "within_between" in config:
         wb_days = within_between_mode(config, within_between)   # refused here: before any GPU call
@@ -1240,6 +1273,70 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
         config = dict(config, groups_rt=True)
     if grp_wb_on:
         config = dict(config, groups_within_between=True)
+    return config, types.SimpleNamespace(wb_days=wb_days, check_days=check_days, rt_days=rt_days, horizon=horizon, group_spec=group_spec,
+                                         grp_rt_on=grp_rt_on, grp_wb_on=grp_wb_on, grp_ngm_on=grp_ngm_on)
+
+
+def posterior_kwargs(config, opt, group_table, kept):
+    """The keywords of `Posterior` for the products that are on, `kept` rows in the per-draw datasets of the sampling phase."""
+    horizon, rt_days, check_days, wb_days = opt.horizon, opt.rt_days, opt.check_days, opt.wb_days
+    return dict(**({} if config["summaries"] == "off" else dict(summaries=config["summaries"])),
+                **(dict(forecast=(horizon, kept)) if horizon else {}),
+                **(dict(rt=(rt_days, kept)) if rt_days else {}),
+                **(dict(check=(check_days, kept)) if check_days else {}),
+                **(dict(within_between=(wb_days, kept)) if wb_days else {}),
+                **(dict(groups=group_table.G) if group_table is not None else {}),
+                **(dict(group_curves={k: (d, kept) for k, on, d in (("rt", opt.grp_rt_on, rt_days), ("within_between", opt.grp_wb_on, wb_days))
+                                      if on}) if opt.grp_rt_on or opt.grp_wb_on else {}))
+
+
+def product_inputs(cov, dates, T, opt, seed, group_table):
+    """What the products need beyond the sampler, as keywords of `run_mcmc` / `product_records`: the calendars of the
+    forecast and of the check, the national weights, the seed, the group table and the population."""
+    kw = {}
+    if opt.horizon:
+        from ..posterior.predict import forecast_calendar
+        kw = dict(forecast_calendar=forecast_calendar(cov, dates, T, opt.horizon), seed=seed)
+    if opt.rt_days:
+        N = np.asarray(cov.N, dtype=np.float64).reshape(-1)
+        kw["rt_weight"] = N / N.sum()                       # reproduction_number.py:82-83
+    if opt.check_days:
+        from ..posterior.predict import check_calendar
+        kw["check_calendar"] = check_calendar(cov, dates, T, opt.check_days)
+        kw["seed"] = seed
+    if group_table is not None:
+        kw["groups"] = group_table
+        if opt.grp_rt_on:
+            kw["population"] = np.asarray(cov.N, dtype=np.float64).reshape(-1)
+    return kw
+
+
+def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool_step_size=False, init_jitter=0.0,
+         events_dtype="auto", hmc="auto", moves="auto", thin=None, summaries=None, diagnostics=None, diagnostics_batch=None,
+         forecast=None, forecast_walk=None, rt=None, check=None, forecast_quantiles=None, within_between=None,
+         rt_quantiles=None, groups=None, groups_rt=None, groups_within_between=None, groups_ngm=None):
+    """Constructs and runs the MCMC (covid19uk/inference/inference.py:473-608).
+
+    Multi-GPU (SURVEY.md 8e): launched as one process per GPU, every rank runs `num_chains` chains with
+    global ids rank*num_chains ... (the Philox streams are keyed by the global id, so the draws of chain c
+    do not depend on how the job is sharded) and writes its own posterior_chain{c}.hd5; there is no
+    data-path collective.  `pool_step_size` adds the one optional exchange: an all_gather of one float64
+    per chain after warm-up.  `thin` overrides config["thin"] (every rank is given the same value), `summaries`
+    config["summaries"] (`summaries_mode`), `diagnostics` / `diagnostics_batch` config["diagnostics"] /
+    config["diagnostics_batch"] (`diagnostics_mode`), `forecast` / `forecast_walk` config["forecast"] /
+    config["forecast_walk"] (`forecast_mode`), `forecast_quantiles` config["forecast_quantiles"]
+    (`forecast_quantiles_mode`), `rt` config["rt"] (`rt_mode`), `check` config["check"] (`check_mode`), `within_between`
+    config["within_between"] (`within_between_mode`), `rt_quantiles` config["rt_quantiles"] (`rt_quantiles_mode`), `groups`
+    config["groups"] (`posterior.groups.parse_groups`: "nations" or a mapping name -> members), `groups_rt` config["groups_rt"]
+    and `groups_within_between` config["groups_within_between"] (on / off; `posterior.groups.require_curves`), `groups_ngm`
+    config["groups_ngm"] (on / off; `posterior.groups.require_ngm`)."""
+    config, opt = resolve_products(config, thin=thin, summaries=summaries, diagnostics=diagnostics, diagnostics_batch=diagnostics_batch,
+                                   forecast=forecast, forecast_walk=forecast_walk, rt=rt, check=check,
+                                   forecast_quantiles=forecast_quantiles, within_between=within_between, rt_quantiles=rt_quantiles,
+                                   groups=groups, groups_rt=groups_rt, groups_within_between=groups_within_between,
+                                   groups_ngm=groups_ngm)
+    wb_days, check_days, rt_days, horizon = opt.wb_days, opt.check_days, opt.rt_days, opt.horizon
+    group_spec, grp_rt_on, grp_wb_on, grp_ngm_on = opt.group_spec, opt.grp_rt_on, opt.grp_wb_on, opt.grp_ngm_on
     lay = job_layout(num_chains, device)                    # before any GPU call
     cov, cases, dates = read_inference_data(data_file)
     # the table against the input's locations, and groups without a source: refused here, before any GPU call
@@ -1290,33 +1387,12 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
 
     total = lay["world"] * B
     names = [chain_file_name(output_file, lay["first_chain_id"] + c, total) for c in range(B)]
+    kept = int(config["num_burst_samples"]) * int(config["num_bursts"])
     posteriors = [Posterior(name, M, T, cfg["m"], num_samples, burst=int(config["num_burst_samples"]),
-                            **({} if config["summaries"] == "off" else dict(summaries=config["summaries"])),
-                            **(dict(forecast=(horizon, int(config["num_burst_samples"]) * int(config["num_bursts"]))) if horizon else {}),
-                            **(dict(rt=(rt_days, int(config["num_burst_samples"]) * int(config["num_bursts"]))) if rt_days else {}),
-                            **(dict(check=(check_days, int(config["num_burst_samples"]) * int(config["num_bursts"]))) if check_days else {}),
-                            **(dict(within_between=(wb_days, int(config["num_burst_samples"]) * int(config["num_bursts"])))
-                               if wb_days else {}),
-                            **(dict(groups=group_table.G) if group_table is not None else {}),
-                            **(dict(group_curves={k: (d, int(config["num_burst_samples"]) * int(config["num_bursts"]))
-                                                  for k, on, d in (("rt", grp_rt_on, rt_days), ("within_between", grp_wb_on, wb_days))
-                                                  if on}) if grp_rt_on or grp_wb_on else {}))
+                            **posterior_kwargs(config, opt, group_table, kept))
                   for name in names]
-    fc_kw = {}
-    if horizon:
-        from ..posterior.predict import forecast_calendar
-        fc_kw = dict(forecast_calendar=forecast_calendar(cov, dates, T, horizon), seed=seed)
-    if rt_days:
-        N = np.asarray(cov.N, dtype=np.float64).reshape(-1)
-        fc_kw["rt_weight"] = N / N.sum()                    # reproduction_number.py:82-83
-    if check_days:
-        from ..posterior.predict import check_calendar
-        fc_kw["check_calendar"] = check_calendar(cov, dates, T, check_days)
-        fc_kw["seed"] = seed
+    fc_kw = product_inputs(cov, dates, T, opt, seed, group_table)
     if group_table is not None:
-        fc_kw["groups"] = group_table
-        if grp_rt_on:
-            fc_kw["population"] = np.asarray(cov.N, dtype=np.float64).reshape(-1)
         for post in posteriors:
             post.write_groups(group_table, cov.N, initial_state)
     run_mcmc(sampler, config, posteriors, pool_step_size=pool_step_size and total > 1, **fc_kw)

@@ -1181,6 +1181,99 @@ class ChainSampler:
             if p.marks_behind and mark is not None:
                 self.mark(mark)
 
+    # -- stored draws into trace slots (include/seir_hip.h, "Stored draws into trace slots") --------------------------
+    def _per_chain_draws(self, theta, events, chains):
+        """`theta` [n,B',P] / `events` [n,B',M,T,3] or per-chain lists of [n,P] / [n,M,T,3] as (chain, theta, events) with
+        contiguous float64 arrays, one per chain of `chains` (default 0 .. B'-1)."""
+        if isinstance(theta, (list, tuple)) != isinstance(events, (list, tuple)):
+            raise ValueError("theta and events: both arrays [n,B',...] or both per-chain lists")
+        if isinstance(theta, (list, tuple)):
+            th, ev = list(theta), list(events)
+        else:
+            theta, events = np.asarray(theta), np.asarray(events)
+            if theta.ndim != 3 or events.ndim != 5:
+                raise ValueError(f"need theta [n,B',{self.P}] and events [n,B',{self.M},{self.T},3]")
+            th, ev = [theta[:, c] for c in range(theta.shape[1])], [events[:, c] for c in range(events.shape[1])]
+        chains = list(range(len(th))) if chains is None else [int(c) for c in chains]
+        if not len(th) == len(ev) == len(chains):
+            raise ValueError(f"{len(th)} theta array(s), {len(ev)} event array(s) and {len(chains)} chain(s)")
+        if len(set(chains)) != len(chains) or any(not 0 <= c < self.B for c in chains):
+            raise ValueError(f"chains={chains}: distinct chains of [0, {self.B})")
+        out = []
+        for c, t, e in zip(chains, th, ev):
+            t = np.ascontiguousarray(t, dtype=np.float64)
+            e = np.ascontiguousarray(e, dtype=np.float64)       # integer events, as Trace.events holds them, become fp64 here
+            n = t.shape[0]
+            if t.shape != (n, self.P) or e.shape != (n, self.M, self.T, 3):
+                raise ValueError(f"chain {c}: need theta [n,{self.P}] and events [n,{self.M},{self.T},3], have {t.shape} and {e.shape}")
+            out.append((c, t, e))
+        if len({t.shape[0] for _, t, _ in out}) > 1:
+            raise ValueError("every chain is loaded with the same number of draws")
+        return out
+
+    def load_status(self, clear: bool = False) -> np.ndarray:
+        """The counters of what was wrong in the draws loaded since creation or the last `clear` (blocking): uint64 [8] --
+        cells that are not an integer, negative, over the trace's width; states below zero; theta entries that are not
+        finite; the key of the first bad item, its call's chain and first slot.  All zeros: every loaded slot is a draw the
+        products may be run on."""
+        out = np.zeros(8, np.uint64)
+        _lib.check(self._lib.seir_sampler_load_status(self._s, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), int(bool(clear))))
+        return out
+
+    def _load_error(self, status, n):
+        """The ValueError for a status that is not all zeros: the counts, and the first bad item by category, chain and
+        (draw, location, day, transition)."""
+        key, chain, first = int(status[5]), int(status[6]), int(status[7])
+        flat, code = key >> 3, key & 7
+        names = _lib.LOAD_CODES
+        counts = ", ".join(f"{int(status[q - 1])} {names[q]}" for q in range(1, 6) if status[q - 1])
+        if code == 5:
+            where = f"(draw {flat // self.P}, parameter {flat % self.P})"
+        else:
+            j, r = divmod(flat, self.M * self.T * 3)
+            m, r = divmod(r, self.T * 3)
+            t, x = divmod(r, 3)
+            what = ("S", "E", "I")[x] + f" behind day {t}" if code == 4 else f"day {t}, transition {('S->E', 'E->I', 'I->R')[x]}"
+            where = f"(draw {j}, location {m}, {what})"
+        return ValueError(f"the stored draws cannot be replayed: {counts}; the first bad item is {names[code]} in chain {chain} at "
+                          f"{where} of the {n} draw(s) loaded from slot {first}")
+
+    def load_trace(self, theta, events, first: int = 0, chains=None) -> int:
+        """Put stored draws into trace slots [first, first + n) of `chains` (default: 0 .. B'-1): `theta` [n,B',P] constrained
+        draws and `events` [n,B',M,T,3], or per-chain lists of [n,P] / [n,M,T,3] (file reads need not be copied together).
+        Chain state, sweep counter, thinning, the other slots and chains and every product's accumulators stay as they are.
+        Raises ValueError, before anything else is enqueued, when a draw is not one the products may be run on: a count that
+        is not an integer in the trace's width, a compartment below zero at a day boundary, a theta entry that is not
+        finite -- naming the first such item.  Returns n."""
+        rows = self._per_chain_draws(theta, events, chains)
+        n = rows[0][1].shape[0] if rows else 0
+        if int(first) < 0 or int(first) + n > self.cap:
+            raise ValueError(f"trace range [{int(first)},{int(first) + n}) outside capacity {self.cap}")
+        for c, t, e in rows:
+            _lib.check(self._lib.seir_sampler_load_trace(self._s, c, int(first), n, _dptr(t), _dptr(e)))
+        status = self.load_status(clear=True)
+        if status.any():
+            raise self._load_error(status, n)
+        return n
+
+    def replay(self, theta, events, events_out: bool = False, summarize=False, forecast=False, rt=False, check=False,
+               within_between=False, groups=False) -> Trace:
+        """`sample` without snapshot, reset_trace and run: the stored draws `theta` [n,B,P] / `events` [n,B,M,T,3] (or
+        per-chain lists) are loaded into slots [0, n) of all chains, the products that are asked for or switched on are
+        enqueued behind them in table order, and the trace and the products are read.  `hmc` and `moves` of the result are
+        zeros; `events` is present only with `events_out`.  There is no persistent launch in it and nothing to recover from.
+        The chain does not notice: its state, sweep counter and thinning are what they were."""
+        on = self._burst_products(locals())                 # first statement: the locals are this call's keywords
+        rows = self._per_chain_draws(theta, events, None)
+        if len(rows) != self.B:
+            raise ValueError(f"replay takes the draws of all {self.B} chain(s), have {len(rows)}")
+        n = self.load_trace([t for _, t, _ in rows], [e for _, _, e in rows])
+        self._enqueue_products(on, 0, n)
+        tr = self.read_trace(n, events=events_out)
+        for p, size, _ in on.values():
+            setattr(tr, p.field, getattr(self, p.read)(*(() if p.enqueue else (size,)), n))
+        return tr
+
     def sample_bursts(self, num_bursts: int, burst: int, consume, events: bool = True, summarize=False, marks=None,
                       forecast=False, rt=False, check=False, within_between=False, groups=False):
         """`num_bursts` x `burst` kept draws (`burst * thin` sweeps each) with the burst buffer used as two halves:

@@ -992,6 +992,45 @@ int seir_group_ngm_rows(seir_ctx *ctx, int32_t n, const double *theta, const int
                         const int32_t *offsets, const int32_t *members, double *out);
 
 /* ------------------------------------------------------------------------
+ * Stored draws into trace slots: every product from a posterior file.
+ *
+ * The reference samples once and derives its products afterwards from the stored draws (covid19uk/posterior/thin.py, then
+ * predict.py, reproduction_number.py, within_between.py).  Every product above reads tr_theta and tr_events of trace slots
+ * [first, first + count) and nothing else, and only range-checks the slots: nothing records which of them sweeps have filled.
+ * seir_sampler_load_trace puts the rows of a posterior file (samples/<parameter>, samples/seir) into trace slots, so that
+ * seir_sampler_summarize / _forecast / _rt / _check / _wb run on them as they run behind a sweep.
+ *
+ * THE definition of what a stored cell may hold, of the codes and of the key: csrc/trace_load.h (kernels and their header
+ * comment: csrc/trace_load_kernels.h; NumPy: covid19uk_amd/posterior/replay.py, check_draws).  Events are stored in the
+ * sampler's width (uint16 for record_events == 2, int32 for 1); a cell that is not an integer in [0, width's maximum] is
+ * stored as 0 and counted.  The state S, E, I behind every day (boundaries 1 .. T; boundary T is where the forecast starts)
+ * is formed from the context's initial state in int64 -- a file's counts are bounded by the width alone, unlike the
+ * sampler's own -- and every compartment below zero is counted.  theta is copied bit for bit and its entries that are not
+ * finite are counted; the hmc and moves entries of the slots become zeros.  Integers only: no floating-point arithmetic beyond
+ * the conversion, no floating-point atomics; nothing depends on the launch geometry, the debug skew or the cut into chunks.
+ * A sampler that never calls these entry points allocates and launches exactly what it did before.
+ * ------------------------------------------------------------------------ */
+/* Fills trace slots [first, first + count) of chain `chain`: theta [count][P] constrained draws in the order of
+ * inference.py:541-552 (the file's values), events [count][M][T][3] fp64 counts in the layout of samples/seir.  Host
+ * pointers.  Chain state, the sweep counter, the slot the next sweep records to, the thinning, the other chains' slots and
+ * every product's accumulators stay as they are; a later seir_sampler_reset_trace + _run overwrites the slots as always.
+ * The rows are staged in a device buffer of at most 64 draws and 256 MiB, allocated at the first load, and cross in chunks
+ * (copy, kernels, next chunk) on the context stream.  Returns when the host buffers may be reused: it waits for its copies,
+ * not for its kernels.  count == 0 does nothing.  SEIR_ERR_STATE with record_events == 0; SEIR_ERR_INVALID for a chain outside
+ * [0, B), a range outside the capacity or a NULL pointer with count > 0 -- all before any launch. */
+int seir_sampler_load_trace(seir_sampler *s, int32_t chain, int32_t first, int32_t count, const double *theta,
+                            const double *events);
+/* Blocking.  The counters since creation or since the last call with clear != 0:
+ *   out[0..2]  cells that are not an integer / negative / over the width (LOAD_NOT_INTEGER, _NEGATIVE, _OVER_WIDTH)
+ *   out[3]     (draw, location, boundary, compartment) states below zero
+ *   out[4]     theta entries that are not finite
+ *   out[5]     the smallest key flat_index * 8 + code of a bad item of the first call that had one (flat_index: the item's
+ *              position in that call's events, read as (draw, location, boundary - 1, compartment) for a state, or theta)
+ *   out[6..7]  that call's chain and first
+ * All zeros: every slot loaded is a draw the product kernels may be run on. */
+int seir_sampler_load_status(seir_sampler *s, uint64_t out[8], int32_t clear);
+
+/* ------------------------------------------------------------------------
  * Reproduction number R_it.
  *
  * calc_posterior_rit (covid19uk/posterior/reproduction_number.py:13-44): for each

@@ -1,0 +1,568 @@
+"""Stored draws into trace slots and the replay of every product from them (include/seir_hip.h, "Stored draws into trace
+slots"; covid19uk_amd/csrc/trace_load_kernels.h; `ChainSampler.load_trace`, `.replay`).
+
+Everything here is an equality: the loaded slots against what was loaded, the status words against the NumPy definition
+`posterior.replay.check_draws`, and every product of a replay against the same product of the live run whose draws were
+replayed -- the product kernels read trace slots and nothing else, so the bits are the same or something is wrong."""
+import dataclasses
+
+import numpy as np
+import pytest
+
+from covid19uk_amd import _lib, synth
+from covid19uk_amd.posterior import groups as G
+from covid19uk_amd.posterior import replay as R
+from covid19uk_amd.seir import _dptr
+from oracle import seir_oracle as so
+from tests import helpers as H
+from tests import test_check_gpu as CG
+from tests import test_forecast_gpu as FG
+from tests.test_groups_gpu import _groups_for
+from tests.test_ngm_gpu import _table, _weights
+from tests.test_recovery_gpu import _case, _same_bits
+from tests.test_rt_device_gpu import _weight
+from tests.test_sampler_gpu import CFG_REF, api  # noqa: F401  (fixture)
+from tests.test_summary_gpu import _sampler
+
+pytestmark = pytest.mark.gpu
+
+
+def _feasible(init, n, T, rng, top=6):
+    """n random epidemics [n,M,T,3] (int64) from `init` [M,4] whose compartments never go below zero."""
+    st = [np.tile(np.asarray(init)[:, x].astype(np.int64), (n, 1)) for x in range(3)]
+    M = st[0].shape[1]
+    ev = np.zeros((n, M, T, 3), np.int64)
+    for t in range(T):
+        k = [np.minimum(rng.integers(0, top, size=(n, M)), st[x]) for x in range(3)]
+        st[0] -= k[0]
+        st[1] += k[0] - k[1]
+        st[2] += k[1] - k[2]
+        ev[:, :, t] = np.stack(k, axis=-1)
+    return ev
+
+
+def _theta(rng, shape):
+    th = rng.standard_normal(shape)
+    flat = th.reshape(-1)
+    flat[0], flat[-1] = -0.0, 5e-324                           # copied as bits: a signed zero and a denormal survive
+    return th
+
+
+def _plausible_theta(case, n, B, seed):
+    """[n,B,P] constrained draws near the generating parameters: what a product may be run on."""
+    T = case["k"].T
+    return so.constrain(synth.jitter_params(case["u"], n * B, scale=0.05, seed=seed, T=T)).reshape(n, B, -1)
+
+
+def _same(a, b, path=""):
+    """Bit for bit: arrays by dtype, shape and bytes (NaN payloads included); dataclasses and dicts field by field."""
+    if dataclasses.is_dataclass(a):
+        assert type(a) is type(b), path
+        for f in dataclasses.fields(a):
+            _same(getattr(a, f.name), getattr(b, f.name), f"{path}.{f.name}")
+    elif isinstance(a, dict):
+        assert sorted(a) == sorted(b), path
+        for k in a:
+            _same(a[k], b[k], f"{path}[{k}]")
+    elif isinstance(a, (list, tuple)):
+        assert len(a) == len(b), path
+        for i, (x, y) in enumerate(zip(a, b)):
+            _same(x, y, f"{path}[{i}]")
+    elif a is None or isinstance(a, (int, float, str)):
+        assert a == b, path
+    else:
+        a, b = np.asarray(a), np.asarray(b)
+        assert a.dtype == b.dtype and a.shape == b.shape, (path, a.dtype, b.dtype, a.shape, b.shape)
+        assert np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes(), path
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 1. round trip
+# ---------------------------------------------------------------------------------------------------------------------
+ROUND = {
+    # name, B, n, first, cap: the ids name the branch of k_trace_load they turn
+    "M=1,T=70": ("micro_1x70", 1, 3, 0, 4),
+    "M=3,T=1": ("micro_3x1", 3, 2, 1, 4),
+    "M=3,T=2": ("micro_3x2", 3, 2, 0, 3),
+    "M=9,T=63,rowblock+1": ("micro_9x63", 3, 2, 0, 3),
+    "M=9,T=64,one_chunk": ("micro_9x64", 8, 2, 1, 3),
+    "M=7,T=65,rowblock-1,one_past_a_chunk": ("micro_7x65", 3, 3, 0, 3),
+    "M=65,T=70": ("micro_65x70", 1, 2, 1, 3),
+    "M=3,T=130,two_chunks_and_two_days": ("micro_3x130", 3, 2, 2, 4),
+    "M=520,T=70": ("slow_520x70", 1, 2, 0, 2),
+}
+
+
+@pytest.mark.parametrize("record", [True, "u16"], ids=["int32", "u16"])
+@pytest.mark.parametrize("case_id", list(ROUND))
+def test_loaded_slots_read_back_and_nothing_else_moves(api, case_id, record):
+    name, B, n, first, cap = ROUND[case_id]
+    case, u, ev, cfg, eps = _case(name, B)
+    k = case["k"]
+    rng = np.random.default_rng([k.M, k.T, B])
+    # chains in reverse order, one skipped where there are three
+    chains = [c for c in reversed(range(B)) if not (B >= 3 and c == 1)]
+    res = {}
+    for skew in (0, 2):
+        model, s = _sampler(api, case, cfg, u, ev, eps, cap, record_events=record, skew=skew)
+        with model, s:
+            before = s.sample(cap)                             # every slot holds a draw of the chain
+            state = s.get_state() + s.get_kernel()
+            theta = _theta(np.random.default_rng(5), (n, len(chains), k.P))
+            events = np.stack([_feasible(case["init"], n, k.T, np.random.default_rng([7, c]), top=70000 if record is True else 6)
+                               for c in chains], axis=1)
+            assert s.load_trace(theta, events, first=first, chains=chains) == n
+            assert not s.load_status().any()
+            after = s.read_trace(cap)
+            res[skew] = after
+            assert after.events.dtype == (np.int32 if record is True else np.uint16)
+            sl = slice(first, first + n)
+            assert theta.tobytes() == np.ascontiguousarray(after.theta[sl][:, chains]).tobytes()
+            assert np.array_equal(after.events[sl][:, chains], events)
+            for c in chains:
+                assert not any(v[sl, c].any() for v in after.hmc.values())
+                assert not any(v[sl, c].any() for mv in after.moves.values() for v in mv.values())
+            # the slots and chains that were not named are what the sweeps left
+            keep = np.ones((cap, B), bool)
+            keep[sl, chains] = False
+            _same(before.theta[keep], after.theta[keep])
+            _same(before.events[keep], after.events[keep])
+            for key in before.hmc:
+                _same(before.hmc[key][keep], after.hmc[key][keep])
+            for mk in before.moves:
+                for key in before.moves[mk]:
+                    _same(before.moves[mk][key][keep], after.moves[mk][key][keep])
+            _same(state, s.get_state() + s.get_kernel())       # the chain did not notice
+    _same_bits(res[0], res[2])
+
+
+@pytest.mark.parametrize("record", [True, "u16"], ids=["int32", "u16"])
+def test_counts_at_the_chunk_edges_and_the_last_slot(api, record):
+    case, u, ev, cfg, eps = _case("micro_3x5", 2)
+    k = case["k"]
+    cap = 131
+    model, s = _sampler(api, case, cfg, u, ev, eps, cap, record_events=record)
+    with model, s:
+        for n in (1, 63, 64, 65, 130):                         # LOAD_JMAX = 64 draws per chunk
+            first = cap - n                                    # up to the last slot of the buffer
+            theta = _theta(np.random.default_rng(n), (n, 2, k.P))
+            events = np.stack([_feasible(case["init"], n, k.T, np.random.default_rng([n, c])) for c in range(2)], axis=1)
+            # per-chain lists, integer events as Trace.events holds them
+            s.load_trace([theta[:, 0], theta[:, 1]], [events[:, 0].astype(np.int32), events[:, 1].astype(np.int32)], first=first)
+            tr = s.read_trace(n, first=first)
+            assert theta.tobytes() == tr.theta.tobytes() and np.array_equal(tr.events, events), n
+        s.load_trace(theta[:0], events[:0], first=cap)         # count == 0: a no-op, at the end of the buffer too
+        with pytest.raises(ValueError, match="outside capacity"):
+            s.load_trace(theta[:2], events[:2], first=cap - 1)
+
+
+def _code(lib, *a):
+    return lib.seir_sampler_load_trace(*a)
+
+
+def test_refusals_come_before_any_launch(api):
+    case, u, ev, cfg, eps = _case("micro_3x5", 2)
+    k = case["k"]
+    theta = np.zeros((2, k.P))
+    events = np.zeros((2, k.M, k.T, 3))
+    model, s = _sampler(api, case, cfg, u, ev, eps, 4)
+    with model, s:
+        lib = s._lib
+        assert _code(lib, None, 0, 0, 1, _dptr(theta), _dptr(events)) == _lib.ERR_INVALID and b"null sampler" in lib.seir_last_error()
+        for chain in (-1, 2):
+            assert _code(lib, s._s, chain, 0, 1, _dptr(theta), _dptr(events)) == _lib.ERR_INVALID
+            assert b"outside [0, 2)" in lib.seir_last_error()
+        for first, count in ((-1, 1), (0, -1), (3, 2), (5, 0)):
+            assert _code(lib, s._s, 0, first, count, _dptr(theta), _dptr(events)) == _lib.ERR_INVALID
+            assert b"outside capacity 4" in lib.seir_last_error()
+        assert _code(lib, s._s, 0, 0, 1, None, _dptr(events)) == _lib.ERR_INVALID and b"null pointer" in lib.seir_last_error()
+        assert _code(lib, s._s, 0, 0, 1, _dptr(theta), None) == _lib.ERR_INVALID
+        assert _code(lib, s._s, 0, 4, 0, None, None) == 0      # count == 0 does nothing
+        assert lib.seir_sampler_load_status(s._s, None, 0) == _lib.ERR_INVALID
+        assert lib.seir_sampler_load_status(None, None, 0) == _lib.ERR_INVALID
+        assert not s.load_status().any()                       # nothing was ever loaded
+        with pytest.raises(ValueError, match="distinct chains"):
+            s.load_trace(theta[:, None], events[:, None], chains=[2])
+        with pytest.raises(ValueError, match="need theta"):
+            s.load_trace(theta[:, None, :-1], events[:, None])
+        with pytest.raises(ValueError, match="all 2 chain"):
+            s.replay(theta[:, None], events[:, None])
+    model, s = _sampler(api, case, cfg, u, ev, eps, 4, record_events=False)
+    with model, s:
+        assert _code(s._lib, s._s, 0, 0, 1, _dptr(theta), _dptr(events)) == _lib.ERR_STATE
+        assert b"record_events=0" in s._lib.seir_last_error()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 2. status
+# ---------------------------------------------------------------------------------------------------------------------
+def _load(s, chain, first, theta, events):
+    theta, events = np.ascontiguousarray(theta, np.float64), np.ascontiguousarray(events, np.float64)
+    _lib.check(s._lib.seir_sampler_load_trace(s._s, chain, first, theta.shape[0], _dptr(theta), _dptr(events)))
+
+
+def _want(case, theta, events, width, chain, first):
+    w = R.check_draws(theta, events, case["init"], width)
+    out = np.zeros(8, np.uint64)
+    out[:6] = w
+    if w[5]:
+        out[6], out[7] = chain, first
+    return out
+
+
+@pytest.mark.parametrize("record", [True, "u16"], ids=["int32", "u16"])
+def test_status_equals_the_numpy_definition(api, record):
+    width = 32 if record is True else 16
+    top = 2 ** 31 - 1 if record is True else 65535
+    case, u, ev, cfg, eps = _case("micro_9x70", 2)
+    k = case["k"]
+    M, T, n = k.M, k.T, 3
+    init = np.asarray(case["init"])
+    rng = np.random.default_rng(3)
+    good = _feasible(init, n, T, rng).astype(np.float64)
+    theta = _theta(rng, (n, k.P))
+    model, s = _sampler(api, case, cfg, u, ev, eps, 8, record_events=record)
+    with model, s:
+        def one(th, e, chain=1, first=2, what=""):
+            _load(s, chain, first, th, e)
+            got = s.load_status(clear=True)
+            assert np.array_equal(got, _want(case, th, e, width, chain, first)), (what, got)
+            assert not s.load_status().any(), what             # clear is honoured
+            return got
+
+        assert not one(theta, good, what="good").any()
+        # each category alone at the first cell, the last cell and either side of the 64-day chunk edge
+        cells = ((0, 0, 0, 0), (n - 1, M - 1, T - 1, 2), (1, 4, 63, 1), (1, 4, 64, 0))
+        for code, bad in ((R.LOAD_NOT_INTEGER, 0.5), (R.LOAD_NOT_INTEGER, np.nan), (R.LOAD_NOT_INTEGER, -np.inf),
+                          (R.LOAD_NOT_INTEGER, 2.0 ** 53), (R.LOAD_NEGATIVE, -1.0), (R.LOAD_OVER_WIDTH, float(top) + 1.0)):
+            for cell in cells:
+                e = good.copy()
+                e[cell] = bad
+                got = one(theta, e, what=(code, bad, cell))
+                assert got[code - 1] == 1 and got[5] != 0
+        # the width's maximum itself passes the cell test (what it does to the state is another category)
+        e = good.copy()
+        e[0, 0, 0, 2] = float(top)
+        assert not one(theta, e, what="top")[:3].any()
+        # a state one below zero at boundary T only: the last day removes one more than there are
+        st = R.check_draws(theta, good, init, width)
+        assert not st.any()
+        cum = good.sum(axis=2)
+        I_T = init[:, 2][None] + cum[..., 1] - cum[..., 2]
+        e = good.copy()
+        e[2, 5, T - 1, 2] += I_T[2, 5] + 1
+        got = one(theta, e, what="boundary T")
+        assert got[3] == 1 and got[5] == (((2 * M + 5) * T + T - 1) * 3 + 2) * 8 + R.LOAD_NEG_STATE and not got[:3].any()
+        # a NaN, an inf in theta
+        th = theta.copy()
+        th[1, 3], th[2, k.P - 1] = np.nan, np.inf
+        got = one(th, good, what="theta")
+        assert got[4] == 2 and got[5] == (k.P + 3) * 8 + R.LOAD_BAD_THETA
+        # random data, a tenth of the cells bad, every category present
+        e = good.copy()
+        pick = rng.random(e.shape) < 0.1
+        e[pick] = rng.choice([0.5, -3.0, np.nan, float(top) + 7.0, 1e300, -0.0, 2.0], size=int(pick.sum()))
+        th = theta.copy()
+        th[0, 0] = -np.inf
+        got = one(th, e, what="random")
+        assert got[:5].all()
+        # two calls before one status: the counts add up, the key is the first call's that had a bad item
+        _load(s, 0, 0, theta, good)
+        _load(s, 1, 4, th, e)
+        e2 = good.copy()
+        e2[0, 0, 0, 0] = 0.5                                   # a smaller key, in a later call
+        _load(s, 0, 5, theta, e2)
+        both = s.load_status(clear=True)
+        assert np.array_equal(both[:5], got[:5] + _want(case, theta, e2, width, 0, 5)[:5]) and np.array_equal(both[5:], [got[5], 1, 4])
+
+
+def test_a_sum_beyond_the_int32_range_is_held_by_the_int64_scan(api):
+    """M = 1 and a few days of cells within the int32 width whose running sums pass 2^31 and 2^32: in int32 arithmetic E
+    would wrap to a small positive number and the draw would pass."""
+    case, u, ev, cfg, eps = _case("micro_1x5", 1)
+    k = case["k"]
+    top = float(2 ** 31 - 1)
+    e = np.zeros((1, 1, 5, 3))
+    e[0, 0, :, 1] = top                                        # E -> I: five days of 2^31 - 1 out of E0
+    theta = np.zeros((1, k.P))
+    model, s = _sampler(api, case, cfg, u, ev, eps, 2)
+    with model, s:
+        _load(s, 0, 0, theta, e)
+        got = s.load_status(clear=True)
+        assert np.array_equal(got, _want(case, theta, e, 32, 0, 0))
+        assert got[3] == 5 and not got[:3].any()               # E below zero behind every day, every cell in the width
+
+
+def test_load_trace_raises_before_a_product_call(api):
+    case, u, ev, cfg, eps = _case("micro_9x70", 2)
+    k = case["k"]
+    n = 3
+    good = np.stack([_feasible(case["init"], n, k.T, np.random.default_rng(c)) for c in range(2)], axis=1)
+    theta = _plausible_theta(case, n, 2, 1)
+    model, s = _sampler(api, case, cfg, u, ev, eps, 4)
+    with model, s:
+        s.reset_summary()
+        FG._reset(s, case, 3)
+        s.replay(theta, good, summarize=True, forecast=True)
+        counts = (s.summary().count.copy(), s.forecast_summary().count.copy(), s._fc_j)
+        bad = good.astype(np.float64)
+        bad[1, 1, 4, 66, 1] = -2.0
+        with pytest.raises(ValueError, match=r"1 negative.*the first bad item is negative in chain 1 at \(draw 1, location 4, day 66, "
+                                             r"transition E->I\)"):
+            s.replay(theta, bad, summarize=True, forecast=True)
+        th = theta.copy()
+        th[2, 0, 7] = np.nan
+        with pytest.raises(ValueError, match=r"theta not finite in chain 0 at \(draw 2, parameter 7\)"):
+            s.replay(th, good, summarize=True, forecast=True)
+        assert not s.load_status().any()                       # the error cleared the counters
+        _same(counts, (s.summary().count, s.forecast_summary().count, s._fc_j))   # no product ran on the bad draws
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 3. - 5. replay equals the live run
+# ---------------------------------------------------------------------------------------------------------------------
+PRODUCTS = dict(summarize=True, forecast=True, rt=True, check=True, within_between=True, groups=True)
+FIELDS = ("theta", "marginals", "forecast", "rt", "check", "wb", "groups", "group_curves")
+
+
+def _everything_on(s, case, tab, Hn, Kc, D, cap, batch):
+    w = _weights(case, tab)
+    s.set_groups(tab.offsets, tab.members)
+    s.set_group_rt(w)
+    s.set_group_within_between(True)
+    s.reset_diagnostics(batch)                                 # the summaries with the diagnostics
+    FG._reset(s, case, Hn)
+    s.keep_forecast_draws(cap)
+    s.reset_rt(D, _weight(case))
+    s.keep_rt_draws(cap)
+    s.set_group_ngm(w, cap)
+    CG._reset(s, case, Kc)
+    s.reset_within_between(D)
+
+
+def _accumulators(s, n, probs=(0.05, 0.5, 0.95)):
+    return dict(summary=s.summary(), diagnostics=s.diagnostics(), forecast=s.forecast_summary(), rt=s.rt_summary(),
+                check=s.check_summary(), wb=s.within_between_summary(),
+                fq=s.forecast_quantiles(probs), fq_pooled=s.forecast_quantiles(probs, pooled=True),
+                rq=s.rt_quantiles(probs), rq_pooled=s.rt_quantiles(probs, pooled=True), ngm=s.read_group_ngm(n))
+
+
+def _fields(traces):
+    out = {}
+    for f in FIELDS:
+        vs = [getattr(t, f) for t in traces]
+        out[f] = {k: np.concatenate([v[k] for v in vs]) for k in vs[0]} if isinstance(vs[0], dict) else np.concatenate(vs)
+    return out
+
+
+def _live(api, case, cfg, u, ev, eps, record, tab, n, Hn, Kc, D, batch, sweeps=None, **kw):
+    """One live run with every product on: (the Trace with its events, its product fields, the accumulators)."""
+    model, s = _sampler(api, case, cfg, u, ev, eps, sweeps or n, record_events=record, **kw)
+    with model, s:
+        _everything_on(s, case, tab, Hn, Kc, D, n, batch)
+        tr = s.sample(n, **PRODUCTS)
+        assert not s.pair_timeouts().any()
+        return tr, _fields([tr]), _accumulators(s, n)
+
+
+def _replayed(api, case, cfg, u, ev, eps, record, tab, theta, events, cuts, Hn, Kc, D, batch, **kw):
+    n = theta.shape[0]
+    model, s = _sampler(api, case, cfg, u, ev, eps, max(cuts), record_events=record, **kw)
+    with model, s:
+        _everything_on(s, case, tab, Hn, Kc, D, n, batch)
+        state = s.get_state()
+        traces, j = [], 0
+        for c in cuts:
+            traces.append(s.replay(theta[j:j + c], events[j:j + c], **PRODUCTS))
+            j += c
+        assert j == n
+        tr = traces[0]
+        assert tr.events is None and not any(v.any() for v in tr.hmc.values())
+        assert not any(v.any() for mv in tr.moves.values() for v in mv.values())
+        _same(state, s.get_state())
+        return _fields(traces), _accumulators(s, n)
+
+
+LIVE = {
+    # name, B, record, n, the cuts of the replay, H, K, D, batch length
+    "M=3,T=5,B=2,burst_protocol_shape": ("micro_3x5", 2, True, 12, ((12,), (4, 4, 4), (5, 7)), 3, 2, 4, 4),
+    "M=9,T=70,B=3,u16": ("micro_9x70", 3, "u16", 6, ((6,), (1, 5)), 7, 5, 6, 3),
+    "M=9,T=70,B=3,int32": ("micro_9x70", 3, True, 6, ((6,),), 7, 5, 6, 3),
+}
+
+
+@pytest.mark.parametrize("case_id", list(LIVE))
+def test_a_replay_gives_the_live_runs_products_bit_for_bit(api, case_id):
+    name, B, record, n, cuts, Hn, Kc, D, batch = LIVE[case_id]
+    case, u, ev, cfg, eps = _case(name, B)
+    tab = _table(_groups_for(case["k"].M))                     # with overlap
+    tr, fields, acc = _live(api, case, cfg, u, ev, eps, record, tab, n, Hn, Kc, D, batch, first_chain_id=3)
+    assert acc["ngm"].any() and fields["forecast"]["forecast_by_day"].any()
+    for cut in cuts:
+        got_fields, got_acc = _replayed(api, case, cfg, u, ev, eps, record, tab, tr.theta, tr.events, cut, Hn, Kc, D, batch,
+                                        first_chain_id=3)
+        _same(fields, got_fields, str(cut))
+        _same(acc, got_acc, str(cut))
+
+
+def test_uk380_nations(api):
+    """UK-380 x 8 chains x 12 draws, `nations`, H = K = D = 14, uint16 trace: the size users run, once."""
+    case = H.build_case("uk380", 43, alpha_t_sd=0.005)
+    B, n = 8, 12
+    u = synth.jitter_params(case["u"], B, scale=0.002, seed=3, T=case["k"].T)
+    ev = np.stack([case["events"]] * B)
+    codes = [str(x) for x in np.load(synth._DATA)["lad19cd"]]
+    tab = G.parse_groups("nations", len(codes), codes)
+    tr, fields, acc = _live(api, case, CFG_REF, u, ev, 1.2e-5, "u16", tab, n, 14, 14, 14, 4)
+    got_fields, got_acc = _replayed(api, case, CFG_REF, u, ev, 1.2e-5, "u16", tab, tr.theta, tr.events, (n,), 14, 14, 14, 4)
+    _same(fields, got_fields)
+    _same(acc, got_acc)
+
+
+def test_replaying_every_kth_row_is_the_thinned_run(api):
+    case, u, ev, cfg, eps = _case("micro_9x70", 2)
+    n, K = 4, 3
+    tab = _table(_groups_for(9))
+    _, fields, acc = _live(api, case, cfg, u, ev, eps, "u16", tab, n, 5, 4, 6, 2, thin=K)
+    model, s = _sampler(api, case, cfg, u, ev, eps, n * K, record_events="u16")
+    with model, s:
+        every = s.sample(n * K)
+    rows = slice(K - 1, None, K)
+    got_fields, got_acc = _replayed(api, case, cfg, u, ev, eps, "u16", tab, every.theta[rows], every.events[rows], (n,), 5, 4, 6, 2)
+    _same(fields, got_fields)
+    _same(acc, got_acc)
+
+
+def test_one_sampler_pools_the_chains_of_two(api):
+    """Two samplers of 2 chains (global chains 0, 1 and 2, 3) record; one of 4 chains replays all four: its pooled order
+    statistics are np.sort over the four chains' draws, taken from the two live runs' own stores chain by chain."""
+    case, u, ev, cfg, eps = _case("micro_9x70", 4)
+    n, Hn, D = 4, 5, 6
+    ranks = np.arange(n)
+    theta, events, fc, rt = [], [], [], []
+    for c0 in (0, 2):
+        model, s = _sampler(api, case, cfg, u[c0:c0 + 2], ev[c0:c0 + 2], eps, n, record_events="u16", first_chain_id=c0)
+        with model, s:
+            FG._reset(s, case, Hn)
+            s.keep_forecast_draws(n)
+            s.reset_rt(D, _weight(case))
+            s.keep_rt_draws(n)
+            tr = s.sample(n, forecast=True, rt=True)
+            theta.append(tr.theta)
+            events.append(tr.events)
+            fc.append(s.forecast_order_stats(ranks))           # [n,2,3,M,H]: all n draws of each chain, sorted
+            rt.append(s.rt_order_stats(ranks))
+    model, s = _sampler(api, case, cfg, u, ev, eps, n, record_events="u16")
+    with model, s:
+        FG._reset(s, case, Hn)
+        s.keep_forecast_draws(n)
+        s.reset_rt(D, _weight(case))
+        s.keep_rt_draws(n)
+        s.replay(np.concatenate(theta, axis=1), np.concatenate(events, axis=1), forecast=True, rt=True)
+        all_ranks = np.arange(4 * n)
+        got_fc, got_rt = s.forecast_order_stats(all_ranks, pooled=True), s.rt_order_stats(all_ranks, pooled=True)
+        own_fc, own_rt = s.forecast_order_stats(ranks), s.rt_order_stats(ranks)
+    want_fc = np.sort(np.concatenate([np.moveaxis(x, 1, 0).reshape((-1,) + x.shape[2:]) for x in fc]), axis=0)
+    want_rt = np.sort(np.concatenate([np.moveaxis(x, 1, 0).reshape((-1,) + x.shape[2:]) for x in rt]), axis=0)
+    _same(want_fc, got_fc)
+    _same(want_rt, got_rt)
+    _same(np.concatenate(fc, axis=1), own_fc)                  # the chains' own streams: keyed by the global chain id
+    _same(np.concatenate(rt, axis=1), own_rt)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 6. the chain does not notice
+# ---------------------------------------------------------------------------------------------------------------------
+def test_a_load_into_the_other_half_leaves_the_chain_alone(api):
+    case, u, ev, cfg, eps = _case("micro_20x60", 3)
+    k = case["k"]
+    n = 4
+    runs = {}
+    for load in (False, True):
+        model, s = _sampler(api, case, cfg, u, ev, eps, 2 * n)
+        with model, s:
+            first = s.sample(n)
+            if load:
+                events = np.stack([_feasible(case["init"], n, k.T, np.random.default_rng(c)) for c in range(3)], axis=1)
+                s.load_trace(_theta(np.random.default_rng(2), (n, 3, k.P)), events, first=n)
+            runs[load] = (first, s.sample(n), s.get_state() + s.get_kernel())
+    _same_bits(runs[False][0], runs[True][0])
+    _same_bits(runs[False][1], runs[True][1])
+    _same(runs[False][2], runs[True][2])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 7. the command line
+# ---------------------------------------------------------------------------------------------------------------------
+def _run(module, args, tmp_path):
+    import os
+    import subprocess
+    import sys
+    env = dict(os.environ, PYTHONPATH=H.ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    r = subprocess.run([sys.executable, "-m", module] + args, cwd=H.ROOT, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-4000:]
+    return r.stderr
+
+
+def test_cli_replay_gives_the_inference_runs_products(api, tmp_path):
+    """The inference command line on NI-11, two chains, with every product on; then the replay command line on its two
+    files with the same flags: every product dataset is the live file's.  Then another horizon on every second row, which
+    the live run never formed, against `SeirModel.simulate` on the file's rows."""
+    import os
+    from types import SimpleNamespace
+
+    import yaml
+    from covid19uk_amd.inference import inference as inf
+    from tests.test_summary_gpu import _datasets
+    tmp = str(tmp_path)
+    cov = synth.make_covariates("ni11")
+    events, _, _ = synth.simulate_epidemic(cov)
+    data = os.path.join(tmp, "data.h5")
+    codes = ["E0%d" % m for m in range(5)] + ["S1%d" % m for m in range(4)] + ["W06", "W07"]
+    inf.write_inference_data(data, cov, events[..., 2], locations=codes)
+    cfg = os.path.join(tmp, "config.yaml")
+    with open(cfg, "w") as f:
+        yaml.safe_dump(dict(Mcmc=dict(dmax=84, nmax=25, m=2, occult_nmax=15, num_event_time_updates=5, num_bursts=2,
+                                      num_burst_samples=6, thin=1)), f)
+    grp = os.path.join(tmp, "groups.yaml")
+    with open(grp, "w") as f:
+        yaml.safe_dump({"east": ["E0*"], "south_and_west": ["S1*", "W06", "W07"], "all": list(range(11)), "one": [3]}, f)
+    flags = ["--summaries", "on", "--forecast", "7", "--forecast-quantiles", "0.05,0.5,0.95", "--rt", "7", "--check", "7",
+             "--within-between", "7", "--groups", grp, "--groups-rt", "--groups-ngm"]
+    live_out = os.path.join(tmp, "posterior.h5")
+    _run("covid19uk_amd.inference.inference", ["-c", cfg, "-o", live_out, "--seed", "4", "--chains", "2", data] + flags, tmp)
+    files = [inf.chain_file_name(live_out, c, 2) for c in range(2)]
+    out = os.path.join(tmp, "products.h5")
+    log = _run("covid19uk.posterior.replay", ["-c", cfg, "-o", out, "--seed", "4", data] + files + flags, tmp)
+    W, n = inf.warmup_size(), 12
+    assert f"Replay: rows {W}..{W + n - 1} step 1 ({n} draw(s)) of 2 file(s)" in log and "Forecast quantiles" in log
+    for c in range(2):
+        live, got = _datasets(files[c]), _datasets(inf.chain_file_name(out, c, 2))
+        want_names = {k for k in live if not k.startswith("results/") and k != "samples/seir"}
+        assert set(got) == want_names | {"replay/source", "replay/rows", "replay/first_chain_id"}
+        assert got["replay/source"][0].decode() == os.path.basename(files[c])
+        assert got["replay/rows"].dtype == np.int64 and np.array_equal(got["replay/rows"], np.arange(W, W + n))
+        assert int(got["replay/first_chain_id"][0]) == 0
+        assert any(k.startswith("forecast/pooled_") for k in got) and any(k.startswith("ngm/") for k in got)
+        for k in sorted(want_names):
+            a, b = live[k], got[k]
+            if k.startswith("samples/") and a.shape[0] == W + n:   # the warm-up's rows are not replayed
+                a = a[W:]
+            assert a.dtype == b.dtype and a.shape == b.shape, k
+            assert a.tobytes() == b.tobytes(), k
+    # another horizon, every second row, nothing else
+    out2 = os.path.join(tmp, "h14.h5")
+    _run("covid19uk_amd.posterior.replay", ["-c", cfg, "-o", out2, "--seed", "4", "--forecast", "14", "--every", "2", data] + files, tmp)
+    rows = np.arange(W, W + n, 2)
+    for c in range(2):
+        live, got = _datasets(files[c]), _datasets(inf.chain_file_name(out2, c, 2))
+        assert np.array_equal(got["replay/rows"], rows) and got["samples/forecast_by_day"].shape == (len(rows), 14, 3)
+        assert not any(k.startswith(("rt/", "check/", "summaries/", "results/")) for k in got) and "samples/seir" not in got
+        assert np.array_equal(got["samples/psi"], live["samples/psi"][rows])
+        case = dict(cov=cov, init=live["initial_state"], k=SimpleNamespace(T=cov.T))
+        theta = R.theta_from_samples({k: live[f"samples/{k}"][rows] for k in R.PARAMETER_KEYS}, cov.M, cov.T)
+        with api[0](cov, live["initial_state"], max_chains=1) as model:
+            want = FG._oracle(model, case, theta[:, None], live["samples/seir"][rows][:, None].astype(np.int64), 14, seed=4, chain0=c)
+        assert np.array_equal(got["samples/forecast_by_day"], want["forecast_by_day"][:, 0])
+        # the file's mean is ref + sum / n from integer accumulators, NumPy's a float sum: both within a few ulp of the exact mean
+        np.testing.assert_allclose(got["forecast/seir_mean"], want["sim"][:, 0].mean(axis=0), rtol=1e-13, atol=1e-13)
