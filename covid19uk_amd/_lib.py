@@ -61,6 +61,15 @@ class SeirSimDesc(ctypes.Structure):
     ]
 
 
+class SeirProductState(ctypes.Structure):
+    """Mirror of `seir_product_state` (include/seir_hip.h)."""
+    _fields_ = [(k, ctypes.c_int32) for k in ("summary_on", "diag_batch_len", "forecast_H", "check_K", "rt_D", "wb_D", "groups_G",
+                                              "groups_nnz")] + [("group_L", ctypes.c_int32 * 3)] + \
+        [(k, ctypes.c_int32) for k in ("group_rt_on", "group_wb_on", "group_rt_D", "group_wb_D", "ngm_D")] + \
+        [(k, ctypes.c_int64) for k in ("fc_j", "ck_j", "rt_j", "ngm_cap", "fc_keep_cap", "rt_keep_cap")] + \
+        [("reserved", ctypes.c_uint64 * 2)]
+
+
 ABI_VERSION = 4               # SEIR_ABI_VERSION
 OPT_DEBUG_SKEW, OPT_XCD_AFFINITY, OPT_GEMM_F32, OPT_EVAL_FORM, OPT_RT_STAGING_KIB = 0, 1, 2, 3, 4
 ERR_INVALID, ERR_STATE = -1, -3   # SEIR_ERR_INVALID, SEIR_ERR_STATE
@@ -269,6 +278,8 @@ _SIGNATURES = {
     "seir_sampler_load_trace": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_double_p,
                                                c_double_p]),
     "seir_sampler_load_status": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32]),
+    # the state of the products, from the sampler's host fields: the binding keeps no copy of it
+    "seir_sampler_product_state": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SeirProductState)]),
 }
 
 _lib = None

@@ -1347,7 +1347,10 @@ static int s_alloc(seir_sampler *s, std::vector<void *> &list, T **p, size_t cou
     HIP_TRY(hipMalloc(&q, bytes));
     list.push_back(q);
     if (kind != seir_sampler::R_OTHER) s->regions.push_back({q, bytes, kind});
+    // hipMemset may return before the device is done, and the null stream is not ordered with the (non-blocking) stream the
+    // kernels run on: without the wait a kernel enqueued right behind the allocation can find its output zeroed under it
     HIP_TRY(hipMemset(q, 0, bytes));
+    HIP_TRY(hipStreamSynchronize(nullptr));
     *p = (T *)q;
     return 0;
 }
@@ -1797,6 +1800,35 @@ extern "C" int seir_sampler_restore(seir_sampler *s, int32_t slot) {
     if ((rc = moments_shadow(s, slot, false))) return rc;
     s->vt_dirty = true;                              // Work::Vt came back with the snapshot, the flag did not
     HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+// What is on, how it is sized, how far it has counted (include/seir_hip.h): host fields only, a poisoned sampler answers too.
+extern "C" int seir_sampler_product_state(seir_sampler *s, seir_product_state *out) {
+    if (!s) return fail(SEIR_ERR_INVALID, "null sampler");
+    if (!out) return fail(SEIR_ERR_INVALID, "null pointer");
+    seir_product_state p{};
+    p.summary_on = s->sum_on;
+    p.diag_batch_len = s->diag_on ? (int32_t)s->diag.L : 0;
+    p.forecast_H = s->fc.on ? s->fc.fb.H : 0;
+    p.check_K = s->ck.on ? s->ck.fb.H : 0;
+    p.rt_D = s->rt_on ? s->rt.D : 0;
+    p.wb_D = s->wb_on ? s->wb.D : 0;
+    p.groups_G = s->grp_on ? s->grp.G : 0;
+    p.groups_nnz = s->grp_on && !s->grp_offsets.empty() ? s->grp_offsets.back() : 0;
+    for (int which = 0; which < 3; ++which) p.group_L[which] = s->grp_out[which].L;
+    p.group_rt_on = s->grt.on;
+    p.group_wb_on = s->gwb.on;
+    p.group_rt_D = s->grt.D;
+    p.group_wb_D = s->gwb.D;
+    p.ngm_D = s->ngm.D;
+    p.fc_j = s->fc.j;
+    p.ck_j = s->ck.j;
+    p.rt_j = s->rt_j;
+    p.ngm_cap = s->ngm.cap;
+    p.fc_keep_cap = s->fc_keep_cap;
+    p.rt_keep_cap = s->rt_keep_cap;
+    *out = p;
     return 0;
 }
 
@@ -2527,6 +2559,7 @@ static int groups_fit(seir_sampler *s, int which) {
     if (e == hipSuccess) e = hipMemset(ev, 0, ev_bytes);
     if (e == hipSuccess && which) e = hipMalloc(&st0, st_bytes);
     if (e == hipSuccess && which) e = hipMemset(st0, 0, st_bytes);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // the zeroing is done: see s_alloc
     if (e != hipSuccess) {
         if (ev) (void)hipFree(ev);
         if (st0) (void)hipFree(st0);
@@ -3701,6 +3734,7 @@ static int gcurve_fit(seir_sampler *s, bool rt) {
         if (e == hipSuccess) e = hipMalloc((void **)&c.cells[x], (size_t)cell_bytes);
         if (e == hipSuccess) e = hipMemset(c.cells[x], 0, (size_t)cell_bytes);
     }
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // the zeroing is done: see s_alloc
     if (e != hipSuccess) {
         gcurve_release(c);
         return fail(SEIR_ERR_DEVICE, "allocating %llu bytes of group curves failed: %s", bytes, hipGetErrorString(e));
@@ -4088,6 +4122,7 @@ extern "C" int seir_sampler_group_ngm(seir_sampler *s, const double *weights, in
     if (e == hipSuccess) e = hipMemset(n.out, 0, (size_t)out_bytes);
     if (e == hipSuccess) e = hipMalloc((void **)&n.P, (size_t)p_bytes);
     if (e == hipSuccess) e = hipMemset(n.P, 0, (size_t)p_bytes);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // the zeroing is done: see s_alloc
     if (e != hipSuccess) {
         ngm_off(s);
         return fail(SEIR_ERR_DEVICE, "allocating %llu bytes of the group next-generation matrix failed: %s", out_bytes + p_bytes,

@@ -10,6 +10,7 @@ traces back.  All sampling arithmetic runs in HIP kernels.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import dataclasses
 import sys
@@ -61,6 +62,13 @@ GROUP_CURVE_KEYS = ("rt_by_group", "within_by_group", "between_by_group")
 SUMMARY_QUANTITIES = ("k_se", "k_ei", "k_ir", "S", "E", "I")
 
 
+# What is on, how it is sized and how far it has counted: `seir_product_state` member for member (include/seir_hip.h says what
+# each one is), as `ChainSampler._state()` reads it from the library, which owns it.  The defaults: nothing is on.
+_STATE_KEYS = tuple(k for k, _ in _lib.SeirProductState._fields_ if k != "reserved")
+ProductState = collections.namedtuple("ProductState", _STATE_KEYS,
+                                      defaults=[(0, 0, 0) if k == "group_L" else 0 for k in _STATE_KEYS])
+
+
 class BurstProduct(typing.NamedTuple):
     """A device product that rides on a burst of kept draws: one row of `BURST_PRODUCTS`."""
     field: str          # the Trace / PinnedTrace field it fills; PinnedTrace's keyword has the same name
@@ -75,12 +83,15 @@ class BurstProduct(typing.NamedTuple):
     marks_behind: bool = False                          # the diagnostics' marks are enqueued right behind this row
 
 
-def _after_reset(attr, name):
-    """The size of a product whose reset leaves its extent in `sampler.<attr>` (0: never reset)."""
+def _after_reset(key, name):
+    """The size of a product whose reset leaves its extent in member `key` of the `ProductState` (0: never reset)."""
     def size(sampler, request, sizes):
-        if request and not getattr(sampler, attr):
+        if not request:
+            return 0
+        extent = getattr(sampler._state(), key)
+        if not extent:
             raise ValueError(f"{name} asked for before reset_{name}")
-        return getattr(sampler, attr) if request else 0
+        return extent
     return size
 
 
@@ -109,14 +120,14 @@ BURST_PRODUCTS = (
                  args=lambda s, req, n: (req is True,), marks_behind=True),   # "marginals": written, not folded
     # forecast=True holds the baseline; a callable (j0, count) -> steps [count,B,H] is asked with j0 = the draws per chain
     # forecast since the reset, as they stand at enqueue time -- after a re-run of a burst it is the same again
-    BurstProduct("forecast", "forecast", _after_reset("_forecast_H", "forecast"), _marginal_arrays(FORECAST_KEYS),
+    BurstProduct("forecast", "forecast", _after_reset("forecast_H", "forecast"), _marginal_arrays(FORECAST_KEYS),
                  "forecast", "read_forecast_marginals", "read_forecast_marginals_async",
-                 args=lambda s, req, n: (req(s._fc_j, n) if callable(req) else None,)),
-    BurstProduct("rt", "rt", _after_reset("_rt_D", "rt"), lambda s, D: ((int(D),), np.float64),
+                 args=lambda s, req, n: (req(s._state().fc_j, n) if callable(req) else None,)),
+    BurstProduct("rt", "rt", _after_reset("rt_D", "rt"), lambda s, D: ((int(D),), np.float64),
                  "rt", "read_rt_draws", "read_rt_draws_async"),
-    BurstProduct("check", "check", _after_reset("_check_K", "check"), _marginal_arrays(CHECK_KEYS),
+    BurstProduct("check", "check", _after_reset("check_K", "check"), _marginal_arrays(CHECK_KEYS),
                  "check", "read_check_marginals", "read_check_marginals_async"),
-    BurstProduct("wb", "within_between", _after_reset("_wb_D", "within_between"),
+    BurstProduct("wb", "within_between", _after_reset("wb_D", "within_between"),
                  lambda s, D: {k: ((int(D),), np.float64) for k in WB_KEYS},
                  "within_between", "read_wb_draws", "read_wb_draws_async"),
     # (G, {source: day extent}): the group sums of the sources that run with the burst
@@ -356,20 +367,7 @@ class PinnedTrace:
 class ChainSampler:
     # thinning interval in force for the next burst (subclasses that never run __init__ sample every sweep)
     _thin = 1
-    _summary_on = False           # reset_summary has been called: the device holds accumulators and marginal arrays
-    _diag_L = 0                   # batch length of the diagnostics in force (0: reset_diagnostics was never called)
-    _forecast_H = 0               # horizon of the forecast in force (0: reset_forecast was never called)
-    _fc_j = 0                     # draws per chain forecast since the last reset_forecast (the library's counter, mirrored)
-    _rt_D = 0                     # window of the reproduction number in force (0: reset_rt was never called)
-    _check_K = 0                  # window of the in-sample check in force (0: reset_check was never called)
-    _wb_D = 0                     # window of the within/between shares in force (0: reset_within_between was never called)
-    _groups_G = 0                 # groups of the table in force (0: none set)
-    _groups_nnz = 0               # members of the table in force
-    _group_rt_on = False          # set_group_rt: group R_t rides on rt
-    _group_wb_on = False          # set_group_within_between: group within / between rides on within_between
-    _group_rt_refused = False     # the last reset_rt could not size the group outputs: rt is on without them
-    _group_wb_refused = False
-    _group_ngm_cap = 0            # set_group_ngm: draws per chain of the group next-generation matrix's store (0: off)
+    _s = None                     # the library's handle; without one (a subclass that never runs __init__) nothing is on
     first_chain_id = 0
 
     def __init__(self, model: SeirModel, config: dict, num_chains: int, seed: int = 0,
@@ -431,7 +429,6 @@ class ChainSampler:
         _lib.check(self._lib.seir_sampler_create(model._ctx, ctypes.byref(desc), ctypes.byref(self._s)))
         self._thin = int(thin)
         self.first_chain_id = int(first_chain_id)
-        self._fc_j_snap = {}
         self.auto_recover = bool(auto_recover) and debug_pair == 0
         self.preferred_form = (hmc, moves)
         self.recoveries = []              # one dict per recovery: burst form that failed, form it was re-run in, message
@@ -444,7 +441,7 @@ class ChainSampler:
         for bf in getattr(self, "_pinned", []):
             bf.close()
         self._pinned, self._pinned_key = [], None
-        if getattr(self, "_s", None) is not None and self._s:
+        if self._s:
             self._lib.seir_sampler_destroy(self._s)
             self._s = ctypes.c_void_p()
 
@@ -461,6 +458,16 @@ class ChainSampler:
         self.close()
 
     # -- state ---------------------------------------------------------------
+    def _state(self) -> ProductState:
+        """The state of the products as the library holds it now (`seir_sampler_product_state`: host fields only, no device
+        call; a sampler with a hand-off time-out pending answers too).  This class keeps no copy: what a reset, a switch, a
+        refusal, a snapshot or a restore did to it is read here ("Who owns the product state")."""
+        if not self._s:
+            return ProductState()
+        st = _lib.SeirProductState()
+        _lib.check(self._lib.seir_sampler_product_state(self._s, ctypes.byref(st)))
+        return ProductState(*(tuple(v) if isinstance(v, ctypes.Array) else v for v in (getattr(st, k) for k in _STATE_KEYS)))
+
     def set_state(self, u, events):
         u = np.ascontiguousarray(u, dtype=np.float64)
         ev = np.ascontiguousarray(events, dtype=np.float64)
@@ -488,14 +495,10 @@ class ChainSampler:
         """Copy the chain state (everything the next sweep's draws are a function of; not the trace) to shadow slot 0 / 1,
         in stream order."""
         _lib.check(self._lib.seir_sampler_snapshot(self._s, int(slot)))
-        if self._forecast_H:
-            self._fc_j_snap[int(slot)] = self._fc_j
 
     def restore(self, slot: int = 0):
         """Back to the snapshot in `slot`; clears a hand-off time-out."""
         _lib.check(self._lib.seir_sampler_restore(self._s, int(slot)))
-        if self._forecast_H and int(slot) in self._fc_j_snap:
-            self._fc_j = self._fc_j_snap[int(slot)]
 
     def set_launch_form(self, hmc: str, moves: str):
         _lib.check(self._lib.seir_sampler_set_launch_form(self._s, HMC_MODES[hmc], MOVES_MODES[moves]))
@@ -651,7 +654,6 @@ class ChainSampler:
         """Enable the summaries (first call) and zero the moment accumulators, `count` and the overflow flag, in stream
         order: the next draw folded becomes `ref`."""
         _lib.check(self._lib.seir_sampler_summary_reset(self._s))
-        self._summary_on = True
 
     def summarize(self, first: int, count: int, accumulate: bool = True):
         """Enqueue the summary of trace slots [first, first+count) behind the sweeps that fill them: their marginals are
@@ -699,8 +701,6 @@ class ChainSampler:
         if int(batch_len) < 1:
             raise ValueError(f"batch_len={batch_len}: a batch has at least one draw")
         _lib.check(self._lib.seir_sampler_diag_reset(self._s, int(batch_len)))
-        self._summary_on = True
-        self._diag_L = int(batch_len)
 
     def mark(self, which: int):
         """Copy (count, sum, sumsq) into mark 0 / 1 on the device, in stream order behind everything queued so far."""
@@ -722,7 +722,7 @@ class ChainSampler:
             _lib.check(self._lib.seir_sampler_read_diag_mark(self._s, w, mc[w].ctypes.data_as(u64p), ms[w].ctypes.data_as(i64p),
                                                              mq[w].ctypes.data_as(u64p)))
         sm = self.summary()
-        return Diagnostics(batch_length=self._diag_L, count=sm.count, ref=sm.ref, sum=sm.sum, sumsq=sm.sumsq, bsum=bsum,
+        return Diagnostics(batch_length=self._state().diag_batch_len, count=sm.count, ref=sm.ref, sum=sm.sum, sumsq=sm.sumsq, bsum=bsum,
                            bsumsq=bsumsq, nbatch=nbatch, mark_count=mc, mark_sum=ms, mark_sumsq=mq)
 
     # -- forecast of the next H days from the burst buffer (include/seir_hip.h, "Forecast on the device") ----------
@@ -738,7 +738,6 @@ class ChainSampler:
         if W.shape != (H,) or wd.shape != (H,):
             raise ValueError(f"need W [{H}] and weekday_c [{H}]")
         _lib.check(self._lib.seir_sampler_forecast_reset(self._s, H, _dptr(W), _dptr(wd), int(seed) & (2 ** 64 - 1)))
-        self._forecast_H, self._fc_j, self._fc_j_snap = H, 0, {}
 
     def forecast(self, first: int, count: int, steps=None):
         """Enqueue the forecast of trace slots [first, first+count) behind the sweeps that fill them and fold it.  `steps`
@@ -746,25 +745,25 @@ class ChainSampler:
         n = int(count)
         if steps is not None:
             steps = np.ascontiguousarray(steps, dtype=np.float64)
-            if steps.shape != (n, self.B, self._forecast_H):
-                raise ValueError(f"need steps [{n},{self.B},{self._forecast_H}]")
+            H = self._state().forecast_H
+            if steps.shape != (n, self.B, H):
+                raise ValueError(f"need steps [{n},{self.B},{H}]")
         _lib.check(self._lib.seir_sampler_forecast(self._s, int(first), n, None if steps is None else _dptr(steps)))
-        self._fc_j += n
 
     def read_forecast_marginals(self, count: int, first: int = 0) -> dict:
         """Blocking read of the forecast marginals of trace slots [first, first+count): FORECAST_KEYS -> int64 arrays with
         leading axes [count, B]."""
-        return self._read_product(self._lib.seir_sampler_read_forecast_marginals, "forecast", self._forecast_H, count, first)
+        return self._read_product(self._lib.seir_sampler_read_forecast_marginals, "forecast", self._state().forecast_H, count, first)
 
     def read_forecast_marginals_async(self, count: int, first: int, into: PinnedTrace):
         """As `read_marginals_async`, for the forecast marginals; completed by `trace_wait()`."""
-        self._read_product(self._lib.seir_sampler_read_forecast_marginals_async, "forecast", self._forecast_H, count, first, into,
+        self._read_product(self._lib.seir_sampler_read_forecast_marginals_async, "forecast", self._state().forecast_H, count, first, into,
                            "forecast arrays")
 
     def forecast_summary(self) -> Summary:
         """The forecast moments folded since the last `reset_forecast` (blocking): a `Summary` whose day axis is the H
         forecast days, [B,M,H,6].  Raises `SeirError` (SEIR_ERR_STATE) if an accumulator overflowed or before a reset."""
-        return self._read_moments(self._lib.seir_sampler_read_forecast, self._forecast_H)
+        return self._read_moments(self._lib.seir_sampler_read_forecast, self._state().forecast_H)
 
     # -- forecast intervals: the draw store and exact order statistics (include/seir_hip.h, "Forecast intervals") ----
     def keep_forecast_draws(self, cap: int):
@@ -781,7 +780,7 @@ class ChainSampler:
         reset (blocking): int32 [R, B, 3, M, H] -- planes `FORECAST_QUANTILE_PLANES` -- or, `pooled`, [R, 3, M, H] over the
         B x count values of all chains of this sampler.  Equal to np.sort(draws, axis=0)[ranks]."""
         ranks = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
-        shape = (len(ranks),) + (() if pooled else (self.B,)) + (3, self.M, self._forecast_H)
+        shape = (len(ranks),) + (() if pooled else (self.B,)) + (3, self.M, self._state().forecast_H)
         out = np.empty(shape, np.int32)
         _lib.check(self._lib.seir_sampler_forecast_order_stats(self._s, ranks.ctypes.data_as(_lib.c_int64_p), len(ranks),
                                                                1 if pooled else 0,
@@ -792,7 +791,7 @@ class ChainSampler:
         """Quantiles `probs` (NumPy's default rule, `posterior.quantiles`) of every cell over the draws kept since the
         reset (blocking): float64 [K, B, 3, M, H], or [K, 3, M, H] when `pooled`."""
         from .posterior import quantiles as Q
-        n = self._fc_j * (self.B if pooled else 1)
+        n = self._state().fc_j * (self.B if pooled else 1)
         ranks = Q.quantile_ranks(n, probs)
         return Q.interpolate(self.forecast_order_stats(ranks, pooled=pooled), ranks, n, probs)
 
@@ -806,17 +805,7 @@ class ChainSampler:
         w = np.ascontiguousarray(weight, dtype=np.float64).reshape(-1)
         if w.shape != (self.M,):
             raise ValueError(f"need weight [{self.M}]")
-        try:
-            _lib.check(self._lib.seir_sampler_rt_reset(self._s, D, _dptr(w)))
-        except _lib.SeirError as e:
-            if self._group_rt_on and "group curves" in str(e):   # the reset is done; the group outputs were refused
-                if D != self._rt_D:
-                    self._group_ngm_cap = 0
-                self._rt_D, self._group_rt_refused = D, True
-            raise
-        if D != self._rt_D:
-            self._group_ngm_cap = 0                         # another window frees the store of the group NGM
-        self._rt_D, self._group_rt_refused = D, False
+        _lib.check(self._lib.seir_sampler_rt_reset(self._s, D, _dptr(w)))
 
     def rt(self, first: int, count: int):
         """Enqueue R_it of trace slots [first, first+count) behind the sweeps that fill them: folded into the moments,
@@ -825,16 +814,16 @@ class ChainSampler:
 
     def read_rt_draws(self, count: int, first: int = 0) -> np.ndarray:
         """Blocking read of R_t [count,B,D] of trace slots [first, first+count)."""
-        return self._read_product(self._lib.seir_sampler_read_rt_draws, "rt", self._rt_D, count, first)
+        return self._read_product(self._lib.seir_sampler_read_rt_draws, "rt", self._state().rt_D, count, first)
 
     def read_rt_draws_async(self, count: int, first: int, into: PinnedTrace):
         """As `read_marginals_async`, for the national curves; completed by `trace_wait()`."""
-        self._read_product(self._lib.seir_sampler_read_rt_draws_async, "rt", self._rt_D, count, first, into, "R_t")
+        self._read_product(self._lib.seir_sampler_read_rt_draws_async, "rt", self._state().rt_D, count, first, into, "R_t")
 
     def rt_summary(self) -> RtSummary:
         """The R_it accumulators folded since the last `reset_rt` (blocking): `RtSummary`, whose `.mean`, `.var` and
         `.prob_gt1` are formed here.  Raises `SeirError` (SEIR_ERR_STATE) before a reset."""
-        shape = (self.B, self._rt_D, self.M)
+        shape = (self.B, self._state().rt_D, self.M)
         cnt = np.zeros(self.B, np.uint64)
         ref, sm, sq, g1 = np.empty(shape), np.empty(shape), np.empty(shape), np.empty(shape, np.uint32)
         _lib.check(self._lib.seir_sampler_read_rt(self._s, cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), _dptr(ref),
@@ -856,7 +845,7 @@ class ChainSampler:
         the reset (blocking): float64 [R, B, D, M] or, `pooled`, [R, D, M] over the B x count values of all chains of this
         sampler.  Equal to np.sort(draws, axis=0)[ranks], bit for bit."""
         ranks = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
-        out = np.empty((len(ranks),) + (() if pooled else (self.B,)) + (self._rt_D, self.M))
+        out = np.empty((len(ranks),) + (() if pooled else (self.B,)) + (self._state().rt_D, self.M))
         _lib.check(self._lib.seir_sampler_rt_order_stats(self._s, ranks.ctypes.data_as(_lib.c_int64_p), len(ranks),
                                                          1 if pooled else 0, _dptr(out)))
         return out
@@ -885,7 +874,6 @@ class ChainSampler:
         if W.shape != (K,) or wd.shape != (K,):
             raise ValueError(f"need W [{K}] and weekday_c [{K}]")
         _lib.check(self._lib.seir_sampler_check_reset(self._s, K, _dptr(W), _dptr(wd), int(seed) & (2 ** 64 - 1)))
-        self._check_K = K
 
     def check(self, first: int, count: int):
         """Enqueue the check of trace slots [first, first+count) behind the sweeps that fill them: the window is simulated
@@ -895,17 +883,17 @@ class ChainSampler:
     def read_check_marginals(self, count: int, first: int = 0) -> dict:
         """Blocking read of the check's marginals of trace slots [first, first+count): CHECK_KEYS -> int64 arrays with
         leading axes [count, B]."""
-        return self._read_product(self._lib.seir_sampler_read_check_marginals, "check", self._check_K, count, first)
+        return self._read_product(self._lib.seir_sampler_read_check_marginals, "check", self._state().check_K, count, first)
 
     def read_check_marginals_async(self, count: int, first: int, into: PinnedTrace):
         """As `read_marginals_async`, for the check's marginals; completed by `trace_wait()`."""
-        self._read_product(self._lib.seir_sampler_read_check_marginals_async, "check", self._check_K, count, first, into,
+        self._read_product(self._lib.seir_sampler_read_check_marginals_async, "check", self._state().check_K, count, first, into,
                            "check arrays")
 
     def check_summary(self) -> CheckSummary:
         """Moments and comparison counts folded since the last `reset_check` (blocking).  Raises `SeirError`
         (SEIR_ERR_STATE) if an accumulator overflowed, if the observed removals differed between draws, or before a reset."""
-        B, M, K = self.B, self.M, self._check_K
+        B, M, K = self.B, self.M, self._state().check_K
         u32 = ctypes.POINTER(ctypes.c_uint32)
         obs = np.empty((B, M, K), np.int32)
         shapes = ((B, M, K), (B, M, K), (B, M), (B, M), (B, K), (B, K), (B,), (B,))
@@ -922,13 +910,7 @@ class ChainSampler:
         D = int(days)
         if not 1 <= D <= self.T:
             raise ValueError(f"within_between days {D}: 1 <= D <= T = {self.T}")
-        try:
-            _lib.check(self._lib.seir_sampler_wb_reset(self._s, D))
-        except _lib.SeirError as e:
-            if self._group_wb_on and "group curves" in str(e):   # the reset is done; the group outputs were refused
-                self._wb_D, self._group_wb_refused = D, True
-            raise
-        self._wb_D, self._group_wb_refused = D, False
+        _lib.check(self._lib.seir_sampler_wb_reset(self._s, D))
 
     def within_between(self, first: int, count: int):
         """Enqueue the shares of trace slots [first, first+count) behind the sweeps that fill them: folded into the
@@ -937,17 +919,17 @@ class ChainSampler:
 
     def read_wb_draws(self, count: int, first: int = 0) -> dict:
         """Blocking read of the national pressures of trace slots [first, first+count): WB_KEYS -> [count,B,D]."""
-        return self._read_product(self._lib.seir_sampler_read_wb_draws, "wb", self._wb_D, count, first)
+        return self._read_product(self._lib.seir_sampler_read_wb_draws, "wb", self._state().wb_D, count, first)
 
     def read_wb_draws_async(self, count: int, first: int, into: PinnedTrace):
         """As `read_marginals_async`, for the national pressures; completed by `trace_wait()`."""
-        self._read_product(self._lib.seir_sampler_read_wb_draws_async, "wb", self._wb_D, count, first, into, "within/between arrays")
+        self._read_product(self._lib.seir_sampler_read_wb_draws_async, "wb", self._state().wb_D, count, first, into, "within/between arrays")
 
     def within_between_summary(self) -> WbSummary:
         """The accumulators folded since the last `reset_within_between` (blocking): `WbSummary`, whose `.within_mean`,
         `.within_var`, `.between_mean` and `.p_within_gt_between` are formed here.  Raises `SeirError` (SEIR_ERR_STATE)
         before a reset."""
-        shape = (self.B, self._wb_D, self.M)
+        shape = (self.B, self._state().wb_D, self.M)
         u32 = ctypes.POINTER(ctypes.c_uint32)
         cnt = np.zeros(self.B, np.uint64)
         n, gt = np.empty(shape, np.uint32), np.empty(shape, np.uint32)
@@ -965,9 +947,6 @@ class ChainSampler:
         i32p = ctypes.POINTER(ctypes.c_int32)
         if offsets is None:
             _lib.check(self._lib.seir_sampler_groups_set(self._s, 0, None, None))
-            self._groups_G = self._groups_nnz = 0
-            self._group_rt_on = self._group_wb_on = False
-            self._group_ngm_cap = 0
             return
         off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
         mem = np.ascontiguousarray(members, dtype=np.int32).reshape(-1)
@@ -977,19 +956,12 @@ class ChainSampler:
                              "CSR pair of at least one group")
         if G > _lib.GROUPS_MAX:
             raise ValueError(f"G={G}: at most {_lib.GROUPS_MAX} groups")
-        try:
-            _lib.check(self._lib.seir_sampler_groups_set(self._s, G, off.ctypes.data_as(i32p), mem.ctypes.data_as(i32p)))
-        except _lib.SeirError as e:
-            if "group curves" not in str(e):
-                raise
-            # the table is in force; group within / between could not be sized for it
-            self._groups_G, self._groups_nnz, self._group_rt_on, self._group_wb_refused = G, int(off[G]), False, True
-            self._group_ngm_cap = 0
-            raise
-        self._groups_G, self._groups_nnz = G, int(off[G])
-        self._group_ngm_cap = 0                             # its weights belonged to the old table, too
-        self._group_rt_on = False                           # its weights belonged to the old table
-        self._group_wb_refused = False
+        _lib.check(self._lib.seir_sampler_groups_set(self._s, G, off.ctypes.data_as(i32p), mem.ctypes.data_as(i32p)))
+
+    def _check_group_weights(self, w):
+        st = self._state()
+        if st.groups_G and w.size != st.groups_nnz:
+            raise ValueError(f"need weights [{st.groups_nnz}], aligned with the table's members")
 
     # -- group curves: R_t and within / between per group (include/seir_hip.h, "Group curves on the device") ------------
     def set_group_rt(self, weights):
@@ -999,30 +971,16 @@ class ChainSampler:
         `posterior.groups.weighted_sum_rows`.  None switches it off.  A later `set_groups` switches it off too."""
         if weights is None:
             _lib.check(self._lib.seir_sampler_group_rt(self._s, None))
-            self._group_rt_on = False
             return
         w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
-        if self._groups_G and w.size != self._groups_nnz:
-            raise ValueError(f"need weights [{self._groups_nnz}], aligned with the table's members")
-        try:
-            _lib.check(self._lib.seir_sampler_group_rt(self._s, _dptr(w)))   # SEIR_ERR_STATE without a table
-        except _lib.SeirError as e:
-            if "group curves" in str(e):                    # outputs refused: the switch is off; any other refusal left it alone
-                self._group_rt_on = False
-            raise
-        self._group_rt_on, self._group_rt_refused = True, False
+        self._check_group_weights(w)
+        _lib.check(self._lib.seir_sampler_group_rt(self._s, _dptr(w)))   # SEIR_ERR_STATE without a table
 
     def set_group_within_between(self, on: bool):
         """Group within / between on or off: while a table is set and `within_between` runs, every draw it folds also
         leaves the members' sums of the within and the between pressure per group and window day ("between": from outside
         each member location, as in the national figure)."""
-        try:
-            _lib.check(self._lib.seir_sampler_group_wb(self._s, 1 if on else 0))
-        except _lib.SeirError as e:
-            if "group curves" in str(e):                    # outputs refused: the switch is off; any other refusal left it alone
-                self._group_wb_on = False
-            raise
-        self._group_wb_on, self._group_wb_refused = bool(on), False
+        _lib.check(self._lib.seir_sampler_group_wb(self._s, 1 if on else 0))
 
     # -- group next-generation matrix (include/seir_hip.h, "Group next-generation matrix on the device") ----------------
     def set_group_ngm(self, weights, cap: int):
@@ -1037,47 +995,41 @@ class ChainSampler:
             raise ValueError(f"cap={cap}: the number of draws per chain to keep")
         if weights is None or cap == 0:
             _lib.check(self._lib.seir_sampler_group_ngm(self._s, None, 0))
-            self._group_ngm_cap = 0
             return
         w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
-        if self._groups_G and w.size != self._groups_nnz:
-            raise ValueError(f"need weights [{self._groups_nnz}], aligned with the table's members")
-        try:
-            _lib.check(self._lib.seir_sampler_group_ngm(self._s, _dptr(w), cap))   # SEIR_ERR_STATE without a table or an rt reset
-        except _lib.SeirError as e:
-            if "group next-generation matrix needs" in str(e):  # store refused: the switch is off; any other refusal left it alone
-                self._group_ngm_cap = 0
-            raise
-        self._group_ngm_cap = cap
+        self._check_group_weights(w)
+        _lib.check(self._lib.seir_sampler_group_ngm(self._s, _dptr(w), cap))   # SEIR_ERR_STATE without a table or an rt reset
 
     def read_group_ngm(self, count: int, first: int = 0) -> np.ndarray:
         """Blocking read of K of draws [first, first+count) since the last `reset_rt`: float64 [count,B,G,G,D]
         (destination group, source group, window day)."""
-        count = int(count)
-        out = np.empty((max(count, 0), self.B, self._groups_G, self._groups_G, self._rt_D), dtype=np.float64)
+        count, st = int(count), self._state()
+        out = np.empty((max(count, 0), self.B, st.groups_G, st.groups_G, st.ngm_D), dtype=np.float64)
         _lib.check(self._lib.seir_sampler_read_group_ngm(self._s, int(first), count, _dptr(out)))
         return out
 
     def _group_curve_days(self, sizes):
         """(G, {key of GROUP_CURVE_KEYS: window days}) of the curves that leave outputs with a burst that runs the rt /
         within_between of `sizes` ({field: size} of the burst's products); () when there is none."""
-        days = {}
-        if sizes["rt"] and self._group_rt_on and self._groups_G and not self._group_rt_refused:
-            days["rt_by_group"] = self._rt_D
-        if sizes["wb"] and self._group_wb_on and self._groups_G and not self._group_wb_refused:
-            days["within_by_group"] = days["between_by_group"] = self._wb_D
-        return (self._groups_G, days) if days else ()
+        days, st = {}, self._state()
+        if sizes["rt"] and st.group_rt_D:                  # the library's own condition for forming the curves
+            days["rt_by_group"] = st.group_rt_D
+        if sizes["wb"] and st.group_wb_D:
+            days["within_by_group"] = days["between_by_group"] = st.group_wb_D
+        return (st.groups_G, days) if days else ()
 
     def read_group_rt(self, count: int, first: int = 0) -> np.ndarray:
         """Blocking read of the group R_t of trace slots [first, first+count): float64 [count,B,G,D]."""
-        out = self._fresh("group_curves", (self._groups_G, {"rt_by_group": self._rt_D}), count)["rt_by_group"]
+        st = self._state()
+        out = self._fresh("group_curves", (st.groups_G, {"rt_by_group": st.group_rt_D}), count)["rt_by_group"]
         _lib.check(self._lib.seir_sampler_read_group_rt(self._s, int(first), int(count), _dptr(out)))
         return out
 
     def read_group_wb(self, count: int, first: int = 0) -> dict:
         """Blocking read of the group pressures of trace slots [first, first+count): within_by_group, between_by_group
         -> float64 [count,B,G,D]."""
-        out = self._fresh("group_curves", (self._groups_G, dict.fromkeys(GROUP_CURVE_KEYS[1:], self._wb_D)), count)
+        st = self._state()
+        out = self._fresh("group_curves", (st.groups_G, dict.fromkeys(GROUP_CURVE_KEYS[1:], st.group_wb_D)), count)
         _lib.check(self._lib.seir_sampler_read_group_wb(self._s, int(first), int(count), *(_dptr(out[k]) for k in GROUP_CURVE_KEYS[1:])))
         return out
 
@@ -1102,13 +1054,11 @@ class ChainSampler:
                                                                   _dptr(g["between_by_group"])))
         return g
 
-    def _group_len(self, source):
-        return {"trace": self.T if self._summary_on else 0, "forecast": self._forecast_H, "check": self._check_K}[source]
-
     def _read_groups(self, fn, source, count, first, into=None):
         which, ev_key, st_key = GROUP_SOURCES[source]
         if into is None:
-            into = self._fresh("groups", (self._groups_G, {source: self._group_len(source)}), count)
+            st = self._state()
+            into = self._fresh("groups", (st.groups_G, {source: st.group_L[which]}), count)
         _lib.check(fn(self._s, which, int(first), int(count), into[ev_key].ctypes.data_as(_lib.c_int64_p),
                       into[st_key].ctypes.data_as(_lib.c_int64_p) if st_key else None))
         return into
@@ -1140,9 +1090,12 @@ class ChainSampler:
         products); or a tuple of those names, each of which must run.  () when `groups` is off."""
         if not groups:
             return ()
-        if not self._groups_G:
+        st = self._state()
+        if not st.groups_G:
             raise ValueError("groups asked for before set_groups")
-        on = dict(trace=self._group_len("trace") if sizes["marginals"] else 0, forecast=sizes["forecast"], check=sizes["check"])
+        # a source is on when it runs with the burst and its group outputs exist (none: the library refused them)
+        runs = dict(trace=sizes["marginals"], forecast=sizes["forecast"], check=sizes["check"])
+        on = {k: st.group_L[which] if runs[k] else 0 for k, (which, _, _) in GROUP_SOURCES.items()}
         if groups is True:
             src = tuple(k for k in GROUP_SOURCES if on[k])
         else:
@@ -1152,13 +1105,13 @@ class ChainSampler:
                 raise ValueError(f"groups={groups!r}: {bad[0]!r} is not one of summarize, forecast, check run with this burst")
         if not src:
             raise ValueError("groups needs one of summarize, forecast, check")
-        return self._groups_G, {k: on[k] for k in src}
+        return st.groups_G, {k: on[k] for k in src}
 
     def _summarize_mode(self, summarize):
         """`summarize` of sample / sample_bursts: False, True (marginals + moments) or "marginals" (accumulate = 0)."""
         if summarize not in (False, True, "marginals"):
             raise ValueError(f"summarize={summarize!r}: False, True or 'marginals'")
-        if summarize and not self._summary_on:
+        if summarize and not self._state().summary_on:
             self.reset_summary()
         return bool(summarize)
 

@@ -1031,6 +1031,44 @@ int seir_sampler_load_trace(seir_sampler *s, int32_t chain, int32_t first, int32
 int seir_sampler_load_status(seir_sampler *s, uint64_t out[8], int32_t clear);
 
 /* ------------------------------------------------------------------------
+ * The state of the products: what is on, how it is sized and how far it has counted.
+ *
+ * The sampler is the one owner of this state; a binding asks for it and keeps no copy ("Who owns the product
+ * state").  Every member is the value the entry points above act on at the moment of the call -- also after a call that
+ * returned an error: a reset that was done before its group outputs were refused shows the new extent and no group outputs.
+ * ------------------------------------------------------------------------ */
+typedef struct seir_product_state {
+    int32_t summary_on;      /* 1: seir_sampler_summary_reset (or _diag_reset) was called, the summaries are enabled */
+    int32_t diag_batch_len;  /* batch length of the diagnostics in force; 0: seir_sampler_diag_reset was never called */
+    int32_t forecast_H;      /* horizon of the forecast in force; 0: never reset */
+    int32_t check_K;         /* window of the in-sample check in force; 0: never reset */
+    int32_t rt_D;            /* window of the reproduction number in force; 0: never reset */
+    int32_t wb_D;            /* window of the within/between shares in force; 0: never reset */
+    int32_t groups_G;        /* groups of the table in force; 0: no table */
+    int32_t groups_nnz;      /* its members (offsets[G]) */
+    int32_t group_L[3];      /* day extent the group sums of the trace, the forecast and the check are sized for (T, H, K);
+                              * 0: none -- no table, the source is off, or its outputs were refused */
+    int32_t group_rt_on;     /* the switch of seir_sampler_group_rt */
+    int32_t group_wb_on;     /* the switch of seir_sampler_group_wb */
+    int32_t group_rt_D;      /* window the outputs of group R_t are sized for; 0: none (switch off, no table, seir_sampler_rt
+                              * never reset, or refused) -- seir_sampler_rt forms the curves exactly when this is not 0 */
+    int32_t group_wb_D;      /* likewise for group within / between and seir_sampler_wb */
+    int32_t ngm_D;           /* window the store of the group next-generation matrix is sized for; 0: off */
+    int64_t fc_j;            /* draws per chain forecast since the last seir_sampler_forecast_reset (the j of the draw id) */
+    int64_t ck_j;            /* draws per chain checked since the last seir_sampler_check_reset */
+    int64_t rt_j;            /* draws per chain folded by seir_sampler_rt since the last seir_sampler_rt_reset */
+    int64_t ngm_cap;         /* draws per chain the store of the group next-generation matrix holds; 0: off */
+    int64_t fc_keep_cap;     /* draws per chain the forecast's draw store holds (seir_sampler_forecast_keep); 0: none */
+    int64_t rt_keep_cap;     /* draws per chain the R_it draw store holds (seir_sampler_rt_keep); 0: none */
+    uint64_t reserved[2];    /* zero */
+} seir_product_state;        /* 16 int32, 6 int64, 2 reserved words: 128 bytes, no implicit padding */
+
+/* Fills *out from the sampler's host fields alone: no device call, no stream synchronisation, no allocation -- it may be
+ * called at any time, between the enqueue of a burst and its wait as well, and it answers for a sampler that reported
+ * SEIR_ERR_HANDOFF too, before the seir_sampler_restore that clears it.  SEIR_ERR_INVALID for a NULL sampler or a NULL out, and for nothing else. */
+int seir_sampler_product_state(seir_sampler *s, seir_product_state *out);
+
+/* ------------------------------------------------------------------------
  * Reproduction number R_it.
  *
  * calc_posterior_rit (covid19uk/posterior/reproduction_number.py:13-44): for each

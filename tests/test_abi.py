@@ -61,6 +61,50 @@ def test_desc_struct_layout_matches_header():
     assert ctypes.sizeof(_lib.SeirDesc) == 16 + 6 * 8 + 8 + 8 + 3 * 8
 
 
+def test_product_state_struct_layout_matches_header():
+    # 16 int32 (group_L is three of them), 6 int64, 2 reserved words
+    assert ctypes.sizeof(_lib.SeirProductState) == 16 * 4 + 6 * 8 + 2 * 8
+    assert _lib.SeirProductState.group_L.offset == 32 and _lib.SeirProductState.fc_j.offset == 64
+    # member for member the header's struct, in its order
+    text = open(os.path.join(ROOT, "include", "seir_hip.h")).read()
+    body = re.search(r"typedef struct seir_product_state \{(.*?)\} seir_product_state;", text, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    declared = [(t, n, int(k or 1)) for t, n, k in re.findall(r"\b(u?int(?:32|64)_t)\s+(\w+)(?:\[(\d+)\])?;", body)]
+    bound = [(f[0], f[1]) for f in _lib.SeirProductState._fields_]
+    ctype = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64}
+    assert bound == [(n, ctype[t] * k if k > 1 else ctype[t]) for t, n, k in declared]
+
+
+def test_product_state_refuses_null_pointers_without_touching_the_gpu(lib):
+    out = _lib.SeirProductState()
+    assert lib.seir_sampler_product_state(None, ctypes.byref(out)) == _lib.ERR_INVALID
+    assert b"null sampler" in lib.seir_last_error()
+    assert lib.seir_sampler_product_state(None, None) == _lib.ERR_INVALID
+
+
+def test_every_key_the_burst_table_sizes_from_is_a_member_of_the_product_state():
+    """The sizes of the burst table come from `ChainSampler._state()` alone: a sampler that has nothing but a record with
+    everything on sizes every row, reads only members of the record, and the class has no private default to read instead."""
+    from covid19uk_amd import sampler as sm
+    read = set()
+
+    class Spy:
+        def __getattr__(self, key):
+            read.add(key)
+            return dict(group_L=(5, 2, 2)).get(key, 2)
+
+    class Bare(sm.ChainSampler):
+        T = 5
+
+        def _state(self):
+            return Spy()
+    on = Bare.__new__(Bare)._burst_products(dict({p.request: True for p in sm.BURST_PRODUCTS if p.request}))
+    assert list(on) == [p.field for p in sm.BURST_PRODUCTS]
+    assert read and read <= set(sm.ProductState._fields), read - set(sm.ProductState._fields)
+    private = [k for k, v in vars(sm.ChainSampler).items() if k.startswith("_") and not k.startswith("__") and not callable(v)]
+    assert private == ["_thin", "_s"], private
+
+
 def test_create_rejects_bad_arguments_without_touching_the_gpu(lib):
     ctx = ctypes.c_void_p()
     desc = _lib.SeirDesc(M=0, T=5, max_chains=1)

@@ -7,7 +7,7 @@ import pytest
 
 import covid19uk_amd.sampler as sm
 from covid19uk_amd import _lib
-from covid19uk_amd.sampler import BURST_PRODUCTS, PRODUCTS, ChainSampler
+from covid19uk_amd.sampler import BURST_PRODUCTS, PRODUCTS, ChainSampler, ProductState
 
 BASE = ("snapshot", "restore", "reset_trace", "run", "mark", "read_trace", "read_trace_async", "trace_wait")
 ENQUEUE = tuple(p.enqueue for p in BURST_PRODUCTS if p.enqueue)
@@ -17,10 +17,27 @@ B, M, T, BURST = 2, 3, 5, 4
 
 
 class OkLib:
-    """libseirhip's stand-in: every function returns SEIR_OK and touches nothing."""
+    """libseirhip's stand-in: every function returns SEIR_OK and touches nothing -- but the forecast's draw counter in the
+    state of its sampler, which it keeps as the library does: a forecast advances it, a snapshot holds it, a restore brings
+    it back."""
+
+    def __init__(self, sampler):
+        self.sampler, self.snap = sampler, {}
 
     def __getattr__(self, name):
         return lambda *a: 0
+
+    def seir_sampler_forecast(self, s, first, count, steps):
+        self.sampler.state = self.sampler.state._replace(fc_j=self.sampler.state.fc_j + count)
+        return 0
+
+    def seir_sampler_snapshot(self, s, slot):
+        self.snap[slot] = self.sampler.state.fc_j
+        return 0
+
+    def seir_sampler_restore(self, s, slot):
+        self.sampler.state = self.sampler.state._replace(fc_j=self.snap[slot])
+        return 0
 
 
 class AllOn(ChainSampler):
@@ -31,10 +48,13 @@ class AllOn(ChainSampler):
 
     def __init__(self):
         self.calls, self.j0, self.time_outs = [], [], 0
-        self._lib, self._s, self._log = OkLib(), None, None
-        self._summary_on, self._forecast_H, self._rt_D, self._check_K, self._wb_D = True, 2, 3, 2, 3
-        self._groups_G, self._groups_nnz, self._group_rt_on, self._group_wb_on = 2, 4, True, True
-        self._fc_j_snap, self._fallback_level, self._clean_bursts, self.recoveries, self.retry_after = {}, 0, 0, [], 8
+        self._lib, self._s, self._log = OkLib(self), None, None
+        self.state = ProductState(summary_on=1, forecast_H=2, rt_D=3, check_K=2, wb_D=3, groups_G=2, groups_nnz=4,
+                                  group_L=(T, 2, 2), group_rt_on=1, group_wb_on=1, group_rt_D=3, group_wb_D=3)
+        self._fallback_level, self._clean_bursts, self.recoveries, self.retry_after = 0, 0, [], 8
+
+    def _state(self):
+        return self.state
 
     def __getattribute__(self, name):
         real = object.__getattribute__(self, name)
@@ -54,7 +74,7 @@ class AllOn(ChainSampler):
 
     def steps(self, j0, count):
         self.j0.append(j0)
-        return np.zeros((count, self.B, self._forecast_H))
+        return np.zeros((count, self.B, self.state.forecast_H))
 
     def requests(self):
         """Every keyword a row of the table asks with; the forecast's as the callable."""
@@ -94,7 +114,7 @@ def test_sample_enqueues_and_reads_every_product_in_table_order():
     tr = s.sample(BURST, **s.requests())
     assert [c[0] for c in s.calls] == ["snapshot", "reset_trace", "run", *ENQUEUE, "read_trace", *READ]
     assert [c[:3] for c in s.calls if c[0] in ENQUEUE] == [(name, 0, BURST) for name in ENQUEUE]
-    assert s.j0 == [0] and s._fc_j == BURST                     # the steps are drawn for the draws the forecast is about to make
+    assert s.j0 == [0] and s.state.fc_j == BURST                # the steps are drawn for the draws the forecast is about to make
     for p in BURST_PRODUCTS:                                    # every field is filled, with the shapes the table states
         got, want = getattr(tr, p.field), p.arrays(s, s._burst_products(s.requests())[p.field][1])
         if isinstance(want, tuple):
@@ -104,7 +124,7 @@ def test_sample_enqueues_and_reads_every_product_in_table_order():
             assert got[k].shape == (BURST, B) + shape and got[k].dtype == dtype, (p.field, k)
     # nothing on: nothing of the table is called
     s = AllOn()
-    s._group_rt_on = s._group_wb_on = False
+    s.state = s.state._replace(group_rt_on=0, group_wb_on=0, group_rt_D=0, group_wb_D=0)
     tr = s.sample(BURST)
     assert [c[0] for c in s.calls] == ["snapshot", "reset_trace", "run", "read_trace"]
     assert all(getattr(tr, field) is None for field in PRODUCTS)
@@ -132,8 +152,9 @@ def test_each_half_of_sample_bursts_enqueues_and_reads_every_product_in_table_or
     assert names.index("trace_wait") > [i for i, n in enumerate(names) if n == "run"][1]
 
 
-TWEAKS = (("_forecast_H", 3), ("_rt_D", 2), ("_check_K", 1), ("_wb_D", 2), ("_groups_G", 3), ("_group_wb_on", False),
-          ("_group_rt_on", False))
+# what the library does to its state at a reset with another extent, at another table, at a switch that goes off
+TWEAKS = ((dict(forecast_H=3, group_L=(T, 3, 2)), dict(rt_D=2, group_rt_D=2), dict(check_K=1, group_L=(T, 3, 1)),
+           dict(wb_D=2, group_wb_D=2), dict(groups_G=3), dict(group_wb_on=0, group_wb_D=0), dict(group_rt_on=0, group_rt_D=0)))
 
 
 def test_the_pinned_buffers_are_kept_until_a_size_changes(nopin):
@@ -145,11 +166,11 @@ def test_the_pinned_buffers_are_kept_until_a_size_changes(nopin):
     sizes = call()
     assert NoPin.built == 2 and call() == sizes and NoPin.built == 2        # two equal calls: built once
     built, moved = 2, set()
-    for attr, value in TWEAKS:
-        setattr(s, attr, value)
+    for tweak in TWEAKS:
+        s.state = s.state._replace(**tweak)
         now = call()
         built += 2
-        assert NoPin.built == built and call() == now and NoPin.built == built, attr
+        assert NoPin.built == built and call() == now and NoPin.built == built, tweak
         moved |= {f for f in PRODUCTS if now.get(f) != sizes.get(f)}
         sizes = now
     now = call(summarize=False, groups=("forecast", "check"))
@@ -162,7 +183,7 @@ def test_the_pinned_buffers_are_kept_until_a_size_changes(nopin):
     assert NoPin.built == built + 6
     # nothing on at all: the class is called without keywords
     s = AllOn()
-    s._group_rt_on = s._group_wb_on = False
+    s.state = s.state._replace(group_rt_on=0, group_wb_on=0, group_rt_D=0, group_wb_D=0)
     s.sample_bursts(2, BURST, lambda tr, i: None)
     assert s._pinned[0].kw == {}
 
@@ -173,7 +194,7 @@ def test_a_burst_that_is_run_again_gets_the_same_steps(nopin):
     got = []
     s.sample_bursts(2, BURST, lambda tr, i: got.append(i), **s.requests())
     assert got == [0, 1] and len(s.recoveries) == 1
-    assert s.j0 == [0, BURST, 0, BURST] and s._fc_j == 2 * BURST
+    assert s.j0 == [0, BURST, 0, BURST] and s.state.fc_j == 2 * BURST
     assert [c[:3] for c in s.calls if c[0] in ENQUEUE] == [(name, h * BURST, BURST) for h in (0, 1, 0, 1) for name in ENQUEUE]
     s = AllOn()
     real_read, failed = s.read_trace, []
@@ -185,4 +206,4 @@ def test_a_burst_that_is_run_again_gets_the_same_steps(nopin):
         return real_read(n, **kw)
     s.read_trace = read_trace
     s.sample(BURST, **s.requests())
-    assert s.j0 == [0, 0] and s._fc_j == BURST and len(s.recoveries) == 1
+    assert s.j0 == [0, 0] and s.state.fc_j == BURST and len(s.recoveries) == 1

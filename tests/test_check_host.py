@@ -410,7 +410,7 @@ def test_on_resets_once_checks_every_burst_behind_the_others_and_writes_the_grou
 class CheckRecorder(Recorder):
     def __init__(self):
         super().__init__()
-        self._check_K = 2
+        self.state = self.state._replace(check_K=2)
 
     def __getattribute__(self, name):
         if name in ("check", "read_check_marginals_async"):
@@ -433,7 +433,7 @@ def test_a_burst_is_checked_behind_its_summary_forecast_and_rt_and_not_at_all_wh
     tr = s.sample(4, summarize=True, forecast=True, rt=True)
     assert not any("check" in c[0] for c in s.calls) and tr.check is None
     s = CheckRecorder()
-    s._check_K = 0
+    s.state = s.state._replace(check_K=0)
     with pytest.raises(ValueError, match="before reset_check"):
         s.sample(4, check=True)
     import covid19uk_amd.sampler as sm

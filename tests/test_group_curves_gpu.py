@@ -588,9 +588,13 @@ def test_outputs_above_half_of_the_free_memory_are_refused_and_the_next_calls_ar
         with pytest.raises(_lib.SeirError, match=r"group curves need \d+ bytes .* more than half of the \d+ bytes free") as e:
             s.reset_rt(D, wn)
         assert e.value.code == _lib.ERR_INVALID
+        st = s._state()
+        assert (st.rt_D, st.rt_j, st.group_rt_on, st.group_rt_D) == (D, 0, 1, 0)
         with pytest.raises(_lib.SeirError, match="more than half of the") as e:
             s.reset_within_between(D)
         assert e.value.code == _lib.ERR_INVALID
+        st = s._state()
+        assert (st.wb_D, st.group_wb_on, st.group_wb_D) == (D, 1, 0)
         out = s.sample(n, rt=True, within_between=True)
         assert out.group_curves is None and out.rt.shape == (n, 3, D) and out.wb["within_pressure"].shape == (n, 3, D)
         for fn in (s.read_group_rt, s.read_group_wb):
@@ -604,6 +608,8 @@ def test_outputs_above_half_of_the_free_memory_are_refused_and_the_next_calls_ar
             with pytest.raises(_lib.SeirError, match="more than half of the") as e:
                 fn(arg)
             assert e.value.code == _lib.ERR_INVALID
+            st = s._state()
+            assert (st.rt_D, st.wb_D, st.group_rt_on, st.group_rt_D, st.group_wb_on, st.group_wb_D) == (D, D, 0, 0, 0, 0)
         s.rt(0, n)
         s.within_between(0, n)
         assert np.array_equal(s.read_rt_draws(n), out.rt)

@@ -478,6 +478,8 @@ def test_outputs_above_half_of_the_free_memory_are_refused_and_the_next_call_is_
         with pytest.raises(_lib.SeirError, match=rf"need {need} bytes .* more than half of the \d+ bytes free") as e:
             FG._reset(s, case, Hn)
         assert e.value.code == _lib.ERR_INVALID
+        st = s._state()
+        assert (st.forecast_H, st.fc_j, st.groups_G, st.group_L) == (Hn, 0, G, (0, 0, 0))
         s.forecast(0, n)                                       # the forecast is on with H = 128 and has no group outputs
         with pytest.raises(_lib.SeirError) as e:
             s.read_group_marginals("forecast", n)
@@ -489,6 +491,8 @@ def test_outputs_above_half_of_the_free_memory_are_refused_and_the_next_call_is_
         with pytest.raises(_lib.SeirError, match="more than half of the") as e:
             _set(s, big)
         assert e.value.code == _lib.ERR_INVALID
+        st = s._state()
+        assert (st.forecast_H, st.groups_G, st.groups_nnz, st.group_L) == (Hn, 1, 1, (0, Hn, 0))
         s.forecast(0, n)
         fw = FG._oracle(model, case, tr.theta, tr.events, Hn)
         got = s.read_group_marginals("forecast", n)

@@ -425,14 +425,14 @@ def test_state_handling_and_refusals(api):
         # another D frees it: the product is off, rt runs on
         s.reset_rt(D + 1, wn)
         s.rt(0, n)
-        assert _code(s.read_group_ngm, 1) == _lib.ERR_STATE and s._group_ngm_cap == 0
+        assert _code(s.read_group_ngm, 1) == _lib.ERR_STATE and s._state().ngm_cap == 0
         # on again for the new window; a new table switches it off
         s.reset_rt(D + 1, wn)
         s.set_group_ngm(w, n)
         s.rt(0, n)
         assert s.read_group_ngm(n).shape == (n, 1, 3, 3, D + 1)
         _set(s, [[0], [1]])
-        assert _code(s.read_group_ngm, 1) == _lib.ERR_STATE and s._group_ngm_cap == 0
+        assert _code(s.read_group_ngm, 1) == _lib.ERR_STATE and s._state().ngm_cap == 0
         # above half of the free memory: refused, the product is off, rt runs on
         big = [[m] for m in range(65)]
         _set(s, big)
@@ -441,7 +441,8 @@ def test_state_handling_and_refusals(api):
         assert cap * 65 * 65 * 70 * 8 > torch.cuda.mem_get_info()[0] / 2
         with pytest.raises(_lib.SeirError, match=r"next-generation matrix needs \d+ bytes .* more than half of the \d+ bytes free") as e:
             s.set_group_ngm(np.ones(65), cap)
-        assert e.value.code == _lib.ERR_INVALID and s._group_ngm_cap == 0
+        assert e.value.code == _lib.ERR_INVALID and s._state().ngm_cap == 0
+        assert (s._state().rt_D, s._state().groups_G, s._state().ngm_D) == (70, 65, 0)
         s.rt(0, n)
         assert s.read_rt_draws(n).shape == (n, 1, 70) and _code(s.read_group_ngm, 1) == _lib.ERR_STATE
         # off by hand

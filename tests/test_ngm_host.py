@@ -62,7 +62,7 @@ def test_new_symbols_are_declared_exported_and_bound_with_the_headers_types():
     for name in ("set_group_ngm", "read_group_ngm"):
         assert callable(getattr(ChainSampler, name))
     assert callable(SeirModel.group_ngm_rows)
-    assert ChainSampler._group_ngm_cap == 0                     # a class-level default: a subclass that never runs __init__
+    assert ChainSampler.__new__(ChainSampler)._state().ngm_cap == 0   # without a handle: a subclass that never runs __init__
     # not a burst product: the tables of the products are what they were
     assert GROUP_CURVE_KEYS == ("rt_by_group", "within_by_group", "between_by_group")
     assert not any("ngm" in p.field for p in BURST_PRODUCTS)

@@ -304,7 +304,7 @@ def test_load_trace_raises_before_a_product_call(api):
         s.reset_summary()
         FG._reset(s, case, 3)
         s.replay(theta, good, summarize=True, forecast=True)
-        counts = (s.summary().count.copy(), s.forecast_summary().count.copy(), s._fc_j)
+        counts = (s.summary().count.copy(), s.forecast_summary().count.copy(), s._state().fc_j)
         bad = good.astype(np.float64)
         bad[1, 1, 4, 66, 1] = -2.0
         with pytest.raises(ValueError, match=r"1 negative.*the first bad item is negative in chain 1 at \(draw 1, location 4, day 66, "
@@ -315,7 +315,7 @@ def test_load_trace_raises_before_a_product_call(api):
         with pytest.raises(ValueError, match=r"theta not finite in chain 0 at \(draw 2, parameter 7\)"):
             s.replay(th, good, summarize=True, forecast=True)
         assert not s.load_status().any()                       # the error cleared the counters
-        _same(counts, (s.summary().count, s.forecast_summary().count, s._fc_j))   # no product ran on the bad draws
+        _same(counts, (s.summary().count, s.forecast_summary().count, s._state().fc_j))   # no product ran on the bad draws
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -336,14 +336,12 @@ def test_refusals(api):
     wp = w.ctypes.data_as(_lib.c_double_p)
     model, s = _sampler(api, case, cfg, u, ev, eps, 4, record_events=False)
     with model, s:
-        s._rt_D = 3                                            # past the Python bookkeeping: the library refuses
         for call in (lambda: s.reset_rt(3, w), lambda: s.rt(0, 1), lambda: s.read_rt_draws(1), lambda: s.rt_summary()):
             with pytest.raises(_lib.SeirError, match="record_events=0") as e:
                 call()
             assert e.value.code == _lib.ERR_INVALID
     model, s = _sampler(api, case, cfg, u, ev, eps, 4)
     with model, s:
-        s._rt_D = 3
         for call in (lambda: s.rt(0, 1), lambda: s.read_rt_draws(1), lambda: s.rt_summary()):
             with pytest.raises(_lib.SeirError, match="seir_sampler_rt_reset") as e:         # before a reset
                 call()

@@ -15,7 +15,7 @@ import pytest
 import __graft_entry__ as entry
 from covid19uk_amd import _lib, hdf5io
 from covid19uk_amd.inference import inference as inf
-from covid19uk_amd.sampler import ChainSampler, RtSummary, Trace
+from covid19uk_amd.sampler import ChainSampler, ProductState, RtSummary, Trace
 from tests.test_forecast_host import ForecastStub
 from tests.test_summary_host import CFG, CTYPE, StubSampler, _read
 
@@ -263,8 +263,11 @@ class Recorder(ChainSampler):
 
     def __init__(self):
         self.calls = []
-        self._summary_on, self._forecast_H, self._rt_D, self._fc_j_snap = True, 2, 3, {}
+        self.state = ProductState(summary_on=1, forecast_H=2, rt_D=3)
         self._fallback_level = 0
+
+    def _state(self):
+        return self.state
 
     def __getattribute__(self, name):
         if name in ("snapshot", "reset_trace", "run", "summarize", "forecast", "rt", "trace_wait", "read_trace_async",
@@ -288,7 +291,7 @@ class Recorder(ChainSampler):
 
     def read_rt_draws(self, n, first=0):
         self.calls.append(("read_rt_draws", n))
-        return np.zeros((n, self.B, self._rt_D))
+        return np.zeros((n, self.B, self.state.rt_D))
 
 
 def test_a_burst_is_folded_behind_its_summary_and_forecast_and_not_at_all_when_off(monkeypatch):

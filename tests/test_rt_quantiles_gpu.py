@@ -360,14 +360,12 @@ def test_refusals(api):
     n, D = 4, 3
     model, s = _sampler(api, case, cfg, u, ev, eps, n, record_events=False)
     with model, s:
-        s._rt_D = D                                            # past the Python bookkeeping: the library refuses
         for call in (lambda: s.keep_rt_draws(4), lambda: s.rt_order_stats([0])):
             with pytest.raises(_lib.SeirError, match="record_events=0") as e:
                 call()
             assert e.value.code == _lib.ERR_INVALID
     model, s = _sampler(api, case, cfg, u, ev, eps, n)
     with model, s:
-        s._rt_D = D
         for call in (lambda: s.keep_rt_draws(4), lambda: s.rt_order_stats([0])):
             with pytest.raises(_lib.SeirError, match="seir_sampler_rt_reset") as e:         # before a reset
                 call()

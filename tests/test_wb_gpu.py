@@ -473,7 +473,6 @@ def test_refusals(api):
     T = case["k"].T
     model, s = _sampler(api, case, cfg, u, ev, eps, 4, record_events=False)
     with model, s:
-        s._wb_D = 3                                            # past the Python bookkeeping: the library refuses
         for call in (lambda: s.reset_within_between(3), lambda: s.within_between(0, 1), lambda: s.read_wb_draws(1),
                      lambda: s.within_between_summary()):
             with pytest.raises(_lib.SeirError, match="record_events=0") as e:
@@ -481,12 +480,10 @@ def test_refusals(api):
             assert e.value.code == _lib.ERR_INVALID
     model, s = _sampler(api, case, cfg, u, ev, eps, 4)
     with model, s:
-        s._wb_D = 3
         for call in (lambda: s.within_between(0, 1), lambda: s.read_wb_draws(1), lambda: s.within_between_summary()):
             with pytest.raises(_lib.SeirError, match="seir_sampler_wb_reset") as e:         # before a reset
                 call()
             assert e.value.code == _lib.ERR_STATE
-        s._wb_D = 0
         with pytest.raises(ValueError, match="before reset_within_between"):
             s.sample(2, within_between=True)
         for D in (0, T + 1, -1):

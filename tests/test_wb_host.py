@@ -315,7 +315,7 @@ def test_on_resets_once_folds_every_burst_behind_the_others_and_writes_the_group
 class WbRecorder(CheckRecorder):
     def __init__(self):
         super().__init__()
-        self._wb_D = 3
+        self.state = self.state._replace(wb_D=3)
 
     def __getattribute__(self, name):
         if name in ("within_between", "read_wb_draws_async"):
@@ -325,7 +325,7 @@ class WbRecorder(CheckRecorder):
 
     def read_wb_draws(self, n, first=0):
         self.calls.append(("read_wb_draws", n))
-        return {k: np.zeros((n, self.B, self._wb_D)) for k in WB_KEYS}
+        return {k: np.zeros((n, self.B, self.state.wb_D)) for k in WB_KEYS}
 
 
 def test_a_burst_is_folded_behind_summary_forecast_rt_and_check_and_not_at_all_when_off(monkeypatch):
@@ -339,7 +339,7 @@ def test_a_burst_is_folded_behind_summary_forecast_rt_and_check_and_not_at_all_w
     tr = s.sample(4, summarize=True, forecast=True, rt=True, check=True)
     assert not any("within_between" in c[0] or "wb" in c[0] for c in s.calls) and tr.wb is None
     s = WbRecorder()
-    s._wb_D = 0
+    s.state = s.state._replace(wb_D=0)
     with pytest.raises(ValueError, match="before reset_within_between"):
         s.sample(4, within_between=True)
     import covid19uk_amd.sampler as sm
