@@ -52,6 +52,8 @@ static int fail(int code, const char *fmt, ...) {
                         __FILE__, __LINE__);                                              \
     } while (0)
 
+#include "dev_mem.h"
+
 struct seir_ctx {
     Dims d{};
     Consts c{};
@@ -59,7 +61,7 @@ struct seir_ctx {
     int Bmax = 0, device = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    std::vector<void *> allocs;
+    std::vector<DevBuf> allocs;
     // staging for the host-pointer entry points
     double *u_stage = nullptr, *ev_stage = nullptr, *logp_stage = nullptr, *grad_stage = nullptr;
     // arguments of the last evaluation (seir_time_kernel replays them)
@@ -81,6 +83,13 @@ struct seir_ctx {
 
 static inline int ceil_to(int x, int q) { return (x + q - 1) / q * q; }
 
+// Trace slots per batch of a product: `base` of them, fewer where `per_slot` bytes of staging planes each would pass the staging
+// bound (SEIR_OPT_RT_STAGING_KIB, else RT_STAGING_BYTES); at least one slot is always taken.
+static int staging_slots(const seir_ctx *ctx, size_t base, size_t per_slot) {
+    const size_t bound = ctx->opt_rt_staging_kib ? (size_t)ctx->opt_rt_staging_kib << 10 : RT_STAGING_BYTES;
+    return (int)std::max<size_t>(1, std::min<size_t>(base, bound / per_slot));
+}
+
 // hipFuncSetAttribute applies to the current device's copy of a kernel: "done once" is kept per device (a bit per
 // ordinal), not per process
 static bool first_on_device(std::atomic<unsigned long long> &mask, int device) {
@@ -90,12 +99,11 @@ static bool first_on_device(std::atomic<unsigned long long> &mask, int device) {
 
 template <typename T>
 static int dev_alloc(seir_ctx *ctx, T **p, size_t count, bool zero = true) {
-    void *q = nullptr;
+    DevBuf b;
     const size_t bytes = count * sizeof(T);
-    HIP_TRY(hipMalloc(&q, bytes ? bytes : sizeof(T)));
-    ctx->allocs.push_back(q);
-    if (zero) HIP_TRY(hipMemset(q, 0, bytes ? bytes : sizeof(T)));
-    *p = (T *)q;
+    if (int rc = zero ? b.zeroed(bytes ? bytes : sizeof(T)) : b.alloc(bytes ? bytes : sizeof(T))) return rc;
+    *p = b.as<T>();
+    ctx->allocs.push_back(std::move(b));
     return 0;
 }
 
@@ -118,7 +126,6 @@ extern "C" void seir_destroy(seir_ctx *ctx) {
     release_eval_all(ctx);
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (void *p : ctx->allocs) (void)hipFree(p);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -376,8 +383,7 @@ template <int SRC>
 static void launch_scan(seir_ctx *ctx, const LaunchCfg &l, const double *events) {
     const Dims &d = l.d;
     const size_t lds = scan_lds_bytes(d.Tp);
-    if (lds > 64 * 1024)
-        (void)hipFuncSetAttribute((const void *)k_scan<SRC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)lds_attribute((const void *)k_scan<SRC>, lds);
     hipLaunchKernelGGL(k_scan<SRC>, dim3(d.nrb_scan, l.nb), dim3(SCAN_WAVES * WAVE), lds,
                        l.st, d, ctx->c, ctx->w, events);
 }
@@ -390,7 +396,7 @@ static void launch_gemm_t(seir_ctx *ctx, const LaunchCfg &l) {
     const size_t lds = gemm_lds_bytes<TN>();
     static std::atomic<unsigned long long> attr_set{0ull};
     if (lds > 64 * 1024 && first_on_device(attr_set, ctx->device))
-        (void)hipFuncSetAttribute((const void *)k_gemm<TN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)lds_attribute((const void *)k_gemm<TN>, lds);
     hipLaunchKernelGGL((k_gemm<TN>), dim3(d.Tp / TN, d.Mp / GEMM_TM, l.nb), dim3(gemm_threads<TN>()), lds, l.st, d, ctx->c,
                        ctx->w);
 }
@@ -411,7 +417,7 @@ static void launch_gemm(seir_ctx *ctx, const LaunchCfg &l) {
         const size_t lds = gemm_lds_bytes<96>();
         static std::atomic<unsigned long long> attr_set{0ull};
         if (lds > 64 * 1024 && first_on_device(attr_set, ctx->device))
-            (void)hipFuncSetAttribute((const void *)k_gemm_w8<GEMM_NCG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            (void)lds_attribute((const void *)k_gemm_w8<GEMM_NCG>, lds);
         hipLaunchKernelGGL(k_gemm_w8<GEMM_NCG>, dim3(d.Tp / 96, d.Mp / GEMM_TM, l.nb), dim3(256 * GEMM_NCG), lds, l.st, d, ctx->c, ctx->w);
     } else {
         launch_gemm_t<64>(ctx, l);
@@ -477,7 +483,7 @@ static void launch_state_params(seir_ctx *ctx, const LaunchCfg &l, const double 
     const size_t lds_a = (size_t)SCAN_WAVES * d.Tp * 2 * sizeof(double);
     static std::atomic<unsigned long long> attr_a{0ull};
     if (lds_a > 64 * 1024 && first_on_device(attr_a, ctx->device))
-        (void)hipFuncSetAttribute((const void *)k_state_params, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a);
+        (void)lds_attribute((const void *)k_state_params, lds_a);
     hipLaunchKernelGGL(k_state_params, dim3(d.nrb_scan + 1, l.nb), dim3(SCAN_WAVES * WAVE), lds_a, l.st, d, ctx->c, ctx->w,
                        events_dev, u_dev);
 }
@@ -494,14 +500,12 @@ static Dims fused_dims(const LaunchCfg &l) {
 // k_move_pair in the sampler -- are used only then.)
 static bool probe_xcd_local(hipStream_t st) {
     const int nblk = 8 * 144;
-    unsigned *xcc = nullptr;
+    DevBuf xcc;
     std::vector<unsigned> host(nblk, 99u);
-    hipError_t e = hipMalloc((void **)&xcc, nblk * sizeof(unsigned));
-    if (e != hipSuccess) return false;
-    hipLaunchKernelGGL(k_xcc_probe, dim3(nblk), dim3(256), 0, st, xcc);
-    e = hipMemcpyAsync(host.data(), xcc, nblk * sizeof(unsigned), hipMemcpyDeviceToHost, st);
+    if (xcc.alloc(nblk * sizeof(unsigned))) return false;
+    hipLaunchKernelGGL(k_xcc_probe, dim3(nblk), dim3(256), 0, st, xcc.as<unsigned>());
+    hipError_t e = hipMemcpyAsync(host.data(), xcc.p, nblk * sizeof(unsigned), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(xcc);
     bool ok = e == hipSuccess;
     for (int L = 8; L < nblk && ok; ++L) ok = host[L] == host[L & 7] && host[L] < 16u;
     for (int a = 0; a < 8 && ok; ++a)
@@ -554,8 +558,8 @@ static int launch_eval_all(seir_ctx *ctx, const LaunchCfg &l, const double *u_de
     const size_t lds = eval_all_lds_bytes<TN>(d);
     static std::atomic<unsigned long long> attr{0ull};
     if (lds > 64 * 1024 && first_on_device(attr, ctx->device)) {
-        (void)hipFuncSetAttribute((const void *)k_eval_all<true, TN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void *)k_eval_all<false, TN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)lds_attribute((const void *)k_eval_all<true, TN>, lds);
+        (void)lds_attribute((const void *)k_eval_all<false, TN>, lds);
     }
     const dim3 grid((unsigned)((1 + per + d.nrb_scan + ncb + 1) * nbv));
     // the reduction block runs inside the launch for value-only calls; with the gradient it is its own launch (measured:
@@ -584,8 +588,8 @@ static void launch_eval_tiles(seir_ctx *ctx, const LaunchCfg &l, const double *e
     const size_t lds_b = eval_tiles_lds_bytes<TN>();
     static std::atomic<unsigned long long> attr_b{0ull};
     if (lds_b > 64 * 1024 && first_on_device(attr_b, ctx->device)) {
-        (void)hipFuncSetAttribute((const void *)k_eval_tiles<true, TN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
-        (void)hipFuncSetAttribute((const void *)k_eval_tiles<false, TN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
+        (void)lds_attribute((const void *)k_eval_tiles<true, TN>, lds_b);
+        (void)lds_attribute((const void *)k_eval_tiles<false, TN>, lds_b);
     }
     const dim3 grid((unsigned)((d.ntc * d.nmt + d.nrb_scan + d.Tp / WAVE) * B));
     if (grad) hipLaunchKernelGGL((k_eval_tiles<true, TN>), grid, dim3(512), lds_b, l.st, d, ctx->c, ctx->w, events_dev, B);
@@ -638,7 +642,7 @@ extern "C" int seir_log_prob_dev(seir_ctx *ctx, int32_t B, const double *u_dev, 
                 Dims dq = d;
                 dq.nmt = d.Mp / GEMM_TM; dq.ntc = d.Tp / tn;
                 const size_t lds = tn == 96 ? eval_all_lds_bytes<96>(dq) : eval_all_lds_bytes<64>(dq);
-                if (lds > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                (void)lds_attribute(fn, lds);
                 if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 512, lds) != hipSuccess) occ = 0;
                 (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
                 ctx->eval_slots[ti][gi] = occ * cus;
@@ -664,8 +668,7 @@ extern "C" int seir_log_prob_dev(seir_ctx *ctx, int32_t B, const double *u_dev, 
         }
     } else {
         const size_t lds = scan_lds_bytes(d.Tp);
-        if (lds > 64 * 1024)
-            (void)hipFuncSetAttribute((const void *)k_scan_params, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)lds_attribute((const void *)k_scan_params, lds);
         hipLaunchKernelGGL(k_scan_params, dim3(d.nrb_scan + 1, B), dim3(SCAN_WAVES * WAVE), lds, l.st, d, ctx->c, ctx->w,
                            events_dev, u_dev);
         launch_gemm(ctx, l);
@@ -826,15 +829,15 @@ extern "C" int seir_selftest_math(seir_ctx *ctx, int32_t n, const double *x, dou
     int rc = check_batch(ctx, 1);
     if (rc) return rc;
     if (n < 1 || !x || !L || !inv || !lf) return fail(SEIR_ERR_INVALID, "bad arguments");
-    double *dx = nullptr;
-    HIP_TRY(hipMalloc((void **)&dx, sizeof(double) * 4 * n));
+    DevBuf buf;
+    if ((rc = buf.alloc(sizeof(double) * 4 * n))) return rc;
+    double *dx = buf.as<double>();
     HIP_TRY(hipMemcpy(dx, x, sizeof(double) * n, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_selftest_math, dim3(64), dim3(256), 0, ctx->stream, ctx->c, n, dx, dx + n, dx + 2 * n, dx + 3 * n);
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     HIP_TRY(hipMemcpy(L, dx + n, sizeof(double) * n, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(inv, dx + 2 * n, sizeof(double) * n, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(lf, dx + 3 * n, sizeof(double) * n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipFree(dx));
     return 0;
 }
 
@@ -844,7 +847,7 @@ static void launch_rt(seir_ctx *ctx, int nb, double *rit_dev) {
     const size_t lds = k_rt_lds_bytes<RT_TT>(d.Mp);
     static std::atomic<unsigned long long> attr_set{0ull};
     if (lds > 64 * 1024 && first_on_device(attr_set, ctx->device))
-        (void)hipFuncSetAttribute((const void *)k_rt<RT_TT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)lds_attribute((const void *)k_rt<RT_TT>, lds);
     hipLaunchKernelGGL(k_rt<RT_TT>, dim3((d.M + 63) / 64, (d.T + RT_TT - 1) / RT_TT, nb), dim3(256), lds, ctx->stream, d,
                        ctx->c, ctx->w, ctx->u_stage, rit_dev);
 }
@@ -856,8 +859,9 @@ extern "C" int seir_reproduction_number(seir_ctx *ctx, int32_t n, const double *
     if (n < 1 || !theta || !events || !R_it) return fail(SEIR_ERR_INVALID, "bad arguments");
     const Dims &d = ctx->d;
     const int Bm = ctx->Bmax;
-    double *rit_dev = nullptr;
-    HIP_TRY(hipMalloc((void **)&rit_dev, sizeof(double) * Bm * d.T * d.M));
+    DevBuf rit;
+    if ((rc = rit.alloc(sizeof(double) * Bm * d.T * d.M))) return rc;
+    double *rit_dev = rit.as<double>();
     for (int s0 = 0; s0 < n; s0 += Bm) {
         const int nb = std::min(Bm, n - s0);
         HIP_TRY(hipMemcpyAsync(ctx->u_stage, theta + (size_t)s0 * d.P, sizeof(double) * nb * d.P,
@@ -873,7 +877,6 @@ extern "C" int seir_reproduction_number(seir_ctx *ctx, int32_t n, const double *
                                hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
-    HIP_TRY(hipFree(rit_dev));
     ctx->prepared = false;                     // the scan overwrote the prepared-events workspace
     return 0;
 }
@@ -881,15 +884,6 @@ extern "C" int seir_reproduction_number(seir_ctx *ctx, int32_t n, const double *
 // ===========================================================================
 // Forward simulation (see include/seir_hip.h, "Chain-binomial forward simulation")
 // ===========================================================================
-namespace {
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) { HIP_TRY(hipMalloc(&p, bytes ? bytes : 8)); return 0; }
-    template <typename T> T *as() const { return (T *)p; }
-};
-}  // namespace
-
 __global__ void k_selftest_math_wide(Consts c, int n, const double *x, double *L, double *inv) {
     __shared__ double2 ltab[LDSTAB_N];
     log_table_to_lds(ltab, c.logtab);
@@ -1056,7 +1050,7 @@ extern "C" int seir_simulate(seir_ctx *ctx, const seir_sim_desc *sd) {
     if ((long long)S * M > 0x7fffffffLL) return fail(SEIR_ERR_INVALID, "num_steps * M overflows the cell counter");
     const size_t lds = k_simulate_lds_bytes(d);
     if (lds > 160 * 1024) return fail(SEIR_ERR_INVALID, "M=%d needs %zu B of LDS for the simulator", M, lds);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_simulate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIP_TRY(lds_attribute((const void *)k_simulate, lds));
     // draws per batch: bound the device output buffer to ~512 MB
     const size_t per_draw = (size_t)M * S * 3 * sizeof(double);
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)sd->num_draws, ((size_t)512 << 20) / per_draw));
@@ -1122,9 +1116,7 @@ extern "C" int seir_selftest_binomial(seir_ctx *ctx, int32_t count, const int32_
 // slots and whether that holds anything.  A shadow taken before the feature that owns the buffer was enabled or last reset
 // holds nothing of it (valid = false): restoring that slot leaves the buffer alone.
 struct Shadowed {
-    void *p = nullptr;
-    size_t bytes = 0;
-    void *snap[2] = {nullptr, nullptr};
+    DevBuf buf, snap[2];
     bool valid[2] = {false, false};
 };
 // One set of moment accumulators (MomentBufs' ref .. overflow) as ONE allocation, every part naturally aligned:
@@ -1136,42 +1128,33 @@ struct MomentAcc : Shadowed {
 };
 
 static void acc_layout(const MomentAcc &a, MomentBufs &mb) {
-    mb.sum = (int64_t *)a.p;
+    mb.sum = a.buf.as<int64_t>();
     mb.sumsq = (uint64_t *)(mb.sum + a.cells);
     mb.count = mb.sumsq + a.cells;
     mb.ref = (int32_t *)(mb.count + a.count_words());
     mb.overflow = (unsigned *)(mb.ref + a.cells);
 }
-static int acc_alloc(Shadowed &a, size_t bytes) {
-    a.bytes = bytes;
-    HIP_TRY(hipMalloc(&a.p, bytes));
-    HIP_TRY(hipMemset(a.p, 0, bytes));
-    return 0;
-}
 static int acc_alloc(MomentAcc &a, size_t cells, size_t B, MomentBufs &mb) {
     a.cells = cells; a.B = B;
-    if (int rc = acc_alloc(a, cells * (sizeof(int64_t) + sizeof(uint64_t) + sizeof(int32_t)) + a.count_words() * sizeof(uint64_t) + 8))
+    if (int rc = a.buf.zeroed(cells * (sizeof(int64_t) + sizeof(uint64_t) + sizeof(int32_t)) + a.count_words() * sizeof(uint64_t) + 8))
         return rc;
     acc_layout(a, mb);
     return 0;
 }
 static int acc_zero(Shadowed &a, hipStream_t st) {
-    HIP_TRY(hipMemsetAsync(a.p, 0, a.bytes, st));
+    HIP_TRY(hipMemsetAsync(a.buf.p, 0, a.buf.bytes, st));
     return 0;
 }
 // save: the buffer into the slot's shadow; else the shadow back, if it holds anything.  In stream order.
 static int acc_shadow(Shadowed &a, int slot, bool save, hipStream_t st) {
     if (!save && !a.valid[slot]) return 0;
-    if (!a.snap[slot]) HIP_TRY(hipMalloc(&a.snap[slot], a.bytes));
-    HIP_TRY(hipMemcpyAsync(save ? a.snap[slot] : a.p, save ? a.p : a.snap[slot], a.bytes, hipMemcpyDeviceToDevice, st));
+    if (!a.snap[slot])
+        if (int rc = a.snap[slot].alloc(a.buf.bytes)) return rc;
+    HIP_TRY(hipMemcpyAsync(save ? a.snap[slot].p : a.buf.p, save ? a.buf.p : a.snap[slot].p, a.buf.bytes, hipMemcpyDeviceToDevice, st));
     if (save) a.valid[slot] = true;
     return 0;
 }
 static void acc_invalidate(Shadowed &a) { a.valid[0] = a.valid[1] = false; }
-static void acc_free(Shadowed &a) {
-    for (void *q : {a.p, a.snap[0], a.snap[1]}) if (q) (void)hipFree(q);
-    a = Shadowed{};
-}
 // Blocking read of whichever parts are asked for, and of the sticky overflow flag.
 static int acc_read(const MomentAcc &a, hipStream_t st, uint64_t *count, int32_t *ref, int64_t *sum, uint64_t *sumsq, unsigned *flag) {
     MomentBufs mb{};
@@ -1187,7 +1170,7 @@ static int acc_read(const MomentAcc &a, hipStream_t st, uint64_t *count, int32_t
 
 // The per-slot group sums of one source (seir_sampler_groups_set): ev [cap][B][G][L][3], st0 [cap][B][G][3] (null for the trace).
 struct GroupOut {
-    int64_t *ev = nullptr, *st0 = nullptr;
+    DevBuf ev, st0;                   // int64
     int L = 0;                        // day extent the arrays are sized for; 0: none (no table, or the source is off)
 };
 
@@ -1197,10 +1180,12 @@ struct GroupOut {
 struct GroupCurve {
     bool on = false;
     int planes = 1;
-    int D = 0, slots = 0;             // window days the buffers are sized for; trace slots per batch
-    int *offsets = nullptr;           // device copy of the table's offsets [G + 1]
-    double *weights = nullptr;        // [nnz] aligned with the members (group R_t), or null
-    double *cells[2] = {nullptr, nullptr}, *out[2] = {nullptr, nullptr};
+    DevBuf weights;                   // double [nnz] aligned with the members (group R_t), or empty
+    struct Bufs {                     // what the table and the window size; Bufs{}: none, the switch and the weights stay
+        int D = 0, slots = 0;         // window days the buffers are sized for; trace slots per batch
+        DevBuf offsets;               // device copy of the table's offsets [G + 1], int
+        DevBuf cells[2], out[2];      // double
+    } b;
 };
 
 // The group next-generation matrix of the kept draws (seir_sampler_group_ngm; ngm_kernels.h): the draw store
@@ -1209,9 +1194,9 @@ struct GroupCurve {
 struct GroupNgm {
     long long cap = 0;                // draws per chain the store holds
     int D = 0, slots = 0;             // window days the buffers are sized for; trace slots per batch
-    int *offsets = nullptr;           // device copy of the table's offsets [G + 1]
-    double *weights = nullptr;        // [nnz] aligned with the members
-    double *P = nullptr, *out = nullptr;
+    DevBuf offsets;                   // device copy of the table's offsets [G + 1], int
+    DevBuf weights;                   // double [nnz] aligned with the members
+    DevBuf P, out;                    // double
 };
 
 // The host's half of a ForecastBufs that is rolled forward day by day from the kept draws (forecast_kernels.h): the forecast
@@ -1221,7 +1206,7 @@ struct Rollout {
     ForecastBufs fb{};
     int slots = 0;                    // trace slots per batch: min(cap, FC_JMAX)
     int ndmax = 0;                    // row stride the planes are allocated for: ceil64(slots * B)
-    std::vector<void *> allocs;       // device buffers sized by fb.H (allocated again when it changes)
+    std::vector<DevBuf> allocs;       // device buffers sized by fb.H (allocated again when it changes)
     MomentAcc acc;                    // fb.mom's ref .. overflow
     long long j = 0;                  // draws per chain rolled forward since the last reset (the j of the draw id)
     long long snap_j[2] = {0, 0};     // j as it was when acc's shadows were taken
@@ -1236,7 +1221,7 @@ struct seir_sampler {
     // instances the planner can choose (24-row / this shape's 32-row tiles), k_move_pairs allowed its LDS request
     int cus = 0, leap_occ[2] = {0, 0};
     bool pairs_lds_attr = false;
-    std::vector<void *> allocs;
+    std::vector<DevBuf> allocs;
     // chains are independent: they are split into groups that run on their own streams
     // so that one group's single-workgroup-per-chain kernels overlap another group's wide ones
     int ngroups = 1;
@@ -1274,7 +1259,7 @@ struct seir_sampler {
     enum { R_OTHER = 0, R_STATE = 1, R_HANDOFF = 2 };
     struct Region { void *p; size_t bytes; int kind; };
     std::vector<Region> regions;
-    void *snap[2] = {nullptr, nullptr};   // shadow copies of the STATE regions, packed
+    DevBuf snap[2];                       // shadow copies of the STATE regions, packed
     bool snap_valid[2] = {false, false};
     size_t snap_bytes = 0;
     bool poisoned = false;            // a fatal hand-off time-out was reported: no sweeps until set_state / refresh / restore
@@ -1293,11 +1278,11 @@ struct seir_sampler {
     Shadowed diag_buf;
     // --- forecast of the next H days (seir_sampler_forecast_reset ...; forecast_kernels.h) ---
     Rollout fc;
-    double *fc_steps_host = nullptr;  // page-locked [cap][B][H]: the caller's random-walk steps on their way to the device
+    PinnedBuf fc_steps_host;          // page-locked double [cap][B][H]: the caller's random-walk steps on their way to the device
     double *fc_steps_dev = nullptr;   // [fc.slots * B][H] (one of fc.allocs)
     hipEvent_t fc_ev_steps = nullptr; // behind the last upload from fc_steps_host
     bool fc_steps_pending = false;
-    int *fc_keep = nullptr;           // the draw store keep[B][3][M][H][fc_keep_cap] (seir_sampler_forecast_keep), or null: off
+    DevBuf fc_keep;                   // the draw store int keep[B][3][M][H][fc_keep_cap] (seir_sampler_forecast_keep), or empty: off
     long long fc_keep_cap = 0;        // draws per chain it holds; position j of a cell is the draw with the forecast's j
     // --- in-sample check of the last K days (seir_sampler_check_reset ...; check_kernels.h): a Rollout with H := K ---
     Rollout ck;                       // its j is not the forecast's
@@ -1308,9 +1293,9 @@ struct seir_sampler {
     bool rt_on = false;
     RtBufs rt{};
     int rt_slots = 0;                 // trace slots the batch planes (ea, S, part) are allocated for
-    std::vector<void *> rt_allocs;    // device buffers sized by the window (allocated again when it changes)
+    std::vector<DevBuf> rt_allocs;    // device buffers sized by the window (allocated again when it changes)
     Shadowed rt_acc;                  // sum [cells] | sumsq [cells] | ref [cells] | count [B, padded] | gt1 [cells]
-    double *rt_keep = nullptr;        // the draw store keepR[B][D][M][rt_keep_stride] (seir_sampler_rt_keep), or null: off
+    DevBuf rt_keep;                   // the draw store double keepR[B][D][M][rt_keep_stride] (seir_sampler_rt_keep), or empty: off
     long long rt_keep_cap = 0;        // draws per chain it holds; position j of a cell is the chain's j-th draw since the reset
     long long rt_keep_stride = 0;     // cap rounded up to RT_KEEP_RUN: every run of a cell is aligned
     long long rt_j = 0;               // the host's copy of RtBufs::count (the same for every chain: calls take all of them)
@@ -1319,11 +1304,12 @@ struct seir_sampler {
     bool wb_on = false;
     WbBufs wb{};
     int wb_slots = 0;                 // trace slots the batch planes (I, part) are allocated for
-    std::vector<void *> wb_allocs;    // device buffers sized by the window (allocated again when it changes)
+    std::vector<DevBuf> wb_allocs;    // device buffers sized by the window (allocated again when it changes)
     Shadowed wb_acc;                  // sum_w | sumsq_w | ref_w | ref_b | sum_b [cells] | count [B, padded] | n [cells] | gt [cells]
     // --- region totals of the kept draws (seir_sampler_groups_set ...; group_kernels.h) ---
     bool grp_on = false;              // a table is set
-    GroupTable grp{};                 // its device copy: segments and members
+    GroupTable grp{};                 // its device copy: segments and members, out of grp_seg and grp_members
+    DevBuf grp_seg, grp_members;
     GroupOut grp_out[3];              // per-slot outputs of the trace, the forecast and the check (L = 0: that source is off)
     // --- group curves: R_t and within / between per group (seir_sampler_group_rt / _group_wb; group_curve_kernels.h) ---
     std::vector<int> grp_offsets;     // the table's offsets [G + 1] on the host (the device copy exists only with a curve on)
@@ -1338,31 +1324,19 @@ struct seir_sampler {
     std::vector<std::pair<int, int>> load_calls;   // (chain, first) of the calls since the last clear, by tag
 };
 
-// Zeroed device memory, registered in `list` (seir_sampler::allocs: freed with the sampler; Rollout::allocs: also when the length
-// changes) and, when it is chain state or hand-off scratch, in the regions a snapshot / restore goes through.
+// Zeroed device memory (DevBuf::zeroed) owned by `list` (seir_sampler::allocs: freed with the sampler; Rollout::allocs: also when
+// the length changes) and, when it is chain state or hand-off scratch, in the regions a snapshot / restore goes through.
 template <typename T>
-static int s_alloc(seir_sampler *s, std::vector<void *> &list, T **p, size_t count, int kind = seir_sampler::R_OTHER) {
-    void *q = nullptr;
-    const size_t bytes = (count ? count : 1) * sizeof(T);
-    HIP_TRY(hipMalloc(&q, bytes));
-    list.push_back(q);
-    if (kind != seir_sampler::R_OTHER) s->regions.push_back({q, bytes, kind});
-    // hipMemset may return before the device is done, and the null stream is not ordered with the (non-blocking) stream the
-    // kernels run on: without the wait a kernel enqueued right behind the allocation can find its output zeroed under it
-    HIP_TRY(hipMemset(q, 0, bytes));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    *p = (T *)q;
+static int s_alloc(seir_sampler *s, std::vector<DevBuf> &list, T **p, size_t count, int kind = seir_sampler::R_OTHER) {
+    DevBuf b;
+    if (int rc = b.zeroed((count ? count : 1) * sizeof(T))) return rc;
+    if (kind != seir_sampler::R_OTHER) s->regions.push_back({b.p, b.bytes, kind});
+    *p = b.as<T>();
+    list.push_back(std::move(b));
     return 0;
 }
 #define S_ALLOC(list, ptr, ...) if (!rc) rc = s_alloc(s, s->list, &(ptr), __VA_ARGS__)
 
-static void rollout_free(Rollout &r) {
-    for (void *p : r.allocs) (void)hipFree(p);
-    r.allocs.clear();
-    acc_free(r.acc);
-    r.on = false;
-    r.fb = ForecastBufs{};
-}
 // The moments with the draw counter: a restore from a slot that holds nothing of them leaves both alone.
 static int rollout_shadow(Rollout &r, int slot, bool save, hipStream_t st) {
     if (save) r.snap_j[slot] = r.j;
@@ -1370,45 +1344,17 @@ static int rollout_shadow(Rollout &r, int slot, bool save, hipStream_t st) {
     return acc_shadow(r.acc, slot, save, st);
 }
 
-// Frees the buffers of a family of group curves; its switch and weights stay.
-static void gcurve_release(GroupCurve &c) {
-    for (int x = 0; x < 2; ++x) {
-        if (c.cells[x]) (void)hipFree(c.cells[x]);
-        if (c.out[x]) (void)hipFree(c.out[x]);
-        c.cells[x] = c.out[x] = nullptr;
-    }
-    if (c.offsets) (void)hipFree(c.offsets);
-    c.offsets = nullptr;
-    c.D = c.slots = 0;
-}
-// Switches group R_t off: its weights belonged to the table that was in force.
-static void gcurve_rt_off(seir_sampler *s) {
-    gcurve_release(s->grt);
-    if (s->grt.weights) (void)hipFree(s->grt.weights);
-    s->grt.weights = nullptr;
-    s->grt.on = false;
-}
 static int gcurve_fit(seir_sampler *s, bool rt);     // with the rest of the group curves, behind the within/between shares
-// Switches the group next-generation matrix off and frees its store: its weights belonged to the table, its sizes to D.
-static void ngm_off(seir_sampler *s) {
-    GroupNgm &n = s->ngm;
-    for (void *p : {(void *)n.offsets, (void *)n.weights, (void *)n.P, (void *)n.out})
-        if (p) (void)hipFree(p);
-    n = GroupNgm{};
-}
 
+// No table: what was sized by it or weighted along its members goes with it -- the group next-generation matrix, group R_t
+// (switch and weights), the buffers of group within / between (its switch stays), the sources' outputs.
 static void groups_free(seir_sampler *s) {
-    ngm_off(s);
-    gcurve_rt_off(s);
-    gcurve_release(s->gwb);
+    s->ngm = GroupNgm{};
+    s->grt = GroupCurve{};
+    s->gwb.b = {};
     s->grp_offsets.clear();
-    for (GroupOut &o : s->grp_out) {
-        if (o.ev) (void)hipFree(o.ev);
-        if (o.st0) (void)hipFree(o.st0);
-        o = GroupOut{};
-    }
-    if (s->grp.seg) (void)hipFree(const_cast<int *>(s->grp.seg));
-    if (s->grp.members) (void)hipFree(const_cast<int *>(s->grp.members));
+    for (GroupOut &o : s->grp_out) o = GroupOut{};
+    s->grp_seg.reset(); s->grp_members.reset();
     s->grp = GroupTable{};
     s->grp_on = false;
 }
@@ -1431,23 +1377,13 @@ extern "C" void seir_sampler_destroy(seir_sampler *s) {
     if (s->copy_stream) { (void)hipStreamSynchronize(s->copy_stream); (void)hipStreamDestroy(s->copy_stream); }
     if (s->ev_burst) (void)hipEventDestroy(s->ev_burst);
     if (s->ev_copy) (void)hipEventDestroy(s->ev_copy);
-    for (void *p : s->allocs) (void)hipFree(p);
-    for (void *p : s->snap) if (p) (void)hipFree(p);
-    for (void *p : s->rt_allocs) (void)hipFree(p);
-    for (void *p : s->wb_allocs) (void)hipFree(p);
-    rollout_free(s->fc); rollout_free(s->ck);
-    acc_free(s->sum_acc); acc_free(s->diag_buf); acc_free(s->rt_acc); acc_free(s->ck_cnt); acc_free(s->wb_acc);
-    if (s->fc_steps_host) (void)hipHostFree(s->fc_steps_host);
-    if (s->fc_keep) (void)hipFree(s->fc_keep);
-    if (s->rt_keep) (void)hipFree(s->rt_keep);
-    groups_free(s);
     if (s->fc_ev_steps) (void)hipEventDestroy(s->fc_ev_steps);
     if (s->ev_load) (void)hipEventDestroy(s->ev_load);
     Work &w = s->ctx->w;
     for (int x = 0; x < 3; ++x) { w.K[x] = nullptr; w.St[x] = nullptr; }
     w.rowtot = w.rngtot = nullptr;
     w.TS = w.sp = w.gst = w.Vt = w.acur = w.rirc = w.CT = w.CG = w.Lpart0 = nullptr;
-    delete s;
+    delete s;                                        // every buffer goes with its owner (dev_mem.h), behind the waits above
 }
 
 // The kernel instances a sweep launches, for the numbers of its plan (sweep_plan.h).
@@ -1654,11 +1590,10 @@ extern "C" int seir_sampler_create(seir_ctx *ctx, const seir_sampler_desc *ds, s
         // k_move_pairs asks for more than half a CU's LDS (one workgroup per CU); the other event-update kernels only above
         // the default 64 KB
         const int nch = move_nch(d.Tp);
-        s->pairs_lds_attr = hipFuncSetAttribute((const void *)move_pairs_fn(nch), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                (int)k_move_pairs_lds_bytes(d)) == hipSuccess;
+        s->pairs_lds_attr = lds_attribute((const void *)move_pairs_fn(nch), k_move_pairs_lds_bytes(d)) == hipSuccess;
         const size_t plds = k_move_pa2_lds_bytes(d);
         for (const void *fn : {(const void *)move_pair_fn(nch), (const void *)move_pa2_fn(nch)})
-            if (plds > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds);
+            (void)lds_attribute(fn, plds);
     }
     if (rc) { seir_sampler_destroy(s); return rc; }
     *out = s;
@@ -1735,7 +1670,7 @@ static size_t summary_cells(const seir_sampler *s) { return (size_t)s->cfg.B * s
 static size_t diag_words(const seir_sampler *s) { return 6 * summary_cells(s) + 3 * (size_t)s->cfg.B; }
 static uint64_t *diag_mark(const seir_sampler *s, int which) {       // count [B] | sum [n] | sumsq [n]
     const size_t n = summary_cells(s), B = (size_t)s->cfg.B;
-    return (uint64_t *)s->diag_buf.p + 2 * n + B + (size_t)which * (B + 2 * n);
+    return s->diag_buf.buf.as<uint64_t>() + 2 * n + B + (size_t)which * (B + 2 * n);
 }
 static int moments_shadow(seir_sampler *s, int slot, bool save) {
     hipStream_t st = s->ctx->stream;
@@ -1769,12 +1704,12 @@ extern "C" int seir_sampler_snapshot(seir_sampler *s, int32_t slot) {
     if (!s->snap_bytes)
         for (const auto &r : s->regions)
             if (r.kind == seir_sampler::R_STATE) s->snap_bytes += (r.bytes + 255) / 256 * 256;
-    if (!s->snap[slot]) HIP_TRY(hipMalloc(&s->snap[slot], s->snap_bytes));
+    if (!s->snap[slot] && (rc = s->snap[slot].alloc(s->snap_bytes))) return rc;
     // in stream order: the snapshot is the state after everything queued so far
     size_t off = 0;
     for (const auto &r : s->regions)
         if (r.kind == seir_sampler::R_STATE) {
-            HIP_TRY(hipMemcpyAsync((char *)s->snap[slot] + off, r.p, r.bytes, hipMemcpyDeviceToDevice, s->ctx->stream));
+            HIP_TRY(hipMemcpyAsync(s->snap[slot].as<char>() + off, r.p, r.bytes, hipMemcpyDeviceToDevice, s->ctx->stream));
             off += (r.bytes + 255) / 256 * 256;
         }
     s->snap_valid[slot] = true;
@@ -1793,7 +1728,7 @@ extern "C" int seir_sampler_restore(seir_sampler *s, int32_t slot) {
     size_t off = 0;
     for (const auto &r : s->regions)
         if (r.kind == seir_sampler::R_STATE) {
-            HIP_TRY(hipMemcpyAsync(r.p, (const char *)s->snap[slot] + off, r.bytes, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemcpyAsync(r.p, s->snap[slot].as<const char>() + off, r.bytes, hipMemcpyDeviceToDevice, st));
             off += (r.bytes + 255) / 256 * 256;
         }
     if ((rc = reset_handoffs(s))) return rc;
@@ -1819,8 +1754,8 @@ extern "C" int seir_sampler_product_state(seir_sampler *s, seir_product_state *o
     for (int which = 0; which < 3; ++which) p.group_L[which] = s->grp_out[which].L;
     p.group_rt_on = s->grt.on;
     p.group_wb_on = s->gwb.on;
-    p.group_rt_D = s->grt.D;
-    p.group_wb_D = s->gwb.D;
+    p.group_rt_D = s->grt.b.D;
+    p.group_wb_D = s->gwb.b.D;
     p.ngm_D = s->ngm.D;
     p.fc_j = s->fc.j;
     p.ck_j = s->ck.j;
@@ -2524,19 +2459,14 @@ static int groups_source_len(const seir_sampler *s, int which) {
     return r.on ? r.fb.H : 0;
 }
 
-// Bytes of the outputs of source `which` at G groups and L days, and the refusal above half of the device's free memory.
+// Bytes of the outputs of source `which` at G groups and L days, and their refusal above half of the device's free memory.
 static unsigned long long groups_bytes(const seir_sampler *s, int G, int which, int L) {
     const unsigned long long rows = (unsigned long long)s->cfg.cap * s->cfg.B * G;
     return rows * L * 3ull * 8ull + (which ? rows * 3ull * 8ull : 0ull);
 }
 static int groups_refuse_bytes(const seir_sampler *s, unsigned long long bytes, int G) {
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    // half of what is free: the policy of a device that is shared, not a measurement
-    if (bytes > (unsigned long long)free_b / 2)
-        return fail(SEIR_ERR_INVALID, "the group sums need %llu bytes (%d slots x %d chains x %d groups x 24 per day and per state), "
-                    "more than half of the %llu bytes free on the device", bytes, s->cfg.cap, s->cfg.B, G, (unsigned long long)free_b);
-    return 0;
+    return refuse_above_half_free(bytes, "the group sums need %llu bytes (%d slots x %d chains x %d groups x 24 per day and per state)",
+                                  bytes, s->cfg.cap, s->cfg.B, G);
 }
 
 // Size the outputs of source `which` for the table and the source's present length (none when either is off).
@@ -2545,27 +2475,17 @@ static int groups_fit(seir_sampler *s, int which) {
     const int L = s->grp_on ? groups_source_len(s, which) : 0;
     if (L == o.L) return 0;
     if (int rc = drain(s)) return rc;
-    if (o.ev) (void)hipFree(o.ev);
-    if (o.st0) (void)hipFree(o.st0);
     o = GroupOut{};
     if (L == 0) return 0;
     const unsigned long long rows = (unsigned long long)s->cfg.cap * s->cfg.B * s->grp.G;
     const unsigned long long bytes = groups_bytes(s, s->grp.G, which, L);
     if (int rc = groups_refuse_bytes(s, bytes, s->grp.G)) return rc;
     // both arrays or neither: a source whose outputs could not be made has none (L = 0) and is not launched for
-    void *ev = nullptr, *st0 = nullptr;
-    const size_t ev_bytes = (size_t)(rows * L * 3ull * 8ull), st_bytes = (size_t)(rows * 3ull * 8ull);
-    hipError_t e = hipMalloc(&ev, ev_bytes);
-    if (e == hipSuccess) e = hipMemset(ev, 0, ev_bytes);
-    if (e == hipSuccess && which) e = hipMalloc(&st0, st_bytes);
-    if (e == hipSuccess && which) e = hipMemset(st0, 0, st_bytes);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // the zeroing is done: see s_alloc
-    if (e != hipSuccess) {
-        if (ev) (void)hipFree(ev);
-        if (st0) (void)hipFree(st0);
-        return fail(SEIR_ERR_DEVICE, "allocating %llu bytes of group sums failed: %s", bytes, hipGetErrorString(e));
-    }
-    o.ev = (int64_t *)ev; o.st0 = (int64_t *)st0; o.L = L;
+    GroupOut made;
+    if (made.ev.zeroed((size_t)(rows * L * 3ull * 8ull)) || (which && made.st0.zeroed((size_t)(rows * 3ull * 8ull))))
+        return alloc_failed(bytes, "group sums");
+    made.L = L;
+    o = std::move(made);
     return 0;
 }
 
@@ -2576,8 +2496,8 @@ static bool groups_live(const seir_sampler *s, int which) { return s->grp_on && 
 static int groups_zero(seir_sampler *s, int which, int32_t first, int32_t count) {
     const GroupOut &o = s->grp_out[which];
     const size_t row = (size_t)s->cfg.B * s->grp.G;
-    HIP_TRY(hipMemsetAsync(o.ev + (size_t)first * row * o.L * 3, 0, sizeof(int64_t) * count * row * o.L * 3, s->ctx->stream));
-    if (o.st0) HIP_TRY(hipMemsetAsync(o.st0 + (size_t)first * row * 3, 0, sizeof(int64_t) * count * row * 3, s->ctx->stream));
+    HIP_TRY(hipMemsetAsync(o.ev.as<int64_t>() + (size_t)first * row * o.L * 3, 0, sizeof(int64_t) * count * row * o.L * 3, s->ctx->stream));
+    if (o.st0) HIP_TRY(hipMemsetAsync(o.st0.as<int64_t>() + (size_t)first * row * 3, 0, sizeof(int64_t) * count * row * 3, s->ctx->stream));
     return 0;
 }
 
@@ -2600,14 +2520,12 @@ extern "C" int seir_sampler_groups_set(seir_sampler *s, int32_t G, const int32_t
         if (const int L = groups_source_len(s, which)) need += groups_bytes(s, G, which, L);
     if ((rc = groups_refuse_bytes(s, need, G))) return rc;
     DevBuf dseg, dmem;
-    const size_t nnz = (size_t)offsets[G];
-    if ((rc = dseg.alloc(seg.size() * sizeof(int))) || (rc = dmem.alloc(nnz * sizeof(int)))) return rc;
-    HIP_TRY(hipMemcpy(dseg.p, seg.data(), seg.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dmem.p, members, nnz * sizeof(int), hipMemcpyHostToDevice));
+    if ((rc = dseg.upload(seg.data(), seg.size() * sizeof(int))) || (rc = dmem.upload(members, (size_t)offsets[G] * sizeof(int))))
+        return rc;
     if ((rc = drain(s))) return rc;
     groups_free(s);
-    s->grp.seg = dseg.as<int>(); s->grp.members = dmem.as<int>();
-    dseg.p = dmem.p = nullptr;                       // the sampler owns them now
+    s->grp_seg = std::move(dseg); s->grp_members = std::move(dmem);
+    s->grp.seg = s->grp_seg.as<int>(); s->grp.members = s->grp_members.as<int>();
     s->grp.nseg = (int)(seg.size() / 3);
     s->grp.G = G;
     s->grp_on = true;
@@ -2621,8 +2539,8 @@ extern "C" int seir_sampler_groups_set(seir_sampler *s, int32_t G, const int32_t
 static int copy_group_marginals(seir_sampler *s, hipStream_t st, int which, int32_t first, int32_t count, int64_t *ev, int64_t *st0) {
     const GroupOut &o = s->grp_out[which];
     const size_t row = (size_t)s->cfg.B * s->grp.G, f = (size_t)first, n = (size_t)count;
-    if (ev) HIP_TRY(hipMemcpyAsync(ev, o.ev + f * row * o.L * 3, sizeof(int64_t) * n * row * o.L * 3, hipMemcpyDeviceToHost, st));
-    if (st0) HIP_TRY(hipMemcpyAsync(st0, o.st0 + f * row * 3, sizeof(int64_t) * n * row * 3, hipMemcpyDeviceToHost, st));
+    if (ev) HIP_TRY(hipMemcpyAsync(ev, o.ev.as<int64_t>() + f * row * o.L * 3, sizeof(int64_t) * n * row * o.L * 3, hipMemcpyDeviceToHost, st));
+    if (st0) HIP_TRY(hipMemcpyAsync(st0, o.st0.as<int64_t>() + f * row * 3, sizeof(int64_t) * n * row * 3, hipMemcpyDeviceToHost, st));
     return 0;
 }
 
@@ -2739,7 +2657,7 @@ extern "C" int seir_sampler_summarize(seir_sampler *s, int32_t first, int32_t co
     if (groups_live(s, 0)) {                         // the region totals of the same slots
         if ((rc = groups_zero(s, 0, first, count))) return rc;
         groups_launch(d, l.st, s->grp, s->cfg.ev16 != 0, s->ch.tr_events, d.M, d.T, (long long)first * B, (long long)first * B,
-                      (long long)count * B, s->grp_out[0].ev, nullptr, 0, 0, nullptr);
+                      (long long)count * B, s->grp_out[0].ev.as<int64_t>(), nullptr, 0, 0, nullptr);
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -2788,10 +2706,10 @@ extern "C" int seir_sampler_diag_reset(seir_sampler *s, int32_t batch_len) {
     if (batch_len < 1) return fail(SEIR_ERR_INVALID, "batch_len=%d: a batch has at least one draw", batch_len);
     if ((rc = need_events(s, "diagnose"))) return rc;
     if (!s->diag_on) {
-        if ((rc = acc_alloc(s->diag_buf, diag_words(s) * sizeof(uint64_t)))) return rc;
+        if ((rc = s->diag_buf.buf.zeroed(diag_words(s) * sizeof(uint64_t)))) return rc;
         const size_t n = summary_cells(s);
-        s->diag.bsum = (int64_t *)s->diag_buf.p;
-        s->diag.bsumsq = (uint64_t *)s->diag_buf.p + n;
+        s->diag.bsum = s->diag_buf.buf.as<int64_t>();
+        s->diag.bsumsq = s->diag_buf.buf.as<uint64_t>() + n;
         s->diag.nbatch = s->diag.bsumsq + n;
         s->diag_on = true;
     }
@@ -2882,7 +2800,8 @@ static int rollout_refuse(const seir_sampler *s, const TraceUser &who, const dou
 static int rollout_resize(seir_sampler *s, Rollout &r, int H) {
     int rc = drain(s);
     if (rc) return rc;
-    rollout_free(r);
+    r.allocs.clear(); r.acc = MomentAcc{}; r.fb = ForecastBufs{};   // everything sized by H; j stays until the reset that follows
+    r.on = false;
     const Dims &d = s->ctx->d;
     const size_t B = (size_t)s->cfg.B, cap = (size_t)s->cfg.cap;
     ForecastBufs &fb = r.fb;
@@ -2903,7 +2822,7 @@ static int rollout_resize(seir_sampler *s, Rollout &r, int H) {
     if (rc) return rc;
     fb.W = Wd; fb.wd = wdd;
     fb.H = H;
-    (void)hipFuncSetAttribute((const void *)k_gemm<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_lds_bytes<64>());
+    (void)lds_attribute((const void *)k_gemm<64>, gemm_lds_bytes<64>());
     return 0;
 }
 
@@ -2938,8 +2857,8 @@ struct RolloutBatch { int j0, nj, ND, ndp; };
 static void groups_rollout_batch(seir_sampler *s, int which, const Dims &d, hipStream_t st, const ForecastBufs &fb, int32_t first,
                                  const RolloutBatch &bt) {
     const GroupOut &o = s->grp_out[which];
-    groups_launch(d, st, s->grp, false, fb.fev, d.M, fb.H, 0, (long long)(first + bt.j0) * s->cfg.B, bt.ND, o.ev, fb.St0,
-                  (long long)d.Mp * bt.ndp, bt.ndp, o.st0);
+    groups_launch(d, st, s->grp, false, fb.fev, d.M, fb.H, 0, (long long)(first + bt.j0) * s->cfg.B, bt.ND, o.ev.as<int64_t>(),
+                  fb.St0, (long long)d.Mp * bt.ndp, bt.ndp, o.st0.as<int64_t>());
 }
 
 // The draws of trace slots [first, first + count) rolled forward fb.H days, in batches of at most r.slots slots.  Per batch:
@@ -2989,8 +2908,8 @@ extern "C" int seir_sampler_forecast_reset(seir_sampler *s, int32_t horizon, con
     if (!r.on || r.fb.H != horizon) {
         if ((rc = rollout_resize(s, r, horizon))) return rc;
         // the steps' buffers and the draw store are sized by H as well; the stream is idle
-        if (s->fc_steps_host) { (void)hipHostFree(s->fc_steps_host); s->fc_steps_host = nullptr; }
-        if (s->fc_keep) { (void)hipFree(s->fc_keep); s->fc_keep = nullptr; s->fc_keep_cap = 0; }
+        s->fc_steps_host.reset();
+        s->fc_keep.reset(); s->fc_keep_cap = 0;
         S_ALLOC(fc.allocs, s->fc_steps_dev, (size_t)r.slots * s->cfg.B * horizon);
         if (rc) return rc;
         if (!s->fc_ev_steps) HIP_TRY(hipEventCreate(&s->fc_ev_steps));
@@ -3018,14 +2937,14 @@ extern "C" int seir_sampler_forecast(seir_sampler *s, int32_t first, int32_t cou
     if (log_baseline_steps) {
         // through page-locked memory indexed by trace slot, so that the call stays asynchronous; a slot's steps are
         // overwritten only once the upload that read them last has been done
-        if (!s->fc_steps_host) HIP_TRY(hipHostMalloc((void **)&s->fc_steps_host, sizeof(double) * s->cfg.cap * B * H, hipHostMallocDefault));
+        if (!s->fc_steps_host.p) HIP_TRY(hipHostMalloc(&s->fc_steps_host.p, sizeof(double) * s->cfg.cap * B * H, hipHostMallocDefault));
         if (s->fc_steps_pending) { HIP_TRY(hipEventSynchronize(s->fc_ev_steps)); s->fc_steps_pending = false; }
-        std::memcpy(s->fc_steps_host + (size_t)first * B * H, log_baseline_steps, sizeof(double) * count * B * H);
+        std::memcpy(s->fc_steps_host.as<double>() + (size_t)first * B * H, log_baseline_steps, sizeof(double) * count * B * H);
     }
     rc = rollout_days(s, r, first, count,
         [&](ForecastBufs &fb, const RolloutBatch &bt) {
             if (log_baseline_steps) {
-                HIP_TRY(hipMemcpyAsync(s->fc_steps_dev, s->fc_steps_host + (size_t)(first + bt.j0) * B * H,
+                HIP_TRY(hipMemcpyAsync(s->fc_steps_dev, s->fc_steps_host.as<double>() + (size_t)(first + bt.j0) * B * H,
                                        sizeof(double) * bt.ND * H, hipMemcpyHostToDevice, l.st));
                 fb.steps = s->fc_steps_dev;
             }
@@ -3037,7 +2956,7 @@ extern "C" int seir_sampler_forecast(seir_sampler *s, int32_t first, int32_t cou
         [&](const ForecastBufs &fb, const RolloutBatch &bt) {
             if (s->fc_keep)
                 hipLaunchKernelGGL(k_forecast_keep, dim3((d.M + KEEP_ROWS - 1) / KEEP_ROWS, B), dim3(64 * KEEP_ROWS), 0, l.st, d,
-                                   (const int *)fb.fev, (const int *)(fb.St0 + 2 * (size_t)d.Mp * bt.ndp), s->fc_keep,
+                                   (const int *)fb.fev, (const int *)(fb.St0 + 2 * (size_t)d.Mp * bt.ndp), s->fc_keep.as<int>(),
                                    s->fc_keep_cap, r.j + bt.j0, H, B, bt.nj, bt.ndp);
             hipLaunchKernelGGL(k_forecast_finish, dim3(bt.nj, B), dim3(64), 0, l.st, d, fb, B, first + bt.j0, bt.nj, bt.ndp);
             if (groups_live(s, 1)) groups_rollout_batch(s, 1, d, l.st, fb, first, bt);
@@ -3077,10 +2996,8 @@ extern "C" int seir_sampler_read_forecast(seir_sampler *s, uint64_t *count, int3
 // once j draws per chain have been taken since the reset (`verb`; `reset` and `call` name the two entry points), a store
 // that already has the capacity stays (the reset has emptied it), and a new one of `bytes` (`shape` spells the product
 // out for the refusal) may take half of what is free on the device; it is zeroed.
-template <typename T>
-static int keep_resize(seir_sampler *s, T *&store, long long &store_cap, int64_t cap, long long j, unsigned long long bytes,
+static int keep_resize(seir_sampler *s, DevBuf &store, long long &store_cap, int64_t cap, long long j, unsigned long long bytes,
                        const char *verb, const char *reset, const char *call, const char *shape) {
-    hipStream_t st = s->ctx->stream;
     if (cap != 0) {
         if (j != 0)
             return fail(SEIR_ERR_STATE, "%lld draws per chain have been %s since the reset: the draw store is sized between "
@@ -3088,21 +3005,12 @@ static int keep_resize(seir_sampler *s, T *&store, long long &store_cap, int64_t
         if (store && store_cap == cap) return 0;
     }
     if (store) {
-        HIP_TRY(hipStreamSynchronize(st));
-        (void)hipFree(store);
-        store = nullptr; store_cap = 0;
+        HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+        store.reset(); store_cap = 0;
     }
     if (cap == 0) return 0;
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    // half of what is free: the policy of a device that is shared, not a measurement
-    if (bytes > (unsigned long long)free_b / 2)
-        return fail(SEIR_ERR_INVALID, "the draw store needs %llu bytes (%s), more than half of the %llu bytes free on the device",
-                    bytes, shape, (unsigned long long)free_b);
-    void *q = nullptr;
-    HIP_TRY(hipMalloc(&q, (size_t)bytes));
-    if (hipMemsetAsync(q, 0, (size_t)bytes, st) != hipSuccess) { (void)hipFree(q); return fail(SEIR_ERR_DEVICE, "hipMemsetAsync failed"); }
-    store = (T *)q;
+    if (int rc = refuse_above_half_free(bytes, "the draw store needs %llu bytes (%s)", bytes, shape)) return rc;
+    if (int rc = store.zeroed((size_t)bytes)) return rc;
     store_cap = cap;
     return 0;
 }
@@ -3195,7 +3103,7 @@ extern "C" int seir_sampler_forecast_order_stats(seir_sampler *s, const int64_t 
     int rc = sampler_check(s);
     if (rc) return rc;
     if ((rc = trace_range_check(s, s->fc.on, FORECAST_USER))) return rc;
-    return keep_order_stats<int32_t>(s, s->fc_keep, s->fc.j, s->fc.fb.mom.count, 3ll * s->ctx->d.M * s->fc.fb.H, s->fc_keep_cap, ranks,
+    return keep_order_stats<int32_t>(s, s->fc_keep.as<const int32_t>(), s->fc.j, s->fc.fb.mom.count, 3ll * s->ctx->d.M * s->fc.fb.H, s->fc_keep_cap, ranks,
                                      R, pooled, out, "seir_sampler_forecast_keep", "forecast", "forecast");
 }
 
@@ -3245,7 +3153,7 @@ extern "C" int seir_order_stats_f64(seir_ctx *ctx, const double *values, int64_t
 static void check_layout(seir_sampler *s, int K) {
     const size_t B = (size_t)s->cfg.B, M = (size_t)s->ctx->d.M, cells = B * M * K;
     CheckCmp &cc = s->ck_cmp;
-    uint32_t *w = (uint32_t *)s->ck_cnt.p;
+    uint32_t *w = s->ck_cnt.buf.as<uint32_t>();
     cc.lt = w; cc.eq = w + cells; cc.obs = (int32_t *)(w + 2 * cells);
     w += 3 * cells;
     cc.loc_lt = w; cc.loc_eq = w + B * M;
@@ -3270,8 +3178,8 @@ extern "C" int seir_sampler_check_reset(seir_sampler *s, int32_t days, const dou
     Rollout &r = s->ck;
     if (!r.on || r.fb.H != days) {
         if ((rc = rollout_resize(s, r, days))) return rc;
-        acc_free(s->ck_cnt);                         // sized by K as well; the stream is idle
-        if ((rc = acc_alloc(s->ck_cnt, check_words(s, days) * sizeof(uint32_t)))) return rc;
+        s->ck_cnt = Shadowed{};                      // sized by K as well; the stream is idle
+        if ((rc = s->ck_cnt.buf.zeroed(check_words(s, days) * sizeof(uint32_t)))) return rc;
         check_layout(s, days);
         r.on = true;
     }
@@ -3396,18 +3304,15 @@ extern "C" int seir_sampler_rt_reset(seir_sampler *s, int32_t days, const double
     if (!s->rt_on || rb.D != D) {
         // first reset, or another window: everything is sized by D
         if ((rc = drain(s))) return rc;
-        for (void *p : s->rt_allocs) (void)hipFree(p);
         s->rt_allocs.clear();
-        acc_free(s->rt_acc);
-        if (s->rt_keep) { (void)hipFree(s->rt_keep); s->rt_keep = nullptr; s->rt_keep_cap = s->rt_keep_stride = 0; }   // sized by D
-        ngm_off(s);                                  // sized by D too
+        s->rt_acc = Shadowed{};
+        s->rt_keep.reset(); s->rt_keep_cap = s->rt_keep_stride = 0;   // sized by D
+        s->ngm = GroupNgm{};                         // sized by D too
         s->rt_on = false;
         rb = RtBufs{};
         rb.D = D; rb.t0 = d.T - D; rb.ncb = (d.M + 63) / 64;
         // the S plane of a batch is bounded: a call is cut into batches of at most rt_slots trace slots
-        const size_t bound = s->ctx->opt_rt_staging_kib ? (size_t)s->ctx->opt_rt_staging_kib << 10 : RT_STAGING_BYTES;
-        const size_t per_slot = (size_t)B * d.Mp * D * sizeof(int);
-        s->rt_slots = (int)std::max<size_t>(1, std::min<size_t>((size_t)s->cfg.cap, bound / per_slot));
+        s->rt_slots = staging_slots(s->ctx, s->cfg.cap, (size_t)B * d.Mp * D * sizeof(int));
         const size_t nd = (size_t)s->rt_slots * B;
         double *wd = nullptr;
         S_ALLOC(rt_allocs, wd, (size_t)rb.ncb * 64);
@@ -3415,24 +3320,22 @@ extern "C" int seir_sampler_rt_reset(seir_sampler *s, int32_t days, const double
         S_ALLOC(rt_allocs, rb.part, nd * D * rb.ncb); S_ALLOC(rt_allocs, rb.Rt, (size_t)s->cfg.cap * B * D);
         rb.weight = wd;
         const size_t cells = (size_t)B * D * d.M;
-        if (!rc) rc = acc_alloc(s->rt_acc, cells * (3 * sizeof(double) + sizeof(uint32_t)) + rt_count_words(s) * sizeof(uint64_t));
+        if (!rc) rc = s->rt_acc.buf.zeroed(cells * (3 * sizeof(double) + sizeof(uint32_t)) + rt_count_words(s) * sizeof(uint64_t));
         if (rc) return rc;
-        rb.sum = (double *)s->rt_acc.p;
+        rb.sum = s->rt_acc.buf.as<double>();
         rb.sumsq = rb.sum + cells;
         rb.ref = rb.sumsq + cells;
         rb.count = (uint64_t *)(rb.ref + cells);
         rb.gt1 = (uint32_t *)(rb.count + rt_count_words(s));
-        const size_t lds = k_rt_trace_lds_bytes<RT_DT>(d.Mp);
-        if (lds > 64 * 1024)
-            (void)hipFuncSetAttribute((const void *)k_rt_trace<RT_DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)lds_attribute((const void *)k_rt_trace<RT_DT>, k_rt_trace_lds_bytes<RT_DT>(d.Mp));
         s->rt_on = true;
     }
     // the caller's array is not retained: a blocking copy behind what is queued (a reset is not on the hot path)
     HIP_TRY(hipMemcpyAsync(const_cast<double *>(rb.weight), weight, sizeof(double) * d.M, hipMemcpyHostToDevice, st));
     if ((rc = acc_zero(s->rt_acc, st))) return rc;
-    if (s->rt_keep) HIP_TRY(hipMemsetAsync(s->rt_keep, 0, sizeof(double) * rt_cells(s) * (size_t)s->rt_keep_stride, st));
+    if (s->rt_keep) HIP_TRY(hipMemsetAsync(s->rt_keep.p, 0, sizeof(double) * rt_cells(s) * (size_t)s->rt_keep_stride, st));
     if (s->ngm.cap)                                  // the group next-generation matrix holds draws [0, count) too
-        HIP_TRY(hipMemsetAsync(s->ngm.out, 0, sizeof(double) * (size_t)s->ngm.cap * B * s->grp.G * s->grp.G * D, st));
+        HIP_TRY(hipMemsetAsync(s->ngm.out.p, 0, sizeof(double) * (size_t)s->ngm.cap * B * s->grp.G * s->grp.G * D, st));
     HIP_TRY(hipStreamSynchronize(st));
     s->rt_j = 0;                                     // empties the draw store too: it holds draws [0, count)
     // what the snapshots taken before this reset hold of it is dropped: restoring one of them leaves the accumulators alone
@@ -3459,8 +3362,8 @@ extern "C" int seir_sampler_rt(seir_sampler *s, int32_t first, int32_t count) {
     Work tw = ctx->w;                                 // k_rt_tables writes Work::ea: the feature's own buffer, not the sampler's
     tw.ea = rb.ea;
     const size_t lds = k_rt_trace_lds_bytes<RT_DT>(d.Mp);
-    const bool curves = s->grt.D != 0;                // group R_t: the batch also fits the cell plane
-    const int slots = std::min(curves ? s->grt.slots : s->rt_slots, s->ngm.cap ? s->ngm.slots : s->rt_slots);
+    const bool curves = s->grt.b.D != 0;                // group R_t: the batch also fits the cell plane
+    const int slots = std::min(curves ? s->grt.b.slots : s->rt_slots, s->ngm.cap ? s->ngm.slots : s->rt_slots);
     for (int j0 = 0; j0 < count; j0 += slots) {
         const int nj = std::min(slots, count - j0), ND = nj * B;
         hipLaunchKernelGGL(k_rt_tables, dim3(ND), dim3(256), 0, l.st, d, tw,
@@ -3473,7 +3376,7 @@ extern "C" int seir_sampler_rt(seir_sampler *s, int32_t first, int32_t count) {
         if (s->ngm.cap) ngm_launch(s, l, first + j0, s->rt_j + j0, nj);      // behind k_rt_prepare: ea and S of the batch lie there
         if (s->rt_keep)                               // in place of k_rt_trace: R_it is formed once
             hipLaunchKernelGGL(k_rt_trace_keep<RT_DT>, dim3(rb.ncb, (D + RT_DT - 1) / RT_DT, B), dim3(256), lds, l.st, d, ctx->c, rb,
-                               (const double *)s->ch.tr_theta, B, first + j0, nj, s->rt_keep, s->rt_keep_stride);
+                               (const double *)s->ch.tr_theta, B, first + j0, nj, s->rt_keep.as<double>(), s->rt_keep_stride);
         else if (curves)                              // in place of k_rt_trace: it also leaves every cell's r in the plane
             gcurve_rt_trace_cells(s, l, first + j0, nj);
         else
@@ -3506,9 +3409,7 @@ extern "C" int seir_sampler_rt_keep(seir_sampler *s, int64_t cap) {
                      "folded", "seir_sampler_rt_reset", "seir_sampler_rt", shape);
     if (!s->rt_keep) s->rt_keep_stride = 0;
     else if (!rc) s->rt_keep_stride = stride;        // a refused resize leaves the store and its stride as they were
-    const size_t lds = k_rt_trace_lds_bytes<RT_DT>(s->ctx->d.Mp);
-    if (s->rt_keep && lds > 64 * 1024)
-        (void)hipFuncSetAttribute((const void *)k_rt_trace_keep<RT_DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (s->rt_keep) (void)lds_attribute((const void *)k_rt_trace_keep<RT_DT>, k_rt_trace_lds_bytes<RT_DT>(s->ctx->d.Mp));
     return rc;
 }
 
@@ -3516,7 +3417,7 @@ extern "C" int seir_sampler_rt_order_stats(seir_sampler *s, const int64_t *ranks
     int rc = sampler_check(s);
     if (rc) return rc;
     if ((rc = rt_check(s))) return rc;
-    if ((rc = keep_order_stats<uint64_t>(s, (const uint64_t *)s->rt_keep, s->rt_j, s->rt.count, (long long)s->rt.D * s->ctx->d.M,
+    if ((rc = keep_order_stats<uint64_t>(s, s->rt_keep.as<const uint64_t>(), s->rt_j, s->rt.count, (long long)s->rt.D * s->ctx->d.M,
                                          s->rt_keep_stride, ranks, R, pooled, (uint64_t *)out, "seir_sampler_rt_keep", "rt", "folded")))
         return rc;
     return check_ev_overflow(s);
@@ -3584,23 +3485,20 @@ extern "C" int seir_sampler_wb_reset(seir_sampler *s, int32_t days) {
     if (!s->wb_on || wb.D != D) {
         // first reset, or another window: everything is sized by D
         if ((rc = drain(s))) return rc;
-        for (void *p : s->wb_allocs) (void)hipFree(p);
         s->wb_allocs.clear();
-        acc_free(s->wb_acc);
+        s->wb_acc = Shadowed{};
         s->wb_on = false;
         wb = WbBufs{};
         wb.D = D; wb.t0 = d.T - D; wb.ncb = (d.M + 63) / 64;
         // the I plane of a batch is bounded as the reproduction number's S plane: a call is cut into batches of at most wb_slots slots
-        const size_t bound = s->ctx->opt_rt_staging_kib ? (size_t)s->ctx->opt_rt_staging_kib << 10 : RT_STAGING_BYTES;
-        const size_t per_slot = (size_t)B * d.Mp * D * sizeof(int);
-        s->wb_slots = (int)std::max<size_t>(1, std::min<size_t>((size_t)s->cfg.cap, bound / per_slot));
+        s->wb_slots = staging_slots(s->ctx, s->cfg.cap, (size_t)B * d.Mp * D * sizeof(int));
         const size_t nd = (size_t)s->wb_slots * B;
         S_ALLOC(wb_allocs, wb.I, nd * D * d.Mp); S_ALLOC(wb_allocs, wb.part, nd * D * wb.ncb * 2);
         S_ALLOC(wb_allocs, wb.Wn, (size_t)s->cfg.cap * B * D); S_ALLOC(wb_allocs, wb.Bn, (size_t)s->cfg.cap * B * D);
         const size_t cells = (size_t)B * D * d.M, cw = rt_count_words(s);
-        if (!rc) rc = acc_alloc(s->wb_acc, cells * (5 * sizeof(double) + 2 * sizeof(uint32_t)) + cw * sizeof(uint64_t));
+        if (!rc) rc = s->wb_acc.buf.zeroed(cells * (5 * sizeof(double) + 2 * sizeof(uint32_t)) + cw * sizeof(uint64_t));
         if (rc) return rc;
-        wb.sum_w = (double *)s->wb_acc.p;
+        wb.sum_w = s->wb_acc.buf.as<double>();
         wb.sumsq_w = wb.sum_w + cells;
         wb.ref_w = wb.sumsq_w + cells;
         wb.ref_b = wb.ref_w + cells;
@@ -3608,9 +3506,7 @@ extern "C" int seir_sampler_wb_reset(seir_sampler *s, int32_t days) {
         wb.count = (uint64_t *)(wb.sum_b + cells);
         wb.n = (uint32_t *)(wb.count + cw);
         wb.gt = wb.n + cells;
-        const size_t lds = k_wb_trace_lds_bytes<WB_DT>(d.Mp);
-        if (lds > 64 * 1024)
-            (void)hipFuncSetAttribute((const void *)k_wb_trace<WB_DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)lds_attribute((const void *)k_wb_trace<WB_DT>, k_wb_trace_lds_bytes<WB_DT>(d.Mp));
         s->wb_on = true;
     }
     if ((rc = acc_zero(s->wb_acc, st))) return rc;
@@ -3631,8 +3527,8 @@ extern "C" int seir_sampler_wb(seir_sampler *s, int32_t first, int32_t count) {
     const int B = s->cfg.B, D = s->wb.D;
     const WbBufs &wb = s->wb;
     const size_t lds = k_wb_trace_lds_bytes<WB_DT>(d.Mp);
-    const bool curves = s->gwb.D != 0;                // group within / between: the batch also fits the two cell planes
-    const int slots = curves ? s->gwb.slots : s->wb_slots;
+    const bool curves = s->gwb.b.D != 0;                // group within / between: the batch also fits the two cell planes
+    const int slots = curves ? s->gwb.b.slots : s->wb_slots;
     for (int j0 = 0; j0 < count; j0 += slots) {
         const int nj = std::min(slots, count - j0), ND = nj * B;
         const dim3 pgrid((d.M + WB_PREP_ROWS - 1) / WB_PREP_ROWS, ND), pblock(64 * WB_PREP_ROWS);
@@ -3706,41 +3602,29 @@ static int gcurve_fit(seir_sampler *s, bool rt) {
     c.planes = rt ? 1 : 2;
     const bool product = rt ? s->rt_on : s->wb_on;
     const int D = (c.on && s->grp_on && product) ? (rt ? s->rt.D : s->wb.D) : 0;
-    if (D == c.D) return 0;
+    if (D == c.b.D) return 0;
     if (int rc = drain(s)) return rc;
-    gcurve_release(c);
+    c.b = {};
     if (D == 0) return 0;
     const Dims &d = s->ctx->d;
     const int B = s->cfg.B, G = s->grp.G;
-    const size_t bound = s->ctx->opt_rt_staging_kib ? (size_t)s->ctx->opt_rt_staging_kib << 10 : RT_STAGING_BYTES;
-    const size_t per_slot = (size_t)B * d.Mp * D * (sizeof(int) + c.planes * sizeof(double));
-    const int base = rt ? s->rt_slots : s->wb_slots;
-    const int slots = (int)std::max<size_t>(1, std::min<size_t>((size_t)base, bound / per_slot));
+    const int slots = staging_slots(s->ctx, rt ? s->rt_slots : s->wb_slots,
+                                    (size_t)B * d.Mp * D * (sizeof(int) + c.planes * sizeof(double)));
     const unsigned long long out_bytes = (unsigned long long)s->cfg.cap * B * G * D * 8ull;
     const unsigned long long cell_bytes = (unsigned long long)slots * B * D * d.Mp * 8ull;
     const unsigned long long bytes = (unsigned long long)c.planes * (out_bytes + cell_bytes);
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    // half of what is free: the policy of a device that is shared, not a measurement (groups_refuse_bytes)
-    if (bytes > (unsigned long long)free_b / 2)
-        return fail(SEIR_ERR_INVALID, "the group curves need %llu bytes (%d planes x (%d slots x %d chains x %d groups x %d days "
-                    "x 8 + %llu of a batch's cells)), more than half of the %llu bytes free on the device", bytes, c.planes,
-                    s->cfg.cap, B, G, D, cell_bytes, (unsigned long long)free_b);
-    hipError_t e = hipMalloc((void **)&c.offsets, sizeof(int) * (size_t)(G + 1));
-    if (e == hipSuccess) e = hipMemcpy(c.offsets, s->grp_offsets.data(), sizeof(int) * (size_t)(G + 1), hipMemcpyHostToDevice);
-    for (int x = 0; x < c.planes && e == hipSuccess; ++x) {
-        e = hipMalloc((void **)&c.out[x], (size_t)out_bytes);
-        if (e == hipSuccess) e = hipMemset(c.out[x], 0, (size_t)out_bytes);
-        if (e == hipSuccess) e = hipMalloc((void **)&c.cells[x], (size_t)cell_bytes);
-        if (e == hipSuccess) e = hipMemset(c.cells[x], 0, (size_t)cell_bytes);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // the zeroing is done: see s_alloc
-    if (e != hipSuccess) {
-        gcurve_release(c);
-        return fail(SEIR_ERR_DEVICE, "allocating %llu bytes of group curves failed: %s", bytes, hipGetErrorString(e));
-    }
+    if (int rc = refuse_above_half_free(bytes, "the group curves need %llu bytes (%d planes x (%d slots x %d chains x %d groups x %d "
+                                        "days x 8 + %llu of a batch's cells))", bytes, c.planes, s->cfg.cap, B, G, D, cell_bytes))
+        return rc;
+    // every buffer or none: a family whose outputs could not be made has none (D = 0) and is not launched for
+    GroupCurve::Bufs b;
+    int rc = b.offsets.upload(s->grp_offsets.data(), sizeof(int) * (size_t)(G + 1));
+    for (int x = 0; x < c.planes && !rc; ++x)
+        if (!(rc = b.out[x].zeroed((size_t)out_bytes))) rc = b.cells[x].zeroed((size_t)cell_bytes);
+    if (rc) return alloc_failed(bytes, "group curves");
     gcurve_lds_attributes(d.Mp);
-    c.D = D; c.slots = slots;
+    b.D = D; b.slots = slots;
+    c.b = std::move(b);
     return 0;
 }
 
@@ -3749,7 +3633,7 @@ extern "C" int seir_sampler_group_rt(seir_sampler *s, const double *weights) {
     if (rc) return rc;
     if (!weights) {
         if (s->grt.on && (rc = drain(s))) return rc;
-        gcurve_rt_off(s);
+        s->grt = GroupCurve{};                       // off: the weights belonged to the table that was in force
         return 0;
     }
     if ((rc = need_events(s, RT_USER.verb))) return rc;
@@ -3758,10 +3642,9 @@ extern "C" int seir_sampler_group_rt(seir_sampler *s, const double *weights) {
     for (size_t k = 0; k < nnz; ++k)
         if (!(fabs(weights[k]) < __builtin_inf())) return fail(SEIR_ERR_INVALID, "weights[%zu] is not finite", k);
     if ((rc = drain(s))) return rc;
-    if (!s->grt.weights) HIP_TRY(hipMalloc((void **)&s->grt.weights, sizeof(double) * nnz));
-    HIP_TRY(hipMemcpy(s->grt.weights, weights, sizeof(double) * nnz, hipMemcpyHostToDevice));
+    if ((rc = s->grt.weights.upload(weights, sizeof(double) * nnz))) return rc;
     s->grt.on = true;
-    if ((rc = gcurve_fit(s, true))) { gcurve_rt_off(s); return rc; }
+    if ((rc = gcurve_fit(s, true))) { s->grt = GroupCurve{}; return rc; }
     return 0;
 }
 
@@ -3770,8 +3653,7 @@ extern "C" int seir_sampler_group_wb(seir_sampler *s, int32_t on) {
     if (rc) return rc;
     if (!on) {
         if (s->gwb.on && (rc = drain(s))) return rc;
-        gcurve_release(s->gwb);
-        s->gwb.on = false;
+        s->gwb = GroupCurve{};
         return 0;
     }
     if ((rc = need_events(s, WB_USER.verb))) return rc;
@@ -3782,10 +3664,10 @@ extern "C" int seir_sampler_group_wb(seir_sampler *s, int32_t on) {
 }
 
 static int copy_group_curves(seir_sampler *s, hipStream_t st, const GroupCurve &c, int32_t first, int32_t count, double *const *dst) {
-    const size_t row = (size_t)s->cfg.B * s->grp.G * c.D;
+    const size_t row = (size_t)s->cfg.B * s->grp.G * c.b.D;
     for (int x = 0; x < c.planes; ++x)
         if (dst[x])
-            HIP_TRY(hipMemcpyAsync(dst[x], c.out[x] + (size_t)first * row, sizeof(double) * count * row, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(dst[x], c.b.out[x].as<double>() + (size_t)first * row, sizeof(double) * count * row, hipMemcpyDeviceToHost, st));
     return 0;
 }
 
@@ -3794,7 +3676,7 @@ static int read_group_curves(seir_sampler *s, bool rt, bool async, int32_t first
     if (rc) return rc;
     if ((rc = rt ? rt_check(s, first, count) : wb_check(s, first, count))) return rc;
     const GroupCurve &c = rt ? s->grt : s->gwb;
-    if (c.D == 0)
+    if (c.b.D == 0)
         return fail(SEIR_ERR_STATE, "%s", !c.on ? (rt ? "group R_t is not enabled: call seir_sampler_group_rt first"
                                                      : "group within/between is not enabled: call seir_sampler_group_wb first")
                                               : "the group curves have no outputs: no table is set, or they were refused");
@@ -4009,8 +3891,8 @@ static void gcurve_wsums_launch(const Dims &d, hipStream_t st, const int *offset
 static void gcurve_sums(seir_sampler *s, const LaunchCfg &l, const GroupCurve &c, int D, int slot0, int nj) {
     const int B = s->cfg.B;
     for (int x = 0; x < c.planes; ++x)
-        gcurve_wsums_launch(l.d, l.st, c.offsets, s->grp.members, c.weights, c.cells[x], s->grp.G, D, l.d.Mp, 0,
-                            (long long)slot0 * B, (long long)nj * B, c.out[x]);
+        gcurve_wsums_launch(l.d, l.st, c.b.offsets.as<int>(), s->grp.members, c.weights.as<double>(), c.b.cells[x].as<double>(),
+                            s->grp.G, D, l.d.Mp, 0, (long long)slot0 * B, (long long)nj * B, c.b.out[x].as<double>());
 }
 
 static void gcurve_rt_trace_cells(seir_sampler *s, const LaunchCfg &l, int slot0, int nj) {
@@ -4018,13 +3900,13 @@ static void gcurve_rt_trace_cells(seir_sampler *s, const LaunchCfg &l, int slot0
     const int B = s->cfg.B;
     hipLaunchKernelGGL(k_rt_trace_cells<RT_DT>, dim3(rb.ncb, (rb.D + RT_DT - 1) / RT_DT, B), dim3(256),
                        k_rt_trace_lds_bytes<RT_DT>(l.d.Mp), l.st, l.d, s->ctx->c, rb, (const double *)s->ch.tr_theta, B, slot0, nj,
-                       s->grt.cells[0], (long long)l.d.Mp);
+                       s->grt.b.cells[0].as<double>(), (long long)l.d.Mp);
 }
 
 static void gcurve_rt_gather(seir_sampler *s, const LaunchCfg &l, long long pos0, int nj) {
     const int B = s->cfg.B, D = s->rt.D;
-    hipLaunchKernelGGL(k_rt_cells_from_keep, dim3((l.d.M + 255) / 256, D, B), dim3(256), 0, l.st, l.d, (const double *)s->rt_keep,
-                       s->rt_keep_stride, pos0, B, D, nj, s->grt.cells[0], (long long)l.d.Mp);
+    hipLaunchKernelGGL(k_rt_cells_from_keep, dim3((l.d.M + 255) / 256, D, B), dim3(256), 0, l.st, l.d, s->rt_keep.as<const double>(),
+                       s->rt_keep_stride, pos0, B, D, nj, s->grt.b.cells[0].as<double>(), (long long)l.d.Mp);
 }
 
 static void gcurve_wb_trace_cells(seir_sampler *s, const LaunchCfg &l, int slot0, int nj) {
@@ -4032,16 +3914,13 @@ static void gcurve_wb_trace_cells(seir_sampler *s, const LaunchCfg &l, int slot0
     const int B = s->cfg.B;
     hipLaunchKernelGGL(k_wb_trace_cells<WB_DT>, dim3(wb.ncb, (wb.D + WB_DT - 1) / WB_DT, B), dim3(256),
                        k_wb_trace_lds_bytes<WB_DT>(l.d.Mp), l.st, l.d, s->ctx->c, wb, (const double *)s->ch.tr_theta, B, slot0, nj,
-                       s->gwb.cells[0], s->gwb.cells[1], (long long)l.d.Mp);
+                       s->gwb.b.cells[0].as<double>(), s->gwb.b.cells[1].as<double>(), (long long)l.d.Mp);
 }
 
 // Above 64 KiB of dynamic LDS a kernel needs the attribute (as k_rt_trace and k_wb_trace get theirs at their resets).
 static void gcurve_lds_attributes(int Mp) {
-    const size_t rl = k_rt_trace_lds_bytes<RT_DT>(Mp), wl = k_wb_trace_lds_bytes<WB_DT>(Mp);
-    if (rl > 64 * 1024)
-        (void)hipFuncSetAttribute((const void *)k_rt_trace_cells<RT_DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rl);
-    if (wl > 64 * 1024)
-        (void)hipFuncSetAttribute((const void *)k_wb_trace_cells<WB_DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl);
+    (void)lds_attribute((const void *)k_rt_trace_cells<RT_DT>, k_rt_trace_lds_bytes<RT_DT>(Mp));
+    (void)lds_attribute((const void *)k_wb_trace_cells<WB_DT>, k_wb_trace_lds_bytes<WB_DT>(Mp));
 }
 
 // ===========================================================================
@@ -4062,19 +3941,17 @@ static void ngm_rows_launch(const Dims &d, const Consts &c, hipStream_t st, cons
 
 // Above 64 KiB of dynamic LDS the kernel needs the attribute (as k_rt_trace gets its own at the rt reset).
 static void ngm_lds_attribute(int Mp) {
-    const size_t lds = k_rt_trace_lds_bytes<RT_DT>(Mp);
-    if (lds > 64 * 1024)
-        (void)hipFuncSetAttribute((const void *)k_ngm_rows<RT_DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)lds_attribute((const void *)k_ngm_rows<RT_DT>, k_rt_trace_lds_bytes<RT_DT>(Mp));
 }
 
 static void ngm_launch(seir_sampler *s, const LaunchCfg &l, int slot0, long long pos0, int nj) {
     const GroupNgm &n = s->ngm;
     const int B = s->cfg.B, G = s->grp.G;
-    ngm_rows_launch(l.d, s->ctx->c, l.st, s->rt, (const double *)s->ch.tr_theta, B, slot0, (long long)nj * B, n.offsets,
-                    s->grp.members, G, n.P, (long long)l.d.Mp);
+    ngm_rows_launch(l.d, s->ctx->c, l.st, s->rt, (const double *)s->ch.tr_theta, B, slot0, (long long)nj * B, n.offsets.as<int>(),
+                    s->grp.members, G, n.P.as<double>(), (long long)l.d.Mp);
     // K [pos][b][g][h][t]: the group sums of P [nd][g][t][.] over the members of h, (draw, g) as the "draw" axis
-    gcurve_wsums_launch(l.d, l.st, n.offsets, s->grp.members, n.weights, n.P, G, n.D, l.d.Mp, 0, pos0 * B * G, (long long)nj * B * G,
-                        n.out);
+    gcurve_wsums_launch(l.d, l.st, n.offsets.as<int>(), s->grp.members, n.weights.as<double>(), n.P.as<double>(), G, n.D, l.d.Mp, 0,
+                        pos0 * B * G, (long long)nj * B * G, n.out.as<double>());
 }
 
 extern "C" int seir_sampler_group_ngm(seir_sampler *s, const double *weights, int64_t cap) {
@@ -4082,7 +3959,7 @@ extern "C" int seir_sampler_group_ngm(seir_sampler *s, const double *weights, in
     if (rc) return rc;
     if (!weights || cap == 0) {
         if (s->ngm.cap && (rc = drain(s))) return rc;
-        ngm_off(s);
+        s->ngm = GroupNgm{};
         return 0;
     }
     if ((rc = need_events(s, RT_USER.verb))) return rc;
@@ -4099,37 +3976,22 @@ extern "C" int seir_sampler_group_ngm(seir_sampler *s, const double *weights, in
     for (size_t k = 0; k < nnz; ++k)
         if (!(fabs(weights[k]) < __builtin_inf())) return fail(SEIR_ERR_INVALID, "weights[%zu] is not finite", k);
     if ((rc = drain(s))) return rc;
-    ngm_off(s);
+    s->ngm = GroupNgm{};                             // a refusal or failure below leaves it off
     // the staging bound covers the S plane, the cell plane of group R_t and P together: the batch shrinks accordingly
-    const size_t bound = s->ctx->opt_rt_staging_kib ? (size_t)s->ctx->opt_rt_staging_kib << 10 : RT_STAGING_BYTES;
-    const size_t per_slot = (size_t)B * d.Mp * D * (sizeof(int) + sizeof(double) + (size_t)G * sizeof(double));
-    const int slots = (int)std::max<size_t>(1, std::min<size_t>((size_t)s->rt_slots, bound / per_slot));
+    const int slots = staging_slots(s->ctx, s->rt_slots, (size_t)B * d.Mp * D * (sizeof(int) + sizeof(double) + (size_t)G * sizeof(double)));
     const unsigned long long out_bytes = (unsigned long long)cap * B * G * G * D * 8ull;
     const unsigned long long p_bytes = (unsigned long long)slots * B * G * D * d.Mp * 8ull;
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    // half of what is free: the policy of a device that is shared, not a measurement (groups_refuse_bytes)
-    if (out_bytes + p_bytes > (unsigned long long)free_b / 2)
-        return fail(SEIR_ERR_INVALID, "the group next-generation matrix needs %llu bytes (%lld draws x %d chains x %d x %d groups x "
-                    "%d days x 8 + %llu of a batch's rows), more than half of the %llu bytes free on the device",
-                    out_bytes + p_bytes, (long long)cap, B, G, G, D, p_bytes, (unsigned long long)free_b);
-    GroupNgm &n = s->ngm;
-    hipError_t e = hipMalloc((void **)&n.offsets, sizeof(int) * (size_t)(G + 1));
-    if (e == hipSuccess) e = hipMemcpy(n.offsets, s->grp_offsets.data(), sizeof(int) * (size_t)(G + 1), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&n.weights, sizeof(double) * nnz);
-    if (e == hipSuccess) e = hipMemcpy(n.weights, weights, sizeof(double) * nnz, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&n.out, (size_t)out_bytes);
-    if (e == hipSuccess) e = hipMemset(n.out, 0, (size_t)out_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&n.P, (size_t)p_bytes);
-    if (e == hipSuccess) e = hipMemset(n.P, 0, (size_t)p_bytes);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // the zeroing is done: see s_alloc
-    if (e != hipSuccess) {
-        ngm_off(s);
-        return fail(SEIR_ERR_DEVICE, "allocating %llu bytes of the group next-generation matrix failed: %s", out_bytes + p_bytes,
-                    hipGetErrorString(e));
-    }
+    if ((rc = refuse_above_half_free(out_bytes + p_bytes, "the group next-generation matrix needs %llu bytes (%lld draws x %d chains x "
+                                     "%d x %d groups x %d days x 8 + %llu of a batch's rows)", out_bytes + p_bytes, (long long)cap, B,
+                                     G, G, D, p_bytes)))
+        return rc;
+    GroupNgm n;
+    if (n.offsets.upload(s->grp_offsets.data(), sizeof(int) * (size_t)(G + 1)) || n.weights.upload(weights, sizeof(double) * nnz) ||
+        n.out.zeroed((size_t)out_bytes) || n.P.zeroed((size_t)p_bytes))
+        return alloc_failed(out_bytes + p_bytes, "the group next-generation matrix");
     ngm_lds_attribute(d.Mp);
     n.cap = cap; n.D = D; n.slots = slots;
+    s->ngm = std::move(n);
     return 0;
 }
 
@@ -4146,7 +4008,7 @@ extern "C" int seir_sampler_read_group_ngm(seir_sampler *s, int64_t first_draw, 
     if (!out) return fail(SEIR_ERR_INVALID, "null pointer");
     const size_t row = (size_t)s->cfg.B * s->grp.G * s->grp.G * s->ngm.D;
     if (count)
-        HIP_TRY(hipMemcpyAsync(out, s->ngm.out + (size_t)first_draw * row, sizeof(double) * (size_t)count * row, hipMemcpyDeviceToHost,
+        HIP_TRY(hipMemcpyAsync(out, s->ngm.out.as<double>() + (size_t)first_draw * row, sizeof(double) * (size_t)count * row, hipMemcpyDeviceToHost,
                                s->ctx->stream));
     HIP_TRY(hipStreamSynchronize(s->ctx->stream));
     return check_ev_overflow(s);
@@ -4165,10 +4027,9 @@ extern "C" int seir_group_ngm_rows(seir_ctx *ctx, int32_t n, const double *theta
     const int D = days;
     const size_t nnz = (size_t)offsets[G];
     // a batch's planes (events, S, P) stay within the staging bound; at least one draw is always taken
-    const size_t bound = ctx->opt_rt_staging_kib ? (size_t)ctx->opt_rt_staging_kib << 10 : RT_STAGING_BYTES;
     const size_t ev_draw = (size_t)d.M * d.T * 3, p_draw = (size_t)G * D * d.M;
-    const size_t per_draw = ev_draw * sizeof(int) + (size_t)d.Mp * D * sizeof(int) + p_draw * sizeof(double);
-    const int nb = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)n, NGM_NDMAX), bound / per_draw));
+    const int nb = staging_slots(ctx, std::min<size_t>((size_t)n, NGM_NDMAX),
+                                 ev_draw * sizeof(int) + (size_t)d.Mp * D * sizeof(int) + p_draw * sizeof(double));
     RtBufs rb{};
     rb.D = D; rb.t0 = d.T - D; rb.ncb = (d.M + 63) / 64;
     DevBuf dth, dev, dea, dS, dP, doff, dmem;
@@ -4240,7 +4101,6 @@ extern "C" int seir_sampler_load_trace(seir_sampler *s, int32_t chain, int32_t f
         const bool words = !s->load_words;
         if (words) S_ALLOC(allocs, s->load_words, (size_t)LOAD_ST_FIRST_KEY + 1);
         if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(nullptr));        // the allocations are zeroed on the null stream, which this one does not wait for
         if (words && (rc = load_words_clear(s, l.st))) return rc;
         s->load_stage = stage;
         s->load_slots = slots;
