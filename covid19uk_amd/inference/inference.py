@@ -11,6 +11,7 @@ windows and moves draws from the device burst buffer to disk.
 """
 from __future__ import annotations
 
+import collections
 import os
 import sys
 import time
@@ -25,6 +26,9 @@ from ..posterior import groups as G_mod
 from ..sampler import MOVE_KEYS, ChainSampler, Summary, mid_p
 from ..seir import SeirModel
 from .mcmc_kernel_factory import event_kernel_config, hmc_kernel_kwargs_default
+from .options import (CHECK_SEED_SALT, DIAGNOSTICS, SUMMARIES, Products, add_product_arguments, check_mode, check_seed,  # noqa: F401
+                      diagnostics_mode, forecast_mode, forecast_quantiles_mode, posterior_kwargs, product_inputs, product_overrides,
+                      resolve_products, rt_mode, rt_quantiles_mode, summaries_mode, thin_interval, within_between_mode)
 
 DTYPE = model_spec.DTYPE
 
@@ -479,122 +483,6 @@ def trace_to_dict(tr, chain):
     return out
 
 
-def thin_interval(config, override=None):
-    """Mcmc.thin ("Thin MCMC samples every 'thin' iterations", example_config.yaml:33; absent: 1), or the command line's
-    `--thin`.  Anything below 1 is refused -- here, before a sampler exists."""
-    thin = int(config.get("thin", 1) if override is None else override)
-    if thin < 1:
-        raise ValueError(f"thin={thin}: the thinning interval is >= 1 (1 keeps every draw)")
-    return thin
-
-
-SUMMARIES = ("off", "on", "only")
-
-
-def summaries_mode(config, override=None):
-    """Mcmc.summaries (absent: "off"), or the command line's `--summaries`: "on" adds the device-side summaries of the
-    latent epidemic to the output, "only" also keeps the event tensors on the device.  Anything else is refused -- here,
-    before a sampler exists."""
-    mode = config.get("summaries", "off") if override is None else override
-    if mode is False or mode is True:                       # YAML reads a bare `on` / `off` as a boolean
-        mode = "on" if mode else "off"
-    if mode not in SUMMARIES:
-        raise ValueError(f"summaries={mode!r}: choose one of {', '.join(SUMMARIES)}")
-    return mode
-
-
-DIAGNOSTICS = ("off", "on")
-
-
-def diagnostics_mode(config, override=None, batch=None):
-    """Mcmc.diagnostics (absent: "off") and Mcmc.diagnostics_batch, or the command line's `--diagnostics` /
-    `--diagnostics-batch`: (mode, batch length).  With "on" the batch length defaults to num_burst_samples (one burst is
-    one batch) and must divide it or be a multiple of it, and the run needs two bursts for its two halves.  Everything
-    else is refused, a batch length given with "off" included -- here, before a sampler exists."""
-    mode = config.get("diagnostics", "off") if override is None else override
-    if mode is False or mode is True:                       # YAML reads a bare `on` / `off` as a boolean
-        mode = "on" if mode else "off"
-    if mode not in DIAGNOSTICS:
-        raise ValueError(f"diagnostics={mode!r}: choose one of {', '.join(DIAGNOSTICS)}")
-    if batch is None:
-        batch = config.get("diagnostics_batch")
-    if mode == "off":
-        if batch is not None:
-            raise ValueError(f"diagnostics batch length {batch} given with diagnostics=off: it would have no effect")
-        return mode, 0
-    nb, ns = int(config["num_bursts"]), int(config["num_burst_samples"])
-    if nb < 2:
-        raise ValueError(f"diagnostics=on needs num_bursts >= 2 (the two halves of split R-hat are whole bursts), have {nb}")
-    L = ns if batch is None else int(batch)
-    if L < 1 or ns < 1 or (L % ns != 0 and ns % L != 0):
-        raise ValueError(f"diagnostics batch length {L}: it must divide num_burst_samples = {ns} or be a multiple of it")
-    return mode, L
-
-
-def forecast_mode(config, override=None, walk=None):
-    """Mcmc.forecast (absent: off) and Mcmc.forecast_walk, or the command line's `--forecast H` / `--forecast-walk`:
-    (H, walk) with H = 0 for off.  H is the number of days simulated forward from the end of the series for every kept
-    draw of the sampling phase, 1 <= H <= 128 (SEIR_FORECAST_MAX_H); `walk` lets the log baseline go on as the prior's
-    random walk instead of holding its last value.  The one place that validates -- before a sampler exists."""
-    from .. import _lib
-    H = config.get("forecast") if override is None else override
-    w = config.get("forecast_walk", False) if walk is None else walk
-    if isinstance(w, str):
-        if w.lower() not in ("on", "off", "true", "false"):
-            raise ValueError(f"forecast_walk={w!r}: on or off")
-        w = w.lower() in ("on", "true")
-    w = bool(w)
-    if H is None or H is False or (isinstance(H, str) and H.lower() == "off"):
-        if w:
-            raise ValueError("forecast_walk given without forecast: it would have no effect")
-        return 0, False
-    if isinstance(H, bool) or (not isinstance(H, (int, np.integer)) and not (isinstance(H, str) and H.strip().lstrip("+-").isdigit())):
-        raise ValueError(f"forecast={H!r}: the horizon is a number of days, 1 .. {_lib.FORECAST_MAX_H}")
-    H = int(H)
-    if not 1 <= H <= _lib.FORECAST_MAX_H:
-        raise ValueError(f"forecast={H}: the horizon is 1 .. {_lib.FORECAST_MAX_H} days")
-    return H, w
-
-
-def forecast_quantiles_mode(config, override=None, horizon=None):
-    """Mcmc.forecast_quantiles (absent: off), or the command line's `--forecast-quantiles 0.05,0.5,0.95`: the tuple of
-    probabilities whose exact per-location quantiles of the forecast draws are formed on the device; () for off.  1 to 8
-    probabilities in [0, 1], strictly increasing (`posterior.quantiles.parse_probs`).  With `horizon` given (0: the
-    forecast is off) quantiles without a forecast are refused.  The one place that validates -- before a sampler exists."""
-    from ..posterior.quantiles import parse_probs
-    probs = parse_probs(config.get("forecast_quantiles") if override is None else override)
-    if probs and horizon is not None and not horizon:
-        raise ValueError("forecast_quantiles given without forecast: it would have no effect")
-    return probs
-
-
-def rt_mode(config, override=None, T=None):
-    """Mcmc.rt (absent: off), or the command line's `--rt D`: the number of days D of the window [T - D, T) over which the
-    reproduction number of every kept draw of the sampling phase is formed on the device; 0 for off.  1 <= D, and D <= T
-    when the length of the series is given.  The one place that validates -- before a sampler exists."""
-    D = config.get("rt") if override is None else override
-    if D is None or D is False or (isinstance(D, str) and D.lower() == "off"):
-        return 0
-    if isinstance(D, bool) or (not isinstance(D, (int, np.integer)) and not (isinstance(D, str) and D.strip().lstrip("+-").isdigit())):
-        raise ValueError(f"rt={D!r}: the window is a number of days, 1 .. T")
-    D = int(D)
-    if D < 1 or (T is not None and D > int(T)):
-        raise ValueError(f"rt={D}: the window is 1 .. T{'' if T is None else f' = {int(T)}'} days")
-    return D
-
-
-def rt_quantiles_mode(config, override=None, rt_days=None):
-    """Mcmc.rt_quantiles (absent: off), or the command line's `--rt-quantiles 0.05,0.5,0.95`: the tuple of probabilities
-    whose exact per-day, per-location quantiles of the R_it draws are formed on the device; () for off.  1 to 8
-    probabilities in [0, 1], strictly increasing (`posterior.quantiles.parse_probs`).  With `rt_days` given (0: rt is off)
-    quantiles without rt are refused.  The one place that validates -- before a sampler exists."""
-    from ..posterior.quantiles import parse_probs
-    probs = parse_probs(config.get("rt_quantiles") if override is None else override, name="rt_quantiles")
-    if probs and rt_days is not None and not rt_days:
-        raise ValueError("rt_quantiles given without rt: it would have no effect")
-    return probs
-
-
 def draw_quantiles(x, probs):
     """Quantiles `probs` over the first axis of x [n, ...] by the one rank rule (`posterior.quantiles`): float64 [K, ...]."""
     from ..posterior import quantiles as Q
@@ -613,48 +501,6 @@ def rt_quantiles_run_line(probs, days, T, n, B, own):
             f"over {n} kept draw(s) per chain and pooled over the {B} chain(s) of this process, selected on the device; on day "
             f"{T - 1} the {probs[0]:g}-{probs[-1]:g} band is {float(width.min()):.3g} to {float(width.max()):.3g} wide and excludes 1 "
             f"in {100.0 * out:.1f} % of the locations; rt/*_quantiles written")
-
-
-def within_between_mode(config, override=None, T=None):
-    """Mcmc.within_between (absent: off), or the command line's `--within-between D`: the number of days D of the window
-    [T - D, T) over which the within/between pressure shares of every kept draw of the sampling phase are formed on the
-    device; 0 for off.  1 <= D, and D <= T when the length of the series is given.  The one place that validates -- before
-    a sampler exists."""
-    D = config.get("within_between") if override is None else override
-    if D is None or D is False or (isinstance(D, str) and D.lower() == "off"):
-        return 0
-    if isinstance(D, bool) or (not isinstance(D, (int, np.integer)) and not (isinstance(D, str) and D.strip().lstrip("+-").isdigit())):
-        raise ValueError(f"within_between={D!r}: the window is a number of days, 1 .. T")
-    D = int(D)
-    if D < 1 or (T is not None and D > int(T)):
-        raise ValueError(f"within_between={D}: the window is 1 .. T{'' if T is None else f' = {int(T)}'} days")
-    return D
-
-
-# The check's Philox key is the run's seed with this constant folded in: the check and the forecast (keyed by the run's seed
-# itself) share a protocol and a draw-id space, and so must never share a key
-CHECK_SEED_SALT = 0x636865636B5F6B31                        # "check_k1"
-
-
-def check_seed(seed):
-    return (int(seed) ^ CHECK_SEED_SALT) & (2 ** 64 - 1)
-
-
-def check_mode(config, override=None, T=None):
-    """Mcmc.check (absent: off), or the command line's `--check K`: the number of days K of the window [T - K, T) that is
-    simulated again from every kept draw of the sampling phase and set against the observed removals; 0 for off.
-    1 <= K <= 128 (SEIR_CHECK_MAX_DAYS), and K <= T when the length of the series is given.  The one place that validates
-    -- before a sampler exists."""
-    from .. import _lib
-    K = config.get("check") if override is None else override
-    if K is None or K is False or (isinstance(K, str) and K.lower() == "off"):
-        return 0
-    if isinstance(K, bool) or (not isinstance(K, (int, np.integer)) and not (isinstance(K, str) and K.strip().lstrip("+-").isdigit())):
-        raise ValueError(f"check={K!r}: the window is a number of days, 1 .. min(T, {_lib.CHECK_MAX_DAYS})")
-    K = int(K)
-    if K < 1 or K > _lib.CHECK_MAX_DAYS or (T is not None and K > int(T)):
-        raise ValueError(f"check={K}: the window is 1 .. min(T{'' if T is None else f' = {int(T)}'}, {_lib.CHECK_MAX_DAYS}) days")
-    return K
 
 
 def check_chain_datasets(cs, c):
@@ -747,322 +593,363 @@ def _stack(bursts, *shape):
     return np.concatenate(bursts) if bursts else np.empty((0,) + shape)
 
 
-def product_records(sampler, config, posteriors, log=sys.stderr, forecast_calendar=None, seed=0, rt_weight=None,
-                    check_calendar=None, groups=None, population=None, total=None, results=True):
-    """What `run_mcmc` and `posterior.replay.replay_files` share: the modes resolved and refused before the first call on the
-    sampler, the products' records (begin, flush, finish) in the order of the resets and the write-up, the keywords of the
-    warm-up's and the sampling phase's draws, the diagnostics' marks and the row bookkeeping.  `total`: the kept draws per
-    chain the products will see (default num_bursts x num_burst_samples: what sizes the draw stores); `results=False`: a
-    burst's flush writes the parameters' rows and the marginals only (a replay has no kernel results and no event tensor)."""
-    # 1. resolve the modes and refuse what cannot run -- before the first call on the sampler
-    s, T = sampler, getattr(sampler, "T", None)
-    thin = thin_interval(config)
-    wb_days = within_between_mode(config, T=T)
-    check_days = check_mode(config, T=T)
-    if check_days and check_calendar is None:
-        raise ValueError("check: run_mcmc needs check_calendar = (W, weekday_c) of the window")
-    rt_days = rt_mode(config, T=T)
-    if rt_days and rt_weight is None:
-        raise ValueError("rt: run_mcmc needs rt_weight = N / N.sum()")
-    horizon, walk = forecast_mode(config)
-    if horizon and forecast_calendar is None:
-        raise ValueError("forecast: run_mcmc needs forecast_calendar = (W, weekday_c) of the forecast days")
-    fq_probs = forecast_quantiles_mode(config, horizon=horizon)
-    rq_probs = rt_quantiles_mode(config, rt_days=rt_days)
-    summaries = summaries_mode(config)
-    diagnostics, batch_len = diagnostics_mode(config)
-    groups_rt = G_mod.switch(config.get("groups_rt"), "groups_rt")
-    groups_wb = G_mod.switch(config.get("groups_within_between"), "groups_within_between")
-    G_mod.require_curves(groups, groups_rt, rt_days, groups_wb, wb_days)
-    if groups_rt and population is None:
-        raise ValueError("groups_rt: run_mcmc needs population = N")
-    groups_ngm = G_mod.switch(config.get("groups_ngm"), "groups_ngm")
-    G_mod.require_ngm(groups, groups_ngm, rt_days, groups_rt)
-    nb, ns = int(config["num_bursts"]), int(config["num_burst_samples"])
-    total = nb * ns if total is None else int(total)        # kept draws per chain that the products will see
-    chain_ids = [getattr(sampler, "first_chain_id", 0) + c for c in range(sampler.B)]
-    warm_kw, burst_kw = {}, {}                              # the keywords of the warm-up's and the sampling phase's draws
-    # `offset` counts every written draw, `kept` the sampling phase's: the row of every product's per-draw datasets (a field is
-    # in a trace exactly when its keyword was passed: all together, on the sampling phase's bursts); `check`: its summary
-    rows = dict(offset=0, kept=0, check=None)
-    records, grp = [], None                                 # (begin, flush, finish) in the order of the resets and the write-up
+# A product's three parts side by side and what it adds to the keywords of the warm-up's and the sampling phase's draws: begin() --
+# the reset behind the warm-up, the draw store where quantiles are on; flush(tr, burst) -- what must outlive the pinned view copied, its
+# datasets written at its row offset, what the end needs kept (burst is None in the warm-up); finish() -- the blocking summary read,
+# the write_* calls and the log line
+Record = collections.namedtuple("Record", "begin flush finish warm_kw burst_kw")
 
-    def write_rows(arrays, row):
-        for c, post in enumerate(posteriors):               # every chain's slice of per-draw arrays [n,B,...] into its file
-            post.write_samples({k: v[:, c] for k, v in arrays.items()}, first_dim_offset=row)
 
-    def writes(field):                                      # the flush of a product whose arrays go to the files as they are
-        def flush(tr, burst):
-            if getattr(tr, field, None) is not None:
-                write_rows(getattr(tr, field), rows["kept"])
-        return flush
+def write_rows(ctx, arrays, row):
+    """Every chain's slice of per-draw arrays [n,B,...] into its file, from row `row` on."""
+    for c, post in enumerate(ctx.posteriors):
+        post.write_samples({k: v[:, c] for k, v in arrays.items()}, first_dim_offset=row)
 
-    # Mcmc.summaries and Mcmc.diagnostics.  Summaries "off": sample / sample_bursts are called exactly as before the option
-    # existed.  Otherwise every written draw gets its marginals (the warm-up without folding), the moments cover the sampling
-    # phase, and with "only" no event tensor is read.  Diagnostics "on" folds the sampling phase's draws whatever `summaries`
-    # says (which then only decides what is written)
-    marks = diagnostics_marks(nb) if diagnostics == "on" else {}
-    theta_acc = diag_mod.DrawAccumulator(batch_len) if diagnostics == "on" else None
-    if summaries != "off":
-        warm_kw.update(events=summaries != "only", summarize="marginals")
-    if summaries != "off" or diagnostics == "on":
-        burst_kw.update(events=summaries != "only", summarize=True)
 
-        def sm_begin():
-            if theta_acc is not None:
-                s.reset_diagnostics(batch_len)              # the moments too: all of it is over the sampling phase
-            else:
-                s.reset_summary()                           # the moments are over the sampling phase
-            if summaries == "only":
-                print("summaries only: the event tensors stay on the device and samples/seir is not created -- what reads it "
-                      "(thin_posterior, predict, reproduction_number) cannot run on this output", file=log, flush=True)
+def _writes(ctx, field):
+    """The flush of a product whose arrays go to the files as they are."""
+    def flush(tr, burst):
+        if getattr(tr, field, None) is not None:
+            write_rows(ctx, getattr(tr, field), ctx.rows["kept"])
+    return flush
 
-        def sm_flush(tr, burst):
-            if theta_acc is not None and burst is not None:     # the parameters' accumulators, marked where the device's are
-                theta_acc.fold(tr.theta)
-                if burst in marks:
-                    theta_acc.mark(marks[burst])
 
-        def sm_finish():
-            dg = None
-            if theta_acc is not None:
-                dg = s.diagnostics()
-                ev = diag_mod.evaluate(dg, theta_acc.result())
-                for c, post in enumerate(posteriors):
-                    post.write_diagnostics(diag_mod.chain_datasets(ev, c))
-                print(diag_mod.run_line(ev, diag_mod.theta_names(s.P, s.M, s.T))
-                      + f" ({s.B} chain(s) of this process, batches of {batch_len})", file=log, flush=True)
-            if summaries != "off":
-                sm = s.summary() if dg is None else Summary(count=dg.count, ref=dg.ref, sum=dg.sum, sumsq=dg.sumsq)
-                mean, var = sm.mean, sm.var
-                for c, post in enumerate(posteriors):
-                    post.write_summary(sm.count[c], mean[c], var[c])
-        records.append((sm_begin, sm_flush, sm_finish))
+def summaries_record(ctx):
+    """Mcmc.summaries and Mcmc.diagnostics.  Summaries "off": sample / sample_bursts are called exactly as before the option
+    existed.  Otherwise every written draw gets its marginals (the warm-up without folding), the moments cover the sampling
+    phase, and with "only" no event tensor is read.  Diagnostics "on" folds the sampling phase's draws whatever `summaries`
+    says (which then only decides what is written)."""
+    s, posteriors, log, summaries, batch_len = ctx.s, ctx.posteriors, ctx.log, ctx.opt.summaries, ctx.opt.batch_len
+    if summaries == "off" and ctx.opt.diagnostics != "on":
+        return None
+    theta_acc = diag_mod.DrawAccumulator(batch_len) if ctx.opt.diagnostics == "on" else None
 
-    # With Mcmc.forecast = H (`forecast_mode`) every kept draw of the sampling phase is forecast H days on the device
-    # behind its burst; `forecast_calendar` = (W [H], weekday_c [H]) (`posterior.predict.forecast_calendar`) and `seed`
-    # (the forecast's Philox stream and, with forecast_walk, the steps) are then needed.  The warm-up is not forecast.
-    # With Mcmc.forecast_quantiles (`forecast_quantiles_mode`; needs Mcmc.forecast) the device keeps cases, cumulative cases
-    # and prevalence of every forecast draw: the store is sized once, right behind the forecast's reset, for num_bursts x
-    # num_burst_samples draws per chain, and at the end of the run exact quantiles per location and forecast day are selected
-    # on the device, per chain and pooled over the chains of this process.  Without the key nothing of it is called.
-    if horizon:
-        burst_kw["forecast"] = forecast_steps_fn(seed, chain_ids, horizon) if walk else True
+    def begin():
+        if theta_acc is not None:
+            s.reset_diagnostics(batch_len)                  # the moments too: all of it is over the sampling phase
+        else:
+            s.reset_summary()                               # the moments are over the sampling phase
+        if summaries == "only":
+            print("summaries only: the event tensors stay on the device and samples/seir is not created -- what reads it "
+                  "(thin_posterior, predict, reproduction_number) cannot run on this output", file=log, flush=True)
 
-        def fc_begin():
-            s.reset_forecast(horizon, forecast_calendar[0], forecast_calendar[1], seed)   # once: the sampling phase
-            if fq_probs:
-                s.keep_forecast_draws(total)              # the draw store of the quantiles: every kept draw of the phase
+    def flush(tr, burst):
+        if theta_acc is not None and burst is not None:     # the parameters' accumulators, marked where the device's are
+            theta_acc.fold(tr.theta)
+            if burst in ctx.marks:
+                theta_acc.mark(ctx.marks[burst])
 
-        def fc_finish():
-            fs = s.forecast_summary()
-            mean, var = fs.mean, fs.var
+    def finish():
+        dg = None
+        if theta_acc is not None:
+            dg = s.diagnostics()
+            ev = diag_mod.evaluate(dg, theta_acc.result())
             for c, post in enumerate(posteriors):
-                post.write_forecast(horizon, s.T, fs.count[c], mean[c], var[c])
-            print(f"Forecast: {horizon} day(s) from day {s.T} for {int(fs.count.min()) if len(fs.count) else 0} kept draw(s) per "
-                  f"chain, formed on the device ({'random-walk' if walk else 'held'} baseline); forecast/* and "
-                  "samples/forecast_* written", file=log, flush=True)
-            if fq_probs and total:
-                own = s.forecast_quantiles(fq_probs)                        # [K,B,3,M,H]
-                pooled = s.forecast_quantiles(fq_probs, pooled=True)        # [K,3,M,H]
-                for c, post in enumerate(posteriors):
-                    post.write_forecast_quantiles(fq_probs, own[:, c], pooled, chain_ids)
-                print(f"Forecast quantiles: {', '.join(f'{p:g}' for p in fq_probs)} of cases, cumulative cases and prevalence per "
-                      f"location and forecast day, exact over {total} kept draw(s) per chain and pooled over the {s.B} "
-                      "chain(s) of this process, selected on the device; forecast/*_quantiles written", file=log, flush=True)
-        records.append((fc_begin, writes("forecast"), fc_finish))
-
-    # With Mcmc.rt = D (`rt_mode`) R_it of every kept draw of the sampling phase over the last D days is formed and folded
-    # on the device behind its burst (and behind the burst's summary and forecast); `rt_weight` [M] = N / N.sum() is then
-    # needed.  The warm-up is not folded; without the key nothing of it is called.
-    # With Mcmc.rt_quantiles (`rt_quantiles_mode`; needs Mcmc.rt) the device keeps R_it of every folded draw: the store is
-    # sized once, right behind the rt reset, for num_bursts x num_burst_samples draws per chain, and at the end of the run
-    # exact quantiles per day and location are selected on the device, per chain and pooled over the chains of this process;
-    # the national curve's quantiles are formed here from the draws of R_t.  Without the key nothing of it is called.
-    if rt_days:
-        burst_kw["rt"], rt_draws = True, []
-
-        def rt_begin():
-            s.reset_rt(rt_days, rt_weight)                  # once: the sampling phase
-            if rq_probs:
-                s.keep_rt_draws(total)                    # the draw store of the quantiles: every kept draw of the phase
-
-        def rt_flush(tr, burst):
-            if getattr(tr, "rt", None) is not None:
-                rt_draws.append(np.array(tr.rt))            # the pinned buffer is used again two bursts later
-                write_rows({"R_t": rt_draws[-1]}, rows["kept"])
-
-        def rt_finish():
-            rs = s.rt_summary()
-            mean, var, prob = rs.mean, rs.var, rs.prob_gt1
-            for c, post in enumerate(posteriors):
-                post.write_rt(rt_days, s.T - rt_days, rs.count[c], mean[c], var[c], prob[c])
-            r_t = _stack(rt_draws, s.B, rt_days)
-            print(rt_run_line(rt_days, s.T, r_t, prob), file=log, flush=True)
-            if rq_probs and total:
-                own = s.rt_quantiles(rq_probs)                              # [K,B,D,M]
-                pooled = s.rt_quantiles(rq_probs, pooled=True)              # [K,D,M]
-                nat = draw_quantiles(r_t, rq_probs)                         # [K,B,D]: costs nothing here
-                pnat = draw_quantiles(r_t.reshape(-1, rt_days), rq_probs)   # [K,D]
-                for c, post in enumerate(posteriors):
-                    post.write_rt_quantiles(rq_probs, own[:, c], pooled, chain_ids, nat[:, c], pnat)
-                print(rt_quantiles_run_line(rq_probs, rt_days, s.T, total, s.B, own), file=log, flush=True)
-        records.append((rt_begin, rt_flush, rt_finish))
-
-    # With Mcmc.check = K (`check_mode`) the last K days are simulated again from every kept draw of the sampling phase and
-    # set against the observed removals on the device, behind the burst's summary, forecast and R_t; `check_calendar` =
-    # (W [K], weekday_c [K]) (`posterior.predict.check_calendar`) is then needed, and the check's stream is keyed by
-    # `check_seed(seed)`.  The warm-up is not checked; without the key nothing of it is called.
-    if check_days:
-        burst_kw["check"] = True
-
-        def ck_finish():
-            rows["check"] = cs = s.check_summary()
-            mean, var = cs.moments.mean, cs.moments.var
-            for c, post in enumerate(posteriors):
-                post.write_check(check_days, s.T - check_days, cs.count[c], mean[c], var[c], check_chain_datasets(cs, c))
-            print(check_run_line(check_days, s.T, cs), file=log, flush=True)
-        records.append((lambda: s.reset_check(check_days, check_calendar[0], check_calendar[1], check_seed(seed)),   # once
-                        writes("check"), ck_finish))
-
-    # With `groups` (a `posterior.groups.GroupTable`, Mcmc.groups resolved by `mcmc`; needs one of summaries on / only,
-    # forecast, check) the table is set on the sampler once, before the first draw: from then on the summary, the forecast
-    # and the check of every burst also form the draw's sums over each group's members on the device, and these cross with
-    # the trace.  In the warm-up that rides on the summary which `summaries` already asks for there, and on nothing else.
-    # The statistics are formed here (`posterior.groups`).  Without it nothing of it is called.
-    # With Mcmc.groups_rt (needs `groups`, Mcmc.rt and `population` = N [M]) and Mcmc.groups_within_between (needs `groups`
-    # and Mcmc.within_between) the switches are set on the sampler once, behind the table: R_t, population-weighted, and the
-    # within / between pressures of every kept draw of the sampling phase are then also formed per group on the device and
-    # cross with the trace (`trace.group_curves`).  Without the keys nothing of it is called.
-    # With Mcmc.groups_ngm (needs `groups`, Mcmc.rt and Mcmc.groups_rt) the group next-generation matrix of every kept draw
-    # of the sampling phase is kept on the device: the switch is set once, behind set_group_rt and the rt reset, with a store
-    # of num_bursts x num_burst_samples draws per chain, and read once at the end of sampling.  It is no burst product: the
-    # draws' keywords are what they were.  Without the key nothing of it is called.
-    if groups is not None:                                  # the one record that calls the sampler here, ahead of the warm-up
-        G_mod.require_source(groups, summaries, horizon, check_days, groups_rt, groups_wb)
-        s.set_groups(groups.offsets, groups.members)        # once; the sources size their outputs at their resets
-        if groups_rt:
-            rt_w = G_mod.rt_weights(groups, population)
-            s.set_group_rt(rt_w)                            # once, behind the table; sized at the rt reset
-            for post in posteriors:
-                post.create_dataset("groups/rt_weights", rt_w)
-        if groups_wb:
-            s.set_group_within_between(True)
-        # the sources whose sums are written: the trace's only with summaries on / only (diagnostics alone also summarises
-        # every burst, but nothing of it goes to the file)
-        grp_src = tuple(k for k, on in (("trace", summaries != "off"), ("forecast", horizon), ("check", check_days)) if on)
+                post.write_diagnostics(diag_mod.chain_datasets(ev, c))
+            print(diag_mod.run_line(ev, diag_mod.theta_names(s.P, s.M, s.T))
+                  + f" ({s.B} chain(s) of this process, batches of {batch_len})", file=log, flush=True)
         if summaries != "off":
-            warm_kw["groups"] = ("trace",)
-        if grp_src:                                         # with the group curves alone there is nothing to ask for
-            burst_kw["groups"] = grp_src
-        grp_fc, grp_ck, grp_rt, grp_wb = [], [], [], []     # the sampling phase's group sums and curves, kept for the statistics
+            sm = s.summary() if dg is None else Summary(count=dg.count, ref=dg.ref, sum=dg.sum, sumsq=dg.sumsq)
+            mean, var = sm.mean, sm.var
+            for c, post in enumerate(posteriors):
+                post.write_summary(sm.count[c], mean[c], var[c])
+    return Record(begin, flush, finish, {} if summaries == "off" else dict(events=summaries != "only", summarize="marginals"),
+                  dict(events=summaries != "only", summarize=True))
 
-        def grp_flush(tr, burst):
-            if getattr(tr, "groups", None) is not None:
-                g = {k: np.array(v) for k, v in tr.groups.items()}   # the pinned buffer is used again two bursts later
-                if "forecast_by_group" in g:
-                    grp_fc.append((g["forecast_by_group"], g["forecast_group_state0"]))
-                if "check_by_group" in g:
-                    grp_ck.append(g["check_by_group"])
-                for c, post in enumerate(posteriors):
-                    if "seir_by_group" in g:
-                        post.write_samples({"seir_by_group": g["seir_by_group"][:, c]}, first_dim_offset=rows["offset"])
-                    post.write_samples({k: v[:, c] for k, v in g.items() if k.startswith("forecast_")}, first_dim_offset=rows["kept"])
-                    post.write_samples({k: v[:, c] for k, v in g.items() if k.startswith("check_")}, first_dim_offset=rows["kept"])
-            if (groups_rt or groups_wb) and getattr(tr, "group_curves", None) is not None:
-                gc = {k: np.array(v) for k, v in tr.group_curves.items()}   # the pinned buffer is used again two bursts later
-                if "rt_by_group" in gc:
-                    grp_rt.append(gc["rt_by_group"])
-                    write_rows({"R_t_by_group": gc["rt_by_group"]}, rows["kept"])
-                if "within_by_group" in gc:
-                    grp_wb.append((gc["within_by_group"], gc["between_by_group"]))
-                    write_rows({"within_pressure_by_group": gc["within_by_group"],
+
+def forecast_record(ctx):
+    """With Mcmc.forecast = H (`forecast_mode`) every kept draw of the sampling phase is forecast H days on the device
+    behind its burst; `forecast_calendar` = (W [H], weekday_c [H]) (`posterior.predict.forecast_calendar`) and `seed`
+    (the forecast's Philox stream and, with forecast_walk, the steps) are then needed.  The warm-up is not forecast.
+    With Mcmc.forecast_quantiles (`forecast_quantiles_mode`; needs Mcmc.forecast) the device keeps cases, cumulative cases
+    and prevalence of every forecast draw: the store is sized once, right behind the forecast's reset, for num_bursts x
+    num_burst_samples draws per chain, and at the end of the run exact quantiles per location and forecast day are selected
+    on the device, per chain and pooled over the chains of this process.  Without the key nothing of it is called."""
+    s, posteriors, log, total, horizon, walk, fq_probs = (ctx.s, ctx.posteriors, ctx.log, ctx.total, ctx.opt.horizon, ctx.opt.walk,
+                                                          ctx.opt.fq_probs)
+    if not horizon:
+        return None
+
+    def begin():
+        s.reset_forecast(horizon, ctx.forecast_calendar[0], ctx.forecast_calendar[1], ctx.seed)   # once: the sampling phase
+        if fq_probs:
+            s.keep_forecast_draws(total)                    # the draw store of the quantiles: every kept draw of the phase
+
+    def finish():
+        fs = s.forecast_summary()
+        mean, var = fs.mean, fs.var
+        for c, post in enumerate(posteriors):
+            post.write_forecast(horizon, s.T, fs.count[c], mean[c], var[c])
+        print(f"Forecast: {horizon} day(s) from day {s.T} for {int(fs.count.min()) if len(fs.count) else 0} kept draw(s) per "
+              f"chain, formed on the device ({'random-walk' if walk else 'held'} baseline); forecast/* and "
+              "samples/forecast_* written", file=log, flush=True)
+        if fq_probs and total:
+            own = s.forecast_quantiles(fq_probs)                        # [K,B,3,M,H]
+            pooled = s.forecast_quantiles(fq_probs, pooled=True)        # [K,3,M,H]
+            for c, post in enumerate(posteriors):
+                post.write_forecast_quantiles(fq_probs, own[:, c], pooled, ctx.chain_ids)
+            print(f"Forecast quantiles: {', '.join(f'{p:g}' for p in fq_probs)} of cases, cumulative cases and prevalence per "
+                  f"location and forecast day, exact over {total} kept draw(s) per chain and pooled over the {s.B} "
+                  "chain(s) of this process, selected on the device; forecast/*_quantiles written", file=log, flush=True)
+    return Record(begin, _writes(ctx, "forecast"), finish, {},
+                  dict(forecast=forecast_steps_fn(ctx.seed, ctx.chain_ids, horizon) if walk else True))
+
+
+def rt_record(ctx):
+    """With Mcmc.rt = D (`rt_mode`) R_it of every kept draw of the sampling phase over the last D days is formed and folded
+    on the device behind its burst (and behind the burst's summary and forecast); `rt_weight` [M] = N / N.sum() is then
+    needed.  The warm-up is not folded; without the key nothing of it is called.
+    With Mcmc.rt_quantiles (`rt_quantiles_mode`; needs Mcmc.rt) the device keeps R_it of every folded draw: the store is
+    sized once, right behind the rt reset, for num_bursts x num_burst_samples draws per chain, and at the end of the run
+    exact quantiles per day and location are selected on the device, per chain and pooled over the chains of this process;
+    the national curve's quantiles are formed here from the draws of R_t.  Without the key nothing of it is called."""
+    s, posteriors, log, total, rt_days, rq_probs = ctx.s, ctx.posteriors, ctx.log, ctx.total, ctx.opt.rt_days, ctx.opt.rq_probs
+    if not rt_days:
+        return None
+    rt_draws = []                                           # the national curve of every burst: flush keeps, finish reads
+
+    def begin():
+        s.reset_rt(rt_days, ctx.rt_weight)                  # once: the sampling phase
+        if rq_probs:
+            s.keep_rt_draws(total)                          # the draw store of the quantiles: every kept draw of the phase
+
+    def flush(tr, burst):
+        if getattr(tr, "rt", None) is not None:
+            rt_draws.append(np.array(tr.rt))                # the pinned buffer is used again two bursts later
+            write_rows(ctx, {"R_t": rt_draws[-1]}, ctx.rows["kept"])
+
+    def finish():
+        rs = s.rt_summary()
+        mean, var, prob = rs.mean, rs.var, rs.prob_gt1
+        for c, post in enumerate(posteriors):
+            post.write_rt(rt_days, s.T - rt_days, rs.count[c], mean[c], var[c], prob[c])
+        r_t = _stack(rt_draws, s.B, rt_days)
+        print(rt_run_line(rt_days, s.T, r_t, prob), file=log, flush=True)
+        if rq_probs and total:
+            own = s.rt_quantiles(rq_probs)                              # [K,B,D,M]
+            pooled = s.rt_quantiles(rq_probs, pooled=True)              # [K,D,M]
+            nat = draw_quantiles(r_t, rq_probs)                         # [K,B,D]: costs nothing here
+            pnat = draw_quantiles(r_t.reshape(-1, rt_days), rq_probs)   # [K,D]
+            for c, post in enumerate(posteriors):
+                post.write_rt_quantiles(rq_probs, own[:, c], pooled, ctx.chain_ids, nat[:, c], pnat)
+            print(rt_quantiles_run_line(rq_probs, rt_days, s.T, total, s.B, own), file=log, flush=True)
+    return Record(begin, flush, finish, {}, dict(rt=True))
+
+
+def check_record(ctx):
+    """With Mcmc.check = K (`check_mode`) the last K days are simulated again from every kept draw of the sampling phase and
+    set against the observed removals on the device, behind the burst's summary, forecast and R_t; `check_calendar` =
+    (W [K], weekday_c [K]) (`posterior.predict.check_calendar`) is then needed, and the check's stream is keyed by
+    `check_seed(seed)`.  The warm-up is not checked; without the key nothing of it is called."""
+    s, check_days = ctx.s, ctx.opt.check_days
+    if not check_days:
+        return None
+
+    def begin():
+        s.reset_check(check_days, ctx.check_calendar[0], ctx.check_calendar[1], check_seed(ctx.seed))   # once
+
+    def finish():
+        ctx.rows["check"] = cs = s.check_summary()          # read by the groups' finish, which runs behind this one
+        mean, var = cs.moments.mean, cs.moments.var
+        for c, post in enumerate(ctx.posteriors):
+            post.write_check(check_days, s.T - check_days, cs.count[c], mean[c], var[c], check_chain_datasets(cs, c))
+        print(check_run_line(check_days, s.T, cs), file=ctx.log, flush=True)
+    return Record(begin, _writes(ctx, "check"), finish, {}, dict(check=True))
+
+
+def groups_record(ctx):
+    """With `groups` (a `posterior.groups.GroupTable`, Mcmc.groups bound by `Products.bind`; needs one of summaries on / only, forecast,
+    check) the table is set on the sampler once, before the first draw: from then on the summary, the forecast and the check of every
+    burst also form the draw's sums over each group's members on the device, and these cross with the trace.  In the warm-up that rides
+    on the summary which `summaries` already asks for there, and on nothing else. The statistics are formed here (`posterior.groups`).
+    Without it nothing of it is called. With Mcmc.groups_rt (needs `groups`, Mcmc.rt and `population` = N [M]) and
+    Mcmc.groups_within_between (needs `groups` and Mcmc.within_between) the switches are set on the sampler once, behind the table: R_t,
+    population-weighted, and the within / between pressures of every kept draw of the sampling phase are then also formed per group on
+    the device and cross with the trace (`trace.group_curves`).  Without the keys nothing of it is called. With Mcmc.groups_ngm (needs
+    `groups`, Mcmc.rt and Mcmc.groups_rt) the group next-generation matrix of every kept draw of the sampling phase is kept on the
+    device: the switch is set once, behind set_group_rt and the rt reset, with a store of num_bursts x num_burst_samples draws per
+    chain, and read once at the end of sampling.  It is no burst product: the draws' keywords are what they were.  Without the key
+    nothing of it is called."""
+    s, opt, posteriors, log, rows, groups, total = ctx.s, ctx.opt, ctx.posteriors, ctx.log, ctx.rows, ctx.groups, ctx.total
+    if groups is None:
+        return None
+    summaries, horizon, check_days, rt_days, wb_days, fq_probs, rq_probs = (opt.summaries, opt.horizon, opt.check_days, opt.rt_days,
+                                                                            opt.wb_days, opt.fq_probs, opt.rq_probs)
+    # the one record that calls the sampler when it is built, ahead of the warm-up
+    s.set_groups(groups.offsets, groups.members)            # once; the sources size their outputs at their resets
+    if opt.grp_rt_on:
+        ctx.rt_w = G_mod.rt_weights(groups, ctx.population)
+        s.set_group_rt(ctx.rt_w)                            # once, behind the table; sized at the rt reset
+        for post in posteriors:
+            post.create_dataset("groups/rt_weights", ctx.rt_w)
+    if opt.grp_wb_on:
+        s.set_group_within_between(True)
+    # the sources whose sums are written: the trace's only with summaries on / only (diagnostics alone also summarises
+    # every burst, but nothing of it goes to the file); with the group curves alone there is nothing to ask for
+    sources = {k: name for k, name, on in (("trace", "the recorded epidemic", summaries != "off"), ("forecast", "the forecast", horizon),
+                                           ("check", "the check", check_days)) if on}
+    grp_fc, grp_ck, grp_rt, grp_wb = [], [], [], []         # the sampling phase's group sums and curves, kept for the statistics
+
+    def begin():
+        if opt.grp_ngm_on:      # the store is sized behind the rt reset (rt_record's begin, which runs first) and set_group_rt
+            s.set_group_ngm(ctx.rt_w, total)
+
+    def flush(tr, burst):
+        if getattr(tr, "groups", None) is not None:
+            g = {k: np.array(v) for k, v in tr.groups.items()}   # the pinned buffer is used again two bursts later
+            if "forecast_by_group" in g:
+                grp_fc.append((g["forecast_by_group"], g["forecast_group_state0"]))
+            if "check_by_group" in g:
+                grp_ck.append(g["check_by_group"])
+            for c, post in enumerate(posteriors):
+                if "seir_by_group" in g:
+                    post.write_samples({"seir_by_group": g["seir_by_group"][:, c]}, first_dim_offset=rows["offset"])
+                post.write_samples({k: v[:, c] for k, v in g.items() if k.startswith("forecast_")}, first_dim_offset=rows["kept"])
+                post.write_samples({k: v[:, c] for k, v in g.items() if k.startswith("check_")}, first_dim_offset=rows["kept"])
+        if (opt.grp_rt_on or opt.grp_wb_on) and getattr(tr, "group_curves", None) is not None:
+            gc = {k: np.array(v) for k, v in tr.group_curves.items()}   # the pinned buffer is used again two bursts later
+            if "rt_by_group" in gc:
+                grp_rt.append(gc["rt_by_group"])
+                write_rows(ctx, {"R_t_by_group": gc["rt_by_group"]}, rows["kept"])
+            if "within_by_group" in gc:
+                grp_wb.append((gc["within_by_group"], gc["between_by_group"]))
+                write_rows(ctx, {"within_pressure_by_group": gc["within_by_group"],
                                 "between_pressure_by_group": gc["between_by_group"]}, rows["kept"])
 
-        def grp_finish():
-            if horizon and grp_fc:
-                ev = np.concatenate([x[0] for x in grp_fc])     # [nf,B,G,H,3]
-                st0 = np.concatenate([x[1] for x in grp_fc])    # [nf,B,G,3]
-                state = G_mod.group_state(ev, st0)
-                q = None
-                if fq_probs:
-                    planes = G_mod.forecast_planes(ev, st0)     # [3,nf,B,G,H]
-                    q = {name: (G_mod.quantiles(planes[x], fq_probs),                                    # [K,B,G,H]
-                                G_mod.quantiles(planes[x].reshape((-1,) + planes.shape[3:]), fq_probs))   # [K,G,H]
-                         for x, name in enumerate(G_mod.PLANES)}
-                for c, post in enumerate(posteriors):
-                    post.write_group_forecast(ev[:, c].mean(axis=0), state[:, c].mean(axis=0),
-                                              None if q is None else {k: (v[0][:, c], v[1]) for k, v in q.items()})
-            if check_days and grp_ck:
-                sim = np.concatenate(grp_ck)                    # [nf,B,G,K,3]
-                for c, post in enumerate(posteriors):
-                    post.write_group_check(G_mod.check_counts(sim[:, c], groups.sum_rows(rows["check"].observed[c])))
-            sources = [k for k, on in (("the recorded epidemic", summaries != "off"), ("the forecast", horizon),
-                                       ("the check", check_days)) if on]
-            if sources:
-                print(G_mod.run_line(groups, sources), file=log, flush=True)
-            if groups_rt:
-                rg = _stack(grp_rt, s.B, groups.G, rt_days)     # [n,B,G,D]
-                q = None
-                if rq_probs and rg.shape[0]:
-                    q = (draw_quantiles(rg, rq_probs), draw_quantiles(rg.reshape((-1,) + rg.shape[2:]), rq_probs))   # [K,B,G,D], [K,G,D]
-                for c, post in enumerate(posteriors):
-                    post.write_group_rt(*G_mod.curve_moments(rg[:, c]), None if q is None else (q[0][:, c], q[1]))
-                print(G_mod.curve_run_line("R_t", groups, rg, "samples/R_t_by_group and rt/group_*"), file=log, flush=True)
-            if groups_ngm:
-                K = s.read_group_ngm(total) if total else np.empty((0, s.B, groups.G, groups.G, rt_days))   # [n,B,G,G,D]
-                rg = _stack(grp_rt, s.B, groups.G, rt_days)     # [n,B,G,D]: the denominator of the local share
-                part = G_mod.is_partition(groups, s.M)
-                pooled = None
-                if rq_probs and K.shape[0]:
-                    ps = G_mod.ngm_stats(K.reshape((-1,) + K.shape[2:]), rg.reshape((-1,) + rg.shape[2:]), rq_probs)
-                    pooled = (ps["K_quantiles"], ps["local_share_quantiles"], chain_ids)
-                for c, post in enumerate(posteriors):
-                    post.write_group_ngm(rt_days, s.T - rt_days, K[:, c],
-                                         G_mod.ngm_stats(K[:, c], rg[:, c], rq_probs if rq_probs and K.shape[0] else None),
-                                         pooled, G_mod.spectral_radius(K[:, c]) if part else None)
-                print(G_mod.ngm_run_line(groups, K, rg), file=log, flush=True)
-            if groups_wb:
-                wg, bg = (_stack([x[i] for x in grp_wb], s.B, groups.G, wb_days) for i in (0, 1))
-                for c, post in enumerate(posteriors):
-                    post.write_group_within_between(*G_mod.share_stats(wg[:, c], bg[:, c]))
-                with np.errstate(divide="ignore", invalid="ignore"):
-                    share = wg / (wg + bg)
-                print(G_mod.curve_run_line("Within share of the infection pressure (between: from outside each member location)",
-                                           groups, share, "samples/*_pressure_by_group and within_between/group_*"),
-                      file=log, flush=True)
-        # the store is sized behind the rt reset (the rt record's begin, which runs first) and the switch of group R_t
-        grp = ((lambda: s.set_group_ngm(rt_w, total)) if groups_ngm else (lambda: None), grp_flush, grp_finish)
-        records.append(grp)
-
-    # With Mcmc.within_between = D (`within_between_mode`) the within/between pressure shares of every kept draw of the
-    # sampling phase over the last D days are formed and folded on the device, behind the burst's summary, forecast, R_t and
-    # check.  The warm-up is not folded; without the key nothing of it is called.
-    if wb_days:
-        burst_kw["within_between"], wb_draws = True, []
-
-        def wb_flush(tr, burst):
-            if getattr(tr, "wb", None) is not None:
-                wb_draws.append({k: np.array(v) for k, v in tr.wb.items()})   # the pinned buffer is used again two bursts later
-                write_rows(wb_draws[-1], rows["kept"])
-
-        def wb_finish():
-            ws = s.within_between_summary()
-            wm, wv, bm, pg = ws.within_mean, ws.within_var, ws.between_mean, ws.p_within_gt_between
+    def finish():
+        if horizon and grp_fc:
+            ev = np.concatenate([x[0] for x in grp_fc])     # [nf,B,G,H,3]
+            st0 = np.concatenate([x[1] for x in grp_fc])    # [nf,B,G,3]
+            state = G_mod.group_state(ev, st0)
+            q = None
+            if fq_probs:
+                planes = G_mod.forecast_planes(ev, st0)     # [3,nf,B,G,H]
+                q = {name: (G_mod.quantiles(planes[x], fq_probs),                                    # [K,B,G,H]
+                            G_mod.quantiles(planes[x].reshape((-1,) + planes.shape[3:]), fq_probs))   # [K,G,H]
+                     for x, name in enumerate(G_mod.PLANES)}
             for c, post in enumerate(posteriors):
-                post.write_within_between(wb_days, s.T - wb_days, ws.count[c], ws.defined[c], wm[c], wv[c], bm[c], pg[c])
-            wn, bn = (_stack([w[k] for w in wb_draws], s.B, wb_days) for k in ("within_pressure", "between_pressure"))
-            print(within_between_run_line(wb_days, s.T, wn, bn, pg), file=log, flush=True)
-        records.append((lambda: s.reset_within_between(wb_days), wb_flush, wb_finish))   # the reset: once, the sampling phase
+                post.write_group_forecast(ev[:, c].mean(axis=0), state[:, c].mean(axis=0),
+                                          None if q is None else {k: (v[0][:, c], v[1]) for k, v in q.items()})
+        if check_days and grp_ck:
+            sim = np.concatenate(grp_ck)                    # [nf,B,G,K,3]
+            for c, post in enumerate(posteriors):
+                post.write_group_check(G_mod.check_counts(sim[:, c], groups.sum_rows(rows["check"].observed[c])))
+        if sources:
+            print(G_mod.run_line(groups, list(sources.values())), file=log, flush=True)
+        rg = _stack(grp_rt, s.B, groups.G, rt_days)         # [n,B,G,D]; for the matrix: the denominator of the local share
+        if opt.grp_rt_on:
+            q = None
+            if rq_probs and rg.shape[0]:
+                q = (draw_quantiles(rg, rq_probs), draw_quantiles(rg.reshape((-1,) + rg.shape[2:]), rq_probs))   # [K,B,G,D], [K,G,D]
+            for c, post in enumerate(posteriors):
+                post.write_group_rt(*G_mod.curve_moments(rg[:, c]), None if q is None else (q[0][:, c], q[1]))
+            print(G_mod.curve_run_line("R_t", groups, rg, "samples/R_t_by_group and rt/group_*"), file=log, flush=True)
+        if opt.grp_ngm_on:
+            K = s.read_group_ngm(total) if total else np.empty((0, s.B, groups.G, groups.G, rt_days))   # [n,B,G,G,D]
+            part = G_mod.is_partition(groups, s.M)
+            pooled = None
+            if rq_probs and K.shape[0]:
+                ps = G_mod.ngm_stats(K.reshape((-1,) + K.shape[2:]), rg.reshape((-1,) + rg.shape[2:]), rq_probs)
+                pooled = (ps["K_quantiles"], ps["local_share_quantiles"], ctx.chain_ids)
+            for c, post in enumerate(posteriors):
+                post.write_group_ngm(rt_days, s.T - rt_days, K[:, c],
+                                     G_mod.ngm_stats(K[:, c], rg[:, c], rq_probs if rq_probs and K.shape[0] else None),
+                                     pooled, G_mod.spectral_radius(K[:, c]) if part else None)
+            print(G_mod.ngm_run_line(groups, K, rg), file=log, flush=True)
+        if opt.grp_wb_on:
+            wg, bg = (_stack([x[i] for x in grp_wb], s.B, groups.G, wb_days) for i in (0, 1))
+            for c, post in enumerate(posteriors):
+                post.write_group_within_between(*G_mod.share_stats(wg[:, c], bg[:, c]))
+            with np.errstate(divide="ignore", invalid="ignore"):
+                share = wg / (wg + bg)
+            print(G_mod.curve_run_line("Within share of the infection pressure (between: from outside each member location)",
+                                       groups, share, "samples/*_pressure_by_group and within_between/group_*"),
+                  file=log, flush=True)
+    return Record(begin, flush, finish, dict(groups=("trace",)) if summaries != "off" else {}, dict(groups=tuple(sources)) if sources else {})
+
+
+def within_between_record(ctx):
+    """With Mcmc.within_between = D (`within_between_mode`) the within/between pressure shares of every kept draw of the
+    sampling phase over the last D days are formed and folded on the device, behind the burst's summary, forecast, R_t and
+    check.  The warm-up is not folded; without the key nothing of it is called."""
+    s, wb_days = ctx.s, ctx.opt.wb_days
+    if not wb_days:
+        return None
+    wb_draws = []                                           # the national pressures of every burst: flush keeps, finish reads
+
+    def begin():
+        s.reset_within_between(wb_days)                     # once: the sampling phase
+
+    def flush(tr, burst):
+        if getattr(tr, "wb", None) is not None:
+            wb_draws.append({k: np.array(v) for k, v in tr.wb.items()})   # the pinned buffer is used again two bursts later
+            write_rows(ctx, wb_draws[-1], ctx.rows["kept"])
+
+    def finish():
+        ws = s.within_between_summary()
+        wm, wv, bm, pg = ws.within_mean, ws.within_var, ws.between_mean, ws.p_within_gt_between
+        for c, post in enumerate(ctx.posteriors):
+            post.write_within_between(wb_days, s.T - wb_days, ws.count[c], ws.defined[c], wm[c], wv[c], bm[c], pg[c])
+        wn, bn = (_stack([w[k] for w in wb_draws], s.B, wb_days) for k in ("within_pressure", "between_pressure"))
+        print(within_between_run_line(wb_days, s.T, wn, bn, pg), file=ctx.log, flush=True)
+    return Record(begin, flush, finish, {}, dict(within_between=True))
+
+
+# in the order of the resets and the write-up
+RECORD_BUILDERS = (summaries_record, forecast_record, rt_record, check_record, groups_record, within_between_record)
+
+
+def product_records(sampler, config, posteriors, log=sys.stderr, forecast_calendar=None, seed=0, rt_weight=None,
+                    check_calendar=None, groups=None, population=None, total=None, results=True):
+    """What `run_mcmc` and `posterior.replay.replay_files` share: the options resolved (`resolve_products`; a resolved section resolves to
+    itself) and the missing inputs refused before the first call on the sampler, the products' `Record`s in the order of the resets and
+    the write-up, the keywords of the warm-up's and the sampling phase's draws, the diagnostics' marks and the row bookkeeping.
+    `total`: the kept draws per chain the products will see (default num_bursts x num_burst_samples: what sizes the draw stores);
+    `results=False`: a burst's flush writes the parameters' rows and the marginals only (a replay has no kernel results and no event
+    tensor)."""
+    config, opt = resolve_products(config)
+    opt.windows(getattr(sampler, "T", None))
+    if opt.check_days and check_calendar is None:
+        raise ValueError("check: run_mcmc needs check_calendar = (W, weekday_c) of the window")
+    if opt.rt_days and rt_weight is None:
+        raise ValueError("rt: run_mcmc needs rt_weight = N / N.sum()")
+    if opt.horizon and forecast_calendar is None:
+        raise ValueError("forecast: run_mcmc needs forecast_calendar = (W, weekday_c) of the forecast days")
+    opt.require(groups)
+    if opt.grp_rt_on and population is None:
+        raise ValueError("groups_rt: run_mcmc needs population = N")
+    nb, ns = int(config["num_bursts"]), int(config["num_burst_samples"])
+
+    ctx = types.SimpleNamespace(
+        s=sampler, opt=opt, posteriors=posteriors, log=log, seed=seed, forecast_calendar=forecast_calendar, rt_weight=rt_weight,
+        check_calendar=check_calendar, groups=groups, population=population,
+        total=nb * ns if total is None else int(total),     # kept draws per chain that the products will see
+        chain_ids=[getattr(sampler, "first_chain_id", 0) + c for c in range(sampler.B)],
+        marks=diagnostics_marks(nb) if opt.diagnostics == "on" else {},
+        # `offset` counts every written draw, `kept` the sampling phase's: the row of every product's per-draw datasets (a field
+        # is in a trace exactly when its keyword was passed: all together, on the sampling phase's bursts); `check`: the
+        # check's summary, written by check_record's finish and read by groups_record's, which runs behind it
+        rows=dict(offset=0, kept=0, check=None),
+        # the weights of the group R_t: written by groups_record when it is built (groups_rt on), read by its begin for the
+        # group next-generation matrix -- set whenever it is read, because `require_ngm` holds groups_ngm to groups_rt
+        rt_w=None)
+    built = {build: build(ctx) for build in RECORD_BUILDERS}   # None: the product is off, nothing of it is called
+    records = [r for r in built.values() if r is not None]
+    warm_kw, burst_kw = {}, {}                              # the keywords of the warm-up's and the sampling phase's draws
+    for r in records:
+        warm_kw.update(r.warm_kw)
+        burst_kw.update(r.burst_kw)
     # a burst is written out groups first, then last record to first: the order the files have always been written in
+    grp = built[groups_record]
     flush_order = ([grp] if grp else []) + [r for r in reversed(records) if r is not grp]
+    rows, summaries = ctx.rows, opt.summaries
 
     def flush(tr, burst=None):
-        for _, product_flush, _ in flush_order:
-            product_flush(tr, burst)
+        for r in flush_order:
+            r.flush(tr, burst)
         for c, post in enumerate(posteriors):
             if not results:                                 # a replay: the parameters' rows and the marginals, nothing else
-                post.write_samples(theta_to_dict(tr.theta[:, c], s.M, s.T, None if summaries == "off" else tr.marginals, c),
+                post.write_samples(theta_to_dict(tr.theta[:, c], sampler.M, sampler.T, None if summaries == "off" else tr.marginals, c),
                                    first_dim_offset=rows["offset"])
                 continue
             post.write_samples(draws_to_dict(tr.theta, tr.events, c, **({} if summaries == "off" else dict(marginals=tr.marginals))),
@@ -1073,7 +960,7 @@ def product_records(sampler, config, posteriors, log=sys.stderr, forecast_calend
             rows["kept"] += tr.theta.shape[0]
         return tr
 
-    return types.SimpleNamespace(records=records, flush=flush, warm_kw=warm_kw, burst_kw=burst_kw, marks=marks, thin=thin,
+    return types.SimpleNamespace(records=records, flush=flush, warm_kw=warm_kw, burst_kw=burst_kw, marks=ctx.marks, thin=opt.thin,
                                  nb=nb, ns=ns, rows=rows)
 
 
@@ -1085,15 +972,12 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     the sampling phase keeps every `thin`-th sweep: num_burst_samples kept draws per burst from
     num_burst_samples * thin sweeps (inference.py:455), thinned on the device.
 
-    What each option adds is said at its record below, a product's three parts side by side: begin() -- the reset behind
-    the warm-up, the draw store where quantiles are on; flush(tr, burst) -- what must outlive the pinned view copied, its
-    datasets written at its row offset, what the end needs kept (burst is None in the warm-up); finish() -- the blocking
-    summary read, the write_* calls and the log line.  A product that is off has no record: nothing of it is called."""
+    What each option adds is said at its builder above (`RECORD_BUILDERS`), a product's three parts side by side in a
+    `Record`.  A product that is off has no record: nothing of it is called."""
     # 1. resolve the modes and refuse what cannot run -- before the first call on the sampler (product_records)
     pr = product_records(sampler, config, posteriors, log=log, forecast_calendar=forecast_calendar, seed=seed, rt_weight=rt_weight,
                          check_calendar=check_calendar, groups=groups, population=population)
-    records, flush, warm_kw, burst_kw, marks, thin, nb, ns, rows = (pr.records, pr.flush, pr.warm_kw, pr.burst_kw, pr.marks,
-                                                                    pr.thin, pr.nb, pr.ns, pr.rows)
+    flush, marks, thin, nb, ns = pr.flush, pr.marks, pr.thin, pr.nb, pr.ns
 
     # 2. warm up
     sampler.set_thin(1)
@@ -1103,7 +987,7 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     def window(n, adapt_mass, running_variance=None):
         sampler.set_adaptation(adapt_step_size=True, adapt_mass=adapt_mass, num_adaptation_steps=n,
                                running_variance=running_variance, **dual_averaging_kwargs)
-        tr = flush(sampler.sample(n, **warm_kw))
+        tr = flush(sampler.sample(n, **pr.warm_kw))
         return tr, get_weighted_running_variance(unconstrain_theta(tr.theta))
 
     print(f"Fast window {first_window_size}", file=log, flush=True)
@@ -1128,8 +1012,8 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     sampler.set_adaptation(adapt_step_size=False)
     sampler.set_kernel(step_size=step_size, variance=sampler.get_kernel()[1])
     sampler.set_thin(thin)                                  # in force from the first burst's trace reset
-    for begin, _, _ in records:
-        begin()
+    for record in pr.records:
+        record.begin()
 
     def on_burst(tr, i):
         flush(tr, i)
@@ -1138,10 +1022,10 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     if nb and ns and sampler.cap >= 2 * ns:
         # bursts overlap: while burst k+1 runs, burst k crosses PCIe into page-locked memory and is written
         # to the HDF5 file on a worker thread (ChainSampler.sample_bursts)
-        sampler.sample_bursts(nb, ns, on_burst, **burst_kw, **(dict(marks=marks) if marks else {}))
+        sampler.sample_bursts(nb, ns, on_burst, **pr.burst_kw, **(dict(marks=marks) if marks else {}))
     else:
         for i in range(nb):
-            tr = sampler.sample(ns, **burst_kw)
+            tr = sampler.sample(ns, **pr.burst_kw)
             if i in marks:
                 sampler.mark(marks[i])
             on_burst(tr, i)
@@ -1151,9 +1035,9 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
               f"(thin {thin}, {sampler.B} chain(s), device->host->disk included)", file=log, flush=True)
 
     # 4. write up
-    for _, _, finish in records:
-        finish()
-    return rows["offset"]
+    for record in pr.records:
+        record.finish()
+    return pr.rows["offset"]
 
 
 def warmup_size():
@@ -1216,101 +1100,6 @@ def launch_forms(lay, device_arg, hmc="auto", moves="auto", env=os.environ):
            ("paired-launch" if shared else "paired") if moves == "auto" else moves
 
 
-def resolve_products(config, thin=None, summaries=None, diagnostics=None, diagnostics_batch=None, forecast=None, forecast_walk=None,
-                     rt=None, check=None, forecast_quantiles=None, within_between=None, rt_quantiles=None, groups=None, groups_rt=None,
-                     groups_within_between=None, groups_ngm=None):
-    """The Mcmc section with the command line's overrides applied, every product option resolved by its `*_mode` function
-    and refused here where it cannot run -- before any GPU call -- and what `mcmc` and `posterior.replay` need of it next to
-    the section: the windows, the horizon, the group specification and the group switches."""
-    wb_days = 0
-    if within_between is not None or "within_between" in config:
-        wb_days = within_between_mode(config, within_between)   # refused here: before any GPU call
-        config = {k: v for k, v in config.items() if k != "within_between"}
-        if wb_days:
-            config = dict(config, within_between=wb_days)
-    check_days = 0
-    if check is not None or "check" in config:
-        check_days = check_mode(config, check)              # refused here: before any GPU call
-        config = {k: v for k, v in config.items() if k != "check"}
-        if check_days:
-            config = dict(config, check=check_days)
-    rt_days = 0
-    if rt is not None or "rt" in config:
-        rt_days = rt_mode(config, rt)                       # refused here: before any GPU call
-        config = {k: v for k, v in config.items() if k != "rt"}
-        if rt_days:
-            config = dict(config, rt=rt_days)
-    if rt_quantiles is not None or "rt_quantiles" in config:
-        rq_probs = rt_quantiles_mode(config, rt_quantiles, rt_days=rt_days)   # refused here: before any GPU call
-        config = {k: v for k, v in config.items() if k != "rt_quantiles"}
-        if rq_probs:
-            config = dict(config, rt_quantiles=list(rq_probs))
-    horizon = 0
-    if forecast is not None or forecast_walk is not None or "forecast" in config or "forecast_walk" in config:
-        horizon, walk = forecast_mode(config, forecast, forecast_walk)    # refused here: before any GPU call
-        config = {k: v for k, v in config.items() if k not in ("forecast", "forecast_walk")}
-        if horizon:
-            config = dict(config, forecast=horizon, forecast_walk=walk)
-    if forecast_quantiles is not None or "forecast_quantiles" in config:
-        fq_probs = forecast_quantiles_mode(config, forecast_quantiles, horizon=horizon)   # refused here: before any GPU call
-        config = {k: v for k, v in config.items() if k != "forecast_quantiles"}
-        if fq_probs:
-            config = dict(config, forecast_quantiles=list(fq_probs))
-    config = dict(config, thin=thin_interval(config, thin))  # refused here if < 1: before any GPU call
-    config = dict(config, summaries=summaries_mode(config, summaries))    # an unknown value likewise
-    if diagnostics is not None or diagnostics_batch is not None or "diagnostics" in config or "diagnostics_batch" in config:
-        mode, batch_len = diagnostics_mode(config, diagnostics, diagnostics_batch)   # and too few bursts, or a batch length that does not fit
-        config = dict(config, diagnostics=mode, **(dict(diagnostics_batch=batch_len) if mode == "on" else {}))
-    group_spec = config.get("groups") if groups is None else groups
-    grp_rt_on = G_mod.switch(config.get("groups_rt") if groups_rt is None else groups_rt, "groups_rt")
-    grp_wb_on = G_mod.switch(config.get("groups_within_between") if groups_within_between is None else groups_within_between,
-                             "groups_within_between")
-    grp_ngm_on = G_mod.switch(config.get("groups_ngm") if groups_ngm is None else groups_ngm, "groups_ngm")
-    config = {k: v for k, v in config.items() if k not in ("groups", "groups_rt", "groups_within_between", "groups_ngm")}
-    if grp_ngm_on:
-        config = dict(config, groups_ngm=True)
-    if grp_rt_on:
-        config = dict(config, groups_rt=True)
-    if grp_wb_on:
-        config = dict(config, groups_within_between=True)
-    return config, types.SimpleNamespace(wb_days=wb_days, check_days=check_days, rt_days=rt_days, horizon=horizon, group_spec=group_spec,
-                                         grp_rt_on=grp_rt_on, grp_wb_on=grp_wb_on, grp_ngm_on=grp_ngm_on)
-
-
-def posterior_kwargs(config, opt, group_table, kept):
-    """The keywords of `Posterior` for the products that are on, `kept` rows in the per-draw datasets of the sampling phase."""
-    horizon, rt_days, check_days, wb_days = opt.horizon, opt.rt_days, opt.check_days, opt.wb_days
-    return dict(**({} if config["summaries"] == "off" else dict(summaries=config["summaries"])),
-                **(dict(forecast=(horizon, kept)) if horizon else {}),
-                **(dict(rt=(rt_days, kept)) if rt_days else {}),
-                **(dict(check=(check_days, kept)) if check_days else {}),
-                **(dict(within_between=(wb_days, kept)) if wb_days else {}),
-                **(dict(groups=group_table.G) if group_table is not None else {}),
-                **(dict(group_curves={k: (d, kept) for k, on, d in (("rt", opt.grp_rt_on, rt_days), ("within_between", opt.grp_wb_on, wb_days))
-                                      if on}) if opt.grp_rt_on or opt.grp_wb_on else {}))
-
-
-def product_inputs(cov, dates, T, opt, seed, group_table):
-    """What the products need beyond the sampler, as keywords of `run_mcmc` / `product_records`: the calendars of the
-    forecast and of the check, the national weights, the seed, the group table and the population."""
-    kw = {}
-    if opt.horizon:
-        from ..posterior.predict import forecast_calendar
-        kw = dict(forecast_calendar=forecast_calendar(cov, dates, T, opt.horizon), seed=seed)
-    if opt.rt_days:
-        N = np.asarray(cov.N, dtype=np.float64).reshape(-1)
-        kw["rt_weight"] = N / N.sum()                       # reproduction_number.py:82-83
-    if opt.check_days:
-        from ..posterior.predict import check_calendar
-        kw["check_calendar"] = check_calendar(cov, dates, T, opt.check_days)
-        kw["seed"] = seed
-    if group_table is not None:
-        kw["groups"] = group_table
-        if opt.grp_rt_on:
-            kw["population"] = np.asarray(cov.N, dtype=np.float64).reshape(-1)
-    return kw
-
-
 def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool_step_size=False, init_jitter=0.0,
          events_dtype="auto", hmc="auto", moves="auto", thin=None, summaries=None, diagnostics=None, diagnostics_batch=None,
          forecast=None, forecast_walk=None, rt=None, check=None, forecast_quantiles=None, within_between=None,
@@ -1321,42 +1110,22 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     global ids rank*num_chains ... (the Philox streams are keyed by the global id, so the draws of chain c
     do not depend on how the job is sharded) and writes its own posterior_chain{c}.hd5; there is no
     data-path collective.  `pool_step_size` adds the one optional exchange: an all_gather of one float64
-    per chain after warm-up.  `thin` overrides config["thin"] (every rank is given the same value), `summaries`
-    config["summaries"] (`summaries_mode`), `diagnostics` / `diagnostics_batch` config["diagnostics"] /
-    config["diagnostics_batch"] (`diagnostics_mode`), `forecast` / `forecast_walk` config["forecast"] /
-    config["forecast_walk"] (`forecast_mode`), `forecast_quantiles` config["forecast_quantiles"]
-    (`forecast_quantiles_mode`), `rt` config["rt"] (`rt_mode`), `check` config["check"] (`check_mode`), `within_between`
-    config["within_between"] (`within_between_mode`), `rt_quantiles` config["rt_quantiles"] (`rt_quantiles_mode`), `groups`
-    config["groups"] (`posterior.groups.parse_groups`: "nations" or a mapping name -> members), `groups_rt` config["groups_rt"]
-    and `groups_within_between` config["groups_within_between"] (on / off; `posterior.groups.require_curves`), `groups_ngm`
-    config["groups_ngm"] (on / off; `posterior.groups.require_ngm`)."""
+    per chain after warm-up.  `thin` (every rank is given the same value) and every product keyword override the key of
+    their name in `config`; `inference/options.py` says what each accepts and refuses."""
     config, opt = resolve_products(config, thin=thin, summaries=summaries, diagnostics=diagnostics, diagnostics_batch=diagnostics_batch,
                                    forecast=forecast, forecast_walk=forecast_walk, rt=rt, check=check,
                                    forecast_quantiles=forecast_quantiles, within_between=within_between, rt_quantiles=rt_quantiles,
                                    groups=groups, groups_rt=groups_rt, groups_within_between=groups_within_between,
-                                   groups_ngm=groups_ngm)
-    wb_days, check_days, rt_days, horizon = opt.wb_days, opt.check_days, opt.rt_days, opt.horizon
-    group_spec, grp_rt_on, grp_wb_on, grp_ngm_on = opt.group_spec, opt.grp_rt_on, opt.grp_wb_on, opt.grp_ngm_on
+                                   groups_ngm=groups_ngm)          # every option refusal: before the data file is opened
     lay = job_layout(num_chains, device)                    # before any GPU call
     cov, cases, dates = read_inference_data(data_file)
-    # the table against the input's locations, and groups without a source: refused here, before any GPU call
-    group_table = None
-    if not G_mod.is_off(group_spec):                        # absent: the input's location coordinate is not even opened
-        group_table = G_mod.parse_groups(group_spec, cases.shape[0], read_location_names(data_file))
-    G_mod.require_curves(group_table, grp_rt_on, rt_days, grp_wb_on, wb_days)   # likewise before any GPU call
-    G_mod.require_ngm(group_table, grp_ngm_on, rt_days, grp_rt_on)
-    G_mod.require_source(group_table, config["summaries"], horizon, check_days, grp_rt_on, grp_wb_on)
     rng = np.random.default_rng(seed)                       # same imputation on every rank: one initial state per job
     B = int(num_chains)
     initial_state, events = model_spec.initial_conditions(cases, cov.N, rng)
     M, T = events.shape[0], events.shape[1]
     P = model_spec.num_params(M, T)
-    if rt_days:
-        rt_mode(config, T=T)                                # the window against the series: still before any GPU call
-    if check_days:
-        check_mode(config, T=T)                             # likewise
-    if wb_days:
-        within_between_mode(config, T=T)                    # likewise
+    # the table, groups without a source, the windows: refused before any GPU call (no groups: the location coordinate is not opened)
+    group_table = opt.bind(cases.shape[0], T, lambda: read_location_names(data_file))
     cfg = event_kernel_config(config)
     num_samples = warmup_size() + int(config["num_burst_samples"]) * int(config["num_bursts"])
     cap = max(800, 2 * int(config["num_burst_samples"]))      # two halves: a burst runs while the previous one is written
@@ -1444,97 +1213,16 @@ def main(argv=None):
     parser.add_argument("--thin", type=int, default=None, metavar="K",
                         help="keep every K-th sweep of the sampling phase, thinned on the device (overrides Mcmc.thin of the "
                              "configuration; the warm-up is never thinned, the shape of the output does not depend on it)")
-    parser.add_argument("--summaries", choices=list(SUMMARIES), default=None,
-                        help="summaries of the latent epidemic formed on the device (overrides Mcmc.summaries; default off): "
-                             "on = per-draw marginals samples/seir_by_day, seir_by_location, state_by_day and per-cell "
-                             "summaries/* mean and variance of events and state over the sampling phase, next to samples/seir; "
-                             "only = the same without samples/seir, whose tensors then never leave the device")
-    parser.add_argument("--diagnostics", choices=list(DIAGNOSTICS), default=None,
-                        help="convergence diagnostics formed on the device and the host as the run goes (overrides "
-                             "Mcmc.diagnostics; default off): on = a group diagnostics/ in every chain's file with split R-hat "
-                             "over this process's chains, batch-means ESS and the half-chain moments that "
-                             "`python -m covid19uk_amd.posterior.diagnostics` pools over files; needs num_bursts >= 2 and "
-                             "folds the sampling phase's draws on the device whatever --summaries says")
-    parser.add_argument("--diagnostics-batch", type=int, default=None, metavar="L",
-                        help="batch length of the batch-means ESS in kept draws (overrides Mcmc.diagnostics_batch; default "
-                             "num_burst_samples, which it must divide or be a multiple of)")
-    parser.add_argument("--forecast", type=int, default=None, metavar="H",
-                        help="simulate H days (1..128) forward from the end of the series for every kept draw of the "
-                             "sampling phase, on the device (overrides Mcmc.forecast; default off): a group forecast/ with "
-                             "the mean and variance of events and state per location and forecast day, and per-draw "
-                             "samples/forecast_by_day, forecast_by_location, forecast_state_by_day; works with "
-                             "--summaries only")
-    parser.add_argument("--forecast-walk", action="store_true", default=None,
-                        help="let the forecast's log baseline continue as the prior's random walk (N(0, 0.005) steps) "
-                             "instead of holding its last value (overrides Mcmc.forecast_walk; needs --forecast)")
-    parser.add_argument("--forecast-quantiles", type=str, default=None, metavar="P,P,...",
-                        help="exact quantiles of the forecast draws per location and forecast day, selected on the device "
-                             "(overrides Mcmc.forecast_quantiles; needs --forecast): 1 to 8 increasing probabilities in [0, 1], "
-                             "e.g. 0.05,0.5,0.95; forecast/cases_quantiles, cum_cases_quantiles, prevalence_quantiles per "
-                             "chain and forecast/pooled_* over the chains of the process; works with --summaries only and --thin")
-    parser.add_argument("--rt", type=int, default=None, metavar="D",
-                        help="form the reproduction number R_it of every kept draw of the sampling phase over the last D "
-                             "days (1..T) on the device (overrides Mcmc.rt; default off): a group rt/ with the mean, "
-                             "variance and P(R > 1) per day and location, and the national curve per draw samples/R_t; "
-                             "works with --summaries only, --thin and --forecast")
-    parser.add_argument("--rt-quantiles", type=str, default=None, metavar="P,P,...", dest="rt_quantiles",
-                        help="exact quantiles of the R_it draws per day of the window and location, selected on the device "
-                             "(overrides Mcmc.rt_quantiles; needs --rt): 1 to 8 increasing probabilities in [0, 1], e.g. "
-                             "0.05,0.5,0.95; rt/R_it_quantiles per chain, rt/pooled_R_it_quantiles over the chains of the "
-                             "process and rt/R_t_quantiles of the national curve; works with --summaries only and --thin")
-    parser.add_argument("--check", type=int, default=None, metavar="K",
-                        help="simulate the last K observed days (1..min(T, 128)) again from every kept draw of the sampling "
-                             "phase and set them against the observed removals, on the device (overrides Mcmc.check; default "
-                             "off): a group check/ with the moments of the re-simulated window, the counts of draws below / "
-                             "at the data per cell, location, day and in total with their mid-p values, and per-draw "
-                             "samples/check_by_day, check_by_location, check_state_by_day; works with --summaries only, "
-                             "--thin, --forecast and --rt")
-    parser.add_argument("--within-between", type=int, default=None, metavar="D", dest="within_between",
-                        help="form the within- and between-location shares of the infection pressure of every kept draw of "
-                             "the sampling phase over the last D days (1..T) on the device (overrides Mcmc.within_between; "
-                             "default off): a group within_between/ with the mean and variance of the within share, the "
-                             "mean of the between share and P(within > between) per day and location, and the national "
-                             "pressures per draw samples/within_pressure, between_pressure; works with --summaries only, "
-                             "--thin, --forecast, --rt and --check")
-    parser.add_argument("--groups", type=str, default=None, metavar="SPEC",
-                        help="per-draw totals over groups of locations, formed on the device for the recorded epidemic "
-                             "(--summaries on/only), the forecast and the check (overrides Mcmc.groups; default off): "
-                             "'nations' groups by the first letter of the location code (needs an input file with a location "
-                             "coordinate), or a path to a YAML mapping name: [members], a member being a location code, a "
-                             "prefix pattern E0* or an integer index; groups/*, samples/*_by_group and the group_* datasets "
-                             "of forecast/ and check/; needs one of --summaries on/only, --forecast, --check")
-    parser.add_argument("--groups-rt", action="store_true", default=None, dest="groups_rt",
-                        help="R_t of every kept draw per group, population-weighted over the group's members, formed on the "
-                             "device (overrides Mcmc.groups_rt; needs --groups and --rt): samples/R_t_by_group, rt/group_R_t_mean, "
-                             "group_R_t_var, group_prob_gt1 and, with --rt-quantiles, rt/group_R_t_quantiles")
-    parser.add_argument("--groups-within-between", action="store_true", default=None, dest="groups_within_between",
-                        help="within / between infection pressure of every kept draw per group, formed on the device (overrides "
-                             "Mcmc.groups_within_between; needs --groups and --within-between): samples/within_pressure_by_group, "
-                             "between_pressure_by_group and within_between/group_*; 'between' is from outside each member "
-                             "location, as in the national figure, not from outside the group")
-    parser.add_argument("--groups-ngm", action="store_true", default=None, dest="groups_ngm",
-                        help="group next-generation matrix of every kept draw, formed on the device (overrides Mcmc.groups_ngm; "
-                             "needs --groups, --rt and --groups-rt): K[g][h][t], the expected infections in group g caused by one "
-                             "typical infective of group h -- samples/ngm_by_group, ngm/K_mean, K_var, local_share_mean (the "
-                             "part of a group's R_t that stays inside it), with --rt-quantiles their quantiles, and for a "
-                             "partition samples/ngm_spectral_radius")
+    add_product_arguments(parser)
     args = parser.parse_args(argv)
     if args.thin is not None and args.thin < 1:
         parser.error(f"--thin {args.thin}: the thinning interval is >= 1")
     with open(args.config, "r") as f:
         config = yaml.load(f, Loader=yaml.FullLoader)
+    always = ("summaries", "diagnostics", "diagnostics_batch", "forecast", "forecast_walk", "rt")   # passed on even when None
     mcmc(args.data_file, args.output, config["Mcmc"], seed=args.seed, num_chains=args.chains, device=args.device,
          pool_step_size=args.pool_step_size, init_jitter=args.init_jitter, events_dtype=args.events_dtype,
-         hmc=args.hmc, moves=args.moves, thin=args.thin, summaries=args.summaries, diagnostics=args.diagnostics,
-         diagnostics_batch=args.diagnostics_batch, forecast=args.forecast, forecast_walk=args.forecast_walk, rt=args.rt,
-         **({} if args.check is None else dict(check=args.check)),
-         **({} if args.within_between is None else dict(within_between=args.within_between)),
-         **({} if args.forecast_quantiles is None else dict(forecast_quantiles=args.forecast_quantiles)),
-         **({} if args.rt_quantiles is None else dict(rt_quantiles=args.rt_quantiles)),
-         **({} if args.groups is None else dict(groups=G_mod.load_spec(args.groups))),
-         **({} if args.groups_rt is None else dict(groups_rt=True)),
-         **({} if args.groups_within_between is None else dict(groups_within_between=True)),
-         **({} if args.groups_ngm is None else dict(groups_ngm=True)))
+         hmc=args.hmc, moves=args.moves, thin=args.thin, **product_overrides(args, always))
 
 
 if __name__ == "__main__":

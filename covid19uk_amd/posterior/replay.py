@@ -201,8 +201,8 @@ def replay_bursts(sampler, sources, rows, burst, records, log=sys.stderr):
 
     t0 = time.perf_counter()
     waited = 0.0
-    for begin, _, _ in pr.records:
-        begin()
+    for record in pr.records:
+        record.begin()
     with ThreadPoolExecutor(max_workers=1) as pool:
         nxt = pool.submit(read, 0)
         for i in range(len(cuts)):
@@ -217,8 +217,8 @@ def replay_bursts(sampler, sources, rows, burst, records, log=sys.stderr):
             with io:
                 pr.flush(tr, i)
             print(f"  burst {i + 1}/{len(cuts)}", file=log, flush=True)
-    for _, _, finish in pr.records:
-        finish()
+    for record in pr.records:
+        record.finish()
     return len(rows), time.perf_counter() - t0, waited
 
 
@@ -236,7 +236,6 @@ def replay_files(data_file, files, output_file, config, seed=0, device=None, fir
     from ..sampler import ChainSampler
     from ..seir import SeirModel
     from .. import model_spec
-    from . import groups as G_mod
     cov, cases, dates = inf.read_inference_data(data_file)
     M, T = int(cases.shape[0]), int(cases.shape[1])
     sources, rows = open_sources(files, M, T, first, stop, every)        # refused here: before any GPU call
@@ -250,15 +249,7 @@ def replay_files(data_file, files, output_file, config, seed=0, device=None, fir
         if config.get("diagnostics") == "on" and n % ns:
             raise ValueError(f"diagnostics: {n} row(s) in bursts of {ns} -- the split R-hat compares half-chains of one length, "
                              "which takes whole bursts (choose --stop or --burst accordingly)")
-        group_table = None
-        if not G_mod.is_off(opt.group_spec):
-            group_table = G_mod.parse_groups(opt.group_spec, M, inf.read_location_names(data_file))
-        G_mod.require_curves(group_table, opt.grp_rt_on, opt.rt_days, opt.grp_wb_on, opt.wb_days)
-        G_mod.require_ngm(group_table, opt.grp_ngm_on, opt.rt_days, opt.grp_rt_on)
-        G_mod.require_source(group_table, config["summaries"], opt.horizon, opt.check_days, opt.grp_rt_on, opt.grp_wb_on)
-        for mode, days in ((inf.rt_mode, opt.rt_days), (inf.check_mode, opt.check_days), (inf.within_between_mode, opt.wb_days)):
-            if days:
-                mode(config, T=T)                                        # the window against the series
+        group_table = opt.bind(M, T, lambda: inf.read_location_names(data_file))   # the table, the windows against the series
         # the initial state the draws were recorded from: the files' own, else the imputation of `seed` as `mcmc` forms it
         states = [src.initial_state() for src in sources]
         if states[0] is not None:
@@ -313,8 +304,7 @@ def main(argv=None):
     from argparse import ArgumentParser
 
     import yaml
-    from ..inference.inference import DIAGNOSTICS, SUMMARIES
-    from . import groups as G_mod
+    from ..inference.options import add_product_arguments, product_overrides
     parser = ArgumentParser(description="Replay stored draws on the device: every product of the inference from posterior files")
     parser.add_argument("-c", "--config", type=str, required=True, help="Config file (its Mcmc section)")
     parser.add_argument("-o", "--output", type=str, required=True, help="Output file (one per input: _chain<id> is added)")
@@ -330,31 +320,13 @@ def main(argv=None):
     parser.add_argument("--device", type=int, default=None, help="HIP device (default 0)")
     parser.add_argument("--events-dtype", choices=["auto", "u16", "int32"], default="auto",
                         help="width of the event counts in the device-side burst buffer")
-    parser.add_argument("--summaries", choices=list(SUMMARIES), default=None)
-    parser.add_argument("--diagnostics", choices=list(DIAGNOSTICS), default=None)
-    parser.add_argument("--diagnostics-batch", type=int, default=None, metavar="L")
-    parser.add_argument("--forecast", type=int, default=None, metavar="H")
-    parser.add_argument("--forecast-walk", action="store_true", default=None)
-    parser.add_argument("--forecast-quantiles", type=str, default=None, metavar="P,P,...")
-    parser.add_argument("--rt", type=int, default=None, metavar="D")
-    parser.add_argument("--rt-quantiles", type=str, default=None, metavar="P,P,...", dest="rt_quantiles")
-    parser.add_argument("--check", type=int, default=None, metavar="K")
-    parser.add_argument("--within-between", type=int, default=None, metavar="D", dest="within_between")
-    parser.add_argument("--groups", type=str, default=None, metavar="SPEC")
-    parser.add_argument("--groups-rt", action="store_true", default=None, dest="groups_rt")
-    parser.add_argument("--groups-within-between", action="store_true", default=None, dest="groups_within_between")
-    parser.add_argument("--groups-ngm", action="store_true", default=None, dest="groups_ngm")
+    add_product_arguments(parser)
     args = parser.parse_args(argv)
     with open(args.config, "r") as f:
         config = yaml.load(f, Loader=yaml.FullLoader)
-    over = {k: getattr(args, k) for k in ("summaries", "diagnostics", "diagnostics_batch", "forecast", "forecast_walk", "rt", "check",
-                                          "forecast_quantiles", "within_between", "rt_quantiles") if getattr(args, k) is not None}
-    if args.groups is not None:
-        over["groups"] = G_mod.load_spec(args.groups)
-    over.update({k: True for k in ("groups_rt", "groups_within_between", "groups_ngm") if getattr(args, k)})
     replay_files(args.data_file, args.posteriors, args.output, config["Mcmc"], seed=args.seed, device=args.device, first=args.first,
                  stop=args.stop, every=args.every, burst=args.burst, first_chain_id=args.first_chain_id,
-                 events_dtype=args.events_dtype, **over)
+                 events_dtype=args.events_dtype, **product_overrides(args))
 
 
 if __name__ == "__main__":
