@@ -1155,6 +1155,19 @@ static int acc_shadow(Shadowed &a, int slot, bool save, hipStream_t st) {
     return 0;
 }
 static void acc_invalidate(Shadowed &a) { a.valid[0] = a.valid[1] = false; }
+// Accumulators with the host's count of the draws per chain folded into them since the product's reset: the counter travels
+// with the block, and a restore from a slot that holds nothing of the block leaves both alone.
+template <typename Acc>
+struct Counted : Acc {
+    long long j = 0, snap_j[2] = {0, 0};                 // the count; what it was when each slot's shadow was taken
+    void drop() { static_cast<Acc &>(*this) = Acc{}; }   // the block goes; j stays until the reset that follows
+};
+template <typename Acc>
+static int counted_shadow(Counted<Acc> &a, int slot, bool save, hipStream_t st) {
+    if (save) a.snap_j[slot] = a.j;
+    else if (a.valid[slot]) a.j = a.snap_j[slot];
+    return acc_shadow(a, slot, save, st);
+}
 // Blocking read of whichever parts are asked for, and of the sticky overflow flag.
 static int acc_read(const MomentAcc &a, hipStream_t st, uint64_t *count, int32_t *ref, int64_t *sum, uint64_t *sumsq, unsigned *flag) {
     MomentBufs mb{};
@@ -1174,12 +1187,11 @@ struct GroupOut {
     int L = 0;                        // day extent the arrays are sized for; 0: none (no table, or the source is off)
 };
 
-// One family of group curves (seir_sampler_group_rt: 1 plane, weighted; seir_sampler_group_wb: 2 planes): the switch, the
-// per-slot outputs out [cap][B][G][D] and the cell planes [slots * B][D][Mp] of a batch.  D = 0: no outputs (the switch is
-// off, there is no table, the product is off, or the outputs were refused) -- nothing is launched then.
+// One family of group curves (seir_sampler_group_rt: weighted; seir_sampler_group_wb), a plane per national curve of its
+// Window: the switch, the per-slot outputs out [cap][B][G][D] and the cell planes [slots * B][D][Mp] of a batch.  D = 0: no
+// outputs (the switch is off, there is no table, the product is off, or the outputs were refused) -- nothing is launched then.
 struct GroupCurve {
     bool on = false;
-    int planes = 1;
     DevBuf weights;                   // double [nnz] aligned with the members (group R_t), or empty
     struct Bufs {                     // what the table and the window size; Bufs{}: none, the switch and the weights stay
         int D = 0, slots = 0;         // window days the buffers are sized for; trace slots per batch
@@ -1199,6 +1211,23 @@ struct GroupNgm {
     DevBuf P, out;                    // double
 };
 
+// The users of a trace range that have to be enabled first, in the words their refusals use: what they do with the events; that
+// they are off; their name; what they have done to a draw; their reset, fold and draw-store entry points; their group curve off.
+struct TraceUser { const char *verb, *not_enabled, *name, *done, *reset, *call, *keep, *no_curve; };
+static const TraceUser SUMMARY_USER = {"summarise", "summaries are not enabled: call seir_sampler_summary_reset first"};
+static const TraceUser RT_USER = {"form the reproduction number from",
+                                   "the reproduction number is not enabled: call seir_sampler_rt_reset first", "rt", "folded",
+                                   "seir_sampler_rt_reset", "seir_sampler_rt", "seir_sampler_rt_keep",
+                                   "group R_t is not enabled: call seir_sampler_group_rt first"};
+static const TraceUser WB_USER = {"form the within/between pressure shares from",
+                                   "the within/between pressure shares are not enabled: call seir_sampler_wb_reset first",
+                                   nullptr, nullptr, nullptr, nullptr, nullptr,
+                                   "group within/between is not enabled: call seir_sampler_group_wb first"};
+static const TraceUser FORECAST_USER = {"forecast from", "the forecast is not enabled: call seir_sampler_forecast_reset first", "forecast",
+                                         "forecast", "seir_sampler_forecast_reset", "seir_sampler_forecast", "seir_sampler_forecast_keep"};
+static const TraceUser CHECK_USER = {"check", "the in-sample check is not enabled: call seir_sampler_check_reset first", "check",
+                                      "checked"};
+
 // The host's half of a ForecastBufs that is rolled forward day by day from the kept draws (forecast_kernels.h): the forecast
 // and the in-sample check each own one (rollout_*, below).
 struct Rollout {
@@ -1207,9 +1236,30 @@ struct Rollout {
     int slots = 0;                    // trace slots per batch: min(cap, FC_JMAX)
     int ndmax = 0;                    // row stride the planes are allocated for: ceil64(slots * B)
     std::vector<DevBuf> allocs;       // device buffers sized by fb.H (allocated again when it changes)
-    MomentAcc acc;                    // fb.mom's ref .. overflow
-    long long j = 0;                  // draws per chain rolled forward since the last reset (the j of the draw id)
-    long long snap_j[2] = {0, 0};     // j as it was when acc's shadows were taken
+    Counted<MomentAcc> acc;           // fb.mom's ref .. overflow; j: draws per chain rolled forward since the last reset (the draw id's j)
+};
+
+// The host's half of a product that folds a window of the last D days of the kept draws (rt_trace_kernels.h, wb_kernels.h):
+// the reproduction number and the within/between pressure shares each own one (window_*, below).  The device's half, the
+// kernel argument (RtBufs, WbBufs), stays with the product, as do its kernels and the layout of its block.
+struct Window {
+    const TraceUser &who;
+    const int planes;                 // national curves per draw, and planes of the group curve: 1 (R_t) or 2 (within, between)
+    bool on = false;                  // enabled by the user's first reset: buffers exist
+    int D = 0;                        // window days everything below is sized for
+    int slots = 0;                    // trace slots the batch planes are allocated for
+    std::vector<DevBuf> allocs;       // device buffers sized by the window (allocated again when it changes)
+    const double *draws[2] = {nullptr, nullptr};   // among them the national curves [cap][B][D] of every slot (Rt; Wn, Bn)
+    Counted<Shadowed> acc;            // the product's block; j: the host's copy of its count (every chain's: calls take them all)
+    GroupCurve curve;                 // the product's curves per group
+    Window(const TraceUser &u, int np) : who(u), planes(np) {}
+};
+
+// The draws of every cell that a product keeps for order statistics (seir_sampler_forecast_keep, seir_sampler_rt_keep), or
+// empty: off.  Position j of a cell's run is the chain's j-th draw since the product's reset, so a reset empties it.
+struct DrawStore {
+    DevBuf buf;                       // int [B][3][M][H][stride] (forecast), double [B][D][M][stride] (R_it)
+    long long cap = 0, stride = 0;    // draws per chain it holds; a cell's run: cap, for R_it rounded up to RT_KEEP_RUN (aligned runs)
 };
 
 struct seir_sampler {
@@ -1282,38 +1332,28 @@ struct seir_sampler {
     double *fc_steps_dev = nullptr;   // [fc.slots * B][H] (one of fc.allocs)
     hipEvent_t fc_ev_steps = nullptr; // behind the last upload from fc_steps_host
     bool fc_steps_pending = false;
-    DevBuf fc_keep;                   // the draw store int keep[B][3][M][H][fc_keep_cap] (seir_sampler_forecast_keep), or empty: off
-    long long fc_keep_cap = 0;        // draws per chain it holds; position j of a cell is the draw with the forecast's j
+    DrawStore keep_fc;                // int keep[B][3][M][H][cap]: position j of a cell is the draw with the forecast's j
     // --- in-sample check of the last K days (seir_sampler_check_reset ...; check_kernels.h): a Rollout with H := K ---
     Rollout ck;                       // its j is not the forecast's
     CheckCmp ck_cmp{};
     Shadowed ck_cnt;                  // ck_cmp's arrays, 32-bit words: lt | eq | obs [B M K] | loc_lt | loc_eq [B M] |
                                       //     day_lt | day_eq [B K] | all_lt | all_eq | moved [B]
     // --- reproduction number of the kept draws (seir_sampler_rt_reset ...; rt_trace_kernels.h) ---
-    bool rt_on = false;
-    RtBufs rt{};
-    int rt_slots = 0;                 // trace slots the batch planes (ea, S, part) are allocated for
-    std::vector<DevBuf> rt_allocs;    // device buffers sized by the window (allocated again when it changes)
-    Shadowed rt_acc;                  // sum [cells] | sumsq [cells] | ref [cells] | count [B, padded] | gt1 [cells]
-    DevBuf rt_keep;                   // the draw store double keepR[B][D][M][rt_keep_stride] (seir_sampler_rt_keep), or empty: off
-    long long rt_keep_cap = 0;        // draws per chain it holds; position j of a cell is the chain's j-th draw since the reset
-    long long rt_keep_stride = 0;     // cap rounded up to RT_KEEP_RUN: every run of a cell is aligned
-    long long rt_j = 0;               // the host's copy of RtBufs::count (the same for every chain: calls take all of them)
-    long long rt_snap_j[2] = {0, 0};  // rt_j as it was when rt_acc's shadows were taken
+    Window rt{RT_USER, 1};            // batch planes ea, S, part; block sum | sumsq | ref [cells] | count [B, padded] | gt1 [cells]
+    RtBufs rtb{};
+    // The R_it draw store double keepR[B][D][M][stride].  It has no shadow: count comes back with the accumulators, and the
+    // host's copy of it with them, so a burst run again overwrites its own positions of the store.
+    DrawStore keep_rt;
     // --- within/between pressure shares of the kept draws (seir_sampler_wb_reset ...; wb_kernels.h) ---
-    bool wb_on = false;
-    WbBufs wb{};
-    int wb_slots = 0;                 // trace slots the batch planes (I, part) are allocated for
-    std::vector<DevBuf> wb_allocs;    // device buffers sized by the window (allocated again when it changes)
-    Shadowed wb_acc;                  // sum_w | sumsq_w | ref_w | ref_b | sum_b [cells] | count [B, padded] | n [cells] | gt [cells]
+    Window wb{WB_USER, 2};            // batch planes I, part; block sum_w | sumsq_w | ref_w | ref_b | sum_b [cells] | count [B, padded] | n | gt [cells]
+    WbBufs wbb{};
     // --- region totals of the kept draws (seir_sampler_groups_set ...; group_kernels.h) ---
     bool grp_on = false;              // a table is set
     GroupTable grp{};                 // its device copy: segments and members, out of grp_seg and grp_members
     DevBuf grp_seg, grp_members;
     GroupOut grp_out[3];              // per-slot outputs of the trace, the forecast and the check (L = 0: that source is off)
-    // --- group curves: R_t and within / between per group (seir_sampler_group_rt / _group_wb; group_curve_kernels.h) ---
+    // --- group curves (seir_sampler_group_rt / _group_wb; group_curve_kernels.h): rt.curve (weighted) and wb.curve ---
     std::vector<int> grp_offsets;     // the table's offsets [G + 1] on the host (the device copy exists only with a curve on)
-    GroupCurve grt, gwb;              // group R_t (one plane, weighted); group within / between (two planes)
     // --- group next-generation matrix (seir_sampler_group_ngm; ngm_kernels.h) ---
     GroupNgm ngm;
     // --- stored draws into trace slots (seir_sampler_load_trace; trace_load_kernels.h): nothing of it exists before the first load ---
@@ -1337,21 +1377,14 @@ static int s_alloc(seir_sampler *s, std::vector<DevBuf> &list, T **p, size_t cou
 }
 #define S_ALLOC(list, ptr, ...) if (!rc) rc = s_alloc(s, s->list, &(ptr), __VA_ARGS__)
 
-// The moments with the draw counter: a restore from a slot that holds nothing of them leaves both alone.
-static int rollout_shadow(Rollout &r, int slot, bool save, hipStream_t st) {
-    if (save) r.snap_j[slot] = r.j;
-    else if (r.acc.valid[slot]) r.j = r.snap_j[slot];
-    return acc_shadow(r.acc, slot, save, st);
-}
-
-static int gcurve_fit(seir_sampler *s, bool rt);     // with the rest of the group curves, behind the within/between shares
+static int gcurve_fit(seir_sampler *s, Window &w);   // with the rest of the group curves, behind the within/between shares
 
 // No table: what was sized by it or weighted along its members goes with it -- the group next-generation matrix, group R_t
 // (switch and weights), the buffers of group within / between (its switch stays), the sources' outputs.
 static void groups_free(seir_sampler *s) {
     s->ngm = GroupNgm{};
-    s->grt = GroupCurve{};
-    s->gwb.b = {};
+    s->rt.curve = GroupCurve{};
+    s->wb.curve.b = {};
     s->grp_offsets.clear();
     for (GroupOut &o : s->grp_out) o = GroupOut{};
     s->grp_seg.reset(); s->grp_members.reset();
@@ -1679,19 +1712,13 @@ static int moments_shadow(seir_sampler *s, int slot, bool save) {
         if (s->diag_on) rc = acc_shadow(s->diag_buf, slot, save, st);
         if (!rc) rc = acc_shadow(s->sum_acc, slot, save, st);
     }
-    if (!rc && s->fc.on) rc = rollout_shadow(s->fc, slot, save, st);
-    if (!rc && s->rt_on) {
-        // count comes back with the accumulators, and the host's copy of it with them: a burst run again overwrites its own
-        // positions of the R_it draw store, which therefore has no shadow
-        if (save) s->rt_snap_j[slot] = s->rt_j;
-        else if (s->rt_acc.valid[slot]) s->rt_j = s->rt_snap_j[slot];
-        rc = acc_shadow(s->rt_acc, slot, save, st);
-    }
+    if (!rc && s->fc.on) rc = counted_shadow(s->fc.acc, slot, save, st);
+    if (!rc && s->rt.on) rc = counted_shadow(s->rt.acc, slot, save, st);
     if (!rc && s->ck.on) {
-        rc = rollout_shadow(s->ck, slot, save, st);
+        rc = counted_shadow(s->ck.acc, slot, save, st);
         if (!rc) rc = acc_shadow(s->ck_cnt, slot, save, st);
     }
-    if (!rc && s->wb_on) rc = acc_shadow(s->wb_acc, slot, save, st);
+    if (!rc && s->wb.on) rc = counted_shadow(s->wb.acc, slot, save, st);
     return rc;
 }
 
@@ -1747,22 +1774,22 @@ extern "C" int seir_sampler_product_state(seir_sampler *s, seir_product_state *o
     p.diag_batch_len = s->diag_on ? (int32_t)s->diag.L : 0;
     p.forecast_H = s->fc.on ? s->fc.fb.H : 0;
     p.check_K = s->ck.on ? s->ck.fb.H : 0;
-    p.rt_D = s->rt_on ? s->rt.D : 0;
-    p.wb_D = s->wb_on ? s->wb.D : 0;
+    p.rt_D = s->rt.on ? s->rt.D : 0;
+    p.wb_D = s->wb.on ? s->wb.D : 0;
     p.groups_G = s->grp_on ? s->grp.G : 0;
     p.groups_nnz = s->grp_on && !s->grp_offsets.empty() ? s->grp_offsets.back() : 0;
     for (int which = 0; which < 3; ++which) p.group_L[which] = s->grp_out[which].L;
-    p.group_rt_on = s->grt.on;
-    p.group_wb_on = s->gwb.on;
-    p.group_rt_D = s->grt.b.D;
-    p.group_wb_D = s->gwb.b.D;
+    p.group_rt_on = s->rt.curve.on;
+    p.group_wb_on = s->wb.curve.on;
+    p.group_rt_D = s->rt.curve.b.D;
+    p.group_wb_D = s->wb.curve.b.D;
     p.ngm_D = s->ngm.D;
-    p.fc_j = s->fc.j;
-    p.ck_j = s->ck.j;
-    p.rt_j = s->rt_j;
+    p.fc_j = s->fc.acc.j;
+    p.ck_j = s->ck.acc.j;
+    p.rt_j = s->rt.acc.j;
     p.ngm_cap = s->ngm.cap;
-    p.fc_keep_cap = s->fc_keep_cap;
-    p.rt_keep_cap = s->rt_keep_cap;
+    p.fc_keep_cap = s->keep_fc.cap;
+    p.rt_keep_cap = s->keep_rt.cap;
     *out = p;
     return 0;
 }
@@ -2316,10 +2343,14 @@ static int on_copy_stream(seir_sampler *s, F fn) {
     return 0;
 }
 
-static int read_trace_check(seir_sampler *s, int32_t first, int32_t count, const void *events) {
-    if (first < 0 || count < 0 || first + count > s->cfg.cap)
-        return fail(SEIR_ERR_INVALID, "trace range [%d,%d) outside capacity %d", first, first + count, s->cfg.cap);
-    return events ? need_events(s, nullptr) : 0;
+// The tail of every read that has an _async form; copy(stream) enqueues the device-to-host copies.  Blocking: on the context
+// stream, waited for, then the draws' own refusals (check_ev_overflow).  async: on the copy stream, as above.
+template <typename F>
+static int deliver(seir_sampler *s, bool async, F copy) {
+    if (async) return on_copy_stream(s, copy);
+    if (int rc = copy(s->ctx->stream)) return rc;
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    return check_ev_overflow(s);
 }
 
 static int copy_trace(seir_sampler *s, hipStream_t st, int32_t first, int32_t count, double *theta, void *events, double *hmc,
@@ -2342,22 +2373,23 @@ static int copy_trace(seir_sampler *s, hipStream_t st, int32_t first, int32_t co
     return 0;
 }
 
-extern "C" int seir_sampler_read_trace(seir_sampler *s, int32_t first, int32_t count, double *theta,
-                                       void *events, double *hmc, double *moves) {
+static int read_trace(seir_sampler *s, bool async, int32_t first, int32_t count, double *theta, void *events, double *hmc,
+                      double *moves) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    if ((rc = read_trace_check(s, first, count, events))) return rc;
-    if ((rc = copy_trace(s, s->ctx->stream, first, count, theta, events, hmc, moves))) return rc;
-    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
-    return check_ev_overflow(s);
+    if (first < 0 || count < 0 || first + count > s->cfg.cap)
+        return fail(SEIR_ERR_INVALID, "trace range [%d,%d) outside capacity %d", first, first + count, s->cfg.cap);
+    if (events && (rc = need_events(s, nullptr))) return rc;
+    return deliver(s, async, [&](hipStream_t st) { return copy_trace(s, st, first, count, theta, events, hmc, moves); });
 }
 
+extern "C" int seir_sampler_read_trace(seir_sampler *s, int32_t first, int32_t count, double *theta,
+                                       void *events, double *hmc, double *moves) {
+    return read_trace(s, false, first, count, theta, events, hmc, moves);
+}
 extern "C" int seir_sampler_read_trace_async(seir_sampler *s, int32_t first, int32_t count, double *theta,
                                              void *events, double *hmc, double *moves) {
-    int rc = sampler_check(s);
-    if (rc) return rc;
-    if ((rc = read_trace_check(s, first, count, events))) return rc;
-    return on_copy_stream(s, [&](hipStream_t st) { return copy_trace(s, st, first, count, theta, events, hmc, moves); });
+    return read_trace(s, true, first, count, theta, events, hmc, moves);
 }
 
 extern "C" int seir_sampler_trace_wait(seir_sampler *s) {
@@ -2374,19 +2406,7 @@ extern "C" int seir_sampler_trace_wait(seir_sampler *s) {
 // ---------------------------------------------------------------------------
 // Summaries of the recorded events (include/seir_hip.h; kernels: summary_kernels.h)
 // ---------------------------------------------------------------------------
-// The users of a trace range that have to be enabled first: what they do with the recorded events, and their refusal.
-// The two that roll the model forward (Rollout) also word the refusals they share: their name, and what they have done to a draw.
-struct TraceUser { const char *verb, *not_enabled, *name, *done; };
-static const TraceUser SUMMARY_USER = {"summarise", "summaries are not enabled: call seir_sampler_summary_reset first"};
-static const TraceUser RT_USER = {"form the reproduction number from",
-                                   "the reproduction number is not enabled: call seir_sampler_rt_reset first"};
-static const TraceUser WB_USER = {"form the within/between pressure shares from",
-                                   "the within/between pressure shares are not enabled: call seir_sampler_wb_reset first"};
-static const TraceUser FORECAST_USER = {"forecast from", "the forecast is not enabled: call seir_sampler_forecast_reset first",
-                                         "forecast", "forecast"};
-static const TraceUser CHECK_USER = {"check", "the in-sample check is not enabled: call seir_sampler_check_reset first", "check",
-                                      "checked"};
-
+// What every user of a trace range (TraceUser) refuses first.
 static int trace_range_check(seir_sampler *s, bool enabled, const TraceUser &what, int32_t first = 0, int32_t count = 0) {
     if (int rc = need_events(s, what.verb)) return rc;
     if (!enabled) return fail(SEIR_ERR_STATE, "%s", what.not_enabled);
@@ -2409,13 +2429,9 @@ static int copy_marginals(seir_sampler *s, hipStream_t st, int32_t first, int32_
 static int read_marginals(seir_sampler *s, bool enabled, const TraceUser &what, const MomentBufs &m, int day_extent, bool async,
                           int32_t first, int32_t count, int64_t *by_day, int64_t *by_loc, int64_t *state_by_day) {
     if (int rc = trace_range_check(s, enabled, what, first, count)) return rc;
-    if (async)   // as seir_sampler_read_trace_async
-        return on_copy_stream(s, [&](hipStream_t st) {
-            return copy_marginals(s, st, first, count, m, (size_t)day_extent, by_day, by_loc, state_by_day);
-        });
-    if (int rc = copy_marginals(s, s->ctx->stream, first, count, m, (size_t)day_extent, by_day, by_loc, state_by_day)) return rc;
-    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
-    return check_ev_overflow(s);
+    return deliver(s, async, [&](hipStream_t st) {
+        return copy_marginals(s, st, first, count, m, (size_t)day_extent, by_day, by_loc, state_by_day);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -2507,7 +2523,7 @@ extern "C" int seir_sampler_groups_set(seir_sampler *s, int32_t G, const int32_t
     if (G == 0) {
         if ((rc = drain(s))) return rc;
         groups_free(s);
-        s->gwb.on = false;
+        s->wb.curve.on = false;
         return 0;
     }
     if ((rc = need_events(s, "sum over groups of locations"))) return rc;
@@ -2533,7 +2549,7 @@ extern "C" int seir_sampler_groups_set(seir_sampler *s, int32_t G, const int32_t
         if ((rc = groups_fit(s, which))) { groups_free(s); return rc; }
     s->grp_offsets.assign(offsets, offsets + G + 1);
     // group R_t went off with the old table's weights (groups_free); group within / between has none and is sized again
-    return s->gwb.on ? gcurve_fit(s, false) : 0;
+    return s->wb.curve.on ? gcurve_fit(s, s->wb) : 0;
 }
 
 static int copy_group_marginals(seir_sampler *s, hipStream_t st, int which, int32_t first, int32_t count, int64_t *ev, int64_t *st0) {
@@ -2556,10 +2572,7 @@ static int read_group_marginals(seir_sampler *s, bool async, int32_t which, int3
         return fail(SEIR_ERR_INVALID, "trace range [%d,%lld) outside capacity %d", first, (long long)first + count, s->cfg.cap);
     if (which == 0 && st0)
         return fail(SEIR_ERR_INVALID, "the trace has no per-draw state0: it is the context's initial state summed over the members");
-    if (async) return on_copy_stream(s, [&](hipStream_t st) { return copy_group_marginals(s, st, which, first, count, ev, st0); });
-    if (int rc = copy_group_marginals(s, s->ctx->stream, which, first, count, ev, st0)) return rc;
-    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
-    return check_ev_overflow(s);
+    return deliver(s, async, [&](hipStream_t st) { return copy_group_marginals(s, st, which, first, count, ev, st0); });
 }
 
 extern "C" int seir_sampler_read_group_marginals(seir_sampler *s, int32_t which, int32_t first, int32_t count,
@@ -2800,7 +2813,7 @@ static int rollout_refuse(const seir_sampler *s, const TraceUser &who, const dou
 static int rollout_resize(seir_sampler *s, Rollout &r, int H) {
     int rc = drain(s);
     if (rc) return rc;
-    r.allocs.clear(); r.acc = MomentAcc{}; r.fb = ForecastBufs{};   // everything sized by H; j stays until the reset that follows
+    r.allocs.clear(); r.acc.drop(); r.fb = ForecastBufs{};       // everything sized by H; j stays until the reset that follows
     r.on = false;
     const Dims &d = s->ctx->d;
     const size_t B = (size_t)s->cfg.B, cap = (size_t)s->cfg.cap;
@@ -2836,7 +2849,7 @@ static int rollout_begin(seir_sampler *s, Rollout &r, const double *W, const dou
     HIP_TRY(hipMemcpyAsync(const_cast<double *>(fb.wd), weekday_c, sizeof(double) * fb.H, hipMemcpyHostToDevice, st));
     if (int rc = acc_zero(r.acc, st)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
-    r.j = 0;
+    r.acc.j = 0;
     // what the snapshots taken before this reset hold of the moments is dropped with them: restoring one of them restores
     // the chain and leaves the accumulators and j as they are
     acc_invalidate(r.acc);
@@ -2844,10 +2857,17 @@ static int rollout_begin(seir_sampler *s, Rollout &r, const double *W, const dou
 }
 
 static int rollout_ids_left(const Rollout &r, const TraceUser &who, int32_t count) {
-    if (r.j + count > (1ll << FC_ID_SHIFT))
-        return fail(SEIR_ERR_INVALID, "%lld draws per chain %s since the reset and %d more: the draw id holds 2^%d", r.j, who.done,
+    if (r.acc.j + count > (1ll << FC_ID_SHIFT))
+        return fail(SEIR_ERR_INVALID, "%lld draws per chain %s since the reset and %d more: the draw id holds 2^%d", r.acc.j, who.done,
                     count, FC_ID_SHIFT);
     return 0;
+}
+
+// Before a fold of `count` more draws behind the j since the reset: a store of `cap` per chain (entry point `sized_by`) holds them.
+static int store_holds(const TraceUser &who, long long j, int32_t count, long long cap, const char *sized_by) {
+    if (j + count <= cap) return 0;
+    return fail(SEIR_ERR_INVALID, "%lld draws per chain %s since the reset and %d more: the draw store holds %lld (%s)", j, who.done,
+                count, cap, sized_by);
 }
 
 // Trace slots [first + j0, first + j0 + nj) of a call: ND = nj * B draws, the planes' row stride ndp = ceil64(ND).
@@ -2864,7 +2884,7 @@ static void groups_rollout_batch(seir_sampler *s, int which, const Dims &d, hipS
 // The draws of trace slots [first, first + count) rolled forward fb.H days, in batches of at most r.slots slots.  Per batch:
 // prepare(fb, batch) -- the user's prepare kernel on the batch's copy of r.fb, which it may amend first -- then per day the
 // contraction and k_forecast_day, then k_forecast_fold, then after_fold(fb, batch).  The draw of slot first + jj has
-// j = r.j + jj; adding count to r.j is left to the caller, behind whatever else it enqueues.
+// j = r.acc.j + jj; adding count to r.acc.j is left to the caller, behind whatever else it enqueues.
 template <typename Prepare, typename AfterFold>
 static int rollout_days(seir_sampler *s, const Rollout &r, int32_t first, int32_t count, Prepare prepare, AfterFold after_fold) {
     seir_ctx *ctx = s->ctx;
@@ -2887,7 +2907,7 @@ static int rollout_days(seir_sampler *s, const Rollout &r, int32_t first, int32_
             hipLaunchKernelGGL((k_gemm<64>), dim3(ndp / 64, d.Mp / GEMM_TM, 1), dim3(gemm_threads<64>()), gemm_lds_bytes<64>(),
                                l.st, gd, ctx->c, gw);
             hipLaunchKernelGGL(k_forecast_day, dim3(ndp / 64, (d.M + FC_DAY_ROWS - 1) / FC_DAY_ROWS), dim3(64 * FC_DAY_ROWS), 0,
-                               l.st, d, ctx->c, fb, B, s->cfg.chain0, (int)(r.j + j0), ND, ndp, h);
+                               l.st, d, ctx->c, fb, B, s->cfg.chain0, (int)(r.acc.j + j0), ND, ndp, h);
         }
         hipLaunchKernelGGL(k_forecast_fold, dim3((d.M + FC_ROWS - 1) / FC_ROWS, B), dim3(64 * FC_ROWS), 0, l.st, d, fb, B,
                            first + j0, nj, ndp);
@@ -2909,7 +2929,7 @@ extern "C" int seir_sampler_forecast_reset(seir_sampler *s, int32_t horizon, con
         if ((rc = rollout_resize(s, r, horizon))) return rc;
         // the steps' buffers and the draw store are sized by H as well; the stream is idle
         s->fc_steps_host.reset();
-        s->fc_keep.reset(); s->fc_keep_cap = 0;
+        s->keep_fc = DrawStore{};
         S_ALLOC(fc.allocs, s->fc_steps_dev, (size_t)r.slots * s->cfg.B * horizon);
         if (rc) return rc;
         if (!s->fc_ev_steps) HIP_TRY(hipEventCreate(&s->fc_ev_steps));
@@ -2926,9 +2946,8 @@ extern "C" int seir_sampler_forecast(seir_sampler *s, int32_t first, int32_t cou
     if ((rc = trace_range_check(s, r.on, FORECAST_USER, first, count))) return rc;
     if (count == 0) return 0;
     if ((rc = rollout_ids_left(r, FORECAST_USER, count))) return rc;
-    if (s->fc_keep && r.j + count > s->fc_keep_cap)
-        return fail(SEIR_ERR_INVALID, "%lld draws per chain forecast since the reset and %d more: the draw store holds %lld "
-                    "(seir_sampler_forecast_keep)", r.j, count, s->fc_keep_cap);
+    const DrawStore &keep = s->keep_fc;
+    if (keep.buf && (rc = store_holds(FORECAST_USER, r.acc.j, count, keep.cap, FORECAST_USER.keep))) return rc;
     seir_ctx *ctx = s->ctx;
     const LaunchCfg l = whole(ctx, s->cfg.B);
     const Dims &d = l.d;
@@ -2954,17 +2973,17 @@ extern "C" int seir_sampler_forecast(seir_sampler *s, int32_t first, int32_t cou
             return 0;
         },
         [&](const ForecastBufs &fb, const RolloutBatch &bt) {
-            if (s->fc_keep)
+            if (keep.buf)
                 hipLaunchKernelGGL(k_forecast_keep, dim3((d.M + KEEP_ROWS - 1) / KEEP_ROWS, B), dim3(64 * KEEP_ROWS), 0, l.st, d,
-                                   (const int *)fb.fev, (const int *)(fb.St0 + 2 * (size_t)d.Mp * bt.ndp), s->fc_keep.as<int>(),
-                                   s->fc_keep_cap, r.j + bt.j0, H, B, bt.nj, bt.ndp);
+                                   (const int *)fb.fev, (const int *)(fb.St0 + 2 * (size_t)d.Mp * bt.ndp), keep.buf.as<int>(),
+                                   keep.stride, r.acc.j + bt.j0, H, B, bt.nj, bt.ndp);
             hipLaunchKernelGGL(k_forecast_finish, dim3(bt.nj, B), dim3(64), 0, l.st, d, fb, B, first + bt.j0, bt.nj, bt.ndp);
             if (groups_live(s, 1)) groups_rollout_batch(s, 1, d, l.st, fb, first, bt);
         });
     if (rc) return rc;
     if (log_baseline_steps) { HIP_TRY(hipEventRecord(s->fc_ev_steps, l.st)); s->fc_steps_pending = true; }
     HIP_TRY(hipGetLastError());
-    r.j += count;
+    r.acc.j += count;
     return 0;
 }
 
@@ -2993,25 +3012,25 @@ extern "C" int seir_sampler_read_forecast(seir_sampler *s, uint64_t *count, int3
 // ---------------------------------------------------------------------------
 // A draw store (the forecast's keep, the R_it store keepR) is sized between its product's reset and the first draws: the
 // one resize behind seir_sampler_forecast_keep / seir_sampler_rt_keep.  cap == 0 frees it.  Otherwise a resize is refused
-// once j draws per chain have been taken since the reset (`verb`; `reset` and `call` name the two entry points), a store
-// that already has the capacity stays (the reset has emptied it), and a new one of `bytes` (`shape` spells the product
-// out for the refusal) may take half of what is free on the device; it is zeroed.
-static int keep_resize(seir_sampler *s, DevBuf &store, long long &store_cap, int64_t cap, long long j, unsigned long long bytes,
-                       const char *verb, const char *reset, const char *call, const char *shape) {
+// once j draws per chain have been taken since the reset (in the words of `who`), a store that already has the capacity
+// stays (the reset has emptied it), and a new one of `bytes` (`shape` spells the product out for the refusal) may take half
+// of what is free on the device; it is zeroed, and its stride is its cap until the caller says otherwise.
+static int keep_resize(seir_sampler *s, DrawStore &store, const TraceUser &who, int64_t cap, long long j, unsigned long long bytes,
+                       const char *shape) {
     if (cap != 0) {
         if (j != 0)
             return fail(SEIR_ERR_STATE, "%lld draws per chain have been %s since the reset: the draw store is sized between "
-                        "%s and the first %s", j, verb, reset, call);
-        if (store && store_cap == cap) return 0;
+                        "%s and the first %s", j, who.done, who.reset, who.call);
+        if (store.buf && store.cap == cap) return 0;
     }
-    if (store) {
+    if (store.buf) {
         HIP_TRY(hipStreamSynchronize(s->ctx->stream));
-        store.reset(); store_cap = 0;
+        store = DrawStore{};
     }
     if (cap == 0) return 0;
     if (int rc = refuse_above_half_free(bytes, "the draw store needs %llu bytes (%s)", bytes, shape)) return rc;
-    if (int rc = store.zeroed((size_t)bytes)) return rc;
-    store_cap = cap;
+    if (int rc = store.buf.zeroed((size_t)bytes)) return rc;
+    store.cap = store.stride = cap;
     return 0;
 }
 
@@ -3025,8 +3044,7 @@ extern "C" int seir_sampler_forecast_keep(seir_sampler *s, int64_t cap) {
     char shape[160];
     snprintf(shape, sizeof shape, "%d chains x 3 x %d locations x %d days x %lld draws x 4", s->cfg.B, s->ctx->d.M, s->fc.fb.H,
              (long long)cap);
-    return keep_resize(s, s->fc_keep, s->fc_keep_cap, cap, s->fc.j, cells * (unsigned long long)cap * 4ull, "forecast",
-                       "seir_sampler_forecast_reset", "seir_sampler_forecast", shape);
+    return keep_resize(s, s->keep_fc, FORECAST_USER, cap, s->fc.acc.j, cells * (unsigned long long)cap * 4ull, shape);
 }
 
 // ranks [R] strictly increasing in [0, n): into the launch's arguments, or the refusal.
@@ -3061,15 +3079,13 @@ static void order_launch(const OrderStatsArgs<V> &a, hipStream_t st) {
 }
 
 // Order statistics of a draw store [B][plane][stride] holding j draws per chain, behind seir_sampler_forecast_order_stats
-// and seir_sampler_rt_order_stats: every chain's count (count_dev [B], the product's own) must be j; out [R][cells].
-// `keep_call`, `what` and `verb` are the product's words in the refusals.
+// and seir_sampler_rt_order_stats, refusing in the words of `who`: every chain's count (count_dev [B]) must be j; out [R][cells].
 template <typename V>
-static int keep_order_stats(seir_sampler *s, const V *store, long long j, const uint64_t *count_dev, long long plane,
-                            long long stride, const int64_t *ranks, int32_t R, int32_t pooled, V *out, const char *keep_call,
-                            const char *what, const char *verb) {
-    if (!store) return fail(SEIR_ERR_STATE, "the draw store is not enabled: call %s first", keep_call);
+static int keep_order_stats(seir_sampler *s, const DrawStore &store, const TraceUser &who, long long j, const uint64_t *count_dev,
+                            long long plane, const int64_t *ranks, int32_t R, int32_t pooled, V *out) {
+    if (!store.buf) return fail(SEIR_ERR_STATE, "the draw store is not enabled: call %s first", who.keep);
     if (!out) return fail(SEIR_ERR_INVALID, "null output pointer");
-    if (j < 1) return fail(SEIR_ERR_STATE, "no draws kept since the %s reset", what);
+    if (j < 1) return fail(SEIR_ERR_STATE, "no draws kept since the %s reset", who.name);
     const int B = s->cfg.B;
     hipStream_t st = s->ctx->stream;
     std::vector<uint64_t> cnt((size_t)B);
@@ -3078,16 +3094,16 @@ static int keep_order_stats(seir_sampler *s, const V *store, long long j, const 
     for (int b = 0; b < B; ++b)
         if ((long long)cnt[b] != j)
             return fail(SEIR_ERR_STATE, "chain %d has %llu draws %s, the store %lld: the chains' counts differ", b,
-                        (unsigned long long)cnt[b], verb, j);
+                        (unsigned long long)cnt[b], who.done, j);
     int rc;
     OrderStatsArgs<V> a{};
     if ((rc = order_ranks(ranks, R, pooled ? j * B : j, a))) return rc;
-    a.values = store;
+    a.values = store.buf.as<const V>();
     a.cells = pooled ? plane : plane * B;
     a.segs = pooled ? B : 1;
     a.seg_len = j;
-    a.seg_stride = plane * stride;
-    a.cell_stride = stride;
+    a.seg_stride = plane * store.stride;
+    a.cell_stride = store.stride;
     DevBuf dout;
     const size_t nout = (size_t)R * (size_t)a.cells;
     if ((rc = dout.alloc(sizeof(V) * nout))) return rc;
@@ -3103,8 +3119,8 @@ extern "C" int seir_sampler_forecast_order_stats(seir_sampler *s, const int64_t 
     int rc = sampler_check(s);
     if (rc) return rc;
     if ((rc = trace_range_check(s, s->fc.on, FORECAST_USER))) return rc;
-    return keep_order_stats<int32_t>(s, s->fc_keep.as<const int32_t>(), s->fc.j, s->fc.fb.mom.count, 3ll * s->ctx->d.M * s->fc.fb.H, s->fc_keep_cap, ranks,
-                                     R, pooled, out, "seir_sampler_forecast_keep", "forecast", "forecast");
+    return keep_order_stats<int32_t>(s, s->keep_fc, FORECAST_USER, s->fc.acc.j, s->fc.fb.mom.count, 3ll * s->ctx->d.M * s->fc.fb.H,
+                                     ranks, R, pooled, out);
 }
 
 // The stateless select behind seir_order_stats / seir_order_stats_f64: values up, out [R][cells] back.
@@ -3210,7 +3226,7 @@ extern "C" int seir_sampler_check(seir_sampler *s, int32_t first, int32_t count)
             return 0;
         },
         [&](const ForecastBufs &fb, const RolloutBatch &bt) {
-            const int fresh = r.j + bt.j0 == 0;
+            const int fresh = r.acc.j + bt.j0 == 0;
             hipLaunchKernelGGL(k_forecast_finish, dim3(bt.nj, B), dim3(64), 0, l.st, d, fb, B, first + bt.j0, bt.nj, bt.ndp);
             hipLaunchKernelGGL(s->cfg.ev16 ? k_check_compare<1> : k_check_compare<0>, rgrid, rblock, 0, l.st, d, fb, s->ck_cmp,
                                (const void *)s->ch.tr_events, B, first + bt.j0, bt.nj, fresh);
@@ -3219,7 +3235,7 @@ extern "C" int seir_sampler_check(seir_sampler *s, int32_t first, int32_t count)
         });
     if (rc) return rc;
     HIP_TRY(hipGetLastError());
-    r.j += count;
+    r.acc.j += count;
     return 0;
 }
 
@@ -3276,94 +3292,112 @@ extern "C" int seir_sampler_read_check_counts(seir_sampler *s, int32_t *obs, uin
 static void gcurve_rt_trace_cells(seir_sampler *s, const LaunchCfg &l, int slot0, int nj);
 static void gcurve_rt_gather(seir_sampler *s, const LaunchCfg &l, long long pos0, int nj);
 static void gcurve_wb_trace_cells(seir_sampler *s, const LaunchCfg &l, int slot0, int nj);
-static void gcurve_sums(seir_sampler *s, const LaunchCfg &l, const GroupCurve &c, int D, int slot0, int nj);
+static void gcurve_sums(seir_sampler *s, const LaunchCfg &l, const Window &w, int slot0, int nj);
 static void gcurve_lds_attributes(int Mp);
 // The launches of the group next-generation matrix (likewise at the end of this file, where ngm_kernels.h is included): the
 // batch's slots [slot0, slot0 + nj) into the store's positions [pos0, pos0 + nj).
 static void ngm_launch(seir_sampler *s, const LaunchCfg &l, int slot0, long long pos0, int nj);
 
-// need_events' refusal as SEIR_ERR_INVALID (a sampler without recorded events is a bad argument to this feature), then
-// trace_range_check's
-static int rt_check(seir_sampler *s, int32_t first = 0, int32_t count = 0) {
-    if (need_events(s, RT_USER.verb)) return SEIR_ERR_INVALID;
-    return trace_range_check(s, s->rt_on, RT_USER, first, count);
+// One Window behind the reproduction number and the within/between shares: what the two resets and every entry point's
+// first refusals have in common.  Where the products differ (R_t's weights, draw store and group next-generation matrix; the
+// planes and the layout of the block; the kernels) the entry points do it.  The first refusals: need_events' as
+// SEIR_ERR_INVALID (a sampler without recorded events is a bad argument to this feature), then trace_range_check's
+static int window_check(seir_sampler *s, const Window &w, int32_t first = 0, int32_t count = 0) {
+    if (need_events(s, w.who.verb)) return SEIR_ERR_INVALID;
+    return trace_range_check(s, w.on, w.who, first, count);
 }
-static size_t rt_cells(const seir_sampler *s) { return (size_t)s->cfg.B * s->rt.D * s->ctx->d.M; }
-static size_t rt_count_words(const seir_sampler *s) { return ((size_t)s->cfg.B + 31) / 32 * 32; }
+static size_t window_cells(const seir_sampler *s, const Window &w) { return (size_t)s->cfg.B * w.D * s->ctx->d.M; }
+static size_t count_words(const seir_sampler *s) { return ((size_t)s->cfg.B + 31) / 32 * 32; }
+
+// First reset, or another window: everything is sized by D.  The integer plane of a batch (R_t's S, the shares' I) is bounded,
+// so a call is cut into batches of at most w.slots slots.  The caller then allocates its planes, lays out its block, sets w.on.
+static int window_resize(seir_sampler *s, Window &w, int D) {
+    if (int rc = drain(s)) return rc;
+    w.allocs.clear(); w.acc.drop();                  // j stays until the reset that follows
+    w.draws[0] = w.draws[1] = nullptr;
+    w.on = false; w.D = D;
+    w.slots = staging_slots(s->ctx, s->cfg.cap, (size_t)s->cfg.B * s->ctx->d.Mp * D * sizeof(int));
+    return 0;
+}
+
+// Begin again: the block and j from zero, then the group curve sized for the window.  also(stream) enqueues what else of the
+// product starts from zero, behind the block.  Synchronises the stream, so what the caller has queued before is done as well.
+template <typename Also>
+static int window_begin(seir_sampler *s, Window &w, Also also) {
+    hipStream_t st = s->ctx->stream;
+    if (int rc = acc_zero(w.acc, st)) return rc;
+    if (int rc = also(st)) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    w.acc.j = 0;
+    acc_invalidate(w.acc);                           // restoring a snapshot from before this reset leaves the accumulators alone
+    return w.curve.on ? gcurve_fit(s, w) : 0;
+}
 
 extern "C" int seir_sampler_rt_reset(seir_sampler *s, int32_t days, const double *weight) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    if (need_events(s, RT_USER.verb)) return SEIR_ERR_INVALID;
+    Window &w = s->rt;
+    if (need_events(s, w.who.verb)) return SEIR_ERR_INVALID;
     const Dims &d = s->ctx->d;
     if (days < 1 || days > d.T) return fail(SEIR_ERR_INVALID, "days=%d outside [1, T = %d]", days, d.T);
     if (!weight) return fail(SEIR_ERR_INVALID, "null weight pointer");
     const int B = s->cfg.B, D = days;
-    hipStream_t st = s->ctx->stream;
-    RtBufs &rb = s->rt;
-    if (!s->rt_on || rb.D != D) {
-        // first reset, or another window: everything is sized by D
-        if ((rc = drain(s))) return rc;
-        s->rt_allocs.clear();
-        s->rt_acc = Shadowed{};
-        s->rt_keep.reset(); s->rt_keep_cap = s->rt_keep_stride = 0;   // sized by D
+    RtBufs &rb = s->rtb;
+    if (!w.on || w.D != D) {
+        if ((rc = window_resize(s, w, D))) return rc;
+        s->keep_rt = DrawStore{};                    // sized by D
         s->ngm = GroupNgm{};                         // sized by D too
-        s->rt_on = false;
         rb = RtBufs{};
         rb.D = D; rb.t0 = d.T - D; rb.ncb = (d.M + 63) / 64;
-        // the S plane of a batch is bounded: a call is cut into batches of at most rt_slots trace slots
-        s->rt_slots = staging_slots(s->ctx, s->cfg.cap, (size_t)B * d.Mp * D * sizeof(int));
-        const size_t nd = (size_t)s->rt_slots * B;
+        const size_t nd = (size_t)w.slots * B;
         double *wd = nullptr;
-        S_ALLOC(rt_allocs, wd, (size_t)rb.ncb * 64);
-        S_ALLOC(rt_allocs, rb.ea, nd * d.Tp); S_ALLOC(rt_allocs, rb.S, nd * d.Mp * D);
-        S_ALLOC(rt_allocs, rb.part, nd * D * rb.ncb); S_ALLOC(rt_allocs, rb.Rt, (size_t)s->cfg.cap * B * D);
+        S_ALLOC(rt.allocs, wd, (size_t)rb.ncb * 64);
+        S_ALLOC(rt.allocs, rb.ea, nd * d.Tp); S_ALLOC(rt.allocs, rb.S, nd * d.Mp * D);
+        S_ALLOC(rt.allocs, rb.part, nd * D * rb.ncb); S_ALLOC(rt.allocs, rb.Rt, (size_t)s->cfg.cap * B * D);
         rb.weight = wd;
-        const size_t cells = (size_t)B * D * d.M;
-        if (!rc) rc = s->rt_acc.buf.zeroed(cells * (3 * sizeof(double) + sizeof(uint32_t)) + rt_count_words(s) * sizeof(uint64_t));
+        w.draws[0] = rb.Rt;
+        const size_t cells = window_cells(s, w);
+        if (!rc) rc = w.acc.buf.zeroed(cells * (3 * sizeof(double) + sizeof(uint32_t)) + count_words(s) * sizeof(uint64_t));
         if (rc) return rc;
-        rb.sum = s->rt_acc.buf.as<double>();
+        rb.sum = w.acc.buf.as<double>();
         rb.sumsq = rb.sum + cells;
         rb.ref = rb.sumsq + cells;
         rb.count = (uint64_t *)(rb.ref + cells);
-        rb.gt1 = (uint32_t *)(rb.count + rt_count_words(s));
+        rb.gt1 = (uint32_t *)(rb.count + count_words(s));
         (void)lds_attribute((const void *)k_rt_trace<RT_DT>, k_rt_trace_lds_bytes<RT_DT>(d.Mp));
-        s->rt_on = true;
+        w.on = true;
     }
     // the caller's array is not retained: a blocking copy behind what is queued (a reset is not on the hot path)
-    HIP_TRY(hipMemcpyAsync(const_cast<double *>(rb.weight), weight, sizeof(double) * d.M, hipMemcpyHostToDevice, st));
-    if ((rc = acc_zero(s->rt_acc, st))) return rc;
-    if (s->rt_keep) HIP_TRY(hipMemsetAsync(s->rt_keep.p, 0, sizeof(double) * rt_cells(s) * (size_t)s->rt_keep_stride, st));
-    if (s->ngm.cap)                                  // the group next-generation matrix holds draws [0, count) too
-        HIP_TRY(hipMemsetAsync(s->ngm.out.p, 0, sizeof(double) * (size_t)s->ngm.cap * B * s->grp.G * s->grp.G * D, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    s->rt_j = 0;                                     // empties the draw store too: it holds draws [0, count)
-    // what the snapshots taken before this reset hold of it is dropped: restoring one of them leaves the accumulators alone
-    acc_invalidate(s->rt_acc);
-    return s->grt.on ? gcurve_fit(s, true) : 0;
+    HIP_TRY(hipMemcpyAsync(const_cast<double *>(rb.weight), weight, sizeof(double) * d.M, hipMemcpyHostToDevice, s->ctx->stream));
+    // j = 0 empties the draw store and the group next-generation matrix too: they hold draws [0, count)
+    return window_begin(s, w, [&](hipStream_t st) {
+        if (s->keep_rt.buf) HIP_TRY(hipMemsetAsync(s->keep_rt.buf.p, 0, sizeof(double) * window_cells(s, w) * (size_t)s->keep_rt.stride, st));
+        if (s->ngm.cap)
+            HIP_TRY(hipMemsetAsync(s->ngm.out.p, 0, sizeof(double) * (size_t)s->ngm.cap * B * s->grp.G * s->grp.G * D, st));
+        return 0;
+    });
 }
 
 extern "C" int seir_sampler_rt(seir_sampler *s, int32_t first, int32_t count) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    if ((rc = rt_check(s, first, count))) return rc;
+    Window &w = s->rt;
+    if ((rc = window_check(s, w, first, count))) return rc;
     if (count == 0) return 0;
-    if (s->rt_keep && s->rt_j + count > s->rt_keep_cap)
-        return fail(SEIR_ERR_INVALID, "%lld draws per chain folded since the reset and %d more: the draw store holds %lld "
-                    "(seir_sampler_rt_keep)", s->rt_j, count, s->rt_keep_cap);
-    if (s->ngm.cap && s->rt_j + count > s->ngm.cap)
-        return fail(SEIR_ERR_INVALID, "%lld draws per chain folded since the reset and %d more: the draw store holds %lld "
-                    "(seir_sampler_group_ngm)", s->rt_j, count, s->ngm.cap);
+    const DrawStore &keep = s->keep_rt;
+    long long &j = w.acc.j;
+    if (keep.buf && (rc = store_holds(w.who, j, count, keep.cap, w.who.keep))) return rc;
+    if (s->ngm.cap && (rc = store_holds(w.who, j, count, s->ngm.cap, "seir_sampler_group_ngm"))) return rc;
     seir_ctx *ctx = s->ctx;
     const LaunchCfg l = whole(ctx, s->cfg.B);
     const Dims &d = l.d;
-    const int B = s->cfg.B, D = s->rt.D;
-    const RtBufs &rb = s->rt;
+    const int B = s->cfg.B, D = w.D;
+    const RtBufs &rb = s->rtb;
     Work tw = ctx->w;                                 // k_rt_tables writes Work::ea: the feature's own buffer, not the sampler's
     tw.ea = rb.ea;
     const size_t lds = k_rt_trace_lds_bytes<RT_DT>(d.Mp);
-    const bool curves = s->grt.b.D != 0;                // group R_t: the batch also fits the cell plane
-    const int slots = std::min(curves ? s->grt.b.slots : s->rt_slots, s->ngm.cap ? s->ngm.slots : s->rt_slots);
+    const bool curves = w.curve.b.D != 0;               // group R_t: the batch also fits the cell plane
+    const int slots = std::min(curves ? w.curve.b.slots : w.slots, s->ngm.cap ? s->ngm.slots : w.slots);
     for (int j0 = 0; j0 < count; j0 += slots) {
         const int nj = std::min(slots, count - j0), ND = nj * B;
         hipLaunchKernelGGL(k_rt_tables, dim3(ND), dim3(256), 0, l.st, d, tw,
@@ -3373,10 +3407,10 @@ extern "C" int seir_sampler_rt(seir_sampler *s, int32_t first, int32_t count) {
             hipLaunchKernelGGL(k_rt_prepare<1>, pgrid, pblock, 0, l.st, d, ctx->c, rb, (const void *)s->ch.tr_events, B, first + j0);
         else
             hipLaunchKernelGGL(k_rt_prepare<0>, pgrid, pblock, 0, l.st, d, ctx->c, rb, (const void *)s->ch.tr_events, B, first + j0);
-        if (s->ngm.cap) ngm_launch(s, l, first + j0, s->rt_j + j0, nj);      // behind k_rt_prepare: ea and S of the batch lie there
-        if (s->rt_keep)                               // in place of k_rt_trace: R_it is formed once
+        if (s->ngm.cap) ngm_launch(s, l, first + j0, j + j0, nj);            // behind k_rt_prepare: ea and S of the batch lie there
+        if (keep.buf)                                 // in place of k_rt_trace: R_it is formed once
             hipLaunchKernelGGL(k_rt_trace_keep<RT_DT>, dim3(rb.ncb, (D + RT_DT - 1) / RT_DT, B), dim3(256), lds, l.st, d, ctx->c, rb,
-                               (const double *)s->ch.tr_theta, B, first + j0, nj, s->rt_keep.as<double>(), s->rt_keep_stride);
+                               (const double *)s->ch.tr_theta, B, first + j0, nj, keep.buf.as<double>(), keep.stride);
         else if (curves)                              // in place of k_rt_trace: it also leaves every cell's r in the plane
             gcurve_rt_trace_cells(s, l, first + j0, nj);
         else
@@ -3384,12 +3418,12 @@ extern "C" int seir_sampler_rt(seir_sampler *s, int32_t first, int32_t count) {
                                (const double *)s->ch.tr_theta, B, first + j0, nj);
         hipLaunchKernelGGL(k_rt_finish, dim3((unsigned)(((size_t)ND * D + 255) / 256)), dim3(256), 0, l.st, rb, B, first + j0, nj);
         if (curves) {
-            if (s->rt_keep) gcurve_rt_gather(s, l, s->rt_j + j0, nj);
-            gcurve_sums(s, l, s->grt, D, first + j0, nj);
+            if (keep.buf) gcurve_rt_gather(s, l, j + j0, nj);
+            gcurve_sums(s, l, w, first + j0, nj);
         }
     }
     HIP_TRY(hipGetLastError());
-    s->rt_j += count;
+    j += count;
     return 0;
 }
 
@@ -3399,61 +3433,66 @@ extern "C" int seir_sampler_rt(seir_sampler *s, int32_t first, int32_t count) {
 extern "C" int seir_sampler_rt_keep(seir_sampler *s, int64_t cap) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    if ((rc = rt_check(s))) return rc;
+    if ((rc = window_check(s, s->rt))) return rc;
     if (cap < 0 || cap > (1ll << 20))
         return fail(SEIR_ERR_INVALID, "cap=%lld outside [0, 2^20]: the draws per chain between two resets", (long long)cap);
     const long long stride = (cap + RT_KEEP_RUN - 1) / RT_KEEP_RUN * RT_KEEP_RUN;
     char shape[160];
     snprintf(shape, sizeof shape, "%d chains x %d days x %d locations x %lld draws x 8", s->cfg.B, s->rt.D, s->ctx->d.M, stride);
-    rc = keep_resize(s, s->rt_keep, s->rt_keep_cap, cap, s->rt_j, (unsigned long long)rt_cells(s) * (unsigned long long)stride * 8ull,
-                     "folded", "seir_sampler_rt_reset", "seir_sampler_rt", shape);
-    if (!s->rt_keep) s->rt_keep_stride = 0;
-    else if (!rc) s->rt_keep_stride = stride;        // a refused resize leaves the store and its stride as they were
-    if (s->rt_keep) (void)lds_attribute((const void *)k_rt_trace_keep<RT_DT>, k_rt_trace_lds_bytes<RT_DT>(s->ctx->d.Mp));
+    DrawStore &keep = s->keep_rt;
+    rc = keep_resize(s, keep, RT_USER, cap, s->rt.acc.j, (unsigned long long)window_cells(s, s->rt) * (unsigned long long)stride * 8ull,
+                     shape);
+    if (keep.buf && !rc) keep.stride = stride;       // a refused resize leaves the store and its stride as they were
+    if (keep.buf) (void)lds_attribute((const void *)k_rt_trace_keep<RT_DT>, k_rt_trace_lds_bytes<RT_DT>(s->ctx->d.Mp));
     return rc;
 }
 
 extern "C" int seir_sampler_rt_order_stats(seir_sampler *s, const int64_t *ranks, int32_t R, int32_t pooled, double *out) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    if ((rc = rt_check(s))) return rc;
-    if ((rc = keep_order_stats<uint64_t>(s, s->rt_keep.as<const uint64_t>(), s->rt_j, s->rt.count, (long long)s->rt.D * s->ctx->d.M,
-                                         s->rt_keep_stride, ranks, R, pooled, (uint64_t *)out, "seir_sampler_rt_keep", "rt", "folded")))
+    if ((rc = window_check(s, s->rt))) return rc;
+    if ((rc = keep_order_stats<uint64_t>(s, s->keep_rt, RT_USER, s->rt.acc.j, s->rtb.count, (long long)s->rt.D * s->ctx->d.M, ranks, R,
+                                         pooled, (uint64_t *)out)))
         return rc;
     return check_ev_overflow(s);
 }
 
-static int copy_rt_draws(seir_sampler *s, hipStream_t st, int32_t first, int32_t count, double *R_t) {
-    const size_t row = (size_t)s->cfg.B * s->rt.D;
-    HIP_TRY(hipMemcpyAsync(R_t, s->rt.Rt + (size_t)first * row, sizeof(double) * count * row, hipMemcpyDeviceToHost, st));
-    return 0;
+// Slots [first, first + count) of a Window's per-draw curves src, `row` doubles per slot in each plane, to a (and b).  Where
+// there is one plane a null destination is refused; of two, either may be left out.
+static int deliver_curves(seir_sampler *s, const Window &w, bool async, const double *const *src, size_t row, int32_t first,
+                          int32_t count, double *a, double *b) {
+    if (w.planes == 1 && !a) return fail(SEIR_ERR_INVALID, "null pointer");
+    double *const dst[2] = {a, b};
+    return deliver(s, async, [&](hipStream_t st) {
+        for (int x = 0; x < w.planes; ++x)
+            if (dst[x])
+                HIP_TRY(hipMemcpyAsync(dst[x], src[x] + (size_t)first * row, sizeof(double) * count * row, hipMemcpyDeviceToHost, st));
+        return 0;
+    });
+}
+
+// What is behind the four readers of the national curves [cap][B][D] of seir_sampler::rt or ::wb.
+static int read_draws(seir_sampler *s, Window seir_sampler::*which, bool async, int32_t first, int32_t count, double *a, double *b) {
+    if (int rc = sampler_check(s)) return rc;
+    const Window &w = s->*which;
+    if (int rc = window_check(s, w, first, count)) return rc;
+    return deliver_curves(s, w, async, w.draws, (size_t)s->cfg.B * w.D, first, count, a, b);
 }
 
 extern "C" int seir_sampler_read_rt_draws(seir_sampler *s, int32_t first, int32_t count, double *R_t) {
-    int rc = sampler_check(s);
-    if (rc) return rc;
-    if ((rc = rt_check(s, first, count))) return rc;
-    if (!R_t) return fail(SEIR_ERR_INVALID, "null pointer");
-    if ((rc = copy_rt_draws(s, s->ctx->stream, first, count, R_t))) return rc;
-    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
-    return check_ev_overflow(s);
+    return read_draws(s, &seir_sampler::rt, false, first, count, R_t, nullptr);
 }
-
 extern "C" int seir_sampler_read_rt_draws_async(seir_sampler *s, int32_t first, int32_t count, double *R_t) {
-    int rc = sampler_check(s);
-    if (rc) return rc;
-    if ((rc = rt_check(s, first, count))) return rc;
-    if (!R_t) return fail(SEIR_ERR_INVALID, "null pointer");
-    return on_copy_stream(s, [&](hipStream_t st) { return copy_rt_draws(s, st, first, count, R_t); });
+    return read_draws(s, &seir_sampler::rt, true, first, count, R_t, nullptr);
 }
 
 extern "C" int seir_sampler_read_rt(seir_sampler *s, uint64_t *count, double *ref, double *sum, double *sumsq, uint32_t *gt1) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    if ((rc = rt_check(s))) return rc;
+    if ((rc = window_check(s, s->rt))) return rc;
     hipStream_t st = s->ctx->stream;
-    const size_t n = rt_cells(s);
-    const RtBufs &rb = s->rt;
+    const size_t n = window_cells(s, s->rt);
+    const RtBufs &rb = s->rtb;
     if (count) HIP_TRY(hipMemcpyAsync(count, rb.count, sizeof(uint64_t) * s->cfg.B, hipMemcpyDeviceToHost, st));
     if (ref) HIP_TRY(hipMemcpyAsync(ref, rb.ref, sizeof(double) * n, hipMemcpyDeviceToHost, st));
     if (sum) HIP_TRY(hipMemcpyAsync(sum, rb.sum, sizeof(double) * n, hipMemcpyDeviceToHost, st));
@@ -3466,39 +3505,27 @@ extern "C" int seir_sampler_read_rt(seir_sampler *s, uint64_t *count, double *re
 // ---------------------------------------------------------------------------
 // Within/between pressure shares on the device (include/seir_hip.h; kernels: wb_kernels.h)
 // ---------------------------------------------------------------------------
-// as rt_check
-static int wb_check(seir_sampler *s, int32_t first = 0, int32_t count = 0) {
-    if (need_events(s, WB_USER.verb)) return SEIR_ERR_INVALID;
-    return trace_range_check(s, s->wb_on, WB_USER, first, count);
-}
-static size_t wb_cells(const seir_sampler *s) { return (size_t)s->cfg.B * s->wb.D * s->ctx->d.M; }
-
 extern "C" int seir_sampler_wb_reset(seir_sampler *s, int32_t days) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    if (need_events(s, WB_USER.verb)) return SEIR_ERR_INVALID;
+    Window &w = s->wb;
+    if (need_events(s, w.who.verb)) return SEIR_ERR_INVALID;
     const Dims &d = s->ctx->d;
     if (days < 1 || days > d.T) return fail(SEIR_ERR_INVALID, "days=%d outside [1, T = %d]", days, d.T);
     const int B = s->cfg.B, D = days;
-    hipStream_t st = s->ctx->stream;
-    WbBufs &wb = s->wb;
-    if (!s->wb_on || wb.D != D) {
-        // first reset, or another window: everything is sized by D
-        if ((rc = drain(s))) return rc;
-        s->wb_allocs.clear();
-        s->wb_acc = Shadowed{};
-        s->wb_on = false;
+    WbBufs &wb = s->wbb;
+    if (!w.on || w.D != D) {
+        if ((rc = window_resize(s, w, D))) return rc;
         wb = WbBufs{};
         wb.D = D; wb.t0 = d.T - D; wb.ncb = (d.M + 63) / 64;
-        // the I plane of a batch is bounded as the reproduction number's S plane: a call is cut into batches of at most wb_slots slots
-        s->wb_slots = staging_slots(s->ctx, s->cfg.cap, (size_t)B * d.Mp * D * sizeof(int));
-        const size_t nd = (size_t)s->wb_slots * B;
-        S_ALLOC(wb_allocs, wb.I, nd * D * d.Mp); S_ALLOC(wb_allocs, wb.part, nd * D * wb.ncb * 2);
-        S_ALLOC(wb_allocs, wb.Wn, (size_t)s->cfg.cap * B * D); S_ALLOC(wb_allocs, wb.Bn, (size_t)s->cfg.cap * B * D);
-        const size_t cells = (size_t)B * D * d.M, cw = rt_count_words(s);
-        if (!rc) rc = s->wb_acc.buf.zeroed(cells * (5 * sizeof(double) + 2 * sizeof(uint32_t)) + cw * sizeof(uint64_t));
+        const size_t nd = (size_t)w.slots * B;
+        S_ALLOC(wb.allocs, wb.I, nd * D * d.Mp); S_ALLOC(wb.allocs, wb.part, nd * D * wb.ncb * 2);
+        S_ALLOC(wb.allocs, wb.Wn, (size_t)s->cfg.cap * B * D); S_ALLOC(wb.allocs, wb.Bn, (size_t)s->cfg.cap * B * D);
+        w.draws[0] = wb.Wn; w.draws[1] = wb.Bn;
+        const size_t cells = window_cells(s, w), cw = count_words(s);
+        if (!rc) rc = w.acc.buf.zeroed(cells * (5 * sizeof(double) + 2 * sizeof(uint32_t)) + cw * sizeof(uint64_t));
         if (rc) return rc;
-        wb.sum_w = s->wb_acc.buf.as<double>();
+        wb.sum_w = w.acc.buf.as<double>();
         wb.sumsq_w = wb.sum_w + cells;
         wb.ref_w = wb.sumsq_w + cells;
         wb.ref_b = wb.ref_w + cells;
@@ -3507,28 +3534,25 @@ extern "C" int seir_sampler_wb_reset(seir_sampler *s, int32_t days) {
         wb.n = (uint32_t *)(wb.count + cw);
         wb.gt = wb.n + cells;
         (void)lds_attribute((const void *)k_wb_trace<WB_DT>, k_wb_trace_lds_bytes<WB_DT>(d.Mp));
-        s->wb_on = true;
+        w.on = true;
     }
-    if ((rc = acc_zero(s->wb_acc, st))) return rc;
-    HIP_TRY(hipStreamSynchronize(st));
-    // what the snapshots taken before this reset hold of it is dropped: restoring one of them leaves the accumulators alone
-    acc_invalidate(s->wb_acc);
-    return s->gwb.on ? gcurve_fit(s, false) : 0;
+    return window_begin(s, w, [](hipStream_t) { return 0; });
 }
 
 extern "C" int seir_sampler_wb(seir_sampler *s, int32_t first, int32_t count) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    if ((rc = wb_check(s, first, count))) return rc;
+    Window &w = s->wb;
+    if ((rc = window_check(s, w, first, count))) return rc;
     if (count == 0) return 0;
     seir_ctx *ctx = s->ctx;
     const LaunchCfg l = whole(ctx, s->cfg.B);
     const Dims &d = l.d;
-    const int B = s->cfg.B, D = s->wb.D;
-    const WbBufs &wb = s->wb;
+    const int B = s->cfg.B, D = w.D;
+    const WbBufs &wb = s->wbb;
     const size_t lds = k_wb_trace_lds_bytes<WB_DT>(d.Mp);
-    const bool curves = s->gwb.b.D != 0;                // group within / between: the batch also fits the two cell planes
-    const int slots = curves ? s->gwb.b.slots : s->wb_slots;
+    const bool curves = w.curve.b.D != 0;               // group within / between: the batch also fits the two cell planes
+    const int slots = curves ? w.curve.b.slots : w.slots;
     for (int j0 = 0; j0 < count; j0 += slots) {
         const int nj = std::min(slots, count - j0), ND = nj * B;
         const dim3 pgrid((d.M + WB_PREP_ROWS - 1) / WB_PREP_ROWS, ND), pblock(64 * WB_PREP_ROWS);
@@ -3542,45 +3566,30 @@ extern "C" int seir_sampler_wb(seir_sampler *s, int32_t first, int32_t count) {
             hipLaunchKernelGGL(k_wb_trace<WB_DT>, dim3(wb.ncb, (D + WB_DT - 1) / WB_DT, B), dim3(256), lds, l.st, d, ctx->c, wb,
                                (const double *)s->ch.tr_theta, B, first + j0, nj);
         hipLaunchKernelGGL(k_wb_finish, dim3((unsigned)(((size_t)ND * D + 255) / 256)), dim3(256), 0, l.st, wb, B, first + j0, nj);
-        if (curves) gcurve_sums(s, l, s->gwb, D, first + j0, nj);
+        if (curves) gcurve_sums(s, l, w, first + j0, nj);
     }
     HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-static int copy_wb_draws(seir_sampler *s, hipStream_t st, int32_t first, int32_t count, double *Wn, double *Bn) {
-    const size_t row = (size_t)s->cfg.B * s->wb.D;
-    if (Wn) HIP_TRY(hipMemcpyAsync(Wn, s->wb.Wn + (size_t)first * row, sizeof(double) * count * row, hipMemcpyDeviceToHost, st));
-    if (Bn) HIP_TRY(hipMemcpyAsync(Bn, s->wb.Bn + (size_t)first * row, sizeof(double) * count * row, hipMemcpyDeviceToHost, st));
+    w.acc.j += count;
     return 0;
 }
 
 extern "C" int seir_sampler_read_wb_draws(seir_sampler *s, int32_t first, int32_t count, double *within_pressure,
                                           double *between_pressure) {
-    int rc = sampler_check(s);
-    if (rc) return rc;
-    if ((rc = wb_check(s, first, count))) return rc;
-    if ((rc = copy_wb_draws(s, s->ctx->stream, first, count, within_pressure, between_pressure))) return rc;
-    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
-    return check_ev_overflow(s);
+    return read_draws(s, &seir_sampler::wb, false, first, count, within_pressure, between_pressure);
 }
-
 extern "C" int seir_sampler_read_wb_draws_async(seir_sampler *s, int32_t first, int32_t count, double *within_pressure,
                                                 double *between_pressure) {
-    int rc = sampler_check(s);
-    if (rc) return rc;
-    if ((rc = wb_check(s, first, count))) return rc;
-    return on_copy_stream(s, [&](hipStream_t st) { return copy_wb_draws(s, st, first, count, within_pressure, between_pressure); });
+    return read_draws(s, &seir_sampler::wb, true, first, count, within_pressure, between_pressure);
 }
 
 extern "C" int seir_sampler_read_wb(seir_sampler *s, uint64_t *count, uint32_t *n, double *ref_w, double *sum_w, double *sumsq_w,
                                     double *ref_b, double *sum_b, uint32_t *gt) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    if ((rc = wb_check(s))) return rc;
+    if ((rc = window_check(s, s->wb))) return rc;
     hipStream_t st = s->ctx->stream;
-    const size_t cells = wb_cells(s);
-    const WbBufs &wb = s->wb;
+    const size_t cells = window_cells(s, s->wb);
+    const WbBufs &wb = s->wbb;
     if (count) HIP_TRY(hipMemcpyAsync(count, wb.count, sizeof(uint64_t) * s->cfg.B, hipMemcpyDeviceToHost, st));
     const struct { double *dst; const double *src; } dbl[] = {{ref_w, wb.ref_w}, {sum_w, wb.sum_w}, {sumsq_w, wb.sumsq_w},
                                                               {ref_b, wb.ref_b}, {sum_b, wb.sum_b}};
@@ -3597,29 +3606,26 @@ extern "C" int seir_sampler_read_wb(seir_sampler *s, uint64_t *count, uint32_t *
 // ---------------------------------------------------------------------------
 // Size the buffers of a family for the table, the switch and the product's window as they are now (none when any is off).
 // The batch shrinks so that the product's integer plane and the cell plane(s) stay within the staging bound together.
-static int gcurve_fit(seir_sampler *s, bool rt) {
-    GroupCurve &c = rt ? s->grt : s->gwb;
-    c.planes = rt ? 1 : 2;
-    const bool product = rt ? s->rt_on : s->wb_on;
-    const int D = (c.on && s->grp_on && product) ? (rt ? s->rt.D : s->wb.D) : 0;
+static int gcurve_fit(seir_sampler *s, Window &w) {
+    GroupCurve &c = w.curve;
+    const int D = (c.on && s->grp_on && w.on) ? w.D : 0;
     if (D == c.b.D) return 0;
     if (int rc = drain(s)) return rc;
     c.b = {};
     if (D == 0) return 0;
     const Dims &d = s->ctx->d;
     const int B = s->cfg.B, G = s->grp.G;
-    const int slots = staging_slots(s->ctx, rt ? s->rt_slots : s->wb_slots,
-                                    (size_t)B * d.Mp * D * (sizeof(int) + c.planes * sizeof(double)));
+    const int slots = staging_slots(s->ctx, w.slots, (size_t)B * d.Mp * D * (sizeof(int) + w.planes * sizeof(double)));
     const unsigned long long out_bytes = (unsigned long long)s->cfg.cap * B * G * D * 8ull;
     const unsigned long long cell_bytes = (unsigned long long)slots * B * D * d.Mp * 8ull;
-    const unsigned long long bytes = (unsigned long long)c.planes * (out_bytes + cell_bytes);
+    const unsigned long long bytes = (unsigned long long)w.planes * (out_bytes + cell_bytes);
     if (int rc = refuse_above_half_free(bytes, "the group curves need %llu bytes (%d planes x (%d slots x %d chains x %d groups x %d "
-                                        "days x 8 + %llu of a batch's cells))", bytes, c.planes, s->cfg.cap, B, G, D, cell_bytes))
+                                        "days x 8 + %llu of a batch's cells))", bytes, w.planes, s->cfg.cap, B, G, D, cell_bytes))
         return rc;
     // every buffer or none: a family whose outputs could not be made has none (D = 0) and is not launched for
     GroupCurve::Bufs b;
     int rc = b.offsets.upload(s->grp_offsets.data(), sizeof(int) * (size_t)(G + 1));
-    for (int x = 0; x < c.planes && !rc; ++x)
+    for (int x = 0; x < w.planes && !rc; ++x)
         if (!(rc = b.out[x].zeroed((size_t)out_bytes))) rc = b.cells[x].zeroed((size_t)cell_bytes);
     if (rc) return alloc_failed(bytes, "group curves");
     gcurve_lds_attributes(d.Mp);
@@ -3631,9 +3637,10 @@ static int gcurve_fit(seir_sampler *s, bool rt) {
 extern "C" int seir_sampler_group_rt(seir_sampler *s, const double *weights) {
     int rc = sampler_check(s);
     if (rc) return rc;
+    GroupCurve &c = s->rt.curve;
     if (!weights) {
-        if (s->grt.on && (rc = drain(s))) return rc;
-        s->grt = GroupCurve{};                       // off: the weights belonged to the table that was in force
+        if (c.on && (rc = drain(s))) return rc;
+        c = GroupCurve{};                            // off: the weights belonged to the table that was in force
         return 0;
     }
     if ((rc = need_events(s, RT_USER.verb))) return rc;
@@ -3642,63 +3649,53 @@ extern "C" int seir_sampler_group_rt(seir_sampler *s, const double *weights) {
     for (size_t k = 0; k < nnz; ++k)
         if (!(fabs(weights[k]) < __builtin_inf())) return fail(SEIR_ERR_INVALID, "weights[%zu] is not finite", k);
     if ((rc = drain(s))) return rc;
-    if ((rc = s->grt.weights.upload(weights, sizeof(double) * nnz))) return rc;
-    s->grt.on = true;
-    if ((rc = gcurve_fit(s, true))) { s->grt = GroupCurve{}; return rc; }
+    if ((rc = c.weights.upload(weights, sizeof(double) * nnz))) return rc;
+    c.on = true;
+    if ((rc = gcurve_fit(s, s->rt))) { c = GroupCurve{}; return rc; }
     return 0;
 }
 
 extern "C" int seir_sampler_group_wb(seir_sampler *s, int32_t on) {
     int rc = sampler_check(s);
     if (rc) return rc;
+    GroupCurve &c = s->wb.curve;
     if (!on) {
-        if (s->gwb.on && (rc = drain(s))) return rc;
-        s->gwb = GroupCurve{};
+        if (c.on && (rc = drain(s))) return rc;
+        c = GroupCurve{};
         return 0;
     }
     if ((rc = need_events(s, WB_USER.verb))) return rc;
     if (!s->grp_on) return fail(SEIR_ERR_STATE, "no group table is set: call seir_sampler_groups_set first");
-    s->gwb.on = true;
-    if ((rc = gcurve_fit(s, false))) { s->gwb.on = false; return rc; }
+    c.on = true;
+    if ((rc = gcurve_fit(s, s->wb))) { c.on = false; return rc; }
     return 0;
 }
 
-static int copy_group_curves(seir_sampler *s, hipStream_t st, const GroupCurve &c, int32_t first, int32_t count, double *const *dst) {
-    const size_t row = (size_t)s->cfg.B * s->grp.G * c.b.D;
-    for (int x = 0; x < c.planes; ++x)
-        if (dst[x])
-            HIP_TRY(hipMemcpyAsync(dst[x], c.b.out[x].as<double>() + (size_t)first * row, sizeof(double) * count * row, hipMemcpyDeviceToHost, st));
-    return 0;
-}
-
-static int read_group_curves(seir_sampler *s, bool rt, bool async, int32_t first, int32_t count, double *a, double *b) {
-    int rc = sampler_check(s);
-    if (rc) return rc;
-    if ((rc = rt ? rt_check(s, first, count) : wb_check(s, first, count))) return rc;
-    const GroupCurve &c = rt ? s->grt : s->gwb;
+// What is behind the four readers of the group curves out [cap][B][G][D] of seir_sampler::rt or ::wb.
+static int read_group_curves(seir_sampler *s, Window seir_sampler::*which, bool async, int32_t first, int32_t count, double *a,
+                             double *b) {
+    if (int rc = sampler_check(s)) return rc;
+    const Window &w = s->*which;
+    if (int rc = window_check(s, w, first, count)) return rc;
+    const GroupCurve &c = w.curve;
     if (c.b.D == 0)
-        return fail(SEIR_ERR_STATE, "%s", !c.on ? (rt ? "group R_t is not enabled: call seir_sampler_group_rt first"
-                                                     : "group within/between is not enabled: call seir_sampler_group_wb first")
+        return fail(SEIR_ERR_STATE, "%s", !c.on ? w.who.no_curve
                                               : "the group curves have no outputs: no table is set, or they were refused");
-    if (rt && !a) return fail(SEIR_ERR_INVALID, "null pointer");
-    double *const dst[2] = {a, b};
-    if (async) return on_copy_stream(s, [&](hipStream_t st) { return copy_group_curves(s, st, c, first, count, dst); });
-    if ((rc = copy_group_curves(s, s->ctx->stream, c, first, count, dst))) return rc;
-    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
-    return check_ev_overflow(s);
+    const double *const src[2] = {c.b.out[0].as<double>(), c.b.out[1].as<double>()};
+    return deliver_curves(s, w, async, src, (size_t)s->cfg.B * s->grp.G * c.b.D, first, count, a, b);
 }
 
 extern "C" int seir_sampler_read_group_rt(seir_sampler *s, int32_t first, int32_t count, double *Rg) {
-    return read_group_curves(s, true, false, first, count, Rg, nullptr);
+    return read_group_curves(s, &seir_sampler::rt, false, first, count, Rg, nullptr);
 }
 extern "C" int seir_sampler_read_group_rt_async(seir_sampler *s, int32_t first, int32_t count, double *Rg) {
-    return read_group_curves(s, true, true, first, count, Rg, nullptr);
+    return read_group_curves(s, &seir_sampler::rt, true, first, count, Rg, nullptr);
 }
 extern "C" int seir_sampler_read_group_wb(seir_sampler *s, int32_t first, int32_t count, double *Wg, double *Bg) {
-    return read_group_curves(s, false, false, first, count, Wg, Bg);
+    return read_group_curves(s, &seir_sampler::wb, false, first, count, Wg, Bg);
 }
 extern "C" int seir_sampler_read_group_wb_async(seir_sampler *s, int32_t first, int32_t count, double *Wg, double *Bg) {
-    return read_group_curves(s, false, true, first, count, Wg, Bg);
+    return read_group_curves(s, &seir_sampler::wb, true, first, count, Wg, Bg);
 }
 
 static void gcurve_wsums_launch(const Dims &d, hipStream_t st, const int *offsets, const int *members, const double *weights,
@@ -3888,33 +3885,34 @@ static void gcurve_wsums_launch(const Dims &d, hipStream_t st, const int *offset
 }
 
 // The batch's cell planes [nj * B][D][Mp] onto out [.][B][G][D] from slot slot0.
-static void gcurve_sums(seir_sampler *s, const LaunchCfg &l, const GroupCurve &c, int D, int slot0, int nj) {
+static void gcurve_sums(seir_sampler *s, const LaunchCfg &l, const Window &w, int slot0, int nj) {
+    const GroupCurve &c = w.curve;
     const int B = s->cfg.B;
-    for (int x = 0; x < c.planes; ++x)
+    for (int x = 0; x < w.planes; ++x)
         gcurve_wsums_launch(l.d, l.st, c.b.offsets.as<int>(), s->grp.members, c.weights.as<double>(), c.b.cells[x].as<double>(),
-                            s->grp.G, D, l.d.Mp, 0, (long long)slot0 * B, (long long)nj * B, c.b.out[x].as<double>());
+                            s->grp.G, w.D, l.d.Mp, 0, (long long)slot0 * B, (long long)nj * B, c.b.out[x].as<double>());
 }
 
 static void gcurve_rt_trace_cells(seir_sampler *s, const LaunchCfg &l, int slot0, int nj) {
-    const RtBufs &rb = s->rt;
+    const RtBufs &rb = s->rtb;
     const int B = s->cfg.B;
     hipLaunchKernelGGL(k_rt_trace_cells<RT_DT>, dim3(rb.ncb, (rb.D + RT_DT - 1) / RT_DT, B), dim3(256),
                        k_rt_trace_lds_bytes<RT_DT>(l.d.Mp), l.st, l.d, s->ctx->c, rb, (const double *)s->ch.tr_theta, B, slot0, nj,
-                       s->grt.b.cells[0].as<double>(), (long long)l.d.Mp);
+                       s->rt.curve.b.cells[0].as<double>(), (long long)l.d.Mp);
 }
 
 static void gcurve_rt_gather(seir_sampler *s, const LaunchCfg &l, long long pos0, int nj) {
     const int B = s->cfg.B, D = s->rt.D;
-    hipLaunchKernelGGL(k_rt_cells_from_keep, dim3((l.d.M + 255) / 256, D, B), dim3(256), 0, l.st, l.d, s->rt_keep.as<const double>(),
-                       s->rt_keep_stride, pos0, B, D, nj, s->grt.b.cells[0].as<double>(), (long long)l.d.Mp);
+    hipLaunchKernelGGL(k_rt_cells_from_keep, dim3((l.d.M + 255) / 256, D, B), dim3(256), 0, l.st, l.d, s->keep_rt.buf.as<const double>(),
+                       s->keep_rt.stride, pos0, B, D, nj, s->rt.curve.b.cells[0].as<double>(), (long long)l.d.Mp);
 }
 
 static void gcurve_wb_trace_cells(seir_sampler *s, const LaunchCfg &l, int slot0, int nj) {
-    const WbBufs &wb = s->wb;
+    const WbBufs &wb = s->wbb;
     const int B = s->cfg.B;
     hipLaunchKernelGGL(k_wb_trace_cells<WB_DT>, dim3(wb.ncb, (wb.D + WB_DT - 1) / WB_DT, B), dim3(256),
                        k_wb_trace_lds_bytes<WB_DT>(l.d.Mp), l.st, l.d, s->ctx->c, wb, (const double *)s->ch.tr_theta, B, slot0, nj,
-                       s->gwb.b.cells[0].as<double>(), s->gwb.b.cells[1].as<double>(), (long long)l.d.Mp);
+                       s->wb.curve.b.cells[0].as<double>(), s->wb.curve.b.cells[1].as<double>(), (long long)l.d.Mp);
 }
 
 // Above 64 KiB of dynamic LDS a kernel needs the attribute (as k_rt_trace and k_wb_trace get theirs at their resets).
@@ -3947,7 +3945,7 @@ static void ngm_lds_attribute(int Mp) {
 static void ngm_launch(seir_sampler *s, const LaunchCfg &l, int slot0, long long pos0, int nj) {
     const GroupNgm &n = s->ngm;
     const int B = s->cfg.B, G = s->grp.G;
-    ngm_rows_launch(l.d, s->ctx->c, l.st, s->rt, (const double *)s->ch.tr_theta, B, slot0, (long long)nj * B, n.offsets.as<int>(),
+    ngm_rows_launch(l.d, s->ctx->c, l.st, s->rtb, (const double *)s->ch.tr_theta, B, slot0, (long long)nj * B, n.offsets.as<int>(),
                     s->grp.members, G, n.P.as<double>(), (long long)l.d.Mp);
     // K [pos][b][g][h][t]: the group sums of P [nd][g][t][.] over the members of h, (draw, g) as the "draw" axis
     gcurve_wsums_launch(l.d, l.st, n.offsets.as<int>(), s->grp.members, n.weights.as<double>(), n.P.as<double>(), G, n.D, l.d.Mp, 0,
@@ -3966,10 +3964,10 @@ extern "C" int seir_sampler_group_ngm(seir_sampler *s, const double *weights, in
     if (cap < 0 || cap > (1ll << 20))
         return fail(SEIR_ERR_INVALID, "cap=%lld outside [0, 2^20]: the draws per chain between two resets", (long long)cap);
     if (!s->grp_on) return fail(SEIR_ERR_STATE, "no group table is set: call seir_sampler_groups_set first");
-    if (!s->rt_on) return fail(SEIR_ERR_STATE, "%s", RT_USER.not_enabled);
-    if (s->rt_j != 0)
+    if (!s->rt.on) return fail(SEIR_ERR_STATE, "%s", RT_USER.not_enabled);
+    if (s->rt.acc.j != 0)
         return fail(SEIR_ERR_STATE, "%lld draws per chain have been folded since the reset: the draw store is sized between "
-                    "seir_sampler_rt_reset and the first seir_sampler_rt", s->rt_j);
+                    "seir_sampler_rt_reset and the first seir_sampler_rt", s->rt.acc.j);
     const Dims &d = s->ctx->d;
     const int B = s->cfg.B, G = s->grp.G, D = s->rt.D;
     const size_t nnz = (size_t)s->grp_offsets[G];
@@ -3978,7 +3976,7 @@ extern "C" int seir_sampler_group_ngm(seir_sampler *s, const double *weights, in
     if ((rc = drain(s))) return rc;
     s->ngm = GroupNgm{};                             // a refusal or failure below leaves it off
     // the staging bound covers the S plane, the cell plane of group R_t and P together: the batch shrinks accordingly
-    const int slots = staging_slots(s->ctx, s->rt_slots, (size_t)B * d.Mp * D * (sizeof(int) + sizeof(double) + (size_t)G * sizeof(double)));
+    const int slots = staging_slots(s->ctx, s->rt.slots, (size_t)B * d.Mp * D * (sizeof(int) + sizeof(double) + (size_t)G * sizeof(double)));
     const unsigned long long out_bytes = (unsigned long long)cap * B * G * G * D * 8ull;
     const unsigned long long p_bytes = (unsigned long long)slots * B * G * D * d.Mp * 8ull;
     if ((rc = refuse_above_half_free(out_bytes + p_bytes, "the group next-generation matrix needs %llu bytes (%lld draws x %d chains x "
@@ -3998,13 +3996,13 @@ extern "C" int seir_sampler_group_ngm(seir_sampler *s, const double *weights, in
 extern "C" int seir_sampler_read_group_ngm(seir_sampler *s, int64_t first_draw, int64_t count, double *out) {
     int rc = sampler_check(s);
     if (rc) return rc;
-    if ((rc = rt_check(s))) return rc;
+    if ((rc = window_check(s, s->rt))) return rc;
     if (!s->ngm.cap)
         return fail(SEIR_ERR_STATE, "the group next-generation matrix is not enabled: call seir_sampler_group_ngm behind "
                     "seir_sampler_rt_reset (a new table, another window or a refusal switches it off)");
-    if (first_draw < 0 || count < 0 || first_draw + count > s->rt_j)
+    if (first_draw < 0 || count < 0 || first_draw + count > s->rt.acc.j)
         return fail(SEIR_ERR_INVALID, "draws [%lld,%lld) outside the %lld folded since the reset", (long long)first_draw,
-                    (long long)(first_draw + count), s->rt_j);
+                    (long long)(first_draw + count), s->rt.acc.j);
     if (!out) return fail(SEIR_ERR_INVALID, "null pointer");
     const size_t row = (size_t)s->cfg.B * s->grp.G * s->grp.G * s->ngm.D;
     if (count)
