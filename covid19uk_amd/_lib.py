@@ -70,6 +70,20 @@ class SeirProductState(ctypes.Structure):
         [("reserved", ctypes.c_uint64 * 2)]
 
 
+class SeirSweepPlan(ctypes.Structure):
+    """Mirror of `seir_sweep_plan` (include/seir_hip.h)."""
+    _fields_ = [(k, ctypes.c_int32) for k in (
+        "hmc", "inner", "ts_mode", "per", "nbv", "nlive", "end_in_leap", "chunk_aff", "final_aff", "leap_nst", "leap_nmt",
+        "leap_wgs", "leap_nbv", "leap_nlive", "leap_launches", "section_launches", "section_evals", "moves", "nband", "nbk",
+        "pair_nlive", "nch", "fpend", "pre", "move_aff", "record", "advance")] + [("reserved", ctypes.c_int32 * 5)]
+
+
+# the enums of SweepPlan (csrc/sweep_plan.h), by the names tests/test_sweep_plan.py gives them
+PLAN_HMC = ("fold", "tailfold", "stage")
+PLAN_INNER = ("single", "leap", "se_chunk", "split")
+PLAN_MOVES = ("pairs", "pair", "split")
+PLAN_FPEND = (None, "k_move_pairs", "k_record", "k_apply_fpend")
+
 ABI_VERSION = 4               # SEIR_ABI_VERSION
 OPT_DEBUG_SKEW, OPT_XCD_AFFINITY, OPT_GEMM_F32, OPT_EVAL_FORM, OPT_RT_STAGING_KIB = 0, 1, 2, 3, 4
 ERR_INVALID, ERR_STATE = -1, -3   # SEIR_ERR_INVALID, SEIR_ERR_STATE
@@ -182,6 +196,7 @@ _SIGNATURES = {
     "seir_sampler_set_launch_form": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]),
     "seir_sampler_launch_form": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32),
                                                 ctypes.POINTER(ctypes.c_int32)]),
+    "seir_sampler_sweep_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SeirSweepPlan)]),
     # summaries of the recorded events on the device: moments and marginals
     "seir_sampler_summary_reset": (ctypes.c_int, [ctypes.c_void_p]),
     "seir_sampler_summarize": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),

@@ -1682,6 +1682,25 @@ extern "C" int seir_sampler_launch_form(seir_sampler *s, int32_t *hmc_mode, int3
     return 0;
 }
 
+static SweepInputs sweep_inputs(const seir_sampler *s, int g);
+
+// The plan enqueue_sweep executes for the first chain group, member for member (include/seir_hip.h): host fields only.
+extern "C" int seir_sampler_sweep_plan(seir_sampler *s, seir_sweep_plan *out) {
+    if (!s) return fail(SEIR_ERR_INVALID, "null sampler");
+    if (!out) return fail(SEIR_ERR_INVALID, "null pointer");
+    const SweepPlan p = plan_sweep(sweep_inputs(s, 0));
+    seir_sweep_plan o{};
+    o.hmc = p.hmc; o.inner = p.inner; o.ts_mode = p.ts_mode; o.per = p.per; o.nbv = p.nbv; o.nlive = p.nlive;
+    o.end_in_leap = p.end_in_leap; o.chunk_aff = p.chunk_aff; o.final_aff = p.final_aff;
+    o.leap_nst = p.leap_nst; o.leap_nmt = p.leap_nmt; o.leap_wgs = p.leap_wgs; o.leap_nbv = p.leap_nbv;
+    o.leap_nlive = p.leap_nlive; o.leap_launches = p.leap_launches;
+    o.section_launches = p.section_launches; o.section_evals = p.section_evals;
+    o.moves = p.moves; o.nband = p.nband; o.nbk = p.nbk; o.pair_nlive = p.pair_nlive; o.nch = p.nch; o.fpend = p.fpend;
+    o.pre = p.pre; o.move_aff = p.move_aff; o.record = p.record; o.advance = p.advance;
+    *out = o;
+    return 0;
+}
+
 // Test hook: what a timed-out wait leaves behind -- chain `chain`'s fatal counter raised, in stream order.  Every wait of
 // that chain then gives up at its first look at the counter (a wait that is served within 256 polls still completes) and
 // the next read of the trace reports the time-out.

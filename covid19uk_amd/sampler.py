@@ -510,6 +510,18 @@ class ChainSampler:
         inv_m = {v: k for k, v in MOVES_MODES.items()}
         return inv_h[h.value], inv_m[m.value]
 
+    def sweep_plan(self) -> dict:
+        """The launch plan in force (`seir_sampler_sweep_plan`: csrc/sweep_plan.h's plan for the first chain group, host
+        fields only).  `launch_form()` is the form that was asked for; this is what the shape, the chains and the chip made
+        of it: "hmc" is "fold" / "tailfold" / "stage", "inner" "single" / "leap" / "se_chunk" / "split", "moves" "pairs" /
+        "pair" / "split", "fpend" None or the kernel's name; every other member is an int."""
+        p = _lib.SeirSweepPlan()
+        _lib.check(self._lib.seir_sampler_sweep_plan(self._s, ctypes.byref(p)))
+        out = {k: int(getattr(p, k)) for k, _ in _lib.SeirSweepPlan._fields_ if k != "reserved"}
+        out["hmc"], out["inner"] = _lib.PLAN_HMC[out["hmc"]], _lib.PLAN_INNER[out["inner"]]
+        out["moves"], out["fpend"] = _lib.PLAN_MOVES[out["moves"]], _lib.PLAN_FPEND[out["fpend"]]
+        return out
+
     def _recover(self, slot: int, err: Exception):
         """A burst failed with a hand-off time-out: back to the snapshot taken at its start, one step down the ladder of
         launch forms.  Raises `err` when there is nothing further down."""

@@ -440,6 +440,32 @@ int seir_sampler_restore(seir_sampler *s, int32_t slot);
  * change.  seir_sampler_launch_form reads the form in force. */
 int seir_sampler_set_launch_form(seir_sampler *s, int32_t hmc_mode, int32_t moves_mode);
 int seir_sampler_launch_form(seir_sampler *s, int32_t *hmc_mode, int32_t *moves_mode);
+/* The launch plan in force: which kernels the next sweep of the first chain group launches.  seir_sampler_launch_form
+ * reads the form that was ASKED for; a form that does not fit the shape, the number of chains or the chip is replaced
+ * silently by the next one that does (csrc/sweep_plan.h: plan_sweep), and this is what it was replaced by.  Host fields
+ * only: no device call, no stream synchronisation.  SEIR_ERR_INVALID for a NULL sampler or a NULL out. */
+typedef struct seir_sweep_plan {
+    int32_t hmc;            /* 0 FOLD: the trajectory in the persistent k_leap; 1 TAILFOLD: L + 1 k_se_chunk launches and
+                             * k_hmc_final; 2 STAGE: k_hmc_step<0>, the inner steps as `inner` says, k_hmc_step<2> */
+    int32_t inner;          /* inner steps: 0 k_hmc_step<1>; 1 k_leap; 2 k_se_chunk; 3 k_se + k_hmc_chunk */
+    int32_t ts_mode;        /* tile scalars of the chunked leapfrog: 0 not chunked; 1 column scalars (Mp <= 512); 2 all four */
+    int32_t per;            /* chunk roles per chain: day chunks + 64-row chunks */
+    int32_t nbv, nlive;     /* chains of the layout of the role launches (a multiple of 8); those that exist when fewer, else 0 */
+    int32_t end_in_leap, chunk_aff, final_aff;
+    int32_t leap_nst;       /* k_leap: 2: 32-row workgroups of two 16-row tiles (k_leap<ts_mode,ntc,2,4>); 1: k_leap<1,6,1,6> */
+    int32_t leap_nmt;       /* k_leap: row tiles of that shape */
+    int32_t leap_wgs, leap_nbv, leap_nlive;
+    int32_t leap_launches;  /* k_leap launches of leap_nbv chains, one after the other */
+    int32_t section_launches, section_evals;   /* what seir_sampler_time_leapfrog reports */
+    int32_t moves;          /* event updates: 0 k_move_pairs (one launch per sweep); 1 k_move_pair per pair; 2 k_move_pa2 per update */
+    int32_t nband;          /* band workgroups per chain inside the pair launch; 0: k_move_delta launches */
+    int32_t nbk, pair_nlive;
+    int32_t nch;            /* 64-day chunks of the proposal kernels' instance: 6, 12 or 16 */
+    int32_t fpend;          /* 0 none; 1 k_move_pairs; 2 k_record; 3 k_apply_fpend */
+    int32_t pre, move_aff, record, advance;
+    int32_t reserved[5];    /* zero */
+} seir_sweep_plan;          /* 32 int32: 128 bytes */
+int seir_sampler_sweep_plan(seir_sampler *s, seir_sweep_plan *out);
 /* Test hook: raises chain `chain`'s fatal time-out counter in stream order, i.e. leaves what a timed-out wait leaves.
  * The sweeps queued behind it run with every long wait of that chain cut short and the next read of the trace fails. */
 int seir_sampler_debug_fail_handoff(seir_sampler *s, int32_t chain);

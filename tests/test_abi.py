@@ -82,6 +82,30 @@ def test_product_state_refuses_null_pointers_without_touching_the_gpu(lib):
     assert lib.seir_sampler_product_state(None, None) == _lib.ERR_INVALID
 
 
+def test_sweep_plan_struct_layout_matches_header_and_the_planner(lib):
+    # 27 int32 and 5 reserved: member for member the header's struct, and every one of them a member of SweepPlan
+    assert ctypes.sizeof(_lib.SeirSweepPlan) == 32 * 4
+    text = open(os.path.join(ROOT, "include", "seir_hip.h")).read()
+    body = re.search(r"typedef struct seir_sweep_plan \{(.*?)\} seir_sweep_plan;", text, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    declared = [n.strip() for line in re.findall(r"\bint32_t\s+([^;]+);", body) for n in line.split(",")]
+    bound = [f[0] for f in _lib.SeirSweepPlan._fields_]
+    assert declared[:-1] == bound[:-1] and declared[-1] == "reserved[5]" and bound[-1] == "reserved"
+    plan = open(os.path.join(ROOT, "covid19uk_amd", "csrc", "sweep_plan.h")).read()
+    members = re.search(r"struct SweepPlan \{(.*?)\n\};", plan, flags=re.S).group(1)
+    members = re.sub(r"//[^\n]*|enum \{[^}]*\};", "", members)
+    planner = {n.strip() for line in re.findall(r"\b(?:int|bool)\s+([^;]+);", members) for n in line.split(",")}
+    assert planner == set(bound[:-1]), planner ^ set(bound[:-1])
+    # the enums by the names the binding gives them, in the planner's order
+    for names, enum in ((_lib.PLAN_HMC, "FOLD, TAILFOLD, STAGE"), (_lib.PLAN_INNER, "SINGLE, LEAP, SE_CHUNK, SPLIT"),
+                        (_lib.PLAN_MOVES, "PAIRS, PAIR, SPLIT_MOVES"), (_lib.PLAN_FPEND, "F_NONE, F_PAIRS, F_RECORD, F_APPLY")):
+        assert f"enum {{ {enum} }};" in plan and len(names) == len(enum.split(","))
+    # host code only: NULL is refused without touching the GPU
+    out = _lib.SeirSweepPlan()
+    assert lib.seir_sampler_sweep_plan(None, ctypes.byref(out)) == _lib.ERR_INVALID
+    assert b"null sampler" in lib.seir_last_error()
+
+
 def test_every_key_the_burst_table_sizes_from_is_a_member_of_the_product_state():
     """The sizes of the burst table come from `ChainSampler._state()` alone: a sampler that has nothing but a record with
     everything on sizes every row, reads only members of the record, and the class has no private default to read instead."""

@@ -23,6 +23,11 @@ HOT_PATH = {
     "k_hmc_step<0,1,1>": (256, 2), "k_hmc_step<2,1,1>": (256, 2), "k_hmc_step<0,2,4>": (256, 2), "k_hmc_step<2,2,4>": (256, 2),
     "k_se<true,1,0>": (128, 4), "k_se<true,1,1>": (128, 4), "k_se<true,1,2>": (128, 4), "k_record": (128, 4),
     "k_gemm_f32": (168, 3),
+    # the instances the plan turns to beyond the BASELINE shapes (tests/test_sampler_shapes_gpu.py runs each of them): 12 day
+    # chunks with few rows; all four tile scalars (Mp > 512: 172 VGPRs, TWO workgroups per CU -- what plan_sweep is told by
+    # the driver, and what tests/test_sweep_plan.py tells it)
+    "k_leap<1,12,2,4>": (168, 3), "k_leap<2,1,2,4>": (192, 2),
+    "k_se_chunk<1,12>": (168, 3), "k_se_chunk<2,6>": (168, 3), "k_se_chunk<2,1>": (168, 3),
     # the stateless evaluation (seir_log_prob_dev) at UK-380 / SYN-2048 (96-day tiles) and NI-11 (64)
     "k_eval_all<true,96>": (128, 4), "k_eval_all<false,96>": (128, 4), "k_eval_tiles<true,96>": (128, 4),
     "k_eval_tiles<false,96>": (128, 4), "k_state_params": (128, 4), "k_finish<true>": (128, 4), "k_finish<false>": (128, 4),

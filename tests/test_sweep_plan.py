@@ -33,20 +33,29 @@ INNER = ("single", "leap", "se_chunk", "split")
 MOVES = ("pairs", "pair", "split")
 FPEND = (None, "k_move_pairs", "k_record", "k_apply_fpend")
 
-# (M, T) of the BASELINE workloads (synth.py)
+# (M, T) of the BASELINE workloads (synth.py); any other shape is named as tests.helpers.build_case names it: "slow_MxT"
 SHAPES = {"uk380": (380, 365), "ni11": (11, 32), "syn2048": (2048, 730)}
-# the chip: 256 CUs; k_leap<1,6,1,6> four workgroups per CU, the 32-row instances three (profiles/r04_kernel_resources.json);
-# k_move_pairs granted its LDS; chains XCD-local, one group, stream launches, affinity 3; bench's MCMC_CONFIG and L = 16
+# the chip: 256 CUs; workgroups per CU of k_leap<1,6,1,6> (four) and of the 32-row instances k_leap<TSM,NTC,2,4> by their TSM:
+# three with the column scalars alone, TWO with all four tile scalars (Mp > 512: 172 VGPRs) -- the compiler's figures, which
+# test_resources.HOT_PATH holds the instances to and the library asks the driver for.  k_move_pairs granted its LDS; chains
+# XCD-local, one group, stream launches, affinity 3; bench's MCMC_CONFIG and L = 16
+LEAP_OCC24, LEAP_OCC32 = 4, {1: 3, 2: 2}
 BASE = dict(nb=8, L=16, n_scans=5, record_events=1, hmc_mode=0, moves_mode=0, leap_rows=0, xcd_local=1, one_group=1,
-            use_graph=0, affinity=3, cus=256, leap_occ24=4, leap_occ32=3, pairs_lds=1)
+            use_graph=0, affinity=3, cus=256, leap_occ24=LEAP_OCC24, leap_occ32=None, pairs_lds=1)
 FIELDS = ("M", "Mp", "Tp", "ntc", "nmt", "nrb_d") + tuple(BASE)
 
 
+def shape_of(shape):
+    return SHAPES[shape] if shape in SHAPES else tuple(int(v) for v in shape.split("_")[1].split("x"))
+
+
 def inputs(shape="uk380", **kw):
-    M, T = SHAPES[shape]
+    M, T = shape_of(shape)
     Mp, Tp = (M + 63) // 64 * 64, (T + 63) // 64 * 64
     row = dict(BASE, M=M, Mp=Mp, Tp=Tp, ntc=Tp // 64, nmt=Mp // 16, nrb_d=(M + 7) // 8)
     row.update(kw)
+    if row["leap_occ32"] is None:                     # the occupancy of THIS shape's instance (chunk_ts_mode of sweep_plan.h)
+        row["leap_occ32"] = LEAP_OCC32[1 if Mp <= 512 else 2]
     return " ".join(str(int(row[f])) for f in FIELDS)
 
 
@@ -265,3 +274,112 @@ def test_baseline_instances_are_on_the_hot_path(plan, shape, nb):
     names = hot_instances(plan(shape, nb=nb), ntc=(T + 63) // 64)
     missing = [n for n in names if n not in HOT_PATH]
     assert not missing, missing
+
+
+# --- the shapes at which the plan turns to another instance of the persistent kernels ---------------------------------------
+
+# (shape, leap_rows, sweeps, the plan): tests/test_sampler_shapes_gpu.py runs every row against the oracle -- three chains,
+# its move configuration's three scans -- and holds the sampler's own seir_sampler_sweep_plan to the same members
+_LEAP12 = dict(hmc="fold", inner="leap", ts_mode=1, leap_nst=2, leap_nmt=12, nch=12, moves="pairs")
+SAMPLER_SHAPE_CASES = [
+    # k_leap<1,6,2,4> by default (Mp no multiple of 24); no padding in rows or days
+    ("slow_64x384", 0, 3, dict(hmc="fold", inner="leap", ts_mode=1, leap_nst=2, leap_nmt=4, nch=6)),
+    # ... one live row in the second 64-row block
+    ("slow_65x330", 0, 3, dict(hmc="fold", inner="leap", ts_mode=1, leap_nst=2, leap_nmt=8)),
+    # k_leap<1,6,1,6> at Mp = 192: two of eight 24-row tiles are all padding, one live day in chunk 6; and in 32-row tiles
+    ("slow_130x321", 0, 3, dict(hmc="fold", inner="leap", ts_mode=1, leap_nst=1, leap_nmt=8)),
+    ("slow_130x321", 32, 3, dict(hmc="fold", inner="leap", ts_mode=1, leap_nst=2, leap_nmt=12)),
+    # 24-row tiles with no padding anywhere
+    ("slow_192x384", 0, 3, dict(hmc="fold", inner="leap", leap_nst=1, leap_nmt=8)),
+    ("slow_192x384", 32, 3, dict(hmc="fold", inner="leap", leap_nst=2, leap_nmt=12)),
+    # k_leap<1,12,2,4>: one live day in chunk 12 and one live row in block 3; the largest shape it fits, no padding
+    ("slow_129x705", 0, 2, _LEAP12),
+    ("slow_192x768", 0, 2, _LEAP12),
+    # one row past: k_se_chunk<1,12> + k_hmc_final<12>
+    ("slow_193x705", 0, 2, dict(hmc="tailfold", inner="se_chunk", ts_mode=1, nch=12)),
+    # k_se_chunk<2,6> + k_hmc_final<6>
+    ("slow_513x321", 0, 2, dict(hmc="tailfold", inner="se_chunk", ts_mode=2, nch=6, moves="pairs", nband=17)),
+    # k_leap<2,1,2,4>; T is exactly one chunk
+    ("slow_577x64", 0, 3, dict(hmc="fold", inner="leap", ts_mode=2, leap_nst=2, leap_nmt=40)),
+    # nmt at its limit; event updates without band workgroups
+    ("slow_1024x33", 0, 3, dict(hmc="fold", inner="leap", ts_mode=2, leap_nmt=64, moves="pair", nband=0)),
+    # one row past: k_se_chunk<2,1> + k_hmc_final<1>
+    ("slow_1025x33", 0, 3, dict(hmc="tailfold", inner="se_chunk", ts_mode=2)),
+]
+SHAPE_IDS = [f"{name}-rows{rows}" if rows else name for name, rows, _, _ in SAMPLER_SHAPE_CASES]
+
+
+def shape_plan(plan, name, rows, nb=3):
+    return plan(name, nb=nb, n_scans=3, leap_rows=rows)
+
+
+@pytest.mark.parametrize("name,rows,n,want", SAMPLER_SHAPE_CASES, ids=SHAPE_IDS)
+def test_sampler_shape_cases(plan, name, rows, n, want):
+    p = shape_plan(plan, name, rows)
+    check(p, **want)
+    check(p, nbv=8, nlive=3, leap_launches=1)
+
+
+def test_sampler_shape_cases_run_every_instance_the_plan_turns_to(plan):
+    ran = set()
+    for name, rows, _, _ in SAMPLER_SHAPE_CASES:
+        p, ntc = shape_plan(plan, name, rows), (shape_of(name)[1] + 63) // 64
+        ran.update(hot_instances(p, ntc) + ([f"k_hmc_final<{ntc}>"] if p["hmc"] == "tailfold" else []))
+    want = {"k_leap<1,12,2,4>", "k_se_chunk<1,12>", "k_hmc_final<12>", "k_se_chunk<2,6>", "k_hmc_final<6>", "k_se_chunk<2,1>",
+            "k_hmc_final<1>", "k_leap<2,1,2,4>", "k_leap<1,6,1,6>", "k_leap<1,6,2,4>"}
+    assert want <= ran, want - ran
+    # ... and the launches whose workgroups must all be resident are held to their occupancy
+    missing = [k for k in want if k not in HOT_PATH and not k.startswith("k_hmc_final")]
+    assert not missing, missing
+
+
+def test_slow_129x705_x16_two_launches_of_8(plan):
+    check(shape_plan(plan, "slow_129x705", 0, nb=16), hmc="fold", leap_nst=2, leap_nmt=12, leap_nbv=8, leap_launches=2)
+
+
+def test_the_edges_of_the_shape_cases(plan):
+    # one row or one day to either side of where an instance ends
+    check(shape_plan(plan, "slow_192x769", 0), hmc="stage", inner="split")          # 13 day chunks: no roles
+    check(shape_plan(plan, "slow_192x704", 0), hmc="stage", inner="split")          # 11
+    check(shape_plan(plan, "slow_512x321", 0), hmc="tailfold", ts_mode=1)
+    check(shape_plan(plan, "slow_576x64", 0), hmc="fold", ts_mode=2, leap_nmt=36)
+    check(shape_plan(plan, "slow_512x64", 0), hmc="fold", ts_mode=1, leap_nmt=32)
+    check(shape_plan(plan, "slow_1024x65", 0), hmc="stage", inner="split")          # 2 day chunks
+
+
+def test_two_workgroups_per_cu_decide_at_sixteen_wide_chains(plan):
+    """Where the occupancy of the ts_mode-2 instance turns the plan: 960 x 33, sixteen chains are (30 + 16) x 16 = 736
+    workgroups -- one launch at three per CU, which the instance does not reach; at its two, two launches of 8."""
+    check(plan("slow_960x33", nb=16), hmc="fold", ts_mode=2, leap_nbv=8, leap_launches=2)
+    check(plan("slow_960x33", nb=16, leap_occ32=3), hmc="fold", ts_mode=2, leap_nbv=16, leap_launches=1)
+
+
+def test_all_four_tile_scalars_never_take_k_leap_with_6_or_12_day_chunks(plan):
+    """k_leap<2,6,2,4> and k_leap<2,12,2,4> are compiled and unreachable on 256 CUs: the smallest shape they would serve
+    (Mp = 576, six chunks) is (108 + 15) x 8 = 984 workgroups against 2 x 256 places."""
+    for M in range(64, 1025, 64):
+        for ntc in (6, 12):
+            for nb in (1, 8, 16):
+                p = plan(f"slow_{M}x{64 * ntc}", nb=nb)
+                assert p["ts_mode"] == (1 if M <= 512 else 2), (M, ntc, nb)
+                if p["ts_mode"] == 2:
+                    assert p["inner"] != "leap" and p["hmc"] == "tailfold", (M, ntc, nb, p)
+                else:
+                    assert p["hmc"] in ("fold", "tailfold"), (M, ntc, nb, p)
+
+
+def test_the_occupancies_fed_to_the_plan_are_the_compilers():
+    """LEAP_OCC24 / LEAP_OCC32 against the resource remarks of this build (256-thread workgroups: one wave per SIMD each,
+    so waves per SIMD are workgroups per CU), and against what test_resources holds the instances to."""
+    import json
+    entry.build()
+    res = json.load(open(entry.RESOURCES))
+    assert res["k_leap<1,6,1,6>"]["occupancy_waves_per_simd"] == LEAP_OCC24 == HOT_PATH["k_leap<1,6,1,6>"][1]
+    seen = 0
+    for name, r in res.items():
+        if name.startswith("k_leap<") and name.endswith(",2,4>"):
+            ts = int(name[len("k_leap<")])
+            assert r["occupancy_waves_per_simd"] == LEAP_OCC32[ts], (name, r)
+            assert HOT_PATH.get(name, (0, LEAP_OCC32[ts]))[1] == LEAP_OCC32[ts], name
+            seen += 1
+    assert seen == 6
