@@ -1,9 +1,8 @@
 """The compiler's account of the library's kernels: parser of `hipcc -Rpass-analysis=kernel-resource-usage` remarks
-(registers, scratch, spills, LDS, occupancy per kernel).  `__graft_entry__.build()` keeps the result next to the library as
-kernel_resources.json (and, for the kernels added since that file's set was pinned, added_kernel_resources.json; for the
-self-test kernels of the device math, selftest_kernel_resources.json; for the kernels of the within/between shares,
-wb_kernel_resources.json; for the kernels of the R_t intervals, rtq_kernel_resources.json);
-tests/test_resources.py holds the hot-path instances to it; tools/dev/resources.py prints it."""
+(registers, scratch, spills, LDS, occupancy per kernel), and the table of which product owns which kernel.
+`__graft_entry__.build()` keeps the account of every kernel next to the library as kernel_resources.json (the tracked copy:
+profiles/kernel_resources.json); `owned` takes one owner's kernels out of it.  tests/test_resources.py holds the fresh
+account to the tracked copy and the hot-path instances to their budgets; tools/dev/resources.py prints it."""
 import re
 
 
@@ -46,3 +45,26 @@ def parse(text):
             ent[key] = int(m.group(1)) if m else None
         out[name] = ent
     return out
+
+
+BASE = "base"
+# owner -> the kernels it brought, by base name (templates: every instance).  Every kernel that no owner names belongs to
+# BASE: the sampler's kernels and the products up to the in-sample check
+OWNERS = {
+    "forecast_quantiles": ("k_forecast_keep", "k_order_stats"),   # forecast_kernels.h, order_stats_kernels.h
+    "selftest": ("k_selftest_fn", "k_selftest_delta", "k_selftest_wave"),   # the device math's self-tests (selftest_kernels.h)
+    "wb": ("k_wb_prepare", "k_wb_trace", "k_wb_finish"),          # the within/between pressure shares (wb_kernels.h)
+    "rt_quantiles": ("k_rt_trace_keep", "k_order_stats_f64"),     # the R_t intervals (rt_keep_kernels.h, order_stats_kernels.h)
+    "groups": ("k_group_sums",),                                  # the region totals (group_kernels.h)
+    "group_curves": ("k_group_wsums", "k_rt_trace_cells", "k_rt_cells_from_keep", "k_wb_trace_cells"),   # group_curve_kernels.h
+    "ngm": ("k_ngm_rows",),                                       # the group next-generation matrix (ngm_kernels.h)
+    "replay": ("k_trace_load", "k_trace_load_theta"),             # stored draws into trace slots (trace_load_kernels.h)
+}
+
+
+def owned(res, owner):
+    """The kernels of `res` (an account: instance -> figures) that belong to `owner`: a key of OWNERS, or BASE."""
+    if owner == BASE:
+        named = {b for names in OWNERS.values() for b in names}
+        return {k: v for k, v in res.items() if k.split("<")[0] not in named}
+    return {k: v for k, v in res.items() if k.split("<")[0] in OWNERS[owner]}

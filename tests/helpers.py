@@ -57,6 +57,18 @@ def build_case(name, seed=20210101, alpha_t_sd=0.0):
                 k=oracle_constants(cov, init))
 
 
+def kernel_account(owner=None):
+    """The compiler's account of a fresh build (`entry.RESOURCES`): of every kernel, or of `owner`'s
+    (covid19uk_amd/kernel_resources.py: a key of OWNERS, or BASE)."""
+    import json
+
+    import __graft_entry__ as entry
+    from covid19uk_amd import kernel_resources
+    entry.build()
+    res = json.load(open(entry.RESOURCES))
+    return res if owner is None else kernel_resources.owned(res, owner)
+
+
 from oracle import c_binding
 
 

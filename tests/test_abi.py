@@ -11,6 +11,7 @@ import pytest
 import __graft_entry__ as entry
 from covid19uk_amd import _lib, model_spec as ms, synth
 from oracle import seir_oracle as so
+from tests import abi_lib
 from tests import helpers as H
 
 ROOT = H.ROOT
@@ -36,6 +37,21 @@ def test_header_symbols_are_exported(lib):
     assert sorted(declared) == _lib.exported_symbols()
 
 
+def test_every_prototype_is_bound_with_the_headers_types(lib):
+    """All of them, not only those a product's test pins (tests/abi_lib.py: check_symbols): the return type is the header's;
+    an argument is the header's type, or a void pointer (to a void pointer) where the header declares a pointer -- the binding
+    passes device pointers and handles that way on purpose."""
+    declared = abi_lib.prototypes()
+    assert sorted(declared) == _declared_symbols() and len(declared) == len(_lib._SIGNATURES)
+    opaque = (ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p))
+    for name, (ret, params) in declared.items():
+        fn = getattr(lib, name)
+        assert fn.restype is abi_lib.CTYPE[ret], (name, ret, fn.restype)
+        assert len(fn.argtypes) == len(params), (name, params, fn.argtypes)
+        for p, got in zip(params, fn.argtypes):
+            assert got is abi_lib.CTYPE[abi_lib.c_type(p)] or (got in opaque and ("*" in p or "[" in p)), (name, p, got)
+
+
 def test_abi_version_4_and_the_handoff_status(lib):
     text = open(os.path.join(ROOT, "include", "seir_hip.h")).read()
     declared = int(re.search(r"#define\s+SEIR_ABI_VERSION\s+(\d+)", text).group(1))
@@ -59,6 +75,8 @@ def test_sampler_desc_struct_layout_matches_header():
 def test_desc_struct_layout_matches_header():
     # 4 int32, 6 pointers, double, pointer, 3 doubles
     assert ctypes.sizeof(_lib.SeirDesc) == 16 + 6 * 8 + 8 + 8 + 3 * 8
+    # seir_sim_desc: 4 int32, uint64 seed, 7 pointers
+    assert ctypes.sizeof(_lib.SeirSimDesc) == 4 * 4 + 8 + 7 * 8
 
 
 def test_product_state_struct_layout_matches_header():

@@ -20,8 +20,10 @@ from covid19uk_amd import _lib, hdf5io, model_spec
 from covid19uk_amd.inference import inference as inf
 from covid19uk_amd.posterior import predict
 from covid19uk_amd.sampler import CHECK_KEYS, CheckSummary, Summary, mid_p
+from tests import helpers as H
+from tests.abi_lib import check_symbols
 from tests.test_rt_device_host import Recorder, RtStub
-from tests.test_summary_host import CFG, CTYPE, StubSampler, _read
+from tests.test_summary_host import CFG, StubSampler, _read
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MARG3 = "int64_t *check_by_day, int64_t *check_by_location, int64_t *check_state_by_day"
@@ -34,32 +36,12 @@ NEW = {
     "seir_sampler_read_check_counts": "seir_sampler *s, int32_t *obs, uint32_t *lt, uint32_t *eq, uint32_t *loc_lt, "
                                       "uint32_t *loc_eq, uint32_t *day_lt, uint32_t *day_eq, uint32_t *all_lt, uint32_t *all_eq",
 }
-CTYPES = dict(CTYPE, **{"const double *": ctypes.POINTER(ctypes.c_double), "uint64_t": ctypes.c_uint64,
-                        "uint32_t *": ctypes.POINTER(ctypes.c_uint32)})
 
 
 # ---- 1. the symbols ------------------------------------------------------------------------------------------------------
 def test_new_symbols_are_declared_exported_and_bound_with_the_headers_types():
-    entry.build()
-    lib = _lib.load()
+    lib = check_symbols(NEW)
     raw = open(os.path.join(ROOT, "include", "seir_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    for name, params in NEW.items():
-        m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-        assert m, f"{name} is not declared in include/seir_hip.h"
-        declared = " ".join(m.group(1).split())
-        assert declared == params, (name, declared)
-        assert name in _lib.exported_symbols()
-        fn = getattr(lib, name)                              # exported by the library
-        want = []
-        for p in declared.split(","):
-            ty = p.strip().rsplit(" ", 1)[0] + (" *" if "*" in p else "")
-            want.append(CTYPES[ty.replace("* *", "*").strip()])
-        assert fn.restype is ctypes.c_int and list(fn.argtypes) == want, (name, fn.argtypes)
-    # new symbols only: the ABI version and the descriptor are the parent's
-    assert lib.seir_abi_version() == 4 and _lib.ABI_VERSION == 4
-    assert re.search(r"#define SEIR_ABI_VERSION 4\b", raw)
-    assert ctypes.sizeof(_lib.SeirSamplerDesc) == 12 * 4 + 8 + 8 * 4
     assert int(re.search(r"#define SEIR_CHECK_MAX_DAYS (\d+)", raw).group(1)) == _lib.CHECK_MAX_DAYS == 128
     # a null sampler is refused before anything touches a device
     one = (ctypes.c_double * 1)(0.0)
@@ -466,8 +448,7 @@ def test_a_burst_is_checked_behind_its_summary_forecast_and_rt_and_not_at_all_wh
 
 # ---- 8. the compiler's account of the new kernels -------------------------------------------------------------------------
 def test_the_new_kernels_have_no_scratch_and_fit_the_lds_and_the_old_ones_are_what_they_were():
-    entry.build()
-    res = json.load(open(entry.RESOURCES))
+    res = H.kernel_account("base")
     new = ["k_check_prepare<0>", "k_check_prepare<1>", "k_check_compare<0>", "k_check_compare<1>", "k_check_totals"]
     assert all(k in res for k in new), sorted(res)
     for k in new:

@@ -4,11 +4,9 @@ the batch update of covid19uk_amd/csrc/summary_update.h compiled as plain C++ ag
 pooling tool on files written by `Posterior`, the configuration, and the compiler's account of the new kernel instances.
 
 `accumulate` below is the NumPy restatement of the accumulators' definitions that the GPU tests compare the device with."""
-import ctypes
 import json
 import math
 import os
-import re
 import shutil
 import subprocess
 import warnings
@@ -21,7 +19,9 @@ import __graft_entry__ as entry
 from covid19uk_amd import _lib, hdf5io
 from covid19uk_amd.inference import inference as inf
 from covid19uk_amd.posterior import diagnostics as dm
-from tests.test_summary_host import CFG, CTYPE, StubSampler, _read
+from tests import helpers as H
+from tests.abi_lib import check_symbols
+from tests.test_summary_host import CFG, StubSampler, _read
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {
@@ -62,25 +62,7 @@ def same_accumulators(got, want):
 
 # ---- 1. the symbols ------------------------------------------------------------------------------------------------------
 def test_new_symbols_are_declared_exported_and_bound_with_the_headers_types():
-    entry.build()
-    lib = _lib.load()
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "seir_hip.h")).read(), flags=re.S)
-    for name, params in NEW.items():
-        m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-        assert m, f"{name} is not declared in include/seir_hip.h"
-        declared = " ".join(m.group(1).split())
-        assert declared == params, (name, declared)
-        assert name in _lib.exported_symbols()
-        fn = getattr(lib, name)                              # exported by the library
-        want = []
-        for p in declared.split(","):
-            ty = p.strip().rsplit(" ", 1)[0] + (" *" if "*" in p else "")
-            want.append(CTYPE[ty.replace("* *", "*").strip()])
-        assert fn.restype is ctypes.c_int and list(fn.argtypes) == want, (name, fn.argtypes)
-    # switched on by a call of its own: the ABI version and the descriptor are the parent's
-    assert lib.seir_abi_version() == 4 and _lib.ABI_VERSION == 4
-    assert re.search(r"#define SEIR_ABI_VERSION 4\b", open(os.path.join(ROOT, "include", "seir_hip.h")).read())
-    assert ctypes.sizeof(_lib.SeirSamplerDesc) == 12 * 4 + 8 + 8 * 4
+    lib = check_symbols(NEW)
     # a null sampler is refused before anything touches a device
     assert lib.seir_sampler_diag_reset(None, 5) == _lib.ERR_INVALID
     assert lib.seir_sampler_diag_mark(None, 0) == _lib.ERR_INVALID
@@ -599,8 +581,7 @@ def test_on_marks_the_halves_and_adds_the_group(tmp_path, nb, summaries, overlap
 
 # ---- 7. the compiler's account of the new instances ---------------------------------------------------------------------
 def test_the_diag_instances_have_no_scratch_and_the_others_are_the_parents():
-    entry.build()
-    res = json.load(open(entry.RESOURCES))
+    res = H.kernel_account("base")
     parent = json.load(open(os.path.join(ROOT, "profiles", "r07_kernel_resources.json")))
     for ev16 in (0, 1):
         r = res[f"k_summarize<{ev16},1>"]

@@ -9,12 +9,13 @@ import re
 import numpy as np
 import pytest
 
-import __graft_entry__ as entry
 from covid19uk_amd import _lib, hdf5io, model_spec
 from covid19uk_amd.inference import inference as inf
 from covid19uk_amd.posterior import predict
 from covid19uk_amd.sampler import FORECAST_KEYS, Summary, forecast_draw_id
-from tests.test_summary_host import CFG, CTYPE, StubSampler, _read
+from tests import helpers as H
+from tests.abi_lib import check_symbols
+from tests.test_summary_host import CFG, StubSampler, _read
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MARG3 = "int64_t *forecast_by_day, int64_t *forecast_by_location, int64_t *forecast_state_by_day"
@@ -25,31 +26,12 @@ NEW = {
     "seir_sampler_read_forecast_marginals_async": "seir_sampler *s, int32_t first, int32_t count, " + MARG3,
     "seir_sampler_read_forecast": "seir_sampler *s, uint64_t *count, int32_t *ref, int64_t *sum, uint64_t *sumsq",
 }
-CTYPES = dict(CTYPE, **{"const double *": ctypes.POINTER(ctypes.c_double), "uint64_t": ctypes.c_uint64})
 
 
 # ---- 1. the symbols ------------------------------------------------------------------------------------------------------
 def test_new_symbols_are_declared_exported_and_bound_with_the_headers_types():
-    entry.build()
-    lib = _lib.load()
+    lib = check_symbols(NEW)
     raw = open(os.path.join(ROOT, "include", "seir_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    for name, params in NEW.items():
-        m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-        assert m, f"{name} is not declared in include/seir_hip.h"
-        declared = " ".join(m.group(1).split())
-        assert declared == params, (name, declared)
-        assert name in _lib.exported_symbols()
-        fn = getattr(lib, name)                              # exported by the library
-        want = []
-        for p in declared.split(","):
-            ty = p.strip().rsplit(" ", 1)[0] + (" *" if "*" in p else "")
-            want.append(CTYPES[ty.replace("* *", "*").strip()])
-        assert fn.restype is ctypes.c_int and list(fn.argtypes) == want, (name, fn.argtypes)
-    # new symbols only: the ABI version and the descriptor are the parent's
-    assert lib.seir_abi_version() == 4 and _lib.ABI_VERSION == 4
-    assert re.search(r"#define SEIR_ABI_VERSION 4\b", raw)
-    assert ctypes.sizeof(_lib.SeirSamplerDesc) == 12 * 4 + 8 + 8 * 4
     assert int(re.search(r"#define SEIR_FORECAST_MAX_H (\d+)", raw).group(1)) == _lib.FORECAST_MAX_H == 128
     # a null sampler is refused before anything touches a device
     one = (ctypes.c_double * 1)(0.0)
@@ -270,8 +252,7 @@ def test_on_resets_once_forecasts_every_burst_and_writes_the_group(tmp_path, sum
 
 # ---- 5. the compiler's account of the new kernels -------------------------------------------------------------------------
 def test_the_forecast_kernels_fit_and_contraction_and_fold_have_no_scratch():
-    entry.build()
-    res = json.load(open(entry.RESOURCES))
+    res = H.kernel_account("base")
     new = ["k_forecast_prepare<0>", "k_forecast_prepare<1>", "k_forecast_day", "k_forecast_fold", "k_forecast_finish"]
     assert all(k in res for k in new), sorted(res)
     for k in ("k_gemm<64>", "k_forecast_fold", "k_forecast_finish", "k_forecast_prepare<0>", "k_forecast_prepare<1>"):

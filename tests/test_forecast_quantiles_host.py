@@ -21,6 +21,8 @@ from covid19uk_amd import _lib, hdf5io
 from covid19uk_amd.inference import inference as inf
 from covid19uk_amd.posterior import quantiles as Q
 from covid19uk_amd.sampler import FORECAST_QUANTILE_PLANES, ChainSampler
+from tests import helpers as H
+from tests.abi_lib import check_symbols
 from tests.test_forecast_host import ForecastStub
 from tests.test_summary_host import CFG, _read
 
@@ -31,35 +33,12 @@ NEW = {
     "seir_order_stats": "seir_ctx *ctx, const int32_t *values, int64_t cells, int32_t segs, int64_t seg_len, "
                         "int64_t seg_stride, int64_t cell_stride, const int64_t *ranks, int32_t R, int32_t *out",
 }
-CTYPES = {"seir_sampler *": ctypes.c_void_p, "seir_ctx *": ctypes.c_void_p, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
-          "const int64_t *": ctypes.POINTER(ctypes.c_int64), "int32_t *": ctypes.POINTER(ctypes.c_int32),
-          "const int32_t *": ctypes.POINTER(ctypes.c_int32)}
 
 
 # ---- 1. the symbols ------------------------------------------------------------------------------------------------------
 def test_new_symbols_are_declared_exported_and_bound_with_the_headers_types():
-    entry.build()
-    lib = _lib.load()
+    lib = check_symbols(NEW)
     raw = open(os.path.join(ROOT, "include", "seir_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    for name, params in NEW.items():
-        m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-        assert m, f"{name} is not declared in include/seir_hip.h"
-        declared = " ".join(m.group(1).split())
-        assert declared == params, (name, declared)
-        assert name in _lib.exported_symbols()
-        fn = getattr(lib, name)                              # exported by the library
-        want = []
-        for p in declared.split(","):
-            ty = p.strip().rsplit(" ", 1)[0] + (" *" if "*" in p else "")
-            want.append(CTYPES[ty.replace("* *", "*").strip()])
-        assert fn.restype is ctypes.c_int and list(fn.argtypes) == want, (name, fn.argtypes)
-    # new symbols only: the ABI version and the descriptors are the parent's
-    assert lib.seir_abi_version() == 4 and _lib.ABI_VERSION == 4
-    assert re.search(r"#define SEIR_ABI_VERSION 4\b", raw)
-    assert ctypes.sizeof(_lib.SeirSamplerDesc) == 12 * 4 + 8 + 8 * 4
-    assert ctypes.sizeof(_lib.SeirDesc) == 4 * 4 + 6 * 8 + 8 + 8 + 3 * 8
-    assert ctypes.sizeof(_lib.SeirSimDesc) == 4 * 4 + 8 + 7 * 8
     assert int(re.search(r"#define SEIR_ORDER_STATS_MAX_RANKS (\d+)", raw).group(1)) == _lib.ORDER_STATS_MAX_RANKS == 16
     assert 2 * Q.MAX_PROBS == _lib.ORDER_STATS_MAX_RANKS
     # a null sampler / context is refused before anything touches a device
@@ -366,16 +345,11 @@ def test_on_keeps_once_behind_the_reset_asks_twice_at_the_end_and_writes_the_dat
 
 # ---- 6. the compiler's account of the new kernels --------------------------------------------------------------------------
 def test_the_new_kernels_have_no_scratch_and_the_others_are_what_they_were():
-    """build() keeps the account of the kernels this product adds in a file of its own (`entry.RESOURCES_ADDED`), because
-    kernel_resources.json is held to the set of kernels of the round before (tests/test_check_host.py); the three files
-    (the third: `entry.RESOURCES_SELFTEST`, the self-test kernels of the device math) together are the compiler's account
-    of the library."""
-    entry.build()
-    res = json.load(open(entry.RESOURCES))
-    added = json.load(open(entry.RESOURCES_ADDED))
+    """The compiler's account of the kernels this product owns (covid19uk_amd/kernel_resources.py), and of the parent's."""
+    res = H.kernel_account("base")
+    added = H.kernel_account("forecast_quantiles")
     new = ["k_forecast_keep", "k_order_stats<1>", "k_order_stats<4>"]
     assert sorted(added) == new and not set(added) & set(res)
-    assert entry.split_resources(dict(res, **added)) == (res, added)
     for k in new:
         assert added[k]["scratch_bytes_per_lane"] == 0 and added[k]["vgpr_spill"] == 0 and added[k]["sgpr_spill"] == 0, (k, added[k])
     # k_forecast_keep: the padded tile [rows 2][planes 3][days 64][draws 32 + 1] and the carries [2][32][2], int32
@@ -385,12 +359,6 @@ def test_the_new_kernels_have_no_scratch_and_the_others_are_what_they_were():
         assert 16 * 256 * 4 <= added[k]["lds_bytes_per_block"] <= 16 * 256 * 4 + 4 * 16 * 4 + 16, (k, added[k])
     # three workgroups of the keep kernel fit a CU's 160 KiB
     assert 3 * added["k_forecast_keep"]["lds_bytes_per_block"] <= 160 * 1024
-    # the committed copy of this round lists the same kernels
-    doc = json.load(open(os.path.join(ROOT, "profiles", "r13_added_kernels.json")))
-    assert set(doc) == set(added)
-    for k in new:
-        assert doc[k]["scratch_bytes_per_lane"] == added[k]["scratch_bytes_per_lane"] and \
-            doc[k]["lds_bytes_per_block"] == added[k]["lds_bytes_per_block"], k
     # every kernel of the parent is in the library as it was
     parent = json.load(open(os.path.join(ROOT, "profiles", "r12_kernel_resources.json")))
     assert set(parent) <= set(res)

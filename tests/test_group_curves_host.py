@@ -2,20 +2,19 @@
 definition of a group sum (`posterior.groups.weighted_sum_rows`) held three ways, the refusals before any GPU call,
 run_mcmc's calls and datasets with a stub sampler, and the compiler's account of the new kernels."""
 import ctypes
-import json
 import math
 import os
-import re
 
 import numpy as np
 import pytest
 
-import __graft_entry__ as entry
 from covid19uk_amd import _lib, hdf5io, synth
 from covid19uk_amd.inference import inference as inf
 from covid19uk_amd.posterior import groups as G
 from covid19uk_amd.sampler import GROUP_CURVE_KEYS, GROUP_KEYS, GROUP_SOURCES, ChainSampler, PinnedTrace, Trace
 from covid19uk_amd.seir import SeirModel
+from tests import helpers as H
+from tests.abi_lib import check_symbols
 from tests.test_rt_quantiles_host import RtqStub
 from tests.test_summary_host import CFG, _read
 from tests.test_wb_host import WbStub
@@ -31,35 +30,11 @@ NEW = {
     "seir_group_wsums": "seir_ctx *ctx, const double *v, int64_t nd, int32_t L, int32_t M, int32_t G, const int32_t *offsets, "
                         "const int32_t *members, const double *weights, double *out",
 }
-CTYPES = {"seir_sampler *": ctypes.c_void_p, "seir_ctx *": ctypes.c_void_p, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
-          "double *": ctypes.POINTER(ctypes.c_double), "const double *": ctypes.POINTER(ctypes.c_double),
-          "const int32_t *": ctypes.POINTER(ctypes.c_int32)}
 
 
 # ---- 1. the symbols ------------------------------------------------------------------------------------------------------
 def test_new_symbols_are_declared_exported_and_bound_with_the_headers_types():
-    entry.build()
-    lib = _lib.load()
-    raw = open(os.path.join(ROOT, "include", "seir_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    for name, params in NEW.items():
-        m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-        assert m, f"{name} is not declared in include/seir_hip.h"
-        declared = " ".join(m.group(1).split())
-        assert declared == params, (name, declared)
-        assert name in _lib.exported_symbols()
-        fn = getattr(lib, name)
-        want = []
-        for p in declared.split(","):
-            ty = p.strip().rsplit(" ", 1)[0] + (" *" if "*" in p else "")
-            want.append(CTYPES[ty.replace("* *", "*").strip()])
-        assert fn.restype is ctypes.c_int and list(fn.argtypes) == want, (name, fn.argtypes)
-    # new symbols only: the ABI version and the descriptors are the parent's
-    assert lib.seir_abi_version() == 4 and _lib.ABI_VERSION == 4
-    assert re.search(r"#define SEIR_ABI_VERSION 4\b", raw)
-    assert ctypes.sizeof(_lib.SeirSamplerDesc) == 12 * 4 + 8 + 8 * 4
-    assert ctypes.sizeof(_lib.SeirDesc) == 4 * 4 + 6 * 8 + 8 + 8 + 3 * 8
-    assert ctypes.sizeof(_lib.SeirSimDesc) == 4 * 4 + 8 + 7 * 8
+    lib = check_symbols(NEW)
     # a null sampler / context is refused before anything touches a device
     one = (ctypes.c_double * 2)(0.0, 1.0)
     idx = (ctypes.c_int32 * 2)(0, 1)
@@ -465,33 +440,20 @@ def test_the_switches_are_set_once_behind_the_table_and_the_datasets_are_written
 
 
 # ---- 5. the compiler's account of the new kernels ---------------------------------------------------------------------------
-def test_the_new_kernels_have_an_account_of_their_own_and_the_other_six_are_the_parents():
-    entry.build()
-    res = json.load(open(entry.RESOURCES_GROUP_CURVES))
+def test_the_new_kernels_are_these_instances_with_their_parents_occupancy_behind_everything_else():
+    res = H.kernel_account("group_curves")
     new = ["k_group_wsums<0>", "k_group_wsums<1>", "k_rt_cells_from_keep", "k_rt_trace_cells<4>", "k_wb_trace_cells<4>"]
     assert sorted(res) == new, sorted(res)
-    assert res == json.load(open(os.path.join(ROOT, "profiles", "r18_group_curves_kernels.json")))
     for k in new:
         assert res[k]["scratch_bytes_per_lane"] == 0 and res[k]["vgpr_spill"] == 0 and res[k]["sgpr_spill"] == 0, (k, res[k])
         assert res[k]["lds_bytes_per_block"] == 0, (k, res[k])   # k_group_wsums shares nothing between its waves; the two
         #                                                          trace kernels' LDS is dynamic, as their parents'
-    base = json.load(open(entry.RESOURCES))
-    wb = json.load(open(entry.RESOURCES_WB))
+    base = H.kernel_account("base")
+    wb = H.kernel_account("wb")
     # the heavy kernels keep their parents' occupancy
     assert res["k_rt_trace_cells<4>"]["occupancy_waves_per_simd"] == base["k_rt_trace<4>"]["occupancy_waves_per_simd"] == 5
     assert res["k_wb_trace_cells<4>"]["occupancy_waves_per_simd"] == wb["k_wb_trace<4>"]["occupancy_waves_per_simd"]
     assert res["k_group_wsums<0>"]["occupancy_waves_per_simd"] == res["k_group_wsums<1>"]["occupancy_waves_per_simd"] == 8
-    for path, committed in ((entry.RESOURCES, "r13_kernel_resources.json"), (entry.RESOURCES_ADDED, "r13_added_kernels.json"),
-                            (entry.RESOURCES_SELFTEST, "r14_selftest_kernels.json"), (entry.RESOURCES_WB, "r15_wb_kernels.json"),
-                            (entry.RESOURCES_RTQ, "r16_rtq_kernels.json"), (entry.RESOURCES_GROUPS, "r17_groups_kernels.json")):
-        got = json.load(open(path))
-        assert not any(k.split("<")[0] in entry.GROUP_CURVES_KERNELS for k in got)
-        assert got == json.load(open(os.path.join(ROOT, "profiles", committed))), committed
-    whole = dict(base, **json.load(open(entry.RESOURCES_ADDED)), **res, **json.load(open(entry.RESOURCES_SELFTEST)), **wb,
-                 **json.load(open(entry.RESOURCES_RTQ)), **json.load(open(entry.RESOURCES_GROUPS)))
-    assert entry.split_resources(whole) == (base, json.load(open(entry.RESOURCES_ADDED)))
-    assert entry.group_curves_resources(whole) == res
-    assert entry.groups_resources(whole) == json.load(open(entry.RESOURCES_GROUPS))
     # the existing kernels' text is what it was: the new file restates the loops and is included behind everything else
     hip = open(os.path.join(ROOT, "covid19uk_amd", "csrc", "seir_hip.hip")).read()
     assert hip.count('#include "group_curve_kernels.h"') == 1

@@ -2,7 +2,6 @@
 be said about the device's half without a GPU: the entry points' declarations and bindings and the compiler's account of
 k_group_sums.  The device's results are held to NumPy and to `SeirModel.simulate` in tests/test_groups_gpu.py."""
 import ctypes
-import json
 import os
 import re
 from fractions import Fraction
@@ -10,12 +9,13 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
-import __graft_entry__ as entry
 from covid19uk_amd import _lib, hdf5io, synth
 from covid19uk_amd.inference import inference as inf
 from covid19uk_amd.posterior import groups as G
 from covid19uk_amd.sampler import GROUP_KEYS, GROUP_SOURCES, ChainSampler
 from covid19uk_amd.seir import SeirModel
+from tests import helpers as H
+from tests.abi_lib import check_symbols
 from tests.test_check_host import CheckStub
 from tests.test_summary_host import CFG, _read
 
@@ -29,35 +29,13 @@ NEW = {
     "seir_group_sums": "seir_ctx *ctx, const int32_t *events, int64_t n, int32_t M, int32_t L, int32_t G, "
                        "const int32_t *offsets, const int32_t *members, int64_t *out",
 }
-CTYPES = {"seir_sampler *": ctypes.c_void_p, "seir_ctx *": ctypes.c_void_p, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
-          "int64_t *": ctypes.POINTER(ctypes.c_int64), "const int32_t *": ctypes.POINTER(ctypes.c_int32)}
 
 
 # ---- 1. the symbols ------------------------------------------------------------------------------------------------------
 def test_new_symbols_are_declared_exported_and_bound_with_the_headers_types():
-    entry.build()
-    lib = _lib.load()
+    lib = check_symbols(NEW)
     raw = open(os.path.join(ROOT, "include", "seir_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    for name, params in NEW.items():
-        m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-        assert m, f"{name} is not declared in include/seir_hip.h"
-        declared = " ".join(m.group(1).split())
-        assert declared == params, (name, declared)
-        assert name in _lib.exported_symbols()
-        fn = getattr(lib, name)                              # exported by the library
-        want = []
-        for p in declared.split(","):
-            ty = p.strip().rsplit(" ", 1)[0] + (" *" if "*" in p else "")
-            want.append(CTYPES[ty.replace("* *", "*").strip()])
-        assert fn.restype is ctypes.c_int and list(fn.argtypes) == want, (name, fn.argtypes)
-    # new symbols only: the ABI version and the descriptors are the parent's
-    assert lib.seir_abi_version() == 4 and _lib.ABI_VERSION == 4
-    assert re.search(r"#define SEIR_ABI_VERSION 4\b", raw)
     assert re.search(r"#define SEIR_GROUPS_MAX 256\b", raw) and _lib.GROUPS_MAX == G.MAX_GROUPS == 256
-    assert ctypes.sizeof(_lib.SeirSamplerDesc) == 12 * 4 + 8 + 8 * 4
-    assert ctypes.sizeof(_lib.SeirDesc) == 4 * 4 + 6 * 8 + 8 + 8 + 3 * 8
-    assert ctypes.sizeof(_lib.SeirSimDesc) == 4 * 4 + 8 + 7 * 8
     # a null sampler / context is refused before anything touches a device
     one = (ctypes.c_int32 * 2)(0, 1)
     out = (ctypes.c_int64 * 3)()
@@ -465,25 +443,12 @@ def test_with_diagnostics_alone_the_traces_sums_are_not_asked_for(tmp_path):
 
 
 # ---- 5. the compiler's account of the new kernel ---------------------------------------------------------------------------
-def test_the_new_kernel_has_an_account_of_its_own_and_the_other_five_are_the_parents():
-    entry.build()
-    res = json.load(open(entry.RESOURCES_GROUPS))
+def test_the_new_kernel_is_these_instances_without_scratch_at_full_occupancy():
+    res = H.kernel_account("groups")
     new = ["k_group_sums<0>", "k_group_sums<1>"]
     assert sorted(res) == new, sorted(res)
-    assert res == json.load(open(os.path.join(ROOT, "profiles", "r17_groups_kernels.json")))
     for k in new:
         assert res[k]["scratch_bytes_per_lane"] == 0 and res[k]["vgpr_spill"] == 0 and res[k]["sgpr_spill"] == 0, (k, res[k])
         # the LDS tile [64 days][3] and the three state sums, 64-bit
         assert res[k]["lds_bytes_per_block"] == (64 * 3 + 3) * 8, (k, res[k])
         assert res[k]["occupancy_waves_per_simd"] == 8
-    for path, committed in ((entry.RESOURCES, "r13_kernel_resources.json"), (entry.RESOURCES_ADDED, "r13_added_kernels.json"),
-                            (entry.RESOURCES_SELFTEST, "r14_selftest_kernels.json"), (entry.RESOURCES_WB, "r15_wb_kernels.json"),
-                            (entry.RESOURCES_RTQ, "r16_rtq_kernels.json")):
-        got = json.load(open(path))
-        assert not any(k.split("<")[0] in entry.GROUPS_KERNELS for k in got)
-        assert got == json.load(open(os.path.join(ROOT, "profiles", committed))), committed
-    whole = dict(json.load(open(entry.RESOURCES)), **json.load(open(entry.RESOURCES_ADDED)), **res,
-                 **json.load(open(entry.RESOURCES_SELFTEST)), **json.load(open(entry.RESOURCES_WB)),
-                 **json.load(open(entry.RESOURCES_RTQ)))
-    assert entry.split_resources(whole) == (json.load(open(entry.RESOURCES)), json.load(open(entry.RESOURCES_ADDED)))
-    assert entry.groups_resources(whole) == res

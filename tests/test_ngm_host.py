@@ -3,22 +3,21 @@ no GPU -- the symbols, the NumPy definition (`posterior.groups.ngm_rows`, `group
 statistics against exact rationals, the spectral radius against hand cases, the refusals before any GPU call, run_mcmc's
 calls and datasets with a stub sampler, and the compiler's account of the new kernel."""
 import ctypes
-import json
 import os
-import re
 import warnings
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
-import __graft_entry__ as entry
 from covid19uk_amd import _lib, hdf5io, synth
 from covid19uk_amd.inference import inference as inf
 from covid19uk_amd.posterior import groups as G
 from covid19uk_amd.sampler import BURST_PRODUCTS, GROUP_CURVE_KEYS, ChainSampler
 from covid19uk_amd.seir import SeirModel
-from tests.test_group_curves_host import CTYPES, FULL, POP, TABLE, BaseStub, CurveStub, _loop, _run, _untimed
+from tests import helpers as H
+from tests.abi_lib import check_symbols
+from tests.test_group_curves_host import FULL, POP, TABLE, BaseStub, CurveStub, _loop, _run, _untimed
 from tests.test_summary_host import CFG
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,27 +31,7 @@ NEW = {
 
 # ---- 1. the symbols ------------------------------------------------------------------------------------------------------
 def test_new_symbols_are_declared_exported_and_bound_with_the_headers_types():
-    entry.build()
-    lib = _lib.load()
-    raw = open(os.path.join(ROOT, "include", "seir_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    for name, params in NEW.items():
-        m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-        assert m, f"{name} is not declared in include/seir_hip.h"
-        declared = " ".join(m.group(1).split())
-        assert declared == params, (name, declared)
-        assert name in _lib.exported_symbols()
-        fn = getattr(lib, name)
-        want = []
-        for p in declared.split(","):
-            ty = p.strip().rsplit(" ", 1)[0] + (" *" if "*" in p else "")
-            want.append(CTYPES[ty.replace("* *", "*").strip()])
-        assert fn.restype is ctypes.c_int and list(fn.argtypes) == want, (name, fn.argtypes)
-    assert lib.seir_abi_version() == 4 and _lib.ABI_VERSION == 4
-    assert re.search(r"#define SEIR_ABI_VERSION 4\b", raw)
-    assert ctypes.sizeof(_lib.SeirSamplerDesc) == 12 * 4 + 8 + 8 * 4
-    assert ctypes.sizeof(_lib.SeirDesc) == 4 * 4 + 6 * 8 + 8 + 8 + 3 * 8
-    assert ctypes.sizeof(_lib.SeirSimDesc) == 4 * 4 + 8 + 7 * 8
+    lib = check_symbols(NEW)
     # a null sampler / context is refused before anything touches a device
     one = (ctypes.c_double * 2)(0.0, 1.0)
     idx = (ctypes.c_int32 * 6)(0, 1, 0, 0, 0, 0)
@@ -393,28 +372,12 @@ def test_the_switch_is_set_once_read_once_and_the_datasets_are_written(tmp_path,
 
 
 # ---- 6. the compiler's account of the new kernel ----------------------------------------------------------------------------
-def test_the_new_kernel_has_an_account_of_its_own_and_the_other_seven_are_the_parents():
-    entry.build()
-    res = json.load(open(entry.RESOURCES_NGM))
+def test_the_new_kernel_is_this_instance_without_scratch_at_its_parents_occupancy():
+    res = H.kernel_account("ngm")
     assert sorted(res) == ["k_ngm_rows<4>"], sorted(res)
-    assert res == json.load(open(os.path.join(ROOT, "profiles", "r21_ngm_kernels.json")))
     k = res["k_ngm_rows<4>"]
     assert k["scratch_bytes_per_lane"] == 0 and k["vgpr_spill"] == 0 and k["sgpr_spill"] == 0, k
     assert k["lds_bytes_per_block"] == 0, k                         # its LDS is dynamic, as its parent's
-    base = json.load(open(entry.RESOURCES))
+    base = H.kernel_account("base")
     # the same loop with fewer live registers (no fold): at least the parent's occupancy
     assert k["occupancy_waves_per_simd"] >= base["k_rt_trace<4>"]["occupancy_waves_per_simd"]
-    for path, committed in ((entry.RESOURCES, "r13_kernel_resources.json"), (entry.RESOURCES_ADDED, "r13_added_kernels.json"),
-                            (entry.RESOURCES_SELFTEST, "r14_selftest_kernels.json"), (entry.RESOURCES_WB, "r15_wb_kernels.json"),
-                            (entry.RESOURCES_RTQ, "r16_rtq_kernels.json"), (entry.RESOURCES_GROUPS, "r17_groups_kernels.json"),
-                            (entry.RESOURCES_GROUP_CURVES, "r18_group_curves_kernels.json")):
-        got = json.load(open(path))
-        assert not any(name.split("<")[0] in entry.NGM_KERNELS for name in got)
-        assert got == json.load(open(os.path.join(ROOT, "profiles", committed))), committed
-    whole = dict(base, **json.load(open(entry.RESOURCES_ADDED)), **res, **json.load(open(entry.RESOURCES_SELFTEST)),
-                 **json.load(open(entry.RESOURCES_WB)), **json.load(open(entry.RESOURCES_RTQ)),
-                 **json.load(open(entry.RESOURCES_GROUPS)), **json.load(open(entry.RESOURCES_GROUP_CURVES)))
-    assert entry.split_resources(whole) == (base, json.load(open(entry.RESOURCES_ADDED)))
-    assert entry.ngm_resources(whole) == res
-    assert entry.group_curves_resources(whole) == json.load(open(entry.RESOURCES_GROUP_CURVES))
-    assert not re.match(r"r\d+_kernel_resources\.json$", "r21_ngm_kernels.json")

@@ -4,10 +4,8 @@ Python restatement, the NumPy definition of the status words against hand cases 
 inverse of `draws_to_dict`, the row selection and every refusal, the driver's calls and datasets with a stub sampler,
 run_mcmc's call list after the factoring, and the compiler's account of the new kernels."""
 import ctypes
-import json
 import math
 import os
-import re
 import shutil
 import struct
 import subprocess
@@ -20,39 +18,22 @@ from covid19uk_amd import _lib, hdf5io
 from covid19uk_amd.inference import inference as inf
 from covid19uk_amd.posterior import replay as R
 from covid19uk_amd.sampler import BURST_PRODUCTS, ChainSampler
+from tests import helpers as H
+from tests.abi_lib import check_symbols
 from tests.test_group_curves_host import FULL, POP, TABLE, _read
 from tests.test_group_curves_host import _run as _run_mcmc
 from tests.test_ngm_host import NgmStub
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {
-    "seir_sampler_load_trace": ("seir_sampler *s, int32_t chain, int32_t first, int32_t count, const double *theta, const double *events",
-                                [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_double),
-                                 ctypes.POINTER(ctypes.c_double)]),
-    "seir_sampler_load_status": ("seir_sampler *s, uint64_t out[8], int32_t clear",
-                                 [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32]),
+    "seir_sampler_load_trace": "seir_sampler *s, int32_t chain, int32_t first, int32_t count, const double *theta, const double *events",
+    "seir_sampler_load_status": "seir_sampler *s, uint64_t out[8], int32_t clear",
 }
 
 
 # ---- 1. the symbols ------------------------------------------------------------------------------------------------------
 def test_new_symbols_are_declared_exported_and_bound_with_the_headers_types():
-    entry.build()
-    lib = _lib.load()
-    raw = open(os.path.join(ROOT, "include", "seir_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    for name, (params, argtypes) in NEW.items():
-        m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-        assert m, f"{name} is not declared in include/seir_hip.h"
-        assert " ".join(m.group(1).split()) == params, name
-        assert name in _lib.exported_symbols()
-        fn = getattr(lib, name)
-        assert fn.restype is ctypes.c_int and list(fn.argtypes) == argtypes, (name, fn.argtypes)
-    # new symbols only: the ABI version and the descriptors are the parent's
-    assert lib.seir_abi_version() == 4 and _lib.ABI_VERSION == 4
-    assert re.search(r"#define SEIR_ABI_VERSION 4\b", raw)
-    assert ctypes.sizeof(_lib.SeirSamplerDesc) == 12 * 4 + 8 + 8 * 4
-    assert ctypes.sizeof(_lib.SeirDesc) == 4 * 4 + 6 * 8 + 8 + 8 + 3 * 8
-    assert ctypes.sizeof(_lib.SeirSimDesc) == 4 * 4 + 8 + 7 * 8
+    lib = check_symbols(NEW)
     # a null sampler is refused before anything touches a device
     one = (ctypes.c_double * 2)(0.0, 1.0)
     out = (ctypes.c_uint64 * 8)()
@@ -498,26 +479,11 @@ def test_run_mcmc_makes_the_parents_call_list(tmp_path):
 
 
 # ---- 7. the compiler's account of the new kernels ----------------------------------------------------------------------
-def test_the_new_kernels_have_an_account_of_their_own_and_the_other_eight_are_the_parents():
-    entry.build()
-    res = json.load(open(entry.RESOURCES_REPLAY))
+def test_the_new_kernels_are_these_instances_without_scratch_or_lds_at_the_summarys_occupancy():
+    res = H.kernel_account("replay")
     assert sorted(res) == ["k_trace_load<0>", "k_trace_load<1>", "k_trace_load_theta<256>"], sorted(res)
-    assert res == json.load(open(os.path.join(ROOT, "profiles", "r22_replay_kernels.json")))
-    base = json.load(open(entry.RESOURCES))
+    base = H.kernel_account("base")
     for name, k in res.items():
         assert k["scratch_bytes_per_lane"] == 0 and k["vgpr_spill"] == 0 and k["sgpr_spill"] == 0, name
         assert k["lds_bytes_per_block"] == 0, name              # the carry lives in the wave's registers: no LDS at all
         assert k["occupancy_waves_per_simd"] >= base["k_summarize<1,0>"]["occupancy_waves_per_simd"], name
-    others = ((entry.RESOURCES, "r13_kernel_resources.json"), (entry.RESOURCES_ADDED, "r13_added_kernels.json"),
-              (entry.RESOURCES_SELFTEST, "r14_selftest_kernels.json"), (entry.RESOURCES_WB, "r15_wb_kernels.json"),
-              (entry.RESOURCES_RTQ, "r16_rtq_kernels.json"), (entry.RESOURCES_GROUPS, "r17_groups_kernels.json"),
-              (entry.RESOURCES_GROUP_CURVES, "r18_group_curves_kernels.json"), (entry.RESOURCES_NGM, "r21_ngm_kernels.json"))
-    whole = dict(res)
-    for path, committed in others:
-        got = json.load(open(path))
-        assert not any(name.split("<")[0] in entry.REPLAY_KERNELS for name in got), committed
-        assert got == json.load(open(os.path.join(ROOT, "profiles", committed))), committed
-        whole.update(got)
-    assert entry.split_resources(whole) == (base, json.load(open(entry.RESOURCES_ADDED)))
-    assert entry.replay_resources(whole) == res
-    assert not re.match(r"r\d+_kernel_resources\.json$", "r22_replay_kernels.json")

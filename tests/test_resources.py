@@ -1,13 +1,19 @@
 """The compiler's account of the kernels (`hipcc -Rpass-analysis=kernel-resource-usage`, kept by `__graft_entry__.build()`
-as covid19uk_amd/kernel_resources.json; a round's copy is committed as profiles/rNN_kernel_resources.json): the instances
+as covid19uk_amd/kernel_resources.json; the tracked copy is profiles/kernel_resources.json): the instances
 that a BASELINE.json configuration launches on its hot path must not acquire scratch -- a spill inside a persistent launch's
-step loop is paid in every step -- and must keep the occupancy their launches' residency arithmetic relies on."""
+step loop is paid in every step -- and must keep the occupancy their launches' residency arithmetic relies on.  And what holds
+across the products (covid19uk_amd/kernel_resources.py: who owns which kernel): a fresh build gives the tracked copy, every
+owner's kernels are there, no kernel has two owners.  What a product asks of its own kernels is in its tests/test_*_host.py."""
 import json
 import os
 
 import pytest
 
 import __graft_entry__ as entry
+from covid19uk_amd import kernel_resources
+from tests import helpers as H
+
+TRACKED = os.path.join(entry.ROOT, "profiles", "kernel_resources.json")
 
 # instance -> (max VGPRs, min waves per SIMD) the host's launch logic assumes; scratch must be 0 for all of them
 HOT_PATH = {
@@ -36,9 +42,7 @@ HOT_PATH = {
 
 @pytest.fixture(scope="module")
 def resources():
-    entry.build()
-    assert os.path.exists(entry.RESOURCES), "build() keeps the compiler's resource remarks next to the library"
-    return json.load(open(entry.RESOURCES))
+    return H.kernel_account()
 
 
 def test_every_hot_path_instance_is_compiled(resources):
@@ -84,12 +88,31 @@ def test_launches_fit_the_lds_at_the_shape_limits(resources):
 
 
 def test_the_committed_copy_is_this_rounds(resources):
-    """profiles/rNN_kernel_resources.json is the tracked copy the docs cite: it must list the same kernels, and agree with a
-    fresh build on what the hot path is held to (scratch) -- register counts may move by a few with the compiler's mood."""
-    import glob
-    files = sorted(glob.glob(os.path.join(entry.ROOT, "profiles", "r*_kernel_resources.json")))
-    assert files, "no committed profiles/rNN_kernel_resources.json"
-    doc = json.load(open(files[-1]))
+    """profiles/kernel_resources.json is the tracked copy the docs cite: it must list the same kernels, and agree with a
+    fresh build on what the hot path is held to (scratch)."""
+    doc = json.load(open(TRACKED))
     assert set(doc) == set(resources)
     for k in HOT_PATH:
         assert doc[k]["scratch_bytes_per_lane"] == resources[k]["scratch_bytes_per_lane"], k
+
+
+def test_a_fresh_build_gives_the_committed_account_kernel_for_kernel_and_field_for_field(resources):
+    """Every kernel of the library and every figure of each: a change to any kernel's registers, LDS, scratch, spills or
+    occupancy, a kernel more or a kernel less, shows here, whichever product owns it."""
+    doc = json.load(open(TRACKED))
+    assert sorted(doc) == sorted(resources)
+    wrong = {k: (resources[k], doc[k]) for k in doc if resources[k] != doc[k]}
+    assert not wrong, wrong
+    assert all(sorted(v) == sorted(kernel_resources.FIELDS) and None not in v.values() for v in resources.values())
+
+
+def test_every_owner_has_its_kernels_and_no_kernel_has_two_owners(resources):
+    named = [b for names in kernel_resources.OWNERS.values() for b in names]
+    assert len(named) == len(set(named)), sorted(b for b in set(named) if named.count(b) > 1)
+    assert kernel_resources.BASE not in kernel_resources.OWNERS
+    compiled = {k.split("<")[0] for k in resources}
+    assert not [b for b in named if b not in compiled]
+    # ... so the owners' accounts, the base owner's included, are disjoint and together the whole account
+    parts = [kernel_resources.owned(resources, o) for o in (kernel_resources.BASE, *kernel_resources.OWNERS)]
+    assert all(parts) and sum(len(p) for p in parts) == len(resources)
+    assert {k: v for p in parts for k, v in p.items()} == resources

@@ -5,19 +5,19 @@ the new kernels.  No GPU."""
 import ctypes
 import json
 import os
-import re
 import warnings
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
-import __graft_entry__ as entry
 from covid19uk_amd import _lib, hdf5io
 from covid19uk_amd.inference import inference as inf
 from covid19uk_amd.sampler import ChainSampler, ProductState, RtSummary, Trace
+from tests import helpers as H
+from tests.abi_lib import check_symbols
 from tests.test_forecast_host import ForecastStub
-from tests.test_summary_host import CFG, CTYPE, StubSampler, _read
+from tests.test_summary_host import CFG, StubSampler, _read
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {
@@ -27,32 +27,11 @@ NEW = {
     "seir_sampler_read_rt_draws_async": "seir_sampler *s, int32_t first, int32_t count, double *R_t",
     "seir_sampler_read_rt": "seir_sampler *s, uint64_t *count, double *ref, double *sum, double *sumsq, uint32_t *gt1",
 }
-CTYPES = dict(CTYPE, **{"const double *": ctypes.POINTER(ctypes.c_double), "double *": ctypes.POINTER(ctypes.c_double),
-                        "uint32_t *": ctypes.POINTER(ctypes.c_uint32)})
 
 
 # ---- 1. the symbols ------------------------------------------------------------------------------------------------------
 def test_new_symbols_are_declared_exported_and_bound_with_the_headers_types():
-    entry.build()
-    lib = _lib.load()
-    raw = open(os.path.join(ROOT, "include", "seir_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    for name, params in NEW.items():
-        m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-        assert m, f"{name} is not declared in include/seir_hip.h"
-        declared = " ".join(m.group(1).split())
-        assert declared == params, (name, declared)
-        assert name in _lib.exported_symbols()
-        fn = getattr(lib, name)                              # exported by the library
-        want = []
-        for p in declared.split(","):
-            ty = p.strip().rsplit(" ", 1)[0] + (" *" if "*" in p else "")
-            want.append(CTYPES[ty.replace("* *", "*").strip()])
-        assert fn.restype is ctypes.c_int and list(fn.argtypes) == want, (name, fn.argtypes)
-    # new symbols only: the ABI version and the descriptor are the parent's
-    assert lib.seir_abi_version() == 4 and _lib.ABI_VERSION == 4
-    assert re.search(r"#define SEIR_ABI_VERSION 4\b", raw)
-    assert ctypes.sizeof(_lib.SeirSamplerDesc) == 12 * 4 + 8 + 8 * 4
+    lib = check_symbols(NEW)
     # a null sampler is refused before anything touches a device
     one = (ctypes.c_double * 1)(1.0)
     assert lib.seir_sampler_rt_reset(None, 1, one) == _lib.ERR_INVALID
@@ -333,8 +312,7 @@ def test_a_burst_is_folded_behind_its_summary_and_forecast_and_not_at_all_when_o
 
 # ---- 6. the compiler's account of the new kernels -------------------------------------------------------------------------
 def test_the_new_kernels_have_no_scratch_and_fit_the_lds():
-    entry.build()
-    res = json.load(open(entry.RESOURCES))
+    res = H.kernel_account("base")
     new = ["k_rt_prepare<0>", "k_rt_prepare<1>", "k_rt_trace<4>", "k_rt_finish"]
     assert all(k in res for k in new), sorted(res)
     for k in new:

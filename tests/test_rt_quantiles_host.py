@@ -4,9 +4,7 @@ as plain C++ and driven through its eight passes against Python's sorted() under
 the key map itself, the configuration and the command line, run_mcmc's call sequence with a stub sampler, the datasets
 written, and the compiler's account of the two new kernels."""
 import ctypes
-import json
 import os
-import re
 import shutil
 import struct
 import subprocess
@@ -20,6 +18,8 @@ from covid19uk_amd.inference import inference as inf
 from covid19uk_amd.posterior import quantiles as Q
 from covid19uk_amd.sampler import ChainSampler
 from covid19uk_amd.seir import SeirModel
+from tests import helpers as H
+from tests.abi_lib import check_symbols
 from tests.test_rt_device_host import RtStub
 from tests.test_summary_host import CFG, _read
 
@@ -30,36 +30,12 @@ NEW = {
     "seir_order_stats_f64": "seir_ctx *ctx, const double *values, int64_t cells, int32_t segs, int64_t seg_len, "
                             "int64_t seg_stride, int64_t cell_stride, const int64_t *ranks, int32_t R, double *out",
 }
-CTYPES = {"seir_sampler *": ctypes.c_void_p, "seir_ctx *": ctypes.c_void_p, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
-          "const int64_t *": ctypes.POINTER(ctypes.c_int64), "double *": ctypes.POINTER(ctypes.c_double),
-          "const double *": ctypes.POINTER(ctypes.c_double)}
 MASK = (1 << 64) - 1
 
 
 # ---- 1. the symbols ------------------------------------------------------------------------------------------------------
 def test_new_symbols_are_declared_exported_and_bound_with_the_headers_types():
-    entry.build()
-    lib = _lib.load()
-    raw = open(os.path.join(ROOT, "include", "seir_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    for name, params in NEW.items():
-        m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-        assert m, f"{name} is not declared in include/seir_hip.h"
-        declared = " ".join(m.group(1).split())
-        assert declared == params, (name, declared)
-        assert name in _lib.exported_symbols()
-        fn = getattr(lib, name)                              # exported by the library
-        want = []
-        for p in declared.split(","):
-            ty = p.strip().rsplit(" ", 1)[0] + (" *" if "*" in p else "")
-            want.append(CTYPES[ty.replace("* *", "*").strip()])
-        assert fn.restype is ctypes.c_int and list(fn.argtypes) == want, (name, fn.argtypes)
-    # new symbols only: the ABI version and the descriptors are the parent's
-    assert lib.seir_abi_version() == 4 and _lib.ABI_VERSION == 4
-    assert re.search(r"#define SEIR_ABI_VERSION 4\b", raw)
-    assert ctypes.sizeof(_lib.SeirSamplerDesc) == 12 * 4 + 8 + 8 * 4
-    assert ctypes.sizeof(_lib.SeirDesc) == 4 * 4 + 6 * 8 + 8 + 8 + 3 * 8
-    assert ctypes.sizeof(_lib.SeirSimDesc) == 4 * 4 + 8 + 7 * 8
+    lib = check_symbols(NEW)
     # a null sampler / context is refused before anything touches a device
     one = (ctypes.c_int64 * 1)(0)
     out = (ctypes.c_double * 1)(0.0)
@@ -405,12 +381,10 @@ def test_draw_quantiles_equal_numpy_quantile():
 
 
 # ---- 5. the compiler's account of the new kernels --------------------------------------------------------------------------
-def test_the_new_kernels_have_an_account_of_their_own_and_the_other_four_are_the_parents():
-    entry.build()
-    res = json.load(open(entry.RESOURCES_RTQ))
+def test_the_new_kernels_are_these_instances_without_scratch_and_keep_four_waves():
+    res = H.kernel_account("rt_quantiles")
     new = ["k_order_stats_f64<1>", "k_order_stats_f64<4>", "k_rt_trace_keep<4>"]
     assert sorted(res) == new, sorted(res)
-    assert res == json.load(open(os.path.join(ROOT, "profiles", "r16_rtq_kernels.json")))
     for k in new:
         assert res[k]["scratch_bytes_per_lane"] == 0 and res[k]["vgpr_spill"] == 0 and res[k]["sgpr_spill"] == 0, (k, res[k])
     # k_order_stats_f64: 16 histograms of 256 bins and the ranks' state (two 64-bit prefixes, rank, group: 16 each)
@@ -421,13 +395,3 @@ def test_the_new_kernels_have_an_account_of_their_own_and_the_other_four_are_the
     # workgroups on 256 CUs, so four to a CU bounds nothing there -- fewer than four would mean that something else grew
     assert res["k_rt_trace_keep<4>"]["lds_bytes_per_block"] == 0
     assert res["k_rt_trace_keep<4>"]["occupancy_waves_per_simd"] >= 4
-    # the other four accounts hold none of the new kernels and are the parent's, instance for instance
-    for path, committed in ((entry.RESOURCES, "r13_kernel_resources.json"), (entry.RESOURCES_ADDED, "r13_added_kernels.json"),
-                            (entry.RESOURCES_SELFTEST, "r14_selftest_kernels.json"), (entry.RESOURCES_WB, "r15_wb_kernels.json")):
-        got = json.load(open(path))
-        assert not any(k.split("<")[0] in entry.RTQ_KERNELS for k in got)
-        assert got == json.load(open(os.path.join(ROOT, "profiles", committed))), committed
-    whole = dict(json.load(open(entry.RESOURCES)), **json.load(open(entry.RESOURCES_ADDED)), **res,
-                 **json.load(open(entry.RESOURCES_SELFTEST)), **json.load(open(entry.RESOURCES_WB)))
-    assert entry.split_resources(whole) == (json.load(open(entry.RESOURCES)), json.load(open(entry.RESOURCES_ADDED)))
-    assert entry.rtq_resources(whole) == res and entry.wb_resources(whole) == json.load(open(entry.RESOURCES_WB))

@@ -3,9 +3,7 @@ the new C-ABI symbols and their argument types, the shared per-cell update (covi
 definition k_summarize calls) compiled as plain C++ and driven against Python integers up to the overflow flag, mean and
 variance from the integer accumulators against NumPy, and the `summaries` option of the configuration, the command line
 and the output file."""
-import ctypes
 import os
-import re
 import shutil
 import subprocess
 
@@ -16,6 +14,8 @@ import __graft_entry__ as entry
 from covid19uk_amd import _lib
 from covid19uk_amd.inference import inference as inf
 from covid19uk_amd.sampler import MARGINAL_KEYS, SUMMARY_QUANTITIES, Summary, Trace, summary_mean, summary_var
+from tests import helpers as H
+from tests.abi_lib import check_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {
@@ -27,29 +27,11 @@ NEW = {
                                          "int64_t *events_by_location, int64_t *state_by_day",
     "seir_sampler_read_summary": "seir_sampler *s, uint64_t *count, int32_t *ref, int64_t *sum, uint64_t *sumsq",
 }
-CTYPE = {"seir_sampler *": ctypes.c_void_p, "int32_t": ctypes.c_int32, "int64_t *": ctypes.POINTER(ctypes.c_int64),
-         "uint64_t *": ctypes.POINTER(ctypes.c_uint64), "int32_t *": ctypes.POINTER(ctypes.c_int32)}
 
 
 # ---- 1. the symbols ------------------------------------------------------------------------------------------------------
 def test_new_symbols_are_declared_exported_and_bound_with_the_headers_types():
-    entry.build()
-    lib = _lib.load()
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "seir_hip.h")).read(), flags=re.S)
-    for name, params in NEW.items():
-        m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-        assert m, f"{name} is not declared in include/seir_hip.h"
-        declared = " ".join(m.group(1).split())
-        assert declared == params, (name, declared)
-        assert name in _lib.exported_symbols()
-        fn = getattr(lib, name)                              # exported by the library
-        want = []
-        for p in declared.split(","):
-            ty = p.strip().rsplit(" ", 1)[0] + (" *" if "*" in p else "")
-            want.append(CTYPE[ty.replace("* *", "*").strip()])
-        assert fn.restype is ctypes.c_int and list(fn.argtypes) == want, (name, fn.argtypes)
-    # the feature is switched on by a call: the ABI version and the descriptor are the parent's
-    assert lib.seir_abi_version() == 4 and ctypes.sizeof(_lib.SeirSamplerDesc) == 12 * 4 + 8 + 8 * 4
+    lib = check_symbols(NEW)
     # a null sampler is refused before anything touches a device
     assert lib.seir_sampler_summary_reset(None) == _lib.ERR_INVALID
     assert lib.seir_sampler_summarize(None, 0, 1, 1) == _lib.ERR_INVALID
@@ -363,8 +345,7 @@ def test_the_kernels_built_from_shared_pieces_keep_the_resources_they_had_on_the
     """Against the build before the pieces were shared (profiles/r09_kernel_resources.json): scratch, spills and LDS equal,
     occupancy not lower, and the register count within the few that move with the compiler's mood."""
     import json
-    entry.build()
-    r = json.load(open(entry.RESOURCES))[kernel]
+    r = H.kernel_account("base")[kernel]
     was = json.load(open(os.path.join(ROOT, "profiles", "r09_kernel_resources.json")))[kernel]
     for k in ("scratch_bytes_per_lane", "vgpr_spill", "sgpr_spill", "lds_bytes_per_block"):
         assert r[k] == was[k], (kernel, k, r, was)

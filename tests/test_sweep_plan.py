@@ -6,6 +6,7 @@ import subprocess
 import pytest
 
 import __graft_entry__ as entry
+from tests import helpers as H
 from tests.test_resources import HOT_PATH
 
 DRIVER = r"""
@@ -371,9 +372,7 @@ def test_all_four_tile_scalars_never_take_k_leap_with_6_or_12_day_chunks(plan):
 def test_the_occupancies_fed_to_the_plan_are_the_compilers():
     """LEAP_OCC24 / LEAP_OCC32 against the resource remarks of this build (256-thread workgroups: one wave per SIMD each,
     so waves per SIMD are workgroups per CU), and against what test_resources holds the instances to."""
-    import json
-    entry.build()
-    res = json.load(open(entry.RESOURCES))
+    res = H.kernel_account("base")
     assert res["k_leap<1,6,1,6>"]["occupancy_waves_per_simd"] == LEAP_OCC24 == HOT_PATH["k_leap<1,6,1,6>"][1]
     seen = 0
     for name, r in res.items():

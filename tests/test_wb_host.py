@@ -3,7 +3,6 @@ the device"): the symbols, the configuration and the command line, run_mcmc's ca
 ChainSampler's own order of calls inside a burst, the host's formulas against exact rationals, the datasets written, the
 csv tool pooled over chain files, and the compiler's account of the new kernels.  No GPU."""
 import ctypes
-import json
 import os
 import re
 import warnings
@@ -12,13 +11,14 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
-import __graft_entry__ as entry
 from covid19uk_amd import _lib, hdf5io
 from covid19uk_amd.inference import inference as inf
 from covid19uk_amd.posterior import within_between as wbtool
 from covid19uk_amd.sampler import WB_KEYS, WbSummary
+from tests import helpers as H
+from tests.abi_lib import check_symbols
 from tests.test_check_host import CheckRecorder, CheckStub
-from tests.test_summary_host import CFG, CTYPE, StubSampler, _read
+from tests.test_summary_host import CFG, StubSampler, _read
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {
@@ -31,31 +31,11 @@ NEW = {
     "seir_sampler_read_wb_draws_async": "seir_sampler *s, int32_t first, int32_t count, double *within_pressure, "
                                         "double *between_pressure",
 }
-CTYPES = dict(CTYPE, **{"double *": ctypes.POINTER(ctypes.c_double), "uint32_t *": ctypes.POINTER(ctypes.c_uint32)})
 
 
 # ---- 1. the symbols ------------------------------------------------------------------------------------------------------
 def test_new_symbols_are_declared_exported_and_bound_with_the_headers_types():
-    entry.build()
-    lib = _lib.load()
-    raw = open(os.path.join(ROOT, "include", "seir_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    for name, params in NEW.items():
-        m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-        assert m, f"{name} is not declared in include/seir_hip.h"
-        declared = " ".join(m.group(1).split())
-        assert declared == params, (name, declared)
-        assert name in _lib.exported_symbols()
-        fn = getattr(lib, name)                              # exported by the library
-        want = []
-        for p in declared.split(","):
-            ty = p.strip().rsplit(" ", 1)[0] + (" *" if "*" in p else "")
-            want.append(CTYPES[ty.replace("* *", "*").strip()])
-        assert fn.restype is ctypes.c_int and list(fn.argtypes) == want, (name, fn.argtypes)
-    # new symbols only: the ABI version and the descriptor are the parent's
-    assert lib.seir_abi_version() == 4 and _lib.ABI_VERSION == 4
-    assert re.search(r"#define SEIR_ABI_VERSION 4\b", raw)
-    assert ctypes.sizeof(_lib.SeirSamplerDesc) == 12 * 4 + 8 + 8 * 4
+    lib = check_symbols(NEW)
     # a null sampler is refused before anything touches a device
     one = (ctypes.c_double * 1)(1.0)
     assert lib.seir_sampler_wb_reset(None, 1) == _lib.ERR_INVALID
@@ -423,12 +403,10 @@ def test_the_csv_tool_pools_the_files_with_the_weights_defined(tmp_path, ext, mo
 
 
 # ---- 7. the compiler's account of the new kernels -------------------------------------------------------------------------
-def test_the_new_kernels_have_an_account_of_their_own_and_the_other_three_are_the_parents():
-    entry.build()
-    res = json.load(open(entry.RESOURCES_WB))
+def test_the_new_kernels_are_these_instances_without_scratch_or_static_lds():
+    res = H.kernel_account("wb")
     new = ["k_wb_prepare<0>", "k_wb_prepare<1>", "k_wb_trace<4>", "k_wb_finish"]
     assert sorted(res) == sorted(new), sorted(res)
-    assert res == json.load(open(os.path.join(ROOT, "profiles", "r15_wb_kernels.json")))
     for k in new:
         assert res[k]["scratch_bytes_per_lane"] == 0 and res[k]["vgpr_spill"] == 0 and res[k]["sgpr_spill"] == 0, (k, res[k])
     # LDS as the constexpr says: no static part anywhere, and k_wb_trace's dynamic part -- x of its 4 days and the four waves'
@@ -441,13 +419,3 @@ def test_the_new_kernels_have_an_account_of_their_own_and_the_other_three_are_th
     assert (4 * 2048 + 4 * 4 * 64) * 8 == 72 * 1024 <= 160 * 1024
     # at UK-380 (Mp = 384) a workgroup takes 20 KiB and the LDS would hold eight: the registers must allow at least six
     assert res["k_wb_trace<4>"]["occupancy_waves_per_simd"] >= 6
-    # the other three accounts hold none of the new kernels and are the parent's, instance for instance
-    for path, committed in ((entry.RESOURCES, "r13_kernel_resources.json"), (entry.RESOURCES_ADDED, "r13_added_kernels.json"),
-                            (entry.RESOURCES_SELFTEST, "r14_selftest_kernels.json")):
-        got = json.load(open(path))
-        assert not any(k.split("<")[0] in entry.WB_KERNELS for k in got)
-        assert got == json.load(open(os.path.join(ROOT, "profiles", committed))), committed
-    whole = dict(json.load(open(entry.RESOURCES)), **json.load(open(entry.RESOURCES_ADDED)), **res,
-                 **json.load(open(entry.RESOURCES_SELFTEST)))
-    assert entry.split_resources(whole) == (json.load(open(entry.RESOURCES)), json.load(open(entry.RESOURCES_ADDED)))
-    assert entry.wb_resources(whole) == res

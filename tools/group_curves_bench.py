@@ -96,12 +96,11 @@ def main():
     u = synth.jitter_params(u0, B, scale=0.002, seed=7, T=T)
     ev = np.stack([events] * B)
     Mp = (M + 63) // 64 * 64
-    kr = json.load(open(entry.RESOURCES_GROUP_CURVES))
-    base = json.load(open(entry.RESOURCES))
+    kr = json.load(open(entry.RESOURCES))
     res = {"workload": a.workload, "M": M, "T": T, "chains": B, "draws": n, "days": D, "groups": tab.names,
            "group_sizes": [int(x) for x in np.diff(tab.offsets)], "device": torch.cuda.get_device_name(0),
            "command": " ".join(sys.argv), "cell_plane_bytes": n * B * D * Mp * 8, "group_output_bytes": n * B * tab.G * D * 8,
-           "k_rt_trace_cells": kr["k_rt_trace_cells<4>"], "k_rt_trace": base["k_rt_trace<4>"]}
+           "k_rt_trace_cells": kr["k_rt_trace_cells<4>"], "k_rt_trace": kr["k_rt_trace<4>"]}
 
     with SeirModel(cov, init, max_chains=B) as model:
         with ChainSampler(model, cfg, B, seed=1, trace_capacity=2 * n, record_events="u16") as s:

@@ -95,12 +95,12 @@ def main():
     u = synth.jitter_params(u0, B, scale=0.002, seed=7, T=T)
     ev = np.stack([events] * B)
     Mp = (M + 63) // 64 * 64
+    kr = json.load(open(entry.RESOURCES))
     res = {"workload": a.workload, "M": M, "T": T, "chains": B, "draws": n, "days": D, "groups": tab.names,
            "group_sizes": [int(x) for x in np.diff(tab.offsets)], "device": torch.cuda.get_device_name(0),
            "command": " ".join(sys.argv), "rows_plane_bytes_per_slot": B * tab.G * D * Mp * 8, "store_bytes": n * B * tab.G * tab.G * D * 8,
            "cells_per_draw": int(tab.offsets[-1]) * M * D, "k_rt_trace_cells_per_draw": M * M * D,
-           "k_ngm_rows": json.load(open(entry.RESOURCES_NGM))["k_ngm_rows<4>"],
-           "k_rt_trace": json.load(open(entry.RESOURCES))["k_rt_trace<4>"]}
+           "k_ngm_rows": kr["k_ngm_rows<4>"], "k_rt_trace": kr["k_rt_trace<4>"]}
 
     with SeirModel(cov, init, max_chains=B) as model:
         with ChainSampler(model, cfg, B, seed=1, trace_capacity=2 * n, record_events="u16") as s:

@@ -83,7 +83,7 @@ def main():
     import __graft_entry__ as entry
     entry.build()
     import torch
-    from covid19uk_amd import _lib, hdf5io, synth
+    from covid19uk_amd import _lib, hdf5io, kernel_resources, synth
     from covid19uk_amd.inference import inference as inf
     from covid19uk_amd.posterior import groups as G
     from covid19uk_amd.posterior import predict
@@ -105,9 +105,10 @@ def main():
     W, wd = predict.forecast_calendar(cov, None, T, Hn)
     Wc, wdc = predict.check_calendar(cov, None, T, 14)
     on = dict(summarize=True, forecast=True, rt=True, check=True, within_between=True, groups=True)
+    kr = json.load(open(entry.RESOURCES))
     res = {"workload": a.workload, "M": M, "T": T, "chains": B, "draws": n, "device": torch.cuda.get_device_name(0),
-           "command": " ".join(sys.argv), "kernels": json.load(open(entry.RESOURCES_REPLAY)),
-           "k_summarize": json.load(open(entry.RESOURCES))["k_summarize<1,0>"]}
+           "command": " ".join(sys.argv), "kernels": kernel_resources.owned(kr, "replay"),
+           "k_summarize": kr["k_summarize<1,0>"]}
     ev_bytes_in, ev_bytes_out = n * M * T * 3 * 8, n * M * T * 3 * 2
     res["bytes_per_chain_burst"] = {"read_fp64": ev_bytes_in + n * P * 8, "written": ev_bytes_out + n * P * 8 + n * (3 + 4 * _lib.MOVE_TRACE) * 8}
 

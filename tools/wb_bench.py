@@ -80,7 +80,7 @@ def main():
     res = {"workload": a.workload, "M": M, "T": T, "chains": B, "draws": n, "device": torch.cuda.get_device_name(0),
            "command": " ".join(sys.argv), "wb_call": []}
     try:
-        kr = json.load(open(entry.RESOURCES_WB))["k_wb_trace<4>"]
+        kr = json.load(open(entry.RESOURCES))["k_wb_trace<4>"]
     except (OSError, KeyError):
         kr = None
 
