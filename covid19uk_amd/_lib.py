@@ -85,10 +85,11 @@ PLAN_MOVES = ("pairs", "pair", "split")
 PLAN_FPEND = (None, "k_move_pairs", "k_record", "k_apply_fpend")
 
 ABI_VERSION = 4               # SEIR_ABI_VERSION
-OPT_DEBUG_SKEW, OPT_XCD_AFFINITY, OPT_GEMM_F32, OPT_EVAL_FORM, OPT_RT_STAGING_KIB = 0, 1, 2, 3, 4
+OPT_DEBUG_SKEW, OPT_XCD_AFFINITY, OPT_GEMM_F32, OPT_EVAL_FORM, OPT_RT_STAGING_KIB, OPT_GENERIC_MOVES = 0, 1, 2, 3, 4, 5
 ERR_INVALID, ERR_STATE = -1, -3   # SEIR_ERR_INVALID, SEIR_ERR_STATE
 ERR_HANDOFF = -4              # SEIR_ERR_HANDOFF
 MMAX = 4                      # SEIR_MMAX
+MM_SMALL = 2                  # csrc/sampler_kernels.h: the sub-moves the event-update kernels have instances of their own for
 MOVE_TRACE = 2 + 4 * MMAX     # SEIR_MOVE_TRACE
 FORECAST_MAX_H = 128          # SEIR_FORECAST_MAX_H
 FORECAST_ID_SHIFT, FORECAST_MAX_CHAIN = 20, 2048   # draw id = (global chain id << 20) + j
@@ -197,6 +198,8 @@ _SIGNATURES = {
     "seir_sampler_launch_form": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32),
                                                 ctypes.POINTER(ctypes.c_int32)]),
     "seir_sampler_sweep_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SeirSweepPlan)]),
+    "seir_move_instance": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32]),
+    "seir_sampler_move_instance": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     # summaries of the recorded events on the device: moments and marginals
     "seir_sampler_summary_reset": (ctypes.c_int, [ctypes.c_void_p]),
     "seir_sampler_summarize": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),

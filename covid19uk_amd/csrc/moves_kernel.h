@@ -98,14 +98,20 @@ __device__ __forceinline__ double mv_log(double x, const double2 *ltab) { return
 // Uniforms and descriptor header of a proposal: they depend on (seed, chain, sweep, scan, slot)
 // only, so the kernel draws them at entry, overlapped with its first round of loads; the first
 // barrier after this call publishes them.
+// MM (every function of this file that takes it): the instance's bound on the sub-moves, MM_SMALL or MMAX
+// (sampler_kernels.h).  Slots keep their numbers -- sub-move j draws from slots 2j and 2j + 1 whatever MM is -- and the
+// slots of sub-moves the instance does not have are not drawn; the descriptor's header is written for all MMAX of them
+// (a descriptor is copied and traced whole).
+template <int MM>
 __device__ inline void mv_draw(const SamplerCfg &s, const Chains &ch, int b, MoveSpec spec, MvShared &sm, int T) {
+    static_assert(MM >= 1 && MM <= MMAX, "the sub-move bound of an instance");
     Move &mv = sm.mv;
     const int tid = threadIdx.x;
-    if (tid >= 2 * MMAX && tid != 64) return;
+    if (tid >= 2 * MM && tid != 64) return;
     const RngKey key = rng_key(s, ch, b);
     const uint32_t stream = RS_MOVE_BASE + (uint32_t)(spec.scan * 4 + spec.slot);
     // one lane per draw slot (slot 15 = the accept uniform), broadcast through LDS
-    if (tid < 2 * MMAX) rng_uniform2(key, stream, (uint32_t)tid, sm.u[tid][0], sm.u[tid][1]);
+    if (tid < 2 * MM) rng_uniform2(key, stream, (uint32_t)tid, sm.u[tid][0], sm.u[tid][1]);
     if (tid == 64) {
         mv.valid = (s.disable_mask >> (1 + spec.slot)) & 1 ? 0 : 1;    // disabled sub-kernel: drawn, never accepted
         mv.n = 0; mv.tgt = spec.tgt; mv.kind = spec.kind; mv.slot = spec.slot;
@@ -114,6 +120,24 @@ __device__ inline void mv_draw(const SamplerCfg &s, const Chains &ch, int b, Mov
         double ua, ub;
         rng_uniform2(key, stream, 15u, ua, ub);
         mv.logu = cold_log(ua);
+    }
+}
+
+// trace row of one update (thread 0).  The columns keep their MMAX-wide layout; those of the sub-moves an instance does
+// not have get the zeros the descriptor's header holds for a sub-move that was not drawn
+template <int MM>
+__device__ __forceinline__ void mv_trace(const SamplerCfg &s, const Chains &ch, int b, const Move &mv, int acc,
+                                         unsigned tr_slot, double lp) {
+    if (tr_slot < (unsigned)s.cap) {
+        double *tr = ch.tr_mv + (((size_t)tr_slot * s.B + b) * 4 + mv.slot) * NMVTR;
+        tr[0] = (double)acc;
+        tr[1] = lp;
+        for (int j = 0; j < MM; ++j) {
+            tr[2 + j] = mv.tm[j]; tr[2 + MMAX + j] = mv.tt[j];
+            tr[2 + 2 * MMAX + j] = mv.tdt[j]; tr[2 + 3 * MMAX + j] = mv.tx[j];
+        }
+        for (int j = MM; j < MMAX; ++j)
+            tr[2 + j] = tr[2 + MMAX + j] = tr[2 + 2 * MMAX + j] = tr[2 + 3 * MMAX + j] = 0.0;
     }
 }
 
@@ -191,7 +215,7 @@ __device__ __forceinline__ int wv_at(const int (&v)[NCH], int t) {
     return r;
 }
 
-template <int NCH>
+template <int NCH, int MM>
 __device__ inline void mv_propose_wave(const Dims &d, const Work &w, const SamplerCfg &s, const Chains &ch, int b,
                                        MoveSpec spec, MvShared &sm, const MvLds &L, const double2 *ltab,
                                        bool rows_only) {
@@ -208,35 +232,35 @@ __device__ inline void mv_propose_wave(const Dims &d, const Work &w, const Sampl
         const int *rt = L.rt;
         const HotRows hr = wv_hot_rows(rt, M, lane);
         const int H = hr.H;
-        const int nsel = min(min(s.mmax, MMAX), H);
+        const int nsel = min(min(s.mmax, MM), H);
         // positions of the nsel distinct hot rows: draw j is an index among the H - j rows not yet chosen.  Written with
         // compile-time indices only (a run-time index would put these few integers in scratch memory, and every
         // access of this latency chain would be a memory round trip)
-        int pos[MMAX], chosen[MMAX], rowj[MMAX];
+        int pos[MM], chosen[MM], rowj[MM];
 #pragma unroll
-        for (int j = 0; j < MMAX; ++j) { pos[j] = 0; rowj[j] = 0; chosen[j] = 0x7fffffff; }
+        for (int j = 0; j < MM; ++j) { pos[j] = 0; rowj[j] = 0; chosen[j] = 0x7fffffff; }
 #pragma unroll
-        for (int j = 0; j < MMAX; ++j) {
+        for (int j = 0; j < MM; ++j) {
             if (j < nsel) {
                 int p = rng_index(sm.u[2 * j][0], H - j);
 #pragma unroll
-                for (int a = 0; a < MMAX; ++a)
+                for (int a = 0; a < MM; ++a)
                     if (a < j && p >= chosen[a]) ++p;            // chosen[0..j-1] ascending
                 pos[j] = p;
                 chosen[j] = p;                                   // insert: bubble down
 #pragma unroll
-                for (int a = MMAX - 1; a >= 1; --a)
+                for (int a = MM - 1; a >= 1; --a)
                     if (a <= j && chosen[a - 1] > chosen[a]) { const int tmp = chosen[a]; chosen[a] = chosen[a - 1]; chosen[a - 1] = tmp; }
             }
         }
 #pragma unroll
-        for (int j = 0; j < MMAX; ++j)
+        for (int j = 0; j < MM; ++j)
             if (j < nsel) rowj[j] = wv_hot_row(hr, rt, M, pos[j], lane);
         if (rows_only) {
             if (tid == 0) {
                 sm.nsel = nsel;
 #pragma unroll
-                for (int j = 0; j < MMAX; ++j)
+                for (int j = 0; j < MM; ++j)
                     if (j < nsel) sm.sel[j] = rowj[j];
             }
             lds_barrier();
@@ -247,7 +271,7 @@ __device__ inline void mv_propose_wave(const Dims &d, const Work &w, const Sampl
             const int j = wave;
             int m = 0;
 #pragma unroll
-            for (int jj = 0; jj < MMAX; ++jj)
+            for (int jj = 0; jj < MM; ++jj)
                 if (jj == j) m = rowj[jj];
             const size_t rowoff = ((size_t)b * d.Mp + m) * d.Tp;
             int rk[NCH], rsrc[NCH], rdst[NCH];
@@ -328,7 +352,7 @@ __device__ inline void mv_propose_wave(const Dims &d, const Work &w, const Sampl
         if (tid == 0) {
             sm.nsel = nsel;
 #pragma unroll
-            for (int j = 0; j < MMAX; ++j)
+            for (int j = 0; j < MM; ++j)
                 if (j < nsel) sm.sel[j] = rowj[j];
         }
         lds_barrier();
@@ -458,11 +482,11 @@ __device__ inline void mv_propose_wave(const Dims &d, const Work &w, const Sampl
 // 12 (T <= 768: SYN-2048 x 730) or 16 (T <= 1024, the sampler's limit); the kernels are instantiated per value, so that
 // an instance carries one size's code.  (Rounds 1-2 had a block-level form for T > 384 -- scans through LDS, ten
 // workgroup barriers; the wave form replaced it at every size in round 3.)
-template <int NCH>
+template <int NCH, int MM>
 __device__ __forceinline__ void mv_propose(const Dims &d, const Work &w, const SamplerCfg &s, const Chains &ch, int b,
                                            MoveSpec spec, MvShared &sm, const MvLds &L, const double2 *ltab,
                                            bool rows_only = false) {
-    mv_propose_wave<NCH>(d, w, s, ch, b, spec, sm, L, ltab, rows_only);
+    mv_propose_wave<NCH, MM>(d, w, s, ch, b, spec, sm, L, ltab, rows_only);
 }
 
 // events of the target transition inside the occult range, for every row, into LDS (M beyond the prefetch width)
@@ -478,9 +502,9 @@ __device__ __forceinline__ void range_totals_to_lds(const Dims &d, const Work &w
 // grid (nrb_d, B), MVB threads.  The pending descriptor is read from buffer pbuf, the next one
 // written to pbuf^1 (late blocks must not see the new one).
 // next.kind == -2: finalize only and advance the chain's sweep counter (closing launch of a sweep).
-template <int NCH>
-__global__ __launch_bounds__(MVB) void k_move_pa2(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, MoveSpec next,
-                                                  int have_prev, int pbuf) {
+template <int NCH, int MM>
+__device__ __forceinline__ void move_pa2_body(const Dims &d, const Consts &c, const Work &w, const SamplerCfg &s, const Chains &ch,
+                                              MoveSpec next, int have_prev, int pbuf) {
     extern __shared__ __attribute__((aligned(16))) int dyn_i[];                     // block 0: rg [M] | rt [M]
     __shared__ MvShared sm;
     __shared__ Move pend;
@@ -520,7 +544,7 @@ __global__ __launch_bounds__(MVB) void k_move_pa2(Dims d, Consts c, Work w, Samp
     }
     if (proposer) {
         if (tid >= 128 && tid < 128 + LOGTAB_N) ltab[tid - 128] = c.logtab[tid - 128];
-        mv_draw(s, ch, b, next, sm, T);
+        mv_draw<MM>(s, ch, b, next, sm, T);
     }
     double hs_th = 0.0, hs_cn = 0.0;
     unsigned tr_slot = 0xffffffffu;
@@ -551,16 +575,16 @@ __global__ __launch_bounds__(MVB) void k_move_pa2(Dims d, Consts c, Work w, Samp
             const int r_lo = bx * rows_per_blk, r_hi = min(M, r_lo + rows_per_blk);
             const int wave = tid >> 6, lane = tid & 63;
             for (int j = r_lo + wave; j < r_hi; j += MVW) {
-                double coef[MMAX];
+                double coef[MM];
 #pragma unroll
-                for (int i = 0; i < MMAX; ++i)
+                for (int i = 0; i < MM; ++i)
                     coef[i] = i < mv.n ? c.Cstar[(size_t)mv.m[i] * d.Kp0 + j] * c.invN[mv.m[i]] * (double)(-mv.dsrc[i])
                                        : 0.0;
                 double *Fr = w.F + ((size_t)b * d.Mp + j) * d.Tp;
                 for (int t = mv.LO + lane; t <= mv.HI; t += WAVE) {
                     double dF = 0.0;
 #pragma unroll
-                    for (int i = 0; i < MMAX; ++i)
+                    for (int i = 0; i < MM; ++i)
                         if (i < mv.n && t > mv.lo[i] && t <= mv.hi[i]) dF += coef[i];
                     if (dF != 0.0) Fr[t] += dF;
                 }
@@ -593,15 +617,7 @@ __global__ __launch_bounds__(MVB) void k_move_pa2(Dims d, Consts c, Work w, Samp
                     hs_th += s_dth; hs_cn += s_dcn;
                     hs[HS_LP_THETA] = hs_th; hs[HS_LP_CONST] = hs_cn;
                 }
-                if (tr_slot < (unsigned)s.cap) {
-                    double *tr = ch.tr_mv + (((size_t)tr_slot * s.B + b) * 4 + mv.slot) * NMVTR;
-                    tr[0] = (double)s_acc;
-                    tr[1] = hs_th + hs_cn;
-                    for (int j = 0; j < MMAX; ++j) {
-                        tr[2 + j] = mv.tm[j]; tr[2 + MMAX + j] = mv.tt[j];
-                        tr[2 + 2 * MMAX + j] = mv.tdt[j]; tr[2 + 3 * MMAX + j] = mv.tx[j];
-                    }
-                }
+                mv_trace<MM>(s, ch, b, mv, s_acc, tr_slot, hs_th + hs_cn);
             }
             lds_barrier();               // LDS only: tid 0's trace stores need not drain before the proposal
         }
@@ -654,11 +670,21 @@ __global__ __launch_bounds__(MVB) void k_move_pa2(Dims d, Consts c, Work w, Samp
 #ifdef SEIR_STAMPS
         L.stamp_hs = stamp_hs; L.stamp_on = stamp_on;
 #endif
-        mv_propose<NCH>(d, w, s, ch, b, next, sm, L, ltab);
+        mv_propose<NCH, MM>(d, w, s, ch, b, next, sm, L, ltab);
         MSTAMP(10);
         if (tid == 0) ch.mv[(size_t)(pbuf ^ 1) * s.B + b] = sm.mv;
         MSTAMP(11);
     }
+}
+template <int NCH>
+__global__ __launch_bounds__(MVB) void k_move_pa2(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, MoveSpec next,
+                                                  int have_prev, int pbuf) {
+    move_pa2_body<NCH, MM_SMALL>(d, c, w, s, ch, next, have_prev, pbuf);
+}
+template <int NCH>
+__global__ __launch_bounds__(MVB) void k_move_pa2_m4(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, MoveSpec next,
+                                                     int have_prev, int pbuf) {
+    move_pa2_body<NCH, MMAX>(d, c, w, s, ch, next, have_prev, pbuf);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -773,26 +799,13 @@ __device__ __forceinline__ void mv_apply_rows(const Dims &d, const Work &w, cons
     }
 }
 
-// trace row of one update (thread 0)
-__device__ __forceinline__ void mv_trace(const SamplerCfg &s, const Chains &ch, int b, const Move &mv, int acc,
-                                         unsigned tr_slot, double lp) {
-    if (tr_slot < (unsigned)s.cap) {
-        double *tr = ch.tr_mv + (((size_t)tr_slot * s.B + b) * 4 + mv.slot) * NMVTR;
-        tr[0] = (double)acc;
-        tr[1] = lp;
-        for (int j = 0; j < MMAX; ++j) {
-            tr[2 + j] = mv.tm[j]; tr[2 + MMAX + j] = mv.tt[j];
-            tr[2 + 2 * MMAX + j] = mv.tdt[j]; tr[2 + 3 * MMAX + j] = mv.tx[j];
-        }
-    }
-}
-
 // log-ratio of a drawn proposal over the rows it updates -> od[0..1] = {theta part, constant part}
+template <int MM>
 __device__ __forceinline__ void mv_own_rows_to_down(const Dims &d, const Consts &c, const Work &w, int b, const Move &mv,
                                                     double psi, const double2 *ltab, const Move *fp, double *red,
                                                     double *od) {
     double dth = 0.0, dcn = 0.0;
-    if (mv.valid && mv.n > 0) own_rows_delta<MVB>(d, c, w, b, mv, psi, 0, d.M, ltab, dth, dcn, fp);
+    if (mv.valid && mv.n > 0) own_rows_delta<MVB, MM>(d, c, w, b, mv, psi, 0, d.M, ltab, dth, dcn, fp);
     mv_sum2(dth, dcn, red);
     if (threadIdx.x == 0) {
         od[0] = dth;
@@ -870,7 +883,7 @@ template <bool SOLO, typename TT>
 __device__ __forceinline__ TT ld_band(const TT *p_) { return SOLO ? *p_ : ld_l2(p_); }
 // NRB: rows per wave of a band workgroup -- 2 (16 rows per workgroup: 24 of them per chain at UK-380, one chain per XCD) or 4 (32
 // rows: 12 per chain, so that (3 + 12) x 16 workgroups -- sixteen chains, two per XCD -- still hold one CU each)
-template <bool SOLO, int NRB>
+template <bool SOLO, int NRB, int MM>
 __device__ __forceinline__ void pair_band_block(const Dims &d, const Consts &c, const Work &w, const SamplerCfg &s,
                                                 const Chains &ch, int b, int bx, int nband, unsigned token, bool has_r1,
                                                 bool has_r2, int buf, int st_slot = 0, int st_step = 0) {
@@ -907,13 +920,13 @@ __device__ __forceinline__ void pair_band_block(const Dims &d, const Consts &c, 
     // evaluation put the persistent launch into scratch: there they are formed where they are used)
     constexpr bool PREF = NRB == 2;
     constexpr int NRP = PREF ? NRB : 1;
-    double cfb[NRP][MMAX], Fpre[NRP][NPF];
+    double cfb[NRP][MM], Fpre[NRP][NPF];
 #pragma unroll
     for (int r = 0; r < NRP; ++r) {
         const int j = r_lo + wave + r * MVW;
         const bool onr = PREF && has_fp && j < r_hi;
 #pragma unroll
-        for (int i = 0; i < MMAX; ++i)
+        for (int i = 0; i < MM; ++i)
             cfb[r][i] = (onr && i < fp.n) ? c.Cstar[(size_t)fp.m[i] * d.Kp0 + j] * c.invN[fp.m[i]] * (double)(-fp.dsrc[i]) : 0.0;
 #pragma unroll
         for (int q = 0; q < NPF; ++q) {
@@ -950,18 +963,18 @@ __device__ __forceinline__ void pair_band_block(const Dims &d, const Consts &c, 
             for (int r0 = 0; r0 < NRB; r0 += NR) {
             int jr[NR];
             bool on[NR];
-            double eb[NR], coef[NR][MMAX], cfp[NR][MMAX];
+            double eb[NR], coef[NR][MM], cfp[NR][MM];
     #pragma unroll
             for (int r = 0; r < NR; ++r) {
                 jr[r] = r_lo + wave + (r0 + r) * MVW;
                 bool mine = false;
     #pragma unroll
-                for (int i = 0; i < MMAX; ++i) mine |= (i < mv.n && mv.m[i] == jr[r]);
+                for (int i = 0; i < MM; ++i) mine |= (i < mv.n && mv.m[i] == jr[r]);
                 on[r] = jr[r] < r_hi && !mine;           // wave-uniform: the updated rows' part is the drawing role's (Chains::Down)
                 const int j = on[r] ? jr[r] : r_lo;
                 eb[r] = w.eb[(size_t)b * d.Mp + j];
     #pragma unroll
-                for (int i = 0; i < MMAX; ++i) {
+                for (int i = 0; i < MM; ++i) {
                     coef[r][i] = (on[r] && i < mv.n) ? c.Cstar[(size_t)mv.m[i] * d.Kp0 + j] * c.invN[mv.m[i]] * (double)(-mv.dsrc[i]) : 0.0;
                     // the accepted update's coefficients: prefetched above for the same rows (two rows per wave), or formed here
                     if (PREF) cfp[r][i] = on[r] ? cfb[PREF ? r : 0][i] : 0.0;
@@ -976,7 +989,7 @@ __device__ __forceinline__ void pair_band_block(const Dims &d, const Consts &c, 
                 for (int r = 0; r < NR; ++r) {
                     dF[r] = 0.0;
     #pragma unroll
-                    for (int i = 0; i < MMAX; ++i)
+                    for (int i = 0; i < MM; ++i)
                         if (i < mv.n && t > mv.lo[i] && t <= mv.hi[i]) dF[r] += coef[r][i];
                     act[r] = on[r] && t <= mv.HI && dF[r] != 0.0;
                     const size_t q = ((size_t)b * d.Mp + (on[r] ? jr[r] : r_lo)) * d.Tp + (act[r] ? t : mv.LO);
@@ -989,7 +1002,7 @@ __device__ __forceinline__ void pair_band_block(const Dims &d, const Consts &c, 
                     if (has_fp) {                          // summed first, as apply_f_band does
                         double dFp = 0.0;
     #pragma unroll
-                        for (int i = 0; i < MMAX; ++i)
+                        for (int i = 0; i < MM; ++i)
                             if (i < fp.n && t > fp.lo[i] && t <= fp.hi[i]) dFp += cfp[r][i];
                         if (dFp != 0.0) F[r] += dFp;
                     }
@@ -1051,9 +1064,9 @@ __device__ __forceinline__ void pair_band_block(const Dims &d, const Consts &c, 
         const int j = r_lo + wave + r * MVW;
         if (j >= r_hi) continue;
         double *Fr = w.F + ((size_t)b * d.Mp + j) * d.Tp;
-        double cfr[MMAX];                                  // this row's coefficients: the prefetched ones, or formed now
+        double cfr[MM];                                  // this row's coefficients: the prefetched ones, or formed now
 #pragma unroll
-        for (int i = 0; i < MMAX; ++i) {
+        for (int i = 0; i < MM; ++i) {
             if (PREF) cfr[i] = cfb[PREF ? r : 0][i];
             else cfr[i] = i < fp.n ? c.Cstar[(size_t)fp.m[i] * d.Kp0 + j] * c.invN[fp.m[i]] * (double)(-fp.dsrc[i]) : 0.0;
         }
@@ -1063,7 +1076,7 @@ __device__ __forceinline__ void pair_band_block(const Dims &d, const Consts &c, 
                 const int t = fp.LO + q * WAVE + lane;
                 double dFp = 0.0;
 #pragma unroll
-                for (int i = 0; i < MMAX; ++i)
+                for (int i = 0; i < MM; ++i)
                     if (i < fp.n && t > fp.lo[i] && t <= fp.hi[i]) dFp += cfr[i];
                 if (t <= fp.HI && dFp != 0.0) Fr[t] = Fpre[PREF ? r : 0][q] + dFp;
             }
@@ -1071,7 +1084,7 @@ __device__ __forceinline__ void pair_band_block(const Dims &d, const Consts &c, 
             for (int t = fp.LO + lane; t <= fp.HI; t += WAVE) {
                 double dFp = 0.0;
 #pragma unroll
-                for (int i = 0; i < MMAX; ++i)
+                for (int i = 0; i < MM; ++i)
                     if (i < fp.n && t > fp.lo[i] && t <= fp.hi[i]) dFp += cfr[i];
                 if (dFp != 0.0) Fr[t] = ld_band<SOLO>(Fr + t) + dFp;
             }
@@ -1088,6 +1101,7 @@ __device__ __forceinline__ void pair_band_block(const Dims &d, const Consts &c, 
 // emptied when the step began and it has loaded nothing of the planes since: plain loads.
 // slot: the sweep's trace slot, from the sweep counter as the launch found it (role 0 advances it in this very step); a
 // sweep that is not recorded (thinning, trace_slot.h) still applies the F band and only skips the copy.
+template <int MM>
 __device__ __forceinline__ void pair_band_finish(const Dims &d, const Consts &c, const Work &w, const SamplerCfg &s,
                                                  const Chains &ch, int b, int bx, int nband, unsigned token, unsigned slot,
                                                  int record) {
@@ -1105,15 +1119,15 @@ __device__ __forceinline__ void pair_band_finish(const Dims &d, const Consts &c,
     __syncthreads();
     for (int m = r_lo + wave; m < r_hi; m += MVW) {
         if (fp.valid == 1) {
-            double coef[MMAX];
+            double coef[MM];
 #pragma unroll
-            for (int i = 0; i < MMAX; ++i)
+            for (int i = 0; i < MM; ++i)
                 coef[i] = i < fp.n ? c.Cstar[(size_t)fp.m[i] * d.Kp0 + m] * c.invN[fp.m[i]] * (double)(-fp.dsrc[i]) : 0.0;
             double *Fr = w.F + ((size_t)b * d.Mp + m) * d.Tp;
             for (int t = fp.LO + lane; t <= fp.HI; t += WAVE) {
                 double dF = 0.0;
 #pragma unroll
-                for (int i = 0; i < MMAX; ++i)
+                for (int i = 0; i < MM; ++i)
                     if (i < fp.n && t > fp.lo[i] && t <= fp.hi[i]) dF += coef[i];
                 if (dF != 0.0) Fr[t] += dF;
             }
@@ -1154,7 +1168,7 @@ __device__ __forceinline__ void pair_band_finish(const Dims &d, const Consts &c,
 // One pair of updates by the workgroup in `slot` of chain b: the body of k_move_pair (one launch per pair) and of one
 // step of k_move_pairs (every pair of a sweep in one launch).  nroles: role slots of the grid (the speculative roles in
 // the low slots, role 0 in the last), nband: band workgroups per chain that take part in THIS pair (0: none).
-template <int NCH, bool SOLO>
+template <int NCH, bool SOLO, int MM>
 __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const Work &w, const SamplerCfg &s, const Chains &ch,
                                           MoveSpec se, MoveSpec next, MoveSpec se_next, int have_prev, int have_pre, int pbuf,
                                           int lidx, int dbg, int nband, int nroles, int slot, int b, int fin = 0,
@@ -1177,15 +1191,15 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
     if (slot >= nroles) {                                  // band workgroups (the highest block ids)
         if (nband == 0) return;
         if (fin) {                                         // the closing step of k_move_pairs: they finish the sweep
-            pair_band_finish(d, c, w, s, ch, b, slot - nroles, nband, pair_token(sweep0, lidx), tslot, fin & 2);
+            pair_band_finish<MM>(d, c, w, s, ch, b, slot - nroles, nband, pair_token(sweep0, lidx), tslot, fin & 2);
             return;
         }
         const unsigned tok = pair_token(ch.sweep[b], lidx);
         const bool r1 = next.kind >= 0 && nroles >= 2, r2 = se_next.kind >= 0 && nroles == 3;
         if ((d.M + nband - 1) / nband > 2 * MVW)              // (uniform) more than 16 rows per band workgroup: four per wave
-            pair_band_block<SOLO, 4>(d, c, w, s, ch, b, slot - nroles, nband, tok, r1, r2, pbuf ^ 1, slot, lidx);
+            pair_band_block<SOLO, 4, MM>(d, c, w, s, ch, b, slot - nroles, nband, tok, r1, r2, pbuf ^ 1, slot, lidx);
         else
-            pair_band_block<SOLO, 2>(d, c, w, s, ch, b, slot - nroles, nband, tok, r1, r2, pbuf ^ 1, slot, lidx);
+            pair_band_block<SOLO, 2, MM>(d, c, w, s, ch, b, slot - nroles, nband, tok, r1, r2, pbuf ^ 1, slot, lidx);
         return;
     }
     const int role = slot == nroles - 1 ? 0 : slot + 1;
@@ -1284,8 +1298,8 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
     }
     psi = w.scal[(size_t)b * NSCAL + SC_PSI];
     QSTAMP(slot, lidx, 6);
-    if (do_se && !pre_avail) mv_draw(s, ch, b, se, sm_se, T);
-    if (role != 0 || do_nx) mv_draw(s, ch, b, mine, sm_nx, T);
+    if (do_se && !pre_avail) mv_draw<MM>(s, ch, b, se, sm_se, T);
+    if (role != 0 || do_nx) mv_draw<MM>(s, ch, b, mine, sm_nx, T);
     QSTAMP(slot, lidx, 14);
     if (have_prev) {
         if (tid >= 64 && tid < 64 + MOVE_DW) reinterpret_cast<int *>(&pendA)[tid - 64] = ld_i;
@@ -1350,7 +1364,7 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
 #endif
         QSTAMP(slot, lidx, 1);
         mv_rows_to_lds(d, w, s, b, mine, pre_ok, pre_nx, fix, L, rtl);
-        mv_propose<NCH>(d, w, s, ch, b, mine, sm_nx, L, ltab);
+        mv_propose<NCH, MM>(d, w, s, ch, b, mine, sm_nx, L, ltab);
         QSTAMP(slot, lidx, 2);
         RSTAMP(10);
         Move *out = (role == 1 ? ch.mv : ch.mvs) + (size_t)(pbuf ^ 1) * s.B + b;
@@ -1365,7 +1379,7 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
         const Move *fpp = (pend_acc && pendp->any_dI) ? pendp : nullptr;
         double *od = role == 1 ? ch.Down + (((size_t)(pbuf ^ 1) * 2 + 0) * s.B + b) * 2
                                : ch.DownS + ((size_t)(pbuf ^ 1) * s.B + b) * 2;
-        mv_own_rows_to_down(d, c, w, b, sm_nx.mv, psi, ltab, fpp, sm_nx.dred, od);
+        mv_own_rows_to_down<MM>(d, c, w, b, sm_nx.mv, psi, ltab, fpp, sm_nx.dred, od);
         QSTAMP(slot, lidx, 3);
         RSTAMP(11);
         if (nband > 0) {                                   // band workgroups: this role reads F no more, its output is in L2
@@ -1420,7 +1434,7 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
                 hs_th += dth0; hs_cn += dcn0;
                 hs[HS_LP_THETA] = hs_th; hs[HS_LP_CONST] = hs_cn;
             }
-            mv_trace(s, ch, b, mv, pend_acc ? 1 : 0, tr_slot, hs_th + hs_cn);
+            mv_trace<MM>(s, ch, b, mv, pend_acc ? 1 : 0, tr_slot, hs_th + hs_cn);
         }
         lds_barrier();
     }
@@ -1458,19 +1472,19 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
         if (!use_pre) {
             if (pre_avail) {                                // not drawn at entry: draw the uniforms and the header now
                 lds_barrier();
-                mv_draw(s, ch, b, se, sm_se, T);
+                mv_draw<MM>(s, ch, b, se, sm_se, T);
             }
             // the pending update was of the other plane (tgt 1): nothing to correct in plane 0's totals
             mv_rows_to_lds(d, w, s, b, se, pre_ok, pre_se, nullptr, L, rtl);
             PSTAMP(2);
-            mv_propose<NCH>(d, w, s, ch, b, se, sm_se, L, ltab);
+            mv_propose<NCH, MM>(d, w, s, ch, b, se, sm_se, L, ltab);
             PSTAMP(3);
         }
         const Move &mv = sm_se.mv;
         if (use_pre && fpp == nullptr) {
             dth = pre_down[0]; dcn = pre_down[1];           // F under the proposal's rows is what role 2 saw
         } else {
-            if (mv.valid && mv.n > 0) own_rows_delta<MVB>(d, c, w, b, mv, psi, 0, M, ltab, dth, dcn, fpp);
+            if (mv.valid && mv.n > 0) own_rows_delta<MVB, MM>(d, c, w, b, mv, psi, 0, M, ltab, dth, dcn, fpp);
             PSTAMP(4);
             mv_sum2(dth, dcn, sm_se.dred);
         }
@@ -1489,7 +1503,7 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
                 hs_th += dth; hs_cn += dcn;
                 hs[HS_LP_THETA] = hs_th; hs[HS_LP_CONST] = hs_cn;
             }
-            mv_trace(s, ch, b, mv, s_acc_se, tr_slot, hs_th + hs_cn);
+            mv_trace<MM>(s, ch, b, mv, s_acc_se, tr_slot, hs_th + hs_cn);
         }
         __syncthreads();             // a re-drawn proposal in (3) must see the state written above
         // band workgroups: the planes are final (token 5); which descriptor stands they learn from the last token
@@ -1508,7 +1522,7 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
             const Move *fix = (pend_acc && pendp->tgt == next.tgt) ? pendp : nullptr;
             mv_rows_to_lds(d, w, s, b, next, pre_ok, pre_nx, fix, L, rtl);
             PSTAMP(6);
-            mv_propose<NCH>(d, w, s, ch, b, next, sm_nx, L, ltab, /*rows_only=*/true);
+            mv_propose<NCH, MM>(d, w, s, ch, b, next, sm_nx, L, ltab, /*rows_only=*/true);
         }
         if (tid == 0) {
             int conf = late ? 1 : 0;                         // role 1 was not there in time: do not trust it
@@ -1525,10 +1539,10 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
         }
         lds_barrier();
         if (s_conf) {                                        // rare: draw it again from the final state
-            mv_propose<NCH>(d, w, s, ch, b, next, sm_nx, L, ltab);
+            mv_propose<NCH, MM>(d, w, s, ch, b, next, sm_nx, L, ltab);
             move_copy(ch.mvfix + (size_t)(pbuf ^ 1) * s.B + b, &sm_nx.mv, MVB - WAVE);
             const Move *fpp = (pend_acc && pendp->any_dI) ? pendp : nullptr;
-            mv_own_rows_to_down(d, c, w, b, sm_nx.mv, psi, ltab, fpp, sm_nx.dred,
+            mv_own_rows_to_down<MM>(d, c, w, b, sm_nx.mv, psi, ltab, fpp, sm_nx.dred,
                                 ch.Down + (((size_t)(pbuf ^ 1) * 2 + 1) * s.B + b) * 2);
         }
         PSTAMP(7);
@@ -1564,10 +1578,10 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
     }
 }
 
-template <int NCH>
-__global__ __launch_bounds__(MVB) void k_move_pair(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, MoveSpec se,
-                                                   MoveSpec next, MoveSpec se_next, int have_prev, int have_pre,
-                                                   int pbuf, int nbk, int lidx, int dbg, int nband) {
+template <int NCH, int MM>
+__device__ __forceinline__ void move_pair_body(const Dims &d, const Consts &c, const Work &w, const SamplerCfg &s, const Chains &ch,
+                                               MoveSpec se, MoveSpec next, MoveSpec se_next, int have_prev, int have_pre,
+                                               int pbuf, int nbk, int lidx, int dbg, int nband) {
     debug_skew(d);
     // block id = slot * nbk + chain with the speculative roles in the low slots: they are dispatched first,
     // so an authoritative workgroup never holds a CU waiting for a partner that has not been placed yet,
@@ -1575,10 +1589,23 @@ __global__ __launch_bounds__(MVB) void k_move_pair(Dims d, Consts c, Work w, Sam
     const int nroles = (int)gridDim.x / nbk - nband, slot = (int)blockIdx.x / nbk;
     const int b = d.b0 + (int)blockIdx.x - slot * nbk;
     if (d.nlive > 0 && (int)blockIdx.x - slot * nbk >= d.nlive) return;             // a chain of the layout that does not exist
-    pair_step<NCH, false>(d, c, w, s, ch, se, next, se_next, have_prev, have_pre, pbuf, lidx, dbg, nband, nroles, slot, b);
+    pair_step<NCH, false, MM>(d, c, w, s, ch, se, next, se_next, have_prev, have_pre, pbuf, lidx, dbg, nband, nroles, slot, b);
     const int b_stamp = b - d.b0;
     (void)b_stamp;
     QSTAMP(slot, lidx, 8);
+}
+// the instances: m <= MM_SMALL under the plain name, every m <= MMAX as _m4 (the host's move_pair_fn picks)
+template <int NCH>
+__global__ __launch_bounds__(MVB) void k_move_pair(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, MoveSpec se,
+                                                   MoveSpec next, MoveSpec se_next, int have_prev, int have_pre,
+                                                   int pbuf, int nbk, int lidx, int dbg, int nband) {
+    move_pair_body<NCH, MM_SMALL>(d, c, w, s, ch, se, next, se_next, have_prev, have_pre, pbuf, nbk, lidx, dbg, nband);
+}
+template <int NCH>
+__global__ __launch_bounds__(MVB) void k_move_pair_m4(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, MoveSpec se,
+                                                      MoveSpec next, MoveSpec se_next, int have_prev, int have_pre,
+                                                      int pbuf, int nbk, int lidx, int dbg, int nband) {
+    move_pair_body<NCH, MMAX>(d, c, w, s, ch, se, next, se_next, have_prev, have_pre, pbuf, nbk, lidx, dbg, nband);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1664,9 +1691,9 @@ __device__ __forceinline__ void pair_debug_delay(int dbg, int slot, int nroles, 
         for (int i = 0; i < 9; ++i) __builtin_amdgcn_s_sleep(127);
 }
 
-template <int NCH>
-__global__ __launch_bounds__(MVB) void k_move_pairs(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, int npairs, int pre_on,
-                                                    int nbk, int dbg, int nband, unsigned pbase, int fin) {
+template <int NCH, int MM>
+__device__ __forceinline__ void move_pairs_body(const Dims &d, const Consts &c, const Work &w, const SamplerCfg &s, const Chains &ch,
+                                                int npairs, int pre_on, int nbk, int dbg, int nband, unsigned pbase, int fin) {
     debug_skew(d);
     const int nroles = (int)gridDim.x / nbk - nband, slot = (int)blockIdx.x / nbk;   // 3 roles
     const int b = d.b0 + (int)blockIdx.x - slot * nbk;
@@ -1687,7 +1714,7 @@ __global__ __launch_bounds__(MVB) void k_move_pairs(Dims d, Consts c, Work w, Sa
         const MoveSpec nx = closing ? MoveSpec{-2, 0, 0, 0} : MoveSpec{half, 1, 2 * half + 1, scan};
         const MoveSpec se_next = pre ? MoveSpec{nh, 0, 2 * nh, nscan} : none;
         if (dbg & PAIR_DBG_DELAYS) pair_debug_delay(dbg, slot, nroles, pair, b);
-        pair_step<NCH, true>(d, c, w, s, ch, se, nx, se_next, pair > 0 ? 1 : 0, (pair > 0 && pre_on && !closing) ? 1 : 0, pair & 1,
+        pair_step<NCH, true, MM>(d, c, w, s, ch, se, nx, se_next, pair > 0 ? 1 : 0, (pair > 0 && pre_on && !closing) ? 1 : 0, pair & 1,
                        closing ? 62 : pair, closing ? 0 : dbg, (closing && !fin) ? 0 : nband, nroles, slot, b, closing ? fin : 0, sweep0,
                        pair - 1, tslot);
         if (closing) break;
@@ -1698,6 +1725,16 @@ __global__ __launch_bounds__(MVB) void k_move_pairs(Dims d, Consts c, Work w, Sa
         else pair_band_next_step();
         QSTAMP(slot, pair, 9);
     }
+}
+template <int NCH>
+__global__ __launch_bounds__(MVB) void k_move_pairs(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, int npairs, int pre_on,
+                                                    int nbk, int dbg, int nband, unsigned pbase, int fin) {
+    move_pairs_body<NCH, MM_SMALL>(d, c, w, s, ch, npairs, pre_on, nbk, dbg, nband, pbase, fin);
+}
+template <int NCH>
+__global__ __launch_bounds__(MVB) void k_move_pairs_m4(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, int npairs, int pre_on,
+                                                       int nbk, int dbg, int nband, unsigned pbase, int fin) {
+    move_pairs_body<NCH, MMAX>(d, c, w, s, ch, npairs, pre_on, nbk, dbg, nband, pbase, fin);
 }
 
 inline size_t k_move_pa2_lds_bytes(const Dims &d) {

@@ -27,8 +27,15 @@
 
 namespace seir {
 
-constexpr int MMAX = 4;           // upper bound on config["m"]
-constexpr int NHS = 32;           // per-chain HMC scalar block
+constexpr int MMAX = 4;           // upper bound on config["m"]: sizes everything that has a layout (Move, the trace columns,
+                                  // MvShared::u, the hand-off words, the Philox slot numbers)
+// The event-update code is instantiated per bound MM <= MMAX on the sub-moves its loops run over (template parameter MM:
+// fully unrolled loops, and the arrays that live inside a function): MM_SMALL serves m <= 2 -- the bench, the reference's
+// example configuration, every BASELINE configuration -- under the kernels' plain names, MMAX every m under `<name>_m4`.
+// A sub-move i >= MM does not exist for an instance: it draws nothing for it, adds nothing, and writes zeros to its trace
+// columns -- what the MMAX instance does with a sub-move i >= Move::n.  The host picks by SamplerCfg::mmax (move_mm).
+constexpr int MM_SMALL = 2;
+constexpr int NHS = 32;          // per-chain HMC scalar block
 enum {
     HS_EPS = 0,       // step size used by the current/next HMC step
     HS_LP_THETA,      // prior + jac + S->E + I->R terms at (q, events)
@@ -2467,7 +2474,8 @@ struct MoveSpec { int kind, tgt, slot, scan; };   // slot 0..3 = S->E move, E->I
 // S->E kernel passes the whole range).  NT threads of the calling block take part.
 // fp != nullptr: an accepted E->I update whose F band has not been written yet (see Chains::fpend);
 // its contribution is added to the F values read here.
-template <int NT>
+// MM: the instance's bound on the sub-moves of mv and of fp (MM_SMALL or MMAX, above); the sums run over i < MM in order.
+template <int NT, int MM>
 __device__ __forceinline__ void own_rows_delta(const Dims &d, const Consts &c, const Work &w, int b, const Move &mv,
                                                double psi, int r_lo, int r_hi, const double2 *ltab, double &dth,
                                                double &dcn, const Move *fp = nullptr) {
@@ -2481,11 +2489,11 @@ __device__ __forceinline__ void own_rows_delta(const Dims &d, const Consts &c, c
     // every updated row (an E->I-type update: F moves under all of them in every window); a day that lies in two
     // windows is taken with the first.  Two event-time moves at distant days made the hull -- and with it the number
     // of (mostly idle) threads -- several times the days that matter, and kept the split below from applying.
-    int wpre[MMAX + 1];
+    int wpre[MM + 1];
     wpre[0] = 0;
 #pragma unroll
-    for (int i = 0; i < MMAX; ++i) wpre[i + 1] = wpre[i] + (i < mv.n ? mv.hi[i] - mv.lo[i] + 1 : 0);
-    const int total_w = wpre[MMAX];
+    for (int i = 0; i < MM; ++i) wpre[i + 1] = wpre[i] + (i < mv.n ? mv.hi[i] - mv.lo[i] + 1 : 0);
+    const int total_w = wpre[MM];
     const int total = mv.tgt == 1 ? mv.n * total_w : total_w;
     // A cell's difference is three independent pieces: the S->E term (one or two series of log(1 - e^-r)) and two
     // differences of binomial coefficients (three log-factorials each).  Each piece of each cell is an item of its own
@@ -2510,13 +2518,13 @@ __device__ __forceinline__ void own_rows_delta(const Dims &d, const Consts &c, c
         if (mv.tgt == 1) { i0 = cell / total_w; pos = cell - i0 * total_w; }
         int k = 0, p0 = 0;
 #pragma unroll
-        for (int i = 1; i < MMAX; ++i)
+        for (int i = 1; i < MM; ++i)
             if (i < mv.n && pos >= wpre[i]) { k = i; p0 = wpre[i]; }
         const int t = mv.lo[k] + (pos - p0);
         if (mv.tgt == 0) i0 = k;
         bool dup = false;
 #pragma unroll
-        for (int i = 0; i < MMAX - 1; ++i) dup |= (mv.tgt == 1 && i < k && t >= mv.lo[i] && t <= mv.hi[i]);
+        for (int i = 0; i < MM - 1; ++i) dup |= (mv.tgt == 1 && i < k && t >= mv.lo[i] && t <= mv.hi[i]);
         if (dup) continue;
         const int j = mv.m[i0];
         if (j < r_lo || j >= r_hi) continue;
@@ -2535,25 +2543,25 @@ __device__ __forceinline__ void own_rows_delta(const Dims &d, const Consts &c, c
             bool f_moves = false;
             if (mv.tgt == 1) {
 #pragma unroll
-                for (int i = 0; i < MMAX; ++i) f_moves |= (i < mv.n && t > mv.lo[i] && t <= mv.hi[i]);
+                for (int i = 0; i < MM; ++i) f_moves |= (i < mv.n && t > mv.lo[i] && t <= mv.hi[i]);
             }
             if (dS == 0 && dE == 0 && dI == 0 && dkt == 0 && !f_moves) continue;
             const int dk0 = mv.tgt == 0 ? dkt : 0, dk1 = mv.tgt == 1 ? dkt : 0;
             if (mask & 1) {
-                double coef[MMAX];
+                double coef[MM];
 #pragma unroll
-                for (int i = 0; i < MMAX; ++i)
+                for (int i = 0; i < MM; ++i)
                     coef[i] = (i < mv.n && mv.tgt == 1)
                                   ? c.Cstar[(size_t)mv.m[i] * d.Kp0 + j] * c.invN[mv.m[i]] * (double)(-mv.dsrc[i])
                                   : 0.0;
-                double cfp[MMAX];
+                double cfp[MM];
 #pragma unroll
-                for (int i = 0; i < MMAX; ++i)
+                for (int i = 0; i < MM; ++i)
                     cfp[i] = (fp && i < fp->n) ? c.Cstar[(size_t)fp->m[i] * d.Kp0 + j] * c.invN[fp->m[i]] * (double)(-fp->dsrc[i])
                                                : 0.0;
                 double dF = 0.0;
 #pragma unroll
-                for (int i = 0; i < MMAX; ++i)
+                for (int i = 0; i < MM; ++i)
                     if (i < mv.n && t > mv.lo[i] && t <= mv.hi[i]) dF += coef[i];
                 const double S = w.St[0][rowoff + t], I = w.St[2][rowoff + t], kse = w.K[0][rowoff + t];
                 const double eb = w.eb[(size_t)b * d.Mp + j];
@@ -2561,7 +2569,7 @@ __device__ __forceinline__ void own_rows_delta(const Dims &d, const Consts &c, c
                 if (fp) {                                  // summed first, as apply_f_band does: F + (c0 + c1) is then
                     double dFp = 0.0;                      // bit for bit the value the band will leave in memory
 #pragma unroll
-                    for (int i = 0; i < MMAX; ++i)
+                    for (int i = 0; i < MM; ++i)
                         if (i < fp->n && t > fp->lo[i] && t <= fp->hi[i]) dFp += cfp[i];
                     if (dFp != 0.0) F += dFp;
                 }
@@ -2611,20 +2619,20 @@ __device__ __forceinline__ void own_rows_delta(const Dims &d, const Consts &c, c
 
 // F[j][t] += sum_i Cstar[j][m_i] dI_i / N_{m_i} on each update's day window, rows [r_lo, r_hi),
 // one wave per row (NW waves in the calling block)
-template <int NW>
+template <int NW, int MM>
 __device__ __forceinline__ void apply_f_band(const Dims &d, const Consts &c, const Work &w, int b, const Move &mv,
                                              int r_lo, int r_hi) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (int j = r_lo + wave; j < r_hi; j += NW) {
-        double coef[MMAX];
+        double coef[MM];
 #pragma unroll
-        for (int i = 0; i < MMAX; ++i)
+        for (int i = 0; i < MM; ++i)
             coef[i] = i < mv.n ? c.Cstar[(size_t)mv.m[i] * d.Kp0 + j] * c.invN[mv.m[i]] * (double)(-mv.dsrc[i]) : 0.0;
         double *Fr = w.F + ((size_t)b * d.Mp + j) * d.Tp;
         for (int t = mv.LO + lane; t <= mv.HI; t += WAVE) {
             double dF = 0.0;
 #pragma unroll
-            for (int i = 0; i < MMAX; ++i)
+            for (int i = 0; i < MM; ++i)
                 if (i < mv.n && t > mv.lo[i] && t <= mv.hi[i]) dF += coef[i];
             if (dF != 0.0) Fr[t] += dF;
         }
@@ -2633,7 +2641,10 @@ __device__ __forceinline__ void apply_f_band(const Dims &d, const Consts &c, con
 
 // End of a sweep in the paired form: the F band of the last accepted E->I update (k_move_delta applies
 // the others on its way in).  grid (nrb_d, B).
-__global__ __launch_bounds__(256) void k_apply_fpend(Dims d, Consts c, Work w, SamplerCfg s, Chains ch) {
+template <int MM>
+__device__ __forceinline__ void apply_fpend_body(const Dims &d, const Consts &c, const Work &w, const SamplerCfg &s,
+                                                 const Chains &ch) {
+    static_assert(MM >= 1 && MM <= MMAX, "the sub-move bound of an instance");
     __shared__ Move fp;
     debug_skew(d);
     int bx = blockIdx.x, by = blockIdx.y;
@@ -2643,7 +2654,13 @@ __global__ __launch_bounds__(256) void k_apply_fpend(Dims d, Consts c, Work w, S
     __syncthreads();
     if (fp.valid != 1) return;
     const int rows_per_blk = (d.M + s.nrb_d - 1) / s.nrb_d;
-    apply_f_band<4>(d, c, w, b, fp, bx * rows_per_blk, min(d.M, (bx + 1) * rows_per_blk));
+    apply_f_band<4, MM>(d, c, w, b, fp, bx * rows_per_blk, min(d.M, (bx + 1) * rows_per_blk));
+}
+__global__ __launch_bounds__(256) void k_apply_fpend(Dims d, Consts c, Work w, SamplerCfg s, Chains ch) {
+    apply_fpend_body<MM_SMALL>(d, c, w, s, ch);
+}
+__global__ __launch_bounds__(256) void k_apply_fpend_m4(Dims d, Consts c, Work w, SamplerCfg s, Chains ch) {
+    apply_fpend_body<MMAX>(d, c, w, s, ch);
 }
 
 // rarely taken branch of band_delta, kept out of line so that its libm calls do not set the register
@@ -2695,9 +2712,11 @@ __device__ __forceinline__ double band_delta(double S, double I, double K0, doub
 // OWN: also the updated rows' part (split forms); the paired form's instance carries none of that code
 // (fewer registers: more blocks in flight when there are many chains).
 constexpr int DELTA_THREADS = 256;   // k_move_delta: 4 waves, 2 rows each (8 waves and 4-row blocks measured slower)
-template <bool OWN>
-__global__ __launch_bounds__(DELTA_THREADS) void k_move_delta(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, int buf,
-                                                    int apply_f) {
+// MM: the instance's bound on the sub-moves (k_move_delta<OWN>: MM_SMALL, k_move_delta_m4<OWN>: MMAX)
+template <bool OWN, int MM>
+__device__ __forceinline__ void move_delta_body(const Dims &d, const Consts &c, const Work &w, const SamplerCfg &s,
+                                                const Chains &ch, int buf, int apply_f) {
+    static_assert(MM >= 1 && MM <= MMAX, "the sub-move bound of an instance");
     __shared__ Move mvA, mvB;
     __shared__ int mv_sel;
     __shared__ Move fp;
@@ -2735,7 +2754,7 @@ __global__ __launch_bounds__(DELTA_THREADS) void k_move_delta(Dims d, Consts c, 
     const Move &mv = mv_sel ? mvB : mvA;           // see load_pending() in moves_kernel.h
     if (apply_f && fp.valid == 1) {
         const int rows_per_blk = (d.M + s.nrb_d - 1) / s.nrb_d;
-        apply_f_band<NW>(d, c, w, b, fp, bx * rows_per_blk, min(d.M, (bx + 1) * rows_per_blk));
+        apply_f_band<NW, MM>(d, c, w, b, fp, bx * rows_per_blk, min(d.M, (bx + 1) * rows_per_blk));
         __syncthreads();                           // the band written above is read below
     }
 #ifdef SEIR_STAMPS
@@ -2753,19 +2772,19 @@ __global__ __launch_bounds__(DELTA_THREADS) void k_move_delta(Dims d, Consts c, 
             for (int j = r_lo + wave; j < r_hi; j += NW) {
                 bool mine = false;
 #pragma unroll
-                for (int i = 0; i < MMAX; ++i) mine |= (i < mv.n && mv.m[i] == j);
+                for (int i = 0; i < MM; ++i) mine |= (i < mv.n && mv.m[i] == j);
                 if (mine) continue;                  // wave-uniform
                 const size_t rowoff = ((size_t)b * d.Mp + j) * d.Tp;
                 const double eb = w.eb[(size_t)b * d.Mp + j];
-                double coef[MMAX];
+                double coef[MM];
 #pragma unroll
-                for (int i = 0; i < MMAX; ++i)      // Cstar is symmetric: read row m_i contiguously
+                for (int i = 0; i < MM; ++i)      // Cstar is symmetric: read row m_i contiguously
                     coef[i] = i < mv.n ? c.Cstar[(size_t)mv.m[i] * d.Kp0 + j] * c.invN[mv.m[i]] * (double)(-mv.dsrc[i])
                                        : 0.0;
                 for (int t = mv.LO + lane; t <= mv.HI; t += WAVE) {
                     double dF = 0.0;
 #pragma unroll
-                    for (int i = 0; i < MMAX; ++i)
+                    for (int i = 0; i < MM; ++i)
                         if (i < mv.n && t > mv.lo[i] && t <= mv.hi[i]) dF += coef[i];
                     if (dF == 0.0) continue;
                     const double S = w.St[0][rowoff + t], I = w.St[2][rowoff + t], kse = w.K[0][rowoff + t];
@@ -2776,7 +2795,7 @@ __global__ __launch_bounds__(DELTA_THREADS) void k_move_delta(Dims d, Consts c, 
         }
         DSTAMP(2);
         // paired form (apply_f): k_move_pair's workgroups have the updated rows' part already (Chains::Down)
-        if (OWN) own_rows_delta<DELTA_THREADS>(d, c, w, b, mv, psi, r_lo, r_hi, ltab, dth, dcn);
+        if (OWN) own_rows_delta<DELTA_THREADS, MM>(d, c, w, b, mv, psi, r_lo, r_hi, ltab, dth, dcn);
     }
     DSTAMP(3);
     dth = wave_sum(dth);
@@ -2792,13 +2811,26 @@ __global__ __launch_bounds__(DELTA_THREADS) void k_move_delta(Dims d, Consts c, 
         out[1] = e;
     }
 }
+template <bool OWN>
+__global__ __launch_bounds__(DELTA_THREADS) void k_move_delta(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, int buf,
+                                                    int apply_f) {
+    move_delta_body<OWN, MM_SMALL>(d, c, w, s, ch, buf, apply_f);
+}
+template <bool OWN>
+__global__ __launch_bounds__(DELTA_THREADS) void k_move_delta_m4(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, int buf,
+                                                       int apply_f) {
+    move_delta_body<OWN, MMAX>(d, c, w, s, ch, buf, apply_f);
+}
 
 // End of sweep: record the event tensor in the reference's [M][T][3] order.  One wave per row,
 // lanes over days (coalesced plane reads, no index division); grid (ceil(M/4), B).
 // `advanced`: the sweep counter was already incremented by the closing k_move_pa2.
 // apply_f (paired form): each wave first writes the F band of the sweep's last accepted E->I update
 // (Chains::fpend) for its row, which saves the separate k_apply_fpend launch.
-__global__ __launch_bounds__(256) void k_record(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, int advanced, int apply_f) {
+template <int MM>
+__device__ __forceinline__ void record_body(const Dims &d, const Consts &c, const Work &w, const SamplerCfg &s, const Chains &ch,
+                                            int advanced, int apply_f) {
+    static_assert(MM >= 1 && MM <= MMAX, "the sub-move bound of an instance");
     __shared__ Move fp;
     debug_skew(d);
     const int b = d.b0 + blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -2808,15 +2840,15 @@ __global__ __launch_bounds__(256) void k_record(Dims d, Consts c, Work w, Sample
         if (threadIdx.x == 0) fp = ch.fpend[b];
         __syncthreads();
         if (fp.valid == 1 && m < d.M) {
-            double coef[MMAX];
+            double coef[MM];
 #pragma unroll
-            for (int i = 0; i < MMAX; ++i)
+            for (int i = 0; i < MM; ++i)
                 coef[i] = i < fp.n ? c.Cstar[(size_t)fp.m[i] * d.Kp0 + m] * c.invN[fp.m[i]] * (double)(-fp.dsrc[i]) : 0.0;
             double *Fr = w.F + ((size_t)b * d.Mp + m) * d.Tp;
             for (int t = fp.LO + lane; t <= fp.HI; t += WAVE) {
                 double dF = 0.0;
 #pragma unroll
-                for (int i = 0; i < MMAX; ++i)
+                for (int i = 0; i < MM; ++i)
                     if (i < fp.n && t > fp.lo[i] && t <= fp.hi[i]) dF += coef[i];
                 if (dF != 0.0) Fr[t] += dF;
             }
@@ -2851,6 +2883,12 @@ __global__ __launch_bounds__(256) void k_record(Dims d, Consts c, Work w, Sample
             }
         }
     }
+}
+__global__ __launch_bounds__(256) void k_record(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, int advanced, int apply_f) {
+    record_body<MM_SMALL>(d, c, w, s, ch, advanced, apply_f);
+}
+__global__ __launch_bounds__(256) void k_record_m4(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, int advanced, int apply_f) {
+    record_body<MMAX>(d, c, w, s, ch, advanced, apply_f);
 }
 
 // Events of planes 0 and 1 inside the occult range, per row (state (re)load; afterwards every accepted

@@ -31,7 +31,8 @@
 
 using namespace seir;
 
-static_assert(plan::WAVE == WAVE && plan::CT_MAXC == CT_MAXC && plan::ROLE_SLOTS == ROLE_SLOTS,
+static_assert(plan::WAVE == WAVE && plan::CT_MAXC == CT_MAXC && plan::ROLE_SLOTS == ROLE_SLOTS && plan::MMAX == MMAX &&
+              plan::MM_SMALL == MM_SMALL && MMAX == SEIR_MMAX,
               "sweep_plan.h reads the kernels' constants");
 
 static thread_local char g_err[512] = "";
@@ -71,6 +72,7 @@ struct seir_ctx {
     int opt_skew = 0, opt_affinity = 3;     // seir_set_option
     int opt_gemm_f32 = 0;
     int opt_rt_staging_kib = 0;       // bound on the S plane of a seir_sampler_rt batch in KiB (0: RT_STAGING_BYTES)
+    int opt_generic_moves = 0;        // 1: the `_m4` event-update instances also where m <= MM_SMALL (move_mm)
     int opt_eval_form = 0;            // 0 auto (one launch where a chain's blocks share an XCD, else three), 1 four launches, 2 three
     int xcd_local = -1;               // -1 not probed yet; 1: blocks with the same id mod 8 share an XCD, eight different ones
     unsigned long long *eval_cnt = nullptr;   // [8][EVC_STRIDE] k_eval_all's counters
@@ -354,6 +356,10 @@ extern "C" int seir_set_option(seir_ctx *ctx, int32_t option, int32_t value) {
         case SEIR_OPT_EVAL_FORM:
             if (value < 0 || value > 2) return fail(SEIR_ERR_INVALID, "eval form is 0 (auto), 1 (four launches) or 2 (three launches)");
             ctx->opt_eval_form = value;
+            return 0;
+        case SEIR_OPT_GENERIC_MOVES:
+            if (value < 0 || value > 1) return fail(SEIR_ERR_INVALID, "generic_moves is 0 or 1");
+            ctx->opt_generic_moves = value;
             return 0;
         case SEIR_OPT_RT_STAGING_KIB:
             if (value < 0) return fail(SEIR_ERR_INVALID, "the staging bound is a number of KiB (0: the default)");
@@ -1299,7 +1305,7 @@ struct seir_sampler {
                                   //     sweep in one launch (k_move_pairs) where band workgroups can be part of it, else one launch per
                                   //     pair (4: always one launch per pair; 3: the same, never with band workgroups in the pair launch);
                                   // 1 = one proposal kernel per update (k_move_pa2); 2 = paired launches without the pre-draw
-    int graph_skew = 0, graph_aff = 3;   // context options the captured graph was built with
+    int graph_skew = 0, graph_aff = 3, graph_mm = 0;   // context options the captured graph was built with (graph_mm: sampler_mm)
     bool have_state = false;
     double *ev_stage = nullptr;       // [B][M][T][3] fp64 staging for set/get_state
     // --- recovery from a failed in-launch hand-off (seir_sampler_snapshot / _restore) ---
@@ -1447,9 +1453,22 @@ static decltype(&k_hmc_step<0, 1, 1>) hmc_step_fn(int stage, const Dims &d) {
     return stage == 0 ? HMC_STEP(0) : stage == 1 ? HMC_STEP(1) : HMC_STEP(2);
 #undef HMC_STEP
 }
-static decltype(&k_move_pair<6>) move_pair_fn(int nch) { return nch == 6 ? k_move_pair<6> : nch == 12 ? k_move_pair<12> : k_move_pair<16>; }
-static decltype(&k_move_pairs<6>) move_pairs_fn(int nch) { return nch == 6 ? k_move_pairs<6> : nch == 12 ? k_move_pairs<12> : k_move_pairs<16>; }
-static decltype(&k_move_pa2<6>) move_pa2_fn(int nch) { return nch == 6 ? k_move_pa2<6> : nch == 12 ? k_move_pa2<12> : k_move_pa2<16>; }
+// The event-update kernels by the day chunks of a row (move_nch) and the sub-move bound of the instance (move_mm): the
+// kernels' plain names are the MM_SMALL instances, `_m4` the ones for every m <= MMAX
+#define MOVE_FN(K_, mm_, ...) ((mm_) == MM_SMALL ? K_<__VA_ARGS__> : K_##_m4<__VA_ARGS__>)
+static decltype(&k_move_pair<6>) move_pair_fn(int nch, int mm) {
+    return nch == 6 ? MOVE_FN(k_move_pair, mm, 6) : nch == 12 ? MOVE_FN(k_move_pair, mm, 12) : MOVE_FN(k_move_pair, mm, 16);
+}
+static decltype(&k_move_pairs<6>) move_pairs_fn(int nch, int mm) {
+    return nch == 6 ? MOVE_FN(k_move_pairs, mm, 6) : nch == 12 ? MOVE_FN(k_move_pairs, mm, 12) : MOVE_FN(k_move_pairs, mm, 16);
+}
+static decltype(&k_move_pa2<6>) move_pa2_fn(int nch, int mm) {
+    return nch == 6 ? MOVE_FN(k_move_pa2, mm, 6) : nch == 12 ? MOVE_FN(k_move_pa2, mm, 12) : MOVE_FN(k_move_pa2, mm, 16);
+}
+static decltype(&k_move_delta<true>) move_delta_fn(bool own, int mm) { return own ? MOVE_FN(k_move_delta, mm, true) : MOVE_FN(k_move_delta, mm, false); }
+static decltype(&k_record) record_fn(int mm) { return mm == MM_SMALL ? k_record : k_record_m4; }
+static decltype(&k_apply_fpend) apply_fpend_fn(int mm) { return mm == MM_SMALL ? k_apply_fpend : k_apply_fpend_m4; }
+#undef MOVE_FN
 
 // seir_sampler_desc::hmc_mode / moves_mode -> the form in force (plan_sweep reads it)
 static void apply_launch_form(seir_sampler *s, int hmc_mode, int moves_mode) {
@@ -1622,11 +1641,16 @@ extern "C" int seir_sampler_create(seir_ctx *ctx, const seir_sampler_desc *ds, s
                 s->leap_occ[nst - 1] = 0;
         // k_move_pairs asks for more than half a CU's LDS (one workgroup per CU); the other event-update kernels only above
         // the default 64 KB
+        // -- for every instance this sampler can come to launch: SEIR_OPT_GENERIC_MOVES may change between two sweeps
         const int nch = move_nch(d.Tp);
-        s->pairs_lds_attr = lds_attribute((const void *)move_pairs_fn(nch), k_move_pairs_lds_bytes(d)) == hipSuccess;
         const size_t plds = k_move_pa2_lds_bytes(d);
-        for (const void *fn : {(const void *)move_pair_fn(nch), (const void *)move_pa2_fn(nch)})
-            (void)lds_attribute(fn, plds);
+        s->pairs_lds_attr = true;
+        for (int mm : {MM_SMALL, MMAX}) {
+            if (mm < move_mm(c.mmax, false)) continue;            // (m > MM_SMALL: the generic instances only)
+            s->pairs_lds_attr = lds_attribute((const void *)move_pairs_fn(nch, mm), k_move_pairs_lds_bytes(d)) == hipSuccess && s->pairs_lds_attr;
+            for (const void *fn : {(const void *)move_pair_fn(nch, mm), (const void *)move_pa2_fn(nch, mm)})
+                (void)lds_attribute(fn, plds);
+        }
     }
     if (rc) { seir_sampler_destroy(s); return rc; }
     *out = s;
@@ -1683,6 +1707,21 @@ extern "C" int seir_sampler_launch_form(seir_sampler *s, int32_t *hmc_mode, int3
 }
 
 static SweepInputs sweep_inputs(const seir_sampler *s, int g);
+
+// the instances the next sweep launches: by the sampler's m and the context's option as they are now
+static int sampler_mm(const seir_sampler *s) { return move_mm(s->cfg.mmax, s->ctx->opt_generic_moves != 0); }
+
+extern "C" int seir_move_instance(int32_t m, int32_t generic_moves) {
+    if (m < 1 || m > MMAX) return fail(SEIR_ERR_INVALID, "m=%d outside [1, %d]", m, MMAX);
+    return move_mm(m, generic_moves != 0);
+}
+
+extern "C" int seir_sampler_move_instance(seir_sampler *s, int32_t *mm) {
+    if (!s) return fail(SEIR_ERR_INVALID, "null sampler");
+    if (!mm) return fail(SEIR_ERR_INVALID, "null pointer");
+    *mm = sampler_mm(s);
+    return 0;
+}
 
 // The plan enqueue_sweep executes for the first chain group, member for member (include/seir_hip.h): host fields only.
 extern "C" int seir_sampler_sweep_plan(seir_sampler *s, seir_sweep_plan *out) {
@@ -2199,16 +2238,17 @@ static void enqueue_sweep(seir_sampler *s, int g) {
     d.aff_nb = p.move_aff ? nb : 0;
     const dim3 gm = p.move_aff ? dim3(c.nrb_d * nb) : dim3(c.nrb_d, nb);
     const size_t plds = k_move_pa2_lds_bytes(d);
+    const int mm = sampler_mm(s);                                // the instances of every event-update kernel below
     int have_prev = 0, pbuf = 0;
     if (p.moves == SweepPlan::SPLIT_MOVES) {
-        const auto pa2_fn = move_pa2_fn(p.nch);
+        const auto pa2_fn = move_pa2_fn(p.nch, mm);
         for (int scan = 0; scan < c.n_scans; ++scan)
             for (int slot = 0; slot < 4; ++slot) {
                 const MoveSpec spec{slot >= 2 ? 1 : 0, slot & 1, slot, scan};
                 hipLaunchKernelGGL(pa2_fn, gm, dim3(MVB), plds, st, d, ctx->c, ctx->w, c, s->ch, spec,
                                    have_prev, pbuf);
                 pbuf ^= 1;
-                hipLaunchKernelGGL((k_move_delta<true>), gm, dim3(DELTA_THREADS), 0, st, d, ctx->c, ctx->w, c, s->ch, pbuf, 0);
+                hipLaunchKernelGGL(move_delta_fn(true, mm), gm, dim3(DELTA_THREADS), 0, st, d, ctx->c, ctx->w, c, s->ch, pbuf, 0);
                 have_prev = 1;
             }
         if (have_prev) {
@@ -2221,7 +2261,7 @@ static void enqueue_sweep(seir_sampler *s, int g) {
         // E->I-type proposal over its band -- by k_move_delta, or by the band workgroups of the pair launch itself
         // (XCD-local hand-off, see pair_band_block)
         const int npairs = 2 * c.n_scans;
-        const auto pair_fn = move_pair_fn(p.nch);
+        const auto pair_fn = move_pair_fn(p.nch, mm);
         Dims dp = d;
         dp.nlive = p.pair_nlive;
         SamplerCfg cp = c;
@@ -2229,7 +2269,7 @@ static void enqueue_sweep(seir_sampler *s, int g) {
         if (p.moves == SweepPlan::PAIRS) {
             // every pair of the sweep and the closing step in ONE launch, resident for the whole sweep (its closing step
             // also does what k_apply_fpend / k_record are launched for in the other forms)
-            hipLaunchKernelGGL(move_pairs_fn(p.nch), dim3((3 + p.nband) * p.nbk), dim3(MVB), k_move_pairs_lds_bytes(d), st, dp, ctx->c, ctx->w, cp,
+            hipLaunchKernelGGL(move_pairs_fn(p.nch, mm), dim3((3 + p.nband) * p.nbk), dim3(MVB), k_move_pairs_lds_bytes(d), st, dp, ctx->c, ctx->w, cp,
                                s->ch, npairs, 1, p.nbk, s->pair_debug, p.nband, s->pbar_count, s->record_events ? 3 : 1);
             s->pbar_count += (unsigned)(npairs * 3);                 // what every live chain's counter shows after this launch: the roles' arrivals
         } else {
@@ -2247,20 +2287,20 @@ static void enqueue_sweep(seir_sampler *s, int g) {
                     have_pre = pre ? 1 : 0;
                     pbuf ^= 1;
                     if (!p.nband)
-                        hipLaunchKernelGGL((k_move_delta<false>), gm, dim3(DELTA_THREADS), 0, st, d, ctx->c, ctx->w, c, s->ch, pbuf, 1);
+                        hipLaunchKernelGGL(move_delta_fn(false, mm), gm, dim3(DELTA_THREADS), 0, st, d, ctx->c, ctx->w, c, s->ch, pbuf, 1);
                     have_prev = 1;
                 }
             if (have_prev) {
                 const MoveSpec none{-1, 0, 0, 0}, close{-2, 0, 0, 0};
                 hipLaunchKernelGGL(pair_fn, dim3(nb), dim3(MVB), plds, st, d, ctx->c, ctx->w, cp, s->ch, none, close, none, 1,
                                    0, pbuf, nb, 62, 0, 0);
-                if (p.fpend == SweepPlan::F_APPLY) hipLaunchKernelGGL(k_apply_fpend, gm, dim3(256), 0, st, d, ctx->c, ctx->w, c, s->ch);
+                if (p.fpend == SweepPlan::F_APPLY) hipLaunchKernelGGL(apply_fpend_fn(mm), gm, dim3(256), 0, st, d, ctx->c, ctx->w, c, s->ch);
             }
         }
     }
     d.aff_nb = 0;
     if (p.record)
-        hipLaunchKernelGGL(k_record, dim3((d.M + 3) / 4, nb), dim3(256), 0, st, d, ctx->c, ctx->w, c, s->ch, p.advance ? 0 : 1,
+        hipLaunchKernelGGL(record_fn(mm), dim3((d.M + 3) / 4, nb), dim3(256), 0, st, d, ctx->c, ctx->w, c, s->ch, p.advance ? 0 : 1,
                            p.fpend == SweepPlan::F_RECORD ? 1 : 0);
     if (p.advance) hipLaunchKernelGGL(k_advance, dim3((nb + 63) / 64), dim3(64), 0, st, s->ch, b0, nb);
 }
@@ -2278,9 +2318,9 @@ extern "C" int seir_sampler_run(seir_sampler *s, int32_t n) {
     for (int g = 0; g < s->ngroups; ++g) {
         hipStream_t st = s->gstream[g];
         HIP_TRY(hipStreamWaitEvent(st, s->ev_fork, 0));
-        if (s->use_graph && (s->graph_skew != s->ctx->opt_skew || s->graph_aff != s->ctx->opt_affinity)) {
+        if (s->use_graph && (s->graph_skew != s->ctx->opt_skew || s->graph_aff != s->ctx->opt_affinity || s->graph_mm != sampler_mm(s))) {
             drop_graph(s);                           // launch options are baked into the captured kernels
-            s->graph_skew = s->ctx->opt_skew; s->graph_aff = s->ctx->opt_affinity;
+            s->graph_skew = s->ctx->opt_skew; s->graph_aff = s->ctx->opt_affinity; s->graph_mm = sampler_mm(s);
         }
         if (s->use_graph && !s->gexec[g]) {
             HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));

@@ -11,6 +11,8 @@ namespace plan {
 constexpr int WAVE = 64;         // device_math.h
 constexpr int CT_MAXC = 16;      // logprob_kernels.h: day chunks the chunked leapfrog handles
 constexpr int ROLE_SLOTS = 64;   // sampler_kernels.h: chunk roles per chain that leave parts of the trajectory's ends
+constexpr int MMAX = 4;          // sampler_kernels.h: sub-moves of an event update (config["m"]) the library serves
+constexpr int MM_SMALL = 2;      // sampler_kernels.h: ... and those the event-update kernels have instances of their own for
 }  // namespace plan
 
 // Can a 1-D grid of per * nb blocks keep every chain whole on one XCD (xcd_affine, logprob_kernels.h)?
@@ -20,6 +22,11 @@ inline bool xcd_affinity_applies(int per, int nb) {
 
 // the moves_mode in force: k_move_pair's launch tokens cover 62 launches per sweep, so more than 30 scans take the split form
 inline int moves_form(int moves_mode, int n_scans) { return n_scans > 30 ? 1 : moves_mode; }
+// the bound on the sub-moves the event-update instances of a sweep are compiled for (every kernel of the plan's `moves`,
+// `fpend` and `record`, and k_move_delta): MM_SMALL -- the kernels' plain names -- where m allows it and the caller has not
+// asked for the generic ones (SEIR_OPT_GENERIC_MOVES), else MMAX -- the `_m4` kernels.  Not part of SweepPlan: which
+// launches a sweep makes does not depend on it
+inline int move_mm(int m, bool generic) { return (m <= plan::MM_SMALL && !generic) ? plan::MM_SMALL : plan::MMAX; }
 // tile scalars of the chunked leapfrog: 1 = column scalars only (the M-chunks sum the row partials themselves), 2 = all four
 inline int chunk_ts_mode(int Mp) { return Mp <= 512 ? 1 : 2; }
 // 64-day chunks a row of the series is held in by the proposing wave (moves_kernel.h; sampler_create caps T at 1024)

@@ -59,7 +59,17 @@ OWNERS = {
     "group_curves": ("k_group_wsums", "k_rt_trace_cells", "k_rt_cells_from_keep", "k_wb_trace_cells"),   # group_curve_kernels.h
     "ngm": ("k_ngm_rows",),                                       # the group next-generation matrix (ngm_kernels.h)
     "replay": ("k_trace_load", "k_trace_load_theta"),             # stored draws into trace slots (trace_load_kernels.h)
+    # the event-update kernels for every m <= 4; their plain names (BASE) are the instances for m <= 2 (moves_kernel.h)
+    "moves_m4": ("k_move_pairs_m4", "k_move_pair_m4", "k_move_pa2_m4", "k_move_delta_m4", "k_record_m4", "k_apply_fpend_m4"),
 }
+
+
+def move_instance_names(mm, nch):
+    """The event-update kernels of sub-move bound `mm` (seir_move_instance: 2 or 4) and `nch` 64-day chunks per row (6, 12
+    or 16), as the account spells them."""
+    suf = {2: "", 4: "_m4"}[mm]
+    return [f"k_move_pairs{suf}<{nch}>", f"k_move_pair{suf}<{nch}>", f"k_move_pa2{suf}<{nch}>", f"k_move_delta{suf}<false>",
+            f"k_move_delta{suf}<true>", f"k_record{suf}", f"k_apply_fpend{suf}"]
 
 
 def owned(res, owner):

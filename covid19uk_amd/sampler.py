@@ -522,6 +522,14 @@ class ChainSampler:
         out["moves"], out["fpend"] = _lib.PLAN_MOVES[out["moves"]], _lib.PLAN_FPEND[out["fpend"]]
         return out
 
+    def move_instance(self) -> int:
+        """The sub-move bound of the event-update instances the next sweep launches (`seir_sampler_move_instance`): 2 --
+        the kernels under their plain names, for m <= 2 -- or 4, the `_m4` kernels (m > 2, or
+        `SeirModel.set_option(generic_moves=True)`).  `kernel_resources.move_instance_names` spells the kernels."""
+        mm = ctypes.c_int32()
+        _lib.check(self._lib.seir_sampler_move_instance(self._s, ctypes.byref(mm)))
+        return int(mm.value)
+
     def _recover(self, slot: int, err: Exception):
         """A burst failed with a hand-off time-out: back to the snapshot taken at its start, one step down the ladder of
         launch forms.  Raises `err` when there is nothing further down."""
@@ -625,6 +633,16 @@ class ChainSampler:
             self._s, int(first), n, _dptr(theta),
             None if ev is None else ev.ctypes.data_as(ctypes.c_void_p), _dptr(hmc), _dptr(mv)))
         return self._as_trace(n, theta, ev, hmc, mv)
+
+    def read_move_columns(self, count: int, first: int = 0) -> np.ndarray:
+        """The move results of trace slots [first, first+count) as they are stored: [count, B, 4, 2 + 4 * MMAX] --
+        is_accepted, target_log_prob, then m, t, delta_t, x_star for all MMAX sub-moves, those beyond `m` included
+        (zeros), which `Trace.moves[...]["proposed_delta"]` cuts off."""
+        n = int(count)
+        theta, hmc = np.empty((n, self.B, self.P)), np.empty((n, self.B, 3))
+        mv = np.empty((n, self.B, 4, _lib.MOVE_TRACE))
+        _lib.check(self._lib.seir_sampler_read_trace(self._s, int(first), n, _dptr(theta), None, _dptr(hmc), _dptr(mv)))
+        return mv
 
     def read_trace_async(self, count: int, first: int, into: PinnedTrace):
         """Enqueue the device->host copy of trace slots [first, first+count) behind the sweeps queued so far;

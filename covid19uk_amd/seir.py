@@ -141,13 +141,18 @@ class SeirModel:
     def sync(self):
         _lib.check(self._lib.seir_sync(self._ctx))
 
-    def set_option(self, debug_skew=None, xcd_affinity=None, gemm_f32=None, eval_form=None, rt_staging_kib=None):
+    def set_option(self, debug_skew=None, xcd_affinity=None, gemm_f32=None, eval_form=None, rt_staging_kib=None,
+                   generic_moves=None):
         """Launch options of the context (seir_set_option): the workgroup-timing test hook, the
         chain <-> XCD block mapping and the launch form of `log_prob_dev` ("fused" -- one launch for 8 or 16 chains where the GPU
         allows it, else three -- | "three-launch" | "four-launch"; none of
         them changes a result beyond summation order), and `gemm_f32`: the mobility contraction
         with fp32 operands on the fp32 matrix instruction (BASELINE config 5; ~1e-8 relative on the log-prob).
-        `rt_staging_kib` (test hook): bound on the staging plane of a `ChainSampler.rt` batch, read by `reset_rt`."""
+        `rt_staging_kib` (test hook): bound on the staging plane of a `ChainSampler.rt` batch, read by `reset_rt`.
+        `generic_moves`: a sampler's event updates run the kernels that serve every m <= 4 (`_m4`) also where m <= 2 has
+        instances of its own; same draws bit for bit (`ChainSampler.move_instance` tells which ones run)."""
+        if generic_moves is not None:
+            _lib.check(self._lib.seir_set_option(self._ctx, _lib.OPT_GENERIC_MOVES, int(bool(generic_moves))))
         if rt_staging_kib is not None:
             _lib.check(self._lib.seir_set_option(self._ctx, _lib.OPT_RT_STAGING_KIB, int(rt_staging_kib)))
         if eval_form is not None:

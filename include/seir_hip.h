@@ -139,9 +139,13 @@ void *seir_stream(seir_ctx *ctx);                  /* hipStream_t of the context
  *   SEIR_OPT_RT_STAGING_KIB  test hook: bound in KiB on the staging plane of a seir_sampler_rt batch (0, the default:
  *                            64 MiB), read by seir_sampler_rt_reset.  A smaller bound cuts a call into more batches of
  *                            trace slots; no result depends on it
+ *   SEIR_OPT_GENERIC_MOVES   1: a sampler's event updates run the instances that serve every m <= SEIR_MMAX (the
+ *                            `_m4` kernels) also where m <= 2 has instances of its own (the kernels' plain names, the
+ *                            default); no result depends on it (speed only: the m <= 2 instances carry no code for
+ *                            sub-moves that cannot exist).  seir_sampler_move_instance tells which ones a sweep launches
  * Options are read when a launch is enqueued (for a sampler using graph replay: at capture). */
 enum { SEIR_OPT_DEBUG_SKEW = 0, SEIR_OPT_XCD_AFFINITY = 1, SEIR_OPT_GEMM_F32 = 2, SEIR_OPT_EVAL_FORM = 3,
-       SEIR_OPT_RT_STAGING_KIB = 4 };
+       SEIR_OPT_RT_STAGING_KIB = 4, SEIR_OPT_GENERIC_MOVES = 5 };
 int seir_set_option(seir_ctx *ctx, int32_t option, int32_t value);
 
 /* Device memory helpers so that a ctypes host can keep inputs resident
@@ -466,6 +470,15 @@ typedef struct seir_sweep_plan {
     int32_t reserved[5];    /* zero */
 } seir_sweep_plan;          /* 32 int32: 128 bytes */
 int seir_sampler_sweep_plan(seir_sampler *s, seir_sweep_plan *out);
+/* Which instances of the event-update kernels (the kernels of `moves`, `fpend` and `record` above, and k_move_delta) serve
+ * updates of m sub-moves: the bound on the sub-moves their code is compiled for -- 2: the kernels under their plain names
+ * (k_move_pairs<nch>, k_move_pair<nch>, k_move_pa2<nch>, k_move_delta<..>, k_record, k_apply_fpend), which serve m <= 2;
+ * SEIR_MMAX: the `_m4` kernels (k_move_pairs_m4<nch>, ...), which serve every m.  Both give the same draws bit for bit
+ * where both apply.  seir_move_instance: the rule itself -- host arithmetic, no device (generic_moves: the value of
+ * SEIR_OPT_GENERIC_MOVES); SEIR_ERR_INVALID for m outside [1, SEIR_MMAX].  seir_sampler_move_instance: what the next
+ * sweep of this sampler launches, from its m and its context's option as they are now. */
+int seir_move_instance(int32_t m, int32_t generic_moves);
+int seir_sampler_move_instance(seir_sampler *s, int32_t *mm);
 /* Test hook: raises chain `chain`'s fatal time-out counter in stream order, i.e. leaves what a timed-out wait leaves.
  * The sweeps queued behind it run with every long wait of that chain cut short and the next read of the trace fails. */
 int seir_sampler_debug_fail_handoff(seir_sampler *s, int32_t chain);
