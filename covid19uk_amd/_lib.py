@@ -298,6 +298,20 @@ _SIGNATURES = {
     "seir_sampler_load_status": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32]),
     # the state of the products, from the sampler's host fields: the binding keeps no copy of it
     "seir_sampler_product_state": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SeirProductState)]),
+    # scenario forecasts riding on the sampler's forecast; the fold of the paired differences alone on host arrays
+    "seir_sampler_scenarios_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_double_p, c_double_p, ctypes.c_int64]),
+    "seir_sampler_scenario_state": (ctypes.c_int, [ctypes.c_void_p, c_int64_p]),
+    "seir_sampler_read_scenarios": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
+                                                   ctypes.POINTER(ctypes.c_int32), c_int64_p, ctypes.POINTER(ctypes.c_uint64)]),
+    "seir_sampler_read_scenario_diffs": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), c_int64_p,
+                                                        ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32),
+                                                        ctypes.POINTER(ctypes.c_uint32)]),
+    "seir_sampler_read_scenario_draws": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_int64_p, c_int64_p]),
+    "seir_scenario_diffs": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                           ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
+                                           ctypes.POINTER(ctypes.c_int32), c_int64_p, ctypes.POINTER(ctypes.c_uint64),
+                                           ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
+                                           ctypes.POINTER(ctypes.c_uint32)]),
 }
 
 _lib = None

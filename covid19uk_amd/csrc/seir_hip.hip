@@ -1268,6 +1268,30 @@ struct DrawStore {
     long long cap = 0, stride = 0;    // draws per chain it holds; a cell's run: cap, for R_it rounded up to RT_KEEP_RUN (aligned runs)
 };
 
+// The scenarios that ride on the forecast (seir_sampler_scenarios_set; scenario_kernels.h), or K = 0: off.  Everything is
+// sized by the forecast's H and goes when that changes.  j is the forecast's (fc.acc.j): scenario and baseline are rolled
+// forward together.
+struct ScenarioSet {
+    int K = 0;
+    long long cap = 0;                // draws per chain the position stores hold
+    std::vector<double> commute;      // [K][H] on the host: W_k is formed again from the calendar of every forecast reset
+    std::vector<DevBuf> allocs;
+    double *log_shift = nullptr, *Wk = nullptr;     // [K][H]
+    int *St = nullptr;                // [3][Mp][K ndmax]
+    double *X = nullptr, *F = nullptr;              // [Mp][K ndmax]
+    double *base = nullptr;           // [K][H][ndmax]
+    int *sev = nullptr;               // [K][fc.slots * B][M][H][3]
+    MomentBufs mom[4]{};              // per scenario: the per-slot marginals (the accumulators' pointers come from acc's layout)
+    int64_t *by_day = nullptr, *state_by_day = nullptr;   // [K][cap][B][H][3] by draw position since the forecast reset
+    // ONE block, shadowed with the forecast's: per scenario the moments (sum | sumsq [c6], count [B, padded]) and the
+    // differences (sum | sumsq [c4]), then the 32-bit parts per scenario (ref [c6]; ref | lt | eq [c4]; the two flags)
+    Shadowed acc;
+    size_t c6 = 0, c4 = 0, B = 0;
+    size_t count_words() const { return (B + 31) / 32 * 32; }
+    size_t words8() const { return 2 * c6 + count_words() + 2 * c4; }
+    size_t words4() const { return c6 + 3 * c4 + 2; }
+};
+
 struct seir_sampler {
     seir_ctx *ctx = nullptr;
     SamplerCfg cfg{};
@@ -1339,6 +1363,8 @@ struct seir_sampler {
     hipEvent_t fc_ev_steps = nullptr; // behind the last upload from fc_steps_host
     bool fc_steps_pending = false;
     DrawStore keep_fc;                // int keep[B][3][M][H][cap]: position j of a cell is the draw with the forecast's j
+    std::vector<double> fc_W_host;    // [H] the commuting volume of the last forecast reset (the scenarios' W_k come from it)
+    ScenarioSet scen;                 // scenarios riding on the forecast (seir_sampler_scenarios_set)
     // --- in-sample check of the last K days (seir_sampler_check_reset ...; check_kernels.h): a Rollout with H := K ---
     Rollout ck;                       // its j is not the forecast's
     CheckCmp ck_cmp{};
@@ -1771,6 +1797,7 @@ static int moments_shadow(seir_sampler *s, int slot, bool save) {
         if (!rc) rc = acc_shadow(s->sum_acc, slot, save, st);
     }
     if (!rc && s->fc.on) rc = counted_shadow(s->fc.acc, slot, save, st);
+    if (!rc && s->fc.on && s->scen.K) rc = acc_shadow(s->scen.acc, slot, save, st);   // their count is the forecast's j
     if (!rc && s->rt.on) rc = counted_shadow(s->rt.acc, slot, save, st);
     if (!rc && s->ck.on) {
         rc = counted_shadow(s->ck.acc, slot, save, st);
@@ -2944,6 +2971,22 @@ static void groups_rollout_batch(seir_sampler *s, int which, const Dims &d, hipS
 // prepare(fb, batch) -- the user's prepare kernel on the batch's copy of r.fb, which it may amend first -- then per day the
 // contraction and k_forecast_day, then k_forecast_fold, then after_fold(fb, batch).  The draw of slot first + jj has
 // j = r.acc.j + jj; adding count to r.acc.j is left to the caller, behind whatever else it enqueues.
+// The H days of a batch, whoever rolls it: per day the contraction F = Cstar . X over `cols` columns (a multiple of 64: one
+// "chain", the columns in the place of the day index) and day(h), the caller's day launch on those columns.
+template <typename Day>
+static void rollout_day_loop(seir_ctx *ctx, const LaunchCfg &l, double *X, double *F, int cols, int H, Day day) {
+    Dims gd = l.d;
+    gd.b0 = 0;
+    gd.Tp = cols;
+    Work gw{};
+    gw.Xn = X; gw.F = F;
+    for (int h = 0; h < H; ++h) {
+        hipLaunchKernelGGL((k_gemm<64>), dim3(cols / 64, l.d.Mp / GEMM_TM, 1), dim3(gemm_threads<64>()), gemm_lds_bytes<64>(), l.st,
+                           gd, ctx->c, gw);
+        day(h);
+    }
+}
+
 template <typename Prepare, typename AfterFold>
 static int rollout_days(seir_sampler *s, const Rollout &r, int32_t first, int32_t count, Prepare prepare, AfterFold after_fold) {
     seir_ctx *ctx = s->ctx;
@@ -2952,28 +2995,26 @@ static int rollout_days(seir_sampler *s, const Rollout &r, int32_t first, int32_
     const int B = s->cfg.B, H = r.fb.H;
     // by_day is summed with atomics: zero the call's slots first
     HIP_TRY(hipMemsetAsync(r.fb.mom.by_day + (size_t)first * B * H * 3, 0, sizeof(int64_t) * count * B * H * 3, l.st));
-    Dims gd = d;                                     // the contraction's view: one "chain", the draw index as the day index
-    gd.b0 = 0;
-    Work gw{};
-    gw.Xn = r.fb.X; gw.F = r.fb.F;
     for (int j0 = 0; j0 < count; j0 += r.slots) {
         const int nj = std::min(r.slots, count - j0), ND = nj * B, ndp = ceil_to(ND, 64);
         const RolloutBatch bt{j0, nj, ND, ndp};
         ForecastBufs fb = r.fb;
         if (int rc = prepare(fb, bt)) return rc;
-        gd.Tp = ndp;
-        for (int h = 0; h < H; ++h) {
-            hipLaunchKernelGGL((k_gemm<64>), dim3(ndp / 64, d.Mp / GEMM_TM, 1), dim3(gemm_threads<64>()), gemm_lds_bytes<64>(),
-                               l.st, gd, ctx->c, gw);
+        rollout_day_loop(ctx, l, r.fb.X, r.fb.F, ndp, H, [&](int h) {
             hipLaunchKernelGGL(k_forecast_day, dim3(ndp / 64, (d.M + FC_DAY_ROWS - 1) / FC_DAY_ROWS), dim3(64 * FC_DAY_ROWS), 0,
                                l.st, d, ctx->c, fb, B, s->cfg.chain0, (int)(r.acc.j + j0), ND, ndp, h);
-        }
+        });
         hipLaunchKernelGGL(k_forecast_fold, dim3((d.M + FC_ROWS - 1) / FC_ROWS, B), dim3(64 * FC_ROWS), 0, l.st, d, fb, B,
                            first + j0, nj, ndp);
         after_fold(fb, bt);
     }
     return 0;
 }
+
+// Scenarios riding on the forecast (behind the rest of the library's kernels: scenario_kernels.h is included at the end)
+static int scenarios_begin(seir_sampler *s);
+static int scenarios_zero_slots(seir_sampler *s, int32_t first, int32_t count);
+static int scenarios_batch(seir_sampler *s, const ForecastBufs &fb, const RolloutBatch &bt, int32_t first);
 
 extern "C" int seir_sampler_forecast_reset(seir_sampler *s, int32_t horizon, const double *W, const double *weekday_c,
                                            uint64_t seed) {
@@ -2989,12 +3030,15 @@ extern "C" int seir_sampler_forecast_reset(seir_sampler *s, int32_t horizon, con
         // the steps' buffers and the draw store are sized by H as well; the stream is idle
         s->fc_steps_host.reset();
         s->keep_fc = DrawStore{};
+        s->scen = ScenarioSet{};
         S_ALLOC(fc.allocs, s->fc_steps_dev, (size_t)r.slots * s->cfg.B * horizon);
         if (rc) return rc;
         if (!s->fc_ev_steps) HIP_TRY(hipEventCreate(&s->fc_ev_steps));
         r.on = true;
     }
     if ((rc = rollout_begin(s, r, W, weekday_c, seed))) return rc;   // j = 0 empties the draw store too: it holds draws [0, j)
+    s->fc_W_host.assign(W, W + horizon);
+    if (s->scen.K && (rc = scenarios_begin(s))) return rc;           // the scenarios stay; their accumulators start again
     return s->grp_on ? groups_fit(s, 1) : 0;
 }
 
@@ -3007,11 +3051,14 @@ extern "C" int seir_sampler_forecast(seir_sampler *s, int32_t first, int32_t cou
     if ((rc = rollout_ids_left(r, FORECAST_USER, count))) return rc;
     const DrawStore &keep = s->keep_fc;
     if (keep.buf && (rc = store_holds(FORECAST_USER, r.acc.j, count, keep.cap, FORECAST_USER.keep))) return rc;
+    if (s->scen.K && (rc = store_holds(FORECAST_USER, r.acc.j, count, s->scen.cap, "seir_sampler_scenarios_set"))) return rc;
     seir_ctx *ctx = s->ctx;
     const LaunchCfg l = whole(ctx, s->cfg.B);
     const Dims &d = l.d;
     const int B = s->cfg.B, H = r.fb.H;
     if (groups_live(s, 1) && (rc = groups_zero(s, 1, first, count))) return rc;
+    if (s->scen.K && (rc = scenarios_zero_slots(s, first, count))) return rc;
+    int sc_rc = 0;
     if (log_baseline_steps) {
         // through page-locked memory indexed by trace slot, so that the call stays asynchronous; a slot's steps are
         // overwritten only once the upload that read them last has been done
@@ -3038,8 +3085,9 @@ extern "C" int seir_sampler_forecast(seir_sampler *s, int32_t first, int32_t cou
                                    keep.stride, r.acc.j + bt.j0, H, B, bt.nj, bt.ndp);
             hipLaunchKernelGGL(k_forecast_finish, dim3(bt.nj, B), dim3(64), 0, l.st, d, fb, B, first + bt.j0, bt.nj, bt.ndp);
             if (groups_live(s, 1)) groups_rollout_batch(s, 1, d, l.st, fb, first, bt);
+            if (s->scen.K && !sc_rc) sc_rc = scenarios_batch(s, fb, bt, first);   // while the batch's planes and fev live
         });
-    if (rc) return rc;
+    if (rc || (rc = sc_rc)) return rc;
     if (log_baseline_steps) { HIP_TRY(hipEventRecord(s->fc_ev_steps, l.st)); s->fc_steps_pending = true; }
     HIP_TRY(hipGetLastError());
     r.acc.j += count;
@@ -4207,4 +4255,306 @@ extern "C" int seir_sampler_load_status(seir_sampler *s, uint64_t out[8], int32_
         }
     }
     return clear ? load_words_clear(s, st) : 0;
+}
+
+// ---------------------------------------------------------------------------
+// Scenario forecasts: the fold of the paired differences (include/seir_hip.h; kernel: scenario_kernels.h)
+// ---------------------------------------------------------------------------
+#include "scenario_kernels.h"
+
+// Draws [j0, j0 + nj) per chain of the two staging tensors into a scenario's accumulators; nj <= SC_JMAX.
+static void scenario_diff_launch(const Dims &d, hipStream_t st, const ScenarioDiffBufs &o, const int *fev, const int *sev, int M,
+                                 int H, int B, int nj, bool fresh) {
+    hipLaunchKernelGGL(k_scenario_diff<SC_U>, dim3((M + SC_ROWS - 1) / SC_ROWS, B), dim3(64 * SC_ROWS), 0, st, d, o, fev, sev, M,
+                       H, B, nj, fresh ? 1 : 0);
+}
+
+extern "C" int seir_scenario_diffs(seir_ctx *ctx, const int32_t *base_events, const int32_t *scenario_events, int64_t n, int32_t B,
+                                   int32_t M, int32_t H, uint64_t folded, int32_t *ref, int64_t *sum, uint64_t *sumsq,
+                                   uint32_t *lt, uint32_t *eq, uint32_t *overflow) {
+    int rc = check_batch(ctx, 1);
+    if (rc) return rc;
+    if (!base_events || !scenario_events || !ref || !sum || !sumsq || !lt || !eq || !overflow)
+        return fail(SEIR_ERR_INVALID, "null pointer");
+    if (n < 1 || B < 1 || M < 1 || B > 65535)
+        return fail(SEIR_ERR_INVALID, "n=%lld, B=%d, M=%d: at least one of each, B at most 65535", (long long)n, B, M);
+    if (H < 1 || H > SEIR_FORECAST_MAX_H) return fail(SEIR_ERR_INVALID, "H=%d outside [1, %d]", H, SEIR_FORECAST_MAX_H);
+    if (folded > 0xffffffffull || folded + (uint64_t)n > 0xffffffffull)
+        return fail(SEIR_ERR_INVALID, "%llu draws per chain folded and %lld more: the comparison counts hold 2^32 - 1",
+                    (unsigned long long)folded, (long long)n);
+    const size_t cells = (size_t)B * M * H * SCENARIO_Q, draw = (size_t)B * M * H * 3;
+    const unsigned long long bytes = 2ull * (unsigned long long)n * draw * sizeof(int32_t) + cells * 28ull;
+    if ((rc = refuse_above_half_free(bytes, "the scenario differences need %llu bytes (2 x %lld draws x %d chains x %d locations x "
+                                            "%d days x 3 x 4)", bytes, (long long)n, B, M, H)))
+        return rc;
+    DevBuf dfev, dsev, dacc;
+    if ((rc = dfev.alloc(sizeof(int32_t) * n * draw)) || (rc = dsev.alloc(sizeof(int32_t) * n * draw)) ||
+        (rc = dacc.alloc(cells * 28 + 8)))
+        return rc;
+    // one block, the 64-bit arrays first: sum | sumsq | ref | lt | eq | overflow
+    ScenarioDiffBufs o{};
+    o.sum = dacc.as<int64_t>();
+    o.sumsq = (uint64_t *)(o.sum + cells);
+    o.ref = (int32_t *)(o.sumsq + cells);
+    o.lt = (uint32_t *)(o.ref + cells);
+    o.eq = o.lt + cells;
+    o.overflow = (unsigned *)(o.eq + cells);
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(dfev.p, base_events, sizeof(int32_t) * n * draw, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dsev.p, scenario_events, sizeof(int32_t) * n * draw, hipMemcpyHostToDevice, st));
+    if (folded) {
+        HIP_TRY(hipMemcpyAsync(o.sum, sum, sizeof(int64_t) * cells, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(o.sumsq, sumsq, sizeof(uint64_t) * cells, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(o.ref, ref, sizeof(int32_t) * cells, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(o.lt, lt, sizeof(uint32_t) * cells, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(o.eq, eq, sizeof(uint32_t) * cells, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(o.overflow, overflow, sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    } else {
+        HIP_TRY(hipMemsetAsync(o.overflow, 0, sizeof(uint32_t), st));
+    }
+    const Dims d = whole(ctx, 1).d;
+    for (int64_t j0 = 0; j0 < n; j0 += SC_JMAX) {
+        const int nj = (int)std::min<int64_t>(SC_JMAX, n - j0);
+        scenario_diff_launch(d, st, o, dfev.as<int>() + (size_t)j0 * draw, dsev.as<int>() + (size_t)j0 * draw, M, H, B, nj,
+                             folded == 0 && j0 == 0);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(sum, o.sum, sizeof(int64_t) * cells, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(sumsq, o.sumsq, sizeof(uint64_t) * cells, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(ref, o.ref, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(lt, o.lt, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(eq, o.eq, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(overflow, o.overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+// ---- scenarios riding on the sampler's forecast ----
+// Scenario k's parts of the one block (ScenarioSet::acc): the moments into mb's accumulator pointers, the differences into df.
+static void scenarios_layout(const ScenarioSet &sc, int k, MomentBufs &mb, ScenarioDiffBufs &df) {
+    uint64_t *w8 = sc.acc.buf.as<uint64_t>() + (size_t)k * sc.words8();
+    mb.sum = (int64_t *)w8;
+    mb.sumsq = w8 + sc.c6;
+    mb.count = w8 + 2 * sc.c6;
+    df.sum = (int64_t *)(w8 + 2 * sc.c6 + sc.count_words());
+    df.sumsq = w8 + 2 * sc.c6 + sc.count_words() + sc.c4;
+    uint32_t *w4 = (uint32_t *)(sc.acc.buf.as<uint64_t>() + (size_t)sc.K * sc.words8()) + (size_t)k * sc.words4();
+    mb.ref = (int32_t *)w4;
+    df.ref = (int32_t *)(w4 + sc.c6);
+    df.lt = w4 + sc.c6 + sc.c4;
+    df.eq = w4 + sc.c6 + 2 * sc.c4;
+    mb.overflow = w4 + sc.c6 + 3 * sc.c4;
+    df.overflow = mb.overflow + 1;
+}
+
+// Behind a forecast reset (and the set itself): W_k from the reset's calendar, the accumulators zero, and what the snapshots
+// hold of them dropped -- but for a slot whose snapshot holds the forecast's block: that was taken at j = 0, and so holds
+// these zeros too.
+static int scenarios_begin(seir_sampler *s) {
+    ScenarioSet &sc = s->scen;
+    const int H = s->fc.fb.H;
+    hipStream_t st = s->ctx->stream;
+    std::vector<double> wk((size_t)sc.K * H);
+    for (int k = 0; k < sc.K; ++k)
+        for (int h = 0; h < H; ++h) wk[(size_t)k * H + h] = s->fc_W_host[h] * sc.commute[(size_t)k * H + h];
+    HIP_TRY(hipMemcpyAsync(sc.Wk, wk.data(), sizeof(double) * wk.size(), hipMemcpyHostToDevice, st));
+    if (int rc = acc_zero(sc.acc, st)) return rc;
+    acc_invalidate(sc.acc);
+    for (int slot = 0; slot < 2; ++slot)
+        if (s->fc.acc.valid[slot])
+            if (int rc = acc_shadow(sc.acc, slot, true, st)) return rc;
+    HIP_TRY(hipStreamSynchronize(st));                // wk is the host's
+    return 0;
+}
+
+// by_day is summed with atomics: zero the call's slots of every scenario first.
+static int scenarios_zero_slots(seir_sampler *s, int32_t first, int32_t count) {
+    const ScenarioSet &sc = s->scen;
+    const size_t row = (size_t)s->cfg.B * s->fc.fb.H * 3;
+    for (int k = 0; k < sc.K; ++k)
+        HIP_TRY(hipMemsetAsync(sc.mom[k].by_day + (size_t)first * row, 0, sizeof(int64_t) * count * row, s->ctx->stream));
+    return 0;
+}
+
+// A batch of the forecast behind its fold: the K scenarios of the batch's draws rolled forward in one set of planes, then per
+// scenario the forecast's fold and finish on its slice, the difference fold against the forecast's staging tensor, and the
+// by-day curves into the position stores.
+static int scenarios_batch(seir_sampler *s, const ForecastBufs &fb, const RolloutBatch &bt, int32_t first) {
+    const ScenarioSet &sc = s->scen;
+    seir_ctx *ctx = s->ctx;
+    const LaunchCfg l = whole(ctx, s->cfg.B);
+    const Dims &d = l.d;
+    const int B = s->cfg.B, H = fb.H, K = sc.K, ND = bt.ND, ndp = bt.ndp, cols = K * ndp;
+    const long long j = s->fc.acc.j + bt.j0;        // the batch's first draw position
+    const ScenarioBufs sb{K, sc.log_shift, sc.Wk, sc.St, sc.X, sc.F, sc.base, sc.sev};
+    const size_t elems = (size_t)std::max(d.Mp, H) * ndp;
+    hipLaunchKernelGGL(k_scenario_begin<SC_BEGIN_THREADS>, dim3((unsigned)((elems + SC_BEGIN_THREADS - 1) / SC_BEGIN_THREADS), K),
+                       dim3(SC_BEGIN_THREADS), 0, l.st, d, ctx->c, fb, sb, ND, ndp);
+    rollout_day_loop(ctx, l, sc.X, sc.F, cols, H, [&](int h) {
+        hipLaunchKernelGGL(k_scenario_day<FC_DAY_ROWS>, dim3(cols / 64, (d.M + FC_DAY_ROWS - 1) / FC_DAY_ROWS),
+                           dim3(64 * FC_DAY_ROWS), 0, l.st, d, ctx->c, fb, sb, B, s->cfg.chain0, (int)j, ND, ndp, h);
+    });
+    const size_t slice = (size_t)ND * d.M * H * 3, row = (size_t)B * H * 3, slot0 = (size_t)(first + bt.j0);
+    for (int k = 0; k < K; ++k) {
+        ForecastBufs fk = fb;
+        ScenarioDiffBufs df{};
+        fk.fev = sc.sev + (size_t)k * slice;
+        fk.mom = sc.mom[k];
+        scenarios_layout(sc, k, fk.mom, df);
+        hipLaunchKernelGGL(k_forecast_fold, dim3((d.M + FC_ROWS - 1) / FC_ROWS, B), dim3(64 * FC_ROWS), 0, l.st, d, fk, B,
+                           first + bt.j0, bt.nj, ndp);
+        scenario_diff_launch(d, l.st, df, fb.fev, fk.fev, d.M, H, B, bt.nj, j == 0);
+        hipLaunchKernelGGL(k_forecast_finish, dim3(bt.nj, B), dim3(64), 0, l.st, d, fk, B, first + bt.j0, bt.nj, ndp);
+        const size_t at = ((size_t)k * sc.cap + (size_t)j) * row;
+        HIP_TRY(hipMemcpyAsync(sc.by_day + at, fk.mom.by_day + slot0 * row, sizeof(int64_t) * bt.nj * row, hipMemcpyDeviceToDevice, l.st));
+        HIP_TRY(hipMemcpyAsync(sc.state_by_day + at, fk.mom.state_by_day + slot0 * row, sizeof(int64_t) * bt.nj * row,
+                               hipMemcpyDeviceToDevice, l.st));
+    }
+    return 0;
+}
+
+static int scenarios_on(seir_sampler *s) {
+    if (int rc = trace_range_check(s, s->fc.on, FORECAST_USER)) return rc;
+    if (!s->scen.K) return fail(SEIR_ERR_STATE, "no scenarios are set: call seir_sampler_scenarios_set first");
+    return 0;
+}
+
+extern "C" int seir_sampler_scenarios_set(seir_sampler *s, int32_t K, const double *log_shift, const double *commute, int64_t cap) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = trace_range_check(s, s->fc.on, FORECAST_USER))) return rc;
+    if (K < 0 || K > SEIR_SCENARIO_MAX) return fail(SEIR_ERR_INVALID, "K=%d outside [0, %d]", K, SEIR_SCENARIO_MAX);
+    if (cap < 0 || cap > (1ll << FC_ID_SHIFT))
+        return fail(SEIR_ERR_INVALID, "cap=%lld outside [0, 2^%d]: the draws per chain between two resets", (long long)cap, FC_ID_SHIFT);
+    if (K == 0 || cap == 0) {
+        if ((rc = drain(s))) return rc;
+        s->scen = ScenarioSet{};
+        return 0;
+    }
+    if (s->fc.acc.j != 0)
+        return fail(SEIR_ERR_STATE, "%lld draws per chain have been forecast since the reset: scenarios are set between "
+                    "seir_sampler_forecast_reset and the first seir_sampler_forecast", s->fc.acc.j);
+    if (!log_shift || !commute) return fail(SEIR_ERR_INVALID, "null pointer");
+    const Dims &d = s->ctx->d;
+    const int H = s->fc.fb.H;
+    for (int i = 0; i < K * H; ++i) {
+        if (!std::isfinite(log_shift[i])) return fail(SEIR_ERR_INVALID, "log_shift[%d][%d] is not finite", i / H, i % H);
+        if (!std::isfinite(commute[i]) || commute[i] < 0.0)
+            return fail(SEIR_ERR_INVALID, "commute[%d][%d]=%g: finite and >= 0", i / H, i % H, commute[i]);
+    }
+    if ((rc = drain(s))) return rc;
+    s->scen = ScenarioSet{};                         // what was set before goes first; a refusal leaves the forecast without scenarios
+    const size_t B = (size_t)s->cfg.B, capT = (size_t)s->cfg.cap, Kz = (size_t)K, ndmax = (size_t)s->fc.ndmax;
+    const size_t plane = (size_t)d.Mp * Kz * ndmax, ndm = (size_t)s->fc.slots * B;
+    ScenarioSet sc;
+    sc.K = K; sc.cap = cap; sc.B = B;
+    sc.c6 = B * d.M * H * seir::SUMMARY_Q; sc.c4 = B * d.M * H * SCENARIO_Q;
+    const size_t acc_bytes = Kz * (sc.words8() * 8 + sc.words4() * 4) + 8;
+    const unsigned long long bytes = 8ull * (2 * Kz * H + 2 * plane + Kz * H * ndmax) + 4ull * (3 * plane + Kz * ndm * d.M * H * 3) +
+                                     8ull * Kz * capT * B * (2ull * H + d.M) * 3 + 16ull * Kz * (unsigned long long)cap * B * H * 3 +
+                                     acc_bytes;
+    if ((rc = refuse_above_half_free(bytes, "the scenarios need %llu bytes (%d scenarios x %zu chains x %d locations x %d days, stores of "
+                                            "%lld draws)", bytes, K, B, d.M, H, (long long)cap)))
+        return rc;
+#define SC_ALLOC(ptr, ...) if (!rc) rc = s_alloc(s, sc.allocs, &(ptr), __VA_ARGS__)
+    SC_ALLOC(sc.log_shift, Kz * H); SC_ALLOC(sc.Wk, Kz * H);
+    SC_ALLOC(sc.St, 3 * plane); SC_ALLOC(sc.X, plane); SC_ALLOC(sc.F, plane);
+    SC_ALLOC(sc.base, Kz * H * ndmax);
+    SC_ALLOC(sc.sev, Kz * ndm * d.M * H * 3);
+    for (int k = 0; k < K; ++k) {
+        SC_ALLOC(sc.mom[k].by_day, capT * B * H * 3); SC_ALLOC(sc.mom[k].by_loc, capT * B * d.M * 3);
+        SC_ALLOC(sc.mom[k].state_by_day, capT * B * H * 3);
+    }
+    SC_ALLOC(sc.by_day, Kz * (size_t)cap * B * H * 3); SC_ALLOC(sc.state_by_day, Kz * (size_t)cap * B * H * 3);
+#undef SC_ALLOC
+    if (!rc) rc = sc.acc.buf.zeroed(acc_bytes);
+    if (rc) return alloc_failed(bytes, "scenarios");
+    sc.commute.assign(commute, commute + Kz * H);
+    HIP_TRY(hipMemcpy(sc.log_shift, log_shift, sizeof(double) * Kz * H, hipMemcpyHostToDevice));
+    s->scen = std::move(sc);
+    if ((rc = scenarios_begin(s))) { s->scen = ScenarioSet{}; return rc; }
+    return 0;
+}
+
+extern "C" int seir_sampler_scenario_state(seir_sampler *s, int64_t out[4]) {
+    if (!s) return fail(SEIR_ERR_INVALID, "null sampler");
+    if (!out) return fail(SEIR_ERR_INVALID, "null pointer");
+    out[0] = s->scen.K;
+    out[1] = s->scen.K ? s->fc.fb.H : 0;
+    out[2] = s->scen.cap;
+    out[3] = s->scen.K ? s->fc.acc.j : 0;
+    return 0;
+}
+
+extern "C" int seir_sampler_read_scenarios(seir_sampler *s, uint64_t *count, int32_t *ref, int64_t *sum, uint64_t *sumsq) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = scenarios_on(s))) return rc;
+    const ScenarioSet &sc = s->scen;
+    hipStream_t st = s->ctx->stream;
+    unsigned flags[SEIR_SCENARIO_MAX] = {0, 0, 0, 0};
+    for (int k = 0; k < sc.K; ++k) {
+        MomentBufs mb{};
+        ScenarioDiffBufs df{};
+        scenarios_layout(sc, k, mb, df);
+        HIP_TRY(hipMemcpyAsync(&flags[k], mb.overflow, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        if (count) HIP_TRY(hipMemcpyAsync(count + (size_t)k * sc.B, mb.count, sizeof(uint64_t) * sc.B, hipMemcpyDeviceToHost, st));
+        if (ref) HIP_TRY(hipMemcpyAsync(ref + (size_t)k * sc.c6, mb.ref, sizeof(int32_t) * sc.c6, hipMemcpyDeviceToHost, st));
+        if (sum) HIP_TRY(hipMemcpyAsync(sum + (size_t)k * sc.c6, mb.sum, sizeof(int64_t) * sc.c6, hipMemcpyDeviceToHost, st));
+        if (sumsq) HIP_TRY(hipMemcpyAsync(sumsq + (size_t)k * sc.c6, mb.sumsq, sizeof(uint64_t) * sc.c6, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int k = 0; k < sc.K; ++k)
+        if (flags[k])
+            return fail(SEIR_ERR_STATE, "a sum of squared deviations reached 2^63: the moment accumulators of scenario %d overflowed "
+                        "(seir_sampler_forecast_reset starts them again)", k);
+    return 0;
+}
+
+extern "C" int seir_sampler_read_scenario_diffs(seir_sampler *s, int32_t *ref, int64_t *sum, uint64_t *sumsq, uint32_t *lt,
+                                                uint32_t *eq) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = scenarios_on(s))) return rc;
+    const ScenarioSet &sc = s->scen;
+    hipStream_t st = s->ctx->stream;
+    unsigned flags[SEIR_SCENARIO_MAX] = {0, 0, 0, 0};
+    for (int k = 0; k < sc.K; ++k) {
+        MomentBufs mb{};
+        ScenarioDiffBufs df{};
+        scenarios_layout(sc, k, mb, df);
+        const size_t at = (size_t)k * sc.c4;
+        HIP_TRY(hipMemcpyAsync(&flags[k], df.overflow, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        if (ref) HIP_TRY(hipMemcpyAsync(ref + at, df.ref, sizeof(int32_t) * sc.c4, hipMemcpyDeviceToHost, st));
+        if (sum) HIP_TRY(hipMemcpyAsync(sum + at, df.sum, sizeof(int64_t) * sc.c4, hipMemcpyDeviceToHost, st));
+        if (sumsq) HIP_TRY(hipMemcpyAsync(sumsq + at, df.sumsq, sizeof(uint64_t) * sc.c4, hipMemcpyDeviceToHost, st));
+        if (lt) HIP_TRY(hipMemcpyAsync(lt + at, df.lt, sizeof(uint32_t) * sc.c4, hipMemcpyDeviceToHost, st));
+        if (eq) HIP_TRY(hipMemcpyAsync(eq + at, df.eq, sizeof(uint32_t) * sc.c4, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int k = 0; k < sc.K; ++k)
+        if (flags[k])
+            return fail(SEIR_ERR_STATE, "a sum of squared deviations reached 2^63: the difference accumulators of scenario %d "
+                        "overflowed (seir_sampler_forecast_reset starts them again)", k);
+    return 0;
+}
+
+extern "C" int seir_sampler_read_scenario_draws(seir_sampler *s, int64_t first, int64_t count, int64_t *by_day, int64_t *state_by_day) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = scenarios_on(s))) return rc;
+    const ScenarioSet &sc = s->scen;
+    if (first < 0 || count < 0 || first + count > s->fc.acc.j)
+        return fail(SEIR_ERR_INVALID, "draw positions [%lld,%lld) outside the %lld draws per chain forecast since the reset",
+                    (long long)first, (long long)(first + count), s->fc.acc.j);
+    hipStream_t st = s->ctx->stream;
+    const size_t row = sc.B * (size_t)s->fc.fb.H * 3, n = (size_t)count * row;
+    for (int k = 0; k < sc.K && n; ++k) {
+        const size_t at = ((size_t)k * sc.cap + (size_t)first) * row;
+        if (by_day) HIP_TRY(hipMemcpyAsync(by_day + (size_t)k * n, sc.by_day + at, sizeof(int64_t) * n, hipMemcpyDeviceToHost, st));
+        if (state_by_day)
+            HIP_TRY(hipMemcpyAsync(state_by_day + (size_t)k * n, sc.state_by_day + at, sizeof(int64_t) * n, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
 }

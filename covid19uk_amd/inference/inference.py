@@ -26,9 +26,9 @@ from ..posterior import groups as G_mod
 from ..sampler import MOVE_KEYS, ChainSampler, Summary, mid_p
 from ..seir import SeirModel
 from .mcmc_kernel_factory import event_kernel_config, hmc_kernel_kwargs_default
-from .options import (CHECK_SEED_SALT, DIAGNOSTICS, SUMMARIES, Products, add_product_arguments, check_mode, check_seed,  # noqa: F401
+from .options import (CHECK_SEED_SALT, DIAGNOSTICS, SUMMARIES, Products, add_product_arguments, add_scenarios_argument, scenarios_override, check_mode, check_seed,  # noqa: F401
                       diagnostics_mode, forecast_mode, forecast_quantiles_mode, posterior_kwargs, product_inputs, product_overrides,
-                      resolve_products, rt_mode, rt_quantiles_mode, summaries_mode, thin_interval, within_between_mode)
+                      resolve_products, resolve_scenarios, rt_mode, rt_quantiles_mode, summaries_mode, thin_interval, within_between_mode)
 
 DTYPE = model_spec.DTYPE
 
@@ -669,11 +669,19 @@ def forecast_record(ctx):
                                                           ctx.opt.fq_probs)
     if not horizon:
         return None
+    sc, base_by_day, writes = ctx.scenarios, [], _writes(ctx, "forecast")
 
     def begin():
         s.reset_forecast(horizon, ctx.forecast_calendar[0], ctx.forecast_calendar[1], ctx.seed)   # once: the sampling phase
         if fq_probs:
             s.keep_forecast_draws(total)                    # the draw store of the quantiles: every kept draw of the phase
+        if sc:
+            s.set_scenarios(sc.log_shift, sc.commute, total)   # once, behind the reset and the draw store: they ride from now on
+
+    def flush(tr, burst):
+        if sc and getattr(tr, "forecast", None) is not None:   # the baseline's curves, for the paired differences of the draws
+            base_by_day.append(np.array(tr.forecast["forecast_by_day"]))
+        writes(tr, burst)
 
     def finish():
         fs = s.forecast_summary()
@@ -691,8 +699,51 @@ def forecast_record(ctx):
             print(f"Forecast quantiles: {', '.join(f'{p:g}' for p in fq_probs)} of cases, cumulative cases and prevalence per "
                   f"location and forecast day, exact over {total} kept draw(s) per chain and pooled over the {s.B} "
                   "chain(s) of this process, selected on the device; forecast/*_quantiles written", file=log, flush=True)
-    return Record(begin, _writes(ctx, "forecast"), finish, {},
+        if sc:
+            scenarios_write_up(ctx, sc, _stack(base_by_day, s.B, horizon, 3))
+    return Record(begin, flush, finish, {},
                   dict(forecast=forecast_steps_fn(ctx.seed, ctx.chain_ids, horizon) if walk else True))
+
+
+def scenarios_write_up(ctx, sc, base_by_day):
+    """The one read of the scenarios at the end of the run (`posterior.scenarios`; Mcmc.scenarios rides on Mcmc.forecast) and what
+    every chain's file gains: the group scenarios/ -- names, log_shift, commute [K,H], horizon, first_day, count; the moments
+    seir_mean, seir_var, state_mean, state_var [K,M,H,3]; of the paired differences to the forecast diff_mean, diff_var, p_below,
+    p_equal [K,M,H,4] (cases, cum_cases, prevalence, cum_infections) with the raw counts diff_lt, diff_eq, so that pooling over
+    files is a sum -- and per kept draw samples/scenario_by_day, scenario_state_by_day and scenario_diff_by_day [n,K,H,3], the last
+    one the scenario's curve minus samples/forecast_by_day (`base_by_day` [n,B,H,3]), formed here; with forecast_quantiles also
+    scenarios/national_diff_quantiles [Kq,K,H,3] of those differences.  One log line per scenario."""
+    from ..posterior import scenarios as SC
+    s, horizon = ctx.s, ctx.opt.horizon
+    sums, diffs, draws = s.scenario_summary(), s.scenario_diffs(), s.read_scenario_draws()
+    n = int(diffs["count"])
+    st = SC.statistics(n, diffs["ref"], diffs["sum"], diffs["sumsq"], diffs["lt"], diffs["eq"]) if n else None
+    by_day = np.moveaxis(draws["by_day"], 0, 2)             # [n,B,K,H,3]
+    state = np.moveaxis(draws["state_by_day"], 0, 2)
+    diff = by_day - np.asarray(base_by_day, np.int64)[:, :, None]
+    width = max(len(name.encode()) for name in sc.names)
+    for c, post in enumerate(ctx.posteriors):
+        post.create_dataset("scenarios/names", np.array([name.encode() for name in sc.names], dtype=f"S{width}"))
+        post.create_dataset("scenarios/log_shift", sc.log_shift)
+        post.create_dataset("scenarios/commute", sc.commute)
+        for key, v in (("horizon", horizon), ("first_day", s.T), ("count", n)):
+            post.create_dataset(f"scenarios/{key}", np.array([float(v)]))
+        mean, var = np.stack([m.mean[c] for m in sums]), np.stack([m.var[c] for m in sums])
+        post._write_moments("scenarios", mean, var)
+        if st is not None:
+            for key in ("mean", "var"):
+                post.create_dataset(f"scenarios/diff_{key}", st[key][:, c])
+            for key in ("p_below", "p_equal"):
+                post.create_dataset(f"scenarios/{key}", st[key][:, c])
+        for key in ("lt", "eq"):
+            post.create_dataset(f"scenarios/diff_{key}", diffs[key][:, c], dtype=np.int64)
+        for key, v in (("scenario_by_day", by_day), ("scenario_state_by_day", state), ("scenario_diff_by_day", diff)):
+            post.create_dataset(f"samples/{key}", np.ascontiguousarray(v[:, c]), dtype=np.int64)
+        if ctx.opt.fq_probs and n:
+            post.create_dataset("scenarios/national_diff_quantiles", draw_quantiles(diff[:, c], ctx.opt.fq_probs))
+    for k, name in enumerate(sc.names):
+        if n:
+            print(SC.run_line(name, diff[:, :, k].reshape(-1, horizon, 3)), file=ctx.log, flush=True)
 
 
 def rt_record(ctx):
@@ -919,9 +970,10 @@ def product_records(sampler, config, posteriors, log=sys.stderr, forecast_calend
     if opt.grp_rt_on and population is None:
         raise ValueError("groups_rt: run_mcmc needs population = N")
     nb, ns = int(config["num_bursts"]), int(config["num_burst_samples"])
+    scenarios = resolve_scenarios(config, opt.horizon)      # Mcmc.scenarios: a resolution of its own; empty when the key is absent
 
     ctx = types.SimpleNamespace(
-        s=sampler, opt=opt, posteriors=posteriors, log=log, seed=seed, forecast_calendar=forecast_calendar, rt_weight=rt_weight,
+        s=sampler, opt=opt, scenarios=scenarios, posteriors=posteriors, log=log, seed=seed, forecast_calendar=forecast_calendar, rt_weight=rt_weight,
         check_calendar=check_calendar, groups=groups, population=population,
         total=nb * ns if total is None else int(total),     # kept draws per chain that the products will see
         chain_ids=[getattr(sampler, "first_chain_id", 0) + c for c in range(sampler.B)],
@@ -1103,7 +1155,7 @@ def launch_forms(lay, device_arg, hmc="auto", moves="auto", env=os.environ):
 def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool_step_size=False, init_jitter=0.0,
          events_dtype="auto", hmc="auto", moves="auto", thin=None, summaries=None, diagnostics=None, diagnostics_batch=None,
          forecast=None, forecast_walk=None, rt=None, check=None, forecast_quantiles=None, within_between=None,
-         rt_quantiles=None, groups=None, groups_rt=None, groups_within_between=None, groups_ngm=None):
+         rt_quantiles=None, groups=None, groups_rt=None, groups_within_between=None, groups_ngm=None, scenarios=None):
     """Constructs and runs the MCMC (covid19uk/inference/inference.py:473-608).
 
     Multi-GPU: launched as one process per GPU, every rank runs `num_chains` chains with
@@ -1111,12 +1163,16 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     do not depend on how the job is sharded) and writes its own posterior_chain{c}.hd5; there is no
     data-path collective.  `pool_step_size` adds the one optional exchange: an all_gather of one float64
     per chain after warm-up.  `thin` (every rank is given the same value) and every product keyword override the key of
-    their name in `config`; `inference/options.py` says what each accepts and refuses."""
+    their name in `config`; `inference/options.py` says what each accepts and refuses.  `scenarios` (the mapping of a
+    `--scenarios FILE.yaml`) likewise takes the place of Mcmc.scenarios."""
+    if scenarios is not None:
+        config = dict(config, scenarios=scenarios)
     config, opt = resolve_products(config, thin=thin, summaries=summaries, diagnostics=diagnostics, diagnostics_batch=diagnostics_batch,
                                    forecast=forecast, forecast_walk=forecast_walk, rt=rt, check=check,
                                    forecast_quantiles=forecast_quantiles, within_between=within_between, rt_quantiles=rt_quantiles,
                                    groups=groups, groups_rt=groups_rt, groups_within_between=groups_within_between,
                                    groups_ngm=groups_ngm)          # every option refusal: before the data file is opened
+    resolve_scenarios(config, opt.horizon)                  # ... the scenarios' too (product_records resolves them again)
     lay = job_layout(num_chains, device)                    # before any GPU call
     cov, cases, dates = read_inference_data(data_file)
     rng = np.random.default_rng(seed)                       # same imputation on every rank: one initial state per job
@@ -1214,6 +1270,7 @@ def main(argv=None):
                         help="keep every K-th sweep of the sampling phase, thinned on the device (overrides Mcmc.thin of the "
                              "configuration; the warm-up is never thinned, the shape of the output does not depend on it)")
     add_product_arguments(parser)
+    add_scenarios_argument(parser)
     args = parser.parse_args(argv)
     if args.thin is not None and args.thin < 1:
         parser.error(f"--thin {args.thin}: the thinning interval is >= 1")
@@ -1222,7 +1279,7 @@ def main(argv=None):
     always = ("summaries", "diagnostics", "diagnostics_batch", "forecast", "forecast_walk", "rt")   # passed on even when None
     mcmc(args.data_file, args.output, config["Mcmc"], seed=args.seed, num_chains=args.chains, device=args.device,
          pool_step_size=args.pool_step_size, init_jitter=args.init_jitter, events_dtype=args.events_dtype,
-         hmc=args.hmc, moves=args.moves, thin=args.thin, **product_overrides(args, always))
+         hmc=args.hmc, moves=args.moves, thin=args.thin, **product_overrides(args, always), **scenarios_override(args))
 
 
 if __name__ == "__main__":

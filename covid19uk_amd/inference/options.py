@@ -228,6 +228,15 @@ def resolve_products(config, **overrides):
     return section, Products(**fields)
 
 
+def resolve_scenarios(config, horizon, override=None):
+    """Mcmc.scenarios (absent: off), or the mapping of a `--scenarios FILE.yaml` (`posterior.scenarios.load_spec`), against
+    the forecast's horizon (`Products.horizon`): a frozen `posterior.scenarios.Scenarios`, empty for off.  A resolution of
+    its own, beside `resolve_products`: with the key absent nothing of the products moves.  Every refusal -- scenarios without
+    a forecast, more than four, a bad name, length or value -- comes here, before any GPU call."""
+    from ..posterior.scenarios import parse_scenarios
+    return parse_scenarios(config.get("scenarios") if override is None else override, horizon)
+
+
 def posterior_kwargs(config, opt, group_table, kept):
     """The keywords of `Posterior` for the products that are on, `kept` rows in the per-draw datasets of the sampling phase."""
     days = dict(forecast=opt.horizon, rt=opt.rt_days, check=opt.check_days, within_between=opt.wb_days)
@@ -337,3 +346,21 @@ def product_overrides(args, always=()):
     if "groups" in given:
         given["groups"] = G_mod.load_spec(given["groups"])
     return {**{k: None for k in always}, **given}
+
+
+def add_scenarios_argument(parser):
+    """`--scenarios FILE.yaml` of both command lines: declared beside the product arguments, resolved by `resolve_scenarios`."""
+    parser.add_argument("--scenarios", type=str, default=None, metavar="FILE.yaml",
+                        help="what-if scenarios riding on the forecast (overrides Mcmc.scenarios; needs --forecast): a YAML mapping name: "
+                             "{transmission: f | [H floats], commute: f | [H floats], from_day: d}, at most four; every kept draw is also "
+                             "rolled forward under each scenario with the forecast's random numbers -- scenarios/* with the moments and the "
+                             "paired differences to the forecast per location and day, samples/scenario_by_day, scenario_state_by_day, "
+                             "scenario_diff_by_day")
+
+
+def scenarios_override(args):
+    """The keyword of `inference.mcmc` / `posterior.replay.replay_files` from the parsed arguments: nothing when the flag was not given."""
+    if getattr(args, "scenarios", None) is None:
+        return {}
+    from ..posterior.scenarios import load_spec
+    return dict(scenarios=load_spec(args.scenarios))

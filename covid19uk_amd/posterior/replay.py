@@ -245,7 +245,11 @@ def replay_files(data_file, files, output_file, config, seed=0, device=None, fir
         if ns < 1:
             raise ValueError(f"burst={ns}: at least one row per replay")
         config = dict(config, num_burst_samples=ns, num_bursts=-(-n // ns), thin=1)
+        if overrides.get("scenarios") is not None:                       # the mapping of --scenarios: in the place of Mcmc.scenarios
+            config = dict(config, scenarios=overrides["scenarios"])
+        overrides = {k: v for k, v in overrides.items() if k != "scenarios"}
         config, opt = inf.resolve_products(config, **overrides)          # every product refusal: before any GPU call
+        inf.resolve_scenarios(config, opt.horizon)                       # ... the scenarios' too
         if config.get("diagnostics") == "on" and n % ns:
             raise ValueError(f"diagnostics: {n} row(s) in bursts of {ns} -- the split R-hat compares half-chains of one length, "
                              "which takes whole bursts (choose --stop or --burst accordingly)")
@@ -304,7 +308,7 @@ def main(argv=None):
     from argparse import ArgumentParser
 
     import yaml
-    from ..inference.options import add_product_arguments, product_overrides
+    from ..inference.options import add_product_arguments, add_scenarios_argument, product_overrides, scenarios_override
     parser = ArgumentParser(description="Replay stored draws on the device: every product of the inference from posterior files")
     parser.add_argument("-c", "--config", type=str, required=True, help="Config file (its Mcmc section)")
     parser.add_argument("-o", "--output", type=str, required=True, help="Output file (one per input: _chain<id> is added)")
@@ -321,12 +325,13 @@ def main(argv=None):
     parser.add_argument("--events-dtype", choices=["auto", "u16", "int32"], default="auto",
                         help="width of the event counts in the device-side burst buffer")
     add_product_arguments(parser)
+    add_scenarios_argument(parser)
     args = parser.parse_args(argv)
     with open(args.config, "r") as f:
         config = yaml.load(f, Loader=yaml.FullLoader)
     replay_files(args.data_file, args.posteriors, args.output, config["Mcmc"], seed=args.seed, device=args.device, first=args.first,
                  stop=args.stop, every=args.every, burst=args.burst, first_chain_id=args.first_chain_id,
-                 events_dtype=args.events_dtype, **product_overrides(args))
+                 events_dtype=args.events_dtype, **product_overrides(args), **scenarios_override(args))
 
 
 if __name__ == "__main__":

@@ -825,6 +825,64 @@ class ChainSampler:
         ranks = Q.quantile_ranks(n, probs)
         return Q.interpolate(self.forecast_order_stats(ranks, pooled=pooled), ranks, n, probs)
 
+    # -- scenarios riding on the forecast (include/seir_hip.h, "Scenario forecasts on the device") ----------------
+    def set_scenarios(self, log_shift, commute, cap: int):
+        """K scenarios ride on the forecast from now on: `log_shift` and `commute` float64 [K, H] (`posterior.scenarios`),
+        `cap` the draws per chain the per-draw stores hold.  Between `reset_forecast` and the first `forecast`; K = 0 or
+        cap = 0 frees everything.  The library refuses what it cannot hold; the forecast then runs on without scenarios."""
+        H = self._state().forecast_H
+        ls = np.zeros((0, H)) if log_shift is None else np.ascontiguousarray(log_shift, dtype=np.float64)
+        cm = np.ones((0, H)) if commute is None else np.ascontiguousarray(commute, dtype=np.float64)
+        if ls.ndim != 2 or ls.shape != cm.shape or (ls.shape[0] and H and ls.shape[1] != H):   # H = 0: the library refuses
+            raise ValueError(f"log_shift {ls.shape} and commute {cm.shape}: need two of [K, {H}]")
+        if int(cap) < 0:
+            raise ValueError(f"cap={cap}: the number of draws per chain to keep")
+        _lib.check(self._lib.seir_sampler_scenarios_set(self._s, ls.shape[0], _dptr(ls), _dptr(cm), int(cap)))
+
+    def scenario_state(self) -> dict:
+        """K, H, cap and j (the draws per chain rolled forward since the forecast reset) as the library holds them; zeros
+        while no scenarios are set.  No device call."""
+        out = np.zeros(4, np.int64)
+        _lib.check(self._lib.seir_sampler_scenario_state(self._s, out.ctypes.data_as(_lib.c_int64_p)))
+        return dict(K=int(out[0]), H=int(out[1]), cap=int(out[2]), j=int(out[3]))
+
+    def scenario_summary(self) -> list:
+        """The scenarios' moments folded since the last `reset_forecast` (blocking): one `Summary` [B,M,H,6] per scenario."""
+        st = self.scenario_state()
+        K, shape = st["K"], (st["K"], self.B, self.M, st["H"], len(SUMMARY_QUANTITIES))
+        cnt = np.zeros((K, self.B), np.uint64)
+        ref, sm, sq = np.empty(shape, np.int32), np.empty(shape, np.int64), np.empty(shape, np.uint64)
+        u64 = ctypes.POINTER(ctypes.c_uint64)
+        _lib.check(self._lib.seir_sampler_read_scenarios(self._s, cnt.ctypes.data_as(u64), ref.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                         sm.ctypes.data_as(_lib.c_int64_p), sq.ctypes.data_as(u64)))
+        return [Summary(count=cnt[k], ref=ref[k], sum=sm[k], sumsq=sq[k]) for k in range(K)]
+
+    def scenario_diffs(self) -> dict:
+        """The accumulators of the paired differences, scenario minus forecast (blocking): `count` (draws per chain), `ref`
+        int32, `sum` int64, `sumsq` uint64, `lt`, `eq` uint32, each [K,B,M,H,4] -- cases, cum_cases, prevalence,
+        cum_infections (`posterior.scenarios.statistics` forms mean, variance and P(below) from them)."""
+        st = self.scenario_state()
+        shape = (st["K"], self.B, self.M, st["H"], 4)
+        out = dict(ref=np.empty(shape, np.int32), sum=np.empty(shape, np.int64), sumsq=np.empty(shape, np.uint64),
+                   lt=np.empty(shape, np.uint32), eq=np.empty(shape, np.uint32))
+        u32 = ctypes.POINTER(ctypes.c_uint32)
+        _lib.check(self._lib.seir_sampler_read_scenario_diffs(
+            self._s, out["ref"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), out["sum"].ctypes.data_as(_lib.c_int64_p),
+            out["sumsq"].ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), out["lt"].ctypes.data_as(u32), out["eq"].ctypes.data_as(u32)))
+        out["count"] = st["j"]
+        return out
+
+    def read_scenario_draws(self, count: int = None, first: int = 0) -> dict:
+        """The scenarios' per-draw curves by draw position since the forecast reset (blocking): `by_day` and `state_by_day`
+        int64 [K, count, B, H, 3]; `count` None: every draw from `first` on."""
+        st = self.scenario_state()
+        n = st["j"] - int(first) if count is None else int(count)
+        shape = (st["K"], max(n, 0), self.B, st["H"], 3)
+        out = dict(by_day=np.empty(shape, np.int64), state_by_day=np.empty(shape, np.int64))
+        _lib.check(self._lib.seir_sampler_read_scenario_draws(self._s, int(first), n, out["by_day"].ctypes.data_as(_lib.c_int64_p),
+                                                              out["state_by_day"].ctypes.data_as(_lib.c_int64_p)))
+        return out
+
     # -- reproduction number of the kept draws (include/seir_hip.h, "Reproduction number on the device") ----------
     def reset_rt(self, days: int, weight):
         """Enable the reproduction number (first call), zero its accumulators and count, set the window to the last `days`

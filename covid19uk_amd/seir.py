@@ -331,6 +331,41 @@ class SeirModel:
                                              mem_arg.ctypes.data_as(ip), out.ctypes.data_as(_lib.c_int64_p)))
         return out
 
+    def scenario_diffs(self, base_events, scenario_events, acc=None):
+        """The fold of a scenario's paired differences on the device (csrc/scenario_kernels.h; include/seir_hip.h,
+        seir_scenario_diffs): `base_events` and `scenario_events` int32 [n, B, M, H, 3], the simulated counts of n draws per
+        chain of the baseline and of the scenario (B, M and H the arrays' own).  `acc`: what an earlier call returned, to fold
+        these draws behind its own, or None.  Returns a dict: `count` (draws per chain folded), `ref` int32, `sum` int64, `sumsq`
+        uint64, `lt`, `eq` uint32, each [B, M, H, 4] (cases, cum_cases, prevalence, cum_infections), and `overflow` -- the
+        integers of `posterior.scenarios.fold_differences`."""
+        fev = np.ascontiguousarray(base_events, dtype=np.int32)
+        sev = np.ascontiguousarray(scenario_events, dtype=np.int32)
+        if fev.ndim != 5 or fev.shape[4] != 3 or sev.shape != fev.shape:
+            raise ValueError(f"events {fev.shape} and {sev.shape}: need two of [n, B, M, H, 3]")
+        n, B, M, H, _ = fev.shape
+        shape = (B, M, H, 4)
+        if acc is None:
+            folded = 0
+            out = dict(ref=np.zeros(shape, np.int32), sum=np.zeros(shape, np.int64), sumsq=np.zeros(shape, np.uint64),
+                       lt=np.zeros(shape, np.uint32), eq=np.zeros(shape, np.uint32))
+            ovf = np.zeros(1, np.uint32)
+        else:
+            folded = int(acc["count"])
+            out = {}
+            for key, ty in (("ref", np.int32), ("sum", np.int64), ("sumsq", np.uint64), ("lt", np.uint32), ("eq", np.uint32)):
+                out[key] = np.array(acc[key], dtype=ty, order="C")
+                if out[key].shape != shape:
+                    raise ValueError(f"acc[{key!r}] {out[key].shape}: these events need {shape}")
+            ovf = np.array([1 if acc["overflow"] else 0], np.uint32)
+        ip, up = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32)
+        _lib.check(self._lib.seir_scenario_diffs(
+            self._ctx, fev.ctypes.data_as(ip), sev.ctypes.data_as(ip), n, B, M, H, folded, out["ref"].ctypes.data_as(ip),
+            out["sum"].ctypes.data_as(_lib.c_int64_p), out["sumsq"].ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+            out["lt"].ctypes.data_as(up), out["eq"].ctypes.data_as(up), ovf.ctypes.data_as(up)))
+        out["count"] = folded + n
+        out["overflow"] = bool(ovf[0])
+        return out
+
     def group_wsums(self, v, offsets, members, weights=None):
         """Group sums of fp64 values on the device (csrc/group_curve_kernels.h; include/seir_hip.h, seir_group_wsums): `v`
         float64 [nd, L, M] (L and M the array's own), the groups a CSR pair as for `group_sums`, `weights` [nnz] aligned with

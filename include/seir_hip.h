@@ -1108,6 +1108,67 @@ typedef struct seir_product_state {
 int seir_sampler_product_state(seir_sampler *s, seir_product_state *out);
 
 /* ------------------------------------------------------------------------
+ * Scenario forecasts on the device: what-if rollouts, paired differences.
+ *
+ * A scenario is the forecast's rollout of a draw with two changes, per forecast day s: the log baseline gets
+ * log_shift[s] added (exp of it multiplies transmission) and the commuting volume is multiplied by commute[s] >= 0.  State,
+ * parameters, Philox key and counter stay the forecast's, so scenario and baseline are coupled variate by variate and the
+ * number a scenario is run for -- its difference to the baseline, per location and day, with its uncertainty -- is sharp.
+ * THE definition of a scenario and of the fold: csrc/scenario_kernels.h; of the differences and a cell's update:
+ * csrc/scenario_update.h; in NumPy: covid19uk_amd/posterior/scenarios.py.
+ *
+ * Per chain b, cell (m, s) and draw, with d_x[s] = k_x^k[m][s] - k_x^0[m][s] (scenario minus baseline, x = se, ei, ir):
+ *     0 cases           d_ir[s]
+ *     1 cum_cases       the inclusive scan of d_ir over the days
+ *     2 prevalence      I at the start of day s, scenario minus baseline: exclusive scan of d_ei minus that of d_ir (day 0: 0)
+ *     3 cum_infections  the inclusive scan of d_se
+ * Over the draws folded a cell keeps, per difference, ref (int32, the first draw's value), sum (int64) and sumsq (uint64) of
+ * the value minus ref, as the summaries do, and lt / eq (uint32), the draws whose difference is < 0 / == 0 (gt is never
+ * stored).  mean = ref + sum / n, var = (sumsq - sum^2 / n) / (n - 1), P(below) = lt / n.  Integers only: no result depends on
+ * the order of the draws, on the launch geometry or on how the draws are cut into calls.
+ * ------------------------------------------------------------------------ */
+#define SEIR_SCENARIO_MAX 4
+#define SEIR_SCENARIO_Q 4
+/* K scenarios ride on the sampler's forecast: log_shift and commute [K][H], H the horizon of the last
+ * seir_sampler_forecast_reset; cap: the draws per chain the per-draw stores hold.  Accepted between a forecast reset and the
+ * first seir_sampler_forecast, as seir_sampler_forecast_keep is (SEIR_ERR_STATE otherwise, and before any forecast reset).
+ * From then on every draw that seir_sampler_forecast rolls forward is also rolled forward under each scenario, in the same
+ * call: per scenario the forecast's moments [B][M][H][6] and per-draw marginals, the difference accumulators above, and the
+ * by_day and state_by_day curves of every draw in stores indexed by the draw's position since the forecast reset.  The
+ * forecast itself keeps its bits.  K = 0 or cap = 0 frees everything.  A forecast reset empties stores and accumulators and
+ * keeps the scenarios (W_k = W[s] * commute[k][s] is formed again from its calendar); a reset to another horizon frees them.
+ * A seir_sampler_forecast that would pass cap is refused before any launch.  SEIR_ERR_INVALID for K outside
+ * [0, SEIR_SCENARIO_MAX], cap outside [0, 2^20], a non-finite value, a negative commute, or buffers above half of the device's
+ * free memory.  The two kinds of refusal differ in what they leave: arguments refused for their values (K, cap, a
+ * non-finite value, a negative commute) and a set refused for its place (SEIR_ERR_STATE) leave the scenarios in force alone,
+ * as a refused table leaves the table in force; a set refused for memory has already dropped them (its buffers are sized
+ * with the old ones gone) -- the forecast then runs on without scenarios.  Snapshot and restore carry the accumulators with the forecast's,
+ * so a burst run again after a hand-off time-out is counted once; the stores are overwritten. */
+int seir_sampler_scenarios_set(seir_sampler *s, int32_t K, const double *log_shift, const double *commute, int64_t cap);
+/* out = K, H, cap, j (the draws per chain rolled forward since the forecast reset); zeros while no scenarios are set.  Host
+ * fields only: no device call. */
+int seir_sampler_scenario_state(seir_sampler *s, int64_t out[4]);
+/* Blocking reads; any pointer may be NULL.  The scenarios' moments: count [K][B], ref, sum, sumsq [K][B][M][H][6] as
+ * seir_sampler_read_forecast's; the difference accumulators: ref, sum, sumsq, lt, eq [K][B][M][H][4].  SEIR_ERR_STATE while no
+ * scenarios are set, or when an accumulator of what is read has overflowed. */
+int seir_sampler_read_scenarios(seir_sampler *s, uint64_t *count, int32_t *ref, int64_t *sum, uint64_t *sumsq);
+int seir_sampler_read_scenario_diffs(seir_sampler *s, int32_t *ref, int64_t *sum, uint64_t *sumsq, uint32_t *lt, uint32_t *eq);
+/* The curves of draw positions [first, first + count) since the forecast reset: by_day and state_by_day
+ * [K][count][B][H][3] (int64), as forecast_by_day and forecast_state_by_day of the forecast's marginals. */
+int seir_sampler_read_scenario_draws(seir_sampler *s, int64_t first, int64_t count, int64_t *by_day, int64_t *state_by_day);
+/* The difference fold alone, on host arrays, blocking.  base_events and scenario_events are the simulated counts of n draws
+ * per chain of the baseline and of one scenario, [n][B][M][H][3] (int32, >= 0; every row's total over the days below 2^31 and
+ * the four differences within int32, as they are for populations below 2^31).  B, M and H are the call's own, not the
+ * context's.  folded: the draws per chain that earlier calls have folded into the accumulators ref, sum, sumsq, lt, eq
+ * [B][M][H][4] and *overflow; with folded == 0 they are outputs only and the call's first draw gives ref.  *overflow is 1
+ * once some sumsq has reached 2^63 (the moments are then void), else 0.  SEIR_ERR_INVALID for a null pointer, n, B, M < 1,
+ * H outside [1, SEIR_FORECAST_MAX_H], B above 65535, folded + n above 2^32 - 1 (lt and eq are uint32), or tensors above half
+ * of the device's free memory. */
+int seir_scenario_diffs(seir_ctx *ctx, const int32_t *base_events, const int32_t *scenario_events, int64_t n, int32_t B,
+                        int32_t M, int32_t H, uint64_t folded, int32_t *ref, int64_t *sum, uint64_t *sumsq, uint32_t *lt,
+                        uint32_t *eq, uint32_t *overflow);
+
+/* ------------------------------------------------------------------------
  * Reproduction number R_it.
  *
  * calc_posterior_rit (covid19uk/posterior/reproduction_number.py:13-44): for each
