@@ -94,6 +94,8 @@ MOVE_TRACE = 2 + 4 * MMAX     # SEIR_MOVE_TRACE
 FORECAST_MAX_H = 128          # SEIR_FORECAST_MAX_H
 FORECAST_ID_SHIFT, FORECAST_MAX_CHAIN = 20, 2048   # draw id = (global chain id << 20) + j
 CHECK_MAX_DAYS = 128          # SEIR_CHECK_MAX_DAYS
+PAIR_ABS_CHUNK = 4096         # SEIR_PAIR_ABS_CHUNK
+PAIR_ABS_MAX_N = 92681        # SEIR_PAIR_ABS_MAX_N
 ORDER_STATS_MAX_RANKS = 16    # SEIR_ORDER_STATS_MAX_RANKS
 GROUPS_MAX = 256              # SEIR_GROUPS_MAX
 # csrc/trace_load.h: the codes of a loaded item (LOAD_OK = 0 ...; out[code - 1] of seir_sampler_load_status counts them)
@@ -312,6 +314,15 @@ _SIGNATURES = {
                                            ctypes.POINTER(ctypes.c_int32), c_int64_p, ctypes.POINTER(ctypes.c_uint64),
                                            ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
                                            ctypes.POINTER(ctypes.c_uint32)]),
+    # the forecast scored against later data; the sum of pairwise absolute differences alone on host arrays
+    "seir_sampler_verify_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]),
+    "seir_sampler_verify_state": (ctypes.c_int, [ctypes.c_void_p, c_int64_p]),
+    "seir_sampler_read_verify": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32),
+                                                ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)]),
+    "seir_sampler_forecast_pair_sums": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_int64_p]),
+    "seir_pair_abs_sums": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, ctypes.c_int32,
+                                          ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_int64_p,
+                                          ctypes.POINTER(ctypes.c_uint32)]),
 }
 
 _lib = None

@@ -6,6 +6,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <utility>
 
 // One hipMalloc'ed block and its only owner.  Nothing frees device memory by name: a block goes when its owner goes out of scope,
@@ -81,9 +82,17 @@ static int alloc_failed(unsigned long long bytes, const char *of_what) {
 
 // One product may take half of what is free on the device: the policy of a device that is shared, not a measurement.  The caller
 // spells out its half of the refusal ("the group sums need N bytes (shape)"); the comparison, the free figure and the tail are here.
+// Test hook: with SEIR_DEBUG_FREE_BYTES=<n> in the environment the free figure is min(the device's, n) -- for the products whose
+// buffers are too small for any device to refuse (the verification's accumulators are 32 B per cell): their refusal is then
+// exercised without a test that holds the memory of a device which others use.  Read at every call; absent, nothing changes.
 __attribute__((format(printf, 2, 3))) static int refuse_above_half_free(unsigned long long bytes, const char *need_fmt, ...) {
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (const char *cap = getenv("SEIR_DEBUG_FREE_BYTES")) {
+        char *end = nullptr;
+        const unsigned long long v = strtoull(cap, &end, 10);
+        if (end != cap && *end == '\0' && v < (unsigned long long)free_b) free_b = (size_t)v;
+    }
     if (bytes <= (unsigned long long)free_b / 2) return 0;
     char need[400];
     va_list ap;

@@ -1292,6 +1292,17 @@ struct ScenarioSet {
     size_t words4() const { return c6 + 3 * c4 + 2; }
 };
 
+// The truth the forecast is scored against (seir_sampler_verify_set; verify_kernels.h), or on = false.  Sized by the
+// forecast's H and gone when that changes; the count of the accumulators is the forecast's j (fc.acc.j).
+struct VerifySet {
+    bool on = false;
+    std::vector<DevBuf> allocs;
+    int32_t *truth = nullptr;         // [M][H], < 0: missing
+    int64_t *cum = nullptr;           // [M][H] its running total over the days, < 0 from a row's first missing day on
+    size_t c2 = 0;                    // B x M x H x 2 cells
+    Shadowed acc;                     // ONE block, shadowed with the forecast's: abs_sum [c2] uint64 | lt [c2] | eq [c2] uint32
+};
+
 struct seir_sampler {
     seir_ctx *ctx = nullptr;
     SamplerCfg cfg{};
@@ -1365,6 +1376,7 @@ struct seir_sampler {
     DrawStore keep_fc;                // int keep[B][3][M][H][cap]: position j of a cell is the draw with the forecast's j
     std::vector<double> fc_W_host;    // [H] the commuting volume of the last forecast reset (the scenarios' W_k come from it)
     ScenarioSet scen;                 // scenarios riding on the forecast (seir_sampler_scenarios_set)
+    VerifySet ver;                    // the later data the forecast is scored against (seir_sampler_verify_set)
     // --- in-sample check of the last K days (seir_sampler_check_reset ...; check_kernels.h): a Rollout with H := K ---
     Rollout ck;                       // its j is not the forecast's
     CheckCmp ck_cmp{};
@@ -1798,6 +1810,7 @@ static int moments_shadow(seir_sampler *s, int slot, bool save) {
     }
     if (!rc && s->fc.on) rc = counted_shadow(s->fc.acc, slot, save, st);
     if (!rc && s->fc.on && s->scen.K) rc = acc_shadow(s->scen.acc, slot, save, st);   // their count is the forecast's j
+    if (!rc && s->fc.on && s->ver.on) rc = acc_shadow(s->ver.acc, slot, save, st);    // and so is the verification's
     if (!rc && s->rt.on) rc = counted_shadow(s->rt.acc, slot, save, st);
     if (!rc && s->ck.on) {
         rc = counted_shadow(s->ck.acc, slot, save, st);
@@ -3015,6 +3028,9 @@ static int rollout_days(seir_sampler *s, const Rollout &r, int32_t first, int32_
 static int scenarios_begin(seir_sampler *s);
 static int scenarios_zero_slots(seir_sampler *s, int32_t first, int32_t count);
 static int scenarios_batch(seir_sampler *s, const ForecastBufs &fb, const RolloutBatch &bt, int32_t first);
+// The forecast scored against later data (verify_kernels.h, included behind scenario_kernels.h)
+static int verify_begin(seir_sampler *s);
+static void verify_batch(seir_sampler *s, const ForecastBufs &fb, const RolloutBatch &bt);
 
 extern "C" int seir_sampler_forecast_reset(seir_sampler *s, int32_t horizon, const double *W, const double *weekday_c,
                                            uint64_t seed) {
@@ -3031,6 +3047,7 @@ extern "C" int seir_sampler_forecast_reset(seir_sampler *s, int32_t horizon, con
         s->fc_steps_host.reset();
         s->keep_fc = DrawStore{};
         s->scen = ScenarioSet{};
+        s->ver = VerifySet{};
         S_ALLOC(fc.allocs, s->fc_steps_dev, (size_t)r.slots * s->cfg.B * horizon);
         if (rc) return rc;
         if (!s->fc_ev_steps) HIP_TRY(hipEventCreate(&s->fc_ev_steps));
@@ -3039,6 +3056,7 @@ extern "C" int seir_sampler_forecast_reset(seir_sampler *s, int32_t horizon, con
     if ((rc = rollout_begin(s, r, W, weekday_c, seed))) return rc;   // j = 0 empties the draw store too: it holds draws [0, j)
     s->fc_W_host.assign(W, W + horizon);
     if (s->scen.K && (rc = scenarios_begin(s))) return rc;           // the scenarios stay; their accumulators start again
+    if (s->ver.on && (rc = verify_begin(s))) return rc;              // the truth stays; its accumulators start again
     return s->grp_on ? groups_fit(s, 1) : 0;
 }
 
@@ -3086,6 +3104,7 @@ extern "C" int seir_sampler_forecast(seir_sampler *s, int32_t first, int32_t cou
             hipLaunchKernelGGL(k_forecast_finish, dim3(bt.nj, B), dim3(64), 0, l.st, d, fb, B, first + bt.j0, bt.nj, bt.ndp);
             if (groups_live(s, 1)) groups_rollout_batch(s, 1, d, l.st, fb, first, bt);
             if (s->scen.K && !sc_rc) sc_rc = scenarios_batch(s, fb, bt, first);   // while the batch's planes and fev live
+            if (s->ver.on) verify_batch(s, fb, bt);
         });
     if (rc || (rc = sc_rc)) return rc;
     if (log_baseline_steps) { HIP_TRY(hipEventRecord(s->fc_ev_steps, l.st)); s->fc_steps_pending = true; }
@@ -4557,4 +4576,199 @@ extern "C" int seir_sampler_read_scenario_draws(seir_sampler *s, int64_t first, 
     }
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Scoring the forecast against later data (include/seir_hip.h; kernels: verify_kernels.h)
+// ---------------------------------------------------------------------------
+#include "verify_kernels.h"
+
+static_assert(VF_JMAX == FC_JMAX, "a batch of the forecast is one launch of the verification fold");
+static_assert(PAIR_CHUNK == SEIR_PAIR_ABS_CHUNK && PAIR_ABS_MAX_N == SEIR_PAIR_ABS_MAX_N, "the header's limits are the kernel's");
+
+static void verify_layout(const VerifySet &v, VerifyBufs &vb) {
+    vb.truth = v.truth;
+    vb.cum = v.cum;
+    vb.abs_sum = v.acc.buf.as<uint64_t>();
+    vb.lt = (uint32_t *)(vb.abs_sum + v.c2);
+    vb.eq = vb.lt + v.c2;
+}
+
+// Behind a forecast reset (and the set itself): the accumulators zero and what the snapshots hold of them dropped -- but for a
+// slot whose snapshot holds the forecast's block: that was taken at j = 0, and so holds these zeros too (as scenarios_begin).
+static int verify_begin(seir_sampler *s) {
+    VerifySet &v = s->ver;
+    hipStream_t st = s->ctx->stream;
+    if (int rc = acc_zero(v.acc, st)) return rc;
+    acc_invalidate(v.acc);
+    for (int slot = 0; slot < 2; ++slot)
+        if (s->fc.acc.valid[slot])
+            if (int rc = acc_shadow(v.acc, slot, true, st)) return rc;
+    return 0;
+}
+
+// A batch of the forecast behind its fold, while its staging tensor lives: an ordinary launch on the context stream.
+static void verify_batch(seir_sampler *s, const ForecastBufs &fb, const RolloutBatch &bt) {
+    const LaunchCfg l = whole(s->ctx, s->cfg.B);
+    VerifyBufs vb{};
+    verify_layout(s->ver, vb);
+    hipLaunchKernelGGL(k_verify_fold<VF_ROWS>, dim3((l.d.M + VF_ROWS - 1) / VF_ROWS, s->cfg.B), dim3(64 * VF_ROWS), 0, l.st, l.d, vb,
+                       (const int *)fb.fev, fb.H, s->cfg.B, bt.nj);
+}
+
+extern "C" int seir_sampler_verify_set(seir_sampler *s, const int32_t *truth) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if (!truth) {                                    // off: with or without a forecast
+        if ((rc = drain(s))) return rc;
+        s->ver = VerifySet{};
+        return 0;
+    }
+    if ((rc = trace_range_check(s, s->fc.on, FORECAST_USER))) return rc;
+    if (s->fc.acc.j != 0)
+        return fail(SEIR_ERR_STATE, "%lld draws per chain have been forecast since the reset: the truth is set between "
+                    "seir_sampler_forecast_reset and the first seir_sampler_forecast", s->fc.acc.j);
+    const int M = s->ctx->d.M, H = s->fc.fb.H;
+    const size_t B = (size_t)s->cfg.B, mh = (size_t)M * H;
+    if ((rc = drain(s))) return rc;
+    s->ver = VerifySet{};                            // what was set before goes first; a refusal leaves the forecast unscored
+    VerifySet v;
+    v.c2 = B * mh * 2;
+    const size_t acc_bytes = v.c2 * 16;
+    const unsigned long long bytes = 12ull * mh + 3ull * acc_bytes;    // the block and its two shadows
+    if ((rc = refuse_above_half_free(bytes, "the verification needs %llu bytes (%zu chains x %d locations x %d days x 2 x 16, "
+                                            "three times)", bytes, B, M, H)))
+        return rc;
+    if (!rc) rc = s_alloc(s, v.allocs, &v.truth, mh);
+    if (!rc) rc = s_alloc(s, v.allocs, &v.cum, mh);
+    if (!rc) rc = v.acc.buf.zeroed(acc_bytes);
+    if (rc) return alloc_failed(bytes, "verification");
+    // the running total per row, -1 from the first missing day on
+    std::vector<int64_t> cum(mh);
+    for (int m = 0; m < M; ++m) {
+        int64_t run = 0;
+        bool ok = true;
+        for (int h = 0; h < H; ++h) {
+            const int32_t y = truth[(size_t)m * H + h];
+            ok = ok && y >= 0;
+            if (ok) run += y;
+            cum[(size_t)m * H + h] = ok ? run : -1;
+        }
+    }
+    HIP_TRY(hipMemcpy(v.truth, truth, sizeof(int32_t) * mh, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(v.cum, cum.data(), sizeof(int64_t) * mh, hipMemcpyHostToDevice));
+    v.on = true;
+    s->ver = std::move(v);
+    if ((rc = verify_begin(s))) { s->ver = VerifySet{}; return rc; }
+    return 0;
+}
+
+extern "C" int seir_sampler_verify_state(seir_sampler *s, int64_t out[4]) {
+    if (!s) return fail(SEIR_ERR_INVALID, "null sampler");
+    if (!out) return fail(SEIR_ERR_INVALID, "null pointer");
+    out[0] = s->ver.on ? 1 : 0;
+    out[1] = s->ver.on ? s->fc.fb.H : 0;
+    out[2] = s->ver.on ? s->fc.acc.j : 0;
+    out[3] = s->ver.on && s->keep_fc.buf ? 1 : 0;
+    return 0;
+}
+
+extern "C" int seir_sampler_read_verify(seir_sampler *s, uint64_t *count, uint32_t *lt, uint32_t *eq, uint64_t *abs_sum) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = trace_range_check(s, s->fc.on, FORECAST_USER))) return rc;
+    if (!s->ver.on) return fail(SEIR_ERR_STATE, "no truth is set: call seir_sampler_verify_set first");
+    VerifyBufs vb{};
+    verify_layout(s->ver, vb);
+    const size_t c2 = s->ver.c2;
+    hipStream_t st = s->ctx->stream;
+    if (count) HIP_TRY(hipMemcpyAsync(count, s->fc.fb.mom.count, sizeof(uint64_t) * s->cfg.B, hipMemcpyDeviceToHost, st));
+    if (lt) HIP_TRY(hipMemcpyAsync(lt, vb.lt, sizeof(uint32_t) * c2, hipMemcpyDeviceToHost, st));
+    if (eq) HIP_TRY(hipMemcpyAsync(eq, vb.eq, sizeof(uint32_t) * c2, hipMemcpyDeviceToHost, st));
+    if (abs_sum) HIP_TRY(hipMemcpyAsync(abs_sum, vb.abs_sum, sizeof(uint64_t) * c2, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+// Cells of n = segs x seg_len values on the device into out [cells] on the host.
+static int pair_abs_run(seir_ctx *ctx, PairAbsArgs a, int64_t *out, uint32_t *overflow) {
+    const long long n = (long long)a.segs * a.seg_len;
+    if (n > SEIR_PAIR_ABS_MAX_N)
+        return fail(SEIR_ERR_INVALID, "n = %d x %lld = %lld values per cell: above %d the sum of pairwise differences can reach 2^63",
+                    a.segs, a.seg_len, n, SEIR_PAIR_ABS_MAX_N);
+    DevBuf dout;
+    if (int rc = dout.zeroed(sizeof(int64_t) * (size_t)a.cells + 8)) return rc;
+    a.out = dout.as<int64_t>();
+    a.overflow = (unsigned *)(a.out + a.cells);
+    hipStream_t st = ctx->stream;
+    uint32_t flag = 0;
+    hipLaunchKernelGGL(k_pair_abs<PAIR_THREADS>, dim3((unsigned)a.cells), dim3(PAIR_THREADS), 0, st, whole(ctx, 1).d, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, a.out, sizeof(int64_t) * (size_t)a.cells, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&flag, a.overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (overflow) *overflow = flag;
+    if (flag) return fail(SEIR_ERR_STATE, "a cell above %d values reached the pair-sum kernel", SEIR_PAIR_ABS_MAX_N);
+    return 0;
+}
+
+extern "C" int seir_sampler_forecast_pair_sums(seir_sampler *s, int32_t pooled, int64_t *out) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = trace_range_check(s, s->fc.on, FORECAST_USER))) return rc;
+    const DrawStore &store = s->keep_fc;
+    const TraceUser &who = FORECAST_USER;
+    if (!store.buf) return fail(SEIR_ERR_STATE, "the draw store is not enabled: call %s first", who.keep);
+    if (!out) return fail(SEIR_ERR_INVALID, "null output pointer");
+    const long long j = s->fc.acc.j;
+    if (j < 1) return fail(SEIR_ERR_STATE, "no draws kept since the %s reset", who.name);
+    const int B = s->cfg.B;
+    hipStream_t st = s->ctx->stream;
+    std::vector<uint64_t> cnt((size_t)B);
+    HIP_TRY(hipMemcpyAsync(cnt.data(), s->fc.fb.mom.count, sizeof(uint64_t) * B, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int b = 0; b < B; ++b)
+        if ((long long)cnt[b] != j)
+            return fail(SEIR_ERR_STATE, "chain %d has %llu draws %s, the store %lld: the chains' counts differ", b,
+                        (unsigned long long)cnt[b], who.done, j);
+    // planes 0 and 1 of keep[B][3][M][H][cap]: per chain (or once, pooled) two launches of M x H cells
+    const long long mh = (long long)s->ctx->d.M * s->fc.fb.H, plane3 = 3 * mh;
+    const int nb = pooled ? 1 : B;
+    for (int b = 0; b < nb; ++b) {
+        PairAbsArgs a{};
+        a.values = store.buf.as<const int32_t>() + (size_t)b * (size_t)plane3 * (size_t)store.stride;
+        a.cells = 2 * mh;                            // planes 0 and 1 are neighbours
+        a.segs = pooled ? B : 1;
+        a.seg_len = j;
+        a.seg_stride = plane3 * store.stride;
+        a.cell_stride = store.stride;
+        if ((rc = pair_abs_run(s->ctx, a, out + (size_t)b * 2 * (size_t)mh, nullptr))) return rc;
+    }
+    return 0;
+}
+
+extern "C" int seir_pair_abs_sums(seir_ctx *ctx, const int32_t *values, int64_t cells, int32_t segs, int64_t seg_len,
+                                  int64_t seg_stride, int64_t cell_stride, int64_t *out, uint32_t *overflow) {
+    int rc = check_batch(ctx, 1);
+    if (rc) return rc;
+    if (!values || !out || !overflow) return fail(SEIR_ERR_INVALID, "null pointer");
+    *overflow = 0;
+    if (cells < 1 || cells > 0x7fffffffll || segs < 1 || seg_len < 1)
+        return fail(SEIR_ERR_INVALID, "cells=%lld, segs=%d, seg_len=%lld: at least one of each, cells below 2^31", (long long)cells, segs,
+                    (long long)seg_len);
+    // each factor against the bound before the product is formed: it then fits 64 bits whatever the caller passed
+    if (segs > SEIR_PAIR_ABS_MAX_N || seg_len > SEIR_PAIR_ABS_MAX_N || (long long)segs * seg_len > SEIR_PAIR_ABS_MAX_N)
+        return fail(SEIR_ERR_INVALID, "n = %d x %lld values per cell: above %d the sum of pairwise differences can reach 2^63", segs,
+                    (long long)seg_len, SEIR_PAIR_ABS_MAX_N);
+    if (cell_stride < 0 || seg_stride < 0 || (segs > 1 && seg_stride < seg_len))
+        return fail(SEIR_ERR_INVALID, "seg_stride=%lld, cell_stride=%lld: no negative stride, and segments do not overlap",
+                    (long long)seg_stride, (long long)cell_stride);
+    const size_t extent = (size_t)(cells - 1) * cell_stride + (size_t)(segs - 1) * seg_stride + (size_t)seg_len;
+    DevBuf dv;
+    if ((rc = dv.alloc(sizeof(int32_t) * extent))) return rc;
+    HIP_TRY(hipMemcpyAsync(dv.p, values, sizeof(int32_t) * extent, hipMemcpyHostToDevice, ctx->stream));
+    PairAbsArgs a{};
+    a.values = dv.as<int32_t>();
+    a.cells = cells; a.segs = segs; a.seg_len = seg_len; a.seg_stride = seg_stride; a.cell_stride = cell_stride;
+    return pair_abs_run(ctx, a, out, overflow);
 }

@@ -26,9 +26,9 @@ from ..posterior import groups as G_mod
 from ..sampler import MOVE_KEYS, ChainSampler, Summary, mid_p
 from ..seir import SeirModel
 from .mcmc_kernel_factory import event_kernel_config, hmc_kernel_kwargs_default
-from .options import (CHECK_SEED_SALT, DIAGNOSTICS, SUMMARIES, Products, add_product_arguments, add_scenarios_argument, scenarios_override, check_mode, check_seed,  # noqa: F401
+from .options import (CHECK_SEED_SALT, DIAGNOSTICS, SUMMARIES, Products, add_product_arguments, add_scenarios_argument, add_verify_argument, scenarios_override, verify_override, check_mode, check_seed,  # noqa: F401
                       diagnostics_mode, forecast_mode, forecast_quantiles_mode, posterior_kwargs, product_inputs, product_overrides,
-                      resolve_products, resolve_scenarios, rt_mode, rt_quantiles_mode, summaries_mode, thin_interval, within_between_mode)
+                      resolve_products, resolve_scenarios, resolve_verify, rt_mode, rt_quantiles_mode, summaries_mode, thin_interval, within_between_mode)
 
 DTYPE = model_spec.DTYPE
 
@@ -669,7 +669,8 @@ def forecast_record(ctx):
                                                           ctx.opt.fq_probs)
     if not horizon:
         return None
-    sc, base_by_day, writes = ctx.scenarios, [], _writes(ctx, "forecast")
+    sc, base_by_day, grp_by_day, writes = ctx.scenarios, [], [], _writes(ctx, "forecast")
+    vf = getattr(ctx, "verify", None)                       # the later data the forecast is scored against, or None
 
     def begin():
         s.reset_forecast(horizon, ctx.forecast_calendar[0], ctx.forecast_calendar[1], ctx.seed)   # once: the sampling phase
@@ -677,10 +678,14 @@ def forecast_record(ctx):
             s.keep_forecast_draws(total)                    # the draw store of the quantiles: every kept draw of the phase
         if sc:
             s.set_scenarios(sc.log_shift, sc.commute, total)   # once, behind the reset and the draw store: they ride from now on
+        if vf is not None:
+            s.set_verify(vf.truth)                          # once, behind the reset, the draw store and the scenarios
 
     def flush(tr, burst):
-        if sc and getattr(tr, "forecast", None) is not None:   # the baseline's curves, for the paired differences of the draws
+        if (sc or vf is not None) and getattr(tr, "forecast", None) is not None:   # the baseline's curves: paired differences, national scores
             base_by_day.append(np.array(tr.forecast["forecast_by_day"]))
+        if vf is not None and ctx.groups is not None and "forecast_by_group" in (getattr(tr, "groups", None) or {}):
+            grp_by_day.append(np.array(tr.groups["forecast_by_group"]))   # the groups' curves, for the per-group scores
         writes(tr, burst)
 
     def finish():
@@ -691,6 +696,7 @@ def forecast_record(ctx):
         print(f"Forecast: {horizon} day(s) from day {s.T} for {int(fs.count.min()) if len(fs.count) else 0} kept draw(s) per "
               f"chain, formed on the device ({'random-walk' if walk else 'held'} baseline); forecast/* and "
               "samples/forecast_* written", file=log, flush=True)
+        own = pooled = None
         if fq_probs and total:
             own = s.forecast_quantiles(fq_probs)                        # [K,B,3,M,H]
             pooled = s.forecast_quantiles(fq_probs, pooled=True)        # [K,3,M,H]
@@ -701,8 +707,91 @@ def forecast_record(ctx):
                   "chain(s) of this process, selected on the device; forecast/*_quantiles written", file=log, flush=True)
         if sc:
             scenarios_write_up(ctx, sc, _stack(base_by_day, s.B, horizon, 3))
+        if vf is not None:
+            verify_write_up(ctx, vf, _stack(base_by_day, s.B, horizon, 3), own, pooled,
+                            _stack(grp_by_day, s.B, ctx.groups.G, horizon, 3) if ctx.groups is not None else None)
     return Record(begin, flush, finish, {},
                   dict(forecast=forecast_steps_fn(ctx.seed, ctx.chain_ids, horizon) if walk else True))
+
+
+def verify_write_up(ctx, vf, by_day, own_q, pooled_q, by_group=None):
+    """The one read of each kind at the end of the run (`posterior.verify`; Mcmc.verify rides on Mcmc.forecast) and what every
+    chain's file gains: the group verify/ -- truth [M,H], valid [M,H,2] (cases, cum_cases), horizon, first_day, count; the raw lt,
+    eq, abs_sum [M,H,2], so that pooling over files is a sum; pit, mae; with the draw store (forecast_quantiles) pair_sum, crps and
+    pooled_pair_sum, pooled_crps (over the chains of this process: pooled_chains); national_truth, national_valid and the
+    national_* scores [H,2] from the per-draw curves samples/forecast_by_day (`by_day` [n,B,H,3]); with forecast_quantiles
+    coverage_probs and coverage, pooled_coverage [P,H,2], the share of valid cells inside every central interval the
+    probabilities contain; with `groups` group_truth [G,H], group_valid and the group_* scores [G,H,2] from the per-draw curves
+    samples/forecast_by_group (`by_group` [n,B,G,H,3]): a group's truth is the sum over its members, valid where every member
+    is.  The pooled pair sum covers B x n values per cell: above `_lib.PAIR_ABS_MAX_N` (`ctx.verify_pooled` False, decided and
+    logged before the first GPU call) pooled_pair_sum and pooled_crps are not written.  One log line."""
+    from ..posterior import verify as V
+    s, horizon, probs = ctx.s, ctx.opt.horizon, ctx.opt.fq_probs
+    y, valid = V.truth_targets(vf.truth)
+    acc = s.verify_summary()                                # one read of the accumulators ...
+    n = int(acc["count"].min()) if len(acc["count"]) else 0
+    store = own_q is not None and n > 0
+    per = s.forecast_pair_sums() if store else None         # ... and one of each kind of the pair sums: [B,2,M,H], [2,M,H]
+    pooled_pair = s.forecast_pair_sums(pooled=True) if store and getattr(ctx, "verify_pooled", True) else None
+    if store:                                               # a cell without truth has all four zero
+        per = np.where(np.moveaxis(valid, -1, 0), per, 0)
+    if pooled_pair is not None:
+        pooled_pair = np.where(np.moveaxis(valid, -1, 0), pooled_pair, 0)
+    pooled = V.pool([dict(count=n, **{k: acc[k][c] for k in ("lt", "eq", "abs_sum")}) for c in range(s.B)])
+    pooled_sc = V.scores(pooled["count"], pooled["lt"], pooled["eq"], pooled["abs_sum"], valid,
+                         None if pooled_pair is None else np.moveaxis(pooled_pair, 0, -1))
+    tnat = np.where((vf.truth >= 0).all(axis=0), np.where(vf.truth >= 0, vf.truth, 0).astype(np.int64).sum(axis=0), -1)[None]
+    ynat, vnat = V.truth_targets(tnat)
+    ygrp = vgrp = None
+    if by_group is not None:
+        ok = ctx.groups.sum_rows((vf.truth < 0).astype(np.int64)) == 0            # [G,H]: every member observed
+        ygrp, vgrp = V.truth_targets(np.where(ok, ctx.groups.sum_rows(np.where(vf.truth >= 0, vf.truth, 0).astype(np.int64)), -1))
+    pairs = V.interval_pairs(probs) if store else []
+    yq = np.moveaxis(y, -1, 0)                              # [2,M,H], as the quantiles' planes 0 and 1
+
+    def cover(q):                                           # q [K,2,M,H] -> [P,H,2]
+        return np.stack([V.coverage(np.moveaxis(q[lo], 0, -1), np.moveaxis(q[hi], 0, -1), np.moveaxis(yq, 0, -1), valid)
+                         for lo, hi, _ in pairs])
+    own_crps = []
+    for c, post in enumerate(ctx.posteriors):
+        sc = V.scores(n, acc["lt"][c], acc["eq"][c], acc["abs_sum"][c], valid, None if per is None else np.moveaxis(per[c], 0, -1))
+        own_crps.append(sc.get("crps"))
+        post.create_dataset("verify/truth", vf.truth, dtype=np.int64)
+        post.create_dataset("verify/valid", valid, dtype=np.int64)
+        for key, v in (("horizon", horizon), ("first_day", s.T), ("count", n)):
+            post.create_dataset(f"verify/{key}", np.array([float(v)]))
+        for key in ("lt", "eq", "abs_sum"):
+            post.create_dataset(f"verify/{key}", acc[key][c], dtype=np.int64)
+        for key in ("pit", "mae"):
+            post.create_dataset(f"verify/{key}", sc[key])
+        if store:
+            post.create_dataset("verify/pair_sum", np.moveaxis(per[c], 0, -1), dtype=np.int64)
+            post.create_dataset("verify/crps", sc["crps"])
+            if pooled_pair is not None:
+                post.create_dataset("verify/pooled_pair_sum", np.moveaxis(pooled_pair, 0, -1), dtype=np.int64)
+                post.create_dataset("verify/pooled_crps", pooled_sc["crps"])
+            post.create_dataset("verify/pooled_chains", np.asarray(ctx.chain_ids), dtype=np.int64)
+        nat = V.score_draws(V.targets(by_day[:, c][:, None]), ynat, vnat)
+        post.create_dataset("verify/national_truth", ynat[0], dtype=np.int64)
+        post.create_dataset("verify/national_valid", vnat[0], dtype=np.int64)
+        for key in ("lt", "eq", "abs_sum", "pair_sum"):
+            post.create_dataset(f"verify/national_{key}", nat[key][0], dtype=np.int64)
+        for key in ("pit", "mae", "crps"):
+            post.create_dataset(f"verify/national_{key}", nat[key][0])
+        if ygrp is not None:
+            grp = V.score_draws(V.targets(by_group[:, c]), ygrp, vgrp)
+            post.create_dataset("verify/group_truth", ygrp[..., 0], dtype=np.int64)
+            post.create_dataset("verify/group_valid", vgrp, dtype=np.int64)
+            for key in ("lt", "eq", "abs_sum", "pair_sum"):
+                post.create_dataset(f"verify/group_{key}", grp[key], dtype=np.int64)
+            for key in ("pit", "mae", "crps"):
+                post.create_dataset(f"verify/group_{key}", grp[key])
+        if pairs:
+            post.create_dataset("verify/coverage_probs", np.array([p for _, _, p in pairs]))
+            post.create_dataset("verify/coverage", cover(own_q[:, c, :2]))
+            post.create_dataset("verify/pooled_coverage", cover(pooled_q[:, :2]))
+    crps = pooled_sc.get("crps") if pooled_pair is not None else (np.stack(own_crps) if store else None)   # else the chains' own
+    print(V.run_line(vf.truth, by_day, pooled_sc["pit"], crps, valid), file=ctx.log, flush=True)
 
 
 def scenarios_write_up(ctx, sc, base_by_day):
@@ -951,7 +1040,7 @@ RECORD_BUILDERS = (summaries_record, forecast_record, rt_record, check_record, g
 
 
 def product_records(sampler, config, posteriors, log=sys.stderr, forecast_calendar=None, seed=0, rt_weight=None,
-                    check_calendar=None, groups=None, population=None, total=None, results=True):
+                    check_calendar=None, groups=None, population=None, total=None, results=True, verify=None):
     """What `run_mcmc` and `posterior.replay.replay_files` share: the options resolved (`resolve_products`; a resolved section resolves to
     itself) and the missing inputs refused before the first call on the sampler, the products' `Record`s in the order of the resets and
     the write-up, the keywords of the warm-up's and the sampling phase's draws, the diagnostics' marks and the row bookkeeping.
@@ -971,9 +1060,28 @@ def product_records(sampler, config, posteriors, log=sys.stderr, forecast_calend
         raise ValueError("groups_rt: run_mcmc needs population = N")
     nb, ns = int(config["num_bursts"]), int(config["num_burst_samples"])
     scenarios = resolve_scenarios(config, opt.horizon)      # Mcmc.scenarios: a resolution of its own; empty when the key is absent
+    if resolve_verify(config, opt.horizon) is not None and verify is None:   # Mcmc.verify likewise; `verify`: posterior.verify.Truth
+        raise ValueError("verify: run_mcmc needs verify = posterior.verify.load_truth(path, data_file, horizon)")
+    if verify is not None:
+        if not opt.horizon:
+            raise ValueError("verify: scoring needs a forecast (set Mcmc.forecast / --forecast H)")
+        if np.shape(verify.truth) != (getattr(sampler, "M", np.shape(verify.truth)[0]), opt.horizon):
+            raise ValueError(f"verify: truth {np.shape(verify.truth)} is not [M, {opt.horizon}]")
+    verify_pooled = True
+    if verify is not None and opt.fq_probs:                 # the pair sums' bound, against what is known before the first GPU call
+        from .. import _lib as lib_mod
+        kept = nb * ns if total is None else int(total)
+        if kept > lib_mod.PAIR_ABS_MAX_N:
+            raise ValueError(f"verify with forecast_quantiles: {kept} kept draws per chain -- the pair sums of the CRPS hold "
+                             f"{lib_mod.PAIR_ABS_MAX_N} values per cell (thin the run, or drop forecast_quantiles for PIT and MAE alone)")
+        if sampler.B * kept > lib_mod.PAIR_ABS_MAX_N:
+            verify_pooled = False
+            print(f"Verify: {sampler.B} chain(s) x {kept} kept draws are {sampler.B * kept} values per pooled cell, above the "
+                  f"{lib_mod.PAIR_ABS_MAX_N} the pair sums hold: verify/pooled_pair_sum and pooled_crps are not written (the "
+                  "chains' own pair_sum and crps are)", file=log, flush=True)
 
     ctx = types.SimpleNamespace(
-        s=sampler, opt=opt, scenarios=scenarios, posteriors=posteriors, log=log, seed=seed, forecast_calendar=forecast_calendar, rt_weight=rt_weight,
+        s=sampler, opt=opt, scenarios=scenarios, verify=verify, verify_pooled=verify_pooled, posteriors=posteriors, log=log, seed=seed, forecast_calendar=forecast_calendar, rt_weight=rt_weight,
         check_calendar=check_calendar, groups=groups, population=population,
         total=nb * ns if total is None else int(total),     # kept draws per chain that the products will see
         chain_ids=[getattr(sampler, "first_chain_id", 0) + c for c in range(sampler.B)],
@@ -1017,7 +1125,7 @@ def product_records(sampler, config, posteriors, log=sys.stderr, forecast_calend
 
 
 def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_step_size=False, forecast_calendar=None,
-             seed=0, rt_weight=None, check_calendar=None, groups=None, population=None):
+             seed=0, rt_weight=None, check_calendar=None, groups=None, population=None, verify=None):
     """The windowed schedule of inference.py:303-470: fast 200, slow 25*2^k (k<6), fast 50,
     then num_bursts x num_burst_samples with the kernel fixed.  Every draw of the warm-up is
     written, as in the reference (its running variance is formed from every draw of a window);
@@ -1028,7 +1136,7 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     `Record`.  A product that is off has no record: nothing of it is called."""
     # 1. resolve the modes and refuse what cannot run -- before the first call on the sampler (product_records)
     pr = product_records(sampler, config, posteriors, log=log, forecast_calendar=forecast_calendar, seed=seed, rt_weight=rt_weight,
-                         check_calendar=check_calendar, groups=groups, population=population)
+                         check_calendar=check_calendar, groups=groups, population=population, verify=verify)
     flush, marks, thin, nb, ns = pr.flush, pr.marks, pr.thin, pr.nb, pr.ns
 
     # 2. warm up
@@ -1155,7 +1263,7 @@ def launch_forms(lay, device_arg, hmc="auto", moves="auto", env=os.environ):
 def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool_step_size=False, init_jitter=0.0,
          events_dtype="auto", hmc="auto", moves="auto", thin=None, summaries=None, diagnostics=None, diagnostics_batch=None,
          forecast=None, forecast_walk=None, rt=None, check=None, forecast_quantiles=None, within_between=None,
-         rt_quantiles=None, groups=None, groups_rt=None, groups_within_between=None, groups_ngm=None, scenarios=None):
+         rt_quantiles=None, groups=None, groups_rt=None, groups_within_between=None, groups_ngm=None, scenarios=None, verify=None):
     """Constructs and runs the MCMC (covid19uk/inference/inference.py:473-608).
 
     Multi-GPU: launched as one process per GPU, every rank runs `num_chains` chains with
@@ -1167,12 +1275,18 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     `--scenarios FILE.yaml`) likewise takes the place of Mcmc.scenarios."""
     if scenarios is not None:
         config = dict(config, scenarios=scenarios)
+    if verify is not None:                                  # the path of --verify FILE: in the place of Mcmc.verify
+        config = dict(config, verify=verify)
     config, opt = resolve_products(config, thin=thin, summaries=summaries, diagnostics=diagnostics, diagnostics_batch=diagnostics_batch,
                                    forecast=forecast, forecast_walk=forecast_walk, rt=rt, check=check,
                                    forecast_quantiles=forecast_quantiles, within_between=within_between, rt_quantiles=rt_quantiles,
                                    groups=groups, groups_rt=groups_rt, groups_within_between=groups_within_between,
                                    groups_ngm=groups_ngm)          # every option refusal: before the data file is opened
     resolve_scenarios(config, opt.horizon)                  # ... the scenarios' too (product_records resolves them again)
+    truth = None
+    if resolve_verify(config, opt.horizon) is not None:     # ... and the truth's: its file is read and held to the fitted one here
+        from ..posterior.verify import load_truth
+        truth = load_truth(resolve_verify(config, opt.horizon), data_file, opt.horizon, log=sys.stderr)
     lay = job_layout(num_chains, device)                    # before any GPU call
     cov, cases, dates = read_inference_data(data_file)
     rng = np.random.default_rng(seed)                       # same imputation on every rank: one initial state per job
@@ -1220,7 +1334,8 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     if group_table is not None:
         for post in posteriors:
             post.write_groups(group_table, cov.N, initial_state)
-    run_mcmc(sampler, config, posteriors, pool_step_size=pool_step_size and total > 1, **fc_kw)
+    run_mcmc(sampler, config, posteriors, pool_step_size=pool_step_size and total > 1, **fc_kw,
+             **({} if truth is None else dict(verify=truth)))
     if sampler.recoveries:
         print(f"{len(sampler.recoveries)} burst(s) were run again after a hand-off time-out (shared GPU?)", flush=True)
     for post in posteriors:
@@ -1271,6 +1386,7 @@ def main(argv=None):
                              "configuration; the warm-up is never thinned, the shape of the output does not depend on it)")
     add_product_arguments(parser)
     add_scenarios_argument(parser)
+    add_verify_argument(parser)
     args = parser.parse_args(argv)
     if args.thin is not None and args.thin < 1:
         parser.error(f"--thin {args.thin}: the thinning interval is >= 1")
@@ -1279,7 +1395,7 @@ def main(argv=None):
     always = ("summaries", "diagnostics", "diagnostics_batch", "forecast", "forecast_walk", "rt")   # passed on even when None
     mcmc(args.data_file, args.output, config["Mcmc"], seed=args.seed, num_chains=args.chains, device=args.device,
          pool_step_size=args.pool_step_size, init_jitter=args.init_jitter, events_dtype=args.events_dtype,
-         hmc=args.hmc, moves=args.moves, thin=args.thin, **product_overrides(args, always), **scenarios_override(args))
+         hmc=args.hmc, moves=args.moves, thin=args.thin, **product_overrides(args, always), **scenarios_override(args), **verify_override(args))
 
 
 if __name__ == "__main__":

@@ -237,6 +237,15 @@ def resolve_scenarios(config, horizon, override=None):
     return parse_scenarios(config.get("scenarios") if override is None else override, horizon)
 
 
+def resolve_verify(config, horizon, override=None):
+    """Mcmc.verify (absent: off), or the path of a `--verify FILE`, against the forecast's horizon (`Products.horizon`): the path of
+    the later input file the forecast is scored against (`posterior.verify`), or None.  A resolution of its own, beside
+    `resolve_products` and `resolve_scenarios`: with the key absent nothing of the products moves.  `verify` without a forecast
+    is refused here; what the file holds is refused by `posterior.verify.load_truth` -- both before any GPU call."""
+    from ..posterior.verify import parse_verify
+    return parse_verify(config.get("verify") if override is None else override, horizon)
+
+
 def posterior_kwargs(config, opt, group_table, kept):
     """The keywords of `Posterior` for the products that are on, `kept` rows in the per-draw datasets of the sampling phase."""
     days = dict(forecast=opt.horizon, rt=opt.rt_days, check=opt.check_days, within_between=opt.wb_days)
@@ -356,6 +365,22 @@ def add_scenarios_argument(parser):
                              "rolled forward under each scenario with the forecast's random numbers -- scenarios/* with the moments and the "
                              "paired differences to the forecast per location and day, samples/scenario_by_day, scenario_state_by_day, "
                              "scenario_diff_by_day")
+
+
+def add_verify_argument(parser):
+    """`--verify FILE` of both command lines: declared beside the product arguments, resolved by `resolve_verify`."""
+    parser.add_argument("--verify", type=str, default=None, metavar="FILE",
+                        help="score the forecast against later data (overrides Mcmc.verify; needs --forecast): an input file (.nc / "
+                             ".hd5 / .npz) whose first T dates are the fitted file's; its cases of the H days behind them are the truth "
+                             "-- verify/* with PIT, MAE and, with --forecast-quantiles, CRPS and interval coverage per location and "
+                             "forecast day")
+
+
+def verify_override(args):
+    """The keyword of `inference.mcmc` / `posterior.replay.replay_files` from the parsed arguments: nothing when the flag was not given."""
+    if getattr(args, "verify", None) is None:
+        return {}
+    return dict(verify=args.verify)
 
 
 def scenarios_override(args):

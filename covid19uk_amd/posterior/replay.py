@@ -247,9 +247,15 @@ def replay_files(data_file, files, output_file, config, seed=0, device=None, fir
         config = dict(config, num_burst_samples=ns, num_bursts=-(-n // ns), thin=1)
         if overrides.get("scenarios") is not None:                       # the mapping of --scenarios: in the place of Mcmc.scenarios
             config = dict(config, scenarios=overrides["scenarios"])
-        overrides = {k: v for k, v in overrides.items() if k != "scenarios"}
+        if overrides.get("verify") is not None:                          # the path of --verify: in the place of Mcmc.verify
+            config = dict(config, verify=overrides["verify"])
+        overrides = {k: v for k, v in overrides.items() if k not in ("scenarios", "verify")}
         config, opt = inf.resolve_products(config, **overrides)          # every product refusal: before any GPU call
         inf.resolve_scenarios(config, opt.horizon)                       # ... the scenarios' too
+        truth = None
+        if inf.resolve_verify(config, opt.horizon) is not None:          # ... and the truth's, held to the fitted file
+            from .verify import load_truth
+            truth = load_truth(inf.resolve_verify(config, opt.horizon), data_file, opt.horizon, log=log)
         if config.get("diagnostics") == "on" and n % ns:
             raise ValueError(f"diagnostics: {n} row(s) in bursts of {ns} -- the split R-hat compares half-chains of one length, "
                              "which takes whole bursts (choose --stop or --burst accordingly)")
@@ -283,7 +289,8 @@ def replay_files(data_file, files, output_file, config, seed=0, device=None, fir
         if group_table is not None:
             for post in posteriors:
                 post.write_groups(group_table, cov.N, initial_state)
-        pr = inf.product_records(sampler, config, posteriors, log=log, total=n, results=False, **kw)
+        pr = inf.product_records(sampler, config, posteriors, log=log, total=n, results=False, **kw,
+                                 **({} if truth is None else dict(verify=truth)))
         n, dt, waited = replay_bursts(sampler, sources, rows, ns, pr, log=log)
         print(f"Replay: rows {int(rows[0])}..{int(rows[-1])} step {int(every)} ({n} draw(s)) of {B} file(s), "
               f"{n * B / dt:.1f} draws/s, {100.0 * waited / dt:.0f} % of the time waiting for the files", file=log, flush=True)
@@ -308,7 +315,8 @@ def main(argv=None):
     from argparse import ArgumentParser
 
     import yaml
-    from ..inference.options import add_product_arguments, add_scenarios_argument, product_overrides, scenarios_override
+    from ..inference.options import (add_product_arguments, add_scenarios_argument, add_verify_argument, product_overrides,
+                                     scenarios_override, verify_override)
     parser = ArgumentParser(description="Replay stored draws on the device: every product of the inference from posterior files")
     parser.add_argument("-c", "--config", type=str, required=True, help="Config file (its Mcmc section)")
     parser.add_argument("-o", "--output", type=str, required=True, help="Output file (one per input: _chain<id> is added)")
@@ -326,12 +334,13 @@ def main(argv=None):
                         help="width of the event counts in the device-side burst buffer")
     add_product_arguments(parser)
     add_scenarios_argument(parser)
+    add_verify_argument(parser)
     args = parser.parse_args(argv)
     with open(args.config, "r") as f:
         config = yaml.load(f, Loader=yaml.FullLoader)
     replay_files(args.data_file, args.posteriors, args.output, config["Mcmc"], seed=args.seed, device=args.device, first=args.first,
                  stop=args.stop, every=args.every, burst=args.burst, first_chain_id=args.first_chain_id,
-                 events_dtype=args.events_dtype, **product_overrides(args), **scenarios_override(args))
+                 events_dtype=args.events_dtype, **product_overrides(args), **scenarios_override(args), **verify_override(args))
 
 
 if __name__ == "__main__":

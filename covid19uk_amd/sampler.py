@@ -825,6 +825,49 @@ class ChainSampler:
         ranks = Q.quantile_ranks(n, probs)
         return Q.interpolate(self.forecast_order_stats(ranks, pooled=pooled), ranks, n, probs)
 
+    # -- the forecast scored against later data (include/seir_hip.h, "Scoring the forecast against later data") ----
+    def set_verify(self, truth):
+        """The forecast is scored against `truth` from now on: int32 [M, H], -1 where nothing was observed
+        (`posterior.verify.extract_truth`).  Between `reset_forecast` and the first `forecast`; None turns it off."""
+        if truth is None:
+            _lib.check(self._lib.seir_sampler_verify_set(self._s, None))
+            return
+        H = self._state().forecast_H
+        y = np.ascontiguousarray(truth)
+        if y.dtype.kind not in "iu" or (H and y.shape != (self.M, H)) or (y.size and (y.min() < -2 ** 31 or y.max() >= 2 ** 31)):
+            raise ValueError(f"truth {y.dtype} {y.shape}: need integers within int32 [{self.M}, {H}]")
+        y = np.ascontiguousarray(y, dtype=np.int32)
+        _lib.check(self._lib.seir_sampler_verify_set(self._s, y.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+
+    def verify_state(self) -> dict:
+        """on, H, j (the draws per chain folded since the forecast reset) and whether the draw store is on, as the library
+        holds them; zeros while no truth is set.  No device call."""
+        out = np.zeros(4, np.int64)
+        _lib.check(self._lib.seir_sampler_verify_state(self._s, out.ctypes.data_as(_lib.c_int64_p)))
+        return dict(on=bool(out[0]), H=int(out[1]), j=int(out[2]), store=bool(out[3]))
+
+    def verify_summary(self) -> dict:
+        """The accumulators against the truth folded since the last `reset_forecast` (blocking): `count` uint64 [B], `lt`,
+        `eq` uint32 and `abs_sum` uint64 [B, M, H, 2] -- cases, cum_cases (`posterior.verify.scores` forms PIT, MAE and
+        CRPS from them)."""
+        st = self.verify_state()
+        shape = (self.B, self.M, st["H"], 2)
+        out = dict(count=np.zeros(self.B, np.uint64), lt=np.empty(shape, np.uint32), eq=np.empty(shape, np.uint32),
+                   abs_sum=np.empty(shape, np.uint64))
+        u32, u64 = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)
+        _lib.check(self._lib.seir_sampler_read_verify(self._s, out["count"].ctypes.data_as(u64), out["lt"].ctypes.data_as(u32),
+                                                      out["eq"].ctypes.data_as(u32), out["abs_sum"].ctypes.data_as(u64)))
+        return out
+
+    def forecast_pair_sums(self, pooled: bool = False) -> np.ndarray:
+        """The sum of pairwise absolute differences of every cell's kept forecast draws (blocking; needs the draw store):
+        int64 [B, 2, M, H] -- planes cases, cum_cases -- or, `pooled`, [2, M, H] over the B x count values of all chains
+        of this sampler.  Equal to `posterior.verify.pair_sum` of the draws."""
+        H = self._state().forecast_H
+        out = np.empty((() if pooled else (self.B,)) + (2, self.M, H), np.int64)
+        _lib.check(self._lib.seir_sampler_forecast_pair_sums(self._s, 1 if pooled else 0, out.ctypes.data_as(_lib.c_int64_p)))
+        return out
+
     # -- scenarios riding on the forecast (include/seir_hip.h, "Scenario forecasts on the device") ----------------
     def set_scenarios(self, log_shift, commute, cap: int):
         """K scenarios ride on the forecast from now on: `log_shift` and `commute` float64 [K, H] (`posterior.scenarios`),

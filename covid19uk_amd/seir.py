@@ -311,6 +311,27 @@ class SeirModel:
                                               out.ctypes.data_as(ip)))
         return out
 
+    def pair_abs_sums(self, values, cells=1, segs=1, seg_len=None, seg_stride=None, cell_stride=None):
+        """The sum of pairwise absolute differences of every cell on the device (csrc/verify_kernels.h, k_pair_abs;
+        include/seir_hip.h, seir_pair_abs_sums): the cell geometry of `order_stats`.  Returns int64 [cells], equal to
+        `posterior.verify.pair_sum` of each cell; the library refuses more than `_lib.PAIR_ABS_MAX_N` values per cell."""
+        v = np.ascontiguousarray(values, dtype=np.int32).reshape(-1)
+        cells, segs = int(cells), int(segs)
+        if seg_len is None:
+            seg_len = v.size // max(cells * segs, 1)
+        seg_stride = int(seg_len) if seg_stride is None else int(seg_stride)
+        cell_stride = segs * seg_stride if cell_stride is None else int(cell_stride)
+        extent = (cells - 1) * cell_stride + (segs - 1) * seg_stride + int(seg_len)
+        if cells < 1 or segs < 1 or int(seg_len) < 1 or min(seg_stride, cell_stride) < 0 or extent > v.size:
+            raise ValueError(f"{cells} cell(s) of {segs} x {seg_len} values at strides {seg_stride}, {cell_stride} do not "
+                             f"lie within the {v.size} values given")
+        out = np.empty(cells, dtype=np.int64)
+        flag = ctypes.c_uint32(0)
+        _lib.check(self._lib.seir_pair_abs_sums(self._ctx, v.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), cells, segs,
+                                                int(seg_len), seg_stride, cell_stride, out.ctypes.data_as(_lib.c_int64_p),
+                                                ctypes.byref(flag)))
+        return out
+
     def group_sums(self, events, offsets, members):
         """Sums over groups of locations on the device (csrc/group_kernels.h; include/seir_hip.h, seir_group_sums): `events`
         int32 [n, M, L, 3] (M and L the array's own), the groups a CSR pair (`offsets` [G+1], `members` [nnz], ascending and

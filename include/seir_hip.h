@@ -1169,6 +1169,50 @@ int seir_scenario_diffs(seir_ctx *ctx, const int32_t *base_events, const int32_t
                         uint32_t *eq, uint32_t *overflow);
 
 /* ------------------------------------------------------------------------
+ * Scoring the forecast against later data.
+ *
+ * Once the days a forecast predicted have been observed, the forecast is scored against them: out of sample, the
+ * complement of the in-sample check.  The targets, per location m and forecast day s, are planes 0 and 1 of the draw store:
+ *     0 cases       the I->R count of the day
+ *     1 cum_cases   its running total over the horizon
+ * truth [M][H] is int32 with -1 (any negative value) for "not observed"; cum_cases of (m, s) has a truth only while every
+ * day <= s of location m has one.  Per chain, cell and target, over the forecast draws x_1..x_n since the forecast's reset:
+ *     lt = #{x_i < y}      eq = #{x_i == y}      abs_sum = sum |x_i - y|      (uint32, uint32, uint64; csrc/verify_update.h)
+ *     pair_sum D = sum_{i<j} |x_i - x_j|                                       (int64; k_pair_abs of csrc/verify_kernels.h)
+ * from which the host forms the mid-p PIT (lt + eq/2)/n, MAE abs_sum/n and the sample CRPS abs_sum/n - D/n^2
+ * (covid19uk_amd/posterior/verify.py is THE definition in NumPy).  lt, eq and abs_sum of several chains or runs pool by a
+ * sum; D does not: the pooled D is the same quantity over the union of the draws, computed with segs = B.  A cell without
+ * truth keeps zeros.  Everything is integer: no result depends on the launch geometry, the debug skew or how a burst is cut
+ * into calls, buffer halves or batches.
+ * ------------------------------------------------------------------------ */
+#define SEIR_PAIR_ABS_CHUNK 4096      /* values of a cell sorted in LDS at a time */
+/* D <= floor(n^2 / 4) (2^32 - 1): below 2^63 exactly while floor(n^2 / 4) <= 2^31, that is n <= 92 681 */
+#define SEIR_PAIR_ABS_MAX_N 92681
+/* truth [M][H] (H the horizon of the last seir_sampler_forecast_reset) rides on the sampler's forecast: set between that
+ * reset and the first seir_sampler_forecast.  From then on every batch that seir_sampler_forecast rolls forward is folded
+ * against it in the same call (k_verify_fold, an ordinary launch on the context stream).  A forecast reset to the same
+ * horizon empties the accumulators and keeps the truth; a reset to another horizon frees it; truth == NULL turns it off (with or without a forecast: never refused for its place).
+ * SEIR_ERR_STATE without a forecast or behind the first forecast call (what is in force stays); SEIR_ERR_INVALID above half
+ * of the device's free memory (what was in force is gone: the forecast runs on unscored).  Snapshot and restore carry the
+ * accumulators with the forecast's, so a burst run again after a hand-off time-out is counted once. */
+int seir_sampler_verify_set(seir_sampler *s, const int32_t *truth);
+/* out = on, H, j (the draws per chain folded since the forecast reset), the draw store is on; zeros while no truth is set.
+ * Host fields only. */
+int seir_sampler_verify_state(seir_sampler *s, int64_t out[4]);
+/* Blocking read; any pointer may be NULL.  count [B] (the forecast's), lt, eq, abs_sum [B][M][H][2]. */
+int seir_sampler_read_verify(seir_sampler *s, uint64_t *count, uint32_t *lt, uint32_t *eq, uint64_t *abs_sum);
+/* D of planes 0 and 1 of the forecast's draw store over the filled positions, per chain (out [B][2][M][H]) or pooled over
+ * the process's chains (out [1][2][M][H]), as seir_sampler_forecast_order_stats runs over them.  Blocking.  Needs the draw
+ * store (seir_sampler_forecast_keep), not a truth.  SEIR_ERR_INVALID for more than SEIR_PAIR_ABS_MAX_N values per cell. */
+int seir_sampler_forecast_pair_sums(seir_sampler *s, int32_t pooled, int64_t *out);
+/* k_pair_abs alone, on host arrays, blocking: cells addressed as seir_order_stats addresses them (`segs` runs of seg_len
+ * int32 values seg_stride apart, the cells cell_stride apart); out [cells].  Exact for every int32 input.  SEIR_ERR_INVALID
+ * for a null pointer, cells, segs or seg_len below 1, a negative stride, overlapping segments, or n = segs x seg_len above
+ * SEIR_PAIR_ABS_MAX_N.  *overflow is 1 if a launch met a cell above that all the same (nothing is written then), else 0. */
+int seir_pair_abs_sums(seir_ctx *ctx, const int32_t *values, int64_t cells, int32_t segs, int64_t seg_len, int64_t seg_stride,
+                       int64_t cell_stride, int64_t *out, uint32_t *overflow);
+
+/* ------------------------------------------------------------------------
  * Reproduction number R_it.
  *
  * calc_posterior_rit (covid19uk/posterior/reproduction_number.py:13-44): for each
