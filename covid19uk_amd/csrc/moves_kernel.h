@@ -800,12 +800,13 @@ __device__ __forceinline__ void mv_apply_rows(const Dims &d, const Work &w, cons
 }
 
 // log-ratio of a drawn proposal over the rows it updates -> od[0..1] = {theta part, constant part}
-template <int MM>
+// (TGT: the proposal's mv.tgt, which every call site knows -- own_rows_delta)
+template <int MM, int TGT>
 __device__ __forceinline__ void mv_own_rows_to_down(const Dims &d, const Consts &c, const Work &w, int b, const Move &mv,
                                                     double psi, const double2 *ltab, const Move *fp, double *red,
                                                     double *od) {
     double dth = 0.0, dcn = 0.0;
-    if (mv.valid && mv.n > 0) own_rows_delta<MVB, MM>(d, c, w, b, mv, psi, 0, d.M, ltab, dth, dcn, fp);
+    if (mv.valid && mv.n > 0) own_rows_delta<MVB, MM, TGT>(d, c, w, b, mv, psi, 0, d.M, ltab, dth, dcn, fp);
     mv_sum2(dth, dcn, red);
     if (threadIdx.x == 0) {
         od[0] = dth;
@@ -1379,7 +1380,9 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
         const Move *fpp = (pend_acc && pendp->any_dI) ? pendp : nullptr;
         double *od = role == 1 ? ch.Down + (((size_t)(pbuf ^ 1) * 2 + 0) * s.B + b) * 2
                                : ch.DownS + ((size_t)(pbuf ^ 1) * s.B + b) * 2;
-        mv_own_rows_to_down<MM>(d, c, w, b, sm_nx.mv, psi, ltab, fpp, sm_nx.dred, od);
+        // (role 1 draws E->I-type proposals, role 2 S->E-type ones)
+        if (role == 1) mv_own_rows_to_down<MM, 1>(d, c, w, b, sm_nx.mv, psi, ltab, fpp, sm_nx.dred, od);
+        else mv_own_rows_to_down<MM, 0>(d, c, w, b, sm_nx.mv, psi, ltab, fpp, sm_nx.dred, od);
         QSTAMP(slot, lidx, 3);
         RSTAMP(11);
         if (nband > 0) {                                   // band workgroups: this role reads F no more, its output is in L2
@@ -1484,7 +1487,7 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
         if (use_pre && fpp == nullptr) {
             dth = pre_down[0]; dcn = pre_down[1];           // F under the proposal's rows is what role 2 saw
         } else {
-            if (mv.valid && mv.n > 0) own_rows_delta<MVB, MM>(d, c, w, b, mv, psi, 0, M, ltab, dth, dcn, fpp);
+            if (mv.valid && mv.n > 0) own_rows_delta<MVB, MM, 0>(d, c, w, b, mv, psi, 0, M, ltab, dth, dcn, fpp);
             PSTAMP(4);
             mv_sum2(dth, dcn, sm_se.dred);
         }
@@ -1542,7 +1545,7 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
             mv_propose<NCH, MM>(d, w, s, ch, b, next, sm_nx, L, ltab);
             move_copy(ch.mvfix + (size_t)(pbuf ^ 1) * s.B + b, &sm_nx.mv, MVB - WAVE);
             const Move *fpp = (pend_acc && pendp->any_dI) ? pendp : nullptr;
-            mv_own_rows_to_down<MM>(d, c, w, b, sm_nx.mv, psi, ltab, fpp, sm_nx.dred,
+            mv_own_rows_to_down<MM, 1>(d, c, w, b, sm_nx.mv, psi, ltab, fpp, sm_nx.dred,
                                 ch.Down + (((size_t)(pbuf ^ 1) * 2 + 1) * s.B + b) * 2);
         }
         PSTAMP(7);

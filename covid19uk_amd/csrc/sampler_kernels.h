@@ -2475,10 +2475,14 @@ struct MoveSpec { int kind, tgt, slot, scan; };   // slot 0..3 = S->E move, E->I
 // fp != nullptr: an accepted E->I update whose F band has not been written yet (see Chains::fpend);
 // its contribution is added to the F values read here.
 // MM: the instance's bound on the sub-moves of mv and of fp (MM_SMALL or MMAX, above); the sums run over i < MM in order.
-template <int NT, int MM>
+// TGT: mv.tgt where the call site knows it (k_move_pair's roles: 0 for an S->E-type proposal, 1 for an E->I-type one) -- the
+// planes and the formulas are then chosen by the compiler; -1: read from the descriptor (k_move_delta<true>, k_move_pa2).
+template <int NT, int MM, int TGT = -1>
 __device__ __forceinline__ void own_rows_delta(const Dims &d, const Consts &c, const Work &w, int b, const Move &mv,
                                                double psi, int r_lo, int r_hi, const double2 *ltab, double &dth,
                                                double &dcn, const Move *fp = nullptr) {
+    static_assert(TGT >= -1 && TGT <= 1, "the plane a proposal moves events of");
+    const int tgt = TGT >= 0 ? TGT : mv.tgt;
     const double r_ei = d.nu * d.dt, L_ei = d.L_ei;
     const double *ea = w.ea + (size_t)b * d.Tp;
     // the (updated row, day of the hull) pairs are spread over the threads: the rows of a proposal are
@@ -2494,7 +2498,7 @@ __device__ __forceinline__ void own_rows_delta(const Dims &d, const Consts &c, c
 #pragma unroll
     for (int i = 0; i < MM; ++i) wpre[i + 1] = wpre[i] + (i < mv.n ? mv.hi[i] - mv.lo[i] + 1 : 0);
     const int total_w = wpre[MM];
-    const int total = mv.tgt == 1 ? mv.n * total_w : total_w;
+    const int total = tgt == 1 ? mv.n * total_w : total_w;
     // A cell's difference is three independent pieces: the S->E term (one or two series of log(1 - e^-r)) and two
     // differences of binomial coefficients (three log-factorials each).  Each piece of each cell is an item of its own
     // for a thread -- a third of the dependent fp64 chain per item (the own-rows part of an E->I-type proposal:
@@ -2506,7 +2510,37 @@ __device__ __forceinline__ void own_rows_delta(const Dims &d, const Consts &c, c
     const bool split = 3 * total <= 2 * NT;
     const int base = al + 2 * total <= NT ? al : total;
     const int nslots = split ? base + 2 * total : total;
+    // (row, day) of a cell, from the descriptor alone
+    auto cell_of = [&](int cell, int &i0, int &k, int &t) {
+        int pos = cell;
+        i0 = 0;
+        if (tgt == 1) { i0 = cell / total_w; pos = cell - i0 * total_w; }
+        int p0 = 0;
+        k = 0;
+#pragma unroll
+        for (int i = 1; i < MM; ++i)
+            if (i < mv.n && pos >= wpre[i]) { k = i; p0 = wpre[i]; }
+        t = mv.lo[k] + (pos - p0);
+        if (tgt == 0) i0 = k;
+    };
+    // A thread's second item of the split case is always a binomial piece (idx >= NT > total): two loads, known from the
+    // descriptor alone.  They are issued ahead of the first item's loads and arithmetic (loaded whether or not the item turns
+    // out to change anything: the address exists) -- one round trip less for the thread.
+    bool have_pre = false;
+    int pre_n = 0, pre_k = 0;
     for (int idx = (int)threadIdx.x; idx < nslots; idx += NT) {
+        const bool use_pre = have_pre;
+        const int cur_n = pre_n, cur_k = pre_k;
+        have_pre = false;
+        if (split && idx + NT < nslots && idx + NT >= base) {
+            const int pc2 = idx + NT >= base + total ? 1 : 0;
+            int i2, k2, t2;
+            cell_of(idx + NT - base - pc2 * total, i2, k2, t2);
+            const size_t q2 = ((size_t)b * d.Mp + mv.m[i2]) * d.Tp + t2;
+            pre_n = (pc2 ? w.St[tgt + 1] : w.St[tgt])[q2];
+            pre_k = (pc2 ? w.K[tgt + 1] : w.K[tgt])[q2];
+            have_pre = true;
+        }
         int cell = idx, mask = 7;
         if (split) {
             if (idx < total) mask = 1;
@@ -2514,17 +2548,11 @@ __device__ __forceinline__ void own_rows_delta(const Dims &d, const Consts &c, c
             else if (idx < base + total) { cell = idx - base; mask = 2; }
             else { cell = idx - base - total; mask = 4; }
         }
-        int i0 = 0, pos = cell;
-        if (mv.tgt == 1) { i0 = cell / total_w; pos = cell - i0 * total_w; }
-        int k = 0, p0 = 0;
-#pragma unroll
-        for (int i = 1; i < MM; ++i)
-            if (i < mv.n && pos >= wpre[i]) { k = i; p0 = wpre[i]; }
-        const int t = mv.lo[k] + (pos - p0);
-        if (mv.tgt == 0) i0 = k;
+        int i0, k, t;
+        cell_of(cell, i0, k, t);
         bool dup = false;
 #pragma unroll
-        for (int i = 0; i < MM - 1; ++i) dup |= (mv.tgt == 1 && i < k && t >= mv.lo[i] && t <= mv.hi[i]);
+        for (int i = 0; i < MM - 1; ++i) dup |= (tgt == 1 && i < k && t >= mv.lo[i] && t <= mv.hi[i]);
         if (dup) continue;
         const int j = mv.m[i0];
         if (j < r_lo || j >= r_hi) continue;
@@ -2535,23 +2563,23 @@ __device__ __forceinline__ void own_rows_delta(const Dims &d, const Consts &c, c
             const bool in_state = t > mv.lo[i0] && t <= mv.hi[i0];
             int dS = 0, dE = 0, dI = 0, dkt = 0;
             if (in_state) {
-                if (mv.tgt == 0) { dS = mv.dsrc[i0]; dE = -mv.dsrc[i0]; }
+                if (tgt == 0) { dS = mv.dsrc[i0]; dE = -mv.dsrc[i0]; }
                 else { dE = mv.dsrc[i0]; dI = -mv.dsrc[i0]; }
             }
             if (t == mv.a[i0]) dkt += mv.dka[i0];
             if (t == mv.b[i0]) dkt += mv.dkb[i0];
             bool f_moves = false;
-            if (mv.tgt == 1) {
+            if (tgt == 1) {
 #pragma unroll
                 for (int i = 0; i < MM; ++i) f_moves |= (i < mv.n && t > mv.lo[i] && t <= mv.hi[i]);
             }
             if (dS == 0 && dE == 0 && dI == 0 && dkt == 0 && !f_moves) continue;
-            const int dk0 = mv.tgt == 0 ? dkt : 0, dk1 = mv.tgt == 1 ? dkt : 0;
+            const int dk0 = tgt == 0 ? dkt : 0, dk1 = tgt == 1 ? dkt : 0;
             if (mask & 1) {
                 double coef[MM];
 #pragma unroll
                 for (int i = 0; i < MM; ++i)
-                    coef[i] = (i < mv.n && mv.tgt == 1)
+                    coef[i] = (i < mv.n && tgt == 1)
                                   ? c.Cstar[(size_t)mv.m[i] * d.Kp0 + j] * c.invN[mv.m[i]] * (double)(-mv.dsrc[i])
                                   : 0.0;
                 double cfp[MM];
@@ -2577,7 +2605,7 @@ __device__ __forceinline__ void own_rows_delta(const Dims &d, const Consts &c, c
                 // only the terms the update changes (terms(new) - terms(old) with the rest cancelled): no I->R log
                 const double rr0 = (ee * (I + psiW * F) + d.rate_floor) * d.dt;
                 // (branch-free series: one straight-line block per case -- device_math.h)
-                if (mv.tgt == 0) {
+                if (tgt == 0) {
                     // S, k_se and E move; the S->E rate (I, F) does not
                     bool odd = false;
                     double L0 = log1mexp_series(rr0, ltab, odd);
@@ -2602,13 +2630,13 @@ __device__ __forceinline__ void own_rows_delta(const Dims &d, const Consts &c, c
             for (int h = 0; h < npc; ++h) {
                 if (!(mask & 6)) break;
                 const int pc = split ? ((mask & 4) ? 1 : 0) : h;
-                const int cn = mv.tgt + pc;                                    // compartment whose coefficient it is: 0 S, 1 E, 2 I
+                const int cn = tgt + pc;                                    // compartment whose coefficient it is: 0 S, 1 E, 2 I
                 // (the piece differs from thread to thread: a select between two uniform pointers, not an indexed one)
-                const auto *Sp = pc ? w.St[mv.tgt + 1] : w.St[mv.tgt];
-                const auto *Kp = pc ? w.K[mv.tgt + 1] : w.K[mv.tgt];
-                const double n0 = Sp[rowoff + t], k0 = Kp[rowoff + t];
+                const auto *Sp = pc ? w.St[tgt + 1] : w.St[tgt];
+                const auto *Kp = pc ? w.K[tgt + 1] : w.K[tgt];
+                const double n0 = use_pre ? cur_n : Sp[rowoff + t], k0 = use_pre ? cur_k : Kp[rowoff + t];
                 const double dn = cn == 0 ? (double)dS : cn == 1 ? (double)dE : (double)dI;
-                const double dk = pc == 0 ? (double)(dk0 + dk1) : 0.0;        // the target transition's events leave compartment mv.tgt
+                const double dk = pc == 0 ? (double)(dk0 + dk1) : 0.0;        // the target transition's events leave compartment tgt
                 double extra = 0.0;
                 if (cn == 1) extra = (double)dk1 * L_ei - (double)(dE - dk1) * r_ei;   // the E->I term of the row (dk1 = 0 for an S->E-type update)
                 dcn += (lbinom_bf(n0 + dn, k0 + dk, ltab) - lbinom_bf(n0, k0, ltab)) + extra;
