@@ -314,6 +314,10 @@ _SIGNATURES = {
                                            ctypes.POINTER(ctypes.c_int32), c_int64_p, ctypes.POINTER(ctypes.c_uint64),
                                            ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
                                            ctypes.POINTER(ctypes.c_uint32)]),
+    # targeted scenarios: per-location operands, and the scenarios' per-draw region totals
+    "seir_sampler_scenarios_set_local": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_double_p, c_double_p, ctypes.c_int64]),
+    "seir_sampler_scenario_groups_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
+    "seir_sampler_read_scenario_group_draws": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_int64_p]),
     # the forecast scored against later data; the sum of pairwise absolute differences alone on host arrays
     "seir_sampler_verify_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     "seir_sampler_verify_state": (ctypes.c_int, [ctypes.c_void_p, c_int64_p]),

@@ -1275,6 +1275,7 @@ struct ScenarioSet {
     int K = 0;
     long long cap = 0;                // draws per chain the position stores hold
     std::vector<double> commute;      // [K][H] on the host: W_k is formed again from the calendar of every forecast reset
+                                      //     (a local set: [K][M][H] as the caller gave it)
     std::vector<DevBuf> allocs;
     double *log_shift = nullptr, *Wk = nullptr;     // [K][H]
     int *St = nullptr;                // [3][Mp][K ndmax]
@@ -1290,6 +1291,14 @@ struct ScenarioSet {
     size_t count_words() const { return (B + 31) / 32 * 32; }
     size_t words8() const { return 2 * c6 + count_words() + 2 * c4; }
     size_t words4() const { return c6 + 3 * c4 + 2; }
+    // A local set (seir_sampler_scenarios_set_local; scenario_local_kernels.h): scenarios_batch launches the local kernels,
+    // which read these two in the place of log_shift, Wk and base (not allocated then).
+    bool local = false;
+    double *log_shift_loc = nullptr, *Wk_loc = nullptr;   // [K][H][M]: the caller's tensors transposed
+    // The per-draw region totals of the scenarios (seir_sampler_scenario_groups_set), by draw position since the forecast
+    // reset like by_day: int64 [K][cap][B][G][H][3], or empty: off.  No shadow: a burst run again overwrites its positions.
+    DevBuf gstore;
+    int gG = 0;                       // groups the store is sized for; 0: none
 };
 
 // The truth the forecast is scored against (seir_sampler_verify_set; verify_kernels.h), or on = false.  Sized by the
@@ -1375,7 +1384,8 @@ struct seir_sampler {
     bool fc_steps_pending = false;
     DrawStore keep_fc;                // int keep[B][3][M][H][cap]: position j of a cell is the draw with the forecast's j
     std::vector<double> fc_W_host;    // [H] the commuting volume of the last forecast reset (the scenarios' W_k come from it)
-    ScenarioSet scen;                 // scenarios riding on the forecast (seir_sampler_scenarios_set)
+    ScenarioSet scen;                 // scenarios riding on the forecast (seir_sampler_scenarios_set, _set_local)
+    bool scen_grp_on = false;         // seir_sampler_scenario_groups_set: the scenarios' region totals are wanted
     VerifySet ver;                    // the later data the forecast is scored against (seir_sampler_verify_set)
     // --- in-sample check of the last K days (seir_sampler_check_reset ...; check_kernels.h): a Rollout with H := K ---
     Rollout ck;                       // its j is not the forecast's
@@ -2567,6 +2577,14 @@ static void groups_launch(const Dims &d, hipStream_t st, const GroupTable &gt, b
                           long long ev_d0, long long out_d0, long long nd, int64_t *out, const int *St0, long long plane, int ndp,
                           int64_t *state0);
 
+// The scenarios' region totals (seir_sampler_scenario_groups_set; defined with the scenarios, at the end of this file): the
+// bytes of the store for K scenarios, `cap` draws per chain, G groups and H days while the switch is on, else 0; and the
+// store sized for what is in force -- at j = 0 made (or refused), behind the first forecast only ever turned off.  `held`: the
+// caller has already held the store's bytes, in a sum of its own, against half of the free memory: they are not held again
+// behind the caller's other allocations, where a second refusal would leave what the first one promised to keep undone.
+static unsigned long long scenario_groups_bytes(const seir_sampler *s, int K, long long cap, int G, int H);
+static int scenario_groups_fit(seir_sampler *s, bool held = false);
+
 // The day extent of source `which` (0 trace, 1 forecast, 2 check) while it is on, else 0.
 static int groups_source_len(const seir_sampler *s, int which) {
     if (which == 0) return s->sum_on ? s->ctx->d.T : 0;
@@ -2623,6 +2641,7 @@ extern "C" int seir_sampler_groups_set(seir_sampler *s, int32_t G, const int32_t
         if ((rc = drain(s))) return rc;
         groups_free(s);
         s->wb.curve.on = false;
+        s->scen.gstore.reset(); s->scen.gG = 0;      // the scenarios' region totals go with the table
         return 0;
     }
     if ((rc = need_events(s, "sum over groups of locations"))) return rc;
@@ -2633,12 +2652,15 @@ extern "C" int seir_sampler_groups_set(seir_sampler *s, int32_t G, const int32_t
     unsigned long long need = 0;
     for (int which = 0; which < 3; ++which)
         if (const int L = groups_source_len(s, which)) need += groups_bytes(s, G, which, L);
+    // the scenarios' store by draw position is made again only before the first forecast; behind it a new table turns it off
+    if (s->fc.on && s->fc.acc.j == 0) need += scenario_groups_bytes(s, s->scen.K, s->scen.cap, G, s->fc.fb.H);
     if ((rc = groups_refuse_bytes(s, need, G))) return rc;
     DevBuf dseg, dmem;
     if ((rc = dseg.upload(seg.data(), seg.size() * sizeof(int))) || (rc = dmem.upload(members, (size_t)offsets[G] * sizeof(int))))
         return rc;
     if ((rc = drain(s))) return rc;
     groups_free(s);
+    s->scen.gstore.reset(); s->scen.gG = 0;
     s->grp_seg = std::move(dseg); s->grp_members = std::move(dmem);
     s->grp.seg = s->grp_seg.as<int>(); s->grp.members = s->grp_members.as<int>();
     s->grp.nseg = (int)(seg.size() / 3);
@@ -2646,6 +2668,7 @@ extern "C" int seir_sampler_groups_set(seir_sampler *s, int32_t G, const int32_t
     s->grp_on = true;
     for (int which = 0; which < 3; ++which)
         if ((rc = groups_fit(s, which))) { groups_free(s); return rc; }
+    if ((rc = scenario_groups_fit(s, true))) { groups_free(s); return rc; }
     s->grp_offsets.assign(offsets, offsets + G + 1);
     // group R_t went off with the old table's weights (groups_free); group within / between has none and is sized again
     return s->wb.curve.on ? gcurve_fit(s, s->wb) : 0;
@@ -3057,7 +3080,8 @@ extern "C" int seir_sampler_forecast_reset(seir_sampler *s, int32_t horizon, con
     s->fc_W_host.assign(W, W + horizon);
     if (s->scen.K && (rc = scenarios_begin(s))) return rc;           // the scenarios stay; their accumulators start again
     if (s->ver.on && (rc = verify_begin(s))) return rc;              // the truth stays; its accumulators start again
-    return s->grp_on ? groups_fit(s, 1) : 0;
+    if (s->grp_on && (rc = groups_fit(s, 1))) return rc;
+    return scenario_groups_fit(s);                                   // the scenarios' region totals, sized where the forecast's are
 }
 
 extern "C" int seir_sampler_forecast(seir_sampler *s, int32_t first, int32_t count, const double *log_baseline_steps) {
@@ -4349,6 +4373,12 @@ extern "C" int seir_scenario_diffs(seir_ctx *ctx, const int32_t *base_events, co
 }
 
 // ---- scenarios riding on the sampler's forecast ----
+// The begin and day launches of a local set (seir_sampler_scenarios_set_local).  Defined at the end of this file, behind
+// scenario_local_kernels.h: a kernel template is emitted where it is first named, and its kernels lie behind every kernel the
+// parent had.
+static void scenarios_local_rollout(seir_sampler *s, const LaunchCfg &l, const ForecastBufs &fb, const ScenarioBufs &sb,
+                                    const RolloutBatch &bt, int j);
+
 // Scenario k's parts of the one block (ScenarioSet::acc): the moments into mb's accumulator pointers, the differences into df.
 static void scenarios_layout(const ScenarioSet &sc, int k, MomentBufs &mb, ScenarioDiffBufs &df) {
     uint64_t *w8 = sc.acc.buf.as<uint64_t>() + (size_t)k * sc.words8();
@@ -4373,10 +4403,18 @@ static int scenarios_begin(seir_sampler *s) {
     ScenarioSet &sc = s->scen;
     const int H = s->fc.fb.H;
     hipStream_t st = s->ctx->stream;
-    std::vector<double> wk((size_t)sc.K * H);
-    for (int k = 0; k < sc.K; ++k)
-        for (int h = 0; h < H; ++h) wk[(size_t)k * H + h] = s->fc_W_host[h] * sc.commute[(size_t)k * H + h];
-    HIP_TRY(hipMemcpyAsync(sc.Wk, wk.data(), sizeof(double) * wk.size(), hipMemcpyHostToDevice, st));
+    const size_t M = sc.local ? (size_t)s->ctx->d.M : 1;
+    std::vector<double> wk((size_t)sc.K * H * M);
+    if (sc.local) {                                   // [K][H][M] out of the caller's [K][M][H]
+        for (int k = 0; k < sc.K; ++k)
+            for (size_t m = 0; m < M; ++m)
+                for (int h = 0; h < H; ++h)
+                    wk[((size_t)k * H + h) * M + m] = s->fc_W_host[h] * sc.commute[((size_t)k * M + m) * H + h];
+    } else {
+        for (int k = 0; k < sc.K; ++k)
+            for (int h = 0; h < H; ++h) wk[(size_t)k * H + h] = s->fc_W_host[h] * sc.commute[(size_t)k * H + h];
+    }
+    HIP_TRY(hipMemcpyAsync(sc.local ? sc.Wk_loc : sc.Wk, wk.data(), sizeof(double) * wk.size(), hipMemcpyHostToDevice, st));
     if (int rc = acc_zero(sc.acc, st)) return rc;
     acc_invalidate(sc.acc);
     for (int slot = 0; slot < 2; ++slot)
@@ -4392,6 +4430,14 @@ static int scenarios_zero_slots(seir_sampler *s, int32_t first, int32_t count) {
     const size_t row = (size_t)s->cfg.B * s->fc.fb.H * 3;
     for (int k = 0; k < sc.K; ++k)
         HIP_TRY(hipMemsetAsync(sc.mom[k].by_day + (size_t)first * row, 0, sizeof(int64_t) * count * row, s->ctx->stream));
+    // k_group_sums adds: the call's draw positions [j, j + count) of the region totals start from zero, so a burst run again
+    // behind a restore overwrites them
+    if (sc.gG) {
+        const size_t grow = row * sc.gG;
+        for (int k = 0; k < sc.K; ++k)
+            HIP_TRY(hipMemsetAsync(sc.gstore.as<int64_t>() + ((size_t)k * sc.cap + (size_t)s->fc.acc.j) * grow, 0,
+                                   sizeof(int64_t) * count * grow, s->ctx->stream));
+    }
     return 0;
 }
 
@@ -4407,12 +4453,16 @@ static int scenarios_batch(seir_sampler *s, const ForecastBufs &fb, const Rollou
     const long long j = s->fc.acc.j + bt.j0;        // the batch's first draw position
     const ScenarioBufs sb{K, sc.log_shift, sc.Wk, sc.St, sc.X, sc.F, sc.base, sc.sev};
     const size_t elems = (size_t)std::max(d.Mp, H) * ndp;
-    hipLaunchKernelGGL(k_scenario_begin<SC_BEGIN_THREADS>, dim3((unsigned)((elems + SC_BEGIN_THREADS - 1) / SC_BEGIN_THREADS), K),
-                       dim3(SC_BEGIN_THREADS), 0, l.st, d, ctx->c, fb, sb, ND, ndp);
-    rollout_day_loop(ctx, l, sc.X, sc.F, cols, H, [&](int h) {
-        hipLaunchKernelGGL(k_scenario_day<FC_DAY_ROWS>, dim3(cols / 64, (d.M + FC_DAY_ROWS - 1) / FC_DAY_ROWS),
-                           dim3(64 * FC_DAY_ROWS), 0, l.st, d, ctx->c, fb, sb, B, s->cfg.chain0, (int)j, ND, ndp, h);
-    });
+    if (sc.local) {
+        scenarios_local_rollout(s, l, fb, sb, bt, (int)j);
+    } else {
+        hipLaunchKernelGGL(k_scenario_begin<SC_BEGIN_THREADS>, dim3((unsigned)((elems + SC_BEGIN_THREADS - 1) / SC_BEGIN_THREADS), K),
+                           dim3(SC_BEGIN_THREADS), 0, l.st, d, ctx->c, fb, sb, ND, ndp);
+        rollout_day_loop(ctx, l, sc.X, sc.F, cols, H, [&](int h) {
+            hipLaunchKernelGGL(k_scenario_day<FC_DAY_ROWS>, dim3(cols / 64, (d.M + FC_DAY_ROWS - 1) / FC_DAY_ROWS),
+                               dim3(64 * FC_DAY_ROWS), 0, l.st, d, ctx->c, fb, sb, B, s->cfg.chain0, (int)j, ND, ndp, h);
+        });
+    }
     const size_t slice = (size_t)ND * d.M * H * 3, row = (size_t)B * H * 3, slot0 = (size_t)(first + bt.j0);
     for (int k = 0; k < K; ++k) {
         ForecastBufs fk = fb;
@@ -4428,6 +4478,9 @@ static int scenarios_batch(seir_sampler *s, const ForecastBufs &fb, const Rollou
         HIP_TRY(hipMemcpyAsync(sc.by_day + at, fk.mom.by_day + slot0 * row, sizeof(int64_t) * bt.nj * row, hipMemcpyDeviceToDevice, l.st));
         HIP_TRY(hipMemcpyAsync(sc.state_by_day + at, fk.mom.state_by_day + slot0 * row, sizeof(int64_t) * bt.nj * row,
                                hipMemcpyDeviceToDevice, l.st));
+        if (sc.gG)                                   // the region totals of the slice, by draw position (zeroed by the call)
+            groups_launch(d, l.st, s->grp, false, fk.fev, d.M, H, 0, ((long long)k * sc.cap + j) * B, ND, sc.gstore.as<int64_t>(),
+                          nullptr, 0, 0, nullptr);
     }
     return 0;
 }
@@ -4438,7 +4491,8 @@ static int scenarios_on(seir_sampler *s) {
     return 0;
 }
 
-extern "C" int seir_sampler_scenarios_set(seir_sampler *s, int32_t K, const double *log_shift, const double *commute, int64_t cap) {
+// What is behind seir_sampler_scenarios_set (local = false: arrays [K][H]) and seir_sampler_scenarios_set_local ([K][M][H]).
+static int scenarios_set(seir_sampler *s, int32_t K, const double *log_shift, const double *commute, int64_t cap, bool local) {
     int rc = sampler_check(s);
     if (rc) return rc;
     if ((rc = trace_range_check(s, s->fc.on, FORECAST_USER))) return rc;
@@ -4456,7 +4510,14 @@ extern "C" int seir_sampler_scenarios_set(seir_sampler *s, int32_t K, const doub
     if (!log_shift || !commute) return fail(SEIR_ERR_INVALID, "null pointer");
     const Dims &d = s->ctx->d;
     const int H = s->fc.fb.H;
-    for (int i = 0; i < K * H; ++i) {
+    const size_t Ml = local ? (size_t)d.M : 1, nop = (size_t)K * Ml * H;
+    for (size_t i = 0; i < nop && local; ++i) {
+        const int k = (int)(i / (Ml * H)), m = (int)(i / H % Ml), h = (int)(i % H);
+        if (!std::isfinite(log_shift[i])) return fail(SEIR_ERR_INVALID, "log_shift[%d][%d][%d] is not finite", k, m, h);
+        if (!std::isfinite(commute[i]) || commute[i] < 0.0)
+            return fail(SEIR_ERR_INVALID, "commute[%d][%d][%d]=%g: finite and >= 0", k, m, h, commute[i]);
+    }
+    for (int i = 0; i < K * H && !local; ++i) {
         if (!std::isfinite(log_shift[i])) return fail(SEIR_ERR_INVALID, "log_shift[%d][%d] is not finite", i / H, i % H);
         if (!std::isfinite(commute[i]) || commute[i] < 0.0)
             return fail(SEIR_ERR_INVALID, "commute[%d][%d]=%g: finite and >= 0", i / H, i % H, commute[i]);
@@ -4469,16 +4530,25 @@ extern "C" int seir_sampler_scenarios_set(seir_sampler *s, int32_t K, const doub
     sc.K = K; sc.cap = cap; sc.B = B;
     sc.c6 = B * d.M * H * seir::SUMMARY_Q; sc.c4 = B * d.M * H * SCENARIO_Q;
     const size_t acc_bytes = Kz * (sc.words8() * 8 + sc.words4() * 4) + 8;
-    const unsigned long long bytes = 8ull * (2 * Kz * H + 2 * plane + Kz * H * ndmax) + 4ull * (3 * plane + Kz * ndm * d.M * H * 3) +
+    // a local set has the two [K][H][M] tensors in the place of the two arrays and the base plane; the region totals' store
+    // is part of the sum while its switch is on and a table is in force
+    const unsigned long long gbytes = scenario_groups_bytes(s, K, cap, s->grp_on ? s->grp.G : 0, H);
+    const unsigned long long bytes = 8ull * (local ? 2 * nop + 2 * plane : 2 * Kz * H + 2 * plane + Kz * H * ndmax) +
+                                     4ull * (3 * plane + Kz * ndm * d.M * H * 3) +
                                      8ull * Kz * capT * B * (2ull * H + d.M) * 3 + 16ull * Kz * (unsigned long long)cap * B * H * 3 +
-                                     acc_bytes;
+                                     acc_bytes + gbytes;
     if ((rc = refuse_above_half_free(bytes, "the scenarios need %llu bytes (%d scenarios x %zu chains x %d locations x %d days, stores of "
                                             "%lld draws)", bytes, K, B, d.M, H, (long long)cap)))
         return rc;
 #define SC_ALLOC(ptr, ...) if (!rc) rc = s_alloc(s, sc.allocs, &(ptr), __VA_ARGS__)
-    SC_ALLOC(sc.log_shift, Kz * H); SC_ALLOC(sc.Wk, Kz * H);
+    sc.local = local;
+    if (local) {
+        SC_ALLOC(sc.log_shift_loc, nop); SC_ALLOC(sc.Wk_loc, nop);
+    } else {
+        SC_ALLOC(sc.log_shift, Kz * H); SC_ALLOC(sc.Wk, Kz * H);
+        SC_ALLOC(sc.base, Kz * H * ndmax);
+    }
     SC_ALLOC(sc.St, 3 * plane); SC_ALLOC(sc.X, plane); SC_ALLOC(sc.F, plane);
-    SC_ALLOC(sc.base, Kz * H * ndmax);
     SC_ALLOC(sc.sev, Kz * ndm * d.M * H * 3);
     for (int k = 0; k < K; ++k) {
         SC_ALLOC(sc.mom[k].by_day, capT * B * H * 3); SC_ALLOC(sc.mom[k].by_loc, capT * B * d.M * 3);
@@ -4488,10 +4558,86 @@ extern "C" int seir_sampler_scenarios_set(seir_sampler *s, int32_t K, const doub
 #undef SC_ALLOC
     if (!rc) rc = sc.acc.buf.zeroed(acc_bytes);
     if (rc) return alloc_failed(bytes, "scenarios");
-    sc.commute.assign(commute, commute + Kz * H);
-    HIP_TRY(hipMemcpy(sc.log_shift, log_shift, sizeof(double) * Kz * H, hipMemcpyHostToDevice));
+    sc.commute.assign(commute, commute + nop);
+    if (local) {                                     // [K][H][M] out of the caller's [K][M][H]
+        std::vector<double> ls(nop);
+        for (int k = 0; k < K; ++k)
+            for (size_t m = 0; m < Ml; ++m)
+                for (int h = 0; h < H; ++h) ls[((size_t)k * H + h) * Ml + m] = log_shift[((size_t)k * Ml + m) * H + h];
+        HIP_TRY(hipMemcpy(sc.log_shift_loc, ls.data(), sizeof(double) * nop, hipMemcpyHostToDevice));
+    } else {
+        HIP_TRY(hipMemcpy(sc.log_shift, log_shift, sizeof(double) * Kz * H, hipMemcpyHostToDevice));
+    }
     s->scen = std::move(sc);
-    if ((rc = scenarios_begin(s))) { s->scen = ScenarioSet{}; return rc; }
+    if ((rc = scenarios_begin(s)) || (rc = scenario_groups_fit(s, true))) { s->scen = ScenarioSet{}; return rc; }
+    return 0;
+}
+
+extern "C" int seir_sampler_scenarios_set(seir_sampler *s, int32_t K, const double *log_shift, const double *commute, int64_t cap) {
+    return scenarios_set(s, K, log_shift, commute, cap, false);
+}
+
+extern "C" int seir_sampler_scenarios_set_local(seir_sampler *s, int32_t K, const double *log_shift, const double *commute,
+                                                int64_t cap) {
+    return scenarios_set(s, K, log_shift, commute, cap, true);
+}
+
+// ---- the scenarios' region totals ----
+static unsigned long long scenario_groups_bytes(const seir_sampler *s, int K, long long cap, int G, int H) {
+    if (!s->scen_grp_on) return 0;
+    return 8ull * (unsigned long long)K * (unsigned long long)cap * s->cfg.B * G * H * 3ull;
+}
+
+static int scenario_groups_fit(seir_sampler *s, bool held) {
+    ScenarioSet &sc = s->scen;
+    const int G = (s->scen_grp_on && s->grp_on && sc.K && s->fc.on) ? s->grp.G : 0;
+    if (G == sc.gG) return 0;
+    if (int rc = drain(s)) return rc;
+    sc.gstore.reset(); sc.gG = 0;
+    if (G == 0 || s->fc.acc.j != 0) return 0;         // behind the first forecast nothing is made: positions [0, j) would be missing
+    const unsigned long long bytes = scenario_groups_bytes(s, sc.K, sc.cap, G, s->fc.fb.H);
+    if (!held)
+        if (int rc = refuse_above_half_free(bytes, "the scenarios' group sums need %llu bytes (%d scenarios x %lld draws x %d chains x "
+                                                   "%d groups x %d days x 24)", bytes, sc.K, sc.cap, s->cfg.B, G, s->fc.fb.H))
+            return rc;
+    if (sc.gstore.zeroed((size_t)bytes)) return alloc_failed(bytes, "scenarios' group sums");
+    sc.gG = G;
+    return 0;
+}
+
+extern "C" int seir_sampler_scenario_groups_set(seir_sampler *s, int32_t on) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if (!on) {
+        if ((rc = drain(s))) return rc;
+        s->scen_grp_on = false;
+        s->scen.gstore.reset(); s->scen.gG = 0;
+        return 0;
+    }
+    if (!s->grp_on) return fail(SEIR_ERR_STATE, "no group table is set: call seir_sampler_groups_set first");
+    s->scen_grp_on = true;
+    if ((rc = scenario_groups_fit(s))) { s->scen_grp_on = false; return rc; }
+    return 0;
+}
+
+extern "C" int seir_sampler_read_scenario_group_draws(seir_sampler *s, int64_t first, int64_t count, int64_t *by_group) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = scenarios_on(s))) return rc;
+    const ScenarioSet &sc = s->scen;
+    if (!sc.gG)
+        return fail(SEIR_ERR_STATE, "the scenarios' group sums are off: seir_sampler_scenario_groups_set with a group table in "
+                    "force, before the first seir_sampler_forecast (a new table behind it turns them off until the next reset)");
+    if (first < 0 || count < 0 || first + count > s->fc.acc.j)
+        return fail(SEIR_ERR_INVALID, "draw positions [%lld,%lld) outside the %lld draws per chain forecast since the reset",
+                    (long long)first, (long long)(first + count), s->fc.acc.j);
+    if (count && !by_group) return fail(SEIR_ERR_INVALID, "null output pointer");
+    hipStream_t st = s->ctx->stream;
+    const size_t row = sc.B * (size_t)sc.gG * s->fc.fb.H * 3, n = (size_t)count * row;
+    for (int k = 0; k < sc.K && n; ++k)
+        HIP_TRY(hipMemcpyAsync(by_group + (size_t)k * n, sc.gstore.as<int64_t>() + ((size_t)k * sc.cap + (size_t)first) * row,
+                               sizeof(int64_t) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }
 
@@ -4771,4 +4917,25 @@ extern "C" int seir_pair_abs_sums(seir_ctx *ctx, const int32_t *values, int64_t 
     a.values = dv.as<int32_t>();
     a.cells = cells; a.segs = segs; a.seg_len = seg_len; a.seg_stride = seg_stride; a.cell_stride = cell_stride;
     return pair_abs_run(ctx, a, out, overflow);
+}
+
+// ---------------------------------------------------------------------------
+// Targeted scenarios: the launches of a local set (declared above, with the scenarios; kernels: scenario_local_kernels.h).  The
+// header is included here, so that its kernels lie behind every kernel the parent had.
+// ---------------------------------------------------------------------------
+#include "scenario_local_kernels.h"
+
+static void scenarios_local_rollout(seir_sampler *s, const LaunchCfg &l, const ForecastBufs &fb, const ScenarioBufs &sb,
+                                    const RolloutBatch &bt, int j) {
+    seir_ctx *ctx = s->ctx;
+    const Dims &d = l.d;
+    const ScenarioLocalBufs lb{s->scen.log_shift_loc, s->scen.Wk_loc};
+    const int K = sb.K, cols = K * bt.ndp;
+    const size_t elems = (size_t)d.Mp * bt.ndp;
+    hipLaunchKernelGGL(k_scenario_local_begin<SC_BEGIN_THREADS>, dim3((unsigned)((elems + SC_BEGIN_THREADS - 1) / SC_BEGIN_THREADS), K),
+                       dim3(SC_BEGIN_THREADS), 0, l.st, d, ctx->c, fb, sb, bt.ND, bt.ndp);
+    rollout_day_loop(ctx, l, sb.X, sb.F, cols, fb.H, [&](int h) {
+        hipLaunchKernelGGL(k_scenario_local_day<FC_DAY_ROWS>, dim3(cols / 64, (d.M + FC_DAY_ROWS - 1) / FC_DAY_ROWS),
+                           dim3(64 * FC_DAY_ROWS), 0, l.st, d, ctx->c, fb, sb, lb, s->cfg.B, s->cfg.chain0, j, bt.ND, bt.ndp, h);
+    });
 }

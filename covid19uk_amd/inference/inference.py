@@ -12,6 +12,7 @@ windows and moves draws from the device burst buffer to disk.
 from __future__ import annotations
 
 import collections
+import functools
 import os
 import sys
 import time
@@ -26,7 +27,7 @@ from ..posterior import groups as G_mod
 from ..sampler import MOVE_KEYS, ChainSampler, Summary, mid_p
 from ..seir import SeirModel
 from .mcmc_kernel_factory import event_kernel_config, hmc_kernel_kwargs_default
-from .options import (CHECK_SEED_SALT, DIAGNOSTICS, SUMMARIES, Products, add_product_arguments, add_scenarios_argument, add_verify_argument, scenarios_override, verify_override, check_mode, check_seed,  # noqa: F401
+from .options import (CHECK_SEED_SALT, DIAGNOSTICS, SUMMARIES, Products, add_product_arguments, add_scenarios_argument, add_verify_argument, scenarios_override, verify_override, bind_scenarios, resolve_scenario_groups, check_mode, check_seed,  # noqa: F401
                       diagnostics_mode, forecast_mode, forecast_quantiles_mode, posterior_kwargs, product_inputs, product_overrides,
                       resolve_products, resolve_scenarios, resolve_verify, rt_mode, rt_quantiles_mode, summaries_mode, thin_interval, within_between_mode)
 
@@ -664,13 +665,17 @@ def forecast_record(ctx):
     With Mcmc.forecast_quantiles (`forecast_quantiles_mode`; needs Mcmc.forecast) the device keeps cases, cumulative cases
     and prevalence of every forecast draw: the store is sized once, right behind the forecast's reset, for num_bursts x
     num_burst_samples draws per chain, and at the end of the run exact quantiles per location and forecast day are selected
-    on the device, per chain and pooled over the chains of this process.  Without the key nothing of it is called."""
+    on the device, per chain and pooled over the chains of this process.  Without the key nothing of it is called.
+    With Mcmc.scenarios the set goes right behind the reset and the draw store -- [K, H] arrays, or [K, M, H] for a specification with
+    a targeted scenario -- and with Mcmc.groups_scenarios the switch of the scenarios' region totals right behind the set; their store
+    is read once, at the end (`scenarios_write_up`)."""
     s, posteriors, log, total, horizon, walk, fq_probs = (ctx.s, ctx.posteriors, ctx.log, ctx.total, ctx.opt.horizon, ctx.opt.walk,
                                                           ctx.opt.fq_probs)
     if not horizon:
         return None
     sc, base_by_day, grp_by_day, writes = ctx.scenarios, [], [], _writes(ctx, "forecast")
     vf = getattr(ctx, "verify", None)                       # the later data the forecast is scored against, or None
+    grp_sc = bool(sc) and getattr(ctx, "grp_sc_on", False)   # the scenarios' region totals (Mcmc.groups_scenarios)
 
     def begin():
         s.reset_forecast(horizon, ctx.forecast_calendar[0], ctx.forecast_calendar[1], ctx.seed)   # once: the sampling phase
@@ -678,13 +683,15 @@ def forecast_record(ctx):
             s.keep_forecast_draws(total)                    # the draw store of the quantiles: every kept draw of the phase
         if sc:
             s.set_scenarios(sc.log_shift, sc.commute, total)   # once, behind the reset and the draw store: they ride from now on
+            if grp_sc:
+                s.set_scenario_groups(True)                 # right behind the set: the table is in force since groups_record was built
         if vf is not None:
             s.set_verify(vf.truth)                          # once, behind the reset, the draw store and the scenarios
 
     def flush(tr, burst):
         if (sc or vf is not None) and getattr(tr, "forecast", None) is not None:   # the baseline's curves: paired differences, national scores
             base_by_day.append(np.array(tr.forecast["forecast_by_day"]))
-        if vf is not None and ctx.groups is not None and "forecast_by_group" in (getattr(tr, "groups", None) or {}):
+        if (vf is not None or grp_sc) and ctx.groups is not None and "forecast_by_group" in (getattr(tr, "groups", None) or {}):
             grp_by_day.append(np.array(tr.groups["forecast_by_group"]))   # the groups' curves, for the per-group scores
         writes(tr, burst)
 
@@ -706,7 +713,8 @@ def forecast_record(ctx):
                   f"location and forecast day, exact over {total} kept draw(s) per chain and pooled over the {s.B} "
                   "chain(s) of this process, selected on the device; forecast/*_quantiles written", file=log, flush=True)
         if sc:
-            scenarios_write_up(ctx, sc, _stack(base_by_day, s.B, horizon, 3))
+            scenarios_write_up(ctx, sc, _stack(base_by_day, s.B, horizon, 3),
+                               **(dict(base_by_group=_stack(grp_by_day, s.B, ctx.groups.G, horizon, 3)) if grp_sc else {}))
         if vf is not None:
             verify_write_up(ctx, vf, _stack(base_by_day, s.B, horizon, 3), own, pooled,
                             _stack(grp_by_day, s.B, ctx.groups.G, horizon, 3) if ctx.groups is not None else None)
@@ -794,14 +802,20 @@ def verify_write_up(ctx, vf, by_day, own_q, pooled_q, by_group=None):
     print(V.run_line(vf.truth, by_day, pooled_sc["pit"], crps, valid), file=ctx.log, flush=True)
 
 
-def scenarios_write_up(ctx, sc, base_by_day):
+def scenarios_write_up(ctx, sc, base_by_day, base_by_group=None):
     """The one read of the scenarios at the end of the run (`posterior.scenarios`; Mcmc.scenarios rides on Mcmc.forecast) and what
     every chain's file gains: the group scenarios/ -- names, log_shift, commute [K,H], horizon, first_day, count; the moments
     seir_mean, seir_var, state_mean, state_var [K,M,H,3]; of the paired differences to the forecast diff_mean, diff_var, p_below,
     p_equal [K,M,H,4] (cases, cum_cases, prevalence, cum_infections) with the raw counts diff_lt, diff_eq, so that pooling over
     files is a sum -- and per kept draw samples/scenario_by_day, scenario_state_by_day and scenario_diff_by_day [n,K,H,3], the last
     one the scenario's curve minus samples/forecast_by_day (`base_by_day` [n,B,H,3]), formed here; with forecast_quantiles also
-    scenarios/national_diff_quantiles [Kq,K,H,3] of those differences.  One log line per scenario."""
+    scenarios/national_diff_quantiles [Kq,K,H,3] of those differences.  One log line per scenario.
+    A specification with a targeted scenario (`posterior.scenarios.LocalScenarios`) writes scenarios/log_shift_by_location and
+    commute_by_location [K,M,H] in the place of log_shift and commute, and scenarios/locations [K,M] uint8, 1 where any multiplier of
+    the row differs from the identity.  With Mcmc.groups_scenarios (`base_by_group` [n,B,G,H,3], the forecast's samples/forecast_by_group)
+    one read of the scenarios' group store: samples/scenario_by_group [n,K,G,H,3] and scenario_diff_by_group, the scenario's totals
+    minus the forecast's, formed here; with forecast_quantiles scenarios/group_diff_quantiles [Kq,K,G,H,3]; one log line per scenario
+    and group."""
     from ..posterior import scenarios as SC
     s, horizon = ctx.s, ctx.opt.horizon
     sums, diffs, draws = s.scenario_summary(), s.scenario_diffs(), s.read_scenario_draws()
@@ -810,11 +824,21 @@ def scenarios_write_up(ctx, sc, base_by_day):
     by_day = np.moveaxis(draws["by_day"], 0, 2)             # [n,B,K,H,3]
     state = np.moveaxis(draws["state_by_day"], 0, 2)
     diff = by_day - np.asarray(base_by_day, np.int64)[:, :, None]
+    local = SC.is_local(sc)
+    by_group = diff_group = None
+    if base_by_group is not None:
+        by_group = np.moveaxis(s.read_scenario_group_draws(), 0, 2)            # [n,B,K,G,H,3]
+        diff_group = by_group - np.asarray(base_by_group, np.int64)[:, :, None]
     width = max(len(name.encode()) for name in sc.names)
     for c, post in enumerate(ctx.posteriors):
         post.create_dataset("scenarios/names", np.array([name.encode() for name in sc.names], dtype=f"S{width}"))
-        post.create_dataset("scenarios/log_shift", sc.log_shift)
-        post.create_dataset("scenarios/commute", sc.commute)
+        if local:
+            post.create_dataset("scenarios/log_shift_by_location", sc.log_shift)
+            post.create_dataset("scenarios/commute_by_location", sc.commute)
+            post.create_dataset("scenarios/locations", sc.locations, dtype=np.uint8)
+        else:
+            post.create_dataset("scenarios/log_shift", sc.log_shift)
+            post.create_dataset("scenarios/commute", sc.commute)
         for key, v in (("horizon", horizon), ("first_day", s.T), ("count", n)):
             post.create_dataset(f"scenarios/{key}", np.array([float(v)]))
         mean, var = np.stack([m.mean[c] for m in sums]), np.stack([m.var[c] for m in sums])
@@ -830,9 +854,16 @@ def scenarios_write_up(ctx, sc, base_by_day):
             post.create_dataset(f"samples/{key}", np.ascontiguousarray(v[:, c]), dtype=np.int64)
         if ctx.opt.fq_probs and n:
             post.create_dataset("scenarios/national_diff_quantiles", draw_quantiles(diff[:, c], ctx.opt.fq_probs))
+        if by_group is not None:
+            for key, v in (("scenario_by_group", by_group), ("scenario_diff_by_group", diff_group)):
+                post.create_dataset(f"samples/{key}", np.ascontiguousarray(v[:, c]), dtype=np.int64)
+            if ctx.opt.fq_probs and n:
+                post.create_dataset("scenarios/group_diff_quantiles", draw_quantiles(diff_group[:, c], ctx.opt.fq_probs))
     for k, name in enumerate(sc.names):
         if n:
             print(SC.run_line(name, diff[:, :, k].reshape(-1, horizon, 3)), file=ctx.log, flush=True)
+        for g in range(ctx.groups.G if by_group is not None and n else 0):
+            print(SC.group_run_line(name, ctx.groups.names[g], diff_group[:, :, k, g].reshape(-1, horizon, 3)), file=ctx.log, flush=True)
 
 
 def rt_record(ctx):
@@ -1040,7 +1071,8 @@ RECORD_BUILDERS = (summaries_record, forecast_record, rt_record, check_record, g
 
 
 def product_records(sampler, config, posteriors, log=sys.stderr, forecast_calendar=None, seed=0, rt_weight=None,
-                    check_calendar=None, groups=None, population=None, total=None, results=True, verify=None):
+                    check_calendar=None, groups=None, population=None, total=None, results=True, verify=None, *,
+                    location_names=None):
     """What `run_mcmc` and `posterior.replay.replay_files` share: the options resolved (`resolve_products`; a resolved section resolves to
     itself) and the missing inputs refused before the first call on the sampler, the products' `Record`s in the order of the resets and
     the write-up, the keywords of the warm-up's and the sampling phase's draws, the diagnostics' marks and the row bookkeeping.
@@ -1060,6 +1092,10 @@ def product_records(sampler, config, posteriors, log=sys.stderr, forecast_calend
         raise ValueError("groups_rt: run_mcmc needs population = N")
     nb, ns = int(config["num_bursts"]), int(config["num_burst_samples"])
     scenarios = resolve_scenarios(config, opt.horizon)      # Mcmc.scenarios: a resolution of its own; empty when the key is absent
+    # a targeted specification's members to rows (`location_names`: the input's codes, a callable that reads them, or None), and
+    # Mcmc.groups_scenarios held to scenarios and groups -- both before the first call on the sampler
+    scenarios = bind_scenarios(scenarios, getattr(sampler, "M", 0), location_names)
+    grp_sc_on = resolve_scenario_groups(config, scenarios, groups)
     if resolve_verify(config, opt.horizon) is not None and verify is None:   # Mcmc.verify likewise; `verify`: posterior.verify.Truth
         raise ValueError("verify: run_mcmc needs verify = posterior.verify.load_truth(path, data_file, horizon)")
     if verify is not None:
@@ -1081,7 +1117,7 @@ def product_records(sampler, config, posteriors, log=sys.stderr, forecast_calend
                   "chains' own pair_sum and crps are)", file=log, flush=True)
 
     ctx = types.SimpleNamespace(
-        s=sampler, opt=opt, scenarios=scenarios, verify=verify, verify_pooled=verify_pooled, posteriors=posteriors, log=log, seed=seed, forecast_calendar=forecast_calendar, rt_weight=rt_weight,
+        s=sampler, opt=opt, scenarios=scenarios, grp_sc_on=grp_sc_on, verify=verify, verify_pooled=verify_pooled, posteriors=posteriors, log=log, seed=seed, forecast_calendar=forecast_calendar, rt_weight=rt_weight,
         check_calendar=check_calendar, groups=groups, population=population,
         total=nb * ns if total is None else int(total),     # kept draws per chain that the products will see
         chain_ids=[getattr(sampler, "first_chain_id", 0) + c for c in range(sampler.B)],
@@ -1125,7 +1161,7 @@ def product_records(sampler, config, posteriors, log=sys.stderr, forecast_calend
 
 
 def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_step_size=False, forecast_calendar=None,
-             seed=0, rt_weight=None, check_calendar=None, groups=None, population=None, verify=None):
+             seed=0, rt_weight=None, check_calendar=None, groups=None, population=None, verify=None, *, location_names=None):
     """The windowed schedule of inference.py:303-470: fast 200, slow 25*2^k (k<6), fast 50,
     then num_bursts x num_burst_samples with the kernel fixed.  Every draw of the warm-up is
     written, as in the reference (its running variance is formed from every draw of a window);
@@ -1136,7 +1172,8 @@ def run_mcmc(sampler: ChainSampler, config, posteriors, log=sys.stderr, pool_ste
     `Record`.  A product that is off has no record: nothing of it is called."""
     # 1. resolve the modes and refuse what cannot run -- before the first call on the sampler (product_records)
     pr = product_records(sampler, config, posteriors, log=log, forecast_calendar=forecast_calendar, seed=seed, rt_weight=rt_weight,
-                         check_calendar=check_calendar, groups=groups, population=population, verify=verify)
+                         check_calendar=check_calendar, groups=groups, population=population, verify=verify,
+                         location_names=location_names)
     flush, marks, thin, nb, ns = pr.flush, pr.marks, pr.thin, pr.nb, pr.ns
 
     # 2. warm up
@@ -1263,7 +1300,8 @@ def launch_forms(lay, device_arg, hmc="auto", moves="auto", env=os.environ):
 def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool_step_size=False, init_jitter=0.0,
          events_dtype="auto", hmc="auto", moves="auto", thin=None, summaries=None, diagnostics=None, diagnostics_batch=None,
          forecast=None, forecast_walk=None, rt=None, check=None, forecast_quantiles=None, within_between=None,
-         rt_quantiles=None, groups=None, groups_rt=None, groups_within_between=None, groups_ngm=None, scenarios=None, verify=None):
+         rt_quantiles=None, groups=None, groups_rt=None, groups_within_between=None, groups_ngm=None, scenarios=None, verify=None, *,
+         groups_scenarios=None):
     """Constructs and runs the MCMC (covid19uk/inference/inference.py:473-608).
 
     Multi-GPU: launched as one process per GPU, every rank runs `num_chains` chains with
@@ -1275,6 +1313,8 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     `--scenarios FILE.yaml`) likewise takes the place of Mcmc.scenarios."""
     if scenarios is not None:
         config = dict(config, scenarios=scenarios)
+    if groups_scenarios is not None:                        # --groups-scenarios: in the place of Mcmc.groups_scenarios
+        config = dict(config, groups_scenarios=groups_scenarios)
     if verify is not None:                                  # the path of --verify FILE: in the place of Mcmc.verify
         config = dict(config, verify=verify)
     config, opt = resolve_products(config, thin=thin, summaries=summaries, diagnostics=diagnostics, diagnostics_batch=diagnostics_batch,
@@ -1282,7 +1322,8 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
                                    forecast_quantiles=forecast_quantiles, within_between=within_between, rt_quantiles=rt_quantiles,
                                    groups=groups, groups_rt=groups_rt, groups_within_between=groups_within_between,
                                    groups_ngm=groups_ngm)          # every option refusal: before the data file is opened
-    resolve_scenarios(config, opt.horizon)                  # ... the scenarios' too (product_records resolves them again)
+    pending = resolve_scenarios(config, opt.horizon)        # ... the scenarios' too (product_records resolves them again)
+    resolve_scenario_groups(config, pending, opt.group_spec)
     truth = None
     if resolve_verify(config, opt.horizon) is not None:     # ... and the truth's: its file is read and held to the fitted one here
         from ..posterior.verify import load_truth
@@ -1296,6 +1337,10 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     P = model_spec.num_params(M, T)
     # the table, groups without a source, the windows: refused before any GPU call (no groups: the location coordinate is not opened)
     group_table = opt.bind(cases.shape[0], T, lambda: read_location_names(data_file))
+    # ... and the members of a targeted scenario against the same codes (read once, and only when a member is a code or a pattern)
+    from ..posterior.scenarios import PendingScenarios
+    codes = functools.lru_cache(maxsize=None)(lambda: read_location_names(data_file)) if isinstance(pending, PendingScenarios) else None
+    bind_scenarios(pending, cases.shape[0], codes)
     cfg = event_kernel_config(config)
     num_samples = warmup_size() + int(config["num_burst_samples"]) * int(config["num_bursts"])
     cap = max(800, 2 * int(config["num_burst_samples"]))      # two halves: a burst runs while the previous one is written
@@ -1331,6 +1376,8 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
                             **posterior_kwargs(config, opt, group_table, kept))
                   for name in names]
     fc_kw = product_inputs(cov, dates, T, opt, seed, group_table)
+    if codes is not None:
+        fc_kw["location_names"] = codes
     if group_table is not None:
         for post in posteriors:
             post.write_groups(group_table, cov.N, initial_state)

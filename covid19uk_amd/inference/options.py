@@ -232,9 +232,38 @@ def resolve_scenarios(config, horizon, override=None):
     """Mcmc.scenarios (absent: off), or the mapping of a `--scenarios FILE.yaml` (`posterior.scenarios.load_spec`), against
     the forecast's horizon (`Products.horizon`): a frozen `posterior.scenarios.Scenarios`, empty for off.  A resolution of
     its own, beside `resolve_products`: with the key absent nothing of the products moves.  Every refusal -- scenarios without
-    a forecast, more than four, a bad name, length or value -- comes here, before any GPU call."""
+    a forecast, more than four, a bad name, length or value -- comes here, before any GPU call.
+    A specification in which a scenario has `locations` or `parts` (targeted scenarios) resolves in two stages: this one,
+    before the data file is opened, checks keys, values, from_day, list lengths and the form of `locations` and gives a
+    `posterior.scenarios.PendingScenarios`; `bind_scenarios` resolves the members to rows once M and the codes are known."""
     from ..posterior.scenarios import parse_scenarios
     return parse_scenarios(config.get("scenarios") if override is None else override, horizon)
+
+
+def bind_scenarios(scenarios, M, location_names=None):
+    """Stage two of `resolve_scenarios`, before any GPU call: the members of a targeted specification to rows of the M
+    locations (`location_names`: a callable that reads the input's location coordinate, or the codes themselves, or None; as
+    for the groups, not called unless a member is a code or a pattern) -- an unknown code, a pattern that matches nothing and
+    an index out of range are refused here.  Anything else is returned as it is."""
+    from ..posterior.scenarios import PendingScenarios, resolve_locations
+    if not isinstance(scenarios, PendingScenarios):
+        return scenarios
+    named = any(isinstance(x, str) for parts in scenarios.parts for members, _, _ in parts for x in members or ())
+    return resolve_locations(scenarios, M, location_names() if callable(location_names) and named else
+                             None if callable(location_names) else location_names)
+
+
+def resolve_scenario_groups(config, scenarios, group_spec, override=None):
+    """Mcmc.groups_scenarios (absent: off), or `--groups-scenarios`: the per-draw region totals of the scenarios, formed on
+    the device (include/seir_hip.h, "Targeted scenarios on the device").  It needs `scenarios` (what `resolve_scenarios`
+    gave) and `groups` (`Products.group_spec`, or a bound table): refused otherwise, before any GPU call.  A resolution beside
+    `resolve_scenarios`: with the key absent nothing moves."""
+    on = G_mod.switch(config.get("groups_scenarios") if override is None else override, "groups_scenarios")
+    if on and not scenarios:
+        raise ValueError("groups_scenarios given without scenarios: there is no scenario to sum over the groups")
+    if on and group_spec is None:
+        raise ValueError("groups_scenarios given without groups: there is no table of groups to sum the scenarios over")
+    return on
 
 
 def resolve_verify(config, horizon, override=None):
@@ -364,7 +393,13 @@ def add_scenarios_argument(parser):
                              "{transmission: f | [H floats], commute: f | [H floats], from_day: d}, at most four; every kept draw is also "
                              "rolled forward under each scenario with the forecast's random numbers -- scenarios/* with the moments and the "
                              "paired differences to the forecast per location and day, samples/scenario_by_day, scenario_state_by_day, "
-                             "scenario_diff_by_day")
+                             "scenario_diff_by_day; a scenario may carry locations: [codes, prefix patterns E0*, indices] or parts: a "
+                             "list of {locations, transmission, commute, from_day} applied in order (a part without locations applies "
+                             "everywhere): a targeted scenario, whose commute scales the commuting-borne pressure on its locations")
+    parser.add_argument("--groups-scenarios", action="store_true", default=None, dest="groups_scenarios",
+                        help="per-draw totals of every scenario over the groups of locations, formed on the device (overrides "
+                             "Mcmc.groups_scenarios; needs --scenarios and --groups): samples/scenario_by_group, "
+                             "scenario_diff_by_group and, with --forecast-quantiles, scenarios/group_diff_quantiles")
 
 
 def add_verify_argument(parser):
@@ -385,7 +420,10 @@ def verify_override(args):
 
 def scenarios_override(args):
     """The keyword of `inference.mcmc` / `posterior.replay.replay_files` from the parsed arguments: nothing when the flag was not given."""
+    out = {}
+    if getattr(args, "groups_scenarios", None) is not None:
+        out["groups_scenarios"] = args.groups_scenarios
     if getattr(args, "scenarios", None) is None:
-        return {}
+        return out
     from ..posterior.scenarios import load_spec
-    return dict(scenarios=load_spec(args.scenarios))
+    return dict(out, scenarios=load_spec(args.scenarios))

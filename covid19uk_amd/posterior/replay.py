@@ -249,9 +249,12 @@ def replay_files(data_file, files, output_file, config, seed=0, device=None, fir
             config = dict(config, scenarios=overrides["scenarios"])
         if overrides.get("verify") is not None:                          # the path of --verify: in the place of Mcmc.verify
             config = dict(config, verify=overrides["verify"])
-        overrides = {k: v for k, v in overrides.items() if k not in ("scenarios", "verify")}
+        if overrides.get("groups_scenarios") is not None:                # --groups-scenarios: in the place of Mcmc.groups_scenarios
+            config = dict(config, groups_scenarios=overrides["groups_scenarios"])
+        overrides = {k: v for k, v in overrides.items() if k not in ("scenarios", "verify", "groups_scenarios")}
         config, opt = inf.resolve_products(config, **overrides)          # every product refusal: before any GPU call
-        inf.resolve_scenarios(config, opt.horizon)                       # ... the scenarios' too
+        pending = inf.resolve_scenarios(config, opt.horizon)             # ... the scenarios' too
+        inf.resolve_scenario_groups(config, pending, opt.group_spec)
         truth = None
         if inf.resolve_verify(config, opt.horizon) is not None:          # ... and the truth's, held to the fitted file
             from .verify import load_truth
@@ -260,6 +263,11 @@ def replay_files(data_file, files, output_file, config, seed=0, device=None, fir
             raise ValueError(f"diagnostics: {n} row(s) in bursts of {ns} -- the split R-hat compares half-chains of one length, "
                              "which takes whole bursts (choose --stop or --burst accordingly)")
         group_table = opt.bind(M, T, lambda: inf.read_location_names(data_file))   # the table, the windows against the series
+        # the members of a targeted scenario against the same codes (read once, and only when a member is a code or a pattern)
+        import functools
+        from .scenarios import PendingScenarios
+        codes = functools.lru_cache(maxsize=None)(lambda: inf.read_location_names(data_file)) if isinstance(pending, PendingScenarios) else None
+        inf.bind_scenarios(pending, M, codes)
         # the initial state the draws were recorded from: the files' own, else the imputation of `seed` as `mcmc` forms it
         states = [src.initial_state() for src in sources]
         if states[0] is not None:
@@ -290,7 +298,8 @@ def replay_files(data_file, files, output_file, config, seed=0, device=None, fir
             for post in posteriors:
                 post.write_groups(group_table, cov.N, initial_state)
         pr = inf.product_records(sampler, config, posteriors, log=log, total=n, results=False, **kw,
-                                 **({} if truth is None else dict(verify=truth)))
+                                 **({} if truth is None else dict(verify=truth)),
+                                 **({} if codes is None else dict(location_names=codes)))
         n, dt, waited = replay_bursts(sampler, sources, rows, ns, pr, log=log)
         print(f"Replay: rows {int(rows[0])}..{int(rows[-1])} step {int(every)} ({n} draw(s)) of {B} file(s), "
               f"{n * B / dt:.1f} draws/s, {100.0 * waited / dt:.0f} % of the time waiting for the files", file=log, flush=True)

@@ -9,7 +9,15 @@ simulator, per chain:
 
     SeirModel.simulate(par, a_path + log_shift[k], spatial, W * commute[k], wd, st0, seed, first_draw_id)
 
-gives scenario k's counts where the same call with `a_path` and `W` gives the baseline's."""
+gives scenario k's counts where the same call with `a_path` and `W` gives the baseline's.
+
+A TARGETED scenario (csrc/scenario_local_kernels.h) has the two operands per location: `log_shift[k][m][s]` is added to the log
+baseline of location m's hazard and `commute[k][m][s]` multiplies the commuting-borne pressure ON location m (the psi W F
+term of its hazard; what m exports is not scaled).  A scenario body may carry `locations:` (a non-empty list of members in
+`posterior.groups`' forms: code, prefix pattern "E0*", integer index) or `parts:`, a list of bodies {locations,
+transmission, commute, from_day}; a part without `locations` applies everywhere.  The multipliers start at 1.0 [M, H]; each
+part multiplies its locations from its `from_day` on, in list order, in float64; log_shift = np.log of the product.
+`local_inputs` is the simulator's view.  A spec in which no scenario has `locations` or `parts` resolves exactly as before."""
 from __future__ import annotations
 
 import dataclasses
@@ -22,6 +30,7 @@ MAX_SCENARIOS = 4                   # SEIR_SCENARIO_MAX
 Q = 4                               # SEIR_SCENARIO_Q
 QUANTITIES = ("cases", "cum_cases", "prevalence", "cum_infections")
 _KEYS = ("transmission", "commute", "from_day")
+_PART_KEYS = _KEYS + ("locations",)
 
 
 # ---- the specification ------------------------------------------------------------------------------------------------
@@ -40,6 +49,35 @@ class Scenarios:
 
     def __bool__(self):
         return bool(self.names)
+
+
+@dataclasses.dataclass(frozen=True)
+class LocalScenarios(Scenarios):
+    """A resolved specification with a targeted scenario in it: `log_shift` and `commute` float64 [K, M, H] (read-only), and
+    `locations` uint8 [K, M], 1 where any multiplier of the row differs from the identity."""
+    locations: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros((0, 0), np.uint8))
+
+
+@dataclasses.dataclass(frozen=True)
+class PendingScenarios:
+    """Stage one of a specification with `locations` or `parts`: every key, value, from_day and list length is checked, the
+    members are not yet rows.  `parts[k]` is a list of (members or None, transmission [H], commute [H]) with the days before
+    the part's from_day already at 1.  `resolve_locations` makes a `LocalScenarios` of it once M and the codes are known."""
+    names: tuple
+    horizon: int
+    parts: tuple
+
+    @property
+    def K(self):
+        return len(self.names)
+
+    def __bool__(self):
+        return bool(self.names)
+
+
+def is_local(sc):
+    """`sc` carries per-location operands (or will, once its members are resolved)."""
+    return isinstance(sc, (LocalScenarios, PendingScenarios))
 
 
 def is_off(spec):
@@ -84,6 +122,8 @@ def parse_scenarios(spec, horizon):
         raise ValueError(f"scenarios={spec!r}: a mapping name -> {{transmission, commute, from_day}}")
     if len(items) > MAX_SCENARIOS:
         raise ValueError(f"scenarios: {len(items)} given, at most {MAX_SCENARIOS} ride on one forecast")
+    if any(isinstance(body, Mapping) and ("locations" in body or "parts" in body) for _, body in items):
+        return _parse_local(items, H)
     names, shifts, commutes = [], [], []
     for name, body in items:
         name = "" if name is None else str(name).strip()
@@ -110,6 +150,83 @@ def parse_scenarios(spec, horizon):
     return Scenarios(tuple(names), H, ls, cm)
 
 
+def _name(name, names):
+    name = "" if name is None else str(name).strip()
+    if not name:
+        raise ValueError("scenarios: a scenario's name is empty")
+    if name in names:
+        raise ValueError(f"scenarios: the name {name!r} is given twice")
+    return name
+
+
+def _part(name, body, H):
+    """One body {locations, transmission, commute, from_day} as (members or None, transmission [H], commute [H])."""
+    body = {} if body is None else body
+    if not isinstance(body, Mapping) or set(body) - set(_PART_KEYS):
+        raise ValueError(f"scenarios: {name}: a mapping with the keys {', '.join(_PART_KEYS)}")
+    d = body.get("from_day", 0)
+    if isinstance(d, bool) or not isinstance(d, (int, np.integer)) or not 0 <= int(d) < H:
+        raise ValueError(f"scenarios: {name}.from_day={d!r}: a forecast day in [0, {H})")
+    tr = _multipliers(name, "transmission", body.get("transmission", 1.0), H, True)
+    cm = _multipliers(name, "commute", body.get("commute", 1.0), H, False)
+    tr[:int(d)] = 1.0
+    cm[:int(d)] = 1.0
+    members = None
+    if "locations" in body:
+        loc = body["locations"]
+        if not isinstance(loc, (list, tuple)) or not loc or \
+                any(isinstance(x, bool) or not isinstance(x, (str, int, np.integer)) for x in loc):
+            raise ValueError(f"scenarios: {name}.locations={loc!r}: a non-empty list of location codes, prefix patterns or indices")
+        members = tuple(loc)
+    return members, tr, cm
+
+
+def _parse_local(items, H):
+    """Stage one of a specification in which some scenario has `locations` or `parts`."""
+    names, parts = [], []
+    for name, body in items:
+        name = _name(name, names)
+        body = {} if body is None else body
+        if isinstance(body, Mapping) and "parts" in body:
+            if set(body) - {"parts"}:
+                raise ValueError(f"scenarios: {name}: a scenario with parts carries nothing else; every part has its own "
+                                 f"{', '.join(_PART_KEYS)}")
+            if not isinstance(body["parts"], (list, tuple)) or not body["parts"]:
+                raise ValueError(f"scenarios: {name}.parts: a non-empty list of mappings with the keys {', '.join(_PART_KEYS)}")
+            parts.append(tuple(_part(f"{name}.parts[{i}]", p, H) for i, p in enumerate(body["parts"])))
+        else:
+            parts.append((_part(name, body, H),))
+        names.append(name)
+    return PendingScenarios(tuple(names), H, tuple(parts))
+
+
+def resolve_locations(sc, M, location_names=None):
+    """Stage two: the members of a `PendingScenarios` to rows by `posterior.groups`' resolver, and the parts composed into
+    [K, M, H] operands.  Refused (ValueError): an unknown code, a pattern that matches nothing, an index outside [0, M).
+    Anything else -- a `Scenarios` as before, or one already resolved -- is returned as it is."""
+    if not isinstance(sc, PendingScenarios):
+        return sc
+    from . import groups as G
+    M, H = int(M), sc.horizon
+    tr_all, cm_all = np.ones((sc.K, M, H)), np.ones((sc.K, M, H))
+    for k, name in enumerate(sc.names):
+        for members, tr, cm in sc.parts[k]:
+            if members is None:
+                rows = slice(None)
+            else:
+                try:
+                    rows = G.parse_groups({name: list(members)}, M, location_names).members
+                except ValueError as e:
+                    raise ValueError(f"scenarios: {name}.locations: {e}") from None
+            tr_all[k, rows] *= tr
+            cm_all[k, rows] *= cm
+    loc = ((tr_all != 1.0) | (cm_all != 1.0)).any(axis=2).astype(np.uint8)
+    ls = np.log(tr_all)
+    for a in (ls, cm_all, loc):
+        a.setflags(write=False)
+    return LocalScenarios(sc.names, H, ls, cm_all, loc)
+
+
 def load_spec(path):
     """The mapping of a `--scenarios FILE.yaml`: the file's `scenarios` key, or the whole file when it has none."""
     import yaml
@@ -122,6 +239,13 @@ def scenario_inputs(a_path, W, sc, k):
     """The simulator's inputs of scenario k from the baseline's: (a_path [.., H] + log_shift[k], W [H] * commute[k]), one
     rounded add and one rounded multiply."""
     return np.asarray(a_path, dtype=np.float64) + sc.log_shift[k], np.asarray(W, dtype=np.float64) * sc.commute[k]
+
+
+def local_inputs(a_path, W, sc, k):
+    """The simulator's per-location inputs of targeted scenario k from the baseline's: (a_path [.., H] -> [.., M, H] +
+    log_shift[k] [M, H], W [H] * commute[k] [M, H]), one rounded add and one rounded multiply per location and day."""
+    return (np.asarray(a_path, dtype=np.float64)[..., None, :] + sc.log_shift[k],
+            np.asarray(W, dtype=np.float64) * sc.commute[k])
 
 
 # ---- the differences and their fold -----------------------------------------------------------------------------------
@@ -190,3 +314,12 @@ def run_line(name, diff_by_day, probs=(0.05, 0.95)):
     lo, hi = np.quantile(cum, probs)
     return (f"Scenario {name}: cumulative cases at day {np.shape(diff_by_day)[-2] - 1} minus the baseline's: mean {cum.mean():.1f}, "
             f"{probs[0]:g} / {probs[1]:g} quantiles {lo:.1f} / {hi:.1f} over {cum.size} draws")
+
+
+def group_run_line(name, group, diff_by_group, probs=(0.05, 0.95)):
+    """The log's line of one scenario and one group of locations: the group's cumulative cases at the last forecast day minus
+    the baseline's, over the draws -- `diff_by_group` [n, H, 3], the scenario's totals over the group minus the forecast's."""
+    cum = np.asarray(diff_by_group, dtype=np.float64)[..., 2].sum(axis=-1)
+    lo, hi = np.quantile(cum, probs)
+    return (f"Scenario {name}, group {group}: cumulative cases at day {np.shape(diff_by_group)[-2] - 1} minus the baseline's: mean "
+            f"{cum.mean():.1f}, {probs[0]:g} / {probs[1]:g} quantiles {lo:.1f} / {hi:.1f} over {cum.size} draws")

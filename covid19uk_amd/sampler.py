@@ -872,15 +872,39 @@ class ChainSampler:
     def set_scenarios(self, log_shift, commute, cap: int):
         """K scenarios ride on the forecast from now on: `log_shift` and `commute` float64 [K, H] (`posterior.scenarios`),
         `cap` the draws per chain the per-draw stores hold.  Between `reset_forecast` and the first `forecast`; K = 0 or
-        cap = 0 frees everything.  The library refuses what it cannot hold; the forecast then runs on without scenarios."""
+        cap = 0 frees everything.  The library refuses what it cannot hold; the forecast then runs on without scenarios.
+        Arrays [K, M, H] are targeted scenarios, whose operands differ by location (include/seir_hip.h, "Targeted scenarios
+        on the device"; `posterior.scenarios.local_inputs`): they go through `seir_sampler_scenarios_set_local`."""
         H = self._state().forecast_H
         ls = np.zeros((0, H)) if log_shift is None else np.ascontiguousarray(log_shift, dtype=np.float64)
         cm = np.ones((0, H)) if commute is None else np.ascontiguousarray(commute, dtype=np.float64)
+        if ls.ndim == 3:
+            if ls.shape != cm.shape or ls.shape[1] != self.M or (ls.shape[0] and H and ls.shape[2] != H):
+                raise ValueError(f"log_shift {ls.shape} and commute {cm.shape}: need two of [K, {self.M}, {H}]")
+            if int(cap) < 0:
+                raise ValueError(f"cap={cap}: the number of draws per chain to keep")
+            _lib.check(self._lib.seir_sampler_scenarios_set_local(self._s, ls.shape[0], _dptr(ls), _dptr(cm), int(cap)))
+            return
         if ls.ndim != 2 or ls.shape != cm.shape or (ls.shape[0] and H and ls.shape[1] != H):   # H = 0: the library refuses
             raise ValueError(f"log_shift {ls.shape} and commute {cm.shape}: need two of [K, {H}]")
         if int(cap) < 0:
             raise ValueError(f"cap={cap}: the number of draws per chain to keep")
         _lib.check(self._lib.seir_sampler_scenarios_set(self._s, ls.shape[0], _dptr(ls), _dptr(cm), int(cap)))
+
+    def set_scenario_groups(self, on: bool = True):
+        """Switch the scenarios' per-draw region totals on or off: with a group table in force (`set_groups`) and scenarios
+        set, every `forecast` also sums each scenario's counts over the groups, by draw position since the forecast reset.
+        Refused without a table; off frees the store."""
+        _lib.check(self._lib.seir_sampler_scenario_groups_set(self._s, 1 if on else 0))
+
+    def read_scenario_group_draws(self, count: int = None, first: int = 0) -> np.ndarray:
+        """The scenarios' region totals by draw position since the forecast reset (blocking): int64 [K, count, B, G, H, 3];
+        `count` None: every draw from `first` on."""
+        st, G = self.scenario_state(), self._state().groups_G
+        n = st["j"] - int(first) if count is None else int(count)
+        out = np.empty((st["K"], max(n, 0), self.B, G, st["H"], 3), np.int64)
+        _lib.check(self._lib.seir_sampler_read_scenario_group_draws(self._s, int(first), n, out.ctypes.data_as(_lib.c_int64_p)))
+        return out
 
     def scenario_state(self) -> dict:
         """K, H, cap and j (the draws per chain rolled forward since the forecast reset) as the library holds them; zeros

@@ -1169,6 +1169,48 @@ int seir_scenario_diffs(seir_ctx *ctx, const int32_t *base_events, const int32_t
                         uint32_t *eq, uint32_t *overflow);
 
 /* ------------------------------------------------------------------------
+ * Targeted scenarios on the device: per-location interventions and region totals.  It extends "Scenario forecasts on the
+ * device" above and "Region totals on the device"; with neither entry point called every call and every bit is as before.
+ *
+ * A targeted scenario is a scenario whose two operands differ by location: log_shift[k][m][s] (any finite double) and
+ * commute[k][m][s] (finite and >= 0) over the M locations and the H forecast days.  The rollout of a draw is
+ * seir_sampler_scenarios_set's with two operands replaced (THE definition: csrc/scenario_local_kernels.h; in NumPy:
+ * covid19uk_amd/posterior/scenarios.py, local_inputs):
+ *     ea   = exp(base_0[s][nd] + log_shift[k][m][s])                          one rounded add, then the same exp
+ *     psiW = psi * Wk[k][m][s],  Wk[k][m][s] = W[s] * commute[k][m][s]        one rounded multiply, formed on the host
+ * State, parameters, Philox key and counter, draw id, the simulator's functions and the contraction stay the forecast's, so
+ * common random numbers couple a targeted scenario to the baseline variate by variate.  Tensors that are constant over m
+ * give bit for bit what seir_sampler_scenarios_set gives with the [K][H] arrays.
+ * A local commute scales the commuting-borne pressure ON location m (the psi W F term of its hazard); it does not scale
+ * what m exports.  A symmetric travel ban changes Cstar and is out of scope, as are state-dependent policies.
+ * Launches: per batch one begin launch and, per day, the contraction and one day launch over K ndp columns, as for a
+ * global set; a wave reads its two operands by scalar loads.  Device bytes: 2 x K x M x H x 8 in the place of the global
+ * set's 2 x K x H x 8 and its base plane K x H x ndmax x 8.
+ * ------------------------------------------------------------------------ */
+/* seir_sampler_scenarios_set with log_shift and commute [K][M][H] (M the context's): the same place (between a forecast
+ * reset and the first seir_sampler_forecast), the same refusals and what they leave (a refused value is named by its
+ * [k][m][s]), the same stores, accumulators, K == 0 || cap == 0, memory policy and snapshot / restore.  It replaces what
+ * either entry point set before; the global entry point replaces a local set.  A forecast reset to the same horizon keeps a
+ * local set (Wk is formed again from the new calendar and the kept commute); a reset to another horizon frees it.
+ * seir_sampler_scenario_state and the three reads above work unchanged on a local set. */
+int seir_sampler_scenarios_set_local(seir_sampler *s, int32_t K, const double *log_shift, const double *commute, int64_t cap);
+/* The per-draw region totals of the scenarios (extends seir_sampler_groups_set to the scenarios' rollouts), opt-in.  With the
+ * switch on, a group table in force and scenarios set (either entry point), every batch of seir_sampler_forecast also sums
+ * each scenario's simulated counts over the table's groups (k_group_sums on the scenario's slice of the staging tensor) into
+ * a store by draw position since the forecast reset, [K][cap][B][G][H][3] int64, cap the scenarios'.  The call's positions
+ * are zeroed in stream order before the launch, so a burst run again after a hand-off time-out overwrites them.  The store is
+ * sized where the forecast's group outputs are (forecast reset, seir_sampler_groups_set) and at seir_sampler_scenarios_set*;
+ * its K x cap x B x G x H x 24 bytes are part of what those calls hold against half of the device's free memory: refused at
+ * seir_sampler_groups_set the table in force stays, refused at seir_sampler_scenarios_set* the forecast runs on without
+ * scenarios.  A new table or G = 0 behind the first forecast turns the store off until the next forecast reset.
+ * SEIR_ERR_STATE for on != 0 without a group table.  on == 0 frees the store. */
+int seir_sampler_scenario_groups_set(seir_sampler *s, int32_t on);
+/* Blocking read of draw positions [first, first + count) since the forecast reset: by_group [K][count][B][G][H][3], the
+ * layout of seir_sampler_read_group_marginals' events_by_group per scenario.  SEIR_ERR_STATE while no scenarios are set or
+ * the store is off; SEIR_ERR_INVALID for positions outside the draws forecast since the reset. */
+int seir_sampler_read_scenario_group_draws(seir_sampler *s, int64_t first, int64_t count, int64_t *by_group);
+
+/* ------------------------------------------------------------------------
  * Scoring the forecast against later data.
  *
  * Once the days a forecast predicted have been observed, the forecast is scored against them: out of sample, the

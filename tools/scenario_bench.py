@@ -10,7 +10,14 @@ default), in ONE call on one box:
     T for the state at day T, `seir_simulate` per chain for the baseline and for every scenario, the NumPy fold of the
     paired differences.  The integers of the two routes are compared before anything is recorded.
 
-    python tools/scenario_bench.py [--out profiles/r29_scenarios.json]"""
+With --local: what the local entry point and the scenarios' region totals cost against the global set, in ONE call,
+interleaved, medians of --reps: the forecast call with K = 1 and K = 4 set globally, the same numbers set through
+`seir_sampler_scenarios_set_local` (tensors constant over the locations), and the local set with the `nations` group sums of
+the scenarios on (the table is in force in all three, so the forecast's own group sums are in every figure).  The integers
+of the global and the local route are compared before anything is recorded.
+
+    python tools/scenario_bench.py [--out profiles/r29_scenarios.json]
+    python tools/scenario_bench.py --local [--out profiles/r32_scenarios_local.json]"""
 import argparse
 import json
 import os
@@ -30,8 +37,11 @@ def main():
     ap.add_argument("--draws", type=int, default=100, help="kept draws per burst")
     ap.add_argument("--horizon", type=int, default=56)
     ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r29_scenarios.json"))
+    ap.add_argument("--local", action="store_true", help="time the local entry point and the region totals against the global set")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "r32_scenarios_local.json" if a.local else "r29_scenarios.json")
     import __graft_entry__ as entry
     entry.build()
     import torch
@@ -61,6 +71,9 @@ def main():
             s.reset_trace()
             s.run(n)
             model.sync()
+            if a.local:
+                local_against_global(a, res, model, s, sets, cov, W, wd)
+                return write(a, res)
 
             def call(K, timed):
                 s.reset_forecast(Hn, W, wd, 5)
@@ -117,11 +130,70 @@ def main():
                                                 "ratio_to_the_device_increment": t_host * 1e3 / (med[4] - med[0])}
             print(f"without the feature, K = 4: {t_host:.2f} s ({t_read:.2f} s reading the trace), same integers: {same}",
                   file=sys.stderr, flush=True)
+    write(a, res)
+
+
+def write(a, res):
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
     print(json.dumps(res))
+
+
+def local_against_global(a, res, model, s, sets, cov, W, wd):
+    """--local: the forecast call with K = 1 and K = 4 set globally, set locally, and set locally with the scenarios' region
+    totals over the nations; a round holds every variant once."""
+    from covid19uk_amd.posterior import groups as G
+    M, n, Hn = cov.M, a.draws, a.horizon
+    codes = [str(x) for x in np.load(os.path.join(ROOT, "covid19uk_amd", "data", "uk_lad2019.npz"))["lad19cd"]]
+    if len(codes) != M:
+        raise SystemExit(f"--local needs the bundled codes: {len(codes)} of them, the workload has M={M}")
+    tab = G.parse_groups("nations", M, codes)
+    s.set_groups(tab.offsets, tab.members)
+    over = lambda x: np.ascontiguousarray(np.repeat(x[:, None, :], M, axis=1))          # noqa: E731  [K,H] -> [K,M,H]
+    variants = [(kind, K) for K in (1, 4) for kind in ("global", "local", "local_groups")]
+
+    def call(kind, K, timed):
+        s.reset_forecast(Hn, W, wd, 5)
+        s.set_scenario_groups(False)
+        ls, cm = sets[K].log_shift, sets[K].commute
+        s.set_scenarios(ls if kind == "global" else over(ls), cm if kind == "global" else over(cm), n)
+        if kind == "local_groups":
+            s.set_scenario_groups(True)
+        model.sync()
+        if timed:
+            model.timer_start()
+        s.forecast(0, n)
+        return model.timer_stop() if timed else model.sync()
+    ints = {}
+    for kind, K in variants:                                                              # untimed: first launches, allocations
+        call(kind, K, False)
+        d, dr = s.scenario_diffs(), s.read_scenario_draws()
+        ints[kind, K] = [d[key] for key in ("ref", "sum", "sumsq", "lt", "eq")] + [dr["by_day"], dr["state_by_day"]]
+        if kind == "local_groups":
+            tot = s.read_scenario_group_draws()
+            if not np.array_equal(tot.sum(axis=3), dr["by_day"]):                         # the nations are a partition
+                raise SystemExit("the nations' totals do not add up to the national curve: nothing recorded")
+    for K in (1, 4):
+        for kind in ("local", "local_groups"):
+            if not all(np.array_equal(x, y) for x, y in zip(ints[kind, K], ints["global", K])):
+                raise SystemExit(f"{kind}, K = {K}: not the global set's integers: nothing recorded")
+    times = {v: [] for v in variants}
+    for _ in range(a.reps):
+        for v in variants:
+            times[v].append(call(*v, True))
+    med = {v: float(np.median(t)) for v, t in times.items()}
+    res["groups"] = dict(table="nations", G=int(tab.G))
+    res["same_integers"] = True
+    res["forecast_call"] = {f"{kind},K={K}": {"ms_median": med[kind, K], "ms_min": float(min(times[kind, K])),
+                                             "ms_max": float(max(times[kind, K])), "ms_all": [float(t) for t in times[kind, K]]}
+                            for kind, K in variants}
+    res["local_minus_global_ms"] = {f"K={K}": med["local", K] - med["global", K] for K in (1, 4)}
+    res["global_spread_ms"] = {f"K={K}": float(max(times["global", K]) - min(times["global", K])) for K in (1, 4)}
+    res["region_totals_ms"] = {f"K={K}": med["local_groups", K] - med["local", K] for K in (1, 4)}
+    print("forecast call, ms (median of %d): " % a.reps + ", ".join(f"{kind} K={K}: {med[kind, K]:.2f}" for kind, K in variants),
+          file=sys.stderr, flush=True)
 
 
 if __name__ == "__main__":
