@@ -15,7 +15,8 @@
 //   k_forecast_day            per day: a lane per (row, draw), the draw contiguous over the wave, so F, St, eb and the
 //       draw's scalars are coalesced loads.  Rates through the simulator's functions (sim_eb, sim_p_se, sim_p_ir),
 //       three sim_binomial variates, state update, X of the next day, and the day's counts as int32 into the staging
-//       tensor fev[ND][M][H][3].
+//       tensor fev[ND][M][H][3]: rollout_day_cell, the one statement of a cell's day, which the scenarios' day kernels
+//       (scenario_kernels.h, scenario_local_kernels.h) call on their own planes with their own two operands.
 //   k_forecast_fold           once per batch: k_summarize<0, 0> over the H forecast days of the staging tensor, with its
 //       pieces (summary_kernels.h) and the state scanned from the PER-DRAW initial state St0.
 //   k_forecast_keep           once per batch, behind the fold and only while the draw store is on: cases, cumulative cases
@@ -133,22 +134,24 @@ __global__ __launch_bounds__(64 * FC_ROWS) void k_forecast_prepare(Dims d, Const
     });
 }
 
-// Forecast day s for every (row, draw): grid (ndp / 64, ceil(M / FC_DAY_ROWS)), 64 FC_DAY_ROWS threads.
-// j0: the chain's draws forecast before this batch (the draw of slot_in_batch jj has j = j0 + jj).
-__global__ __launch_bounds__(64 * FC_DAY_ROWS) void k_forecast_day(Dims d, Consts c, ForecastBufs fb, int B, int chain0,
-                                                                   int j0, int ND, int ndp, int s) {
-    debug_skew(d);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int nd = blockIdx.x * 64 + lane, m = blockIdx.y * FC_DAY_ROWS + wv;
-    if (nd >= ND || m >= d.M) return;
+// THE rollout day of one (row m, draw nd) cell, whoever rolls it: the forecast, a scenario (scenario_kernels.h) or a targeted
+// scenario (scenario_local_kernels.h).  The running state is St[x plane + idx], x = S, E, I, with X and F at idx; eb is the
+// forecast's, at ebi; the draw's scalars, wd and the Philox key (k0, k1, draw id, s M + m) are the forecast's and depend on nd,
+// m and s alone -- never on the column block -- which is what couples a scenario to the baseline variate by variate.  The
+// callers differ in where the planes lie, in the two operands ea_of() = exp(log baseline) and psiW_of(psi) = psi W, called
+// where the rates are formed, and in the draw's position `draw` in the staging tensor ev [..][M][H][3].
+// Dims, Consts and ForecastBufs by value, as the kernels take them.
+template <typename Ea, typename PsiW>
+__device__ __forceinline__ void rollout_day_cell(Dims d, Consts c, ForecastBufs fb, int *St, double *X, const double *Fp,
+                                                 size_t plane, size_t idx, size_t ebi, int nd, int m, int B, int chain0, int j0,
+                                                 int ndp, int s, int *ev, size_t draw, Ea ea_of, PsiW psiW_of) {
     const int M = d.M, H = fb.H;
-    const size_t plane = (size_t)d.Mp * ndp, idx = (size_t)m * ndp + nd;
     const int jj = nd / B, b = nd - jj * B;
-    int S = fb.St[idx], E = fb.St[plane + idx], I = fb.St[2 * plane + idx];
-    const double F = fb.F[idx], eb = fb.eb[idx];
+    int S = St[idx], E = St[plane + idx], I = St[2 * plane + idx];
+    const double F = Fp[idx], eb = fb.eb[ebi];
     const double psi = fb.sc[nd], g0 = fb.sc[ndp + nd], g1 = fb.sc[2 * ndp + nd];
-    const double ea = exp(fb.base[(size_t)s * ndp + nd]);
-    const double psiW = psi * fb.W[s];
+    const double ea = ea_of();
+    const double psiW = psiW_of(psi);
     const double p_ir = sim_p_ir(g0, g1, fb.wd[s], d.dt);
     const double p_ei = sim_p_ei(d.nu, d.dt);
     const double p_se = sim_p_se(ea, eb, (double)I, psiW, F, d.rate_floor, d.dt);
@@ -158,10 +161,23 @@ __global__ __launch_bounds__(64 * FC_DAY_ROWS) void k_forecast_day(Dims d, Const
     const int y2 = sim_binomial(I, p_ir, key, RS_SIM_BASE + 2);
     SumEv32 out;
     out.k[0] = y0; out.k[1] = y1; out.k[2] = y2;
-    reinterpret_cast<SumEv32 *>(fb.fev)[((size_t)nd * M + m) * H + s] = out;
+    reinterpret_cast<SumEv32 *>(ev)[(draw * M + m) * H + s] = out;
     S -= y0; E += y0 - y1; I += y1 - y2;
-    fb.St[idx] = S; fb.St[plane + idx] = E; fb.St[2 * plane + idx] = I;
-    fb.X[idx] = (double)I * c.invN[m];
+    St[idx] = S; St[plane + idx] = E; St[2 * plane + idx] = I;
+    X[idx] = (double)I * c.invN[m];
+}
+
+// Forecast day s for every (row, draw): grid (ndp / 64, ceil(M / FC_DAY_ROWS)), 64 FC_DAY_ROWS threads.
+// j0: the chain's draws forecast before this batch (the draw of slot_in_batch jj has j = j0 + jj).
+__global__ __launch_bounds__(64 * FC_DAY_ROWS) void k_forecast_day(Dims d, Consts c, ForecastBufs fb, int B, int chain0,
+                                                                   int j0, int ND, int ndp, int s) {
+    debug_skew(d);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int nd = blockIdx.x * 64 + lane, m = blockIdx.y * FC_DAY_ROWS + wv;
+    if (nd >= ND || m >= d.M) return;
+    const size_t idx = (size_t)m * ndp + nd;
+    rollout_day_cell(d, c, fb, fb.St, fb.X, fb.F, (size_t)d.Mp * ndp, idx, idx, nd, m, B, chain0, j0, ndp, s, fb.fev, (size_t)nd,
+                     [&] { return exp(fb.base[(size_t)s * ndp + nd]); }, [&](double psi) { return psi * fb.W[s]; });
 }
 
 static_assert(FC_ROWS == SUM_ROWS && FC_JB == SUM_JB && FC_JMAX == SUM_JMAX, "k_forecast_fold uses k_summarize's pieces");
@@ -206,13 +222,7 @@ __global__ __launch_bounds__(64 * FC_ROWS) void k_forecast_fold(Dims d, Forecast
 #pragma unroll
                     for (int x = 0; x < 3; ++x) s0[x] = fb.St0[x * plane + (size_t)m * ndp + nd];
 #pragma unroll
-                for (int x = 0; x < 3; ++x) {
-                    const int inc = wave_incl_scan(kk[x], lane);
-                    const int cr = carry[wv][j][x];
-                    ex[x] = cr + inc - kk[x];
-                    const int tot = cr + __builtin_amdgcn_readlane(inc, 63);
-                    if (lane == 0) carry[wv][j][x] = tot;
-                }
+                for (int x = 0; x < 3; ++x) ex[x] = chunk_excl_scan(kk[x], lane, carry[wv][j][x]);
                 if (live) {
 #pragma unroll
                     for (int x = 0; x < 3; ++x)

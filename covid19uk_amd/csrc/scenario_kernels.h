@@ -20,7 +20,7 @@
 // scenario_update.h per cell (b, m, s) and draw, and folds them into the cell's accumulators.  k_forecast_fold's shape:
 //   - a wave per (row, chain), a lane per forecast day, SC_ROWS waves on neighbouring rows per workgroup; 64-day chunks, the
 //     prefixes over days by a DPP wave scan per transition inside a chunk and a carry per draw from chunk to chunk (3 ints, LDS;
-//     only the owning wave touches it);
+//     only the owning wave touches it): chunk_excl_scan of summary_kernels.h;
 //   - the batch's draws are the INNER loop: a cell's accumulators (4 x 28 B) are loaded before it, held in registers across
 //     it and stored after it, so they cross memory once per launch; the loads of U draws (a 12-byte access of each tensor per
 //     lane, contiguous over the wave) are issued before the first of them is used.
@@ -35,8 +35,9 @@
 //       add).  St0, eb and sc are read from the forecast's planes of the same batch, which it leaves intact: the T-long event
 //       sums are not repeated.
 //   k_gemm<64>            per day, unchanged, with Tp := K ndp: F[Mp][K ndp] = Cstar . X.
-//   k_scenario_day<R>     per day: k_forecast_day's arithmetic on K ndp columns with W_k[s]; the scalars and eb indexed by
-//       nd = c mod ndp, the RNG key built from nd alone; the counts into the staging tensor sev[K][ND][M][H][3].
+//   k_scenario_day<R>     per day: k_forecast_day's cell (rollout_day_cell, forecast_kernels.h) on K ndp columns with base_k[s]
+//       and W_k[s]; the scalars and eb indexed by nd = c mod ndp, the RNG key built from nd alone; the counts into the staging
+//       tensor sev[K][ND][M][H][3].
 // Fold and finish of scenario k are k_forecast_fold and k_forecast_finish on k's slice of sev and a MomentBufs of its own.
 #pragma once
 
@@ -63,13 +64,10 @@ struct ScenarioBufs {
     int *sev;                      // [K][ND][M][H][3] the simulated counts
 };
 
-// grid (ceil(max(Mp, H) ndp / T), K), T threads: element i of block k's planes (row i / ndp, draw i mod ndp).
-template <int T>
-__global__ __launch_bounds__(T) void k_scenario_begin(Dims d, Consts c, ForecastBufs fb, ScenarioBufs sb, int ND, int ndp) {
-    debug_skew(d);
-    const int k = blockIdx.y, H = fb.H;
-    const size_t i = (size_t)blockIdx.x * T + threadIdx.x;
-    const int r = (int)(i / ndp), nd = (int)(i - (size_t)r * ndp);
+// What a begin kernel does whatever the operands are: the element (row r, draw nd) of column block k's planes, St <- St0 and
+// X = I0 * invN by forecast_prepare_draws' operation (zero in the padded rows and draws: the contraction reads them).
+__device__ __forceinline__ void scenario_begin_planes(Dims d, Consts c, ForecastBufs fb, ScenarioBufs sb, int k, int r, int nd,
+                                                      int ND, int ndp) {
     const size_t ndk = (size_t)sb.K * ndp, fplane = (size_t)d.Mp * ndp, splane = (size_t)d.Mp * ndk;
     if (r < d.Mp) {
         const size_t src = (size_t)r * ndp + nd, dst = (size_t)r * ndk + (size_t)k * ndp + nd;
@@ -79,11 +77,21 @@ __global__ __launch_bounds__(T) void k_scenario_begin(Dims d, Consts c, Forecast
         sb.St[2 * splane + dst] = I;
         sb.X[dst] = (r < d.M && nd < ND) ? (double)I * c.invN[r] : 0.0;
     }
+}
+
+// grid (ceil(max(Mp, H) ndp / T), K), T threads: element i of block k's planes (row i / ndp, draw i mod ndp).
+template <int T>
+__global__ __launch_bounds__(T) void k_scenario_begin(Dims d, Consts c, ForecastBufs fb, ScenarioBufs sb, int ND, int ndp) {
+    debug_skew(d);
+    const int k = blockIdx.y, H = fb.H;
+    const size_t i = (size_t)blockIdx.x * T + threadIdx.x;
+    const int r = (int)(i / ndp), nd = (int)(i - (size_t)r * ndp);
+    scenario_begin_planes(d, c, fb, sb, k, r, nd, ND, ndp);
     if (r < H) sb.base[((size_t)k * H + r) * ndp + nd] = nd < ND ? fb.base[(size_t)r * ndp + nd] + sb.log_shift[k * H + r] : 0.0;
 }
 
-// Forecast day s for every (row, scenario, draw): grid (K ndp / 64, ceil(M / R)), 64 R threads; k_forecast_day but for the
-// column block's baseline and commuting volume.
+// Forecast day s for every (row, scenario, draw): grid (K ndp / 64, ceil(M / R)), 64 R threads; rollout_day_cell on column
+// c = k ndp + nd of the scenarios' planes, with the column block's baseline and commuting volume.
 template <int R>
 __global__ __launch_bounds__(64 * R) void k_scenario_day(Dims d, Consts c, ForecastBufs fb, ScenarioBufs sb, int B, int chain0,
                                                          int j0, int ND, int ndp, int s) {
@@ -92,27 +100,12 @@ __global__ __launch_bounds__(64 * R) void k_scenario_day(Dims d, Consts c, Forec
     const int col = blockIdx.x * 64 + lane, m = blockIdx.y * R + wv;
     const int k = col / ndp, nd = col - k * ndp;
     if (nd >= ND || m >= d.M) return;
-    const int M = d.M, H = fb.H;
-    const size_t ndk = (size_t)sb.K * ndp, plane = (size_t)d.Mp * ndk, idx = (size_t)m * ndk + col;
-    const int jj = nd / B, b = nd - jj * B;
-    int S = sb.St[idx], E = sb.St[plane + idx], I = sb.St[2 * plane + idx];
-    const double F = sb.F[idx], eb = fb.eb[(size_t)m * ndp + nd];
-    const double psi = fb.sc[nd], g0 = fb.sc[ndp + nd], g1 = fb.sc[2 * ndp + nd];
-    const double ea = exp(sb.base[((size_t)k * H + s) * ndp + nd]);
-    const double psiW = psi * sb.Wk[k * H + s];
-    const double p_ir = sim_p_ir(g0, g1, fb.wd[s], d.dt);
-    const double p_ei = sim_p_ei(d.nu, d.dt);
-    const double p_se = sim_p_se(ea, eb, (double)I, psiW, F, d.rate_floor, d.dt);
-    RngKey key{fb.k0, fb.k1, ((uint32_t)(chain0 + b) << FC_ID_SHIFT) + (uint32_t)(j0 + jj), (uint32_t)(s * M + m)};
-    const int y0 = sim_binomial(S, p_se, key, RS_SIM_BASE + 0);
-    const int y1 = sim_binomial(E, p_ei, key, RS_SIM_BASE + 1);
-    const int y2 = sim_binomial(I, p_ir, key, RS_SIM_BASE + 2);
-    SumEv32 out;
-    out.k[0] = y0; out.k[1] = y1; out.k[2] = y2;
-    reinterpret_cast<SumEv32 *>(sb.sev)[(((size_t)k * ND + nd) * M + m) * H + s] = out;
-    S -= y0; E += y0 - y1; I += y1 - y2;
-    sb.St[idx] = S; sb.St[plane + idx] = E; sb.St[2 * plane + idx] = I;
-    sb.X[idx] = (double)I * c.invN[m];
+    const int H = fb.H;
+    const size_t ndk = (size_t)sb.K * ndp;
+    rollout_day_cell(d, c, fb, sb.St, sb.X, sb.F, (size_t)d.Mp * ndk, (size_t)m * ndk + col, (size_t)m * ndp + nd, nd, m, B,
+                     chain0, j0, ndp, s, sb.sev, (size_t)k * ND + nd,
+                     [&] { return exp(sb.base[((size_t)k * H + s) * ndp + nd]); },
+                     [&](double psi) { return psi * sb.Wk[k * H + s]; });
 }
 
 // A scenario's difference accumulators, [B][M][H][SCENARIO_Q] each.
@@ -175,11 +168,7 @@ __global__ __launch_bounds__(64 * SC_ROWS) void k_scenario_diff(Dims d, Scenario
 #pragma unroll
                 for (int x = 0; x < 3; ++x) {
                     dx[x] = ks[u][x] - kf[u][x];
-                    const int inc = wave_incl_scan(dx[x], lane);
-                    const int cr = carry[wv][j][x];
-                    ex[x] = cr + inc - dx[x];
-                    const int tot = cr + __builtin_amdgcn_readlane(inc, 63);
-                    if (lane == 0) carry[wv][j][x] = tot;
+                    ex[x] = chunk_excl_scan(dx[x], lane, carry[wv][j][x]);
                 }
                 if (live) {
                     int32_t val[SCENARIO_Q];

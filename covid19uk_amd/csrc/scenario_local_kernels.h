@@ -4,7 +4,7 @@
 // THE definition of a targeted scenario.  Scenario k is two tensors over the M locations and the H forecast days:
 //     log_shift[k][m][s]   any finite double
 //     commute[k][m][s]     finite and >= 0
-// and the rollout of a draw in column (k, nd) is k_scenario_day's with two operands replaced:
+// and the rollout of a draw in column (k, nd) is k_scenario_day's -- rollout_day_cell (forecast_kernels.h) -- with its two operands:
 //     ea   = exp(base_0[s][nd] + log_shift[k][m][s])     one rounded add, then the same exp
 //     psiW = psi * Wk[k][m][s],  Wk[k][m][s] = W[s] * commute[k][m][s]     one rounded multiply, formed on the host
 // Everything else is the forecast's: the state at day T, eb, psi, gamma0, gamma1, wd, the Philox key and counter (attempt,
@@ -27,7 +27,7 @@
 // scalar loads per wave and day, not 64 identical vector loads.
 //
 // The local path has no base[K][H][ndp] plane: the add has moved into the day kernel, which reads the forecast's own
-// base_0[s][nd].  k_scenario_local_begin is k_scenario_begin without that write.
+// base_0[s][nd].  k_scenario_local_begin is scenario_begin_planes alone, without k_scenario_begin's write of that plane.
 #pragma once
 
 #include "scenario_kernels.h"
@@ -44,21 +44,13 @@ struct ScenarioLocalBufs {
 template <int T>
 __global__ __launch_bounds__(T) void k_scenario_local_begin(Dims d, Consts c, ForecastBufs fb, ScenarioBufs sb, int ND, int ndp) {
     debug_skew(d);
-    const int k = blockIdx.y;
     const size_t i = (size_t)blockIdx.x * T + threadIdx.x;
     const int r = (int)(i / ndp), nd = (int)(i - (size_t)r * ndp);
-    const size_t ndk = (size_t)sb.K * ndp, fplane = (size_t)d.Mp * ndp, splane = (size_t)d.Mp * ndk;
-    if (r >= d.Mp) return;
-    const size_t src = (size_t)r * ndp + nd, dst = (size_t)r * ndk + (size_t)k * ndp + nd;
-    const int I = fb.St0[2 * fplane + src];
-    sb.St[dst] = fb.St0[src];
-    sb.St[splane + dst] = fb.St0[fplane + src];
-    sb.St[2 * splane + dst] = I;
-    sb.X[dst] = (r < d.M && nd < ND) ? (double)I * c.invN[r] : 0.0;
+    scenario_begin_planes(d, c, fb, sb, blockIdx.y, r, nd, ND, ndp);
 }
 
-// Forecast day s for every (row, scenario, draw): grid (K ndp / 64, ceil(M / R)), 64 R threads; k_scenario_day but for the
-// two operands, which are the row's own.
+// Forecast day s for every (row, scenario, draw): grid (K ndp / 64, ceil(M / R)), 64 R threads; rollout_day_cell on
+// k_scenario_day's planes, with the two operands the row's own.
 template <int R>
 __global__ __launch_bounds__(64 * R) void k_scenario_local_day(Dims d, Consts c, ForecastBufs fb, ScenarioBufs sb,
                                                                ScenarioLocalBufs lb, int B, int chain0, int j0, int ND, int ndp,
@@ -68,28 +60,12 @@ __global__ __launch_bounds__(64 * R) void k_scenario_local_day(Dims d, Consts c,
     const int col = blockIdx.x * 64 + lane, m = blockIdx.y * R + wv;
     const int k = (blockIdx.x * 64) / ndp, nd = col - k * ndp;       // ndp is a multiple of 64: the wave's scenario
     if (nd >= ND || m >= d.M) return;
-    const int M = d.M, H = fb.H;
-    const size_t ndk = (size_t)sb.K * ndp, plane = (size_t)d.Mp * ndk, idx = (size_t)m * ndk + col;
-    const int jj = nd / B, b = nd - jj * B;
-    int S = sb.St[idx], E = sb.St[plane + idx], I = sb.St[2 * plane + idx];
-    const double F = sb.F[idx], eb = fb.eb[(size_t)m * ndp + nd];
-    const double psi = fb.sc[nd], g0 = fb.sc[ndp + nd], g1 = fb.sc[2 * ndp + nd];
-    const int op = __builtin_amdgcn_readfirstlane((k * H + s) * M + m);   // k < 4, H <= 128: below 2^31 for every M
-    const double ea = exp(fb.base[(size_t)s * ndp + nd] + lb.log_shift[op]);
-    const double psiW = psi * lb.Wk[op];
-    const double p_ir = sim_p_ir(g0, g1, fb.wd[s], d.dt);
-    const double p_ei = sim_p_ei(d.nu, d.dt);
-    const double p_se = sim_p_se(ea, eb, (double)I, psiW, F, d.rate_floor, d.dt);
-    RngKey key{fb.k0, fb.k1, ((uint32_t)(chain0 + b) << FC_ID_SHIFT) + (uint32_t)(j0 + jj), (uint32_t)(s * M + m)};
-    const int y0 = sim_binomial(S, p_se, key, RS_SIM_BASE + 0);
-    const int y1 = sim_binomial(E, p_ei, key, RS_SIM_BASE + 1);
-    const int y2 = sim_binomial(I, p_ir, key, RS_SIM_BASE + 2);
-    SumEv32 out;
-    out.k[0] = y0; out.k[1] = y1; out.k[2] = y2;
-    reinterpret_cast<SumEv32 *>(sb.sev)[(((size_t)k * ND + nd) * M + m) * H + s] = out;
-    S -= y0; E += y0 - y1; I += y1 - y2;
-    sb.St[idx] = S; sb.St[plane + idx] = E; sb.St[2 * plane + idx] = I;
-    sb.X[idx] = (double)I * c.invN[m];
+    const size_t ndk = (size_t)sb.K * ndp;
+    const int op = __builtin_amdgcn_readfirstlane((k * fb.H + s) * d.M + m);   // k < 4, H <= 128: below 2^31 for every M
+    rollout_day_cell(d, c, fb, sb.St, sb.X, sb.F, (size_t)d.Mp * ndk, (size_t)m * ndk + col, (size_t)m * ndp + nd, nd, m, B,
+                     chain0, j0, ndp, s, sb.sev, (size_t)k * ND + nd,
+                     [&] { return exp(fb.base[(size_t)s * ndp + nd] + lb.log_shift[op]); },
+                     [&](double psi) { return psi * lb.Wk[op]; });
 }
 
 }  // namespace seir

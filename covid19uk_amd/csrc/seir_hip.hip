@@ -4379,6 +4379,19 @@ extern "C" int seir_scenario_diffs(seir_ctx *ctx, const int32_t *base_events, co
 static void scenarios_local_rollout(seir_sampler *s, const LaunchCfg &l, const ForecastBufs &fb, const ScenarioBufs &sb,
                                     const RolloutBatch &bt, int j);
 
+// The rollout of a batch's K column blocks, whichever set rolls it: `begin` over `elems` elements of every block's planes, then
+// the H days over the K ndp columns with day(grid, block, h), the set's day launch.
+using ScenarioBegin = void (*)(Dims, Consts, ForecastBufs, ScenarioBufs, int, int);
+template <typename Day>
+static void scenarios_rollout(seir_ctx *ctx, const LaunchCfg &l, const ForecastBufs &fb, const ScenarioBufs &sb,
+                              const RolloutBatch &bt, ScenarioBegin begin, size_t elems, Day day) {
+    const int cols = sb.K * bt.ndp;
+    hipLaunchKernelGGL(begin, dim3((unsigned)((elems + SC_BEGIN_THREADS - 1) / SC_BEGIN_THREADS), sb.K), dim3(SC_BEGIN_THREADS), 0,
+                       l.st, l.d, ctx->c, fb, sb, bt.ND, bt.ndp);
+    const dim3 grid(cols / 64, (l.d.M + FC_DAY_ROWS - 1) / FC_DAY_ROWS), block(64 * FC_DAY_ROWS);
+    rollout_day_loop(ctx, l, sb.X, sb.F, cols, fb.H, [&](int h) { day(grid, block, h); });
+}
+
 // Scenario k's parts of the one block (ScenarioSet::acc): the moments into mb's accumulator pointers, the differences into df.
 static void scenarios_layout(const ScenarioSet &sc, int k, MomentBufs &mb, ScenarioDiffBufs &df) {
     uint64_t *w8 = sc.acc.buf.as<uint64_t>() + (size_t)k * sc.words8();
@@ -4449,18 +4462,17 @@ static int scenarios_batch(seir_sampler *s, const ForecastBufs &fb, const Rollou
     seir_ctx *ctx = s->ctx;
     const LaunchCfg l = whole(ctx, s->cfg.B);
     const Dims &d = l.d;
-    const int B = s->cfg.B, H = fb.H, K = sc.K, ND = bt.ND, ndp = bt.ndp, cols = K * ndp;
+    const int B = s->cfg.B, H = fb.H, K = sc.K, ND = bt.ND, ndp = bt.ndp;
     const long long j = s->fc.acc.j + bt.j0;        // the batch's first draw position
     const ScenarioBufs sb{K, sc.log_shift, sc.Wk, sc.St, sc.X, sc.F, sc.base, sc.sev};
-    const size_t elems = (size_t)std::max(d.Mp, H) * ndp;
     if (sc.local) {
         scenarios_local_rollout(s, l, fb, sb, bt, (int)j);
     } else {
-        hipLaunchKernelGGL(k_scenario_begin<SC_BEGIN_THREADS>, dim3((unsigned)((elems + SC_BEGIN_THREADS - 1) / SC_BEGIN_THREADS), K),
-                           dim3(SC_BEGIN_THREADS), 0, l.st, d, ctx->c, fb, sb, ND, ndp);
-        rollout_day_loop(ctx, l, sc.X, sc.F, cols, H, [&](int h) {
-            hipLaunchKernelGGL(k_scenario_day<FC_DAY_ROWS>, dim3(cols / 64, (d.M + FC_DAY_ROWS - 1) / FC_DAY_ROWS),
-                               dim3(64 * FC_DAY_ROWS), 0, l.st, d, ctx->c, fb, sb, B, s->cfg.chain0, (int)j, ND, ndp, h);
+        // a variable, so that the begin is named -- and emitted -- in front of the day kernel; it also writes the base plane's H rows
+        const ScenarioBegin begin = k_scenario_begin<SC_BEGIN_THREADS>;
+        scenarios_rollout(ctx, l, fb, sb, bt, begin, (size_t)std::max(d.Mp, H) * ndp, [&](dim3 grid, dim3 block, int h) {
+            hipLaunchKernelGGL(k_scenario_day<FC_DAY_ROWS>, grid, block, 0, l.st, d, ctx->c, fb, sb, B, s->cfg.chain0, (int)j, ND,
+                               ndp, h);
         });
     }
     const size_t slice = (size_t)ND * d.M * H * 3, row = (size_t)B * H * 3, slot0 = (size_t)(first + bt.j0);
@@ -4927,15 +4939,10 @@ extern "C" int seir_pair_abs_sums(seir_ctx *ctx, const int32_t *values, int64_t 
 
 static void scenarios_local_rollout(seir_sampler *s, const LaunchCfg &l, const ForecastBufs &fb, const ScenarioBufs &sb,
                                     const RolloutBatch &bt, int j) {
-    seir_ctx *ctx = s->ctx;
-    const Dims &d = l.d;
     const ScenarioLocalBufs lb{s->scen.log_shift_loc, s->scen.Wk_loc};
-    const int K = sb.K, cols = K * bt.ndp;
-    const size_t elems = (size_t)d.Mp * bt.ndp;
-    hipLaunchKernelGGL(k_scenario_local_begin<SC_BEGIN_THREADS>, dim3((unsigned)((elems + SC_BEGIN_THREADS - 1) / SC_BEGIN_THREADS), K),
-                       dim3(SC_BEGIN_THREADS), 0, l.st, d, ctx->c, fb, sb, bt.ND, bt.ndp);
-    rollout_day_loop(ctx, l, sb.X, sb.F, cols, fb.H, [&](int h) {
-        hipLaunchKernelGGL(k_scenario_local_day<FC_DAY_ROWS>, dim3(cols / 64, (d.M + FC_DAY_ROWS - 1) / FC_DAY_ROWS),
-                           dim3(64 * FC_DAY_ROWS), 0, l.st, d, ctx->c, fb, sb, lb, s->cfg.B, s->cfg.chain0, j, bt.ND, bt.ndp, h);
+    const ScenarioBegin begin = k_scenario_local_begin<SC_BEGIN_THREADS>;   // in front of the day kernel, as in scenarios_batch
+    scenarios_rollout(s->ctx, l, fb, sb, bt, begin, (size_t)l.d.Mp * bt.ndp, [&](dim3 grid, dim3 block, int h) {
+        hipLaunchKernelGGL(k_scenario_local_day<FC_DAY_ROWS>, grid, block, 0, l.st, l.d, s->ctx->c, fb, sb, lb, s->cfg.B,
+                           s->cfg.chain0, j, bt.ND, bt.ndp, h);
     });
 }

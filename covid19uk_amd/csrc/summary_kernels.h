@@ -83,10 +83,23 @@ __device__ __forceinline__ void summary_load(const void *__restrict__ tr, size_t
 
 // The pieces of the fold that k_summarize and k_forecast_fold (forecast_kernels.h) share.  Pieces, and not one body templated
 // on where the draws come from: as ONE inlined function the loop nest takes 81 VGPRs in k_summarize<0,0> and k_forecast_fold
-// where it takes 73 and 69 in the kernels, a wave or two of occupancy.  These four leave the machine code of all five kernels
-// what it was; the carry scan, the store of the accumulators and the row totals as functions do not (the same registers, other
-// code, and one-chain calls 0.2 to 1 % slower), so those stay written out in both kernels, with the loop nest (DESIGN.md,
-// "One accumulator, three users").
+// where it takes 73 and 69 in the kernels, a wave or two of occupancy.  fold_values, fold_tile_flush, fold_lds_zero and
+// fold_load leave the machine code of all five kernels what it was with the text written out; so does chunk_excl_scan, but
+// for two independent instructions that change places in the two DIAG instances.  The store of the
+// accumulators and the row totals stay written out in both kernels, with the loop nest ("One accumulator, three
+// users").
+
+// The chunk step of a prefix over days, also k_scenario_diff's (scenario_kernels.h): the lane's exclusive prefix of v over
+// the days so far, from the wave scan inside the 64-day chunk and the carry (LDS, the owning wave's alone) from the chunks
+// before, which lane 0 then moves on by the chunk's total.  Every lane of the wave calls it.
+__device__ __forceinline__ int chunk_excl_scan(int v, int lane, int &carry) {
+    const int inc = wave_incl_scan(v, lane);
+    const int cr = carry;
+    const int ex = cr + inc - v;
+    const int tot = cr + __builtin_amdgcn_readlane(inc, 63);
+    if (lane == 0) carry = tot;
+    return ex;
+}
 
 // The six quantities of a cell: the day's counts, and the state before them from the initial state s0 and the prefix.
 __device__ __forceinline__ void fold_values(const int (&k)[3], const int (&s0)[3], const int (&ex)[3], int (&val)[SUMMARY_Q]) {
@@ -193,13 +206,7 @@ __global__ __launch_bounds__(64 * SUM_ROWS) void k_summarize(Dims d, Consts c, M
                     const int jj = ju + u, j = jb + jj;
                     int ex[3];
 #pragma unroll
-                    for (int x = 0; x < 3; ++x) {
-                        const int inc = wave_incl_scan(kk[u][x], lane);
-                        const int cr = carry[wv][j][x];
-                        ex[x] = cr + inc - kk[u][x];
-                        const int tot = cr + __builtin_amdgcn_readlane(inc, 63);
-                        if (lane == 0) carry[wv][j][x] = tot;
-                    }
+                    for (int x = 0; x < 3; ++x) ex[x] = chunk_excl_scan(kk[u][x], lane, carry[wv][j][x]);
                     if (live) {
 #pragma unroll
                         for (int x = 0; x < 3; ++x)

@@ -69,6 +69,28 @@ def kernel_account(owner=None):
     return res if owner is None else kernel_resources.owned(res, owner)
 
 
+def device_functions(tmp_path):
+    """{mangled name: (address, size)} of the FUNC symbols of the library's gfx950 code object, read with the LLVM tools that
+    lie next to the compiler that built it."""
+    import subprocess
+
+    import __graft_entry__ as entry
+    entry.build()
+    rocm = os.path.dirname(os.path.dirname(os.path.realpath(entry._hipcc())))
+    tools = next(d for d in (os.path.join(rocm, "lib", "llvm", "bin"), os.path.join(rocm, "llvm", "bin"))
+                 if os.path.exists(os.path.join(d, "clang-offload-bundler")))
+    fat, co = str(tmp_path / "lib.fatbin"), str(tmp_path / "lib.co")
+    subprocess.check_call([os.path.join(tools, "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", entry.LIB, fat])
+    subprocess.check_call([os.path.join(tools, "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={fat}",
+                           "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"])
+    out = {}
+    for line in subprocess.check_output([os.path.join(tools, "llvm-readelf"), "-sW", co], text=True).splitlines():
+        p = line.split()
+        if len(p) >= 8 and p[3] == "FUNC":
+            out[p[7]] = (int(p[1], 16), int(p[2]))
+    return out
+
+
 from oracle import c_binding
 
 

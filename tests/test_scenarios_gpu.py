@@ -236,6 +236,10 @@ SCEN_CASES = {
     "M=520,H=128,K=2": ("slow_520x70", CFG_SMALL, 3e-5, 2, True, 3, 128, dict(a=dict(transmission=0.5), b=dict(commute=0.0)), False),
     "uk380x8,12,H=14,K=2": ("uk380", CFG_REF, 1.2e-5, 8, "u16", 12, 14, dict(a=dict(transmission=0.8, from_day=7), b=dict(commute=0.5)),
                             False),
+    # the day cell's indexing all at once: M no multiple of the day kernel's 4 rows, ND = 65 (two column blocks per scenario, the
+    # second with one live draw), K = 2, and B = 5, which does not divide 64: a wave's draws begin in the middle of a slot
+    "ni11,B=5,ND=65,H=3,K=2": ("ni11", CFG_REF, 0.002, 5, "u16", 13, 3,
+                               dict(a=dict(transmission=0.5), b=dict(transmission=1.2, commute=0.5, from_day=1)), False),
 }
 
 

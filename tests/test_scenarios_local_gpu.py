@@ -31,8 +31,11 @@ pytestmark = pytest.mark.gpu
 
 # name, cfg, eps, B, record, n, H, K: the shapes of tests/test_scenarios_gpu.py's SCEN_CASES -- M = 1 / H = 1; one row past the day
 # kernel's 4-row block and the fold's 8-row block with H one chunk and one day past it; one row past a 64-row tile; several
-# row tiles with two day chunks; K = 1, 2, 4; 1, 3, 8 chains; both trace widths
+# row tiles with two day chunks; K = 1, 2, 4; 1, 3, 8 chains; both trace widths; and NI-11 with 13 draws of 5 chains -- M no
+# multiple of the day kernel's 4 rows, ND = 65 (two column blocks per scenario, the second with one live draw), K = 2, B not
+# dividing 64 -- all at once
 SHAPES = {
+    "M=11,H=3,K=2,B=5,ND=65,u16": ("ni11", CFG_REF, 0.002, 5, "u16", 13, 3, 2),
     "M=1,H=1,K=1,B=3,u16": ("micro_1x70", CFG_SMALL, 0.002, 3, "u16", 6, 1, 1),
     "M=9,H=64,K=4,B=3,u16": ("micro_9x64", CFG_SMALL, 0.0004, 3, "u16", 5, 64, 4),
     "M=9,H=65,K=2,B=8": ("micro_9x64", CFG_SMALL, 0.0004, 8, True, 4, 65, 2),

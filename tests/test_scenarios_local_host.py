@@ -379,3 +379,21 @@ def test_the_kernels_account_owner_scenarios_local_and_the_resources_condition()
         assert v["vgpr_spill"] == 0 and v["sgpr_spill"] == 0, (k, v)
     begin = res["k_scenario_local_begin<256>"]
     assert begin["scratch_bytes_per_lane"] == 0 and begin["lds_bytes_per_block"] == 0
+
+
+def test_the_scenario_kernels_keep_their_order_in_the_code_object(tmp_path):
+    """A kernel template is emitted where the host code first names it: every begin instance lies in front of its day
+    instance, the global pair in front of the local pair, and the local pair behind every other kernel of the library --
+    what the host's launches (`scenarios_batch`, `scenarios_local_rollout` in seir_hip.hip) have to keep, so that no other
+    kernel moves."""
+    fn = H.device_functions(tmp_path)
+
+    def at(part):
+        hits = [v[0] for k, v in fn.items() if part in k]
+        assert len(hits) == 1, (part, hits)
+        return hits[0]
+
+    begin, day = at("16k_scenario_beginILi256E"), at("14k_scenario_dayILi4E")
+    lbegin, lday = at("22k_scenario_local_beginILi256E"), at("20k_scenario_local_dayILi4E")
+    assert begin < day < lbegin < lday
+    assert sorted(a for a, _ in fn.values())[-2:] == [lbegin, lday]
