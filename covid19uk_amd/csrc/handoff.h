@@ -151,11 +151,7 @@ __device__ __forceinline__ void ll_wait(const uint4 *const (&p)[N], unsigned seq
 #ifndef LEAP_ROLE_PRIO
 #define LEAP_ROLE_PRIO 3            // k_leap's role waves (see there)
 #endif
-#ifdef LL_POLL_DROP_PRIO
-#define LL_RPRIO LEAP_ROLE_PRIO
-#else
-#define LL_RPRIO -1
-#endif
+#define LL_RPRIO -1                 // the roles' polls keep their priority
 template <int N, int RPRIO = -1> __device__ __forceinline__ void ll_poll(const uint4 *const (&p)[N], unsigned seq, unsigned *late, double (&v)[N]) {
     u32x4 x[N];
     ll_wait<N, LL_POLL_SLEEP, HS_CHECK_LL, HS_LIMIT_LL, RPRIO>(p, seq, late, x);

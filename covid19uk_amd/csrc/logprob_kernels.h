@@ -18,6 +18,7 @@
 #pragma once
 #include "device_math.h"
 #include "handoff.h"
+#include "stamps.h"
 
 namespace seir {
 
@@ -785,11 +786,7 @@ __device__ __forceinline__ void se_tile(const Dims &d, const Consts &c, const Wo
     const int b = d.b0 + bz, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int t = bx * WAVE + lane;
     const int m0 = by * SE_TM + wave * SE_RW;
-#ifdef SE_STAMPS
-    // developer timeline (tools/dev/se_timeline.py): start / end of every tile workgroup in the two free tile scalars
-    unsigned long long se_t0 = 0;
-    if (GRAD && SRC == 1 && TSM == 1) se_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
+    const SeStamp se_st = SE_STAMP_BEGIN(GRAD && SRC == 1 && TSM == 1);   // developer timeline (stamps.h: SE)
     if (threadIdx.x < LOGTAB_N) ltab[threadIdx.x] = c.logtab[threadIdx.x];   // barrier below, after the loads
     const double psi = w.scal[(size_t)b * NSCAL + SC_PSI];
     const double ea_t = w.ea[(size_t)b * d.Tp + t];
@@ -893,20 +890,7 @@ __device__ __forceinline__ void se_tile(const Dims &d, const Consts &c, const Wo
             if (lane == 0) { w.TS[tile * 4 + 2] = rl; w.TS[tile * 4 + 3] = rs; }
         }
     }
-#ifdef SE_STAMPS
-    if (GRAD && SRC == 1 && TSM == 1) {
-        __syncthreads();                                  // every wave's stores issued and acknowledged
-        if (threadIdx.x == 0) {
-            unsigned xcc, hw;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-            unsigned long long *ts = reinterpret_cast<unsigned long long *>(w.TS);
-            ts[tile * 4 + 2] = se_t0;
-            ts[tile * 4 + 3] = (__builtin_amdgcn_s_memrealtime() & 0xffffffffffffull) | ((unsigned long long)(xcc & 0xf) << 60) |
-                               ((unsigned long long)((hw >> 8) & 0xfff) << 48);
-        }
-    }
-#endif
+    SE_STAMP_END(se_st, GRAD && SRC == 1 && TSM == 1, w.TS, tile);
 }
 
 template <bool GRAD, int SRC, int TSM = 0>
@@ -987,6 +971,20 @@ __host__ __device__ inline size_t gemm_se_lds_bytes() {
     const size_t epi = ((size_t)GEMM_TM * (TN + 2) + 4 * TN + 2 * GEMM_TM + 16) * sizeof(double);
     return panels > epi ? panels : epi;
 }
+// gemm_se_tile's staging of one chunk: global -> the named registers of a Stage -> LDS (names from the function's scope)
+#define GSE_LOAD(st, kb)                                                        \
+    do {                                                                        \
+        st.a = *(const v2d *)(pa + (size_t)(kb) * d.Kp0);                   \
+        st.b0 = *(const v2d *)(pb0 + (size_t)(kb) * d.Tp);                  \
+        if (NB > 1) st.b1 = *(const v2d *)(pb1 + (size_t)(kb) * d.Tp);      \
+    } while (0)
+#define GSE_STORE(st, buf)                                                      \
+    do {                                                                        \
+        double *A_ = lds + (buf) * PANEL, *B_ = A_ + GSE_KC * GEMM_RS;          \
+        *(v2d *)(A_ + ea_row * GEMM_RS + ea_col) = st.a;                        \
+        *(v2d *)(B_ + eb0_row * RSB + eb0_col) = st.b0;                         \
+        if (NB > 1) *(v2d *)(has_b1 ? B_ + eb1_row * RSB + eb1_col : lds + 2 * PANEL) = st.b1;  \
+    } while (0)
 template <bool GRAD, int TN>
 __device__ __forceinline__ void gemm_se_tile(const Dims &d, const Consts &c, const Work &w, int bx, int by, int bz) {
     extern __shared__ double lds[];                 // 2 x (A [KC][RS] | B [KC][RSB]); the epilogue's tile and reduction buffers afterwards
@@ -1014,19 +1012,6 @@ __device__ __forceinline__ void gemm_se_tile(const Dims &d, const Consts &c, con
     const bool has_b1 = NB > 1 && tid + NT < EB;
     const double *pa = c.Cstar + (size_t)ea_row * d.Kp0 + m0 + ea_col;
     const double *pb0 = Xb + (size_t)eb0_row * d.Tp + t0 + eb0_col, *pb1 = Xb + (size_t)eb1_row * d.Tp + t0 + eb1_col;
-#define GSE_LOAD(st, kb)                                                        \
-    do {                                                                        \
-        st.a = *(const v2d *)(pa + (size_t)(kb) * d.Kp0);                   \
-        st.b0 = *(const v2d *)(pb0 + (size_t)(kb) * d.Tp);                  \
-        if (NB > 1) st.b1 = *(const v2d *)(pb1 + (size_t)(kb) * d.Tp);      \
-    } while (0)
-#define GSE_STORE(st, buf)                                                      \
-    do {                                                                        \
-        double *A_ = lds + (buf) * PANEL, *B_ = A_ + GSE_KC * GEMM_RS;          \
-        *(v2d *)(A_ + ea_row * GEMM_RS + ea_col) = st.a;                        \
-        *(v2d *)(B_ + eb0_row * RSB + eb0_col) = st.b0;                         \
-        if (NB > 1) *(v2d *)(has_b1 ? B_ + eb1_row * RSB + eb1_col : lds + 2 * PANEL) = st.b1;  \
-    } while (0)
     d4 acc[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) acc[j] = (d4){0.0, 0.0, 0.0, 0.0};
@@ -1467,11 +1452,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void k_eval_all(Dims d, Consts c, Work w, const double *__restrict__ events, const double *__restrict__ u_all,
                 double *__restrict__ logp, double *__restrict__ grad, unsigned long long *cnt,
                 unsigned long long targetA, unsigned long long targetB, int *err, int do_finish) {
-#ifdef EVAL_STAMPS
-#define ESTAMP(i) do { if (threadIdx.x == 0 && chain == 0 && tile_or0 == 0) cnt[NB * EVC_STRIDE + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define ESTAMP(i) do {} while (0)
-#endif
     const int NB = d.aff_nb;                                // chains of the layout: a multiple of 8
     const int wave_s = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int per = d.ntc * d.nmt, ncb = d.Tp / WAVE;
@@ -1495,8 +1475,7 @@ void k_eval_all(Dims d, Consts c, Work w, const double *__restrict__ events, con
         // separate state blocks ahead of the tiles made happen (the matrix work of such a CU doubles) -- then waits
         // for the whole chain's state and evaluates its tile
         const int tile = L / NB;
-        const int tile_or0 = tile;
-        ESTAMP(0);
+        ESTAMP(tile, 0);                                    // developer timeline (stamps.h: EVAL)
         const int rbt = (d.nrb_scan + per - 1) / per;
         if (rbt == 2 && tile * 2 + 1 < d.nrb_scan && d.Tp <= SCAN_CB * WAVE) {
             scan_rows_state2(d, c, w, events, tile * 2, tile * 2 + 1, chain);      // both blocks' events in flight at once
@@ -1507,12 +1486,12 @@ void k_eval_all(Dims d, Consts c, Work w, const double *__restrict__ events, con
                 __syncthreads();                            // the next row block reuses the scan's LDS
             }
         }
-        ESTAMP(1);
+        ESTAMP(tile, 1);
         evc_arrive(cA, wave_s);
         evc_wait(cA, targetA, err);
-        ESTAMP(2);
+        ESTAMP(tile, 2);
         gemm_se_tile<GRAD, TN>(d, c, w, tile % d.ntc, tile / d.ntc, chain);
-        ESTAMP(3);
+        ESTAMP(tile, 3);
         evc_arrive(cB, wave_s);
         return;
     }
@@ -1531,15 +1510,13 @@ void k_eval_all(Dims d, Consts c, Work w, const double *__restrict__ events, con
         return;
     }
     if (!do_finish) return;
-    const int tile_or0 = 0;
-    ESTAMP(4);
+    ESTAMP(0, 4);
     evc_wait(cB, targetB, err);
-    ESTAMP(5);
+    ESTAMP(0, 5);
     if (threadIdx.x >= 256) return;
     finish_chain<GRAD>(d, c, w, u_all, logp, grad, 1, d.b0 + chain);
-    ESTAMP(6);
+    ESTAMP(0, 6);
 }
-#undef ESTAMP
 template <int TN>
 inline size_t eval_all_lds_bytes(const Dims &d) {
     const size_t a = eval_tiles_lds_bytes<TN>(), b2 = (size_t)SCAN_WAVES * d.Tp * 2 * sizeof(double);

@@ -21,23 +21,7 @@
 
 namespace seir {
 
-#ifdef SEIR_STAMPS
-#ifndef SEIR_STAMP_SLOT
-#define SEIR_STAMP_SLOT 1
-#endif
-#define MSTAMP(i) do { if (threadIdx.x == 0 && stamp_on) ((unsigned long long *)(stamp_hs + 16))[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define MSTAMP(i) do {} while (0)
-#endif
-
-// developer probe (tools/dev/pair_timeline.py): plain stores of the clock by thread 0 of chain 0's workgroups, per step of
-// the pair launch: Chains::leap_st[(slot * 12 + step) * 16 + i]
-#ifdef PAIR_STAMPS
-#define QSTAMP(slot_, step_, i_) do { if (threadIdx.x == 0 && (b_stamp) == 0 && (step_) < 12 && (slot_) < 27) \
-    ch.leap_st[((size_t)(slot_) * 12 + (step_)) * 16 + (i_)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define QSTAMP(slot_, step_, i_) do {} while (0)
-#endif
+// (MSTAMP and QSTAMP in this file: developer timelines, stamps.h: SEIR and PAIR)
 
 constexpr int MVB = 512;              // threads
 constexpr int MVW = MVB / WAVE;       // waves
@@ -84,12 +68,9 @@ __device__ __forceinline__ void mv_sum2(double &a, double &b2, double *sh) {
 }
 
 // arrays the proposal works from
-struct MvLds {
+struct MvLds : MoveStamp {
     const int *rt;         // [M] row totals of the target transition's events (LDS copy, patched)
     int *rg;               // [M] events of the target transition inside the occult range (LDS)
-#ifdef SEIR_STAMPS
-    double *stamp_hs; bool stamp_on;
-#endif
 };
 
 // log of a small positive integer-valued double (counts, bounds): table log; log 1 = 0 exactly
@@ -221,10 +202,7 @@ __device__ inline void mv_propose_wave(const Dims &d, const Work &w, const Sampl
                                        bool rows_only) {
     Move &mv = sm.mv;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, M = d.M, T = d.T;
-#ifdef SEIR_STAMPS
-    double *stamp_hs = L.stamp_hs; const bool stamp_on = L.stamp_on;
-#endif
-    MSTAMP(4);
+    MSTAMP(L, 4);
     const int tgt = spec.tgt;
     lds_barrier();                                           // publishes sm.u / the header (mv_draw) and the totals in LDS
     if (spec.kind == 0) {
@@ -266,7 +244,7 @@ __device__ inline void mv_propose_wave(const Dims &d, const Work &w, const Sampl
             lds_barrier();
             return;
         }
-        MSTAMP(5);
+        MSTAMP(L, 5);
         if (wave < nsel) {
             const int j = wave;
             int m = 0;
@@ -283,7 +261,7 @@ __device__ inline void mv_propose_wave(const Dims &d, const Work &w, const Sampl
                 rsrc[c] = in ? w.St[tgt][rowoff + t] : 0;
                 rdst[c] = in ? w.St[tgt + 1][rowoff + t] : 0;
             }
-            MSTAMP(6);
+            MSTAMP(L, 6);
             // day: the floor(u D)-th day with events
             int D = 0;
             unsigned long long hot[NCH];
@@ -299,7 +277,7 @@ __device__ inline void mv_propose_wave(const Dims &d, const Work &w, const Sampl
                     if (!found) r -= cnt;
                 }
             }
-            MSTAMP(7);
+            MSTAMP(L, 7);
             const int v = rng_index(sm.u[2 * j + 1][0], 2 * s.dmax);
             const int delta = v < s.dmax ? v - s.dmax : v - s.dmax + 1;
             const int t2 = t + delta;
@@ -324,7 +302,7 @@ __device__ inline void mv_propose_wave(const Dims &d, const Work &w, const Sampl
                 }
                 mdec = wave_min_int(mdec);
                 minc = wave_min_int(minc);
-                MSTAMP(8);
+                MSTAMP(L, 8);
                 const int kt = wv_at<NCH>(rk, t), kt2 = wv_at<NCH>(rk, t2);
                 if (lane == 0) {
                     const bool dec_unbounded = !later && tgt == 0;   // S: prev_event_id None -> no bound
@@ -356,7 +334,7 @@ __device__ inline void mv_propose_wave(const Dims &d, const Work &w, const Sampl
                 if (j < nsel) sm.sel[j] = rowj[j];
         }
         lds_barrier();
-        MSTAMP(9);
+        MSTAMP(L, 9);
         if (tid == 0) {
             // compact the in-range updates (order preserved) and combine the correction
             int n = 0;
@@ -387,7 +365,7 @@ __device__ inline void mv_propose_wave(const Dims &d, const Work &w, const Sampl
             const bool is_del = (u_br < 0.5) && Hd > 0;
             msel = is_del ? wv_hot_row(hr, rg, M, rng_index(u_m, Hd), lane) : rng_index(u_m, M);
             if (!rows_only) {
-                MSTAMP(5);
+                MSTAMP(L, 5);
                 const int m = msel;
                 const size_t rowoff = ((size_t)b * d.Mp + m) * d.Tp;
                 int rk[NCH], rsrc[NCH], rdst[NCH];
@@ -401,7 +379,7 @@ __device__ inline void mv_propose_wave(const Dims &d, const Work &w, const Sampl
                 }
                 // the closed end of the series (state after the last day) is part of every window (t, T]
                 const int end_src = comp_start(d, w, rowoff, tgt, T), end_dst = comp_start(d, w, rowoff, tgt + 1, T);
-                MSTAMP(6);
+                MSTAMP(L, 6);
                 // hot days of the row inside the range; the day of a delete is the floor(u Dm)-th of them
                 int Dm = 0;
                 unsigned long long hot[NCH];
@@ -422,7 +400,7 @@ __device__ inline void mv_propose_wave(const Dims &d, const Work &w, const Sampl
                         if (!found) r -= cnt;
                     }
                 }
-                MSTAMP(7);
+                MSTAMP(L, 7);
                 int m0 = 0x7fffffff, m1 = 0x7fffffff;
 #pragma unroll
                 for (int c = 0; c < NCH; ++c) {
@@ -431,7 +409,7 @@ __device__ inline void mv_propose_wave(const Dims &d, const Work &w, const Sampl
                 }
                 m0 = min(wave_min_int(m0), end_src);
                 m1 = min(wave_min_int(m1), end_dst);
-                MSTAMP(8);
+                MSTAMP(L, 8);
                 const int kt = wv_at<NCH>(rk, t);
                 if (lane == 0) {
                     const int min_src = tgt == 0 ? 0x7fffffff : m0, min_dst = m1;
@@ -520,11 +498,8 @@ __device__ __forceinline__ void move_pa2_body(const Dims &d, const Consts &c, co
     // now, in the same round trip as the pending descriptor and the partial sums; what the
     // pending update changes (row totals, range totals) is patched after the decision.
     const bool proposer = bx == 0 && next.kind >= 0;
-#ifdef SEIR_STAMPS
-    double *stamp_hs = ch.hs + (size_t)b * NHS;
-    const bool stamp_on = proposer && b == 0 && next.slot == SEIR_STAMP_SLOT && next.scan == 0;
-#endif
-    MSTAMP(0);
+    const MoveStamp mst = MOVE_STAMP_CTX(proposer && b == 0 && next.slot == SEIR_STAMP_SLOT && next.scan == 0);
+    MSTAMP(mst, 0);
     constexpr int PRE_RT = 4;                                  // rows per thread (M <= 2048)
     const int R = s.tr_hi - s.tr_lo;
     const bool pre_rt = proposer && M <= PRE_RT * MVB;
@@ -561,7 +536,7 @@ __device__ __forceinline__ void move_pa2_body(const Dims &d, const Consts &c, co
             dcn += ch.Dpart[((size_t)b * s.nrb_d + i) * 2 + 1];
         }
         mv_sum2(dth, dcn, sm.dred);
-        MSTAMP(1);
+        MSTAMP(mst, 1);
         if (tid == 0) {
             const double ratio = dth + dcn + pend.logq;
             s_acc = (pend.valid && pend.logu < ratio) ? 1 : 0;   // NaN -> reject
@@ -622,7 +597,7 @@ __device__ __forceinline__ void move_pa2_body(const Dims &d, const Consts &c, co
             lds_barrier();               // LDS only: tid 0's trace stores need not drain before the proposal
         }
     }
-    MSTAMP(2);
+    MSTAMP(mst, 2);
     // nothing in this launch reads the counter after block 0's trace write above
     if (bx == 0 && next.kind == -2 && tid == 0) ch.sweep[b] += 1;
     if (proposer) {
@@ -666,14 +641,12 @@ __device__ __forceinline__ void move_pa2_body(const Dims &d, const Consts &c, co
                 range_totals_to_lds(d, w, s, b, next.tgt, L.rg);
             }
         }
-        MSTAMP(3);
-#ifdef SEIR_STAMPS
-        L.stamp_hs = stamp_hs; L.stamp_on = stamp_on;
-#endif
+        MSTAMP(mst, 3);
+        MOVE_STAMP_PASS(L, mst);
         mv_propose<NCH, MM>(d, w, s, ch, b, next, sm, L, ltab);
-        MSTAMP(10);
+        MSTAMP(mst, 10);
         if (tid == 0) ch.mv[(size_t)(pbuf ^ 1) * s.B + b] = sm.mv;
-        MSTAMP(11);
+        MSTAMP(mst, 11);
     }
 }
 template <int NCH>
@@ -884,12 +857,13 @@ template <bool SOLO, typename TT>
 __device__ __forceinline__ TT ld_band(const TT *p_) { return SOLO ? *p_ : ld_l2(p_); }
 // NRB: rows per wave of a band workgroup -- 2 (16 rows per workgroup: 24 of them per chain at UK-380, one chain per XCD) or 4 (32
 // rows: 12 per chain, so that (3 + 12) x 16 workgroups -- sixteen chains, two per XCD -- still hold one CU each)
+#ifndef PAIR_BAND_BACKOFF
+#define PAIR_BAND_BACKOFF 0            // x 64 cycles a band workgroup sleeps before it first looks for role 0's token
+#endif
 template <bool SOLO, int NRB, int MM>
 __device__ __forceinline__ void pair_band_block(const Dims &d, const Consts &c, const Work &w, const SamplerCfg &s,
                                                 const Chains &ch, int b, int bx, int nband, unsigned token, bool has_r1,
-                                                bool has_r2, int buf, int st_slot = 0, int st_step = 0) {
-    const int b_stamp = b - d.b0;
-    (void)b_stamp;
+                                                bool has_r2, int buf, PairStamp qst = PairStamp{}) {
     __shared__ Move mvA, mvB, fp;
     __shared__ int mv_sel;
     __shared__ double sh_th[MVW], sh_cn[MVW];
@@ -904,14 +878,11 @@ __device__ __forceinline__ void pair_band_block(const Dims &d, const Consts &c, 
     const int r_lo = bx * rpb, r_hi = min(d.M, r_lo + rpb);
     // ---- the update accepted in this launch (token 4, early in the authoritative role): its descriptor, and what its F
     // band needs for this workgroup's rows -- coefficients and the F values themselves (nobody writes F but this code)
-#ifndef PAIR_BAND_BACKOFF
-#define PAIR_BAND_BACKOFF 0
-#endif
     if (tid == 0) {
         if (PAIR_BAND_BACKOFF > 0) __builtin_amdgcn_s_sleep(PAIR_BAND_BACKOFF);   // (role 0 decides the pending update ~3.5 us into a step)
         wait_token(done + 4, token, ch.late + ch.late_fatal + b);
     }
-    QSTAMP(st_slot, st_step, 1);
+    QSTAMP(qst, 1);
     __syncthreads();
     move_copy_l2(&fp, ch.fpend + b, 128);
     __syncthreads();
@@ -945,10 +916,10 @@ __device__ __forceinline__ void pair_band_block(const Dims &d, const Consts &c, 
         // the speculative role publishes its descriptor as hand-off words well before it is done (token 1): wave 1 looks for
         // them while thread 0 waits for the planes
         if (wave == 1) move_wait_ll<MOVE_DW>(reinterpret_cast<int *>(&mvA), ch.llmv + ((size_t)buf * s.B + b) * 32, lane, token, ch.late + ch.late_fatal + b);
-        QSTAMP(st_slot, st_step, 2);
+        QSTAMP(qst, 2);
         __syncthreads();
     } else {
-        QSTAMP(st_slot, st_step, 2);
+        QSTAMP(qst, 2);
         __syncthreads();
         move_copy_l2(&mvA, ch.mv + (size_t)buf * s.B + b, 0);
         __syncthreads();
@@ -1015,7 +986,7 @@ __device__ __forceinline__ void pair_band_block(const Dims &d, const Consts &c, 
         return dth;
     };
     double dth = evaluate(mvA);
-    QSTAMP(st_slot, st_step, 3);
+    QSTAMP(qst, 3);
     if (tid == 0) mv_sel = (int)wait_token_flag(done + 0, token, ch.late + ch.late_fatal + b);   // (Chains::mvsel rides on the token)
     __syncthreads();
     if (mv_sel) {                                          // uniform, rare
@@ -1038,13 +1009,13 @@ __device__ __forceinline__ void pair_band_block(const Dims &d, const Consts &c, 
             out[0] = dsum;
             out[1] = 0.0;
         }
-        QSTAMP(st_slot, st_step, 4);
+        QSTAMP(qst, 4);
         // the F band: once nobody reads F any more
         if (has_fp) {
             if (has_r1) wait_token(done + 1, token, ch.late + ch.late_fatal + b);
             if (has_r2) wait_token(done + 2, token, ch.late + ch.late_fatal + b);
         }
-        QSTAMP(st_slot, st_step, 5);
+        QSTAMP(qst, 5);
     }
     auto publish = [&]() {
         if (!SOLO) return;
@@ -1054,7 +1025,7 @@ __device__ __forceinline__ void pair_band_block(const Dims &d, const Consts &c, 
         if (tid == 0) {
             uint4 *out = ch.llD + (((size_t)buf * s.B + b) * nband + bx) * 2;
             pair_sums_store(out, dsum, 0.0, token);
-            QSTAMP(st_slot, st_step, 10);
+            QSTAMP(qst, 10);
         }
     };
     if (!has_fp) { publish(); return; }
@@ -1186,9 +1157,8 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid));
     asm volatile("" : "+s"(b));
-    const int b_stamp = b - d.b0;
-    (void)b_stamp;
-    QSTAMP(slot, lidx, 0);
+    const PairStamp qst = PAIR_STAMP_CTX(b - d.b0, slot, lidx);   // developer timelines (stamps.h: PAIR; SEIR below)
+    QSTAMP(qst, 0);
     if (slot >= nroles) {                                  // band workgroups (the highest block ids)
         if (nband == 0) return;
         if (fin) {                                         // the closing step of k_move_pairs: they finish the sweep
@@ -1198,9 +1168,9 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
         const unsigned tok = pair_token(ch.sweep[b], lidx);
         const bool r1 = next.kind >= 0 && nroles >= 2, r2 = se_next.kind >= 0 && nroles == 3;
         if ((d.M + nband - 1) / nband > 2 * MVW)              // (uniform) more than 16 rows per band workgroup: four per wave
-            pair_band_block<SOLO, 4, MM>(d, c, w, s, ch, b, slot - nroles, nband, tok, r1, r2, pbuf ^ 1, slot, lidx);
+            pair_band_block<SOLO, 4, MM>(d, c, w, s, ch, b, slot - nroles, nband, tok, r1, r2, pbuf ^ 1, qst);
         else
-            pair_band_block<SOLO, 2, MM>(d, c, w, s, ch, b, slot - nroles, nband, tok, r1, r2, pbuf ^ 1, slot, lidx);
+            pair_band_block<SOLO, 2, MM>(d, c, w, s, ch, b, slot - nroles, nband, tok, r1, r2, pbuf ^ 1, qst);
         return;
     }
     const int role = slot == nroles - 1 ? 0 : slot + 1;
@@ -1208,28 +1178,9 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
     const bool do_se = role == 0 && se.kind >= 0, do_nx = next.kind >= 0, do_pre = se_next.kind >= 0 && nroles == 3;
     if (role == 1 && !do_nx) return;
     if (role == 2 && !do_pre) return;
-#ifdef SEIR_STAMPS
-    double *stamp_hs = ch.hs + (size_t)b * NHS;
-    const bool stamp_on = do_se && b == 0 && se.slot == (SEIR_STAMP_SLOT & 2) && se.scan == 0;
-#define PSTAMP(i) do { if (threadIdx.x == 0 && stamp_on) ((unsigned long long *)(stamp_hs + 16))[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#ifndef SEIR_STAMP_ROLE
-#define SEIR_STAMP_ROLE 1
-#endif
-    // a speculative role's phases (slots 8..11): role SEIR_STAMP_ROLE of chain 0 in the launch whose S->E slot matches
-    const bool rstamp_on = role == SEIR_STAMP_ROLE && b == 0 && se.slot == (SEIR_STAMP_SLOT & 2) && se.scan == 0;
-#ifdef SEIR_STAMP_PROPOSE      // phases inside the speculative role's mv_propose (slots 4..9); its own phases move to 12..15
-#define RSTAMP(i) do { if (threadIdx.x == 0 && rstamp_on) ((unsigned long long *)(stamp_hs + 16))[(i) + 4] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#undef PSTAMP
-#define PSTAMP(i) do {} while (0)
-#else
-#define RSTAMP(i) do { if (threadIdx.x == 0 && rstamp_on) ((unsigned long long *)(stamp_hs + 16))[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#endif
-#else
-#define PSTAMP(i) do {} while (0)
-#define RSTAMP(i) do {} while (0)
-#endif
-    PSTAMP(0);
-    RSTAMP(8);
+    const MoveStamp pst = PAIR_ROLE0_STAMPS(do_se, b, se), rst = PAIR_SPEC_STAMPS(role, b, se);
+    MSTAMP(pst, 0);
+    MSTAMP(rst, stamps::SW_ROLE + 0);
     // ---- entry: everything that does not depend on a decision made in this launch
     const bool pre_ok = M <= PRE_RT * MVB;
     const MoveSpec &mine = role == 2 ? se_next : next;          // the proposal a speculative role draws
@@ -1276,9 +1227,7 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
             double th, cn;
             pair_sums_wait(src, pair_token(ch.sweep[b], lprev), ch.late + ch.late_fatal + b, th, cn);
             if (i0 < s.nrb_d) { dth0 = th; dcn0 = cn; }
-#ifdef PAIR_STAMPS
-            if (tid == DW0 && b_stamp == 0 && lidx < 12) ch.leap_st[((size_t)slot * 12 + lidx) * 16 + 7] = __builtin_amdgcn_s_memrealtime();
-#endif
+            QSTAMP_T(qst, tid == DW0, 7);
         }
     }
     const bool pre_avail = do_se && have_pre;
@@ -1298,10 +1247,10 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
         tr_slot = SOLO ? tslot : chain_trace_slot(s, ch, ch.sweep[b]);
     }
     psi = w.scal[(size_t)b * NSCAL + SC_PSI];
-    QSTAMP(slot, lidx, 6);
+    QSTAMP(qst, 6);
     if (do_se && !pre_avail) mv_draw<MM>(s, ch, b, se, sm_se, T);
     if (role != 0 || do_nx) mv_draw<MM>(s, ch, b, mine, sm_nx, T);
-    QSTAMP(slot, lidx, 14);
+    QSTAMP(qst, 14);
     if (have_prev) {
         if (tid >= 64 && tid < 64 + MOVE_DW) reinterpret_cast<int *>(&pendA)[tid - 64] = ld_i;
         if (tid >= 128 && tid < 128 + MOVE_DW) reinterpret_cast<int *>(&pendB)[tid - 128] = ld_i;
@@ -1321,9 +1270,9 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
     if (role != 0) {
         // the totals are in registers: tell role 0 it may start writing
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        QSTAMP(slot, lidx, 12);
+        QSTAMP(qst, 12);
         __syncthreads();
-        QSTAMP(slot, lidx, 13);
+        QSTAMP(qst, 13);
         // test hooks (seir_sampler_desc::debug_pair): 1 = role 1 posts its token late, 2 = never; 4 / 8: role 2
         const int late_bit = role == 1 ? 1 : 4, absent_bit = role == 1 ? 2 : 8;
         if (dbg & late_bit)
@@ -1340,7 +1289,7 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
     const Move *pendp = nullptr;
     if (have_prev) {
         __syncthreads();                                   // the descriptors fetched at entry are in LDS
-        QSTAMP(slot, lidx, 15);
+        QSTAMP(qst, 15);
         const Move &pend = s_sel ? pendB : pendA;          // speculative one, or re-drawn after a row conflict
         pendp = &pend;
         if (s.nrb_d <= WAVE) {
@@ -1359,15 +1308,13 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
         // ------------------------------------------------------------ speculative proposal (role 1: E->I-type
         // of this pair, role 2: S->E-type of the next pair)
         const Move *fix = (pend_acc && pendp->tgt == mine.tgt) ? pendp : nullptr;
-        RSTAMP(9);
-#if defined(SEIR_STAMPS) && defined(SEIR_STAMP_PROPOSE)
-        L.stamp_hs = stamp_hs; L.stamp_on = rstamp_on;
-#endif
-        QSTAMP(slot, lidx, 1);
+        MSTAMP(rst, stamps::SW_ROLE + 1);
+        MOVE_STAMP_PASS_INSIDE(L, rst);
+        QSTAMP(qst, 1);
         mv_rows_to_lds(d, w, s, b, mine, pre_ok, pre_nx, fix, L, rtl);
         mv_propose<NCH, MM>(d, w, s, ch, b, mine, sm_nx, L, ltab);
-        QSTAMP(slot, lidx, 2);
-        RSTAMP(10);
+        QSTAMP(qst, 2);
+        MSTAMP(rst, stamps::SW_ROLE + 2);
         Move *out = (role == 1 ? ch.mv : ch.mvs) + (size_t)(pbuf ^ 1) * s.B + b;
         move_copy(out, &sm_nx.mv, MVB - WAVE);             // by the last wave: nobody's loads queue behind the store
         // band workgroups start from this descriptor while the log-ratio over the updated rows is still being evaluated: as
@@ -1383,8 +1330,8 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
         // (role 1 draws E->I-type proposals, role 2 S->E-type ones)
         if (role == 1) mv_own_rows_to_down<MM, 1>(d, c, w, b, sm_nx.mv, psi, ltab, fpp, sm_nx.dred, od);
         else mv_own_rows_to_down<MM, 0>(d, c, w, b, sm_nx.mv, psi, ltab, fpp, sm_nx.dred, od);
-        QSTAMP(slot, lidx, 3);
-        RSTAMP(11);
+        QSTAMP(qst, 3);
+        MSTAMP(rst, stamps::SW_ROLE + 3);
         if (nband > 0) {                                   // band workgroups: this role reads F no more, its output is in L2
             __syncthreads();
             if (tid == 0)
@@ -1441,8 +1388,8 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
         }
         lds_barrier();
     }
-    PSTAMP(1);
-    QSTAMP(slot, lidx, 1);
+    MSTAMP(pst, 1);
+    QSTAMP(qst, 1);
     if (fin && nband > 0) {
         // closing step of k_move_pairs: the band workgroups finish the sweep (pair_band_finish) once the planes are final
         __syncthreads();                                   // mv_apply_rows ends drained; the trace stores need not be
@@ -1479,16 +1426,16 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
             }
             // the pending update was of the other plane (tgt 1): nothing to correct in plane 0's totals
             mv_rows_to_lds(d, w, s, b, se, pre_ok, pre_se, nullptr, L, rtl);
-            PSTAMP(2);
+            MSTAMP(pst, 2);
             mv_propose<NCH, MM>(d, w, s, ch, b, se, sm_se, L, ltab);
-            PSTAMP(3);
+            MSTAMP(pst, 3);
         }
         const Move &mv = sm_se.mv;
         if (use_pre && fpp == nullptr) {
             dth = pre_down[0]; dcn = pre_down[1];           // F under the proposal's rows is what role 2 saw
         } else {
             if (mv.valid && mv.n > 0) own_rows_delta<MVB, MM, 0>(d, c, w, b, mv, psi, 0, M, ltab, dth, dcn, fpp);
-            PSTAMP(4);
+            MSTAMP(pst, 4);
             mv_sum2(dth, dcn, sm_se.dred);
         }
         if (tid == 0) {
@@ -1512,8 +1459,8 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
         // band workgroups: the planes are final (token 5); which descriptor stands they learn from the last token
         if (nband > 0 && tid == 0)
             st_l2(ch.done + (size_t)b * 2 * TAIL_STRIDE + 5, token);
-        PSTAMP(5);
-        QSTAMP(slot, lidx, 2);
+        MSTAMP(pst, 5);
+        QSTAMP(qst, 2);
     }
     // ---- (3) certify role 1's proposal; closing launch: advance the sweep counter
     if (next.kind == -2 && tid == 0) ch.sweep[b] += 1;
@@ -1524,7 +1471,7 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
             // plane 1 totals were prefetched before (1): correct them if the pending (plane 1) update was accepted
             const Move *fix = (pend_acc && pendp->tgt == next.tgt) ? pendp : nullptr;
             mv_rows_to_lds(d, w, s, b, next, pre_ok, pre_nx, fix, L, rtl);
-            PSTAMP(6);
+            MSTAMP(pst, 6);
             mv_propose<NCH, MM>(d, w, s, ch, b, next, sm_nx, L, ltab, /*rows_only=*/true);
         }
         if (tid == 0) {
@@ -1548,8 +1495,8 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
             mv_own_rows_to_down<MM, 1>(d, c, w, b, sm_nx.mv, psi, ltab, fpp, sm_nx.dred,
                                 ch.Down + (((size_t)(pbuf ^ 1) * 2 + 1) * s.B + b) * 2);
         }
-        PSTAMP(7);
-        QSTAMP(slot, lidx, 3);
+        MSTAMP(pst, 7);
+        QSTAMP(qst, 3);
     }
     // ---- (4) the note for the next launch about the proposal role 2 is pre-drawing
     if (do_pre && tid == 0) {
@@ -1593,9 +1540,7 @@ __device__ __forceinline__ void move_pair_body(const Dims &d, const Consts &c, c
     const int b = d.b0 + (int)blockIdx.x - slot * nbk;
     if (d.nlive > 0 && (int)blockIdx.x - slot * nbk >= d.nlive) return;             // a chain of the layout that does not exist
     pair_step<NCH, false, MM>(d, c, w, s, ch, se, next, se_next, have_prev, have_pre, pbuf, lidx, dbg, nband, nroles, slot, b);
-    const int b_stamp = b - d.b0;
-    (void)b_stamp;
-    QSTAMP(slot, lidx, 8);
+    QSTAMP(PAIR_STAMP_CTX(b - d.b0, slot, lidx), 8);
 }
 // the instances: m <= MM_SMALL under the plain name, every m <= MMAX as _m4 (the host's move_pair_fn picks)
 template <int NCH>
@@ -1633,11 +1578,13 @@ constexpr int PBAR_STRIDE = 64;                               // 32-bit words pe
 // `target`: what the chain's counter shows once every role of the chain has finished the step -- the counter runs on
 // over the launches (the host knows how many steps have been counted: seir_sampler::pbar_count), so the last one in
 // has nothing to reset or to raise, and the others poll the counter itself
-__device__ __forceinline__ void pair_chain_barrier(const Chains &ch, int b, unsigned target, int b_stamp = 0, int st_slot = 0,
-                                                   int st_step = 0) {
+#ifndef PBAR_SLEEP
+#define PBAR_SLEEP 1                                          // x 64 cycles between two looks at the counter
+#endif
+__device__ __forceinline__ void pair_chain_barrier(const Chains &ch, int b, unsigned target, PairStamp qst = PairStamp{}) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wave's stores of the step are in L2
     __syncthreads();
-    QSTAMP(st_slot, st_step, 10);
+    QSTAMP(qst, 10);
     if (threadIdx.x == 0) {
         unsigned *cnt = ch.pbar + (size_t)b * PBAR_STRIDE;
         const unsigned old = add_l2(cnt, 1u);
@@ -1653,14 +1600,11 @@ __device__ __forceinline__ void pair_chain_barrier(const Chains &ch, int b, unsi
         // (Issued AHEAD of the arrival instead, so that the last workgroup in has the two round trips side by side: slower,
         // 0.3063 against 0.3029 ms per sweep -- the atomic queues behind the invalidate.)
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#ifndef PBAR_SLEEP
-#define PBAR_SLEEP 1
-#endif
         if (old + 1u != target)
             hs_wait<PBAR_SLEEP, HS_CHECK, HS_LIMIT, HS_CALLER>([&] { return (int)(ld_l2(cnt) - target) >= 0; }, ch.late + ch.late_fatal + b);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    QSTAMP(st_slot, st_step, 11);
+    QSTAMP(qst, 11);
     __syncthreads();
 }
 
@@ -1721,12 +1665,11 @@ __device__ __forceinline__ void move_pairs_body(const Dims &d, const Consts &c, 
                        closing ? 62 : pair, closing ? 0 : dbg, (closing && !fin) ? 0 : nband, nroles, slot, b, closing ? fin : 0, sweep0,
                        pair - 1, tslot);
         if (closing) break;
-        const int b_stamp = b - d.b0;
-        (void)b_stamp;
-        QSTAMP(slot, pair, 8);
-        if (slot < nroles) pair_chain_barrier(ch, b, pbase + (unsigned)((pair + 1) * nroles), b_stamp, slot, pair);
+        const PairStamp qst = PAIR_STAMP_CTX(b - d.b0, slot, pair);
+        QSTAMP(qst, 8);
+        if (slot < nroles) pair_chain_barrier(ch, b, pbase + (unsigned)((pair + 1) * nroles), qst);
         else pair_band_next_step();
-        QSTAMP(slot, pair, 9);
+        QSTAMP(qst, 9);
     }
 }
 template <int NCH>

@@ -119,7 +119,7 @@ struct Chains {
     double *k0part;                                      // [B][ROLE_SLOTS] k_leap with the trajectory's first step folded in: the roles' parts of
                                                          //         the start point's kinetic energy
     double *irl0;                                        // [B] ... and the I->R term of its log-probability
-    unsigned long long *leap_st;                         // [B][16][8] developer timeline of k_leap (LEAP_STAMPS builds only)
+    unsigned long long *stamps;                          // [stamps::buffer_words(B)] developer timelines (stamps.h: the stamped builds only)
     // k_leap's hand-offs as self-validating words (below: "Hand-off words"): what a tile leaves for the roles, per step parity
     uint4 *llK;                                          // [B][2][Mp/16][Tp]   column sums (Work::Kpart)
     uint4 *llR;                                          // [B][2][ntc][Mp]     row sums (Work::Rpart)
@@ -214,16 +214,7 @@ constexpr int HB = 512;             // threads (8 waves: leaves 256 VGPRs per la
 constexpr int HWV = HB / WAVE;      // waves
 // HT / HM (template parameters): days / rows per thread, ceil(Tp/HB) in {1,2}, ceil(M/HB) in {1,2,4}
 constexpr int NRED = 8;
-#ifdef SEIR_STAMPS
-#ifndef SEIR_STAMP_STAGE
-#define SEIR_STAMP_STAGE 2
-#endif
-#define STAMP(i) do { if (threadIdx.x == 0 && blockIdx.x == 0 && STAGE == SEIR_STAMP_STAGE) ((unsigned long long *)(hs + 16))[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define STAMP_DRAIN(i) do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); STAMP(i); } while (0)
-#else
-#define STAMP(i) do {} while (0)
-#define STAMP_DRAIN(i) do {} while (0)
-#endif
+// (STAMP / STAMP_DRAIN in k_hmc_step: developer timeline, stamps.h: SEIR)
 
 // standard normal for component i of the momentum (Box-Muller; components 2j, 2j+1 share a Philox call)
 __device__ SEIR_COLD double momentum_normal(RngKey key, int i) {
@@ -1047,13 +1038,8 @@ __device__ __forceinline__ void role_gather(const Dims &d, const Chains &ch, con
 template <int NTC, bool COH, bool PERS = false, bool TRAJ = PERS, typename Wait>
 __device__ __forceinline__ void hmc_chunk_role(const Dims &d, const Consts &c, const Work &w, const SamplerCfg &s,
                                                const Chains &ch, int par, int bx, int b, Wait wait, int lane_in = -1,
-                                               unsigned long long *probe = nullptr, double *gbuf = nullptr, int traj = 0,
+                                               RoleStamp probe = RoleStamp{nullptr}, double *gbuf = nullptr, int traj = 0,
                                                double eps_in = 0.0, bool tab_ready = false, const LeapLL &ll = LeapLL{}) {
-#ifdef LEAP_STAMPS
-#define CPROBE(k) do { asm volatile("s_nop 0" ::: "memory"); if (probe && threadIdx.x == 0) probe[(k) < 8 ? (k) : 2 * 128 + (k) - 8] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define CPROBE(k) do {} while (0)
-#endif
     __shared__ double2 ltab[LOGTAB_N];
     auto LDP = [](const double *p_) {
         return COH ? ld_l2(p_) : *p_;
@@ -1131,7 +1117,7 @@ __device__ __forceinline__ void hmc_chunk_role(const Dims &d, const Consts &c, c
         // The I->R part of the step needs nothing of this step's tiles -- gamma0 and gamma1 move by the chunk parts the
         // previous step left (Work::CG) -- so all of it (two wave sums, the new rates, the series, two more wave sums: half of
         // the role's dependent operations) runs BEFORE the wait, under the tile phase.  Same operations, same results.
-        CPROBE(10);                                         // entry loads issued
+        CPROBE(probe, 10);                                         // entry loads issued
         if (PERS) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the workgroup's other waves are alive there: no s_barrier)
         else lds_barrier();                                // ltab (single wave: orders the LDS writes)
         if (first) {
@@ -1181,8 +1167,8 @@ __device__ __forceinline__ void hmc_chunk_role(const Dims &d, const Consts &c, c
             }
         }
         const double gg0 = wave_sum(cg0_l), gg1 = wave_sum(cg1_l);
-        if (probe) { asm volatile("" :: "v"(gg0), "v"(gg1)); }
-        CPROBE(11);                                         // entry loads back, two wave sums
+        CPROBE_HOLD(probe, "v"(gg0), "v"(gg1));
+        CPROBE(probe, 11);                                         // entry loads back, two wave sums
         const double pg0n = pg0 + kick * (gg0 - g0 / 1.0e4), g0n = g0 + eps * vg0 * pg0n;
         const double pg1n = pg1 + kick * (gg1 - g1 / 1.0e4), g1n = g1 + eps * vg1 * pg1n;
         double ng0p = 0.0, ng1p = 0.0, rnew = 0.0;
@@ -1196,7 +1182,7 @@ __device__ __forceinline__ void hmc_chunk_role(const Dims &d, const Consts &c, c
             ng1p = grr * rnew * wd_t;
         }
         const double ng0s = wave_sum(ng0p), ng1s = wave_sum(ng1p);
-        if (probe) { asm volatile("" :: "v"(ng0s), "v"(ng1s)); }
+        CPROBE_HOLD(probe, "v"(ng0s), "v"(ng1s));
         double irl_fin = 0.0;
         if (fin) {
             // the I->R term itself at the end point's rates (the accept test's log-probability), this chunk's days
@@ -1209,7 +1195,7 @@ __device__ __forceinline__ void hmc_chunk_role(const Dims &d, const Consts &c, c
             }
             irl_fin = wave_sum(xl);
         }
-        CPROBE(12);                                         // I->R part done
+        CPROBE(probe, 12);                                         // I->R part done
         wait();
         // ---- from here on: this step's partial sums
         double col = 0.0;
@@ -1222,8 +1208,8 @@ __device__ __forceinline__ void hmc_chunk_role(const Dims &d, const Consts &c, c
             col = (gbuf[G::C + lane] + gbuf[G::C + WAVE + lane]) + (gbuf[G::C + 2 * WAVE + lane] + gbuf[G::C + 3 * WAVE + lane]);
 #pragma unroll
             for (int cc = 0; cc < NC; ++cc) { bs[cc] = gbuf[G::BS + cc * WAVE + lane]; as[cc] = gbuf[G::AS + cc * WAVE + lane]; }
-            if (probe) { asm volatile("" :: "v"(col)); }
-            CPROBE(8);                                          // column sums in
+            CPROBE_HOLD(probe, "v"(col));
+            CPROBE(probe, 8);                                          // column sums in
         } else {
         // column sums of this chunk
         {
@@ -1244,8 +1230,8 @@ __device__ __forceinline__ void hmc_chunk_role(const Dims &d, const Consts &c, c
             }
             col = (c0 + c1) + (c2 + c3);
         }
-        if (probe) { asm volatile("" :: "v"(col)); }
-        CPROBE(8);                                          // column sums in
+        CPROBE_HOLD(probe, "v"(col));
+        CPROBE(probe, 8);                                          // column sums in
         // tile scalars of row tile `lane` (and lane+64, ... when there are more)
 #pragma unroll
         for (int cc = 0; cc < NC; ++cc) {
@@ -1285,11 +1271,11 @@ __device__ __forceinline__ void hmc_chunk_role(const Dims &d, const Consts &c, c
             lat += bs[cc];
         }
         p_pre = eps * kick * p_pre + (lane < ci ? cta_l + eps * (ctvp_l - kick * PREC * ctva_l) : 0.0);
-        if (probe) { asm volatile("" :: "v"(col), "v"(p_pre)); }
-        CPROBE(5);                                          // loads back
+        CPROBE_HOLD(probe, "v"(col), "v"(p_pre));
+        CPROBE(probe, 5);                                          // loads back
         const double later = wave_sum(p_later), allB = wave_sum(p_all), pre = wave_sum(p_pre);
-        if (probe) { asm volatile("" :: "v"(later), "v"(allB), "v"(pre)); }
-        CPROBE(6);                                          // three wave sums
+        CPROBE_HOLD(probe, "v"(later), "v"(allB), "v"(pre));
+        CPROBE(probe, 6);                                          // three wave sums
         // this chunk's entries
         const double insuf = wave_incl_suffix_scan(col, lane);
         const double g = own ? (insuf + later) - alpha * PREC : 0.0;
@@ -1313,8 +1299,8 @@ __device__ __forceinline__ void hmc_chunk_role(const Dims &d, const Consts &c, c
             if (lane == 0) ch.k0part[(size_t)b * ROLE_SLOTS + bx] = kin;
         }
         const double a_new = a0n + pre + wave_incl_scan(an, lane);
-        if (probe) { asm volatile("" :: "v"(a_new)); }
-        CPROBE(7);                                          // two scans
+        CPROBE_HOLD(probe, "v"(a_new));
+        CPROBE(probe, 7);                                          // two scans
         // (the chunk sums for the next step before the exponential: independent of it, so the two chains overlap)
         const double ca = wave_sum(an), cvp = wave_sum(v * pn), cva = wave_sum(v * an);
         if (own) { q[oT + t] = an; p[oT + t] = pn; }
@@ -1371,7 +1357,7 @@ __device__ __forceinline__ void hmc_chunk_role(const Dims &d, const Consts &c, c
             u0 = LDQ(gr + 0); u1 = LDQ(gr + 1); beta = LDQ(gr + 2); p0 = LDQ(gr + 6); p1 = LDQ(gr + 7); p2 = LDQ(gr + 8);
             psi = LDQ(gr + 12); sig = LDQ(gr + 13); s0 = LDQ(gr + 14); s1 = LDQ(gr + 15);
         }
-        CPROBE(5);                                          // M-chunk: entry loads issued
+        CPROBE(probe, 5);                                          // M-chunk: entry loads issued
         double Qs = 0.0;                                   // (Q s)_m at the current position
         const bool qs_lds = PERS && role_qs_by_helper(c);  // (k_leap: by a helper wave of the role's workgroup, through LDS)
         if (own && !qs_lds) {
@@ -1396,8 +1382,8 @@ __device__ __forceinline__ void hmc_chunk_role(const Dims &d, const Consts &c, c
                 for (int e = c.Qrow[m]; e < c.Qrow[m + 1]; ++e) Qs += c.Qval[e] * LDQ(spr + c.Qcol[e]);
             }
         }
-        if (probe) { asm volatile("" :: "v"(Qs)); }
-        CPROBE(6);                                          // M-chunk: (Q s) formed
+        CPROBE_HOLD(probe, "v"(Qs));
+        CPROBE(probe, 6);                                          // M-chunk: (Q s) formed
         const bool rows_here = d.chunked == 1;             // small M: sum_m l_m R_m, sum_m s_m R_m from the row partials
         constexpr int RPL = 8;                             // Mp <= 512: rows lane, lane+64, ...
         // (k_leap: the rows' l_m and s_m -- the previous step's -- before the wait; what waits for the tiles comes from the
@@ -1414,7 +1400,7 @@ __device__ __forceinline__ void hmc_chunk_role(const Dims &d, const Consts &c, c
                 sxp[kk] = 0.0;                              // (from the helper waves, through LDS: role_pregather)
             }
         }
-        CPROBE(7);                                          // M-chunk: at the wait
+        CPROBE(probe, 7);                                          // M-chunk: at the wait
         wait();
         // ---- from here on: this step's partial sums
         double R = 0.0;
@@ -1493,11 +1479,11 @@ __device__ __forceinline__ void hmc_chunk_role(const Dims &d, const Consts &c, c
             }
         }
         }
-        if (probe) { asm volatile("" :: "v"(ps), "v"(rl), "v"(rs), "v"(R)); }
-        CPROBE(8);                                          // M-chunk: the partial sums are in
+        CPROBE_HOLD(probe, "v"(ps), "v"(rl), "v"(rs), "v"(R));
+        CPROBE(probe, 8);                                          // M-chunk: the partial sums are in
         ps = wave_sum(ps); rl = wave_sum(rl); rs = wave_sum(rs);
-        if (probe) { asm volatile("" :: "v"(ps), "v"(rl), "v"(rs)); }
-        CPROBE(10);                                         // M-chunk: three wave sums
+        CPROBE_HOLD(probe, "v"(ps), "v"(rl), "v"(rs));
+        CPROBE(probe, 10);                                         // M-chunk: three wave sums
         const double g = own ? sig * R - Qs : 0.0;
         const double pn = pm + kick * g;
         const double sn = sm + eps * v * pn;
@@ -1526,8 +1512,8 @@ __device__ __forceinline__ void hmc_chunk_role(const Dims &d, const Consts &c, c
         const double spx = softplus_sigmoid_tab(ux, ltab, sgx);
         const double psin = lane_value(spx, 0) + e0, sign = lane_value(spx, 1) + e0;
         const double s0n = lane_value(sgx, 0), s1n = lane_value(sgx, 1);
-        if (probe) { asm volatile("" :: "v"(psin), "v"(sign), "v"(s0n), "v"(s1n)); }
-        CPROBE(11);                                         // M-chunk: softplus and sigmoid of the new psi, sigma
+        CPROBE_HOLD(probe, "v"(psin), "v"(sign), "v"(s0n), "v"(s1n));
+        CPROBE(probe, 11);                                         // M-chunk: softplus and sigmoid of the new psi, sigma
         if (own) {
             const double eb_new = exp(betan * lm + sign * sn) * inN;
             q[oM + m] = sn; p[oM + m] = pn;
@@ -1738,6 +1724,9 @@ constexpr int TAIL_FLAG_STRIDE = 528;
 // (No waves-per-SIMD bound here: stating the occupancy the compiler arrives at by itself -- three waves for the 12-chunk
 // instances, 158 VGPRs either way -- made k_se_chunk<2,12> 16 % slower at SYN-2048, 1 518 against 1 317 us per trajectory: the
 // scheduler clusters the tile's loads differently once it is given a target.  Four waves (128 VGPRs, 132 B of scratch): 1 477.)
+#ifndef SE_CHUNK_ROLE_PRIO
+#define SE_CHUNK_ROLE_PRIO 3                 // a role's priority: ahead of the tile waves it shares its SIMD with (in k_se_chunk)
+#endif
 template <int TSM, int NTC>
 __global__ __launch_bounds__(256)
 void k_se_chunk(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, int par, unsigned long long target, int traj) {
@@ -1746,15 +1735,7 @@ void k_se_chunk(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, int par, unsi
         int bz, tile;
         xcd_affine(blockIdx.x, ntile, d.aff_nb, bz, tile);
         if (d.nlive > 0 && bz >= d.nlive) return;      // a chain of the layout that does not exist
-#ifdef TAIL_STAMPS
-        // developer timeline (tools/dev/tail_timeline.py), in the unused words 8..15 of the chain's own counter line (the
-        // counter is word 0: the stamps disturb the hand-off they time -- good for its shape, not for its duration):
-        // 8 first tile start, 9 last tile arrival,
-        // 10 first role past its wait, 11 last role past its wait, 12 last role done, 13 first role start -- of the launches
-        // with par = 1 since the last reset (the probe runs trajectories of three leapfrog steps: exactly one such launch)
-        unsigned long long *stp = ch.tail + (size_t)(d.b0 + bz) * TAIL_STRIDE + 8;
-        if (threadIdx.x == 0 && par == 1) min_l2(stp + 0, __builtin_amdgcn_s_memrealtime());
-#endif
+        TSTAMP_MIN(d.b0 + bz, 0);                      // developer timeline (stamps.h: TAIL)
         se_tile<true, 1, TSM>(d, c, w, tile % d.ntc, tile / d.ntc, bz);
         __syncthreads();                               // vmcnt(0): this tile's partial sums are in the XCD's L2
         if (threadIdx.x == 0) {
@@ -1764,25 +1745,17 @@ void k_se_chunk(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, int par, unsi
             if (old + 1 == target)
                 st_l2(ch.tail + TAIL_FLAG_AT(s.B, d.b0 + bz), target);
         }
-#ifdef TAIL_STAMPS
-        if (threadIdx.x == 0 && par == 1) max_l2(stp + 1, __builtin_amdgcn_s_memrealtime());
-#endif
+        TSTAMP_MAX(d.b0 + bz, 1);
         return;
     }
     if (threadIdx.x >= WAVE) return;                   // a role is one wave
-#ifndef SE_CHUNK_ROLE_PRIO
-#define SE_CHUNK_ROLE_PRIO 3
-#endif
     // ... of serial code, on SIMDs it shares with the tile waves of chains that are still at their cells: ahead of them (as k_leap's)
     __builtin_amdgcn_s_setprio(SE_CHUNK_ROLE_PRIO);
     const int L = (int)blockIdx.x - n_tiles;
     const int bz = L % d.aff_nb, role = L / d.aff_nb, b = d.b0 + bz;
     if (d.nlive > 0 && bz >= d.nlive) return;
     const unsigned long long *flag = ch.tail + TAIL_FLAG_AT(s.B, b);   // raised by the chain's last tile
-#ifdef TAIL_STAMPS
-    unsigned long long *stp = ch.tail + (size_t)b * TAIL_STRIDE + 8;
-    if (threadIdx.x == 0 && par == 1) min_l2(stp + 5, __builtin_amdgcn_s_memrealtime());
-#endif
+    TSTAMP_MIN(b, 5);
     // traj (hmc_mode 6: the whole trajectory as L + 1 of these launches): 1 = the trajectory's first step (the momentum is
     // drawn here, the start point read from Chains::q0: k_hmc_step<0>'s work in chunk form), 2 = the step after it, 3 = the last
     // half kick (the accept test follows in k_hmc_final); 0 = an inner step, the only kind the other forms launch
@@ -1794,18 +1767,9 @@ void k_se_chunk(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, int par, unsi
         // launch takes 11.0 us and the sleep is worth little.)
         if (ntile >= 32) __builtin_amdgcn_s_sleep(TAIL_BACKOFF);
         hs_wait<1, HS_CHECK, HS_LIMIT, HS_THREAD0>([&] { return ld_l2(flag) >= target; }, ch.late + ch.late_fatal + b);
-#ifdef TAIL_STAMPS
-        if (threadIdx.x == 0 && par == 1) {
-            const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-            min_l2(stp + 2, now);
-            max_l2(stp + 3, now);
-        }
-#endif
-    }, -1, nullptr, nullptr, traj);
-#ifdef TAIL_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (threadIdx.x == 0 && par == 1) max_l2(stp + 4, __builtin_amdgcn_s_memrealtime());
-#endif
+        TSTAMP_MINMAX(b, 2, 3);
+    }, -1, RoleStamp{nullptr}, nullptr, traj);
+    TSTAMP_MAX_DRAINED(b, 4);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1844,39 +1808,19 @@ constexpr int LEAP_BACKOFF = LEAP_BACKOFF_N;     // x 64 cycles slept before a t
                                                  // 133.7 / 133.5 us per launch at UK-380; NI-11, whose steps are shorter: level up to 48,
                                                  // 108 against 95 at 100)
 constexpr int LEAP_BACKOFF_ROLE = 12;            // ... and a role before its second look at the tiles' flags (the trajectory's end)
+#ifndef LEAP_CB6
+#define LEAP_CB6 3                               // cells in flight per wave of a six-row tile (leap_tile: CB)
+#endif
+#ifndef LEAP_RW6_WAVES
+#define LEAP_RW6_WAVES 4                         // waves per SIMD the six-row instance is compiled for (leap_waves_per_simd)
+#endif
 constexpr int LEAP_NSH = 8;          // counters / flag copies per chain, 128 bytes apart
 constexpr int LEAP_CH = 1024;        // 64-bit words of Chains::leap per chain
 #define LEAP_CNT1(b_, k_) (ch.leap + (size_t)(b_) * LEAP_CH + (k_) * 16)            // tiles counted in on shard k, over all launches
 #define LEAP_FLAG1(b_, k_) (ch.leap + (size_t)(b_) * LEAP_CH + 128 + (k_) * 16)     // last step whose shard-k tiles are all in
 #define LEAP_CNT2(b_) (ch.leap + (size_t)(b_) * LEAP_CH + 256)                      // roles done, over all launches
 #define LEAP_FLAG2(b_, k_) (ch.leap + (size_t)(b_) * LEAP_CH + 272 + (k_) * 16)     // last step whose roles are all done (8 copies)
-#ifdef LEAP_STAMPS
-// developer timeline (tools/dev/leap_timeline.py): per chain and step, min / max over the tile workgroups of "past the wait
-// for the tables" (0, 1) and "counted in" (2, 3), min / max over the roles of "past the wait for the tiles" (4, 5) and "done" (6, 7)
-// (LEAP_STAMPS=2; they are atomics on one line per chain and stretch what they time: =1 keeps only the probes below)
-#if LEAP_STAMPS >= 2
-#define LSTAMP_MIN(k) min_l2(ch.leap_st + ((size_t)b * 16 + (it & 15)) * 8 + (k), __builtin_amdgcn_s_memrealtime())
-#define LSTAMP_MAX(k) max_l2(ch.leap_st + ((size_t)b * 16 + (it & 15)) * 8 + (k), __builtin_amdgcn_s_memrealtime())
-#else
-#define LSTAMP_MIN(k) do {} while (0)
-#define LSTAMP_MAX(k) do {} while (0)
-#endif
-// and of two tile workgroups of chain 0 (the first and one in the middle) and two roles (T-chunk 0, M-chunk 0): plain stores of their own
-// stamps, tiles behind the chains' blocks, roles in the blocks of chains 1 and 2
-#define LPROBE(k) do { if (b == 0 && threadIdx.x == 0 && (tix == 0 || tix == nwg / 2 + 5)) \
-    ch.leap_st[((size_t)s.B * 16 + (tix == 0 ? 0 : 16) + (it & 15)) * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-// every tile workgroup of chain 0 in step 7: [tix][k], behind the probes' blocks (k = 0 past the wait, 1 cells done, 2 counted in, 3 HW_ID)
-#define LALL(k) do { if (b == 0 && threadIdx.x == 0 && it == 7 && tix < 1024) \
-    ch.leap_st[((size_t)s.B + 2) * 128 + (size_t)tix * 4 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define RPROBE(k) do { if (b == 0 && threadIdx.x == 0 && (role == 0 || role == d.ntc)) \
-    ch.leap_st[((size_t)(role == 0 ? 1 : 2) * 16 + (it & 15)) * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define LSTAMP_MIN(k) do {} while (0)
-#define LSTAMP_MAX(k) do {} while (0)
-#define LPROBE(k) do {} while (0)
-#define LALL(k) do {} while (0)
-#define RPROBE(k) do {} while (0)
-#endif
+// (LSTAMP_MIN / _MAX, LPROBE, LALL, RPROBE, CPROBE in k_leap and hmc_chunk_role: developer timeline, stamps.h: LEAP)
 // A wait of k_leap for a flag (handoff.h: a time-out means its workgroups cannot all have been resident -- something else
 // holds part of the chip, e.g. a second process with a launch of the same kind)
 __device__ __forceinline__ void leap_wait(const unsigned long long *flag, unsigned long long target, unsigned *late) {
@@ -2100,9 +2044,6 @@ __device__ __forceinline__ void leap_tile(const Dims &d, const Consts &c, const 
             // CB cells in flight at a time: all four of a 16-row tile's; of six rows per wave two batches of three, which is
             // what fits the 128 registers of four waves per SIMD (six interleaved chains of the series: 171) -- with four
             // waves on a SIMD three independent chains per wave already cover the fp64 latency
-            #ifndef LEAP_CB6
-#define LEAP_CB6 3
-#endif
             constexpr int CB = RW == 6 ? LEAP_CB6 : RW;
 #pragma unroll
             for (int r0 = 0; r0 < RW; r0 += CB) {
@@ -2221,24 +2162,14 @@ __device__ __forceinline__ void leap_tile(const Dims &d, const Consts &c, const 
             LSTAMP_MIN(2); LSTAMP_MAX(3);
             LPROBE(6);                                           // counted in (the atomic has returned)
             LALL(2);
-#ifdef LEAP_STAMPS
-            if (b == 0 && it == 7 && tix < 1024) {
-                unsigned hw, xcc;
-                asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-                asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-                ch.leap_st[((size_t)s.B + 2) * 128 + (size_t)tix * 4 + 3] = ((unsigned long long)xcc << 32) | hw;
-            }
-#endif
+            LALL_HW_ID();
         }
     }
 }
 
 // waves per SIMD the instance is compiled for: the launch needs every workgroup resident, so the register budget follows from
 // how many workgroups a CU must hold (RW = 6, one 24-row tile per workgroup: three tile workgroups per CU and the roles beside
-// them -- four waves per SIMD, 128 VGPRs)
-#ifndef LEAP_RW6_WAVES
-#define LEAP_RW6_WAVES 4
-#endif
+// them -- four waves per SIMD, 128 VGPRs: LEAP_RW6_WAVES, with k_leap's other knobs above)
 constexpr int leap_waves_per_simd(int nst, int rw = SE_RW) { return rw == 6 ? LEAP_RW6_WAVES : nst == 1 ? 5 : 3; }
 template <int TSM, int NTC, int NST, int RW = SE_RW>
 __global__ __launch_bounds__(256, (NTC == 12 && RW == SE_RW) ? (leap_waves_per_simd(NST) < 3 ? leap_waves_per_simd(NST) : 3) : leap_waves_per_simd(NST, RW))
@@ -2251,14 +2182,9 @@ void k_leap(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, int par0, int nst
         int bz, tile;
         xcd_affine(blockIdx.x, nwg, d.aff_nb, bz, tile);
         if (d.nlive > 0 && bz >= d.nlive) return;      // a chain of the layout that does not exist
-#if !defined(LEAP_PART) || LEAP_PART == 1
         leap_tile<TSM, NST, RW>(d, c, w, s, ch, tile % d.ntc, tile / d.ntc, bz, par0, nsteps, step_base, role_base, fold);
-#endif
         return;
     }
-#if defined(LEAP_PART) && LEAP_PART == 1       // (developer builds: register use of the tile part alone)
-    return;
-#endif
     // a role: wave 0 runs it, the workgroup's other three waves share its loads of the tiles' partial sums (role_gather)
     __shared__ double gbuf[RoleGather<(NTC > 0 ? NTC : CT_MAXC)>::SIZE];
     const int L = (int)blockIdx.x - n_tiles;
@@ -2271,9 +2197,6 @@ void k_leap(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, int par0, int nst
     // in, and a wave that gets an issue slot only when three dense fp64 waves leave one took 1.5 us for its last ten instructions
     // (141 -> 135 us per launch; measured level while the tiles still waited for the roles' flag)
     __builtin_amdgcn_s_setprio(LEAP_ROLE_PRIO);
-#ifdef LEAP_HELPER_PRIO                            // (developer builds: the helper waves at another priority than the role's own)
-    if ((threadIdx.x >> 6) != 0) __builtin_amdgcn_s_setprio(LEAP_HELPER_PRIO);
-#endif
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane_w = (int)(threadIdx.x & 63);
     const int nsh = min(LEAP_NSH, nwg);
@@ -2311,13 +2234,9 @@ void k_leap(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, int par0, int nst
             // the helper waves: the rows' spatial effects of the current position once the previous step's roles are done
             // (the first step of a folded trajectory reads q itself), then the partial sums once the tiles are in
             if (it > 0) {
-#ifndef LEAP_WAIT_KEEP_PRIO
                 __builtin_amdgcn_s_setprio(0);        // (asleep-and-look: not ahead of the tiles it shares the SIMD with)
-#endif
                 leap_wait(flag2, role_base + (unsigned long long)it, late);
-#ifndef LEAP_WAIT_KEEP_PRIO
                 __builtin_amdgcn_s_setprio(LEAP_ROLE_PRIO);
-#endif
             }
             {
                 const bool first_ = (fold & 1) && it == 0;
@@ -2330,26 +2249,15 @@ void k_leap(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, int par0, int nst
         }
         // what the roles of the previous step wrote (chunk sums, global parameters, spatial effects, q and p)
         if (it > 0) {
-#ifndef LEAP_WAIT_KEEP_PRIO
             __builtin_amdgcn_s_setprio(0);            // (asleep-and-look: not ahead of the tiles it shares the SIMD with: 133.9 -> 132.7 us)
-#endif
             leap_wait(flag2, role_base + (unsigned long long)it, late);
-#ifndef LEAP_WAIT_KEEP_PRIO
             __builtin_amdgcn_s_setprio(LEAP_ROLE_PRIO);
-#endif
         }
         RPROBE(0);                                               // the previous step's roles are done
         hmc_chunk_role<NTC, true, true>(d, c, w, s, ch, par, role, b, [&] {
             if (threadIdx.x == 0) { LSTAMP_MIN(4); LSTAMP_MAX(5); }
             RPROBE(1);                                           // at the wait for the step's tiles (role_gather)
-        }, lane_op,
-#if defined(LEAP_STAMPS) && defined(LEAP_CPROBE)      // (the stamps INSIDE a role force its loads back early: they show the order of things, not the role's duration)
-        (b == 0 && role == 0) ? ch.leap_st + ((size_t)1 * 16 + (it & 15)) * 8 :
-        (b == 0 && role == d.ntc) ? ch.leap_st + ((size_t)2 * 16 + (it & 15)) * 8 : nullptr,
-#else
-        nullptr,
-#endif
-        gbuf, (fin_in && it == nsteps - 1) ? 3 : (fold & 1) ? (it == 0 ? 1 : it == 1 ? 2 : 0) : 0, eps_l, it > 0, ll);
+        }, lane_op, ROLE_STAMP_CTX(), gbuf, (fin_in && it == nsteps - 1) ? 3 : (fold & 1) ? (it == 0 ? 1 : it == 1 ? 2 : 0) : 0, eps_l, it > 0, ll);
         RPROBE(2);                                               // stores issued
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // this role's stores are in the XCD's L2
         RPROBE(3);
@@ -2755,25 +2663,8 @@ __device__ __forceinline__ void move_delta_body(const Dims &d, const Consts &c, 
     int bx = blockIdx.x, by = blockIdx.y;
     if (d.aff_nb > 0) xcd_affine(blockIdx.x, s.nrb_d, d.aff_nb, by, bx);
     const int b = d.b0 + by, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#ifdef SEIR_STAMPS
-#ifndef SEIR_STAMP_SLOT
-#define SEIR_STAMP_SLOT 1
-#endif
-#ifndef SEIR_STAMP_BLOCK
-#define SEIR_STAMP_BLOCK 0
-#endif
-    double *dst_hs = ch.hs + (size_t)b * NHS;
-#ifdef SEIR_STAMP_PROPOSE
-#define DSTAMP(i) do {} while (0)
-    bool dstamp_on = false;
-#else
-#define DSTAMP(i) do { if (threadIdx.x == 0 && b == 0 && bx == SEIR_STAMP_BLOCK && dstamp_on) ((unsigned long long *)(dst_hs + 16))[12 + i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-    bool dstamp_on = true;
-#endif
-#else
-#define DSTAMP(i) do {} while (0)
-#endif
-    DSTAMP(0);
+    MoveStamp dst = DELTA_STAMPS(b, bx);             // developer timeline (stamps.h: SEIR)
+    MSTAMP(dst, stamps::SW_DELTA + 0);
     move_copy(&mvA, ch.mv + (size_t)buf * s.B + b, 0);
     move_copy(&mvB, ch.mvfix + (size_t)buf * s.B + b, 64);
     if (threadIdx.x == 192) mv_sel = ch.mvsel[(size_t)buf * s.B + b];
@@ -2785,10 +2676,8 @@ __device__ __forceinline__ void move_delta_body(const Dims &d, const Consts &c, 
         apply_f_band<NW, MM>(d, c, w, b, fp, bx * rows_per_blk, min(d.M, (bx + 1) * rows_per_blk));
         __syncthreads();                           // the band written above is read below
     }
-#ifdef SEIR_STAMPS
-    dstamp_on = mv.slot == SEIR_STAMP_SLOT;
-#endif
-    DSTAMP(1);
+    MOVE_STAMP_AND(dst, mv.slot == SEIR_STAMP_SLOT);
+    MSTAMP(dst, stamps::SW_DELTA + 1);
     double dth = 0.0, dcn = 0.0;
     if (mv.valid && mv.n > 0) {
         const double psi = w.scal[(size_t)b * NSCAL + SC_PSI];
@@ -2821,11 +2710,11 @@ __device__ __forceinline__ void move_delta_body(const Dims &d, const Consts &c, 
                 }
             }
         }
-        DSTAMP(2);
+        MSTAMP(dst, stamps::SW_DELTA + 2);
         // paired form (apply_f): k_move_pair's workgroups have the updated rows' part already (Chains::Down)
         if (OWN) own_rows_delta<DELTA_THREADS, MM>(d, c, w, b, mv, psi, r_lo, r_hi, ltab, dth, dcn);
     }
-    DSTAMP(3);
+    MSTAMP(dst, stamps::SW_DELTA + 3);
     dth = wave_sum(dth);
     dcn = wave_sum(dcn);
     if (lane == 0) { sh_th[wave] = dth; sh_cn[wave] = dcn; }

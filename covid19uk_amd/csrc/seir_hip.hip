@@ -720,13 +720,6 @@ extern "C" int seir_log_prob_grad(seir_ctx *ctx, int32_t B, const double *u, con
     return host_eval(ctx, B, u, events, logp, grad);
 }
 
-#ifdef EVAL_STAMPS
-extern "C" int seir_debug_eval_stamps(seir_ctx *ctx, unsigned long long *out) {
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(out, ctx->eval_cnt + 8 * EVC_STRIDE, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return 0;
-}
-#endif
 // k_eval_all's bounded waits: a time-out means a consumer block went on without its producers' data
 static int check_eval_handoffs(seir_ctx *ctx) {
     if (!ctx->eval_err) return 0;
@@ -1620,7 +1613,7 @@ extern "C" int seir_sampler_create(seir_ctx *ctx, const seir_sampler_desc *ds, s
     S_HAND(ch.llmv, (size_t)2 * B * 32);
     S_HAND(ch.k0part, (size_t)B * ROLE_SLOTS);
     S_HAND(ch.irl0, (size_t)B);
-    S_ALLOC(allocs, ch.leap_st, (size_t)(B + 2) * 16 * 8 + 4096);
+    S_ALLOC(allocs, ch.stamps, stamps::buffer_words(B));   // developer timelines (stamps.h): the largest family's region
     S_HAND(ch.done, (size_t)B * 2 * TAIL_STRIDE);
     S_HAND(ch.pbar, (size_t)B * PBAR_STRIDE);
     S_HAND(ch.finpart, (size_t)B * ROLE_SLOTS * 4);
@@ -3941,49 +3934,6 @@ extern "C" int seir_sampler_time_leapfrog(seir_sampler *s, int32_t sweeps, float
     return 0;
 }
 
-#ifdef SE_STAMPS
-extern "C" int seir_debug_read_ts(seir_ctx *ctx, double *out, int64_t n) {
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(out, ctx->w.TS, sizeof(double) * n, hipMemcpyDeviceToHost));
-    return 0;
-}
-#endif
-
-#if defined(LEAP_STAMPS) || defined(PAIR_STAMPS)
-// [B][16][8] stamps of k_leap; reset = 1: min-words to ~0, max-words to 0 (call before the sweep to look at)
-extern "C" int seir_debug_leap_stamps(seir_sampler *s, unsigned long long *out, int reset) {
-    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
-    const size_t n = (size_t)(s->cfg.B + 2) * 16 * 8 + 4096;
-    HIP_TRY(hipMemcpy(out, s->ch.leap_st, n * 8, hipMemcpyDeviceToHost));
-    if (reset) {
-        std::vector<unsigned long long> h(n);
-        for (size_t i = 0; i < n; ++i) h[i] = (i & 1) ? 0ull : ~0ull;
-        HIP_TRY(hipMemcpy(s->ch.leap_st, h.data(), n * 8, hipMemcpyHostToDevice));
-    }
-    return 0;
-}
-#endif
-
-#ifdef TAIL_STAMPS
-// words 8..15 of every chain's counter line; reset = 1: min-words to ~0, max-words to 0 (call before the launch to look at)
-extern "C" int seir_debug_tail_stamps(seir_sampler *s, unsigned long long *out, int reset) {
-    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
-    const int B = s->cfg.B;
-    std::vector<unsigned long long> h((size_t)B * TAIL_STRIDE);
-    HIP_TRY(hipMemcpy(h.data(), s->ch.tail, h.size() * 8, hipMemcpyDeviceToHost));
-    for (int b = 0; b < B; ++b)
-        for (int k = 0; k < 8; ++k) out[b * 8 + k] = h[(size_t)b * TAIL_STRIDE + 8 + k];
-    if (reset) {
-        for (int b = 0; b < B; ++b) {
-            unsigned long long *p = h.data() + (size_t)b * TAIL_STRIDE + 8;
-            p[0] = p[2] = p[5] = ~0ull; p[1] = p[3] = p[4] = 0;
-        }
-        HIP_TRY(hipMemcpy(s->ch.tail, h.data(), h.size() * 8, hipMemcpyHostToDevice));
-    }
-    return 0;
-}
-#endif
-
 extern "C" int seir_sampler_pair_timeouts(seir_sampler *s, uint32_t *out) {
     int rc = sampler_check(s);
     if (rc) return rc;
@@ -3995,10 +3945,48 @@ extern "C" int seir_sampler_pair_timeouts(seir_sampler *s, uint32_t *out) {
     return 0;
 }
 
-#ifdef SEIR_STAMPS
-extern "C" int seir_sampler_debug_hs(seir_sampler *s, double *out) {
+#if STAMPS_ON
+// The stamped developer builds (stamps.h; tools/dev/stamps.py): the build's family region, read once everything enqueued has
+// finished.  reset: afterwards the region is rewritten by the table's pattern -- min-words ~0, every other word 0.
+static void stamps_reset_pattern(std::vector<unsigned long long> &h, int B) {
+    for (size_t i = 0; i < h.size(); ++i) h[i] = stamps::min_word(stamps::FAMILY, B, i) ? ~0ull : 0ull;
+}
+// the sampler's families (SEIR, PAIR, LEAP, TAIL): words [0, n_words) of Chains::stamps
+extern "C" int seir_stamps_read(seir_sampler *s, unsigned long long *out, int64_t n_words, int reset) {
+    constexpr bool mine = stamps::FAMILY == stamps::F_SEIR || stamps::FAMILY == stamps::F_PAIR || stamps::FAMILY == stamps::F_LEAP ||
+                          stamps::FAMILY == stamps::F_TAIL;
+    const size_t ext = stamps::extent(stamps::FAMILY, s->cfg.B);
+    static_assert(stamps::extent(stamps::F_SEIR, 1) <= stamps::buffer_words(1), "the buffer holds every family");
+    if (!mine) return fail(SEIR_ERR_STATE, "this build's stamp family belongs to the context: seir_stamps_read_ctx");
+    if (!out || n_words < 0 || (size_t)n_words > ext || ext > stamps::buffer_words(s->cfg.B))
+        return fail(SEIR_ERR_INVALID, "stamps: %lld words asked for, the family's region has %zu", (long long)n_words, ext);
     HIP_TRY(hipStreamSynchronize(s->ctx->stream));
-    HIP_TRY(hipMemcpy(out, s->ch.hs, sizeof(double) * s->cfg.B * NHS, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, s->ch.stamps, (size_t)n_words * 8, hipMemcpyDeviceToHost));
+    if (reset) {
+        std::vector<unsigned long long> h(ext);
+        stamps_reset_pattern(h, s->cfg.B);
+        HIP_TRY(hipMemcpy(s->ch.stamps, h.data(), ext * 8, hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+// the context's families.  SE: the tile scalars [tiles][4] (words 2 and 3 of a tile are its stamps; every launch rewrites them:
+// no reset); EVAL: the words behind the counters of the last launch's chains
+extern "C" int seir_stamps_read_ctx(seir_ctx *ctx, unsigned long long *out, int64_t n_words, int reset) {
+    if (!out || n_words < 0) return fail(SEIR_ERR_INVALID, "stamps: null pointer or negative count");
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (stamps::FAMILY == stamps::F_SE) {
+        if (!ctx->w.TS || (size_t)n_words > (size_t)ctx->Bmax * ctx->d.nmt * ctx->d.ntc * stamps::SE_NW)
+            return fail(SEIR_ERR_INVALID, "stamps: the tile scalars hold %d x %d x %d tiles of 4 words", ctx->Bmax, ctx->d.nmt, ctx->d.ntc);
+        HIP_TRY(hipMemcpy(out, ctx->w.TS, (size_t)n_words * 8, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    if (stamps::FAMILY != stamps::F_EVAL) return fail(SEIR_ERR_STATE, "this build's stamp family belongs to the sampler: seir_stamps_read");
+    if (!ctx->eval_cnt || ctx->eval_nb < 1 || n_words > stamps::EVAL_WORDS)
+        return fail(SEIR_ERR_INVALID, "stamps: no one-launch evaluation yet, or more than %d words", stamps::EVAL_WORDS);
+    static_assert(stamps::EVAL_WORDS <= 16, "the spare words behind the counters (launch_eval_all)");
+    unsigned long long *base = ctx->eval_cnt + (size_t)((ctx->eval_nb + 7) / 8 * 8) * EVC_STRIDE;
+    HIP_TRY(hipMemcpy(out, base, (size_t)n_words * 8, hipMemcpyDeviceToHost));
+    if (reset) HIP_TRY(hipMemset(base, 0, stamps::EVAL_WORDS * 8));
     return 0;
 }
 #endif

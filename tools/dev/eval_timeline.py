@@ -1,12 +1,10 @@
 #!/usr/bin/env python3
 """Developer probe (GPU box): where the one-launch stateless evaluation (k_eval_all) spends its time -- stamps of tile 0 of
 chain 0 and of the chain's finish block.
-Build: bash tools/dev/build_variant.sh evst -DEVAL_STAMPS=1 -mllvm -disable-machine-licm;  python tools/dev/eval_timeline.py evst [grad]"""
-import ctypes, os, sys, numpy as np
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..")
-sys.path.insert(0, ROOT)
-from covid19uk_amd import _lib
-_lib.LIB_PATH = os.path.join(ROOT, "tools", "dev", "variants", f"libseirhip_{sys.argv[1]}.so")
+Build: bash tools/dev/build_variant.sh evst;  python tools/dev/eval_timeline.py evst [grad]"""
+import sys, numpy as np
+import stamps
+stamps.load_variant(sys.argv[1])
 import torch
 from covid19uk_amd import synth
 from covid19uk_amd.seir import SeirModel
@@ -19,8 +17,6 @@ u = synth.jitter_params(u0, B, T=cov.T)
 dev = torch.device("cuda:0")
 ut = torch.tensor(u, device=dev); evt = torch.tensor(np.stack([events] * B), device=dev)
 lp = torch.empty(B, dtype=torch.float64, device=dev); g = torch.empty(B, u.shape[1], dtype=torch.float64, device=dev)
-lib = _lib.load()
-lib.seir_debug_eval_stamps.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 with SeirModel(cov, init, max_chains=B) as model:
     for _ in range(5):
         model.log_prob_dev(ut, evt, lp, g if with_grad else None)
@@ -29,9 +25,7 @@ with SeirModel(cov, init, max_chains=B) as model:
     for rep in range(15):
         model.log_prob_dev(ut, evt, lp, g if with_grad else None)
         model.sync()
-        out = np.zeros(8, dtype=np.uint64)
-        lib.seir_debug_eval_stamps(model._ctx, out.ctypes.data)
-        rows.append(out.astype(np.int64) * 10.0)
+        rows.append(stamps.read(model, "eval")["words"].astype(np.int64) * 10.0)
     st = np.stack(rows)
     rel = st - st[:, :1]
     med = np.median(rel, axis=0)
