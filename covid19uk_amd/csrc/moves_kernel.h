@@ -677,13 +677,19 @@ __global__ __launch_bounds__(MVB) void k_move_pa2_m4(Dims d, Consts c, Work w, S
 // of the four updates are those of k_move_pa2 / the oracle.
 // ---------------------------------------------------------------------------------------------
 constexpr int PRE_RT = 4;                                      // prefetched rows per thread (M <= 2048)
+// Rows k * MVB + tid, k >= 1, exist only where M > MVB: the iterations k >= 1 of the two functions below stand behind ONE
+// wave-uniform test of M (a scalar branch), so that at M <= 512 -- every BASELINE shape but SYN-2048 -- a role executes
+// iteration 0 and that branch, not three more guarded iterations of addresses and predicates, twice per step.  (A second
+// PRE_RT constant would have done the same at the price of twice the instances.)
+#ifndef PAIR_PRE_ROWS_ALL
+#define PAIR_PRE_ROWS_ALL 0            // 1: all PRE_RT iterations whatever M is, as up to round 34 (A/B builds)
+#endif
 
 // row totals (kind 0) or per-row events inside the occult range (kind 1) of plane spec.tgt
 __device__ __forceinline__ void mv_prefetch_rows(const Dims &d, const Work &w, const SamplerCfg &s, int b, MoveSpec spec,
                                                  bool on, int (&pre)[PRE_RT]) {
     const int tid = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < PRE_RT; ++k) {
+    auto row = [&](int k) {
         const int m = tid + k * MVB;
         pre[k] = 0;
         if (on && m < d.M) {
@@ -693,6 +699,14 @@ __device__ __forceinline__ void mv_prefetch_rows(const Dims &d, const Work &w, c
                 pre[k] = w.rngtot[((size_t)b * 2 + spec.tgt) * d.Mp + m];
             }
         }
+    };
+    row(0);
+    if (PAIR_PRE_ROWS_ALL || d.M > MVB) {                      // (uniform)
+#pragma unroll
+        for (int k = 1; k < PRE_RT; ++k) row(k);
+    } else {
+#pragma unroll
+        for (int k = 1; k < PRE_RT; ++k) pre[k] = 0;
     }
 }
 
@@ -704,10 +718,13 @@ __device__ __forceinline__ void mv_rows_to_lds(const Dims &d, const Work &w, con
     const int tid = threadIdx.x, M = d.M;
     int *dst = spec.kind == 0 ? rtl : L.rg;
     if (pre_ok) {
+        if (tid < M) dst[tid] = pre[0];
+        if (PAIR_PRE_ROWS_ALL || M > MVB) {                    // (uniform, as in mv_prefetch_rows)
 #pragma unroll
-        for (int k = 0; k < PRE_RT; ++k) {
-            const int m = tid + k * MVB;
-            if (m < M) dst[m] = pre[k];
+            for (int k = 1; k < PRE_RT; ++k) {
+                const int m = tid + k * MVB;
+                if (m < M) dst[m] = pre[k];
+            }
         }
         lds_barrier();
         if (fix && tid == 0)
@@ -860,9 +877,13 @@ __device__ __forceinline__ TT ld_band(const TT *p_) { return SOLO ? *p_ : ld_l2(
 #ifndef PAIR_BAND_BACKOFF
 #define PAIR_BAND_BACKOFF 0            // x 64 cycles a band workgroup sleeps before it first looks for role 0's token
 #endif
+// rpb: rows per band workgroup, ceil(M / nband) -- a constant of the launch, from the host (band_rows, sweep_plan.h)
+#ifndef PAIR_BAND_ROWS_DIV
+#define PAIR_BAND_ROWS_DIV 0           // 1: the band workgroups divide their rows out of M and nband in every step (A/B builds)
+#endif
 template <bool SOLO, int NRB, int MM>
 __device__ __forceinline__ void pair_band_block(const Dims &d, const Consts &c, const Work &w, const SamplerCfg &s,
-                                                const Chains &ch, int b, int bx, int nband, unsigned token, bool has_r1,
+                                                const Chains &ch, int b, int bx, int nband, int rpb, unsigned token, bool has_r1,
                                                 bool has_r2, int buf, PairStamp qst = PairStamp{}) {
     __shared__ Move mvA, mvB, fp;
     __shared__ int mv_sel;
@@ -874,7 +895,6 @@ __device__ __forceinline__ void pair_band_block(const Dims &d, const Consts &c, 
     if (tid < LDSTAB_N) ltab[tid] = c.logtab[tid];
     const double psi = w.scal[(size_t)b * NSCAL + SC_PSI];      // constant during the event updates
     const unsigned *done = ch.done + (size_t)b * 2 * TAIL_STRIDE;
-    const int rpb = (d.M + nband - 1) / nband;
     const int r_lo = bx * rpb, r_hi = min(d.M, r_lo + rpb);
     // ---- the update accepted in this launch (token 4, early in the authoritative role): its descriptor, and what its F
     // band needs for this workgroup's rows -- coefficients and the F values themselves (nobody writes F but this code)
@@ -1075,14 +1095,13 @@ __device__ __forceinline__ void pair_band_block(const Dims &d, const Consts &c, 
 // sweep that is not recorded (thinning, trace_slot.h) still applies the F band and only skips the copy.
 template <int MM>
 __device__ __forceinline__ void pair_band_finish(const Dims &d, const Consts &c, const Work &w, const SamplerCfg &s,
-                                                 const Chains &ch, int b, int bx, int nband, unsigned token, unsigned slot,
+                                                 const Chains &ch, int b, int bx, int rpb, unsigned token, unsigned slot,
                                                  int record) {
     __shared__ Move fp;
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid));                          // (see pair_step)
     const int wave = tid >> 6, lane = tid & 63;
     const unsigned *done = ch.done + (size_t)b * 2 * TAIL_STRIDE;
-    const int rpb = (d.M + nband - 1) / nband;
     const int r_lo = bx * rpb, r_hi = min(d.M, r_lo + rpb);
     if (tid == 0) wait_token(done + 4, token, ch.late + ch.late_fatal + b);
     __syncthreads();
@@ -1143,7 +1162,7 @@ __device__ __forceinline__ void pair_band_finish(const Dims &d, const Consts &c,
 template <int NCH, bool SOLO, int MM>
 __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const Work &w, const SamplerCfg &s, const Chains &ch,
                                           MoveSpec se, MoveSpec next, MoveSpec se_next, int have_prev, int have_pre, int pbuf,
-                                          int lidx, int dbg, int nband, int nroles, int slot, int b, int fin = 0,
+                                          int lidx, int dbg, int nband, int rpb_host, int nroles, int slot, int b, int fin = 0,
                                           unsigned sweep0 = 0u, int lprev = 0, unsigned tslot = TRACE_NOT_RECORDED) {
     extern __shared__ __attribute__((aligned(16))) int dyn_i[];                     // rg [M] | rt [M]
     __shared__ MvShared sm_se, sm_nx;
@@ -1161,16 +1180,19 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
     QSTAMP(qst, 0);
     if (slot >= nroles) {                                  // band workgroups (the highest block ids)
         if (nband == 0) return;
+        // rows per band workgroup: a constant of the launch, from the host with the launch arguments (they come through the
+        // scalar cache, which the per-step L1 drop leaves alone) -- not divided out in every step by every band workgroup
+        const int rpb = PAIR_BAND_ROWS_DIV ? (d.M + nband - 1) / nband : rpb_host;
         if (fin) {                                         // the closing step of k_move_pairs: they finish the sweep
-            pair_band_finish<MM>(d, c, w, s, ch, b, slot - nroles, nband, pair_token(sweep0, lidx), tslot, fin & 2);
+            pair_band_finish<MM>(d, c, w, s, ch, b, slot - nroles, rpb, pair_token(sweep0, lidx), tslot, fin & 2);
             return;
         }
         const unsigned tok = pair_token(ch.sweep[b], lidx);
         const bool r1 = next.kind >= 0 && nroles >= 2, r2 = se_next.kind >= 0 && nroles == 3;
-        if ((d.M + nband - 1) / nband > 2 * MVW)              // (uniform) more than 16 rows per band workgroup: four per wave
-            pair_band_block<SOLO, 4, MM>(d, c, w, s, ch, b, slot - nroles, nband, tok, r1, r2, pbuf ^ 1, qst);
+        if (rpb > 2 * MVW)                                    // (uniform) more than 16 rows per band workgroup: four per wave
+            pair_band_block<SOLO, 4, MM>(d, c, w, s, ch, b, slot - nroles, nband, rpb, tok, r1, r2, pbuf ^ 1, qst);
         else
-            pair_band_block<SOLO, 2, MM>(d, c, w, s, ch, b, slot - nroles, nband, tok, r1, r2, pbuf ^ 1, qst);
+            pair_band_block<SOLO, 2, MM>(d, c, w, s, ch, b, slot - nroles, nband, rpb, tok, r1, r2, pbuf ^ 1, qst);
         return;
     }
     const int role = slot == nroles - 1 ? 0 : slot + 1;
@@ -1531,7 +1553,7 @@ __device__ __forceinline__ void pair_step(const Dims &d, const Consts &c, const 
 template <int NCH, int MM>
 __device__ __forceinline__ void move_pair_body(const Dims &d, const Consts &c, const Work &w, const SamplerCfg &s, const Chains &ch,
                                                MoveSpec se, MoveSpec next, MoveSpec se_next, int have_prev, int have_pre,
-                                               int pbuf, int nbk, int lidx, int dbg, int nband) {
+                                               int pbuf, int nbk, int lidx, int dbg, int nband, int rpb) {
     debug_skew(d);
     // block id = slot * nbk + chain with the speculative roles in the low slots: they are dispatched first,
     // so an authoritative workgroup never holds a CU waiting for a partner that has not been placed yet,
@@ -1539,21 +1561,21 @@ __device__ __forceinline__ void move_pair_body(const Dims &d, const Consts &c, c
     const int nroles = (int)gridDim.x / nbk - nband, slot = (int)blockIdx.x / nbk;
     const int b = d.b0 + (int)blockIdx.x - slot * nbk;
     if (d.nlive > 0 && (int)blockIdx.x - slot * nbk >= d.nlive) return;             // a chain of the layout that does not exist
-    pair_step<NCH, false, MM>(d, c, w, s, ch, se, next, se_next, have_prev, have_pre, pbuf, lidx, dbg, nband, nroles, slot, b);
+    pair_step<NCH, false, MM>(d, c, w, s, ch, se, next, se_next, have_prev, have_pre, pbuf, lidx, dbg, nband, rpb, nroles, slot, b);
     QSTAMP(PAIR_STAMP_CTX(b - d.b0, slot, lidx), 8);
 }
 // the instances: m <= MM_SMALL under the plain name, every m <= MMAX as _m4 (the host's move_pair_fn picks)
 template <int NCH>
 __global__ __launch_bounds__(MVB) void k_move_pair(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, MoveSpec se,
                                                    MoveSpec next, MoveSpec se_next, int have_prev, int have_pre,
-                                                   int pbuf, int nbk, int lidx, int dbg, int nband) {
-    move_pair_body<NCH, MM_SMALL>(d, c, w, s, ch, se, next, se_next, have_prev, have_pre, pbuf, nbk, lidx, dbg, nband);
+                                                   int pbuf, int nbk, int lidx, int dbg, int nband, int rpb) {
+    move_pair_body<NCH, MM_SMALL>(d, c, w, s, ch, se, next, se_next, have_prev, have_pre, pbuf, nbk, lidx, dbg, nband, rpb);
 }
 template <int NCH>
 __global__ __launch_bounds__(MVB) void k_move_pair_m4(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, MoveSpec se,
                                                       MoveSpec next, MoveSpec se_next, int have_prev, int have_pre,
-                                                      int pbuf, int nbk, int lidx, int dbg, int nband) {
-    move_pair_body<NCH, MMAX>(d, c, w, s, ch, se, next, se_next, have_prev, have_pre, pbuf, nbk, lidx, dbg, nband);
+                                                      int pbuf, int nbk, int lidx, int dbg, int nband, int rpb) {
+    move_pair_body<NCH, MMAX>(d, c, w, s, ch, se, next, se_next, have_prev, have_pre, pbuf, nbk, lidx, dbg, nband, rpb);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1640,7 +1662,8 @@ __device__ __forceinline__ void pair_debug_delay(int dbg, int slot, int nroles, 
 
 template <int NCH, int MM>
 __device__ __forceinline__ void move_pairs_body(const Dims &d, const Consts &c, const Work &w, const SamplerCfg &s, const Chains &ch,
-                                                int npairs, int pre_on, int nbk, int dbg, int nband, unsigned pbase, int fin) {
+                                                int npairs, int pre_on, int nbk, int dbg, int nband, int rpb, unsigned pbase,
+                                                int fin) {
     debug_skew(d);
     const int nroles = (int)gridDim.x / nbk - nband, slot = (int)blockIdx.x / nbk;   // 3 roles
     const int b = d.b0 + (int)blockIdx.x - slot * nbk;
@@ -1662,7 +1685,7 @@ __device__ __forceinline__ void move_pairs_body(const Dims &d, const Consts &c, 
         const MoveSpec se_next = pre ? MoveSpec{nh, 0, 2 * nh, nscan} : none;
         if (dbg & PAIR_DBG_DELAYS) pair_debug_delay(dbg, slot, nroles, pair, b);
         pair_step<NCH, true, MM>(d, c, w, s, ch, se, nx, se_next, pair > 0 ? 1 : 0, (pair > 0 && pre_on && !closing) ? 1 : 0, pair & 1,
-                       closing ? 62 : pair, closing ? 0 : dbg, (closing && !fin) ? 0 : nband, nroles, slot, b, closing ? fin : 0, sweep0,
+                       closing ? 62 : pair, closing ? 0 : dbg, (closing && !fin) ? 0 : nband, rpb, nroles, slot, b, closing ? fin : 0, sweep0,
                        pair - 1, tslot);
         if (closing) break;
         const PairStamp qst = PAIR_STAMP_CTX(b - d.b0, slot, pair);
@@ -1674,13 +1697,13 @@ __device__ __forceinline__ void move_pairs_body(const Dims &d, const Consts &c, 
 }
 template <int NCH>
 __global__ __launch_bounds__(MVB) void k_move_pairs(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, int npairs, int pre_on,
-                                                    int nbk, int dbg, int nband, unsigned pbase, int fin) {
-    move_pairs_body<NCH, MM_SMALL>(d, c, w, s, ch, npairs, pre_on, nbk, dbg, nband, pbase, fin);
+                                                    int nbk, int dbg, int nband, int rpb, unsigned pbase, int fin) {
+    move_pairs_body<NCH, MM_SMALL>(d, c, w, s, ch, npairs, pre_on, nbk, dbg, nband, rpb, pbase, fin);
 }
 template <int NCH>
 __global__ __launch_bounds__(MVB) void k_move_pairs_m4(Dims d, Consts c, Work w, SamplerCfg s, Chains ch, int npairs, int pre_on,
-                                                       int nbk, int dbg, int nband, unsigned pbase, int fin) {
-    move_pairs_body<NCH, MMAX>(d, c, w, s, ch, npairs, pre_on, nbk, dbg, nband, pbase, fin);
+                                                       int nbk, int dbg, int nband, int rpb, unsigned pbase, int fin) {
+    move_pairs_body<NCH, MMAX>(d, c, w, s, ch, npairs, pre_on, nbk, dbg, nband, rpb, pbase, fin);
 }
 
 inline size_t k_move_pa2_lds_bytes(const Dims &d) {

@@ -22,6 +22,7 @@
 #pragma once
 #include "handoff.h"
 #include "logprob_kernels.h"
+#include "move_cells.h"
 #include "philox.h"
 #include "trace_slot.h"
 
@@ -2370,6 +2371,9 @@ __device__ inline int comp_start(const Dims &d, const Work &w, size_t rowoff, in
     return v;
 }
 
+#ifndef MOVE_CELL_ROW_DIV
+#define MOVE_CELL_ROW_DIV 0            // 1: own_rows_delta finds a cell's row by a division, as it did up to round 34 (A/B builds)
+#endif
 struct MoveSpec { int kind, tgt, slot, scan; };   // slot 0..3 = S->E move, E->I move, S->E occult, E->I occult
 
 // Per-cell log-likelihood pieces (the full form the differences below are taken from):
@@ -2422,7 +2426,8 @@ __device__ __forceinline__ void own_rows_delta(const Dims &d, const Consts &c, c
     auto cell_of = [&](int cell, int &i0, int &k, int &t) {
         int pos = cell;
         i0 = 0;
-        if (tgt == 1) { i0 = cell / total_w; pos = cell - i0 * total_w; }
+        // (the row of an E->I-type proposal's cell: a count of compares -- move_cells.h -- not a run-time division)
+        if (tgt == 1) { i0 = MOVE_CELL_ROW_DIV ? cell / total_w : cell_row<MM>(cell, total_w, mv.n); pos = cell - i0 * total_w; }
         int p0 = 0;
         k = 0;
 #pragma unroll

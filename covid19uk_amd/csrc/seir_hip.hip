@@ -2313,7 +2313,7 @@ static void enqueue_sweep(seir_sampler *s, int g) {
             // every pair of the sweep and the closing step in ONE launch, resident for the whole sweep (its closing step
             // also does what k_apply_fpend / k_record are launched for in the other forms)
             hipLaunchKernelGGL(move_pairs_fn(p.nch, mm), dim3((3 + p.nband) * p.nbk), dim3(MVB), k_move_pairs_lds_bytes(d), st, dp, ctx->c, ctx->w, cp,
-                               s->ch, npairs, 1, p.nbk, s->pair_debug, p.nband, s->pbar_count, s->record_events ? 3 : 1);
+                               s->ch, npairs, 1, p.nbk, s->pair_debug, p.nband, band_rows(d.M, p.nband), s->pbar_count, s->record_events ? 3 : 1);
             s->pbar_count += (unsigned)(npairs * 3);                 // what every live chain's counter shows after this launch: the roles' arrivals
         } else {
             int have_pre = 0;
@@ -2326,7 +2326,7 @@ static void enqueue_sweep(seir_sampler *s, int g) {
                     const int nh = (half + 1) & 1, nscan = scan + (half == 1 ? 1 : 0);
                     const MoveSpec se_next = pre ? MoveSpec{nh, 0, 2 * nh, nscan} : MoveSpec{-1, 0, 0, 0};
                     hipLaunchKernelGGL(pair_fn, dim3(((pre ? 3 : 2) + p.nband) * p.nbk), dim3(MVB), plds, st, dp, ctx->c, ctx->w, cp,
-                                       s->ch, se, nx, se_next, have_prev, have_pre, pbuf, p.nbk, pair, s->pair_debug, p.nband);
+                                       s->ch, se, nx, se_next, have_prev, have_pre, pbuf, p.nbk, pair, s->pair_debug, p.nband, band_rows(d.M, p.nband));
                     have_pre = pre ? 1 : 0;
                     pbuf ^= 1;
                     if (!p.nband)
@@ -2336,7 +2336,7 @@ static void enqueue_sweep(seir_sampler *s, int g) {
             if (have_prev) {
                 const MoveSpec none{-1, 0, 0, 0}, close{-2, 0, 0, 0};
                 hipLaunchKernelGGL(pair_fn, dim3(nb), dim3(MVB), plds, st, d, ctx->c, ctx->w, cp, s->ch, none, close, none, 1,
-                                   0, pbuf, nb, 62, 0, 0);
+                                   0, pbuf, nb, 62, 0, 0, 0);
                 if (p.fpend == SweepPlan::F_APPLY) hipLaunchKernelGGL(apply_fpend_fn(mm), gm, dim3(256), 0, st, d, ctx->c, ctx->w, c, s->ch);
             }
         }

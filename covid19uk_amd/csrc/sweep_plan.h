@@ -29,6 +29,9 @@ inline int moves_form(int moves_mode, int n_scans) { return n_scans > 30 ? 1 : m
 inline int move_mm(int m, bool generic) { return (m <= plan::MM_SMALL && !generic) ? plan::MM_SMALL : plan::MMAX; }
 // tile scalars of the chunked leapfrog: 1 = column scalars only (the M-chunks sum the row partials themselves), 2 = all four
 inline int chunk_ts_mode(int Mp) { return Mp <= 512 ? 1 : 2; }
+// rows per band workgroup of the pair launches (pair_band_block, moves_kernel.h): ceil(M / nband), a constant of the launch
+// that the kernels take as an argument (0: no band workgroups)
+inline int band_rows(int M, int nband) { return nband > 0 ? (M + nband - 1) / nband : 0; }
 // 64-day chunks a row of the series is held in by the proposing wave (moves_kernel.h; sampler_create caps T at 1024)
 inline int move_nch(int Tp) { return Tp <= 6 * plan::WAVE ? 6 : Tp <= 12 * plan::WAVE ? 12 : 16; }
 
