@@ -318,6 +318,16 @@ _SIGNATURES = {
     "seir_sampler_scenarios_set_local": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_double_p, c_double_p, ctypes.c_int64]),
     "seir_sampler_scenario_groups_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "seir_sampler_read_scenario_group_draws": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_int64_p]),
+    # triggered scenarios: two operand pairs and a rule on the draw's own case counts; the fold of the rule's record alone
+    "seir_sampler_scenarios_set_triggered": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_double_p, c_double_p, c_double_p,
+                                                            c_double_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                                            ctypes.POINTER(ctypes.c_int32), ctypes.c_int64]),
+    "seir_sampler_read_scenario_triggers": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]),
+    "seir_sampler_read_scenario_trigger_draws": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                                ctypes.POINTER(ctypes.c_int32)]),
+    "seir_trigger_counts": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int64, ctypes.c_int32,
+                                           ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32),
+                                           ctypes.POINTER(ctypes.c_int32)]),
     # the forecast scored against later data; the sum of pairwise absolute differences alone on host arrays
     "seir_sampler_verify_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     "seir_sampler_verify_state": (ctypes.c_int, [ctypes.c_void_p, c_int64_p]),

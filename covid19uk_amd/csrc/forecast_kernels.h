@@ -140,9 +140,10 @@ __global__ __launch_bounds__(64 * FC_ROWS) void k_forecast_prepare(Dims d, Const
 // m and s alone -- never on the column block -- which is what couples a scenario to the baseline variate by variate.  The
 // callers differ in where the planes lie, in the two operands ea_of() = exp(log baseline) and psiW_of(psi) = psi W, called
 // where the rates are formed, and in the draw's position `draw` in the staging tensor ev [..][M][H][3].
-// Dims, Consts and ForecastBufs by value, as the kernels take them.
+// Dims, Consts and ForecastBufs by value, as the kernels take them.  Returns the day's I->R count,
+// which a triggered scenario's window takes (scenario_trigger_kernels.h); the other callers drop it.
 template <typename Ea, typename PsiW>
-__device__ __forceinline__ void rollout_day_cell(Dims d, Consts c, ForecastBufs fb, int *St, double *X, const double *Fp,
+__device__ __forceinline__ int rollout_day_cell(Dims d, Consts c, ForecastBufs fb, int *St, double *X, const double *Fp,
                                                  size_t plane, size_t idx, size_t ebi, int nd, int m, int B, int chain0, int j0,
                                                  int ndp, int s, int *ev, size_t draw, Ea ea_of, PsiW psiW_of) {
     const int M = d.M, H = fb.H;
@@ -165,6 +166,7 @@ __device__ __forceinline__ void rollout_day_cell(Dims d, Consts c, ForecastBufs 
     S -= y0; E += y0 - y1; I += y1 - y2;
     St[idx] = S; St[plane + idx] = E; St[2 * plane + idx] = I;
     X[idx] = (double)I * c.invN[m];
+    return y2;
 }
 
 // Forecast day s for every (row, draw): grid (ndp / 64, ceil(M / FC_DAY_ROWS)), 64 FC_DAY_ROWS threads.

@@ -1286,8 +1286,23 @@ struct ScenarioSet {
     size_t words4() const { return c6 + 3 * c4 + 2; }
     // A local set (seir_sampler_scenarios_set_local; scenario_local_kernels.h): scenarios_batch launches the local kernels,
     // which read these two in the place of log_shift, Wk and base (not allocated then).
-    bool local = false;
+    // A triggered set (seir_sampler_scenarios_set_triggered; scenario_trigger_kernels.h): the local tensors are its off pair,
+    // and it has the on pair, the rule and the rule's planes and products below.
+    enum Mode { GLOBAL = 0, LOCAL = 1, TRIGGERED = 2 };
+    Mode mode = GLOBAL;
+    bool local() const { return mode != GLOBAL; }       // the operands are [K][H][M] tensors
+    bool triggered() const { return mode == TRIGGERED; }
     double *log_shift_loc = nullptr, *Wk_loc = nullptr;   // [K][H][M]: the caller's tensors transposed
+    std::vector<double> commute_on;   // [K][M][H] on the host, as commute is
+    double *log_shift_on = nullptr, *Wk_on = nullptr;     // [K][H][M]
+    int32_t *trig_on = nullptr, *trig_off = nullptr;      // [K][M] thresholds
+    int32_t *trig_params = nullptr;   // [K][4] window, from_day, min_days, review_every
+    int wmax = 0;                     // the largest window: hist's rows
+    int32_t *hist = nullptr;          // [wmax][Mp][ndmax]
+    int32_t *win = nullptr, *age = nullptr;               // [Mp][K ndmax]
+    uint64_t *mask = nullptr;         // [2][Mp][K ndmax]
+    int32_t *active_by_day = nullptr; // [K][cap][B][H] by draw position since the forecast reset; overwritten, no shadow
+    Shadowed tacc;                    // active_count [K][B][M][H] uint32: shadowed, invalidated and zeroed where acc is
     // The per-draw region totals of the scenarios (seir_sampler_scenario_groups_set), by draw position since the forecast
     // reset like by_day: int64 [K][cap][B][G][H][3], or empty: off.  No shadow: a burst run again overwrites its positions.
     DevBuf gstore;
@@ -1813,6 +1828,7 @@ static int moments_shadow(seir_sampler *s, int slot, bool save) {
     }
     if (!rc && s->fc.on) rc = counted_shadow(s->fc.acc, slot, save, st);
     if (!rc && s->fc.on && s->scen.K) rc = acc_shadow(s->scen.acc, slot, save, st);   // their count is the forecast's j
+    if (!rc && s->fc.on && s->scen.K && s->scen.triggered()) rc = acc_shadow(s->scen.tacc, slot, save, st);
     if (!rc && s->fc.on && s->ver.on) rc = acc_shadow(s->ver.acc, slot, save, st);    // and so is the verification's
     if (!rc && s->rt.on) rc = counted_shadow(s->rt.acc, slot, save, st);
     if (!rc && s->ck.on) {
@@ -4366,18 +4382,30 @@ extern "C" int seir_scenario_diffs(seir_ctx *ctx, const int32_t *base_events, co
 // parent had.
 static void scenarios_local_rollout(seir_sampler *s, const LaunchCfg &l, const ForecastBufs &fb, const ScenarioBufs &sb,
                                     const RolloutBatch &bt, int j);
+// The same of a triggered set (seir_sampler_scenarios_set_triggered), and the fold of its masks behind the days: behind
+// scenario_trigger_kernels.h, which is included behind scenario_local_kernels.h.
+static void scenarios_trigger_rollout(seir_sampler *s, const LaunchCfg &l, const ForecastBufs &fb, const ScenarioBufs &sb,
+                                      const RolloutBatch &bt, int32_t first, int j);
+static void scenarios_trigger_fold(seir_sampler *s, const LaunchCfg &l, const RolloutBatch &bt, int k, long long j);
 
 // The rollout of a batch's K column blocks, whichever set rolls it: `begin` over `elems` elements of every block's planes, then
 // the H days over the K ndp columns with day(grid, block, h), the set's day launch.
+// launch_begin(grid, block) is the set's begin launch: a triggered set's takes more than a ScenarioBegin's arguments.
 using ScenarioBegin = void (*)(Dims, Consts, ForecastBufs, ScenarioBufs, int, int);
+template <typename Begin, typename Day>
+static void scenarios_rollout_with(seir_ctx *ctx, const LaunchCfg &l, const ForecastBufs &fb, const ScenarioBufs &sb,
+                                   const RolloutBatch &bt, size_t elems, Begin launch_begin, Day day) {
+    const int cols = sb.K * bt.ndp;
+    launch_begin(dim3((unsigned)((elems + SC_BEGIN_THREADS - 1) / SC_BEGIN_THREADS), sb.K), dim3(SC_BEGIN_THREADS));
+    const dim3 grid(cols / 64, (l.d.M + FC_DAY_ROWS - 1) / FC_DAY_ROWS), block(64 * FC_DAY_ROWS);
+    rollout_day_loop(ctx, l, sb.X, sb.F, cols, fb.H, [&](int h) { day(grid, block, h); });
+}
 template <typename Day>
 static void scenarios_rollout(seir_ctx *ctx, const LaunchCfg &l, const ForecastBufs &fb, const ScenarioBufs &sb,
                               const RolloutBatch &bt, ScenarioBegin begin, size_t elems, Day day) {
-    const int cols = sb.K * bt.ndp;
-    hipLaunchKernelGGL(begin, dim3((unsigned)((elems + SC_BEGIN_THREADS - 1) / SC_BEGIN_THREADS), sb.K), dim3(SC_BEGIN_THREADS), 0,
-                       l.st, l.d, ctx->c, fb, sb, bt.ND, bt.ndp);
-    const dim3 grid(cols / 64, (l.d.M + FC_DAY_ROWS - 1) / FC_DAY_ROWS), block(64 * FC_DAY_ROWS);
-    rollout_day_loop(ctx, l, sb.X, sb.F, cols, fb.H, [&](int h) { day(grid, block, h); });
+    scenarios_rollout_with(ctx, l, fb, sb, bt, elems, [&](dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(begin, grid, block, 0, l.st, l.d, ctx->c, fb, sb, bt.ND, bt.ndp);
+    }, day);
 }
 
 // Scenario k's parts of the one block (ScenarioSet::acc): the moments into mb's accumulator pointers, the differences into df.
@@ -4404,9 +4432,22 @@ static int scenarios_begin(seir_sampler *s) {
     ScenarioSet &sc = s->scen;
     const int H = s->fc.fb.H;
     hipStream_t st = s->ctx->stream;
-    const size_t M = sc.local ? (size_t)s->ctx->d.M : 1;
-    std::vector<double> wk((size_t)sc.K * H * M);
-    if (sc.local) {                                   // [K][H][M] out of the caller's [K][M][H]
+    const size_t M = sc.local() ? (size_t)s->ctx->d.M : 1;
+    std::vector<double> wk((size_t)sc.K * H * M), wk_on;
+    if (sc.triggered()) {                             // the on pair's, by the same rounded multiply
+        wk_on.resize(wk.size());
+        for (int k = 0; k < sc.K; ++k)
+            for (size_t m = 0; m < M; ++m)
+                for (int h = 0; h < H; ++h)
+                    wk_on[((size_t)k * H + h) * M + m] = s->fc_W_host[h] * sc.commute_on[((size_t)k * M + m) * H + h];
+        HIP_TRY(hipMemcpyAsync(sc.Wk_on, wk_on.data(), sizeof(double) * wk_on.size(), hipMemcpyHostToDevice, st));
+        if (int rc = acc_zero(sc.tacc, st)) return rc;
+        acc_invalidate(sc.tacc);
+        for (int slot = 0; slot < 2; ++slot)
+            if (s->fc.acc.valid[slot])
+                if (int rc = acc_shadow(sc.tacc, slot, true, st)) return rc;
+    }
+    if (sc.local()) {                                 // [K][H][M] out of the caller's [K][M][H]
         for (int k = 0; k < sc.K; ++k)
             for (size_t m = 0; m < M; ++m)
                 for (int h = 0; h < H; ++h)
@@ -4415,7 +4456,7 @@ static int scenarios_begin(seir_sampler *s) {
         for (int k = 0; k < sc.K; ++k)
             for (int h = 0; h < H; ++h) wk[(size_t)k * H + h] = s->fc_W_host[h] * sc.commute[(size_t)k * H + h];
     }
-    HIP_TRY(hipMemcpyAsync(sc.local ? sc.Wk_loc : sc.Wk, wk.data(), sizeof(double) * wk.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(sc.local() ? sc.Wk_loc : sc.Wk, wk.data(), sizeof(double) * wk.size(), hipMemcpyHostToDevice, st));
     if (int rc = acc_zero(sc.acc, st)) return rc;
     acc_invalidate(sc.acc);
     for (int slot = 0; slot < 2; ++slot)
@@ -4453,7 +4494,9 @@ static int scenarios_batch(seir_sampler *s, const ForecastBufs &fb, const Rollou
     const int B = s->cfg.B, H = fb.H, K = sc.K, ND = bt.ND, ndp = bt.ndp;
     const long long j = s->fc.acc.j + bt.j0;        // the batch's first draw position
     const ScenarioBufs sb{K, sc.log_shift, sc.Wk, sc.St, sc.X, sc.F, sc.base, sc.sev};
-    if (sc.local) {
+    if (sc.triggered()) {
+        scenarios_trigger_rollout(s, l, fb, sb, bt, first, (int)j);
+    } else if (sc.local()) {
         scenarios_local_rollout(s, l, fb, sb, bt, (int)j);
     } else {
         // a variable, so that the begin is named -- and emitted -- in front of the day kernel; it also writes the base plane's H rows
@@ -4481,6 +4524,7 @@ static int scenarios_batch(seir_sampler *s, const ForecastBufs &fb, const Rollou
         if (sc.gG)                                   // the region totals of the slice, by draw position (zeroed by the call)
             groups_launch(d, l.st, s->grp, false, fk.fev, d.M, H, 0, ((long long)k * sc.cap + j) * B, ND, sc.gstore.as<int64_t>(),
                           nullptr, 0, 0, nullptr);
+        if (sc.triggered()) scenarios_trigger_fold(s, l, bt, k, j);
     }
     return 0;
 }
@@ -4491,8 +4535,18 @@ static int scenarios_on(seir_sampler *s) {
     return 0;
 }
 
-// What is behind seir_sampler_scenarios_set (local = false: arrays [K][H]) and seir_sampler_scenarios_set_local ([K][M][H]).
-static int scenarios_set(seir_sampler *s, int32_t K, const double *log_shift, const double *commute, int64_t cap, bool local) {
+// The on pair and the rule of seir_sampler_scenarios_set_triggered, next to the off pair that every face gives.
+struct TriggerArgs {
+    const double *log_shift_on, *commute_on;         // [K][M][H]
+    const int32_t *on, *off;                         // [K][M]
+    const int32_t *params;                           // [K][4] window, from_day, min_days, review_every
+};
+
+// What is behind seir_sampler_scenarios_set (GLOBAL: arrays [K][H]), seir_sampler_scenarios_set_local (LOCAL: [K][M][H]) and
+// seir_sampler_scenarios_set_triggered (TRIGGERED: LOCAL's tensors as the off pair, and `trig`).
+static int scenarios_set(seir_sampler *s, int32_t K, const double *log_shift, const double *commute, int64_t cap,
+                         ScenarioSet::Mode mode, const TriggerArgs *trig = nullptr) {
+    const bool local = mode != ScenarioSet::GLOBAL, triggered = mode == ScenarioSet::TRIGGERED;
     int rc = sampler_check(s);
     if (rc) return rc;
     if ((rc = trace_range_check(s, s->fc.on, FORECAST_USER))) return rc;
@@ -4508,6 +4562,8 @@ static int scenarios_set(seir_sampler *s, int32_t K, const double *log_shift, co
         return fail(SEIR_ERR_STATE, "%lld draws per chain have been forecast since the reset: scenarios are set between "
                     "seir_sampler_forecast_reset and the first seir_sampler_forecast", s->fc.acc.j);
     if (!log_shift || !commute) return fail(SEIR_ERR_INVALID, "null pointer");
+    if (triggered && (!trig->log_shift_on || !trig->commute_on || !trig->on || !trig->off || !trig->params))
+        return fail(SEIR_ERR_INVALID, "null pointer");
     const Dims &d = s->ctx->d;
     const int H = s->fc.fb.H;
     const size_t Ml = local ? (size_t)d.M : 1, nop = (size_t)K * Ml * H;
@@ -4522,6 +4578,27 @@ static int scenarios_set(seir_sampler *s, int32_t K, const double *log_shift, co
         if (!std::isfinite(commute[i]) || commute[i] < 0.0)
             return fail(SEIR_ERR_INVALID, "commute[%d][%d]=%g: finite and >= 0", i / H, i % H, commute[i]);
     }
+    int wmax = 0;
+    for (size_t i = 0; i < nop && triggered; ++i) {
+        const int k = (int)(i / (Ml * H)), m = (int)(i / H % Ml), h = (int)(i % H);
+        if (!std::isfinite(trig->log_shift_on[i])) return fail(SEIR_ERR_INVALID, "log_shift_on[%d][%d][%d] is not finite", k, m, h);
+        if (!std::isfinite(trig->commute_on[i]) || trig->commute_on[i] < 0.0)
+            return fail(SEIR_ERR_INVALID, "commute_on[%d][%d][%d]=%g: finite and >= 0", k, m, h, trig->commute_on[i]);
+    }
+    for (int k = 0; k < K && triggered; ++k) {
+        const int32_t *p = trig->params + 4 * k;
+        if (p[0] < 1 || p[0] > SEIR_TRIGGER_MAX_WINDOW)
+            return fail(SEIR_ERR_INVALID, "params[%d][0]=%d: the window is in [1, %d]", k, p[0], SEIR_TRIGGER_MAX_WINDOW);
+        if (p[1] < 0 || p[1] > H) return fail(SEIR_ERR_INVALID, "params[%d][1]=%d: from_day is in [0, %d]", k, p[1], H);
+        if (p[2] < 0) return fail(SEIR_ERR_INVALID, "params[%d][2]=%d: min_days is >= 0", k, p[2]);
+        if (p[3] < 1) return fail(SEIR_ERR_INVALID, "params[%d][3]=%d: review_every is >= 1", k, p[3]);
+        wmax = std::max(wmax, (int)p[0]);
+        for (int m = 0; m < d.M; ++m) {
+            const int32_t on = trig->on[(size_t)k * d.M + m], off = trig->off[(size_t)k * d.M + m];
+            if (off < 0 || off > on)
+                return fail(SEIR_ERR_INVALID, "on[%d][%d]=%d, off[%d][%d]=%d: 0 <= off <= on", k, m, on, k, m, off);
+        }
+    }
     if ((rc = drain(s))) return rc;
     s->scen = ScenarioSet{};                         // what was set before goes first; a refusal leaves the forecast without scenarios
     const size_t B = (size_t)s->cfg.B, capT = (size_t)s->cfg.cap, Kz = (size_t)K, ndmax = (size_t)s->fc.ndmax;
@@ -4533,17 +4610,31 @@ static int scenarios_set(seir_sampler *s, int32_t K, const double *log_shift, co
     // a local set has the two [K][H][M] tensors in the place of the two arrays and the base plane; the region totals' store
     // is part of the sum while its switch is on and a table is in force
     const unsigned long long gbytes = scenario_groups_bytes(s, K, cap, s->grp_on ? s->grp.G : 0, H);
+    // a triggered set adds the on pair, the thresholds and parameters, hist, the three planes (win, age, the two mask words) and
+    // its two outputs
+    const size_t tacc_bytes = Kz * B * d.M * H * sizeof(uint32_t);
+    const unsigned long long tbytes = !triggered ? 0ull :
+        8ull * 2 * nop + 4ull * (2 * Kz * d.M + 4 * Kz) + 4ull * (size_t)wmax * d.Mp * ndmax + (4ull + 4ull + 16ull) * plane +
+        tacc_bytes + 4ull * Kz * (unsigned long long)cap * B * H;
     const unsigned long long bytes = 8ull * (local ? 2 * nop + 2 * plane : 2 * Kz * H + 2 * plane + Kz * H * ndmax) +
                                      4ull * (3 * plane + Kz * ndm * d.M * H * 3) +
                                      8ull * Kz * capT * B * (2ull * H + d.M) * 3 + 16ull * Kz * (unsigned long long)cap * B * H * 3 +
-                                     acc_bytes + gbytes;
+                                     acc_bytes + gbytes + tbytes;
     if ((rc = refuse_above_half_free(bytes, "the scenarios need %llu bytes (%d scenarios x %zu chains x %d locations x %d days, stores of "
                                             "%lld draws)", bytes, K, B, d.M, H, (long long)cap)))
         return rc;
 #define SC_ALLOC(ptr, ...) if (!rc) rc = s_alloc(s, sc.allocs, &(ptr), __VA_ARGS__)
-    sc.local = local;
+    sc.mode = mode;
     if (local) {
         SC_ALLOC(sc.log_shift_loc, nop); SC_ALLOC(sc.Wk_loc, nop);
+        if (triggered) {
+            sc.wmax = wmax;
+            SC_ALLOC(sc.log_shift_on, nop); SC_ALLOC(sc.Wk_on, nop);
+            SC_ALLOC(sc.trig_on, Kz * d.M); SC_ALLOC(sc.trig_off, Kz * d.M); SC_ALLOC(sc.trig_params, 4 * Kz);
+            SC_ALLOC(sc.hist, (size_t)wmax * d.Mp * ndmax);
+            SC_ALLOC(sc.win, plane); SC_ALLOC(sc.age, plane); SC_ALLOC(sc.mask, 2 * plane);
+            SC_ALLOC(sc.active_by_day, Kz * (size_t)cap * B * H);
+        }
     } else {
         SC_ALLOC(sc.log_shift, Kz * H); SC_ALLOC(sc.Wk, Kz * H);
         SC_ALLOC(sc.base, Kz * H * ndmax);
@@ -4557,6 +4648,7 @@ static int scenarios_set(seir_sampler *s, int32_t K, const double *log_shift, co
     SC_ALLOC(sc.by_day, Kz * (size_t)cap * B * H * 3); SC_ALLOC(sc.state_by_day, Kz * (size_t)cap * B * H * 3);
 #undef SC_ALLOC
     if (!rc) rc = sc.acc.buf.zeroed(acc_bytes);
+    if (!rc && triggered) rc = sc.tacc.buf.zeroed(tacc_bytes);
     if (rc) return alloc_failed(bytes, "scenarios");
     sc.commute.assign(commute, commute + nop);
     if (local) {                                     // [K][H][M] out of the caller's [K][M][H]
@@ -4565,6 +4657,16 @@ static int scenarios_set(seir_sampler *s, int32_t K, const double *log_shift, co
             for (size_t m = 0; m < Ml; ++m)
                 for (int h = 0; h < H; ++h) ls[((size_t)k * H + h) * Ml + m] = log_shift[((size_t)k * Ml + m) * H + h];
         HIP_TRY(hipMemcpy(sc.log_shift_loc, ls.data(), sizeof(double) * nop, hipMemcpyHostToDevice));
+        if (triggered) {
+            sc.commute_on.assign(trig->commute_on, trig->commute_on + nop);
+            for (int k = 0; k < K; ++k)
+                for (size_t m = 0; m < Ml; ++m)
+                    for (int h = 0; h < H; ++h) ls[((size_t)k * H + h) * Ml + m] = trig->log_shift_on[((size_t)k * Ml + m) * H + h];
+            HIP_TRY(hipMemcpy(sc.log_shift_on, ls.data(), sizeof(double) * nop, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(sc.trig_on, trig->on, sizeof(int32_t) * Kz * d.M, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(sc.trig_off, trig->off, sizeof(int32_t) * Kz * d.M, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(sc.trig_params, trig->params, sizeof(int32_t) * 4 * Kz, hipMemcpyHostToDevice));
+        }
     } else {
         HIP_TRY(hipMemcpy(sc.log_shift, log_shift, sizeof(double) * Kz * H, hipMemcpyHostToDevice));
     }
@@ -4574,12 +4676,55 @@ static int scenarios_set(seir_sampler *s, int32_t K, const double *log_shift, co
 }
 
 extern "C" int seir_sampler_scenarios_set(seir_sampler *s, int32_t K, const double *log_shift, const double *commute, int64_t cap) {
-    return scenarios_set(s, K, log_shift, commute, cap, false);
+    return scenarios_set(s, K, log_shift, commute, cap, ScenarioSet::GLOBAL);
 }
 
 extern "C" int seir_sampler_scenarios_set_local(seir_sampler *s, int32_t K, const double *log_shift, const double *commute,
                                                 int64_t cap) {
-    return scenarios_set(s, K, log_shift, commute, cap, true);
+    return scenarios_set(s, K, log_shift, commute, cap, ScenarioSet::LOCAL);
+}
+
+extern "C" int seir_sampler_scenarios_set_triggered(seir_sampler *s, int32_t K, const double *log_shift, const double *commute,
+                                                    const double *log_shift_on, const double *commute_on, const int32_t *on,
+                                                    const int32_t *off, const int32_t *params, int64_t cap) {
+    const TriggerArgs trig{log_shift_on, commute_on, on, off, params};
+    return scenarios_set(s, K, log_shift, commute, cap, ScenarioSet::TRIGGERED, &trig);
+}
+
+static int scenario_triggers_on(seir_sampler *s) {
+    if (int rc = scenarios_on(s)) return rc;
+    if (!s->scen.triggered())
+        return fail(SEIR_ERR_STATE, "the scenarios in force have no triggers: call seir_sampler_scenarios_set_triggered first");
+    return 0;
+}
+
+extern "C" int seir_sampler_read_scenario_triggers(seir_sampler *s, uint32_t *active_count) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = scenario_triggers_on(s))) return rc;
+    if (!active_count) return fail(SEIR_ERR_INVALID, "null output pointer");
+    hipStream_t st = s->ctx->stream;
+    HIP_TRY(hipMemcpyAsync(active_count, s->scen.tacc.buf.p, s->scen.tacc.buf.bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int seir_sampler_read_scenario_trigger_draws(seir_sampler *s, int64_t first, int64_t count, int32_t *active_by_day) {
+    int rc = sampler_check(s);
+    if (rc) return rc;
+    if ((rc = scenario_triggers_on(s))) return rc;
+    const ScenarioSet &sc = s->scen;
+    if (first < 0 || count < 0 || first + count > s->fc.acc.j)
+        return fail(SEIR_ERR_INVALID, "draw positions [%lld,%lld) outside the %lld draws per chain forecast since the reset",
+                    (long long)first, (long long)(first + count), s->fc.acc.j);
+    if (count && !active_by_day) return fail(SEIR_ERR_INVALID, "null output pointer");
+    hipStream_t st = s->ctx->stream;
+    const size_t row = sc.B * (size_t)s->fc.fb.H, n = (size_t)count * row;
+    for (int k = 0; k < sc.K && n; ++k)
+        HIP_TRY(hipMemcpyAsync(active_by_day + (size_t)k * n, sc.active_by_day + ((size_t)k * sc.cap + (size_t)first) * row,
+                               sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
 }
 
 // ---- the scenarios' region totals ----
@@ -4917,6 +5062,92 @@ extern "C" int seir_pair_abs_sums(seir_ctx *ctx, const int32_t *values, int64_t 
     a.values = dv.as<int32_t>();
     a.cells = cells; a.segs = segs; a.seg_len = seg_len; a.seg_stride = seg_stride; a.cell_stride = cell_stride;
     return pair_abs_run(ctx, a, out, overflow);
+}
+
+// ---------------------------------------------------------------------------
+// Triggered scenarios: the launches of a triggered set and the fold of its masks (declared above, with the scenarios;
+// kernels: scenario_trigger_kernels.h).  The header is included here, so that its kernels lie behind every kernel the parent had
+// but the local set's pair: those two stay the last of the code object (they are emitted where scenarios_local_rollout, below,
+// names them), and every other kernel keeps its address.
+// ---------------------------------------------------------------------------
+#include "scenario_trigger_kernels.h"
+
+static_assert(TRIGGER_MAX_WINDOW == SEIR_TRIGGER_MAX_WINDOW, "the header's bound is the kernels'");
+
+static void scenarios_trigger_rollout(seir_sampler *s, const LaunchCfg &l, const ForecastBufs &fb, const ScenarioBufs &sb,
+                                      const RolloutBatch &bt, int32_t first, int j) {
+    const ScenarioSet &sc = s->scen;
+    const ScenarioLocalBufs lb{sc.log_shift_loc, sc.Wk_loc};
+    const ScenarioTriggerBufs tb{sc.log_shift_on, sc.Wk_on, sc.trig_on, sc.trig_off, sc.trig_params, sc.wmax,
+                                 sc.hist,         sc.win,   sc.age,     sc.mask};
+    scenarios_rollout_with(s->ctx, l, fb, sb, bt, (size_t)l.d.Mp * bt.ndp, [&](dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(s->cfg.ev16 ? k_trigger_begin<1> : k_trigger_begin<0>, grid, block, 0, l.st, l.d, s->ctx->c, fb, sb, tb,
+                           (const void *)s->ch.tr_events, s->cfg.B, first + bt.j0, bt.ND, bt.ndp);
+    }, [&](dim3 grid, dim3 block, int h) {
+        hipLaunchKernelGGL(k_scenario_trigger_day<FC_DAY_ROWS>, grid, block, 0, l.st, l.d, s->ctx->c, fb, sb, lb, tb, s->cfg.B,
+                           s->cfg.chain0, j, bt.ND, bt.ndp, h);
+    });
+}
+
+// The masks of nj draws per chain into a count block [B][M][H] and the curves of nj draw positions [nj][B][H].
+static void trigger_fold_launch(const Dims &d, hipStream_t st, const uint64_t *mask, size_t plane, size_t stride, size_t col0,
+                                uint32_t *count, int32_t *by_day, int M, int H, int B, int nj, bool fresh) {
+    hipLaunchKernelGGL(k_trigger_fold<TRIG_U>, dim3((M + TRIG_ROWS - 1) / TRIG_ROWS + (nj + TRIG_ROWS - 1) / TRIG_ROWS, B),
+                       dim3(64 * TRIG_ROWS), 0, st, d, mask, plane, stride, col0, count, by_day, M, H, B, nj, fresh ? 1 : 0);
+}
+
+static void scenarios_trigger_fold(seir_sampler *s, const LaunchCfg &l, const RolloutBatch &bt, int k, long long j) {
+    const ScenarioSet &sc = s->scen;
+    const Dims &d = l.d;
+    const int B = s->cfg.B, H = s->fc.fb.H;
+    const size_t ndk = (size_t)sc.K * bt.ndp;
+    trigger_fold_launch(d, l.st, sc.mask, (size_t)d.Mp * ndk, ndk, (size_t)k * bt.ndp,
+                        sc.tacc.buf.as<uint32_t>() + (size_t)k * B * d.M * H,
+                        sc.active_by_day + ((size_t)k * sc.cap + (size_t)j) * B * H, d.M, H, B, bt.nj, j == 0);
+}
+
+extern "C" int seir_trigger_counts(seir_ctx *ctx, const uint64_t *masks, int64_t n, int32_t B, int32_t M, int32_t H, uint64_t folded,
+                                   uint32_t *active_count, int32_t *active_by_day) {
+    int rc = check_batch(ctx, 1);
+    if (rc) return rc;
+    if (!masks || !active_count || !active_by_day) return fail(SEIR_ERR_INVALID, "null pointer");
+    if (n < 1 || B < 1 || M < 1 || B > 65535)
+        return fail(SEIR_ERR_INVALID, "n=%lld, B=%d, M=%d: at least one of each, B at most 65535", (long long)n, B, M);
+    if (H < 1 || H > SEIR_FORECAST_MAX_H) return fail(SEIR_ERR_INVALID, "H=%d outside [1, %d]", H, SEIR_FORECAST_MAX_H);
+    if (folded > 0xffffffffull || folded + (uint64_t)n > 0xffffffffull)
+        return fail(SEIR_ERR_INVALID, "%llu draws per chain folded and %lld more: the counts hold 2^32 - 1",
+                    (unsigned long long)folded, (long long)n);
+    // a launch's planes [2][M][ndp], the draw index nd = jj B + b contiguous as in the sampler's batches
+    const int njmax = (int)std::min<int64_t>(n, SC_JMAX);
+    const size_t ndp = (size_t)ceil_to(njmax * B, 64), plane = (size_t)M * ndp, cells = (size_t)B * M * H;
+    const unsigned long long bytes = 16ull * plane + 4ull * cells + 4ull * (unsigned long long)n * B * H;
+    if ((rc = refuse_above_half_free(bytes, "the trigger counts need %llu bytes (%lld draws x %d chains x %d locations x %d days)",
+                                     bytes, (long long)n, B, M, H)))
+        return rc;
+    DevBuf dmask, dcount, dby;
+    if ((rc = dmask.alloc(16 * plane)) || (rc = dcount.alloc(4 * cells)) || (rc = dby.alloc(4 * (size_t)n * B * H))) return rc;
+    hipStream_t st = ctx->stream;
+    if (folded) HIP_TRY(hipMemcpyAsync(dcount.p, active_count, 4 * cells, hipMemcpyHostToDevice, st));
+    const Dims d = whole(ctx, 1).d;
+    std::vector<uint64_t> host(2 * plane);
+    for (int64_t j0 = 0; j0 < n; j0 += SC_JMAX) {
+        const int nj = (int)std::min<int64_t>(SC_JMAX, n - j0);
+        std::fill(host.begin(), host.end(), 0ull);
+        for (int jj = 0; jj < nj; ++jj)                // [n][B][M][2] into [2][M][ndp]
+            for (int b = 0; b < B; ++b)
+                for (int m = 0; m < M; ++m)
+                    for (int x = 0; x < 2; ++x)
+                        host[(size_t)x * plane + (size_t)m * ndp + (size_t)jj * B + b] = masks[((((size_t)j0 + jj) * B + b) * M + m) * 2 + x];
+        HIP_TRY(hipMemcpyAsync(dmask.p, host.data(), 16 * plane, hipMemcpyHostToDevice, st));
+        trigger_fold_launch(d, st, dmask.as<uint64_t>(), plane, ndp, 0, dcount.as<uint32_t>(), dby.as<int32_t>() + (size_t)j0 * B * H, M,
+                            H, B, nj, folded == 0 && j0 == 0);
+        HIP_TRY(hipStreamSynchronize(st));             // host is filled again
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(active_count, dcount.p, 4 * cells, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(active_by_day, dby.p, 4 * (size_t)n * B * H, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
 }
 
 // ---------------------------------------------------------------------------

@@ -136,6 +136,7 @@ def _load():
     fn("H5Eset_auto2", c_int, hid_t, c_void_p, c_void_p)
     lib.H5Eset_auto2(0, None, None)                  # errors are reported through return codes
     for name in ("H5T_NATIVE_DOUBLE_g", "H5T_NATIVE_INT32_g", "H5T_NATIVE_INT8_g", "H5T_NATIVE_INT64_g", "H5T_NATIVE_UINT8_g",
+                 "H5T_NATIVE_UINT32_g",
                  "H5T_C_S1_g", "H5P_CLS_DATASET_CREATE_ID_g", "H5P_CLS_LINK_CREATE_ID_g"):
         _ids[name] = hid_t.in_dll(lib, name).value
     _lib = lib
@@ -182,7 +183,8 @@ def _check(rc, what):
 
 _NATIVE = {np.dtype("float64"): "H5T_NATIVE_DOUBLE_g", np.dtype("int32"): "H5T_NATIVE_INT32_g",
            np.dtype("int8"): "H5T_NATIVE_INT8_g", np.dtype("int64"): "H5T_NATIVE_INT64_g",
-           np.dtype("uint8"): "H5T_NATIVE_UINT8_g"}       # uint8: masks such as scenarios/locations (read back as int64, as every integer)
+           np.dtype("uint8"): "H5T_NATIVE_UINT8_g",       # uint8: masks such as scenarios/locations (read back as int64, as every integer)
+           np.dtype("uint32"): "H5T_NATIVE_UINT32_g"}     # uint32: counts of draws such as scenarios/active_count
 
 
 def _dims(shape):

@@ -673,6 +673,7 @@ def forecast_record(ctx):
                                                           ctx.opt.fq_probs)
     if not horizon:
         return None
+    from ..posterior import scenarios as SC_mod
     sc, base_by_day, grp_by_day, writes = ctx.scenarios, [], [], _writes(ctx, "forecast")
     vf = getattr(ctx, "verify", None)                       # the later data the forecast is scored against, or None
     grp_sc = bool(sc) and getattr(ctx, "grp_sc_on", False)   # the scenarios' region totals (Mcmc.groups_scenarios)
@@ -681,8 +682,11 @@ def forecast_record(ctx):
         s.reset_forecast(horizon, ctx.forecast_calendar[0], ctx.forecast_calendar[1], ctx.seed)   # once: the sampling phase
         if fq_probs:
             s.keep_forecast_draws(total)                    # the draw store of the quantiles: every kept draw of the phase
-        if sc:
+        if sc and SC_mod.is_triggered(sc):                  # a specification with a trigger: the whole set through the triggered entry
+            s.set_scenarios(sc.log_shift, sc.commute, total, triggers=sc.trigger_args())
+        elif sc:
             s.set_scenarios(sc.log_shift, sc.commute, total)   # once, behind the reset and the draw store: they ride from now on
+        if sc:
             if grp_sc:
                 s.set_scenario_groups(True)                 # right behind the set: the table is in force since groups_record was built
         if vf is not None:
@@ -815,7 +819,13 @@ def scenarios_write_up(ctx, sc, base_by_day, base_by_group=None):
     the row differs from the identity.  With Mcmc.groups_scenarios (`base_by_group` [n,B,G,H,3], the forecast's samples/forecast_by_group)
     one read of the scenarios' group store: samples/scenario_by_group [n,K,G,H,3] and scenario_diff_by_group, the scenario's totals
     minus the forecast's, formed here; with forecast_quantiles scenarios/group_diff_quantiles [Kq,K,G,H,3]; one log line per scenario
-    and group."""
+    and group.
+    A specification with a trigger (`posterior.scenarios.TriggeredScenarios`) makes two more reads, the record of the rule, and
+    writes the rule -- scenarios/trigger_on, trigger_off [K,M] int32, trigger_window, _from_day, _min_days, _review_every [K], the
+    on pair log_shift_on_by_location, commute_on_by_location [K,M,H] -- scenarios/active_count [K,M,H] uint32 (the draws in which
+    the location is under the measure on the day: pooling over files is a sum), p_active = active_count / count,
+    samples/scenario_active_by_day [n,K,H] int32 (the locations under the measure) and, with forecast_quantiles,
+    scenarios/active_by_day_quantiles [Kq,K,H]; one more log line per triggered scenario."""
     from ..posterior import scenarios as SC
     s, horizon = ctx.s, ctx.opt.horizon
     sums, diffs, draws = s.scenario_summary(), s.scenario_diffs(), s.read_scenario_draws()
@@ -825,6 +835,10 @@ def scenarios_write_up(ctx, sc, base_by_day, base_by_group=None):
     state = np.moveaxis(draws["state_by_day"], 0, 2)
     diff = by_day - np.asarray(base_by_day, np.int64)[:, :, None]
     local = SC.is_local(sc)
+    triggered = SC.is_triggered(sc)
+    if triggered:
+        active_count = s.scenario_triggers()["active_count"]                   # [K,B,M,H]
+        active_by_day = np.moveaxis(s.read_scenario_trigger_draws(), 0, 2)     # [n,B,K,H]
     by_group = diff_group = None
     if base_by_group is not None:
         by_group = np.moveaxis(s.read_scenario_group_draws(), 0, 2)            # [n,B,K,G,H,3]
@@ -859,9 +873,23 @@ def scenarios_write_up(ctx, sc, base_by_day, base_by_group=None):
                 post.create_dataset(f"samples/{key}", np.ascontiguousarray(v[:, c]), dtype=np.int64)
             if ctx.opt.fq_probs and n:
                 post.create_dataset("scenarios/group_diff_quantiles", draw_quantiles(diff_group[:, c], ctx.opt.fq_probs))
+        if triggered:
+            for key, v in (("trigger_on", sc.trigger_on), ("trigger_off", sc.trigger_off), ("trigger_window", sc.window),
+                           ("trigger_from_day", sc.from_day), ("trigger_min_days", sc.min_days), ("trigger_review_every", sc.review_every)):
+                post.create_dataset(f"scenarios/{key}", v, dtype=np.int32)
+            post.create_dataset("scenarios/log_shift_on_by_location", sc.log_shift_on)
+            post.create_dataset("scenarios/commute_on_by_location", sc.commute_on)
+            post.create_dataset("scenarios/active_count", active_count[:, c], dtype=np.uint32)
+            if n:
+                post.create_dataset("scenarios/p_active", active_count[:, c] / n)
+            post.create_dataset("samples/scenario_active_by_day", np.ascontiguousarray(active_by_day[:, c]), dtype=np.int32)
+            if ctx.opt.fq_probs and n:
+                post.create_dataset("scenarios/active_by_day_quantiles", draw_quantiles(active_by_day[:, c], ctx.opt.fq_probs))
     for k, name in enumerate(sc.names):
         if n:
             print(SC.run_line(name, diff[:, :, k].reshape(-1, horizon, 3)), file=ctx.log, flush=True)
+        if n and triggered and sc.triggered[k]:
+            print(SC.trigger_run_line(name, active_by_day[:, :, k].reshape(-1, horizon)), file=ctx.log, flush=True)
         for g in range(ctx.groups.G if by_group is not None and n else 0):
             print(SC.group_run_line(name, ctx.groups.names[g], diff_group[:, :, k, g].reshape(-1, horizon, 3)), file=ctx.log, flush=True)
 
@@ -1094,7 +1122,7 @@ def product_records(sampler, config, posteriors, log=sys.stderr, forecast_calend
     scenarios = resolve_scenarios(config, opt.horizon)      # Mcmc.scenarios: a resolution of its own; empty when the key is absent
     # a targeted specification's members to rows (`location_names`: the input's codes, a callable that reads them, or None), and
     # Mcmc.groups_scenarios held to scenarios and groups -- both before the first call on the sampler
-    scenarios = bind_scenarios(scenarios, getattr(sampler, "M", 0), location_names)
+    scenarios = bind_scenarios(scenarios, getattr(sampler, "M", 0), location_names, population)
     grp_sc_on = resolve_scenario_groups(config, scenarios, groups)
     if resolve_verify(config, opt.horizon) is not None and verify is None:   # Mcmc.verify likewise; `verify`: posterior.verify.Truth
         raise ValueError("verify: run_mcmc needs verify = posterior.verify.load_truth(path, data_file, horizon)")
@@ -1340,7 +1368,7 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     # ... and the members of a targeted scenario against the same codes (read once, and only when a member is a code or a pattern)
     from ..posterior.scenarios import PendingScenarios
     codes = functools.lru_cache(maxsize=None)(lambda: read_location_names(data_file)) if isinstance(pending, PendingScenarios) else None
-    bind_scenarios(pending, cases.shape[0], codes)
+    bind_scenarios(pending, cases.shape[0], codes, cov.N)   # ... and a trigger's per-100k thresholds against the populations
     cfg = event_kernel_config(config)
     num_samples = warmup_size() + int(config["num_burst_samples"]) * int(config["num_bursts"])
     cap = max(800, 2 * int(config["num_burst_samples"]))      # two halves: a burst runs while the previous one is written
@@ -1378,6 +1406,9 @@ def mcmc(data_file, output_file, config, seed=0, num_chains=1, device=None, pool
     fc_kw = product_inputs(cov, dates, T, opt, seed, group_table)
     if codes is not None:
         fc_kw["location_names"] = codes
+    from ..posterior.scenarios import is_triggered
+    if is_triggered(pending):
+        fc_kw.setdefault("population", np.asarray(cov.N, dtype=np.float64).reshape(-1))
     if group_table is not None:
         for post in posteriors:
             post.write_groups(group_table, cov.N, initial_state)

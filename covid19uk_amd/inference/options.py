@@ -240,17 +240,22 @@ def resolve_scenarios(config, horizon, override=None):
     return parse_scenarios(config.get("scenarios") if override is None else override, horizon)
 
 
-def bind_scenarios(scenarios, M, location_names=None):
+def bind_scenarios(scenarios, M, location_names=None, populations=None):
     """Stage two of `resolve_scenarios`, before any GPU call: the members of a targeted specification to rows of the M
     locations (`location_names`: a callable that reads the input's location coordinate, or the codes themselves, or None; as
     for the groups, not called unless a member is a code or a pattern) -- an unknown code, a pattern that matches nothing and
-    an index out of range are refused here.  Anything else is returned as it is."""
+    an index out of range are refused here.  Anything else is returned as it is.
+    With a `trigger:` on any scenario `populations` [M] turns its per-100k thresholds into counts, here, where the driver holds
+    them: a threshold above INT32_MAX and a rate without populations are refused."""
     from ..posterior.scenarios import PendingScenarios, resolve_locations
     if not isinstance(scenarios, PendingScenarios):
         return scenarios
-    named = any(isinstance(x, str) for parts in scenarios.parts for members, _, _ in parts for x in members or ())
-    return resolve_locations(scenarios, M, location_names() if callable(location_names) and named else
-                             None if callable(location_names) else location_names)
+    named = any(isinstance(x, str) for parts in scenarios.parts for members, _, _ in parts for x in members or ()) or \
+        any(isinstance(x, str) for r in scenarios.rules if r is not None for x in r.members or ())
+    names = location_names() if callable(location_names) and named else None if callable(location_names) else location_names
+    if not scenarios.rules:
+        return resolve_locations(scenarios, M, names)
+    return resolve_locations(scenarios, M, names, populations)
 
 
 def resolve_scenario_groups(config, scenarios, group_spec, override=None):
@@ -395,7 +400,11 @@ def add_scenarios_argument(parser):
                              "paired differences to the forecast per location and day, samples/scenario_by_day, scenario_state_by_day, "
                              "scenario_diff_by_day; a scenario may carry locations: [codes, prefix patterns E0*, indices] or parts: a "
                              "list of {locations, transmission, commute, from_day} applied in order (a part without locations applies "
-                             "everywhere): a targeted scenario, whose commute scales the commuting-borne pressure on its locations")
+                             "everywhere): a targeted scenario, whose commute scales the commuting-borne pressure on its locations; "
+                             "a scenario may also carry trigger: {cases_per_100k | cases, release_per_100k | release, window, min_days, "
+                             "review_every, from_day, locations} and then: {transmission, commute}: a measure that switches on and off "
+                             "per draw and location by the draw's own simulated case counts -- scenarios/active_count, p_active, "
+                             "samples/scenario_active_by_day")
     parser.add_argument("--groups-scenarios", action="store_true", default=None, dest="groups_scenarios",
                         help="per-draw totals of every scenario over the groups of locations, formed on the device (overrides "
                              "Mcmc.groups_scenarios; needs --scenarios and --groups): samples/scenario_by_group, "

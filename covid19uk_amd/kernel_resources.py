@@ -61,6 +61,8 @@ OWNERS = {
     "replay": ("k_trace_load", "k_trace_load_theta"),             # stored draws into trace slots (trace_load_kernels.h)
     "scenarios": ("k_scenario_begin", "k_scenario_day", "k_scenario_diff"),   # scenarios riding on the forecast (scenario_kernels.h)
     "scenarios_local": ("k_scenario_local_begin", "k_scenario_local_day"),   # per-location operands (scenario_local_kernels.h)
+    # measures that switch on case counts (scenario_trigger_kernels.h)
+    "scenario_triggers": ("k_trigger_begin", "k_scenario_trigger_day", "k_trigger_fold"),
     "verify": ("k_verify_fold", "k_pair_abs"),                    # the forecast scored against later data (verify_kernels.h)
     # the event-update kernels for every m <= 4; their plain names (BASE) are the instances for m <= 2 (moves_kernel.h)
     "moves_m4": ("k_move_pairs_m4", "k_move_pair_m4", "k_move_pa2_m4", "k_move_delta_m4", "k_record_m4", "k_apply_fpend_m4"),

@@ -267,7 +267,7 @@ def replay_files(data_file, files, output_file, config, seed=0, device=None, fir
         import functools
         from .scenarios import PendingScenarios
         codes = functools.lru_cache(maxsize=None)(lambda: inf.read_location_names(data_file)) if isinstance(pending, PendingScenarios) else None
-        inf.bind_scenarios(pending, M, codes)
+        inf.bind_scenarios(pending, M, codes, cov.N)                     # ... and a trigger's per-100k thresholds
         # the initial state the draws were recorded from: the files' own, else the imputation of `seed` as `mcmc` forms it
         states = [src.initial_state() for src in sources]
         if states[0] is not None:
@@ -294,6 +294,9 @@ def replay_files(data_file, files, output_file, config, seed=0, device=None, fir
         posteriors = [inf.Posterior(name, M, T, cfg["m"], n, burst=ns, results=False, **inf.posterior_kwargs(config, opt, group_table, n))
                       for name in names]
         kw = inf.product_inputs(cov, dates, T, opt, seed, group_table)
+        from .scenarios import is_triggered
+        if is_triggered(pending):
+            kw.setdefault("population", np.asarray(cov.N, dtype=np.float64).reshape(-1))
         if group_table is not None:
             for post in posteriors:
                 post.write_groups(group_table, cov.N, initial_state)

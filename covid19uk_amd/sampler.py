@@ -869,20 +869,49 @@ class ChainSampler:
         return out
 
     # -- scenarios riding on the forecast (include/seir_hip.h, "Scenario forecasts on the device") ----------------
-    def set_scenarios(self, log_shift, commute, cap: int):
+    def set_scenarios(self, log_shift, commute, cap: int, triggers=None):
         """K scenarios ride on the forecast from now on: `log_shift` and `commute` float64 [K, H] (`posterior.scenarios`),
         `cap` the draws per chain the per-draw stores hold.  Between `reset_forecast` and the first `forecast`; K = 0 or
         cap = 0 frees everything.  The library refuses what it cannot hold; the forecast then runs on without scenarios.
         Arrays [K, M, H] are targeted scenarios, whose operands differ by location (include/seir_hip.h, "Targeted scenarios
-        on the device"; `posterior.scenarios.local_inputs`): they go through `seir_sampler_scenarios_set_local`."""
+        on the device"; `posterior.scenarios.local_inputs`): they go through `seir_sampler_scenarios_set_local`.
+        `triggers`: a mapping that makes the [K, M, H] arrays the off pair of triggered scenarios (include/seir_hip.h,
+        "Triggered scenarios on the device"; `posterior.scenarios.trigger_states`) -- `log_shift_on`, `commute_on` [K, M, H],
+        the thresholds `on`, `off` int32 [K, M] and `window`, `from_day`, `min_days`, `review_every` [K] -- through
+        `seir_sampler_scenarios_set_triggered`."""
         H = self._state().forecast_H
         ls = np.zeros((0, H)) if log_shift is None else np.ascontiguousarray(log_shift, dtype=np.float64)
         cm = np.ones((0, H)) if commute is None else np.ascontiguousarray(commute, dtype=np.float64)
+        if triggers is not None and ls.ndim != 3:
+            raise ValueError(f"log_shift {ls.shape}: triggered scenarios take the off pair as [K, {self.M}, {H}]")
         if ls.ndim == 3:
             if ls.shape != cm.shape or ls.shape[1] != self.M or (ls.shape[0] and H and ls.shape[2] != H):
                 raise ValueError(f"log_shift {ls.shape} and commute {cm.shape}: need two of [K, {self.M}, {H}]")
             if int(cap) < 0:
                 raise ValueError(f"cap={cap}: the number of draws per chain to keep")
+            if triggers is not None:
+                K = ls.shape[0]
+                lo = np.ascontiguousarray(triggers["log_shift_on"], dtype=np.float64)
+                co = np.ascontiguousarray(triggers["commute_on"], dtype=np.float64)
+                if lo.shape != ls.shape or co.shape != ls.shape:
+                    raise ValueError(f"log_shift_on {lo.shape} and commute_on {co.shape}: need two of {ls.shape}")
+                th = []
+                for key in ("on", "off"):
+                    v = np.asarray(triggers[key])
+                    if v.shape != (K, self.M) or (v.size and (v.min() < -2 ** 31 or v.max() > 2 ** 31 - 1)):
+                        raise ValueError(f"triggers[{key!r}] {v.shape}: int32 [{K}, {self.M}]")
+                    th.append(np.ascontiguousarray(v, dtype=np.int32))
+                par = np.empty((K, 4), np.int32)
+                for i, key in enumerate(("window", "from_day", "min_days", "review_every")):
+                    v = np.asarray(triggers[key])
+                    if v.shape != (K,) or (v.size and (v.min() < -2 ** 31 or v.max() > 2 ** 31 - 1)):
+                        raise ValueError(f"triggers[{key!r}] {v.shape}: int32 [{K}]")
+                    par[:, i] = v
+                ip = ctypes.POINTER(ctypes.c_int32)
+                _lib.check(self._lib.seir_sampler_scenarios_set_triggered(
+                    self._s, K, _dptr(ls), _dptr(cm), _dptr(lo), _dptr(co), th[0].ctypes.data_as(ip), th[1].ctypes.data_as(ip),
+                    par.ctypes.data_as(ip), int(cap)))
+                return
             _lib.check(self._lib.seir_sampler_scenarios_set_local(self._s, ls.shape[0], _dptr(ls), _dptr(cm), int(cap)))
             return
         if ls.ndim != 2 or ls.shape != cm.shape or (ls.shape[0] and H and ls.shape[1] != H):   # H = 0: the library refuses
@@ -904,6 +933,25 @@ class ChainSampler:
         n = st["j"] - int(first) if count is None else int(count)
         out = np.empty((st["K"], max(n, 0), self.B, G, st["H"], 3), np.int64)
         _lib.check(self._lib.seir_sampler_read_scenario_group_draws(self._s, int(first), n, out.ctypes.data_as(_lib.c_int64_p)))
+        return out
+
+    def scenario_triggers(self) -> dict:
+        """The record of the triggered scenarios' rules folded since the last `reset_forecast` (blocking): `count` (draws per
+        chain) and `active_count` uint32 [K, B, M, H], the draws of chain b in which location m is under the measure on day s.
+        Refused unless the set in force is a triggered one."""
+        st = self.scenario_state()
+        out = np.empty((st["K"], self.B, self.M, st["H"]), np.uint32)
+        _lib.check(self._lib.seir_sampler_read_scenario_triggers(self._s, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
+        return dict(count=st["j"], active_count=out)
+
+    def read_scenario_trigger_draws(self, count: int = None, first: int = 0) -> np.ndarray:
+        """The number of locations under the measure by draw position since the forecast reset (blocking): int32
+        [K, count, B, H]; `count` None: every draw from `first` on."""
+        st = self.scenario_state()
+        n = st["j"] - int(first) if count is None else int(count)
+        out = np.empty((st["K"], max(n, 0), self.B, st["H"]), np.int32)
+        _lib.check(self._lib.seir_sampler_read_scenario_trigger_draws(self._s, int(first), n,
+                                                                      out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
         return out
 
     def scenario_state(self) -> dict:

@@ -387,6 +387,29 @@ class SeirModel:
         out["overflow"] = bool(ovf[0])
         return out
 
+    def trigger_counts(self, masks, H, acc=None):
+        """The fold of a triggered scenario's record on the device (csrc/scenario_trigger_kernels.h; include/seir_hip.h,
+        seir_trigger_counts): `masks` uint64 [n, B, M, 2], bit s of a cell's 128 set iff the location is under the measure on
+        day s in that draw; `H` the days counted.  `acc`: what an earlier call returned, to fold these draws behind its own, or
+        None.  Returns a dict: `count` (draws per chain folded), `active_count` uint32 [B, M, H] and `active_by_day` int32
+        [n, B, H] of this call's draws -- the integers of `posterior.scenarios.fold_triggers`."""
+        mk = np.ascontiguousarray(masks, dtype=np.uint64)
+        if mk.ndim != 4 or mk.shape[3] != 2:
+            raise ValueError(f"masks {mk.shape}: need [n, B, M, 2]")
+        n, B, M, _ = mk.shape
+        H = int(H)
+        if acc is None:
+            folded, cnt = 0, np.zeros((B, M, max(H, 0)), np.uint32)
+        else:
+            folded, cnt = int(acc["count"]), np.array(acc["active_count"], dtype=np.uint32, order="C")
+            if cnt.shape != (B, M, H):
+                raise ValueError(f"acc['active_count'] {cnt.shape}: these masks need {(B, M, H)}")
+        by_day = np.zeros((n, B, max(H, 0)), np.int32)
+        _lib.check(self._lib.seir_trigger_counts(
+            self._ctx, mk.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), n, B, M, H, folded,
+            cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), by_day.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+        return dict(count=folded + n, active_count=cnt, active_by_day=by_day)
+
     def group_wsums(self, v, offsets, members, weights=None):
         """Group sums of fp64 values on the device (csrc/group_curve_kernels.h; include/seir_hip.h, seir_group_wsums): `v`
         float64 [nd, L, M] (L and M the array's own), the groups a CSR pair as for `group_sums`, `weights` [nnz] aligned with

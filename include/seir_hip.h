@@ -1182,7 +1182,7 @@ int seir_scenario_diffs(seir_ctx *ctx, const int32_t *base_events, const int32_t
  * common random numbers couple a targeted scenario to the baseline variate by variate.  Tensors that are constant over m
  * give bit for bit what seir_sampler_scenarios_set gives with the [K][H] arrays.
  * A local commute scales the commuting-borne pressure ON location m (the psi W F term of its hazard); it does not scale
- * what m exports.  A symmetric travel ban changes Cstar and is out of scope, as are state-dependent policies.
+ * what m exports.  A symmetric travel ban changes Cstar and is out of scope.
  * Launches: per batch one begin launch and, per day, the contraction and one day launch over K ndp columns, as for a
  * global set; a wave reads its two operands by scalar loads.  Device bytes: 2 x K x M x H x 8 in the place of the global
  * set's 2 x K x H x 8 and its base plane K x H x ndmax x 8.
@@ -1209,6 +1209,51 @@ int seir_sampler_scenario_groups_set(seir_sampler *s, int32_t on);
  * layout of seir_sampler_read_group_marginals' events_by_group per scenario.  SEIR_ERR_STATE while no scenarios are set or
  * the store is off; SEIR_ERR_INVALID for positions outside the draws forecast since the reset. */
 int seir_sampler_read_scenario_group_draws(seir_sampler *s, int64_t first, int64_t count, int64_t *by_group);
+
+/* ------------------------------------------------------------------------
+ * Triggered scenarios on the device: measures that switch on and off by the draw's own simulated case counts.  It extends
+ * "Targeted scenarios on the device" above; with none of its entry points called every call and every bit is as before.
+ *
+ * A triggered scenario k is a targeted scenario with two operand pairs per (m, s) -- the off pair log_shift, commute and the
+ * on pair log_shift_on, commute_on, each under the targeted tensors' refusals -- and a rule that picks one of them per draw
+ * and day (THE definition: csrc/scenario_trigger_kernels.h and csrc/trigger_update.h; in NumPy:
+ * covid19uk_amd/posterior/scenarios.py, trigger_states and triggered_inputs).  Per scenario the rule has window w in
+ * [1, SEIR_TRIGGER_MAX_WINDOW], from_day in [0, H], min_days >= 0 and review_every >= 1, per location the integer thresholds
+ * 0 <= off[k][m] <= on[k][m] <= INT32_MAX (on = INT32_MAX: the location never triggers).  At the start of rollout day s, per
+ * (k, m, draw): c = the sum of the I->R counts of the w days before absolute day T + s (scenario k's own simulated counts
+ * for days >= T, the draw's recorded counts for days in [0, T), 0 before day 0); on a review day (s >= from_day and
+ * (s - from_day) % review_every == 0): not active and c >= on: active <- 1, age <- 0; otherwise active and age >= min_days and
+ * c < off: active <- 0.  Day s is rolled with the on pair iff active; behind it, if active, age <- age + 1.  At day 0
+ * active = 0.  The day is the targeted scenario's with the selected operands: one rounded add, one rounded multiply either
+ * way, so a rule that never fires is bit for bit the targeted scenario with the off tensors and a rule that fires everywhere
+ * at day 0 and never releases the targeted scenario with the on tensors.  Common random numbers couple it to the baseline.
+ * Products, integers only: active_count [K][B][M][H] (uint32), the draws of chain b in which m is under the measure on day s,
+ * and active_by_day [K][cap][B][H] (int32), the locations under the measure by draw position since the forecast reset.
+ * Launches: per batch one begin launch, per day the contraction and one day launch (as for a targeted set), and per batch
+ * and scenario one fold of the rule's record (two 64-bit words per row and column).  Out of scope: rules on anything but
+ * the location's own I->R counts, pooling over ranks.
+ * ------------------------------------------------------------------------ */
+#define SEIR_TRIGGER_MAX_WINDOW 28
+/* seir_sampler_scenarios_set_local with a rule: log_shift, commute (the off pair) and log_shift_on, commute_on (the on pair)
+ * [K][M][H]; on, off [K][M]; params [K][4] = window, from_day, min_days, review_every.  The same place, K == 0 || cap == 0,
+ * stores, memory policy (the new tensors, planes and outputs are part of the sum held against half of the free memory),
+ * snapshot / restore (active_count travels with the scenarios' accumulators) and what a refusal leaves as the other two
+ * entry points; a refused value is named by its indices.  It replaces what any entry point set before, and they replace it.
+ * The three reads of a scenario set and the scenarios' region totals work unchanged on a triggered set. */
+int seir_sampler_scenarios_set_triggered(seir_sampler *s, int32_t K, const double *log_shift, const double *commute,
+                                         const double *log_shift_on, const double *commute_on, const int32_t *on,
+                                         const int32_t *off, const int32_t *params, int64_t cap);
+/* Blocking reads: active_count [K][B][M][H]; active_by_day [K][count][B][H] of draw positions [first, first + count).
+ * SEIR_ERR_STATE while no scenarios are set or the set in force is not a triggered one. */
+int seir_sampler_read_scenario_triggers(seir_sampler *s, uint32_t *active_count);
+int seir_sampler_read_scenario_trigger_draws(seir_sampler *s, int64_t first, int64_t count, int32_t *active_by_day);
+/* The fold of the rule's record alone, on host arrays, blocking.  masks [n][B][M][2] (uint64): bit s of the 128 is set iff
+ * the location is under the measure on day s in that draw; bits at days >= H are ignored.  B, M and H are the call's own.
+ * folded: the draws per chain that earlier calls have folded into active_count [B][M][H]; with folded == 0 it is an output
+ * only.  active_by_day [n][B][H] is an output.  SEIR_ERR_INVALID for a null pointer, n, B, M < 1, H outside
+ * [1, SEIR_FORECAST_MAX_H], B above 65535, folded + n above 2^32 - 1, or buffers above half of the device's free memory. */
+int seir_trigger_counts(seir_ctx *ctx, const uint64_t *masks, int64_t n, int32_t B, int32_t M, int32_t H, uint64_t folded,
+                        uint32_t *active_count, int32_t *active_by_day);
 
 /* ------------------------------------------------------------------------
  * Scoring the forecast against later data.

@@ -16,8 +16,15 @@ interleaved, medians of --reps: the forecast call with K = 1 and K = 4 set globa
 the scenarios on (the table is in force in all three, so the forecast's own group sums are in every figure).  The integers
 of the global and the local route are compared before anything is recorded.
 
+With --trigger: what a rule costs against the targeted set, in ONE call, interleaved, medians of --reps, K = 1 and K = 4: the
+forecast call with the targeted set (tensors that vary over the locations), the same numbers through
+`seir_sampler_scenarios_set_triggered` with a rule that never fires, a rule that fires in roughly half of the (draw, location)
+cells (a 7-day window against the median over the draws of the row's recorded window sum; then: transmission x 0.7), and the
+two reads of the record.  The integers of the never-firing set are compared with the targeted set's before anything is recorded.
+
     python tools/scenario_bench.py [--out profiles/r29_scenarios.json]
-    python tools/scenario_bench.py --local [--out profiles/r32_scenarios_local.json]"""
+    python tools/scenario_bench.py --local [--out profiles/r32_scenarios_local.json]
+    python tools/scenario_bench.py --trigger [--out profiles/r36_scenario_triggers.json]"""
 import argparse
 import json
 import os
@@ -38,10 +45,12 @@ def main():
     ap.add_argument("--horizon", type=int, default=56)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--local", action="store_true", help="time the local entry point and the region totals against the global set")
+    ap.add_argument("--trigger", action="store_true", help="time a triggered set against the targeted set with the same numbers")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "r32_scenarios_local.json" if a.local else "r29_scenarios.json")
+        a.out = os.path.join(ROOT, "profiles", "r36_scenario_triggers.json" if a.trigger else
+                             "r32_scenarios_local.json" if a.local else "r29_scenarios.json")
     import __graft_entry__ as entry
     entry.build()
     import torch
@@ -73,6 +82,9 @@ def main():
             model.sync()
             if a.local:
                 local_against_global(a, res, model, s, sets, cov, W, wd)
+                return write(a, res)
+            if a.trigger:
+                triggered_against_targeted(a, res, model, s, cov, W, wd)
                 return write(a, res)
 
             def call(K, timed):
@@ -192,6 +204,66 @@ def local_against_global(a, res, model, s, sets, cov, W, wd):
     res["local_minus_global_ms"] = {f"K={K}": med["local", K] - med["global", K] for K in (1, 4)}
     res["global_spread_ms"] = {f"K={K}": float(max(times["global", K]) - min(times["global", K])) for K in (1, 4)}
     res["region_totals_ms"] = {f"K={K}": med["local_groups", K] - med["local", K] for K in (1, 4)}
+    print("forecast call, ms (median of %d): " % a.reps + ", ".join(f"{kind} K={K}: {med[kind, K]:.2f}" for kind, K in variants),
+          file=sys.stderr, flush=True)
+
+
+def triggered_against_targeted(a, res, model, s, cov, W, wd):
+    """--trigger: the forecast call with K = 1 and K = 4 targeted scenarios, the same through the triggered entry with a rule that
+    never fires, with a rule that fires in about half of the cells, and the two reads; a round holds every variant once."""
+    M, B, n, Hn, w = cov.M, a.chains, a.draws, a.horizon, 7
+    rng = np.random.default_rng(36)
+    ls, cm = rng.normal(-0.1, 0.1, size=(4, M, Hn)), rng.uniform(0.5, 1.5, size=(4, M, Hn))
+    ls_on, cm_on = ls + np.log(0.7), cm
+    c0 = s.read_trace(n).events[..., -w:, 2].astype(np.int64).sum(axis=-1)            # [n, B, M]: the window at day 0
+    half = np.median(c0.reshape(n * B, M), axis=0).astype(np.int64)
+    never = np.full(M, 2 ** 31 - 1, np.int64)
+    variants = [(kind, K) for K in (1, 4) for kind in ("targeted", "never", "half")]
+
+    def rule(K, on):
+        return dict(log_shift_on=ls_on[:K], commute_on=cm_on[:K], on=np.tile(on, (K, 1)), off=np.tile(on // 2 if on is half else 0 * on, (K, 1)),
+                    window=np.full(K, w), from_day=np.zeros(K, int), min_days=np.full(K, 3), review_every=np.ones(K, int))
+
+    def call(kind, K, timed):
+        s.reset_forecast(Hn, W, wd, 5)
+        s.set_scenarios(ls[:K], cm[:K], n, **({} if kind == "targeted" else dict(triggers=rule(K, never if kind == "never" else half))))
+        model.sync()
+        if timed:
+            model.timer_start()
+        s.forecast(0, n)
+        return model.timer_stop() if timed else model.sync()
+    ints, share = {}, {}
+    for kind, K in variants:                                                              # untimed: first launches, allocations
+        call(kind, K, False)
+        d, dr = s.scenario_diffs(), s.read_scenario_draws()
+        ints[kind, K] = [d[key] for key in ("ref", "sum", "sumsq", "lt", "eq")] + [dr["by_day"], dr["state_by_day"]]
+        if kind != "targeted":
+            share[kind, K] = float(s.scenario_triggers()["active_count"].mean() / n)
+    for K in (1, 4):
+        if not all(np.array_equal(x, y) for x, y in zip(ints["never", K], ints["targeted", K])) or share["never", K] != 0.0:
+            raise SystemExit(f"never-firing rule, K = {K}: not the targeted set's integers: nothing recorded")
+        if all(np.array_equal(x, y) for x, y in zip(ints["half", K], ints["targeted", K])):
+            raise SystemExit(f"half-firing rule, K = {K}: the targeted set's integers -- the rule did nothing: nothing recorded")
+    times, reads = {v: [] for v in variants}, {K: [] for K in (1, 4)}
+    for _ in range(a.reps):
+        for v in variants:
+            times[v].append(call(*v, True))
+            if v[0] == "half":
+                model.sync()
+                t0 = time.perf_counter()
+                s.scenario_triggers()
+                s.read_scenario_trigger_draws()
+                reads[v[1]].append((time.perf_counter() - t0) * 1e3)
+    med = {v: float(np.median(t)) for v, t in times.items()}
+    res["same_integers"] = True
+    res["share_of_cell_days_under_the_measure"] = {f"{kind},K={K}": v for (kind, K), v in share.items()}
+    res["forecast_call"] = {f"{kind},K={K}": {"ms_median": med[kind, K], "ms_min": float(min(times[kind, K])),
+                                             "ms_max": float(max(times[kind, K])), "ms_all": [float(t) for t in times[kind, K]]}
+                            for kind, K in variants}
+    res["never_minus_targeted_ms"] = {f"K={K}": med["never", K] - med["targeted", K] for K in (1, 4)}
+    res["half_minus_targeted_ms"] = {f"K={K}": med["half", K] - med["targeted", K] for K in (1, 4)}
+    res["targeted_spread_ms"] = {f"K={K}": float(max(times["targeted", K]) - min(times["targeted", K])) for K in (1, 4)}
+    res["two_reads_ms"] = {f"K={K}": {"median": float(np.median(reads[K])), "all": [float(t) for t in reads[K]]} for K in (1, 4)}
     print("forecast call, ms (median of %d): " % a.reps + ", ".join(f"{kind} K={K}: {med[kind, K]:.2f}" for kind, K in variants),
           file=sys.stderr, flush=True)
 
